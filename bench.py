@@ -16,10 +16,14 @@ Every rank holds a replica of the index and its own shard of the read records; t
 `python3 bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (fresh child processes,
 before anything touches the GPU); under torch.distributed.run it reads RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the environment.
 
-Prints ONE JSON line on rank 0.  `roofline`: algorithmic bytes of the algorithm that runs (the lazy search: probe proofs, walk,
-verified restarts), counted by its CPU restatement in oracle/ on a read sample, per launch / device time of the step from HIP
-events on the launch stream; the reference algorithm's bytes are kept beside it under `reference_equivalent`.  `cpu_baseline`:
-the CPU oracle in reference-shaped mode timed on the host (a port: the reference binary cannot be built here).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the line: `value`, `ms_per_step`, the
+configuration, and the device times of the timed steps' parts (`roofline.kernel_ms_parts`, HIP events on the launch stream).
+`--dump-outputs DIR` writes what the last timed step computed (a seeded sample of its pairs) to DIR as .npy files.
+`--full` adds everything else, after the timed steps: the ground-truth check; `roofline`'s algorithmic bytes of the algorithm that
+runs (the lazy search: probe proofs, walk, verified restarts), counted by its CPU restatement in oracle/ on a read sample, per
+device time of the step, with the reference algorithm's bytes beside it under `reference_equivalent`; `cpu_baseline`: the CPU
+oracle in reference-shaped mode timed on the host (a port: the reference binary cannot be built here); the text, comparison and
+end-to-end legs.  Each of those can be switched off again with its --no-* option.
 """
 import argparse
 import hashlib
@@ -77,7 +81,14 @@ def parse_args(argv=None):
                     "below 2^32 nodes, every read searched in every part) -- unitig sets beyond 2^32 nodes on one GPU; 1 GPU, iid workloads; the line's `value` is the set's")
     ap.add_argument("--no-verify", action="store_true", help="with --parts-max-bases: skip the build-time check that no k-mer lies in two parts")
     ap.add_argument("--kernel", type=int, default=-1)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="after the timed steps: the ground-truth check, the CPU baseline with the oracle parity and "
+                    "roofline bytes, the text, comparison and end-to-end legs (each can be switched off again by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write what the last step computed to DIR/*.npy "
+                    "(float64: the pairs of a seeded sample of the reads, their read numbers, the number of k-mers found)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def kernel_source_hash():
@@ -112,6 +123,43 @@ def make_inputs(synth, np, kind, gsize, k):
             dst = int(gsize * (0.2 + 0.035 * i))
             g[dst:dst + L] = c; skip[max(0, dst - k):dst + L] = 1
     return g, synth.unitigs(g, k), skip
+
+
+DUMP_BLOCK, DUMP_MAX_PAIRS, DUMP_SEED = 64, 1 << 21, 20261016   # --dump-outputs: at most 2^21 pairs = 32 MB as float64
+
+
+def dump_sample(np, n_reads, nk_read):
+    """read numbers (in the rank's shard) whose pairs --dump-outputs writes: every read if their pairs fit DUMP_MAX_PAIRS, else
+    blocks of DUMP_BLOCK consecutive reads drawn with a fixed seed -- the same reads whenever the arguments are the same"""
+    max_reads = DUMP_MAX_PAIRS // max(1, nk_read)
+    if n_reads <= max_reads:
+        return np.arange(n_reads, dtype=np.int64)
+    n_blocks = n_reads // DUMP_BLOCK
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_blocks, min(n_blocks, max(1, max_reads // DUMP_BLOCK)), replace=False))
+    return (pick[:, None] * DUMP_BLOCK + np.arange(DUMP_BLOCK)).reshape(-1)
+
+
+def download_reads(np, batches, per, nk_read, sample):
+    """the pairs of the given (ascending) read numbers, read `i` being read i - b * per of batch b = i // per: one download per run of
+    consecutive reads inside a batch"""
+    out, i = [], 0
+    while i < len(sample):
+        r0 = int(sample[i]); bi = r0 // per; j = i + 1
+        while j < len(sample) and sample[j] == sample[j - 1] + 1 and sample[j] // per == bi:
+            j += 1
+        out.append(batches[bi].download_range((r0 - bi * per) * nk_read, (j - i) * nk_read))
+        i = j
+    return np.concatenate(out) if out else np.zeros((0, 2), dtype=np.int32)
+
+
+def write_outputs(dirname, np, sample, pairs, n_found):
+    """--dump-outputs: pairs.npy = the (unitig id, offset) pairs of the sampled reads in read order, (-1, -1) for a k-mer not found;
+    sample_reads.npy = their read numbers; n_found.npy = the k-mers found in the whole step.  float64 holds every id and offset exactly."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "pairs.npy"), np.asarray(pairs, dtype=np.float64))
+    np.save(os.path.join(dirname, "sample_reads.npy"), np.asarray(sample, dtype=np.float64))
+    np.save(os.path.join(dirname, "n_found.npy"), np.array([n_found], dtype=np.float64))
+    log("outputs of the last step written to %s: pairs of %d reads (%d k-mers), %d k-mers found in the step" % (dirname, len(sample), len(pairs), n_found))
 
 
 def spawn_ranks(args):
@@ -317,12 +365,17 @@ def run_rank(args):
     kern_ms = parts["step"]
     n_reads_rank, n_kmers_rank = n_reads, n_kmers
     n_reads, n_kmers_b0 = len(reads), batch.n_kmers   # (everything below the timed region looks at the first batch)
+    nk_read = max(0, read_len - k + 1)
+    if args.dump_outputs and rank == 0:   # (before anything below runs the batches again)
+        sample = dump_sample(np, n_reads_rank, nk_read)
+        write_outputs(args.dump_outputs, np, sample, download_reads(np, batches, per, nk_read, sample),
+                      sum(b.download(want_pairs=False)[1] for b in batches))
 
     # ---- several ranks: what the host side costs when all GPUs of the node are fed at once ("scaling limit is
     #      host-side: input parse and D2H of 8 B/k-mer over PCIe").  Every rank pushes the same number of reads from page-locked host buffers
     #      through fin_search_batch (H2D + step + D2H, pipelined) at the same time; max over ranks; never `value` ----
     pcie_all = None
-    if world > 1 and not args.no_e2e:
+    if world > 1 and args.full and not args.no_e2e:
         ns_p = min(n_reads, 2_000_000)
         subp = reads.subset(0, ns_p)
         nk_p = ns_p * max(0, read_len - k + 1)
@@ -346,7 +399,7 @@ def run_rank(args):
     # ---- the reference's own timed region (search_fmin.hh:46-71) ends with the output TEXT: one more measurement, outside `value`, of
     #      step + text formatting on the device (fin_text.hip), events on the same stream ----
     with_text = None
-    if rank == 0 and read_len >= k and not args.no_text and n_batches == 1:
+    if args.full and rank == 0 and read_len >= k and not args.no_text and n_batches == 1:
         tstream = torch.cuda.current_stream()
         e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
         legs_t = {}
@@ -366,26 +419,26 @@ def run_rank(args):
                          text_from_pairs={"ms_step": legs_t[0]["ms_step"], "ms_text": legs_t[0]["ms_text"], "text_mode": 0})
         # (the last pass ran in mode 0: the batch's pairs are complete for the checks below)
 
-    # ---- checks on the results of the timed launches (rank 0 carries the oracle leg) ----
-    n_check = args.check_reads or (n_reads if world == 1 and n_batches == 1 else min(n_reads, 2_000_000))
-    n_check = min(n_check, n_reads)
-    nk_read = max(0, read_len - k + 1)
-    if n_check == n_reads:
-        pairs, n_pos = batch.download()
-    else:
-        pairs = batch.download_range(0, n_check * nk_read)
-        _, n_pos = batch.download(want_pairs=False)
-    chk = reads if n_check == n_reads else reads.subset(0, n_check)
-    if rank == 0 or kind == "iid":
-        bad, checked, first_bad = synth.check_ground_truth(idx, u, chk, pairs, skip=skip)
-        if bad:
-            raise SystemExit("rank %d: %d of %d error-free k-mers localized wrongly (first bad read %d)" % (rank, bad, checked, first_bad))
-        log("rank %d: ground truth ok on %d error-free k-mers of the first %d reads; %d of %d k-mers found (first batch)" % (rank, checked, n_check, n_pos, n_kmers_b0))
-    else:
-        # (the duplicated / repeat-rich generators' first-occurrence maps live on rank 0 only -- the other ranks' unitigs come from
-        #  /dev/shm without them, and the plain check would call the duplicated k-mers wrong: rank 0 checks its whole shard)
-        checked = 0
-        log("rank %d: %d of %d k-mers found (ground truth of the '%s' generator is checked on rank 0)" % (rank, n_pos, n_kmers_b0, kind))
+    # ---- --full: checks on the results of the timed launches (rank 0 carries the oracle leg) ----
+    checked = 0
+    if args.full:
+        n_check = args.check_reads or (n_reads if world == 1 and n_batches == 1 else min(n_reads, 2_000_000))
+        n_check = min(n_check, n_reads)
+        if n_check == n_reads:
+            pairs, n_pos = batch.download()
+        else:
+            pairs = batch.download_range(0, n_check * nk_read)
+            _, n_pos = batch.download(want_pairs=False)
+        chk = reads if n_check == n_reads else reads.subset(0, n_check)
+        if rank == 0 or kind == "iid":
+            bad, checked, first_bad = synth.check_ground_truth(idx, u, chk, pairs, skip=skip)
+            if bad:
+                raise SystemExit("rank %d: %d of %d error-free k-mers localized wrongly (first bad read %d)" % (rank, bad, checked, first_bad))
+            log("rank %d: ground truth ok on %d error-free k-mers of the first %d reads; %d of %d k-mers found (first batch)" % (rank, checked, n_check, n_pos, n_kmers_b0))
+        else:
+            # (the duplicated / repeat-rich generators' first-occurrence maps live on rank 0 only -- the other ranks' unitigs come from
+            #  /dev/shm without them, and the plain check would call the duplicated k-mers wrong: rank 0 checks its whole shard)
+            log("rank %d: %d of %d k-mers found (ground truth of the '%s' generator is checked on rank 0)" % (rank, n_pos, n_kmers_b0, kind))
 
     out = None
     if rank == 0:
@@ -425,7 +478,7 @@ def run_rank(args):
             pc = batch.pipeline_counts(48)
             roof["pipeline_queue_slots"] = {"kernel3_list": pc[2], "stream_rounds": pc[6:6 + 4 * 9:4], "walk_rounds": pc[7:7 + 4 * 8:4]}
             roof["reads_finished_by_the_fast_path"] = pc[4 * 8 + 9]; roof["deferred_strands_searched"] = pc[4 * 8 + 8]
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             from oracle.oracle import Counters, LazyCounters, OracleIndex
             ns = min(args.cpu_sample, n_reads)
             t2 = time.time()
@@ -528,7 +581,7 @@ def run_rank(args):
         out["roofline"] = roof
         if pcie_all:
             out["end_to_end_all_ranks"] = pcie_all
-        if not args.no_e2e and world == 1:
+        if args.full and not args.no_e2e and world == 1:
             try:
                 out["end_to_end"] = end_to_end(fa, idx, reads, k, read_len, min(n_reads, 4_000_000), local_rank)
             except Exception as e:
@@ -567,11 +620,17 @@ def run_partitioned(args, fa, synth, np, torch, wname, gsize, k, read_len, n_rea
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
     ms_dev, _ = b.step_time_ms(skip_first=args.warmup)
-    pairs, n_pos = b.download()
-    bad, checked, first_bad = synth.check_ground_truth(pidx, u, rd, pairs)
-    if bad:
-        raise SystemExit("%d of %d error-free k-mers localized wrongly by the partitioned index (first bad read %d)" % (bad, checked, first_bad))
-    log("ground truth ok on %d error-free k-mers of %d reads; %d of %d k-mers found" % (checked, n_reads, n_pos, b.n_kmers))
+    pairs, n_pos = b.download(want_pairs=bool(args.full or args.dump_outputs))
+    if args.dump_outputs:
+        nk_read = max(0, read_len - k + 1)
+        sample = dump_sample(np, n_reads, nk_read)
+        write_outputs(args.dump_outputs, np, sample, pairs.reshape(n_reads, nk_read, 2)[sample].reshape(-1, 2), n_pos)
+    checked = 0
+    if args.full:
+        bad, checked, first_bad = synth.check_ground_truth(pidx, u, rd, pairs)
+        if bad:
+            raise SystemExit("%d of %d error-free k-mers localized wrongly by the partitioned index (first bad read %d)" % (bad, checked, first_bad))
+        log("ground truth ok on %d error-free k-mers of %d reads; %d of %d k-mers found" % (checked, n_reads, n_pos, b.n_kmers))
     value = b.n_kmers * args.steps / elapsed
     print(json.dumps({
         "metric": "localized k-mers/s (k=%d)" % k, "value": value, "unit": "k-mers/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,

@@ -124,7 +124,7 @@ def test_bench_gpus_2_rehearsal_on_one_gpu():
     """The real bench with two ranks sharing GPU 0 (rehearsal switches, gloo for the barrier): n_gpus == 2, every rank's shard
     passes the ground-truth check inside bench.py, and the aggregate counts both ranks' k-mers."""
     out = _bench({"FINITO_BENCH_BACKEND": "gloo", "FINITO_BENCH_DEVICE": "0"}, "--gpus", "2", "--steps", "2", "--warmup", "1",
-                 "--genome", "3000000", "--reads", "30000", "--no-cpu", "--no-e2e")
+                 "--genome", "3000000", "--reads", "30000", "--full", "--no-cpu", "--no-e2e")
     # configs[3] is a STRONG-scaling statement: one read set, rank r takes records [total r / N, total (r+1) / N)
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert out["config"]["reads_total"] == 30000 and out["config"]["reads_per_gpu"] == 15000 and out["config"]["kmers_per_gpu_per_step"] == 15000 * 120
@@ -138,7 +138,7 @@ def test_bench_strong_mode_on_one_gpu_in_several_batches():
     """`--workload chr1x8 --gpus 1`: the N = 1 point of the strong-scaling mode -- the whole read set on one GPU, in as many device batches as
     the per-batch limit asks for (forced small here); the same records whichever way the set is cut, so the first batch's ground truth holds."""
     out = _bench({}, "--workload", "chr1x8", "--gpus", "1", "--steps", "2", "--warmup", "1", "--genome", "3000000", "--reads", "50000",
-                 "--batch-reads", "20000", "--no-cpu", "--no-e2e")
+                 "--batch-reads", "20000", "--full", "--no-cpu", "--no-e2e")
     assert out["n_gpus"] == 1 and out["scaling"] == "strong" and out["config"]["batches_per_gpu"] == 3
     assert out["config"]["reads_total"] == 50000 and out["config"]["kmers_per_step"] == 50000 * 120 == out["config"]["kmers_per_gpu_per_step"]
     assert abs(out["value"] - 50000 * 120 * 2 / (out["ms_per_step"] * 2e-3)) / out["value"] < 1e-6

@@ -4,7 +4,7 @@ TAG=${1:-kt}; shift
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/kt_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu --no-e2e "$@" > $OUT/trace.json 2> $OUT/trace.log || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 3 --warmup 1 --full --no-cpu --no-e2e "$@" > $OUT/trace.json 2> $OUT/trace.log || exit 1
 F=$(find $OUT/trace -name "*kernel_stats.csv" | head -1)
 cp $F $OUT/kernel_stats.csv
 python3 - $F <<'PY'

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd $ROOT
 OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 if [ "$PART" != "rest" ]; then
 for W in chr1 ecoli k63 chr1_repeats chr1_dups k63_repeats k127; do
-  python bench.py --workload $W > $OUT/bench_$W.json 2> $OUT/bench_$W.err || { echo "bench $W failed"; tail -5 $OUT/bench_$W.err; exit 1; }
+  python bench.py --workload $W --full > $OUT/bench_$W.json 2> $OUT/bench_$W.err || { echo "bench $W failed"; tail -5 $OUT/bench_$W.err; exit 1; }
   python - $OUT/bench_$W.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d["roofline"]
@@ -17,12 +17,12 @@ print(d["config"]["workload"].split(" = ")[0], "%.4g k-mers/s" % d["value"], "%.
 PY
 done
 # round 5: the strong-scaling mode's N = 1 point (configs[3]: ONE set of 100 M reads, here in four device batches on one GPU) and indexes beyond 2^30 bases (1.2 Gbp; 3 Gbp = a human genome; 4.1 Gbp = 96 % of the 2^32-node limit)
-python bench.py --workload chr1x8 --gpus 1 --steps 2 --warmup 1 --no-cpu --no-e2e --no-legs > $OUT/bench_chr1x8_n1.json 2> $OUT/bench_chr1x8_n1.err || { echo "bench chr1x8 (N=1) failed"; tail -5 $OUT/bench_chr1x8_n1.err; }
-python bench.py --workload chr1 --genome 1200000000 --steps 3 --warmup 1 --no-cpu --no-e2e --no-legs > $OUT/bench_1200Mbp.json 2> $OUT/bench_1200Mbp.err || { echo "bench 1.2 Gbp failed"; tail -5 $OUT/bench_1200Mbp.err; }
-python bench.py --workload chr1 --genome 3000000000 --steps 3 --warmup 1 --no-cpu --no-e2e --no-legs --no-text > $OUT/bench_3000Mbp.json 2> $OUT/bench_3000Mbp.err || { echo "bench 3 Gbp failed"; tail -5 $OUT/bench_3000Mbp.err; }
-python bench.py --workload chr1 --genome 4100000000 --steps 3 --warmup 1 --no-cpu --no-e2e --no-legs --no-text > $OUT/bench_4100Mbp.json 2> $OUT/bench_4100Mbp.err || { echo "bench 4.1 Gbp failed"; tail -5 $OUT/bench_4100Mbp.err; }
+python bench.py --workload chr1x8 --gpus 1 --steps 2 --warmup 1 --full --no-cpu --no-e2e --no-legs > $OUT/bench_chr1x8_n1.json 2> $OUT/bench_chr1x8_n1.err || { echo "bench chr1x8 (N=1) failed"; tail -5 $OUT/bench_chr1x8_n1.err; }
+python bench.py --workload chr1 --genome 1200000000 --steps 3 --warmup 1 --full --no-cpu --no-e2e --no-legs > $OUT/bench_1200Mbp.json 2> $OUT/bench_1200Mbp.err || { echo "bench 1.2 Gbp failed"; tail -5 $OUT/bench_1200Mbp.err; }
+python bench.py --workload chr1 --genome 3000000000 --steps 3 --warmup 1 --full --no-cpu --no-e2e --no-legs --no-text > $OUT/bench_3000Mbp.json 2> $OUT/bench_3000Mbp.err || { echo "bench 3 Gbp failed"; tail -5 $OUT/bench_3000Mbp.err; }
+python bench.py --workload chr1 --genome 4100000000 --steps 3 --warmup 1 --full --no-cpu --no-e2e --no-legs --no-text > $OUT/bench_4100Mbp.json 2> $OUT/bench_4100Mbp.err || { echo "bench 4.1 Gbp failed"; tail -5 $OUT/bench_4100Mbp.err; }
 # beyond 2^32 nodes: 6.2 Gbp of unitigs as a partitioned index of two parts (k = 63: an iid genome of that size repeats 31-mers by chance and is refused)
-python bench.py --workload k63 --genome 6000000000 --parts-max-bases 3200000000 --steps 3 --warmup 1 > $OUT/bench_pindex_k63_6Gbp.json 2> $OUT/bench_pindex_k63_6Gbp.err || { echo "bench partitioned 6 Gbp failed"; tail -5 $OUT/bench_pindex_k63_6Gbp.err; }
+python bench.py --workload k63 --genome 6000000000 --parts-max-bases 3200000000 --steps 3 --warmup 1 --full > $OUT/bench_pindex_k63_6Gbp.json 2> $OUT/bench_pindex_k63_6Gbp.err || { echo "bench partitioned 6 Gbp failed"; tail -5 $OUT/bench_pindex_k63_6Gbp.err; }
 grep -h "partitioned index built\|ground truth" $OUT/bench_pindex_k63_6Gbp.err
 for F in bench_chr1x8_n1 bench_1200Mbp bench_3000Mbp bench_4100Mbp; do python - $OUT/$F.json <<'PY'
 import json, sys
