@@ -308,6 +308,17 @@ class Batch:
         self.L.fin_batch_run_info(self.h, out)
         return {"kernel": int(out[0]), "no_prefill": bool(out[1]), "deferred": bool(out[2]), "fast_path": bool(out[3])}
 
+    def debug_ingest(self, n_chunks=0):
+        """the most recent run's ingest (fin_batch_debug_ingest): (fused, its first n_chunks packed chunks as uint32 words [n, 4], the pre-pass verdicts [n_reads, 2])"""
+        fused = C.c_uint32(0)
+        ch = np.zeros((n_chunks, 4), dtype=np.uint32)
+        pv = np.zeros((self.n_reads, 2), dtype=np.uint32)
+        rc = self.L.fin_batch_debug_ingest(self.h, C.byref(fused), ch.ctypes.data_as(C.c_void_p), C.c_uint64(n_chunks), pv.ctypes.data_as(C.c_void_p),
+                                           C.c_uint64(2 * self.n_reads))
+        if rc != 0:
+            raise FinitoError(rc, "fin_batch_debug_ingest")
+        return bool(fused.value), ch, pv
+
     def kernel_time_ms(self):
         ms, n = C.c_double(0), C.c_uint64(0)
         self.L.fin_batch_kernel_time(self.h, C.byref(ms), C.byref(n))

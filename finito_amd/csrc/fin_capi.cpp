@@ -93,7 +93,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -121,6 +121,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"debug_ovf_cap", 0, 0, 1ll << 31},            // tests: capacity of the overflow list as the kernels see it (0: what the batch allocated)
     {"debug_pp_seg", 0, 0, 1024},                  // tests: reads per block of the pair pre-pass (0: by batch size; else a multiple of 256 up to 1024)
     {"lean_walk", 1, 0, 1},                        // kernel 4, lean tables: the walk kernel's lean instantiations (no prefix-table states: fewer registers); k <= 31: two k-mer-table look-ups per epoch in a run of absent k-mers (round 5)
+    {"fused_ingest", 1, 0, 1},                     // kernel 4 with the pre-pass's fast path: no pack kernel -- the fast pre-pass packs the ASCII reads itself and writes the chunks of the reads it does not finish (batches whose reads are all at most FIN_FAST_CHUNKS * 32 bases long); 0 = the pack kernel first (round 5)
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -691,6 +692,8 @@ struct fin_batch {
     struct RunEvents { hipEvent_t e[5]; };
     std::vector<RunEvents> runs;
     uint64_t n_chunks = 0;
+    uint64_t max_read_len = 0;   // (the fused ingest takes batches of short reads only: one lane packs a read)
+    bool last_fused = false;     // the most recent run's ingest was the fast pre-pass's (no pack kernel)
     int last_strands = FIN_MERGED; uint32_t last_kernel = 0, last_no_prefill = 0, last_ovf_cap = 0xFFFFFFFFu;
     int ovf_state = 0; uint32_t last_ovf = 0;   // the most recent run's overflow list: 0 not looked at yet, 1 within its capacity, 2 overran (results withheld)
     size_t cap_pass = 0, cap_bases = 0, cap_desc = 0, cap_desc2 = 0, cap_offs = 0, cap_out_offs = 0, cap_out = 0, cap_ovf_list = 0, cap_packed = 0;
@@ -737,7 +740,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     std::vector<uint64_t>& offs = b->h_offs; std::vector<uint64_t>& out_offs = b->h_out_offs;
     std::vector<FinReadDesc>& desc = b->h_desc; std::vector<FinReadDesc>& desc2 = b->h_desc2;
     offs.resize(n_reads + 1); out_offs.resize(n_reads + 1); desc.resize(n_reads + 1); desc2.resize(n_reads + 1);
-    uint64_t n_chunks = 0;
+    uint64_t n_chunks = 0, max_len = 0;
     out_offs[0] = 0;
     for (uint64_t r = 0; r <= n_reads; r++) offs[r] = offsets[r] - base0;
     for (uint64_t r = 0; r < n_reads; r++) {
@@ -747,6 +750,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
         desc[r] = FinReadDesc{offs[r], (uint32_t)len, (uint32_t)out_offs[r]};
         desc2[r] = FinReadDesc{n_chunks, (uint32_t)len, (uint32_t)out_offs[r]};   // off = first packed chunk of the read
         n_chunks += 2 * ((len + 31) / 32);
+        max_len = std::max<uint64_t>(max_len, len);
     }
     desc[n_reads] = FinReadDesc{offs[n_reads], 0, (uint32_t)out_offs[n_reads]};
     desc2[n_reads] = FinReadDesc{n_chunks, 0, (uint32_t)out_offs[n_reads]};
@@ -830,7 +834,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     if ((e = hipMemcpyAsync(b->d_desc2, desc2.data(), rd * sizeof(FinReadDesc), hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e, "hipMemcpy(descriptors)");
     // (the ASCII reads are what is resident: packing them to 2-bit chunks of both strands -- the reference's get_rc and base
     //  decoding, inside its timed region, search_fmin.hh:46-71 -- is the first kernel of every step, see fin_batch_run)
-    b->n_chunks = n_chunks;
+    b->n_chunks = n_chunks; b->max_read_len = max_len;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "upload");
     b->ran = false; b->last_stream = nullptr;
     b->rounds_hint = 0; b->ctr_pending = false;   // (new reads: nothing is known about the rounds they need)
@@ -942,7 +946,13 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
         HIPCHK(hipEventRecord(b->ev_join, b->side_stream));
         out_ready = b->ev_join;
     }
-    if (kern != 0)
+    // the fused ingest: kernel 4's pair pre-pass runs a fast kernel (merged strands, deferral, its fast path writing the pairs) and every read is
+    // short enough for one lane to pack it -- then that kernel reads the ASCII itself and writes the chunks of the reads it does not finish, the
+    // only ones any later kernel reads (the chunks of a FIN_PASS_DONE read are undefined; every run ingests its reads again)
+    const bool fused = kern == 4 && b->q_slots && optv(b->idx, O_fused_ingest) && strands == FIN_MERGED && b->dev.defer_ok && no_prefill && b->dev.fast_path &&
+                       fin_pair_prepass_fuses(&b->dev) && b->max_read_len <= 32u * FIN_FAST_CHUNKS;
+    b->last_fused = fused;
+    if (kern != 0 && !fused)
         rc = fin_launch_pack_reads(b->d_bases, (const uint64_t*)b->d_offs, (const FinReadDesc*)b->d_desc2, b->d_packed, (uint32_t)b->n_reads, b->n_chunks, st);
     if (rc != 0) { set_err(err, errlen, std::string("pack kernel launch failed: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
     if (kern == 0)
@@ -960,7 +970,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
                                   (const uint64_t*)b->d_out_offs, b->d_out, b->n_kmers, (uint32_t)b->n_reads, strands, lds_limit,
                                   b->d_ovf_list, b->d_ovf_count, b->d_ovf_scratch, b->ovf_blocks, (uint32_t*)b->d_pass, (uint32_t*)b->d_seed, b->d_ws, b->q_slots, b->d_ctr,
                                   b->grid_blocks_probe, b->grid_blocks_stream, b->grid_blocks_walk, b->grid_blocks3, st, ev.e[1], ev.e[3], ev.e[2], out_ready, no_prefill,
-                                  b->rounds_hint ? b->rounds_hint : fin_v4_max_rounds());
+                                  b->rounds_hint ? b->rounds_hint : fin_v4_max_rounds(), fused ? 1 : 0);
     } else if (kern == 3 || kern == 4)   // (4 without queues: selected after this batch was loaded, or too many reads for the 29 bits a read number has in an item)
         rc = fin_launch_search_v3(&b->dev, (const uint8_t*)b->d_bases, b->d_packed, (const FinReadDesc*)b->d_desc2, (const uint64_t*)b->d_offs,
                                   (const uint64_t*)b->d_out_offs, b->d_out, b->n_kmers, (uint32_t)b->n_reads, strands,
@@ -1289,6 +1299,19 @@ int fin_batch_pipeline_counts(fin_batch* b, uint32_t* out, uint32_t n_words) {
 // what the most recent fin_batch_run decided (the per-run decision, not a guess from the replica): out[0] the kernel that ran
 // (after the k > 128 rule), [1] 1 = nothing prefilled the output (the pipeline wrote every slot once), [2] 1 = second strands were deferred,
 // [3] 1 = the pre-pass's fast path was on
+// diagnostic (tests of the fused ingest): the most recent run's packed chunks (n_chunks of 16 bytes, may be NULL) and pre-pass verdicts
+// (2 * n_reads words, may be NULL); *fused = 1 when that run's ingest was the fast pre-pass's.  Synchronises the run's stream.
+int fin_batch_debug_ingest(const fin_batch* b, uint32_t* fused, void* chunks, uint64_t n_chunks, uint32_t* pass, uint64_t n_pass_words) {
+    if (!b || !fused) return FIN_EINVAL;
+    *fused = b->ran && b->last_fused ? 1u : 0u;
+    if (!b->ran) return FIN_OK;
+    if (n_chunks > b->n_chunks || n_pass_words > 2 * b->n_reads) return FIN_EINVAL;
+    if (hipSetDevice(b->device) != hipSuccess || hipStreamSynchronize(b->last_stream) != hipSuccess) return FIN_ENODEV;
+    if (chunks && n_chunks && hipMemcpy(chunks, b->d_packed, n_chunks * 16, hipMemcpyDeviceToHost) != hipSuccess) return FIN_ENODEV;
+    if (pass && n_pass_words && hipMemcpy(pass, b->d_pass, n_pass_words * 4, hipMemcpyDeviceToHost) != hipSuccess) return FIN_ENODEV;
+    return FIN_OK;
+}
+
 int fin_batch_run_info(const fin_batch* b, uint32_t out[4]) {
     if (!b || !out) return FIN_EINVAL;
     out[0] = b->last_kernel; out[1] = b->last_no_prefill; out[2] = b->ran ? b->dev.defer_ok : 0u; out[3] = (b->ran && b->dev.defer_ok && b->last_no_prefill) ? b->dev.fast_path : 0u;

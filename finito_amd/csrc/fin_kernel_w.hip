@@ -1125,7 +1125,8 @@ extern "C" int fin_launch_search_v4(const FinDevIndex* ix, const uint8_t* bases,
                                     int strands, uint32_t lds_deque_limit, uint32_t* ovf_list, uint32_t* ovf_count,
                                     uint64_t* ovf_scratch, uint32_t ovf_blocks, uint32_t* pass, uint32_t* seed, void* ws, uint64_t q_slots, uint32_t* ctr,
                                     uint32_t grid_probe, uint32_t grid_stream, uint32_t grid_walk, uint32_t grid_v3,
-                                    hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev_mid, hipEvent_t out_ready, int no_prefill, uint32_t rounds) {
+                                    hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev_mid, hipEvent_t out_ready, int no_prefill, uint32_t rounds,
+                                    int fused_ingest) {
     if (n_reads == 0) return 0;
     // no_prefill (the caller checked fin_v4_writes_gaps): no (-1,-1) pass over the output -- every first item goes to the walk kernel,
     // whose lanes write the absent slots of their strands with the pairs, and the route kernel fills the reads nobody searches
@@ -1156,7 +1157,8 @@ extern "C" int fin_launch_search_v4(const FinDevIndex* ix, const uint8_t* bases,
     uint32_t* const list = (uint32_t*)(aq + q_slots);
     if (!ix->pos && !(ix->kt3 && ix->fbf)) seed = nullptr;
     // (the fast path of the pair pre-pass writes the reads it finishes itself -- only when nothing prefills the output behind it)
-    int rc = fin_launch_probe_stage(ix, packed, desc, n_reads, strands, pass, seed, wc_probe, grid_probe, (no_prefill && ix->fast_path) ? out : nullptr, ctr + 4 * FIN_V4_ROUNDS + 9, stream);
+    int rc = fin_launch_probe_stage(ix, packed, desc, n_reads, strands, pass, seed, wc_probe, grid_probe, (no_prefill && ix->fast_path) ? out : nullptr, ctr + 4 * FIN_V4_ROUNDS + 9,
+                                    fused_ingest ? bases : nullptr, fused_ingest ? offs : nullptr, stream);
     if (rc) return rc;
     if (ev_mid) (void)hipEventRecord(ev_mid, stream);
     {

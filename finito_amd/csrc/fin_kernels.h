@@ -5,6 +5,8 @@
 
 #include "fin_format.h"
 
+#define FIN_FAST_CHUNKS 8   // the fast pre-pass keeps a read's chunks of one strand in LDS: reads of up to 256 bases (and the fused ingest needs no longer ones)
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -32,7 +34,8 @@ int fin_v3_blocks_per_cu(void);
 // single-stage launchers used by kernel 4's pipeline (fin_kernel_w.hip)
 int fin_launch_probe_stage(const FinDevIndex* ix, const void* packed, const FinReadDesc* desc, uint32_t n_reads, int strands, uint32_t* pass,
                            uint32_t* seed /* 2 * n_reads + 4 words: the seed node of every verdict, or NULL */, uint32_t* work_counter, uint32_t grid_blocks,
-                           void* fast_out /* the batch's pairs when the fast path may write them (nothing prefills the output), else NULL */, uint32_t* n_fast, hipStream_t stream);
+                           void* fast_out /* the batch's pairs when the fast path may write them (nothing prefills the output), else NULL */, uint32_t* n_fast,
+                           const uint8_t* bases, const uint64_t* offs /* fused ingest (fin_launch_pair_prepass), else NULL */, hipStream_t stream);
 int fin_launch_stream_stage(const FinDevIndex* ix, const void* packed, const FinReadDesc* desc, uint32_t lds_deque_limit, uint32_t* ovf_list,
                             uint32_t* ovf_count, uint32_t* work_counter, const void* items_in, const uint32_t* n_in, void* items_out,
                             uint32_t* n_out, uint32_t grid_blocks, hipStream_t stream);
@@ -42,8 +45,12 @@ int fin_launch_v3_list(const FinDevIndex* ix, const void* packed, const FinReadD
 // the pair pre-pass (fin_prepass.hip): verdicts and seeds of both strands of every read; defer: one of them FIN_PASS_DEFERRED where possible
 // out (may be NULL): the batch's pairs -- with it, a read the FAST PATH finishes (whole read against one unitig's text, gaps proven absent by
 // the canonical string filter) is written here and gets the verdict FIN_PASS_DONE on both strands; n_fast (may be NULL): how many
+// bases, offs (may be NULL): FUSED INGEST -- the fast kernels pack the ASCII reads themselves and write the chunks of every read they do not finish
+// (a read they finish has undefined chunks); only where fin_pair_prepass_fuses() and no read is longer than FIN_FAST_CHUNKS * 32 bases, else an error
 int fin_launch_pair_prepass(const FinDevIndex* ix, const void* packed, const FinReadDesc* desc, uint32_t n_reads, uint32_t* pass, uint32_t* seed,
-                            int defer, uint32_t grid_hint, void* out, uint32_t* n_fast, hipStream_t stream);
+                            int defer, uint32_t grid_hint, void* out, uint32_t* n_fast, const uint8_t* bases, const uint64_t* offs, hipStream_t stream);
+// 1: fin_launch_pair_prepass with out and defer runs a fast kernel on this index, which can take the ingest over
+int fin_pair_prepass_fuses(const FinDevIndex* ix);
 int fin_stream_blocks_per_cu(void);
 void fin_debug_dump_time(void);   // -DFIN_V3_TIME builds: per-segment wave-cycle shares to stderr
 int fin_walk_blocks_per_cu(void);
@@ -60,7 +67,8 @@ int fin_launch_search_v4(const FinDevIndex* ix, const uint8_t* bases, const void
                          hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev_mid,
                          hipEvent_t out_ready /* NULL: the launcher prefills the output itself; else the prefill is done when this event fires */,
                          int no_prefill /* 1 (only if fin_v4_writes_gaps): nobody prefills, the pipeline writes every slot itself */,
-                         uint32_t rounds /* stream / walk rounds to launch, 1 .. fin_v4_max_rounds() */);
+                         uint32_t rounds /* stream / walk rounds to launch, 1 .. fin_v4_max_rounds() */,
+                         int fused_ingest /* 1: no pack kernel, the pair pre-pass's fast kernel ingests `bases` (fin_launch_pair_prepass) */);
 uint32_t fin_v4_max_rounds(void);
 int fin_v4_writes_gaps(const FinDevIndex* ix, const uint32_t* seed);
 int fin_probe_blocks_per_cu(void);

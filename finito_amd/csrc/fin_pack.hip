@@ -14,28 +14,10 @@
 
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_pack.h"
 
 #define FIN_PACK_SPAN 4096u   // at most; a small batch takes shorter spans so that the chip still has waves enough (fin_launch_pack_reads)
 
-namespace {
-// 0x80 in every byte of v that is zero (exact: no borrow crosses a byte)
-__device__ __forceinline__ uint32_t zero_bytes(uint32_t v) { return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u; }
-
-// four ASCII bases (byte j = position j) -> 8 code bits (2 per base) and 4 validity bits
-__device__ __forceinline__ void pack4(uint32_t w, bool comp, uint32_t& codes, uint32_t& valid) {
-    const uint32_t x = w & 0xDFDFDFDFu;                                   // upper case
-    const uint32_t r = (x >> 1) & 0x03030303u;                            // A 0, C 1, T 2, G 3
-    // the one letter a byte with these two bits can be: 'A' + {0, 2, 0x13, 6}[r], byte-wise (0/1 bytes times small constants: no carry)
-    const uint32_t b0 = r & 0x01010101u, b1 = (r >> 1) & 0x01010101u;
-    const uint32_t expect = 0x41414141u + (b0 << 1) + b1 * 0x13u - (b0 & b1) * 0x0Fu;
-    const uint32_t ok = zero_bytes(x ^ expect) >> 7;                      // 1 in every byte that is a base
-    uint32_t y = r ^ b1;                                                  // A 0, C 1, G 2, T 3
-    if (comp) y ^= 0x03030303u;
-    y &= ok * 3u;                                                         // an invalid base has code 0
-    codes = (y * 0x01041040u) >> 24;                                      // byte j's two bits -> bits 2j
-    valid = ((ok * 0x01020408u) >> 24) & 0xFu;                            // byte j's flag -> bit j
-}
-}  // namespace
 
 __global__ __launch_bounds__(FIN_TPB) void fin_pack_reads_kernel(const uint8_t* bases, const uint64_t* offs, const FinReadDesc* desc,
                                                                   uint4* packed, uint32_t n_reads, uint64_t n_chunks, uint32_t span) {
@@ -73,32 +55,8 @@ __global__ __launch_bounds__(FIN_TPB) void fin_pack_reads_kernel(const uint8_t* 
                 const uint32_t nch = (len + 31u) >> 5;
                 const uint32_t w = (uint32_t)(c + lane - first);
                 const bool s = w >= nch;                            // reverse-complement half
-                const uint32_t ci = s ? w - nch : w;
-                const uint32_t p0 = ci * 32u;                       // first position of the chunk in strand coordinates
-                const uint32_t cnt = len - p0 < 32u ? len - p0 : 32u;
-                // forward: bytes o+p0 ..; reverse: window [o+len-p0-32, o+len-p0) read backwards (64 guard bytes around the buffer)
-                const uint8_t* src = s ? bases + o + len - p0 - 32 : bases + o + p0;
-                uint4 va, vb;
-                __builtin_memcpy(&va, src, 16); __builtin_memcpy(&vb, src + 16, 16);
-                const uint32_t wds[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
-                uint64_t codes = 0; uint32_t valid = 0;
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    // strand positions 4q..4q+3: forward = dword q; reverse = dword 7-q with its bytes reversed, complemented
-                    const uint32_t wd = s ? __builtin_bswap32(wds[7 - q]) : wds[q];
-                    uint32_t c8, v4;
-                    pack4(wd, s, c8, v4);
-                    codes |= (uint64_t)c8 << (8 * q);
-                    valid |= v4 << (4 * q);
-                }
-                const uint32_t keep = cnt >= 32u ? 0xFFFFFFFFu : ((1u << cnt) - 1u);
-                valid &= keep;
-                // codes of invalid positions are 0: spread the 32 validity bits to 2 bits each
-                uint64_t m = valid;
-                m = (m | (m << 16)) & 0x0000FFFF0000FFFFull; m = (m | (m << 8)) & 0x00FF00FF00FF00FFull;
-                m = (m | (m << 4)) & 0x0F0F0F0F0F0F0F0Full; m = (m | (m << 2)) & 0x3333333333333333ull;
-                m = (m | (m << 1)) & 0x5555555555555555ull;
-                codes &= m | (m << 1);
+                uint64_t codes; uint32_t valid;
+                fin_pack::make_chunk(bases + o, len, s ? w - nch : w, s, codes, valid);
                 {   // (written once, read by later kernels from HBM anyway: a 1.6 GB stream does not stay in any cache)
                     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
                     const u4 t = {(uint32_t)codes, (uint32_t)(codes >> 32), valid, 0u};

@@ -19,9 +19,11 @@
 // the stepping loop runs with full waves too.
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_pack.h"
 
 #ifndef FIN_V3_PM_ADD
 #define FIN_V3_PM_ADD 4      // (as in fin_kernel_v3.hip: probe length = prefix-table depth + this)
@@ -250,10 +252,11 @@ __device__ __forceinline__ bool kt3_find_h(const FinDevIndex& ix, uint64_t h, ui
 // place item without asking again (W_DESC, fin_kernel_w.hip), so the claim is compared with the text here -- one or two 16-byte windows, and only for the
 // reads the fast path does not finish (its own comparison covers the others).  false: another k-mer's tag -- the strand becomes a probe item, whose look-up
 // meets the claim again and hands the read to kernel 3.
-__device__ __forceinline__ bool pp_claim_holds(const FinDevIndex& ix, const uint4* ch, uint32_t g) {
+template <bool WIDE = true, typename CH>   // WIDE false: k <= 63 (the fused kernels)
+__device__ __forceinline__ bool pp_claim_holds(const FinDevIndex& ix, const CH& ch, uint32_t g) {
     const uint32_t k = ix.k;
     if (g < k - 1u || g >= ix.total_len) return false;
-    if (k >= 64u) {   // a wide key (lean tables above 63, round 5): 32 bases at a time -- the strand's chunk j against the text behind the place
+    if (WIDE && k >= 64u) {   // a wide key (lean tables above 63, round 5): 32 bases at a time -- the strand's chunk j against the text behind the place
         const uint32_t gs0 = g - (k - 1u);
         for (uint32_t j = 0; 32u * j < k; j++) {
             const uint32_t nb = k - 32u * j < 32u ? k - 32u * j : 32u, gp = gs0 + 32u * j, o2 = gp & 63u;
@@ -293,7 +296,8 @@ __device__ __forceinline__ bool look_ktab(const PpConsts& K, const FinDevIndex& 
 }
 
 // ... and the k-mer that ENDS at position t of a strand (its bases lie in one or two chunks)
-__device__ __forceinline__ bool look_ktab_at(const PpConsts& K, const FinDevIndex& ix, const uint4* ch, uint32_t t, uint32_t& g_ans, bool& verified) {
+template <typename CH>
+__device__ __forceinline__ bool look_ktab_at(const PpConsts& K, const FinDevIndex& ix, const CH& ch, uint32_t t, uint32_t& g_ans, bool& verified) {
     const uint32_t p = t - (uint32_t)(K.k - 1), j0 = p >> 5, j1 = t >> 5, o = p & 31u;
     const uint4 a = ch[j0];
     uint4 c;
@@ -311,7 +315,8 @@ __device__ __forceinline__ bool look_ktab_at(const PpConsts& K, const FinDevInde
 }
 
 // 33 <= k <= 63: the k-mer that ends at position t of a strand -- two key words; its bases lie in up to three chunks
-__device__ __forceinline__ bool look_ktab2_at(const FinDevIndex& ix, const uint4* ch, uint32_t t, uint32_t r_len, uint32_t& g_ans, bool& verified) {
+template <typename CH>
+__device__ __forceinline__ bool look_ktab2_at(const FinDevIndex& ix, const CH& ch, uint32_t t, uint32_t r_len, uint32_t& g_ans, bool& verified) {
     const uint32_t k = ix.k, p = t - (k - 1u), j0 = p >> 5, o = p & 31u, jl = (r_len - 1u) >> 5;
     const uint4 a = ch[j0], b = ch[j0 + 1u <= jl ? j0 + 1u : jl], c = ch[j0 + 2u <= jl ? j0 + 2u : jl];
     const uint64_t wa = a.x | ((uint64_t)a.y << 32), wb = b.x | ((uint64_t)b.y << 32), wc = c.x | ((uint64_t)c.y << 32);
@@ -326,7 +331,8 @@ __device__ __forceinline__ bool look_ktab2_at(const FinDevIndex& ix, const uint4
 // 64 <= k <= 255: the k-mer that ends at position t of a strand, its ceil(k / 32) key words folded into the hash as they are made from the strand's chunks (the
 // table holds no k-mer, so none is kept here either: the fast path's comparison of the whole read with the text is what proves the claim).  (The walk kernel
 // folds the same words one epoch each as its chunk cache brings them, fin_kernel_w.hip W_KF0B.)
-__device__ __forceinline__ bool look_ktabN_at(const FinDevIndex& ix, const uint4* ch, uint32_t t, uint32_t r_len, uint32_t& g_ans, bool& verified) {
+template <typename CH>
+__device__ __forceinline__ bool look_ktabN_at(const FinDevIndex& ix, const CH& ch, uint32_t t, uint32_t r_len, uint32_t& g_ans, bool& verified) {
     const uint32_t k = ix.k, p = t - (k - 1u), j0 = p >> 5, o = p & 31u, jl = (r_len - 1u) >> 5, nw = (k + 31u) >> 5;
     uint4 a = ch[j0];
     uint64_t key = 0;
@@ -367,8 +373,39 @@ __device__ unsigned long long g_fin_ppdbg[16];
 #else
 #define PPDBG(i) ((void)0)
 #endif
-#define FIN_FAST_CHUNKS 8      // chunks of strand A kept in LDS for the strings (reads of up to 256 bases)
 struct FastRun { uint32_t ok, u, off0, nE; uint64_t Es, Es2; };   // Es, Es2: the disagreeing positions, 16 bits each, ascending (four in each word)
+
+// The fused ingest (phase 1 of the fast kernels with `bases`): a strand's chunks made from the forward codes that the lane's LDS row holds (`row`,
+// stride FIN_TPB; 0 at a non-ACGT base) -- the reverse strand's chunk j is the reverse complement of the 32 forward bases that end at len - 32 j.
+// `ok`: the strand's positions below it are ACGT (len: every one).  Validity bits say "position < ok", and codes at and behind a position that is
+// not valid are 0: that is bit for bit the pack kernel's chunk wherever the read is ACGT, and else for the strand's bases in front of its first
+// non-ACGT base -- all that phase 1 reads of such a read (its first k-mer; fast_try gives it up); its chunks are packed from its ASCII again.
+struct StrandChunks {
+    const uint64_t* row; uint32_t len, ok; bool rev;
+    __device__ __forceinline__ uint4 operator[](uint32_t j) const {
+        const uint32_t q = len - 32u * j, o = ok - 32u * j;   // (j < ceil(len / 32): q >= 1)
+        const uint32_t cnt = (int)o <= 0 ? 0u : (o < q ? o : q) < 32u ? (o < q ? o : q) : 32u;
+        uint64_t w;
+        if (!rev) w = row[j * FIN_TPB];
+        else {
+            uint64_t x;
+            if (q >= 32u) {
+                const uint32_t p = q - 32u, a = p >> 5, sh = p & 31u;
+                x = row[a * FIN_TPB] >> (2u * sh);
+                if (sh) x |= row[(a + 1u) * FIN_TPB] << (64u - 2u * sh);
+            } else x = row[0] << (64u - 2u * q);     // the q bases at the top: what lies below them turns into codes past cnt, cut off next
+            w = fin_pack::revcomp32(x);
+        }
+        if (cnt < 32u) w &= (1ull << (2u * cnt)) - 1ull;
+        return make_uint4((uint32_t)w, (uint32_t)(w >> 32), cnt < 32u ? (1u << cnt) - 1u : 0xFFFFFFFFu, 0u);
+    }
+};
+// what the lane's LDS row holds for fast_try: a strand read from memory puts its codes there itself; the fused ingest's row holds the forward
+// strand's codes for good (its chunks are written from there after phase 1): a reverse strand A asks the canonical filter at mirrored positions
+__device__ __forceinline__ bool row_holds(const uint4*) { return false; }
+__device__ __forceinline__ bool row_holds(const StrandChunks&) { return true; }
+__device__ __forceinline__ bool row_mirrored(const uint4*) { return false; }
+__device__ __forceinline__ bool row_mirrored(const StrandChunks& c) { return c.rev; }
 
 __device__ __forceinline__ uint64_t pp_revcomp(uint64_t f, uint32_t m, uint64_t mask) {
     uint64_t r = __brevll(f);
@@ -398,8 +435,10 @@ __device__ __forceinline__ bool cbf_known(const CbfAsk& q) {
 // answer for it (verified).  true: res describes every slot of the read.
 // (written for memory-level parallelism: a lane's loads of one stage -- the read's chunks and the text beside them; the strings across one
 //  disagreeing base -- are issued together and used afterwards; nothing in a stage returns early)
-__device__ __forceinline__ bool fast_try(const PpConsts& K, const FinDevIndex& ix, const uint4* ch, uint32_t t_anchor, uint32_t r_len, uint32_t g_ans, uint64_t* lds, FastRun& res) {
+template <typename CH>
+__device__ __forceinline__ bool fast_try(const PpConsts& K, const FinDevIndex& ix, const CH& ch, uint32_t t_anchor, uint32_t r_len, uint32_t g_ans, uint64_t* lds, FastRun& res) {
     const uint32_t k = (uint32_t)K.k, m = ix.cbf_m;
+    const bool put = !row_holds(ch), mir = row_mirrored(ch);   // (a string of strand A at a = its reverse complement at r_len - a - m: the filter is canonical)
     const uint32_t nch = (r_len + 31u) >> 5;
     if (nch > FIN_FAST_CHUNKS || g_ans < t_anchor) { PPDBG(1); return false; }
     const uint32_t gs = g_ans - t_anchor;           // the text position of the read's first base
@@ -434,7 +473,7 @@ __device__ __forceinline__ bool fast_try(const PpConsts& K, const FinDevIndex& i
                 const uint64_t tb = sh ? (w0 >> sh) | (w1 << (64u - sh)) : w0;
                 w0 = w1;
                 const uint64_t rb = c[i].x | ((uint64_t)c[i].y << 32);
-                lds[j * FIN_TPB] = rb;
+                if (put) lds[j * FIN_TPB] = rb;
                 const uint32_t nb = r_len - 32u * j < 32u ? r_len - 32u * j : 32u;
                 const uint32_t vm = nb == 32u ? 0xFFFFFFFFu : (1u << nb) - 1u;
                 bad = bad || (c[i].z & vm) != vm;         // a non-ACGT base
@@ -469,9 +508,9 @@ __device__ __forceinline__ bool fast_try(const PpConsts& K, const FinDevIndex& i
         uint32_t lo = E > k - 1u ? E : k - 1u; if (lo < covered + 1u) lo = covered + 1u;
         const uint32_t hi = E + k - 1u < r_len - 1u ? E + k - 1u : r_len - 1u;
         CbfAsk q0, q1, q2; bool h0 = false, h1 = false, h2 = false;
-        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, lds, a, m, mask, q0); h0 = true; covered = a + k - 1u; lo = covered + 1u; }
-        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, lds, a, m, mask, q1); h1 = true; covered = a + k - 1u; lo = covered + 1u; }
-        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, lds, a, m, mask, q2); h2 = true; covered = a + k - 1u; lo = covered + 1u; }
+        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, lds, mir ? r_len - a - m : a, m, mask, q0); h0 = true; covered = a + k - 1u; lo = covered + 1u; }
+        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, lds, mir ? r_len - a - m : a, m, mask, q1); h1 = true; covered = a + k - 1u; lo = covered + 1u; }
+        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, lds, mir ? r_len - a - m : a, m, mask, q2); h2 = true; covered = a + k - 1u; lo = covered + 1u; }
         // the first k-mer behind this stretch of absent ends is reported where the text has it only if that place is safe
         const uint32_t t = E + k;
         const bool last = e + 1u == nE || E_at(e + 1u) > t;
@@ -525,9 +564,12 @@ __device__ __forceinline__ bool fast_all_absent(const PpConsts& K, const FinDevI
 // KT2 (with FAST): the fast path's looks go to the k-mer table but the PIPELINE's verdicts do not come from them -- k >= 33 (this flow's looks reach
 // any k-mer end through up to three chunks), or round 3's tables (seeds are nodes, which the compact table does not hold): verdicts come from probe
 // steps as before, made afterwards and only for the reads the fast path did not finish (list L); under lean tables 2 (k >= 33) the looks are the verdicts
-template <bool FAST, bool KT2>
+// FUSED (with FAST): phase 1 ingests the reads itself (fin_launch_pair_prepass's `bases`) and writes to packed_out the chunks of every read it does
+// not finish, before the barrier behind it -- the later phases and kernels read them there
+template <bool FAST, bool KT2, bool FUSED = false>
 __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, const uint4* packed, const FinReadDesc* desc, uint32_t n_reads, uint32_t seg,
-                                                      uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast) {
+                                                      uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast,
+                                                      const uint8_t* bases = nullptr, const uint64_t* offs = nullptr, uint4* packed_out = nullptr) {
     // lists of reads (numbers inside the block's segment).  lds_list: from the front, list A -- both first looks failed, the fast path goes on
     // with other k-mers of the read (phase 2) --; from the back, the stepping loop's reads (phase 4).  lds_b: list B, phase 3.
     __shared__ uint16_t lds_list[FIN_PP_SEG_MAX];
@@ -548,7 +590,8 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
     K.fmask = K.F ? (K.F == 16 ? 0xFFFFFFFFu : (1u << (2 * K.F)) - 1u) : 0u;
     // (this flow's looks ARE the pipeline's verdicts and its seeds are places: lean tables.  With round 3's tables seeds are nodes, which the compact k-mer
     //  table does not hold: the KT2 flow -- the table for the fast path, verdicts by probe steps -- or, without the fast path, probe steps alone)
-    const bool look_kt = ix.kt3 != nullptr && K.k <= 32 && K.fbf != nullptr;
+    // (the fused fast kernel runs only where this holds -- fin_launch_pair_prepass: its phase 1 has no probe steps)
+    const bool look_kt = (FUSED && !KT2) || (ix.kt3 != nullptr && K.k <= 32 && K.fbf != nullptr);
     const uint32_t k1 = (uint32_t)(K.k - 1);
     // a strand's slot of pass[] between the two loops: k-1 = its look succeeded (final), NONE = absent (final), FIN_PASS_DEFERRED (final),
     // anything else = the k-mer end its stepping starts at (>= k: a failed look proves end k-1 absent)
@@ -594,8 +637,8 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
         }
     };
     // the fast path's look at the k-mer that ends at position t of a strand: found (hit), its answer g, whether the text there spells it
-    auto flook = [&](const uint4* ch, uint32_t t, uint32_t r_len, uint32_t& g, bool& ver) -> bool {
-        if (K.k >= 64) return look_ktabN_at(ix, ch, t, r_len, g, ver);
+    auto flook = [&](const auto& ch, uint32_t t, uint32_t r_len, uint32_t& g, bool& ver) -> bool {
+        if (!FUSED && K.k >= 64) return look_ktabN_at(ix, ch, t, r_len, g, ver);   // (the fused kernels run at k <= 63 only)
         if (K.k >= 33) return look_ktab2_at(ix, ch, t, r_len, g, ver);
         return t == k1 ? look_ktab(K, ix, ch[0], g, ver) : look_ktab_at(K, ix, ch, t, g, ver);
     };
@@ -625,9 +668,40 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
         FinReadDesc d = {0, 0, 0};
         if (r < r_hi) d = desc[r];
         const uint32_t r_len = d.len, r_nch = (r_len + 31u) >> 5;
-        const uint4* const cf = packed + d.off, *const cv = cf + r_nch;
+        typename std::conditional<FUSED, StrandChunks, const uint4*>::type cf, cv;
+        bool acgt = true;   // (fused ingest)
+        if constexpr (FUSED) {
+            // the fused ingest: the read's forward codes into the lane's LDS row (16-byte loads of its ASCII), and where its first and last
+            // non-ACGT bases lie
+            uint64_t* const row = lds_ck + threadIdx.x;
+            const uint8_t* const rd = bases + (r < r_hi ? offs[r] : 0ull);
+            uint32_t fi = r_len, li = NONE;
+            for (uint32_t j = 0; j < r_nch; j++) {
+                uint64_t c; uint32_t v;
+                fin_pack::make_chunk(rd, r_len, j, false, c, v);
+                row[j * FIN_TPB] = c;
+                const uint32_t cnt = r_len - 32u * j;
+                const uint32_t inv = ~v & (cnt < 32u ? (1u << cnt) - 1u : 0xFFFFFFFFu);
+                if (inv) { if (fi == r_len) fi = 32u * j + (uint32_t)(__ffs((int)inv) - 1); li = 32u * j + 31u - (uint32_t)__clz((int)inv); }
+            }
+            cf = StrandChunks{row, r_len, fi, false}; cv = StrandChunks{row, r_len, li == NONE ? r_len : r_len - 1u - li, true};
+            acgt = li == NONE;
+        } else { cf = packed + d.off; cv = cf + r_nch; }
         uint2 verdict = make_uint2(NONE, NONE), sd = make_uint2(NONE, NONE);
         FastRun fr = {0u, 0u, 0u, 0u, 0ull, 0ull}; bool fr_rev = false, to_a = false;
+        // (fused ingest) a read not finished here: its chunks of both strands, for the later phases and kernels
+        auto spill = [&]() {
+            if constexpr (FUSED) {
+                if (r < r_hi && !fr.ok) {
+                    if (acgt) for (uint32_t j = 0; j < r_nch; j++) { packed_out[d.off + j] = cf[j]; packed_out[d.off + r_nch + j] = cv[j]; }
+                    else for (uint32_t j = 0; j < 2u * r_nch; j++) {   // (a non-ACGT base: from its ASCII, as the pack kernel does)
+                        uint64_t c; uint32_t v;
+                        fin_pack::make_chunk(bases + offs[r], r_len, j < r_nch ? j : j - r_nch, j >= r_nch, c, v);
+                        packed_out[d.off + j] = make_uint4((uint32_t)c, (uint32_t)(c >> 32), v, 0u);
+                    }
+                }
+            }
+        };
         if (KT2) {
             if (r < r_hi) {
                 bool hit = false, settled = false;
@@ -644,12 +718,13 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
                         // strand's seed -- a PLACE; nothing is left for the probe steps of phase L
                         const uint32_t other = (uint32_t)K.k < r_len ? FIN_PASS_DEFERRED : NONE;   // (a strand without a k-mer end behind its first is absent, not deferred)
                         *(uint2*)(pass + 2 * (size_t)r) = f_hit ? make_uint2(k1, FIN_PASS_DEFERRED) : make_uint2(other, k1);
-                        if (seed) *(uint2*)(seed + 2 * (size_t)r) = make_uint2((f_hit && ver_f && pp_claim_holds(ix, cf, g_f)) ? g_f : NONE, (v_hit && ver_v && pp_claim_holds(ix, cv, g_v)) ? g_v : NONE);
+                        if (seed) *(uint2*)(seed + 2 * (size_t)r) = make_uint2((f_hit && ver_f && pp_claim_holds<!FUSED>(ix, cf, g_f)) ? g_f : NONE, (v_hit && ver_v && pp_claim_holds<!FUSED>(ix, cv, g_v)) ? g_v : NONE);
                         settled = true;
                     }
                 }
                 if (!fr.ok && !settled && (hit || !(r_len >= (uint32_t)K.k && defer && r_len < 65536u))) to_l(r);
             }
+            spill();
             write_out(fr, fr_rev, r, d.out_off, r_len);
             continue;
         }
@@ -679,7 +754,7 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
                     to_a = !f_hit && !v_hit;
                     if (to_a) PPDBG(9);
                 }
-            } else {
+            } else if constexpr (!FUSED) {
                 const bool f_hit = probe_step(K, cf, r_len, f_t0, sd.x);
                 if (f_hit && can_defer) v_t0 = FIN_PASS_DEFERRED;
                 else {
@@ -688,8 +763,8 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
                 }
             }
             if (look_kt && !fr.ok) {   // the place seeds this read takes into the pipeline: claims, compared with the text
-                if (sd.x != NONE && !pp_claim_holds(ix, cf, sd.x)) sd.x = NONE;
-                if (sd.y != NONE && !pp_claim_holds(ix, cv, sd.y)) sd.y = NONE;
+                if (sd.x != NONE && !pp_claim_holds<!FUSED>(ix, cf, sd.x)) sd.x = NONE;
+                if (sd.y != NONE && !pp_claim_holds<!FUSED>(ix, cv, sd.y)) sd.y = NONE;
             }
             verdict = fr.ok ? make_uint2(FIN_PASS_DONE, FIN_PASS_DONE) : make_uint2(f_t0, v_t0);
         }
@@ -699,6 +774,7 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
             if (to_a) lds_list[atomicAdd(&lds_na, 1u)] = (uint16_t)(r - r_lo);
             else if (!is_final(verdict.x) || !is_final(verdict.y)) lds_list[FIN_PP_SEG_MAX - 1u - atomicAdd(&lds_n, 1u)] = (uint16_t)(r - r_lo);
         }
+        spill();
         if (FAST) write_out(fr, fr_rev, r, d.out_off, r_len);
     }
     __syncthreads();
@@ -833,25 +909,48 @@ __global__ __launch_bounds__(FIN_TPB) void fin_fast2_prepass_kernel(FinDevIndex 
                                                                     uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast) {
     fin_pair_prepass_body<true, true>(ix, packed, desc, n_reads, seg, pass, seed, defer, out, n_fast);
 }
+// the two fast kernels with the fused ingest: no pack kernel in front of them; they write the chunks of the reads they do not finish
+__global__ __launch_bounds__(FIN_TPB) void fin_fast_prepass_fused_kernel(FinDevIndex ix, uint4* packed, const FinReadDesc* desc, uint32_t n_reads, uint32_t seg,
+                                                                         uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast, const uint8_t* bases, const uint64_t* offs) {
+    fin_pair_prepass_body<true, false, true>(ix, packed, desc, n_reads, seg, pass, seed, defer, out, n_fast, bases, offs, packed);
+}
+__global__ __launch_bounds__(FIN_TPB) void fin_fast2_prepass_fused_kernel(FinDevIndex ix, uint4* packed, const FinReadDesc* desc, uint32_t n_reads, uint32_t seg,
+                                                                          uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast, const uint8_t* bases, const uint64_t* offs) {
+    fin_pair_prepass_body<true, true, true>(ix, packed, desc, n_reads, seg, pass, seed, defer, out, n_fast, bases, offs, packed);
+}
+
+// the fast path: merged searches with a deferred strand on an index with the k-mer table (any k since round 5) and the canonical string filter.  Lean tables at
+// k <= 32: the looks are the verdicts (fin_fast_prepass_kernel, 1); else they serve the fast path alone and probe steps make the verdicts (fin_fast2_..., 2).  0: neither
+static int pp_fast_kernel(const FinDevIndex* ix) {
+    if (ix->kt3 && ix->cbf && ix->cbf_m >= 1 && ix->cbf_m <= ix->k && (ix->k >= 33 || !ix->fbf)) return 2;   // (k > 63: with option fast_path 2)
+    if (ix->kt3 && ix->fbf && ix->cbf && ix->k <= 32 && ix->cbf_m >= 1 && ix->cbf_m <= ix->k) return 1;
+    return 0;
+}
+extern "C" int fin_pair_prepass_fuses(const FinDevIndex* ix) { return pp_fast_kernel(ix) != 0 && ix->k <= 63; }
 
 // reads per block: whole iterations of the block's threads, FIN_PP_SEG_MAX at most; small batches get smaller segments so that the grid
 // still fills the chip
 extern "C" int fin_launch_pair_prepass(const FinDevIndex* ix, const void* packed, const FinReadDesc* desc, uint32_t n_reads, uint32_t* pass, uint32_t* seed,
-                                       int defer, uint32_t grid_hint, void* out, uint32_t* n_fast, hipStream_t stream) {
+                                       int defer, uint32_t grid_hint, void* out, uint32_t* n_fast, const uint8_t* bases, const uint64_t* offs, hipStream_t stream) {
     if (n_reads == 0) return 0;
     uint32_t seg = (n_reads + grid_hint - 1) / (grid_hint ? grid_hint : 1u);
     seg = (seg + FIN_TPB - 1) / FIN_TPB * FIN_TPB;
     if (seg > FIN_PP_SEG_MAX) seg = FIN_PP_SEG_MAX;
     if (n_reads >= 512u * FIN_PP_SEG_MAX) seg = FIN_PP_SEG_MAX;   // (long segments keep the phases' lists full: measured on 1 M and 10 M reads, 1024 beats 768 / 512 / 256)
     if (ix->pp_seg >= FIN_TPB && ix->pp_seg <= FIN_PP_SEG_MAX && ix->pp_seg % FIN_TPB == 0) seg = ix->pp_seg;   // (option "debug_pp_seg": tests reach the longest segments with small batches)
-    // the fast path: merged searches with a deferred strand on an index with the k-mer table (any k since round 5) and the canonical string filter.  Lean tables at
-    // k <= 32: the looks are the verdicts (fin_fast_prepass_kernel); else they serve the fast path alone and probe steps make the verdicts (fin_fast2_...)
-    if (out && defer && ix->kt3 && ix->cbf && ix->cbf_m >= 1 && ix->cbf_m <= ix->k && (ix->k >= 33 || !ix->fbf))
-        hipLaunchKernelGGL(fin_fast2_prepass_kernel, dim3((n_reads + seg - 1) / seg), dim3(FIN_TPB), 0, stream, *ix, (const uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast);
-    else if (out && defer && ix->kt3 && ix->fbf && ix->cbf && ix->k <= 32 && ix->cbf_m >= 1 && ix->cbf_m <= ix->k)
-        hipLaunchKernelGGL(fin_fast_prepass_kernel, dim3((n_reads + seg - 1) / seg), dim3(FIN_TPB), 0, stream, *ix, (const uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast);
+    const int fast = (out && defer) ? pp_fast_kernel(ix) : 0;
+    const dim3 grid((n_reads + seg - 1) / seg);
+    if (bases && (!fast || !offs || ix->k > 63)) return (int)hipErrorInvalidValue;   // (the caller skipped the pack kernel: only a fast kernel ingests)
+    if (bases && fast == 2)
+        hipLaunchKernelGGL(fin_fast2_prepass_fused_kernel, grid, dim3(FIN_TPB), 0, stream, *ix, (uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast, bases, offs);
+    else if (bases)
+        hipLaunchKernelGGL(fin_fast_prepass_fused_kernel, grid, dim3(FIN_TPB), 0, stream, *ix, (uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast, bases, offs);
+    else if (fast == 2)
+        hipLaunchKernelGGL(fin_fast2_prepass_kernel, grid, dim3(FIN_TPB), 0, stream, *ix, (const uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast);
+    else if (fast == 1)
+        hipLaunchKernelGGL(fin_fast_prepass_kernel, grid, dim3(FIN_TPB), 0, stream, *ix, (const uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast);
     else
-        hipLaunchKernelGGL(fin_pair_prepass_kernel, dim3((n_reads + seg - 1) / seg), dim3(FIN_TPB), 0, stream, *ix, (const uint4*)packed, desc, n_reads, seg, pass, seed, defer);
+        hipLaunchKernelGGL(fin_pair_prepass_kernel, grid, dim3(FIN_TPB), 0, stream, *ix, (const uint4*)packed, desc, n_reads, seg, pass, seed, defer);
     return (int)hipGetLastError();
 }
 

@@ -340,6 +340,10 @@ int fin_batch_pipeline_counts(fin_batch* b, uint32_t* out, uint32_t n_words);
  * [2] 1 = second strands were deferred (option "defer_strand" and the replica's tables allowing), [3] 1 = the pre-pass's fast path was on
  * (option "fast_path"; k <= 63 with the k-mer table and the canonical string filter) */
 int fin_batch_run_info(const fin_batch* b, uint32_t out[4]);
+/* Diagnostic: the most recent run's packed 2-bit chunks (16 bytes each, both strands of every read; with the fused ingest -- option "fused_ingest",
+ * the fast pre-pass packs the reads itself -- only the chunks of reads whose verdict is not "finished by the fast path" are defined) and its
+ * pre-pass verdicts (two words per read).  *fused = 1 when that run used the fused ingest.  Either buffer may be NULL. */
+int fin_batch_debug_ingest(const fin_batch* b, uint32_t* fused, void* chunks, uint64_t n_chunks, uint32_t* pass, uint64_t n_pass_words);
 
 /* ---- partitioned indexes (fin_pindex): unitig sets beyond 2^32 nodes (round 5) ----------------------------------------------------------------------
  * The reference counts in int64_t (common.hh:79-93, FinimizerIndex.hh:30-33); one fin_index holds fewer than 2^32 nodes / text bases (FIN_ELIMIT above: a
