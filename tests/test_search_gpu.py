@@ -1393,7 +1393,7 @@ def test_round3_tables_on_request(kernel):
         assert_reads_equal(p, o, reads)
         p.close()
     finally:
-        L.fin_set_option(b"lean_tables", 1)
+        L.fin_set_option(b"lean_tables", 2)   # (the default since round 5)
 
 
 def test_per_handle_options(kernel):

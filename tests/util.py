@@ -49,6 +49,56 @@ def sample_reads(rng, genome, n_reads, read_len, err=0.01, random_frac=0.05):
     return reads
 
 
+# ---- the chunk format of a step, restated without the package ------------------------------------------------------------------------
+# A chunk = 32 bases of one strand as {u64 2-bit codes (A0 C1 G2 T3, base j at bits 2j), u32 validity bits, u32 0}; per read
+# [forward chunks | reverse-complement chunks], ceil(len / 32) of each.  A byte is a base iff b & 0xDF is one of "ACGT" (the reference's
+# c & ~32, common.hh:106); any other byte, and every position past the read, has code 0 and validity bit 0.  The reverse strand's
+# position i is the complement (3 - code) of byte len-1-i, where that byte is a base.
+_REF_CODE = np.zeros(256, dtype=np.uint64)
+_REF_VALID = np.zeros(256, dtype=bool)
+for _b in range(256):
+    if (_b & 0xDF) in b"ACGT":
+        _REF_CODE[_b] = b"ACGT".index(_b & 0xDF)
+        _REF_VALID[_b] = True
+
+
+def ref_chunks(reads):
+    """the packed chunks of a read set as the format states them: uint32 [n_chunks, 4] (lo codes, hi codes, validity, 0)"""
+    codes, valid = [], []
+    for s in reads:
+        a = np.frombuffer(s.encode() if isinstance(s, str) else bytes(s), dtype=np.uint8)
+        n = len(a)
+        width = 32 * ((n + 31) // 32)
+        for strand in (a, a[::-1]):
+            c = np.zeros(width, dtype=np.uint64)
+            v = np.zeros(width, dtype=bool)
+            v[:n] = _REF_VALID[strand]
+            c[:n] = _REF_CODE[strand]
+            if strand is not a:
+                c[:n] = np.where(v[:n], 3 - c[:n], 0)
+            codes.append(c)
+            valid.append(v)
+    if not codes:
+        return np.zeros((0, 4), dtype=np.uint32)
+    c = np.concatenate(codes).reshape(-1, 32)
+    v = np.concatenate(valid).reshape(-1, 32)
+    sh = np.arange(32, dtype=np.uint64)
+    w = (c << (2 * sh)).sum(axis=1, dtype=np.uint64)
+    m = (v.astype(np.uint64) << sh).sum(axis=1, dtype=np.uint64)
+    out = np.zeros((len(w), 4), dtype=np.uint32)
+    out[:, 0] = (w & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    out[:, 1] = (w >> np.uint64(32)).astype(np.uint32)
+    out[:, 2] = m.astype(np.uint32)
+    return out
+
+
+def chunk_offsets(reads):
+    """first chunk of every read, and the total at the end: int64 [n_reads + 1]"""
+    off = np.zeros(len(reads) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([2 * ((len(r) + 31) // 32) for r in reads])
+    return off
+
+
 def unpack_bits(words, n):
     return np.unpackbits(np.ascontiguousarray(words, dtype=np.uint64).view(np.uint8), bitorder="little")[:n]
 
