@@ -149,6 +149,9 @@ struct FinDevIndex {
     uint32_t text_only;
     uint32_t lean_walk;          // host side only (set per run, option "lean_walk"): 1 = under lean tables the walk kernel's lean instantiations (k <= 31: two k-mer-table look-ups per epoch in a run of misses)
     uint32_t pp_seg;             // host side only (set per run, option "debug_pp_seg"; 0: by batch size): reads per block of the pair pre-pass
+    uint32_t pp_max_len;         // host side only (set per run): the batch's longest read -- the fused pre-pass sizes its LDS rows by it
+    uint32_t pp_park;            // host side only (set per run, option "pp_park"): 1 = the fused pre-pass parks list A's reads in LDS
+    uint32_t pp_park_cap;        // host side only (set per run, option "debug_pp_park_cap"; 0xFFFFFFFF: by the LDS budget): most reads a block parks
 };
 // What the fast path knows about a read it finished (fin_prepass.hip: FastRun): strand A (meta bit 8: the reverse strand) lies in unitig u with its
 // first base at offset off0 and disagrees with the text at positions E (meta bits 0..7: how many; 16 bits each, Es then Es2); meta >> 16 = 2: every

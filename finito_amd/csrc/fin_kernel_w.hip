@@ -1152,6 +1152,7 @@ extern "C" int fin_launch_search_v4(const FinDevIndex* ix, const uint8_t* bases,
     //           [6+4r] stream items of round r, [7+4r] anchor items of round r   (stream items of round R land in [6+4R])
     //           [4*FIN_V4_ROUNDS+8] deferred strands the walk kernel's lanes went on with (a statistic)
     //           [4*FIN_V4_ROUNDS+9] reads the pre-pass's fast path finished (a statistic)
+    //           [4*FIN_V4_ROUNDS+10], [+11] (fused ingest) reads the pre-pass parked in LDS, reads of its list A beyond a block's park area (statistics)
     uint32_t* const wc_probe = ctr, *const wc_v3 = ctr + 1, *const n_list = ctr + 2;
     uint4* const sq0 = (uint4*)ws, *const sq1 = sq0 + q_slots, *const aq = sq1 + q_slots;
     uint32_t* const list = (uint32_t*)(aq + q_slots);

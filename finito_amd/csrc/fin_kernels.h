@@ -46,7 +46,9 @@ int fin_launch_v3_list(const FinDevIndex* ix, const void* packed, const FinReadD
 // out (may be NULL): the batch's pairs -- with it, a read the FAST PATH finishes (whole read against one unitig's text, gaps proven absent by
 // the canonical string filter) is written here and gets the verdict FIN_PASS_DONE on both strands; n_fast (may be NULL): how many
 // bases, offs (may be NULL): FUSED INGEST -- the fast kernels pack the ASCII reads themselves and write the chunks of every read they do not finish
-// (a read they finish has undefined chunks); only where fin_pair_prepass_fuses() and no read is longer than FIN_FAST_CHUNKS * 32 bases, else an error
+// (a read they finish has undefined chunks); only where fin_pair_prepass_fuses() and no read is longer than ix->pp_max_len <= FIN_FAST_CHUNKS * 32
+// bases, else an error.  Then n_fast (if not NULL) has three words: [1] += reads parked in LDS for phases 2 and 3 (ix->pp_park, ix->pp_park_cap),
+// [2] += reads of list A beyond a block's park area
 int fin_launch_pair_prepass(const FinDevIndex* ix, const void* packed, const FinReadDesc* desc, uint32_t n_reads, uint32_t* pass, uint32_t* seed,
                             int defer, uint32_t grid_hint, void* out, uint32_t* n_fast, const uint8_t* bases, const uint64_t* offs, hipStream_t stream);
 // 1: fin_launch_pair_prepass with out and defer runs a fast kernel on this index, which can take the ingest over

@@ -376,23 +376,23 @@ __device__ unsigned long long g_fin_ppdbg[16];
 struct FastRun { uint32_t ok, u, off0, nE; uint64_t Es, Es2; };   // Es, Es2: the disagreeing positions, 16 bits each, ascending (four in each word)
 
 // The fused ingest (phase 1 of the fast kernels with `bases`): a strand's chunks made from the forward codes that the lane's LDS row holds (`row`,
-// stride FIN_TPB; 0 at a non-ACGT base) -- the reverse strand's chunk j is the reverse complement of the 32 forward bases that end at len - 32 j.
+// chunk j at row[j * stride]: FIN_TPB in the lanes' rows, the capacity in the park area; 0 at a non-ACGT base) -- the reverse strand's chunk j is the reverse complement of the 32 forward bases that end at len - 32 j.
 // `ok`: the strand's positions below it are ACGT (len: every one).  Validity bits say "position < ok", and codes at and behind a position that is
 // not valid are 0: that is bit for bit the pack kernel's chunk wherever the read is ACGT, and else for the strand's bases in front of its first
 // non-ACGT base -- all that phase 1 reads of such a read (its first k-mer; fast_try gives it up); its chunks are packed from its ASCII again.
 struct StrandChunks {
-    const uint64_t* row; uint32_t len, ok; bool rev;
+    const uint64_t* row; uint32_t stride, len, ok; bool rev;
     __device__ __forceinline__ uint4 operator[](uint32_t j) const {
         const uint32_t q = len - 32u * j, o = ok - 32u * j;   // (j < ceil(len / 32): q >= 1)
         const uint32_t cnt = (int)o <= 0 ? 0u : (o < q ? o : q) < 32u ? (o < q ? o : q) : 32u;
         uint64_t w;
-        if (!rev) w = row[j * FIN_TPB];
+        if (!rev) w = row[j * stride];
         else {
             uint64_t x;
             if (q >= 32u) {
                 const uint32_t p = q - 32u, a = p >> 5, sh = p & 31u;
-                x = row[a * FIN_TPB] >> (2u * sh);
-                if (sh) x |= row[(a + 1u) * FIN_TPB] << (64u - 2u * sh);
+                x = row[a * stride] >> (2u * sh);
+                if (sh) x |= row[(a + 1u) * stride] << (64u - 2u * sh);
             } else x = row[0] << (64u - 2u * q);     // the q bases at the top: what lies below them turns into codes past cnt, cut off next
             w = fin_pack::revcomp32(x);
         }
@@ -406,18 +406,21 @@ __device__ __forceinline__ bool row_holds(const uint4*) { return false; }
 __device__ __forceinline__ bool row_holds(const StrandChunks&) { return true; }
 __device__ __forceinline__ bool row_mirrored(const uint4*) { return false; }
 __device__ __forceinline__ bool row_mirrored(const StrandChunks& c) { return c.rev; }
+// ... and where that row is: a strand read from memory -- the lane's own row `lds` (stride FIN_TPB); the fused ingest's -- its own
+__device__ __forceinline__ const uint64_t* ask_row(const uint4*, const uint64_t* lds, uint32_t& stride) { stride = FIN_TPB; return lds; }
+__device__ __forceinline__ const uint64_t* ask_row(const StrandChunks& c, const uint64_t*, uint32_t& stride) { stride = c.stride; return c.row; }
 
 __device__ __forceinline__ uint64_t pp_revcomp(uint64_t f, uint32_t m, uint64_t mask) {
     uint64_t r = __brevll(f);
     r = ((r >> 1) & 0x5555555555555555ull) | ((r & 0x5555555555555555ull) << 1);
     return (r >> (64u - 2u * m)) ^ mask;
 }
-// the canonical string filter's block of q[a .. a+m-1] and the bits the string sets in it (lds: the lane's chunk codes, stride FIN_TPB)
+// the canonical string filter's block of q[a .. a+m-1] and the bits the string sets in it (lds: the read's chunk codes, chunk j at lds[j * ls])
 struct CbfAsk { uint4 blk; uint32_t mw[4]; };
-__device__ __forceinline__ void cbf_ask(const FinDevIndex& ix, const uint64_t* lds, uint32_t a, uint32_t m, uint64_t mask, CbfAsk& q) {
+__device__ __forceinline__ void cbf_ask(const FinDevIndex& ix, const uint64_t* lds, uint32_t ls, uint32_t a, uint32_t m, uint64_t mask, CbfAsk& q) {
     const uint32_t j = a >> 5, o = a & 31u;
-    uint64_t w = lds[j * FIN_TPB] >> (2 * o);
-    if (o + m > 32u) w |= lds[(j + 1) * FIN_TPB] << (64u - 2u * o);
+    uint64_t w = lds[j * ls] >> (2 * o);
+    if (o + m > 32u) w |= lds[(j + 1) * ls] << (64u - 2u * o);
     const uint64_t f = w & mask, v = pp_revcomp(f, m, mask);
     const uint64_t h = fin_cbf_hash(f < v ? f : v);
     q.blk = *(const uint4*)(ix.cbf + ((h >> 35) & ((1ull << ix.cbf_log2) - 1ull)));
@@ -439,6 +442,8 @@ template <typename CH>
 __device__ __forceinline__ bool fast_try(const PpConsts& K, const FinDevIndex& ix, const CH& ch, uint32_t t_anchor, uint32_t r_len, uint32_t g_ans, uint64_t* lds, FastRun& res) {
     const uint32_t k = (uint32_t)K.k, m = ix.cbf_m;
     const bool put = !row_holds(ch), mir = row_mirrored(ch);   // (a string of strand A at a = its reverse complement at r_len - a - m: the filter is canonical)
+    uint32_t ls;
+    const uint64_t* const arow = ask_row(ch, lds, ls);
     const uint32_t nch = (r_len + 31u) >> 5;
     if (nch > FIN_FAST_CHUNKS || g_ans < t_anchor) { PPDBG(1); return false; }
     const uint32_t gs = g_ans - t_anchor;           // the text position of the read's first base
@@ -508,9 +513,9 @@ __device__ __forceinline__ bool fast_try(const PpConsts& K, const FinDevIndex& i
         uint32_t lo = E > k - 1u ? E : k - 1u; if (lo < covered + 1u) lo = covered + 1u;
         const uint32_t hi = E + k - 1u < r_len - 1u ? E + k - 1u : r_len - 1u;
         CbfAsk q0, q1, q2; bool h0 = false, h1 = false, h2 = false;
-        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, lds, mir ? r_len - a - m : a, m, mask, q0); h0 = true; covered = a + k - 1u; lo = covered + 1u; }
-        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, lds, mir ? r_len - a - m : a, m, mask, q1); h1 = true; covered = a + k - 1u; lo = covered + 1u; }
-        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, lds, mir ? r_len - a - m : a, m, mask, q2); h2 = true; covered = a + k - 1u; lo = covered + 1u; }
+        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, arow, ls, mir ? r_len - a - m : a, m, mask, q0); h0 = true; covered = a + k - 1u; lo = covered + 1u; }
+        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, arow, ls, mir ? r_len - a - m : a, m, mask, q1); h1 = true; covered = a + k - 1u; lo = covered + 1u; }
+        if (lo <= hi) { const uint32_t a = lo - (m - 1u) < E ? lo - (m - 1u) : E; cbf_ask(ix, arow, ls, mir ? r_len - a - m : a, m, mask, q2); h2 = true; covered = a + k - 1u; lo = covered + 1u; }
         // the first k-mer behind this stretch of absent ends is reported where the text has it only if that place is safe
         const uint32_t t = E + k;
         const bool last = e + 1u == nE || E_at(e + 1u) > t;
@@ -528,26 +533,34 @@ __device__ __forceinline__ bool fast_try(const PpConsts& K, const FinDevIndex& i
 // A read none of whose looks found a k-mer: is EVERY k-mer of it absent, on both strands?  Strings of m bases that end at the first unsettled
 // k-mer end, one after the other (each settles k-m+1 ends), asked of the canonical string filter -- a read from nowhere takes about
 // len / (k-m+1) loads, all of them independent, where the pipeline proves each strand by itself with a prefix-table entry and node blocks per
-// string.  false: a string the filter knows (or a non-ACGT base): the pipeline decides.
-__device__ __forceinline__ bool fast_all_absent(const PpConsts& K, const FinDevIndex& ix, const uint4* ch, uint32_t r_len, uint64_t* lds) {
+// string.  false: a string the filter knows (or a non-ACGT base): the pipeline decides.  ch: the forward strand's chunks -- from memory (put
+// into the lane's row `lds` first) or a parked read's (asked where they lie)
+template <typename CH>
+__device__ __forceinline__ bool fast_all_absent(const PpConsts& K, const FinDevIndex& ix, const CH& ch, uint32_t r_len, uint64_t* lds) {
     const uint32_t k = (uint32_t)K.k, m = ix.cbf_m;
     const uint32_t nch = (r_len + 31u) >> 5;
     if (nch > FIN_FAST_CHUNKS) return false;
-    bool bad = false;
-    for (uint32_t j = 0; j < nch; j++) {
-        const uint4 c = ch[j];
-        const uint32_t nb = r_len - 32u * j < 32u ? r_len - 32u * j : 32u;
-        const uint32_t vm = nb == 32u ? 0xFFFFFFFFu : (1u << nb) - 1u;
-        bad = bad || (c.z & vm) != vm;
-        lds[j * FIN_TPB] = c.x | ((uint64_t)c.y << 32);
+    if constexpr (std::is_same<CH, StrandChunks>::value) {
+        if (ch.ok < r_len) return false;
+    } else {
+        bool bad = false;
+        for (uint32_t j = 0; j < nch; j++) {
+            const uint4 c = ch[j];
+            const uint32_t nb = r_len - 32u * j < 32u ? r_len - 32u * j : 32u;
+            const uint32_t vm = nb == 32u ? 0xFFFFFFFFu : (1u << nb) - 1u;
+            bad = bad || (c.z & vm) != vm;
+            lds[j * FIN_TPB] = c.x | ((uint64_t)c.y << 32);
+        }
+        if (bad) return false;
     }
-    if (bad) return false;
+    uint32_t ls;
+    const uint64_t* const arow = ask_row(ch, lds, ls);
     const uint64_t mask = m >= 32u ? ~0ull : ((1ull << (2u * m)) - 1ull);
     bool known = false;
     for (uint32_t t = k - 1u; t < r_len; ) {   // (four strings' loads at a time)
         CbfAsk q[4]; bool h[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) { h[i] = t < r_len; const uint32_t a = (h[i] ? t : k - 1u) - (m - 1u); cbf_ask(ix, lds, a, m, mask, q[i]); if (h[i]) t = a + k; }
+        for (int i = 0; i < 4; i++) { h[i] = t < r_len; const uint32_t a = (h[i] ? t : k - 1u) - (m - 1u); cbf_ask(ix, arow, ls, a, m, mask, q[i]); if (h[i]) t = a + k; }
 #pragma unroll
         for (int i = 0; i < 4; i++) known = known || (h[i] && cbf_known(q[i]));
         if (known) break;
@@ -565,11 +578,17 @@ __device__ __forceinline__ bool fast_all_absent(const PpConsts& K, const FinDevI
 // any k-mer end through up to three chunks), or round 3's tables (seeds are nodes, which the compact table does not hold): verdicts come from probe
 // steps as before, made afterwards and only for the reads the fast path did not finish (list L); under lean tables 2 (k >= 33) the looks are the verdicts
 // FUSED (with FAST): phase 1 ingests the reads itself (fin_launch_pair_prepass's `bases`) and writes to packed_out the chunks of every read it does
-// not finish, before the barrier behind it -- the later phases and kernels read them there
+// not finish, before the barrier behind it -- the later phases and kernels read them there.  Its lanes' rows (rch chunks each) and the PARK AREA
+// lie in dynamic LDS: the first `cap` reads of list A that are all ACGT keep their forward codes there (park[j * cap + slot], slot = the read's
+// place in list A) with their length and first output pair, and are not written out: phases 2 and 3 read them from the park area, and only a
+// parked read those phases do not finish has its chunks written, before the barrier behind phase 3.  n_fast[1], n_fast[2]: reads parked, reads
+// of list A beyond the capacity
+extern __shared__ uint64_t fin_pp_dyn[];
 template <bool FAST, bool KT2, bool FUSED = false>
 __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, const uint4* packed, const FinReadDesc* desc, uint32_t n_reads, uint32_t seg,
                                                       uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast,
-                                                      const uint8_t* bases = nullptr, const uint64_t* offs = nullptr, uint4* packed_out = nullptr) {
+                                                      const uint8_t* bases = nullptr, const uint64_t* offs = nullptr, uint4* packed_out = nullptr,
+                                                      uint32_t rch = 0, uint32_t cap = 0) {
     // lists of reads (numbers inside the block's segment).  lds_list: from the front, list A -- both first looks failed, the fast path goes on
     // with other k-mers of the read (phase 2) --; from the back, the stepping loop's reads (phase 4).  lds_b: list B, phase 3.
     __shared__ uint16_t lds_list[FIN_PP_SEG_MAX];
@@ -578,8 +597,13 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
     // once phases 2 and 3 are over: pushed to the back of lds_list while those phases still read list A from its front, they overwrote unread
     // entries of A as soon as n_a + pushes passed FIN_PP_SEG_MAX (every read of a 1024-read segment missing both first looks)
     __shared__ uint16_t lds_l[FAST ? FIN_PP_SEG_MAX : 1];
-    __shared__ uint32_t lds_n, lds_na, lds_nb, lds_nl;
-    __shared__ uint64_t lds_ck[FAST ? FIN_FAST_CHUNKS * FIN_TPB : 1];   // the fast path: strand A's chunk codes, per lane
+    __shared__ uint32_t lds_n, lds_na, lds_nb, lds_nl, lds_np;
+    __shared__ uint64_t lds_ck[FAST && !FUSED ? FIN_FAST_CHUNKS * FIN_TPB : 1];   // the fast path: strand A's chunk codes, per lane
+    // (fused: the rows, rch chunks per lane, then the park area -- codes, first output pairs, lengths; 0 = the slot holds no read)
+    uint64_t* const ck = FUSED ? fin_pp_dyn : lds_ck;
+    uint64_t* const park = ck + (size_t)rch * FIN_TPB;
+    uint32_t* const park_out = (uint32_t*)(park + (size_t)rch * cap);
+    uint16_t* const park_len = (uint16_t*)(park_out + cap);
     PpConsts K;
     K.blk_base = (const char*)ix.blocks; K.ptab = ix.ptab; K.filt = ix.filt;
     K.n = ix.n_nodes; K.C0 = ix.C[0]; K.C1 = ix.C[1]; K.C2 = ix.C[2]; K.C3 = ix.C[3]; K.C4 = ix.C[4];
@@ -597,7 +621,7 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
     // anything else = the k-mer end its stepping starts at (>= k: a failed look proves end k-1 absent)
     auto is_final = [&](uint32_t v) { return v == k1 || v == NONE || v == FIN_PASS_DEFERRED || v == FIN_PASS_DONE; };
 
-    if (threadIdx.x == 0) { lds_n = 0; lds_na = 0; lds_nb = 0; lds_nl = 0; }
+    if (threadIdx.x == 0) { lds_n = 0; lds_na = 0; lds_nb = 0; lds_nl = 0; lds_np = 0; }
     __syncthreads();
     const uint32_t r_lo = blockIdx.x * seg, r_hi = r_lo + seg < n_reads ? r_lo + seg : n_reads;
     const uint32_t lane = threadIdx.x & 63u;
@@ -673,7 +697,7 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
         if constexpr (FUSED) {
             // the fused ingest: the read's forward codes into the lane's LDS row (16-byte loads of its ASCII), and where its first and last
             // non-ACGT bases lie
-            uint64_t* const row = lds_ck + threadIdx.x;
+            uint64_t* const row = ck + threadIdx.x;
             const uint8_t* const rd = bases + (r < r_hi ? offs[r] : 0ull);
             uint32_t fi = r_len, li = NONE;
             for (uint32_t j = 0; j < r_nch; j++) {
@@ -684,15 +708,33 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
                 const uint32_t inv = ~v & (cnt < 32u ? (1u << cnt) - 1u : 0xFFFFFFFFu);
                 if (inv) { if (fi == r_len) fi = 32u * j + (uint32_t)(__ffs((int)inv) - 1); li = 32u * j + 31u - (uint32_t)__clz((int)inv); }
             }
-            cf = StrandChunks{row, r_len, fi, false}; cv = StrandChunks{row, r_len, li == NONE ? r_len : r_len - 1u - li, true};
+            cf = StrandChunks{row, FIN_TPB, r_len, fi, false}; cv = StrandChunks{row, FIN_TPB, r_len, li == NONE ? r_len : r_len - 1u - li, true};
             acgt = li == NONE;
         } else { cf = packed + d.off; cv = cf + r_nch; }
         uint2 verdict = make_uint2(NONE, NONE), sd = make_uint2(NONE, NONE);
-        FastRun fr = {0u, 0u, 0u, 0u, 0ull, 0ull}; bool fr_rev = false, to_a = false;
-        // (fused ingest) a read not finished here: its chunks of both strands, for the later phases and kernels
+        FastRun fr = {0u, 0u, 0u, 0u, 0ull, 0ull}; bool fr_rev = false, to_a = false, parked = false;
+        // list A: the read's place in it; (fused ingest) the first cap places park their reads -- those that are all ACGT
+        auto to_list_a = [&]() {
+            const uint32_t ia = atomicAdd(&lds_na, 1u);
+            lds_list[ia] = (uint16_t)(r - r_lo);
+            if constexpr (FUSED) {
+                if (ia < cap) {
+                    parked = acgt;
+                    park_len[ia] = parked ? (uint16_t)r_len : (uint16_t)0u;
+                    if (parked) {
+                        park_out[ia] = d.out_off;
+                        for (uint32_t j = 0; j < r_nch; j++) park[j * cap + ia] = cf.row[j * FIN_TPB];
+                    }
+                }
+            }
+        };
+        auto count_parked = [&]() {   // (wave-converged)
+            if constexpr (FUSED) { const uint64_t mp = __ballot(parked); if (lane == 0 && mp) atomicAdd(&lds_np, (uint32_t)__popcll(mp)); }
+        };
+        // (fused ingest) a read not finished here and not parked: its chunks of both strands, for the later phases and kernels
         auto spill = [&]() {
             if constexpr (FUSED) {
-                if (r < r_hi && !fr.ok) {
+                if (r < r_hi && !fr.ok && !parked) {
                     if (acgt) for (uint32_t j = 0; j < r_nch; j++) { packed_out[d.off + j] = cf[j]; packed_out[d.off + r_nch + j] = cv[j]; }
                     else for (uint32_t j = 0; j < 2u * r_nch; j++) {   // (a non-ACGT base: from its ASCII, as the pack kernel does)
                         uint64_t c; uint32_t v;
@@ -710,9 +752,9 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
                     const bool f_hit = flook(cf, k1, r_len, g_f, ver_f);
                     const bool v_hit = !f_hit && flook(cv, k1, r_len, g_v, ver_v);
                     hit = f_hit || v_hit;
-                    if (((f_hit && ver_f) || (v_hit && ver_v)) && fast_try(K, ix, v_hit ? cv : cf, k1, r_len, v_hit ? g_v : g_f, lds_ck + threadIdx.x, fr)) fr_rev = v_hit;
+                    if (((f_hit && ver_f) || (v_hit && ver_v)) && fast_try(K, ix, v_hit ? cv : cf, k1, r_len, v_hit ? g_v : g_f, ck + threadIdx.x, fr)) fr_rev = v_hit;
                     if (fr.ok) *(uint2*)(pass + 2 * (size_t)r) = make_uint2(FIN_PASS_DONE, FIN_PASS_DONE);
-                    else if (!hit) lds_list[atomicAdd(&lds_na, 1u)] = (uint16_t)(r - r_lo);
+                    else if (!hit) to_list_a();
                     else if (K.fbf) {
                         // lean tables: the table's look IS the pipeline's verdict (a k-mer it has is in the index), and a verified answer is the
                         // strand's seed -- a PLACE; nothing is left for the probe steps of phase L
@@ -725,6 +767,7 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
                 if (!fr.ok && !settled && (hit || !(r_len >= (uint32_t)K.k && defer && r_len < 65536u))) to_l(r);
             }
             spill();
+            count_parked();
             write_out(fr, fr_rev, r, d.out_off, r_len);
             continue;
         }
@@ -747,7 +790,7 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
                 if (FAST && can_defer) {
                     // ONE attempt per read, for whichever strand's look succeeded (the lanes of a wave run it together)
                     const bool af = f_hit && ver_f, av = !f_hit && v_hit && ver_v;
-                    if ((af || av) && fast_try(K, ix, av ? cv : cf, k1, r_len, av ? g_v : g_f, lds_ck + threadIdx.x, fr)) fr_rev = av;
+                    if ((af || av) && fast_try(K, ix, av ? cv : cf, k1, r_len, av ? g_v : g_f, ck + threadIdx.x, fr)) fr_rev = av;
                     if ((f_hit && !ver_f) || (!f_hit && v_hit && !ver_v)) PPDBG(8);
                     // neither first k-mer is in the index (a sequencing error in the first 31 bases of the strand that matches -- the other
                     // strand's k-mers are not in the table at all -- or a read from nowhere): phase 2 looks at other k-mers of the read
@@ -771,76 +814,108 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
         if (r < r_hi) {
             *(uint2*)(pass + 2 * (size_t)r) = verdict;
             if (seed) *(uint2*)(seed + 2 * (size_t)r) = sd;
-            if (to_a) lds_list[atomicAdd(&lds_na, 1u)] = (uint16_t)(r - r_lo);
+            if (to_a) to_list_a();
             else if (!is_final(verdict.x) || !is_final(verdict.y)) lds_list[FIN_PP_SEG_MAX - 1u - atomicAdd(&lds_n, 1u)] = (uint16_t)(r - r_lo);
         }
         spill();
+        count_parked();
         if (FAST) write_out(fr, fr_rev, r, d.out_off, r_len);
     }
     __syncthreads();
+    if constexpr (FUSED) {
+        if (threadIdx.x == 0 && n_fast) {
+            if (lds_np) atomicAdd(n_fast + 1, lds_np);
+            if (lds_na > cap) atomicAdd(n_fast + 2, lds_na - cap);
+        }
+    }
     if (FAST) {
         // ---- phase 2, list A: the strands' LAST k-mers (verdicts and seeds stay what the first looks made them: a read the fast path does not
         //      finish goes to the stepping loop as before).  A look that finds a k-mer settles the attempt, whichever way it ends; none: list B ----
+        // (fused: a read parked at slot i of list A is read from the park area -- park_chunks -- and leaves it by spill_parked if these phases do
+        //  not finish it; list B holds places in list A)
         const uint32_t n_a = lds_na;
+        auto park_chunks = [&](uint32_t i, uint32_t r_len, bool rev) { return StrandChunks{park + i, cap, r_len, r_len, rev}; };
+        auto spill_parked = [&](uint32_t i, uint32_t r) {
+            if constexpr (FUSED) {
+                const FinReadDesc d = desc[r];
+                const uint32_t r_nch = (d.len + 31u) >> 5;
+                const StrandChunks f = park_chunks(i, d.len, false), v = park_chunks(i, d.len, true);
+                for (uint32_t j = 0; j < r_nch; j++) { packed_out[d.off + j] = f[j]; packed_out[d.off + r_nch + j] = v[j]; }
+            }
+        };
+        // the read's length and first output pair, and where its chunks are: parked (true) or in memory from chunk c_off on
+        auto from_park = [&](bool on, uint32_t i, uint32_t r, uint32_t& r_len, uint32_t& out_off, uint64_t& c_off) -> bool {
+            if constexpr (FUSED) {
+                if (on && i < cap && park_len[i]) { r_len = park_len[i]; out_off = park_out[i]; c_off = 0; return true; }
+            }
+            FinReadDesc d = {0, 0, 0};
+            if (on) d = desc[r];
+            r_len = d.len; out_off = d.out_off; c_off = d.off;
+            return false;
+        };
         for (uint32_t ib = 0; ib < n_a; ib += FIN_TPB) {
             const uint32_t i = ib + threadIdx.x;
             const bool on = i < n_a;
             const uint32_t r = r_lo + (on ? lds_list[i] : 0u);
-            FinReadDesc d = {0, 0, 0};
-            if (on) d = desc[r];
-            const uint32_t r_len = d.len, r_nch = (r_len + 31u) >> 5;
-            const uint4* const cf = packed + d.off, *const cv = cf + r_nch;
+            uint32_t r_len, out_off; uint64_t c_off;
+            const bool pk = from_park(on, i, r, r_len, out_off, c_off);
             FastRun fr = {0u, 0u, 0u, 0u, 0ull, 0ull}; bool fr_rev = false;
             if (on) {
                 bool hit = false, to_b = true;
                 const uint32_t t = r_len - 1u;
-                if (t > k1) {
+                auto last_look = [&](const auto& cf, const auto& cv) {
                     uint32_t g_f = NONE, g_v = NONE; bool ver_f = false, ver_v = false;
                     const bool f_hit = flook(cf, t, r_len, g_f, ver_f);
                     const bool v_hit = !f_hit && flook(cv, t, r_len, g_v, ver_v);
                     hit = f_hit || v_hit; to_b = !hit;
                     const bool af = f_hit && ver_f, av = v_hit && ver_v;
-                    if ((af || av) && fast_try(K, ix, av ? cv : cf, t, r_len, av ? g_v : g_f, lds_ck + threadIdx.x, fr)) fr_rev = av;
+                    if ((af || av) && fast_try(K, ix, av ? cv : cf, t, r_len, av ? g_v : g_f, ck + threadIdx.x, fr)) fr_rev = av;
+                };
+                if (t > k1) {
+                    if (pk) { if constexpr (FUSED) last_look(park_chunks(i, r_len, false), park_chunks(i, r_len, true)); }
+                    else { const uint4* const cf = packed + c_off; last_look(cf, cf + ((r_len + 31u) >> 5)); }
                 }
                 if (fr.ok) *(uint2*)(pass + 2 * (size_t)r) = make_uint2(FIN_PASS_DONE, FIN_PASS_DONE);
-                else if (to_b) lds_b[atomicAdd(&lds_nb, 1u)] = (uint16_t)(r - r_lo);
-                else to_l(r);
+                else if (to_b) lds_b[atomicAdd(&lds_nb, 1u)] = (uint16_t)(FUSED ? i : r - r_lo);
+                else { if (pk) spill_parked(i, r); to_l(r); }
             }
-            write_out(fr, fr_rev, r, d.out_off, r_len);
+            write_out(fr, fr_rev, r, out_off, r_len);
         }
         __syncthreads();
         // ---- phase 3, list B: the strands' MIDDLE k-mers; no k-mer found anywhere: every k-mer of the read absent on both strands, if the
         //      canonical string filter knows none of the strings across it ----
         const uint32_t n_b = lds_nb;
         for (uint32_t ib = 0; ib < n_b; ib += FIN_TPB) {
-            const uint32_t i = ib + threadIdx.x;
-            const bool on = i < n_b;
-            const uint32_t r = r_lo + (on ? lds_b[i] : 0u);
-            FinReadDesc d = {0, 0, 0};
-            if (on) d = desc[r];
-            const uint32_t r_len = d.len, r_nch = (r_len + 31u) >> 5;
-            const uint4* const cf = packed + d.off, *const cv = cf + r_nch;
+            const uint32_t e = ib + threadIdx.x;
+            const bool on = e < n_b;
+            const uint32_t i = on ? lds_b[e] : 0u;   // (fused: the read's place in list A)
+            const uint32_t r = r_lo + (on ? (FUSED ? lds_list[i] : i) : 0u);
+            uint32_t r_len, out_off; uint64_t c_off;
+            const bool pk = from_park(on, i, r, r_len, out_off, c_off);
             FastRun fr = {0u, 0u, 0u, 0u, 0ull, 0ull}; bool fr_rev = false;
             if (on) {
                 bool hit = false;
-                // (the middle k-mer, in both strands.  More positions, and more than FIN_FAST_MAXE = 4 disagreeing bases, were measured: they finish
-                //  more reads -- chr1 93.3 instead of 90.7 %, k = 63 86.7 instead of 76.7 % -- and cost the pre-pass more than the pipeline gets back:
-                //  a wave waits for its lane with the most disagreeing bases)
-                for (uint32_t w = 0; w < 1u && !hit; w++) {
+                auto middle_look = [&](const auto& cf, const auto& cv) {
+                    // (the middle k-mer, in both strands.  More positions, and more than FIN_FAST_MAXE = 4 disagreeing bases, were measured: they finish
+                    //  more reads -- chr1 93.3 instead of 90.7 %, k = 63 86.7 instead of 76.7 % -- and cost the pre-pass more than the pipeline gets back:
+                    //  a wave waits for its lane with the most disagreeing bases)
                     const uint32_t t = (r_len + (uint32_t)K.k) / 2u - 1u;
-                    if (t <= k1 || t >= r_len - 1u) continue;
-                    uint32_t g_f = NONE, g_v = NONE; bool ver_f = false, ver_v = false;
-                    const bool f_hit = flook(cf, t, r_len, g_f, ver_f);
-                    const bool v_hit = !f_hit && flook(cv, t, r_len, g_v, ver_v);
-                    hit = f_hit || v_hit;
-                    const bool af = f_hit && ver_f, av = v_hit && ver_v;
-                    if ((af || av) && fast_try(K, ix, av ? cv : cf, t, r_len, av ? g_v : g_f, lds_ck + threadIdx.x, fr)) fr_rev = av;
-                }
-                if (!hit && fast_all_absent(K, ix, cf, r_len, lds_ck + threadIdx.x)) { fr.ok = 2u; fr.nE = 0u; }
+                    if (t > k1 && t < r_len - 1u) {
+                        uint32_t g_f = NONE, g_v = NONE; bool ver_f = false, ver_v = false;
+                        const bool f_hit = flook(cf, t, r_len, g_f, ver_f);
+                        const bool v_hit = !f_hit && flook(cv, t, r_len, g_v, ver_v);
+                        hit = f_hit || v_hit;
+                        const bool af = f_hit && ver_f, av = v_hit && ver_v;
+                        if ((af || av) && fast_try(K, ix, av ? cv : cf, t, r_len, av ? g_v : g_f, ck + threadIdx.x, fr)) fr_rev = av;
+                    }
+                    if (!hit && fast_all_absent(K, ix, cf, r_len, ck + threadIdx.x)) { fr.ok = 2u; fr.nE = 0u; }
+                };
+                if (pk) { if constexpr (FUSED) middle_look(park_chunks(i, r_len, false), park_chunks(i, r_len, true)); }
+                else { const uint4* const cf = packed + c_off; middle_look(cf, cf + ((r_len + 31u) >> 5)); }
                 if (fr.ok) *(uint2*)(pass + 2 * (size_t)r) = make_uint2(FIN_PASS_DONE, FIN_PASS_DONE);
-                else to_l(r);
+                else { if (pk) spill_parked(i, r); to_l(r); }
             }
-            write_out(fr, fr_rev, r, d.out_off, r_len);
+            write_out(fr, fr_rev, r, out_off, r_len);
         }
         if (n_fast && lane == 0 && fast_done) atomicAdd(n_fast, fast_done);
         __syncthreads();
@@ -909,14 +984,36 @@ __global__ __launch_bounds__(FIN_TPB) void fin_fast2_prepass_kernel(FinDevIndex 
                                                                     uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast) {
     fin_pair_prepass_body<true, true>(ix, packed, desc, n_reads, seg, pass, seed, defer, out, n_fast);
 }
-// the two fast kernels with the fused ingest: no pack kernel in front of them; they write the chunks of the reads they do not finish
+// the two fast kernels with the fused ingest: no pack kernel in front of them; they write the chunks of the reads they do not finish.  Dynamic LDS:
+// rch chunks per lane, then the park area of cap reads (pp_fused_lds)
 __global__ __launch_bounds__(FIN_TPB) void fin_fast_prepass_fused_kernel(FinDevIndex ix, uint4* packed, const FinReadDesc* desc, uint32_t n_reads, uint32_t seg,
-                                                                         uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast, const uint8_t* bases, const uint64_t* offs) {
-    fin_pair_prepass_body<true, false, true>(ix, packed, desc, n_reads, seg, pass, seed, defer, out, n_fast, bases, offs, packed);
+                                                                         uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast, const uint8_t* bases, const uint64_t* offs,
+                                                                         uint32_t rch, uint32_t cap) {
+    fin_pair_prepass_body<true, false, true>(ix, packed, desc, n_reads, seg, pass, seed, defer, out, n_fast, bases, offs, packed, rch, cap);
 }
 __global__ __launch_bounds__(FIN_TPB) void fin_fast2_prepass_fused_kernel(FinDevIndex ix, uint4* packed, const FinReadDesc* desc, uint32_t n_reads, uint32_t seg,
-                                                                          uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast, const uint8_t* bases, const uint64_t* offs) {
-    fin_pair_prepass_body<true, true, true>(ix, packed, desc, n_reads, seg, pass, seed, defer, out, n_fast, bases, offs, packed);
+                                                                          uint32_t* pass, uint32_t* seed, int defer, int2* out, uint32_t* n_fast, const uint8_t* bases, const uint64_t* offs,
+                                                                          uint32_t rch, uint32_t cap) {
+    fin_pair_prepass_body<true, true, true>(ix, packed, desc, n_reads, seg, pass, seed, defer, out, n_fast, bases, offs, packed, rch, cap);
+}
+
+// LDS a block of the fused kernels may hold: five blocks -- the VGPR-limited 5 waves per SIMD -- in a CU's 160 KB, less a margin for the allocation granule
+#define FIN_PP_LDS_BUDGET 32000u
+// the fused kernels' dynamic LDS for reads of up to max_len bases in segments of seg reads: rch chunks per lane, and the park area's capacity (option
+// "pp_park" 0: none; "debug_pp_park_cap": at most that many) -- 8 bytes per chunk of a read, 4 for its first output pair, 2 for its length
+static size_t pp_fused_lds(const FinDevIndex* ix, const void* kernel, uint32_t seg, uint32_t& rch, uint32_t& cap) {
+    static const size_t static_lds = [kernel] {   // (the same in both fused kernels: their lists and counters)
+        hipFuncAttributes a;
+        return hipFuncGetAttributes(&a, kernel) == hipSuccess && a.sharedSizeBytes ? (size_t)a.sharedSizeBytes : (size_t)(3u * 2u * FIN_PP_SEG_MAX + 64u);
+    }();
+    rch = ix->pp_max_len ? (ix->pp_max_len + 31u) >> 5 : FIN_FAST_CHUNKS;   // (0: not set -- room for the longest read the fusion takes)
+    const size_t rows = (size_t)rch * FIN_TPB * 8u, slot = (size_t)rch * 8u + 4u + 2u;
+    size_t c = FIN_PP_LDS_BUDGET > static_lds + rows ? (FIN_PP_LDS_BUDGET - static_lds - rows) / slot : 0u;
+    if (c > seg) c = seg;
+    if (!ix->pp_park) c = 0;
+    if (ix->pp_park_cap != 0xFFFFFFFFu && ix->pp_park_cap < c) c = ix->pp_park_cap;
+    cap = (uint32_t)c;
+    return (rows + c * slot + 7u) & ~(size_t)7u;
 }
 
 // the fast path: merged searches with a deferred strand on an index with the k-mer table (any k since round 5) and the canonical string filter.  Lean tables at
@@ -941,11 +1038,16 @@ extern "C" int fin_launch_pair_prepass(const FinDevIndex* ix, const void* packed
     const int fast = (out && defer) ? pp_fast_kernel(ix) : 0;
     const dim3 grid((n_reads + seg - 1) / seg);
     if (bases && (!fast || !offs || ix->k > 63)) return (int)hipErrorInvalidValue;   // (the caller skipped the pack kernel: only a fast kernel ingests)
-    if (bases && fast == 2)
-        hipLaunchKernelGGL(fin_fast2_prepass_fused_kernel, grid, dim3(FIN_TPB), 0, stream, *ix, (uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast, bases, offs);
-    else if (bases)
-        hipLaunchKernelGGL(fin_fast_prepass_fused_kernel, grid, dim3(FIN_TPB), 0, stream, *ix, (uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast, bases, offs);
-    else if (fast == 2)
+    if (bases) {
+        uint32_t rch, cap;
+        const void* const kern = fast == 2 ? (const void*)fin_fast2_prepass_fused_kernel : (const void*)fin_fast_prepass_fused_kernel;
+        const size_t dyn = pp_fused_lds(ix, kern, seg, rch, cap);
+        if (rch > FIN_FAST_CHUNKS) return (int)hipErrorInvalidValue;
+        if (fast == 2)
+            hipLaunchKernelGGL(fin_fast2_prepass_fused_kernel, grid, dim3(FIN_TPB), dyn, stream, *ix, (uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast, bases, offs, rch, cap);
+        else
+            hipLaunchKernelGGL(fin_fast_prepass_fused_kernel, grid, dim3(FIN_TPB), dyn, stream, *ix, (uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast, bases, offs, rch, cap);
+    } else if (fast == 2)
         hipLaunchKernelGGL(fin_fast2_prepass_kernel, grid, dim3(FIN_TPB), 0, stream, *ix, (const uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast);
     else if (fast == 1)
         hipLaunchKernelGGL(fin_fast_prepass_kernel, grid, dim3(FIN_TPB), 0, stream, *ix, (const uint4*)packed, desc, n_reads, seg, pass, seed, defer, (int2*)out, n_fast);
