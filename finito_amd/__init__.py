@@ -146,6 +146,16 @@ def lib():
         L.fin_batch_overflow_reads.argtypes = [vp]
         L.fin_format_pairs.restype = i64
         L.fin_format_pairs.argtypes = [i32p, i64, cp]
+        L.fin_hits_create.argtypes = [vp, C.c_int, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_hits_reset.argtypes = [vp, vp]
+        L.fin_batch_add_hits.argtypes = [vp, vp, vp, cp, C.c_size_t]
+        L.fin_hits_device_counts.restype = vp
+        L.fin_hits_device_counts.argtypes = [vp]
+        L.fin_hits_download.argtypes = [vp, u64p, u64p, cp, C.c_size_t]
+        L.fin_hits_free.argtypes = [vp]
+        L.fin_search_batch_unitig_counts.argtypes = [vp, cp, u64p, u64, C.c_int, u64p, u64p, cp, C.c_size_t]
+        L.fin_search_batch_add_hits.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
+        L.fin_records_unitig_counts.argtypes = [vp, u64, vp, u64, C.c_int, u64, u64p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -334,6 +344,63 @@ class Batch:
     def close(self):
         if getattr(self, "h", None):
             self.L.fin_batch_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Hits:
+    """uint64 found-k-mer counts per unitig, resident in HBM beside one replica of the index (fin_hits_* of the C ABI): the profile of
+    everything that was added, however many reads that was.  Unitig numbers are the index's own, the numbers the pairs carry."""
+
+    def __init__(self, index, device=0):
+        self.index = index
+        self.L = lib()
+        self.n_unitigs = index.n_unitigs
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_hits_create(index.h, int(device), C.byref(h), err, 512), err)
+        self.h = h
+
+    def add(self, batch, stream=None):
+        """counts += the hits of the batch's most recent run, on a HIP stream, behind that run; no sync (fin_batch_add_hits).  Adding the
+        same run twice counts it twice."""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_add_hits(batch.h, self.h, C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add_reads(self, reads, strands=FIN_MERGED):
+        """search a read set from host buffers, sub-batches pipelined as in search_reads, and add its hits; nothing comes back (fin_search_batch_add_hits)"""
+        bases, offsets = flatten(reads)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_add_hits(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+                                                int(strands), self.h, err, 512), err)
+        return self
+
+    def reset(self, stream=None):
+        rc = self.L.fin_hits_reset(self.h, C.c_void_p(stream or 0))
+        if rc != 0:
+            raise FinitoError(rc, "fin_hits_reset")
+        return self
+
+    def download(self):
+        """(uint64 counts[n_unitigs], their sum = the k-mers found); waits for the adds (fin_hits_download)"""
+        out = np.zeros(max(self.n_unitigs, 1), dtype=np.uint64)
+        tot = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_hits_download(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(tot), err, 512), err)
+        return out[: self.n_unitigs], int(tot.value)
+
+    def device_ptr(self):
+        return int(self.L.fin_hits_device_counts(self.h) or 0)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fin_hits_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -596,6 +663,21 @@ class FinimizerIndex:
                                                recs.ctypes.data_as(C.c_void_p), stream.ctypes.data_as(C.c_void_p), nk, C.byref(got), err, 512), err)
         return recs, stream[: int(got.value)]
 
+    def hits(self, device=0):
+        """a zeroed per-unitig accumulator beside the replica on `device` (Hits)"""
+        return Hits(self, device)
+
+    def unitig_counts(self, reads, strands=FIN_MERGED):
+        """the profile of a read set over host buffers (fin_search_batch_unitig_counts): (uint64 counts[n_unitigs], total_positive) -- how many of the
+        reads' k-mers were found in each unitig; only the counts come back from the device"""
+        bases, offsets = flatten(reads)
+        out = np.zeros(max(self.n_unitigs, 1), dtype=np.uint64)
+        npos = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_unitig_counts(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+                                                     int(strands), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(npos), err, 512), err)
+        return out[: self.n_unitigs], int(npos.value)
+
     def search_reads_text(self, reads, strands=FIN_MERGED):
         """run_fmin_queries_streaming with its printed text as the result (fin_search_batch_text): (bytes, total_positive)"""
         bases, offsets = flatten(reads)
@@ -801,6 +883,17 @@ def expand_records(recs, stream, k, n_threads=0):
     if rc != 0:
         raise FinitoError(rc, "fin_expand_records: records and stream do not belong together")
     return out[:nk], int(pos.value)
+
+
+def records_unitig_counts(recs, stream, k, n_unitigs, n_threads=0):
+    """fin_records_unitig_counts (host): uint64 counts[n_unitigs] of the found k-mers per unitig, from records + stream, without making the pairs"""
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE); stream = np.ascontiguousarray(stream, dtype=np.int32)
+    out = np.zeros(max(int(n_unitigs), 1), dtype=np.uint64)
+    rc = lib().fin_records_unitig_counts(recs.ctypes.data_as(C.c_void_p), len(recs), stream.ctypes.data_as(C.c_void_p), len(stream.reshape(-1, 2)), int(k),
+                                         int(n_unitigs), out.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_unitig_counts: a unitig number outside [0, n_unitigs), or records and stream do not belong together")
+    return out[: int(n_unitigs)]
 
 
 def format_pairs(pairs):

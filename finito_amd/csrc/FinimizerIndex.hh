@@ -222,6 +222,20 @@ public:
             check(fin_search_batch(h, bases, offsets, n_reads, FIN_FWD, nullptr, &pos, err, sizeof err), err);
         return pos;
     }
+    // the PROFILE of a batch of reads over the unitig set (fin_search_batch_unitig_counts): counts[u] = how many of the reads' k-mers (both strands merged) were
+    // found in unitig u, numbered as the pairs number them; only the counts come back from the device.  Not for a partitioned index; one device (the first)
+    void unitig_counts(const char* bases, const uint64_t* offsets, uint64_t n_reads, std::vector<uint64_t>& counts, uint64_t& total_positive) const {
+        if (ph) throw std::runtime_error("per-unitig counts are not available on a partitioned index");
+        char err[512] = {0};
+        counts.assign((size_t)number_of_unitigs(), 0);
+        check(fin_search_batch_unitig_counts(h, bases, offsets, n_reads, FIN_MERGED, counts.data(), &total_positive, err, sizeof err), err);
+    }
+    // the same for a caller that streams chunks: every chunk is added into `acc` (fin_hits_create on this index), which is downloaded once at the end
+    void add_unitig_hits(const char* bases, const uint64_t* offsets, uint64_t n_reads, fin_hits* acc) const {
+        if (ph) throw std::runtime_error("per-unitig counts are not available on a partitioned index");
+        char err[512] = {0};
+        check(fin_search_batch_add_hits(h, bases, offsets, n_reads, FIN_MERGED, acc, err, sizeof err), err);
+    }
     // same, into a caller buffer of 2*(number of k-mers)+2 int32 (page-locked memory from fin_host_alloc makes the copies DMA)
     void search_batch_into(const char* bases, const uint64_t* offsets, uint64_t n_reads, int32_t* pairs, uint64_t& total_positive) const {
         char err[512] = {0};

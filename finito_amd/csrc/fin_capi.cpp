@@ -93,7 +93,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_hits_combine, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -124,6 +124,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"fused_ingest", 1, 0, 1},                     // kernel 4 with the pre-pass's fast path: no pack kernel -- the fast pre-pass packs the ASCII reads itself and writes the chunks of the reads it does not finish (batches whose reads are all at most FIN_FAST_CHUNKS * 32 bases long); 0 = the pack kernel first (round 5)
     {"pp_park", 1, 0, 1},                          // with the fused ingest: the reads of list A (both first looks failed) stay in LDS for phases 2 and 3 of the fast pre-pass, and only those they do not finish are written out; 0 = every read phase 1 does not finish is written out and read back (round 6)
     {"debug_pp_park_cap", -1, -1, 1024},           // tests: at most this many parked reads per pre-pass block (-1: as many as the LDS budget holds)
+    {"hits_combine", 4, 0, 64},                    // fin_batch_add_hits: what a wave sums before an add goes to memory (fin_hits.hip) -- rounds in which the record lanes of one unitig merge, and the run held back between rows of pairs; 0 = every record lane and every run of a row adds by itself
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -1255,6 +1256,158 @@ int fin_expand_records(const fin_read_record* recs, uint64_t n_reads, const int3
     return FIN_OK;
 }
 
+// ---- the profile over the unitig set (fin_hits.hip) ---------------------------------------------------------------------------------
+struct fin_hits {
+    const fin_index* idx = nullptr;
+    int device = -1;
+    uint64_t n_unitigs = 0;
+    void* d_counts = nullptr;   // uint64[n_unitigs], then the flag word (fin_launch_hits_add)
+    // what fin_hits_download waits for: an event per stream that work on the counts was put on
+    std::mutex mu; std::vector<std::pair<hipStream_t, hipEvent_t>> pending;
+};
+static uint32_t* hits_flags(const fin_hits* h) { return (uint32_t*)((uint64_t*)h->d_counts + h->n_unitigs); }
+static int hits_mark(fin_hits* h, hipStream_t st, char* err, size_t errlen) {
+    std::lock_guard<std::mutex> g(h->mu);
+    for (auto& p : h->pending) if (p.first == st) { HIPCHK(hipEventRecord(p.second, st)); return FIN_OK; }
+    hipEvent_t ev = nullptr;
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    h->pending.push_back({st, ev});
+    HIPCHK(hipEventRecord(ev, st));
+    return FIN_OK;
+}
+
+void fin_hits_free(fin_hits* h) {
+    if (!h) return;
+    if (h->device >= 0) (void)hipSetDevice(h->device);
+    for (auto& p : h->pending) { (void)hipEventSynchronize(p.second); (void)hipEventDestroy(p.second); }
+    (void)hipFree(h->d_counts);
+    delete h;
+}
+
+int fin_hits_create(const fin_index* idx, int device, fin_hits** out, char* err, size_t errlen) {
+    if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (!idx->replica_on(device)) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
+    HIPCHK(hipSetDevice(device));
+    fin_hits* h = new (std::nothrow) fin_hits();
+    if (!h) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
+    h->idx = idx; h->device = device; h->n_unitigs = idx->n_unitigs;
+    if (hipMalloc(&h->d_counts, h->n_unitigs * 8 + 8) != hipSuccess) { (void)hipGetLastError(); delete h; set_err(err, errlen, "out of device memory (unitig counts)"); return FIN_ENOMEM; }
+    if (hipMemset(h->d_counts, 0, h->n_unitigs * 8 + 8) != hipSuccess) { fin_hits_free(h); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    *out = h;
+    return FIN_OK;
+}
+
+int fin_hits_reset(fin_hits* h, void* hip_stream) {
+    if (!h) return FIN_EINVAL;
+    if (hipSetDevice(h->device) != hipSuccess) return FIN_ENODEV;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (hipMemsetAsync(h->d_counts, 0, h->n_unitigs * 8 + 8, st) != hipSuccess) return FIN_ENODEV;
+    return hits_mark(h, st, nullptr, 0);
+}
+
+void* fin_hits_device_counts(const fin_hits* h) { return h ? h->d_counts : nullptr; }
+
+int fin_batch_add_hits(fin_batch* b, fin_hits* h, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !h) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->ran) { set_err(err, errlen, "this batch has not run: there are no hits to add (fin_batch_run first)"); return FIN_EINVAL; }
+    if (b->idx != h->idx || b->device != h->device) { set_err(err, errlen, "batch and accumulator belong to different indexes or devices"); return FIN_EINVAL; }
+    if (b->ovf_state == 2) { set_err(err, errlen, "the overflow list of this batch overran: results withheld"); return FIN_ELIMIT; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (st != b->last_stream) {   // behind the run, whichever stream it was launched on
+        hipEvent_t ev = b->runs.back().e[4];
+        HIPCHK(hipStreamWaitEvent(st, ev, 0));
+    }
+    const int rc = fin_launch_hits_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, h->d_counts,
+                                       (uint32_t)h->n_unitigs, hits_flags(h), b->d_ovf_count, b->last_ovf_cap, (uint32_t)optv(b->idx, O_hits_combine), st);
+    if (rc != 0) { set_err(err, errlen, std::string("hits kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    return hits_mark(h, st, err, errlen);
+}
+
+int fin_hits_download(fin_hits* h, uint64_t* counts_out, uint64_t* total, char* err, size_t errlen) {
+    if (!h || (h->n_unitigs && !counts_out && !total)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(h->device));
+    {
+        std::lock_guard<std::mutex> g(h->mu);
+        for (auto& p : h->pending) HIPCHK(hipEventSynchronize(p.second));
+    }
+    uint32_t flags = 0;
+    HIPCHK(hipMemcpy(&flags, hits_flags(h), 4, hipMemcpyDeviceToHost));
+    if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)"); return FIN_ELIMIT; }
+    if (flags & 2u) { set_err(err, errlen, "a pair with a unitig number outside the index was met (not counted)"); return FIN_EINVAL; }
+    std::vector<uint64_t> tmp;
+    uint64_t* dst = counts_out;
+    if (!dst) { tmp.resize((size_t)h->n_unitigs); dst = tmp.data(); }
+    if (h->n_unitigs) HIPCHK(hipMemcpy(dst, h->d_counts, h->n_unitigs * 8, hipMemcpyDeviceToHost));
+    if (total) { uint64_t t = 0; for (uint64_t u = 0; u < h->n_unitigs; u++) t += dst[u]; *total = t; }
+    return FIN_OK;
+}
+
+// host: the profile from records + stream -- fin_expand_records' arithmetic without the pairs.  A chunk of reads per thread, each with counts of its own
+// when the unitig set is small, else atomic adds into the caller's array
+int fin_records_unitig_counts(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t n_unitigs,
+                              uint64_t* counts_out, int n_threads) {
+    if ((n_reads && !recs) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !counts_out)) return FIN_EINVAL;
+    int T = n_threads > 0 ? n_threads : fin_host_threads();
+    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
+    for (uint64_t u = 0; u < n_unitigs; u++) counts_out[u] = 0;
+    std::vector<uint64_t> str0((size_t)T + 1, 0);
+    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
+        const auto lh = bounds(t);
+        uint64_t sp = 0;
+        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
+        str0[(size_t)t + 1] = sp;
+    }
+    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
+    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
+    bool ok = true;
+#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
+    for (int t = 0; t < T; t++) {
+        const auto lh = bounds(t);
+        uint64_t sp = str0[(size_t)t];
+        bool good = true;
+        auto add = [&](uint64_t u, uint64_t n) {
+            if (u >= n_unitigs) { good = false; return; }
+            if (T == 1) counts_out[u] += n;
+            else __atomic_fetch_add(counts_out + u, n, __ATOMIC_RELAXED);
+        };
+        for (uint64_t r = lh.first; r < lh.second && good; r++) {
+            const fin_read_record& R = recs[r];
+            const uint32_t nk = R.nk, kind = R.meta >> 16;
+            if (kind == 0u) {
+                const int32_t* const src = stream_pairs + 2 * sp;
+                for (uint32_t i = 0; i < nk;) {   // a run of slots in one unitig: one add
+                    const int32_t u = src[2 * i];
+                    uint32_t j = i + 1;
+                    while (j < nk && src[2 * j] == u) j++;
+                    if (u >= 0) add((uint64_t)u, j - i);
+                    else if (u != -1) good = false;
+                    i = j;
+                }
+                sp += nk;
+            } else if (kind == 1u) {
+                const uint32_t nE = R.meta & 0xFFu;
+                uint64_t gaps = 0;
+                uint32_t done_to = 0;
+                for (uint32_t e = 0; e < nE && e < 8u; e++) {
+                    const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
+                    uint32_t lo = E >= (uint32_t)(k - 1) ? E - (uint32_t)(k - 1) : 0u, hi = E < nk ? E : (nk ? nk - 1u : 0u);
+                    if (lo < done_to) lo = done_to;
+                    if (nk && lo <= hi) gaps += hi - lo + 1u;
+                    if (hi + 1u > done_to) done_to = hi + 1u;
+                }
+                if (nk - gaps) add(R.u, nk - gaps);
+            }
+        }
+        ok = good && ok;
+    }
+    return ok ? FIN_OK : FIN_EINVAL;
+}
+
 int fin_batch_step_time(const fin_batch* b, uint64_t skip_first, double ms_parts[5], uint64_t* n_runs) {
     if (!b) return FIN_EINVAL;
     double t[5] = {0, 0, 0, 0, 0}; uint64_t n = 0;
@@ -1342,6 +1495,7 @@ struct TextSink {
     // (records instead of text when `recs` is set: fin_search_batch_records -- `len` then counts a sub-batch's stream pairs)
     fin_read_record* recs = nullptr; int32_t* rpairs = nullptr; uint64_t rcap = 0; uint64_t read0 = 0;
     char* buf = nullptr; uint64_t cap = 0;
+    fin_hits* hits = nullptr;   // the profile instead of text (fin_search_batch_unitig_counts): every sub-batch is added on the device, nothing comes back
     std::vector<uint64_t> len; std::vector<char> known;
     std::mutex mu; std::condition_variable cv;
     uint64_t total = 0;
@@ -1410,6 +1564,10 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
             }
             if (rc == FIN_OK) { b->text_mode = ts ? 2 : 0; rc = fin_batch_run(b, strands, (void*)b->own_stream, e, sizeof e); }   // (text sink: the text is the only product)
             uint64_t pos = 0;
+            if (rc == FIN_OK && ts && ts->hits) {
+                // (behind the run on the batch's own stream: the next batch_load on that stream finds the add done; fin_hits_download waits for the last ones)
+                rc = fin_batch_add_hits(b, ts->hits, (void*)b->own_stream, e, sizeof e);
+            } else
             if (rc == FIN_OK && ts && ts->recs) {
                 // records: the sub-batch's stream of pairs lands behind the streams of all earlier sub-batches, its records at its reads' numbers
                 uint64_t L = 0;
@@ -1550,6 +1708,28 @@ int fin_search_batch_records(const fin_index* idx, const char* bases, const uint
     TextSink ts; ts.recs = recs_out; ts.rpairs = stream_pairs_out; ts.rcap = stream_pairs_out ? stream_cap_pairs : 0; ts.read0 = 0;
     const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, FIN_MERGED, nullptr, nullptr, err, errlen, &ts);
     if (rc == FIN_OK && n_stream_pairs) *n_stream_pairs = ts.total;
+    return rc;
+}
+
+int fin_search_batch_add_hits(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_hits* h, char* err, size_t errlen) {
+    if (!idx || !offsets || !h || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (h->idx != idx) { set_err(err, errlen, "the accumulator belongs to another index"); return FIN_EINVAL; }
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.hits = h;
+    return search_range_on(idx, h->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+}
+
+int fin_search_batch_unitig_counts(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint64_t* counts_out,
+                                   uint64_t* n_positive, char* err, size_t errlen) {
+    if (!idx || !offsets || (idx->n_unitigs && !counts_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (n_positive) *n_positive = 0;
+    fin_hits* h = nullptr;
+    int rc = fin_hits_create(idx, idx->replicas[0].device, &h, err, errlen);
+    if (rc != FIN_OK) return rc;
+    rc = fin_search_batch_add_hits(idx, bases, offsets, n_reads, strands, h, err, errlen);
+    if (rc == FIN_OK) rc = fin_hits_download(h, counts_out, n_positive, err, errlen);
+    fin_hits_free(h);
     return rc;
 }
 

@@ -117,6 +117,11 @@ int fin_launch_kt3_query(const FinDevIndex* ix, const uint64_t* k0, const uint64
 uint32_t fin_rec_blocks(uint32_t n_reads);
 int fin_launch_rec_count(const void* frec, const uint64_t* out_offs, uint32_t n_reads, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total, hipStream_t stream);
 int fin_launch_rec_compact(void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, const uint64_t* blk_off, void* stream_out, hipStream_t stream);
+// fin_hits.hip: counts[u] += the found k-mers of a finished step per unitig.  frec (null: the step left none -- the pair array is scanned end to end): the fast
+// path's records, read as they stand (kind 1: one number per read; kind 0: the read's pairs through out_offs; kind 2: nothing).  flags: one u32 of the
+// accumulator (bit 0: the step's overflow list overran -- nothing added; bit 1: a unitig number >= n_unitigs met -- not added).  combine: option "hits_combine"
+int fin_launch_hits_add(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint64_t n_pairs, uint32_t k, void* counts,
+                        uint32_t n_unitigs, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t combine, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -443,6 +443,10 @@ static const char* SEARCH_HELP =
     "      --strand-counts arg  1: also count the k-mers found on each strand by itself, as the reference logs them (\"Found kmers\",\n"
     "                        \"Found kmers reverse\") and sums them into <index>.stats: two more search passes per read (default: 0 --\n"
     "                        the stats field is then the merged count)\n"
+    "      --unitig-counts FILE  also write the run's profile over the unitig set: one line `unitig<TAB>count` per unitig of the index, in\n"
+    "                        unitig order, zeros included -- how many query k-mers (both strands merged, all query files) were found in it.\n"
+    "                        Counted on the first GPU, nothing per k-mer comes back for it. Not for a partitioned index.\n"
+    "      --no-text arg     1 (only with --unitig-counts): do not make or write the pair text, the profile is the only result\n"
     "  -h, --help            Print usage\n";
 
 static int build_fmin(int argc, char** argv) {
@@ -608,6 +612,11 @@ struct OutSink {   // regular files are written by all threads at once, anything
 // --strand-counts 1: kmers_count / kmers_count_rev of search_fmin.hh:66-67 -- the hits of search(read) and of search(rc(read)) each by
 // itself, which the merged pairs do not show (a forward hit hides the reverse strand's) -- from two forward-only passes per chunk
 static bool g_strand_counts = false;
+// --unitig-counts FILE: every chunk's hits are added into one accumulator on the first device (fin_search_batch_add_hits), downloaded once after the last
+// chunk; --no-text 1: that is all a chunk is searched for
+static fin_hits* g_hits = nullptr;
+static bool g_no_text = false;
+static uint64_t g_hits_total = 0;   // the accumulator's sum after the previous query file
 
 static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breader, OutSink& out, const FinimizerIndex& index, const string& stats_filename) {
     const int64_t k = index.get_k();
@@ -681,16 +690,20 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         const int64_t len = (int64_t)(c->offsets[r + 1] - c->offsets[r]);
                         c->pair_off[r + 1] = c->pair_off[r] + (uint64_t)(len >= k ? len - k + 1 : 0);
                     }
-                    // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
-                    if (!c->text) {
-                        lock_guard<mutex> g(g_prewarmed.mu);
-                        if (!g_prewarmed.texts.empty()) { c->text = g_prewarmed.texts.back(); g_prewarmed.texts.pop_back(); }
-                    }
-                    if (!c->text) c->text = fin_text_create();
-                    c->as_text = gpu_text && c->text && index.search_batch_text(c->bases.get(0), c->offsets.data(), n_reads, c->text, c->positive);
-                    if (!c->as_text) {
-                        int32_t* pairs = (int32_t*)c->pairs.get((size_t)(2 * c->pair_off[n_reads] + 2) * sizeof(int32_t));
-                        index.search_batch_into(c->bases.get(0), c->offsets.data(), n_reads, pairs, c->positive);
+                    if (g_no_text) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);   // the profile is all this chunk is searched for
+                    else {
+                        // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
+                        if (!c->text) {
+                            lock_guard<mutex> g(g_prewarmed.mu);
+                            if (!g_prewarmed.texts.empty()) { c->text = g_prewarmed.texts.back(); g_prewarmed.texts.pop_back(); }
+                        }
+                        if (!c->text) c->text = fin_text_create();
+                        c->as_text = gpu_text && c->text && index.search_batch_text(c->bases.get(0), c->offsets.data(), n_reads, c->text, c->positive);
+                        if (!c->as_text) {
+                            int32_t* pairs = (int32_t*)c->pairs.get((size_t)(2 * c->pair_off[n_reads] + 2) * sizeof(int32_t));
+                            index.search_batch_into(c->bases.get(0), c->offsets.data(), n_reads, pairs, c->positive);
+                        }
+                        if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);   // (a second pass over the chunk on the device: the text is what bounds this loop)
                     }
                     if (g_strand_counts) {
                         c->positive_fwd = index.count_found_one_strand(c->bases.get(0), c->offsets.data(), n_reads);
@@ -734,6 +747,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                 const vector<uint64_t>& pair_off = c->pair_off;
                 number_of_queries += (int64_t)pair_off[n_reads];
                 total_positive += c->positive; kmers_count += c->positive_fwd; kmers_count_rev += c->positive_rev;
+                if (g_no_text) { t_last = cur_time_micros(); t_write += t_last - tw0; free_q.push(c); continue; }
                 if (c->as_text) {   // already text: all threads write their slice of it
                     const char* tp = fin_text_data(c->text); const uint64_t tn = fin_text_size(c->text);
                     // (pwrite by all threads; appending through a shared mapping was tried and is slower: 1.1 s against 0.9 s for 5.2 GB
@@ -780,6 +794,12 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
         cerr << "[timing] stage busy seconds: parse " << t_parse.load() * 1e-6 << "  search(+PCIe" << (gpu_text ? "+GPU text" : "") << ") " << t_search.load() * 1e-6
              << "  " << (gpu_text ? "write " : "format+write ") << t_write.load() * 1e-6 << endl;
     if (first_error) rethrow_exception(first_error);
+    if (g_no_text) {   // no pairs came back: the found k-mers of this file are what the accumulator's sum grew by
+        char err[512] = {0};
+        uint64_t tot = 0;
+        if (fin_hits_download(g_hits, nullptr, &tot, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        total_positive = tot - g_hits_total; g_hits_total = tot;
+    }
     // the reference's timed region is search + formatting + printing per read; here: first chunk entering the search until the last
     // chunk is written, minus the time the search stage sat waiting for the parser
     int64_t total_micros = t_first >= 0 && t_last >= 0 ? t_last - t_first - search_wait_micros : 0;
@@ -799,9 +819,12 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
+    g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
+    if (g_no_text && !o.has("unitig-counts")) throw runtime_error("--no-text 1 is only legal together with --unitig-counts (the run would have no result)");
+    if (g_no_text && g_strand_counts) throw runtime_error("--no-text 1 and --strand-counts 1 do not go together");
     if (!o.has("query-file")) throw runtime_error("Option 'query-file' has no value");
     if (!o.has("index-file")) throw runtime_error("Option 'index-file' has no value");
     string queryfile = o.get("query-file");
@@ -819,6 +842,8 @@ static int search_fmin(int argc, char** argv) {
         throw runtime_error("Number of input and output files does not match (" + to_string(query_files.size()) + " vs " +
                             to_string(output_files.value().size()) + ")");
     string index_prefix = o.get("index-file");
+    const string counts_file = o.get("unitig-counts", "");
+    if (!counts_file.empty()) check_writable(counts_file);
     cerr << "Loading index..." << endl;
     const int first_dev = stoi(o.get("device", "0"));
     // beside the index load: page-lock the pipeline's buffers (four chunks of 48 MB of bases and of up to 16 bytes of text per k-mer)
@@ -854,7 +879,13 @@ static int search_fmin(int argc, char** argv) {
     const int64_t t_l0 = cur_time_micros();
     index.load(index_prefix);
     const int64_t t_l1 = cur_time_micros();
+    if (!counts_file.empty() && index.partitioned()) throw runtime_error("--unitig-counts is not available with a partitioned index");
     index.to_device();
+    struct HitsOwner { ~HitsOwner() { fin_hits_free(g_hits); g_hits = nullptr; } } hits_owner;
+    if (!counts_file.empty()) {
+        char err[512] = {0};
+        if (fin_hits_create(index.handle(), first_dev, &g_hits, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
              << (cur_time_micros() - t_l1) * 1e-6 << endl;
@@ -874,6 +905,17 @@ static int search_fmin(int argc, char** argv) {
             SeqReader reader(query_files[i]);
             number_of_queries += run_fmin_queries_streaming(&reader, nullptr, out, index, index_prefix + ".stats");
         }
+    }
+    if (g_hits) {   // the profile, after the last chunk: one line per unitig of the index
+        char err[512] = {0};
+        vector<uint64_t> counts((size_t)index.number_of_unitigs() + 1);
+        if (fin_hits_download(g_hits, counts.data(), nullptr, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        string text;
+        text.reserve(counts.size() * 12);
+        for (size_t u = 0; u + 1 < counts.size(); u++) { text += to_string(u); text += '\t'; text += to_string(counts[u]); text += '\n'; }
+        ofstream cf(counts_file, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + counts_file);
     }
     prewarm_stop = true;
     if (prewarm.joinable()) prewarm.join();

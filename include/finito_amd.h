@@ -415,6 +415,44 @@ int fin_expand_records(const fin_read_record* recs, uint64_t n_reads, const int3
 int fin_batch_records(fin_batch* b, uint64_t* n_stream_pairs, char* err, size_t errlen);
 int fin_batch_download_records(fin_batch* b, fin_read_record* recs_out, int32_t* stream_pairs_out, char* err, size_t errlen);
 
+/* ---- the PROFILE of a run over the unitig set: how many query k-mers were found in each unitig ----
+ * For abundance estimates, presence / absence of a unitig in a sample, unitig-to-colour tables: the caller wants one number per unitig, not a pair per
+ * k-mer.  An accumulator is a uint64 count per unitig in HBM beside one replica of the index; fin_batch_add_hits adds what the batch's most recent
+ * fin_batch_run found, on the device (fin_hits.hip): a read the pre-pass's fast path finished (a record, see above) is one number for one unitig
+ * and its pairs are never read -- in text mode 2 they do not even exist --, the other reads' pairs are scanned where the step left them.  Nothing per k-mer
+ * crosses PCIe; the result is 8 bytes per unitig for any number of reads.  Unitig numbers are the index's own (permute_unitigs order), the numbers the pairs
+ * carry.  Counts are integer adds: exact, whatever order the reads arrive in.
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi, sums across the ranks of a job -- a caller with several GPUs keeps an accumulator
+ * per replica and adds the downloaded arrays. */
+typedef struct fin_hits fin_hits;
+/* zeroed counts for `idx` on `device` (FIN_ENODEV: the index has no replica there) */
+int fin_hits_create(const fin_index* idx, int device, fin_hits** out, char* err, size_t errlen);
+/* zeroes the counts, on the given stream */
+int fin_hits_reset(fin_hits* h, void* hip_stream);
+/* counts += the hits of the batch's most recent run, on the given stream, ordered behind that run; does not wait.  Every call adds: the same run added twice
+ * counts twice (that is the caller's business).  Reads the run's records and pairs as they stand and changes neither: fin_batch_records,
+ * fin_batch_format_text and fin_batch_download give afterwards what they give without it.  FIN_EINVAL: the batch has not run, or batch and accumulator belong
+ * to different indexes or devices.  The batch must not be reloaded or run again on ANOTHER stream before the add has finished (on the same stream the order
+ * is the stream's).  A run whose overflow list overran has no results: nothing of it is added and fin_hits_download reports FIN_ELIMIT until the reset. */
+int fin_batch_add_hits(fin_batch* b, fin_hits* h, void* hip_stream, char* err, size_t errlen);
+/* uint64[fin_index_n_unitigs] in HBM (valid once the adds on their streams have finished) */
+void* fin_hits_device_counts(const fin_hits* h);
+/* waits for every add and reset issued so far; counts_out[fin_index_n_unitigs] (may be NULL), *total (may be NULL) = their sum = the k-mers found */
+int fin_hits_download(fin_hits* h, uint64_t* counts_out, uint64_t* total, char* err, size_t errlen);
+void fin_hits_free(fin_hits* h);
+/* host buffers in, only the profile out: fin_search_batch's pipeline over sub-batches (options max_batch_kmers, pipeline_kmers, pipeline_depth), each run in
+ * text mode 2 where the fast path is on and added on the device; counts_out[fin_index_n_unitigs], *n_positive (may be NULL) as fin_search_batch reports it.
+ * Reads shorter than k and an empty read set are legal and contribute nothing. */
+int fin_search_batch_unitig_counts(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint64_t* counts_out,
+                                   uint64_t* n_positive, char* err, size_t errlen);
+/* the same loop into a resident accumulator (of this index; its device is searched): nothing is downloaded -- a caller that streams chunks of reads
+ * through it takes the profile once, with fin_hits_download, after the last chunk (the `finito search-fmin --unitig-counts` loop) */
+int fin_search_batch_add_hits(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_hits* h, char* err, size_t errlen);
+/* host: the same profile from records + stream (the arithmetic of fin_expand_records, without making the pairs); counts_out[n_unitigs] is overwritten.
+ * n_threads <= 0: all cores.  FIN_EINVAL: a unitig number >= n_unitigs, or a stream that is not this record set's */
+int fin_records_unitig_counts(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t n_unitigs,
+                              uint64_t* counts_out, int n_threads);
+
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
  * k-mer is in no unitig), 1 a verified claim, 2 an unverified one (| 8: the exact side table has the k-mer, g is its answer), | 4 the text at [g-k+1, g] spells
