@@ -156,6 +156,16 @@ def lib():
         L.fin_search_batch_unitig_counts.argtypes = [vp, cp, u64p, u64, C.c_int, u64p, u64p, cp, C.c_size_t]
         L.fin_search_batch_add_hits.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
         L.fin_records_unitig_counts.argtypes = [vp, u64, vp, u64, C.c_int, u64, u64p, C.c_int]
+        L.fin_cover_create.argtypes = [vp, C.c_int, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_cover_reset.argtypes = [vp, vp]
+        L.fin_batch_add_cover.argtypes = [vp, vp, vp, cp, C.c_size_t]
+        L.fin_cover_device_bits.restype = vp
+        L.fin_cover_device_bits.argtypes = [vp]
+        L.fin_cover_download.argtypes = [vp, u64p, u64p, u64p, cp, C.c_size_t]
+        L.fin_cover_free.argtypes = [vp]
+        L.fin_search_batch_add_cover.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
+        L.fin_search_batch_unitig_coverage.argtypes = [vp, cp, u64p, u64, C.c_int, u64p, u64p, cp, C.c_size_t]
+        L.fin_records_cover.argtypes = [vp, u64, vp, u64, C.c_int, i64p, u64, u64p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -401,6 +411,65 @@ class Hits:
     def close(self):
         if getattr(self, "h", None):
             self.L.fin_hits_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Cover:
+    """one bit per base of the concatenated unitig text, resident in HBM beside one replica of the index (fin_cover_* of the C ABI): bit start(u) + off is set
+    iff a found pair (u, off) was added -- which k-mers of each unitig were seen, where Hits says how often the unitig was hit."""
+
+    def __init__(self, index, device=0):
+        self.index = index
+        self.L = lib()
+        self.n_unitigs = index.n_unitigs
+        self.n_words = (index.total_len + 63) // 64
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_cover_create(index.h, int(device), C.byref(h), err, 512), err)
+        self.h = h
+
+    def add(self, batch, stream=None):
+        """bits |= the found places of the batch's most recent run, on a HIP stream, behind that run; no sync (fin_batch_add_cover).  Adding the same run
+        twice changes nothing."""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_add_cover(batch.h, self.h, C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add_reads(self, reads, strands=FIN_MERGED):
+        """search a read set from host buffers, sub-batches pipelined as in search_reads, and set its places; nothing comes back (fin_search_batch_add_cover)"""
+        bases, offsets = flatten(reads)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_add_cover(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+                                                 int(strands), self.h, err, 512), err)
+        return self
+
+    def reset(self, stream=None):
+        rc = self.L.fin_cover_reset(self.h, C.c_void_p(stream or 0))
+        if rc != 0:
+            raise FinitoError(rc, "fin_cover_reset")
+        return self
+
+    def download(self):
+        """(uint64 bits[(total_len + 63) // 64], uint64 covered[n_unitigs], their sum = the distinct k-mers found); waits for the adds (fin_cover_download)"""
+        bits = np.zeros(max(self.n_words, 1), dtype=np.uint64)
+        cov = np.zeros(max(self.n_unitigs, 1), dtype=np.uint64)
+        tot = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_cover_download(self.h, bits.ctypes.data_as(C.POINTER(C.c_uint64)), cov.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(tot), err, 512), err)
+        return bits[: self.n_words], cov[: self.n_unitigs], int(tot.value)
+
+    def device_ptr(self):
+        return int(self.L.fin_cover_device_bits(self.h) or 0)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fin_cover_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -678,6 +747,21 @@ class FinimizerIndex:
                                                      int(strands), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(npos), err, 512), err)
         return out[: self.n_unitigs], int(npos.value)
 
+    def cover(self, device=0):
+        """a zeroed coverage bitmap beside the replica on `device` (Cover)"""
+        return Cover(self, device)
+
+    def unitig_coverage(self, reads, strands=FIN_MERGED):
+        """the breadth of a read set over host buffers (fin_search_batch_unitig_coverage): (uint64 covered[n_unitigs], total_positive) -- how many DISTINCT
+        k-mers of each unitig were found, and the k-mers found as search_reads reports them; only the covered numbers come back from the device"""
+        bases, offsets = flatten(reads)
+        out = np.zeros(max(self.n_unitigs, 1), dtype=np.uint64)
+        npos = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_unitig_coverage(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+                                                       int(strands), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(npos), err, 512), err)
+        return out[: self.n_unitigs], int(npos.value)
+
     def search_reads_text(self, reads, strands=FIN_MERGED):
         """run_fmin_queries_streaming with its printed text as the result (fin_search_batch_text): (bytes, total_positive)"""
         bases, offsets = flatten(reads)
@@ -894,6 +978,19 @@ def records_unitig_counts(recs, stream, k, n_unitigs, n_threads=0):
     if rc != 0:
         raise FinitoError(rc, "fin_records_unitig_counts: a unitig number outside [0, n_unitigs), or records and stream do not belong together")
     return out[: int(n_unitigs)]
+
+
+def records_cover(recs, stream, k, ends, n_threads=0):
+    """fin_records_cover (host): the coverage bitmap uint64[(ends[-1] + 63) // 64] from records + stream, without making the pairs; `ends` as export(X_ENDS)"""
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE); stream = np.ascontiguousarray(stream, dtype=np.int32)
+    ends = np.ascontiguousarray(ends, dtype=np.int64)
+    n_words = (int(ends[-1]) + 63) // 64 if len(ends) else 0
+    out = np.zeros(max(n_words, 1), dtype=np.uint64)
+    rc = lib().fin_records_cover(recs.ctypes.data_as(C.c_void_p), len(recs), stream.ctypes.data_as(C.c_void_p), len(stream.reshape(-1, 2)), int(k),
+                                 ends.ctypes.data_as(C.POINTER(C.c_int64)), len(ends), out.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_cover: a unitig number outside the index, a k-mer that does not lie inside its unitig, or records and stream do not belong together")
+    return out[:n_words]
 
 
 def format_pairs(pairs):

@@ -93,7 +93,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_hits_combine, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_hits_combine, O_cover_probe, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -125,6 +125,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"pp_park", 1, 0, 1},                          // with the fused ingest: the reads of list A (both first looks failed) stay in LDS for phases 2 and 3 of the fast pre-pass, and only those they do not finish are written out; 0 = every read phase 1 does not finish is written out and read back (round 6)
     {"debug_pp_park_cap", -1, -1, 1024},           // tests: at most this many parked reads per pre-pass block (-1: as many as the LDS budget holds)
     {"hits_combine", 4, 0, 64},                    // fin_batch_add_hits: what a wave sums before an add goes to memory (fin_hits.hip) -- rounds in which the record lanes of one unitig merge, and the run held back between rows of pairs; 0 = every record lane and every run of a row adds by itself
+    {"cover_probe", 0, 0, 1},                      // fin_batch_add_cover: 1 = a lane loads the bitmap word first and skips the atomic OR when every bit it would set is set already (exact: bits are only ever set between resets, fin_cover.hip); 0 = always OR.  Measured (profiles/r09/cover.md): 1 wins behind text-mode-2 steps once the bitmap fills (0.83 against 1.14 ms on chr1), 0 behind default steps (4.0 against 5.0 ms) and summed over both
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -1257,29 +1258,52 @@ int fin_expand_records(const fin_read_record* recs, uint64_t n_reads, const int3
 }
 
 // ---- the profile over the unitig set (fin_hits.hip) ---------------------------------------------------------------------------------
+// what the download of a device accumulator (fin_hits, fin_cover) waits for: an event per stream that work on the accumulator was put on
+struct AccPending {
+    std::mutex mu; std::vector<std::pair<hipStream_t, hipEvent_t>> pending;
+    int mark(hipStream_t st, char* err, size_t errlen) {
+        std::lock_guard<std::mutex> g(mu);
+        for (auto& p : pending) if (p.first == st) { HIPCHK(hipEventRecord(p.second, st)); return FIN_OK; }
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        pending.push_back({st, ev});
+        HIPCHK(hipEventRecord(ev, st));
+        return FIN_OK;
+    }
+    int wait(char* err, size_t errlen) {
+        std::lock_guard<std::mutex> g(mu);
+        for (auto& p : pending) HIPCHK(hipEventSynchronize(p.second));
+        return FIN_OK;
+    }
+    void drop() { for (auto& p : pending) { (void)hipEventSynchronize(p.second); (void)hipEventDestroy(p.second); } pending.clear(); }
+};
+// behind the batch's most recent run, whichever stream it was launched on: what fin_batch_add_hits and fin_batch_add_cover check and order alike
+static int acc_behind_run(fin_batch* b, const fin_index* acc_idx, int acc_device, hipStream_t st, char* err, size_t errlen) {
+    if (!b->ran) { set_err(err, errlen, "this batch has not run: there are no hits to add (fin_batch_run first)"); return FIN_EINVAL; }
+    if (b->idx != acc_idx || b->device != acc_device) { set_err(err, errlen, "batch and accumulator belong to different indexes or devices"); return FIN_EINVAL; }
+    if (b->ovf_state == 2) { set_err(err, errlen, "the overflow list of this batch overran: results withheld"); return FIN_ELIMIT; }
+    HIPCHK(hipSetDevice(b->device));
+    if (st != b->last_stream) {
+        hipEvent_t ev = b->runs.back().e[4];
+        HIPCHK(hipStreamWaitEvent(st, ev, 0));
+    }
+    return FIN_OK;
+}
+
 struct fin_hits {
     const fin_index* idx = nullptr;
     int device = -1;
     uint64_t n_unitigs = 0;
     void* d_counts = nullptr;   // uint64[n_unitigs], then the flag word (fin_launch_hits_add)
-    // what fin_hits_download waits for: an event per stream that work on the counts was put on
-    std::mutex mu; std::vector<std::pair<hipStream_t, hipEvent_t>> pending;
+    AccPending pend;
 };
 static uint32_t* hits_flags(const fin_hits* h) { return (uint32_t*)((uint64_t*)h->d_counts + h->n_unitigs); }
-static int hits_mark(fin_hits* h, hipStream_t st, char* err, size_t errlen) {
-    std::lock_guard<std::mutex> g(h->mu);
-    for (auto& p : h->pending) if (p.first == st) { HIPCHK(hipEventRecord(p.second, st)); return FIN_OK; }
-    hipEvent_t ev = nullptr;
-    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    h->pending.push_back({st, ev});
-    HIPCHK(hipEventRecord(ev, st));
-    return FIN_OK;
-}
+static int hits_mark(fin_hits* h, hipStream_t st, char* err, size_t errlen) { return h->pend.mark(st, err, errlen); }
 
 void fin_hits_free(fin_hits* h) {
     if (!h) return;
     if (h->device >= 0) (void)hipSetDevice(h->device);
-    for (auto& p : h->pending) { (void)hipEventSynchronize(p.second); (void)hipEventDestroy(p.second); }
+    h->pend.drop();
     (void)hipFree(h->d_counts);
     delete h;
 }
@@ -1311,15 +1335,8 @@ void* fin_hits_device_counts(const fin_hits* h) { return h ? h->d_counts : nullp
 
 int fin_batch_add_hits(fin_batch* b, fin_hits* h, void* hip_stream, char* err, size_t errlen) {
     if (!b || !h) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    if (!b->ran) { set_err(err, errlen, "this batch has not run: there are no hits to add (fin_batch_run first)"); return FIN_EINVAL; }
-    if (b->idx != h->idx || b->device != h->device) { set_err(err, errlen, "batch and accumulator belong to different indexes or devices"); return FIN_EINVAL; }
-    if (b->ovf_state == 2) { set_err(err, errlen, "the overflow list of this batch overran: results withheld"); return FIN_ELIMIT; }
-    HIPCHK(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (st != b->last_stream) {   // behind the run, whichever stream it was launched on
-        hipEvent_t ev = b->runs.back().e[4];
-        HIPCHK(hipStreamWaitEvent(st, ev, 0));
-    }
+    if (const int brc = acc_behind_run(b, h->idx, h->device, st, err, errlen)) return brc;
     const int rc = fin_launch_hits_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, h->d_counts,
                                        (uint32_t)h->n_unitigs, hits_flags(h), b->d_ovf_count, b->last_ovf_cap, (uint32_t)optv(b->idx, O_hits_combine), st);
     if (rc != 0) { set_err(err, errlen, std::string("hits kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
@@ -1329,10 +1346,7 @@ int fin_batch_add_hits(fin_batch* b, fin_hits* h, void* hip_stream, char* err, s
 int fin_hits_download(fin_hits* h, uint64_t* counts_out, uint64_t* total, char* err, size_t errlen) {
     if (!h || (h->n_unitigs && !counts_out && !total)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     HIPCHK(hipSetDevice(h->device));
-    {
-        std::lock_guard<std::mutex> g(h->mu);
-        for (auto& p : h->pending) HIPCHK(hipEventSynchronize(p.second));
-    }
+    if (const int wrc = h->pend.wait(err, errlen)) return wrc;
     uint32_t flags = 0;
     HIPCHK(hipMemcpy(&flags, hits_flags(h), 4, hipMemcpyDeviceToHost));
     if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)"); return FIN_ELIMIT; }
@@ -1401,6 +1415,160 @@ int fin_records_unitig_counts(const fin_read_record* recs, uint64_t n_reads, con
                     if (hi + 1u > done_to) done_to = hi + 1u;
                 }
                 if (nk - gaps) add(R.u, nk - gaps);
+            }
+        }
+        ok = good && ok;
+    }
+    return ok ? FIN_OK : FIN_EINVAL;
+}
+
+// ---- breadth of coverage over the unitig text (fin_cover.hip) -------------------------------------------------------------------------
+struct fin_cover {
+    const fin_index* idx = nullptr;
+    int device = -1;
+    uint64_t n_unitigs = 0, total_len = 0, n_words = 0;
+    const uint32_t* d_ends = nullptr;   // the replica's ends_p
+    void* d_bits = nullptr;             // uint64[n_words], then the flag word (fin_launch_cover_add)
+    void* d_covered = nullptr;          // uint64[n_unitigs]: fin_cover_download's popcounts
+    std::mutex count_mu;                // one download at a time counts into d_covered
+    AccPending pend;
+};
+static uint32_t* cover_flags(const fin_cover* c) { return (uint32_t*)((uint64_t*)c->d_bits + c->n_words); }
+
+void fin_cover_free(fin_cover* c) {
+    if (!c) return;
+    if (c->device >= 0) (void)hipSetDevice(c->device);
+    c->pend.drop();
+    (void)hipFree(c->d_bits); (void)hipFree(c->d_covered);
+    delete c;
+}
+
+int fin_cover_create(const fin_index* idx, int device, fin_cover** out, char* err, size_t errlen) {
+    if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    const fin_index::Replica* rep = idx->replica_on(device);
+    if (!rep) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
+    HIPCHK(hipSetDevice(device));
+    fin_cover* c = new (std::nothrow) fin_cover();
+    if (!c) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
+    c->idx = idx; c->device = device; c->n_unitigs = idx->n_unitigs; c->total_len = idx->total_len; c->n_words = (idx->total_len + 63) / 64; c->d_ends = rep->dev.ends;
+    if (hipMalloc(&c->d_bits, c->n_words * 8 + 8) != hipSuccess) { (void)hipGetLastError(); delete c; set_err(err, errlen, "out of device memory (coverage bitmap)"); return FIN_ENOMEM; }
+    if (hipMemset(c->d_bits, 0, c->n_words * 8 + 8) != hipSuccess) { fin_cover_free(c); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    if (c->n_unitigs && hipMalloc(&c->d_covered, c->n_unitigs * 8) != hipSuccess) { (void)hipGetLastError(); c->d_covered = nullptr; fin_cover_free(c); set_err(err, errlen, "out of device memory (covered counts)"); return FIN_ENOMEM; }
+    *out = c;
+    return FIN_OK;
+}
+
+int fin_cover_reset(fin_cover* c, void* hip_stream) {
+    if (!c) return FIN_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return FIN_ENODEV;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (hipMemsetAsync(c->d_bits, 0, c->n_words * 8 + 8, st) != hipSuccess) return FIN_ENODEV;
+    return c->pend.mark(st, nullptr, 0);
+}
+
+void* fin_cover_device_bits(const fin_cover* c) { return c ? c->d_bits : nullptr; }
+
+int fin_batch_add_cover(fin_batch* b, fin_cover* c, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (const int brc = acc_behind_run(b, c->idx, c->device, st, err, errlen)) return brc;
+    const int rc = fin_launch_cover_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, c->d_ends,
+                                        (uint32_t)c->n_unitigs, c->total_len, c->d_bits, cover_flags(c), b->d_ovf_count, b->last_ovf_cap,
+                                        (uint32_t)optv(b->idx, O_cover_probe), st);
+    if (rc != 0) { set_err(err, errlen, std::string("cover kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    return c->pend.mark(st, err, errlen);
+}
+
+int fin_cover_download(fin_cover* c, uint64_t* bits_out, uint64_t* covered_out, uint64_t* total_covered, char* err, size_t errlen) {
+    if (!c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int wrc = c->pend.wait(err, errlen)) return wrc;
+    uint32_t flags = 0;
+    HIPCHK(hipMemcpy(&flags, cover_flags(c), 4, hipMemcpyDeviceToHost));
+    if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: it has no results, nothing of it was set (reset the accumulator)"); return FIN_ELIMIT; }
+    if (flags & 2u) { set_err(err, errlen, "a pair with a unitig number or a position outside the index was met (not set)"); return FIN_EINVAL; }
+    if (bits_out && c->n_words) HIPCHK(hipMemcpy(bits_out, c->d_bits, c->n_words * 8, hipMemcpyDeviceToHost));
+    if (covered_out || total_covered) {
+        std::vector<uint64_t> tmp;
+        uint64_t* dst = covered_out;
+        if (!dst) { tmp.resize((size_t)c->n_unitigs); dst = tmp.data(); }
+        if (c->n_unitigs) {
+            std::lock_guard<std::mutex> g(c->count_mu);
+            const int rc = fin_launch_cover_count(c->d_bits, c->d_ends, (uint32_t)c->n_unitigs, c->total_len, c->d_covered, nullptr);
+            if (rc != 0) { set_err(err, errlen, std::string("cover count kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+            HIPCHK(hipMemcpy(dst, c->d_covered, c->n_unitigs * 8, hipMemcpyDeviceToHost));   // (the null stream: behind the kernel)
+        }
+        if (total_covered) { uint64_t t = 0; for (uint64_t u = 0; u < c->n_unitigs; u++) t += dst[u]; *total_covered = t; }
+    }
+    return FIN_OK;
+}
+
+// host: the bitmap from records + stream -- fin_expand_records' arithmetic, the pairs never made.  A chunk of reads per thread; with more than one thread
+// the words are ORed atomically
+int fin_records_cover(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
+                      uint64_t n_unitigs, uint64_t* bits_out, int n_threads) {
+    if ((n_reads && !recs) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && (!unitig_ends || !bits_out))) return FIN_EINVAL;
+    int64_t prev = 0;
+    for (uint64_t u = 0; u < n_unitigs; u++) { if (unitig_ends[u] < prev) return FIN_EINVAL; prev = unitig_ends[u]; }
+    const uint64_t total_len = (uint64_t)prev, n_words = (total_len + 63) / 64;
+    for (uint64_t w = 0; w < n_words; w++) bits_out[w] = 0;
+    int T = n_threads > 0 ? n_threads : fin_host_threads();
+    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
+    std::vector<uint64_t> str0((size_t)T + 1, 0);
+    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
+        const auto lh = bounds(t);
+        uint64_t sp = 0;
+        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
+        str0[(size_t)t + 1] = sp;
+    }
+    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
+    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
+    bool ok = true;
+#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
+    for (int t = 0; t < T; t++) {
+        const auto lh = bounds(t);
+        uint64_t sp = str0[(size_t)t];
+        bool good = true;
+        // offsets [off_lo, off_hi) of unitig u, each the first base of a found k-mer: it must lie whole inside the unitig
+        auto set = [&](uint64_t u, uint64_t off_lo, uint64_t off_hi) {
+            if (off_lo >= off_hi) return;
+            if (u >= n_unitigs) { good = false; return; }
+            const uint64_t start = u ? (uint64_t)unitig_ends[u - 1] : 0, end = (uint64_t)unitig_ends[u];
+            if (start + off_hi - 1 + (uint64_t)k > end) { good = false; return; }
+            const uint64_t g0 = start + off_lo, g1 = start + off_hi;
+            for (uint64_t w = g0 >> 6; (w << 6) < g1; w++) {
+                const uint64_t wb = w << 6, lo = g0 > wb ? g0 : wb, hi = g1 < wb + 64 ? g1 : wb + 64;
+                const uint64_t m = (~0ull >> (64 - (hi - lo))) << (lo - wb);
+                if (T == 1) bits_out[w] |= m;
+                else __atomic_fetch_or(bits_out + w, m, __ATOMIC_RELAXED);
+            }
+        };
+        for (uint64_t r = lh.first; r < lh.second && good; r++) {
+            const fin_read_record& R = recs[r];
+            const uint32_t nk = R.nk, kind = R.meta >> 16;
+            if (kind == 0u) {
+                const int32_t* const src = stream_pairs + 2 * sp;
+                for (uint32_t i = 0; i < nk; i++) {
+                    const int32_t u = src[2 * i], off = src[2 * i + 1];
+                    if (u >= 0 && off >= 0) set((uint64_t)u, (uint64_t)off, (uint64_t)off + 1);
+                    else if (u != -1) good = false;
+                }
+                sp += nk;
+            } else if (kind == 1u && nk) {
+                const uint32_t nE = R.meta & 0xFFu;
+                uint32_t done_to = 0, from = 0;   // `from`: where the found stretch in front of the next gap begins
+                for (uint32_t e = 0; e < nE && e < 8u; e++) {
+                    const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
+                    uint32_t lo = E >= (uint32_t)(k - 1) ? E - (uint32_t)(k - 1) : 0u, hi = E < nk ? E : nk - 1u;
+                    if (lo < done_to) lo = done_to;
+                    if (lo <= hi) { set(R.u, (uint64_t)R.off0 + from, (uint64_t)R.off0 + lo); from = hi + 1u; }
+                    if (hi + 1u > done_to) done_to = hi + 1u;
+                }
+                set(R.u, (uint64_t)R.off0 + from, (uint64_t)R.off0 + nk);
             }
         }
         ok = good && ok;
@@ -1496,6 +1664,7 @@ struct TextSink {
     fin_read_record* recs = nullptr; int32_t* rpairs = nullptr; uint64_t rcap = 0; uint64_t read0 = 0;
     char* buf = nullptr; uint64_t cap = 0;
     fin_hits* hits = nullptr;   // the profile instead of text (fin_search_batch_unitig_counts): every sub-batch is added on the device, nothing comes back
+    fin_cover* cover = nullptr; // the coverage bitmap (fin_search_batch_add_cover); with `hits` too, both adds go behind the same run
     std::vector<uint64_t> len; std::vector<char> known;
     std::mutex mu; std::condition_variable cv;
     uint64_t total = 0;
@@ -1564,9 +1733,10 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
             }
             if (rc == FIN_OK) { b->text_mode = ts ? 2 : 0; rc = fin_batch_run(b, strands, (void*)b->own_stream, e, sizeof e); }   // (text sink: the text is the only product)
             uint64_t pos = 0;
-            if (rc == FIN_OK && ts && ts->hits) {
+            if (rc == FIN_OK && ts && (ts->hits || ts->cover)) {
                 // (behind the run on the batch's own stream: the next batch_load on that stream finds the add done; fin_hits_download waits for the last ones)
-                rc = fin_batch_add_hits(b, ts->hits, (void*)b->own_stream, e, sizeof e);
+                if (ts->hits) rc = fin_batch_add_hits(b, ts->hits, (void*)b->own_stream, e, sizeof e);
+                if (rc == FIN_OK && ts->cover) rc = fin_batch_add_cover(b, ts->cover, (void*)b->own_stream, e, sizeof e);
             } else
             if (rc == FIN_OK && ts && ts->recs) {
                 // records: the sub-batch's stream of pairs lands behind the streams of all earlier sub-batches, its records at its reads' numbers
@@ -1730,6 +1900,34 @@ int fin_search_batch_unitig_counts(const fin_index* idx, const char* bases, cons
     rc = fin_search_batch_add_hits(idx, bases, offsets, n_reads, strands, h, err, errlen);
     if (rc == FIN_OK) rc = fin_hits_download(h, counts_out, n_positive, err, errlen);
     fin_hits_free(h);
+    return rc;
+}
+
+int fin_search_batch_add_cover(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_cover* c, char* err, size_t errlen) {
+    if (!idx || !offsets || !c || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (c->idx != idx) { set_err(err, errlen, "the accumulator belongs to another index"); return FIN_EINVAL; }
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.cover = c;
+    return search_range_on(idx, c->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+}
+
+int fin_search_batch_unitig_coverage(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint64_t* covered_out,
+                                     uint64_t* n_positive, char* err, size_t errlen) {
+    if (!idx || !offsets || (idx->n_unitigs && !covered_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (n_positive) *n_positive = 0;
+    const int device = idx->replicas[0].device;
+    fin_cover* c = nullptr;
+    fin_hits* h = nullptr;   // the found k-mers are a sum of depths, which the bitmap does not hold: asked for, they come from a profile added behind the same runs
+    int rc = fin_cover_create(idx, device, &c, err, errlen);
+    if (rc == FIN_OK && n_positive) rc = fin_hits_create(idx, device, &h, err, errlen);
+    if (rc == FIN_OK && n_reads) {
+        TextSink ts; ts.cover = c; ts.hits = h;
+        rc = search_range_on(idx, device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+    }
+    if (rc == FIN_OK) rc = fin_cover_download(c, nullptr, covered_out, nullptr, err, errlen);
+    if (rc == FIN_OK && h) rc = fin_hits_download(h, nullptr, n_positive, err, errlen);
+    fin_hits_free(h); fin_cover_free(c);
     return rc;
 }
 

@@ -122,6 +122,14 @@ int fin_launch_rec_compact(void* frec, const uint64_t* out_offs, const void* pai
 // accumulator (bit 0: the step's overflow list overran -- nothing added; bit 1: a unitig number >= n_unitigs met -- not added).  combine: option "hits_combine"
 int fin_launch_hits_add(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint64_t n_pairs, uint32_t k, void* counts,
                         uint32_t n_unitigs, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t combine, hipStream_t stream);
+// fin_cover.hip: bits[ends_p[u] + off] |= 1 for every found pair (u, off) of a finished step -- one bit per base of the unitig text, uint64 words.  frec / out_offs /
+// pairs / ovf_count / ovf_cap as fin_launch_hits_add.  flags: one u32 of the accumulator (bit 0: the step's overflow list overran -- nothing set; bit 1: a unitig
+// number >= n_unitigs or a position >= total_len met -- skipped).  probe: option "cover_probe" (load the word first, skip the atomic OR when nothing would change)
+int fin_launch_cover_add(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint64_t n_pairs, uint32_t k, const uint32_t* ends_p,
+                         uint32_t n_unitigs, uint64_t total_len, void* bits, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t probe,
+                         hipStream_t stream);
+// covered[u] = popcount of unitig u's stretch of the bitmap (uint64[n_unitigs], zeroed here on `stream`)
+int fin_launch_cover_count(const void* bits, const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len, void* covered, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

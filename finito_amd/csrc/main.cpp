@@ -446,7 +446,14 @@ static const char* SEARCH_HELP =
     "      --unitig-counts FILE  also write the run's profile over the unitig set: one line `unitig<TAB>count` per unitig of the index, in\n"
     "                        unitig order, zeros included -- how many query k-mers (both strands merged, all query files) were found in it.\n"
     "                        Counted on the first GPU, nothing per k-mer comes back for it. Not for a partitioned index.\n"
-    "      --no-text arg     1 (only with --unitig-counts): do not make or write the pair text, the profile is the only result\n"
+    "      --unitig-coverage FILE  also write the run's breadth over the unitig set: one line `unitig<TAB>kmers<TAB>covered` per unitig of the\n"
+    "                        index, in unitig order -- kmers = length - k + 1, covered = how many DISTINCT k-mers of the unitig were found (a\n"
+    "                        bitmap on the first GPU, one bit per base of the unitig text). Goes with --unitig-counts. Not for a partitioned index.\n"
+    "                        Costs one more search of every chunk on the device, beside the one for the text and the one for\n"
+    "                        --unitig-counts; with --no-text 1 and no --unitig-counts a chunk is still searched twice (the second\n"
+    "                        pass counts the found k-mers the log reports).\n"
+    "      --no-text arg     1 (only with --unitig-counts or --unitig-coverage): do not make or write the pair text, the profile and / or the\n"
+    "                        coverage are the only results\n"
     "  -h, --help            Print usage\n";
 
 static int build_fmin(int argc, char** argv) {
@@ -614,7 +621,13 @@ struct OutSink {   // regular files are written by all threads at once, anything
 static bool g_strand_counts = false;
 // --unitig-counts FILE: every chunk's hits are added into one accumulator on the first device (fin_search_batch_add_hits), downloaded once after the last
 // chunk; --no-text 1: that is all a chunk is searched for
-static fin_hits* g_hits = nullptr;
+static fin_hits* g_hits = nullptr;   // (with --no-text 1 there is one even without --unitig-counts: its sum is the run's found k-mers)
+// --unitig-coverage FILE: the same for the coverage bitmap (fin_search_batch_add_cover)
+static fin_cover* g_cover = nullptr;
+static void add_cover_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
+    char err[512] = {0};
+    if (fin_search_batch_add_cover(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
+}
 static bool g_no_text = false;
 static uint64_t g_hits_total = 0;   // the accumulator's sum after the previous query file
 
@@ -690,7 +703,10 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         const int64_t len = (int64_t)(c->offsets[r + 1] - c->offsets[r]);
                         c->pair_off[r + 1] = c->pair_off[r] + (uint64_t)(len >= k ? len - k + 1 : 0);
                     }
-                    if (g_no_text) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);   // the profile is all this chunk is searched for
+                    if (g_no_text) {   // the profile / the coverage is all this chunk is searched for
+                        index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);
+                        if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                    }
                     else {
                         // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
                         if (!c->text) {
@@ -704,6 +720,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                             index.search_batch_into(c->bases.get(0), c->offsets.data(), n_reads, pairs, c->positive);
                         }
                         if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);   // (a second pass over the chunk on the device: the text is what bounds this loop)
+                        if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                     }
                     if (g_strand_counts) {
                         c->positive_fwd = index.count_found_one_strand(c->bases.get(0), c->offsets.data(), n_reads);
@@ -819,11 +836,11 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts")) throw runtime_error("--no-text 1 is only legal together with --unitig-counts (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage")) throw runtime_error("--no-text 1 is only legal together with --unitig-counts or --unitig-coverage (the run would have no result)");
     if (g_no_text && g_strand_counts) throw runtime_error("--no-text 1 and --strand-counts 1 do not go together");
     if (!o.has("query-file")) throw runtime_error("Option 'query-file' has no value");
     if (!o.has("index-file")) throw runtime_error("Option 'index-file' has no value");
@@ -844,6 +861,8 @@ static int search_fmin(int argc, char** argv) {
     string index_prefix = o.get("index-file");
     const string counts_file = o.get("unitig-counts", "");
     if (!counts_file.empty()) check_writable(counts_file);
+    const string cover_file = o.get("unitig-coverage", "");
+    if (!cover_file.empty()) check_writable(cover_file);
     cerr << "Loading index..." << endl;
     const int first_dev = stoi(o.get("device", "0"));
     // beside the index load: page-lock the pipeline's buffers (four chunks of 48 MB of bases and of up to 16 bytes of text per k-mer)
@@ -880,11 +899,17 @@ static int search_fmin(int argc, char** argv) {
     index.load(index_prefix);
     const int64_t t_l1 = cur_time_micros();
     if (!counts_file.empty() && index.partitioned()) throw runtime_error("--unitig-counts is not available with a partitioned index");
+    if (!cover_file.empty() && index.partitioned()) throw runtime_error("--unitig-coverage is not available with a partitioned index");
     index.to_device();
     struct HitsOwner { ~HitsOwner() { fin_hits_free(g_hits); g_hits = nullptr; } } hits_owner;
-    if (!counts_file.empty()) {
+    if (!counts_file.empty() || g_no_text) {
         char err[512] = {0};
         if (fin_hits_create(index.handle(), first_dev, &g_hits, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    }
+    struct CoverOwner { ~CoverOwner() { fin_cover_free(g_cover); g_cover = nullptr; } } cover_owner;
+    if (!cover_file.empty()) {
+        char err[512] = {0};
+        if (fin_cover_create(index.handle(), first_dev, &g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
@@ -906,7 +931,25 @@ static int search_fmin(int argc, char** argv) {
             number_of_queries += run_fmin_queries_streaming(&reader, nullptr, out, index, index_prefix + ".stats");
         }
     }
-    if (g_hits) {   // the profile, after the last chunk: one line per unitig of the index
+    if (g_cover) {   // the coverage, after the last chunk: one line per unitig of the index
+        char err[512] = {0};
+        const size_t nu = (size_t)index.number_of_unitigs();
+        vector<uint64_t> covered(nu + 1);
+        vector<int64_t> ends(nu + 1);
+        if (fin_cover_download(g_cover, nullptr, covered.data(), nullptr, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        if (fin_index_export(index.handle(), FIN_X_ENDS, ends.data(), nu * sizeof(int64_t), err, sizeof err) != FIN_OK) throw runtime_error(err);
+        const int64_t k = index.get_k();
+        string text;
+        text.reserve(nu * 20);
+        for (size_t u = 0; u < nu; u++) {
+            const int64_t len = ends[u] - (u ? ends[u - 1] : 0);
+            text += to_string(u); text += '\t'; text += to_string(len - k + 1); text += '\t'; text += to_string(covered[u]); text += '\n';
+        }
+        ofstream cf(cover_file, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + cover_file);
+    }
+    if (g_hits && !counts_file.empty()) {   // the profile, after the last chunk: one line per unitig of the index
         char err[512] = {0};
         vector<uint64_t> counts((size_t)index.number_of_unitigs() + 1);
         if (fin_hits_download(g_hits, counts.data(), nullptr, err, sizeof err) != FIN_OK) throw runtime_error(err);

@@ -453,6 +453,49 @@ int fin_search_batch_add_hits(const fin_index* idx, const char* bases, const uin
 int fin_records_unitig_counts(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t n_unitigs,
                               uint64_t* counts_out, int n_threads);
 
+/* ---- BREADTH of a run over the unitig set: which k-mers of each unitig were found, as a bitmap in HBM ----
+ * fin_hits counts how often a unitig was hit (depth); containment and "present if at least x % of its k-mers were seen" rules need how many DISTINCT k-mers of
+ * the unitig were seen, and which.  The bitmap covers the concatenated unitig text and has fin_index_total_len bits.  A found pair (u, off) sets bit
+ * g = start(u) + off, where start(u) is unitigs.ends[u - 1] of FIN_X_ENDS (0 for u = 0; ends_p[u] on the device).  Position g is bit g & 63 of uint64 word
+ * g >> 6.  Consequences:
+ *  - the last k - 1 positions of every unitig are never set: no k-mer begins there;
+ *  - covered[u] = popcount(bits[start(u) .. start(u + 1))) is at most len(u) - k + 1;
+ *  - on a set that is not disjoint only the place the reference reports for a k-mer is ever set, the other copy stays 0 (as fin_hits counts a k-mer in the copy
+ *    that is the reference's choice);
+ *  - adding the same run twice changes nothing: OR is idempotent (fin_hits counts it twice).
+ * fin_batch_add_cover launches one kernel behind the batch's most recent run (fin_cover.hip): a read the fast path finished sets its bits from
+ * its 32-byte record, a mask and one atomic OR per 64-bit word it touches; the other reads' pairs are scanned in place, a run of consecutive offsets -- ascending
+ * or descending -- one OR per word.  Option "cover_probe" (default 0; 1: the word is loaded first and the atomic skipped when it would change nothing -- faster behind text-mode-2 steps into a bitmap that has filled, slower behind default steps).
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi, ORing across the ranks of a job (a caller with several GPUs keeps an accumulator per
+ * replica and ORs the downloaded bitmaps), per-position depth, the C++ mirror (FinimizerIndex.hh). */
+typedef struct fin_cover fin_cover;
+/* a zeroed bitmap for `idx` on `device` (FIN_ENODEV: the index has no replica there) */
+int fin_cover_create(const fin_index* idx, int device, fin_cover** out, char* err, size_t errlen);
+/* zeroes the bitmap, on the given stream */
+int fin_cover_reset(fin_cover* c, void* hip_stream);
+/* bits |= the found places of the batch's most recent run, on the given stream, ordered behind that run; does not wait.  Same ordering and refusal rules as
+ * fin_batch_add_hits: FIN_EINVAL when the batch has not run or batch and accumulator belong to different indexes or devices; records, pairs and text are read
+ * only; a run whose overflow list overran sets nothing and fin_cover_download reports FIN_ELIMIT until the reset. */
+int fin_batch_add_cover(fin_batch* b, fin_cover* c, void* hip_stream, char* err, size_t errlen);
+/* uint64[(fin_index_total_len + 63) / 64] in HBM (valid once the adds on their streams have finished) */
+void* fin_cover_device_bits(const fin_cover* c);
+/* waits for every add and reset issued so far.  bits_out[(total_len + 63) / 64], covered_out[fin_index_n_unitigs] (a popcount kernel over the bitmap, run here),
+ * *total_covered = the sum of covered = the distinct k-mers found; each may be NULL */
+int fin_cover_download(fin_cover* c, uint64_t* bits_out, uint64_t* covered_out, uint64_t* total_covered, char* err, size_t errlen);
+/* fin_search_batch_add_hits' loop with the bitmap as its product: host buffers in, sub-batches pipelined, each run in text mode 2 where the fast path is on,
+ * nothing downloaded */
+int fin_search_batch_add_cover(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_cover* c, char* err, size_t errlen);
+/* host buffers in, covered_out[fin_index_n_unitigs] out (a fresh bitmap on the first replica's device); *n_positive (may be NULL) = the k-mers found, as
+ * fin_search_batch reports it -- a sum of depths, taken from a fin_hits profile added behind the same runs when it is asked for */
+int fin_search_batch_unitig_coverage(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint64_t* covered_out,
+                                     uint64_t* n_positive, char* err, size_t errlen);
+void fin_cover_free(fin_cover* c);
+/* host, no device: the same bitmap from records + stream (the arithmetic of fin_expand_records, the pairs never made).  unitig_ends[n_unitigs] as FIN_X_ENDS;
+ * bits_out[(unitig_ends[n_unitigs - 1] + 63) / 64] is overwritten.  n_threads <= 0: all cores.  FIN_EINVAL: a unitig number >= n_unitigs, a k-mer that does not lie
+ * inside its unitig, or a stream that is not this record set's */
+int fin_records_cover(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
+                      uint64_t n_unitigs, uint64_t* bits_out, int n_threads);
+
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
  * k-mer is in no unitig), 1 a verified claim, 2 an unverified one (| 8: the exact side table has the k-mer, g is its answer), | 4 the text at [g-k+1, g] spells
