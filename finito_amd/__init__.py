@@ -166,6 +166,15 @@ def lib():
         L.fin_search_batch_add_cover.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
         L.fin_search_batch_unitig_coverage.argtypes = [vp, cp, u64p, u64, C.c_int, u64p, u64p, cp, C.c_size_t]
         L.fin_records_cover.argtypes = [vp, u64, vp, u64, C.c_int, i64p, u64, u64p, C.c_int]
+        L.fin_batch_segments.argtypes = [vp, u64p, cp, C.c_size_t]
+        L.fin_batch_device_segments.argtypes = [vp]
+        L.fin_batch_device_segments.restype = vp
+        L.fin_batch_device_segment_offsets.argtypes = [vp]
+        L.fin_batch_device_segment_offsets.restype = vp
+        L.fin_batch_download_segments.argtypes = [vp, u64p, vp, cp, C.c_size_t]
+        L.fin_search_batch_segments.argtypes = [vp, cp, u64p, u64, C.c_int, u64p, vp, u64, u64p, u64p, cp, C.c_size_t]
+        L.fin_expand_segments.argtypes = [u64p, vp, u64, vp, vp, u64p, C.c_int]
+        L.fin_records_segments.argtypes = [vp, u64, vp, u64, C.c_int, u64p, vp, u64, u64p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -312,6 +321,21 @@ class Batch:
 
     def device_pairs_ptr(self):
         return int(self.L.fin_batch_device_pairs(self.h) or 0)
+
+    def segments(self):
+        """the most recent run's results as segments, made on the device (fin_batch_segments + fin_batch_download_segments): (seg_offs uint64[n_reads + 1],
+        segs SEGMENT_DTYPE[n_segments]) -- read r's segments are segs[seg_offs[r]:seg_offs[r + 1]]"""
+        n = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_segments(self.h, C.byref(n), err, 512), err)
+        seg_offs = np.zeros(self.n_reads + 1, dtype=np.uint64)
+        segs = np.zeros(max(int(n.value), 1), dtype=SEGMENT_DTYPE)
+        _check(self.L.fin_batch_download_segments(self.h, seg_offs.ctypes.data_as(C.POINTER(C.c_uint64)), segs.ctypes.data_as(C.c_void_p), err, 512), err)
+        return seg_offs, segs[: int(n.value)]
+
+    def device_segments_ptr(self):
+        """(segments, seg_offs) device pointers, 0 before segments()"""
+        return int(self.L.fin_batch_device_segments(self.h) or 0), int(self.L.fin_batch_device_segment_offsets(self.h) or 0)
 
     def pipeline_counts(self, n=64):
         """kernel 4's queue counters of the last run (fin_batch_pipeline_counts)"""
@@ -732,6 +756,20 @@ class FinimizerIndex:
                                                recs.ctypes.data_as(C.c_void_p), stream.ctypes.data_as(C.c_void_p), nk, C.byref(got), err, 512), err)
         return recs, stream[: int(got.value)]
 
+    def search_reads_segments(self, reads, strands=FIN_MERGED):
+        """fin_search_batch_segments: (seg_offs uint64[n_reads + 1], segs SEGMENT_DTYPE[n_segments], n_positive) -- every read's found stretches inside a
+        unitig, made on the device; nothing per k-mer comes back"""
+        bases, offsets = flatten(reads)
+        n = len(offsets) - 1
+        nk = int(np.maximum(np.diff(offsets.astype(np.int64)) - self.k + 1, 0).sum())
+        seg_offs = np.zeros(n + 1, dtype=np.uint64)
+        segs = np.zeros(max(nk, 1), dtype=SEGMENT_DTYPE)
+        got, npos = C.c_uint64(0), C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_segments(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands),
+                                                seg_offs.ctypes.data_as(C.POINTER(C.c_uint64)), segs.ctypes.data_as(C.c_void_p), nk, C.byref(got), C.byref(npos), err, 512), err)
+        return seg_offs, segs[: int(got.value)].copy(), int(npos.value)
+
     def hits(self, device=0):
         """a zeroed per-unitig accumulator beside the replica on `device` (Hits)"""
         return Hits(self, device)
@@ -806,6 +844,7 @@ class FinimizerIndex:
 
 
 RECORD_DTYPE = np.dtype([("u", np.uint32), ("off0", np.uint32), ("meta", np.uint32), ("nk", np.uint32), ("Es", np.uint64), ("Es2", np.uint64)])
+SEGMENT_DTYPE = np.dtype([("u", np.int32), ("off", np.int32), ("slot", np.uint32), ("len", np.int32)])   # fin_segment
 
 
 class PartitionedBatch:
@@ -991,6 +1030,38 @@ def records_cover(recs, stream, k, ends, n_threads=0):
     if rc != 0:
         raise FinitoError(rc, "fin_records_cover: a unitig number outside the index, a k-mer that does not lie inside its unitig, or records and stream do not belong together")
     return out[:n_words]
+
+
+def expand_segments(seg_offs, segs, nk_per_read, n_threads=0):
+    """fin_expand_segments (host): the pairs fin_search_batch delivers, from segments; nk_per_read[r] = max(0, length of read r - k + 1); returns (pairs, n_positive)"""
+    seg_offs = np.ascontiguousarray(seg_offs, dtype=np.uint64); segs = np.ascontiguousarray(segs, dtype=SEGMENT_DTYPE)
+    nks = np.ascontiguousarray(nk_per_read, dtype=np.uint32)
+    if len(seg_offs) != len(nks) + 1 or (len(seg_offs) and int(seg_offs[-1]) > len(segs)):
+        raise FinitoError(FIN_EINVAL, "expand_segments: seg_offs does not fit the reads or the segments")
+    nk = int(nks.astype(np.int64).sum())
+    out = np.empty((max(nk, 1), 2), dtype=np.int32)
+    pos = C.c_uint64(0)
+    rc = lib().fin_expand_segments(seg_offs.ctypes.data_as(C.POINTER(C.c_uint64)), segs.ctypes.data_as(C.c_void_p), len(nks), nks.ctypes.data_as(C.c_void_p),
+                                   out.ctypes.data_as(C.c_void_p), C.byref(pos), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_expand_segments: a segment outside its read, overlapping or unsorted segments, a segment of length 0 or with a negative offset")
+    return out[:nk], int(pos.value)
+
+
+def records_segments(recs, stream, k, seg_cap=None, n_threads=0):
+    """fin_records_segments (host): the canonical segments (seg_offs, segs) from records + stream, without making the pairs; seg_cap: room for that many
+    segments (default: the record set's number of k-mers, which always suffices)"""
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE); stream = np.ascontiguousarray(stream, dtype=np.int32)
+    cap = int(recs["nk"].astype(np.int64).sum()) if seg_cap is None else int(seg_cap)
+    seg_offs = np.zeros(len(recs) + 1, dtype=np.uint64)
+    segs = np.zeros(max(cap, 1), dtype=SEGMENT_DTYPE)
+    n = C.c_uint64(0)
+    rc = lib().fin_records_segments(recs.ctypes.data_as(C.c_void_p), len(recs), stream.ctypes.data_as(C.c_void_p), len(stream.reshape(-1, 2)), int(k),
+                                    seg_offs.ctypes.data_as(C.POINTER(C.c_uint64)), segs.ctypes.data_as(C.c_void_p), cap, C.byref(n), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_segments: %s" % ("room for %d segments, %d needed" % (cap, n.value) if rc == FIN_ELIMIT else
+                                                            "records and stream do not belong together, or a pair that is neither found nor (-1,-1)"))
+    return seg_offs, segs[: int(n.value)].copy()
 
 
 def format_pairs(pairs):

@@ -683,6 +683,9 @@ struct fin_batch {
     int text_mode = 0; bool last_frec = false, last_text_only = false, count_from_text = false;
     // records (fin_batch_records): the dense stream of the pairs of the reads the fast path did not finish
     void* d_cstream = nullptr; size_t cap_cstream = 0; uint64_t rec_stream_pairs = 0; bool rec_ready = false, rec_passthrough = false;
+    // segments (fin_batch_segments): per-read counts, block sums and offsets, seg_offs[n_reads + 1] and the segments; kept and only grown
+    void* d_sgm_cnt = nullptr; void* d_sgm_bsum = nullptr; void* d_sgm_boff = nullptr; void* d_sgm_offs = nullptr; void* d_sgm = nullptr;
+    size_t cap_sgm_cnt = 0, cap_sgm_bsum = 0, cap_sgm_boff = 0, cap_sgm_offs = 0, cap_sgm = 0; uint64_t n_segments = 0; bool sgm_ready = false;
     uint64_t text_bytes = 0;
     // kernel 4: the queue counters of the most recent finished run, copied to page-locked memory behind every run: the next run launches only
     // as many stream / walk rounds as that one needed, plus one (fin_launch_search_v4's `rounds`)
@@ -717,6 +720,7 @@ void fin_batch_free(fin_batch* b) {
     if (b->h_ctr) (void)hipHostFree(b->h_ctr);
     if (b->ev_ctr) (void)hipEventDestroy(b->ev_ctr);
     (void)hipFree(b->d_cstream); (void)hipFree(b->d_frec); (void)hipFree(b->d_seg); (void)hipFree(b->d_text); (void)hipFree(b->d_last_bits); (void)hipFree(b->d_blk_sum); (void)hipFree(b->d_blk_off); (void)hipFree(b->d_total);
+    (void)hipFree(b->d_sgm_cnt); (void)hipFree(b->d_sgm_bsum); (void)hipFree(b->d_sgm_boff); (void)hipFree(b->d_sgm_offs); (void)hipFree(b->d_sgm);
     (void)hipFree(b->d_ovf_list); (void)hipFree(b->d_ovf_count); (void)hipFree(b->d_ovf_scratch); (void)hipFree(b->d_count);
     for (auto& r : b->runs) for (auto& e : r.e) (void)hipEventDestroy(e);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -840,7 +844,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     //  decoding, inside its timed region, search_fmin.hh:46-71 -- is the first kernel of every step, see fin_batch_run)
     b->n_chunks = n_chunks; b->max_read_len = max_len;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "upload");
-    b->ran = false; b->last_stream = nullptr;
+    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false;
     b->rounds_hint = 0; b->ctr_pending = false;   // (new reads: nothing is known about the rounds they need)
     b->text_reads_state = 0;
     return FIN_OK;
@@ -884,7 +888,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     b->dev.budget_mult = (uint32_t)optv(b->idx, O_epoch_budget_mult); b->dev.budget_add = (uint32_t)optv(b->idx, O_epoch_budget_add);
     b->dev.ovf_cap = (uint32_t)std::min<uint64_t>(b->cap_ovf_list / 4, 0xFFFFFFFFull);
     if (const int64_t forced = optv(b->idx, O_debug_ovf_cap)) b->dev.ovf_cap = (uint32_t)std::min<int64_t>(forced, (int64_t)b->dev.ovf_cap);   // (tests: a tiny list)
-    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false;
+    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false;
     b->dev.pp_seg = (uint32_t)optv(b->idx, O_debug_pp_seg);
     b->dev.pp_max_len = (uint32_t)std::min<uint64_t>(b->max_read_len, 0xFFFFFFFFull);
     b->dev.pp_park = (uint32_t)optv(b->idx, O_pp_park);
@@ -1009,7 +1013,7 @@ int fin_batch_set_pairs(fin_batch* b, const int32_t* pairs, char* err, size_t er
     HIPCHK(hipSetDevice(b->device));
     if (b->last_stream) HIPCHK(hipStreamSynchronize(b->last_stream));
     HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
-    b->last_frec = false; b->last_text_only = false; b->count_from_text = false;   // (the records of the last run say nothing about these pairs)
+    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false;   // (the records of the last run say nothing about these pairs)
     return FIN_OK;
 }
 
@@ -1253,6 +1257,214 @@ int fin_expand_records(const fin_read_record* recs, uint64_t n_reads, const int3
 #pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
     for (int t = 0; t < T; t++) ok = pass(t, true) && ok;
     if (!ok) return FIN_EINVAL;
+    if (n_positive) { uint64_t f = 0; for (uint64_t x : pos) f += x; *n_positive = f; }
+    return FIN_OK;
+}
+
+// ---- results as segments (fin_segments.hip) ---------------------------------------------------------------------------------------
+static_assert(sizeof(fin_segment) == 16, "a segment is 16 bytes");
+
+int fin_batch_segments(fin_batch* b, uint64_t* n_segments, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null batch"); return FIN_EINVAL; }
+    if (!b->ran) { set_err(err, errlen, "this batch has not run: there is nothing to make segments of (fin_batch_run first)"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    b->sgm_ready = false;
+    if (b->n_kmers == 0) {   // no read has a k-mer (the step searched nothing: there is no overflow list to look at): every read owns no segment
+        if (batch_grow(b, &b->d_sgm_offs, b->cap_sgm_offs, (size_t)b->n_reads * 8 + 8, st)) { set_err(err, errlen, "out of device memory (segment tables)"); return FIN_ENOMEM; }
+        HIPCHK(hipMemsetAsync(b->d_sgm_offs, 0, (size_t)b->n_reads * 8 + 8, st));
+        HIPCHK(hipStreamSynchronize(st));
+        b->n_segments = 0; b->sgm_ready = true;
+        if (n_segments) *n_segments = 0;
+        return FIN_OK;
+    }
+    if (const int orc = batch_overrun_check(b, st, err, errlen)) return orc;   // a run without results: nothing is written
+    const uint32_t nr = (uint32_t)b->n_reads, nb = fin_sgm_blocks(nr);
+    if (batch_grow(b, &b->d_sgm_offs, b->cap_sgm_offs, (size_t)nr * 8 + 8, st) || batch_grow(b, &b->d_sgm_cnt, b->cap_sgm_cnt, (size_t)nr * 4 + 4, st) ||
+        batch_grow(b, &b->d_sgm_bsum, b->cap_sgm_bsum, (size_t)nb * 4 + 4, st) || batch_grow(b, &b->d_sgm_boff, b->cap_sgm_boff, (size_t)nb * 8 + 8, st)) {
+        set_err(err, errlen, "out of device memory (segment tables)"); return FIN_ENOMEM;
+    }
+    if (!b->d_total) HIPCHK(hipMalloc((void**)&b->d_total, 8));
+    const void* frec = b->last_frec ? b->d_frec : nullptr;
+    int rc = fin_launch_sgm_count(frec, (const uint64_t*)b->d_out_offs, b->d_out, nr, b->dev.k, (uint32_t*)b->d_sgm_cnt, (uint32_t*)b->d_sgm_bsum, (uint64_t*)b->d_sgm_boff, b->d_total, st);
+    if (rc != 0) { set_err(err, errlen, std::string("segment kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, b->d_total, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (batch_grow(b, &b->d_sgm, b->cap_sgm, (size_t)total * 16 + 16, st)) { set_err(err, errlen, "out of device memory (segments)"); return FIN_ENOMEM; }
+    rc = fin_launch_sgm_write(frec, (const uint64_t*)b->d_out_offs, b->d_out, nr, b->dev.k, (const uint32_t*)b->d_sgm_cnt, (const uint64_t*)b->d_sgm_boff, (uint64_t*)b->d_sgm_offs, b->d_sgm, st);
+    if (rc != 0) { set_err(err, errlen, std::string("segment kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    b->n_segments = total; b->sgm_ready = true;
+    if (n_segments) *n_segments = total;
+    return FIN_OK;
+}
+
+void* fin_batch_device_segments(const fin_batch* b) { return b && b->sgm_ready ? b->d_sgm : nullptr; }
+void* fin_batch_device_segment_offsets(const fin_batch* b) { return b && b->sgm_ready ? b->d_sgm_offs : nullptr; }
+
+int fin_batch_download_segments(fin_batch* b, uint64_t* seg_offs_out, fin_segment* segs_out, char* err, size_t errlen) {
+    if (!b || !seg_offs_out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->sgm_ready) { set_err(err, errlen, "fin_batch_segments first"); return FIN_EINVAL; }
+    if (b->n_segments && !segs_out) { set_err(err, errlen, "null segment buffer"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    HIPCHK(hipMemcpyAsync(seg_offs_out, b->d_sgm_offs, (size_t)b->n_reads * 8 + 8, hipMemcpyDeviceToHost, st));
+    if (b->n_segments) HIPCHK(hipMemcpyAsync(segs_out, b->d_sgm, (size_t)b->n_segments * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
+extern "C++" {
+// the canonical segmentation of one read's slots (include/finito_amd.h): emit(u, off, slot, len) per segment, in slot order.  false: a pair that is neither
+// found nor (-1,-1)
+template <class F>
+static bool segment_slots(const int32_t* p, uint32_t nk, F&& emit) {
+    int lp = 0;            // link(i - 1)
+    uint32_t head = 0; bool in = false; int dir = 0;   // the open segment: its head slot, the sign of its internal links (0: one slot so far)
+    auto close = [&](uint32_t end) {
+        if (!in) return;
+        const uint32_t n = end - head;
+        emit(p[2 * head], p[2 * head + 1], head, dir < 0 ? -(int32_t)n : (int32_t)n);
+        in = false;
+    };
+    for (uint32_t i = 0; i < nk; i++) {
+        const int32_t u = p[2 * i], off = p[2 * i + 1];
+        if (u < 0) {
+            if (u != -1) return false;
+            close(i); lp = 0;
+            continue;
+        }
+        int l = 0;
+        if (i && p[2 * i - 2] == u) { const int64_t d = (int64_t)off - (int64_t)p[2 * i - 1]; l = d == 1 ? 1 : d == -1 ? -1 : 0; }
+        if (l == 0 || (lp != 0 && lp != l)) { close(i); head = i; in = true; dir = 0; }
+        else dir = l;
+        lp = l;
+    }
+    close(nk);
+    return true;
+}
+// the found stretches of a kind-1 record as segments, in slot order (the arithmetic of fin_expand_records)
+template <class F>
+static void segment_record(const fin_read_record& R, int k, F&& emit) {
+    const uint32_t nk = R.nk, nE = R.meta & 0xFFu;
+    if (!nk) return;
+    const bool rev = (R.meta >> 8) & 1u;
+    uint32_t from[9], to[9], n = 0, done_to = 0, at = 0;
+    for (uint32_t e = 0; e < nE && e < 8u; e++) {
+        const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
+        uint32_t lo = E >= (uint32_t)(k - 1) ? E - (uint32_t)(k - 1) : 0u, hi = E < nk ? E : nk - 1u;
+        if (lo < done_to) lo = done_to;
+        if (lo <= hi) { if (lo > at) { from[n] = at; to[n] = lo; n++; } at = hi + 1u; }
+        if (hi + 1u > done_to) done_to = hi + 1u;
+    }
+    if (nk > at) { from[n] = at; to[n] = nk; n++; }
+    for (uint32_t s = 0; s < n; s++) {
+        if (!rev) emit((int32_t)R.u, (int32_t)(R.off0 + from[s]), from[s], (int32_t)(to[s] - from[s]));
+        else { const uint32_t q = n - 1u - s, len = to[q] - from[q]; emit((int32_t)R.u, (int32_t)(R.off0 + to[q] - 1u), nk - to[q], len == 1u ? 1 : -(int32_t)len); }
+    }
+}
+
+}  // extern "C++"
+
+// host: the same segments from records + stream, the pairs never made -- the CPU statement of fin_segments.hip.  A chunk of reads per thread: first how many
+// segments and stream pairs each chunk has, then the segments
+int fin_records_segments(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t* seg_offs_out,
+                         fin_segment* segs_out, uint64_t seg_cap, uint64_t* n_segments, int n_threads) {
+    if ((n_reads && !recs) || k < 1 || (n_stream_pairs && !stream_pairs) || !seg_offs_out) return FIN_EINVAL;
+    if (n_segments) *n_segments = 0;
+    int T = n_threads > 0 ? n_threads : fin_host_threads();
+    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
+    std::vector<uint64_t> seg0((size_t)T + 1, 0), str0((size_t)T + 1, 0);
+    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
+        const auto lh = bounds(t);
+        uint64_t sp = 0;
+        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
+        str0[(size_t)t + 1] = sp;
+    }
+    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
+    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
+    auto pass = [&](int t, bool write) {
+        const auto lh = bounds(t);
+        uint64_t sp = str0[(size_t)t], sg = write ? seg0[(size_t)t] : 0;
+        auto emit = [&](int32_t u, int32_t off, uint32_t slot, int32_t len) { if (write) segs_out[sg] = fin_segment{u, off, slot, len}; sg++; };
+        for (uint64_t r = lh.first; r < lh.second; r++) {
+            const fin_read_record& R = recs[r];
+            const uint32_t kind = R.meta >> 16;
+            if (write) seg_offs_out[r] = sg;
+            if (kind == 0u) { if (!segment_slots(stream_pairs + 2 * sp, R.nk, emit)) return false; sp += R.nk; }
+            else if (kind == 1u) segment_record(R, k, emit);
+        }
+        if (!write) seg0[(size_t)t + 1] = sg;
+        return true;
+    };
+    bool ok = true;
+#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
+    for (int t = 0; t < T; t++) ok = pass(t, false) && ok;
+    if (!ok) return FIN_EINVAL;
+    for (int t = 0; t < T; t++) seg0[(size_t)t + 1] += seg0[(size_t)t];
+    const uint64_t total = seg0[(size_t)T];
+    if (n_segments) *n_segments = total;
+    if (total > seg_cap || (total && !segs_out)) return total > seg_cap ? FIN_ELIMIT : FIN_EINVAL;
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) (void)pass(t, true);
+    seg_offs_out[n_reads] = total;
+    return FIN_OK;
+}
+
+// host: fin_search_batch's pairs from segments.  Every read is checked before anything of it is written
+int fin_expand_segments(const uint64_t* seg_offs, const fin_segment* segs, uint64_t n_reads, const uint32_t* nk_per_read, int32_t* pairs_out, uint64_t* n_positive,
+                        int n_threads) {
+    if (!seg_offs || (n_reads && !nk_per_read)) return FIN_EINVAL;
+    for (uint64_t r = 0; r < n_reads; r++) if (seg_offs[r + 1] < seg_offs[r]) return FIN_EINVAL;
+    if (n_reads && seg_offs[n_reads] > seg_offs[0] && !segs) return FIN_EINVAL;
+    int T = n_threads > 0 ? n_threads : fin_host_threads();
+    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
+    std::vector<uint64_t> out0((size_t)T + 1, 0), pos((size_t)T, 0);
+    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
+    bool ok = true;
+#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
+    for (int t = 0; t < T; t++) {   // where each chunk's pairs begin; every segment checked
+        const auto lh = bounds(t);
+        uint64_t o = 0; bool good = true;
+        for (uint64_t r = lh.first; r < lh.second && good; r++) {
+            const uint64_t nk = nk_per_read[r];
+            uint64_t next = 0;   // the first slot a segment may begin at
+            for (uint64_t s = seg_offs[r]; s < seg_offs[r + 1]; s++) {
+                const fin_segment& S = segs[s];
+                const uint64_t n = S.len < 0 ? (uint64_t)(-(int64_t)S.len) : (uint64_t)S.len;
+                if (n == 0 || S.u < 0 || S.off < 0 || S.slot < next || (uint64_t)S.slot + n > nk) { good = false; break; }
+                if (S.len < 0 ? (int64_t)S.off - (int64_t)(n - 1) < 0 : (int64_t)S.off + (int64_t)(n - 1) > 0x7FFFFFFFll) { good = false; break; }
+                next = (uint64_t)S.slot + n;
+            }
+            o += nk;
+        }
+        out0[(size_t)t + 1] = o;
+        ok = good && ok;
+    }
+    if (!ok) return FIN_EINVAL;
+    for (int t = 0; t < T; t++) out0[(size_t)t + 1] += out0[(size_t)t];
+    if (out0[(size_t)T] && !pairs_out) return FIN_EINVAL;
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) {
+        const auto lh = bounds(t);
+        uint64_t o = out0[(size_t)t], found = 0;
+        for (uint64_t r = lh.first; r < lh.second; r++) {
+            const uint64_t nk = nk_per_read[r];
+            int32_t* const dst = pairs_out + 2 * o;
+            for (uint64_t i = 0; i < 2 * nk; i++) dst[i] = -1;
+            for (uint64_t s = seg_offs[r]; s < seg_offs[r + 1]; s++) {
+                const fin_segment& S = segs[s];
+                const int32_t step = S.len < 0 ? -1 : 1;
+                const uint32_t n = (uint32_t)(S.len < 0 ? -(int64_t)S.len : (int64_t)S.len);   // (checked above: 1 .. nk)
+                for (uint32_t j = 0; j < n; j++) { dst[2 * (S.slot + j)] = S.u; dst[2 * (S.slot + j) + 1] = S.off + step * (int32_t)j; }
+                found += n;
+            }
+            o += nk;
+        }
+        pos[(size_t)t] = found;
+    }
     if (n_positive) { uint64_t f = 0; for (uint64_t x : pos) f += x; *n_positive = f; }
     return FIN_OK;
 }
@@ -1665,6 +1877,8 @@ struct TextSink {
     char* buf = nullptr; uint64_t cap = 0;
     fin_hits* hits = nullptr;   // the profile instead of text (fin_search_batch_unitig_counts): every sub-batch is added on the device, nothing comes back
     fin_cover* cover = nullptr; // the coverage bitmap (fin_search_batch_add_cover); with `hits` too, both adds go behind the same run
+    // (segments when `seg_offs` is set: fin_search_batch_segments -- `len` then counts a sub-batch's segments, seg_offs is rebased to the whole read set)
+    uint64_t* seg_offs = nullptr; fin_segment* segs = nullptr; uint64_t seg_cap = 0; std::atomic<bool> seg_over{false};
     std::vector<uint64_t> len; std::vector<char> known;
     std::mutex mu; std::condition_variable cv;
     uint64_t total = 0;
@@ -1737,6 +1951,34 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
                 // (behind the run on the batch's own stream: the next batch_load on that stream finds the add done; fin_hits_download waits for the last ones)
                 if (ts->hits) rc = fin_batch_add_hits(b, ts->hits, (void*)b->own_stream, e, sizeof e);
                 if (rc == FIN_OK && ts->cover) rc = fin_batch_add_cover(b, ts->cover, (void*)b->own_stream, e, sizeof e);
+            } else
+            if (rc == FIN_OK && ts && ts->seg_offs) {
+                // segments: made behind the run on the device; the sub-batch's land behind those of all earlier sub-batches, its seg_offs at its reads' numbers
+                uint64_t L = 0;
+                rc = fin_batch_segments(b, &L, e, sizeof e);
+                {
+                    std::lock_guard<std::mutex> g(ts->mu);
+                    ts->len[i] = rc == FIN_OK ? L : 0; ts->known[i] = 1;
+                }
+                ts->cv.notify_all();
+                if (rc == FIN_OK) {
+                    uint64_t at = 0;
+                    {
+                        std::unique_lock<std::mutex> g(ts->mu);
+                        ts->cv.wait(g, [&] { for (size_t j = 0; j < i; j++) if (!ts->known[j]) return false; return true; });
+                        for (size_t j = 0; j < i; j++) at += ts->len[j];
+                    }
+                    if (at + L > ts->seg_cap) ts->seg_over.store(true);   // (nothing more is copied; the sub-batches go on being counted, so the caller learns how many there are)
+                    else if (!ts->seg_over.load()) {
+                        std::vector<uint64_t> so((size_t)(s.hi - s.lo) + 1);
+                        rc = fin_batch_download_segments(b, so.data(), ts->segs ? ts->segs + at : nullptr, e, sizeof e);
+                        if (rc == FIN_OK) {
+                            uint64_t* const dst = ts->seg_offs + (s.lo - ts->read0);   // (entry 0 is the sub-batch before's last, or the caller's)
+                            for (size_t r = 1; r < so.size(); r++) dst[r] = so[r] + at;
+                            for (uint64_t q = 0; q < L; q++) { const int32_t n = ts->segs[at + q].len; pos += (uint64_t)(n < 0 ? -(int64_t)n : (int64_t)n); }
+                        }
+                    }
+                }
             } else
             if (rc == FIN_OK && ts && ts->recs) {
                 // records: the sub-batch's stream of pairs lands behind the streams of all earlier sub-batches, its records at its reads' numbers
@@ -1878,6 +2120,26 @@ int fin_search_batch_records(const fin_index* idx, const char* bases, const uint
     TextSink ts; ts.recs = recs_out; ts.rpairs = stream_pairs_out; ts.rcap = stream_pairs_out ? stream_cap_pairs : 0; ts.read0 = 0;
     const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, FIN_MERGED, nullptr, nullptr, err, errlen, &ts);
     if (rc == FIN_OK && n_stream_pairs) *n_stream_pairs = ts.total;
+    return rc;
+}
+
+int fin_search_batch_segments(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint64_t* seg_offs_out,
+                              fin_segment* segs_out, uint64_t seg_cap, uint64_t* n_segments, uint64_t* n_positive, char* err, size_t errlen) {
+    if (!idx || !offsets || !seg_offs_out || (seg_cap && !segs_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (n_segments) *n_segments = 0;
+    if (n_positive) *n_positive = 0;
+    seg_offs_out[0] = 0;
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.seg_offs = seg_offs_out; ts.segs = segs_out; ts.seg_cap = segs_out ? seg_cap : 0; ts.read0 = 0;
+    uint64_t pos = 0;
+    const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
+    if (rc == FIN_OK && n_segments) *n_segments = ts.total;
+    if (rc == FIN_OK && ts.seg_over.load()) {
+        set_err(err, errlen, "segment buffer too small: room for " + std::to_string(ts.seg_cap) + " segments, " + std::to_string(ts.total) + " needed");
+        return FIN_ELIMIT;
+    }
+    if (rc == FIN_OK && n_positive) *n_positive = pos;
     return rc;
 }
 

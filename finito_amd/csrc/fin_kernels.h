@@ -130,6 +130,14 @@ int fin_launch_cover_add(const void* frec, const uint64_t* out_offs, const void*
                          hipStream_t stream);
 // covered[u] = popcount of unitig u's stretch of the bitmap (uint64[n_unitigs], zeroed here on `stream`)
 int fin_launch_cover_count(const void* bits, const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len, void* covered, hipStream_t stream);
+// fin_segments.hip: a finished step's results as segments {u, off, slot, len} of 16 bytes, dense and in read order, delimited per read by seg_offs[n_reads + 1].
+// frec / out_offs / pairs as fin_launch_hits_add.  fin_launch_sgm_count: cnt[n_reads] u32, blk_sum[fin_sgm_blocks()] u32, blk_off as many u64, *total the
+// batch's segments; fin_launch_sgm_write, once segs has room for them: seg_offs and the segments
+uint32_t fin_sgm_blocks(uint32_t n_reads);
+int fin_launch_sgm_count(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, uint32_t* cnt, uint32_t* blk_sum,
+                         uint64_t* blk_off, uint64_t* total, hipStream_t stream);
+int fin_launch_sgm_write(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const uint32_t* cnt,
+                         const uint64_t* blk_off, uint64_t* seg_offs, void* segs, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,231 @@
+// fin_segments.hip -- a batch's results as SEGMENTS: per read, the straight stretches its found slots make inside a unitig (include/finito_amd.h: fin_segment,
+// fin_batch_segments).  A segment {u, off, slot, len} says that output slots slot .. slot + |len| - 1 of the read were found in unitig u, slot
+// slot + j at offset off + j (len > 0) or off - j (len < 0).  The output is dense and in read order: seg_offs[n_reads + 1] (uint64, CSR) and the segments.
+//
+// The rule (canonical and local -- three neighbouring slots decide, no scan over the read).  link(i) = +1 / -1 when slots i - 1 and i are both found, in the same
+// unitig, and off[i] - off[i - 1] is +1 / -1; 0 otherwise, and link(0) = 0.  A found slot i is a segment HEAD when link(i) = 0, or when link(i - 1) is neither
+// 0 nor link(i).  A segment runs from its head to the slot before the next head or the next absent slot; its direction is the sign of its internal links (+ for
+// a single slot).  Offsets 5,6,5,6,5 in one unitig give [5,6] [5] [6] [5].  This is NOT fin_cover_rec_kernel's run rule (that one merges greedily, a bitmap
+// does not care where a run is cut).
+//
+// What is read.  Where the step left records (kernel 4, merged strands, fast path on, text mode 1 or 2), a lane per read:
+//   kind 1 -- the 32-byte record alone: the found strand slots are [0, nk) minus at most eight gaps, worked out exactly as fin_expand_records does (clamping to
+//             [0, nk - 1], a gap never starts below the end of its predecessor): at most nine stretches, each one segment.  A read found on its reverse strand
+//             (meta bit 8) has output slot i = strand slot nk - 1 - i: its stretches come out in reverse order, `off` at the stretch's highest offset, len < 0.
+//             The read's pairs are never touched -- in text mode 2 they do not exist.
+//   kind 2 -- nothing.
+//   kind 0 -- the wave scans the read's pairs through out_offs, a row of 64 slots at a time (the next row's load is issued before this row is worked on): links from neighbour compares, heads from the rule, a ballot.  The
+//             two-slot history (the last slot of the row before, and its link) is carried across rows in wave-uniform registers.  A head lane writes its
+//             segment; a segment still open at a row's end gets its u, off and slot from its head lane and its length from the row that closes it, so every
+//             byte is written once.
+// Where the step left no records (forward-only search, kernels 0 / 2 / 3, fast path off, k > 63, text mode 0) every read is scanned as a kind-0 read.
+//
+// Three steps, because the output is dense: (1) fin_sgm_kernel<false> counts per read (cnt[r]) and per block of 256 reads; (2) fin_sgm_scan_kernel, one block,
+// makes the blocks' exclusive prefix and the total in uint64; (3) fin_sgm_kernel<true> scans its block's counts, writes seg_offs and the segments.  The kind-0
+// pairs are read twice.  Records, pairs and text are read only; plain vector stores only.
+#include "fin_device.h"
+#include "fin_kernels.h"
+
+#define FIN_SGM_BLK 256u   // reads per block: a lane per read
+
+namespace {
+typedef unsigned long long ull;
+
+// the found stretches [from, to) of a kind-1 record's strand slots, ascending: emit(ordinal, from, to); returns how many
+template <class F>
+__device__ __forceinline__ uint32_t sgm_rec_walk(const uint4 a, const uint4 b, uint32_t k, F&& emit) {
+    const uint32_t nk = a.w, nE = min(a.z & 0xFFu, 8u), k1 = k - 1u;
+    uint32_t done_to = 0, from = 0, n = 0;
+#pragma unroll
+    for (uint32_t e = 0; e < 8u; e++) {
+        if (e < nE) {
+            const uint32_t w = e < 2u ? b.x : e < 4u ? b.y : e < 6u ? b.z : b.w, E = (e & 1u) ? w >> 16 : w & 0xFFFFu;
+            uint32_t lo = E >= k1 ? E - k1 : 0u;
+            const uint32_t hi = E < nk ? E : nk - 1u;
+            if (lo < done_to) lo = done_to;
+            if (lo <= hi) {
+                if (lo > from) { emit(n, from, lo); n++; }
+                from = hi + 1u;
+            }
+            if (hi + 1u > done_to) done_to = hi + 1u;
+        }
+    }
+    if (nk > from) { emit(n, from, nk); n++; }
+    return n;
+}
+
+// slots [lo, hi) of the pair array are one read's: its segments counted (WRITE false) or written to out[0 ..) (WRITE true), the whole wave, a row of 64 slots
+// at a time.  Wave-converged; returns the read's number of segments in every lane.
+template <bool WRITE>
+__device__ __forceinline__ uint32_t sgm_scan(const int2* pairs, uint64_t lo, uint64_t hi, uint4* out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t pu = 0xFFFFFFFFu, poff = 0u;   // the last slot of the row before (0xFFFFFFFF: absent, or there is none)
+    int plink = 0;                          // and its link
+    uint32_t cnt = 0;
+    bool open = false;                      // a segment reached the end of the row before: its ordinal, its slots so far, its direction (0: not known yet)
+    uint32_t open_idx = 0, open_len = 0;
+    int open_dir = 0;
+    int2 pn = make_int2(-1, -1);            // the row to come, loaded a row ahead: two loads in flight, the compares of one row hide the other's latency
+    if (lo + lane < hi) pn = pairs[lo + lane];
+    for (uint64_t base = lo; base < hi; base += 64u) {
+        const uint64_t j = base + lane;
+        const bool last_row = base + 64u >= hi;
+        const int2 p = pn;                  // (-1,-1) in a lane beyond the read's end
+        pn = make_int2(-1, -1);
+        if (j + 64u < hi) pn = pairs[j + 64u];
+        const uint32_t u = (uint32_t)p.x, off = (uint32_t)p.y;
+        const bool found = u != 0xFFFFFFFFu;   // (an inactive lane holds (-1,-1))
+        uint32_t up = (uint32_t)__shfl_up((int)u, 1), offp = (uint32_t)__shfl_up((int)off, 1);
+        if (lane == 0u) { up = pu; offp = poff; }
+        int link = 0;
+        if (found && u == up) link = off == offp + 1u ? 1 : off + 1u == offp ? -1 : 0;   // (u == up and found: the slot before is found too)
+        int linkp = __shfl_up(link, 1);
+        if (lane == 0u) linkp = plink;
+        const bool head = found && (link == 0 || (linkp != 0 && linkp != link));
+        const ull H = __ballot(head);
+        if (WRITE) {
+            const ull B = __ballot(head || !found);   // where a segment ends: the next head, the next absent slot, the read's end
+            const ull PD = __ballot(link == -1);
+            if (open) {
+                const uint32_t b = B ? (uint32_t)__ffsll((long long)B) - 1u : 64u;   // slots of this row that continue it
+                if (b > 0u && open_dir == 0) open_dir = (PD & 1ull) ? -1 : 1;
+                open_len += b;
+                if (b < 64u || last_row) {
+                    if (lane == 0u) ((int*)(out + open_idx))[3] = open_dir < 0 ? -(int)open_len : (int)open_len;
+                    open = false;
+                }
+            }
+            if (head) {
+                const ull above = lane == 63u ? 0ull : (B >> (lane + 1u)) << (lane + 1u);
+                const uint32_t end = above ? (uint32_t)__ffsll((long long)above) - 1u : 64u;
+                const uint32_t n = end - lane;   // 1 .. 64
+                const bool down = n > 1u && ((PD >> (lane + 1u)) & 1ull);
+                const uint32_t idx = cnt + (uint32_t)__popcll(H & ((1ull << lane) - 1ull));
+                if (end == 64u && !last_row) {   // open: the closing row writes len
+                    uint32_t* const w = (uint32_t*)(out + idx);
+                    w[0] = u; w[1] = off; w[2] = (uint32_t)(j - lo);
+                } else out[idx] = make_uint4(u, off, (uint32_t)(j - lo), (uint32_t)(down ? -(int)n : (int)n));
+            }
+            if (H && !last_row) {
+                const uint32_t hl = 63u - (uint32_t)__clzll((long long)H);
+                if ((hl == 63u ? 0ull : B >> (hl + 1u)) == 0ull) {
+                    open = true; open_idx = cnt + (uint32_t)__popcll(H) - 1u; open_len = 64u - hl;
+                    open_dir = open_len > 1u ? (((PD >> (hl + 1u)) & 1ull) ? -1 : 1) : 0;
+                }
+            }
+        }
+        cnt += (uint32_t)__popcll(H);
+        pu = (uint32_t)__builtin_amdgcn_readlane((int)u, 63); poff = (uint32_t)__builtin_amdgcn_readlane((int)off, 63);
+        plink = __builtin_amdgcn_readlane(link, 63);
+    }
+    return cnt;
+}
+}  // namespace
+
+// WRITE false: cnt[r] = read r's number of segments, blk_sum[block] their sum over the block's reads.
+// WRITE true:  seg_offs[r] = blk_off[block] + the exclusive prefix of cnt[] inside the block, seg_offs[n_reads] the total; the segments.
+// frec null: the step left no records, every read is scanned.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void fin_sgm_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k, uint32_t* cnt,
+                                                      uint32_t* blk_sum, const uint64_t* blk_off, uint64_t* seg_offs, uint4* segs) {
+    __shared__ uint32_t lds_w[4];
+    const uint32_t r = blockIdx.x * FIN_SGM_BLK + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t kind = 2u;
+    uint64_t p_lo = 0, p_hi = 0;
+    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+    if (r < n_reads) {
+        kind = 0u;
+        if (frec) {
+            a = ((const uint4*)(frec + r))[0];   // u, off0, meta, nk
+            kind = a.z >> 16;
+            if (kind == 1u) b = ((const uint4*)(frec + r))[1];
+        }
+        if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
+    }
+    uint32_t mine = 0;
+    uint64_t at = 0;   // WRITE: where this read's segments begin
+    if (WRITE) {
+        if (r < n_reads) mine = cnt[r];
+        uint32_t inc = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)inc, d); if ((int)lane >= d) inc += y; }
+        if (lane == 63u) lds_w[wave] = inc;
+        __syncthreads();
+        uint32_t before = 0;
+        for (uint32_t w = 0; w < wave; w++) before += lds_w[w];
+        at = blk_off[blockIdx.x] + before + inc - mine;
+        if (r < n_reads) seg_offs[r] = at;
+        if (r == n_reads - 1u) seg_offs[n_reads] = at + mine;
+    }
+    if (kind == 1u && a.w != 0u) {
+        if (WRITE) {
+            const bool rev = (a.z >> 8) & 1u;
+            uint4* const out = segs + at;
+            (void)sgm_rec_walk(a, b, k, [&](uint32_t s, uint32_t from, uint32_t to) {
+                const uint32_t n = to - from;
+                if (!rev) out[s] = make_uint4(a.x, a.y + from, from, n);
+                else out[mine - 1u - s] = make_uint4(a.x, a.y + to - 1u, a.w - to, (uint32_t)(n == 1u ? 1 : -(int)n));
+            });
+        } else mine = sgm_rec_walk(a, b, k, [](uint32_t, uint32_t, uint32_t) {});
+    }
+    // ---- the searched reads' pairs: the wave takes its lanes' reads one after the other ----
+    ull todo = __ballot(kind == 0u && p_hi > p_lo);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1ull;
+        const uint64_t lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_lo >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_lo, src);
+        const uint64_t hi = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_hi >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_hi, src);
+        const uint64_t at_s = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(at >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)at, src);
+        const uint32_t c = sgm_scan<WRITE>(pairs, lo, hi, segs + at_s);
+        if (!WRITE && (int)lane == src) mine = c;
+    }
+    if (!WRITE) {
+        if (r < n_reads) cnt[r] = mine;
+        uint32_t s = mine;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s += (uint32_t)__shfl_xor((int)s, d);
+        if (lane == 0u) lds_w[wave] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) blk_sum[blockIdx.x] = lds_w[0] + lds_w[1] + lds_w[2] + lds_w[3];
+    }
+}
+
+// exclusive prefix of the block sums (one block: fin_rec_scan_kernel's pattern) and the total, both uint64 -- a batch's k-mers may number more than 2^32
+__global__ __launch_bounds__(1024) void fin_sgm_scan_kernel(const uint32_t* blk_sum, uint32_t n_blk, uint64_t* blk_off, uint64_t* total) {
+    __shared__ uint64_t lds[1024];
+    const uint32_t per = (n_blk + 1023u) / 1024u, b0 = threadIdx.x * per;
+    uint64_t s = 0;
+    for (uint32_t i = 0; i < per; i++) if (b0 + i < n_blk) s += blk_sum[b0 + i];
+    lds[threadIdx.x] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {
+        const uint64_t y = threadIdx.x >= d ? lds[threadIdx.x - d] : 0ull;
+        __syncthreads();
+        lds[threadIdx.x] += y;
+        __syncthreads();
+    }
+    uint64_t at = lds[threadIdx.x] - s;
+    for (uint32_t i = 0; i < per; i++) if (b0 + i < n_blk) { blk_off[b0 + i] = at; at += blk_sum[b0 + i]; }
+    if (threadIdx.x == 1023u) *total = lds[1023];
+}
+
+extern "C" uint32_t fin_sgm_blocks(uint32_t n_reads) { return (n_reads + FIN_SGM_BLK - 1u) / FIN_SGM_BLK; }
+// cnt: n_reads u32; blk_sum: fin_sgm_blocks() u32; blk_off: as many u64; total: one u64 (the batch's segments).  The counting pass and the scan.  n_reads > 0
+extern "C" int fin_launch_sgm_count(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, uint32_t* cnt, uint32_t* blk_sum,
+                                    uint64_t* blk_off, uint64_t* total, hipStream_t stream) {
+    const uint32_t nb = fin_sgm_blocks(n_reads);
+    if (nb == 0) return (int)hipMemsetAsync(total, 0, 8, stream);
+    hipLaunchKernelGGL(fin_sgm_kernel<false>, dim3(nb), dim3(256), 0, stream, (const FinFastRec*)frec, out_offs, (const int2*)pairs, n_reads, k, cnt, blk_sum,
+                       (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint4*)nullptr);
+    hipLaunchKernelGGL(fin_sgm_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)blk_sum, nb, blk_off, total);
+    return (int)hipGetLastError();
+}
+// seg_offs: n_reads + 1 u64; segs: room for *total segments of 16 bytes
+extern "C" int fin_launch_sgm_write(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const uint32_t* cnt,
+                                    const uint64_t* blk_off, uint64_t* seg_offs, void* segs, hipStream_t stream) {
+    const uint32_t nb = fin_sgm_blocks(n_reads);
+    if (nb == 0) return (int)hipMemsetAsync(seg_offs, 0, 8, stream);
+    hipLaunchKernelGGL(fin_sgm_kernel<true>, dim3(nb), dim3(256), 0, stream, (const FinFastRec*)frec, out_offs, (const int2*)pairs, n_reads, k, (uint32_t*)cnt,
+                       (uint32_t*)nullptr, blk_off, seg_offs, (uint4*)segs);
+    return (int)hipGetLastError();
+}

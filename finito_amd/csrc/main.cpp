@@ -452,8 +452,13 @@ static const char* SEARCH_HELP =
     "                        Costs one more search of every chunk on the device, beside the one for the text and the one for\n"
     "                        --unitig-counts; with --no-text 1 and no --unitig-counts a chunk is still searched twice (the second\n"
     "                        pass counts the found k-mers the log reports).\n"
-    "      --no-text arg     1 (only with --unitig-counts or --unitig-coverage): do not make or write the pair text, the profile and / or the\n"
-    "                        coverage are the only results\n"
+    "      --segments FILE   also write every read's path through the unitig set: one line `read<TAB>slot<TAB>length<TAB>unitig<TAB>offset<TAB>+|-` per\n"
+    "                        segment -- `length` consecutive k-mers of read `read` (0-based ordinal in the query file, counted through a list of\n"
+    "                        query files), from its k-mer number `slot` on, found in `unitig` at `offset`, `offset + 1`, ... (+) or `offset`,\n"
+    "                        `offset - 1`, ... (-). Reads without a found k-mer have no line. Made on the first GPU from one more search of every\n"
+    "                        chunk; goes with -o, --unitig-counts and --unitig-coverage. Not for a partitioned index.\n"
+    "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage or --segments): do not make or write the pair text, the profile, the\n"
+    "                        coverage and / or the segments are the only results\n"
     "  -h, --help            Print usage\n";
 
 static int build_fmin(int argc, char** argv) {
@@ -628,6 +633,37 @@ static void add_cover_chunk(const FinimizerIndex& index, const char* bases, cons
     char err[512] = {0};
     if (fin_search_batch_add_cover(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
 }
+// --segments FILE: every chunk's segments are made on the first device (fin_search_batch_segments) and written as lines, by the search stage, in chunk order
+static FILE* g_seg_file = nullptr;
+static uint64_t g_seg_read0 = 0;   // reads in the chunks (and query files) before this one
+static double g_seg_per_read = 0;   // the most segments per read a chunk has had
+static vector<uint64_t> g_seg_offs; static vector<fin_segment> g_segs; static string g_seg_text;
+static uint64_t segments_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t n_kmers) {
+    char err[512] = {0};
+    // room for four segments per read at first (a read is rarely more than two or three), or half as many again as the densest chunk so far needed; a chunk
+    // that needs more says how many and is searched once more with exactly that room -- one per k-mer always suffices
+    g_seg_offs.resize(n_reads + 1);
+    uint64_t n_seg = 0, pos = 0, cap = min<uint64_t>(n_kmers, (uint64_t)(max(4.0, 1.5 * g_seg_per_read) * (double)n_reads) + 1024);
+    for (;;) {
+        if (g_segs.size() < cap + 1) g_segs.resize(cap + 1);
+        const int rc = fin_search_batch_segments(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_seg_offs.data(), g_segs.data(), cap, &n_seg, &pos, err, sizeof err);
+        if (rc == FIN_OK) break;
+        if (rc != FIN_ELIMIT || n_seg <= cap) throw runtime_error(err);
+        cap = n_seg;
+    }
+    if (n_reads) g_seg_per_read = max(g_seg_per_read, (double)n_seg / (double)n_reads);
+    string& t = g_seg_text;
+    t.clear();
+    for (uint64_t r = 0; r < n_reads; r++)
+        for (uint64_t q = g_seg_offs[r]; q < g_seg_offs[r + 1]; q++) {
+            const fin_segment& S = g_segs[q];
+            t += to_string(g_seg_read0 + r); t += '\t'; t += to_string(S.slot); t += '\t'; t += to_string(S.len < 0 ? -(int64_t)S.len : (int64_t)S.len); t += '\t';
+            t += to_string(S.u); t += '\t'; t += to_string(S.off); t += S.len < 0 ? "\t-\n" : "\t+\n";
+        }
+    if (!t.empty() && fwrite(t.data(), 1, t.size(), g_seg_file) != t.size()) throw runtime_error("Error writing the segments file");
+    g_seg_read0 += n_reads;
+    return pos;
+}
 static bool g_no_text = false;
 static uint64_t g_hits_total = 0;   // the accumulator's sum after the previous query file
 
@@ -703,9 +739,10 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         const int64_t len = (int64_t)(c->offsets[r + 1] - c->offsets[r]);
                         c->pair_off[r + 1] = c->pair_off[r] + (uint64_t)(len >= k ? len - k + 1 : 0);
                     }
-                    if (g_no_text) {   // the profile / the coverage is all this chunk is searched for
-                        index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);
+                    if (g_no_text) {   // the profile / the coverage / the segments are all this chunk is searched for
+                        if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_seg_file) c->positive = segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                     }
                     else {
                         // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
@@ -721,6 +758,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         }
                         if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);   // (a second pass over the chunk on the device: the text is what bounds this loop)
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_seg_file) (void)segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                     }
                     if (g_strand_counts) {
                         c->positive_fwd = index.count_found_one_strand(c->bases.get(0), c->offsets.data(), n_reads);
@@ -811,7 +849,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
         cerr << "[timing] stage busy seconds: parse " << t_parse.load() * 1e-6 << "  search(+PCIe" << (gpu_text ? "+GPU text" : "") << ") " << t_search.load() * 1e-6
              << "  " << (gpu_text ? "write " : "format+write ") << t_write.load() * 1e-6 << endl;
     if (first_error) rethrow_exception(first_error);
-    if (g_no_text) {   // no pairs came back: the found k-mers of this file are what the accumulator's sum grew by
+    if (g_no_text && g_hits) {   // no pairs came back: the found k-mers of this file are what the accumulator's sum grew by (with --segments alone: their lengths)
         char err[512] = {0};
         uint64_t tot = 0;
         if (fin_hits_download(g_hits, nullptr, &tot, err, sizeof err) != FIN_OK) throw runtime_error(err);
@@ -836,11 +874,11 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "segments", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage")) throw runtime_error("--no-text 1 is only legal together with --unitig-counts or --unitig-coverage (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("segments")) throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage or --segments (the run would have no result)");
     if (g_no_text && g_strand_counts) throw runtime_error("--no-text 1 and --strand-counts 1 do not go together");
     if (!o.has("query-file")) throw runtime_error("Option 'query-file' has no value");
     if (!o.has("index-file")) throw runtime_error("Option 'index-file' has no value");
@@ -863,6 +901,8 @@ static int search_fmin(int argc, char** argv) {
     if (!counts_file.empty()) check_writable(counts_file);
     const string cover_file = o.get("unitig-coverage", "");
     if (!cover_file.empty()) check_writable(cover_file);
+    const string seg_file = o.get("segments", "");
+    if (!seg_file.empty()) check_writable(seg_file);
     cerr << "Loading index..." << endl;
     const int first_dev = stoi(o.get("device", "0"));
     // beside the index load: page-lock the pipeline's buffers (four chunks of 48 MB of bases and of up to 16 bytes of text per k-mer)
@@ -900,9 +940,10 @@ static int search_fmin(int argc, char** argv) {
     const int64_t t_l1 = cur_time_micros();
     if (!counts_file.empty() && index.partitioned()) throw runtime_error("--unitig-counts is not available with a partitioned index");
     if (!cover_file.empty() && index.partitioned()) throw runtime_error("--unitig-coverage is not available with a partitioned index");
+    if (!seg_file.empty() && index.partitioned()) throw runtime_error("--segments is not available with a partitioned index");
     index.to_device();
     struct HitsOwner { ~HitsOwner() { fin_hits_free(g_hits); g_hits = nullptr; } } hits_owner;
-    if (!counts_file.empty() || g_no_text) {
+    if (!counts_file.empty() || (g_no_text && seg_file.empty())) {   // (with --segments the found k-mers are the sum of the segments' lengths)
         char err[512] = {0};
         if (fin_hits_create(index.handle(), first_dev, &g_hits, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
@@ -910,6 +951,12 @@ static int search_fmin(int argc, char** argv) {
     if (!cover_file.empty()) {
         char err[512] = {0};
         if (fin_cover_create(index.handle(), first_dev, &g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    }
+    struct SegOwner { ~SegOwner() { if (g_seg_file) fclose(g_seg_file); g_seg_file = nullptr; } } seg_owner;
+    if (!seg_file.empty()) {
+        g_seg_file = fopen(seg_file.c_str(), "wb");
+        if (!g_seg_file) throw runtime_error("Error writing to file: " + seg_file);
+        g_seg_read0 = 0;
     }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
@@ -930,6 +977,11 @@ static int search_fmin(int argc, char** argv) {
             SeqReader reader(query_files[i]);
             number_of_queries += run_fmin_queries_streaming(&reader, nullptr, out, index, index_prefix + ".stats");
         }
+    }
+    if (g_seg_file) {
+        const bool bad = fflush(g_seg_file) != 0 || ferror(g_seg_file);
+        fclose(g_seg_file); g_seg_file = nullptr;
+        if (bad) throw runtime_error("Error writing to file: " + seg_file);
     }
     if (g_cover) {   // the coverage, after the last chunk: one line per unitig of the index
         char err[512] = {0};

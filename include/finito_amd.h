@@ -496,6 +496,50 @@ void fin_cover_free(fin_cover* c);
 int fin_records_cover(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
                       uint64_t n_unitigs, uint64_t* bits_out, int n_threads);
 
+/* ---- results as SEGMENTS: a read's path through the unitig set, made on the device for every read ----
+ * Records (above) are compact only for the reads the fast path finished; a read the pipeline searched -- an indel, a mosaic over several unitigs, more than eight
+ * substitutions, any read at k > 63 or in a forward-only search -- still comes back as 8 bytes per k-mer, although it is almost always two to five straight
+ * stretches inside a unitig.  Segments are those stretches, for EVERY read, in one format:
+ *   a segment {u, off, slot, len} says that the read's output slots slot .. slot + |len| - 1 were found in unitig u;
+ *   slots are the read's own, 0-based, in the order of fin_search_batch's pairs; slot slot + j is at offset off + j when len > 0, at off - j when len < 0;
+ *   a slot that lies in no segment is (-1,-1); a segment of one slot has len = +1; a read's segments are ordered by slot and do not overlap;
+ *   seg_offs[n_reads + 1] (uint64) delimits them per read, CSR style: read r owns segments seg_offs[r] .. seg_offs[r + 1] - 1.
+ * The segmentation is canonical and local, so every producer gives the same bytes.  link(i), for i >= 1, is +1 if slots i - 1 and i are both found, in the same
+ * unitig, and off[i] - off[i - 1] = +1; -1 for the same with a difference of -1; 0 otherwise; link(0) = 0.  A found slot i is a segment HEAD when link(i) = 0, or
+ * when link(i - 1) != 0 and link(i - 1) != link(i).  A segment runs from its head to the slot before the next head or the next absent slot; its direction is the
+ * sign of its internal links.  The rule is deliberately not greedy: a period-2 read over a unitig that holds ACACA... gives offsets 5,6,5,6,5 and the rule makes
+ * [5,6] [5] [6] [5] of them -- from three neighbouring slots alone, with no scan over the read (a greedy scan would say [5,6] [5,6] [5]); 6,5,6,7 gives
+ * [6,5] [6,7].  A repeated identical pair (difference 0) breaks a segment too, and so does a change of unitig with consecutive offsets.
+ * A read found on its reverse strand has descending offsets: `off` is the stretch's highest offset and len < 0.
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi, the C++ mirror, segments that bridge a substitution (chains). */
+typedef struct fin_segment { int32_t u; int32_t off; uint32_t slot; int32_t len; } fin_segment;   /* 16 bytes */
+/* Behind the batch's most recent run, on that run's stream (fin_segments.hip): a counting pass, a scan, a writing pass; waits for the count, *n_segments (may be
+ * NULL) = how many there are.  seg_offs and the segments stay in HBM, in buffers the batch keeps and only grows.  Works in every text mode, for FIN_MERGED and
+ * FIN_FWD, for every k: a read the fast path finished (text modes 1 and 2) is segmented from its 32-byte record alone -- in mode 2 its pairs do not exist --, every
+ * other read's pairs are scanned in place.  Read-only on records, pairs and text: everything the batch gives afterwards is what it gives without the call.
+ * FIN_EINVAL: the batch has not run.  FIN_ELIMIT: the run's overflow list overran -- it has no results, nothing is written. */
+int fin_batch_segments(fin_batch* b, uint64_t* n_segments, char* err, size_t errlen);
+void* fin_batch_device_segments(const fin_batch* b);          /* fin_segment[n_segments] in HBM; NULL before fin_batch_segments, and may be NULL when there are none */
+void* fin_batch_device_segment_offsets(const fin_batch* b);   /* uint64[n_reads + 1] in HBM; NULL before fin_batch_segments */
+/* seg_offs_out[n_reads + 1], segs_out[n_segments] (may be NULL when there are none) */
+int fin_batch_download_segments(fin_batch* b, uint64_t* seg_offs_out, fin_segment* segs_out, char* err, size_t errlen);
+/* host buffers in, only seg_offs and the segments out: fin_search_batch_records' pipeline over sub-batches, each run in text mode 2 where the fast path is on and
+ * segmented on the device behind its run; seg_offs_out[n_reads + 1] is rebased to the whole read set.  segs_out has room for seg_cap segments: the input's
+ * number of k-mers always suffices; FIN_ELIMIT if the result does not fit -- *n_segments then says how many there are, the buffers' contents are undefined.  *n_positive (may be NULL) = the k-mers found (the sum of |len|).  Reads shorter
+ * than k and an empty read set are legal. */
+int fin_search_batch_segments(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint64_t* seg_offs_out,
+                              fin_segment* segs_out, uint64_t seg_cap, uint64_t* n_segments, uint64_t* n_positive, char* err, size_t errlen);
+/* host, no device: fin_search_batch's pairs from segments, bit for bit.  nk_per_read[r] = read r's number of slots, max(0, length - k + 1);
+ * pairs_out[2 * sum of nk]; *n_positive (may be NULL) the pairs found; n_threads <= 0: all cores.  FIN_EINVAL, before anything is written: a segment leaves
+ * [0, nk), a read's segments overlap or are unsorted, a segment has len = 0, the offsets of a segment would go negative, seg_offs descends. */
+int fin_expand_segments(const uint64_t* seg_offs, const fin_segment* segs, uint64_t n_reads, const uint32_t* nk_per_read, int32_t* pairs_out, uint64_t* n_positive,
+                        int n_threads);
+/* host, no device: the same canonical segments from records + stream, without making the pairs -- the CPU statement of what the kernel does.
+ * seg_offs_out[n_reads + 1]; segs_out has room for seg_cap segments, *n_segments (may be NULL) how many there are (also when FIN_ELIMIT says they do not fit).
+ * FIN_EINVAL: a stream that is not this record set's, or a stream pair that is neither found nor (-1,-1) */
+int fin_records_segments(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t* seg_offs_out,
+                         fin_segment* segs_out, uint64_t seg_cap, uint64_t* n_segments, int n_threads);
+
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
  * k-mer is in no unitig), 1 a verified claim, 2 an unverified one (| 8: the exact side table has the k-mer, g is its answer), | 4 the text at [g-k+1, g] spells
