@@ -166,6 +166,16 @@ def lib():
         L.fin_search_batch_add_cover.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
         L.fin_search_batch_unitig_coverage.argtypes = [vp, cp, u64p, u64, C.c_int, u64p, u64p, cp, C.c_size_t]
         L.fin_records_cover.argtypes = [vp, u64, vp, u64, C.c_int, i64p, u64, u64p, C.c_int]
+        L.fin_depth_create.argtypes = [vp, C.c_int, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_depth_reset.argtypes = [vp, vp]
+        L.fin_batch_add_depth.argtypes = [vp, vp, vp, cp, C.c_size_t]
+        L.fin_depth_device_diff.restype = vp
+        L.fin_depth_device_diff.argtypes = [vp]
+        L.fin_depth_download.argtypes = [vp, C.c_uint32, vp, vp, u64p, cp, C.c_size_t]
+        L.fin_depth_free.argtypes = [vp]
+        L.fin_search_batch_add_depth.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
+        L.fin_search_batch_unitig_depth.argtypes = [vp, cp, u64p, u64, C.c_int, C.c_uint32, vp, u64p, cp, C.c_size_t]
+        L.fin_records_depth.argtypes = [vp, u64, vp, u64, C.c_int, i64p, u64, vp, C.c_int]
         L.fin_batch_segments.argtypes = [vp, u64p, cp, C.c_size_t]
         L.fin_batch_device_segments.argtypes = [vp]
         L.fin_batch_device_segments.restype = vp
@@ -503,6 +513,67 @@ class Cover:
             pass
 
 
+class Depth:
+    """how many times each position of the concatenated unitig text was found, resident in HBM beside one replica of the index as a difference array
+    (fin_depth_* of the C ABI): between Hits (the depth summed over a unitig) and Cover (where it is above zero)."""
+
+    def __init__(self, index, device=0):
+        self.index = index
+        self.L = lib()
+        self.n_unitigs = index.n_unitigs
+        self.total_len = index.total_len
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_depth_create(index.h, int(device), C.byref(h), err, 512), err)
+        self.h = h
+
+    def add(self, batch, stream=None):
+        """depth += the found places of the batch's most recent run, on a HIP stream, behind that run; no sync (fin_batch_add_depth).  Adding the same run
+        twice counts it twice."""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_add_depth(batch.h, self.h, C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add_reads(self, reads, strands=FIN_MERGED):
+        """search a read set from host buffers, sub-batches pipelined as in search_reads, and add its places; nothing comes back (fin_search_batch_add_depth)"""
+        bases, offsets = flatten(reads)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_add_depth(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+                                                 int(strands), self.h, err, 512), err)
+        return self
+
+    def reset(self, stream=None):
+        rc = self.L.fin_depth_reset(self.h, C.c_void_p(stream or 0))
+        if rc != 0:
+            raise FinitoError(rc, "fin_depth_reset")
+        return self
+
+    def download(self, min_depth=1, want_positions=True):
+        """(uint32 depth[total_len] -- None without want_positions --, DEPTH_STAT_DTYPE stats[n_unitigs] with n_at_least counted against min_depth, the sum over
+        all positions = the k-mers found); waits for the adds, runs the prefix sum on the device and leaves the accumulator as it is (fin_depth_download)"""
+        depth = np.zeros(max(self.total_len, 1), dtype=np.uint32) if want_positions else None
+        stats = np.zeros(max(self.n_unitigs, 1), dtype=DEPTH_STAT_DTYPE)
+        tot = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_depth_download(self.h, int(min_depth), depth.ctypes.data_as(C.c_void_p) if want_positions else None, stats.ctypes.data_as(C.c_void_p),
+                                         C.byref(tot), err, 512), err)
+        return (depth[: self.total_len] if want_positions else None), stats[: self.n_unitigs], int(tot.value)
+
+    def device_ptr(self):
+        return int(self.L.fin_depth_device_diff(self.h) or 0)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fin_depth_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FinimizerIndex:
     """Mirror of the reference class (FinimizerIndex.hh:26-259) backed by the HIP path."""
 
@@ -800,6 +871,21 @@ class FinimizerIndex:
                                                        int(strands), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(npos), err, 512), err)
         return out[: self.n_unitigs], int(npos.value)
 
+    def depth(self, device=0):
+        """a zeroed per-position depth accumulator beside the replica on `device` (Depth)"""
+        return Depth(self, device)
+
+    def unitig_depth(self, reads, strands=FIN_MERGED, min_depth=1):
+        """the depth of a read set over host buffers, per unitig (fin_search_batch_unitig_depth): (DEPTH_STAT_DTYPE stats[n_unitigs], total_positive) -- each
+        unitig's summed and greatest depth and how many of its positions were found at least min_depth times; only the statistics come back from the device"""
+        bases, offsets = flatten(reads)
+        out = np.zeros(max(self.n_unitigs, 1), dtype=DEPTH_STAT_DTYPE)
+        npos = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_unitig_depth(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+                                                    int(strands), int(min_depth), out.ctypes.data_as(C.c_void_p), C.byref(npos), err, 512), err)
+        return out[: self.n_unitigs], int(npos.value)
+
     def search_reads_text(self, reads, strands=FIN_MERGED):
         """run_fmin_queries_streaming with its printed text as the result (fin_search_batch_text): (bytes, total_positive)"""
         bases, offsets = flatten(reads)
@@ -845,6 +931,7 @@ class FinimizerIndex:
 
 RECORD_DTYPE = np.dtype([("u", np.uint32), ("off0", np.uint32), ("meta", np.uint32), ("nk", np.uint32), ("Es", np.uint64), ("Es2", np.uint64)])
 SEGMENT_DTYPE = np.dtype([("u", np.int32), ("off", np.int32), ("slot", np.uint32), ("len", np.int32)])   # fin_segment
+DEPTH_STAT_DTYPE = np.dtype([("sum", np.uint64), ("max", np.uint32), ("n_at_least", np.uint32)])            # fin_depth_stat
 
 
 class PartitionedBatch:
@@ -1030,6 +1117,19 @@ def records_cover(recs, stream, k, ends, n_threads=0):
     if rc != 0:
         raise FinitoError(rc, "fin_records_cover: a unitig number outside the index, a k-mer that does not lie inside its unitig, or records and stream do not belong together")
     return out[:n_words]
+
+
+def records_depth(recs, stream, k, ends, n_threads=0):
+    """fin_records_depth (host): the per-position depth uint32[ends[-1]] from records + stream, without making the pairs; `ends` as export(X_ENDS)"""
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE); stream = np.ascontiguousarray(stream, dtype=np.int32)
+    ends = np.ascontiguousarray(ends, dtype=np.int64)
+    total_len = int(ends[-1]) if len(ends) else 0
+    out = np.zeros(max(total_len, 1), dtype=np.uint32)
+    rc = lib().fin_records_depth(recs.ctypes.data_as(C.c_void_p), len(recs), stream.ctypes.data_as(C.c_void_p), len(stream.reshape(-1, 2)), int(k),
+                                 ends.ctypes.data_as(C.POINTER(C.c_int64)), len(ends), out.ctypes.data_as(C.c_void_p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_depth: a unitig number outside the index, a k-mer that does not lie inside its unitig, or records and stream do not belong together")
+    return out[:total_len]
 
 
 def expand_segments(seg_offs, segs, nk_per_read, n_threads=0):

@@ -93,7 +93,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_hits_combine, O_cover_probe, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -126,6 +126,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"debug_pp_park_cap", -1, -1, 1024},           // tests: at most this many parked reads per pre-pass block (-1: as many as the LDS budget holds)
     {"hits_combine", 4, 0, 64},                    // fin_batch_add_hits: what a wave sums before an add goes to memory (fin_hits.hip) -- rounds in which the record lanes of one unitig merge, and the run held back between rows of pairs; 0 = every record lane and every run of a row adds by itself
     {"cover_probe", 0, 0, 1},                      // fin_batch_add_cover: 1 = a lane loads the bitmap word first and skips the atomic OR when every bit it would set is set already (exact: bits are only ever set between resets, fin_cover.hip); 0 = always OR.  Measured (profiles/r09/cover.md): 1 wins behind text-mode-2 steps once the bitmap fills (0.83 against 1.14 ms on chr1), 0 behind default steps (4.0 against 5.0 ms) and summed over both
+    {"debug_depth_tile", 0, 0, 4096},              // tests: fin_depth_download's prefix sum in tiles of this many elements and chunks of 64 tiles (0: tiles of 4096 elements, chunks of 4096 tiles)
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -1470,7 +1471,7 @@ int fin_expand_segments(const uint64_t* seg_offs, const fin_segment* segs, uint6
 }
 
 // ---- the profile over the unitig set (fin_hits.hip) ---------------------------------------------------------------------------------
-// what the download of a device accumulator (fin_hits, fin_cover) waits for: an event per stream that work on the accumulator was put on
+// what the download of a device accumulator (fin_hits, fin_cover, fin_depth) waits for: an event per stream that work on the accumulator was put on
 struct AccPending {
     std::mutex mu; std::vector<std::pair<hipStream_t, hipEvent_t>> pending;
     int mark(hipStream_t st, char* err, size_t errlen) {
@@ -1489,7 +1490,7 @@ struct AccPending {
     }
     void drop() { for (auto& p : pending) { (void)hipEventSynchronize(p.second); (void)hipEventDestroy(p.second); } pending.clear(); }
 };
-// behind the batch's most recent run, whichever stream it was launched on: what fin_batch_add_hits and fin_batch_add_cover check and order alike
+// behind the batch's most recent run, whichever stream it was launched on: what fin_batch_add_hits, fin_batch_add_cover and fin_batch_add_depth check and order alike
 static int acc_behind_run(fin_batch* b, const fin_index* acc_idx, int acc_device, hipStream_t st, char* err, size_t errlen) {
     if (!b->ran) { set_err(err, errlen, "this batch has not run: there are no hits to add (fin_batch_run first)"); return FIN_EINVAL; }
     if (b->idx != acc_idx || b->device != acc_device) { set_err(err, errlen, "batch and accumulator belong to different indexes or devices"); return FIN_EINVAL; }
@@ -1788,6 +1789,180 @@ int fin_records_cover(const fin_read_record* recs, uint64_t n_reads, const int32
     return ok ? FIN_OK : FIN_EINVAL;
 }
 
+// ---- per-position depth over the unitig text (fin_depth.hip) ---------------------------------------------------------------------------
+struct fin_depth {
+    const fin_index* idx = nullptr;
+    int device = -1;
+    uint64_t n_unitigs = 0, total_len = 0;
+    const uint32_t* d_ends = nullptr;   // the replica's ends_p
+    void* d_diff = nullptr;             // int32[total_len + 1], the difference array, then the flag word (fin_launch_depth_add)
+    // fin_depth_download's: made by the first download, kept
+    uint32_t* d_stage = nullptr;        // uint32[stage_len]: one chunk's depths
+    uint32_t* d_tile = nullptr;         // uint32[fin_depth_max_chunk_tiles()]: the chunk's tile sums, then the carry word
+    void* d_stats = nullptr;            // fin_depth_stat[n_unitigs]
+    uint64_t stage_len = 0;
+    std::mutex scan_mu;                 // one download at a time scans through the staging buffer
+    AccPending pend;
+};
+static_assert(sizeof(fin_depth_stat) == 16 && sizeof(FinDepthStat) == 16, "fin_depth_stat is 16 bytes on both sides");
+static uint32_t* depth_flags(const fin_depth* d) { return (uint32_t*)((int32_t*)d->d_diff + d->total_len + 1); }
+static size_t depth_bytes(const fin_depth* d) { return (size_t)(d->total_len + 2) * 4; }
+
+void fin_depth_free(fin_depth* d) {
+    if (!d) return;
+    if (d->device >= 0) (void)hipSetDevice(d->device);
+    d->pend.drop();
+    (void)hipFree(d->d_diff); (void)hipFree(d->d_stage); (void)hipFree(d->d_tile); (void)hipFree(d->d_stats);
+    delete d;
+}
+
+int fin_depth_create(const fin_index* idx, int device, fin_depth** out, char* err, size_t errlen) {
+    if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    const fin_index::Replica* rep = idx->replica_on(device);
+    if (!rep) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
+    HIPCHK(hipSetDevice(device));
+    fin_depth* d = new (std::nothrow) fin_depth();
+    if (!d) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
+    d->idx = idx; d->device = device; d->n_unitigs = idx->n_unitigs; d->total_len = idx->total_len; d->d_ends = rep->dev.ends;
+    if (hipMalloc(&d->d_diff, depth_bytes(d)) != hipSuccess) { (void)hipGetLastError(); delete d; set_err(err, errlen, "out of device memory (depth difference array)"); return FIN_ENOMEM; }
+    if (hipMemset(d->d_diff, 0, depth_bytes(d)) != hipSuccess) { fin_depth_free(d); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    *out = d;
+    return FIN_OK;
+}
+
+int fin_depth_reset(fin_depth* d, void* hip_stream) {
+    if (!d) return FIN_EINVAL;
+    if (hipSetDevice(d->device) != hipSuccess) return FIN_ENODEV;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (hipMemsetAsync(d->d_diff, 0, depth_bytes(d), st) != hipSuccess) return FIN_ENODEV;
+    return d->pend.mark(st, nullptr, 0);
+}
+
+void* fin_depth_device_diff(const fin_depth* d) { return d ? d->d_diff : nullptr; }
+
+int fin_batch_add_depth(fin_batch* b, fin_depth* d, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !d) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (const int brc = acc_behind_run(b, d->idx, d->device, st, err, errlen)) return brc;
+    const int rc = fin_launch_depth_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, d->d_ends,
+                                        (uint32_t)d->n_unitigs, d->total_len, d->d_diff, depth_flags(d), b->d_ovf_count, b->last_ovf_cap, st);
+    if (rc != 0) { set_err(err, errlen, std::string("depth kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    return d->pend.mark(st, err, errlen);
+}
+
+int fin_depth_download(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, fin_depth_stat* stats_out, uint64_t* total, char* err, size_t errlen) {
+    if (!d) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(d->device));
+    if (const int wrc = d->pend.wait(err, errlen)) return wrc;
+    uint32_t flags = 0;
+    HIPCHK(hipMemcpy(&flags, depth_flags(d), 4, hipMemcpyDeviceToHost));
+    if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)"); return FIN_ELIMIT; }
+    if (flags & 2u) { set_err(err, errlen, "a pair with a unitig number or a position outside the index was met (not counted)"); return FIN_EINVAL; }
+    if (total) *total = 0;
+    const bool want_stats = stats_out || total;
+    if (!depth_out && !want_stats) return FIN_OK;
+    if (d->total_len == 0 || d->n_unitigs == 0) return FIN_OK;
+    // the prefix sum, a chunk of the difference array at a time through one staging buffer: no second array of total_len entries on the device
+    const uint32_t dbg = (uint32_t)optv(d->idx, O_debug_depth_tile);
+    const uint32_t tile = dbg ? dbg : fin_depth_max_tile(), chunk_tiles = dbg ? 64u : fin_depth_max_chunk_tiles();
+    const uint64_t chunk = (uint64_t)tile * chunk_tiles;
+    std::lock_guard<std::mutex> g(d->scan_mu);
+    if (!d->d_stage) {
+        d->stage_len = std::min<uint64_t>((uint64_t)fin_depth_max_tile() * fin_depth_max_chunk_tiles(), d->total_len);
+        if (hipMalloc((void**)&d->d_stage, (size_t)d->stage_len * 4) != hipSuccess) { (void)hipGetLastError(); d->d_stage = nullptr; set_err(err, errlen, "out of device memory (depth staging buffer)"); return FIN_ENOMEM; }
+    }
+    if (!d->d_tile && hipMalloc((void**)&d->d_tile, ((size_t)fin_depth_max_chunk_tiles() + 1) * 4) != hipSuccess) { (void)hipGetLastError(); d->d_tile = nullptr; set_err(err, errlen, "out of device memory (depth tile sums)"); return FIN_ENOMEM; }
+    if (want_stats && !d->d_stats && hipMalloc(&d->d_stats, (size_t)d->n_unitigs * sizeof(fin_depth_stat)) != hipSuccess) { (void)hipGetLastError(); d->d_stats = nullptr; set_err(err, errlen, "out of device memory (depth statistics)"); return FIN_ENOMEM; }
+    uint32_t* const d_carry = d->d_tile + fin_depth_max_chunk_tiles();
+    HIPCHK(hipMemsetAsync(d_carry, 0, 4, nullptr));
+    if (want_stats) HIPCHK(hipMemsetAsync(d->d_stats, 0, (size_t)d->n_unitigs * sizeof(fin_depth_stat), nullptr));
+    for (uint64_t base = 0; base < d->total_len; base += chunk) {
+        const uint64_t n = std::min<uint64_t>(chunk, d->total_len - base);
+        int rc = fin_launch_depth_scan_chunk((const int32_t*)d->d_diff + base, n, tile, d->d_tile, d_carry, d->d_stage, nullptr);
+        if (rc == 0 && want_stats) rc = fin_launch_depth_stats(d->d_stage, base, n, d->d_ends, (uint32_t)d->n_unitigs, min_depth, d->d_stats, nullptr);
+        if (rc != 0) { set_err(err, errlen, std::string("depth scan kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+        if (depth_out) HIPCHK(hipMemcpy(depth_out + base, d->d_stage, (size_t)n * 4, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels, and done before the next chunk is staged)
+    }
+    if (want_stats) {
+        std::vector<fin_depth_stat> tmp;
+        fin_depth_stat* dst = stats_out;
+        if (!dst) { tmp.resize((size_t)d->n_unitigs); dst = tmp.data(); }
+        HIPCHK(hipMemcpy(dst, d->d_stats, (size_t)d->n_unitigs * sizeof(fin_depth_stat), hipMemcpyDeviceToHost));
+        if (total) { uint64_t t = 0; for (uint64_t u = 0; u < d->n_unitigs; u++) t += dst[u].sum; *total = t; }
+    }
+    return FIN_OK;
+}
+
+// host: the depth from records + stream -- fin_expand_records' arithmetic, the pairs never made.  A chunk of reads per thread; with more than one thread the
+// positions are added atomically
+int fin_records_depth(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
+                      uint64_t n_unitigs, uint32_t* depth_out, int n_threads) {
+    if ((n_reads && !recs) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && (!unitig_ends || !depth_out))) return FIN_EINVAL;
+    int64_t prev = 0;
+    for (uint64_t u = 0; u < n_unitigs; u++) { if (unitig_ends[u] < prev) return FIN_EINVAL; prev = unitig_ends[u]; }
+    const uint64_t total_len = (uint64_t)prev;
+    for (uint64_t g = 0; g < total_len; g++) depth_out[g] = 0;
+    int T = n_threads > 0 ? n_threads : fin_host_threads();
+    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
+    std::vector<uint64_t> str0((size_t)T + 1, 0);
+    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
+        const auto lh = bounds(t);
+        uint64_t sp = 0;
+        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
+        str0[(size_t)t + 1] = sp;
+    }
+    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
+    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
+    bool ok = true;
+#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
+    for (int t = 0; t < T; t++) {
+        const auto lh = bounds(t);
+        uint64_t sp = str0[(size_t)t];
+        bool good = true;
+        // offsets [off_lo, off_hi) of unitig u, each the first base of a found k-mer: it must lie whole inside the unitig
+        auto add = [&](uint64_t u, uint64_t off_lo, uint64_t off_hi) {
+            if (off_lo >= off_hi) return;
+            if (u >= n_unitigs) { good = false; return; }
+            const uint64_t start = u ? (uint64_t)unitig_ends[u - 1] : 0, end = (uint64_t)unitig_ends[u];
+            if (start + off_hi - 1 + (uint64_t)k > end) { good = false; return; }
+            for (uint64_t g = start + off_lo; g < start + off_hi; g++) {
+                if (T == 1) depth_out[g]++;
+                else __atomic_fetch_add(depth_out + g, 1u, __ATOMIC_RELAXED);
+            }
+        };
+        for (uint64_t r = lh.first; r < lh.second && good; r++) {
+            const fin_read_record& R = recs[r];
+            const uint32_t nk = R.nk, kind = R.meta >> 16;
+            if (kind == 0u) {
+                const int32_t* const src = stream_pairs + 2 * sp;
+                for (uint32_t i = 0; i < nk; i++) {
+                    const int32_t u = src[2 * i], off = src[2 * i + 1];
+                    if (u >= 0 && off >= 0) add((uint64_t)u, (uint64_t)off, (uint64_t)off + 1);
+                    else if (u != -1) good = false;
+                }
+                sp += nk;
+            } else if (kind == 1u && nk) {
+                const uint32_t nE = R.meta & 0xFFu;
+                uint32_t done_to = 0, from = 0;   // `from`: where the found stretch in front of the next gap begins
+                for (uint32_t e = 0; e < nE && e < 8u; e++) {
+                    const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
+                    uint32_t lo = E >= (uint32_t)(k - 1) ? E - (uint32_t)(k - 1) : 0u, hi = E < nk ? E : nk - 1u;
+                    if (lo < done_to) lo = done_to;
+                    if (lo <= hi) { add(R.u, (uint64_t)R.off0 + from, (uint64_t)R.off0 + lo); from = hi + 1u; }
+                    if (hi + 1u > done_to) done_to = hi + 1u;
+                }
+                add(R.u, (uint64_t)R.off0 + from, (uint64_t)R.off0 + nk);
+            }
+        }
+        ok = good && ok;
+    }
+    return ok ? FIN_OK : FIN_EINVAL;
+}
+
 int fin_batch_step_time(const fin_batch* b, uint64_t skip_first, double ms_parts[5], uint64_t* n_runs) {
     if (!b) return FIN_EINVAL;
     double t[5] = {0, 0, 0, 0, 0}; uint64_t n = 0;
@@ -1877,6 +2052,7 @@ struct TextSink {
     char* buf = nullptr; uint64_t cap = 0;
     fin_hits* hits = nullptr;   // the profile instead of text (fin_search_batch_unitig_counts): every sub-batch is added on the device, nothing comes back
     fin_cover* cover = nullptr; // the coverage bitmap (fin_search_batch_add_cover); with `hits` too, both adds go behind the same run
+    fin_depth* depth = nullptr; // the per-position depth (fin_search_batch_add_depth), likewise
     // (segments when `seg_offs` is set: fin_search_batch_segments -- `len` then counts a sub-batch's segments, seg_offs is rebased to the whole read set)
     uint64_t* seg_offs = nullptr; fin_segment* segs = nullptr; uint64_t seg_cap = 0; std::atomic<bool> seg_over{false};
     std::vector<uint64_t> len; std::vector<char> known;
@@ -1947,10 +2123,11 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
             }
             if (rc == FIN_OK) { b->text_mode = ts ? 2 : 0; rc = fin_batch_run(b, strands, (void*)b->own_stream, e, sizeof e); }   // (text sink: the text is the only product)
             uint64_t pos = 0;
-            if (rc == FIN_OK && ts && (ts->hits || ts->cover)) {
+            if (rc == FIN_OK && ts && (ts->hits || ts->cover || ts->depth)) {
                 // (behind the run on the batch's own stream: the next batch_load on that stream finds the add done; fin_hits_download waits for the last ones)
                 if (ts->hits) rc = fin_batch_add_hits(b, ts->hits, (void*)b->own_stream, e, sizeof e);
                 if (rc == FIN_OK && ts->cover) rc = fin_batch_add_cover(b, ts->cover, (void*)b->own_stream, e, sizeof e);
+                if (rc == FIN_OK && ts->depth) rc = fin_batch_add_depth(b, ts->depth, (void*)b->own_stream, e, sizeof e);
             } else
             if (rc == FIN_OK && ts && ts->seg_offs) {
                 // segments: made behind the run on the device; the sub-batch's land behind those of all earlier sub-batches, its seg_offs at its reads' numbers
@@ -2190,6 +2367,28 @@ int fin_search_batch_unitig_coverage(const fin_index* idx, const char* bases, co
     if (rc == FIN_OK) rc = fin_cover_download(c, nullptr, covered_out, nullptr, err, errlen);
     if (rc == FIN_OK && h) rc = fin_hits_download(h, nullptr, n_positive, err, errlen);
     fin_hits_free(h); fin_cover_free(c);
+    return rc;
+}
+
+int fin_search_batch_add_depth(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_depth* d, char* err, size_t errlen) {
+    if (!idx || !offsets || !d || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (d->idx != idx) { set_err(err, errlen, "the accumulator belongs to another index"); return FIN_EINVAL; }
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.depth = d;
+    return search_range_on(idx, d->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+}
+
+int fin_search_batch_unitig_depth(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint32_t min_depth,
+                                  fin_depth_stat* stats_out, uint64_t* n_positive, char* err, size_t errlen) {
+    if (!idx || !offsets || (idx->n_unitigs && !stats_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (n_positive) *n_positive = 0;
+    fin_depth* d = nullptr;
+    int rc = fin_depth_create(idx, idx->replicas[0].device, &d, err, errlen);
+    if (rc != FIN_OK) return rc;
+    rc = fin_search_batch_add_depth(idx, bases, offsets, n_reads, strands, d, err, errlen);
+    if (rc == FIN_OK) rc = fin_depth_download(d, min_depth, nullptr, stats_out, n_positive, err, errlen);   // (the found k-mers are the sum of the depths)
+    fin_depth_free(d);
     return rc;
 }
 

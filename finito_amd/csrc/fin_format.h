@@ -157,6 +157,8 @@ struct FinDevIndex {
 // first base at offset off0 and disagrees with the text at positions E (meta bits 0..7: how many; 16 bits each, Es then Es2); meta >> 16 = 2: every
 // k-mer of the read is absent.  Slot sl of strand A is (u, off0 + sl) unless a disagreeing position lies in [sl, sl + k - 1]
 struct FinFastRec { uint32_t u, off0, meta, nk; uint64_t Es, Es2; };
+// A unitig's depth statistics as the device keeps them (fin_depth.hip): the layout of fin_depth_stat (include/finito_amd.h)
+struct FinDepthStat { unsigned long long sum; uint32_t max, n_at_least; };
 // The compact k-mer table's bucket (FinDevIndex::kt3): four slots {g, meta}.  An empty slot is all ones; a used slot's meta has bit 31 clear.
 struct FinKt3Bucket { uint32_t w[8]; };
 struct FinKtxSlot { uint32_t k0_lo, k0_hi, k1_lo, k1_hi, g, claim, pad0, pad1; };

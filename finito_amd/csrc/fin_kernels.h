@@ -130,6 +130,19 @@ int fin_launch_cover_add(const void* frec, const uint64_t* out_offs, const void*
                          hipStream_t stream);
 // covered[u] = popcount of unitig u's stretch of the bitmap (uint64[n_unitigs], zeroed here on `stream`)
 int fin_launch_cover_count(const void* bits, const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len, void* covered, hipStream_t stream);
+// fin_depth.hip: diff[g_lo] += 1, diff[g_hi + 1] -= 1 for every straight stretch of found places [g_lo, g_hi] of a finished step -- int32 diff[total_len + 1], the
+// difference array of the per-position depth.  frec / out_offs / pairs / ovf_count / ovf_cap as fin_launch_hits_add.  flags: one u32 of the accumulator (bit 0: the
+// step's overflow list overran -- nothing added; bit 1: a slot with a unitig number >= n_unitigs or a place >= total_len met -- it counts as absent)
+int fin_launch_depth_add(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint64_t n_pairs, uint32_t k, const uint32_t* ends_p,
+                         uint32_t n_unitigs, uint64_t total_len, void* diff, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, hipStream_t stream);
+// the prefix sum of one chunk of the difference array: depth[0 .. n) = *carry + diff[0] + ... + diff[i]; n <= tile * fin_depth_max_chunk_tiles(),
+// 1 <= tile <= fin_depth_max_tile(); tile_sum: a u32 per tile of the chunk; *carry moves on to the chunk's end.  Three kernels, none waits for another block
+uint32_t fin_depth_max_tile(void);
+uint32_t fin_depth_max_chunk_tiles(void);
+int fin_launch_depth_scan_chunk(const void* diff, uint64_t n, uint32_t tile, uint32_t* tile_sum, uint32_t* carry, uint32_t* depth, hipStream_t stream);
+// stats[u] += {sum, max, positions with depth >= min_depth} (FinDepthStat, zeroed by the caller) over depth[0 .. n), the depths of text positions g_base ..
+int fin_launch_depth_stats(const uint32_t* depth, uint64_t g_base, uint64_t n, const uint32_t* ends_p, uint32_t n_unitigs, uint32_t min_depth, void* stats,
+                           hipStream_t stream);
 // fin_segments.hip: a finished step's results as segments {u, off, slot, len} of 16 bytes, dense and in read order, delimited per read by seg_offs[n_reads + 1].
 // frec / out_offs / pairs as fin_launch_hits_add.  fin_launch_sgm_count: cnt[n_reads] u32, blk_sum[fin_sgm_blocks()] u32, blk_off as many u64, *total the
 // batch's segments; fin_launch_sgm_write, once segs has room for them: seg_offs and the segments

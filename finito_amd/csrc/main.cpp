@@ -452,13 +452,19 @@ static const char* SEARCH_HELP =
     "                        Costs one more search of every chunk on the device, beside the one for the text and the one for\n"
     "                        --unitig-counts; with --no-text 1 and no --unitig-counts a chunk is still searched twice (the second\n"
     "                        pass counts the found k-mers the log reports).\n"
+    "      --unitig-depth FILE  also write the run's per-position depth over the unitig set, summed up per unitig: one line\n"
+    "                        `unitig<TAB>kmers<TAB>sum<TAB>max<TAB>solid` per unitig of the index, in unitig order -- kmers = length - k + 1, sum = the\n"
+    "                        unitig's count of --unitig-counts, max = the most often any one of its k-mers was found, solid = how many of its k-mers\n"
+    "                        were found at least T times (--min-depth). Kept on the first GPU, 4 bytes per base of the unitig text, from one more\n"
+    "                        search of every chunk; goes with -o, --unitig-counts, --unitig-coverage and --segments. Not for a partitioned index.\n"
+    "      --min-depth T     the T of --unitig-depth (default: 1); only with --unitig-depth\n"
     "      --segments FILE   also write every read's path through the unitig set: one line `read<TAB>slot<TAB>length<TAB>unitig<TAB>offset<TAB>+|-` per\n"
     "                        segment -- `length` consecutive k-mers of read `read` (0-based ordinal in the query file, counted through a list of\n"
     "                        query files), from its k-mer number `slot` on, found in `unitig` at `offset`, `offset + 1`, ... (+) or `offset`,\n"
     "                        `offset - 1`, ... (-). Reads without a found k-mer have no line. Made on the first GPU from one more search of every\n"
     "                        chunk; goes with -o, --unitig-counts and --unitig-coverage. Not for a partitioned index.\n"
-    "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage or --segments): do not make or write the pair text, the profile, the\n"
-    "                        coverage and / or the segments are the only results\n"
+    "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth or --segments): do not make or write the pair text, the\n"
+    "                        profile, the coverage, the depth and / or the segments are the only results\n"
     "  -h, --help            Print usage\n";
 
 static int build_fmin(int argc, char** argv) {
@@ -633,6 +639,12 @@ static void add_cover_chunk(const FinimizerIndex& index, const char* bases, cons
     char err[512] = {0};
     if (fin_search_batch_add_cover(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
 }
+// --unitig-depth FILE: the same for the per-position depth (fin_search_batch_add_depth)
+static fin_depth* g_depth = nullptr;
+static void add_depth_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
+    char err[512] = {0};
+    if (fin_search_batch_add_depth(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_depth, err, sizeof err) != FIN_OK) throw runtime_error(err);
+}
 // --segments FILE: every chunk's segments are made on the first device (fin_search_batch_segments) and written as lines, by the search stage, in chunk order
 static FILE* g_seg_file = nullptr;
 static uint64_t g_seg_read0 = 0;   // reads in the chunks (and query files) before this one
@@ -742,6 +754,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                     if (g_no_text) {   // the profile / the coverage / the segments are all this chunk is searched for
                         if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_depth) add_depth_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_seg_file) c->positive = segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                     }
                     else {
@@ -758,6 +771,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         }
                         if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);   // (a second pass over the chunk on the device: the text is what bounds this loop)
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_depth) add_depth_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_seg_file) (void)segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                     }
                     if (g_strand_counts) {
@@ -874,11 +888,20 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "segments", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("segments")) throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage or --segments (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments")) throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth or --segments (the run would have no result)");
+    if (o.has("min-depth") && !o.has("unitig-depth")) throw runtime_error("--min-depth is only legal together with --unitig-depth");
+    uint32_t min_depth = 1;
+    if (o.has("min-depth")) {
+        const string v = o.get("min-depth");
+        size_t used = 0; unsigned long long t = 0;
+        try { t = stoull(v, &used); } catch (...) { used = 0; }
+        if (v.empty() || used != v.size() || v[0] == '-' || t > 0xFFFFFFFFull) throw runtime_error("--min-depth wants a number from 0 to 4294967295");
+        min_depth = (uint32_t)t;
+    }
     if (g_no_text && g_strand_counts) throw runtime_error("--no-text 1 and --strand-counts 1 do not go together");
     if (!o.has("query-file")) throw runtime_error("Option 'query-file' has no value");
     if (!o.has("index-file")) throw runtime_error("Option 'index-file' has no value");
@@ -901,6 +924,8 @@ static int search_fmin(int argc, char** argv) {
     if (!counts_file.empty()) check_writable(counts_file);
     const string cover_file = o.get("unitig-coverage", "");
     if (!cover_file.empty()) check_writable(cover_file);
+    const string depth_file = o.get("unitig-depth", "");
+    if (!depth_file.empty()) check_writable(depth_file);
     const string seg_file = o.get("segments", "");
     if (!seg_file.empty()) check_writable(seg_file);
     cerr << "Loading index..." << endl;
@@ -940,6 +965,7 @@ static int search_fmin(int argc, char** argv) {
     const int64_t t_l1 = cur_time_micros();
     if (!counts_file.empty() && index.partitioned()) throw runtime_error("--unitig-counts is not available with a partitioned index");
     if (!cover_file.empty() && index.partitioned()) throw runtime_error("--unitig-coverage is not available with a partitioned index");
+    if (!depth_file.empty() && index.partitioned()) throw runtime_error("--unitig-depth is not available with a partitioned index");
     if (!seg_file.empty() && index.partitioned()) throw runtime_error("--segments is not available with a partitioned index");
     index.to_device();
     struct HitsOwner { ~HitsOwner() { fin_hits_free(g_hits); g_hits = nullptr; } } hits_owner;
@@ -951,6 +977,11 @@ static int search_fmin(int argc, char** argv) {
     if (!cover_file.empty()) {
         char err[512] = {0};
         if (fin_cover_create(index.handle(), first_dev, &g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    }
+    struct DepthOwner { ~DepthOwner() { fin_depth_free(g_depth); g_depth = nullptr; } } depth_owner;
+    if (!depth_file.empty()) {
+        char err[512] = {0};
+        if (fin_depth_create(index.handle(), first_dev, &g_depth, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     struct SegOwner { ~SegOwner() { if (g_seg_file) fclose(g_seg_file); g_seg_file = nullptr; } } seg_owner;
     if (!seg_file.empty()) {
@@ -1000,6 +1031,25 @@ static int search_fmin(int argc, char** argv) {
         ofstream cf(cover_file, ios::binary | ios::trunc);
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + cover_file);
+    }
+    if (g_depth) {   // the depth, after the last chunk: the prefix sum and the statistics on the device, one line per unitig of the index
+        char err[512] = {0};
+        const size_t nu = (size_t)index.number_of_unitigs();
+        vector<fin_depth_stat> stats(nu + 1);
+        vector<int64_t> ends(nu + 1);
+        if (fin_depth_download(g_depth, min_depth, nullptr, stats.data(), nullptr, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        if (fin_index_export(index.handle(), FIN_X_ENDS, ends.data(), nu * sizeof(int64_t), err, sizeof err) != FIN_OK) throw runtime_error(err);
+        const int64_t k = index.get_k();
+        string text;
+        text.reserve(nu * 32);
+        for (size_t u = 0; u < nu; u++) {
+            const int64_t len = ends[u] - (u ? ends[u - 1] : 0);
+            text += to_string(u); text += '\t'; text += to_string(len - k + 1); text += '\t'; text += to_string(stats[u].sum); text += '\t';
+            text += to_string(stats[u].max); text += '\t'; text += to_string(stats[u].n_at_least); text += '\n';
+        }
+        ofstream cf(depth_file, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + depth_file);
     }
     if (g_hits && !counts_file.empty()) {   // the profile, after the last chunk: one line per unitig of the index
         char err[512] = {0};

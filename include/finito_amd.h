@@ -496,6 +496,54 @@ void fin_cover_free(fin_cover* c);
 int fin_records_cover(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
                       uint64_t n_unitigs, uint64_t* bits_out, int n_threads);
 
+/* ---- DEPTH of a run over the unitig set: how many times each k-mer position of the unitig text was found ----
+ * What lies between fin_hits (the depth summed over a unitig) and fin_cover (where it is above zero): abundance that one repeated stretch does not dominate,
+ * "solid" k-mers seen at least t times, breakpoints and collapsed repeats as steps along a unitig.
+ *   depth[g], for g in [0, fin_index_total_len), is the number of found pairs (u, off) with start(u) + off == g, summed over every run added since the last
+ *   reset; start(u) is unitigs.ends[u - 1] of FIN_X_ENDS (0 for u = 0; ends_p[u] on the device) -- the geometry of fin_cover.
+ *  - bit g of the bitmap is depth[g] > 0, and fin_hits' count of unitig u is the sum of depth over u;
+ *  - the last k - 1 positions of every unitig stay 0: no k-mer begins there;
+ *  - on a set that is not disjoint only the place the reference reports for a k-mer counts (as for fin_hits and fin_cover);
+ *  - adding the same run twice doubles its contribution: unlike the bitmap, depth is not idempotent;
+ *  - depth is uint32 and the arithmetic is modulo 2^32: the result is exact while every position's true depth is below 2^32.  Nothing saturates.
+ * The accumulator is an int32 DIFFERENCE array of total_len + 1 entries in HBM beside one replica (4 bytes per indexed base).  Everything a step leaves behind is a
+ * set of ranges: a stretch of found places [g_lo, g_hi] is +1 at g_lo and -1 at g_hi + 1, whichever way the offsets run in the read -- two atomic adds per
+ * stretch, not one per k-mer (fin_depth.hip).  fin_depth_download makes the depths with a prefix sum on the device, a chunk at a time through a fixed staging
+ * buffer, and leaves the difference array as it is: add, download, add, download gives the sum.
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi, sums across the ranks of a job (a caller with several GPUs keeps an accumulator per
+ * replica and adds the downloaded arrays), the C++ mirror (FinimizerIndex.hh), medians on the device, saturation. */
+typedef struct fin_depth fin_depth;
+/* a unitig's statistics: the sum of its positions' depths (= fin_hits' count), the greatest, and how many positions have depth >= min_depth */
+typedef struct fin_depth_stat { uint64_t sum; uint32_t max; uint32_t n_at_least; } fin_depth_stat;   /* 16 bytes */
+/* a zeroed accumulator for `idx` on `device` (FIN_ENODEV: the index has no replica there) */
+int fin_depth_create(const fin_index* idx, int device, fin_depth** out, char* err, size_t errlen);
+/* zeroes the accumulator, on the given stream */
+int fin_depth_reset(fin_depth* d, void* hip_stream);
+/* depth += the found places of the batch's most recent run: one launch on the given stream, ordered behind that run; does not wait.  fin_batch_add_cover's
+ * ordering and refusal rules: FIN_EINVAL when the batch has not run or batch and accumulator belong to different indexes or devices; records, pairs and text are
+ * read only; a run whose overflow list overran adds nothing and fin_depth_download reports FIN_ELIMIT until the reset.  A slot whose unitig number or place lies
+ * outside the index counts as absent and fin_depth_download reports FIN_EINVAL "outside the index" until the reset. */
+int fin_batch_add_depth(fin_batch* b, fin_depth* d, void* hip_stream, char* err, size_t errlen);
+/* the difference array, int32[fin_index_total_len + 1] in HBM (valid once the adds on their streams have finished): depth[g] = diff[0] + ... + diff[g] */
+void* fin_depth_device_diff(const fin_depth* d);
+/* waits for every add and reset issued so far, then runs the prefix sum and the statistics on the device.  depth_out[fin_index_total_len],
+ * stats_out[fin_index_n_unitigs] (n_at_least counted against min_depth), *total = the sum over all positions = the k-mers found; each may be NULL.  The
+ * accumulator is not changed. */
+int fin_depth_download(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, fin_depth_stat* stats_out, uint64_t* total, char* err, size_t errlen);
+/* fin_search_batch_add_cover's loop with the depth as its product: host buffers in, sub-batches pipelined, each run in text mode 2 where the fast path is on and
+ * added on the device behind its run, nothing downloaded */
+int fin_search_batch_add_depth(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_depth* d, char* err, size_t errlen);
+/* host buffers in, stats_out[fin_index_n_unitigs] out (a fresh accumulator on the first replica's device); *n_positive (may be NULL) = the k-mers found, as
+ * fin_search_batch reports it: the sum of the depths */
+int fin_search_batch_unitig_depth(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint32_t min_depth,
+                                  fin_depth_stat* stats_out, uint64_t* n_positive, char* err, size_t errlen);
+/* host, no device: the same depths from records + stream (the arithmetic of fin_expand_records, the pairs never made).  unitig_ends[n_unitigs] as FIN_X_ENDS;
+ * depth_out[unitig_ends[n_unitigs - 1]] is overwritten.  n_threads <= 0: all cores.  FIN_EINVAL: a unitig number >= n_unitigs, a k-mer that does not lie inside
+ * its unitig, or a stream that is not this record set's */
+int fin_records_depth(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
+                      uint64_t n_unitigs, uint32_t* depth_out, int n_threads);
+void fin_depth_free(fin_depth* d);
+
 /* ---- results as SEGMENTS: a read's path through the unitig set, made on the device for every read ----
  * Records (above) are compact only for the reads the fast path finished; a read the pipeline searched -- an indel, a mosaic over several unitigs, more than eight
  * substitutions, any read at k > 63 or in a forward-only search -- still comes back as 8 bytes per k-mer, although it is almost always two to five straight
