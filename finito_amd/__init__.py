@@ -125,6 +125,9 @@ def lib():
         L.fin_batch_n_base_strands.restype = u64
         L.fin_batch_n_base_strands.argtypes = [vp]
         L.fin_batch_set_pairs.argtypes = [vp, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]
+        L.fin_batch_set_records.argtypes = [vp, vp, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]
+        L.fin_batch_records.argtypes = [vp, u64p, cp, C.c_size_t]
+        L.fin_batch_download_records.argtypes = [vp, vp, vp, cp, C.c_size_t]
         L.fin_batch_device_pairs.restype = vp
         L.fin_batch_device_pairs.argtypes = [vp]
         L.fin_batch_download.argtypes = [vp, i32p, u64p, cp, C.c_size_t]
@@ -328,6 +331,29 @@ class Batch:
         a = np.ascontiguousarray(pairs, dtype=np.int32)
         err = C.create_string_buffer(512)
         _check(self.L.fin_batch_set_pairs(self.h, a.ctypes.data_as(C.POINTER(C.c_int32)), err, 512), err)
+
+    def set_records(self, recs, pairs=None):
+        """diagnostic: overwrite the records the most recent run left -- and, with `pairs`, the batch's pairs -- in HBM (fin_batch_set_records) -- for tests of
+        the record consumers.  Refused unless that run left records and every record passes the host-side checks of include/finito_amd.h"""
+        r = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        if len(r) != self.n_reads:
+            raise FinitoError(FIN_EINVAL, "set_records: %d records for %d reads" % (len(r), self.n_reads))
+        a = None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32)
+        if a is not None and a.size != 2 * self.n_kmers:
+            raise FinitoError(FIN_EINVAL, "set_records: %d pair words for %d k-mers" % (a.size, self.n_kmers))
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_set_records(self.h, r.ctypes.data_as(C.c_void_p), None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32)), err, 512), err)
+
+    def records(self):
+        """the most recent run's results as records + stream (fin_batch_records + fin_batch_download_records): (recs RECORD_DTYPE[n_reads], int32 stream [n, 2] --
+        the pairs of the kind-0 reads in read order)"""
+        n = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_records(self.h, C.byref(n), err, 512), err)
+        recs = np.zeros(max(self.n_reads, 1), dtype=RECORD_DTYPE)
+        stream = np.zeros((max(int(n.value), 1), 2), dtype=np.int32)
+        _check(self.L.fin_batch_download_records(self.h, recs.ctypes.data_as(C.c_void_p), stream.ctypes.data_as(C.c_void_p), err, 512), err)
+        return recs[: self.n_reads], stream[: int(n.value)]
 
     def device_pairs_ptr(self):
         return int(self.L.fin_batch_device_pairs(self.h) or 0)

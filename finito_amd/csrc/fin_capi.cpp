@@ -1018,6 +1018,48 @@ int fin_batch_set_pairs(fin_batch* b, const int32_t* pairs, char* err, size_t er
     return FIN_OK;
 }
 
+// diagnostic (tests of the record consumers): overwrite the records of the most recent run -- and, optionally, its pairs -- with hand-made ones.  Everything a
+// kernel trusts is checked here, on the host, before a byte is copied (include/finito_amd.h); no kernel is launched
+int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32_t* pairs, char* err, size_t errlen) {
+    if (!b || !recs) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->ran || !b->last_frec || !b->d_frec) {
+        set_err(err, errlen, "the most recent run left no records (kernel 4, merged strands, fast path on, text mode 1 or 2): there is nothing to overwrite");
+        return FIN_EINVAL;
+    }
+    const uint32_t k = b->dev.k;
+    for (uint64_t r = 0; r < b->n_reads; r++) {
+        const fin_read_record& R = recs[r];
+        const uint64_t nk = b->h_out_offs[r + 1] - b->h_out_offs[r];
+        const uint32_t kind = R.meta >> 16;
+        const char* what = nullptr;
+        if (kind > 2u) what = "a kind that is not 0, 1 or 2";
+        else if (kind == 0u) {
+            if (R.u || R.off0 || R.meta || R.nk || R.Es || R.Es2) what = "a kind-0 record that is not all zero (the device tells a finished read by meta >> 16 != 0)";
+        } else if (R.nk != nk || nk == 0) what = "nk is not the read's number of k-mers, or the read has none";
+        else if (kind == 1u) {
+            const uint32_t nE = R.meta & 0xFFu;
+            if (nE > 8u) what = "more than eight positions";
+            uint32_t prev = 0;
+            for (uint32_t e = 0; e < 8u && !what; e++) {
+                const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
+                if (e >= nE) { if (E) what = "an unused position field that is not zero"; continue; }
+                if (E < prev) what = "positions that do not ascend";
+                else if ((uint64_t)E >= nk + k - 1u) what = "a position at or beyond nk + k - 1";
+                prev = E;
+            }
+        }
+        if (what) { set_err(err, errlen, "record " + std::to_string(r) + ": " + what); return FIN_EINVAL; }
+    }
+    HIPCHK(hipSetDevice(b->device));
+    if (b->last_stream) HIPCHK(hipStreamSynchronize(b->last_stream));
+    if (b->n_reads) HIPCHK(hipMemcpy(b->d_frec, recs, (size_t)b->n_reads * sizeof(FinFastRec), hipMemcpyHostToDevice));
+    if (pairs && b->n_kmers) HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
+    // last_frec / last_text_only stay as the run left them (a text-only batch still refuses its pairs); whatever was made from the old records goes
+    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0;
+    b->rec_ready = false; b->rec_passthrough = false; b->rec_stream_pairs = 0;
+    return FIN_OK;
+}
+
 // (a push beyond the overflow list's capacity is dropped on the device -- fin_ovf_push -- and that read would keep a partial
 //  result: the list is sized so that this cannot happen, and if it ever does NO entry point delivers results of that run -- pairs, ranges or text)
 static int batch_overrun_check(fin_batch* b, hipStream_t st, char* err, size_t errlen) {

@@ -414,6 +414,18 @@ int fin_expand_records(const fin_read_record* recs, uint64_t n_reads, const int3
  * the batch's pairs) fin_batch_records gathers the stream on the device and says how long it is; fin_batch_download_records copies both to the host */
 int fin_batch_records(fin_batch* b, uint64_t* n_stream_pairs, char* err, size_t errlen);
 int fin_batch_download_records(fin_batch* b, fin_read_record* recs_out, int32_t* stream_pairs_out, char* err, size_t errlen);
+/* diagnostic (tests of everything that consumes records on the device: the record-derived text, fin_batch_add_hits / _cover / _depth, fin_batch_segments,
+ * fin_batch_records), the sibling of fin_batch_set_pairs: overwrite the records the batch's most recent run left with recs[n_reads] and, when pairs != NULL, its
+ * pairs with pairs[2 * n_kmers].  Legal only after a run that left records (kernel 4, merged strands, fast path on, text mode 1 or 2): FIN_EINVAL otherwise.
+ * Waits for that run, copies, launches no kernel.  The batch stays what the run made it -- after a text-mode-2 run fin_batch_download still refuses the pairs --
+ * and forgets what it made from the old records: segments, the gathered stream, the formatted text and the count taken from it.
+ * The kernels trust a record's fields, so they are checked on the host before anything is copied; FIN_EINVAL with a message unless, for every read,
+ *  - kind = meta >> 16 is 0, 1 or 2;
+ *  - kind 1 or 2: nk is the read's own number of k-mers, max(0, length - k + 1), and at least 1;
+ *  - kind 1: meta & 0xFF <= 8, the positions ascend (equal neighbours allowed), each is below nk + k - 1, position fields beyond meta & 0xFF are zero;
+ *  - kind 0: the whole record is zero, nk too (the device tells a finished read by meta >> 16 != 0; fin_batch_records stamps nk later).
+ * u and off0 are NOT checked: a place outside the index is something the consumers themselves handle (flag bit 1 of the accumulators). */
+int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32_t* pairs /* may be NULL */, char* err, size_t errlen);
 
 /* ---- the PROFILE of a run over the unitig set: how many query k-mers were found in each unitig ----
  * For abundance estimates, presence / absence of a unitig in a sample, unitig-to-colour tables: the caller wants one number per unitig, not a pair per

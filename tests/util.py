@@ -191,3 +191,125 @@ def defer_family_case(rng, case, k, n_reads=60):
                 w = list(u); w[int(rng.integers(0, len(w)))] = "ACGTN"[int(rng.integers(0, 5))]; reads.append("".join(w))
     reads += [rc(r) for r in reads]
     return g, unitigs, reads
+
+
+# ---- hand-made fast-path records (include/finito_amd.h: fin_read_record; fin_batch_set_records) ---------------------------------------
+# The pair pre-pass writes records with at most four positions for reads of at most 256 bases; the format -- and every device consumer of it -- allows eight
+# positions and nk up to 2^16 - 1.  This generator makes the whole format: all three kinds mixed inside every wave of 64 reads, three blocks of 256 reads of one
+# kind each (the kind-1 block on ONE unitig), 0 to 8 positions on either strand drawn from the shapes in _record_positions.  Kind-1 records and kind-0 pairs
+# name real places of the unitig set (`ends`), so bitmap, depth and text of the result mean something.
+UNIFORM_BLOCKS = ((3, 1), (6, 0), (9, 2))   # (block of 256 reads, its kind)
+POSITION_SHAPES = 7
+
+
+def _record_positions(rng, nk, k, nE, shape):
+    """nE ascending positions in [0, nk + k - 2]: 0 uniform; 1 clustered, neighbours 0..k apart (gaps that overlap, touch at exactly k, coincide); 2 equal
+    neighbours; 3 all below k - 1 (a gap clamped at slot 0); 4 all at or above nk (clamped at nk - 1); 5 drawn from k - 1, nk - 1, nk, nk + k - 2;
+    6 a set that covers every slot (where nE * k >= nk, else uniform)"""
+    top = nk + k - 2
+    if nE == 0:
+        return []
+    if shape == 6 and nE * k < nk:
+        shape = 0
+    if shape == 0:
+        E = rng.integers(0, top + 1, nE)
+    elif shape == 1:
+        E = int(rng.integers(0, top + 1)) + np.concatenate([[0], np.cumsum(rng.integers(0, k + 1, nE - 1))])
+    elif shape == 2:
+        E = np.repeat(rng.integers(0, top + 1, (nE + 1) // 2), 2)[:nE]
+    elif shape == 3:
+        E = rng.integers(0, k - 1, nE)
+    elif shape == 4:
+        E = rng.integers(nk, top + 1, nE)
+    elif shape == 5:
+        E = rng.choice([k - 1, nk - 1, nk, top], nE)
+    else:
+        E = (np.arange(nE) + 1) * k - 1
+    return sorted(int(min(x, top)) for x in E)
+
+
+def hand_made_record(rng, rec, nk, k, kmers, nE, rev, shape, u=None):
+    """fill `rec` (one element of a RECORD_DTYPE array) as a kind-1 record of nk slots inside a unitig with room for them (kmers[u] = its number of k-mers):
+    off0 = 0, off0 such that the last slot is the unitig's last k-mer, or anything between"""
+    if u is None:
+        ok = np.nonzero(kmers >= nk)[0]
+        u = int(ok[rng.integers(0, len(ok))])
+    room = int(kmers[u]) - nk
+    assert room >= 0
+    t = rng.random()
+    Es = _record_positions(rng, nk, k, nE, shape)
+    rec["u"], rec["off0"], rec["nk"] = u, 0 if t < 0.25 else room if t < 0.5 else int(rng.integers(0, room + 1)), nk
+    rec["meta"] = nE | (rev << 8) | (1 << 16)
+    rec["Es"] = sum(E << (16 * e) for e, E in enumerate(Es[:4])); rec["Es2"] = sum(E << (16 * e) for e, E in enumerate(Es[4:]))
+
+
+def searched_read_pairs(rng, nk, kmers):
+    """a kind-0 read's pairs: ascending and descending runs inside a unitig, absent stretches, one pair repeated"""
+    out = []
+    while len(out) < nk:
+        n = min(nk - len(out), int(rng.integers(1, 90)))
+        t = rng.random()
+        if t < 0.2:
+            out += [(-1, -1)] * n
+            continue
+        u = int(rng.integers(0, len(kmers))); n = min(n, int(kmers[u])); a = int(rng.integers(0, int(kmers[u]) - n + 1))
+        out += [(u, a)] * n if t < 0.3 else [(u, o) for o in (range(a, a + n) if t < 0.65 else range(a + n - 1, a - 1, -1))]
+    return out
+
+
+def hand_made_records(rng, nks, k, ends):
+    """(recs RECORD_DTYPE[len(nks)], int32 stream [n, 2]) in the form fin_batch_download_records delivers: a kind-0 record is {0, 0, 0, nk, 0, 0} and its pairs
+    are the next nk of the stream.  nks[r] >= 1 is read r's number of k-mers; ends = the unitigs' cumulative ends (FIN_X_ENDS)"""
+    import finito_amd as fa
+    nks = np.asarray(nks, dtype=np.int64); n = len(nks)
+    ends = np.asarray(ends, dtype=np.int64)
+    kmers = np.diff(np.concatenate([[0], ends])) - k + 1
+    assert (nks >= 1).all() and (kmers >= 1).all() and nks.max() <= kmers.max() and n >= 256 * (UNIFORM_BLOCKS[-1][0] + 1)
+    kinds = rng.choice(3, n, p=[0.14, 0.74, 0.12])
+    for w in range(0, n - 2, 64):                       # every wave holds all three kinds
+        kinds[w + rng.permutation(min(64, n - w))[:3]] = [0, 1, 2]
+    for blk, kind in UNIFORM_BLOCKS:
+        kinds[256 * blk:256 * blk + 256] = kind
+    ones = np.nonzero(kinds == 1)[0]
+    cell = rng.permutation(len(ones)) % 18              # nE uniform over 0..8 on either strand, every combination equally often
+    one_unitig = int(np.argmax(kmers))
+    in_block = {r for blk, kind in UNIFORM_BLOCKS if kind == 1 for r in range(256 * blk, 256 * blk + 256)}
+    recs = np.zeros(n, dtype=fa.RECORD_DTYPE)
+    recs["nk"] = nks
+    recs["meta"][kinds == 2] = 2 << 16
+    stream = []
+    for r in np.nonzero(kinds == 0)[0]:
+        stream += searched_read_pairs(rng, int(nks[r]), kmers)
+    for j, r in enumerate(ones):
+        hand_made_record(rng, recs[r:r + 1], int(nks[r]), k, kmers, int(cell[j] % 9), int(cell[j] // 9), int(rng.integers(0, POSITION_SHAPES)),
+                         u=one_unitig if int(r) in in_block else None)
+    return recs, np.array(stream, dtype=np.int32).reshape(-1, 2)
+
+
+_HAND_MADE = {}
+
+
+def hand_made_case(k):
+    """the one input the device consumers (tests/test_records_device.py) and the host functions (tests/test_records_host.py) both face at this k: a 40 000-base
+    genome cut into unitigs of at most 700 bases, 3 019 reads of k .. 300 bases whose content is free (they fix nk), hand-made records over them, and
+    `pairs` = what the records mean (tests/test_records.py::brute_expand).  Made once per k and shared; nobody changes it"""
+    if k not in _HAND_MADE:
+        from types import SimpleNamespace
+        from oracle.oracle import OracleIndex
+        from tests.test_records import brute_expand
+        rng = np.random.default_rng(5000 + k)
+        g = random_genome(rng, 40000)
+        unitigs = cut_unitigs(rng, g, k, max_len=700)
+        ends = OracleIndex.build(unitigs, k).ends()
+        lens = rng.integers(k, 301, 3019)
+        bases = rng.integers(0, 4, int(lens.sum()))
+        reads, at = [], 0
+        for L in lens:
+            reads.append("".join("ACGT"[x] for x in bases[at:at + L])); at += int(L)
+        nks = lens - k + 1
+        recs, stream = hand_made_records(rng, nks, k, ends)
+        pairs = brute_expand(recs, stream, k)
+        for a in (ends, nks, recs, stream, pairs):
+            a.setflags(write=False)
+        _HAND_MADE[k] = SimpleNamespace(k=k, genome=g, unitigs=unitigs, ends=ends, reads=reads, nks=nks, recs=recs, stream=stream, pairs=pairs)
+    return _HAND_MADE[k]
