@@ -93,7 +93,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -124,6 +124,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"fused_ingest", 1, 0, 1},                     // kernel 4 with the pre-pass's fast path: no pack kernel -- the fast pre-pass packs the ASCII reads itself and writes the chunks of the reads it does not finish (batches whose reads are all at most FIN_FAST_CHUNKS * 32 bases long); 0 = the pack kernel first (round 5)
     {"pp_park", 1, 0, 1},                          // with the fused ingest: the reads of list A (both first looks failed) stay in LDS for phases 2 and 3 of the fast pre-pass, and only those they do not finish are written out; 0 = every read phase 1 does not finish is written out and read back (round 6)
     {"debug_pp_park_cap", -1, -1, 1024},           // tests: at most this many parked reads per pre-pass block (-1: as many as the LDS budget holds)
+    {"pp_wide_out", 1, 0, 1},                      // the fast pre-pass's write-out of the reads it finishes: 1 = from a gap mask the read's own lane makes once, two slots and one 16-byte store per lane (round 13); 0 = slot by slot, every lane comparing its slot with the read's disagreeing positions, 8 bytes per lane
     {"hits_combine", 4, 0, 64},                    // fin_batch_add_hits: what a wave sums before an add goes to memory (fin_hits.hip) -- rounds in which the record lanes of one unitig merge, and the run held back between rows of pairs; 0 = every record lane and every run of a row adds by itself
     {"cover_probe", 0, 0, 1},                      // fin_batch_add_cover: 1 = a lane loads the bitmap word first and skips the atomic OR when every bit it would set is set already (exact: bits are only ever set between resets, fin_cover.hip); 0 = always OR.  Measured (profiles/r09/cover.md): 1 wins behind text-mode-2 steps once the bitmap fills (0.83 against 1.14 ms on chr1), 0 behind default steps (4.0 against 5.0 ms) and summed over both
     {"debug_depth_tile", 0, 0, 4096},              // tests: fin_depth_download's prefix sum in tiles of this many elements and chunks of 64 tiles (0: tiles of 4096 elements, chunks of 4096 tiles)
@@ -893,6 +894,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     b->dev.pp_seg = (uint32_t)optv(b->idx, O_debug_pp_seg);
     b->dev.pp_max_len = (uint32_t)std::min<uint64_t>(b->max_read_len, 0xFFFFFFFFull);
     b->dev.pp_park = (uint32_t)optv(b->idx, O_pp_park);
+    b->dev.pp_wide_out = (uint32_t)optv(b->idx, O_pp_wide_out);
     b->dev.pp_park_cap = (uint32_t)(int32_t)optv(b->idx, O_debug_pp_park_cap);
     b->dev.lean_walk = (uint32_t)optv(b->idx, O_lean_walk);
     {   // text re-anchoring needs the upload's verdict on every text place (the bitmap, or the knowledge that all are safe); the anchor table

@@ -147,6 +147,7 @@ struct FinDevIndex {
     // text_only: the pairs of such reads are not written at all (the text is the batch's only product, as in search_fmin.hh:62-65)
     struct FinFastRec* frec;
     uint32_t text_only;
+    uint32_t pp_wide_out;        // set per run, option "pp_wide_out": 1 = the fast pre-pass writes a finished read's pairs from a per-read gap mask, two slots per lane and store (fin_prepass.hip: write_out)
     uint32_t lean_walk;          // host side only (set per run, option "lean_walk"): 1 = under lean tables the walk kernel's lean instantiations (k <= 31: two k-mer-table look-ups per epoch in a run of misses)
     uint32_t pp_seg;             // host side only (set per run, option "debug_pp_seg"; 0: by batch size): reads per block of the pair pre-pass
     uint32_t pp_max_len;         // host side only (set per run): the batch's longest read -- the fused pre-pass sizes its LDS rows by it

@@ -373,6 +373,7 @@ __device__ unsigned long long g_fin_ppdbg[16];
 #else
 #define PPDBG(i) ((void)0)
 #endif
+typedef uint32_t fin_u4 __attribute__((ext_vector_type(4)));   // a 16-byte store of two output pairs (the wide write-out)
 struct FastRun { uint32_t ok, u, off0, nE; uint64_t Es, Es2; };   // Es, Es2: the disagreeing positions, 16 bits each, ascending (four in each word)
 
 // The fused ingest (phase 1 of the fast kernels with `bases`): a strand's chunks made from the forward codes that the lane's LDS row holds (`row`,
@@ -638,6 +639,59 @@ __device__ __forceinline__ void fin_pair_prepass_body(const FinDevIndex& ix, con
                 q[1] = make_uint4((uint32_t)fr.Es, (uint32_t)(fr.Es >> 32), (uint32_t)fr.Es2, (uint32_t)(fr.Es2 >> 32));
             }
             if (ix.text_only) return;
+        }
+        if (ix.pp_wide_out) {
+            // The wide write-out (round 13): what a read's slots hold is worked out once per wave pass by the lane that owns the read, not slot by
+            // slot by the whole wave.  Per ROW of 128 slots -- a row begins at the 16-byte boundary at or in front of the read's first pair, so with an
+            // odd first pair its slot 0 is the row's place 1 -- the owner makes two 64-bit gap masks: bit L of ga / gb says that the row's place 2L /
+            // 2L + 1 is (-1,-1).  A disagreeing position E closes strand A's slots [E - (k-1), E], mirrored for a reverse strand A; ok == 2 closes all.
+            // Slot i of the output is (u, ob + (i ^ sgn)): sgn = 0 and ob = off0 for a forward strand A, sgn = ~0 and ob = off0 + nk for a reverse one.
+            // The wave then takes the reads one by one: eight broadcasts, lane L writes places 2L and 2L + 1 of the row with ONE 16-byte store -- 8 bytes
+            // where only one of the two is a slot of the read (an odd first pair, an odd end).
+            const uint32_t nk = r_len - k1;
+            const uint32_t par = (uint32_t)((uintptr_t)(out + out_off) >> 3) & 1u;
+            for (uint32_t row = 0;; row++) {
+                uint64_t mrow = __ballot(fr.ok != 0u && 128u * row < nk + par);
+                if (!mrow) break;
+                uint64_t ga = 0ull, gb = 0ull;
+                if (fr.ok == 2u) ga = gb = ~0ull;
+                else if (fr.ok) {
+                    const int sb = (int)(128u * row) - (int)par;   // the slot at the row's place 0
+                    for (uint32_t e = 0; e < fr.nE; e++) {
+                        const uint32_t E = (uint32_t)((e < 4u ? fr.Es : fr.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
+                        const uint32_t s_lo = E > k1 ? E - k1 : 0u, s_hi = E < nk - 1u ? E : nk - 1u;
+                        int j_lo = (int)(fr_rev ? nk - 1u - s_hi : s_lo) - sb, j_hi = (int)(fr_rev ? nk - 1u - s_lo : s_hi) - sb;
+                        j_lo = j_lo > 0 ? j_lo : 0; j_hi = j_hi < 127 ? j_hi : 127;
+                        if (j_lo <= j_hi) {
+                            const int a_lo = (j_lo + 1) >> 1, a_hi = j_hi >> 1, b_lo = j_lo >> 1, b_hi = (j_hi - 1) >> 1;   // (b_hi = -1: j_hi = 0, no odd place)
+                            if (a_lo <= a_hi) ga |= (~0ull >> (63 - a_hi)) & (~0ull << a_lo);
+                            if (b_lo <= b_hi) gb |= (~0ull >> (63 - b_hi)) & (~0ull << b_lo);
+                        }
+                    }
+                }
+                while (mrow) {
+                    const int src = __ffsll((long long)mrow) - 1;
+                    mrow &= mrow - 1ull;
+                    auto lane_of = [&](uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); };
+                    const uint32_t o_base = lane_of(out_off), o_nk = lane_of(r_len) - k1, p_u = lane_of(fr.u), p_sgn = 0u - lane_of((uint32_t)fr_rev);
+                    const uint32_t p_ob = lane_of(fr.off0) + (o_nk & p_sgn);
+                    const uint64_t p_ga = lane_of((uint32_t)ga) | ((uint64_t)lane_of((uint32_t)(ga >> 32)) << 32), p_gb = lane_of((uint32_t)gb) | ((uint64_t)lane_of((uint32_t)(gb >> 32)) << 32);
+                    int2* const dst = out + o_base;
+                    const int p_sb = (int)(128u * row) - (int)((uint32_t)((uintptr_t)dst >> 3) & 1u);
+                    const int a = p_sb + 2 * (int)lane;          // the lane's slots: a and a + 1 (a = -1: place 0 of a row that begins in front of the read)
+                    const bool va = (uint32_t)a < o_nk, vb = (uint32_t)(a + 1) < o_nk;
+                    const bool gap_a = (p_ga >> lane) & 1ull, gap_b = (p_gb >> lane) & 1ull;
+                    const uint32_t off_a = ((uint32_t)a ^ p_sgn) + p_ob, off_b = off_a + (1u | p_sgn);
+                    fin_u4 val;
+                    val.x = gap_a ? 0xFFFFFFFFu : p_u; val.y = gap_a ? 0xFFFFFFFFu : off_a;
+                    val.z = gap_b ? 0xFFFFFFFFu : p_u; val.w = gap_b ? 0xFFFFFFFFu : off_b;
+                    int2* const q = dst + a;                      // (16-byte aligned: a has the parity of the row's first place)
+                    if (va && vb) __builtin_nontemporal_store(val, (fin_u4*)q);
+                    else if (va) __builtin_nontemporal_store((unsigned long long)val.x | ((unsigned long long)val.y << 32), (unsigned long long*)q);
+                    else if (vb) __builtin_nontemporal_store((unsigned long long)val.z | ((unsigned long long)val.w << 32), (unsigned long long*)(q + 1));
+                }
+            }
+            return;
         }
         while (mdone) {
             const int src = __ffsll((long long)mdone) - 1;
