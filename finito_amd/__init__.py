@@ -188,6 +188,19 @@ def lib():
         L.fin_search_batch_segments.argtypes = [vp, cp, u64p, u64, C.c_int, u64p, vp, u64, u64p, u64p, cp, C.c_size_t]
         L.fin_expand_segments.argtypes = [u64p, vp, u64, vp, vp, u64p, C.c_int]
         L.fin_records_segments.argtypes = [vp, u64, vp, u64, C.c_int, u64p, vp, u64, u64p, C.c_int]
+        L.fin_batch_read_summaries.argtypes = [vp, cp, C.c_size_t]
+        L.fin_batch_device_read_summaries.argtypes = [vp]
+        L.fin_batch_device_read_summaries.restype = vp
+        L.fin_batch_download_read_summaries.argtypes = [vp, vp, cp, C.c_size_t]
+        L.fin_batch_screen.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, u64p, cp, C.c_size_t]
+        L.fin_batch_device_screen_ids.argtypes = [vp]
+        L.fin_batch_device_screen_ids.restype = vp
+        L.fin_batch_device_screen_bits.argtypes = [vp]
+        L.fin_batch_device_screen_bits.restype = vp
+        L.fin_batch_download_screen.argtypes = [vp, vp, u64p, cp, C.c_size_t]
+        L.fin_search_batch_read_summaries.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u64p, cp, C.c_size_t]
+        L.fin_search_batch_screen.argtypes = [vp, cp, u64p, u64, C.c_int, C.c_uint32, C.c_uint32, C.c_int, u64p, u64p, cp, C.c_size_t]
+        L.fin_records_read_summaries.argtypes = [vp, u64, vp, u64, C.c_int, vp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -372,6 +385,36 @@ class Batch:
     def device_segments_ptr(self):
         """(segments, seg_offs) device pointers, 0 before segments()"""
         return int(self.L.fin_batch_device_segments(self.h) or 0), int(self.L.fin_batch_device_segment_offsets(self.h) or 0)
+
+    def read_summaries(self):
+        """the most recent run's results as one summary per read, made on the device (fin_batch_read_summaries + fin_batch_download_read_summaries):
+        READ_SUMMARY_DTYPE[n_reads] -- n_found, n_segments, longest, span over the read's output slots"""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_read_summaries(self.h, err, 512), err)
+        out = np.zeros(max(self.n_reads, 1), dtype=READ_SUMMARY_DTYPE)
+        _check(self.L.fin_batch_download_read_summaries(self.h, out.ctypes.data_as(C.c_void_p), err, 512), err)
+        return out[: self.n_reads]
+
+    def device_read_summaries_ptr(self):
+        """the summaries' device pointer, 0 before read_summaries() / screen()"""
+        return int(self.L.fin_batch_device_read_summaries(self.h) or 0)
+
+    def screen(self, min_found=1, min_permille=0, invert=False):
+        """the reads that pass (n_found >= min_found and 1000 * n_found >= min_permille * nk) != invert, decided on the device (fin_batch_screen +
+        fin_batch_download_screen): (ids uint32[n_pass] ascending, bits uint64[(n_reads + 63) // 64] -- bit r & 63 of word r >> 6 is read r's)"""
+        if not (0 <= int(min_found) <= 0xFFFFFFFF and 0 <= int(min_permille) <= 0xFFFFFFFF):
+            raise FinitoError(FIN_EINVAL, "screen: min_found and min_permille are unsigned 32-bit numbers")
+        n = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_screen(self.h, int(min_found), int(min_permille), 1 if invert else 0, C.byref(n), err, 512), err)
+        ids = np.zeros(max(int(n.value), 1), dtype=np.uint32)
+        bits = np.zeros(max((self.n_reads + 63) // 64, 1), dtype=np.uint64)
+        _check(self.L.fin_batch_download_screen(self.h, ids.ctypes.data_as(C.c_void_p), bits.ctypes.data_as(C.POINTER(C.c_uint64)), err, 512), err)
+        return ids[: int(n.value)], bits[: (self.n_reads + 63) // 64]
+
+    def device_screen_ptr(self):
+        """(ids, bits) device pointers, 0 before screen()"""
+        return int(self.L.fin_batch_device_screen_ids(self.h) or 0), int(self.L.fin_batch_device_screen_bits(self.h) or 0)
 
     def pipeline_counts(self, n=64):
         """kernel 4's queue counters of the last run (fin_batch_pipeline_counts)"""
@@ -867,6 +910,35 @@ class FinimizerIndex:
                                                 seg_offs.ctypes.data_as(C.POINTER(C.c_uint64)), segs.ctypes.data_as(C.c_void_p), nk, C.byref(got), C.byref(npos), err, 512), err)
         return seg_offs, segs[: int(got.value)].copy(), int(npos.value)
 
+    def search_reads_summaries(self, reads, strands=FIN_MERGED):
+        """fin_search_batch_read_summaries: (READ_SUMMARY_DTYPE[n_reads], n_positive) -- 16 bytes per read come back, nothing per k-mer"""
+        bases, offsets = flatten(reads)
+        n = len(offsets) - 1
+        out = np.zeros(max(n, 1), dtype=READ_SUMMARY_DTYPE)
+        npos = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_read_summaries(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands),
+                                                      out.ctypes.data_as(C.c_void_p), C.byref(npos), err, 512), err)
+        return out[:n], int(npos.value)
+
+    def screen_reads(self, reads, min_found=1, min_permille=0, invert=False, strands=FIN_MERGED):
+        """fin_search_batch_screen: a bool per read -- it passes (n_found >= min_found and 1000 * n_found >= min_permille * nk) != invert; one bit per read
+        comes back"""
+        if not (0 <= int(min_found) <= 0xFFFFFFFF and 0 <= int(min_permille) <= 0xFFFFFFFF):
+            raise FinitoError(FIN_EINVAL, "screen_reads: min_found and min_permille are unsigned 32-bit numbers")
+        bases, offsets = flatten(reads)
+        n = len(offsets) - 1
+        bits = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
+        n_pass = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_screen(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands),
+                                              int(min_found), int(min_permille), 1 if invert else 0, bits.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                              C.byref(n_pass), err, 512), err)
+        out = np.unpackbits(bits.view(np.uint8), bitorder="little")[:n].astype(bool)
+        if int(out.sum()) != int(n_pass.value):
+            raise FinitoError(FIN_EINVAL, "screen_reads: the bitmap holds %d reads, the device counted %d" % (int(out.sum()), int(n_pass.value)))
+        return out
+
     def hits(self, device=0):
         """a zeroed per-unitig accumulator beside the replica on `device` (Hits)"""
         return Hits(self, device)
@@ -957,6 +1029,7 @@ class FinimizerIndex:
 
 RECORD_DTYPE = np.dtype([("u", np.uint32), ("off0", np.uint32), ("meta", np.uint32), ("nk", np.uint32), ("Es", np.uint64), ("Es2", np.uint64)])
 SEGMENT_DTYPE = np.dtype([("u", np.int32), ("off", np.int32), ("slot", np.uint32), ("len", np.int32)])   # fin_segment
+READ_SUMMARY_DTYPE = np.dtype([("n_found", np.uint32), ("n_segments", np.uint32), ("longest", np.uint32), ("span", np.uint32)])   # fin_read_summary
 DEPTH_STAT_DTYPE = np.dtype([("sum", np.uint64), ("max", np.uint32), ("n_at_least", np.uint32)])            # fin_depth_stat
 
 
@@ -1188,6 +1261,17 @@ def records_segments(recs, stream, k, seg_cap=None, n_threads=0):
         raise FinitoError(rc, "fin_records_segments: %s" % ("room for %d segments, %d needed" % (cap, n.value) if rc == FIN_ELIMIT else
                                                             "records and stream do not belong together, or a pair that is neither found nor (-1,-1)"))
     return seg_offs, segs[: int(n.value)].copy()
+
+
+def records_read_summaries(recs, stream, k, n_threads=0):
+    """fin_records_read_summaries (host): READ_SUMMARY_DTYPE[n_reads] from records + stream, without making the pairs"""
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE); stream = np.ascontiguousarray(stream, dtype=np.int32)
+    out = np.zeros(max(len(recs), 1), dtype=READ_SUMMARY_DTYPE)
+    rc = lib().fin_records_read_summaries(recs.ctypes.data_as(C.c_void_p), len(recs), stream.ctypes.data_as(C.c_void_p), len(stream.reshape(-1, 2)), int(k),
+                                          out.ctypes.data_as(C.c_void_p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_read_summaries: records and stream do not belong together, or a pair that is neither found nor (-1,-1)")
+    return out[: len(recs)]
 
 
 def format_pairs(pairs):

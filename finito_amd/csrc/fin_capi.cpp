@@ -688,6 +688,9 @@ struct fin_batch {
     // segments (fin_batch_segments): per-read counts, block sums and offsets, seg_offs[n_reads + 1] and the segments; kept and only grown
     void* d_sgm_cnt = nullptr; void* d_sgm_bsum = nullptr; void* d_sgm_boff = nullptr; void* d_sgm_offs = nullptr; void* d_sgm = nullptr;
     size_t cap_sgm_cnt = 0, cap_sgm_bsum = 0, cap_sgm_boff = 0, cap_sgm_offs = 0, cap_sgm = 0; uint64_t n_segments = 0; bool sgm_ready = false;
+    // per-read summaries and the screen made from them (fin_batch_read_summaries, fin_batch_screen): kept and only grown
+    void* d_rsum = nullptr; void* d_scr_bits = nullptr; void* d_scr_ids = nullptr; void* d_scr_bsum = nullptr; void* d_scr_boff = nullptr;
+    size_t cap_rsum = 0, cap_scr_bits = 0, cap_scr_ids = 0, cap_scr_bsum = 0, cap_scr_boff = 0; uint64_t n_pass = 0; bool rsum_ready = false, scr_ready = false;
     uint64_t text_bytes = 0;
     // kernel 4: the queue counters of the most recent finished run, copied to page-locked memory behind every run: the next run launches only
     // as many stream / walk rounds as that one needed, plus one (fin_launch_search_v4's `rounds`)
@@ -723,6 +726,7 @@ void fin_batch_free(fin_batch* b) {
     if (b->ev_ctr) (void)hipEventDestroy(b->ev_ctr);
     (void)hipFree(b->d_cstream); (void)hipFree(b->d_frec); (void)hipFree(b->d_seg); (void)hipFree(b->d_text); (void)hipFree(b->d_last_bits); (void)hipFree(b->d_blk_sum); (void)hipFree(b->d_blk_off); (void)hipFree(b->d_total);
     (void)hipFree(b->d_sgm_cnt); (void)hipFree(b->d_sgm_bsum); (void)hipFree(b->d_sgm_boff); (void)hipFree(b->d_sgm_offs); (void)hipFree(b->d_sgm);
+    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff);
     (void)hipFree(b->d_ovf_list); (void)hipFree(b->d_ovf_count); (void)hipFree(b->d_ovf_scratch); (void)hipFree(b->d_count);
     for (auto& r : b->runs) for (auto& e : r.e) (void)hipEventDestroy(e);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -846,7 +850,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     //  decoding, inside its timed region, search_fmin.hh:46-71 -- is the first kernel of every step, see fin_batch_run)
     b->n_chunks = n_chunks; b->max_read_len = max_len;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "upload");
-    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false;
+    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false;
     b->rounds_hint = 0; b->ctr_pending = false;   // (new reads: nothing is known about the rounds they need)
     b->text_reads_state = 0;
     return FIN_OK;
@@ -890,7 +894,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     b->dev.budget_mult = (uint32_t)optv(b->idx, O_epoch_budget_mult); b->dev.budget_add = (uint32_t)optv(b->idx, O_epoch_budget_add);
     b->dev.ovf_cap = (uint32_t)std::min<uint64_t>(b->cap_ovf_list / 4, 0xFFFFFFFFull);
     if (const int64_t forced = optv(b->idx, O_debug_ovf_cap)) b->dev.ovf_cap = (uint32_t)std::min<int64_t>(forced, (int64_t)b->dev.ovf_cap);   // (tests: a tiny list)
-    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false;
+    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false;
     b->dev.pp_seg = (uint32_t)optv(b->idx, O_debug_pp_seg);
     b->dev.pp_max_len = (uint32_t)std::min<uint64_t>(b->max_read_len, 0xFFFFFFFFull);
     b->dev.pp_park = (uint32_t)optv(b->idx, O_pp_park);
@@ -1016,7 +1020,7 @@ int fin_batch_set_pairs(fin_batch* b, const int32_t* pairs, char* err, size_t er
     HIPCHK(hipSetDevice(b->device));
     if (b->last_stream) HIPCHK(hipStreamSynchronize(b->last_stream));
     HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
-    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false;   // (the records of the last run say nothing about these pairs)
+    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false;   // (the records of the last run say nothing about these pairs)
     return FIN_OK;
 }
 
@@ -1057,7 +1061,7 @@ int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32
     if (b->n_reads) HIPCHK(hipMemcpy(b->d_frec, recs, (size_t)b->n_reads * sizeof(FinFastRec), hipMemcpyHostToDevice));
     if (pairs && b->n_kmers) HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
     // last_frec / last_text_only stay as the run left them (a text-only batch still refuses its pairs); whatever was made from the old records goes
-    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0;
+    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false;
     b->rec_ready = false; b->rec_passthrough = false; b->rec_stream_pairs = 0;
     return FIN_OK;
 }
@@ -1512,6 +1516,128 @@ int fin_expand_segments(const uint64_t* seg_offs, const fin_segment* segs, uint6
     }
     if (n_positive) { uint64_t f = 0; for (uint64_t x : pos) f += x; *n_positive = f; }
     return FIN_OK;
+}
+
+// ---- per-read summaries and the screen made from them (fin_readsum.hip) -------------------------------------------------------------
+static_assert(sizeof(fin_read_summary) == 16, "a read summary is 16 bytes");
+
+int fin_batch_read_summaries(fin_batch* b, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null batch"); return FIN_EINVAL; }
+    if (!b->ran) { set_err(err, errlen, "this batch has not run: there is nothing to summarise (fin_batch_run first)"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    b->rsum_ready = false; b->scr_ready = false;
+    // (no read has a k-mer: the step searched nothing, there is no overflow list to look at -- every summary is zero)
+    if (b->n_kmers != 0) if (const int orc = batch_overrun_check(b, st, err, errlen)) return orc;   // a run without results: nothing is written
+    const uint32_t nr = (uint32_t)b->n_reads;
+    if (batch_grow(b, &b->d_rsum, b->cap_rsum, (size_t)nr * 16 + 16, st)) { set_err(err, errlen, "out of device memory (read summaries)"); return FIN_ENOMEM; }
+    if (b->n_kmers == 0) HIPCHK(hipMemsetAsync(b->d_rsum, 0, (size_t)nr * 16 + 16, st));
+    else {
+        const int rc = fin_launch_read_summaries(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, nr, b->dev.k, b->d_rsum, st);
+        if (rc != 0) { set_err(err, errlen, std::string("read summary kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    }
+    b->rsum_ready = true;
+    return FIN_OK;
+}
+
+void* fin_batch_device_read_summaries(const fin_batch* b) { return b && b->rsum_ready ? b->d_rsum : nullptr; }
+
+int fin_batch_download_read_summaries(fin_batch* b, fin_read_summary* out, char* err, size_t errlen) {
+    if (!b || (b->n_reads && !out)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->rsum_ready) { set_err(err, errlen, "fin_batch_read_summaries first"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    if (b->n_reads) HIPCHK(hipMemcpyAsync(out, b->d_rsum, (size_t)b->n_reads * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
+int fin_batch_screen(fin_batch* b, uint32_t min_found, uint32_t min_permille, int invert, uint64_t* n_pass, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null batch"); return FIN_EINVAL; }
+    if (min_permille > 1000u) { set_err(err, errlen, "min_permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (!b->rsum_ready) if (const int rc = fin_batch_read_summaries(b, err, errlen)) return rc;
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    b->scr_ready = false;
+    const uint32_t nr = (uint32_t)b->n_reads, nb = fin_rsm_blocks(nr);
+    if (batch_grow(b, &b->d_scr_bits, b->cap_scr_bits, (size_t)((nr + 63u) / 64u) * 8 + 8, st) || batch_grow(b, &b->d_scr_bsum, b->cap_scr_bsum, (size_t)nb * 4 + 4, st) ||
+        batch_grow(b, &b->d_scr_boff, b->cap_scr_boff, (size_t)nb * 8 + 8, st)) {
+        set_err(err, errlen, "out of device memory (screen tables)"); return FIN_ENOMEM;
+    }
+    if (!b->d_total) HIPCHK(hipMalloc((void**)&b->d_total, 8));
+    int rc = fin_launch_screen_bits(b->d_rsum, (const uint64_t*)b->d_out_offs, nr, min_found, min_permille, invert, (uint64_t*)b->d_scr_bits, (uint32_t*)b->d_scr_bsum,
+                                    (uint64_t*)b->d_scr_boff, b->d_total, st);
+    if (rc != 0) { set_err(err, errlen, std::string("screen kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, b->d_total, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (total > nr) { set_err(err, errlen, "screen kernels: more passing reads than reads"); return FIN_ENODEV; }
+    if (batch_grow(b, &b->d_scr_ids, b->cap_scr_ids, (size_t)total * 4 + 16, st)) { set_err(err, errlen, "out of device memory (screen ids)"); return FIN_ENOMEM; }
+    rc = fin_launch_screen_ids((const uint64_t*)b->d_scr_bits, (const uint64_t*)b->d_scr_boff, nr, (uint32_t*)b->d_scr_ids, st);
+    if (rc != 0) { set_err(err, errlen, std::string("screen kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    b->n_pass = total; b->scr_ready = true;
+    if (n_pass) *n_pass = total;
+    return FIN_OK;
+}
+
+void* fin_batch_device_screen_ids(const fin_batch* b) { return b && b->scr_ready ? b->d_scr_ids : nullptr; }
+void* fin_batch_device_screen_bits(const fin_batch* b) { return b && b->scr_ready ? b->d_scr_bits : nullptr; }
+
+int fin_batch_download_screen(fin_batch* b, uint32_t* ids_out, uint64_t* bits_out, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null batch"); return FIN_EINVAL; }
+    if (!b->scr_ready) { set_err(err, errlen, "fin_batch_screen first"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    const size_t n_words = (size_t)((b->n_reads + 63) / 64);
+    if (ids_out && b->n_pass) HIPCHK(hipMemcpyAsync(ids_out, b->d_scr_ids, (size_t)b->n_pass * 4, hipMemcpyDeviceToHost, st));
+    if (bits_out && n_words) HIPCHK(hipMemcpyAsync(bits_out, b->d_scr_bits, n_words * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
+// host: the same summaries from records + stream -- the CPU statement of fin_readsum.hip, over the segments segment_slots / segment_record make: n_found is the
+// sum of their lengths, span runs from the first one's slot to the last one's end
+int fin_records_read_summaries(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, fin_read_summary* out,
+                               int n_threads) {
+    if ((n_reads && (!recs || !out)) || k < 1 || (n_stream_pairs && !stream_pairs)) return FIN_EINVAL;
+    int T = n_threads > 0 ? n_threads : fin_host_threads();
+    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
+    std::vector<uint64_t> str0((size_t)T + 1, 0);
+    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
+        const auto lh = bounds(t);
+        uint64_t sp = 0;
+        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
+        str0[(size_t)t + 1] = sp;
+    }
+    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
+    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
+    bool ok = true;
+#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
+    for (int t = 0; t < T; t++) {
+        const auto lh = bounds(t);
+        uint64_t sp = str0[(size_t)t];
+        bool good = true;
+        for (uint64_t r = lh.first; r < lh.second && good; r++) {
+            const fin_read_record& R = recs[r];
+            const uint32_t kind = R.meta >> 16;
+            fin_read_summary S{0, 0, 0, 0};
+            uint32_t first = 0, end = 0;
+            auto emit = [&](int32_t, int32_t, uint32_t slot, int32_t len) {
+                const uint32_t n = (uint32_t)(len < 0 ? -(int64_t)len : (int64_t)len);
+                if (S.n_segments == 0) first = slot;
+                S.n_found += n; S.n_segments++; if (n > S.longest) S.longest = n;
+                end = slot + n;
+            };
+            if (kind == 0u) { good = segment_slots(stream_pairs + 2 * sp, R.nk, emit); sp += R.nk; }
+            else if (kind == 1u) segment_record(R, k, emit);
+            S.span = end - first;
+            out[r] = S;
+        }
+        ok = good && ok;
+    }
+    return ok ? FIN_OK : FIN_EINVAL;
 }
 
 // ---- the profile over the unitig set (fin_hits.hip) ---------------------------------------------------------------------------------
@@ -2099,6 +2225,10 @@ struct TextSink {
     fin_depth* depth = nullptr; // the per-position depth (fin_search_batch_add_depth), likewise
     // (segments when `seg_offs` is set: fin_search_batch_segments -- `len` then counts a sub-batch's segments, seg_offs is rebased to the whole read set)
     uint64_t* seg_offs = nullptr; fin_segment* segs = nullptr; uint64_t seg_cap = 0; std::atomic<bool> seg_over{false};
+    // (summaries when `rsum` is set: fin_search_batch_read_summaries -- a sub-batch's land at its reads' numbers; a screen when `screen` is set:
+    //  fin_search_batch_screen -- a sub-batch's bitmap is shifted into scr_bits (may be null) at its first read's bit, under `mu`)
+    fin_read_summary* rsum = nullptr;
+    bool screen = false; uint32_t scr_min_found = 0, scr_min_permille = 0; int scr_invert = 0; uint64_t* scr_bits = nullptr; std::atomic<uint64_t> scr_pass{0};
     std::vector<uint64_t> len; std::vector<char> known;
     std::mutex mu; std::condition_variable cv;
     uint64_t total = 0;
@@ -2197,6 +2327,32 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
                             uint64_t* const dst = ts->seg_offs + (s.lo - ts->read0);   // (entry 0 is the sub-batch before's last, or the caller's)
                             for (size_t r = 1; r < so.size(); r++) dst[r] = so[r] + at;
                             for (uint64_t q = 0; q < L; q++) { const int32_t n = ts->segs[at + q].len; pos += (uint64_t)(n < 0 ? -(int64_t)n : (int64_t)n); }
+                        }
+                    }
+                }
+            } else
+            if (rc == FIN_OK && ts && ts->rsum) {
+                rc = fin_batch_read_summaries(b, e, sizeof e);
+                fin_read_summary* const dst = ts->rsum + (s.lo - ts->read0);
+                if (rc == FIN_OK) rc = fin_batch_download_read_summaries(b, dst, e, sizeof e);
+                if (rc == FIN_OK) for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_found;
+            } else
+            if (rc == FIN_OK && ts && ts->screen) {
+                uint64_t np = 0;
+                rc = fin_batch_screen(b, ts->scr_min_found, ts->scr_min_permille, ts->scr_invert, &np, e, sizeof e);
+                if (rc == FIN_OK) ts->scr_pass += np;
+                if (rc == FIN_OK && ts->scr_bits) {
+                    // the sub-batch's bitmap begins at bit 0; in the whole read set's it begins at its first read's bit, which need not start a word
+                    const uint64_t n = s.hi - s.lo, at = s.lo - ts->read0;
+                    std::vector<uint64_t> w((size_t)((n + 63) / 64) + 1, 0);
+                    rc = fin_batch_download_screen(b, nullptr, w.data(), e, sizeof e);
+                    if (rc == FIN_OK) {
+                        const uint32_t sh = (uint32_t)(at & 63);
+                        std::lock_guard<std::mutex> g(ts->mu);   // (neighbouring sub-batches share a word)
+                        for (size_t q = 0; q + 1 < w.size(); q++) {
+                            if (!w[q]) continue;
+                            ts->scr_bits[(at >> 6) + q] |= w[q] << sh;
+                            if (sh && (w[q] >> (64u - sh))) ts->scr_bits[(at >> 6) + q + 1] |= w[q] >> (64u - sh);   // (a set bit is a read below s.hi: the word exists)
                         }
                     }
                 }
@@ -2361,6 +2517,33 @@ int fin_search_batch_segments(const fin_index* idx, const char* bases, const uin
         return FIN_ELIMIT;
     }
     if (rc == FIN_OK && n_positive) *n_positive = pos;
+    return rc;
+}
+
+int fin_search_batch_read_summaries(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_read_summary* out,
+                                    uint64_t* n_positive, char* err, size_t errlen) {
+    if (!idx || !offsets || (n_reads && !out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (n_positive) *n_positive = 0;
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.rsum = out; ts.read0 = 0;
+    uint64_t pos = 0;
+    const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
+    if (rc == FIN_OK && n_positive) *n_positive = pos;
+    return rc;
+}
+
+int fin_search_batch_screen(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint32_t min_found, uint32_t min_permille,
+                            int invert, uint64_t* bits_out, uint64_t* n_pass, char* err, size_t errlen) {
+    if (!idx || !offsets || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (min_permille > 1000u) { set_err(err, errlen, "min_permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (n_pass) *n_pass = 0;
+    if (n_reads == 0) return FIN_OK;
+    if (bits_out) for (uint64_t w = 0; w < (n_reads + 63) / 64; w++) bits_out[w] = 0;
+    TextSink ts; ts.screen = true; ts.scr_min_found = min_found; ts.scr_min_permille = min_permille; ts.scr_invert = invert; ts.scr_bits = bits_out; ts.read0 = 0;
+    const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+    if (rc == FIN_OK && n_pass) *n_pass = ts.scr_pass.load();
     return rc;
 }
 

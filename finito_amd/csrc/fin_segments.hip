@@ -25,34 +25,12 @@
 // pairs are read twice.  Records, pairs and text are read only; plain vector stores only.
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_rec_walk.h"
 
 #define FIN_SGM_BLK 256u   // reads per block: a lane per read
 
 namespace {
 typedef unsigned long long ull;
-
-// the found stretches [from, to) of a kind-1 record's strand slots, ascending: emit(ordinal, from, to); returns how many
-template <class F>
-__device__ __forceinline__ uint32_t sgm_rec_walk(const uint4 a, const uint4 b, uint32_t k, F&& emit) {
-    const uint32_t nk = a.w, nE = min(a.z & 0xFFu, 8u), k1 = k - 1u;
-    uint32_t done_to = 0, from = 0, n = 0;
-#pragma unroll
-    for (uint32_t e = 0; e < 8u; e++) {
-        if (e < nE) {
-            const uint32_t w = e < 2u ? b.x : e < 4u ? b.y : e < 6u ? b.z : b.w, E = (e & 1u) ? w >> 16 : w & 0xFFFFu;
-            uint32_t lo = E >= k1 ? E - k1 : 0u;
-            const uint32_t hi = E < nk ? E : nk - 1u;
-            if (lo < done_to) lo = done_to;
-            if (lo <= hi) {
-                if (lo > from) { emit(n, from, lo); n++; }
-                from = hi + 1u;
-            }
-            if (hi + 1u > done_to) done_to = hi + 1u;
-        }
-    }
-    if (nk > from) { emit(n, from, nk); n++; }
-    return n;
-}
 
 // slots [lo, hi) of the pair array are one read's: its segments counted (WRITE false) or written to out[0 ..) (WRITE true), the whole wave, a row of 64 slots
 // at a time.  Wave-converged; returns the read's number of segments in every lane.
@@ -209,6 +187,11 @@ __global__ __launch_bounds__(1024) void fin_sgm_scan_kernel(const uint32_t* blk_
     if (threadIdx.x == 1023u) *total = lds[1023];
 }
 
+// the scan by itself, for the other dense outputs made from per-block counts (fin_readsum.hip: the screen's ids).  n_blk > 0
+extern "C" int fin_launch_blk_scan(const uint32_t* blk_sum, uint32_t n_blk, uint64_t* blk_off, uint64_t* total, hipStream_t stream) {
+    hipLaunchKernelGGL(fin_sgm_scan_kernel, dim3(1), dim3(1024), 0, stream, blk_sum, n_blk, blk_off, total);
+    return (int)hipGetLastError();
+}
 extern "C" uint32_t fin_sgm_blocks(uint32_t n_reads) { return (n_reads + FIN_SGM_BLK - 1u) / FIN_SGM_BLK; }
 // cnt: n_reads u32; blk_sum: fin_sgm_blocks() u32; blk_off: as many u64; total: one u64 (the batch's segments).  The counting pass and the scan.  n_reads > 0
 extern "C" int fin_launch_sgm_count(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, uint32_t* cnt, uint32_t* blk_sum,

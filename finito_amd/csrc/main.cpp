@@ -463,8 +463,21 @@ static const char* SEARCH_HELP =
     "                        query files), from its k-mer number `slot` on, found in `unitig` at `offset`, `offset + 1`, ... (+) or `offset`,\n"
     "                        `offset - 1`, ... (-). Reads without a found k-mer have no line. Made on the first GPU from one more search of every\n"
     "                        chunk; goes with -o, --unitig-counts and --unitig-coverage. Not for a partitioned index.\n"
-    "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth or --segments): do not make or write the pair text, the\n"
-    "                        profile, the coverage, the depth and / or the segments are the only results\n"
+    "      --read-summary FILE  also write one line per read, in input order: `read<TAB>k-mers<TAB>found<TAB>segments<TAB>longest<TAB>span` -- `read` as\n"
+    "                        --segments prints it, k-mers = length - k + 1 (0 for a shorter read), found = how many of them were found, segments = the\n"
+    "                        read's number of --segments lines, longest = the longest of them, span = last found k-mer - first found k-mer + 1.\n"
+    "                        Made on the first GPU from one more search of every chunk, 16 bytes per read come back; goes with -o, --unitig-counts,\n"
+    "                        --unitig-coverage, --unitig-depth, --segments and --screen. Not for a partitioned index.\n"
+    "      --screen FILE     also write the numbers of the reads that pass the screen, one per line, ascending: a read passes when found >= N and\n"
+    "                        1000 * found >= P * k-mers (found, k-mers as in --read-summary). Decided on the first GPU from one more search of every\n"
+    "                        chunk, one bit per read comes back; goes with everything --read-summary goes with. Not for a partitioned index. The reads\n"
+    "                        themselves are not written. With --no-text 1 and no --unitig-counts, --segments or --read-summary a chunk is searched\n"
+    "                        twice (the second pass counts the found k-mers the log reports).\n"
+    "      --min-found N     the N of --screen (default: 1)\n"
+    "      --min-permille P  the P of --screen, 0 to 1000 (default: 0)\n"
+    "      --screen-invert arg  1: write the reads that do NOT pass (default: 0)\n"
+    "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary or --screen): do not make or\n"
+    "                        write the pair text, the other results asked for are the only ones\n"
     "  -h, --help            Print usage\n";
 
 static int build_fmin(int argc, char** argv) {
@@ -676,6 +689,43 @@ static uint64_t segments_chunk(const FinimizerIndex& index, const char* bases, c
     g_seg_read0 += n_reads;
     return pos;
 }
+// --read-summary FILE: every chunk's per-read summaries are made on the first device (fin_search_batch_read_summaries) and written as lines, by the search
+// stage, in chunk order.  --screen FILE: the same for the screen (fin_search_batch_screen): the passing reads' run-wide numbers
+static FILE* g_rs_file = nullptr;
+static uint64_t g_rs_read0 = 0;   // reads in the chunks (and query files) before this one
+static vector<fin_read_summary> g_rs; static string g_rs_text;
+static uint64_t read_summary_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads, const uint64_t* pair_off) {
+    char err[512] = {0};
+    g_rs.resize(n_reads + 1);
+    uint64_t pos = 0;
+    if (fin_search_batch_read_summaries(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_rs.data(), &pos, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    string& t = g_rs_text;
+    t.clear();
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const fin_read_summary& S = g_rs[r];
+        t += to_string(g_rs_read0 + r); t += '\t'; t += to_string(pair_off[r + 1] - pair_off[r]); t += '\t'; t += to_string(S.n_found); t += '\t';
+        t += to_string(S.n_segments); t += '\t'; t += to_string(S.longest); t += '\t'; t += to_string(S.span); t += '\n';
+    }
+    if (!t.empty() && fwrite(t.data(), 1, t.size(), g_rs_file) != t.size()) throw runtime_error("Error writing the read summary file");
+    g_rs_read0 += n_reads;
+    return pos;
+}
+static FILE* g_scr_file = nullptr;
+static uint64_t g_scr_read0 = 0;
+static uint32_t g_scr_min_found = 1, g_scr_min_permille = 0; static int g_scr_invert = 0;
+static vector<uint64_t> g_scr_bits; static string g_scr_text;
+static void screen_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
+    char err[512] = {0};
+    g_scr_bits.assign((n_reads + 63) / 64 + 1, 0);
+    if (fin_search_batch_screen(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_scr_min_found, g_scr_min_permille, g_scr_invert, g_scr_bits.data(), nullptr, err, sizeof err) != FIN_OK)
+        throw runtime_error(err);
+    string& t = g_scr_text;
+    t.clear();
+    for (uint64_t w = 0; w < (n_reads + 63) / 64; w++)
+        for (uint64_t x = g_scr_bits[w]; x; x &= x - 1) { t += to_string(g_scr_read0 + 64 * w + (uint64_t)__builtin_ctzll(x)); t += '\n'; }
+    if (!t.empty() && fwrite(t.data(), 1, t.size(), g_scr_file) != t.size()) throw runtime_error("Error writing the screen file");
+    g_scr_read0 += n_reads;
+}
 static bool g_no_text = false;
 static uint64_t g_hits_total = 0;   // the accumulator's sum after the previous query file
 
@@ -756,6 +806,8 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_depth) add_depth_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_seg_file) c->positive = segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
+                        if (g_rs_file) c->positive = read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
+                        if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                     }
                     else {
                         // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
@@ -773,6 +825,8 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_depth) add_depth_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_seg_file) (void)segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
+                        if (g_rs_file) (void)read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
+                        if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                     }
                     if (g_strand_counts) {
                         c->positive_fwd = index.count_found_one_strand(c->bases.get(0), c->offsets.data(), n_reads);
@@ -888,11 +942,25 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments")) throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth or --segments (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen"))
+        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary or --screen (the run would have no result)");
+    for (const char* name : {"min-found", "min-permille", "screen-invert"})
+        if (o.has(name) && !o.has("screen")) throw runtime_error(string("--") + name + " is only legal together with --screen");
+    auto u32_option = [&](const char* name, unsigned long long dflt, unsigned long long top) {
+        if (!o.has(name)) return (uint32_t)dflt;
+        const string v = o.get(name);
+        size_t used = 0; unsigned long long t = 0;
+        try { t = stoull(v, &used); } catch (...) { used = 0; }
+        if (v.empty() || used != v.size() || v[0] == '-' || t > top) throw runtime_error(string("--") + name + " wants a number from 0 to " + to_string(top));
+        return (uint32_t)t;
+    };
+    g_scr_min_found = u32_option("min-found", 1, 0xFFFFFFFFull);
+    g_scr_min_permille = u32_option("min-permille", 0, 1000);
+    g_scr_invert = o.has("screen-invert") && o.get("screen-invert") != "0" && o.get("screen-invert") != "false" ? 1 : 0;
     if (o.has("min-depth") && !o.has("unitig-depth")) throw runtime_error("--min-depth is only legal together with --unitig-depth");
     uint32_t min_depth = 1;
     if (o.has("min-depth")) {
@@ -928,6 +996,10 @@ static int search_fmin(int argc, char** argv) {
     if (!depth_file.empty()) check_writable(depth_file);
     const string seg_file = o.get("segments", "");
     if (!seg_file.empty()) check_writable(seg_file);
+    const string rs_file = o.get("read-summary", "");
+    if (!rs_file.empty()) check_writable(rs_file);
+    const string scr_file = o.get("screen", "");
+    if (!scr_file.empty()) check_writable(scr_file);
     cerr << "Loading index..." << endl;
     const int first_dev = stoi(o.get("device", "0"));
     // beside the index load: page-lock the pipeline's buffers (four chunks of 48 MB of bases and of up to 16 bytes of text per k-mer)
@@ -967,9 +1039,11 @@ static int search_fmin(int argc, char** argv) {
     if (!cover_file.empty() && index.partitioned()) throw runtime_error("--unitig-coverage is not available with a partitioned index");
     if (!depth_file.empty() && index.partitioned()) throw runtime_error("--unitig-depth is not available with a partitioned index");
     if (!seg_file.empty() && index.partitioned()) throw runtime_error("--segments is not available with a partitioned index");
+    if (!rs_file.empty() && index.partitioned()) throw runtime_error("--read-summary is not available with a partitioned index");
+    if (!scr_file.empty() && index.partitioned()) throw runtime_error("--screen is not available with a partitioned index");
     index.to_device();
     struct HitsOwner { ~HitsOwner() { fin_hits_free(g_hits); g_hits = nullptr; } } hits_owner;
-    if (!counts_file.empty() || (g_no_text && seg_file.empty())) {   // (with --segments the found k-mers are the sum of the segments' lengths)
+    if (!counts_file.empty() || (g_no_text && seg_file.empty() && rs_file.empty())) {   // (with --segments the found k-mers are the sum of the segments' lengths, with --read-summary the sum of `found`)
         char err[512] = {0};
         if (fin_hits_create(index.handle(), first_dev, &g_hits, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
@@ -988,6 +1062,17 @@ static int search_fmin(int argc, char** argv) {
         g_seg_file = fopen(seg_file.c_str(), "wb");
         if (!g_seg_file) throw runtime_error("Error writing to file: " + seg_file);
         g_seg_read0 = 0;
+    }
+    struct ReadSumOwner { ~ReadSumOwner() { if (g_rs_file) fclose(g_rs_file); g_rs_file = nullptr; if (g_scr_file) fclose(g_scr_file); g_scr_file = nullptr; } } rs_owner;
+    if (!rs_file.empty()) {
+        g_rs_file = fopen(rs_file.c_str(), "wb");
+        if (!g_rs_file) throw runtime_error("Error writing to file: " + rs_file);
+        g_rs_read0 = 0;
+    }
+    if (!scr_file.empty()) {
+        g_scr_file = fopen(scr_file.c_str(), "wb");
+        if (!g_scr_file) throw runtime_error("Error writing to file: " + scr_file);
+        g_scr_read0 = 0;
     }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
@@ -1013,6 +1098,16 @@ static int search_fmin(int argc, char** argv) {
         const bool bad = fflush(g_seg_file) != 0 || ferror(g_seg_file);
         fclose(g_seg_file); g_seg_file = nullptr;
         if (bad) throw runtime_error("Error writing to file: " + seg_file);
+    }
+    if (g_rs_file) {
+        const bool bad = fflush(g_rs_file) != 0 || ferror(g_rs_file);
+        fclose(g_rs_file); g_rs_file = nullptr;
+        if (bad) throw runtime_error("Error writing to file: " + rs_file);
+    }
+    if (g_scr_file) {
+        const bool bad = fflush(g_scr_file) != 0 || ferror(g_scr_file);
+        fclose(g_scr_file); g_scr_file = nullptr;
+        if (bad) throw runtime_error("Error writing to file: " + scr_file);
     }
     if (g_cover) {   // the coverage, after the last chunk: one line per unitig of the index
         char err[512] = {0};

@@ -418,7 +418,7 @@ int fin_batch_download_records(fin_batch* b, fin_read_record* recs_out, int32_t*
  * fin_batch_records), the sibling of fin_batch_set_pairs: overwrite the records the batch's most recent run left with recs[n_reads] and, when pairs != NULL, its
  * pairs with pairs[2 * n_kmers].  Legal only after a run that left records (kernel 4, merged strands, fast path on, text mode 1 or 2): FIN_EINVAL otherwise.
  * Waits for that run, copies, launches no kernel.  The batch stays what the run made it -- after a text-mode-2 run fin_batch_download still refuses the pairs --
- * and forgets what it made from the old records: segments, the gathered stream, the formatted text and the count taken from it.
+ * and forgets what it made from the old records: segments, read summaries and the screen, the gathered stream, the formatted text and the count taken from it.
  * The kernels trust a record's fields, so they are checked on the host before anything is copied; FIN_EINVAL with a message unless, for every read,
  *  - kind = meta >> 16 is 0, 1 or 2;
  *  - kind 1 or 2: nk is the read's own number of k-mers, max(0, length - k + 1), and at least 1;
@@ -599,6 +599,52 @@ int fin_expand_segments(const uint64_t* seg_offs, const fin_segment* segs, uint6
  * FIN_EINVAL: a stream that is not this record set's, or a stream pair that is neither found nor (-1,-1) */
 int fin_records_segments(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t* seg_offs_out,
                          fin_segment* segs_out, uint64_t seg_cap, uint64_t* n_segments, int n_threads);
+
+/* ---- per-read SUMMARIES and read SCREENING, made on the device ----
+ * The per-read counterpart of fin_hits: which reads belong to the reference, and how well -- host depletion, contamination screening, pulling one organism's
+ * reads out of a metagenome, discarding chimeric or adapter-laden reads.  16 bytes per read come back, or one bit per read, or 4 bytes per passing read.
+ * All four fields are defined over the read's output slots 0 .. nk - 1, the order of fin_search_batch's pairs:
+ *   n_found     the slots whose pair is not (-1,-1); their sum over a batch is its n_positive;
+ *   n_segments  the read's number of segments under the rule above (link(i) and link(i - 1) decide a head: offsets 5,6,5,6,5 give 4) -- it equals
+ *               seg_offs[r + 1] - seg_offs[r] of fin_batch_segments;
+ *   longest     the largest |len| among those segments, 0 if there are none;
+ *   span        last found slot - first found slot + 1, 0 if none.  span - n_found = the absent slots inside the matched region (errors, variants); nk - span
+ *               = what is missing at the ends (clipping, adapters, a read leaving the reference).
+ * All four are invariant under reversing the slot order: a read found on its reverse strand (a kind-1 record with meta bit 8) needs no special case.
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror (it has no segments either). */
+typedef struct fin_read_summary { uint32_t n_found, n_segments, longest, span; } fin_read_summary;   /* 16 bytes */
+/* Behind the batch's most recent run, on that run's stream and ordered behind the run (fin_readsum.hip): one kernel, a lane per read; a read the fast path
+ * finished (text modes 1 and 2) is summarised from its 32-byte record alone -- in mode 2 its pairs do not exist --, every other read's pairs are scanned in place.
+ * The summaries stay in HBM, in a buffer the batch keeps and only grows; a second call gives the same answer.  Read-only on records, pairs, text and segments.
+ * Works in every text mode, for FIN_MERGED and FIN_FWD, for every k; empty batches and batches of reads without k-mers are legal.  fin_batch_run,
+ * fin_batch_reload, fin_batch_set_records and fin_batch_set_pairs forget the summaries and the screen, as they forget the segments.
+ * FIN_EINVAL: the batch has not run.  FIN_ELIMIT: the run's overflow list overran -- it has no results, nothing is written. */
+int fin_batch_read_summaries(fin_batch* b, char* err, size_t errlen);
+void* fin_batch_device_read_summaries(const fin_batch* b);   /* fin_read_summary[n_reads] in HBM; NULL before fin_batch_read_summaries */
+int fin_batch_download_read_summaries(fin_batch* b, fin_read_summary* out, char* err, size_t errlen);   /* out[n_reads] */
+/* The screen: read r passes when (n_found >= min_found && 1000 * n_found >= min_permille * nk) != (invert != 0), in 64-bit arithmetic, nk = the read's number of
+ * output slots.  The rule is taken literally: a read without k-mers passes a screen that is not inverted only when min_found = 0.  min_permille is 0 .. 1000,
+ * else FIN_EINVAL.  Makes the summaries if they are not there; waits for the count, *n_pass (may be NULL) = the passing reads.  Two results stay in HBM:
+ *   bits  uint64[(n_reads + 63) / 64], bit r & 63 of word r >> 6 is read r's; bits at and beyond n_reads are 0;
+ *   ids   uint32[n_pass], the passing reads' numbers, ascending. */
+int fin_batch_screen(fin_batch* b, uint32_t min_found, uint32_t min_permille, int invert, uint64_t* n_pass, char* err, size_t errlen);
+void* fin_batch_device_screen_ids(const fin_batch* b);    /* NULL before fin_batch_screen */
+void* fin_batch_device_screen_bits(const fin_batch* b);   /* NULL before fin_batch_screen */
+/* ids_out[n_pass] (may be NULL), bits_out[(n_reads + 63) / 64] (may be NULL) */
+int fin_batch_download_screen(fin_batch* b, uint32_t* ids_out, uint64_t* bits_out, char* err, size_t errlen);
+/* host buffers in: fin_search_batch's pipeline over sub-batches, each run in text mode 2 where the fast path is on (as fin_search_batch_segments does) and
+ * summarised / screened on the device behind its run.  out[n_reads]; *n_positive (may be NULL) = the k-mers found (the sum of n_found).  bits_out (may be NULL):
+ * the whole read set's bitmap, (n_reads + 63) / 64 words, put together on the host from the sub-batches' -- a sub-batch need not begin at a multiple of 64 reads;
+ * *n_pass (may be NULL) = the passing reads.  Reads shorter than k and an empty read set are legal. */
+int fin_search_batch_read_summaries(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_read_summary* out,
+                                    uint64_t* n_positive, char* err, size_t errlen);
+int fin_search_batch_screen(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint32_t min_found, uint32_t min_permille,
+                            int invert, uint64_t* bits_out, uint64_t* n_pass, char* err, size_t errlen);
+/* host, no device: the same summaries from records + stream, without making the pairs -- the CPU statement of what the kernel does (the sibling of
+ * fin_records_segments / fin_records_unitig_counts).  out[n_reads]; n_threads <= 0: all cores.  FIN_EINVAL: a stream that is not this record set's, or a stream pair
+ * that is neither found nor (-1,-1) */
+int fin_records_read_summaries(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, fin_read_summary* out,
+                               int n_threads);
 
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
