@@ -20,6 +20,7 @@ _LIB = None
 FIN_FWD, FIN_MERGED = 0, 1
 FIN_OK, FIN_EINVAL, FIN_EIO, FIN_ENODEV, FIN_ENOMEM, FIN_ELIMIT = 0, -1, -2, -3, -4, -5   # include/finito_amd.h
 X_C, X_PLANE_A, X_LCS, X_FMIN, X_USTART, X_GOFF, X_ENDS, X_CONCAT = 0, 1, 5, 6, 7, 8, 9, 10
+DT_PTAB, DT_JTAB, DT_FILT, DT_SAFE, DT_RCWIN, DT_CBF, DT_FBF = range(7)   # fin_index_debug_table
 
 
 class FinitoError(RuntimeError):
@@ -108,6 +109,10 @@ def lib():
         L.fin_index_anchor_build_ms.argtypes = [vp, C.c_int]
         L.fin_index_anchor_build_ms.restype = C.c_double
         L.fin_index_debug_seed_table.argtypes = [vp, C.c_int, vp, cp, C.c_size_t]
+        L.fin_index_debug_table_bytes.argtypes = [vp, C.c_int, C.c_int]
+        L.fin_index_debug_table_bytes.restype = C.c_int64
+        L.fin_index_debug_table.argtypes = [vp, C.c_int, C.c_int, vp, u64, cp, C.c_size_t]
+        L.fin_index_string_filter_geometry.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.fin_index_finimizer_stats.argtypes = [vp, cp, u64p, u64, C.c_int, i64, i64p, i64p, i64p, cp, C.c_size_t]
         L.fin_search.argtypes = [vp, cp, i64, i64p, i64p, cp, C.c_size_t]
         L.fin_search_batch.argtypes = [vp, cp, u64p, u64, C.c_int, i32p, u64p, cp, C.c_size_t]
@@ -745,6 +750,29 @@ class FinimizerIndex:
         err = C.create_string_buffer(512)
         rc = self.L.fin_index_debug_seed_table(self.h, int(device), out.ctypes.data_as(C.c_void_p), err, 512)
         return out if rc == 0 else None
+
+    def debug_table(self, what, device=0):
+        """fin_index_debug_table: a derived table of the device replica as it lies in HBM (DT_*), or None when that replica carries none: DT_PTAB / DT_JTAB
+        uint32 [4^T, 2] (l, r), DT_FILT uint32 words, DT_SAFE uint64 words (bit g & 63 of word g >> 6), DT_RCWIN uint8 (a byte per 512 text positions),
+        DT_CBF / DT_FBF uint32 [blocks, 4]"""
+        nbytes = int(self.L.fin_index_debug_table_bytes(self.h, int(device), int(what)))
+        if nbytes < 0:
+            raise FinitoError(FIN_EINVAL, "debug_table: no replica on device %d, or no table %r" % (device, what))
+        if nbytes == 0:
+            return None
+        dt = {DT_SAFE: np.uint64, DT_RCWIN: np.uint8}.get(what, np.uint32)
+        out = np.zeros(nbytes // np.dtype(dt).itemsize, dtype=dt)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_index_debug_table(self.h, int(device), int(what), out.ctypes.data_as(C.c_void_p), out.nbytes, err, 512), err)
+        return out.reshape(-1, 2) if what in (DT_PTAB, DT_JTAB) else out.reshape(-1, 4) if what in (DT_CBF, DT_FBF) else out
+
+    def string_filter_geometry(self, device=0):
+        """(cbf_m, cbf_log2) of the device replica's string filters: the length of their strings and log2 of their number of 128-bit blocks; (0, 0): none"""
+        m, lg = C.c_uint32(0), C.c_uint32(0)
+        rc = self.L.fin_index_string_filter_geometry(self.h, int(device), C.byref(m), C.byref(lg))
+        if rc != 0:
+            raise FinitoError(rc, "string_filter_geometry: no replica on device %d" % device)
+        return int(m.value), int(lg.value)
 
     def kmer_table_query(self, kmers, device=0):
         """fin_index_debug_kmer_table: what the compact k-mer table claims about each k-mer (strings over ACGT of length k): (g, flags) arrays"""

@@ -650,6 +650,50 @@ int fin_index_debug_seed_table(const fin_index* x, int device, uint32_t* out, ch
     return FIN_OK;
 }
 
+// diagnostic (tests): a derived table of the replica on `device` as it lies in HBM -- where it is and how many bytes of its allocation are the table (the rest is padding)
+static const void* debug_table_of(const fin_index* x, const fin_index::Replica& r, int what, uint64_t& bytes) {
+    const FinDevIndex& d = r.dev;
+    const void* p = nullptr; bytes = 0;
+    switch (what) {
+        case FIN_DT_PTAB: p = r.d_ptab; bytes = sizeof(FinPrefixIval) << (2 * d.ptab_t); break;
+        case FIN_DT_JTAB: p = r.d_jtab; bytes = sizeof(FinPrefixIval) << (2 * d.jtab_t); break;
+        case FIN_DT_FILT: p = r.d_filt; bytes = (1ull << (2 * d.filt_f)) / 8; break;
+        case FIN_DT_SAFE: p = r.d_safe; bytes = (x->total_len + 63) / 64 * 8; break;
+        case FIN_DT_RCWIN: p = r.d_rcwin; bytes = (x->total_len + 511) / 512; break;
+        case FIN_DT_CBF: p = r.d_cbf; bytes = 16ull << d.cbf_log2; break;
+        case FIN_DT_FBF: p = r.d_fbf; bytes = 16ull << d.cbf_log2; break;
+        default: break;
+    }
+    if (!p) bytes = 0;
+    return p;
+}
+int64_t fin_index_debug_table_bytes(const fin_index* x, int device, int what) {
+    const fin_index::Replica* r = x ? x->replica_on(device) : nullptr;
+    if (!r || what < FIN_DT_PTAB || what > FIN_DT_FBF) return -1;
+    uint64_t bytes = 0;
+    (void)debug_table_of(x, *r, what, bytes);
+    return (int64_t)bytes;
+}
+int fin_index_debug_table(const fin_index* x, int device, int what, void* out, uint64_t out_bytes, char* err, size_t errlen) {
+    if (!x || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    const fin_index::Replica* r = x->replica_on(device);
+    if (!r) { set_err(err, errlen, "no replica on that device"); return FIN_EINVAL; }
+    uint64_t bytes = 0;
+    const void* p = debug_table_of(x, *r, what, bytes);
+    if (!p) { set_err(err, errlen, "the replica on that device has no such table"); return FIN_EINVAL; }
+    if (out_bytes < bytes) { set_err(err, errlen, "table buffer too small"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipMemcpy(out, p, bytes, hipMemcpyDeviceToHost));
+    return FIN_OK;
+}
+int fin_index_string_filter_geometry(const fin_index* x, int device, uint32_t* m, uint32_t* log2_blocks) {
+    const fin_index::Replica* r = x ? x->replica_on(device) : nullptr;
+    if (!r) return FIN_EINVAL;
+    if (m) *m = r->d_cbf ? r->dev.cbf_m : 0u;
+    if (log2_blocks) *log2_blocks = r->d_cbf ? r->dev.cbf_log2 : 0u;
+    return FIN_OK;
+}
+
 // diagnostic (tests): what the compact k-mer table of the replica on `device` claims about n k-mers given as their two key words (2-bit codes, first base in the low
 // bits; k1 = 0 for k <= 32): out[2 i] = g, out[2 i + 1] = flags (fin_kt3_query_kernel).  FIN_EINVAL: that replica has no k-mer table
 int fin_index_debug_kmer_table(const fin_index* x, int device, const uint64_t* k0, const uint64_t* k1, uint64_t n, uint32_t* out, char* err, size_t errlen) {

@@ -233,6 +233,30 @@ int64_t fin_index_rc_pairs(const fin_index* idx, int device);
  * the dummy node that holds d bases; out[2v+1] = the entry's unitig, top bit set when the text at that place does not spell the k-mer
  * (unverified); 2 * n_nodes entries.  FIN_EINVAL if there is none. */
 int fin_index_debug_seed_table(const fin_index* idx, int device, uint32_t* out, char* err, size_t errlen);
+/* diagnostic (tests): the other tables the upload derived on the replica on `device`, as they lie in HBM -- a plain copy of the table's payload, without the
+ * padding of its allocation.  `what`:
+ *   FIN_DT_PTAB / FIN_DT_JTAB  4^T / 4^J entries {uint32 l, uint32 r}: the SBWT interval of the string whose key (sum code(s[i]) << 2i) is the entry's number, l > r
+ *                              when the string is the suffix of no node
+ *   FIN_DT_FILT                4^F bits as uint32 words: bit key = the string of F bases with that key lies inside a unitig
+ *   FIN_DT_SAFE                uint64[ceil(total_len / 64)]: bit g = the k-mer the text spells at [g-k+1, g] is reported at g by the reference (absent when every
+ *                              k-mer place is safe)
+ *   FIN_DT_RCWIN               uint8[ceil(total_len / 512)]: bit w of byte b = a k-mer that ends in the text positions [512 b + 64 w, 512 b + 64 w + 64) has its reverse
+ *                              complement in the index (absent when no k-mer has)
+ *   FIN_DT_CBF / FIN_DT_FBF    2^log2 blocks of four uint32: the canonical / directional string filter (geometry: fin_index_string_filter_geometry)
+ * fin_index_debug_table_bytes: the payload's size, 0 when the replica carries no such table, -1: no replica there or no such `what`.  fin_index_debug_table copies
+ * it into out (out_bytes >= that size); FIN_EINVAL when there is no replica, no such table, or no room. */
+#define FIN_DT_PTAB 0
+#define FIN_DT_JTAB 1
+#define FIN_DT_FILT 2
+#define FIN_DT_SAFE 3
+#define FIN_DT_RCWIN 4
+#define FIN_DT_CBF 5
+#define FIN_DT_FBF 6
+int64_t fin_index_debug_table_bytes(const fin_index* idx, int device, int what);
+int fin_index_debug_table(const fin_index* idx, int device, int what, void* out, uint64_t out_bytes, char* err, size_t errlen);
+/* the string filters of the replica on `device`: *m = the length of their strings in bases, *log2_blocks = log2 of their number of 128-bit blocks (either may be
+ * null); both 0 when the replica has none.  FIN_EINVAL: no replica there */
+int fin_index_string_filter_geometry(const fin_index* idx, int device, uint32_t* m, uint32_t* log2_blocks);
 
 /* Read-only views of the members FinimizerIndex exposes publicly (FinimizerIndex.hh:108-115), decoded from the
  * HBM layout into plain arrays.  `what` selects the member; out must hold fin_index_export_size(idx, what) bytes. */

@@ -313,3 +313,294 @@ def hand_made_case(k):
             a.setflags(write=False)
         _HAND_MADE[k] = SimpleNamespace(k=k, genome=g, unitigs=unitigs, ends=ends, reads=reads, nks=nks, recs=recs, stream=stream, pairs=pairs)
     return _HAND_MADE[k]
+
+
+# ---- the tables an upload derives on the device, restated from their definitions (finito_amd/csrc/fin_format.h: FinDevIndex) ---------------------------
+# Inputs are what fin_index_export gives -- the text as one code per base (FIN_X_CONCAT), the unitigs' exclusive ends (FIN_X_ENDS), the C array and the four
+# planes as one 0/1 per node -- and, for the safe places, the oracle.  Nothing here calls the library.
+FIN_CBF_BITS = 5
+_M64 = (1 << 64) - 1
+
+
+def text_of(concat):
+    return "".join("ACGT"[c] for c in concat)
+
+
+def default_cbf_m(k):
+    """the string length an upload picks for its string filters by itself: 20, less for k < 29 (3 (k - m + 1) >= k)"""
+    return max(1, min(k + 1 - (k + 2) // 3, 20, k))
+
+
+def string_key(s):
+    """key of a string: sum code(s[j]) << 2j"""
+    return sum("ACGT".index(ch) << (2 * j) for j, ch in enumerate(s))
+
+
+def cbf_hash(key):
+    """fin_cbf_hash on a Python integer"""
+    key ^= key >> 29; key = (key * 0xBF58476D1CE4E5B9) & _M64; key ^= key >> 32; key = (key * 0x94D049BB133111EB) & _M64; key ^= key >> 29
+    return key
+
+
+def cbf_bits(key, log2):
+    """the bit numbers (in the whole filter) a string with this key sets / needs: FIN_CBF_BITS of them inside one block of 128"""
+    h = cbf_hash(key)
+    block = (h >> 35) & ((1 << log2) - 1)
+    return [128 * block + ((h >> (7 * i)) & 127) for i in range(FIN_CBF_BITS)]
+
+
+def string_keys(concat, ends, m):
+    """every string of m bases that lies inside one unitig: (its key, its reverse complement's key, the text position of its last base), uint64 / int64 arrays"""
+    code = np.asarray(concat, dtype=np.uint64)
+    n = len(code)
+    if n < m:
+        return np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.int64)
+    uid = np.searchsorted(np.asarray(ends, dtype=np.int64), np.arange(n), side="right")
+    a = np.nonzero(uid[:n - m + 1] == uid[m - 1:])[0]
+    f = np.zeros(len(a), dtype=np.uint64); v = np.zeros(len(a), dtype=np.uint64)
+    for j in range(m):
+        f |= code[a + j] << np.uint64(2 * j)
+        v |= (np.uint64(3) - code[a + m - 1 - j]) << np.uint64(2 * j)
+    return f, v, (a + m - 1).astype(np.int64)
+
+
+def ref_string_filter(concat, ends, m, log2, canonical):
+    """FinDevIndex::cbf (canonical) / fbf: uint32 [2^log2, 4]"""
+    f, v, _ = string_keys(concat, ends, m)
+    key = np.minimum(f, v) if canonical else f
+    h = key.copy()
+    h ^= h >> np.uint64(29); h *= np.uint64(0xBF58476D1CE4E5B9); h ^= h >> np.uint64(32); h *= np.uint64(0x94D049BB133111EB); h ^= h >> np.uint64(29)
+    block = ((h >> np.uint64(35)) & np.uint64((1 << log2) - 1)).astype(np.int64)
+    words = np.zeros(4 << log2, dtype=np.uint32)
+    for i in range(FIN_CBF_BITS):
+        p = ((h >> np.uint64(7 * i)) & np.uint64(127)).astype(np.int64)
+        np.bitwise_or.at(words, 4 * block + (p >> 5), (np.uint32(1) << (p & 31).astype(np.uint32)))
+    return words.reshape(-1, 4)
+
+
+def ref_absence_filter(concat, ends, F):
+    """FinDevIndex::filt: 4^F bits as uint32 words, bit key set iff the string with that key lies inside one unitig"""
+    f, _, _ = string_keys(concat, ends, F)
+    words = np.zeros((1 << (2 * F)) // 32, dtype=np.uint32)
+    np.bitwise_or.at(words, (f >> np.uint64(5)).astype(np.int64), np.uint32(1) << (f & np.uint64(31)).astype(np.uint32))
+    return words
+
+
+def ref_prefix_intervals(C, planes, n_nodes, T):
+    """FinDevIndex::ptab / jtab: the SBWT search from [0, n_nodes - 1] for all 4^T keys at once, l <- C[c] + rank_c(l), r <- C[c] + rank_c(r + 1) - 1 with
+    c = base i of the key (bits 2i); planes[c] = one 0/1 per node.  Returns (l, r, nonempty), int64 / bool [4^T]; l and r mean nothing where nonempty is false"""
+    cum = np.zeros((4, n_nodes + 1), dtype=np.int64)
+    for c in range(4):
+        cum[c, 1:] = np.cumsum(np.asarray(planes[c][:n_nodes], dtype=np.int64))
+    C = np.asarray(C, dtype=np.int64)
+    keys = np.arange(1 << (2 * T), dtype=np.int64)
+    l = np.zeros(len(keys), dtype=np.int64); r = np.full(len(keys), n_nodes - 1, dtype=np.int64)
+    alive = np.ones(len(keys), dtype=bool)
+    for i in range(T):
+        c = (keys >> (2 * i)) & 3
+        nl = C[c] + cum[c, l]; nr = C[c] + cum[c, r + 1] - 1
+        alive &= nl <= nr
+        l = np.where(alive, nl, 0); r = np.where(alive, nr, 0)
+    return l, r, alive
+
+
+def kmer_ends(ends, k):
+    """the text positions that end a k-mer inside a unitig, ascending"""
+    ends = np.asarray(ends, dtype=np.int64)
+    starts = np.concatenate([[0], ends[:-1]])
+    return np.concatenate([np.arange(s + k - 1, e) for s, e in zip(starts, ends)] + [np.zeros(0, np.int64)]).astype(np.int64)
+
+
+def ref_safe(oracle, text, ends, k):
+    """FinDevIndex::safe on the positions that end a k-mer: (those positions, uint8 bit per position) -- the bit is set iff the oracle's search of that k-mer alone
+    reports the place that ends there"""
+    ends = np.asarray(ends, dtype=np.int64)
+    starts = np.concatenate([[0], ends[:-1]])
+    at = kmer_ends(ends, k)
+    answer = {}
+    bit = np.zeros(len(at), dtype=np.uint8)
+    for i, g in enumerate(at):
+        q = text[g - k + 1:g + 1]
+        if q not in answer:
+            (u, off), = oracle.search(q)[0]
+            answer[q] = int(starts[u]) + off + k - 1 if u >= 0 else -1
+        bit[i] = answer[q] == g
+    return at, bit
+
+
+def ref_rcwin(text, ends, k):
+    """FinDevIndex::rcwin: (uint8 [ceil(len / 512)], the number of k-mer places whose k-mer has its reverse complement among the k-mers of the text)"""
+    at = kmer_ends(ends, k)
+    kmers = {text[g - k + 1:g + 1] for g in at}
+    win = np.zeros((len(text) + 511) // 512, dtype=np.uint8)
+    n = 0
+    for g in at:
+        if rc(text[g - k + 1:g + 1]) in kmers:
+            win[g >> 9] |= 1 << ((g >> 6) & 7)
+            n += 1
+    return win, n
+
+
+def bits_at(words, at):
+    """bits `at` of a bitmap given as uint64 words"""
+    at = np.asarray(at, dtype=np.int64)
+    return ((np.asarray(words, dtype=np.uint64)[at >> 6] >> (at & 63).astype(np.uint64)) & np.uint64(1)).astype(np.uint8)
+
+
+def bit_table_diff(got, want):
+    """two bit tables of the same shape, two-sided: {'lacking': bits the definition sets and `got` does not -- a missing entry, a correctness bug --,
+    'extra': bits `got` sets and the definition does not -- a precision bug --, 'first_lacking' / 'first_extra': the flat word index of the first such word or None}"""
+    got = np.asarray(got).reshape(-1); want = np.asarray(want).reshape(-1)
+    assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
+    lack = want & ~got; extra = got & ~want
+    cnt = lambda a: int(np.unpackbits(a.view(np.uint8)).sum())
+    first = lambda a: int(np.nonzero(a)[0][0]) if a.any() else None
+    return {"lacking": cnt(lack), "extra": cnt(extra), "first_lacking": first(lack), "first_extra": first(extra)}
+
+
+def assert_bit_tables_equal(got, want, what):
+    d = bit_table_diff(got, want)
+    assert d["lacking"] == 0 and d["extra"] == 0, ("%s: the device lacks %d bits the definition sets (first in word %s): entries are MISSING, a correctness bug; "
+                                                  "it sets %d bits the definition does not (first in word %s): a precision bug" %
+                                                  (what, d["lacking"], d["first_lacking"], d["extra"], d["first_extra"]))
+
+
+def interval_table_diff(tab, l, r, nonempty):
+    """keys at which an interval table [4^T, 2] disagrees with ref_prefix_intervals: (l, r) equal where the definition's interval is non-empty, l > r elsewhere"""
+    tab = np.asarray(tab, dtype=np.int64)
+    bad = np.where(nonempty, (tab[:, 0] != l) | (tab[:, 1] != r), ~(tab[:, 0] > tab[:, 1]))
+    return np.nonzero(bad)[0]
+
+
+# ---- the unitig sets the upload-table tests run on (tests/test_upload_tables.py on the device, tests/test_upload_tables_host.py asserts the classes) --------------
+# A builder lane takes 512 text positions, so what matters is where unitigs and strings lie against the multiples of 512 -- in the INDEX's order of the unitigs
+# (by first k-mer, colexicographically; equal ones by input number).  Shortening a unitig at its end keeps its first k-mer, hence the order: that is how a set is
+# made to measure.
+UPLOAD_SEG = 512
+UPLOAD_KS = (12, 16, 21, 31, 32, 33, 63, 100)
+
+
+def _index_order(unitigs, k):
+    return sorted(range(len(unitigs)), key=lambda i: (unitigs[i][:k][::-1], i))
+
+
+def _shorten(unitigs, k, which, excess):
+    """take `excess` bases off the ends of the unitigs `which`, in that order (none below k bases); False: they have not that many to give"""
+    for i in which:
+        cut = min(excess, len(unitigs[i]) - k)
+        if cut:
+            unitigs[i] = unitigs[i][:len(unitigs[i]) - cut]; excess -= cut
+        if not excess:
+            return True
+    return False
+
+
+def end_a_unitig_at(unitigs, k, at, spare=()):
+    """a copy of the set in which, in the index's order, a unitig ends exactly at text position `at`: the unitigs in front of the one that crossed it are
+    shortened (the nearest first, none of `spare`), then that one.  (the copy, that unitig's number), or None: impossible"""
+    unitigs = list(unitigs)
+    order = _index_order(unitigs, k); cum = 0
+    for j, i in enumerate(order):
+        cum += len(unitigs[i])
+        if cum >= at:
+            return (unitigs, i) if _shorten(unitigs, k, [x for x in reversed(order[:j]) if x not in spare] + [i], cum - at) else None
+    return None
+
+
+def fit_total(unitigs, k, total):
+    unitigs = list(unitigs)
+    assert _shorten(unitigs, k, list(reversed(_index_order(unitigs, k))), sum(len(u) for u in unitigs) - total), "the set cannot be cut down to %d bases" % total
+    return unitigs
+
+
+_UPLOAD_CASES = None
+
+
+def upload_table_cases():
+    """the unitig sets, made once: a list of namespaces (name, k, unitigs); nobody changes them.  Per k of UPLOAD_KS a "general" set -- a unitig of more than 1024
+    bases, a dozen of k .. k + 8 bases, one of exactly k, pieces of a genome in either orientation, a unitig made to end on a multiple of 512 with at least 2k - 1
+    bases, 2k + 10 bases in the first and the last unitig of the index's order --; sets whose whole text has k, 511, 512, 513 and a multiple of 512 plus m - 2 bases (m: the string filters' default length); sets of the deferral
+    family (identical unitigs, near-duplicates, duplicated stretches, reverse-complement copies); disjoint sets with reverse-complement copies and, k even, a k-mer
+    that is its own reverse complement; tiny sets at k = 4, 5 and 9 for interval tables as deep as k and k - 1"""
+    global _UPLOAD_CASES
+    if _UPLOAD_CASES is not None:
+        return _UPLOAD_CASES
+    from types import SimpleNamespace
+    cases = []
+    add = lambda name, k, unitigs: cases.append(SimpleNamespace(name=name, k=k, unitigs=tuple(unitigs)))
+    for k in UPLOAD_KS:
+        rng = np.random.default_rng(9000 + k)
+        us = [random_genome(rng, 1300)] + [random_genome(rng, k + int(rng.integers(0, 9))) for _ in range(12)] + [random_genome(rng, k)]
+        us += cut_unitigs(rng, random_genome(rng, 1500), k, max_len=3 * k + 100, flip=True)
+        # the first and the last unitig of the index's order (their first k-mers end with AAAA / TTTT), with room for 2k - 1 bases and more
+        us += [random_genome(rng, k - 4) + end * 4 + random_genome(rng, k + 14) for end in "AT"]
+        done = None
+        for at in range(UPLOAD_SEG, sum(len(u) for u in us), UPLOAD_SEG):   # the first multiple at which the unitig that ends there has 2k - 1 bases
+            cut = end_a_unitig_at(us, k, at, spare=(0, len(us) - 2, len(us) - 1))
+            if cut and len(cut[0][cut[1]]) >= 2 * k - 1 and cut[1] != 0:
+                done = cut[0]
+                break
+        assert done is not None
+        add("general_k%d" % k, k, done)
+    for k, total in ((12, 12), (12, 511), (12, 512), (12, 513), (12, 2 * UPLOAD_SEG + default_cbf_m(12) - 2), (31, UPLOAD_SEG + default_cbf_m(31) - 2),
+                     (63, 2 * UPLOAD_SEG + default_cbf_m(63) - 2)):
+        rng = np.random.default_rng(9500 + 7 * k + total)
+        us = [random_genome(rng, k)] if total == k else fit_total(cut_unitigs(rng, random_genome(rng, total + 10), k, max_len=max(90, 4 * k), flip=True), k, total)
+        add("total_%d_k%d" % (total, k), k, us)
+    for k, case in ((12, 3), (21, 4), (33, 1), (63, 2)):
+        rng = np.random.default_rng(9700 + k)
+        add("family_k%d" % k, k, defer_family_case(rng, case, k, n_reads=3)[1])
+    for k in (12, 16, 21, 32):
+        rng = np.random.default_rng(9800 + k)
+        g = random_genome(rng, 1200)
+        us = cut_unitigs(rng, g, k, max_len=4 * k + 60, flip=False) + [rc(g[200:200 + 5 * k])]   # (one orientation: the copy's k-mers are in no other unitig)
+        if k % 2 == 0:
+            w = random_genome(rng, k // 2)
+            us.append(random_genome(rng, 7) + w + rc(w) + random_genome(rng, 7))
+        add("rc_k%d" % k, k, us)
+    for k in (4, 5, 9):
+        rng = np.random.default_rng(9900 + k)
+        add("tiny_k%d" % k, k, cut_unitigs(rng, random_genome(rng, 300), k, max_len=40, flip=True))
+    _UPLOAD_CASES = cases
+    return cases
+
+
+def upload_case(name):
+    return next(c for c in upload_table_cases() if c.name == name)
+
+
+_UPLOAD_HOST = {}
+
+
+def upload_case_host(case):
+    """what the references need of a case, from the host builder and the oracle, made once per case and shared: concat (codes), text, ends, starts, C, planes
+    (0/1 per node), n_nodes, oracle.  The oracle's own index of the same unitigs must be the exported one"""
+    if case.name not in _UPLOAD_HOST:
+        from types import SimpleNamespace
+        import finito_amd as fa
+        from oracle.oracle import OracleIndex
+        p = fa.FinimizerIndex.build(list(case.unitigs), case.k)
+        concat = p.export(fa.X_CONCAT); ends = p.export(fa.X_ENDS).astype(np.int64); n = p.n_nodes
+        planes = [unpack_bits(p.export(fa.X_PLANE_A + c), n) for c in range(4)]
+        C = p.export(fa.X_C)[:4].astype(np.int64)
+        p.close()
+        o = OracleIndex.build(list(case.unitigs), case.k)
+        assert np.array_equal(o.concat(), concat) and np.array_equal(o.ends(), ends)
+        for a in (concat, ends, C):
+            a.setflags(write=False)
+        _UPLOAD_HOST[case.name] = SimpleNamespace(concat=concat, text=text_of(concat), ends=ends, starts=np.concatenate([[0], ends[:-1]]), C=C, planes=planes, n_nodes=n,
+                                                  oracle=o, memo={})
+    return _UPLOAD_HOST[case.name]
+
+
+def yes_reads(text, k, a, b):
+    """reads that follow unitig A = text[a[0]:a[1]] for k + 5 bases (its last ones, or first ones) and carry 2k - 1 bases of B = text[b[0]:b[1]] at every offset:
+    both orders, both strands"""
+    A = text[a[0]:a[1]]; B = text[b[0]:b[1]]
+    n = min(len(A), k + 5)
+    reads = []
+    for o in range(len(B) - (2 * k - 1) + 1):
+        piece = B[o:o + 2 * k - 1]
+        for r in (A[-n:] + piece, piece + A[:n]):
+            reads += [r, rc(r)]
+    return reads
