@@ -206,6 +206,25 @@ def lib():
         L.fin_search_batch_read_summaries.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u64p, cp, C.c_size_t]
         L.fin_search_batch_screen.argtypes = [vp, cp, u64p, u64, C.c_int, C.c_uint32, C.c_uint32, C.c_int, u64p, u64p, cp, C.c_size_t]
         L.fin_records_read_summaries.argtypes = [vp, u64, vp, u64, C.c_int, vp, C.c_int]
+        u32 = C.c_uint32
+        L.fin_labels_create.argtypes = [vp, C.c_int, vp, u32, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_labels_reset.argtypes = [vp, vp]
+        L.fin_labels_device_labels.argtypes = [vp]
+        L.fin_labels_device_labels.restype = vp
+        L.fin_labels_device_reads.argtypes = [vp]
+        L.fin_labels_device_reads.restype = vp
+        L.fin_labels_download.argtypes = [vp, u64p, u64p, cp, C.c_size_t]
+        L.fin_labels_free.argtypes = [vp]
+        L.fin_labels_free.restype = None
+        L.fin_batch_classify.argtypes = [vp, vp, cp, C.c_size_t]
+        L.fin_batch_device_read_classes.argtypes = [vp]
+        L.fin_batch_device_read_classes.restype = vp
+        L.fin_batch_download_read_classes.argtypes = [vp, vp, cp, C.c_size_t]
+        L.fin_batch_add_classes.argtypes = [vp, vp, u32, u32, u32, vp, cp, C.c_size_t]
+        L.fin_search_batch_classify.argtypes = [vp, cp, u64p, u64, C.c_int, vp, vp, u64p, cp, C.c_size_t]
+        L.fin_search_batch_add_classes.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, u32, cp, C.c_size_t]
+        L.fin_records_read_classes.argtypes = [vp, u64, vp, u64, C.c_int, vp, u64, vp, C.c_int]
+        L.fin_index_unitig_numbers.argtypes = [vp, cp, u64p, u64, vp, cp, C.c_size_t]
         _LIB = L
     return _LIB
 
@@ -421,6 +440,19 @@ class Batch:
         """(ids, bits) device pointers, 0 before screen()"""
         return int(self.L.fin_batch_device_screen_ids(self.h) or 0), int(self.L.fin_batch_device_screen_bits(self.h) or 0)
 
+    def classify(self, labels):
+        """the most recent run's results as one class per read under a labelling (Labels), made on the device (fin_batch_classify +
+        fin_batch_download_read_classes): READ_CLASS_DTYPE[n_reads] -- label (FIN_NO_LABEL: none), n_best, n_second, n_labelled"""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_classify(self.h, labels.h, err, 512), err)
+        out = np.zeros(max(self.n_reads, 1), dtype=READ_CLASS_DTYPE)
+        _check(self.L.fin_batch_download_read_classes(self.h, out.ctypes.data_as(C.c_void_p), err, 512), err)
+        return out[: self.n_reads]
+
+    def device_read_classes_ptr(self):
+        """the classes' device pointer, 0 before classify() / Labels.add()"""
+        return int(self.L.fin_batch_device_read_classes(self.h) or 0)
+
     def pipeline_counts(self, n=64):
         """kernel 4's queue counters of the last run (fin_batch_pipeline_counts)"""
         out = (C.c_uint32 * n)()
@@ -519,6 +551,85 @@ class Hits:
     def close(self):
         if getattr(self, "h", None):
             self.L.fin_hits_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _class_thresholds(what, min_found, min_permille, min_margin):
+    if not all(0 <= int(v) <= 0xFFFFFFFF for v in (min_found, min_permille, min_margin)):
+        raise FinitoError(FIN_EINVAL, what + ": min_found, min_permille and min_margin are unsigned 32-bit numbers")
+    return int(min_found), int(min_permille), int(min_margin)
+
+
+class Labels:
+    """a labelling of the index's unitigs (uint32 per unitig: a label below n_labels, or FIN_NO_LABEL) resident in HBM beside one replica, with the tally of the
+    reads assigned to each label (fin_labels_* of the C ABI).  Unitig numbers are the index's own (FinimizerIndex.unitig_numbers maps an input order to them)."""
+
+    def __init__(self, index, unitig_labels, n_labels=None, device=0):
+        self.index = index
+        self.L = lib()
+        lab = np.asarray(unitig_labels)
+        if lab.ndim != 1 or len(lab) != index.n_unitigs:
+            raise FinitoError(FIN_EINVAL, "labels: one label per unitig of the index (%d), got %s" % (index.n_unitigs, lab.shape))
+        if len(lab) and (lab.dtype.kind not in "iu" or int(lab.min()) < 0 or int(lab.max()) > FIN_NO_LABEL):
+            raise FinitoError(FIN_EINVAL, "labels: unsigned 32-bit numbers, FIN_NO_LABEL for none")
+        lab = np.ascontiguousarray(lab, dtype=np.uint32)
+        if n_labels is None:
+            named = lab[lab != FIN_NO_LABEL]
+            n_labels = int(named.max()) + 1 if len(named) else 1
+        if not 0 <= int(n_labels) <= 0xFFFFFFFF:
+            raise FinitoError(FIN_EINVAL, "labels: n_labels is 1 .. 2^31")
+        self.n_labels = int(n_labels)
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_labels_create(index.h, int(device), lab.ctypes.data_as(C.c_void_p), self.n_labels, C.byref(h), err, 512), err)
+        self.h = h
+
+    def add(self, batch, min_found=1, min_permille=0, min_margin=0, stream=None):
+        """tally += the reads of the batch's most recent run: a read goes to its class's label when n_best >= max(min_found, 1), 1000 * n_best >= min_permille * nk
+        and n_best >= n_second + min_margin, else to `unassigned`; on a HIP stream, behind that run, no sync (fin_batch_add_classes).  Adding twice counts twice."""
+        t = _class_thresholds("Labels.add", min_found, min_permille, min_margin)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_add_classes(batch.h, self.h, t[0], t[1], t[2], C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add_reads(self, reads, min_found=1, min_permille=0, min_margin=0, strands=FIN_MERGED):
+        """search a read set from host buffers, sub-batches pipelined as in search_reads, and tally its reads; nothing comes back (fin_search_batch_add_classes)"""
+        t = _class_thresholds("Labels.add_reads", min_found, min_permille, min_margin)
+        bases, offsets = flatten(reads)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_add_classes(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+                                                   int(strands), self.h, t[0], t[1], t[2], err, 512), err)
+        return self
+
+    def reset(self, stream=None):
+        """zero the tally; the labelling stays"""
+        rc = self.L.fin_labels_reset(self.h, C.c_void_p(stream or 0))
+        if rc != 0:
+            raise FinitoError(rc, "fin_labels_reset")
+        return self
+
+    def download(self):
+        """(uint64 reads[n_labels + 1] -- the reads assigned to each label, then the unassigned ones --, their sum = the reads added); waits for the adds
+        (fin_labels_download)"""
+        out = np.zeros(self.n_labels + 1, dtype=np.uint64)
+        tot = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_labels_download(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(tot), err, 512), err)
+        return out, int(tot.value)
+
+    def device_ptrs(self):
+        """(labels uint32[n_unitigs], reads uint64[n_labels + 1]) device pointers"""
+        return int(self.L.fin_labels_device_labels(self.h) or 0), int(self.L.fin_labels_device_reads(self.h) or 0)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fin_labels_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -967,6 +1078,31 @@ class FinimizerIndex:
             raise FinitoError(FIN_EINVAL, "screen_reads: the bitmap holds %d reads, the device counted %d" % (int(out.sum()), int(n_pass.value)))
         return out
 
+    def labels(self, unitig_labels, n_labels=None, device=0):
+        """a labelling of this index's unitigs beside the replica on `device`, with a zeroed tally (Labels); n_labels defaults to the largest label + 1"""
+        return Labels(self, unitig_labels, n_labels, device)
+
+    def classify_reads(self, reads, labels, strands=FIN_MERGED):
+        """fin_search_batch_classify: READ_CLASS_DTYPE[n_reads] from host buffers -- 16 bytes per read come back, nothing per k-mer"""
+        bases, offsets = flatten(reads)
+        n = len(offsets) - 1
+        out = np.zeros(max(n, 1), dtype=READ_CLASS_DTYPE)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_classify(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands), labels.h,
+                                                out.ctypes.data_as(C.c_void_p), None, err, 512), err)
+        return out[:n]
+
+    def unitig_numbers(self, unitigs):
+        """fin_index_unitig_numbers: uint32[len(unitigs)] -- the index's number of each given unitig sequence (the index renumbers its input); raises for a
+        sequence that is not a unitig of this index"""
+        bases, offsets = flatten(unitigs)
+        n = len(offsets) - 1
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_index_unitig_numbers(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                               out.ctypes.data_as(C.c_void_p), err, 512), err)
+        return out[:n]
+
     def hits(self, device=0):
         """a zeroed per-unitig accumulator beside the replica on `device` (Hits)"""
         return Hits(self, device)
@@ -1058,6 +1194,8 @@ class FinimizerIndex:
 RECORD_DTYPE = np.dtype([("u", np.uint32), ("off0", np.uint32), ("meta", np.uint32), ("nk", np.uint32), ("Es", np.uint64), ("Es2", np.uint64)])
 SEGMENT_DTYPE = np.dtype([("u", np.int32), ("off", np.int32), ("slot", np.uint32), ("len", np.int32)])   # fin_segment
 READ_SUMMARY_DTYPE = np.dtype([("n_found", np.uint32), ("n_segments", np.uint32), ("longest", np.uint32), ("span", np.uint32)])   # fin_read_summary
+READ_CLASS_DTYPE = np.dtype([("label", np.uint32), ("n_best", np.uint32), ("n_second", np.uint32), ("n_labelled", np.uint32)])   # fin_read_class
+FIN_NO_LABEL = 0xFFFFFFFF
 DEPTH_STAT_DTYPE = np.dtype([("sum", np.uint64), ("max", np.uint32), ("n_at_least", np.uint32)])            # fin_depth_stat
 
 
@@ -1299,6 +1437,19 @@ def records_read_summaries(recs, stream, k, n_threads=0):
                                           out.ctypes.data_as(C.c_void_p), int(n_threads))
     if rc != 0:
         raise FinitoError(rc, "fin_records_read_summaries: records and stream do not belong together, or a pair that is neither found nor (-1,-1)")
+    return out[: len(recs)]
+
+
+def records_read_classes(recs, stream, k, unitig_labels, n_threads=0):
+    """fin_records_read_classes (host): READ_CLASS_DTYPE[n_reads] from records + stream under unitig_labels (uint32 per unitig), without making the pairs"""
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE); stream = np.ascontiguousarray(stream, dtype=np.int32)
+    lab = np.ascontiguousarray(unitig_labels, dtype=np.uint32)
+    out = np.zeros(max(len(recs), 1), dtype=READ_CLASS_DTYPE)
+    rc = lib().fin_records_read_classes(recs.ctypes.data_as(C.c_void_p), len(recs), stream.ctypes.data_as(C.c_void_p), len(stream.reshape(-1, 2)), int(k),
+                                        lab.ctypes.data_as(C.c_void_p), len(lab), out.ctypes.data_as(C.c_void_p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_read_classes: a unitig number outside the labelling, records and stream that do not belong together, or a pair that is "
+                              "neither found nor (-1,-1)")
     return out[: len(recs)]
 
 

@@ -735,6 +735,8 @@ struct fin_batch {
     // per-read summaries and the screen made from them (fin_batch_read_summaries, fin_batch_screen): kept and only grown
     void* d_rsum = nullptr; void* d_scr_bits = nullptr; void* d_scr_ids = nullptr; void* d_scr_bsum = nullptr; void* d_scr_boff = nullptr;
     size_t cap_rsum = 0, cap_scr_bits = 0, cap_scr_ids = 0, cap_scr_bsum = 0, cap_scr_boff = 0; uint64_t n_pass = 0; bool rsum_ready = false, scr_ready = false;
+    // per-read classes under a labelling (fin_batch_classify): kept and only grown; cls_labels = the serial number of the labelling they were made for
+    void* d_cls = nullptr; size_t cap_cls = 0; bool cls_ready = false; uint64_t cls_labels = 0;
     uint64_t text_bytes = 0;
     // kernel 4: the queue counters of the most recent finished run, copied to page-locked memory behind every run: the next run launches only
     // as many stream / walk rounds as that one needed, plus one (fin_launch_search_v4's `rounds`)
@@ -770,7 +772,7 @@ void fin_batch_free(fin_batch* b) {
     if (b->ev_ctr) (void)hipEventDestroy(b->ev_ctr);
     (void)hipFree(b->d_cstream); (void)hipFree(b->d_frec); (void)hipFree(b->d_seg); (void)hipFree(b->d_text); (void)hipFree(b->d_last_bits); (void)hipFree(b->d_blk_sum); (void)hipFree(b->d_blk_off); (void)hipFree(b->d_total);
     (void)hipFree(b->d_sgm_cnt); (void)hipFree(b->d_sgm_bsum); (void)hipFree(b->d_sgm_boff); (void)hipFree(b->d_sgm_offs); (void)hipFree(b->d_sgm);
-    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff);
+    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls);
     (void)hipFree(b->d_ovf_list); (void)hipFree(b->d_ovf_count); (void)hipFree(b->d_ovf_scratch); (void)hipFree(b->d_count);
     for (auto& r : b->runs) for (auto& e : r.e) (void)hipEventDestroy(e);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -894,7 +896,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     //  decoding, inside its timed region, search_fmin.hh:46-71 -- is the first kernel of every step, see fin_batch_run)
     b->n_chunks = n_chunks; b->max_read_len = max_len;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "upload");
-    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false;
+    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false;
     b->rounds_hint = 0; b->ctr_pending = false;   // (new reads: nothing is known about the rounds they need)
     b->text_reads_state = 0;
     return FIN_OK;
@@ -938,7 +940,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     b->dev.budget_mult = (uint32_t)optv(b->idx, O_epoch_budget_mult); b->dev.budget_add = (uint32_t)optv(b->idx, O_epoch_budget_add);
     b->dev.ovf_cap = (uint32_t)std::min<uint64_t>(b->cap_ovf_list / 4, 0xFFFFFFFFull);
     if (const int64_t forced = optv(b->idx, O_debug_ovf_cap)) b->dev.ovf_cap = (uint32_t)std::min<int64_t>(forced, (int64_t)b->dev.ovf_cap);   // (tests: a tiny list)
-    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false;
+    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false;
     b->dev.pp_seg = (uint32_t)optv(b->idx, O_debug_pp_seg);
     b->dev.pp_max_len = (uint32_t)std::min<uint64_t>(b->max_read_len, 0xFFFFFFFFull);
     b->dev.pp_park = (uint32_t)optv(b->idx, O_pp_park);
@@ -1064,7 +1066,7 @@ int fin_batch_set_pairs(fin_batch* b, const int32_t* pairs, char* err, size_t er
     HIPCHK(hipSetDevice(b->device));
     if (b->last_stream) HIPCHK(hipStreamSynchronize(b->last_stream));
     HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
-    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false;   // (the records of the last run say nothing about these pairs)
+    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false;   // (the records of the last run say nothing about these pairs)
     return FIN_OK;
 }
 
@@ -1105,7 +1107,7 @@ int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32
     if (b->n_reads) HIPCHK(hipMemcpy(b->d_frec, recs, (size_t)b->n_reads * sizeof(FinFastRec), hipMemcpyHostToDevice));
     if (pairs && b->n_kmers) HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
     // last_frec / last_text_only stay as the run left them (a text-only batch still refuses its pairs); whatever was made from the old records goes
-    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false;
+    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false;
     b->rec_ready = false; b->rec_passthrough = false; b->rec_stream_pairs = 0;
     return FIN_OK;
 }
@@ -1786,6 +1788,180 @@ int fin_hits_download(fin_hits* h, uint64_t* counts_out, uint64_t* total, char* 
     return FIN_OK;
 }
 
+// ---- read classification by unitig labels (fin_classify.hip) ---------------------------------------------------------------------------
+static_assert(sizeof(fin_read_class) == 16, "a read class is 16 bytes");
+struct fin_labels {
+    const fin_index* idx = nullptr;
+    int device = -1;
+    uint64_t n_unitigs = 0; uint32_t n_labels = 0;
+    uint64_t serial = 0;        // which labelling a batch's classes were made for (an address can come back after a free)
+    void* d_labels = nullptr;   // uint32[n_unitigs]
+    void* d_reads = nullptr;    // the tally: uint64[n_labels + 1]
+    AccPending pend;
+};
+static std::atomic<uint64_t> g_labels_serial{0};
+
+void fin_labels_free(fin_labels* l) {
+    if (!l) return;
+    if (l->device >= 0) (void)hipSetDevice(l->device);
+    l->pend.drop();
+    (void)hipFree(l->d_labels); (void)hipFree(l->d_reads);
+    delete l;
+}
+
+int fin_labels_create(const fin_index* idx, int device, const uint32_t* unitig_labels, uint32_t n_labels, fin_labels** out, char* err, size_t errlen) {
+    if (!idx || !out || (idx->n_unitigs && !unitig_labels)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (n_labels == 0 || n_labels > 0x80000000u) { set_err(err, errlen, "n_labels is 1 .. 2^31"); return FIN_EINVAL; }
+    for (uint64_t u = 0; u < idx->n_unitigs; u++)
+        if (unitig_labels[u] != FIN_NO_LABEL && unitig_labels[u] >= n_labels) {
+            set_err(err, errlen, "unitig " + std::to_string(u) + " has label " + std::to_string(unitig_labels[u]) + ": neither below n_labels = " + std::to_string(n_labels) + " nor FIN_NO_LABEL");
+            return FIN_EINVAL;
+        }
+    if (!idx->replica_on(device)) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
+    HIPCHK(hipSetDevice(device));
+    fin_labels* l = new (std::nothrow) fin_labels();
+    if (!l) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
+    l->idx = idx; l->device = device; l->n_unitigs = idx->n_unitigs; l->n_labels = n_labels; l->serial = ++g_labels_serial;
+    const size_t tally = ((size_t)n_labels + 1) * 8;
+    if (hipMalloc(&l->d_labels, (size_t)l->n_unitigs * 4 + 16) != hipSuccess || hipMalloc(&l->d_reads, tally) != hipSuccess) {
+        (void)hipGetLastError(); fin_labels_free(l); set_err(err, errlen, "out of device memory (unitig labels and tally)"); return FIN_ENOMEM;
+    }
+    if ((l->n_unitigs && hipMemcpy(l->d_labels, unitig_labels, (size_t)l->n_unitigs * 4, hipMemcpyHostToDevice) != hipSuccess) || hipMemset(l->d_reads, 0, tally) != hipSuccess) {
+        fin_labels_free(l); set_err(err, errlen, "copying the labels failed"); return FIN_ENODEV;
+    }
+    *out = l;
+    return FIN_OK;
+}
+
+int fin_labels_reset(fin_labels* l, void* hip_stream) {
+    if (!l) return FIN_EINVAL;
+    if (hipSetDevice(l->device) != hipSuccess) return FIN_ENODEV;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (hipMemsetAsync(l->d_reads, 0, ((size_t)l->n_labels + 1) * 8, st) != hipSuccess) return FIN_ENODEV;
+    return l->pend.mark(st, nullptr, 0);
+}
+
+void* fin_labels_device_labels(const fin_labels* l) { return l ? l->d_labels : nullptr; }
+void* fin_labels_device_reads(const fin_labels* l) { return l ? l->d_reads : nullptr; }
+
+int fin_labels_download(fin_labels* l, uint64_t* reads_out, uint64_t* total, char* err, size_t errlen) {
+    if (!l) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(l->device));
+    if (const int wrc = l->pend.wait(err, errlen)) return wrc;
+    const size_t n = (size_t)l->n_labels + 1;
+    std::vector<uint64_t> tmp;
+    uint64_t* dst = reads_out;
+    if (!dst) { if (!total) return FIN_OK; tmp.resize(n); dst = tmp.data(); }
+    HIPCHK(hipMemcpy(dst, l->d_reads, n * 8, hipMemcpyDeviceToHost));
+    if (total) { uint64_t t = 0; for (size_t q = 0; q < n; q++) t += dst[q]; *total = t; }
+    return FIN_OK;
+}
+
+int fin_batch_classify(fin_batch* b, const fin_labels* l, char* err, size_t errlen) {
+    if (!b || !l) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->ran) { set_err(err, errlen, "this batch has not run: there is nothing to classify (fin_batch_run first)"); return FIN_EINVAL; }
+    if (b->idx != l->idx || b->device != l->device) { set_err(err, errlen, "batch and labelling belong to different indexes or devices"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    b->cls_ready = false;
+    // (no read has a k-mer: the step searched nothing, there is no overflow list to look at -- every class is the empty one)
+    if (b->n_kmers != 0) if (const int orc = batch_overrun_check(b, st, err, errlen)) return orc;   // a run without results: nothing is written
+    const uint32_t nr = (uint32_t)b->n_reads;
+    if (batch_grow(b, &b->d_cls, b->cap_cls, (size_t)nr * 16 + 16, st)) { set_err(err, errlen, "out of device memory (read classes)"); return FIN_ENOMEM; }
+    const int rc = fin_launch_classify(b->n_kmers != 0 && b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, nr, b->dev.k,
+                                       (const uint32_t*)l->d_labels, (uint32_t)l->n_unitigs, b->d_cls, st);
+    if (rc != 0) { set_err(err, errlen, std::string("classify kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    b->cls_ready = true; b->cls_labels = l->serial;
+    return FIN_OK;
+}
+
+void* fin_batch_device_read_classes(const fin_batch* b) { return b && b->cls_ready ? b->d_cls : nullptr; }
+
+int fin_batch_download_read_classes(fin_batch* b, fin_read_class* out, char* err, size_t errlen) {
+    if (!b || (b->n_reads && !out)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->cls_ready) { set_err(err, errlen, "fin_batch_classify first"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    if (b->n_reads) HIPCHK(hipMemcpyAsync(out, b->d_cls, (size_t)b->n_reads * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
+int fin_batch_add_classes(fin_batch* b, fin_labels* l, uint32_t min_found, uint32_t min_permille, uint32_t min_margin, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !l) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (min_permille > 1000u) { set_err(err, errlen, "min_permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (!b->cls_ready || b->cls_labels != l->serial) if (const int rc = fin_batch_classify(b, l, err, errlen)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (const int brc = acc_behind_run(b, l->idx, l->device, st, err, errlen)) return brc;
+    if (st != b->last_stream) {   // the classes were made on the run's stream, behind the run: the add waits for them too
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(ev, b->last_stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+        (void)hipEventDestroy(ev);   // (released once it has completed)
+        HIPCHK(e);
+    }
+    const int rc = fin_launch_class_tally(b->d_cls, (const uint64_t*)b->d_out_offs, (uint32_t)b->n_reads, l->n_labels, min_found, min_permille, min_margin,
+                                          (uint64_t*)l->d_reads, st);
+    if (rc != 0) { set_err(err, errlen, std::string("class tally kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    return l->pend.mark(st, err, errlen);
+}
+
+// host: the same classes from records + stream -- the CPU statement of fin_classify.hip, over the segments segment_slots / segment_record make: a segment of
+// |len| slots in unitig u is |len| votes for labels[u]
+int fin_records_read_classes(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k,
+                             const uint32_t* unitig_labels, uint64_t n_unitigs, fin_read_class* out, int n_threads) {
+    if ((n_reads && (!recs || !out)) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !unitig_labels)) return FIN_EINVAL;
+    int T = n_threads > 0 ? n_threads : fin_host_threads();
+    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
+    std::vector<uint64_t> str0((size_t)T + 1, 0);
+    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
+        const auto lh = bounds(t);
+        uint64_t sp = 0;
+        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
+        str0[(size_t)t + 1] = sp;
+    }
+    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
+    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
+    bool ok = true;
+#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
+    for (int t = 0; t < T; t++) {
+        const auto lh = bounds(t);
+        uint64_t sp = str0[(size_t)t];
+        bool good = true;
+        std::vector<std::pair<uint32_t, uint32_t>> votes;   // (label, slots) per segment, then sorted by label
+        for (uint64_t r = lh.first; r < lh.second && good; r++) {
+            const fin_read_record& R = recs[r];
+            const uint32_t kind = R.meta >> 16;
+            votes.clear();
+            auto emit = [&](int32_t u, int32_t, uint32_t, int32_t len) {
+                if ((uint64_t)(uint32_t)u >= n_unitigs) { good = false; return; }
+                const uint32_t L = unitig_labels[(uint32_t)u];
+                if (L != FIN_NO_LABEL) votes.push_back({L, (uint32_t)(len < 0 ? -(int64_t)len : (int64_t)len)});
+            };
+            if (kind == 0u) { good = segment_slots(stream_pairs + 2 * sp, R.nk, emit) && good; sp += R.nk; }
+            else if (kind == 1u) segment_record(R, k, emit);
+            std::sort(votes.begin(), votes.end());
+            fin_read_class C{FIN_NO_LABEL, 0, 0, 0};
+            for (size_t i = 0; i < votes.size();) {   // ascending labels: a later label wins only with a larger count
+                uint32_t c = 0; size_t j = i;
+                for (; j < votes.size() && votes[j].first == votes[i].first; j++) c += votes[j].second;
+                C.n_labelled += c;
+                if (c > C.n_best) { C.n_second = C.n_best; C.n_best = c; C.label = votes[i].first; }
+                else if (c > C.n_second) C.n_second = c;
+                i = j;
+            }
+            out[r] = C;
+        }
+        ok = good && ok;
+    }
+    return ok ? FIN_OK : FIN_EINVAL;
+}
+
 // host: the profile from records + stream -- fin_expand_records' arithmetic without the pairs.  A chunk of reads per thread, each with counts of its own
 // when the unitig set is small, else atomic adds into the caller's array
 int fin_records_unitig_counts(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t n_unitigs,
@@ -2273,6 +2449,9 @@ struct TextSink {
     //  fin_search_batch_screen -- a sub-batch's bitmap is shifted into scr_bits (may be null) at its first read's bit, under `mu`)
     fin_read_summary* rsum = nullptr;
     bool screen = false; uint32_t scr_min_found = 0, scr_min_permille = 0; int scr_invert = 0; uint64_t* scr_bits = nullptr; std::atomic<uint64_t> scr_pass{0};
+    // (classes when `cls` is set: fin_search_batch_classify -- a sub-batch's land at its reads' numbers; with `tally` every sub-batch is added to the
+    //  labelling's tally on the device instead and nothing comes back: fin_search_batch_add_classes)
+    const fin_labels* labels = nullptr; fin_read_class* cls = nullptr; fin_labels* tally = nullptr; uint32_t cls_min_found = 0, cls_min_permille = 0, cls_min_margin = 0;
     std::vector<uint64_t> len; std::vector<char> known;
     std::mutex mu; std::condition_variable cv;
     uint64_t total = 0;
@@ -2380,6 +2559,15 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
                 fin_read_summary* const dst = ts->rsum + (s.lo - ts->read0);
                 if (rc == FIN_OK) rc = fin_batch_download_read_summaries(b, dst, e, sizeof e);
                 if (rc == FIN_OK) for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_found;
+            } else
+            if (rc == FIN_OK && ts && ts->tally) {
+                rc = fin_batch_add_classes(b, ts->tally, ts->cls_min_found, ts->cls_min_permille, ts->cls_min_margin, (void*)b->own_stream, e, sizeof e);
+            } else
+            if (rc == FIN_OK && ts && ts->cls) {
+                rc = fin_batch_classify(b, ts->labels, e, sizeof e);
+                fin_read_class* const dst = ts->cls + (s.lo - ts->read0);
+                if (rc == FIN_OK) rc = fin_batch_download_read_classes(b, dst, e, sizeof e);
+                if (rc == FIN_OK) for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_labelled;
             } else
             if (rc == FIN_OK && ts && ts->screen) {
                 uint64_t np = 0;
@@ -2589,6 +2777,56 @@ int fin_search_batch_screen(const fin_index* idx, const char* bases, const uint6
     const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
     if (rc == FIN_OK && n_pass) *n_pass = ts.scr_pass.load();
     return rc;
+}
+
+int fin_search_batch_classify(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_labels* l,
+                              fin_read_class* out, uint64_t* n_positive, char* err, size_t errlen) {
+    if (!idx || !offsets || !l || (n_reads && !out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (l->idx != idx) { set_err(err, errlen, "the labelling belongs to another index"); return FIN_EINVAL; }
+    if (n_positive) *n_positive = 0;
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.labels = l; ts.cls = out; ts.read0 = 0;
+    uint64_t pos = 0;
+    const int rc = search_range_on(idx, l->device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
+    if (rc == FIN_OK && n_positive) *n_positive = pos;
+    return rc;
+}
+
+int fin_search_batch_add_classes(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_labels* l, uint32_t min_found,
+                                 uint32_t min_permille, uint32_t min_margin, char* err, size_t errlen) {
+    if (!idx || !offsets || !l || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (l->idx != idx) { set_err(err, errlen, "the labelling belongs to another index"); return FIN_EINVAL; }
+    if (min_permille > 1000u) { set_err(err, errlen, "min_permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.tally = l; ts.cls_min_found = min_found; ts.cls_min_permille = min_permille; ts.cls_min_margin = min_margin;
+    return search_range_on(idx, l->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+}
+
+// the index's numbers of the caller's unitigs: each one's first k-mer, searched forward, must come back as (u, 0)
+int fin_index_unitig_numbers(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint32_t* out, char* err, size_t errlen) {
+    if (!idx || !offsets || (n_seqs && (!bases || !out))) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    const uint64_t k = idx->k;
+    for (uint64_t i = 0; i < n_seqs; i++)
+        if (offsets[i + 1] - offsets[i] < k) { set_err(err, errlen, "sequence " + std::to_string(i) + " is shorter than k = " + std::to_string(k) + ": not a unitig of this index"); return FIN_EINVAL; }
+    if (n_seqs == 0) return FIN_OK;
+    std::string firsts((size_t)(n_seqs * k), 'A');
+    std::vector<uint64_t> offs((size_t)n_seqs + 1);
+    for (uint64_t i = 0; i < n_seqs; i++) { memcpy(&firsts[(size_t)(i * k)], bases + offsets[i], (size_t)k); offs[(size_t)i] = i * k; }
+    offs[(size_t)n_seqs] = n_seqs * k;
+    std::vector<int32_t> pairs((size_t)n_seqs * 2);
+    const int rc = fin_search_batch(idx, firsts.data(), offs.data(), n_seqs, FIN_FWD, pairs.data(), nullptr, err, errlen);
+    if (rc != FIN_OK) return rc;
+    for (uint64_t i = 0; i < n_seqs; i++) {
+        const int32_t u = pairs[(size_t)(2 * i)], off = pairs[(size_t)(2 * i + 1)];
+        if (u < 0) { set_err(err, errlen, "sequence " + std::to_string(i) + ": its first k-mer is not in the index -- not a unitig of this index"); return FIN_EINVAL; }
+        if (off != 0) {
+            set_err(err, errlen, "sequence " + std::to_string(i) + ": its first k-mer is at offset " + std::to_string(off) + " of unitig " + std::to_string(u) + ", not at the start of a unitig");
+            return FIN_EINVAL;
+        }
+        out[i] = (uint32_t)u;
+    }
+    return FIN_OK;
 }
 
 int fin_search_batch_add_hits(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_hits* h, char* err, size_t errlen) {

@@ -162,6 +162,13 @@ int fin_launch_read_summaries(const void* frec, const uint64_t* out_offs, const 
 int fin_launch_screen_bits(const void* sum, const uint64_t* out_offs, uint32_t n_reads, uint32_t min_found, uint32_t min_permille, int invert, uint64_t* bits,
                            uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total, hipStream_t stream);
 int fin_launch_screen_ids(const uint64_t* bits, const uint64_t* blk_off, uint32_t n_reads, uint32_t* ids, hipStream_t stream);
+// fin_classify.hip: a finished step's results as one class {label, n_best, n_second, n_labelled} of 16 bytes per read (cls[n_reads]) under labels[n_unitigs]
+// (uint32 each, 0xFFFFFFFF: no label).  frec / out_offs / pairs as fin_launch_hits_add; a unitig number at or above n_unitigs has no label.
+// fin_launch_class_tally: reads[label] += 1 for every read the rule assigns, reads[n_labels] += 1 for every other one (uint64[n_labels + 1])
+int fin_launch_classify(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const uint32_t* labels, uint32_t n_unitigs,
+                        void* cls, hipStream_t stream);
+int fin_launch_class_tally(const void* cls, const uint64_t* out_offs, uint32_t n_reads, uint32_t n_labels, uint32_t min_found, uint32_t min_permille,
+                           uint32_t min_margin, uint64_t* reads, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -476,8 +476,22 @@ static const char* SEARCH_HELP =
     "      --min-found N     the N of --screen (default: 1)\n"
     "      --min-permille P  the P of --screen, 0 to 1000 (default: 0)\n"
     "      --screen-invert arg  1: write the reads that do NOT pass (default: 0)\n"
-    "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary or --screen): do not make or\n"
-    "                        write the pair text, the other results asked for are the only ones\n"
+    "      --label-unitigs FASTA  the unitigs the index was built from, in the order --labels speaks of (needed by --classify and --label-report)\n"
+    "      --labels FILE     one line per record of --label-unitigs, in its order: the unitig's label, a non-negative integer, or `-` for none (k-mers\n"
+    "                        found in such a unitig vote for no label)\n"
+    "      --classify FILE   also write one line per read, in input order: `read<TAB>k-mers<TAB>label<TAB>best<TAB>second<TAB>labelled` -- `read` and k-mers\n"
+    "                        as in --read-summary, label = the label most of the read's found k-mers carry (ties: the smaller one; `-` if none is labelled),\n"
+    "                        best = how many carry it, second = how many carry the runner-up, labelled = how many carry any label. Made on the first GPU\n"
+    "                        from one more search of every chunk, 16 bytes per read come back; goes with everything --read-summary goes with. Not for a\n"
+    "                        partitioned index.\n"
+    "      --label-report FILE  also write `label<TAB>reads` per label, then `unassigned<TAB>reads`: a read is assigned to its label when best >= max(N, 1),\n"
+    "                        1000 * best >= P * k-mers and best >= second + M. Tallied on the first GPU from one more search of every chunk, nothing per\n"
+    "                        read comes back; goes with everything --read-summary goes with. Not for a partitioned index.\n"
+    "      --class-min-found N     the N of --label-report (default: 1)\n"
+    "      --class-min-permille P  the P of --label-report, 0 to 1000 (default: 0)\n"
+    "      --class-min-margin M    the M of --label-report (default: 0; 1 leaves ties unassigned)\n"
+    "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify or\n"
+    "                        --label-report): do not make or write the pair text, the other results asked for are the only ones\n"
     "  -h, --help            Print usage\n";
 
 static int build_fmin(int argc, char** argv) {
@@ -726,6 +740,72 @@ static void screen_chunk(const FinimizerIndex& index, const char* bases, const u
     if (!t.empty() && fwrite(t.data(), 1, t.size(), g_scr_file) != t.size()) throw runtime_error("Error writing the screen file");
     g_scr_read0 += n_reads;
 }
+// --classify FILE: every chunk's per-read classes under the labelling of --label-unitigs / --labels are made on the first device (fin_search_batch_classify) and
+// written as lines, by the search stage, in chunk order.  --label-report FILE: every chunk's reads are tallied on the device (fin_search_batch_add_classes)
+static fin_labels* g_labels = nullptr;
+static FILE* g_cls_file = nullptr;
+static bool g_cls_report = false;
+static uint64_t g_cls_read0 = 0;
+static uint32_t g_cls_min_found = 1, g_cls_min_permille = 0, g_cls_min_margin = 0;
+static vector<fin_read_class> g_cls; static string g_cls_text;
+static void classify_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads, const uint64_t* pair_off) {
+    char err[512] = {0};
+    if (g_cls_file) {
+        g_cls.resize(n_reads + 1);
+        if (fin_search_batch_classify(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_labels, g_cls.data(), nullptr, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        string& t = g_cls_text;
+        t.clear();
+        for (uint64_t r = 0; r < n_reads; r++) {
+            const fin_read_class& S = g_cls[r];
+            t += to_string(g_cls_read0 + r); t += '\t'; t += to_string(pair_off[r + 1] - pair_off[r]); t += '\t';
+            if (S.label == FIN_NO_LABEL) t += '-'; else t += to_string(S.label);
+            t += '\t'; t += to_string(S.n_best); t += '\t'; t += to_string(S.n_second); t += '\t'; t += to_string(S.n_labelled); t += '\n';
+        }
+        if (!t.empty() && fwrite(t.data(), 1, t.size(), g_cls_file) != t.size()) throw runtime_error("Error writing the classification file");
+    }
+    if (g_cls_report && fin_search_batch_add_classes(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_labels, g_cls_min_found, g_cls_min_permille, g_cls_min_margin,
+                                                     err, sizeof err) != FIN_OK)
+        throw runtime_error(err);
+    g_cls_read0 += n_reads;
+}
+// the labelling of --label-unitigs FASTA --labels FILE, in the index's unitig numbers (fin_index_unitig_numbers); *n_labels = the largest label + 1
+static vector<uint32_t> load_labelling(const FinimizerIndex& index, const string& fasta, const string& file, uint32_t* n_labels) {
+    string bases; vector<uint64_t> offsets{0};
+    {
+        SeqReader reader(fasta);
+        while (reader.get_next_read_to_buffer() > 0) { bases += reader.read_buf; offsets.push_back(bases.size()); }
+    }
+    const size_t n = offsets.size() - 1;
+    ifstream in(file);
+    if (!in) throw runtime_error("Could not open the labels file " + file);
+    vector<uint32_t> given;
+    string line;
+    uint64_t top = 0;
+    while (getline(in, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        const string where = file + " line " + to_string(given.size() + 1);
+        if (given.size() == n) throw runtime_error(where + ": more lines than " + fasta + " has records (" + to_string(n) + ")");
+        if (line == "-") { given.push_back(FIN_NO_LABEL); continue; }
+        size_t used = 0; unsigned long long v = 0;
+        try { v = stoull(line, &used); } catch (...) { used = 0; }
+        if (line.empty() || used != line.size() || !isdigit((unsigned char)line[0]) || v >= 0x80000000ull)
+            throw runtime_error(where + ": `" + line + "` is neither a label (a number from 0 to 2147483647) nor `-`");
+        given.push_back((uint32_t)v);
+        if (v + 1 > top) top = v + 1;
+    }
+    if (given.size() != n) throw runtime_error(file + " ends after line " + to_string(given.size()) + ": " + fasta + " has " + to_string(n) + " records, each needs a line");
+    const size_t nu = (size_t)index.number_of_unitigs();
+    vector<uint32_t> number(n + 1), labels(nu + 1, FIN_NO_LABEL);
+    vector<char> seen(nu + 1, 0);
+    char err[512] = {0};
+    if (fin_index_unitig_numbers(index.handle(), bases.data(), offsets.data(), n, number.data(), err, sizeof err) != FIN_OK) throw runtime_error(fasta + ": " + err);
+    for (size_t i = 0; i < n; i++) {
+        if (seen[number[i]]) throw runtime_error(fasta + ": record " + to_string(i) + " is a unitig an earlier record already named");
+        seen[number[i]] = 1; labels[number[i]] = given[i];
+    }
+    *n_labels = (uint32_t)(top ? top : 1);
+    return labels;
+}
 static bool g_no_text = false;
 static uint64_t g_hits_total = 0;   // the accumulator's sum after the previous query file
 
@@ -808,6 +888,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_seg_file) c->positive = segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                         if (g_rs_file) c->positive = read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                     }
                     else {
                         // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
@@ -827,6 +908,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_seg_file) (void)segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                         if (g_rs_file) (void)read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                     }
                     if (g_strand_counts) {
                         c->positive_fwd = index.count_found_one_strand(c->bases.get(0), c->offsets.data(), n_reads);
@@ -942,12 +1024,16 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen"))
-        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary or --screen (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report"))
+        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify or --label-report (the run would have no result)");
+    if ((o.has("classify") || o.has("label-report")) && !(o.has("label-unitigs") && o.has("labels"))) throw runtime_error("--classify and --label-report want a labelling: --label-unitigs FASTA --labels FILE");
+    if ((o.has("label-unitigs") || o.has("labels")) && !o.has("classify") && !o.has("label-report")) throw runtime_error("--label-unitigs and --labels are only legal together with --classify or --label-report");
+    for (const char* name : {"class-min-found", "class-min-permille", "class-min-margin"})
+        if (o.has(name) && !o.has("label-report")) throw runtime_error(string("--") + name + " is only legal together with --label-report");
     for (const char* name : {"min-found", "min-permille", "screen-invert"})
         if (o.has(name) && !o.has("screen")) throw runtime_error(string("--") + name + " is only legal together with --screen");
     auto u32_option = [&](const char* name, unsigned long long dflt, unsigned long long top) {
@@ -960,6 +1046,9 @@ static int search_fmin(int argc, char** argv) {
     };
     g_scr_min_found = u32_option("min-found", 1, 0xFFFFFFFFull);
     g_scr_min_permille = u32_option("min-permille", 0, 1000);
+    g_cls_min_found = u32_option("class-min-found", 1, 0xFFFFFFFFull);
+    g_cls_min_permille = u32_option("class-min-permille", 0, 1000);
+    g_cls_min_margin = u32_option("class-min-margin", 0, 0xFFFFFFFFull);
     g_scr_invert = o.has("screen-invert") && o.get("screen-invert") != "0" && o.get("screen-invert") != "false" ? 1 : 0;
     if (o.has("min-depth") && !o.has("unitig-depth")) throw runtime_error("--min-depth is only legal together with --unitig-depth");
     uint32_t min_depth = 1;
@@ -1000,6 +1089,9 @@ static int search_fmin(int argc, char** argv) {
     if (!rs_file.empty()) check_writable(rs_file);
     const string scr_file = o.get("screen", "");
     if (!scr_file.empty()) check_writable(scr_file);
+    const string cls_file = o.get("classify", ""), report_file = o.get("label-report", "");
+    if (!cls_file.empty()) check_writable(cls_file);
+    if (!report_file.empty()) check_writable(report_file);
     cerr << "Loading index..." << endl;
     const int first_dev = stoi(o.get("device", "0"));
     // beside the index load: page-lock the pipeline's buffers (four chunks of 48 MB of bases and of up to 16 bytes of text per k-mer)
@@ -1041,6 +1133,8 @@ static int search_fmin(int argc, char** argv) {
     if (!seg_file.empty() && index.partitioned()) throw runtime_error("--segments is not available with a partitioned index");
     if (!rs_file.empty() && index.partitioned()) throw runtime_error("--read-summary is not available with a partitioned index");
     if (!scr_file.empty() && index.partitioned()) throw runtime_error("--screen is not available with a partitioned index");
+    if (!cls_file.empty() && index.partitioned()) throw runtime_error("--classify is not available with a partitioned index");
+    if (!report_file.empty() && index.partitioned()) throw runtime_error("--label-report is not available with a partitioned index");
     index.to_device();
     struct HitsOwner { ~HitsOwner() { fin_hits_free(g_hits); g_hits = nullptr; } } hits_owner;
     if (!counts_file.empty() || (g_no_text && seg_file.empty() && rs_file.empty())) {   // (with --segments the found k-mers are the sum of the segments' lengths, with --read-summary the sum of `found`)
@@ -1073,6 +1167,19 @@ static int search_fmin(int argc, char** argv) {
         g_scr_file = fopen(scr_file.c_str(), "wb");
         if (!g_scr_file) throw runtime_error("Error writing to file: " + scr_file);
         g_scr_read0 = 0;
+    }
+    struct ClassOwner { ~ClassOwner() { if (g_cls_file) fclose(g_cls_file); g_cls_file = nullptr; fin_labels_free(g_labels); g_labels = nullptr; } } class_owner;
+    uint32_t n_labels = 0;
+    if (!cls_file.empty() || !report_file.empty()) {
+        const vector<uint32_t> labels = load_labelling(index, o.get("label-unitigs"), o.get("labels"), &n_labels);
+        char err[512] = {0};
+        if (fin_labels_create(index.handle(), first_dev, labels.data(), n_labels, &g_labels, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        g_cls_report = !report_file.empty();
+        g_cls_read0 = 0;
+        if (!cls_file.empty()) {
+            g_cls_file = fopen(cls_file.c_str(), "wb");
+            if (!g_cls_file) throw runtime_error("Error writing to file: " + cls_file);
+        }
     }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
@@ -1108,6 +1215,22 @@ static int search_fmin(int argc, char** argv) {
         const bool bad = fflush(g_scr_file) != 0 || ferror(g_scr_file);
         fclose(g_scr_file); g_scr_file = nullptr;
         if (bad) throw runtime_error("Error writing to file: " + scr_file);
+    }
+    if (g_cls_file) {
+        const bool bad = fflush(g_cls_file) != 0 || ferror(g_cls_file);
+        fclose(g_cls_file); g_cls_file = nullptr;
+        if (bad) throw runtime_error("Error writing to file: " + cls_file);
+    }
+    if (g_labels && g_cls_report) {   // the tally, after the last chunk: one line per label, then the unassigned reads
+        char err[512] = {0};
+        vector<uint64_t> reads((size_t)n_labels + 1);
+        if (fin_labels_download(g_labels, reads.data(), nullptr, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        string text;
+        for (size_t l = 0; l < n_labels; l++) { text += to_string(l); text += '\t'; text += to_string(reads[l]); text += '\n'; }
+        text += "unassigned\t"; text += to_string(reads[n_labels]); text += '\n';
+        ofstream cf(report_file, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + report_file);
     }
     if (g_cover) {   // the coverage, after the last chunk: one line per unitig of the index
         char err[512] = {0};

@@ -442,7 +442,7 @@ int fin_batch_download_records(fin_batch* b, fin_read_record* recs_out, int32_t*
  * fin_batch_records), the sibling of fin_batch_set_pairs: overwrite the records the batch's most recent run left with recs[n_reads] and, when pairs != NULL, its
  * pairs with pairs[2 * n_kmers].  Legal only after a run that left records (kernel 4, merged strands, fast path on, text mode 1 or 2): FIN_EINVAL otherwise.
  * Waits for that run, copies, launches no kernel.  The batch stays what the run made it -- after a text-mode-2 run fin_batch_download still refuses the pairs --
- * and forgets what it made from the old records: segments, read summaries and the screen, the gathered stream, the formatted text and the count taken from it.
+ * and forgets what it made from the old records: segments, read summaries and the screen, read classes, the gathered stream, the formatted text and the count taken from it.
  * The kernels trust a record's fields, so they are checked on the host before anything is copied; FIN_EINVAL with a message unless, for every read,
  *  - kind = meta >> 16 is 0, 1 or 2;
  *  - kind 1 or 2: nk is the read's own number of k-mers, max(0, length - k + 1), and at least 1;
@@ -669,6 +669,66 @@ int fin_search_batch_screen(const fin_index* idx, const char* bases, const uint6
  * that is neither found nor (-1,-1) */
 int fin_records_read_summaries(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, fin_read_summary* out,
                                int n_threads);
+
+/* ---- read CLASSIFICATION by unitig labels, made on the device ----
+ * What a user of (unitig, offset) does next is look the unitig up in a table of their own -- which genome, species, plasmid, contig bin or colour it belongs to --
+ * and decide per read.  A LABELLING is that table: one uint32 per unitig of the index, in the index's own unitig numbers (the ones the pairs carry): a label in
+ * [0, n_labels), or FIN_NO_LABEL for an unlabelled or shared unitig -- k-mers found there vote for nobody.  For a read with output slots 0 .. nk - 1, every found
+ * slot whose unitig u has labels[u] != FIN_NO_LABEL counts c[labels[u]] += 1, and the read's class is
+ *   n_labelled  the sum of c;
+ *   label       argmax c, ties to the SMALLER label;
+ *   n_best      c[label];
+ *   n_second    the largest c[L] over L != label, 0 if there is none;
+ * or {FIN_NO_LABEL, 0, 0, 0} when no found slot is labelled.  The class is exact for every read, however many distinct labels it touches, and invariant under
+ * reversing the slot order: a read found on its reverse strand (a kind-1 record with meta bit 8) needs no special case.  16 bytes per read come back, or one
+ * uint64 per label for a whole run (the tally: an abundance report in reads).
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, several labels per unitig (colour sets), and labelling
+ * unitigs by searching reference genomes (fin_index_unitig_numbers below maps the caller's unitig order to the index's numbers; the labels are the caller's). */
+#define FIN_NO_LABEL 0xFFFFFFFFu
+typedef struct fin_read_class { uint32_t label, n_best, n_second, n_labelled; } fin_read_class;   /* 16 bytes */
+typedef struct fin_labels fin_labels;
+/* a labelling beside the replica on `device`, with its zeroed tally: unitig_labels[fin_index_n_unitigs], copied.  FIN_EINVAL: n_labels is 0 or above 2^31, or a
+ * label >= n_labels that is not FIN_NO_LABEL (the message names the unitig).  FIN_ENODEV: no replica on that device. */
+int fin_labels_create(const fin_index* idx, int device, const uint32_t* unitig_labels, uint32_t n_labels, fin_labels** out, char* err, size_t errlen);
+int fin_labels_reset(fin_labels* l, void* hip_stream);   /* zeroes the tally only (asynchronous on hip_stream); the labelling stays */
+void* fin_labels_device_labels(const fin_labels* l);     /* uint32[fin_index_n_unitigs] in HBM */
+void* fin_labels_device_reads(const fin_labels* l);      /* the tally, uint64[n_labels + 1] in HBM (valid once the adds on their streams have finished) */
+/* waits for every add and reset issued so far; reads_out[n_labels + 1] (may be NULL): the reads assigned to each label, then the unassigned ones; *total (may be
+ * NULL) = their sum = the reads added */
+int fin_labels_download(fin_labels* l, uint64_t* reads_out, uint64_t* total, char* err, size_t errlen);
+void fin_labels_free(fin_labels* l);
+/* Behind the batch's most recent run, on that run's stream and ordered behind the run (fin_classify.hip): one kernel, a lane per read; a read the fast path
+ * finished (text modes 1 and 2) lies in one unitig and is classified from its 32-byte record and one label -- in mode 2 its pairs do not exist --, every other
+ * read's pairs are scanned in place.  The classes stay in HBM, in a buffer the batch keeps and only grows; a second call with the same labelling gives the same
+ * answer, a call with another labelling replaces them.  Read-only on records, pairs, text, segments, summaries and screen.  Works in every text mode, for
+ * FIN_MERGED and FIN_FWD, for every k; empty batches and batches of reads without k-mers are legal.  fin_batch_run, fin_batch_reload, fin_batch_set_records and
+ * fin_batch_set_pairs forget the classes.
+ * FIN_EINVAL: the batch has not run, or the labelling belongs to another index or device.  FIN_ELIMIT: the run's overflow list overran -- it has no results. */
+int fin_batch_classify(fin_batch* b, const fin_labels* l, char* err, size_t errlen);
+void* fin_batch_device_read_classes(const fin_batch* b);   /* fin_read_class[n_reads] in HBM; NULL before fin_batch_classify */
+int fin_batch_download_read_classes(fin_batch* b, fin_read_class* out, char* err, size_t errlen);   /* out[n_reads] */
+/* The tally: read r is ASSIGNED to its class's label when n_best >= max(min_found, 1), 1000 * n_best >= min_permille * nk and n_best >= n_second + min_margin,
+ * in 64-bit arithmetic, nk = the read's number of output slots; reads[label] += 1 then, reads[n_labels] += 1 otherwise -- the tally's sum is the number of reads
+ * added.  min_margin = 1 leaves ties unassigned.  Makes the classes if they are not there for this labelling; the add runs on hip_stream, ordered behind the run,
+ * as fin_batch_add_hits does; adding twice counts twice.  min_permille is 0 .. 1000, else FIN_EINVAL. */
+int fin_batch_add_classes(fin_batch* b, fin_labels* l, uint32_t min_found, uint32_t min_permille, uint32_t min_margin, void* hip_stream, char* err, size_t errlen);
+/* host buffers in: fin_search_batch's pipeline over sub-batches, each run in text mode 2 where the fast path is on (as fin_search_batch_read_summaries does) and
+ * classified / tallied on the device behind its run, on the labelling's device.  out[n_reads]; *n_positive (may be NULL) = the labelled k-mers found (the sum of
+ * n_labelled).  Reads shorter than k and an empty read set are legal. */
+int fin_search_batch_classify(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_labels* l,
+                              fin_read_class* out, uint64_t* n_positive, char* err, size_t errlen);
+int fin_search_batch_add_classes(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_labels* l, uint32_t min_found,
+                                 uint32_t min_permille, uint32_t min_margin, char* err, size_t errlen);
+/* host, no device: the same classes from records + stream, without making the pairs -- the CPU statement of what the kernel does (the sibling of
+ * fin_records_read_summaries).  unitig_labels[n_unitigs]; out[n_reads]; n_threads <= 0: all cores.  FIN_EINVAL: a unitig number >= n_unitigs, a stream that is not
+ * this record set's, or a stream pair that is neither found nor (-1,-1) */
+int fin_records_read_classes(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k,
+                             const uint32_t* unitig_labels, uint64_t n_unitigs, fin_read_class* out, int n_threads);
+/* what makes a labelling writable at all: the index renumbers the unitigs it is built from and keeps no input order.  For each of n_seqs unitig sequences
+ * (bases + offsets, as a read set) the first k-mer is searched (forward strand, the index must be on a device) and out[i] = the unitig of the pair it gives,
+ * whose offset must be 0.  FIN_EINVAL, with a message that names the sequence, for one shorter than k, one that is not a unitig of this index, or one whose first
+ * k-mer the index reports elsewhere (a unitig set that is not disjoint). */
+int fin_index_unitig_numbers(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint32_t* out, char* err, size_t errlen);
 
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
