@@ -225,6 +225,28 @@ def lib():
         L.fin_search_batch_add_classes.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, u32, cp, C.c_size_t]
         L.fin_records_read_classes.argtypes = [vp, u64, vp, u64, C.c_int, vp, u64, vp, C.c_int]
         L.fin_index_unitig_numbers.argtypes = [vp, cp, u64p, u64, vp, cp, C.c_size_t]
+        L.fin_colors_create.argtypes = [vp, C.c_int, u32, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_colors_upload.argtypes = [vp, u64p, cp, C.c_size_t]
+        L.fin_colors_reset.argtypes = [vp, vp]
+        L.fin_colors_device_bits.argtypes = [vp]
+        L.fin_colors_device_bits.restype = vp
+        L.fin_colors_n_colors.argtypes = [vp]
+        L.fin_colors_n_colors.restype = u32
+        L.fin_colors_words.argtypes = [vp]
+        L.fin_colors_words.restype = u32
+        L.fin_colors_download.argtypes = [vp, u64p, u64p, cp, C.c_size_t]
+        L.fin_colors_free.argtypes = [vp]
+        L.fin_colors_free.restype = None
+        L.fin_batch_add_colors.argtypes = [vp, vp, u32, vp, cp, C.c_size_t]
+        L.fin_search_batch_add_colors.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, cp, C.c_size_t]
+        L.fin_batch_pseudoalign.argtypes = [vp, vp, u32, cp, C.c_size_t]
+        L.fin_batch_device_pseudo_rows.argtypes = [vp]
+        L.fin_batch_device_pseudo_rows.restype = vp
+        L.fin_batch_device_pseudo_heads.argtypes = [vp]
+        L.fin_batch_device_pseudo_heads.restype = vp
+        L.fin_batch_download_pseudo.argtypes = [vp, u64p, vp, cp, C.c_size_t]
+        L.fin_search_batch_pseudoalign.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u64p, vp, u64p, cp, C.c_size_t]
+        L.fin_records_pseudoalign.argtypes = [vp, u64, vp, u64, C.c_int, u64p, u64, u32, u32, u64p, vp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -453,6 +475,21 @@ class Batch:
         """the classes' device pointer, 0 before classify() / Labels.add()"""
         return int(self.L.fin_batch_device_read_classes(self.h) or 0)
 
+    def pseudoalign(self, colors, permille=1000):
+        """the most recent run's results as one colour row per read under a colour matrix (Colors), made on the device (fin_batch_pseudoalign +
+        fin_batch_download_pseudo): (rows uint64[n_reads, W], heads READ_PSEUDO_DTYPE[n_reads]) -- colour c is in a read's row iff at least permille thousandths
+        of its coloured k-mers have it; 1000: the intersection, 0: the union"""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_pseudoalign(self.h, colors.h, _permille("Batch.pseudoalign", permille), err, 512), err)
+        rows = np.zeros((max(self.n_reads, 1), colors.words), dtype=np.uint64)
+        heads = np.zeros(max(self.n_reads, 1), dtype=READ_PSEUDO_DTYPE)
+        _check(self.L.fin_batch_download_pseudo(self.h, rows.ctypes.data_as(C.POINTER(C.c_uint64)), heads.ctypes.data_as(C.c_void_p), err, 512), err)
+        return rows[: self.n_reads], heads[: self.n_reads]
+
+    def device_pseudo_ptrs(self):
+        """(rows, heads) device pointers, 0 before pseudoalign()"""
+        return int(self.L.fin_batch_device_pseudo_rows(self.h) or 0), int(self.L.fin_batch_device_pseudo_heads(self.h) or 0)
+
     def pipeline_counts(self, n=64):
         """kernel 4's queue counters of the last run (fin_batch_pipeline_counts)"""
         out = (C.c_uint32 * n)()
@@ -630,6 +667,91 @@ class Labels:
     def close(self):
         if getattr(self, "h", None):
             self.L.fin_labels_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _permille(what, permille):
+    if not 0 <= int(permille) <= 0xFFFFFFFF:
+        raise FinitoError(FIN_EINVAL, what + ": permille is an unsigned 32-bit number")
+    return int(permille)
+
+
+class Colors:
+    """the colour set of every unitig of the index -- which of n_colors references it occurs in -- as a bit matrix uint64[n_unitigs, W], W = ceil(n_colors / 64),
+    resident in HBM beside one replica (fin_colors_* of the C ABI): colour c of unitig u is bit c & 63 of bits[u, c >> 6].  1 <= n_colors <= 4096.  Unitig numbers
+    are the index's own."""
+
+    def __init__(self, index, n_colors, device=0):
+        self.index = index
+        self.L = lib()
+        self.n_unitigs = index.n_unitigs
+        if not 0 <= int(n_colors) <= 0xFFFFFFFF:
+            raise FinitoError(FIN_ELIMIT, "colors: n_colors is 1 .. 4096")
+        self.n_colors = int(n_colors)
+        self.words = (self.n_colors + 63) // 64
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_create(index.h, int(device), self.n_colors, C.byref(h), err, 512), err)
+        self.h = h
+
+    def upload(self, bits):
+        """replace the matrix: uint64[n_unitigs, W]; a set bit at or above n_colors is refused (fin_colors_upload)"""
+        a = np.asarray(bits)
+        if a.shape != (self.n_unitigs, self.words) or a.dtype.kind not in "iu":
+            raise FinitoError(FIN_EINVAL, "colors: a matrix of shape (%d, %d), got %s" % (self.n_unitigs, self.words, a.shape))
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_upload(self.h, a.ctypes.data_as(C.POINTER(C.c_uint64)), err, 512), err)
+        return self
+
+    def add(self, batch, color, stream=None):
+        """every unitig in which the batch's most recent run found a k-mer gets `color`, on a HIP stream, behind that run; no sync (fin_batch_add_colors).
+        Adding twice changes nothing."""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_add_colors(batch.h, self.h, self._color(color), C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add_reads(self, reads, color, strands=FIN_MERGED):
+        """search a sequence set (a reference genome's) from host buffers, sub-batches pipelined as in search_reads, and give `color` to every unitig it is
+        found in; nothing comes back (fin_search_batch_add_colors)"""
+        bases, offsets = flatten(reads)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_add_colors(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+                                                  int(strands), self.h, self._color(color), err, 512), err)
+        return self
+
+    def _color(self, color):
+        if not 0 <= int(color) < self.n_colors:
+            raise FinitoError(FIN_EINVAL, "colors: colour %r is not in 0 .. %d" % (color, self.n_colors - 1))
+        return int(color)
+
+    def reset(self, stream=None):
+        """zero the matrix"""
+        rc = self.L.fin_colors_reset(self.h, C.c_void_p(stream or 0))
+        if rc != 0:
+            raise FinitoError(rc, "fin_colors_reset")
+        return self
+
+    def download(self):
+        """(uint64 bits[n_unitigs, W], the number of set bits); waits for the adds (fin_colors_download)"""
+        out = np.zeros((max(self.n_unitigs, 1), self.words), dtype=np.uint64)
+        n = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_download(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n), err, 512), err)
+        return out[: self.n_unitigs], int(n.value)
+
+    def device_ptr(self):
+        return int(self.L.fin_colors_device_bits(self.h) or 0)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fin_colors_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -1092,6 +1214,25 @@ class FinimizerIndex:
                                                 out.ctypes.data_as(C.c_void_p), None, err, 512), err)
         return out[:n]
 
+    def colors(self, n_colors, bits=None, device=0):
+        """a colour matrix of this index on `device` (Colors), zeroed or holding `bits`"""
+        c = Colors(self, n_colors, device)
+        return c if bits is None else c.upload(bits)
+
+    def pseudoalign_reads(self, reads, colors, permille=1000, strands=FIN_MERGED, want_rows=True):
+        """(rows uint64[n_reads, W] or None, heads READ_PSEUDO_DTYPE[n_reads], the coloured k-mers found): a read set pseudoaligned from host buffers, sub-batches
+        pipelined (fin_search_batch_pseudoalign)"""
+        bases, offsets = flatten(reads)
+        n = len(offsets) - 1
+        rows = np.zeros((max(n, 1), colors.words), dtype=np.uint64) if want_rows else None
+        heads = np.zeros(max(n, 1), dtype=READ_PSEUDO_DTYPE)
+        npos = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_pseudoalign(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands), colors.h,
+                                                   _permille("pseudoalign_reads", permille), rows.ctypes.data_as(C.POINTER(C.c_uint64)) if want_rows else None,
+                                                   heads.ctypes.data_as(C.c_void_p), C.byref(npos), err, 512), err)
+        return (rows[:n] if want_rows else None), heads[:n], int(npos.value)
+
     def unitig_numbers(self, unitigs):
         """fin_index_unitig_numbers: uint32[len(unitigs)] -- the index's number of each given unitig sequence (the index renumbers its input); raises for a
         sequence that is not a unitig of this index"""
@@ -1196,6 +1337,8 @@ SEGMENT_DTYPE = np.dtype([("u", np.int32), ("off", np.int32), ("slot", np.uint32
 READ_SUMMARY_DTYPE = np.dtype([("n_found", np.uint32), ("n_segments", np.uint32), ("longest", np.uint32), ("span", np.uint32)])   # fin_read_summary
 READ_CLASS_DTYPE = np.dtype([("label", np.uint32), ("n_best", np.uint32), ("n_second", np.uint32), ("n_labelled", np.uint32)])   # fin_read_class
 FIN_NO_LABEL = 0xFFFFFFFF
+READ_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), ("n_colors", np.uint32), ("reserved", np.uint32)])   # fin_read_pseudo
+FIN_MAX_COLORS = 4096
 DEPTH_STAT_DTYPE = np.dtype([("sum", np.uint64), ("max", np.uint32), ("n_at_least", np.uint32)])            # fin_depth_stat
 
 
@@ -1451,6 +1594,25 @@ def records_read_classes(recs, stream, k, unitig_labels, n_threads=0):
         raise FinitoError(rc, "fin_records_read_classes: a unitig number outside the labelling, records and stream that do not belong together, or a pair that is "
                               "neither found nor (-1,-1)")
     return out[: len(recs)]
+
+
+def records_pseudoalign(recs, stream, k, bits, n_colors, permille=1000, n_threads=0):
+    """host: (rows uint64[n_reads, W], heads READ_PSEUDO_DTYPE[n_reads]) from records + stream under the colour matrix bits[n_unitigs, W]
+    (fin_records_pseudoalign) -- the CPU statement of Batch.pseudoalign"""
+    r = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+    st = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1, 2)
+    W = (int(n_colors) + 63) // 64 if 0 <= int(n_colors) <= 0xFFFFFFFF else 0
+    b = np.ascontiguousarray(bits, dtype=np.uint64).reshape(-1, max(W, 1))
+    if not (0 <= int(n_colors) <= 0xFFFFFFFF and 0 <= int(permille) <= 0xFFFFFFFF):
+        raise FinitoError(FIN_EINVAL, "records_pseudoalign: n_colors and permille are unsigned 32-bit numbers")
+    rows = np.zeros((max(len(r), 1), max(W, 1)), dtype=np.uint64)
+    heads = np.zeros(max(len(r), 1), dtype=READ_PSEUDO_DTYPE)
+    rc = lib().fin_records_pseudoalign(r.ctypes.data_as(C.c_void_p), len(r), st.ctypes.data_as(C.c_void_p), len(st), int(k), b.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                       len(b), int(n_colors), int(permille), rows.ctypes.data_as(C.POINTER(C.c_uint64)), heads.ctypes.data_as(C.c_void_p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_pseudoalign: n_colors outside 1 .. 4096, permille above 1000, a bit at or above n_colors, a unitig number outside the "
+                              "matrix, or records and stream that do not belong together")
+    return rows[: len(r)], heads[: len(r)]
 
 
 def format_pairs(pairs):

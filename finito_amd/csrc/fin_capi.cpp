@@ -737,6 +737,8 @@ struct fin_batch {
     size_t cap_rsum = 0, cap_scr_bits = 0, cap_scr_ids = 0, cap_scr_bsum = 0, cap_scr_boff = 0; uint64_t n_pass = 0; bool rsum_ready = false, scr_ready = false;
     // per-read classes under a labelling (fin_batch_classify): kept and only grown; cls_labels = the serial number of the labelling they were made for
     void* d_cls = nullptr; size_t cap_cls = 0; bool cls_ready = false; uint64_t cls_labels = 0;
+    // per-read colour rows and heads under a colour matrix (fin_batch_pseudoalign): kept and only grown; psa_words = the matrix's words per row
+    void* d_psa_rows = nullptr; size_t cap_psa_rows = 0; void* d_psa_heads = nullptr; size_t cap_psa_heads = 0; bool psa_ready = false; uint32_t psa_words = 0;
     uint64_t text_bytes = 0;
     // kernel 4: the queue counters of the most recent finished run, copied to page-locked memory behind every run: the next run launches only
     // as many stream / walk rounds as that one needed, plus one (fin_launch_search_v4's `rounds`)
@@ -772,7 +774,7 @@ void fin_batch_free(fin_batch* b) {
     if (b->ev_ctr) (void)hipEventDestroy(b->ev_ctr);
     (void)hipFree(b->d_cstream); (void)hipFree(b->d_frec); (void)hipFree(b->d_seg); (void)hipFree(b->d_text); (void)hipFree(b->d_last_bits); (void)hipFree(b->d_blk_sum); (void)hipFree(b->d_blk_off); (void)hipFree(b->d_total);
     (void)hipFree(b->d_sgm_cnt); (void)hipFree(b->d_sgm_bsum); (void)hipFree(b->d_sgm_boff); (void)hipFree(b->d_sgm_offs); (void)hipFree(b->d_sgm);
-    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls);
+    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls); (void)hipFree(b->d_psa_rows); (void)hipFree(b->d_psa_heads);
     (void)hipFree(b->d_ovf_list); (void)hipFree(b->d_ovf_count); (void)hipFree(b->d_ovf_scratch); (void)hipFree(b->d_count);
     for (auto& r : b->runs) for (auto& e : r.e) (void)hipEventDestroy(e);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -896,7 +898,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     //  decoding, inside its timed region, search_fmin.hh:46-71 -- is the first kernel of every step, see fin_batch_run)
     b->n_chunks = n_chunks; b->max_read_len = max_len;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "upload");
-    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false;
+    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false;
     b->rounds_hint = 0; b->ctr_pending = false;   // (new reads: nothing is known about the rounds they need)
     b->text_reads_state = 0;
     return FIN_OK;
@@ -940,7 +942,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     b->dev.budget_mult = (uint32_t)optv(b->idx, O_epoch_budget_mult); b->dev.budget_add = (uint32_t)optv(b->idx, O_epoch_budget_add);
     b->dev.ovf_cap = (uint32_t)std::min<uint64_t>(b->cap_ovf_list / 4, 0xFFFFFFFFull);
     if (const int64_t forced = optv(b->idx, O_debug_ovf_cap)) b->dev.ovf_cap = (uint32_t)std::min<int64_t>(forced, (int64_t)b->dev.ovf_cap);   // (tests: a tiny list)
-    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false;
+    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false;
     b->dev.pp_seg = (uint32_t)optv(b->idx, O_debug_pp_seg);
     b->dev.pp_max_len = (uint32_t)std::min<uint64_t>(b->max_read_len, 0xFFFFFFFFull);
     b->dev.pp_park = (uint32_t)optv(b->idx, O_pp_park);
@@ -1066,7 +1068,7 @@ int fin_batch_set_pairs(fin_batch* b, const int32_t* pairs, char* err, size_t er
     HIPCHK(hipSetDevice(b->device));
     if (b->last_stream) HIPCHK(hipStreamSynchronize(b->last_stream));
     HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
-    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false;   // (the records of the last run say nothing about these pairs)
+    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false;   // (the records of the last run say nothing about these pairs)
     return FIN_OK;
 }
 
@@ -1107,7 +1109,7 @@ int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32
     if (b->n_reads) HIPCHK(hipMemcpy(b->d_frec, recs, (size_t)b->n_reads * sizeof(FinFastRec), hipMemcpyHostToDevice));
     if (pairs && b->n_kmers) HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
     // last_frec / last_text_only stay as the run left them (a text-only batch still refuses its pairs); whatever was made from the old records goes
-    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false;
+    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false;
     b->rec_ready = false; b->rec_passthrough = false; b->rec_stream_pairs = 0;
     return FIN_OK;
 }
@@ -1704,6 +1706,12 @@ struct AccPending {
         for (auto& p : pending) HIPCHK(hipEventSynchronize(p.second));
         return FIN_OK;
     }
+    // `st` waits for everything marked so far (a reader of the accumulator on another stream than its adds)
+    int order(hipStream_t st, char* err, size_t errlen) {
+        std::lock_guard<std::mutex> g(mu);
+        for (auto& p : pending) if (p.first != st) HIPCHK(hipStreamWaitEvent(st, p.second, 0));
+        return FIN_OK;
+    }
     void drop() { for (auto& p : pending) { (void)hipEventSynchronize(p.second); (void)hipEventDestroy(p.second); } pending.clear(); }
 };
 // behind the batch's most recent run, whichever stream it was launched on: what fin_batch_add_hits, fin_batch_add_cover and fin_batch_add_depth check and order alike
@@ -1956,6 +1964,203 @@ int fin_records_read_classes(const fin_read_record* recs, uint64_t n_reads, cons
                 i = j;
             }
             out[r] = C;
+        }
+        ok = good && ok;
+    }
+    return ok ? FIN_OK : FIN_EINVAL;
+}
+
+// ---- colour sets per unitig and read pseudoalignment (fin_colors.hip) -------------------------------------------------------------------
+static_assert(sizeof(fin_read_pseudo) == 16, "a pseudoalignment head is 16 bytes");
+struct fin_colors {
+    const fin_index* idx = nullptr;
+    int device = -1;
+    uint64_t n_unitigs = 0; uint32_t n_colors = 0, words = 0;
+    void* d_bits = nullptr;     // uint64[n_unitigs * words], then the flag word (fin_launch_colors_add)
+    AccPending pend;
+};
+static size_t colors_bytes(const fin_colors* c) { return (size_t)c->n_unitigs * c->words * 8; }
+static uint32_t* colors_flags(const fin_colors* c) { return (uint32_t*)((char*)c->d_bits + colors_bytes(c)); }
+// the first unitig with a bit at or above n_colors set, or n_unitigs
+static uint64_t colors_first_stray(const uint64_t* bits, uint64_t n_unitigs, uint32_t n_colors, uint32_t W) {
+    if ((n_colors & 63u) == 0u) return n_unitigs;   // (the last word is all colours)
+    const uint64_t stray = ~0ull << (n_colors & 63u);
+    for (uint64_t u = 0; u < n_unitigs; u++) if (bits[u * W + (W - 1)] & stray) return u;
+    return n_unitigs;
+}
+
+void fin_colors_free(fin_colors* c) {
+    if (!c) return;
+    if (c->device >= 0) (void)hipSetDevice(c->device);
+    c->pend.drop();
+    (void)hipFree(c->d_bits);
+    delete c;
+}
+
+int fin_colors_create(const fin_index* idx, int device, uint32_t n_colors, fin_colors** out, char* err, size_t errlen) {
+    if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (n_colors == 0 || n_colors > FIN_MAX_COLORS) { set_err(err, errlen, "n_colors is 1 .. " + std::to_string(FIN_MAX_COLORS)); return FIN_ELIMIT; }
+    if (!idx->replica_on(device)) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
+    HIPCHK(hipSetDevice(device));
+    fin_colors* c = new (std::nothrow) fin_colors();
+    if (!c) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
+    c->idx = idx; c->device = device; c->n_unitigs = idx->n_unitigs; c->n_colors = n_colors; c->words = (n_colors + 63u) / 64u;
+    if (hipMalloc(&c->d_bits, colors_bytes(c) + 8) != hipSuccess) { (void)hipGetLastError(); delete c; set_err(err, errlen, "out of device memory (colour matrix)"); return FIN_ENOMEM; }
+    if (hipMemset(c->d_bits, 0, colors_bytes(c) + 8) != hipSuccess) { fin_colors_free(c); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    *out = c;
+    return FIN_OK;
+}
+
+int fin_colors_upload(fin_colors* c, const uint64_t* bits, char* err, size_t errlen) {
+    if (!c || (c->n_unitigs && !bits)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    const uint64_t bad = colors_first_stray(bits, c->n_unitigs, c->n_colors, c->words);
+    if (bad != c->n_unitigs) { set_err(err, errlen, "unitig " + std::to_string(bad) + " has a bit at or above n_colors = " + std::to_string(c->n_colors) + " set"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int wrc = c->pend.wait(err, errlen)) return wrc;
+    if (c->n_unitigs) HIPCHK(hipMemcpy(c->d_bits, bits, colors_bytes(c), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(colors_flags(c), 0, 8));
+    return FIN_OK;
+}
+
+int fin_colors_reset(fin_colors* c, void* hip_stream) {
+    if (!c) return FIN_EINVAL;
+    if (hipSetDevice(c->device) != hipSuccess) return FIN_ENODEV;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (hipMemsetAsync(c->d_bits, 0, colors_bytes(c) + 8, st) != hipSuccess) return FIN_ENODEV;
+    return c->pend.mark(st, nullptr, 0);
+}
+
+void* fin_colors_device_bits(const fin_colors* c) { return c ? c->d_bits : nullptr; }
+uint32_t fin_colors_n_colors(const fin_colors* c) { return c ? c->n_colors : 0; }
+uint32_t fin_colors_words(const fin_colors* c) { return c ? c->words : 0; }
+
+int fin_colors_download(fin_colors* c, uint64_t* bits_out, uint64_t* n_set, char* err, size_t errlen) {
+    if (!c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int wrc = c->pend.wait(err, errlen)) return wrc;
+    uint32_t flags = 0;
+    HIPCHK(hipMemcpy(&flags, colors_flags(c), 4, hipMemcpyDeviceToHost));
+    if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: it has no results, nothing of it was coloured (reset the colours)"); return FIN_ELIMIT; }
+    const size_t n = (size_t)c->n_unitigs * c->words;
+    std::vector<uint64_t> tmp;
+    uint64_t* dst = bits_out;
+    if (!dst) { if (!n_set) return FIN_OK; tmp.resize(n); dst = tmp.data(); }
+    if (n) HIPCHK(hipMemcpy(dst, c->d_bits, n * 8, hipMemcpyDeviceToHost));
+    if (n_set) { uint64_t t = 0; for (size_t q = 0; q < n; q++) t += (uint64_t)__builtin_popcountll(dst[q]); *n_set = t; }
+    return FIN_OK;
+}
+
+int fin_batch_add_colors(fin_batch* b, fin_colors* c, uint32_t color, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (color >= c->n_colors) { set_err(err, errlen, "colour " + std::to_string(color) + " is not below n_colors = " + std::to_string(c->n_colors)); return FIN_EINVAL; }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (const int brc = acc_behind_run(b, c->idx, c->device, st, err, errlen)) return brc;
+    if (b->n_kmers != 0) {   // (no read has a k-mer: the step searched nothing)
+        const int rc = fin_launch_colors_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->dev.k, c->d_bits, c->words,
+                                             (uint32_t)c->n_unitigs, color, colors_flags(c), b->d_ovf_count, b->last_ovf_cap, st);
+        if (rc != 0) { set_err(err, errlen, std::string("colour kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    }
+    return c->pend.mark(st, err, errlen);
+}
+
+int fin_batch_pseudoalign(fin_batch* b, const fin_colors* c, uint32_t permille, char* err, size_t errlen) {
+    if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (!b->ran) { set_err(err, errlen, "this batch has not run: there is nothing to pseudoalign (fin_batch_run first)"); return FIN_EINVAL; }
+    if (b->idx != c->idx || b->device != c->device) { set_err(err, errlen, "batch and colours belong to different indexes or devices"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    b->psa_ready = false;
+    // (no read has a k-mer: the step searched nothing, there is no overflow list to look at -- every row is empty)
+    if (b->n_kmers != 0) if (const int orc = batch_overrun_check(b, st, err, errlen)) return orc;   // a run without results: nothing is written
+    const uint32_t nr = (uint32_t)b->n_reads;
+    if (batch_grow(b, &b->d_psa_rows, b->cap_psa_rows, (size_t)nr * c->words * 8 + 16, st) || batch_grow(b, &b->d_psa_heads, b->cap_psa_heads, (size_t)nr * 16 + 16, st)) {
+        set_err(err, errlen, "out of device memory (colour rows of the reads)"); return FIN_ENOMEM;
+    }
+    if (const int orc = const_cast<fin_colors*>(c)->pend.order(st, err, errlen)) return orc;   // the adds to the matrix, on whichever streams, come first
+    const int rc = fin_launch_pseudoalign(b->n_kmers != 0 && b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, nr, b->dev.k, c->d_bits, c->words,
+                                          (uint32_t)c->n_unitigs, permille, b->d_psa_rows, b->d_psa_heads, st);
+    if (rc != 0) { set_err(err, errlen, std::string("pseudoalignment kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    b->psa_ready = true; b->psa_words = c->words;
+    return FIN_OK;
+}
+
+void* fin_batch_device_pseudo_rows(const fin_batch* b) { return b && b->psa_ready ? b->d_psa_rows : nullptr; }
+void* fin_batch_device_pseudo_heads(const fin_batch* b) { return b && b->psa_ready ? b->d_psa_heads : nullptr; }
+
+int fin_batch_download_pseudo(fin_batch* b, uint64_t* rows_out, fin_read_pseudo* heads_out, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->psa_ready) { set_err(err, errlen, "fin_batch_pseudoalign first"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    if (b->n_reads && rows_out) HIPCHK(hipMemcpyAsync(rows_out, b->d_psa_rows, (size_t)b->n_reads * b->psa_words * 8, hipMemcpyDeviceToHost, st));
+    if (b->n_reads && heads_out) HIPCHK(hipMemcpyAsync(heads_out, b->d_psa_heads, (size_t)b->n_reads * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
+// host: the same rows and heads from records + stream -- the CPU statement of fin_col_pseudo_kernel, over the segments segment_slots / segment_record make: a
+// segment of |len| slots in unitig u is |len| counts for every colour of u
+int fin_records_pseudoalign(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint64_t* bits,
+                            uint64_t n_unitigs, uint32_t n_colors, uint32_t permille, uint64_t* rows_out, fin_read_pseudo* heads_out, int n_threads) {
+    if ((n_reads && (!recs || !rows_out || !heads_out)) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !bits)) return FIN_EINVAL;
+    if (n_colors == 0 || n_colors > FIN_MAX_COLORS) return FIN_ELIMIT;
+    if (permille > 1000u) return FIN_EINVAL;
+    const uint32_t W = (n_colors + 63u) / 64u;
+    if (colors_first_stray(bits, n_unitigs, n_colors, W) != n_unitigs) return FIN_EINVAL;
+    int T = n_threads > 0 ? n_threads : fin_host_threads();
+    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
+    std::vector<uint64_t> str0((size_t)T + 1, 0);
+    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
+        const auto lh = bounds(t);
+        uint64_t sp = 0;
+        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
+        str0[(size_t)t + 1] = sp;
+    }
+    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
+    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
+    bool ok = true;
+#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
+    for (int t = 0; t < T; t++) {
+        const auto lh = bounds(t);
+        uint64_t sp = str0[(size_t)t];
+        bool good = true;
+        std::vector<std::pair<uint32_t, uint32_t>> segs;   // (unitig, slots) per segment
+        std::vector<uint64_t> cnt((size_t)W * 64);
+        for (uint64_t r = lh.first; r < lh.second && good; r++) {
+            const fin_read_record& R = recs[r];
+            const uint32_t kind = R.meta >> 16;
+            segs.clear();
+            auto emit = [&](int32_t u, int32_t, uint32_t, int32_t len) {
+                if ((uint64_t)(uint32_t)u >= n_unitigs) { good = false; return; }
+                segs.push_back({(uint32_t)u, (uint32_t)(len < 0 ? -(int64_t)len : (int64_t)len)});
+            };
+            if (kind == 0u) { good = segment_slots(stream_pairs + 2 * sp, R.nk, emit) && good; sp += R.nk; }
+            else if (kind == 1u) segment_record(R, k, emit);
+            std::fill(cnt.begin(), cnt.end(), 0);
+            uint64_t n_found = 0, n_colored = 0;
+            for (const auto& sg : segs) {
+                n_found += sg.second;
+                const uint64_t* row = bits + (uint64_t)sg.first * W;
+                bool ne = false;
+                for (uint32_t w = 0; w < W; w++) {
+                    uint64_t x = row[w];
+                    if (x) ne = true;
+                    for (; x; x &= x - 1) cnt[(size_t)w * 64 + (size_t)__builtin_ctzll(x)] += sg.second;
+                }
+                if (ne) n_colored += sg.second;
+            }
+            uint32_t pc = 0;
+            for (uint32_t w = 0; w < W; w++) {
+                uint64_t o = 0;
+                for (uint32_t q = 0; q < 64u; q++) { const uint64_t c = cnt[(size_t)w * 64 + q]; if (c >= 1 && 1000ull * c >= (uint64_t)permille * n_colored) o |= 1ull << q; }
+                rows_out[r * W + w] = o; pc += (uint32_t)__builtin_popcountll(o);
+            }
+            heads_out[r] = fin_read_pseudo{(uint32_t)n_found, (uint32_t)n_colored, pc, 0};
         }
         ok = good && ok;
     }
@@ -2452,6 +2657,10 @@ struct TextSink {
     // (classes when `cls` is set: fin_search_batch_classify -- a sub-batch's land at its reads' numbers; with `tally` every sub-batch is added to the
     //  labelling's tally on the device instead and nothing comes back: fin_search_batch_add_classes)
     const fin_labels* labels = nullptr; fin_read_class* cls = nullptr; fin_labels* tally = nullptr; uint32_t cls_min_found = 0, cls_min_permille = 0, cls_min_margin = 0;
+    // (colouring when `paint` is set: fin_search_batch_add_colors -- every sub-batch's unitigs get `paint_color` on the device, nothing comes back;
+    //  pseudoalignment when `psa` is set: fin_search_batch_pseudoalign -- a sub-batch's rows (may be null) and heads land at its reads' numbers)
+    fin_colors* paint = nullptr; uint32_t paint_color = 0;
+    const fin_colors* psa = nullptr; uint32_t psa_permille = 0; uint64_t* psa_rows = nullptr; fin_read_pseudo* psa_heads = nullptr;
     std::vector<uint64_t> len; std::vector<char> known;
     std::mutex mu; std::condition_variable cv;
     uint64_t total = 0;
@@ -2559,6 +2768,16 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
                 fin_read_summary* const dst = ts->rsum + (s.lo - ts->read0);
                 if (rc == FIN_OK) rc = fin_batch_download_read_summaries(b, dst, e, sizeof e);
                 if (rc == FIN_OK) for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_found;
+            } else
+            if (rc == FIN_OK && ts && ts->paint) {
+                rc = fin_batch_add_colors(b, ts->paint, ts->paint_color, (void*)b->own_stream, e, sizeof e);
+            } else
+            if (rc == FIN_OK && ts && ts->psa) {
+                rc = fin_batch_pseudoalign(b, ts->psa, ts->psa_permille, e, sizeof e);
+                const uint64_t at = s.lo - ts->read0;
+                fin_read_pseudo* const dst = ts->psa_heads + at;
+                if (rc == FIN_OK) rc = fin_batch_download_pseudo(b, ts->psa_rows ? ts->psa_rows + at * fin_colors_words(ts->psa) : nullptr, dst, e, sizeof e);
+                if (rc == FIN_OK) for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_colored;
             } else
             if (rc == FIN_OK && ts && ts->tally) {
                 rc = fin_batch_add_classes(b, ts->tally, ts->cls_min_found, ts->cls_min_permille, ts->cls_min_margin, (void*)b->own_stream, e, sizeof e);
@@ -2788,6 +3007,30 @@ int fin_search_batch_classify(const fin_index* idx, const char* bases, const uin
     TextSink ts; ts.labels = l; ts.cls = out; ts.read0 = 0;
     uint64_t pos = 0;
     const int rc = search_range_on(idx, l->device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
+    if (rc == FIN_OK && n_positive) *n_positive = pos;
+    return rc;
+}
+
+int fin_search_batch_add_colors(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_colors* c, uint32_t color, char* err,
+                                size_t errlen) {
+    if (!idx || !offsets || !c || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (c->idx != idx) { set_err(err, errlen, "the colours belong to another index"); return FIN_EINVAL; }
+    if (color >= c->n_colors) { set_err(err, errlen, "colour " + std::to_string(color) + " is not below n_colors = " + std::to_string(c->n_colors)); return FIN_EINVAL; }
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.paint = c; ts.paint_color = color;
+    return search_range_on(idx, c->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+}
+
+int fin_search_batch_pseudoalign(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_colors* c, uint32_t permille,
+                                 uint64_t* rows_out, fin_read_pseudo* heads_out, uint64_t* n_positive, char* err, size_t errlen) {
+    if (!idx || !offsets || !c || (n_reads && !heads_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (c->idx != idx) { set_err(err, errlen, "the colours belong to another index"); return FIN_EINVAL; }
+    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (n_positive) *n_positive = 0;
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.psa = c; ts.psa_permille = permille; ts.psa_rows = rows_out; ts.psa_heads = heads_out; ts.read0 = 0;
+    uint64_t pos = 0;
+    const int rc = search_range_on(idx, c->device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
     if (rc == FIN_OK && n_positive) *n_positive = pos;
     return rc;
 }

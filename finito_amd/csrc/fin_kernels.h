@@ -169,6 +169,13 @@ int fin_launch_classify(const void* frec, const uint64_t* out_offs, const void* 
                         void* cls, hipStream_t stream);
 int fin_launch_class_tally(const void* cls, const uint64_t* out_offs, uint32_t n_reads, uint32_t n_labels, uint32_t min_found, uint32_t min_permille,
                            uint32_t min_margin, uint64_t* reads, hipStream_t stream);
+// fin_colors.hip -- colour sets per unitig: bits uint64[n_unitigs * W], then one flag word (bit 0: a step whose overflow list overran was offered).
+// fin_launch_colors_add: bit `color` for every unitig in which the step found a k-mer (frec null: every read's pairs are scanned).
+// fin_launch_pseudoalign: rows uint64[n_reads * W] and heads {n_found, n_coloured, popcount, 0} per read under the threshold permille
+int fin_launch_colors_add(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, void* bits, uint32_t W, uint32_t n_unitigs,
+                          uint32_t color, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, hipStream_t stream);
+int fin_launch_pseudoalign(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const void* bits, uint32_t W,
+                           uint32_t n_unitigs, uint32_t permille, void* rows, void* heads, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

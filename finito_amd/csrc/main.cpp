@@ -490,8 +490,19 @@ static const char* SEARCH_HELP =
     "      --class-min-found N     the N of --label-report (default: 1)\n"
     "      --class-min-permille P  the P of --label-report, 0 to 1000 (default: 0)\n"
     "      --class-min-margin M    the M of --label-report (default: 0; 1 leaves ties unassigned)\n"
-    "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify or\n"
-    "                        --label-report): do not make or write the pair text, the other results asked for are the only ones\n"
+    "      --color-refs LIST  colour the index's unitigs by search: LIST holds one FASTA/FASTQ path per line, the line's number (from 0, empty lines\n"
+    "                        skipped, at most 4096) is the colour; every sequence of file c is searched on the first GPU and every unitig in which one of\n"
+    "                        its k-mers is found gets colour c. Sequences longer than 4096 k-mers are cut into windows that overlap by k - 1 bases, so\n"
+    "                        that no k-mer is lost. Needed by --colors-out and --pseudoalign. Not for a partitioned index.\n"
+    "      --colors-out FILE  write `unitig<TAB>c1,c2,...` per unitig of the index, in the index's unitig numbers, `-` for a unitig without a colour\n"
+    "      --pseudoalign FILE  also write one line per read, in input order: `read<TAB>k-mers<TAB>found<TAB>coloured<TAB>c1,c2,...` -- `read` and k-mers as\n"
+    "                        in --read-summary, found = the k-mers found, coloured = those of them in a unitig with a colour, then the colours that at\n"
+    "                        least P thousandths of the coloured k-mers have (`-` for none). Made on the first GPU from one more search of every chunk;\n"
+    "                        goes with everything --read-summary goes with. Not for a partitioned index.\n"
+    "      --pseudo-permille P  the P of --pseudoalign, 0 to 1000 (default: 1000, the intersection; 0 is the union)\n"
+    "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify,\n"
+    "                        --label-report, --colors-out or --pseudoalign): do not make or write the pair text, the other results asked for are the\n"
+    "                        only ones\n"
     "  -h, --help            Print usage\n";
 
 static int build_fmin(int argc, char** argv) {
@@ -806,6 +817,65 @@ static vector<uint32_t> load_labelling(const FinimizerIndex& index, const string
     *n_labels = (uint32_t)(top ? top : 1);
     return labels;
 }
+// --pseudoalign FILE: every chunk's reads are pseudoaligned against the colours of --color-refs on the first device (fin_search_batch_pseudoalign) and written as
+// lines, by the search stage, in chunk order
+static fin_colors* g_colors = nullptr;
+static FILE* g_psa_file = nullptr;
+static uint64_t g_psa_read0 = 0;
+static uint32_t g_psa_permille = 1000;
+static vector<uint64_t> g_psa_rows; static vector<fin_read_pseudo> g_psa_heads; static string g_psa_text;
+static void append_colors(string& t, const uint64_t* row, uint32_t W) {
+    bool any = false;
+    for (uint32_t w = 0; w < W; w++)
+        for (uint64_t x = row[w]; x; x &= x - 1) { if (any) t += ','; t += to_string(64 * w + (uint32_t)__builtin_ctzll(x)); any = true; }
+    if (!any) t += '-';
+}
+static void pseudoalign_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads, const uint64_t* pair_off) {
+    char err[512] = {0};
+    const uint32_t W = fin_colors_words(g_colors);
+    g_psa_rows.resize((size_t)n_reads * W + 1); g_psa_heads.resize(n_reads + 1);
+    if (fin_search_batch_pseudoalign(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_colors, g_psa_permille, g_psa_rows.data(), g_psa_heads.data(), nullptr, err,
+                                     sizeof err) != FIN_OK)
+        throw runtime_error(err);
+    string& t = g_psa_text;
+    t.clear();
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const fin_read_pseudo& S = g_psa_heads[r];
+        t += to_string(g_psa_read0 + r); t += '\t'; t += to_string(pair_off[r + 1] - pair_off[r]); t += '\t'; t += to_string(S.n_found); t += '\t';
+        t += to_string(S.n_colored); t += '\t';
+        append_colors(t, g_psa_rows.data() + (size_t)r * W, W);
+        t += '\n';
+    }
+    if (!t.empty() && fwrite(t.data(), 1, t.size(), g_psa_file) != t.size()) throw runtime_error("Error writing the pseudoalignment file");
+    g_psa_read0 += n_reads;
+}
+// colour `color` for every unitig in which a k-mer of the file's sequences is found.  A sequence of more than COLOR_WINDOW k-mers is cut into windows that overlap
+// by k - 1 bases: every k-mer lies in exactly one window, and a window is a read of ordinary length for the search pipeline (a chromosome as one read would be
+// one sub-batch, scanned by one wave)
+static void color_by_search(const FinimizerIndex& index, const string& fasta, uint32_t color) {
+    const uint64_t COLOR_WINDOW = 4096, FLUSH_BASES = 64u << 20;
+    const uint64_t k = (uint64_t)index.get_k();
+    string bases; vector<uint64_t> offsets{0};
+    auto flush = [&]() {
+        char err[512] = {0};
+        if (offsets.size() > 1 && fin_search_batch_add_colors(index.handle(), bases.data(), offsets.data(), offsets.size() - 1, FIN_MERGED, g_colors, color, err, sizeof err) != FIN_OK)
+            throw runtime_error(fasta + ": " + err);
+        bases.clear(); offsets.assign(1, 0);
+    };
+    SeqReader reader(fasta);
+    int64_t len;
+    while ((len = reader.get_next_read_to_buffer()) > 0) {
+        const char* seq = reader.read_buf.data();
+        const uint64_t n = (uint64_t)len;
+        if (n < k) continue;   // no k-mer
+        for (uint64_t at = 0; at + k <= n; at += COLOR_WINDOW) {   // k-mers [at, at + COLOR_WINDOW)
+            const uint64_t end = min<uint64_t>(n, at + COLOR_WINDOW + k - 1);
+            bases.append(seq + at, (size_t)(end - at)); offsets.push_back(bases.size());
+        }
+        if (bases.size() >= FLUSH_BASES) flush();
+    }
+    flush();
+}
 static bool g_no_text = false;
 static uint64_t g_hits_total = 0;   // the accumulator's sum after the previous query file
 
@@ -889,6 +959,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_rs_file) c->positive = read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
+                        if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                     }
                     else {
                         // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
@@ -909,6 +980,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_rs_file) (void)read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
+                        if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                     }
                     if (g_strand_counts) {
                         c->positive_fwd = index.count_found_one_strand(c->bases.get(0), c->offsets.data(), n_reads);
@@ -1024,12 +1096,15 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report"))
-        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify or --label-report (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign"))
+        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify, --label-report, --colors-out or --pseudoalign (the run would have no result)");
+    if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
+    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out")) throw runtime_error("--color-refs is only legal together with --pseudoalign or --colors-out");
+    if (o.has("pseudo-permille") && !o.has("pseudoalign")) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign");
     if ((o.has("classify") || o.has("label-report")) && !(o.has("label-unitigs") && o.has("labels"))) throw runtime_error("--classify and --label-report want a labelling: --label-unitigs FASTA --labels FILE");
     if ((o.has("label-unitigs") || o.has("labels")) && !o.has("classify") && !o.has("label-report")) throw runtime_error("--label-unitigs and --labels are only legal together with --classify or --label-report");
     for (const char* name : {"class-min-found", "class-min-permille", "class-min-margin"})
@@ -1049,6 +1124,13 @@ static int search_fmin(int argc, char** argv) {
     g_cls_min_found = u32_option("class-min-found", 1, 0xFFFFFFFFull);
     g_cls_min_permille = u32_option("class-min-permille", 0, 1000);
     g_cls_min_margin = u32_option("class-min-margin", 0, 0xFFFFFFFFull);
+    g_psa_permille = u32_option("pseudo-permille", 1000, 1000);
+    vector<string> color_refs;
+    if (o.has("color-refs")) {
+        color_refs = readlines(o.get("color-refs"));
+        if (color_refs.empty()) throw runtime_error("--color-refs: " + o.get("color-refs") + " is empty, it names no reference");
+        if (color_refs.size() > FIN_MAX_COLORS) throw runtime_error("--color-refs: " + o.get("color-refs") + " names " + to_string(color_refs.size()) + " references, at most " + to_string(FIN_MAX_COLORS) + " colours are supported");
+    }
     g_scr_invert = o.has("screen-invert") && o.get("screen-invert") != "0" && o.get("screen-invert") != "false" ? 1 : 0;
     if (o.has("min-depth") && !o.has("unitig-depth")) throw runtime_error("--min-depth is only legal together with --unitig-depth");
     uint32_t min_depth = 1;
@@ -1092,6 +1174,9 @@ static int search_fmin(int argc, char** argv) {
     const string cls_file = o.get("classify", ""), report_file = o.get("label-report", "");
     if (!cls_file.empty()) check_writable(cls_file);
     if (!report_file.empty()) check_writable(report_file);
+    const string colors_file = o.get("colors-out", ""), psa_file = o.get("pseudoalign", "");
+    if (!colors_file.empty()) check_writable(colors_file);
+    if (!psa_file.empty()) check_writable(psa_file);
     cerr << "Loading index..." << endl;
     const int first_dev = stoi(o.get("device", "0"));
     // beside the index load: page-lock the pipeline's buffers (four chunks of 48 MB of bases and of up to 16 bytes of text per k-mer)
@@ -1135,6 +1220,7 @@ static int search_fmin(int argc, char** argv) {
     if (!scr_file.empty() && index.partitioned()) throw runtime_error("--screen is not available with a partitioned index");
     if (!cls_file.empty() && index.partitioned()) throw runtime_error("--classify is not available with a partitioned index");
     if (!report_file.empty() && index.partitioned()) throw runtime_error("--label-report is not available with a partitioned index");
+    if (!color_refs.empty() && index.partitioned()) throw runtime_error("--color-refs is not available with a partitioned index");
     index.to_device();
     struct HitsOwner { ~HitsOwner() { fin_hits_free(g_hits); g_hits = nullptr; } } hits_owner;
     if (!counts_file.empty() || (g_no_text && seg_file.empty() && rs_file.empty())) {   // (with --segments the found k-mers are the sum of the segments' lengths, with --read-summary the sum of `found`)
@@ -1181,6 +1267,31 @@ static int search_fmin(int argc, char** argv) {
             if (!g_cls_file) throw runtime_error("Error writing to file: " + cls_file);
         }
     }
+    struct ColorOwner { ~ColorOwner() { if (g_psa_file) fclose(g_psa_file); g_psa_file = nullptr; fin_colors_free(g_colors); g_colors = nullptr; } } color_owner;
+    if (!color_refs.empty()) {
+        for (auto& f : color_refs) check_readable(f);
+        char err[512] = {0};
+        if (fin_colors_create(index.handle(), first_dev, (uint32_t)color_refs.size(), &g_colors, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        for (size_t c = 0; c < color_refs.size(); c++) color_by_search(index, color_refs[c], (uint32_t)c);
+        const size_t nu = (size_t)index.number_of_unitigs();
+        const uint32_t W = fin_colors_words(g_colors);
+        vector<uint64_t> bits(nu * W + 1);
+        uint64_t n_set = 0;
+        if (fin_colors_download(g_colors, bits.data(), &n_set, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        write_log("Coloured " + to_string(nu) + " unitigs by " + to_string(color_refs.size()) + " references: " + to_string(n_set) + " (unitig, colour) pairs");
+        if (!colors_file.empty()) {
+            string text;
+            for (size_t u = 0; u < nu; u++) { text += to_string(u); text += '\t'; append_colors(text, bits.data() + u * W, W); text += '\n'; }
+            ofstream cf(colors_file, ios::binary | ios::trunc);
+            cf.write(text.data(), (streamsize)text.size());
+            if (!cf) throw runtime_error("Error writing to file: " + colors_file);
+        }
+        if (!psa_file.empty()) {
+            g_psa_file = fopen(psa_file.c_str(), "wb");
+            if (!g_psa_file) throw runtime_error("Error writing to file: " + psa_file);
+            g_psa_read0 = 0;
+        }
+    }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
              << (cur_time_micros() - t_l1) * 1e-6 << endl;
@@ -1220,6 +1331,11 @@ static int search_fmin(int argc, char** argv) {
         const bool bad = fflush(g_cls_file) != 0 || ferror(g_cls_file);
         fclose(g_cls_file); g_cls_file = nullptr;
         if (bad) throw runtime_error("Error writing to file: " + cls_file);
+    }
+    if (g_psa_file) {
+        const bool bad = fflush(g_psa_file) != 0 || ferror(g_psa_file);
+        fclose(g_psa_file); g_psa_file = nullptr;
+        if (bad) throw runtime_error("Error writing to file: " + psa_file);
     }
     if (g_labels && g_cls_report) {   // the tally, after the last chunk: one line per label, then the unassigned reads
         char err[512] = {0};

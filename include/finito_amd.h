@@ -682,8 +682,9 @@ int fin_records_read_summaries(const fin_read_record* recs, uint64_t n_reads, co
  * or {FIN_NO_LABEL, 0, 0, 0} when no found slot is labelled.  The class is exact for every read, however many distinct labels it touches, and invariant under
  * reversing the slot order: a read found on its reverse strand (a kind-1 record with meta bit 8) needs no special case.  16 bytes per read come back, or one
  * uint64 per label for a whole run (the tally: an abundance report in reads).
- * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, several labels per unitig (colour sets), and labelling
- * unitigs by searching reference genomes (fin_index_unitig_numbers below maps the caller's unitig order to the index's numbers; the labels are the caller's). */
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror.  Several labels per unitig and labelling unitigs by
+ * searching reference genomes are the COLOUR SETS below (fin_colors); fin_index_unitig_numbers maps the caller's unitig order to the index's numbers for a
+ * labelling the caller brings. */
 #define FIN_NO_LABEL 0xFFFFFFFFu
 typedef struct fin_read_class { uint32_t label, n_best, n_second, n_labelled; } fin_read_class;   /* 16 bytes */
 typedef struct fin_labels fin_labels;
@@ -729,6 +730,63 @@ int fin_records_read_classes(const fin_read_record* recs, uint64_t n_reads, cons
  * whose offset must be 0.  FIN_EINVAL, with a message that names the sequence, for one shorter than k, one that is not a unitig of this index, or one whose first
  * k-mer the index reports elsewhere (a unitig set that is not disjoint). */
 int fin_index_unitig_numbers(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint32_t* out, char* err, size_t errlen);
+
+/* ---- COLOUR SETS per unitig and read PSEUDOALIGNMENT, made on the device ----
+ * The index's input is the unitig set of a de Bruijn graph over many references, and most unitigs of such a graph are shared.  A COLOUR MATRIX says which
+ * references each unitig occurs in: uint64 bits[n_unitigs][W], W = ceil(n_colors / 64), in the index's own unitig numbers; colour c of unitig u is bit c & 63 of
+ * bits[u * W + (c >> 6)]; bits at or above n_colors are always 0.  LIMIT: 1 <= n_colors <= FIN_MAX_COLORS = 4096, so W <= 64 -- one row is at most one 64-bit
+ * word per lane of a wave; anything else is FIN_ELIMIT.  The matrix lives in HBM beside one replica of the index.
+ * PSEUDOALIGNMENT (as in Themisto, Bifrost, Metagraph), exact and in integers, over a read's output slots 0 .. nk - 1: a found slot whose unitig has a non-empty
+ * row is COLOURED; n_found = the found slots, n_colored = the coloured ones, cnt[c] = the coloured slots whose unitig has colour c.  For a threshold permille in
+ * 0 .. 1000 colour c is in the read's row iff cnt[c] >= 1 and 1000 * cnt[c] >= permille * n_colored (64-bit arithmetic).  permille = 1000 is the intersection over
+ * the coloured k-mers -- found k-mers in uncoloured unitigs and absent k-mers are ignored --, permille = 0 the union.  All of it is invariant under reversing the
+ * slot order.  A pair whose unitig number is at or above the index's number of unitigs counts as absent on the device and is FIN_EINVAL on the host.
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, a per-colour tally of reads, more than 4096 colours,
+ * compressed or deduplicated colour sets. */
+#define FIN_MAX_COLORS 4096u
+typedef struct fin_read_pseudo { uint32_t n_found, n_colored, n_colors, reserved /* 0 */; } fin_read_pseudo;   /* 16 bytes; n_colors = the popcount of the read's row */
+typedef struct fin_colors fin_colors;
+/* a zeroed matrix beside the replica on `device`.  FIN_ELIMIT: n_colors is 0 or above FIN_MAX_COLORS.  FIN_ENODEV: no replica on that device. */
+int fin_colors_create(const fin_index* idx, int device, uint32_t n_colors, fin_colors** out, char* err, size_t errlen);
+/* replaces the matrix (waits for every add issued so far): bits[fin_index_n_unitigs * fin_colors_words].  FIN_EINVAL if any bit at or above n_colors is set; the
+ * message names the unitig. */
+int fin_colors_upload(fin_colors* c, const uint64_t* bits, char* err, size_t errlen);
+int fin_colors_reset(fin_colors* c, void* hip_stream);   /* zeroes the matrix (asynchronous on hip_stream) */
+void* fin_colors_device_bits(const fin_colors* c);       /* uint64[fin_index_n_unitigs * fin_colors_words] in HBM */
+uint32_t fin_colors_n_colors(const fin_colors* c);
+uint32_t fin_colors_words(const fin_colors* c);          /* W */
+/* waits for every add and reset issued so far; bits_out (may be NULL): the matrix; *n_set (may be NULL) = the total number of set bits.  FIN_ELIMIT: a run whose
+ * overflow list overran was added (nothing of it was coloured) */
+int fin_colors_download(fin_colors* c, uint64_t* bits_out, uint64_t* n_set, char* err, size_t errlen);
+void fin_colors_free(fin_colors* c);
+/* COLOURING BY SEARCH: behind the batch's most recent run, on hip_stream, ordered as fin_batch_add_hits is: every unitig in which that run found at least one
+ * k-mer gets bit `color` set (fin_colors.hip: one plain load per unitig met, an atomic OR only where the bit is clear).  Adding twice changes nothing.  Search
+ * reference genome i through the index and add with color = i: that is the colouring.  Works in every text mode, FIN_MERGED and FIN_FWD, every k.
+ * FIN_EINVAL: color >= n_colors, the batch has not run, or the colours belong to another index or device.  FIN_ELIMIT: the run's overflow list overran. */
+int fin_batch_add_colors(fin_batch* b, fin_colors* c, uint32_t color, void* hip_stream, char* err, size_t errlen);
+/* fin_search_batch_add_hits' loop with the colouring as its product: host buffers in, sub-batches pipelined, each run in text mode 2 where the fast path is on */
+int fin_search_batch_add_colors(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_colors* c, uint32_t color, char* err,
+                                size_t errlen);
+/* Behind the batch's most recent run, on that run's stream, and behind every add to the matrix issued so far: one kernel, a lane per read; a read the fast path
+ * finished lies in one unitig, its row is that unitig's row (a wave-cooperative copy), every other read's pairs are scanned in place.  Exact for every read,
+ * however many distinct unitigs it touches.  rows uint64[n_reads][W] and fin_read_pseudo[n_reads] stay in HBM, in buffers the batch keeps and only grows.  Read-only
+ * on records, pairs, text, segments, summaries, screen and classes.  Empty batches and batches of reads without k-mers are legal.  fin_batch_run,
+ * fin_batch_reload, fin_batch_set_records and fin_batch_set_pairs forget the rows.
+ * FIN_EINVAL: permille > 1000, the batch has not run, or the colours belong to another index or device.  FIN_ELIMIT: the run's overflow list overran. */
+int fin_batch_pseudoalign(fin_batch* b, const fin_colors* c, uint32_t permille, char* err, size_t errlen);
+void* fin_batch_device_pseudo_rows(const fin_batch* b);    /* uint64[n_reads * W] in HBM; NULL before fin_batch_pseudoalign */
+void* fin_batch_device_pseudo_heads(const fin_batch* b);   /* fin_read_pseudo[n_reads] in HBM; NULL before fin_batch_pseudoalign */
+int fin_batch_download_pseudo(fin_batch* b, uint64_t* rows_out, fin_read_pseudo* heads_out, char* err, size_t errlen);   /* either pointer may be NULL */
+/* host buffers in: fin_search_batch's pipeline over sub-batches, each run in text mode 2 where the fast path is on (the twin of fin_search_batch_classify), on
+ * the colours' device.  rows_out[n_reads * W] (may be NULL), heads_out[n_reads]; *n_positive (may be NULL) = the coloured k-mers found (the sum of n_colored).
+ * Reads shorter than k and an empty read set are legal. */
+int fin_search_batch_pseudoalign(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_colors* c, uint32_t permille,
+                                 uint64_t* rows_out, fin_read_pseudo* heads_out, uint64_t* n_positive, char* err, size_t errlen);
+/* host, no device: the same rows and heads from records + stream (the sibling of fin_records_read_classes).  bits[n_unitigs * W]; rows_out[n_reads * W];
+ * heads_out[n_reads]; n_threads <= 0: all cores.  FIN_ELIMIT: n_colors is 0 or above FIN_MAX_COLORS.  FIN_EINVAL: permille > 1000, a set bit at or above
+ * n_colors, a unitig number >= n_unitigs, a stream that is not this record set's, or a stream pair that is neither found nor (-1,-1) */
+int fin_records_pseudoalign(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint64_t* bits,
+                            uint64_t n_unitigs, uint32_t n_colors, uint32_t permille, uint64_t* rows_out, fin_read_pseudo* heads_out, int n_threads);
 
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
