@@ -516,6 +516,15 @@ class Batch:
             raise FinitoError(rc, "fin_batch_debug_ingest")
         return bool(fused.value), ch, pv
 
+    def debug_side_stream(self):
+        """diagnostic: the side stream of option "overlap_prefill" as an int handle (fin_batch_debug_side_stream)"""
+        self.L.fin_batch_debug_side_stream.restype = C.c_void_p
+        self.L.fin_batch_debug_side_stream.argtypes = [C.c_void_p]
+        h = self.L.fin_batch_debug_side_stream(self.h)
+        if not h:
+            raise FinitoError(FIN_ENODEV, "fin_batch_debug_side_stream")
+        return int(h)
+
     def kernel_time_ms(self):
         ms, n = C.c_double(0), C.c_uint64(0)
         self.L.fin_batch_kernel_time(self.h, C.byref(ms), C.byref(n))

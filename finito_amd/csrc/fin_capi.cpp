@@ -1,6 +1,7 @@
 // fin_capi.cpp -- implementation of the C ABI declared in include/finito_amd.h.
 // Host orchestration only: index lifetime, HBM replica, batches, launches.  No CPU search path exists here:
 // without a HIP device every search entry point fails with FIN_ENODEV.
+#include <functional>
 #include <hip/hip_runtime_api.h>
 #include <sched.h>
 
@@ -1058,6 +1059,16 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     return FIN_OK;
 }
 
+// diagnostic (tests of the stream contract): the side stream of option "overlap_prefill", made here if no run has made it yet
+void* fin_batch_debug_side_stream(fin_batch* b) {
+    if (!b || hipSetDevice(b->device) != hipSuccess) return nullptr;
+    if (!b->side_stream) {
+        if (hipStreamCreateWithFlags(&b->side_stream, hipStreamNonBlocking) != hipSuccess) { b->side_stream = nullptr; return nullptr; }
+        if (hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming) != hipSuccess) return nullptr;
+    }
+    return (void*)b->side_stream;
+}
+
 uint64_t fin_batch_n_kmers(const fin_batch* b) { return b ? b->n_kmers : 0; }
 uint64_t fin_batch_n_base_strands(const fin_batch* b) { return b ? (b->last_strands == FIN_MERGED ? b->n_base_strands : b->total_bases) : 0; }
 void* fin_batch_device_pairs(const fin_batch* b) { return b ? b->d_out : nullptr; }
@@ -1712,7 +1723,36 @@ struct AccPending {
         for (auto& p : pending) if (p.first != st) HIPCHK(hipStreamWaitEvent(st, p.second, 0));
         return FIN_OK;
     }
-    void drop() { for (auto& p : pending) { (void)hipEventSynchronize(p.second); (void)hipEventDestroy(p.second); } pending.clear(); }
+    // a reset does not commute with the adds: it runs behind everything issued so far on other streams, and every later add on another stream runs behind it
+    // (the reset's own event -- a stream's mark is recorded again by its next add --, which behind_reset makes an add's stream wait for).  One lock is held from
+    // the waits over `zero` (the memset, on `st`) to the two records, so an add from another host thread falls before the reset or behind it, never in between.
+    // Adds among themselves stay unordered: they are atomic and commute
+    hipStream_t reset_st = nullptr; hipEvent_t reset_ev = nullptr;
+    int reset(hipStream_t st, const std::function<hipError_t()>& zero) {
+        char* err = nullptr; const size_t errlen = 0;
+        std::lock_guard<std::mutex> g(mu);
+        for (auto& p : pending) if (p.first != st) HIPCHK(hipStreamWaitEvent(st, p.second, 0));
+        if (zero() != hipSuccess) return FIN_ENODEV;
+        if (!reset_ev) HIPCHK(hipEventCreateWithFlags(&reset_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(reset_ev, st));
+        reset_st = st;
+        for (auto& p : pending) if (p.first == st) { HIPCHK(hipEventRecord(p.second, st)); return FIN_OK; }
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        pending.push_back({st, ev});
+        HIPCHK(hipEventRecord(ev, st));
+        return FIN_OK;
+    }
+    int behind_reset(hipStream_t st, char* err, size_t errlen) {
+        std::lock_guard<std::mutex> g(mu);
+        if (reset_ev && reset_st != st) HIPCHK(hipStreamWaitEvent(st, reset_ev, 0));
+        return FIN_OK;
+    }
+    void drop() {
+        for (auto& p : pending) { (void)hipEventSynchronize(p.second); (void)hipEventDestroy(p.second); }
+        pending.clear();
+        if (reset_ev) { (void)hipEventSynchronize(reset_ev); (void)hipEventDestroy(reset_ev); reset_ev = nullptr; }
+    }
 };
 // behind the batch's most recent run, whichever stream it was launched on: what fin_batch_add_hits, fin_batch_add_cover and fin_batch_add_depth check and order alike
 static int acc_behind_run(fin_batch* b, const fin_index* acc_idx, int acc_device, hipStream_t st, char* err, size_t errlen) {
@@ -1764,8 +1804,7 @@ int fin_hits_reset(fin_hits* h, void* hip_stream) {
     if (!h) return FIN_EINVAL;
     if (hipSetDevice(h->device) != hipSuccess) return FIN_ENODEV;
     hipStream_t st = (hipStream_t)hip_stream;
-    if (hipMemsetAsync(h->d_counts, 0, h->n_unitigs * 8 + 8, st) != hipSuccess) return FIN_ENODEV;
-    return hits_mark(h, st, nullptr, 0);
+    return h->pend.reset(st, [&] { return hipMemsetAsync(h->d_counts, 0, h->n_unitigs * 8 + 8, st); });
 }
 
 void* fin_hits_device_counts(const fin_hits* h) { return h ? h->d_counts : nullptr; }
@@ -1774,6 +1813,7 @@ int fin_batch_add_hits(fin_batch* b, fin_hits* h, void* hip_stream, char* err, s
     if (!b || !h) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     hipStream_t st = (hipStream_t)hip_stream;
     if (const int brc = acc_behind_run(b, h->idx, h->device, st, err, errlen)) return brc;
+    if (const int orc = h->pend.behind_reset(st, err, errlen)) return orc;
     const int rc = fin_launch_hits_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, h->d_counts,
                                        (uint32_t)h->n_unitigs, hits_flags(h), b->d_ovf_count, b->last_ovf_cap, (uint32_t)optv(b->idx, O_hits_combine), st);
     if (rc != 0) { set_err(err, errlen, std::string("hits kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
@@ -1847,8 +1887,7 @@ int fin_labels_reset(fin_labels* l, void* hip_stream) {
     if (!l) return FIN_EINVAL;
     if (hipSetDevice(l->device) != hipSuccess) return FIN_ENODEV;
     hipStream_t st = (hipStream_t)hip_stream;
-    if (hipMemsetAsync(l->d_reads, 0, ((size_t)l->n_labels + 1) * 8, st) != hipSuccess) return FIN_ENODEV;
-    return l->pend.mark(st, nullptr, 0);
+    return l->pend.reset(st, [&] { return hipMemsetAsync(l->d_reads, 0, ((size_t)l->n_labels + 1) * 8, st); });
 }
 
 void* fin_labels_device_labels(const fin_labels* l) { return l ? l->d_labels : nullptr; }
@@ -1903,6 +1942,7 @@ int fin_batch_add_classes(fin_batch* b, fin_labels* l, uint32_t min_found, uint3
     if (!b->cls_ready || b->cls_labels != l->serial) if (const int rc = fin_batch_classify(b, l, err, errlen)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (const int brc = acc_behind_run(b, l->idx, l->device, st, err, errlen)) return brc;
+    if (const int orc = l->pend.behind_reset(st, err, errlen)) return orc;
     if (st != b->last_stream) {   // the classes were made on the run's stream, behind the run: the add waits for them too
         hipEvent_t ev = nullptr;
         HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -2028,8 +2068,7 @@ int fin_colors_reset(fin_colors* c, void* hip_stream) {
     if (!c) return FIN_EINVAL;
     if (hipSetDevice(c->device) != hipSuccess) return FIN_ENODEV;
     hipStream_t st = (hipStream_t)hip_stream;
-    if (hipMemsetAsync(c->d_bits, 0, colors_bytes(c) + 8, st) != hipSuccess) return FIN_ENODEV;
-    return c->pend.mark(st, nullptr, 0);
+    return c->pend.reset(st, [&] { return hipMemsetAsync(c->d_bits, 0, colors_bytes(c) + 8, st); });
 }
 
 void* fin_colors_device_bits(const fin_colors* c) { return c ? c->d_bits : nullptr; }
@@ -2057,6 +2096,7 @@ int fin_batch_add_colors(fin_batch* b, fin_colors* c, uint32_t color, void* hip_
     if (color >= c->n_colors) { set_err(err, errlen, "colour " + std::to_string(color) + " is not below n_colors = " + std::to_string(c->n_colors)); return FIN_EINVAL; }
     hipStream_t st = (hipStream_t)hip_stream;
     if (const int brc = acc_behind_run(b, c->idx, c->device, st, err, errlen)) return brc;
+    if (const int orc = c->pend.behind_reset(st, err, errlen)) return orc;
     if (b->n_kmers != 0) {   // (no read has a k-mer: the step searched nothing)
         const int rc = fin_launch_colors_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->dev.k, c->d_bits, c->words,
                                              (uint32_t)c->n_unitigs, color, colors_flags(c), b->d_ovf_count, b->last_ovf_cap, st);
@@ -2272,8 +2312,7 @@ int fin_cover_reset(fin_cover* c, void* hip_stream) {
     if (!c) return FIN_EINVAL;
     if (hipSetDevice(c->device) != hipSuccess) return FIN_ENODEV;
     hipStream_t st = (hipStream_t)hip_stream;
-    if (hipMemsetAsync(c->d_bits, 0, c->n_words * 8 + 8, st) != hipSuccess) return FIN_ENODEV;
-    return c->pend.mark(st, nullptr, 0);
+    return c->pend.reset(st, [&] { return hipMemsetAsync(c->d_bits, 0, c->n_words * 8 + 8, st); });
 }
 
 void* fin_cover_device_bits(const fin_cover* c) { return c ? c->d_bits : nullptr; }
@@ -2282,6 +2321,7 @@ int fin_batch_add_cover(fin_batch* b, fin_cover* c, void* hip_stream, char* err,
     if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     hipStream_t st = (hipStream_t)hip_stream;
     if (const int brc = acc_behind_run(b, c->idx, c->device, st, err, errlen)) return brc;
+    if (const int orc = c->pend.behind_reset(st, err, errlen)) return orc;
     const int rc = fin_launch_cover_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, c->d_ends,
                                         (uint32_t)c->n_unitigs, c->total_len, c->d_bits, cover_flags(c), b->d_ovf_count, b->last_ovf_cap,
                                         (uint32_t)optv(b->idx, O_cover_probe), st);
@@ -2431,8 +2471,7 @@ int fin_depth_reset(fin_depth* d, void* hip_stream) {
     if (!d) return FIN_EINVAL;
     if (hipSetDevice(d->device) != hipSuccess) return FIN_ENODEV;
     hipStream_t st = (hipStream_t)hip_stream;
-    if (hipMemsetAsync(d->d_diff, 0, depth_bytes(d), st) != hipSuccess) return FIN_ENODEV;
-    return d->pend.mark(st, nullptr, 0);
+    return d->pend.reset(st, [&] { return hipMemsetAsync(d->d_diff, 0, depth_bytes(d), st); });
 }
 
 void* fin_depth_device_diff(const fin_depth* d) { return d ? d->d_diff : nullptr; }
@@ -2441,6 +2480,7 @@ int fin_batch_add_depth(fin_batch* b, fin_depth* d, void* hip_stream, char* err,
     if (!b || !d) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     hipStream_t st = (hipStream_t)hip_stream;
     if (const int brc = acc_behind_run(b, d->idx, d->device, st, err, errlen)) return brc;
+    if (const int orc = d->pend.behind_reset(st, err, errlen)) return orc;
     const int rc = fin_launch_depth_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, d->d_ends,
                                         (uint32_t)d->n_unitigs, d->total_len, d->d_diff, depth_flags(d), b->d_ovf_count, b->last_ovf_cap, st);
     if (rc != 0) { set_err(err, errlen, std::string("depth kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }

@@ -368,6 +368,10 @@ int fin_batch_run_info(const fin_batch* b, uint32_t out[4]);
 /* Diagnostic: the most recent run's packed 2-bit chunks (16 bytes each, both strands of every read; with the fused ingest -- option "fused_ingest",
  * the fast pre-pass packs the reads itself -- only the chunks of reads whose verdict is not "finished by the fast path" are defined) and its
  * pre-pass verdicts (two words per read).  *fused = 1 when that run used the fused ingest.  Either buffer may be NULL. */
+/* Diagnostic (tests of the stream contract): the side stream on which option "overlap_prefill" prefills the output of a kernel-4 run (a hipStream_t the batch
+ * owns, created here if no run has made it yet; NULL on error).  Work a test queues on it sits in front of the next run's prefill: the pipeline's first writer
+ * must wait for both. */
+void* fin_batch_debug_side_stream(fin_batch* b);
 int fin_batch_debug_ingest(const fin_batch* b, uint32_t* fused, void* chunks, uint64_t n_chunks, uint32_t* pass, uint64_t n_pass_words);
 
 /* ---- partitioned indexes (fin_pindex): unitig sets beyond 2^32 nodes (round 5) ----------------------------------------------------------------------
@@ -463,7 +467,10 @@ int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32
 typedef struct fin_hits fin_hits;
 /* zeroed counts for `idx` on `device` (FIN_ENODEV: the index has no replica there) */
 int fin_hits_create(const fin_index* idx, int device, fin_hits** out, char* err, size_t errlen);
-/* zeroes the counts, on the given stream */
+/* zeroes the counts, on the given stream; does not wait.  A reset does not commute with the adds, so the library orders it, for this and every other accumulator
+ * (fin_cover, fin_depth, fin_labels, fin_colors): it runs behind every add and reset issued so far, whichever streams they were given, and every add issued
+ * after it runs behind it -- calls take effect in the order they were issued, also when they come from several host threads (a reset is one step under the
+ * accumulator's lock).  Adds on different streams stay unordered among themselves (they commute). */
 int fin_hits_reset(fin_hits* h, void* hip_stream);
 /* counts += the hits of the batch's most recent run, on the given stream, ordered behind that run; does not wait.  Every call adds: the same run added twice
  * counts twice (that is the caller's business).  Reads the run's records and pairs as they stand and changes neither: fin_batch_records,
@@ -507,7 +514,7 @@ int fin_records_unitig_counts(const fin_read_record* recs, uint64_t n_reads, con
 typedef struct fin_cover fin_cover;
 /* a zeroed bitmap for `idx` on `device` (FIN_ENODEV: the index has no replica there) */
 int fin_cover_create(const fin_index* idx, int device, fin_cover** out, char* err, size_t errlen);
-/* zeroes the bitmap, on the given stream */
+/* zeroes the bitmap, on the given stream; does not wait; ordered against the adds as fin_hits_reset is */
 int fin_cover_reset(fin_cover* c, void* hip_stream);
 /* bits |= the found places of the batch's most recent run, on the given stream, ordered behind that run; does not wait.  Same ordering and refusal rules as
  * fin_batch_add_hits: FIN_EINVAL when the batch has not run or batch and accumulator belong to different indexes or devices; records, pairs and text are read
@@ -553,7 +560,7 @@ typedef struct fin_depth fin_depth;
 typedef struct fin_depth_stat { uint64_t sum; uint32_t max; uint32_t n_at_least; } fin_depth_stat;   /* 16 bytes */
 /* a zeroed accumulator for `idx` on `device` (FIN_ENODEV: the index has no replica there) */
 int fin_depth_create(const fin_index* idx, int device, fin_depth** out, char* err, size_t errlen);
-/* zeroes the accumulator, on the given stream */
+/* zeroes the accumulator, on the given stream; does not wait; ordered against the adds as fin_hits_reset is */
 int fin_depth_reset(fin_depth* d, void* hip_stream);
 /* depth += the found places of the batch's most recent run: one launch on the given stream, ordered behind that run; does not wait.  fin_batch_add_cover's
  * ordering and refusal rules: FIN_EINVAL when the batch has not run or batch and accumulator belong to different indexes or devices; records, pairs and text are
@@ -691,7 +698,7 @@ typedef struct fin_labels fin_labels;
 /* a labelling beside the replica on `device`, with its zeroed tally: unitig_labels[fin_index_n_unitigs], copied.  FIN_EINVAL: n_labels is 0 or above 2^31, or a
  * label >= n_labels that is not FIN_NO_LABEL (the message names the unitig).  FIN_ENODEV: no replica on that device. */
 int fin_labels_create(const fin_index* idx, int device, const uint32_t* unitig_labels, uint32_t n_labels, fin_labels** out, char* err, size_t errlen);
-int fin_labels_reset(fin_labels* l, void* hip_stream);   /* zeroes the tally only (asynchronous on hip_stream); the labelling stays */
+int fin_labels_reset(fin_labels* l, void* hip_stream);   /* zeroes the tally only (asynchronous on hip_stream; ordered against the adds as fin_hits_reset is); the labelling stays */
 void* fin_labels_device_labels(const fin_labels* l);     /* uint32[fin_index_n_unitigs] in HBM */
 void* fin_labels_device_reads(const fin_labels* l);      /* the tally, uint64[n_labels + 1] in HBM (valid once the adds on their streams have finished) */
 /* waits for every add and reset issued so far; reads_out[n_labels + 1] (may be NULL): the reads assigned to each label, then the unassigned ones; *total (may be
@@ -711,7 +718,10 @@ int fin_batch_download_read_classes(fin_batch* b, fin_read_class* out, char* err
 /* The tally: read r is ASSIGNED to its class's label when n_best >= max(min_found, 1), 1000 * n_best >= min_permille * nk and n_best >= n_second + min_margin,
  * in 64-bit arithmetic, nk = the read's number of output slots; reads[label] += 1 then, reads[n_labels] += 1 otherwise -- the tally's sum is the number of reads
  * added.  min_margin = 1 leaves ties unassigned.  Makes the classes if they are not there for this labelling; the add runs on hip_stream, ordered behind the run,
- * as fin_batch_add_hits does; adding twice counts twice.  min_permille is 0 .. 1000, else FIN_EINVAL. */
+ * as fin_batch_add_hits does; adding twice counts twice.  min_permille is 0 .. 1000, else FIN_EINVAL.  Unlike the other adds this one WAITS for the run when it has to
+ * make the classes and nobody has fetched the run's overflow verdict yet (fin_batch_classify decides FIN_ELIMIT on the host: the tally has no flag of its own);
+ * behind any reader of that run -- a download, fin_batch_records, fin_batch_classify -- or with the classes made, it does not wait: the classes are made on the
+ * run's stream, the tally on hip_stream behind an event recorded there. */
 int fin_batch_add_classes(fin_batch* b, fin_labels* l, uint32_t min_found, uint32_t min_permille, uint32_t min_margin, void* hip_stream, char* err, size_t errlen);
 /* host buffers in: fin_search_batch's pipeline over sub-batches, each run in text mode 2 where the fast path is on (as fin_search_batch_read_summaries does) and
  * classified / tallied on the device behind its run, on the labelling's device.  out[n_reads]; *n_positive (may be NULL) = the labelled k-mers found (the sum of
@@ -751,7 +761,7 @@ int fin_colors_create(const fin_index* idx, int device, uint32_t n_colors, fin_c
 /* replaces the matrix (waits for every add issued so far): bits[fin_index_n_unitigs * fin_colors_words].  FIN_EINVAL if any bit at or above n_colors is set; the
  * message names the unitig. */
 int fin_colors_upload(fin_colors* c, const uint64_t* bits, char* err, size_t errlen);
-int fin_colors_reset(fin_colors* c, void* hip_stream);   /* zeroes the matrix (asynchronous on hip_stream) */
+int fin_colors_reset(fin_colors* c, void* hip_stream);   /* zeroes the matrix (asynchronous on hip_stream; ordered against the adds as fin_hits_reset is) */
 void* fin_colors_device_bits(const fin_colors* c);       /* uint64[fin_index_n_unitigs * fin_colors_words] in HBM */
 uint32_t fin_colors_n_colors(const fin_colors* c);
 uint32_t fin_colors_words(const fin_colors* c);          /* W */

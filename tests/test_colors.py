@@ -409,3 +409,51 @@ def test_refusals_on_the_device(set31):
         fa.FinimizerIndex.build(unitigs[:5], 31).colors(5)
     assert e.value.code == fa.FIN_ENODEV
     foreign.close(); p2.close(); b.close(); col.close()
+
+
+def test_a_withheld_step_colours_nothing_has_no_rows_and_is_reported_until_the_reset():
+    """a step whose overflow list overran (tests/test_unitig_coverage.py::test_a_withheld_step_sets_nothing_and_is_reported_until_the_reset's recipe) has no
+    results: Colors.add reads the counter itself, sets no bit and flags the matrix -- fin_colors_download reports FIN_ELIMIT until the reset --, pseudoalign
+    reports FIN_ELIMIT and writes no row; after the reset the matrix is clean and a good step coloured and pseudoaligned is exact"""
+    from tests.util import sample_reads
+    k = 31
+    rng = np.random.default_rng(11)
+    g = random_genome(rng, 40000)
+    unitigs = cut_unitigs(rng, g, k, max_len=500)
+    p = fa.FinimizerIndex.build(unitigs, k).to_device(0)
+    o = OracleIndex.build(unitigs, k)
+    reads = sample_reads(rng, g, 500, 150)
+    e1 = oracle_pairs(o, reads)
+    member = np.zeros((p.n_unitigs, 5), dtype=np.uint8); member[np.unique(e1[e1[:, 0] >= 0, 0]), 3] = 1
+    want = pack_members(member)
+    L = fa.lib()
+    col, other = p.colors(5), p.colors(5, random_matrix(rng, len(unitigs), 5))
+    try:
+        assert L.fin_set_option(b"lds_deque_limit", 1) == 0 and L.fin_set_option(b"seed_anchors", 0) == 0 and L.fin_set_option(b"debug_ovf_cap", 3) == 0
+        for mode in (0, 2):
+            b = p.batch(reads); b.text_mode(mode); b.run(fa.FIN_MERGED)
+            col.add(b, 3)                              # nobody has looked at the step's overflow counter yet: the kernel does
+            with pytest.raises(fa.FinitoError) as e:
+                col.download()
+            assert e.value.code == fa.FIN_ELIMIT and "overflow list" in str(e.value)
+            with pytest.raises(fa.FinitoError) as e:   # ... and keeps saying so
+                col.download()
+            assert e.value.code == fa.FIN_ELIMIT
+            bits, n_set = col.reset().download()
+            assert n_set == 0 and not bits.any(), "a withheld step set colours (mode %d)" % mode
+            with pytest.raises(fa.FinitoError) as e:
+                b.pseudoalign(other)
+            assert e.value.code == fa.FIN_ELIMIT and "overflow list" in str(e.value) and b.device_pseudo_ptrs() == (0, 0)
+            with pytest.raises(fa.FinitoError) as e:   # once the host knows, the add itself refuses
+                col.add(b, 3)
+            assert e.value.code == fa.FIN_ELIMIT and col.download()[1] == 0
+            b.close()
+        assert L.fin_set_option(b"debug_ovf_cap", 0) == 0
+        b = p.batch(reads); b.text_mode(2); b.run(fa.FIN_MERGED)
+        bits, n_set = col.add(b, 3).download()
+        assert np.array_equal(bits, want) and n_set == int(member.sum()) > 0, "a good step after the reset"
+        assert_pseudo(b.pseudoalign(col), rows_of(e1, nks_of(reads, k), want, 5, 1000), "a good step after the reset")
+        b.close()
+    finally:
+        L.fin_set_option(b"lds_deque_limit", 16); L.fin_set_option(b"seed_anchors", 1); L.fin_set_option(b"debug_ovf_cap", 0)
+        col.close(); other.close(); p.close()

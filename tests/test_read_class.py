@@ -367,3 +367,43 @@ def test_unitig_numbers(set31):
         with pytest.raises(fa.FinitoError) as e:   # shorter than k; begins inside a unitig; not in the index at all
             p.unitig_numbers(bad)
         assert e.value.code == fa.FIN_EINVAL and word in str(e.value)
+
+
+def test_a_withheld_step_has_no_classes_and_tallies_nothing():
+    """a step whose overflow list overran (tests/test_segments.py::test_a_withheld_step_has_no_segments' recipe) has no results: classify and Labels.add -- which
+    makes the classes -- report FIN_ELIMIT, no class is written and the tally stays empty; a good step tallied afterwards is exact"""
+    from tests.util import sample_reads
+    k = 31
+    rng = np.random.default_rng(11)
+    g = random_genome(rng, 40000)
+    unitigs = cut_unitigs(rng, g, k, max_len=500)
+    p = fa.FinimizerIndex.build(unitigs, k).to_device(0)
+    o = OracleIndex.build(unitigs, k)
+    reads = sample_reads(rng, g, 500, 150)
+    nks = nks_of(reads, k)
+    labels = run_labelling(rng, len(unitigs))
+    want = classes_of(oracle_pairs(o, reads), nks, labels)
+    L = fa.lib()
+    lab = p.labels(labels)
+    try:
+        assert L.fin_set_option(b"lds_deque_limit", 1) == 0 and L.fin_set_option(b"seed_anchors", 0) == 0 and L.fin_set_option(b"debug_ovf_cap", 3) == 0
+        for mode in (0, 2):
+            for first in (lambda: lab.add(b), lambda: b.classify(lab)):   # either may be the first to look at the step's overflow counter
+                b = p.batch(reads); b.text_mode(mode); b.run(fa.FIN_MERGED)
+                for call in (first, lambda: lab.add(b), lambda: b.classify(lab)):
+                    with pytest.raises(fa.FinitoError) as e:
+                        call()
+                    assert e.value.code == fa.FIN_ELIMIT and "overflow list" in str(e.value)
+                assert b.device_read_classes_ptr() == 0
+                tally, total = lab.download()
+                assert total == 0 and not tally.any(), "a withheld step was tallied (mode %d)" % mode
+                b.close()
+        assert L.fin_set_option(b"debug_ovf_cap", 0) == 0
+        b = p.batch(reads); b.text_mode(2); b.run(fa.FIN_MERGED)
+        tally, total = lab.add(b).download()
+        assert np.array_equal(tally, tally_of(want, nks, lab.n_labels, 1, 0, 0)) and total == len(reads), "a good step afterwards"
+        assert_classes(b.classify(lab), want, "a good step afterwards")
+        b.close()
+    finally:
+        L.fin_set_option(b"lds_deque_limit", 16); L.fin_set_option(b"seed_anchors", 1); L.fin_set_option(b"debug_ovf_cap", 0)
+        lab.close(); p.close()

@@ -89,3 +89,47 @@ def test_records_of_a_batch_expand_to_the_pairs():
         assert (recs["meta"] >> 16 == 0).all()
         assert np.array_equal(fa.expand_records(recs, stream, k)[0].astype(np.int64), o.search_batch(reads[:400])[0])
         p.close()
+
+
+@pytest.mark.gpu
+def test_a_withheld_step_has_no_records_and_no_text():
+    """a step whose overflow list overran (tests/test_segments.py::test_a_withheld_step_has_no_segments' recipe) has no results: records() and text() report
+    FIN_ELIMIT, no stream is gathered and no text formatted; a good step afterwards gives the oracle's pairs and text"""
+    from oracle.oracle import OracleIndex, format_pairs
+    from tests.util import cut_unitigs, random_genome, sample_reads
+    C = fa.C
+    k = 31
+    rng = np.random.default_rng(11)
+    g = random_genome(rng, 40000)
+    unitigs = cut_unitigs(rng, g, k, max_len=500)
+    p = fa.FinimizerIndex.build(unitigs, k).to_device(0)
+    o = OracleIndex.build(unitigs, k)
+    reads = sample_reads(rng, g, 500, 150)
+    exp = o.search_batch(reads, n_threads=8)[0]
+    nk = 150 - k + 1
+    want_text = "".join(format_pairs(exp[r * nk:(r + 1) * nk]) for r in range(len(reads))).encode()
+    L = fa.lib()
+    err = C.create_string_buffer(512)
+    try:
+        assert L.fin_set_option(b"lds_deque_limit", 1) == 0 and L.fin_set_option(b"seed_anchors", 0) == 0 and L.fin_set_option(b"debug_ovf_cap", 3) == 0
+        for mode in (0, 1, 2):
+            b = p.batch(reads); b.text_mode(mode); b.run(fa.FIN_MERGED)
+            for call in (b.records, b.text, b.records):
+                with pytest.raises(fa.FinitoError) as e:
+                    call()
+                assert e.value.code == fa.FIN_ELIMIT and "overflow list" in str(e.value)
+            # nothing was made: no stream to download, no text length reported
+            recs, stream = np.zeros(len(reads), dtype=fa.RECORD_DTYPE), np.zeros((len(exp), 2), dtype=np.int32)
+            assert L.fin_batch_download_records(b.h, recs.ctypes.data_as(C.c_void_p), stream.ctypes.data_as(C.c_void_p), err, 512) == fa.FIN_EINVAL
+            n = C.c_uint64(12345)
+            assert L.fin_batch_format_text(b.h, C.byref(n), err, 512) == fa.FIN_ELIMIT and n.value == 12345
+            assert not recs.view(np.uint8).any() and not stream.any()
+            b.close()
+        assert L.fin_set_option(b"debug_ovf_cap", 0) == 0
+        b = p.batch(reads); b.text_mode(2); b.run(fa.FIN_MERGED)
+        recs, stream = b.records()
+        assert np.array_equal(brute_expand(recs, stream, k).astype(np.int64), exp) and b.text() == want_text, "a good step afterwards"
+        b.close()
+    finally:
+        L.fin_set_option(b"lds_deque_limit", 16); L.fin_set_option(b"seed_anchors", 1); L.fin_set_option(b"debug_ovf_cap", 0)
+        p.close()

@@ -282,6 +282,50 @@ def test_wrong_pairing_is_refused_and_the_device_stays_usable(set31):
     b.close(); h.close(); h_other.close(); other.close()
 
 
+def test_a_withheld_step_adds_nothing_and_is_reported_until_the_reset():
+    """a step whose overflow list overran (tests/test_unitig_coverage.py::test_a_withheld_step_sets_nothing_and_is_reported_until_the_reset's recipe) has no
+    results: the add reads the counter itself, counts nothing and flags the accumulator; fin_hits_download reports FIN_ELIMIT until the reset, after which the
+    accumulator is clean and usable"""
+    k = 31
+    rng = np.random.default_rng(11)
+    g = random_genome(rng, 40000)
+    unitigs = cut_unitigs(rng, g, k, max_len=500)
+    p = fa.FinimizerIndex.build(unitigs, k).to_device(0)
+    o = OracleIndex.build(unitigs, k)
+    reads = sample_reads(rng, g, 500, 150)
+    want = expected(o, reads, p.n_unitigs)
+    L = fa.lib()
+    h = p.hits()
+    try:
+        assert L.fin_set_option(b"lds_deque_limit", 1) == 0 and L.fin_set_option(b"seed_anchors", 0) == 0 and L.fin_set_option(b"debug_ovf_cap", 3) == 0
+        for mode in (0, 2):
+            b = p.batch(reads); b.text_mode(mode); b.run(fa.FIN_MERGED)
+            h.add(b)                                   # nobody has looked at the step's overflow counter yet: the kernel does
+            with pytest.raises(fa.FinitoError) as e:
+                h.download()
+            assert e.value.code == fa.FIN_ELIMIT and "overflow list" in str(e.value)
+            with pytest.raises(fa.FinitoError) as e:   # ... and keeps saying so
+                h.download()
+            assert e.value.code == fa.FIN_ELIMIT
+            counts, total = h.reset().download()
+            assert total == 0 and not counts.any(), "a withheld step was counted (mode %d)" % mode
+            with pytest.raises(fa.FinitoError) as e:   # once the host knows (a download looked), the add itself refuses
+                b.download(want_pairs=False) if mode == 0 else b.text()
+            assert e.value.code == fa.FIN_ELIMIT
+            with pytest.raises(fa.FinitoError) as e:
+                h.add(b)
+            assert e.value.code == fa.FIN_ELIMIT and "overflow list" in str(e.value)
+            assert h.download()[1] == 0
+            b.close()
+        assert L.fin_set_option(b"debug_ovf_cap", 0) == 0
+        b = p.batch(reads); b.text_mode(2); b.run(fa.FIN_MERGED)
+        assert_profile(*h.add(b).download(), want, "a good step after the reset")
+        b.close()
+    finally:
+        L.fin_set_option(b"lds_deque_limit", 16); L.fin_set_option(b"seed_anchors", 1); L.fin_set_option(b"debug_ovf_cap", 0)
+        h.close(); p.close()
+
+
 def test_cli_unitig_counts(tmp_path):
     rng = np.random.default_rng(99)
     g = random_genome(rng, 30000)
