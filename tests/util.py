@@ -604,3 +604,198 @@ def yes_reads(text, k, a, b):
         for r in (A[-n:] + piece, piece + A[:n]):
             reads += [r, rc(r)]
     return reads
+
+
+# ---- the enumerated digit case (tests/test_record_digits_host.py asserts its conditions, tests/test_record_digits.py gives it to the device) ----------------------
+# fin_batch_set_records checks neither u nor off0, and text, segments, read summaries and the record gather have no notion of the index: records may name any unitig
+# number up to 2^31 - 1 at any offset.  The kind-1 records here are ENUMERATED -- every digit count of the unitig number against every boundary of the offset at
+# which fin_text.hip's arithmetic changes (a digit more, another H = offset / 1000, H + 1 longer than H), at every nk that puts the boundary into the first group of
+# 128 pairs, at slot 127 / 128 and into the third group -- and thinned by strides, not by drawing; only the searched reads' pairs and the filler positions are drawn.
+DIGIT_K = 31
+INT32_MAX = 2 ** 31 - 1
+DIGIT_NKS = (1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 270)
+DIGIT_NES = (0, 1, 4, 5, 8)
+DIGIT_H_GAINS = (9, 99, 999, 9999, 99999, 999999)      # H + 1 has a digit more than H
+DIGIT_BOUNDARIES = tuple(sorted({10 ** e for e in range(1, 10)} | {2 ** 31, 1000, 2000, 123000, 7654000} | {1000 * (H + 1) for H in DIGIT_H_GAINS}))
+DIGIT_LOW_ENDS = (9, 10, 99, 100, 999)                 # last offsets of reads below 1000: one to three digits and no H
+DIGIT_SHAPES = (7, 8, 3, 4, 1, 7, 8, 5, 0, 6, 2)       # _record_positions' shapes, in the order the enumeration hands them out
+DIGIT_RUN = (512, 768)                                  # the reads of the run on one 6-digit unitig
+DIGIT_RUN_UNITIG = 314159
+DIGIT_LONG = ((4097, 0, 10 ** 6 - 2000), (9001, 0, 10 ** 9 - 5000), (4097, 1, 10 ** 9 - 4000), (9001, 1, 10 ** 6 - 8000))   # (nk, strand, off0)
+DIGIT_LONG_UNITIG = 1987654321
+DIGIT_MAX_READS = 16                                    # per kind: reads of 24-byte pairs only, one made to start at each byte offset modulo 16
+_WAVE_KIND0, _WAVE_KIND2 = (5, 21, 37, 53), (11, 43)    # places inside every wave of 64 reads
+_WAVE_MAX, _WAVE_LONG = (30, 60), 50                    # a 24-byte read (its filler one place in front of it); a long read
+
+
+def digit_unitig_numbers():
+    """per digit count 1..10: the smallest number, one in between, the largest (2^31 - 1 caps the ten-digit ones)"""
+    out = []
+    for n in range(1, 11):
+        lo, hi = (0 if n == 1 else 10 ** (n - 1)), min(10 ** n - 1, INT32_MAX)
+        out += [lo, lo + (hi - lo) * 3 // 7, hi]
+    return out
+
+
+def digit_offsets(nk):
+    """[(off0, P)]: off0 = 0, the reads that end on DIGIT_LOW_ENDS (P None), and the five places against every boundary P; what would leave int32 is left out"""
+    out = [(0, None)] + [(e - nk + 1, None) for e in DIGIT_LOW_ENDS]
+    for P in DIGIT_BOUNDARIES:
+        out += [(o, P) for o in (P - nk, P - nk + 1, P - nk // 2, P - 1, P)]
+    seen, kept = set(), []
+    for o, P in out:
+        if o >= 0 and o + nk - 1 <= INT32_MAX and (o, P) not in seen:
+            seen.add((o, P)); kept.append((o, P))
+    return kept
+
+
+def _positions_at(rng, nk, k, nE, shape, s):
+    """_record_positions and two shapes "around slot s" (s = None: shape 0 instead): 7 a gap that covers slot s, the others anywhere within 2k of it; 8 a gap that
+    ends just before slot s, which stays found (the others lie in front of it)"""
+    top = nk + k - 2
+    if nE == 0 or shape < 7:
+        return _record_positions(rng, nk, k, nE, shape)
+    if s is None or (shape == 8 and s == 0):
+        return _record_positions(rng, nk, k, nE, 0)
+    if shape == 7:
+        E = [s + int(rng.integers(0, k))] + [int(x) for x in rng.integers(max(0, s - 2 * k), s + 2 * k + 1, nE - 1)]
+    else:
+        E = [s - 1] + [int(x) for x in rng.integers(0, s, nE - 1)]
+    return sorted(min(x, top) for x in E)
+
+
+def _set_record(rec, u, off0, nk, rev, Es):
+    rec["u"], rec["off0"], rec["nk"], rec["meta"] = u, off0, nk, len(Es) | (rev << 8) | (1 << 16)
+    rec["Es"] = sum(E << (16 * e) for e, E in enumerate(Es[:4])); rec["Es2"] = sum(E << (16 * e) for e, E in enumerate(Es[4:]))
+
+
+def arbitrary_pairs(rng, n, absent):
+    """the generator of tests/test_search_gpu.py::test_output_text_of_arbitrary_pairs: numbers of 1..10 digits in both fields, a share `absent` of (-1,-1)"""
+    digits = rng.integers(1, 11, (n, 2))
+    vals = np.minimum((10.0 ** (digits - rng.random((n, 2)))).astype(np.int64), INT32_MAX).astype(np.int32)
+    vals[rng.random(n) < absent] = -1
+    return vals
+
+
+def pair_text_len(pairs):
+    """bytes of every pair's text, separator included: int64 [n]"""
+    p = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    nd = lambda v: np.searchsorted(10 ** np.arange(1, 10), np.maximum(v, 0), side="right") + 1
+    return np.where(p[:, 0] < 0, 8, nd(p[:, 0]) + nd(p[:, 1]) + 4)
+
+
+_DIGIT_CASE = None
+
+
+def digit_case():
+    """the one input tests/test_record_digits_host.py (no GPU) and tests/test_record_digits.py face: a 40 000-base genome's index at k = 31, reads whose content is
+    free (they fix nk), and over them
+      - the enumerated kind-1 records: (boundary, place against it, nk, strand) in full, the unitig number and (number of positions, shape) handed out by strides;
+      - reads DIGIT_RUN: kind 1 on ONE 6-digit unitig; four long reads (DIGIT_LONG) on a 10-digit unitig across 10^6 and 10^9;
+      - 2 * DIGIT_MAX_READS reads whose pairs all take 24 bytes -- searched ones of 260 pairs (2147483647,2147483647), finished ones of 257 slots that end on
+        offset 2^31 - 1 of unitig 2^31 - 1 --, each behind a one-pair filler read chosen so that the j-th of its kind starts at byte j modulo 16 of the text;
+      - in every wave of 64 reads outside the run four searched reads of arbitrary_pairs and two kind-2 reads.
+    Namespace: k, unitigs, ends, reads, nks, recs, stream, pairs (brute_expand), boundary (per read: its P or -1).  Made once and shared; nobody changes it"""
+    global _DIGIT_CASE
+    if _DIGIT_CASE is not None:
+        return _DIGIT_CASE
+    from types import SimpleNamespace
+    import finito_amd as fa
+    from oracle.oracle import OracleIndex
+    from tests.test_records import brute_expand
+    k = DIGIT_K
+    rng = np.random.default_rng(7031)
+    g = random_genome(rng, 40000)
+    unitigs = cut_unitigs(rng, g, k, max_len=700)
+    ends = OracleIndex.build(unitigs, k).ends()
+    numbers = digit_unitig_numbers()
+    # the enumeration: boundary and place, nk, strand in full; one unitig number per (place, nk), the same on both strands, by a stride coprime to their count
+    specs = []
+    for nk in DIGIT_NKS:
+        for off0, P in digit_offsets(nk):
+            for rev in (0, 1):
+                specs.append((off0, P, nk, rev))
+    specs.sort(key=lambda x: (x[1] is not None, x[1] or 0, x[0], x[2], x[3]))
+    one = []
+    for i, (off0, P, nk, rev) in enumerate(specs):
+        u = numbers[(11 * (i // 2)) % len(numbers)]
+        nE, shape = DIGIT_NES[i % 5], DIGIT_SHAPES[(i // 5) % len(DIGIT_SHAPES)]
+        s = None
+        if P is not None:   # the slot at P - 1 or at P, alternately, whichever the read has
+            s = [x for x in ((P - 1 - off0, P - off0) if (i // 55) % 2 == 0 else (P - off0, P - 1 - off0)) if 0 <= x < nk]
+            s = s[0] if s else None
+        one.append((u, off0, nk, rev, _positions_at(rng, nk, k, nE, shape, s), -1 if P is None else P))
+    # the layout: kinds 0 and 2 at fixed places of every wave, the run, the 24-byte reads behind their fillers, the long reads; kind 1 everywhere else
+    n_special = 2 * 2 * DIGIT_MAX_READS + len(DIGIT_LONG)
+    per_wave = 64 - len(_WAVE_KIND0) - len(_WAVE_KIND2)
+    n_waves = (len(one) + n_special + per_wave - 1) // per_wave + (DIGIT_RUN[1] - DIGIT_RUN[0]) // 64
+    n = 64 * n_waves
+    run_waves = set(range(DIGIT_RUN[0] // 64, DIGIT_RUN[1] // 64))
+    free = [w for w in range(n_waves) if w not in run_waves]
+    assert len(free) >= DIGIT_MAX_READS + len(DIGIT_LONG)
+    plan = {}
+    for j in range(2 * DIGIT_MAX_READS):   # two per wave: a searched one, a finished one
+        at = 64 * free[j // 2] + _WAVE_MAX[j % 2]
+        plan[at - 1], plan[at] = ("filler", j), ("max0" if j % 2 == 0 else "max1", j // 2)
+    for j, spec in enumerate(DIGIT_LONG):
+        plan[64 * free[len(free) - 1 - j] + _WAVE_LONG] = ("long", spec)
+    recs = np.zeros(n, dtype=fa.RECORD_DTYPE)
+    boundary = np.full(n, -1, dtype=np.int64)
+    stream_of, fillers, maxes = {}, [], []
+    next_one = next_nk = 0
+    for r in range(n):
+        w, at = divmod(r, 64)
+        if DIGIT_RUN[0] <= r < DIGIT_RUN[1]:
+            j = r - DIGIT_RUN[0]
+            nk = DIGIT_NKS[j % len(DIGIT_NKS)]
+            off0 = (999, 9999, 99999, 123456, 999999)[j % 5] - (j % 7) * (nk // 6)
+            _set_record(recs[r:r + 1], DIGIT_RUN_UNITIG, max(off0, 0), nk, (j // 3) % 2, _record_positions(rng, nk, k, DIGIT_NES[j % 5], j % POSITION_SHAPES))
+        elif r in plan:
+            what, arg = plan[r]
+            if what == "filler":
+                recs["nk"][r] = 1; stream_of[r] = np.array([[1, 1]], dtype=np.int32); fillers.append(r)
+            elif what == "max0":
+                recs["nk"][r] = 260 + arg % 11; stream_of[r] = np.full((260 + arg % 11, 2), INT32_MAX, dtype=np.int32); maxes.append(r)
+            elif what == "max1":
+                _set_record(recs[r:r + 1], INT32_MAX, 2 ** 31 - 257, 257, arg % 2, []); maxes.append(r)
+            else:
+                nk, rev, off0 = arg
+                P = 10 ** 6 if off0 < 10 ** 6 else 10 ** 9
+                _set_record(recs[r:r + 1], DIGIT_LONG_UNITIG, off0, nk, rev, _positions_at(rng, nk, k, (0, 8, 5, 4)[DIGIT_LONG.index(arg)], 7, P - off0))
+        elif at in _WAVE_KIND0:
+            nk = DIGIT_NKS[next_nk % len(DIGIT_NKS)]; next_nk += 1
+            recs["nk"][r] = nk; stream_of[r] = arbitrary_pairs(rng, nk, (0.0, 0.3, 0.9)[next_nk % 3])
+        elif at in _WAVE_KIND2:
+            recs["nk"][r] = DIGIT_NKS[next_nk % len(DIGIT_NKS)]; next_nk += 1
+            recs["meta"][r] = 2 << 16
+        else:
+            u, off0, nk, rev, Es, P = one[next_one % len(one)]; next_one += 1   # (the last wave is filled up from the start of the enumeration)
+            _set_record(recs[r:r + 1], u, off0, nk, rev, Es); boundary[r] = P
+    assert next_one >= len(one), "the enumeration did not fit: %d of %d" % (next_one, len(one))
+    # the fillers, in read order: a pair of 6 .. 21 bytes that puts the read behind it at its byte offset modulo 16
+    nks = recs["nk"].astype(np.int64)
+    zero = [r for r in range(n) if int(recs["meta"][r]) >> 16 == 0]
+    stream = np.concatenate([stream_of[r] for r in zero]).astype(np.int32)
+    in_stream = dict(zip(zero, np.concatenate([[0], np.cumsum(nks[zero])])))
+    pairs = brute_expand(recs, stream, k)
+    first = np.concatenate([[0], np.cumsum(nks)])
+    length = np.add.reduceat(pair_text_len(pairs), first[:-1])
+    for f, m in zip(fillers, maxes):
+        assert m == f + 1
+        want = plan[m][1] % 16
+        fill = 6 + (want - int(length[:f].sum()) - 6) % 16
+        nu = min(10, fill - 5)
+        stream[in_stream[f]] = pairs[first[f]] = (10 ** (nu - 1), 10 ** (fill - 4 - nu - 1))
+        length[f] = fill
+    assert np.array_equal(np.add.reduceat(pair_text_len(pairs), first[:-1]), length)
+    for m in maxes:
+        assert int(length[:m].sum()) % 16 == plan[m][1] % 16
+    lens = nks + k - 1
+    bases = rng.integers(0, 4, int(lens.sum()))
+    reads, at = [], 0
+    for L in lens:
+        reads.append("".join("ACGT"[x] for x in bases[at:at + L])); at += int(L)
+    for a in (ends, nks, recs, stream, pairs, boundary):
+        a.setflags(write=False)
+    _DIGIT_CASE = SimpleNamespace(k=k, unitigs=unitigs, ends=ends, reads=reads, nks=nks, recs=recs, stream=stream, pairs=pairs, boundary=boundary)
+    return _DIGIT_CASE
