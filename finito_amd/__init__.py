@@ -247,6 +247,17 @@ def lib():
         L.fin_batch_download_pseudo.argtypes = [vp, u64p, vp, cp, C.c_size_t]
         L.fin_search_batch_pseudoalign.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u64p, vp, u64p, cp, C.c_size_t]
         L.fin_records_pseudoalign.argtypes = [vp, u64, vp, u64, C.c_int, u64p, u64, u32, u32, u64p, vp, C.c_int]
+        L.fin_eqclasses_create.argtypes = [vp, u64, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_eqclasses_reset.argtypes = [vp, vp]
+        L.fin_eqclasses_free.argtypes = [vp]
+        L.fin_eqclasses_free.restype = None
+        L.fin_eqclasses_add_rows.argtypes = [vp, vp, u64, vp, cp, C.c_size_t]
+        L.fin_batch_add_eqclasses.argtypes = [vp, vp, u32, vp, cp, C.c_size_t]
+        L.fin_search_batch_add_eqclasses.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, cp, C.c_size_t]
+        L.fin_eqclasses_download.argtypes = [vp, u64p, u64p, u64, u64p, u64p, cp, C.c_size_t]
+        L.fin_eqclasses_stats.argtypes = [vp, u64p, cp, C.c_size_t]
+        L.fin_rows_eqclasses.argtypes = [u64p, u64, u32, u64p, u64p, u64, u64p, u64p]
+        L.fin_eqclasses_color_tally.argtypes = [u64p, u64p, u64, u32, u64p, u64p]
         _LIB = L
     return _LIB
 
@@ -758,9 +769,108 @@ class Colors:
     def device_ptr(self):
         return int(self.L.fin_colors_device_bits(self.h) or 0)
 
+    def eqclasses(self, max_classes=1 << 20):
+        """an accumulator of equivalence classes beside this matrix (EqClasses)"""
+        return EqClasses(self, max_classes)
+
     def close(self):
         if getattr(self, "h", None):
             self.L.fin_colors_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EqClasses:
+    """the equivalence classes of pseudoaligned reads -- the distinct colour rows the added runs produced and how many reads have each --, accumulated in HBM
+    beside a colour matrix (fin_eqclasses_* of the C ABI).  An all-zero row is an unaligned read and belongs to no class.  At most max_classes (1 .. 2^26)
+    distinct rows; free it before the colours."""
+
+    def __init__(self, colors, max_classes=1 << 20):
+        self.colors = colors
+        self.index = colors.index
+        self.L = lib()
+        self.n_colors = colors.n_colors
+        self.words = colors.words
+        if not 0 <= int(max_classes) <= 0xFFFFFFFFFFFFFFFF:
+            raise FinitoError(FIN_ELIMIT, "eqclasses: max_classes is 1 .. 2^26")
+        self.max_classes = int(max_classes)
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_eqclasses_create(colors.h, self.max_classes, C.byref(h), err, 512), err)
+        self.h = h
+
+    def add(self, batch, permille=1000, stream=None):
+        """the batch's most recent run, pseudoaligned against the colours at `permille` and added, on a HIP stream; no sync (fin_batch_add_eqclasses).  Adding
+        twice counts twice."""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_add_eqclasses(batch.h, self.h, _permille("EqClasses.add", permille), C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add_rows(self, ptr, n_rows, stream=None):
+        """rows any producer left in HBM: a device pointer to uint64[n_rows, W], valid until the add has finished (fin_eqclasses_add_rows)"""
+        if not 0 <= int(n_rows) <= 0xFFFFFFFFFFFFFFFF:
+            raise FinitoError(FIN_EINVAL, "EqClasses.add_rows: n_rows is an unsigned 64-bit number")
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_eqclasses_add_rows(self.h, C.c_void_p(int(ptr) or 0), int(n_rows), C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add_reads(self, reads, permille=1000, strands=FIN_MERGED):
+        """search a read set from host buffers, sub-batches pipelined as in search_reads, and add every read's row; nothing comes back
+        (fin_search_batch_add_eqclasses)"""
+        bases, offsets = flatten(reads)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_add_eqclasses(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+                                                     int(strands), self.h, _permille("EqClasses.add_reads", permille), err, 512), err)
+        return self
+
+    def reset(self, stream=None):
+        """empty the accumulator and clear its flags"""
+        rc = self.L.fin_eqclasses_reset(self.h, C.c_void_p(stream or 0))
+        if rc != 0:
+            raise FinitoError(rc, "fin_eqclasses_reset")
+        return self
+
+    def download(self):
+        """(rows uint64[n, W], reads uint64[n], n_unaligned) in canonical order -- np.unique(rows, axis=0)'s; waits for the adds (fin_eqclasses_download)"""
+        u64p = C.POINTER(C.c_uint64)
+        n, un = C.c_uint64(0), C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        cap = 0
+        rows = np.zeros((1, self.words), dtype=np.uint64)
+        reads = np.zeros(1, dtype=np.uint64)
+        while True:   # the first call learns the number of classes
+            rc = self.L.fin_eqclasses_download(self.h, rows.ctypes.data_as(u64p), reads.ctypes.data_as(u64p), cap, C.byref(n), C.byref(un), err, 512)
+            if rc == FIN_ELIMIT and int(n.value) > cap:
+                cap = int(n.value)
+                rows = np.zeros((cap, self.words), dtype=np.uint64)
+                reads = np.zeros(cap, dtype=np.uint64)
+                n.value = 0
+                continue
+            _check(rc, err)
+            return rows[: int(n.value)], reads[: int(n.value)], int(un.value)
+
+    def tally(self):
+        """(reads_with uint64[n_colors], reads_only uint64[n_colors], n_unaligned): per colour, the reads whose class contains it and the reads whose class
+        is that colour alone -- derived from the classes (fin_eqclasses_color_tally)"""
+        rows, reads, un = self.download()
+        w, o = eqclasses_color_tally(rows, reads, self.n_colors)
+        return w, o, un
+
+    def stats(self):
+        """[rows added, unaligned, classes, rows that went through the serial pass]; waits (fin_eqclasses_stats)"""
+        out = np.zeros(4, dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_eqclasses_stats(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), err, 512), err)
+        return [int(v) for v in out]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fin_eqclasses_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -1622,6 +1732,42 @@ def records_pseudoalign(recs, stream, k, bits, n_colors, permille=1000, n_thread
         raise FinitoError(rc, "fin_records_pseudoalign: n_colors outside 1 .. 4096, permille above 1000, a bit at or above n_colors, a unitig number outside the "
                               "matrix, or records and stream that do not belong together")
     return rows[: len(r)], heads[: len(r)]
+
+
+def rows_eqclasses(rows, n_colors):
+    """host: (class rows uint64[n, W], reads uint64[n], n_unaligned) of rows uint64[n_rows, W] in canonical order (fin_rows_eqclasses) -- the CPU statement of
+    EqClasses"""
+    if not 1 <= int(n_colors) <= 4096:
+        raise FinitoError(FIN_ELIMIT, "rows_eqclasses: n_colors is 1 .. 4096")
+    W = max((int(n_colors) + 63) // 64, 1)
+    a = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, W)
+    u64p = C.POINTER(C.c_uint64)
+    cap = max(len(a), 1)
+    out = np.zeros((cap, W), dtype=np.uint64)
+    reads = np.zeros(cap, dtype=np.uint64)
+    n, un = C.c_uint64(0), C.c_uint64(0)
+    rc = lib().fin_rows_eqclasses(a.ctypes.data_as(u64p), len(a), int(n_colors), out.ctypes.data_as(u64p), reads.ctypes.data_as(u64p), cap, C.byref(n), C.byref(un))
+    if rc != 0:
+        raise FinitoError(rc, "fin_rows_eqclasses: n_colors outside 1 .. 4096, or a row with a bit at or above n_colors")
+    return out[: int(n.value)], reads[: int(n.value)], int(un.value)
+
+
+def eqclasses_color_tally(class_rows, class_reads, n_colors):
+    """host: (reads_with uint64[n_colors], reads_only uint64[n_colors]) of classes {row, reads} (fin_eqclasses_color_tally)"""
+    if not 1 <= int(n_colors) <= 4096:
+        raise FinitoError(FIN_ELIMIT, "eqclasses_color_tally: n_colors is 1 .. 4096")
+    W = max((int(n_colors) + 63) // 64, 1)
+    a = np.ascontiguousarray(class_rows, dtype=np.uint64).reshape(-1, W)
+    r = np.ascontiguousarray(class_reads, dtype=np.uint64).reshape(-1)
+    if len(a) != len(r):
+        raise FinitoError(FIN_EINVAL, "eqclasses_color_tally: %d rows and %d counts" % (len(a), len(r)))
+    u64p = C.POINTER(C.c_uint64)
+    w = np.zeros(max(int(n_colors), 1), dtype=np.uint64)
+    o = np.zeros(max(int(n_colors), 1), dtype=np.uint64)
+    rc = lib().fin_eqclasses_color_tally(a.ctypes.data_as(u64p), r.ctypes.data_as(u64p), len(a), int(n_colors), w.ctypes.data_as(u64p), o.ctypes.data_as(u64p))
+    if rc != 0:
+        raise FinitoError(rc, "fin_eqclasses_color_tally: n_colors outside 1 .. 4096, or a class with a bit at or above n_colors")
+    return w[: int(n_colors)], o[: int(n_colors)]
 
 
 def format_pairs(pairs):

@@ -94,7 +94,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -129,6 +129,8 @@ static const OptDef OPTS[O_COUNT] = {
     {"hits_combine", 4, 0, 64},                    // fin_batch_add_hits: what a wave sums before an add goes to memory (fin_hits.hip) -- rounds in which the record lanes of one unitig merge, and the run held back between rows of pairs; 0 = every record lane and every run of a row adds by itself
     {"cover_probe", 0, 0, 1},                      // fin_batch_add_cover: 1 = a lane loads the bitmap word first and skips the atomic OR when every bit it would set is set already (exact: bits are only ever set between resets, fin_cover.hip); 0 = always OR.  Measured (profiles/r09/cover.md): 1 wins behind text-mode-2 steps once the bitmap fills (0.83 against 1.14 ms on chr1), 0 behind default steps (4.0 against 5.0 ms) and summed over both
     {"debug_depth_tile", 0, 0, 4096},              // tests: fin_depth_download's prefix sum in tiles of this many elements and chunks of 64 tiles (0: tiles of 4096 elements, chunks of 4096 tiles)
+    {"ec_tag_bits", 63, 1, 63},                    // fin_eqclasses: bits of a row's tag in the table (fin_eqclasses.hip); tests narrow it so that distinct rows share tags and go through the serial pass.  Read by the first add after the accumulator's creation or reset and kept until the next reset: a table's tags are made one way
+    {"ec_combine", 1, 0, 1},                       // fin_eqclasses' count pass: 1 = a wave's adds combined over its distinct slots, one atomic each; 0 = one atomic per row (tools/ab_eqclasses.py measures both)
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -2207,6 +2209,209 @@ int fin_records_pseudoalign(const fin_read_record* recs, uint64_t n_reads, const
     return ok ? FIN_OK : FIN_EINVAL;
 }
 
+// ---- equivalence classes of pseudoaligned reads (fin_eqclasses.hip) ---------------------------------------------------------------------
+struct fin_eqclasses {
+    const fin_colors* colors = nullptr;
+    const fin_index* idx = nullptr;
+    int device = -1;
+    uint32_t n_colors = 0, words = 0, lg = 0;
+    uint64_t max_classes = 0, slots = 0;
+    void* d_tab = nullptr;      // ctr uint64[8] | tags uint64[slots] | counts uint64[slots] | rows uint64[slots * words]
+    void* d_scratch = nullptr;  // slot_of uint32[cap_rows] | coll uint32[cap_rows]: kept and only grown
+    size_t cap_rows = 0;
+    uint32_t tag_bits = 0;      // option "ec_tag_bits" as the first add since the creation or the last reset read it (0: none yet)
+    std::mutex mu;              // an add (order, three launches, mark) and a reset are one step each: calls from several host threads take effect in issue order
+    AccPending pend;
+};
+static uint64_t* ec_ctr(const fin_eqclasses* e) { return (uint64_t*)e->d_tab; }
+static uint64_t* ec_tags(const fin_eqclasses* e) { return (uint64_t*)e->d_tab + 8; }
+static uint64_t* ec_counts(const fin_eqclasses* e) { return ec_tags(e) + e->slots; }
+static uint64_t* ec_rows(const fin_eqclasses* e) { return ec_counts(e) + e->slots; }
+static size_t ec_zero_bytes(const fin_eqclasses* e) { return (size_t)(8 + 2 * e->slots) * 8; }   // (a slot's row is written when the slot is claimed)
+
+void fin_eqclasses_free(fin_eqclasses* e) {
+    if (!e) return;
+    if (e->device >= 0) (void)hipSetDevice(e->device);
+    e->pend.drop();
+    (void)hipFree(e->d_tab); (void)hipFree(e->d_scratch);
+    delete e;
+}
+
+int fin_eqclasses_create(const fin_colors* c, uint64_t max_classes, fin_eqclasses** out, char* err, size_t errlen) {
+    if (!c || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (max_classes == 0 || max_classes > (1ull << 26)) { set_err(err, errlen, "max_classes is 1 .. 2^26"); return FIN_ELIMIT; }
+    HIPCHK(hipSetDevice(c->device));
+    fin_eqclasses* e = new (std::nothrow) fin_eqclasses();
+    if (!e) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
+    e->colors = c; e->idx = c->idx; e->device = c->device; e->n_colors = c->n_colors; e->words = c->words; e->max_classes = max_classes;
+    e->lg = 1;
+    while ((1ull << e->lg) < 2 * max_classes) e->lg++;
+    e->slots = 1ull << e->lg;
+    const size_t bytes = ec_zero_bytes(e) + (size_t)e->slots * e->words * 8;
+    if (hipMalloc(&e->d_tab, bytes) != hipSuccess) { (void)hipGetLastError(); delete e; set_err(err, errlen, "out of device memory (table of equivalence classes)"); return FIN_ENOMEM; }
+    if (hipMemset(e->d_tab, 0, ec_zero_bytes(e)) != hipSuccess) { fin_eqclasses_free(e); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    *out = e;
+    return FIN_OK;
+}
+
+int fin_eqclasses_reset(fin_eqclasses* e, void* hip_stream) {
+    if (!e) return FIN_EINVAL;
+    if (hipSetDevice(e->device) != hipSuccess) return FIN_ENODEV;
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::lock_guard<std::mutex> g(e->mu);
+    e->tag_bits = 0;
+    return e->pend.reset(st, [&] { return hipMemsetAsync(e->d_tab, 0, ec_zero_bytes(e), st); });
+}
+
+// the add proper, on `st`: behind every add and reset issued so far, whichever streams they were given
+static int ec_add_rows(fin_eqclasses* e, const void* d_rows, uint64_t n_rows, hipStream_t st, char* err, size_t errlen) {
+    if (n_rows >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 rows in one add"); return FIN_ELIMIT; }
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n_rows > e->cap_rows) {   // (the adds under way use the old scratch)
+        if (const int wrc = e->pend.wait(err, errlen)) return wrc;
+        (void)hipFree(e->d_scratch); e->d_scratch = nullptr; e->cap_rows = 0;
+        const size_t want = (size_t)n_rows + (size_t)n_rows / 8 + 64;
+        if (hipMalloc(&e->d_scratch, want * 8) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (scratch of the equivalence classes)"); return FIN_ENOMEM; }
+        e->cap_rows = want;
+    }
+    if (e->tag_bits == 0) e->tag_bits = (uint32_t)optv(e->idx, O_ec_tag_bits);
+    if (const int orc = e->pend.order(st, err, errlen)) return orc;
+    if (n_rows) {
+        const int rc = fin_launch_ec_add(d_rows, (uint32_t)n_rows, e->words, e->n_colors, ec_tags(e), ec_counts(e), ec_rows(e), e->lg, e->max_classes, e->tag_bits,
+                                         (uint32_t)optv(e->idx, O_ec_combine), ec_ctr(e), (uint32_t*)e->d_scratch, (uint32_t*)e->d_scratch + e->cap_rows, st);
+        if (rc != 0) { set_err(err, errlen, std::string("equivalence class kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    }
+    return e->pend.mark(st, err, errlen);
+}
+
+int fin_eqclasses_add_rows(fin_eqclasses* e, const void* d_rows, uint64_t n_rows, void* hip_stream, char* err, size_t errlen) {
+    if (!e || (n_rows && !d_rows)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    return ec_add_rows(e, d_rows, n_rows, (hipStream_t)hip_stream, err, errlen);
+}
+
+int fin_batch_add_eqclasses(fin_batch* b, fin_eqclasses* e, uint32_t permille, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !e) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    // always: the batch does not remember which matrix and threshold its rows belong to, and the matrix may have changed
+    if (const int rc = fin_batch_pseudoalign(b, e->colors, permille, err, errlen)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (st != b->last_stream) {   // the rows were made on the run's stream, behind the run: the add waits for them
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        hipError_t rc = hipEventRecord(ev, b->last_stream);
+        if (rc == hipSuccess) rc = hipStreamWaitEvent(st, ev, 0);
+        (void)hipEventDestroy(ev);   // (released once it has completed)
+        HIPCHK(rc);
+    }
+    return ec_add_rows(e, b->d_psa_rows, b->n_reads, st, err, errlen);
+}
+
+int fin_eqclasses_stats(fin_eqclasses* e, uint64_t out[4], char* err, size_t errlen) {
+    if (!e || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int wrc = e->pend.wait(err, errlen)) return wrc;
+    HIPCHK(hipMemcpy(out, ec_ctr(e), 32, hipMemcpyDeviceToHost));
+    return FIN_OK;
+}
+
+// canonical order: ascending by word 0, then word 1 ..., unsigned -- np.unique(rows, axis=0)'s.  perm[i] = the i-th class's place in rows
+static void ec_canonical(const uint64_t* rows, uint64_t n, uint32_t W, std::vector<uint64_t>& perm) {
+    perm.resize((size_t)n);
+    for (uint64_t i = 0; i < n; i++) perm[(size_t)i] = i;
+    std::sort(perm.begin(), perm.end(), [&](uint64_t a, uint64_t b) { return std::lexicographical_compare(rows + a * W, rows + a * W + W, rows + b * W, rows + b * W + W); });
+}
+
+int fin_eqclasses_download(fin_eqclasses* e, uint64_t* rows_out, uint64_t* reads_out, uint64_t cap, uint64_t* n_classes, uint64_t* n_unaligned, char* err, size_t errlen) {
+    if (!e || !n_classes || (cap && (!rows_out || !reads_out))) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int wrc = e->pend.wait(err, errlen)) return wrc;
+    uint64_t ctr[8];
+    HIPCHK(hipMemcpy(ctr, ec_ctr(e), sizeof ctr, hipMemcpyDeviceToHost));
+    if (ctr[4] & 1u) { set_err(err, errlen, "a row with a bit at or above n_colors was added (not counted; reset the accumulator)"); return FIN_EINVAL; }
+    if ((ctr[4] & 2u) || ctr[2] > e->max_classes) { set_err(err, errlen, "more than max_classes distinct rows (max_classes = " + std::to_string(e->max_classes) + "; reset the accumulator)"); return FIN_ELIMIT; }
+    // compaction on the device: the occupied slots counted per block, scanned, gathered into a dense list -- the table itself never crosses PCIe
+    const uint32_t W = e->words, nb = fin_ec_blocks((uint32_t)e->slots);
+    void* d_tmp = nullptr; void* d_dense = nullptr;
+    const size_t off_bytes = (size_t)nb * 8 + 8, sum_bytes = (size_t)nb * 4;
+    if (hipMalloc(&d_tmp, off_bytes + sum_bytes) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (compaction of the equivalence classes)"); return FIN_ENOMEM; }
+    uint64_t* const d_off = (uint64_t*)d_tmp; uint64_t* const d_total = d_off + nb; uint32_t* const d_sum = (uint32_t*)((char*)d_tmp + off_bytes);
+    int rc = fin_launch_ec_occupied(ec_tags(e), (uint32_t)e->slots, d_sum, d_off, d_total, nullptr);
+    uint64_t total = 0;
+    hipError_t he = rc == 0 ? hipMemcpy(&total, d_total, 8, hipMemcpyDeviceToHost) : (hipError_t)rc;
+    std::vector<uint64_t> rows, reads;
+    if (he == hipSuccess && total) {
+        rows.resize((size_t)total * W); reads.resize((size_t)total);
+        he = hipMalloc(&d_dense, (size_t)total * (W + 1) * 8);
+        if (he == hipSuccess) {
+            rc = fin_launch_ec_gather(ec_tags(e), ec_counts(e), ec_rows(e), (uint32_t)e->slots, W, d_off, d_dense, (uint64_t*)d_dense + total * W, nullptr);
+            he = rc == 0 ? hipMemcpy(rows.data(), d_dense, (size_t)total * W * 8, hipMemcpyDeviceToHost) : (hipError_t)rc;
+            if (he == hipSuccess) he = hipMemcpy(reads.data(), (uint64_t*)d_dense + total * W, (size_t)total * 8, hipMemcpyDeviceToHost);
+        }
+    }
+    (void)hipFree(d_tmp); (void)hipFree(d_dense);
+    if (he != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, std::string("compaction of the equivalence classes: ") + hipGetErrorString(he)); return FIN_ENODEV; }
+    *n_classes = total;
+    if (n_unaligned) *n_unaligned = ctr[1];
+    if (total > cap) { set_err(err, errlen, "room for " + std::to_string(cap) + " classes, " + std::to_string(total) + " needed"); return FIN_ELIMIT; }
+    std::vector<uint64_t> perm;
+    ec_canonical(rows.data(), total, W, perm);
+    for (uint64_t i = 0; i < total; i++) {
+        memcpy(rows_out + i * W, rows.data() + perm[(size_t)i] * W, (size_t)W * 8);
+        reads_out[i] = reads[(size_t)perm[(size_t)i]];
+    }
+    return FIN_OK;
+}
+
+// host: the CPU statement of the accumulator -- the rows sorted, runs of equal rows counted
+int fin_rows_eqclasses(const uint64_t* rows, uint64_t n_rows, uint32_t n_colors, uint64_t* rows_out, uint64_t* reads_out, uint64_t cap, uint64_t* n_classes,
+                       uint64_t* n_unaligned) {
+    if (n_colors == 0 || n_colors > FIN_MAX_COLORS) return FIN_ELIMIT;
+    if ((n_rows && !rows) || !n_classes || (cap && (!rows_out || !reads_out))) return FIN_EINVAL;
+    const uint32_t W = (n_colors + 63u) / 64u;
+    const uint64_t stray = (n_colors & 63u) ? ~0ull << (n_colors & 63u) : 0ull;
+    std::vector<uint64_t> live;
+    uint64_t n_un = 0;
+    for (uint64_t r = 0; r < n_rows; r++) {
+        const uint64_t* row = rows + r * W;
+        if (row[W - 1] & stray) return FIN_EINVAL;
+        bool ne = false;
+        for (uint32_t w = 0; w < W; w++) if (row[w]) ne = true;
+        if (ne) live.push_back(r); else n_un++;
+    }
+    std::sort(live.begin(), live.end(), [&](uint64_t a, uint64_t b) { return std::lexicographical_compare(rows + a * W, rows + a * W + W, rows + b * W, rows + b * W + W); });
+    uint64_t n = 0;
+    for (size_t i = 0; i < live.size();) {
+        size_t j = i + 1;
+        while (j < live.size() && !memcmp(rows + live[i] * W, rows + live[j] * W, (size_t)W * 8)) j++;
+        if (n < cap) { memcpy(rows_out + n * W, rows + live[i] * W, (size_t)W * 8); reads_out[n] = (uint64_t)(j - i); }
+        n++; i = j;
+    }
+    *n_classes = n;
+    if (n_unaligned) *n_unaligned = n_un;
+    return n > cap ? FIN_ELIMIT : FIN_OK;
+}
+
+// host: reads_with[c] = the reads of the classes that contain colour c; reads_only[c] = the reads of the class {c}
+int fin_eqclasses_color_tally(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, uint64_t* reads_with, uint64_t* reads_only) {
+    if (n_colors == 0 || n_colors > FIN_MAX_COLORS) return FIN_ELIMIT;
+    if ((n_classes && (!class_rows || !class_reads)) || !reads_with || !reads_only) return FIN_EINVAL;
+    const uint32_t W = (n_colors + 63u) / 64u;
+    const uint64_t stray = (n_colors & 63u) ? ~0ull << (n_colors & 63u) : 0ull;
+    for (uint64_t i = 0; i < n_classes; i++) if (class_rows[i * W + (W - 1)] & stray) return FIN_EINVAL;
+    for (uint32_t c = 0; c < n_colors; c++) reads_with[c] = reads_only[c] = 0;
+    for (uint64_t i = 0; i < n_classes; i++) {
+        const uint64_t* row = class_rows + i * W;
+        uint32_t pc = 0, last = 0;
+        for (uint32_t w = 0; w < W; w++)
+            for (uint64_t m = row[w]; m; m &= m - 1) { last = 64u * w + (uint32_t)__builtin_ctzll(m); reads_with[last] += class_reads[i]; pc++; }
+        if (pc == 1u) reads_only[last] += class_reads[i];
+    }
+    return FIN_OK;
+}
+
 // host: the profile from records + stream -- fin_expand_records' arithmetic without the pairs.  A chunk of reads per thread, each with counts of its own
 // when the unitig set is small, else atomic adds into the caller's array
 int fin_records_unitig_counts(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t n_unitigs,
@@ -2701,6 +2906,8 @@ struct TextSink {
     //  pseudoalignment when `psa` is set: fin_search_batch_pseudoalign -- a sub-batch's rows (may be null) and heads land at its reads' numbers)
     fin_colors* paint = nullptr; uint32_t paint_color = 0;
     const fin_colors* psa = nullptr; uint32_t psa_permille = 0; uint64_t* psa_rows = nullptr; fin_read_pseudo* psa_heads = nullptr;
+    // (equivalence classes when `eqc` is set: fin_search_batch_add_eqclasses -- every sub-batch is pseudoaligned and added on the device, nothing comes back)
+    fin_eqclasses* eqc = nullptr; uint32_t eqc_permille = 0;
     std::vector<uint64_t> len; std::vector<char> known;
     std::mutex mu; std::condition_variable cv;
     uint64_t total = 0;
@@ -2818,6 +3025,9 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
                 fin_read_pseudo* const dst = ts->psa_heads + at;
                 if (rc == FIN_OK) rc = fin_batch_download_pseudo(b, ts->psa_rows ? ts->psa_rows + at * fin_colors_words(ts->psa) : nullptr, dst, e, sizeof e);
                 if (rc == FIN_OK) for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_colored;
+            } else
+            if (rc == FIN_OK && ts && ts->eqc) {
+                rc = fin_batch_add_eqclasses(b, ts->eqc, ts->eqc_permille, (void*)b->own_stream, e, sizeof e);
             } else
             if (rc == FIN_OK && ts && ts->tally) {
                 rc = fin_batch_add_classes(b, ts->tally, ts->cls_min_found, ts->cls_min_permille, ts->cls_min_margin, (void*)b->own_stream, e, sizeof e);
@@ -3083,6 +3293,16 @@ int fin_search_batch_add_classes(const fin_index* idx, const char* bases, const 
     if (n_reads == 0) return FIN_OK;
     TextSink ts; ts.tally = l; ts.cls_min_found = min_found; ts.cls_min_permille = min_permille; ts.cls_min_margin = min_margin;
     return search_range_on(idx, l->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+}
+
+int fin_search_batch_add_eqclasses(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_eqclasses* e, uint32_t permille,
+                                   char* err, size_t errlen) {
+    if (!idx || !offsets || !e || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (e->idx != idx) { set_err(err, errlen, "the equivalence classes belong to another index"); return FIN_EINVAL; }
+    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.eqc = e; ts.eqc_permille = permille;
+    return search_range_on(idx, e->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
 }
 
 // the index's numbers of the caller's unitigs: each one's first k-mer, searched forward, must come back as (u, 0)

@@ -176,6 +176,16 @@ int fin_launch_colors_add(const void* frec, const uint64_t* out_offs, const void
                           uint32_t color, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, hipStream_t stream);
 int fin_launch_pseudoalign(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const void* bits, uint32_t W,
                            uint32_t n_unitigs, uint32_t permille, void* rows, void* heads, hipStream_t stream);
+// fin_eqclasses.hip -- equivalence classes of colour rows: an open-addressing table of 2^lg slots (tags, counts: a u64 per slot; tab_rows: W u64 per slot; ctr:
+// 8 u64 -- rows added, unaligned, classes, rows through the serial pass, flags, the collision list's length).  fin_launch_ec_add: rows uint64[n_rows * W] are added
+// in three launches (claim, verify and count, collisions serially); slot_of and coll: n_rows u32 of scratch each.  tag_bits / combine: options "ec_tag_bits" and
+// "ec_combine".  fin_launch_ec_occupied + fin_launch_ec_gather: the occupied slots as a dense {row, reads} list in slot order
+int fin_launch_ec_add(const void* rows, uint32_t n_rows, uint32_t W, uint32_t n_colors, void* tags, void* counts, void* tab_rows, uint32_t lg, uint64_t max_classes,
+                      uint32_t tag_bits, uint32_t combine, void* ctr, uint32_t* slot_of, uint32_t* coll, hipStream_t stream);
+uint32_t fin_ec_blocks(uint32_t slots);
+int fin_launch_ec_occupied(const void* tags, uint32_t slots, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total, hipStream_t stream);
+int fin_launch_ec_gather(const void* tags, const void* counts, const void* tab_rows, uint32_t slots, uint32_t W, const uint64_t* blk_off, void* out_rows,
+                         void* out_reads, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

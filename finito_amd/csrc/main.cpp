@@ -499,10 +499,17 @@ static const char* SEARCH_HELP =
     "                        in --read-summary, found = the k-mers found, coloured = those of them in a unitig with a colour, then the colours that at\n"
     "                        least P thousandths of the coloured k-mers have (`-` for none). Made on the first GPU from one more search of every chunk;\n"
     "                        goes with everything --read-summary goes with. Not for a partitioned index.\n"
-    "      --pseudo-permille P  the P of --pseudoalign, 0 to 1000 (default: 1000, the intersection; 0 is the union)\n"
+    "      --pseudo-permille P  the P of --pseudoalign, --eqclasses and --color-report, 0 to 1000 (default: 1000, the intersection; 0 is the union)\n"
+    "      --eqclasses FILE  the equivalence classes of the reads under the colours of --color-refs: one line `reads<TAB>n_colours<TAB>c1,c2,...` per\n"
+    "                        distinct non-empty colour set a read has at the P of --pseudo-permille, reads = how many reads have it, in ascending order\n"
+    "                        of the sets as bit rows. Accumulated on the first GPU from one more search of every chunk, nothing per read comes back;\n"
+    "                        written after the last chunk. Goes with everything --read-summary goes with. Not for a partitioned index.\n"
+    "      --color-report FILE  from the same classes: `colour<TAB>reads<TAB>reads_only` for every colour -- the reads whose set contains the colour and\n"
+    "                        the reads whose set is that colour alone --, then `unaligned<TAB>N`, the reads without a colour\n"
+    "      --eq-max-classes N  room for N distinct colour sets, 1 to 67108864 (default: 1048576); more is an error\n"
     "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify,\n"
-    "                        --label-report, --colors-out or --pseudoalign): do not make or write the pair text, the other results asked for are the\n"
-    "                        only ones\n"
+    "                        --label-report, --colors-out, --pseudoalign, --eqclasses or --color-report): do not make or write the pair text, the other\n"
+    "                        results asked for are the only ones\n"
     "  -h, --help            Print usage\n";
 
 static int build_fmin(int argc, char** argv) {
@@ -876,6 +883,13 @@ static void color_by_search(const FinimizerIndex& index, const string& fasta, ui
     }
     flush();
 }
+// --eqclasses FILE / --color-report FILE: one accumulator of equivalence classes for the whole run; every chunk's reads are pseudoaligned and added on the
+// first device (fin_search_batch_add_eqclasses), nothing per read comes back; both files are written after the last chunk
+static fin_eqclasses* g_eqc = nullptr;
+static void eqclasses_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
+    char err[512] = {0};
+    if (fin_search_batch_add_eqclasses(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_eqc, g_psa_permille, err, sizeof err) != FIN_OK) throw runtime_error(err);
+}
 static bool g_no_text = false;
 static uint64_t g_hits_total = 0;   // the accumulator's sum after the previous query file
 
@@ -960,6 +974,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
+                        if (g_eqc) eqclasses_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                     }
                     else {
                         // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
@@ -981,6 +996,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
+                        if (g_eqc) eqclasses_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                     }
                     if (g_strand_counts) {
                         c->positive_fwd = index.count_found_one_strand(c->bases.get(0), c->offsets.data(), n_reads);
@@ -1096,15 +1112,18 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign"))
-        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify, --label-report, --colors-out or --pseudoalign (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report"))
+        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses or --color-report (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
-    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out")) throw runtime_error("--color-refs is only legal together with --pseudoalign or --colors-out");
-    if (o.has("pseudo-permille") && !o.has("pseudoalign")) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign");
+    if ((o.has("eqclasses") || o.has("color-report")) && !o.has("color-refs")) throw runtime_error("--eqclasses and --color-report want colours: --color-refs LIST");
+    const bool eq_asked = o.has("eqclasses") || o.has("color-report");
+    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses or --color-report");
+    if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses or --color-report");
+    if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses or --color-report");
     if ((o.has("classify") || o.has("label-report")) && !(o.has("label-unitigs") && o.has("labels"))) throw runtime_error("--classify and --label-report want a labelling: --label-unitigs FASTA --labels FILE");
     if ((o.has("label-unitigs") || o.has("labels")) && !o.has("classify") && !o.has("label-report")) throw runtime_error("--label-unitigs and --labels are only legal together with --classify or --label-report");
     for (const char* name : {"class-min-found", "class-min-permille", "class-min-margin"})
@@ -1125,6 +1144,8 @@ static int search_fmin(int argc, char** argv) {
     g_cls_min_permille = u32_option("class-min-permille", 0, 1000);
     g_cls_min_margin = u32_option("class-min-margin", 0, 0xFFFFFFFFull);
     g_psa_permille = u32_option("pseudo-permille", 1000, 1000);
+    const uint32_t eq_max_classes = u32_option("eq-max-classes", 1u << 20, 1u << 26);
+    if (eq_max_classes == 0) throw runtime_error("--eq-max-classes wants a number from 1 to " + to_string(1u << 26));
     vector<string> color_refs;
     if (o.has("color-refs")) {
         color_refs = readlines(o.get("color-refs"));
@@ -1175,6 +1196,9 @@ static int search_fmin(int argc, char** argv) {
     if (!cls_file.empty()) check_writable(cls_file);
     if (!report_file.empty()) check_writable(report_file);
     const string colors_file = o.get("colors-out", ""), psa_file = o.get("pseudoalign", "");
+    const string eqc_file = o.get("eqclasses", ""), crep_file = o.get("color-report", "");
+    if (!eqc_file.empty()) check_writable(eqc_file);
+    if (!crep_file.empty()) check_writable(crep_file);
     if (!colors_file.empty()) check_writable(colors_file);
     if (!psa_file.empty()) check_writable(psa_file);
     cerr << "Loading index..." << endl;
@@ -1267,7 +1291,7 @@ static int search_fmin(int argc, char** argv) {
             if (!g_cls_file) throw runtime_error("Error writing to file: " + cls_file);
         }
     }
-    struct ColorOwner { ~ColorOwner() { if (g_psa_file) fclose(g_psa_file); g_psa_file = nullptr; fin_colors_free(g_colors); g_colors = nullptr; } } color_owner;
+    struct ColorOwner { ~ColorOwner() { if (g_psa_file) fclose(g_psa_file); g_psa_file = nullptr; fin_eqclasses_free(g_eqc); g_eqc = nullptr; fin_colors_free(g_colors); g_colors = nullptr; } } color_owner;
     if (!color_refs.empty()) {
         for (auto& f : color_refs) check_readable(f);
         char err[512] = {0};
@@ -1291,6 +1315,7 @@ static int search_fmin(int argc, char** argv) {
             if (!g_psa_file) throw runtime_error("Error writing to file: " + psa_file);
             g_psa_read0 = 0;
         }
+        if ((!eqc_file.empty() || !crep_file.empty()) && fin_eqclasses_create(g_colors, eq_max_classes, &g_eqc, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
@@ -1336,6 +1361,41 @@ static int search_fmin(int argc, char** argv) {
         const bool bad = fflush(g_psa_file) != 0 || ferror(g_psa_file);
         fclose(g_psa_file); g_psa_file = nullptr;
         if (bad) throw runtime_error("Error writing to file: " + psa_file);
+    }
+    if (g_eqc) {   // the classes and the tally derived from them, after the last chunk
+        char err[512] = {0};
+        const uint32_t W = fin_colors_words(g_colors), nc = fin_colors_n_colors(g_colors);
+        uint64_t n = 0, un = 0;
+        vector<uint64_t> rows(1), reads(1);
+        int rc = fin_eqclasses_download(g_eqc, rows.data(), reads.data(), 0, &n, &un, err, sizeof err);   // (how many there are)
+        if (rc == FIN_ELIMIT && n > 0) {
+            rows.assign((size_t)n * W, 0); reads.assign((size_t)n, 0);
+            rc = fin_eqclasses_download(g_eqc, rows.data(), reads.data(), n, &n, &un, err, sizeof err);
+        }
+        if (rc != FIN_OK) throw runtime_error(err);
+        if (!eqc_file.empty()) {
+            string text;
+            for (uint64_t i = 0; i < n; i++) {
+                uint32_t pc = 0;
+                for (uint32_t w = 0; w < W; w++) pc += (uint32_t)__builtin_popcountll(rows[(size_t)i * W + w]);
+                text += to_string(reads[(size_t)i]); text += '\t'; text += to_string(pc); text += '\t';
+                append_colors(text, rows.data() + (size_t)i * W, W);
+                text += '\n';
+            }
+            ofstream cf(eqc_file, ios::binary | ios::trunc);
+            cf.write(text.data(), (streamsize)text.size());
+            if (!cf) throw runtime_error("Error writing to file: " + eqc_file);
+        }
+        if (!crep_file.empty()) {
+            vector<uint64_t> with(nc), only(nc);
+            if (fin_eqclasses_color_tally(rows.data(), reads.data(), n, nc, with.data(), only.data()) != FIN_OK) throw runtime_error("the colour tally of the equivalence classes failed");
+            string text;
+            for (uint32_t c = 0; c < nc; c++) { text += to_string(c); text += '\t'; text += to_string(with[c]); text += '\t'; text += to_string(only[c]); text += '\n'; }
+            text += "unaligned\t"; text += to_string(un); text += '\n';
+            ofstream cf(crep_file, ios::binary | ios::trunc);
+            cf.write(text.data(), (streamsize)text.size());
+            if (!cf) throw runtime_error("Error writing to file: " + crep_file);
+        }
     }
     if (g_labels && g_cls_report) {   // the tally, after the last chunk: one line per label, then the unassigned reads
         char err[512] = {0};

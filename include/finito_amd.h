@@ -468,9 +468,10 @@ typedef struct fin_hits fin_hits;
 /* zeroed counts for `idx` on `device` (FIN_ENODEV: the index has no replica there) */
 int fin_hits_create(const fin_index* idx, int device, fin_hits** out, char* err, size_t errlen);
 /* zeroes the counts, on the given stream; does not wait.  A reset does not commute with the adds, so the library orders it, for this and every other accumulator
- * (fin_cover, fin_depth, fin_labels, fin_colors): it runs behind every add and reset issued so far, whichever streams they were given, and every add issued
+ * (fin_cover, fin_depth, fin_labels, fin_colors, fin_eqclasses): it runs behind every add and reset issued so far, whichever streams they were given, and every add issued
  * after it runs behind it -- calls take effect in the order they were issued, also when they come from several host threads (a reset is one step under the
- * accumulator's lock).  Adds on different streams stay unordered among themselves (they commute). */
+ * accumulator's lock).  Adds on different streams stay unordered among themselves (they commute) -- except fin_eqclasses' adds, which the library orders too
+ * (see there). */
 int fin_hits_reset(fin_hits* h, void* hip_stream);
 /* counts += the hits of the batch's most recent run, on the given stream, ordered behind that run; does not wait.  Every call adds: the same run added twice
  * counts twice (that is the caller's business).  Reads the run's records and pairs as they stand and changes neither: fin_batch_records,
@@ -751,8 +752,8 @@ int fin_index_unitig_numbers(const fin_index* idx, const char* bases, const uint
  * 0 .. 1000 colour c is in the read's row iff cnt[c] >= 1 and 1000 * cnt[c] >= permille * n_colored (64-bit arithmetic).  permille = 1000 is the intersection over
  * the coloured k-mers -- found k-mers in uncoloured unitigs and absent k-mers are ignored --, permille = 0 the union.  All of it is invariant under reversing the
  * slot order.  A pair whose unitig number is at or above the index's number of unitigs counts as absent on the device and is FIN_EINVAL on the host.
- * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, a per-colour tally of reads, more than 4096 colours,
- * compressed or deduplicated colour sets. */
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, more than 4096 colours, compressed or deduplicated colour sets.  (A per-colour
+ * tally of reads: the EQUIVALENCE CLASSES below.) */
 #define FIN_MAX_COLORS 4096u
 typedef struct fin_read_pseudo { uint32_t n_found, n_colored, n_colors, reserved /* 0 */; } fin_read_pseudo;   /* 16 bytes; n_colors = the popcount of the read's row */
 typedef struct fin_colors fin_colors;
@@ -797,6 +798,56 @@ int fin_search_batch_pseudoalign(const fin_index* idx, const char* bases, const 
  * n_colors, a unitig number >= n_unitigs, a stream that is not this record set's, or a stream pair that is neither found nor (-1,-1) */
 int fin_records_pseudoalign(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint64_t* bits,
                             uint64_t n_unitigs, uint32_t n_colors, uint32_t permille, uint64_t* rows_out, fin_read_pseudo* heads_out, int n_threads);
+
+/* ---- EQUIVALENCE CLASSES of pseudoaligned reads, counted on the device ----
+ * What abundance estimation, strain demixing and "how many reads does each reference explain" start from is not a colour row per read but the distinct rows a run
+ * produced and how many reads have each (kallisto's and Themisto-to-mSWEEP's sufficient statistic): a few thousand classes for millions of reads.  An
+ * accumulator belongs to one fin_colors, and through it to that object's index, device, n_colors and W.  Over every row added since the last reset, exact and in
+ * integers:
+ *   a row whose W words are all zero is UNALIGNED: it counts in n_unaligned and belongs to no class;
+ *   every other row belongs to the class of the rows bit-identical to it; reads[class] = the rows added to it;
+ *   the sum of reads + n_unaligned = the rows added.  Adding the same run twice counts twice, as fin_hits does;
+ *   classes are reported in CANONICAL order: ascending by word 0, then word 1 and so on, as unsigned 64-bit integers (numpy's np.unique(rows, axis=0));
+ *   a row with a bit at or above n_colors is not counted and flags the accumulator: the download reports FIN_EINVAL until the reset;
+ *   more than max_classes distinct non-empty rows flag it too: the download reports FIN_ELIMIT until the reset (the table does not grow).
+ * The per-colour TALLY is derived from the classes (fin_eqclasses_color_tally): reads_with[c] = the reads of the classes that contain colour c, reads_only[c] =
+ * the reads of the class {c}, 0 if there is none.
+ * HBM: slots * (8 W + 16) bytes plus 64 bytes of counters, slots = the power of two >= 2 max_classes; and 8 bytes per row of the largest add as scratch.
+ * ORDER: unlike the other accumulators' adds, adds to this one do NOT commute at the memory level (fin_eqclasses.hip: a slot is claimed in one kernel and its
+ * row is compared in the next).  So where the others say "adds on different streams stay unordered", here every add runs behind every add and reset of this
+ * accumulator issued so far, on whichever stream; order, launches and mark are one step under the accumulator's lock, so adds from several host threads take
+ * effect in issue order.  Resets are ordered as fin_hits_reset is.
+ * Out of scope: an abundance model over the classes, partitioned indexes, fin_search_batch_multi / dist.py, the C++ mirror (a caller with several GPUs keeps an
+ * accumulator per replica and merges the downloads with fin_rows_eqclasses' arithmetic), a growing table, more than 4096 colours. */
+typedef struct fin_eqclasses fin_eqclasses;
+/* an empty accumulator beside the colours.  FIN_ELIMIT: max_classes is not 1 .. 2^26.  Free it before the colours. */
+int fin_eqclasses_create(const fin_colors* c, uint64_t max_classes, fin_eqclasses** out, char* err, size_t errlen);
+int fin_eqclasses_reset(fin_eqclasses* e, void* hip_stream);   /* empties it and clears its flags (asynchronous on hip_stream) */
+void fin_eqclasses_free(fin_eqclasses* e);
+/* rows any producer left in HBM: uint64[n_rows * W] on the accumulator's device, valid until the add has finished; on hip_stream, no sync.  n_rows < 2^31 */
+int fin_eqclasses_add_rows(fin_eqclasses* e, const void* d_rows, uint64_t n_rows, void* hip_stream, char* err, size_t errlen);
+/* the batch's most recent run, pseudoaligned against the accumulator's colours at `permille`, then added.  fin_batch_pseudoalign is ALWAYS called first (the
+ * batch does not remember which matrix and threshold its rows belong to): its FIN_EINVAL / FIN_ELIMIT are this call's -- the batch has not run, another index or
+ * device, permille > 1000, a run whose overflow list overran (nothing of it is added) --, it may wait for the run's overflow verdict, and afterwards the batch's
+ * pseudo rows and heads are those of this call.  The rows are made on the run's stream; the add on hip_stream waits for them. */
+int fin_batch_add_eqclasses(fin_batch* b, fin_eqclasses* e, uint32_t permille, void* hip_stream, char* err, size_t errlen);
+/* fin_search_batch_add_classes' loop with the classes as its product: host buffers in, sub-batches pipelined, each run in text mode 2 where the fast path is on.
+ * Reads shorter than k count as unaligned rows; an empty read set is legal. */
+int fin_search_batch_add_eqclasses(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_eqclasses* e, uint32_t permille,
+                                   char* err, size_t errlen);
+/* waits for every add and reset issued so far, then compacts the table on the device: what crosses PCIe is n_classes * (8 W + 8) bytes.  *n_classes is always set
+ * on FIN_OK; rows_out[cap * W] and reads_out[cap] are filled, in canonical order, when cap >= *n_classes -- FIN_ELIMIT otherwise, *n_classes still set.
+ * *n_unaligned may be NULL.  FIN_EINVAL: a row with a bit at or above n_colors was added; FIN_ELIMIT: more than max_classes distinct rows -- both until the reset. */
+int fin_eqclasses_download(fin_eqclasses* e, uint64_t* rows_out, uint64_t* reads_out, uint64_t cap, uint64_t* n_classes, uint64_t* n_unaligned, char* err, size_t errlen);
+/* waits; out[0] rows added, [1] unaligned, [2] classes, [3] rows that went through the serial pass (distinct rows under one tag; option "ec_tag_bits", 1 .. 63,
+ * default 63, narrows the tags for tests -- it is read by the first add after the creation or a reset and holds until the next reset) */
+int fin_eqclasses_stats(fin_eqclasses* e, uint64_t out[4], char* err, size_t errlen);
+/* host, no device: the same classes from rows[n_rows * W].  FIN_EINVAL: a bit at or above n_colors; FIN_ELIMIT: n_colors is 0 or above FIN_MAX_COLORS, or cap is
+ * too small (*n_classes still set) */
+int fin_rows_eqclasses(const uint64_t* rows, uint64_t n_rows, uint32_t n_colors, uint64_t* rows_out, uint64_t* reads_out, uint64_t cap, uint64_t* n_classes,
+                       uint64_t* n_unaligned);
+/* host: the per-colour tally of n_classes classes: reads_with[n_colors], reads_only[n_colors] */
+int fin_eqclasses_color_tally(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, uint64_t* reads_with, uint64_t* reads_only);
 
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
