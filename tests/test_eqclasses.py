@@ -11,6 +11,7 @@ from oracle.oracle import OracleIndex
 from tests.test_colors import hand_picked
 from tests.test_colors_host import pack, random_matrix, rows_of, words_of
 from tests.test_eqclasses_host import assert_classes, classes_of_rows, random_rows, tally_of
+from tests.test_eqclasses_table_host import tags_of
 from tests.test_read_summary_host import assert_summaries, summaries_of
 from tests.test_segments import nks_of, oracle_pairs
 from tests.test_segments_host import assert_segments, segments_of
@@ -229,6 +230,25 @@ def test_rows_that_share_a_tag_go_through_the_serial_pass(small, W, tag_bits):
     eq.reset().add_rows(t.data_ptr(), len(rows))
     assert_all(eq, want, n_colors, "W=%d, after the reset" % W, n_rows=2000)
     assert eq.stats()[3] == 0
+    # the owners first: above, which row of a tag wins its slot is a race, so the figure is only positive.  With one row per tag in the table before the others
+    # arrive, a row goes through the serial pass iff it is not its tag's owner row -- the exact figure, by the mirror of tests/test_eqclasses_table_host.py
+    tags = tags_of(rows, tag_bits)
+    owners = rows[np.sort(np.unique(tags, return_index=True)[1])]
+    owner_of = {int(tg): r.tobytes() for tg, r in zip(tags_of(owners, tag_bits), owners)}
+    serial = sum(1 for tg, r in zip(tags, rows) if owner_of[int(tg)] != r.tobytes())
+    assert len(owners) == min(300, (1 << tag_bits) - 1) and 0 < serial < 2000
+    t0 = on_device(owners)
+    p.set_option("ec_tag_bits", tag_bits)
+    try:
+        eq.reset().add_rows(t0.data_ptr(), len(owners))
+        assert eq.stats()[3] == 0
+        for n in (1, 2):
+            eq.add_rows(t.data_ptr(), len(rows))
+            assert_all(eq, classes_of_rows(np.concatenate([owners] + [rows] * n), n_colors), n_colors, "W=%d, %d tag bits, the owners first, add %d" % (W, tag_bits, n),
+                       n_rows=len(owners) + 2000 * n)
+            assert eq.stats()[3] == serial * n
+    finally:
+        p.set_option("ec_tag_bits", None)
     eq.close(); col.close()
 
 
