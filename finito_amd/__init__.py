@@ -23,6 +23,12 @@ X_C, X_PLANE_A, X_LCS, X_FMIN, X_USTART, X_GOFF, X_ENDS, X_CONCAT = 0, 1, 5, 6, 
 DT_PTAB, DT_JTAB, DT_FILT, DT_SAFE, DT_RCWIN, DT_CBF, DT_FBF = range(7)   # fin_index_debug_table
 
 
+class AbundanceInfo(C.Structure):
+    """fin_abundance_info of include/finito_amd.h"""
+    _fields_ = [("n_classes", C.c_uint64), ("n_reads", C.c_uint64), ("n_unaligned", C.c_uint64), ("iters", C.c_uint32), ("converged", C.c_uint32),
+                ("loglik", C.c_double), ("max_change", C.c_double)]
+
+
 class FinitoError(RuntimeError):
     """std::runtime_error of the reference (caught in src/main.cpp:51-57)."""
 
@@ -258,6 +264,9 @@ def lib():
         L.fin_eqclasses_stats.argtypes = [vp, u64p, cp, C.c_size_t]
         L.fin_rows_eqclasses.argtypes = [u64p, u64, u32, u64p, u64p, u64, u64p, u64p]
         L.fin_eqclasses_color_tally.argtypes = [u64p, u64p, u64, u32, u64p, u64p]
+        f64p = C.POINTER(C.c_double)
+        L.fin_eqclasses_abundance.argtypes = [vp, f64p, u32, C.c_double, f64p, f64p, C.POINTER(AbundanceInfo), cp, C.c_size_t]
+        L.fin_classes_abundance.argtypes = [u64p, u64p, u64, u32, f64p, u32, C.c_double, f64p, f64p, C.POINTER(AbundanceInfo), C.c_int]
         _LIB = L
     return _LIB
 
@@ -861,6 +870,20 @@ class EqClasses:
         w, o = eqclasses_color_tally(rows, reads, self.n_colors)
         return w, o, un
 
+    def abundance(self, lengths=None, max_iters=1000, tol=1e-6, trace=False):
+        """expected reads per colour by EM over the classes, on the device: an Abundance; waits for the adds and leaves the accumulator as it found it
+        (fin_eqclasses_abundance).  lengths: one finite positive number per colour (None: all 1); trace: keep the log-likelihood of every iteration -- an
+        array given here is written in place, entries behind `iters` left alone"""
+        lens, mi, tol = _abundance_args("EqClasses.abundance", self.n_colors, lengths, max_iters, tol)
+        alpha = np.zeros(self.n_colors, dtype=np.float64)
+        tr = _abundance_trace("EqClasses.abundance", trace, mi)
+        info = AbundanceInfo()
+        err = C.create_string_buffer(512)
+        f64p = C.POINTER(C.c_double)
+        _check(self.L.fin_eqclasses_abundance(self.h, lens.ctypes.data_as(f64p) if lens is not None else None, mi, tol, alpha.ctypes.data_as(f64p),
+                                              tr.ctypes.data_as(f64p) if tr is not None else None, C.byref(info), err, 512), err)
+        return Abundance(alpha, lens, info, tr)
+
     def stats(self):
         """[rows added, unaligned, classes, rows that went through the serial pass]; waits (fin_eqclasses_stats)"""
         out = np.zeros(4, dtype=np.uint64)
@@ -878,6 +901,55 @@ class EqClasses:
             self.close()
         except Exception:
             pass
+
+
+class Abundance:
+    """the result of an abundance estimate: alpha = expected reads per colour, theta = alpha / N, rho = (alpha / len) / sum(alpha / len) -- the
+    share of the sample's copies; iters, converged, loglik (of the last iteration), max_change (max |delta alpha| / max(alpha, 1) of the last iteration),
+    n_reads (N, the aligned reads), n_unaligned, n_classes; trace = the log-likelihood of iterations 0 .. iters - 1 when asked for, else None"""
+
+    def __init__(self, alpha, lengths, info, trace):
+        self.alpha = alpha
+        self.n_reads, self.n_unaligned, self.n_classes = int(info.n_reads), int(info.n_unaligned), int(info.n_classes)
+        self.iters, self.converged = int(info.iters), bool(info.converged)
+        self.loglik, self.max_change = float(info.loglik), float(info.max_change)
+        self.theta = alpha / self.n_reads if self.n_reads else np.zeros_like(alpha)
+        per_len = alpha / lengths if lengths is not None else alpha
+        self.rho = per_len / per_len.sum() if per_len.sum() > 0 else np.zeros_like(alpha)
+        self.trace = trace[: self.iters] if trace is not None else None
+
+
+def _abundance_args(what, n_colors, lengths, max_iters, tol):
+    """the checks of fin_eqclasses_abundance and fin_classes_abundance, made here so that the message can say what was wrong"""
+    if not 1 <= int(n_colors) <= 4096:
+        raise FinitoError(FIN_ELIMIT, "%s: n_colors is 1 .. 4096" % what)
+    mi = int(max_iters)
+    if mi < 1:
+        raise FinitoError(FIN_EINVAL, "%s: max_iters is 1 .. 100000" % what)
+    if mi > 100000:
+        raise FinitoError(FIN_ELIMIT, "%s: max_iters is 1 .. 100000" % what)
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise FinitoError(FIN_EINVAL, "%s: tol is a number >= 0" % what)
+    lens = None
+    if lengths is not None:
+        lens = np.ascontiguousarray(lengths, dtype=np.float64).reshape(-1)
+        if len(lens) != int(n_colors):
+            raise FinitoError(FIN_EINVAL, "%s: %d lengths for %d colours" % (what, len(lens), int(n_colors)))
+        bad = np.nonzero(~(np.isfinite(lens) & (lens > 0)))[0]
+        if len(bad):
+            raise FinitoError(FIN_EINVAL, "%s: the length of colour %d is not a finite positive number" % (what, int(bad[0])))
+    return lens, mi, tol
+
+
+def _abundance_trace(what, trace, max_iters):
+    if trace is None or trace is False:
+        return None
+    if trace is True:
+        return np.zeros(max_iters, dtype=np.float64)
+    if not (isinstance(trace, np.ndarray) and trace.dtype == np.float64 and trace.ndim == 1 and trace.flags.c_contiguous and len(trace) >= max_iters):
+        raise FinitoError(FIN_EINVAL, "%s: trace is a bool or a contiguous float64 array of at least max_iters entries" % what)
+    return trace
 
 
 class Cover:
@@ -1750,6 +1822,26 @@ def rows_eqclasses(rows, n_colors):
     if rc != 0:
         raise FinitoError(rc, "fin_rows_eqclasses: n_colors outside 1 .. 4096, or a row with a bit at or above n_colors")
     return out[: int(n.value)], reads[: int(n.value)], int(un.value)
+
+
+def classes_abundance(class_rows, class_reads, n_colors, lengths=None, max_iters=1000, tol=1e-6, trace=False, n_threads=0):
+    """host: the estimate of EqClasses.abundance from classes {row, reads} in the order given: an Abundance with n_unaligned = 0 (fin_classes_abundance)"""
+    lens, mi, tol = _abundance_args("classes_abundance", n_colors, lengths, max_iters, tol)
+    W = (int(n_colors) + 63) // 64
+    a = np.ascontiguousarray(class_rows, dtype=np.uint64).reshape(-1, W)
+    r = np.ascontiguousarray(class_reads, dtype=np.uint64).reshape(-1)
+    if len(a) != len(r):
+        raise FinitoError(FIN_EINVAL, "classes_abundance: %d rows and %d counts" % (len(a), len(r)))
+    alpha = np.zeros(int(n_colors), dtype=np.float64)
+    tr = _abundance_trace("classes_abundance", trace, mi)
+    info = AbundanceInfo()
+    u64p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+    rc = lib().fin_classes_abundance(a.ctypes.data_as(u64p), r.ctypes.data_as(u64p), len(a), int(n_colors), lens.ctypes.data_as(f64p) if lens is not None else None, mi, tol,
+                                     alpha.ctypes.data_as(f64p), tr.ctypes.data_as(f64p) if tr is not None else None, C.byref(info), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_classes_abundance: more than 2^26 classes" if rc == FIN_ELIMIT else
+                          "fin_classes_abundance: a class with a bit at or above n_colors, an empty row or a class of 0 reads")
+    return Abundance(alpha, lens, info, tr)
 
 
 def eqclasses_color_tally(class_rows, class_reads, n_colors):

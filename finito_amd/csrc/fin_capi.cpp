@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -94,7 +95,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -131,6 +132,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"debug_depth_tile", 0, 0, 4096},              // tests: fin_depth_download's prefix sum in tiles of this many elements and chunks of 64 tiles (0: tiles of 4096 elements, chunks of 4096 tiles)
     {"ec_tag_bits", 63, 1, 63},                    // fin_eqclasses: bits of a row's tag in the table (fin_eqclasses.hip); tests narrow it so that distinct rows share tags and go through the serial pass.  Read by the first add after the accumulator's creation or reset and kept until the next reset: a table's tags are made one way
     {"ec_combine", 1, 0, 1},                       // fin_eqclasses' count pass: 1 = a wave's adds combined over its distinct slots, one atomic each; 0 = one atomic per row (tools/ab_eqclasses.py measures both)
+    {"ab_chunk", 0, 0, 1ll << 26},                 // fin_eqclasses_abundance's column pass: classes per chunk, rounded up to a multiple of 64 (fin_abundance.hip); 0 = auto: 256, more once that would make over 1024 chunks (which also bounds what a value can ask for).  The order of the column sums is a function of it, so two estimates compare bit for bit only under one value; tests set 64 so that small cases cross chunk seams
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -2323,6 +2325,13 @@ static void ec_canonical(const uint64_t* rows, uint64_t n, uint32_t W, std::vect
     std::sort(perm.begin(), perm.end(), [&](uint64_t a, uint64_t b) { return std::lexicographical_compare(rows + a * W, rows + a * W + W, rows + b * W, rows + b * W + W); });
 }
 
+// what a flagged accumulator answers its readers until the reset
+static int ec_flagged(const fin_eqclasses* e, const uint64_t* ctr, char* err, size_t errlen) {
+    if (ctr[4] & 1u) { set_err(err, errlen, "a row with a bit at or above n_colors was added (not counted; reset the accumulator)"); return FIN_EINVAL; }
+    if ((ctr[4] & 2u) || ctr[2] > e->max_classes) { set_err(err, errlen, "more than max_classes distinct rows (max_classes = " + std::to_string(e->max_classes) + "; reset the accumulator)"); return FIN_ELIMIT; }
+    return FIN_OK;
+}
+
 int fin_eqclasses_download(fin_eqclasses* e, uint64_t* rows_out, uint64_t* reads_out, uint64_t cap, uint64_t* n_classes, uint64_t* n_unaligned, char* err, size_t errlen) {
     if (!e || !n_classes || (cap && (!rows_out || !reads_out))) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     HIPCHK(hipSetDevice(e->device));
@@ -2330,8 +2339,7 @@ int fin_eqclasses_download(fin_eqclasses* e, uint64_t* rows_out, uint64_t* reads
     if (const int wrc = e->pend.wait(err, errlen)) return wrc;
     uint64_t ctr[8];
     HIPCHK(hipMemcpy(ctr, ec_ctr(e), sizeof ctr, hipMemcpyDeviceToHost));
-    if (ctr[4] & 1u) { set_err(err, errlen, "a row with a bit at or above n_colors was added (not counted; reset the accumulator)"); return FIN_EINVAL; }
-    if ((ctr[4] & 2u) || ctr[2] > e->max_classes) { set_err(err, errlen, "more than max_classes distinct rows (max_classes = " + std::to_string(e->max_classes) + "; reset the accumulator)"); return FIN_ELIMIT; }
+    if (const int frc = ec_flagged(e, ctr, err, errlen)) return frc;
     // compaction on the device: the occupied slots counted per block, scanned, gathered into a dense list -- the table itself never crosses PCIe
     const uint32_t W = e->words, nb = fin_ec_blocks((uint32_t)e->slots);
     void* d_tmp = nullptr; void* d_dense = nullptr;
@@ -2408,6 +2416,170 @@ int fin_eqclasses_color_tally(const uint64_t* class_rows, const uint64_t* class_
         for (uint32_t w = 0; w < W; w++)
             for (uint64_t m = row[w]; m; m &= m - 1) { last = 64u * w + (uint32_t)__builtin_ctzll(m); reads_with[last] += class_reads[i]; pc++; }
         if (pc == 1u) reads_only[last] += class_reads[i];
+    }
+    return FIN_OK;
+}
+
+// ---- abundances from the classes (fin_abundance.hip) ---------------------------------------------------------------------
+#define FIN_AB_MAX_ITERS 100000u
+#define FIN_AB_GROUP 32u   // iterations enqueued between two looks at the device's {done, iters}
+static int ab_check_args(uint32_t n_colors, const double* lengths, uint32_t max_iters, double tol, char* err, size_t errlen) {
+    if (n_colors == 0 || n_colors > FIN_MAX_COLORS) { set_err(err, errlen, "n_colors is 1 .. 4096"); return FIN_ELIMIT; }
+    if (max_iters == 0) { set_err(err, errlen, "max_iters is 1 .. 100000"); return FIN_EINVAL; }
+    if (max_iters > FIN_AB_MAX_ITERS) { set_err(err, errlen, "max_iters is 1 .. 100000"); return FIN_ELIMIT; }
+    if (!(tol >= 0.0)) { set_err(err, errlen, "tol is a number >= 0"); return FIN_EINVAL; }
+    if (lengths)
+        for (uint32_t c = 0; c < n_colors; c++)
+            if (!(lengths[c] > 0.0) || !std::isfinite(lengths[c])) { set_err(err, errlen, "the length of colour " + std::to_string(c) + " is not a finite positive number"); return FIN_EINVAL; }
+    return FIN_OK;
+}
+static void ab_empty(uint32_t n_colors, double* alpha_out, fin_abundance_info* info, uint64_t n_unaligned) {
+    for (uint32_t c = 0; c < n_colors; c++) alpha_out[c] = 0.0;
+    if (info) { *info = fin_abundance_info(); info->n_unaligned = n_unaligned; info->converged = 1; }
+}
+
+int fin_eqclasses_abundance(fin_eqclasses* e, const double* lengths, uint32_t max_iters, double tol, double* alpha_out, double* loglik_trace, fin_abundance_info* info,
+                            char* err, size_t errlen) {
+    if (!e || !alpha_out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int arc = ab_check_args(e->n_colors, lengths, max_iters, tol, err, errlen)) return arc;
+    HIPCHK(hipSetDevice(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const int wrc = e->pend.wait(err, errlen)) return wrc;
+    uint64_t ctr[8];
+    HIPCHK(hipMemcpy(ctr, ec_ctr(e), sizeof ctr, hipMemcpyDeviceToHost));
+    if (const int frc = ec_flagged(e, ctr, err, errlen)) return frc;
+    const uint32_t W = e->words, nc = e->n_colors, nb = fin_ec_blocks((uint32_t)e->slots), ab_chunk = (uint32_t)optv(e->idx, O_ab_chunk);
+    // every device buffer of the call, freed on every way out
+    struct Bufs { std::vector<void*> p; ~Bufs() { for (void* q : p) (void)hipFree(q); } void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return q; } } bufs;
+    // (beside the table: the dense rows and reads, 8 C (W + 1) bytes, their word-major copy, 8 C W, and 8 (C + n_chunks 64 W) of q and partials)
+    const auto nomem = [&] { set_err(err, errlen, "out of device memory (abundances from the equivalence classes: beside the table, 16 W + 16 bytes per class and up to 32 MB of partial sums)"); return FIN_ENOMEM; };
+    // the download's compaction: the occupied slots counted per block, scanned, gathered -- the rows stay on the device
+    const size_t off_bytes = (size_t)nb * 8 + 8;
+    void* const d_tmp = bufs.get(off_bytes + (size_t)nb * 4);
+    if (!d_tmp) return nomem();
+    uint64_t* const d_off = (uint64_t*)d_tmp; uint64_t* const d_total = d_off + nb; uint32_t* const d_sum = (uint32_t*)((char*)d_tmp + off_bytes);
+    int rc = fin_launch_ec_occupied(ec_tags(e), (uint32_t)e->slots, d_sum, d_off, d_total, nullptr);
+    if (rc != 0) { set_err(err, errlen, std::string("compaction of the equivalence classes: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    uint64_t C = 0;
+    HIPCHK(hipMemcpy(&C, d_total, 8, hipMemcpyDeviceToHost));
+    if (C == 0) { ab_empty(nc, alpha_out, info, ctr[1]); return FIN_OK; }
+    if (C > e->max_classes) { set_err(err, errlen, "more than max_classes distinct rows"); return FIN_ELIMIT; }   // (the flags said otherwise: never)
+    const uint64_t N = ctr[0] - ctr[1];     // the aligned reads: every row added is unaligned or in a class
+    uint32_t cpb, n_ll, chunk, n_chunks;
+    fin_ab_geometry(C, W, ab_chunk, &cpb, &n_ll, &chunk, &n_chunks);
+    const size_t padded = (size_t)64 * W;
+    uint64_t* const d_rows = (uint64_t*)bufs.get((size_t)C * (W + 1) * 8);
+    uint64_t* const d_rowsT = W > 1 ? (uint64_t*)bufs.get((size_t)C * W * 8) : d_rows;
+    // doubles: len | alpha | x | q | part | ll_part | blk_chg | trace, then the state and blk_ok
+    const size_t n_dbl = 3 * padded + (size_t)C + (size_t)n_chunks * padded + n_ll + 64 + max_iters;
+    double* const d_dbl = (double*)bufs.get(n_dbl * 8 + sizeof(FinAbState) + 64 * 4);
+    if (!d_rows || !d_rowsT || !d_dbl) return nomem();
+    uint64_t* const d_reads = d_rows + (size_t)C * W;
+    double* const d_len = d_dbl; double* const d_alpha = d_len + padded; double* const d_x = d_alpha + padded; double* const d_q = d_x + padded;
+    double* const d_part = d_q + C; double* const d_ll = d_part + (size_t)n_chunks * padded; double* const d_chg = d_ll + n_ll; double* const d_trace = d_chg + 64;
+    FinAbState* const d_state = (FinAbState*)(d_trace + max_iters); uint32_t* const d_ok = (uint32_t*)(d_state + 1);
+    rc = fin_launch_ec_gather(ec_tags(e), ec_counts(e), ec_rows(e), (uint32_t)e->slots, W, d_off, d_rows, d_reads, nullptr);
+    if (rc == 0 && W > 1) rc = fin_launch_ab_transpose(d_rows, C, W, d_rowsT, nullptr);
+    if (rc != 0) { set_err(err, errlen, std::string("abundance kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    std::vector<double> host(3 * padded, 0.0);   // len (1 behind n_colors), alpha, x
+    for (size_t c = 0; c < padded; c++) host[c] = c < nc && lengths ? lengths[c] : 1.0;
+    for (uint32_t c = 0; c < nc; c++) { host[padded + c] = (double)N / (double)nc; host[2 * padded + c] = host[padded + c] / host[c]; }
+    HIPCHK(hipMemcpy(d_dbl, host.data(), host.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_state, 0, sizeof(FinAbState) + 64 * 4));
+    FinAbState st = FinAbState();
+    for (uint32_t t = 0; t < max_iters && !st.done;) {
+        const uint32_t t1 = std::min(max_iters, t + FIN_AB_GROUP);
+        for (; t < t1; t++) {
+            rc = fin_launch_ab_iteration(d_state, d_rows, d_rowsT, d_reads, C, W, nc, ab_chunk, d_len, (double)N, tol, d_alpha, d_x, d_q, d_part, d_ll, d_ok, d_chg, t,
+                                         d_trace, nullptr);
+            if (rc != 0) { set_err(err, errlen, std::string("abundance kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+        }
+        HIPCHK(hipMemcpy(&st, d_state, 8, hipMemcpyDeviceToHost));   // {done, iters}: the copy waits for the group
+    }
+    HIPCHK(hipMemcpy(&st, d_state, sizeof st, hipMemcpyDeviceToHost));
+    if (st.iters == 0 || st.iters > max_iters) { set_err(err, errlen, "abundance kernels: the iteration count on the device is out of range"); return FIN_ENODEV; }
+    HIPCHK(hipMemcpy(alpha_out, d_alpha, (size_t)nc * 8, hipMemcpyDeviceToHost));
+    if (loglik_trace) HIPCHK(hipMemcpy(loglik_trace, d_trace, (size_t)st.iters * 8, hipMemcpyDeviceToHost));
+    if (info) {
+        info->n_classes = C; info->n_reads = N; info->n_unaligned = ctr[1];
+        info->iters = st.iters; info->converged = st.done ? 1u : 0u;
+        info->loglik = st.loglik; info->max_change = st.max_change;
+    }
+    return FIN_OK;
+}
+
+// host twin: the definition over the classes in the order given.  Sums in fixed blocks, whatever the number of threads: d_j over the row's bits in ascending order,
+// ll over blocks of 4096 classes and then over the blocks, S_c over chunks of classes (the device's automatic chunk) and then over the chunks
+int fin_classes_abundance(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, const double* lengths, uint32_t max_iters,
+                          double tol, double* alpha_out, double* loglik_trace, fin_abundance_info* info, int n_threads) {
+    if (const int arc = ab_check_args(n_colors, lengths, max_iters, tol, nullptr, 0)) return arc;
+    if ((n_classes && (!class_rows || !class_reads)) || !alpha_out) return FIN_EINVAL;
+    if (n_classes > (1ull << 26)) return FIN_ELIMIT;
+    const uint32_t W = (n_colors + 63u) / 64u;
+    const uint64_t stray = (n_colors & 63u) ? ~0ull << (n_colors & 63u) : 0ull;
+    const int64_t C = (int64_t)n_classes;
+    uint64_t N = 0;
+    for (int64_t j = 0; j < C; j++) {
+        const uint64_t* row = class_rows + (size_t)j * W;
+        bool ne = false;
+        for (uint32_t w = 0; w < W; w++) if (row[w]) ne = true;
+        if ((row[W - 1] & stray) || !ne || class_reads[j] == 0) return FIN_EINVAL;   // a class is a non-empty set with at least one read
+        N += class_reads[j];
+    }
+    if (C == 0) { ab_empty(n_colors, alpha_out, info, 0); return FIN_OK; }
+    const int T = n_threads > 0 ? n_threads : fin_host_threads();
+    uint32_t cpb, n_ll, chunk, n_chunks;
+    fin_ab_geometry(n_classes, W, 0, &cpb, &n_ll, &chunk, &n_chunks);
+    const int64_t LB = 4096, n_lb = (C + LB - 1) / LB;
+    std::vector<double> alpha(n_colors, (double)N / (double)n_colors), x(n_colors), q((size_t)C), ll_blk((size_t)n_lb), part((size_t)n_chunks * n_colors);
+    uint32_t iters = 0, converged = 0;
+    double ll = 0.0, chg = 0.0;
+    for (uint32_t t = 0; t < max_iters && !converged; t++) {
+        for (uint32_t c = 0; c < n_colors; c++) x[c] = alpha[c] / (lengths ? lengths[c] : 1.0);
+#pragma omp parallel for num_threads(T) schedule(static)
+        for (int64_t b = 0; b < n_lb; b++) {
+            double s = 0.0;
+            for (int64_t j = b * LB; j < std::min(C, (b + 1) * LB); j++) {
+                const uint64_t* row = class_rows + (size_t)j * W;
+                double d = 0.0;
+                for (uint32_t w = 0; w < W; w++)
+                    for (uint64_t m = row[w]; m; m &= m - 1) d += x[64u * w + (uint32_t)__builtin_ctzll(m)];
+                const double n = (double)class_reads[j];
+                q[(size_t)j] = d > 0.0 ? n / d : 0.0;
+                if (d > 0.0) s += n * std::log(d / (double)N);
+            }
+            ll_blk[(size_t)b] = s;
+        }
+        ll = 0.0;
+        for (int64_t b = 0; b < n_lb; b++) ll += ll_blk[(size_t)b];
+#pragma omp parallel for num_threads(T) schedule(static)
+        for (int64_t k = 0; k < (int64_t)n_chunks; k++) {
+            double* const p = part.data() + (size_t)k * n_colors;
+            for (uint32_t c = 0; c < n_colors; c++) p[c] = 0.0;
+            for (int64_t j = k * (int64_t)chunk; j < std::min(C, (k + 1) * (int64_t)chunk); j++) {
+                const uint64_t* row = class_rows + (size_t)j * W;
+                for (uint32_t w = 0; w < W; w++)
+                    for (uint64_t m = row[w]; m; m &= m - 1) p[64u * w + (uint32_t)__builtin_ctzll(m)] += q[(size_t)j];
+            }
+        }
+        bool ok = true;
+        chg = 0.0;
+        for (uint32_t c = 0; c < n_colors; c++) {
+            double S = 0.0;
+            for (uint32_t k = 0; k < n_chunks; k++) S += part[(size_t)k * n_colors + c];
+            const double a1 = x[c] * S, scale = a1 > 1.0 ? a1 : 1.0, diff = std::fabs(a1 - alpha[c]);
+            if (!(diff <= tol * scale)) ok = false;
+            if (diff / scale > chg) chg = diff / scale;
+            alpha[c] = a1;
+        }
+        if (loglik_trace) loglik_trace[t] = ll;
+        iters = t + 1;
+        if (ok) converged = 1;
+    }
+    for (uint32_t c = 0; c < n_colors; c++) alpha_out[c] = alpha[c];
+    if (info) {
+        info->n_classes = n_classes; info->n_reads = N; info->n_unaligned = 0;
+        info->iters = iters; info->converged = converged; info->loglik = ll; info->max_change = chg;
     }
     return FIN_OK;
 }

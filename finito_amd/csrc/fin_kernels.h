@@ -186,6 +186,18 @@ uint32_t fin_ec_blocks(uint32_t slots);
 int fin_launch_ec_occupied(const void* tags, uint32_t slots, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total, hipStream_t stream);
 int fin_launch_ec_gather(const void* tags, const void* counts, const void* tab_rows, uint32_t slots, uint32_t W, const uint64_t* blk_off, void* out_rows,
                          void* out_reads, hipStream_t stream);
+// fin_abundance.hip -- EM over the dense class list fin_launch_ec_gather leaves (rows uint64[C][W], reads uint64[C]).  FinAbState is the device-side
+// word the kernels stop on: zeroed before iteration 0, written by an iteration's last kernel.  fin_ab_geometry: the launch geometry of an estimate -- classes per
+// block of the first pass and its blocks, classes per chunk of the column pass and its chunks -- a function of C, W and option "ab_chunk" (0: auto) alone, which
+// is what the fixed order of every sum rests on.  fin_launch_ab_transpose: rowsT[W][C] from rows[C][W].  fin_launch_ab_iteration: iteration t in four launches
+// (x, alpha, len: 64 W doubles; q: C; part: n_chunks * 64 W; ll_part: n_ll; blk_ok: 64 u32; blk_chg: 64; trace: a double per iteration enqueued); it changes
+// nothing once state->done is set
+typedef struct FinAbState { uint32_t done, iters; double max_change, loglik; } FinAbState;
+void fin_ab_geometry(uint64_t C, uint32_t W, uint32_t ab_chunk, uint32_t* cpb, uint32_t* n_ll, uint32_t* chunk, uint32_t* n_chunks);
+int fin_launch_ab_transpose(const void* rows, uint64_t C, uint32_t W, void* rowsT, hipStream_t stream);
+int fin_launch_ab_iteration(void* state, const void* rows, const void* rowsT, const void* reads, uint64_t C, uint32_t W, uint32_t n_colors, uint32_t ab_chunk,
+                            const double* len, double n_total, double tol, double* alpha, double* x, double* q, double* part, double* ll_part, uint32_t* blk_ok,
+                            double* blk_chg, uint32_t t, double* trace, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

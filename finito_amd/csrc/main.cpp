@@ -20,6 +20,7 @@
 #include <atomic>
 #include <cerrno>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
@@ -507,9 +508,17 @@ static const char* SEARCH_HELP =
     "      --color-report FILE  from the same classes: `colour<TAB>reads<TAB>reads_only` for every colour -- the reads whose set contains the colour and\n"
     "                        the reads whose set is that colour alone --, then `unaligned<TAB>N`, the reads without a colour\n"
     "      --eq-max-classes N  room for N distinct colour sets, 1 to 67108864 (default: 1048576); more is an error\n"
+    "      --abundance FILE  from the same classes, on the GPU: expected reads per reference by EM (each class's reads split over its colours in\n"
+    "                        proportion to the current estimate, repeated). `colour<TAB>reads<TAB>share` per colour -- reads = the expected reads, share =\n"
+    "                        reads / length over its sum, both as %.10g --, then `unaligned<TAB>N`, `iterations<TAB>T<TAB>converged` (or `max_iters`) and\n"
+    "                        `loglik<TAB>L`. Goes with --eqclasses and --color-report (one accumulator for all three) and with --no-text 1.\n"
+    "      --ab-lengths FILE  one positive number per line, line number = colour: the effective length of each reference (default: all 1).\n"
+    "                        Empty lines are skipped and do not count, as in the list of --color-refs\n"
+    "      --ab-max-iters N  at most N iterations, 1 to 100000 (default: 1000)\n"
+    "      --ab-tol X        stop once no colour's reads change by more than X max(reads, 1) (default: 1e-6)\n"
     "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify,\n"
-    "                        --label-report, --colors-out, --pseudoalign, --eqclasses or --color-report): do not make or write the pair text, the other\n"
-    "                        results asked for are the only ones\n"
+    "                        --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance): do not make or write the pair\n"
+    "                        text, the other results asked for are the only ones\n"
     "  -h, --help            Print usage\n";
 
 static int build_fmin(int argc, char** argv) {
@@ -1112,18 +1121,20 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report"))
-        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses or --color-report (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance"))
+        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
-    if ((o.has("eqclasses") || o.has("color-report")) && !o.has("color-refs")) throw runtime_error("--eqclasses and --color-report want colours: --color-refs LIST");
-    const bool eq_asked = o.has("eqclasses") || o.has("color-report");
-    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses or --color-report");
-    if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses or --color-report");
-    if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses or --color-report");
+    if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
+    const bool eq_asked = o.has("eqclasses") || o.has("color-report") || o.has("abundance");
+    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
+    if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
+    if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses, --color-report or --abundance");
+    for (const char* name : {"ab-lengths", "ab-max-iters", "ab-tol"})
+        if (o.has(name) && !o.has("abundance")) throw runtime_error(string("--") + name + " is only legal together with --abundance");
     if ((o.has("classify") || o.has("label-report")) && !(o.has("label-unitigs") && o.has("labels"))) throw runtime_error("--classify and --label-report want a labelling: --label-unitigs FASTA --labels FILE");
     if ((o.has("label-unitigs") || o.has("labels")) && !o.has("classify") && !o.has("label-report")) throw runtime_error("--label-unitigs and --labels are only legal together with --classify or --label-report");
     for (const char* name : {"class-min-found", "class-min-permille", "class-min-margin"})
@@ -1146,6 +1157,15 @@ static int search_fmin(int argc, char** argv) {
     g_psa_permille = u32_option("pseudo-permille", 1000, 1000);
     const uint32_t eq_max_classes = u32_option("eq-max-classes", 1u << 20, 1u << 26);
     if (eq_max_classes == 0) throw runtime_error("--eq-max-classes wants a number from 1 to " + to_string(1u << 26));
+    const uint32_t ab_max_iters = u32_option("ab-max-iters", 1000, 100000);
+    if (ab_max_iters == 0) throw runtime_error("--ab-max-iters wants a number from 1 to 100000");
+    auto positive_number = [](const string& v, bool zero_too, double& out) {   // a finite number above 0 (or from 0 on), nothing behind it
+        size_t used = 0;
+        try { out = stod(v, &used); } catch (...) { return false; }
+        return used == v.size() && std::isfinite(out) && (out > 0.0 || (zero_too && out == 0.0));
+    };
+    double ab_tol = 1e-6;
+    if (o.has("ab-tol") && !positive_number(o.get("ab-tol"), true, ab_tol)) throw runtime_error("--ab-tol wants a number from 0 on");
     vector<string> color_refs;
     if (o.has("color-refs")) {
         color_refs = readlines(o.get("color-refs"));
@@ -1196,7 +1216,20 @@ static int search_fmin(int argc, char** argv) {
     if (!cls_file.empty()) check_writable(cls_file);
     if (!report_file.empty()) check_writable(report_file);
     const string colors_file = o.get("colors-out", ""), psa_file = o.get("pseudoalign", "");
-    const string eqc_file = o.get("eqclasses", ""), crep_file = o.get("color-report", "");
+    const string eqc_file = o.get("eqclasses", ""), crep_file = o.get("color-report", ""), ab_file = o.get("abundance", "");
+    vector<double> ab_lengths;   // --ab-lengths: one positive number per line, line number = colour; a wrong count is an error before any search
+    if (o.has("ab-lengths")) {
+        const vector<string> lines = readlines(o.get("ab-lengths"));
+        if (lines.size() != color_refs.size())
+            throw runtime_error("--ab-lengths: " + o.get("ab-lengths") + " has " + to_string(lines.size()) + " lines, --color-refs names " + to_string(color_refs.size()) + " references");
+        ab_lengths.resize(lines.size());
+        for (size_t c = 0; c < lines.size(); c++) {
+            string v = lines[c];
+            if (!v.empty() && v.back() == '\r') v.pop_back();
+            if (!positive_number(v, false, ab_lengths[c])) throw runtime_error("--ab-lengths: line " + to_string(c + 1) + " (colour " + to_string(c) + ") is not a finite positive number");
+        }
+    }
+    if (!ab_file.empty()) check_writable(ab_file);
     if (!eqc_file.empty()) check_writable(eqc_file);
     if (!crep_file.empty()) check_writable(crep_file);
     if (!colors_file.empty()) check_writable(colors_file);
@@ -1315,7 +1348,7 @@ static int search_fmin(int argc, char** argv) {
             if (!g_psa_file) throw runtime_error("Error writing to file: " + psa_file);
             g_psa_read0 = 0;
         }
-        if ((!eqc_file.empty() || !crep_file.empty()) && fin_eqclasses_create(g_colors, eq_max_classes, &g_eqc, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        if ((!eqc_file.empty() || !crep_file.empty() || !ab_file.empty()) && fin_eqclasses_create(g_colors, eq_max_classes, &g_eqc, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
@@ -1362,7 +1395,31 @@ static int search_fmin(int argc, char** argv) {
         fclose(g_psa_file); g_psa_file = nullptr;
         if (bad) throw runtime_error("Error writing to file: " + psa_file);
     }
-    if (g_eqc) {   // the classes and the tally derived from them, after the last chunk
+    if (g_eqc && !ab_file.empty()) {   // the abundances, estimated on the device from the run's classes: the rows stay there
+        char err[512] = {0};
+        const uint32_t nc = fin_colors_n_colors(g_colors);
+        vector<double> alpha(nc);
+        fin_abundance_info info;
+        if (fin_eqclasses_abundance(g_eqc, ab_lengths.empty() ? nullptr : ab_lengths.data(), ab_max_iters, ab_tol, alpha.data(), nullptr, &info, err, sizeof err) != FIN_OK)
+            throw runtime_error(err);
+        double per_len_sum = 0.0;
+        for (uint32_t c = 0; c < nc; c++) per_len_sum += alpha[c] / (ab_lengths.empty() ? 1.0 : ab_lengths[c]);
+        string text;
+        char num[96];
+        for (uint32_t c = 0; c < nc; c++) {
+            const double share = per_len_sum > 0.0 ? alpha[c] / (ab_lengths.empty() ? 1.0 : ab_lengths[c]) / per_len_sum : 0.0;
+            snprintf(num, sizeof num, "%u\t%.10g\t%.10g\n", c, alpha[c], share);
+            text += num;
+        }
+        text += "unaligned\t"; text += to_string(info.n_unaligned); text += '\n';
+        text += "iterations\t"; text += to_string(info.iters); text += info.converged ? "\tconverged\n" : "\tmax_iters\n";
+        snprintf(num, sizeof num, "loglik\t%.10g\n", info.loglik);
+        text += num;
+        ofstream cf(ab_file, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + ab_file);
+    }
+    if (g_eqc && (!eqc_file.empty() || !crep_file.empty())) {   // the classes and the tally derived from them, after the last chunk
         char err[512] = {0};
         const uint32_t W = fin_colors_words(g_colors), nc = fin_colors_n_colors(g_colors);
         uint64_t n = 0, un = 0;

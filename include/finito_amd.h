@@ -817,7 +817,7 @@ int fin_records_pseudoalign(const fin_read_record* recs, uint64_t n_reads, const
  * row is compared in the next).  So where the others say "adds on different streams stay unordered", here every add runs behind every add and reset of this
  * accumulator issued so far, on whichever stream; order, launches and mark are one step under the accumulator's lock, so adds from several host threads take
  * effect in issue order.  Resets are ordered as fin_hits_reset is.
- * Out of scope: an abundance model over the classes, partitioned indexes, fin_search_batch_multi / dist.py, the C++ mirror (a caller with several GPUs keeps an
+ * Out of scope: partitioned indexes, fin_search_batch_multi / dist.py, the C++ mirror (a caller with several GPUs keeps an
  * accumulator per replica and merges the downloads with fin_rows_eqclasses' arithmetic), a growing table, more than 4096 colours. */
 typedef struct fin_eqclasses fin_eqclasses;
 /* an empty accumulator beside the colours.  FIN_ELIMIT: max_classes is not 1 .. 2^26.  Free it before the colours. */
@@ -848,6 +848,46 @@ int fin_rows_eqclasses(const uint64_t* rows, uint64_t n_rows, uint32_t n_colors,
                        uint64_t* n_unaligned);
 /* host: the per-colour tally of n_classes classes: reads_with[n_colors], reads_only[n_colors] */
 int fin_eqclasses_color_tally(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, uint64_t* reads_with, uint64_t* reads_only);
+
+/* ---- ABUNDANCES from the equivalence classes: EM on the device ----
+ * The step every consumer of such classes runs next (kallisto's EM, mSWEEP's behind Themisto): split each class's reads over its colours in proportion to the
+ * current estimate, and repeat.  INPUTS: the classes (R_j, n_j), j < C, of one accumulator -- R_j a non-empty set of colours, n_j >= 1 its reads; N = the sum of
+ * the n_j, the aligned reads (unaligned reads take no part); optionally len[c] > 0, one finite double per colour, the effective length of reference c (NULL: all
+ * 1.0).  All arithmetic is in IEEE double.
+ *   START      alpha0_c = N / n_colors for every colour.
+ *   ITERATION  t = 0, 1, ...:  x_c = alpha_c / len[c];  d_j = the sum of x_c over c in R_j;  ll_t = the sum over j of n_j log(d_j / N);  q_j = n_j / d_j;
+ *              S_c = the sum of q_j over the classes that contain c;  alpha'_c = x_c S_c.  (The M-step factorises: class j's reads assigned to c are
+ *              n_j x_c / d_j, so their sum over the classes is x_c S_c.)
+ *   STOPPING   after iteration t the estimate has converged if |alpha'_c - alpha_c| <= tol max(alpha'_c, 1) for every colour.  iters = the smallest t + 1 at
+ *              which that holds, else max_iters; converged says which of the two it was; alpha_out = alpha after `iters` iterations; loglik = ll_(iters-1);
+ *              loglik_trace[t] = ll_t for t < iters, the entries behind that are left alone.
+ * FACTS: the alpha_c sum to N after every iteration.  A colour that is in no class has alpha = 0 from the first iteration on, exactly.  The sum of alpha'_c over
+ * c in R_j is at least n_j, so no d_j ever reaches 0 (the kernel still writes q_j = 0 where d_j is not positive, instead of dividing).  ll_t does not decrease:
+ * this is EM on a mixture with fixed component densities 1 / len[c].
+ * RESULTS: alpha is expected reads per colour; theta = alpha / N and rho = (alpha / len) / sum(alpha / len) are the caller's to derive (the Python layer does).
+ * LIMITS: 1 <= max_iters <= 100000, so the number of launches is bounded (FIN_ELIMIT above, FIN_EINVAL for 0); tol >= 0 and not NaN (FIN_EINVAL; with tol = 0
+ * the loop stops only at an exact fixed point); every len[c] finite and positive (FIN_EINVAL, the message names the colour).  Read counts above 2^53 are
+ * rounded on conversion to double.
+ * DETERMINISM: there are no floating-point atomics; every sum has a fixed order that depends only on C, W and option "ab_chunk" (classes per chunk of the column
+ * pass: 0 = auto, else rounded up to a multiple of 64), so two estimates of the same filled accumulator are bit-identical.  The table's slot order depends on
+ * claim races: two fills of the same rows may differ by rounding, and only by that. */
+typedef struct fin_abundance_info {
+    uint64_t n_classes, n_reads, n_unaligned;   /* n_reads = N */
+    uint32_t iters, converged;
+    double loglik, max_change;                  /* max_change = max_c |delta alpha_c| / max(alpha_c, 1) of the last iteration */
+} fin_abundance_info;
+/* a waiting call of fin_eqclasses_download's kind: under the accumulator's lock it waits for every add and reset issued so far, refuses a flagged accumulator
+ * with the download's codes and messages, compacts the table on the device and iterates on that dense list.  What crosses PCIe is n_colors doubles, the info and,
+ * if asked for, the trace (loglik_trace[max_iters], may be NULL); the rows never cross.  The accumulator is left as it was found.  HBM for the call, freed when
+ * it returns: 16 W + 16 bytes per class (the dense list and its word-major copy) and up to 32 MB of partial sums; FIN_ENOMEM if that is not there.  No classes: FIN_OK, alpha all
+ * 0, iters = 0, converged = 1, loglik = 0.  alpha_out[n_colors]; info may be NULL. */
+int fin_eqclasses_abundance(fin_eqclasses* e, const double* lengths, uint32_t max_iters, double tol, double* alpha_out, double* loglik_trace,
+                            fin_abundance_info* info, char* err, size_t errlen);
+/* host twin, no device: the same estimate from downloaded classes, in the order given (n_unaligned = 0: the classes do not say).  FIN_EINVAL also for a bit at or
+ * above n_colors, an empty row or a class of 0 reads; FIN_ELIMIT also for n_colors 0 or above FIN_MAX_COLORS.  n_threads <= 0: all cores; the result does not
+ * depend on it */
+int fin_classes_abundance(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, const double* lengths, uint32_t max_iters,
+                          double tol, double* alpha_out, double* loglik_trace, fin_abundance_info* info, int n_threads);
 
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
