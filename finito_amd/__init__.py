@@ -253,6 +253,16 @@ def lib():
         L.fin_batch_download_pseudo.argtypes = [vp, u64p, vp, cp, C.c_size_t]
         L.fin_search_batch_pseudoalign.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u64p, vp, u64p, cp, C.c_size_t]
         L.fin_records_pseudoalign.argtypes = [vp, u64, vp, u64, C.c_int, u64p, u64, u32, u32, u64p, vp, C.c_int]
+        L.fin_batch_pseudoalign_paired.argtypes = [vp, vp, u32, u32, cp, C.c_size_t]
+        L.fin_batch_device_pair_rows.argtypes = [vp]
+        L.fin_batch_device_pair_rows.restype = vp
+        L.fin_batch_device_pair_heads.argtypes = [vp]
+        L.fin_batch_device_pair_heads.restype = vp
+        L.fin_batch_download_pair_pseudo.argtypes = [vp, u64p, vp, cp, C.c_size_t]
+        L.fin_batch_add_eqclasses_paired.argtypes = [vp, vp, u32, u32, vp, cp, C.c_size_t]
+        L.fin_search_batch_pseudoalign_paired.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, u64p, vp, u64p, cp, C.c_size_t]
+        L.fin_search_batch_add_eqclasses_paired.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, cp, C.c_size_t]
+        L.fin_records_pseudoalign_paired.argtypes = [vp, u64, vp, u64, C.c_int, u64p, u64, u32, u32, u32, u64p, vp, C.c_int]
         L.fin_eqclasses_create.argtypes = [vp, u64, C.POINTER(vp), cp, C.c_size_t]
         L.fin_eqclasses_reset.argtypes = [vp, vp]
         L.fin_eqclasses_free.argtypes = [vp]
@@ -509,6 +519,23 @@ class Batch:
     def device_pseudo_ptrs(self):
         """(rows, heads) device pointers, 0 before pseudoalign()"""
         return int(self.L.fin_batch_device_pseudo_rows(self.h) or 0), int(self.L.fin_batch_device_pseudo_heads(self.h) or 0)
+
+    def pseudoalign_pairs(self, colors, permille=1000, both=False):
+        """the most recent run's reads as interleaved mates -- fragment f is reads 2f and 2f + 1 --, one colour row per FRAGMENT under a colour matrix, made on
+        the device (fin_batch_pseudoalign_paired + fin_batch_download_pair_pseudo): (rows uint64[F, W], heads PAIR_PSEUDO_DTYPE[F]).  The definition of
+        pseudoalign() over both mates' slots together; at 1000 the AND of the mates' rows where both have coloured k-mers, else the row of the one that has; at 0
+        the OR.  both: the row is empty unless both mates have a coloured k-mer (FIN_PAIR_BOTH).  The per-read rows of pseudoalign() are left alone"""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_pseudoalign_paired(self.h, colors.h, _permille("Batch.pseudoalign_pairs", permille), FIN_PAIR_BOTH if both else FIN_PAIR_ANY, err, 512), err)
+        nf = self.n_reads // 2
+        rows = np.zeros((max(nf, 1), colors.words), dtype=np.uint64)
+        heads = np.zeros(max(nf, 1), dtype=PAIR_PSEUDO_DTYPE)
+        _check(self.L.fin_batch_download_pair_pseudo(self.h, rows.ctypes.data_as(C.POINTER(C.c_uint64)), heads.ctypes.data_as(C.c_void_p), err, 512), err)
+        return rows[:nf], heads[:nf]
+
+    def device_pair_ptrs(self):
+        """(rows, heads) device pointers of the fragments' rows, 0 before pseudoalign_pairs()"""
+        return int(self.L.fin_batch_device_pair_rows(self.h) or 0), int(self.L.fin_batch_device_pair_heads(self.h) or 0)
 
     def pipeline_counts(self, n=64):
         """kernel 4's queue counters of the last run (fin_batch_pipeline_counts)"""
@@ -820,6 +847,14 @@ class EqClasses:
         _check(self.L.fin_batch_add_eqclasses(batch.h, self.h, _permille("EqClasses.add", permille), C.c_void_p(stream or 0), err, 512), err)
         return self
 
+    def add_pairs(self, batch, permille=1000, both=False, stream=None):
+        """the batch's most recent run as interleaved mates: one row per FRAGMENT, made by Batch.pseudoalign_pairs' kernel and added, on a HIP stream; no sync
+        (fin_batch_add_eqclasses_paired).  A fragment is one "read" of its class"""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_add_eqclasses_paired(batch.h, self.h, _permille("EqClasses.add_pairs", permille), FIN_PAIR_BOTH if both else FIN_PAIR_ANY,
+                                                     C.c_void_p(stream or 0), err, 512), err)
+        return self
+
     def add_rows(self, ptr, n_rows, stream=None):
         """rows any producer left in HBM: a device pointer to uint64[n_rows, W], valid until the add has finished (fin_eqclasses_add_rows)"""
         if not 0 <= int(n_rows) <= 0xFFFFFFFFFFFFFFFF:
@@ -835,6 +870,15 @@ class EqClasses:
         err = C.create_string_buffer(512)
         _check(self.L.fin_search_batch_add_eqclasses(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
                                                      int(strands), self.h, _permille("EqClasses.add_reads", permille), err, 512), err)
+        return self
+
+    def add_read_pairs(self, reads, permille=1000, both=False, strands=FIN_MERGED):
+        """add_reads for interleaved mates: every fragment's row is added; no sub-batch splits a pair (fin_search_batch_add_eqclasses_paired)"""
+        bases, offsets = flatten(reads)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_add_eqclasses_paired(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                            len(offsets) - 1, int(strands), self.h, _permille("EqClasses.add_read_pairs", permille),
+                                                            FIN_PAIR_BOTH if both else FIN_PAIR_ANY, err, 512), err)
         return self
 
     def reset(self, stream=None):
@@ -1424,6 +1468,22 @@ class FinimizerIndex:
                                                    heads.ctypes.data_as(C.c_void_p), C.byref(npos), err, 512), err)
         return (rows[:n] if want_rows else None), heads[:n], int(npos.value)
 
+    def pseudoalign_pairs(self, reads, colors, permille=1000, both=False, strands=FIN_MERGED, want_rows=True):
+        """(rows uint64[F, W] or None, heads PAIR_PSEUDO_DTYPE[F], the coloured k-mers found): interleaved mates pseudoaligned as fragments from host buffers,
+        sub-batches pipelined and cut between pairs only (fin_search_batch_pseudoalign_paired)"""
+        bases, offsets = flatten(reads)
+        n = len(offsets) - 1
+        nf = n // 2
+        rows = np.zeros((max(nf, 1), colors.words), dtype=np.uint64) if want_rows else None
+        heads = np.zeros(max(nf, 1), dtype=PAIR_PSEUDO_DTYPE)
+        npos = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_pseudoalign_paired(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands),
+                                                          colors.h, _permille("pseudoalign_pairs", permille), FIN_PAIR_BOTH if both else FIN_PAIR_ANY,
+                                                          rows.ctypes.data_as(C.POINTER(C.c_uint64)) if want_rows else None, heads.ctypes.data_as(C.c_void_p),
+                                                          C.byref(npos), err, 512), err)
+        return (rows[:nf] if want_rows else None), heads[:nf], int(npos.value)
+
     def unitig_numbers(self, unitigs):
         """fin_index_unitig_numbers: uint32[len(unitigs)] -- the index's number of each given unitig sequence (the index renumbers its input); raises for a
         sequence that is not a unitig of this index"""
@@ -1529,6 +1589,8 @@ READ_SUMMARY_DTYPE = np.dtype([("n_found", np.uint32), ("n_segments", np.uint32)
 READ_CLASS_DTYPE = np.dtype([("label", np.uint32), ("n_best", np.uint32), ("n_second", np.uint32), ("n_labelled", np.uint32)])   # fin_read_class
 FIN_NO_LABEL = 0xFFFFFFFF
 READ_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), ("n_colors", np.uint32), ("reserved", np.uint32)])   # fin_read_pseudo
+PAIR_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), ("n_colors", np.uint32), ("n_colored_first", np.uint32)])   # fin_pair_pseudo
+FIN_PAIR_ANY, FIN_PAIR_BOTH = 0, 1
 FIN_MAX_COLORS = 4096
 DEPTH_STAT_DTYPE = np.dtype([("sum", np.uint64), ("max", np.uint32), ("n_at_least", np.uint32)])            # fin_depth_stat
 
@@ -1804,6 +1866,28 @@ def records_pseudoalign(recs, stream, k, bits, n_colors, permille=1000, n_thread
         raise FinitoError(rc, "fin_records_pseudoalign: n_colors outside 1 .. 4096, permille above 1000, a bit at or above n_colors, a unitig number outside the "
                               "matrix, or records and stream that do not belong together")
     return rows[: len(r)], heads[: len(r)]
+
+
+def records_pseudoalign_pairs(recs, stream, k, bits, n_colors, permille=1000, both=False, n_threads=0, mode=None):
+    """host: (rows uint64[F, W], heads PAIR_PSEUDO_DTYPE[F]) from the records + stream of interleaved mates (fin_records_pseudoalign_paired) -- the CPU statement
+    of Batch.pseudoalign_pairs.  mode (FIN_PAIR_ANY / FIN_PAIR_BOTH) overrides `both`"""
+    r = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+    st = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1, 2)
+    W = (int(n_colors) + 63) // 64 if 0 <= int(n_colors) <= 0xFFFFFFFF else 0
+    b = np.ascontiguousarray(bits, dtype=np.uint64).reshape(-1, max(W, 1))
+    m = (FIN_PAIR_BOTH if both else FIN_PAIR_ANY) if mode is None else int(mode)
+    if not (0 <= int(n_colors) <= 0xFFFFFFFF and 0 <= int(permille) <= 0xFFFFFFFF and 0 <= m <= 0xFFFFFFFF):
+        raise FinitoError(FIN_EINVAL, "records_pseudoalign_pairs: n_colors, permille and mode are unsigned 32-bit numbers")
+    nf = len(r) // 2
+    rows = np.zeros((max(nf, 1), max(W, 1)), dtype=np.uint64)
+    heads = np.zeros(max(nf, 1), dtype=PAIR_PSEUDO_DTYPE)
+    rc = lib().fin_records_pseudoalign_paired(r.ctypes.data_as(C.c_void_p), len(r), st.ctypes.data_as(C.c_void_p), len(st), int(k), b.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                              len(b), int(n_colors), int(permille), m, rows.ctypes.data_as(C.POINTER(C.c_uint64)), heads.ctypes.data_as(C.c_void_p),
+                                              int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_pseudoalign_paired: an odd number of reads, a mode that is neither FIN_PAIR_ANY nor FIN_PAIR_BOTH, n_colors outside 1 .. 4096, "
+                              "permille above 1000, a bit at or above n_colors, a unitig number outside the matrix, or records and stream that do not belong together")
+    return rows[:nf], heads[:nf]
 
 
 def rows_eqclasses(rows, n_colors):

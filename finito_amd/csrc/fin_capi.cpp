@@ -744,6 +744,8 @@ struct fin_batch {
     void* d_cls = nullptr; size_t cap_cls = 0; bool cls_ready = false; uint64_t cls_labels = 0;
     // per-read colour rows and heads under a colour matrix (fin_batch_pseudoalign): kept and only grown; psa_words = the matrix's words per row
     void* d_psa_rows = nullptr; size_t cap_psa_rows = 0; void* d_psa_heads = nullptr; size_t cap_psa_heads = 0; bool psa_ready = false; uint32_t psa_words = 0;
+    // per-fragment colour rows and heads (fin_batch_pseudoalign_paired): buffers of their own, kept and only grown; forgotten whenever the per-read rows are
+    void* d_pair_rows = nullptr; size_t cap_pair_rows = 0; void* d_pair_heads = nullptr; size_t cap_pair_heads = 0; bool pair_ready = false; uint32_t pair_words = 0;
     uint64_t text_bytes = 0;
     // kernel 4: the queue counters of the most recent finished run, copied to page-locked memory behind every run: the next run launches only
     // as many stream / walk rounds as that one needed, plus one (fin_launch_search_v4's `rounds`)
@@ -779,7 +781,7 @@ void fin_batch_free(fin_batch* b) {
     if (b->ev_ctr) (void)hipEventDestroy(b->ev_ctr);
     (void)hipFree(b->d_cstream); (void)hipFree(b->d_frec); (void)hipFree(b->d_seg); (void)hipFree(b->d_text); (void)hipFree(b->d_last_bits); (void)hipFree(b->d_blk_sum); (void)hipFree(b->d_blk_off); (void)hipFree(b->d_total);
     (void)hipFree(b->d_sgm_cnt); (void)hipFree(b->d_sgm_bsum); (void)hipFree(b->d_sgm_boff); (void)hipFree(b->d_sgm_offs); (void)hipFree(b->d_sgm);
-    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls); (void)hipFree(b->d_psa_rows); (void)hipFree(b->d_psa_heads);
+    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls); (void)hipFree(b->d_psa_rows); (void)hipFree(b->d_psa_heads); (void)hipFree(b->d_pair_rows); (void)hipFree(b->d_pair_heads);
     (void)hipFree(b->d_ovf_list); (void)hipFree(b->d_ovf_count); (void)hipFree(b->d_ovf_scratch); (void)hipFree(b->d_count);
     for (auto& r : b->runs) for (auto& e : r.e) (void)hipEventDestroy(e);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -903,7 +905,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     //  decoding, inside its timed region, search_fmin.hh:46-71 -- is the first kernel of every step, see fin_batch_run)
     b->n_chunks = n_chunks; b->max_read_len = max_len;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "upload");
-    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false;
+    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false;
     b->rounds_hint = 0; b->ctr_pending = false;   // (new reads: nothing is known about the rounds they need)
     b->text_reads_state = 0;
     return FIN_OK;
@@ -947,7 +949,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     b->dev.budget_mult = (uint32_t)optv(b->idx, O_epoch_budget_mult); b->dev.budget_add = (uint32_t)optv(b->idx, O_epoch_budget_add);
     b->dev.ovf_cap = (uint32_t)std::min<uint64_t>(b->cap_ovf_list / 4, 0xFFFFFFFFull);
     if (const int64_t forced = optv(b->idx, O_debug_ovf_cap)) b->dev.ovf_cap = (uint32_t)std::min<int64_t>(forced, (int64_t)b->dev.ovf_cap);   // (tests: a tiny list)
-    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false;
+    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false;
     b->dev.pp_seg = (uint32_t)optv(b->idx, O_debug_pp_seg);
     b->dev.pp_max_len = (uint32_t)std::min<uint64_t>(b->max_read_len, 0xFFFFFFFFull);
     b->dev.pp_park = (uint32_t)optv(b->idx, O_pp_park);
@@ -1083,7 +1085,7 @@ int fin_batch_set_pairs(fin_batch* b, const int32_t* pairs, char* err, size_t er
     HIPCHK(hipSetDevice(b->device));
     if (b->last_stream) HIPCHK(hipStreamSynchronize(b->last_stream));
     HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
-    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false;   // (the records of the last run say nothing about these pairs)
+    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false;   // (the records of the last run say nothing about these pairs)
     return FIN_OK;
 }
 
@@ -1124,7 +1126,7 @@ int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32
     if (b->n_reads) HIPCHK(hipMemcpy(b->d_frec, recs, (size_t)b->n_reads * sizeof(FinFastRec), hipMemcpyHostToDevice));
     if (pairs && b->n_kmers) HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
     // last_frec / last_text_only stay as the run left them (a text-only batch still refuses its pairs); whatever was made from the old records goes
-    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false;
+    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false;
     b->rec_ready = false; b->rec_passthrough = false; b->rec_stream_pairs = 0;
     return FIN_OK;
 }
@@ -2211,6 +2213,118 @@ int fin_records_pseudoalign(const fin_read_record* recs, uint64_t n_reads, const
     return ok ? FIN_OK : FIN_EINVAL;
 }
 
+// ---- paired-end pseudoalignment: one colour row per fragment (fin_paired.hip) -------------------------------------------------------------
+static_assert(sizeof(fin_pair_pseudo) == 16, "a fragment's pseudoalignment head is 16 bytes");
+int fin_batch_pseudoalign_paired(fin_batch* b, const fin_colors* c, uint32_t permille, uint32_t mode, char* err, size_t errlen) {
+    if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (mode != FIN_PAIR_ANY && mode != FIN_PAIR_BOTH) { set_err(err, errlen, "mode is FIN_PAIR_ANY (0) or FIN_PAIR_BOTH (1)"); return FIN_EINVAL; }
+    if (!b->ran) { set_err(err, errlen, "this batch has not run: there is nothing to pseudoalign (fin_batch_run first)"); return FIN_EINVAL; }
+    if (b->idx != c->idx || b->device != c->device) { set_err(err, errlen, "batch and colours belong to different indexes or devices"); return FIN_EINVAL; }
+    if (b->n_reads & 1u) { set_err(err, errlen, "paired pseudoalignment wants interleaved mates: " + std::to_string(b->n_reads) + " reads are an odd number"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    b->pair_ready = false;
+    if (b->n_kmers != 0) if (const int orc = batch_overrun_check(b, st, err, errlen)) return orc;   // a run without results: nothing is written
+    const uint32_t nf = (uint32_t)(b->n_reads / 2);
+    if (batch_grow(b, &b->d_pair_rows, b->cap_pair_rows, (size_t)nf * c->words * 8 + 16, st) || batch_grow(b, &b->d_pair_heads, b->cap_pair_heads, (size_t)nf * 16 + 16, st)) {
+        set_err(err, errlen, "out of device memory (colour rows of the fragments)"); return FIN_ENOMEM;
+    }
+    if (const int orc = const_cast<fin_colors*>(c)->pend.order(st, err, errlen)) return orc;   // the adds to the matrix, on whichever streams, come first
+    const int rc = fin_launch_pseudoalign_paired(b->n_kmers != 0 && b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, nf, b->dev.k, c->d_bits,
+                                                 c->words, (uint32_t)c->n_unitigs, permille, mode, b->d_pair_rows, b->d_pair_heads, st);
+    if (rc != 0) { set_err(err, errlen, std::string("paired pseudoalignment kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    b->pair_ready = true; b->pair_words = c->words;
+    return FIN_OK;
+}
+
+void* fin_batch_device_pair_rows(const fin_batch* b) { return b && b->pair_ready ? b->d_pair_rows : nullptr; }
+void* fin_batch_device_pair_heads(const fin_batch* b) { return b && b->pair_ready ? b->d_pair_heads : nullptr; }
+
+int fin_batch_download_pair_pseudo(fin_batch* b, uint64_t* rows_out, fin_pair_pseudo* heads_out, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->pair_ready) { set_err(err, errlen, "fin_batch_pseudoalign_paired first"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    const size_t nf = (size_t)(b->n_reads / 2);
+    if (nf && rows_out) HIPCHK(hipMemcpyAsync(rows_out, b->d_pair_rows, nf * b->pair_words * 8, hipMemcpyDeviceToHost, st));
+    if (nf && heads_out) HIPCHK(hipMemcpyAsync(heads_out, b->d_pair_heads, nf * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
+// host: the definition over the two mates' segments -- fin_records_pseudoalign with a fragment's segments pooled and the first mate's coloured slots kept apart
+int fin_records_pseudoalign_paired(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint64_t* bits,
+                                   uint64_t n_unitigs, uint32_t n_colors, uint32_t permille, uint32_t mode, uint64_t* rows_out, fin_pair_pseudo* heads_out, int n_threads) {
+    const uint64_t nf = n_reads / 2;
+    if ((n_reads && !recs) || (nf && (!rows_out || !heads_out)) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !bits)) return FIN_EINVAL;
+    if (n_colors == 0 || n_colors > FIN_MAX_COLORS) return FIN_ELIMIT;
+    if (permille > 1000u || (n_reads & 1u) || (mode != FIN_PAIR_ANY && mode != FIN_PAIR_BOTH)) return FIN_EINVAL;
+    const uint32_t W = (n_colors + 63u) / 64u;
+    if (colors_first_stray(bits, n_unitigs, n_colors, W) != n_unitigs) return FIN_EINVAL;
+    int T = n_threads > 0 ? n_threads : fin_host_threads();
+    if ((uint64_t)T > nf / 1024 + 1) T = (int)(nf / 1024 + 1);
+    std::vector<uint64_t> str0((size_t)T + 1, 0);
+    auto bounds = [&](int t) { return std::make_pair(nf * (uint64_t)t / (uint64_t)T, nf * (uint64_t)(t + 1) / (uint64_t)T); };   // (in fragments)
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
+        const auto lh = bounds(t);
+        uint64_t sp = 0;
+        for (uint64_t r = 2 * lh.first; r < 2 * lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
+        str0[(size_t)t + 1] = sp;
+    }
+    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
+    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
+    bool ok = true;
+#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
+    for (int t = 0; t < T; t++) {
+        const auto lh = bounds(t);
+        uint64_t sp = str0[(size_t)t];
+        bool good = true;
+        std::vector<std::pair<uint32_t, uint32_t>> segs;   // (unitig, slots) per segment, the first mate's first
+        std::vector<uint64_t> cnt((size_t)W * 64);
+        for (uint64_t f = lh.first; f < lh.second && good; f++) {
+            segs.clear();
+            size_t n_first_segs = 0;
+            auto emit = [&](int32_t u, int32_t, uint32_t, int32_t len) {
+                if ((uint64_t)(uint32_t)u >= n_unitigs) { good = false; return; }
+                segs.push_back({(uint32_t)u, (uint32_t)(len < 0 ? -(int64_t)len : (int64_t)len)});
+            };
+            for (uint64_t r = 2 * f; r < 2 * f + 2; r++) {
+                const fin_read_record& R = recs[r];
+                const uint32_t kind = R.meta >> 16;
+                if (kind == 0u) { good = segment_slots(stream_pairs + 2 * sp, R.nk, emit) && good; sp += R.nk; }
+                else if (kind == 1u) segment_record(R, k, emit);
+                if (r == 2 * f) n_first_segs = segs.size();
+            }
+            std::fill(cnt.begin(), cnt.end(), 0);
+            uint64_t n_found = 0, n_colored = 0, n_first = 0;
+            for (size_t q = 0; q < segs.size(); q++) {
+                const auto& sg = segs[q];
+                n_found += sg.second;
+                const uint64_t* row = bits + (uint64_t)sg.first * W;
+                bool ne = false;
+                for (uint32_t w = 0; w < W; w++) {
+                    uint64_t x = row[w];
+                    if (x) ne = true;
+                    for (; x; x &= x - 1) cnt[(size_t)w * 64 + (size_t)__builtin_ctzll(x)] += sg.second;
+                }
+                if (ne) { n_colored += sg.second; if (q < n_first_segs) n_first += sg.second; }
+            }
+            const bool keep = mode == FIN_PAIR_ANY || (n_first != 0 && n_colored != n_first);
+            uint32_t pc = 0;
+            for (uint32_t w = 0; w < W; w++) {
+                uint64_t o = 0;
+                if (keep) for (uint32_t q = 0; q < 64u; q++) { const uint64_t c = cnt[(size_t)w * 64 + q]; if (c >= 1 && 1000ull * c >= (uint64_t)permille * n_colored) o |= 1ull << q; }
+                rows_out[f * W + w] = o; pc += (uint32_t)__builtin_popcountll(o);
+            }
+            heads_out[f] = fin_pair_pseudo{(uint32_t)n_found, (uint32_t)n_colored, pc, (uint32_t)n_first};
+        }
+        ok = good && ok;
+    }
+    return ok ? FIN_OK : FIN_EINVAL;
+}
+
 // ---- equivalence classes of pseudoaligned reads (fin_eqclasses.hip) ---------------------------------------------------------------------
 struct fin_eqclasses {
     const fin_colors* colors = nullptr;
@@ -2307,6 +2421,22 @@ int fin_batch_add_eqclasses(fin_batch* b, fin_eqclasses* e, uint32_t permille, v
         HIPCHK(rc);
     }
     return ec_add_rows(e, b->d_psa_rows, b->n_reads, st, err, errlen);
+}
+
+int fin_batch_add_eqclasses_paired(fin_batch* b, fin_eqclasses* e, uint32_t permille, uint32_t mode, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !e) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    // always, as fin_batch_add_eqclasses does: the batch does not remember which matrix, threshold and mode its rows belong to
+    if (const int rc = fin_batch_pseudoalign_paired(b, e->colors, permille, mode, err, errlen)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (st != b->last_stream) {   // the rows were made on the run's stream, behind the run: the add waits for them
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        hipError_t rc = hipEventRecord(ev, b->last_stream);
+        if (rc == hipSuccess) rc = hipStreamWaitEvent(st, ev, 0);
+        (void)hipEventDestroy(ev);   // (released once it has completed)
+        HIPCHK(rc);
+    }
+    return ec_add_rows(e, b->d_pair_rows, b->n_reads / 2, st, err, errlen);   // a fragment is one row
 }
 
 int fin_eqclasses_stats(fin_eqclasses* e, uint64_t out[4], char* err, size_t errlen) {
@@ -3080,6 +3210,9 @@ struct TextSink {
     const fin_colors* psa = nullptr; uint32_t psa_permille = 0; uint64_t* psa_rows = nullptr; fin_read_pseudo* psa_heads = nullptr;
     // (equivalence classes when `eqc` is set: fin_search_batch_add_eqclasses -- every sub-batch is pseudoaligned and added on the device, nothing comes back)
     fin_eqclasses* eqc = nullptr; uint32_t eqc_permille = 0;
+    // (fragments when `group` is 2: fin_search_batch_pseudoalign_paired / _add_eqclasses_paired -- the reads are interleaved mates, a sub-batch ends only after an
+    //  even number of reads counted from the range's first, psa_pheads takes the fragments' heads and rows and heads land at the fragments' numbers)
+    uint64_t group = 1; uint32_t pair_mode = 0; fin_pair_pseudo* psa_pheads = nullptr;
     std::vector<uint64_t> len; std::vector<char> known;
     std::mutex mu; std::condition_variable cv;
     uint64_t total = 0;
@@ -3090,18 +3223,22 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
     // A device batch addresses k-mers and bases with 32 bits (also bounds the HBM one sub-batch takes)
     const uint64_t MAX_BASES = 1ull << 31, MAX_READS = 1ull << 26;
     const uint64_t MAX_KMERS = std::min<uint64_t>((uint64_t)optv(idx, O_max_batch_kmers), (uint64_t)optv(idx, O_pipeline_kmers));
-    const uint64_t k = idx->k;
+    const uint64_t k = idx->k, group = ts ? ts->group : 1;
     struct Sub { uint64_t lo, hi, pair_off; };
     std::vector<Sub> subs;
     {
         uint64_t pair_off = 0;
         do {
             uint64_t h2 = lo, nb = 0, nk = 0;
-            while (h2 < hi) {
-                const uint64_t len = offsets[h2 + 1] - offsets[h2];
-                const uint64_t kk = len >= k ? len - k + 1 : 0;
-                if (h2 > lo && (nb + len > MAX_BASES || nk + kk > MAX_KMERS || h2 - lo >= MAX_READS)) break;
-                nb += len; nk += kk; h2++;
+            while (h2 < hi) {   // a group of `group` reads at a time (1, or 2: a pair of mates is never split); the first group is always taken
+                const uint64_t g2 = std::min<uint64_t>(h2 + group, hi);
+                uint64_t glen = 0, gkk = 0;
+                for (uint64_t r = h2; r < g2; r++) {
+                    const uint64_t len = offsets[r + 1] - offsets[r];
+                    glen += len; gkk += len >= k ? len - k + 1 : 0;
+                }
+                if (h2 > lo && (nb + glen > MAX_BASES || nk + gkk > MAX_KMERS || g2 - lo > MAX_READS)) break;
+                nb += glen; nk += gkk; h2 = g2;
             }
             subs.push_back(Sub{lo, h2, pair_off});
             pair_off += nk; lo = h2;
@@ -3190,6 +3327,16 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
             } else
             if (rc == FIN_OK && ts && ts->paint) {
                 rc = fin_batch_add_colors(b, ts->paint, ts->paint_color, (void*)b->own_stream, e, sizeof e);
+            } else
+            if (rc == FIN_OK && ts && ts->psa && ts->group == 2) {
+                rc = fin_batch_pseudoalign_paired(b, ts->psa, ts->psa_permille, ts->pair_mode, e, sizeof e);
+                const uint64_t at = (s.lo - ts->read0) / 2;   // (every sub-batch begins at an even read)
+                fin_pair_pseudo* const dst = ts->psa_pheads + at;
+                if (rc == FIN_OK) rc = fin_batch_download_pair_pseudo(b, ts->psa_rows ? ts->psa_rows + at * fin_colors_words(ts->psa) : nullptr, dst, e, sizeof e);
+                if (rc == FIN_OK) for (uint64_t f = 0; f < (s.hi - s.lo) / 2; f++) pos += dst[f].n_colored;
+            } else
+            if (rc == FIN_OK && ts && ts->eqc && ts->group == 2) {
+                rc = fin_batch_add_eqclasses_paired(b, ts->eqc, ts->eqc_permille, ts->pair_mode, (void*)b->own_stream, e, sizeof e);
             } else
             if (rc == FIN_OK && ts && ts->psa) {
                 rc = fin_batch_pseudoalign(b, ts->psa, ts->psa_permille, e, sizeof e);
@@ -3457,6 +3604,22 @@ int fin_search_batch_pseudoalign(const fin_index* idx, const char* bases, const 
     return rc;
 }
 
+int fin_search_batch_pseudoalign_paired(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_colors* c,
+                                        uint32_t permille, uint32_t mode, uint64_t* rows_out, fin_pair_pseudo* heads_out, uint64_t* n_positive, char* err, size_t errlen) {
+    if (!idx || !offsets || !c || (n_reads >= 2 && !heads_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (c->idx != idx) { set_err(err, errlen, "the colours belong to another index"); return FIN_EINVAL; }
+    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (mode != FIN_PAIR_ANY && mode != FIN_PAIR_BOTH) { set_err(err, errlen, "mode is FIN_PAIR_ANY (0) or FIN_PAIR_BOTH (1)"); return FIN_EINVAL; }
+    if (n_reads & 1u) { set_err(err, errlen, "paired pseudoalignment wants interleaved mates: " + std::to_string(n_reads) + " reads are an odd number"); return FIN_EINVAL; }
+    if (n_positive) *n_positive = 0;
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.psa = c; ts.psa_permille = permille; ts.psa_rows = rows_out; ts.psa_pheads = heads_out; ts.read0 = 0; ts.group = 2; ts.pair_mode = mode;
+    uint64_t pos = 0;
+    const int rc = search_range_on(idx, c->device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
+    if (rc == FIN_OK && n_positive) *n_positive = pos;
+    return rc;
+}
+
 int fin_search_batch_add_classes(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_labels* l, uint32_t min_found,
                                  uint32_t min_permille, uint32_t min_margin, char* err, size_t errlen) {
     if (!idx || !offsets || !l || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
@@ -3474,6 +3637,18 @@ int fin_search_batch_add_eqclasses(const fin_index* idx, const char* bases, cons
     if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
     if (n_reads == 0) return FIN_OK;
     TextSink ts; ts.eqc = e; ts.eqc_permille = permille;
+    return search_range_on(idx, e->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+}
+
+int fin_search_batch_add_eqclasses_paired(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_eqclasses* e,
+                                          uint32_t permille, uint32_t mode, char* err, size_t errlen) {
+    if (!idx || !offsets || !e || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    if (e->idx != idx) { set_err(err, errlen, "the equivalence classes belong to another index"); return FIN_EINVAL; }
+    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (mode != FIN_PAIR_ANY && mode != FIN_PAIR_BOTH) { set_err(err, errlen, "mode is FIN_PAIR_ANY (0) or FIN_PAIR_BOTH (1)"); return FIN_EINVAL; }
+    if (n_reads & 1u) { set_err(err, errlen, "paired pseudoalignment wants interleaved mates: " + std::to_string(n_reads) + " reads are an odd number"); return FIN_EINVAL; }
+    if (n_reads == 0) return FIN_OK;
+    TextSink ts; ts.eqc = e; ts.eqc_permille = permille; ts.group = 2; ts.pair_mode = mode;
     return search_range_on(idx, e->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
 }
 

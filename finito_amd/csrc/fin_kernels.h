@@ -176,6 +176,10 @@ int fin_launch_colors_add(const void* frec, const uint64_t* out_offs, const void
                           uint32_t color, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, hipStream_t stream);
 int fin_launch_pseudoalign(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const void* bits, uint32_t W,
                            uint32_t n_unitigs, uint32_t permille, void* rows, void* heads, hipStream_t stream);
+// fin_paired.hip -- one colour row per FRAGMENT (reads 2f and 2f + 1 of the step): rows uint64[n_frags * W] and heads {n_found, n_coloured, popcount,
+// n_coloured of the first mate} under the threshold permille; mode 0: any mate, 1: the row is zero unless both mates have a coloured slot
+int fin_launch_pseudoalign_paired(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_frags, uint32_t k, const void* bits, uint32_t W,
+                                  uint32_t n_unitigs, uint32_t permille, uint32_t mode, void* rows, void* heads, hipStream_t stream);
 // fin_eqclasses.hip -- equivalence classes of colour rows: an open-addressing table of 2^lg slots (tags, counts: a u64 per slot; tab_rows: W u64 per slot; ctr:
 // 8 u64 -- rows added, unaligned, classes, rows through the serial pass, flags, the collision list's length).  fin_launch_ec_add: rows uint64[n_rows * W] are added
 // in three launches (claim, verify and count, collisions serially); slot_of and coll: n_rows u32 of scratch each.  tag_bits / combine: options "ec_tag_bits" and

@@ -516,6 +516,13 @@ static const char* SEARCH_HELP =
     "                        Empty lines are skipped and do not count, as in the list of --color-refs\n"
     "      --ab-max-iters N  at most N iterations, 1 to 100000 (default: 1000)\n"
     "      --ab-tol X        stop once no colour's reads change by more than X max(reads, 1) (default: 1e-6)\n"
+    "      --paired arg      1: the query file holds INTERLEAVED mates, records 2f and 2f + 1 are fragment f (needs --color-refs). Chunks are cut after an\n"
+    "                        even number of records; a file with an odd number of records is an error. --pseudoalign then writes one line per fragment,\n"
+    "                        `fragment<TAB>k-mers<TAB>found<TAB>coloured<TAB>coloured_first<TAB>c1,c2,...` -- the k-mers of both mates together, coloured_first = the\n"
+    "                        first mate's share of coloured --, and --eqclasses, --color-report and --abundance count fragments: the definition of\n"
+    "                        --pseudoalign over both mates' k-mers together (at P = 1000 the intersection of the mates' sets where both have coloured\n"
+    "                        k-mers). Everything else is per read as before\n"
+    "      --pair-both arg   1 (only with --paired 1): a fragment has colours only if BOTH mates have a coloured k-mer\n"
     "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify,\n"
     "                        --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance): do not make or write the pair\n"
     "                        text, the other results asked for are the only ones\n"
@@ -840,6 +847,8 @@ static FILE* g_psa_file = nullptr;
 static uint64_t g_psa_read0 = 0;
 static uint32_t g_psa_permille = 1000;
 static vector<uint64_t> g_psa_rows; static vector<fin_read_pseudo> g_psa_heads; static string g_psa_text;
+// --paired 1: the query's records are interleaved mates; --pseudoalign, --eqclasses, --color-report and --abundance take fragments (fin_search_batch_*_paired)
+static bool g_paired = false; static uint32_t g_pair_mode = FIN_PAIR_ANY; static vector<fin_pair_pseudo> g_pair_heads; static string g_query_name;
 static void append_colors(string& t, const uint64_t* row, uint32_t W) {
     bool any = false;
     for (uint32_t w = 0; w < W; w++)
@@ -849,6 +858,25 @@ static void append_colors(string& t, const uint64_t* row, uint32_t W) {
 static void pseudoalign_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads, const uint64_t* pair_off) {
     char err[512] = {0};
     const uint32_t W = fin_colors_words(g_colors);
+    if (g_paired) {   // (the parser cuts chunks after an even number of records)
+        const uint64_t nf = n_reads / 2;
+        g_psa_rows.resize((size_t)nf * W + 1); g_pair_heads.resize(nf + 1);
+        if (fin_search_batch_pseudoalign_paired(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_colors, g_psa_permille, g_pair_mode, g_psa_rows.data(),
+                                                g_pair_heads.data(), nullptr, err, sizeof err) != FIN_OK)
+            throw runtime_error(err);
+        string& t = g_psa_text;
+        t.clear();
+        for (uint64_t f = 0; f < nf; f++) {
+            const fin_pair_pseudo& S = g_pair_heads[f];
+            t += to_string(g_psa_read0 + f); t += '\t'; t += to_string(pair_off[2 * f + 2] - pair_off[2 * f]); t += '\t'; t += to_string(S.n_found); t += '\t';
+            t += to_string(S.n_colored); t += '\t'; t += to_string(S.n_colored_first); t += '\t';
+            append_colors(t, g_psa_rows.data() + (size_t)f * W, W);
+            t += '\n';
+        }
+        if (!t.empty() && fwrite(t.data(), 1, t.size(), g_psa_file) != t.size()) throw runtime_error("Error writing the pseudoalignment file");
+        g_psa_read0 += nf;
+        return;
+    }
     g_psa_rows.resize((size_t)n_reads * W + 1); g_psa_heads.resize(n_reads + 1);
     if (fin_search_batch_pseudoalign(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_colors, g_psa_permille, g_psa_rows.data(), g_psa_heads.data(), nullptr, err,
                                      sizeof err) != FIN_OK)
@@ -897,6 +925,10 @@ static void color_by_search(const FinimizerIndex& index, const string& fasta, ui
 static fin_eqclasses* g_eqc = nullptr;
 static void eqclasses_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
     char err[512] = {0};
+    if (g_paired) {
+        if (fin_search_batch_add_eqclasses_paired(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_eqc, g_psa_permille, g_pair_mode, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        return;
+    }
     if (fin_search_batch_add_eqclasses(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_eqc, g_psa_permille, err, sizeof err) != FIN_OK) throw runtime_error(err);
 }
 static bool g_no_text = false;
@@ -939,7 +971,11 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                 char* dst = c->bases.get(BATCH_BASES);
                 for (;;) {
                     const int64_t len = reader->get_next_read_to_buffer();
-                    if (len == 0) { more = false; break; }
+                    if (len == 0) {
+                        if (g_paired && (c->offsets.size() - 1) % 2 != 0)   // (every earlier chunk is even: this chunk's parity is the file's)
+                            throw runtime_error("--paired 1: " + g_query_name + " has an odd number of records, its last record has no mate");
+                        more = false; break;
+                    }
                     if (c->n_bases + (size_t)len > c->bases.cap) {   // a read longer than the room that is left: enlarge, keeping the content
                         PinnedBuf bigger; char* nd = bigger.get(c->n_bases + (size_t)len + BATCH_BASES / 4);
                         memcpy(nd, dst, c->n_bases);
@@ -948,7 +984,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                     }
                     memcpy(dst + c->n_bases, reader->read_buf.data(), (size_t)len);
                     c->n_bases += (size_t)len; c->offsets.push_back(c->n_bases);
-                    if (c->n_bases >= BATCH_BASES) break;
+                    if (c->n_bases >= BATCH_BASES && (!g_paired || (c->offsets.size() - 1) % 2 == 0)) break;   // (--paired 1: never between two mates)
                 }
                 if (c->offsets.size() > 1) search_q.push(c); else free_q.push(c);
             }
@@ -1121,7 +1157,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
@@ -1129,6 +1165,11 @@ static int search_fmin(int argc, char** argv) {
         throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
+    g_paired = o.has("paired") && o.get("paired") != "0" && o.get("paired") != "false";
+    const bool pair_both = o.has("pair-both") && o.get("pair-both") != "0" && o.get("pair-both") != "false";
+    if (g_paired && !o.has("color-refs")) throw runtime_error("--paired 1 wants colours: --color-refs LIST (fragments are what --pseudoalign, --eqclasses, --color-report and --abundance then take)");
+    if (pair_both && !g_paired) throw runtime_error("--pair-both 1 is only legal together with --paired 1");
+    g_pair_mode = pair_both ? FIN_PAIR_BOTH : FIN_PAIR_ANY;
     const bool eq_asked = o.has("eqclasses") || o.has("color-report") || o.has("abundance");
     if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
     if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
@@ -1362,7 +1403,8 @@ static int search_fmin(int argc, char** argv) {
     for (size_t i = 0; i < query_files.size(); i++) {
         write_log("Running streaming queries from input file " + query_files[i]);
         OutSink out(output_files.has_value() ? &output_files.value()[i] : nullptr);
-        if (BlockReader::usable(query_files[i])) {
+        g_query_name = query_files[i];
+        if (!g_paired && BlockReader::usable(query_files[i])) {   // (--paired 1: the record loop, which cuts chunks between fragments only)
             BlockReader breader(query_files[i]);
             number_of_queries += run_fmin_queries_streaming(nullptr, &breader, out, index, index_prefix + ".stats");
         } else {

@@ -753,7 +753,7 @@ int fin_index_unitig_numbers(const fin_index* idx, const char* bases, const uint
  * the coloured k-mers -- found k-mers in uncoloured unitigs and absent k-mers are ignored --, permille = 0 the union.  All of it is invariant under reversing the
  * slot order.  A pair whose unitig number is at or above the index's number of unitigs counts as absent on the device and is FIN_EINVAL on the host.
  * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, more than 4096 colours, compressed or deduplicated colour sets.  (A per-colour
- * tally of reads: the EQUIVALENCE CLASSES below.) */
+ * tally of reads: the EQUIVALENCE CLASSES below.  Paired-end data: one row per FRAGMENT, the same definition over both mates' slots, DESIGN.md 4.17 below.) */
 #define FIN_MAX_COLORS 4096u
 typedef struct fin_read_pseudo { uint32_t n_found, n_colored, n_colors, reserved /* 0 */; } fin_read_pseudo;   /* 16 bytes; n_colors = the popcount of the read's row */
 typedef struct fin_colors fin_colors;
@@ -803,7 +803,7 @@ int fin_records_pseudoalign(const fin_read_record* recs, uint64_t n_reads, const
  * What abundance estimation, strain demixing and "how many reads does each reference explain" start from is not a colour row per read but the distinct rows a run
  * produced and how many reads have each (kallisto's and Themisto-to-mSWEEP's sufficient statistic): a few thousand classes for millions of reads.  An
  * accumulator belongs to one fin_colors, and through it to that object's index, device, n_colors and W.  Over every row added since the last reset, exact and in
- * integers:
+ * integers (a row may be a read's or a FRAGMENT's, 4.17: the accumulator counts rows, and "reads" below means rows):
  *   a row whose W words are all zero is UNALIGNED: it counts in n_unaligned and belongs to no class;
  *   every other row belongs to the class of the rows bit-identical to it; reads[class] = the rows added to it;
  *   the sum of reads + n_unaligned = the rows added.  Adding the same run twice counts twice, as fin_hits does;
@@ -849,10 +849,49 @@ int fin_rows_eqclasses(const uint64_t* rows, uint64_t n_rows, uint32_t n_colors,
 /* host: the per-colour tally of n_classes classes: reads_with[n_colors], reads_only[n_colors] */
 int fin_eqclasses_color_tally(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, uint64_t* reads_with, uint64_t* reads_only);
 
+/* ---- PAIRED-END pseudoalignment: one colour row per FRAGMENT, made on the device ----
+ * Short-read data is almost always paired-end: the two mates come from one molecule, and the fragment is the unit of observation.  A batch of n_reads = 2F reads
+ * holds F fragments, INTERLEAVED: fragment f is reads 2f (first mate) and 2f + 1 (second mate); an odd n_reads is FIN_EINVAL.  The fragment's slots are the output
+ * slots of both mates together, and the definition above (4.14) is applied to that pooled slot list word for word: n_found and n_colored are the sums over both
+ * mates, cnt[c] = the coloured slots of either mate whose unitig has colour c, colour c is in the fragment's row iff cnt[c] >= 1 and 1000 * cnt[c] >= permille *
+ * n_colored (64-bit).  No orientation or insert-size model takes part: the row is invariant under swapping the mates and under reversing either mate's slot order.
+ *   permille = 1000, both mates with n_colored >= 1: the AND of the two mates' per-read rows (cnt_a[c] <= n_a and cnt_b[c] <= n_b, so cnt_a[c] + cnt_b[c] >= n_a +
+ *   n_b forces both equalities); otherwise the row of the mate that has coloured k-mers -- kallisto's rule.  permille = 0: the OR of the mates' rows.
+ * mode FIN_PAIR_ANY: as above.  FIN_PAIR_BOTH: the row is all zero and n_colors = 0 unless BOTH mates have at least one coloured slot; the three counts are reported
+ * either way.  Any other mode is FIN_EINVAL.
+ * A fragment's row is a row like any other: fin_eqclasses_add_rows, the classes and fin_eqclasses_abundance take it as it stands, a fragment counting as one "read".
+ * Out of scope: a second query file read in lockstep, orientation or insert-size filters, partitioned indexes, fin_search_batch_multi / dist.py, the C++ mirror. */
+#define FIN_PAIR_ANY 0u
+#define FIN_PAIR_BOTH 1u
+typedef struct fin_pair_pseudo { uint32_t n_found, n_colored, n_colors, n_colored_first; } fin_pair_pseudo;   /* 16 bytes; n_colored_first = the first mate's share of n_colored */
+/* fin_batch_pseudoalign's ordering: behind the batch's most recent run, on that run's stream, behind every add to the matrix; the overrun check comes first.  One
+ * kernel, a lane per fragment (fin_paired.hip).  rows uint64[F][W] and fin_pair_pseudo[F] go into buffers OF THEIR OWN, which the batch keeps and only grows: the
+ * per-read rows of fin_batch_pseudoalign survive this call and this call's results survive that one.  Whatever forgets the per-read rows forgets these too.  F = 0
+ * is legal.  FIN_EINVAL: an odd n_reads, a mode that is neither, permille > 1000, the batch has not run, colours of another index or device -- such a call writes
+ * nothing and leaves an earlier result of the same run downloadable, as fin_batch_pseudoalign does.  FIN_ELIMIT: the run's overflow list overran (no result). */
+int fin_batch_pseudoalign_paired(fin_batch* b, const fin_colors* c, uint32_t permille, uint32_t mode, char* err, size_t errlen);
+void* fin_batch_device_pair_rows(const fin_batch* b);    /* uint64[F * W] in HBM; NULL before fin_batch_pseudoalign_paired */
+void* fin_batch_device_pair_heads(const fin_batch* b);   /* fin_pair_pseudo[F] in HBM; NULL before fin_batch_pseudoalign_paired */
+int fin_batch_download_pair_pseudo(fin_batch* b, uint64_t* rows_out, fin_pair_pseudo* heads_out, char* err, size_t errlen);   /* either pointer may be NULL */
+/* fin_batch_add_eqclasses for fragments: fin_batch_pseudoalign_paired is ALWAYS called first (its errors are this call's), then its F rows are added on
+ * hip_stream, which waits for them.  A fragment is one row and therefore one "read" of its class. */
+int fin_batch_add_eqclasses_paired(fin_batch* b, fin_eqclasses* e, uint32_t permille, uint32_t mode, void* hip_stream, char* err, size_t errlen);
+/* host buffers in, interleaved mates: fin_search_batch_pseudoalign's pipeline, whose sub-batches end only after an even number of reads (also at the limits on
+ * reads, bases and k-mers of a sub-batch), so no pair is split.  rows_out[F * W] (may be NULL) and heads_out[F] land at the fragments' numbers; *n_positive (may
+ * be NULL) = the sum of n_colored.  An odd n_reads is FIN_EINVAL before anything runs. */
+int fin_search_batch_pseudoalign_paired(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_colors* c,
+                                        uint32_t permille, uint32_t mode, uint64_t* rows_out, fin_pair_pseudo* heads_out, uint64_t* n_positive, char* err, size_t errlen);
+int fin_search_batch_add_eqclasses_paired(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_eqclasses* e,
+                                          uint32_t permille, uint32_t mode, char* err, size_t errlen);
+/* host, no device: the same rows and heads from records + stream, beside fin_records_pseudoalign, the definition run over the two mates' segments.  rows_out[F * W],
+ * heads_out[F], F = n_reads / 2.  fin_records_pseudoalign's error codes, and FIN_EINVAL for an odd n_reads or a mode that is neither */
+int fin_records_pseudoalign_paired(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint64_t* bits,
+                                   uint64_t n_unitigs, uint32_t n_colors, uint32_t permille, uint32_t mode, uint64_t* rows_out, fin_pair_pseudo* heads_out, int n_threads);
+
 /* ---- ABUNDANCES from the equivalence classes: EM on the device ----
  * The step every consumer of such classes runs next (kallisto's EM, mSWEEP's behind Themisto): split each class's reads over its colours in proportion to the
  * current estimate, and repeat.  INPUTS: the classes (R_j, n_j), j < C, of one accumulator -- R_j a non-empty set of colours, n_j >= 1 its reads; N = the sum of
- * the n_j, the aligned reads (unaligned reads take no part); optionally len[c] > 0, one finite double per colour, the effective length of reference c (NULL: all
+ * the n_j, the aligned reads (unaligned reads take no part; where the rows added were FRAGMENTS' rows, 4.17, a "read" is a fragment); optionally len[c] > 0, one finite double per colour, the effective length of reference c (NULL: all
  * 1.0).  All arithmetic is in IEEE double.
  *   START      alpha0_c = N / n_colors for every colour.
  *   ITERATION  t = 0, 1, ...:  x_c = alpha_c / len[c];  d_j = the sum of x_c over c in R_j;  ll_t = the sum over j of n_j log(d_j / N);  q_j = n_j / d_j;
