@@ -277,6 +277,11 @@ def lib():
         f64p = C.POINTER(C.c_double)
         L.fin_eqclasses_abundance.argtypes = [vp, f64p, u32, C.c_double, f64p, f64p, C.POINTER(AbundanceInfo), cp, C.c_size_t]
         L.fin_classes_abundance.argtypes = [u64p, u64p, u64, u32, f64p, u32, C.c_double, f64p, f64p, C.POINTER(AbundanceInfo), C.c_int]
+        u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        L.fin_bootstrap_check.argtypes = [u64, u32, cp, C.c_size_t]
+        L.fin_eqclasses_bootstrap.argtypes = [vp, f64p, u32, C.c_double, u32, u64, f64p, C.POINTER(AbundanceInfo), f64p, u64p, u32p, u8p, cp, C.c_size_t]
+        L.fin_classes_resample.argtypes = [u64p, u64p, u64, u32, u64, u32, u64p, C.c_int]
+        L.fin_classes_bootstrap.argtypes = [u64p, u64p, u64, u32, f64p, u32, C.c_double, u32, u64, f64p, C.POINTER(AbundanceInfo), f64p, u64p, u32p, u8p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -928,6 +933,18 @@ class EqClasses:
                                               tr.ctypes.data_as(f64p) if tr is not None else None, C.byref(info), err, 512), err)
         return Abundance(alpha, lens, info, tr)
 
+    def bootstrap(self, n_boot, seed=0, lengths=None, max_iters=1000, tol=1e-6):
+        """the estimate of abundance() and n_boot (1 .. 4096) bootstrap replicates of it, the class counts of each resampled on the device: a Bootstrap
+        (fin_eqclasses_bootstrap).  A Poisson bootstrap keyed by the class's row: the replicates are a function of the classes, seed and the
+        replicate's number alone.  Waits for the adds and leaves the accumulator as it found it"""
+        lens, mi, tol = _abundance_args("EqClasses.bootstrap", self.n_colors, lengths, max_iters, tol)
+        nb, seed = _bootstrap_args("EqClasses.bootstrap", n_boot, seed)
+        out = _BootOut(nb, self.n_colors)
+        err = C.create_string_buffer(512)
+        f64p = C.POINTER(C.c_double)
+        _check(self.L.fin_eqclasses_bootstrap(self.h, lens.ctypes.data_as(f64p) if lens is not None else None, mi, tol, nb, seed, *out.args(), err, 512), err)
+        return out.result(lens, seed)
+
     def stats(self):
         """[rows added, unaligned, classes, rows that went through the serial pass]; waits (fin_eqclasses_stats)"""
         out = np.zeros(4, dtype=np.uint64)
@@ -961,6 +978,48 @@ class Abundance:
         per_len = alpha / lengths if lengths is not None else alpha
         self.rho = per_len / per_len.sum() if per_len.sum() > 0 else np.zeros_like(alpha)
         self.trace = trace[: self.iters] if trace is not None else None
+
+
+class Bootstrap:
+    """the result of a bootstrap: point = the Abundance of the classes as they are; per replicate b alpha[b] (expected reads per colour),
+    n_reads[b] (N_b, the replicate's reads), iters[b], converged[b]; theta = alpha / n_reads (0 where N_b = 0); mean and sd of alpha over the replicates
+    (ddof = 1; sd is 0 for one replicate), made on the host; seed"""
+
+    def __init__(self, point, alpha, n_reads, iters, converged, seed):
+        self.point, self.alpha, self.n_reads, self.iters, self.converged, self.seed = point, alpha, n_reads, iters, converged, seed
+        nz = n_reads > 0
+        self.theta = np.zeros_like(alpha)
+        self.theta[nz] = alpha[nz] / n_reads[nz].astype(np.float64)[:, None]
+        self.mean = alpha.mean(axis=0)
+        self.sd = alpha.std(axis=0, ddof=1) if len(alpha) > 1 else np.zeros(alpha.shape[1])
+
+
+class _BootOut:
+    """the output arrays of fin_eqclasses_bootstrap and fin_classes_bootstrap"""
+
+    def __init__(self, n_boot, n_colors):
+        self.point, self.info = np.zeros(n_colors, dtype=np.float64), AbundanceInfo()
+        self.alpha = np.zeros((n_boot, n_colors), dtype=np.float64)
+        self.n_reads, self.iters, self.conv = np.zeros(n_boot, dtype=np.uint64), np.zeros(n_boot, dtype=np.uint32), np.zeros(n_boot, dtype=np.uint8)
+
+    def args(self):
+        f64p = C.POINTER(C.c_double)
+        return (self.point.ctypes.data_as(f64p), C.byref(self.info), self.alpha.ctypes.data_as(f64p), self.n_reads.ctypes.data_as(C.POINTER(C.c_uint64)),
+                self.iters.ctypes.data_as(C.POINTER(C.c_uint32)), self.conv.ctypes.data_as(C.POINTER(C.c_uint8)))
+
+    def result(self, lens, seed):
+        return Bootstrap(Abundance(self.point, lens, self.info, None), self.alpha, self.n_reads, self.iters, self.conv.astype(bool), seed)
+
+
+def _bootstrap_args(what, n_boot, seed):
+    nb, seed = int(n_boot), int(seed)
+    if nb < 1:
+        raise FinitoError(FIN_EINVAL, "%s: n_boot is 1 .. 4096" % what)
+    if nb > 4096:
+        raise FinitoError(FIN_ELIMIT, "%s: n_boot is 1 .. 4096" % what)
+    if not 0 <= seed <= 0xFFFFFFFFFFFFFFFF:
+        raise FinitoError(FIN_EINVAL, "%s: seed is an unsigned 64-bit number" % what)
+    return nb, seed
 
 
 def _abundance_args(what, n_colors, lengths, max_iters, tol):
@@ -1926,6 +1985,48 @@ def classes_abundance(class_rows, class_reads, n_colors, lengths=None, max_iters
         raise FinitoError(rc, "fin_classes_abundance: more than 2^26 classes" if rc == FIN_ELIMIT else
                           "fin_classes_abundance: a class with a bit at or above n_colors, an empty row or a class of 0 reads")
     return Abundance(alpha, lens, info, tr)
+
+
+def _classes(what, class_rows, class_reads, n_colors):
+    W = (int(n_colors) + 63) // 64
+    a = np.ascontiguousarray(class_rows, dtype=np.uint64).reshape(-1, W)
+    r = np.ascontiguousarray(class_reads, dtype=np.uint64).reshape(-1)
+    if len(a) != len(r):
+        raise FinitoError(FIN_EINVAL, "%s: %d rows and %d counts" % (what, len(a), len(r)))
+    return a, r
+
+
+def classes_resample(class_rows, class_reads, n_colors, seed=0, b=0, n_threads=0):
+    """host: the class counts uint64[n] of bootstrap replicate b under `seed`, for classes {row, reads} in the order given -- the order does not matter
+    (fin_classes_resample)"""
+    if not 1 <= int(n_colors) <= 4096:
+        raise FinitoError(FIN_ELIMIT, "classes_resample: n_colors is 1 .. 4096")
+    _, seed = _bootstrap_args("classes_resample", 1, seed)
+    if not 0 <= int(b) < 4096:
+        raise FinitoError(FIN_ELIMIT, "classes_resample: b is 0 .. 4095")
+    a, r = _classes("classes_resample", class_rows, class_reads, n_colors)
+    out = np.zeros(len(a), dtype=np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    rc = lib().fin_classes_resample(a.ctypes.data_as(u64p), r.ctypes.data_as(u64p), len(a), int(n_colors), seed, int(b), out.ctypes.data_as(u64p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_classes_resample: more than 2^26 classes, or a class of 2^40 reads or more")
+    return out
+
+
+def classes_bootstrap(class_rows, class_reads, n_colors, n_boot, seed=0, lengths=None, max_iters=1000, tol=1e-6, n_threads=0):
+    """host: EqClasses.bootstrap from classes {row, reads} in the order given: a Bootstrap whose replicates are classes_abundance over their non-zero classes
+    (fin_classes_bootstrap)"""
+    lens, mi, tol = _abundance_args("classes_bootstrap", n_colors, lengths, max_iters, tol)
+    nb, seed = _bootstrap_args("classes_bootstrap", n_boot, seed)
+    a, r = _classes("classes_bootstrap", class_rows, class_reads, n_colors)
+    out = _BootOut(nb, int(n_colors))
+    u64p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+    rc = lib().fin_classes_bootstrap(a.ctypes.data_as(u64p), r.ctypes.data_as(u64p), len(a), int(n_colors), lens.ctypes.data_as(f64p) if lens is not None else None, mi, tol,
+                                     nb, seed, *out.args(), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_classes_bootstrap: more than 2^26 classes, or N x n_boot above 2^38" if rc == FIN_ELIMIT else
+                          "fin_classes_bootstrap: a class with a bit at or above n_colors, an empty row or a class of 0 reads")
+    return out.result(lens, seed)
 
 
 def eqclasses_color_tally(class_rows, class_reads, n_colors):

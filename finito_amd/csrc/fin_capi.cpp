@@ -22,6 +22,7 @@
 
 #include "../../include/finito_amd.h"
 #include "fin_index.hpp"
+#include "fin_bootrng.h"
 #include "fin_kernels.h"
 
 static void set_err(char* err, size_t errlen, const std::string& msg) {
@@ -2568,72 +2569,174 @@ static void ab_empty(uint32_t n_colors, double* alpha_out, fin_abundance_info* i
     if (info) { *info = fin_abundance_info(); info->n_unaligned = n_unaligned; info->converged = 1; }
 }
 
-int fin_eqclasses_abundance(fin_eqclasses* e, const double* lengths, uint32_t max_iters, double tol, double* alpha_out, double* loglik_trace, fin_abundance_info* info,
-                            char* err, size_t errlen) {
-    if (!e || !alpha_out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    if (const int arc = ab_check_args(e->n_colors, lengths, max_iters, tol, err, errlen)) return arc;
-    HIPCHK(hipSetDevice(e->device));
-    std::lock_guard<std::mutex> g(e->mu);
+// every device buffer of an estimate, freed on every way out
+struct AbBufs {
+    std::vector<void*> p;
+    ~AbBufs() { for (void* q : p) (void)hipFree(q); }
+    void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return q; }
+};
+// the dense class list of an accumulator and the buffers of the estimates over it: what fin_eqclasses_abundance and fin_eqclasses_bootstrap prepare alike
+struct AbPrep {
+    AbBufs bufs;
+    uint64_t ctr[8] = {0};
+    uint64_t C = 0, N = 0;                  // classes; the aligned reads
+    uint32_t W = 0, nc = 0, ab_chunk = 0, max_iters = 0;
+    size_t padded = 0;
+    uint64_t *d_rows = nullptr, *d_rowsT = nullptr, *d_reads = nullptr;
+    double *d_len = nullptr, *d_alpha = nullptr, *d_x = nullptr, *d_q = nullptr, *d_part = nullptr, *d_ll = nullptr, *d_chg = nullptr, *d_trace = nullptr;
+    FinAbState* d_state = nullptr;
+    uint32_t* d_ok = nullptr;
+    std::vector<double> host;               // len (1 behind n_colors) | alpha | x, 64 W each
+};
+// under the accumulator's lock, on its device: the wait and the counters, the flag check, the compaction, the gather and the transpose, the buffers.  C = 0 on
+// FIN_OK: no classes, nothing was allocated for an estimate.  `nomem`: what FIN_ENOMEM says
+static int ab_prepare(fin_eqclasses* e, const double* lengths, uint32_t max_iters, const char* nomem_msg, AbPrep& P, char* err, size_t errlen) {
     if (const int wrc = e->pend.wait(err, errlen)) return wrc;
-    uint64_t ctr[8];
-    HIPCHK(hipMemcpy(ctr, ec_ctr(e), sizeof ctr, hipMemcpyDeviceToHost));
-    if (const int frc = ec_flagged(e, ctr, err, errlen)) return frc;
+    HIPCHK(hipMemcpy(P.ctr, ec_ctr(e), sizeof P.ctr, hipMemcpyDeviceToHost));
+    if (const int frc = ec_flagged(e, P.ctr, err, errlen)) return frc;
     const uint32_t W = e->words, nc = e->n_colors, nb = fin_ec_blocks((uint32_t)e->slots), ab_chunk = (uint32_t)optv(e->idx, O_ab_chunk);
-    // every device buffer of the call, freed on every way out
-    struct Bufs { std::vector<void*> p; ~Bufs() { for (void* q : p) (void)hipFree(q); } void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return q; } } bufs;
+    P.W = W; P.nc = nc; P.ab_chunk = ab_chunk; P.max_iters = max_iters;
     // (beside the table: the dense rows and reads, 8 C (W + 1) bytes, their word-major copy, 8 C W, and 8 (C + n_chunks 64 W) of q and partials)
-    const auto nomem = [&] { set_err(err, errlen, "out of device memory (abundances from the equivalence classes: beside the table, 16 W + 16 bytes per class and up to 32 MB of partial sums)"); return FIN_ENOMEM; };
+    const auto nomem = [&] { set_err(err, errlen, nomem_msg); return FIN_ENOMEM; };
     // the download's compaction: the occupied slots counted per block, scanned, gathered -- the rows stay on the device
     const size_t off_bytes = (size_t)nb * 8 + 8;
-    void* const d_tmp = bufs.get(off_bytes + (size_t)nb * 4);
+    void* const d_tmp = P.bufs.get(off_bytes + (size_t)nb * 4);
     if (!d_tmp) return nomem();
     uint64_t* const d_off = (uint64_t*)d_tmp; uint64_t* const d_total = d_off + nb; uint32_t* const d_sum = (uint32_t*)((char*)d_tmp + off_bytes);
     int rc = fin_launch_ec_occupied(ec_tags(e), (uint32_t)e->slots, d_sum, d_off, d_total, nullptr);
     if (rc != 0) { set_err(err, errlen, std::string("compaction of the equivalence classes: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
     uint64_t C = 0;
     HIPCHK(hipMemcpy(&C, d_total, 8, hipMemcpyDeviceToHost));
-    if (C == 0) { ab_empty(nc, alpha_out, info, ctr[1]); return FIN_OK; }
+    if (C == 0) return FIN_OK;
     if (C > e->max_classes) { set_err(err, errlen, "more than max_classes distinct rows"); return FIN_ELIMIT; }   // (the flags said otherwise: never)
-    const uint64_t N = ctr[0] - ctr[1];     // the aligned reads: every row added is unaligned or in a class
+    P.N = P.ctr[0] - P.ctr[1];              // the aligned reads: every row added is unaligned or in a class
     uint32_t cpb, n_ll, chunk, n_chunks;
     fin_ab_geometry(C, W, ab_chunk, &cpb, &n_ll, &chunk, &n_chunks);
     const size_t padded = (size_t)64 * W;
-    uint64_t* const d_rows = (uint64_t*)bufs.get((size_t)C * (W + 1) * 8);
-    uint64_t* const d_rowsT = W > 1 ? (uint64_t*)bufs.get((size_t)C * W * 8) : d_rows;
+    P.padded = padded;
+    P.d_rows = (uint64_t*)P.bufs.get((size_t)C * (W + 1) * 8);
+    P.d_rowsT = W > 1 ? (uint64_t*)P.bufs.get((size_t)C * W * 8) : P.d_rows;
     // doubles: len | alpha | x | q | part | ll_part | blk_chg | trace, then the state and blk_ok
     const size_t n_dbl = 3 * padded + (size_t)C + (size_t)n_chunks * padded + n_ll + 64 + max_iters;
-    double* const d_dbl = (double*)bufs.get(n_dbl * 8 + sizeof(FinAbState) + 64 * 4);
-    if (!d_rows || !d_rowsT || !d_dbl) return nomem();
-    uint64_t* const d_reads = d_rows + (size_t)C * W;
-    double* const d_len = d_dbl; double* const d_alpha = d_len + padded; double* const d_x = d_alpha + padded; double* const d_q = d_x + padded;
-    double* const d_part = d_q + C; double* const d_ll = d_part + (size_t)n_chunks * padded; double* const d_chg = d_ll + n_ll; double* const d_trace = d_chg + 64;
-    FinAbState* const d_state = (FinAbState*)(d_trace + max_iters); uint32_t* const d_ok = (uint32_t*)(d_state + 1);
-    rc = fin_launch_ec_gather(ec_tags(e), ec_counts(e), ec_rows(e), (uint32_t)e->slots, W, d_off, d_rows, d_reads, nullptr);
-    if (rc == 0 && W > 1) rc = fin_launch_ab_transpose(d_rows, C, W, d_rowsT, nullptr);
+    double* const d_dbl = (double*)P.bufs.get(n_dbl * 8 + sizeof(FinAbState) + 64 * 4);
+    if (!P.d_rows || !P.d_rowsT || !d_dbl) return nomem();
+    P.d_reads = P.d_rows + (size_t)C * W;
+    P.d_len = d_dbl; P.d_alpha = P.d_len + padded; P.d_x = P.d_alpha + padded; P.d_q = P.d_x + padded;
+    P.d_part = P.d_q + C; P.d_ll = P.d_part + (size_t)n_chunks * padded; P.d_chg = P.d_ll + n_ll; P.d_trace = P.d_chg + 64;
+    P.d_state = (FinAbState*)(P.d_trace + max_iters); P.d_ok = (uint32_t*)(P.d_state + 1);
+    rc = fin_launch_ec_gather(ec_tags(e), ec_counts(e), ec_rows(e), (uint32_t)e->slots, W, d_off, P.d_rows, P.d_reads, nullptr);
+    if (rc == 0 && W > 1) rc = fin_launch_ab_transpose(P.d_rows, C, W, P.d_rowsT, nullptr);
     if (rc != 0) { set_err(err, errlen, std::string("abundance kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
-    std::vector<double> host(3 * padded, 0.0);   // len (1 behind n_colors), alpha, x
-    for (size_t c = 0; c < padded; c++) host[c] = c < nc && lengths ? lengths[c] : 1.0;
-    for (uint32_t c = 0; c < nc; c++) { host[padded + c] = (double)N / (double)nc; host[2 * padded + c] = host[padded + c] / host[c]; }
-    HIPCHK(hipMemcpy(d_dbl, host.data(), host.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_state, 0, sizeof(FinAbState) + 64 * 4));
+    P.host.assign(3 * padded, 0.0);
+    for (size_t c = 0; c < padded; c++) P.host[c] = c < nc && lengths ? lengths[c] : 1.0;
+    P.C = C;
+    return FIN_OK;
+}
+// one estimate over the prepared list: the counts `d_counts` (the list's reads, or a replicate's) and their total, from alpha0 = n_total / n_colors with a fresh
+// state; *st: the device's state word when it stopped
+static int ab_estimate(AbPrep& P, const uint64_t* d_counts, uint64_t n_total, double tol, FinAbState* st_out, char* err, size_t errlen) {
+    const size_t padded = P.padded;
+    const uint32_t nc = P.nc, max_iters = P.max_iters;
+    for (uint32_t c = 0; c < nc; c++) { P.host[padded + c] = (double)n_total / (double)nc; P.host[2 * padded + c] = P.host[padded + c] / P.host[c]; }
+    HIPCHK(hipMemcpy(P.d_len, P.host.data(), P.host.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(P.d_state, 0, sizeof(FinAbState) + 64 * 4));
     FinAbState st = FinAbState();
     for (uint32_t t = 0; t < max_iters && !st.done;) {
         const uint32_t t1 = std::min(max_iters, t + FIN_AB_GROUP);
         for (; t < t1; t++) {
-            rc = fin_launch_ab_iteration(d_state, d_rows, d_rowsT, d_reads, C, W, nc, ab_chunk, d_len, (double)N, tol, d_alpha, d_x, d_q, d_part, d_ll, d_ok, d_chg, t,
-                                         d_trace, nullptr);
+            const int rc = fin_launch_ab_iteration(P.d_state, P.d_rows, P.d_rowsT, d_counts, P.C, P.W, nc, P.ab_chunk, P.d_len, (double)n_total, tol, P.d_alpha, P.d_x, P.d_q,
+                                                   P.d_part, P.d_ll, P.d_ok, P.d_chg, t, P.d_trace, nullptr);
             if (rc != 0) { set_err(err, errlen, std::string("abundance kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
         }
-        HIPCHK(hipMemcpy(&st, d_state, 8, hipMemcpyDeviceToHost));   // {done, iters}: the copy waits for the group
+        HIPCHK(hipMemcpy(&st, P.d_state, 8, hipMemcpyDeviceToHost));   // {done, iters}: the copy waits for the group
     }
-    HIPCHK(hipMemcpy(&st, d_state, sizeof st, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&st, P.d_state, sizeof st, hipMemcpyDeviceToHost));
     if (st.iters == 0 || st.iters > max_iters) { set_err(err, errlen, "abundance kernels: the iteration count on the device is out of range"); return FIN_ENODEV; }
-    HIPCHK(hipMemcpy(alpha_out, d_alpha, (size_t)nc * 8, hipMemcpyDeviceToHost));
-    if (loglik_trace) HIPCHK(hipMemcpy(loglik_trace, d_trace, (size_t)st.iters * 8, hipMemcpyDeviceToHost));
+    *st_out = st;
+    return FIN_OK;
+}
+// the point estimate's outputs
+static int ab_point(AbPrep& P, double tol, double* alpha_out, double* loglik_trace, fin_abundance_info* info, char* err, size_t errlen) {
+    FinAbState st;
+    if (const int rc = ab_estimate(P, P.d_reads, P.N, tol, &st, err, errlen)) return rc;
+    HIPCHK(hipMemcpy(alpha_out, P.d_alpha, (size_t)P.nc * 8, hipMemcpyDeviceToHost));
+    if (loglik_trace) HIPCHK(hipMemcpy(loglik_trace, P.d_trace, (size_t)st.iters * 8, hipMemcpyDeviceToHost));
     if (info) {
-        info->n_classes = C; info->n_reads = N; info->n_unaligned = ctr[1];
+        info->n_classes = P.C; info->n_reads = P.N; info->n_unaligned = P.ctr[1];
         info->iters = st.iters; info->converged = st.done ? 1u : 0u;
         info->loglik = st.loglik; info->max_change = st.max_change;
+    }
+    return FIN_OK;
+}
+
+int fin_eqclasses_abundance(fin_eqclasses* e, const double* lengths, uint32_t max_iters, double tol, double* alpha_out, double* loglik_trace, fin_abundance_info* info,
+                            char* err, size_t errlen) {
+    if (!e || !alpha_out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int arc = ab_check_args(e->n_colors, lengths, max_iters, tol, err, errlen)) return arc;
+    HIPCHK(hipSetDevice(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    AbPrep P;
+    if (const int prc = ab_prepare(e, lengths, max_iters, "out of device memory (abundances from the equivalence classes: beside the table, 16 W + 16 bytes per class and up to 32 MB of partial sums)", P, err, errlen)) return prc;
+    if (P.C == 0) { ab_empty(e->n_colors, alpha_out, info, P.ctr[1]); return FIN_OK; }
+    return ab_point(P, tol, alpha_out, loglik_trace, info, err, errlen);
+}
+
+// ---- bootstrap replicates of the estimate (fin_bootstrap.hip, fin_bootrng.h) ------------------------------------------------
+int fin_bootstrap_check(uint64_t n_reads, uint32_t n_boot, char* err, size_t errlen) {
+    if (n_boot == 0) { set_err(err, errlen, "n_boot is 1 .. 4096"); return FIN_EINVAL; }
+    if (n_boot > FIN_BOOT_MAX) { set_err(err, errlen, "n_boot is 1 .. 4096"); return FIN_ELIMIT; }
+    if (n_reads > FIN_BOOT_MAX_DRAWS / n_boot) {
+        set_err(err, errlen, "N x n_boot = " + std::to_string(n_reads) + " reads x " + std::to_string(n_boot) + " replicates is more than 2^38 draws in one call");
+        return FIN_ELIMIT;
+    }
+    return FIN_OK;
+}
+
+int fin_eqclasses_bootstrap(fin_eqclasses* e, const double* lengths, uint32_t max_iters, double tol, uint32_t n_boot, uint64_t seed, double* alpha_out,
+                            fin_abundance_info* info, double* boot_alpha_out, uint64_t* boot_reads_out, uint32_t* boot_iters_out, uint8_t* boot_converged_out, char* err,
+                            size_t errlen) {
+    if (!e || !alpha_out || !boot_alpha_out || !boot_reads_out || !boot_iters_out || !boot_converged_out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int arc = ab_check_args(e->n_colors, lengths, max_iters, tol, err, errlen)) return arc;
+    if (const int brc = fin_bootstrap_check(0, n_boot, err, errlen)) return brc;
+    HIPCHK(hipSetDevice(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    AbPrep P;
+    static const char* const nomem_msg = "out of device memory (bootstrap of the abundances: beside the table, 16 W + 40 bytes per class and up to 32 MB of partial sums)";
+    if (const int prc = ab_prepare(e, lengths, max_iters, nomem_msg, P, err, errlen)) return prc;
+    const uint32_t nc = P.nc;
+    const auto empty_replicate = [&](uint32_t b) {
+        for (uint32_t c = 0; c < nc; c++) boot_alpha_out[(size_t)b * nc + c] = 0.0;
+        boot_reads_out[b] = 0; boot_iters_out[b] = 0; boot_converged_out[b] = 1;
+    };
+    if (P.C == 0) {
+        ab_empty(nc, alpha_out, info, P.ctr[1]);
+        for (uint32_t b = 0; b < n_boot; b++) empty_replicate(b);
+        return FIN_OK;
+    }
+    if (const int brc = fin_bootstrap_check(P.N, n_boot, err, errlen)) return brc;
+    const uint64_t C = P.C;
+    // hash | prefix | counts, then the N_b word and the slab total: 24 bytes per class (the slabs, uint32[C], lie where the counts will)
+    uint64_t* const d_boot = (uint64_t*)P.bufs.get(((size_t)3 * C + 2) * 8);
+    if (!d_boot) { set_err(err, errlen, nomem_msg); return FIN_ENOMEM; }
+    uint64_t* const d_hash = d_boot; uint64_t* const d_pref = d_hash + C; uint64_t* const d_counts = d_pref + C; uint64_t* const d_nb = d_counts + C; uint64_t* const d_S = d_nb + 1;
+    if (const int rc = ab_point(P, tol, alpha_out, nullptr, info, err, errlen)) return rc;
+    int rc = fin_launch_ab_rowhash(P.d_rows, C, P.W, d_hash, nullptr);
+    if (rc == 0) rc = fin_launch_ab_slabs(P.d_reads, C, (uint32_t*)d_counts, d_pref, d_S, nullptr);
+    if (rc != 0) { set_err(err, errlen, std::string("bootstrap kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    uint64_t S = 0;
+    HIPCHK(hipMemcpy(&S, d_S, 8, hipMemcpyDeviceToHost));
+    if (S == 0 || S > P.N / FIN_BOOT_SLAB + C) { set_err(err, errlen, "bootstrap kernels: the slab count on the device is out of range"); return FIN_ENODEV; }
+    for (uint32_t b = 0; b < n_boot; b++) {
+        HIPCHK(hipMemsetAsync(d_counts, 0, ((size_t)C + 1) * 8, nullptr));
+        rc = fin_launch_ab_resample(d_hash, P.d_reads, d_pref, C, S, seed, b, d_counts, d_nb, nullptr);
+        if (rc != 0) { set_err(err, errlen, std::string("bootstrap kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+        uint64_t n_b = 0;
+        HIPCHK(hipMemcpy(&n_b, d_nb, 8, hipMemcpyDeviceToHost));
+        if (n_b == 0) { empty_replicate(b); continue; }
+        FinAbState st;
+        if (const int erc = ab_estimate(P, d_counts, n_b, tol, &st, err, errlen)) return erc;
+        HIPCHK(hipMemcpy(boot_alpha_out + (size_t)b * nc, P.d_alpha, (size_t)nc * 8, hipMemcpyDeviceToHost));
+        boot_reads_out[b] = n_b; boot_iters_out[b] = st.iters; boot_converged_out[b] = st.done ? 1 : 0;
     }
     return FIN_OK;
 }
@@ -2710,6 +2813,67 @@ int fin_classes_abundance(const uint64_t* class_rows, const uint64_t* class_read
     if (info) {
         info->n_classes = n_classes; info->n_reads = N; info->n_unaligned = 0;
         info->iters = iters; info->converged = converged; info->loglik = ll; info->max_change = chg;
+    }
+    return FIN_OK;
+}
+
+// host twin of the resample: the exact counts of replicate b, in the order given (which does not matter).  The device's slabs, a slab per loop step, summed
+// into the class with integer atomics: the result does not depend on the threads
+int fin_classes_resample(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, uint64_t seed, uint32_t b, uint64_t* counts_out,
+                         int n_threads) {
+    if (n_colors == 0 || n_colors > FIN_MAX_COLORS || b >= FIN_BOOT_MAX || n_classes > (1ull << 26)) return FIN_ELIMIT;
+    if (n_classes && (!class_rows || !class_reads || !counts_out)) return FIN_EINVAL;
+    const uint32_t W = (n_colors + 63u) / 64u;
+    std::vector<uint64_t> h((size_t)n_classes), pref((size_t)n_classes + 1, 0);
+    for (uint64_t j = 0; j < n_classes; j++) {
+        if (class_reads[j] >= (1ull << 40)) return FIN_ELIMIT;
+        uint64_t x = 0;
+        for (uint32_t w = 0; w < W; w++) x ^= ec_word_hash(class_rows[(size_t)j * W + w], w);
+        h[(size_t)j] = x;
+        pref[(size_t)j + 1] = pref[(size_t)j] + (class_reads[j] + (FIN_BOOT_SLAB - 1u)) / FIN_BOOT_SLAB;
+        counts_out[j] = 0;
+    }
+    const int64_t S = (int64_t)pref[(size_t)n_classes];
+    const int T = n_threads > 0 ? n_threads : fin_host_threads();
+#pragma omp parallel for num_threads(T) schedule(static)
+    for (int64_t s = 0; s < S; s++) {
+        const size_t j = (size_t)(std::upper_bound(pref.begin(), pref.end(), (uint64_t)s) - pref.begin()) - 1;   // the last j with pref[j] <= s
+        const uint64_t n = class_reads[j], i0 = ((uint64_t)s - pref[j]) * (FIN_BOOT_SLAB / 4u), i1 = std::min((n + 3u) / 4u, i0 + FIN_BOOT_SLAB / 4u);
+        uint64_t sum = 0;
+        for (uint64_t i = i0; i < i1; i++) sum += fin_boot_block_sum(h[j], i, n, b, seed);
+        if (sum) __atomic_fetch_add(counts_out + j, sum, __ATOMIC_RELAXED);
+    }
+    return FIN_OK;
+}
+
+// host twin of fin_eqclasses_bootstrap: the point estimate over the classes, and for every replicate fin_classes_abundance over its non-zero classes in the
+// order given
+int fin_classes_bootstrap(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, const double* lengths, uint32_t max_iters,
+                          double tol, uint32_t n_boot, uint64_t seed, double* alpha_out, fin_abundance_info* info, double* boot_alpha_out, uint64_t* boot_reads_out,
+                          uint32_t* boot_iters_out, uint8_t* boot_converged_out, int n_threads) {
+    if (const int arc = ab_check_args(n_colors, lengths, max_iters, tol, nullptr, 0)) return arc;
+    if (!boot_alpha_out || !boot_reads_out || !boot_iters_out || !boot_converged_out) return FIN_EINVAL;
+    if (const int brc = fin_bootstrap_check(0, n_boot, nullptr, 0)) return brc;
+    fin_abundance_info point;
+    if (const int rc = fin_classes_abundance(class_rows, class_reads, n_classes, n_colors, lengths, max_iters, tol, alpha_out, nullptr, &point, n_threads)) return rc;
+    if (info) *info = point;
+    if (const int brc = fin_bootstrap_check(point.n_reads, n_boot, nullptr, 0)) return brc;
+    const uint32_t W = (n_colors + 63u) / 64u;
+    std::vector<uint64_t> counts((size_t)n_classes), rows, reads;
+    for (uint32_t b = 0; b < n_boot; b++) {
+        if (const int rc = fin_classes_resample(class_rows, class_reads, n_classes, n_colors, seed, b, counts.data(), n_threads)) return rc;
+        rows.clear(); reads.clear();
+        uint64_t n_b = 0;
+        for (uint64_t j = 0; j < n_classes; j++)
+            if (counts[(size_t)j]) {
+                rows.insert(rows.end(), class_rows + (size_t)j * W, class_rows + (size_t)j * W + W);
+                reads.push_back(counts[(size_t)j]);
+                n_b += counts[(size_t)j];
+            }
+        fin_abundance_info bi;
+        if (const int rc = fin_classes_abundance(rows.data(), reads.data(), reads.size(), n_colors, lengths, max_iters, tol, boot_alpha_out + (size_t)b * n_colors, nullptr, &bi,
+                                                 n_threads)) return rc;
+        boot_reads_out[b] = n_b; boot_iters_out[b] = bi.iters; boot_converged_out[b] = bi.converged ? 1 : 0;
     }
     return FIN_OK;
 }

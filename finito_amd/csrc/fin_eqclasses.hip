@@ -34,6 +34,7 @@
 // offsets and the total, fin_ec_gather_kernel writes the dense {row, reads} list.
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_rowhash.h"   // ec_mix, ec_word_hash, ec_wave_xor: the row hash, shared with fin_bootstrap.hip
 
 #define FIN_EC_BLK 256u
 #define EC_UNAL 0xFFFFFFFFu   // slot_of: the row is all zero
@@ -44,19 +45,6 @@ typedef unsigned long long ull;
 
 __device__ __forceinline__ uint32_t ec_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
 __device__ __forceinline__ uint64_t ec_bcast64(uint64_t v, int src) { return ((uint64_t)ec_bcast((uint32_t)(v >> 32), src) << 32) | ec_bcast((uint32_t)v, src); }
-__device__ __forceinline__ uint64_t ec_wave_xor(uint64_t v) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { lo ^= (uint32_t)__shfl_xor((int)lo, d); hi ^= (uint32_t)__shfl_xor((int)hi, d); }
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t ec_mix(uint64_t x) {
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// word i's share of the row's hash: the row's hash is the xor of its words' shares
-__device__ __forceinline__ uint64_t ec_word_hash(uint64_t word, uint32_t i) { return ec_mix(word + (uint64_t)(i + 1u) * 0x9E3779B97F4A7C15ull); }
 __device__ __forceinline__ uint64_t ec_tag(uint64_t h, uint32_t tag_bits) {
     const uint64_t t = h & ((1ull << tag_bits) - 1ull);   // tag_bits is 1 .. 63
     return t ? t : 1ull;

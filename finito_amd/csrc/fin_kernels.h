@@ -202,6 +202,13 @@ int fin_launch_ab_transpose(const void* rows, uint64_t C, uint32_t W, void* rows
 int fin_launch_ab_iteration(void* state, const void* rows, const void* rowsT, const void* reads, uint64_t C, uint32_t W, uint32_t n_colors, uint32_t ab_chunk,
                             const double* len, double n_total, double tol, double* alpha, double* x, double* q, double* part, double* ll_part, uint32_t* blk_ok,
                             double* blk_chg, uint32_t t, double* trace, hipStream_t stream);
+// fin_bootstrap.hip -- a bootstrap replicate's class counts, drawn over the same dense list (the draws: fin_bootrng.h).  fin_launch_ab_rowhash:
+// h[C], the rows' 64-bit hashes.  fin_launch_ab_slabs: slabs[C] (uint32, ceil(n_j / 4096); n_j < 2^40), their exclusive prefix[C] and *total.
+// fin_launch_ab_resample: replicate b (< 4096) under `seed` -- counts[C] and *n_b, both zeroed by the caller before the launch; S: that total, read by the host
+int fin_launch_ab_rowhash(const void* rows, uint64_t C, uint32_t W, void* h, hipStream_t stream);
+int fin_launch_ab_slabs(const void* reads, uint64_t C, uint32_t* slabs, uint64_t* prefix, uint64_t* total, hipStream_t stream);
+int fin_launch_ab_resample(const void* h, const void* reads, const uint64_t* prefix, uint64_t C, uint64_t S, uint64_t seed, uint32_t b, void* counts, void* n_b,
+                           hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

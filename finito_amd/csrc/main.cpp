@@ -516,6 +516,11 @@ static const char* SEARCH_HELP =
     "                        Empty lines are skipped and do not count, as in the list of --color-refs\n"
     "      --ab-max-iters N  at most N iterations, 1 to 100000 (default: 1000)\n"
     "      --ab-tol X        stop once no colour's reads change by more than X max(reads, 1) (default: 1e-6)\n"
+    "      --ab-bootstraps B  with --abundance: B bootstrap replicates of the estimate, 1 to 4096, the class counts of each resampled on the GPU (a Poisson\n"
+    "                        bootstrap keyed by the class's colour set: the same reads and seed give the same replicates). Every colour line gains\n"
+    "                        `<TAB>boot_mean<TAB>boot_sd` -- mean and standard deviation (B - 1 in the divisor; 0 for B = 1) of the replicates' reads, as %.10g --,\n"
+    "                        and a line `bootstraps<TAB>B<TAB>seed<TAB>S` follows the `loglik` line\n"
+    "      --ab-seed S       the seed of --ab-bootstraps, an unsigned 64-bit number (default: 0)\n"
     "      --paired arg      1: the query file holds INTERLEAVED mates, records 2f and 2f + 1 are fragment f (needs --color-refs). Chunks are cut after an\n"
     "                        even number of records; a file with an odd number of records is an error. --pseudoalign then writes one line per fragment,\n"
     "                        `fragment<TAB>k-mers<TAB>found<TAB>coloured<TAB>coloured_first<TAB>c1,c2,...` -- the k-mers of both mates together, coloured_first = the\n"
@@ -1157,7 +1162,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
@@ -1174,7 +1179,8 @@ static int search_fmin(int argc, char** argv) {
     if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
     if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
     if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses, --color-report or --abundance");
-    for (const char* name : {"ab-lengths", "ab-max-iters", "ab-tol"})
+    if (o.has("ab-seed") && !o.has("ab-bootstraps")) throw runtime_error("--ab-seed is only legal together with --ab-bootstraps");
+    for (const char* name : {"ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps"})
         if (o.has(name) && !o.has("abundance")) throw runtime_error(string("--") + name + " is only legal together with --abundance");
     if ((o.has("classify") || o.has("label-report")) && !(o.has("label-unitigs") && o.has("labels"))) throw runtime_error("--classify and --label-report want a labelling: --label-unitigs FASTA --labels FILE");
     if ((o.has("label-unitigs") || o.has("labels")) && !o.has("classify") && !o.has("label-report")) throw runtime_error("--label-unitigs and --labels are only legal together with --classify or --label-report");
@@ -1200,6 +1206,18 @@ static int search_fmin(int argc, char** argv) {
     if (eq_max_classes == 0) throw runtime_error("--eq-max-classes wants a number from 1 to " + to_string(1u << 26));
     const uint32_t ab_max_iters = u32_option("ab-max-iters", 1000, 100000);
     if (ab_max_iters == 0) throw runtime_error("--ab-max-iters wants a number from 1 to 100000");
+    uint32_t ab_bootstraps = 0;             // 0: none asked for
+    if (o.has("ab-bootstraps")) {
+        try { ab_bootstraps = u32_option("ab-bootstraps", 0, 4096); } catch (const runtime_error&) { ab_bootstraps = 0; }
+        if (ab_bootstraps == 0) throw runtime_error("--ab-bootstraps wants a number from 1 to 4096");
+    }
+    uint64_t ab_seed = 0;
+    if (o.has("ab-seed")) {
+        const string v = o.get("ab-seed");
+        size_t used = 0;
+        try { ab_seed = stoull(v, &used); } catch (...) { used = 0; }
+        if (v.empty() || used != v.size() || v[0] == '-') throw runtime_error("--ab-seed wants an unsigned 64-bit number");
+    }
     auto positive_number = [](const string& v, bool zero_too, double& out) {   // a finite number above 0 (or from 0 on), nothing behind it
         size_t used = 0;
         try { out = stod(v, &used); } catch (...) { return false; }
@@ -1442,7 +1460,26 @@ static int search_fmin(int argc, char** argv) {
         const uint32_t nc = fin_colors_n_colors(g_colors);
         vector<double> alpha(nc);
         fin_abundance_info info;
-        if (fin_eqclasses_abundance(g_eqc, ab_lengths.empty() ? nullptr : ab_lengths.data(), ab_max_iters, ab_tol, alpha.data(), nullptr, &info, err, sizeof err) != FIN_OK)
+        const double* const lens = ab_lengths.empty() ? nullptr : ab_lengths.data();
+        vector<double> boot_mean, boot_sd;   // --ab-bootstraps: over the replicates, per colour
+        if (ab_bootstraps) {
+            const uint32_t B = ab_bootstraps;
+            vector<double> boot((size_t)B * nc);
+            vector<uint64_t> boot_reads(B);
+            vector<uint32_t> boot_iters(B);
+            vector<uint8_t> boot_conv(B);
+            if (fin_eqclasses_bootstrap(g_eqc, lens, ab_max_iters, ab_tol, B, ab_seed, alpha.data(), &info, boot.data(), boot_reads.data(), boot_iters.data(), boot_conv.data(), err,
+                                        sizeof err) != FIN_OK)
+                throw runtime_error(err);
+            boot_mean.assign(nc, 0.0); boot_sd.assign(nc, 0.0);
+            for (uint32_t c = 0; c < nc; c++) {
+                double sum = 0.0, dev = 0.0;
+                for (uint32_t b = 0; b < B; b++) sum += boot[(size_t)b * nc + c];
+                boot_mean[c] = sum / B;
+                for (uint32_t b = 0; b < B; b++) dev += (boot[(size_t)b * nc + c] - boot_mean[c]) * (boot[(size_t)b * nc + c] - boot_mean[c]);
+                boot_sd[c] = B > 1 ? std::sqrt(dev / (B - 1)) : 0.0;
+            }
+        } else if (fin_eqclasses_abundance(g_eqc, lens, ab_max_iters, ab_tol, alpha.data(), nullptr, &info, err, sizeof err) != FIN_OK)
             throw runtime_error(err);
         double per_len_sum = 0.0;
         for (uint32_t c = 0; c < nc; c++) per_len_sum += alpha[c] / (ab_lengths.empty() ? 1.0 : ab_lengths[c]);
@@ -1450,13 +1487,15 @@ static int search_fmin(int argc, char** argv) {
         char num[96];
         for (uint32_t c = 0; c < nc; c++) {
             const double share = per_len_sum > 0.0 ? alpha[c] / (ab_lengths.empty() ? 1.0 : ab_lengths[c]) / per_len_sum : 0.0;
-            snprintf(num, sizeof num, "%u\t%.10g\t%.10g\n", c, alpha[c], share);
+            if (ab_bootstraps) snprintf(num, sizeof num, "%u\t%.10g\t%.10g\t%.10g\t%.10g\n", c, alpha[c], share, boot_mean[c], boot_sd[c]);
+            else snprintf(num, sizeof num, "%u\t%.10g\t%.10g\n", c, alpha[c], share);
             text += num;
         }
         text += "unaligned\t"; text += to_string(info.n_unaligned); text += '\n';
         text += "iterations\t"; text += to_string(info.iters); text += info.converged ? "\tconverged\n" : "\tmax_iters\n";
         snprintf(num, sizeof num, "loglik\t%.10g\n", info.loglik);
         text += num;
+        if (ab_bootstraps) { text += "bootstraps\t"; text += to_string(ab_bootstraps); text += "\tseed\t"; text += to_string(ab_seed); text += '\n'; }
         ofstream cf(ab_file, ios::binary | ios::trunc);
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + ab_file);

@@ -928,6 +928,42 @@ int fin_eqclasses_abundance(fin_eqclasses* e, const double* lengths, uint32_t ma
 int fin_classes_abundance(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, const double* lengths, uint32_t max_iters,
                           double tol, double* alpha_out, double* loglik_trace, fin_abundance_info* info, int n_threads);
 
+/* ---- BOOTSTRAP REPLICATES of the abundance estimate, resampled on the device ----
+ * How far to trust alpha: the estimate repeated over resampled class counts, the spread per colour left to the caller (kallisto -b, sleuth, mSWEEP's bootstrap).
+ * A POISSON BOOTSTRAP KEYED BY THE CLASS'S ROW -- not the multinomial one, which draws along the cumulative class counts and so depends on the order of the
+ * classes; the dense list's order is the table's slot order, which depends on claim races, and the same data and seed must give the same replicates.
+ *   ROW HASH      h_j = the xor over the words i < W of mix(word_i + (i + 1) 0x9E3779B97F4A7C15), mix = the splitmix64 finaliser: the hash the table narrows to
+ *                 its tag.
+ *   GENERATOR     Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, key {seed low 32, seed high 32}.  Block i of class
+ *                 j in replicate b: counter {h_j low, h_j high, i low 32, (i >> 32) | (b << 8)}; output word m (0 .. 3) belongs to read r = 4 i + m of the class,
+ *                 words with r >= n_j are discarded.
+ *   MULTIPLICITY  X(u) = the number of k in 0 .. 12 with u >= T_k, T_k = floor(2^32 e^-1 sum_{i <= k} 1 / i!) = 5e2d58d8 bc5ab1b1 eb715e1d fb239797 ff1025f5
+ *                 ffd90f3b fffa8b71 ffff540c ffffed1f fffffe21 ffffffd4 fffffffc ffffffff: Poisson(1) quantised to 2^-32, at most 13.
+ *   COUNTS        n_j^(b) = the sum of X over the reads r < n_j;  N_b = the sum of the n_j^(b): exact integers, a function of (row, n_j, seed, b) alone.  N_b varies
+ *                 around N by about sqrt(N) and is reported.
+ *   ESTIMATE      replicate b's is the definition above over the counts n_j^(b) and N_b: alpha0_c = N_b / n_colors; a class whose count is 0 contributes
+ *                 nothing (q_j = 0, a log term of 0); N_b = 0 -- with N = 1 a replicate is empty with probability 1 / e -- gives alpha all 0, iters 0,
+ *                 converged 1.  The point estimate is fin_eqclasses_abundance's, bit for bit.
+ * LIMITS: n_boot = 0 is FIN_EINVAL, n_boot > 4096 FIN_ELIMIT; N n_boot > 2^38 FIN_ELIMIT (it bounds the draws of a call; the message names both factors);
+ * n_j < 2^40.  fin_bootstrap_check makes these checks by themselves.
+ * A waiting call of fin_eqclasses_abundance's kind, with its refusals; ONE dense list is prepared for the 1 + n_boot estimates.  HBM beside that call's: 24 bytes
+ * per class (hash, slab prefix, counts).  Across PCIe: the point estimate, and per replicate 8 n_colors + 13 bytes.  alpha_out[n_colors]; info may be NULL;
+ * boot_alpha_out[n_boot * n_colors], boot_reads_out[n_boot] = N_b, boot_iters_out[n_boot], boot_converged_out[n_boot].  No classes: the point estimate as
+ * fin_eqclasses_abundance gives it and every replicate empty.  The accumulator is left as it was found.  Replicate b does not depend on n_boot. */
+int fin_bootstrap_check(uint64_t n_reads, uint32_t n_boot, char* err, size_t errlen);
+int fin_eqclasses_bootstrap(fin_eqclasses* e, const double* lengths, uint32_t max_iters, double tol, uint32_t n_boot, uint64_t seed,
+                            double* alpha_out /* n_colors: the point estimate */, fin_abundance_info* info /* the point estimate's, may be NULL */,
+                            double* boot_alpha_out /* n_boot x n_colors */, uint64_t* boot_reads_out /* n_boot: N_b */,
+                            uint32_t* boot_iters_out /* n_boot */, uint8_t* boot_converged_out /* n_boot */, char* err, size_t errlen);
+/* host twins, no device.  fin_classes_resample: the exact counts of replicate b (< 4096, else FIN_ELIMIT) for classes in the order given -- the order does not
+ * matter, counts_out[j] belongs to class j; a class of 0 reads has count 0.  fin_classes_bootstrap: the outputs of fin_eqclasses_bootstrap, each replicate being
+ * fin_classes_abundance over its non-zero classes in the order given; fin_classes_abundance's argument checks, and fin_bootstrap_check's */
+int fin_classes_resample(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, uint64_t seed, uint32_t b,
+                         uint64_t* counts_out, int n_threads);
+int fin_classes_bootstrap(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, const double* lengths, uint32_t max_iters,
+                          double tol, uint32_t n_boot, uint64_t seed, double* alpha_out, fin_abundance_info* info, double* boot_alpha_out, uint64_t* boot_reads_out,
+                          uint32_t* boot_iters_out, uint8_t* boot_converged_out, int n_threads);
+
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
  * k-mer is in no unitig), 1 a verified claim, 2 an unverified one (| 8: the exact side table has the k-mer, g is its answer), | 4 the text at [g-k+1, g] spells
