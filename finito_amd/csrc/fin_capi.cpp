@@ -3,7 +3,6 @@
 // without a HIP device every search entry point fails with FIN_ENODEV.
 #include <functional>
 #include <hip/hip_runtime_api.h>
-#include <sched.h>
 
 #include <algorithm>
 #include <atomic>
@@ -23,6 +22,7 @@
 #include "../../include/finito_amd.h"
 #include "fin_index.hpp"
 #include "fin_bootrng.h"
+#include "fin_host.h"
 #include "fin_kernels.h"
 
 static void set_err(char* err, size_t errlen, const std::string& msg) {
@@ -166,24 +166,6 @@ int fin_index_clear_option(fin_index* idx, const char* name) {
     if (!idx || !name) return FIN_EINVAL;
     for (int i = 0; i < O_COUNT; i++) if (!strcmp(name, OPTS[i].name)) { idx->opt_set[i].store(false); return FIN_OK; }
     return FIN_EINVAL;
-}
-
-int fin_host_threads(void) {
-    int n = 1;
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) n = CPU_COUNT(&set);
-    if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-        char a[64]; long long per = 0;
-        if (fscanf(f, "%63s %lld", a, &per) == 2 && strcmp(a, "max") != 0 && per > 0) {
-            long long q = atoll(a) / per;
-            if (q >= 1 && q < n) n = (int)q;
-        }
-        fclose(f);
-    }
-    int cap = 64;
-    if (const char* e = getenv("FINITO_THREADS")) { int v = atoi(e); if (v > 0) cap = v; }
-    if (n > cap) n = cap;
-    return n < 1 ? 1 : n;
 }
 
 int fin_index_build(const char* unitig_bases, const uint64_t* unitig_offsets, uint64_t n_unitigs, int k, int n_threads,
@@ -1319,63 +1301,6 @@ int fin_batch_download_records(fin_batch* b, fin_read_record* recs_out, int32_t*
     return FIN_OK;
 }
 
-// host: the pairs fin_search_batch delivers, from records + stream.  A chunk of reads per thread: first where each chunk's pairs and stream begin, then the pairs.
-int fin_expand_records(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, int32_t* pairs_out,
-                       uint64_t* n_positive, int n_threads) {
-    if ((n_reads && (!recs || !pairs_out)) || k < 1 || (n_stream_pairs && !stream_pairs)) return FIN_EINVAL;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
-    std::vector<uint64_t> out0((size_t)T + 1, 0), str0((size_t)T + 1, 0), pos((size_t)T, 0);
-    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
-    auto pass = [&](int t, bool write) {
-        const auto lh = bounds(t);
-        // (the counting pass starts every chunk at 0 -- its neighbour's count lands in the slot this chunk's start is read from in the second pass)
-        uint64_t o = write ? out0[(size_t)t] : 0, sp = write ? str0[(size_t)t] : 0, found = 0;
-        for (uint64_t r = lh.first; r < lh.second; r++) {
-            const fin_read_record& R = recs[r];
-            const uint32_t nk = R.nk, kind = R.meta >> 16;
-            if (write) {
-                int32_t* const dst = pairs_out + 2 * o;
-                if (kind == 0u) {
-                    if (sp + nk > n_stream_pairs) return false;
-                    memcpy(dst, stream_pairs + 2 * sp, (size_t)nk * 8);
-                    for (uint32_t i = 0; i < nk; i++) found += dst[2 * i] != -1;
-                } else if (kind == 2u) {
-                    for (uint32_t i = 0; i < 2 * nk; i++) dst[i] = -1;
-                } else {
-                    // one run: slot sl of strand A is (u, off0 + sl) unless a disagreeing position lies in [sl, sl + k - 1]; the reverse strand's slots mirror
-                    const bool rev = (R.meta >> 8) & 1u;
-                    const uint32_t nE = R.meta & 0xFFu;
-                    for (uint32_t i = 0; i < nk; i++) { const uint32_t sl = rev ? nk - 1u - i : i; dst[2 * i] = (int32_t)R.u; dst[2 * i + 1] = (int32_t)(R.off0 + sl); }
-                    uint64_t gaps = 0;
-                    uint32_t done_to = 0;   // slots below this are settled (the positions ascend: stretches of absent slots may touch or overlap)
-                    for (uint32_t e = 0; e < nE && e < 8u; e++) {
-                        const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
-                        uint32_t lo = E >= (uint32_t)(k - 1) ? E - (uint32_t)(k - 1) : 0u, hi = E < nk ? E : (nk ? nk - 1u : 0u);
-                        if (lo < done_to) lo = done_to;
-                        for (uint32_t sl = lo; nk && sl <= hi; sl++) { const uint32_t i = rev ? nk - 1u - sl : sl; dst[2 * i] = -1; dst[2 * i + 1] = -1; gaps++; }
-                        if (hi + 1u > done_to) done_to = hi + 1u;
-                    }
-                    found += nk - gaps;
-                }
-            }
-            o += nk; if (kind == 0u) sp += nk;
-        }
-        if (!write) { out0[(size_t)t + 1] = o; str0[(size_t)t + 1] = sp; } else pos[(size_t)t] = found;
-        return true;
-    };
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) (void)pass(t, false);
-    for (int t = 0; t < T; t++) { out0[(size_t)t + 1] += out0[(size_t)t]; str0[(size_t)t + 1] += str0[(size_t)t]; }
-    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) ok = pass(t, true) && ok;
-    if (!ok) return FIN_EINVAL;
-    if (n_positive) { uint64_t f = 0; for (uint64_t x : pos) f += x; *n_positive = f; }
-    return FIN_OK;
-}
-
 // ---- results as segments (fin_segments.hip) ---------------------------------------------------------------------------------------
 static_assert(sizeof(fin_segment) == 16, "a segment is 16 bytes");
 
@@ -1426,161 +1351,6 @@ int fin_batch_download_segments(fin_batch* b, uint64_t* seg_offs_out, fin_segmen
     HIPCHK(hipMemcpyAsync(seg_offs_out, b->d_sgm_offs, (size_t)b->n_reads * 8 + 8, hipMemcpyDeviceToHost, st));
     if (b->n_segments) HIPCHK(hipMemcpyAsync(segs_out, b->d_sgm, (size_t)b->n_segments * 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    return FIN_OK;
-}
-
-extern "C++" {
-// the canonical segmentation of one read's slots (include/finito_amd.h): emit(u, off, slot, len) per segment, in slot order.  false: a pair that is neither
-// found nor (-1,-1)
-template <class F>
-static bool segment_slots(const int32_t* p, uint32_t nk, F&& emit) {
-    int lp = 0;            // link(i - 1)
-    uint32_t head = 0; bool in = false; int dir = 0;   // the open segment: its head slot, the sign of its internal links (0: one slot so far)
-    auto close = [&](uint32_t end) {
-        if (!in) return;
-        const uint32_t n = end - head;
-        emit(p[2 * head], p[2 * head + 1], head, dir < 0 ? -(int32_t)n : (int32_t)n);
-        in = false;
-    };
-    for (uint32_t i = 0; i < nk; i++) {
-        const int32_t u = p[2 * i], off = p[2 * i + 1];
-        if (u < 0) {
-            if (u != -1) return false;
-            close(i); lp = 0;
-            continue;
-        }
-        int l = 0;
-        if (i && p[2 * i - 2] == u) { const int64_t d = (int64_t)off - (int64_t)p[2 * i - 1]; l = d == 1 ? 1 : d == -1 ? -1 : 0; }
-        if (l == 0 || (lp != 0 && lp != l)) { close(i); head = i; in = true; dir = 0; }
-        else dir = l;
-        lp = l;
-    }
-    close(nk);
-    return true;
-}
-// the found stretches of a kind-1 record as segments, in slot order (the arithmetic of fin_expand_records)
-template <class F>
-static void segment_record(const fin_read_record& R, int k, F&& emit) {
-    const uint32_t nk = R.nk, nE = R.meta & 0xFFu;
-    if (!nk) return;
-    const bool rev = (R.meta >> 8) & 1u;
-    uint32_t from[9], to[9], n = 0, done_to = 0, at = 0;
-    for (uint32_t e = 0; e < nE && e < 8u; e++) {
-        const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
-        uint32_t lo = E >= (uint32_t)(k - 1) ? E - (uint32_t)(k - 1) : 0u, hi = E < nk ? E : nk - 1u;
-        if (lo < done_to) lo = done_to;
-        if (lo <= hi) { if (lo > at) { from[n] = at; to[n] = lo; n++; } at = hi + 1u; }
-        if (hi + 1u > done_to) done_to = hi + 1u;
-    }
-    if (nk > at) { from[n] = at; to[n] = nk; n++; }
-    for (uint32_t s = 0; s < n; s++) {
-        if (!rev) emit((int32_t)R.u, (int32_t)(R.off0 + from[s]), from[s], (int32_t)(to[s] - from[s]));
-        else { const uint32_t q = n - 1u - s, len = to[q] - from[q]; emit((int32_t)R.u, (int32_t)(R.off0 + to[q] - 1u), nk - to[q], len == 1u ? 1 : -(int32_t)len); }
-    }
-}
-
-}  // extern "C++"
-
-// host: the same segments from records + stream, the pairs never made -- the CPU statement of fin_segments.hip.  A chunk of reads per thread: first how many
-// segments and stream pairs each chunk has, then the segments
-int fin_records_segments(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t* seg_offs_out,
-                         fin_segment* segs_out, uint64_t seg_cap, uint64_t* n_segments, int n_threads) {
-    if ((n_reads && !recs) || k < 1 || (n_stream_pairs && !stream_pairs) || !seg_offs_out) return FIN_EINVAL;
-    if (n_segments) *n_segments = 0;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
-    std::vector<uint64_t> seg0((size_t)T + 1, 0), str0((size_t)T + 1, 0);
-    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
-        const auto lh = bounds(t);
-        uint64_t sp = 0;
-        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
-        str0[(size_t)t + 1] = sp;
-    }
-    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
-    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
-    auto pass = [&](int t, bool write) {
-        const auto lh = bounds(t);
-        uint64_t sp = str0[(size_t)t], sg = write ? seg0[(size_t)t] : 0;
-        auto emit = [&](int32_t u, int32_t off, uint32_t slot, int32_t len) { if (write) segs_out[sg] = fin_segment{u, off, slot, len}; sg++; };
-        for (uint64_t r = lh.first; r < lh.second; r++) {
-            const fin_read_record& R = recs[r];
-            const uint32_t kind = R.meta >> 16;
-            if (write) seg_offs_out[r] = sg;
-            if (kind == 0u) { if (!segment_slots(stream_pairs + 2 * sp, R.nk, emit)) return false; sp += R.nk; }
-            else if (kind == 1u) segment_record(R, k, emit);
-        }
-        if (!write) seg0[(size_t)t + 1] = sg;
-        return true;
-    };
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) ok = pass(t, false) && ok;
-    if (!ok) return FIN_EINVAL;
-    for (int t = 0; t < T; t++) seg0[(size_t)t + 1] += seg0[(size_t)t];
-    const uint64_t total = seg0[(size_t)T];
-    if (n_segments) *n_segments = total;
-    if (total > seg_cap || (total && !segs_out)) return total > seg_cap ? FIN_ELIMIT : FIN_EINVAL;
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) (void)pass(t, true);
-    seg_offs_out[n_reads] = total;
-    return FIN_OK;
-}
-
-// host: fin_search_batch's pairs from segments.  Every read is checked before anything of it is written
-int fin_expand_segments(const uint64_t* seg_offs, const fin_segment* segs, uint64_t n_reads, const uint32_t* nk_per_read, int32_t* pairs_out, uint64_t* n_positive,
-                        int n_threads) {
-    if (!seg_offs || (n_reads && !nk_per_read)) return FIN_EINVAL;
-    for (uint64_t r = 0; r < n_reads; r++) if (seg_offs[r + 1] < seg_offs[r]) return FIN_EINVAL;
-    if (n_reads && seg_offs[n_reads] > seg_offs[0] && !segs) return FIN_EINVAL;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
-    std::vector<uint64_t> out0((size_t)T + 1, 0), pos((size_t)T, 0);
-    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) {   // where each chunk's pairs begin; every segment checked
-        const auto lh = bounds(t);
-        uint64_t o = 0; bool good = true;
-        for (uint64_t r = lh.first; r < lh.second && good; r++) {
-            const uint64_t nk = nk_per_read[r];
-            uint64_t next = 0;   // the first slot a segment may begin at
-            for (uint64_t s = seg_offs[r]; s < seg_offs[r + 1]; s++) {
-                const fin_segment& S = segs[s];
-                const uint64_t n = S.len < 0 ? (uint64_t)(-(int64_t)S.len) : (uint64_t)S.len;
-                if (n == 0 || S.u < 0 || S.off < 0 || S.slot < next || (uint64_t)S.slot + n > nk) { good = false; break; }
-                if (S.len < 0 ? (int64_t)S.off - (int64_t)(n - 1) < 0 : (int64_t)S.off + (int64_t)(n - 1) > 0x7FFFFFFFll) { good = false; break; }
-                next = (uint64_t)S.slot + n;
-            }
-            o += nk;
-        }
-        out0[(size_t)t + 1] = o;
-        ok = good && ok;
-    }
-    if (!ok) return FIN_EINVAL;
-    for (int t = 0; t < T; t++) out0[(size_t)t + 1] += out0[(size_t)t];
-    if (out0[(size_t)T] && !pairs_out) return FIN_EINVAL;
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) {
-        const auto lh = bounds(t);
-        uint64_t o = out0[(size_t)t], found = 0;
-        for (uint64_t r = lh.first; r < lh.second; r++) {
-            const uint64_t nk = nk_per_read[r];
-            int32_t* const dst = pairs_out + 2 * o;
-            for (uint64_t i = 0; i < 2 * nk; i++) dst[i] = -1;
-            for (uint64_t s = seg_offs[r]; s < seg_offs[r + 1]; s++) {
-                const fin_segment& S = segs[s];
-                const int32_t step = S.len < 0 ? -1 : 1;
-                const uint32_t n = (uint32_t)(S.len < 0 ? -(int64_t)S.len : (int64_t)S.len);   // (checked above: 1 .. nk)
-                for (uint32_t j = 0; j < n; j++) { dst[2 * (S.slot + j)] = S.u; dst[2 * (S.slot + j) + 1] = S.off + step * (int32_t)j; }
-                found += n;
-            }
-            o += nk;
-        }
-        pos[(size_t)t] = found;
-    }
-    if (n_positive) { uint64_t f = 0; for (uint64_t x : pos) f += x; *n_positive = f; }
     return FIN_OK;
 }
 
@@ -1659,51 +1429,6 @@ int fin_batch_download_screen(fin_batch* b, uint32_t* ids_out, uint64_t* bits_ou
     if (bits_out && n_words) HIPCHK(hipMemcpyAsync(bits_out, b->d_scr_bits, n_words * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return FIN_OK;
-}
-
-// host: the same summaries from records + stream -- the CPU statement of fin_readsum.hip, over the segments segment_slots / segment_record make: n_found is the
-// sum of their lengths, span runs from the first one's slot to the last one's end
-int fin_records_read_summaries(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, fin_read_summary* out,
-                               int n_threads) {
-    if ((n_reads && (!recs || !out)) || k < 1 || (n_stream_pairs && !stream_pairs)) return FIN_EINVAL;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
-    std::vector<uint64_t> str0((size_t)T + 1, 0);
-    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
-        const auto lh = bounds(t);
-        uint64_t sp = 0;
-        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
-        str0[(size_t)t + 1] = sp;
-    }
-    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
-    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) {
-        const auto lh = bounds(t);
-        uint64_t sp = str0[(size_t)t];
-        bool good = true;
-        for (uint64_t r = lh.first; r < lh.second && good; r++) {
-            const fin_read_record& R = recs[r];
-            const uint32_t kind = R.meta >> 16;
-            fin_read_summary S{0, 0, 0, 0};
-            uint32_t first = 0, end = 0;
-            auto emit = [&](int32_t, int32_t, uint32_t slot, int32_t len) {
-                const uint32_t n = (uint32_t)(len < 0 ? -(int64_t)len : (int64_t)len);
-                if (S.n_segments == 0) first = slot;
-                S.n_found += n; S.n_segments++; if (n > S.longest) S.longest = n;
-                end = slot + n;
-            };
-            if (kind == 0u) { good = segment_slots(stream_pairs + 2 * sp, R.nk, emit); sp += R.nk; }
-            else if (kind == 1u) segment_record(R, k, emit);
-            S.span = end - first;
-            out[r] = S;
-        }
-        ok = good && ok;
-    }
-    return ok ? FIN_OK : FIN_EINVAL;
 }
 
 // ---- the profile over the unitig set (fin_hits.hip) ---------------------------------------------------------------------------------
@@ -1964,59 +1689,6 @@ int fin_batch_add_classes(fin_batch* b, fin_labels* l, uint32_t min_found, uint3
     return l->pend.mark(st, err, errlen);
 }
 
-// host: the same classes from records + stream -- the CPU statement of fin_classify.hip, over the segments segment_slots / segment_record make: a segment of
-// |len| slots in unitig u is |len| votes for labels[u]
-int fin_records_read_classes(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k,
-                             const uint32_t* unitig_labels, uint64_t n_unitigs, fin_read_class* out, int n_threads) {
-    if ((n_reads && (!recs || !out)) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !unitig_labels)) return FIN_EINVAL;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
-    std::vector<uint64_t> str0((size_t)T + 1, 0);
-    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
-        const auto lh = bounds(t);
-        uint64_t sp = 0;
-        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
-        str0[(size_t)t + 1] = sp;
-    }
-    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
-    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) {
-        const auto lh = bounds(t);
-        uint64_t sp = str0[(size_t)t];
-        bool good = true;
-        std::vector<std::pair<uint32_t, uint32_t>> votes;   // (label, slots) per segment, then sorted by label
-        for (uint64_t r = lh.first; r < lh.second && good; r++) {
-            const fin_read_record& R = recs[r];
-            const uint32_t kind = R.meta >> 16;
-            votes.clear();
-            auto emit = [&](int32_t u, int32_t, uint32_t, int32_t len) {
-                if ((uint64_t)(uint32_t)u >= n_unitigs) { good = false; return; }
-                const uint32_t L = unitig_labels[(uint32_t)u];
-                if (L != FIN_NO_LABEL) votes.push_back({L, (uint32_t)(len < 0 ? -(int64_t)len : (int64_t)len)});
-            };
-            if (kind == 0u) { good = segment_slots(stream_pairs + 2 * sp, R.nk, emit) && good; sp += R.nk; }
-            else if (kind == 1u) segment_record(R, k, emit);
-            std::sort(votes.begin(), votes.end());
-            fin_read_class C{FIN_NO_LABEL, 0, 0, 0};
-            for (size_t i = 0; i < votes.size();) {   // ascending labels: a later label wins only with a larger count
-                uint32_t c = 0; size_t j = i;
-                for (; j < votes.size() && votes[j].first == votes[i].first; j++) c += votes[j].second;
-                C.n_labelled += c;
-                if (c > C.n_best) { C.n_second = C.n_best; C.n_best = c; C.label = votes[i].first; }
-                else if (c > C.n_second) C.n_second = c;
-                i = j;
-            }
-            out[r] = C;
-        }
-        ok = good && ok;
-    }
-    return ok ? FIN_OK : FIN_EINVAL;
-}
-
 // ---- colour sets per unitig and read pseudoalignment (fin_colors.hip) -------------------------------------------------------------------
 static_assert(sizeof(fin_read_pseudo) == 16, "a pseudoalignment head is 16 bytes");
 struct fin_colors {
@@ -2028,13 +1700,6 @@ struct fin_colors {
 };
 static size_t colors_bytes(const fin_colors* c) { return (size_t)c->n_unitigs * c->words * 8; }
 static uint32_t* colors_flags(const fin_colors* c) { return (uint32_t*)((char*)c->d_bits + colors_bytes(c)); }
-// the first unitig with a bit at or above n_colors set, or n_unitigs
-static uint64_t colors_first_stray(const uint64_t* bits, uint64_t n_unitigs, uint32_t n_colors, uint32_t W) {
-    if ((n_colors & 63u) == 0u) return n_unitigs;   // (the last word is all colours)
-    const uint64_t stray = ~0ull << (n_colors & 63u);
-    for (uint64_t u = 0; u < n_unitigs; u++) if (bits[u * W + (W - 1)] & stray) return u;
-    return n_unitigs;
-}
 
 void fin_colors_free(fin_colors* c) {
     if (!c) return;
@@ -2148,72 +1813,6 @@ int fin_batch_download_pseudo(fin_batch* b, uint64_t* rows_out, fin_read_pseudo*
     return FIN_OK;
 }
 
-// host: the same rows and heads from records + stream -- the CPU statement of fin_col_pseudo_kernel, over the segments segment_slots / segment_record make: a
-// segment of |len| slots in unitig u is |len| counts for every colour of u
-int fin_records_pseudoalign(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint64_t* bits,
-                            uint64_t n_unitigs, uint32_t n_colors, uint32_t permille, uint64_t* rows_out, fin_read_pseudo* heads_out, int n_threads) {
-    if ((n_reads && (!recs || !rows_out || !heads_out)) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !bits)) return FIN_EINVAL;
-    if (n_colors == 0 || n_colors > FIN_MAX_COLORS) return FIN_ELIMIT;
-    if (permille > 1000u) return FIN_EINVAL;
-    const uint32_t W = (n_colors + 63u) / 64u;
-    if (colors_first_stray(bits, n_unitigs, n_colors, W) != n_unitigs) return FIN_EINVAL;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
-    std::vector<uint64_t> str0((size_t)T + 1, 0);
-    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
-        const auto lh = bounds(t);
-        uint64_t sp = 0;
-        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
-        str0[(size_t)t + 1] = sp;
-    }
-    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
-    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) {
-        const auto lh = bounds(t);
-        uint64_t sp = str0[(size_t)t];
-        bool good = true;
-        std::vector<std::pair<uint32_t, uint32_t>> segs;   // (unitig, slots) per segment
-        std::vector<uint64_t> cnt((size_t)W * 64);
-        for (uint64_t r = lh.first; r < lh.second && good; r++) {
-            const fin_read_record& R = recs[r];
-            const uint32_t kind = R.meta >> 16;
-            segs.clear();
-            auto emit = [&](int32_t u, int32_t, uint32_t, int32_t len) {
-                if ((uint64_t)(uint32_t)u >= n_unitigs) { good = false; return; }
-                segs.push_back({(uint32_t)u, (uint32_t)(len < 0 ? -(int64_t)len : (int64_t)len)});
-            };
-            if (kind == 0u) { good = segment_slots(stream_pairs + 2 * sp, R.nk, emit) && good; sp += R.nk; }
-            else if (kind == 1u) segment_record(R, k, emit);
-            std::fill(cnt.begin(), cnt.end(), 0);
-            uint64_t n_found = 0, n_colored = 0;
-            for (const auto& sg : segs) {
-                n_found += sg.second;
-                const uint64_t* row = bits + (uint64_t)sg.first * W;
-                bool ne = false;
-                for (uint32_t w = 0; w < W; w++) {
-                    uint64_t x = row[w];
-                    if (x) ne = true;
-                    for (; x; x &= x - 1) cnt[(size_t)w * 64 + (size_t)__builtin_ctzll(x)] += sg.second;
-                }
-                if (ne) n_colored += sg.second;
-            }
-            uint32_t pc = 0;
-            for (uint32_t w = 0; w < W; w++) {
-                uint64_t o = 0;
-                for (uint32_t q = 0; q < 64u; q++) { const uint64_t c = cnt[(size_t)w * 64 + q]; if (c >= 1 && 1000ull * c >= (uint64_t)permille * n_colored) o |= 1ull << q; }
-                rows_out[r * W + w] = o; pc += (uint32_t)__builtin_popcountll(o);
-            }
-            heads_out[r] = fin_read_pseudo{(uint32_t)n_found, (uint32_t)n_colored, pc, 0};
-        }
-        ok = good && ok;
-    }
-    return ok ? FIN_OK : FIN_EINVAL;
-}
-
 // ---- paired-end pseudoalignment: one colour row per fragment (fin_paired.hip) -------------------------------------------------------------
 static_assert(sizeof(fin_pair_pseudo) == 16, "a fragment's pseudoalignment head is 16 bytes");
 int fin_batch_pseudoalign_paired(fin_batch* b, const fin_colors* c, uint32_t permille, uint32_t mode, char* err, size_t errlen) {
@@ -2252,78 +1851,6 @@ int fin_batch_download_pair_pseudo(fin_batch* b, uint64_t* rows_out, fin_pair_ps
     if (nf && heads_out) HIPCHK(hipMemcpyAsync(heads_out, b->d_pair_heads, nf * 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return FIN_OK;
-}
-
-// host: the definition over the two mates' segments -- fin_records_pseudoalign with a fragment's segments pooled and the first mate's coloured slots kept apart
-int fin_records_pseudoalign_paired(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint64_t* bits,
-                                   uint64_t n_unitigs, uint32_t n_colors, uint32_t permille, uint32_t mode, uint64_t* rows_out, fin_pair_pseudo* heads_out, int n_threads) {
-    const uint64_t nf = n_reads / 2;
-    if ((n_reads && !recs) || (nf && (!rows_out || !heads_out)) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !bits)) return FIN_EINVAL;
-    if (n_colors == 0 || n_colors > FIN_MAX_COLORS) return FIN_ELIMIT;
-    if (permille > 1000u || (n_reads & 1u) || (mode != FIN_PAIR_ANY && mode != FIN_PAIR_BOTH)) return FIN_EINVAL;
-    const uint32_t W = (n_colors + 63u) / 64u;
-    if (colors_first_stray(bits, n_unitigs, n_colors, W) != n_unitigs) return FIN_EINVAL;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > nf / 1024 + 1) T = (int)(nf / 1024 + 1);
-    std::vector<uint64_t> str0((size_t)T + 1, 0);
-    auto bounds = [&](int t) { return std::make_pair(nf * (uint64_t)t / (uint64_t)T, nf * (uint64_t)(t + 1) / (uint64_t)T); };   // (in fragments)
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
-        const auto lh = bounds(t);
-        uint64_t sp = 0;
-        for (uint64_t r = 2 * lh.first; r < 2 * lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
-        str0[(size_t)t + 1] = sp;
-    }
-    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
-    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) {
-        const auto lh = bounds(t);
-        uint64_t sp = str0[(size_t)t];
-        bool good = true;
-        std::vector<std::pair<uint32_t, uint32_t>> segs;   // (unitig, slots) per segment, the first mate's first
-        std::vector<uint64_t> cnt((size_t)W * 64);
-        for (uint64_t f = lh.first; f < lh.second && good; f++) {
-            segs.clear();
-            size_t n_first_segs = 0;
-            auto emit = [&](int32_t u, int32_t, uint32_t, int32_t len) {
-                if ((uint64_t)(uint32_t)u >= n_unitigs) { good = false; return; }
-                segs.push_back({(uint32_t)u, (uint32_t)(len < 0 ? -(int64_t)len : (int64_t)len)});
-            };
-            for (uint64_t r = 2 * f; r < 2 * f + 2; r++) {
-                const fin_read_record& R = recs[r];
-                const uint32_t kind = R.meta >> 16;
-                if (kind == 0u) { good = segment_slots(stream_pairs + 2 * sp, R.nk, emit) && good; sp += R.nk; }
-                else if (kind == 1u) segment_record(R, k, emit);
-                if (r == 2 * f) n_first_segs = segs.size();
-            }
-            std::fill(cnt.begin(), cnt.end(), 0);
-            uint64_t n_found = 0, n_colored = 0, n_first = 0;
-            for (size_t q = 0; q < segs.size(); q++) {
-                const auto& sg = segs[q];
-                n_found += sg.second;
-                const uint64_t* row = bits + (uint64_t)sg.first * W;
-                bool ne = false;
-                for (uint32_t w = 0; w < W; w++) {
-                    uint64_t x = row[w];
-                    if (x) ne = true;
-                    for (; x; x &= x - 1) cnt[(size_t)w * 64 + (size_t)__builtin_ctzll(x)] += sg.second;
-                }
-                if (ne) { n_colored += sg.second; if (q < n_first_segs) n_first += sg.second; }
-            }
-            const bool keep = mode == FIN_PAIR_ANY || (n_first != 0 && n_colored != n_first);
-            uint32_t pc = 0;
-            for (uint32_t w = 0; w < W; w++) {
-                uint64_t o = 0;
-                if (keep) for (uint32_t q = 0; q < 64u; q++) { const uint64_t c = cnt[(size_t)w * 64 + q]; if (c >= 1 && 1000ull * c >= (uint64_t)permille * n_colored) o |= 1ull << q; }
-                rows_out[f * W + w] = o; pc += (uint32_t)__builtin_popcountll(o);
-            }
-            heads_out[f] = fin_pair_pseudo{(uint32_t)n_found, (uint32_t)n_colored, pc, (uint32_t)n_first};
-        }
-        ok = good && ok;
-    }
-    return ok ? FIN_OK : FIN_EINVAL;
 }
 
 // ---- equivalence classes of pseudoaligned reads (fin_eqclasses.hip) ---------------------------------------------------------------------
@@ -2878,69 +2405,6 @@ int fin_classes_bootstrap(const uint64_t* class_rows, const uint64_t* class_read
     return FIN_OK;
 }
 
-// host: the profile from records + stream -- fin_expand_records' arithmetic without the pairs.  A chunk of reads per thread, each with counts of its own
-// when the unitig set is small, else atomic adds into the caller's array
-int fin_records_unitig_counts(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, uint64_t n_unitigs,
-                              uint64_t* counts_out, int n_threads) {
-    if ((n_reads && !recs) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !counts_out)) return FIN_EINVAL;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
-    for (uint64_t u = 0; u < n_unitigs; u++) counts_out[u] = 0;
-    std::vector<uint64_t> str0((size_t)T + 1, 0);
-    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
-        const auto lh = bounds(t);
-        uint64_t sp = 0;
-        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
-        str0[(size_t)t + 1] = sp;
-    }
-    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
-    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) {
-        const auto lh = bounds(t);
-        uint64_t sp = str0[(size_t)t];
-        bool good = true;
-        auto add = [&](uint64_t u, uint64_t n) {
-            if (u >= n_unitigs) { good = false; return; }
-            if (T == 1) counts_out[u] += n;
-            else __atomic_fetch_add(counts_out + u, n, __ATOMIC_RELAXED);
-        };
-        for (uint64_t r = lh.first; r < lh.second && good; r++) {
-            const fin_read_record& R = recs[r];
-            const uint32_t nk = R.nk, kind = R.meta >> 16;
-            if (kind == 0u) {
-                const int32_t* const src = stream_pairs + 2 * sp;
-                for (uint32_t i = 0; i < nk;) {   // a run of slots in one unitig: one add
-                    const int32_t u = src[2 * i];
-                    uint32_t j = i + 1;
-                    while (j < nk && src[2 * j] == u) j++;
-                    if (u >= 0) add((uint64_t)u, j - i);
-                    else if (u != -1) good = false;
-                    i = j;
-                }
-                sp += nk;
-            } else if (kind == 1u) {
-                const uint32_t nE = R.meta & 0xFFu;
-                uint64_t gaps = 0;
-                uint32_t done_to = 0;
-                for (uint32_t e = 0; e < nE && e < 8u; e++) {
-                    const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
-                    uint32_t lo = E >= (uint32_t)(k - 1) ? E - (uint32_t)(k - 1) : 0u, hi = E < nk ? E : (nk ? nk - 1u : 0u);
-                    if (lo < done_to) lo = done_to;
-                    if (nk && lo <= hi) gaps += hi - lo + 1u;
-                    if (hi + 1u > done_to) done_to = hi + 1u;
-                }
-                if (nk - gaps) add(R.u, nk - gaps);
-            }
-        }
-        ok = good && ok;
-    }
-    return ok ? FIN_OK : FIN_EINVAL;
-}
-
 // ---- breadth of coverage over the unitig text (fin_cover.hip) -------------------------------------------------------------------------
 struct fin_cover {
     const fin_index* idx = nullptr;
@@ -3022,77 +2486,6 @@ int fin_cover_download(fin_cover* c, uint64_t* bits_out, uint64_t* covered_out, 
         if (total_covered) { uint64_t t = 0; for (uint64_t u = 0; u < c->n_unitigs; u++) t += dst[u]; *total_covered = t; }
     }
     return FIN_OK;
-}
-
-// host: the bitmap from records + stream -- fin_expand_records' arithmetic, the pairs never made.  A chunk of reads per thread; with more than one thread
-// the words are ORed atomically
-int fin_records_cover(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
-                      uint64_t n_unitigs, uint64_t* bits_out, int n_threads) {
-    if ((n_reads && !recs) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && (!unitig_ends || !bits_out))) return FIN_EINVAL;
-    int64_t prev = 0;
-    for (uint64_t u = 0; u < n_unitigs; u++) { if (unitig_ends[u] < prev) return FIN_EINVAL; prev = unitig_ends[u]; }
-    const uint64_t total_len = (uint64_t)prev, n_words = (total_len + 63) / 64;
-    for (uint64_t w = 0; w < n_words; w++) bits_out[w] = 0;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
-    std::vector<uint64_t> str0((size_t)T + 1, 0);
-    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
-        const auto lh = bounds(t);
-        uint64_t sp = 0;
-        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
-        str0[(size_t)t + 1] = sp;
-    }
-    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
-    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) {
-        const auto lh = bounds(t);
-        uint64_t sp = str0[(size_t)t];
-        bool good = true;
-        // offsets [off_lo, off_hi) of unitig u, each the first base of a found k-mer: it must lie whole inside the unitig
-        auto set = [&](uint64_t u, uint64_t off_lo, uint64_t off_hi) {
-            if (off_lo >= off_hi) return;
-            if (u >= n_unitigs) { good = false; return; }
-            const uint64_t start = u ? (uint64_t)unitig_ends[u - 1] : 0, end = (uint64_t)unitig_ends[u];
-            if (start + off_hi - 1 + (uint64_t)k > end) { good = false; return; }
-            const uint64_t g0 = start + off_lo, g1 = start + off_hi;
-            for (uint64_t w = g0 >> 6; (w << 6) < g1; w++) {
-                const uint64_t wb = w << 6, lo = g0 > wb ? g0 : wb, hi = g1 < wb + 64 ? g1 : wb + 64;
-                const uint64_t m = (~0ull >> (64 - (hi - lo))) << (lo - wb);
-                if (T == 1) bits_out[w] |= m;
-                else __atomic_fetch_or(bits_out + w, m, __ATOMIC_RELAXED);
-            }
-        };
-        for (uint64_t r = lh.first; r < lh.second && good; r++) {
-            const fin_read_record& R = recs[r];
-            const uint32_t nk = R.nk, kind = R.meta >> 16;
-            if (kind == 0u) {
-                const int32_t* const src = stream_pairs + 2 * sp;
-                for (uint32_t i = 0; i < nk; i++) {
-                    const int32_t u = src[2 * i], off = src[2 * i + 1];
-                    if (u >= 0 && off >= 0) set((uint64_t)u, (uint64_t)off, (uint64_t)off + 1);
-                    else if (u != -1) good = false;
-                }
-                sp += nk;
-            } else if (kind == 1u && nk) {
-                const uint32_t nE = R.meta & 0xFFu;
-                uint32_t done_to = 0, from = 0;   // `from`: where the found stretch in front of the next gap begins
-                for (uint32_t e = 0; e < nE && e < 8u; e++) {
-                    const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
-                    uint32_t lo = E >= (uint32_t)(k - 1) ? E - (uint32_t)(k - 1) : 0u, hi = E < nk ? E : nk - 1u;
-                    if (lo < done_to) lo = done_to;
-                    if (lo <= hi) { set(R.u, (uint64_t)R.off0 + from, (uint64_t)R.off0 + lo); from = hi + 1u; }
-                    if (hi + 1u > done_to) done_to = hi + 1u;
-                }
-                set(R.u, (uint64_t)R.off0 + from, (uint64_t)R.off0 + nk);
-            }
-        }
-        ok = good && ok;
-    }
-    return ok ? FIN_OK : FIN_EINVAL;
 }
 
 // ---- per-position depth over the unitig text (fin_depth.hip) ---------------------------------------------------------------------------
@@ -3199,74 +2592,6 @@ int fin_depth_download(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, fi
         if (total) { uint64_t t = 0; for (uint64_t u = 0; u < d->n_unitigs; u++) t += dst[u].sum; *total = t; }
     }
     return FIN_OK;
-}
-
-// host: the depth from records + stream -- fin_expand_records' arithmetic, the pairs never made.  A chunk of reads per thread; with more than one thread the
-// positions are added atomically
-int fin_records_depth(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
-                      uint64_t n_unitigs, uint32_t* depth_out, int n_threads) {
-    if ((n_reads && !recs) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && (!unitig_ends || !depth_out))) return FIN_EINVAL;
-    int64_t prev = 0;
-    for (uint64_t u = 0; u < n_unitigs; u++) { if (unitig_ends[u] < prev) return FIN_EINVAL; prev = unitig_ends[u]; }
-    const uint64_t total_len = (uint64_t)prev;
-    for (uint64_t g = 0; g < total_len; g++) depth_out[g] = 0;
-    int T = n_threads > 0 ? n_threads : fin_host_threads();
-    if ((uint64_t)T > n_reads / 1024 + 1) T = (int)(n_reads / 1024 + 1);
-    std::vector<uint64_t> str0((size_t)T + 1, 0);
-    auto bounds = [&](int t) { return std::make_pair(n_reads * (uint64_t)t / (uint64_t)T, n_reads * (uint64_t)(t + 1) / (uint64_t)T); };
-#pragma omp parallel for num_threads(T) schedule(static)
-    for (int t = 0; t < T; t++) {   // where each chunk's share of the stream begins
-        const auto lh = bounds(t);
-        uint64_t sp = 0;
-        for (uint64_t r = lh.first; r < lh.second; r++) if ((recs[r].meta >> 16) == 0u) sp += recs[r].nk;
-        str0[(size_t)t + 1] = sp;
-    }
-    for (int t = 0; t < T; t++) str0[(size_t)t + 1] += str0[(size_t)t];
-    if (str0[(size_t)T] != n_stream_pairs) return FIN_EINVAL;   // records and stream do not belong together
-    bool ok = true;
-#pragma omp parallel for num_threads(T) schedule(static) reduction(&& : ok)
-    for (int t = 0; t < T; t++) {
-        const auto lh = bounds(t);
-        uint64_t sp = str0[(size_t)t];
-        bool good = true;
-        // offsets [off_lo, off_hi) of unitig u, each the first base of a found k-mer: it must lie whole inside the unitig
-        auto add = [&](uint64_t u, uint64_t off_lo, uint64_t off_hi) {
-            if (off_lo >= off_hi) return;
-            if (u >= n_unitigs) { good = false; return; }
-            const uint64_t start = u ? (uint64_t)unitig_ends[u - 1] : 0, end = (uint64_t)unitig_ends[u];
-            if (start + off_hi - 1 + (uint64_t)k > end) { good = false; return; }
-            for (uint64_t g = start + off_lo; g < start + off_hi; g++) {
-                if (T == 1) depth_out[g]++;
-                else __atomic_fetch_add(depth_out + g, 1u, __ATOMIC_RELAXED);
-            }
-        };
-        for (uint64_t r = lh.first; r < lh.second && good; r++) {
-            const fin_read_record& R = recs[r];
-            const uint32_t nk = R.nk, kind = R.meta >> 16;
-            if (kind == 0u) {
-                const int32_t* const src = stream_pairs + 2 * sp;
-                for (uint32_t i = 0; i < nk; i++) {
-                    const int32_t u = src[2 * i], off = src[2 * i + 1];
-                    if (u >= 0 && off >= 0) add((uint64_t)u, (uint64_t)off, (uint64_t)off + 1);
-                    else if (u != -1) good = false;
-                }
-                sp += nk;
-            } else if (kind == 1u && nk) {
-                const uint32_t nE = R.meta & 0xFFu;
-                uint32_t done_to = 0, from = 0;   // `from`: where the found stretch in front of the next gap begins
-                for (uint32_t e = 0; e < nE && e < 8u; e++) {
-                    const uint32_t E = (uint32_t)((e < 4u ? R.Es : R.Es2) >> (16u * (e & 3u))) & 0xFFFFu;
-                    uint32_t lo = E >= (uint32_t)(k - 1) ? E - (uint32_t)(k - 1) : 0u, hi = E < nk ? E : nk - 1u;
-                    if (lo < done_to) lo = done_to;
-                    if (lo <= hi) { add(R.u, (uint64_t)R.off0 + from, (uint64_t)R.off0 + lo); from = hi + 1u; }
-                    if (hi + 1u > done_to) done_to = hi + 1u;
-                }
-                add(R.u, (uint64_t)R.off0 + from, (uint64_t)R.off0 + nk);
-            }
-        }
-        ok = good && ok;
-    }
-    return ok ? FIN_OK : FIN_EINVAL;
 }
 
 int fin_batch_step_time(const fin_batch* b, uint64_t skip_first, double ms_parts[5], uint64_t* n_runs) {

@@ -163,18 +163,12 @@ __device__ __forceinline__ uint4 col_pseudo_scan(const int2* pairs, uint64_t lo,
     return make_uint4(n_found, n_colored, pc, 0u);
 }
 
-// a step whose overflow list overran has no results (batch_overrun_check, fin_capi.cpp): nothing is set, the matrix is flagged
-__device__ __forceinline__ bool col_withheld(const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t* flags) {
-    if (!ovf_count || *ovf_count <= ovf_cap) return false;
-    if (blockIdx.x == 0 && threadIdx.x == 0) (void)__hip_atomic_fetch_or(flags, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-}
 }  // namespace
 
 // bits[u][color] = 1 for every unitig u in which the run found a k-mer.  frec null: the step left no records, every read is scanned.
 __global__ __launch_bounds__(256) void fin_col_add_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k, ull* bits,
                                                           uint32_t W, uint32_t n_unitigs, uint32_t color, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap) {
-    if (col_withheld(ovf_count, ovf_cap, flags)) return;
+    if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
     const uint32_t r = blockIdx.x * FIN_COL_BLK + threadIdx.x;
     uint32_t kind = 2u;
     uint64_t p_lo = 0, p_hi = 0;

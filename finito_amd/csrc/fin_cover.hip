@@ -6,7 +6,7 @@
 //
 // What is read.  Where the step left records (kernel 4, merged strands, fast path on, text mode 1 or 2), a lane per read:
 //   kind 1 -- the 32-byte record alone.  Slot sl of strand A is (u, off0 + sl) unless a disagreeing position lies in [sl, sl + k - 1]: the found strand slots are
-//             [0, nk) minus at most eight gap intervals, worked out exactly as fin_expand_records does (clamping to [0, nk - 1], a gap never starts below the end
+//             [0, nk) minus at most eight gap intervals, the gaps of fin_rec_walk.h (clamping to [0, nk - 1], a gap never starts below the end
 //             of its predecessor).  Strand-slot order ascends in `off` whichever strand A is, so the strand bit does not matter.  The lane walks the words that
 //             [g0, g0 + nk) touches and makes ONE mask per word -- the range's bits minus the gaps' -- and one OR: two or three for a 150-base read.
 //   kind 2 -- nothing.
@@ -38,6 +38,7 @@
 // Out of scope: partitioned indexes, fin_search_batch_multi, ORing across ranks (the caller ORs the downloaded bitmaps), per-position depth, the C++ mirror.
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_rec_walk.h"
 
 #define FIN_COVER_FLAT 4096u   // slots a wave scans in the flat form
 
@@ -96,19 +97,13 @@ __device__ __forceinline__ void cover_scan(const int2* pairs, uint64_t lo, uint6
         }
     }
 }
-// a step whose overflow list overran has no results (batch_overrun_check, fin_capi.cpp): nothing is set, the accumulator is flagged
-__device__ __forceinline__ bool cover_withheld(const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t* flags) {
-    if (!ovf_count || *ovf_count <= ovf_cap) return false;
-    if (blockIdx.x == 0 && threadIdx.x == 0) cover_flag(flags, 1u);
-    return true;
-}
 }  // namespace
 
 // A step that left records: a lane per read.  kind 1 -- the record's found ranges, a mask per word; kind 2 -- nothing; kind 0 -- the wave scans the read's pairs
 __global__ __launch_bounds__(256) void fin_cover_rec_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
                                                             const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len, ull* bits, uint32_t* flags,
                                                             const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t probe) {
-    if (cover_withheld(ovf_count, ovf_cap, flags)) return;
+    if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     uint32_t kind = 2u;
     uint64_t p_lo = 0, p_hi = 0;
@@ -117,32 +112,15 @@ __global__ __launch_bounds__(256) void fin_cover_rec_kernel(const FinFastRec* fr
         kind = a.z >> 16;
         if (kind == 1u && a.w != 0u) {
             const uint4 b = ((const uint4*)(frec + r))[1];
-            const uint32_t nk = a.w, nE = min(a.z & 0xFFu, 8u), k1 = k - 1u;
-            // the gaps as strand slots [glo, ghi), ascending and disjoint (fin_expand_records: stretches of absent slots may touch or overlap -- a gap
-            // never starts below `done_to`); an empty one is glo = ghi = 0
-            uint32_t glo[8], ghi[8];
-            uint32_t done_to = 0;
-#pragma unroll
-            for (uint32_t e = 0; e < 8u; e++) {
-                glo[e] = 0u; ghi[e] = 0u;
-                if (e < nE) {
-                    const uint32_t w = e < 2u ? b.x : e < 4u ? b.y : e < 6u ? b.z : b.w, E = (e & 1u) ? w >> 16 : w & 0xFFFFu;
-                    uint32_t lo = E >= k1 ? E - k1 : 0u;
-                    const uint32_t hi = E < nk ? E : nk - 1u;
-                    if (lo < done_to) lo = done_to;
-                    if (lo <= hi) { glo[e] = lo; ghi[e] = hi + 1u; }
-                    if (hi + 1u > done_to) done_to = hi + 1u;
-                }
-            }
+            const uint32_t nk = a.w;
             if (a.x >= n_unitigs) cover_flag(flags, 2u);
             else {
                 const uint64_t g0 = (uint64_t)ends_p[a.x] + a.y;
                 uint64_t g1 = g0 + nk;
                 if (g1 > total_len) { cover_flag(flags, 2u); g1 = g0 < total_len ? total_len : g0; }   // (what lies inside the text is still set)
                 for (uint64_t w = g0 >> 6; (w << 6) < g1; w++) {   // nk may reach 2^16 - 1: a loop over words, not a fixed count
-                    ull m = cover_word_mask(w << 6, g0, g1);
-#pragma unroll
-                    for (uint32_t e = 0; e < 8u; e++) m &= ~cover_word_mask(w << 6, g0 + glo[e], g0 + ghi[e]);
+                    ull m = cover_word_mask(w << 6, g0, g1);   // the range's bits, minus those of the gaps (fin_rec_walk.h; they do not depend on w)
+                    fin_rec_gaps(nk, a.z & 0xFFu, b.x, b.y, b.z, b.w, k, [&](uint32_t lo, uint32_t hi_excl) { m &= ~cover_word_mask(w << 6, g0 + lo, g0 + hi_excl); });
                     cover_or(bits, w, m, probe != 0u);
                 }
             }
@@ -153,16 +131,14 @@ __global__ __launch_bounds__(256) void fin_cover_rec_kernel(const FinFastRec* fr
     while (todo) {
         const int src = __ffsll((long long)todo) - 1;
         todo &= todo - 1ull;
-        const uint64_t lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_lo >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_lo, src);
-        const uint64_t hi = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_hi >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_hi, src);
-        cover_scan(pairs, lo, hi, ends_p, n_unitigs, total_len, bits, flags, probe != 0u);
+        cover_scan(pairs, fin_bcast64(p_lo, src), fin_bcast64(p_hi, src), ends_p, n_unitigs, total_len, bits, flags, probe != 0u);
     }
 }
 
 // A step that left no records: every slot of the pair array, FIN_COVER_FLAT consecutive slots per wave (runs then reach across reads, which a bitmap does not mind)
 __global__ __launch_bounds__(256) void fin_cover_flat_kernel(const int2* pairs, uint64_t n_pairs, const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len,
                                                              ull* bits, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t probe) {
-    if (cover_withheld(ovf_count, ovf_cap, flags)) return;
+    if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
     const uint64_t n_spans = (n_pairs + FIN_COVER_FLAT - 1u) / FIN_COVER_FLAT;
     for (uint64_t s = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); s < n_spans; s += (uint64_t)gridDim.x * 4u) {
         const uint64_t lo = s * FIN_COVER_FLAT, hi = lo + FIN_COVER_FLAT < n_pairs ? lo + FIN_COVER_FLAT : n_pairs;

@@ -9,8 +9,8 @@
 // that only a hand-made pair can name.  Arithmetic is modulo 2^32: exact while every position's true depth is below 2^32.
 //
 // What is read.  Where the step left records (kernel 4, merged strands, fast path on, text mode 1 or 2), a lane per read:
-//   kind 1 -- the 32-byte record and ends_p[u] alone: the found strand slots are [0, nk) minus at most eight gaps, worked out exactly as fin_expand_records does
-//             (clamping to [0, nk - 1], a gap never starts below the end of its predecessor) and kept as ranges as fin_cover_rec_kernel keeps them.  Strand-slot
+//   kind 1 -- the 32-byte record and ends_p[u] alone: the found strand slots are [0, nk) minus at most eight gaps: the found stretches of fin_rec_walk.h
+//             (clamping to [0, nk - 1], a gap never starts below the end of its predecessor).  Strand-slot
 //             order ascends in `off` whichever strand A is.  Two adds per stretch; in text mode 2 the read's pairs do not exist and are never touched.
 //   kind 2 -- nothing.
 //   kind 0 -- the wave scans the read's pairs through out_offs, a row of 64 slots at a time.  fin_cover's run rule (greedy, not the segment rule: depth does not
@@ -35,6 +35,7 @@
 // Out of scope: partitioned indexes, fin_search_batch_multi, sums across ranks (the caller adds the downloaded arrays), the C++ mirror, medians, saturation.
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_rec_walk.h"
 
 #define FIN_DEPTH_FLAT 4096u   // slots a wave scans in the flat form
 #define FIN_DEPTH_STAT_P 8u    // positions a lane of the statistics kernel takes
@@ -85,12 +86,6 @@ __device__ __forceinline__ void depth_scan(const int2* pairs, uint64_t lo, uint6
         }
     }
 }
-// a step whose overflow list overran has no results (batch_overrun_check, fin_capi.cpp): nothing is added, the accumulator is flagged
-__device__ __forceinline__ bool depth_withheld(const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t* flags) {
-    if (!ovf_count || *ovf_count <= ovf_cap) return false;
-    if (blockIdx.x == 0 && threadIdx.x == 0) depth_flag(flags, 1u);
-    return true;
-}
 
 // ---- the prefix sum's tiles: `tile` elements (1 .. 4096) per block of 256 threads, thread t holding elements [t * per, t * per + per) of the tile ----
 // v[j] = element t * per + j of the tile that begins at `base` (0 beyond the tile or beyond n).  A whole tile of 4096 is loaded as four 16-byte words a thread
@@ -126,7 +121,7 @@ __device__ __forceinline__ uint32_t depth_block_exclusive(uint32_t mine, uint32_
 __global__ __launch_bounds__(256) void fin_depth_rec_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
                                                             const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len, int32_t* diff, uint32_t* flags,
                                                             const uint32_t* ovf_count, uint32_t ovf_cap) {
-    if (depth_withheld(ovf_count, ovf_cap, flags)) return;
+    if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     uint32_t kind = 2u;
     uint64_t p_lo = 0, p_hi = 0;
@@ -137,29 +132,15 @@ __global__ __launch_bounds__(256) void fin_depth_rec_kernel(const FinFastRec* fr
             if (a.x >= n_unitigs) depth_flag(flags, 2u);
             else {
                 const uint4 b = ((const uint4*)(frec + r))[1];
-                const uint32_t nk = a.w, nE = min(a.z & 0xFFu, 8u), k1 = k - 1u;
+                const uint32_t nk = a.w;
                 const uint64_t g0 = (uint64_t)ends_p[a.x] + a.y;
                 uint32_t lim = nk;   // strand slots [0, lim) name places of the text
                 if (g0 + nk > total_len) { depth_flag(flags, 2u); lim = g0 < total_len ? (uint32_t)(total_len - g0) : 0u; }   // (the slots beyond it count as absent)
-                // the found stretches lie between the gaps [lo, hi] (fin_expand_records: stretches of absent slots may touch or overlap -- a gap never starts
-                // below `done_to`); `from`: where the found stretch in front of the next gap begins
-                uint32_t done_to = 0, from = 0;
-#pragma unroll
-                for (uint32_t e = 0; e < 8u; e++) {
-                    if (e < nE) {
-                        const uint32_t w = e < 2u ? b.x : e < 4u ? b.y : e < 6u ? b.z : b.w, E = (e & 1u) ? w >> 16 : w & 0xFFFFu;
-                        uint32_t lo = E >= k1 ? E - k1 : 0u;
-                        const uint32_t hi = E < nk ? E : nk - 1u;
-                        if (lo < done_to) lo = done_to;
-                        if (lo <= hi) {
-                            const uint32_t to = lo < lim ? lo : lim;
-                            if (from < to) depth_range(diff, g0 + from, g0 + to);
-                            from = hi + 1u;
-                        }
-                        if (hi + 1u > done_to) done_to = hi + 1u;
-                    }
-                }
-                if (from < lim) depth_range(diff, g0 + from, g0 + lim);
+                // the found stretches (fin_rec_walk.h), each cut off at `lim`
+                (void)sgm_rec_walk(a, b, k, [&](uint32_t, uint32_t from, uint32_t to) {
+                    if (to > lim) to = lim;
+                    if (from < to) depth_range(diff, g0 + from, g0 + to);
+                });
             }
         } else if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
     }
@@ -168,16 +149,14 @@ __global__ __launch_bounds__(256) void fin_depth_rec_kernel(const FinFastRec* fr
     while (todo) {
         const int src = __ffsll((long long)todo) - 1;
         todo &= todo - 1ull;
-        const uint64_t lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_lo >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_lo, src);
-        const uint64_t hi = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_hi >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_hi, src);
-        depth_scan(pairs, lo, hi, ends_p, n_unitigs, total_len, diff, flags);
+        depth_scan(pairs, fin_bcast64(p_lo, src), fin_bcast64(p_hi, src), ends_p, n_unitigs, total_len, diff, flags);
     }
 }
 
 // A step that left no records: every slot of the pair array, FIN_DEPTH_FLAT consecutive slots per wave (runs then reach across reads, which depth does not mind)
 __global__ __launch_bounds__(256) void fin_depth_flat_kernel(const int2* pairs, uint64_t n_pairs, const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len,
                                                              int32_t* diff, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap) {
-    if (depth_withheld(ovf_count, ovf_cap, flags)) return;
+    if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
     const uint64_t n_spans = (n_pairs + FIN_DEPTH_FLAT - 1u) / FIN_DEPTH_FLAT;
     for (uint64_t s = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); s < n_spans; s += (uint64_t)gridDim.x * 4u) {
         const uint64_t lo = s * FIN_DEPTH_FLAT, hi = lo + FIN_DEPTH_FLAT < n_pairs ? lo + FIN_DEPTH_FLAT : n_pairs;

@@ -2,8 +2,8 @@
 // (include/finito_amd.h: fin_hits, fin_batch_add_hits).
 //
 // Nothing per k-mer leaves the device and, for the reads the pair pre-pass's fast path finished, nothing per k-mer is even read: such a read is a 32-byte
-// record (FinFastRec) and its share of the profile is ONE number for ONE unitig -- nk minus the slots a disagreeing position covers, the `found += nk - gaps`
-// of fin_expand_records (fin_capi.cpp), worked out by one lane.  The other reads' pairs are scanned where the step left them: consecutive slots with the
+// record (FinFastRec) and its share of the profile is ONE number for ONE unitig -- nk minus the slots a disagreeing position covers, nk minus the summed
+// gaps of fin_rec_walk.h, worked out by one lane.  The other reads' pairs are scanned where the step left them: consecutive slots with the
 // same unitig are one run, and a run is one add.  A step that left no records (forward-only search, the other kernels, fast path off, text mode 0) is the
 // flat pair array scanned end to end; runs then reach across reads, which a count does not mind.
 //
@@ -19,6 +19,7 @@
 // Nothing here writes anything but counts[] and the accumulator's flag word; the records and the pairs are read only.
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_rec_walk.h"
 
 #define FIN_HITS_FLAT 4096u   // slots a wave scans in the flat form (64 rows: the held-back run pays off)
 
@@ -72,19 +73,13 @@ __device__ __forceinline__ void hits_flush(ull* counts, uint32_t n_unitigs, uint
     if ((threadIdx.x & 63u) == 0u && c.n) hits_add(counts, n_unitigs, flags, c.u, c.n);
     c.n = 0ull;
 }
-// a step whose overflow list overran has no results (batch_overrun_check, fin_capi.cpp): nothing is added, the accumulator is flagged
-__device__ __forceinline__ bool hits_withheld(const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t* flags) {
-    if (!ovf_count || *ovf_count <= ovf_cap) return false;
-    if (blockIdx.x == 0 && threadIdx.x == 0) (void)__hip_atomic_fetch_or(flags, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-}
 }  // namespace
 
 // A step that left records: a lane per read.  kind 1 -- the record's number, summed over the wave's lanes with the same unitig; kind 2 -- nothing;
 // kind 0 -- the wave scans the read's pairs, read by read
 __global__ __launch_bounds__(256) void fin_hits_rec_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
                                                            ull* counts, uint32_t n_unitigs, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t combine) {
-    if (hits_withheld(ovf_count, ovf_cap, flags)) return;
+    if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     uint32_t u = 0, cnt = 0, kind = 2u;
@@ -94,20 +89,9 @@ __global__ __launch_bounds__(256) void fin_hits_rec_kernel(const FinFastRec* fre
         kind = a.z >> 16;
         if (kind == 1u) {
             const uint4 b = ((const uint4*)(frec + r))[1];
-            const uint32_t nk = a.w, nE = min(a.z & 0xFFu, 8u), k1 = k - 1u;
-            uint32_t gaps = 0, done_to = 0;   // (fin_expand_records: the positions ascend, stretches of absent slots may touch or overlap)
-#pragma unroll
-            for (uint32_t e = 0; e < 8u; e++) {
-                if (e < nE && nk) {
-                    const uint32_t w = e < 2u ? b.x : e < 4u ? b.y : e < 6u ? b.z : b.w, E = (e & 1u) ? w >> 16 : w & 0xFFFFu;
-                    uint32_t lo = E >= k1 ? E - k1 : 0u;
-                    const uint32_t hi = E < nk ? E : nk - 1u;
-                    if (lo < done_to) lo = done_to;
-                    if (lo <= hi) gaps += hi - lo + 1u;
-                    if (hi + 1u > done_to) done_to = hi + 1u;
-                }
-            }
-            u = a.x; cnt = nk - gaps;
+            uint32_t gaps = 0;
+            fin_rec_gaps(a.w, a.z & 0xFFu, b.x, b.y, b.z, b.w, k, [&](uint32_t lo, uint32_t hi_excl) { gaps += hi_excl - lo; });
+            u = a.x; cnt = a.w - gaps;
         } else if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
     }
     // ---- the records' numbers ----
@@ -127,9 +111,7 @@ __global__ __launch_bounds__(256) void fin_hits_rec_kernel(const FinFastRec* fre
     while (todo) {
         const int src = __ffsll((long long)todo) - 1;
         todo &= todo - 1ull;
-        const uint64_t lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_lo >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_lo, src);
-        const uint64_t hi = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_hi >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_hi, src);
-        hits_scan(pairs, lo, hi, counts, n_unitigs, flags, combine != 0u, c);
+        hits_scan(pairs, fin_bcast64(p_lo, src), fin_bcast64(p_hi, src), counts, n_unitigs, flags, combine != 0u, c);
     }
     hits_flush(counts, n_unitigs, flags, c);
 }
@@ -137,7 +119,7 @@ __global__ __launch_bounds__(256) void fin_hits_rec_kernel(const FinFastRec* fre
 // A step that left no records: every slot of the pair array, FIN_HITS_FLAT consecutive slots per wave
 __global__ __launch_bounds__(256) void fin_hits_flat_kernel(const int2* pairs, uint64_t n_pairs, ull* counts, uint32_t n_unitigs, uint32_t* flags,
                                                             const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t combine) {
-    if (hits_withheld(ovf_count, ovf_cap, flags)) return;
+    if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
     const uint64_t n_spans = (n_pairs + FIN_HITS_FLAT - 1u) / FIN_HITS_FLAT;
     HitsCarry c = {0xFFFFFFFFu, 0ull};
     for (uint64_t s = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); s < n_spans; s += (uint64_t)gridDim.x * 4u) {

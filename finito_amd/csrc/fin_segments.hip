@@ -151,10 +151,7 @@ __global__ __launch_bounds__(256) void fin_sgm_kernel(const FinFastRec* frec, co
     while (todo) {
         const int src = __ffsll((long long)todo) - 1;
         todo &= todo - 1ull;
-        const uint64_t lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_lo >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_lo, src);
-        const uint64_t hi = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_hi >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_hi, src);
-        const uint64_t at_s = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(at >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)at, src);
-        const uint32_t c = sgm_scan<WRITE>(pairs, lo, hi, segs + at_s);
+        const uint32_t c = sgm_scan<WRITE>(pairs, fin_bcast64(p_lo, src), fin_bcast64(p_hi, src), segs + fin_bcast64(at, src));
         if (!WRITE && (int)lane == src) mine = c;
     }
     if (!WRITE) {
