@@ -24,6 +24,7 @@
 // criterion change nothing; the host enqueues groups of iterations and reads the 8 bytes between groups.
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_wave.h"
 
 #define FIN_AB_BLK 256u
 #define FIN_AB_RED_WAVES 16u
@@ -31,8 +32,6 @@
 namespace {
 typedef unsigned long long ull;
 
-__device__ __forceinline__ uint32_t ab_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-__device__ __forceinline__ ull ab_bcast64(ull v, int src) { return ((ull)ab_bcast((uint32_t)(v >> 32), src) << 32) | ab_bcast((uint32_t)v, src); }
 // the sum over lanes 0 .. width - 1 (a power of two <= 64), the same in each of them: the order is the butterfly's, whatever the values
 __device__ __forceinline__ double ab_butterfly(double v, uint32_t width) {
     for (uint32_t d = width >> 1; d >= 1u; d >>= 1) v += __shfl_xor(v, (int)d);
@@ -109,8 +108,8 @@ __global__ __launch_bounds__(256) void fin_ab_colsum_kernel(const FinAbState* st
         while (todo) {                      // the classes of this step that have a colour of word w, ascending
             const int src = __ffsll((long long)todo) - 1;
             todo &= todo - 1ull;
-            const ull m = ab_bcast64(word, src);
-            const double qv = __longlong_as_double((long long)ab_bcast64(qb, src));
+            const ull m = fin_bcast64(word, src);
+            const double qv = __longlong_as_double((long long)fin_bcast64(qb, src));
             if ((m >> lane) & 1ull) acc += qv;
         }
     }
@@ -144,8 +143,7 @@ __global__ __launch_bounds__(1024) void fin_ab_colred_kernel(const FinAbState* s
         alpha[c] = a1;
         x[c] = a1 / len[c];
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) chg = fmax(chg, __shfl_xor(chg, d));
+    chg = fin_wave_fmax(chg);
     const bool all_ok = __ballot(!ok) == 0ull;
     if (lane == 0u) { blk_ok[w] = all_ok ? 1u : 0u; blk_chg[w] = chg; }
 }
@@ -161,8 +159,7 @@ __global__ __launch_bounds__(64) void fin_ab_finish_kernel(FinAbState* st, const
     ll = ab_butterfly(ll, 64u);
     const bool ok = lane < W ? blk_ok[lane] != 0u : true;   // W <= 64
     double chg = lane < W ? blk_chg[lane] : 0.0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) chg = fmax(chg, __shfl_xor(chg, d));
+    chg = fin_wave_fmax(chg);
     const bool all_ok = __ballot(!ok) == 0ull;
     if (lane == 0u) {
         trace[t] = ll;

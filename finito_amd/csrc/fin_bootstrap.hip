@@ -22,6 +22,7 @@
 #include "fin_bootrng.h"
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_wave.h"
 
 #define FIN_BOOT_BLK 256u
 #define FIN_BOOT_MAX_GRID (1u << 20)   // blocks of a resample launch: gridDim.x * blockDim.x stays below 2^32
@@ -69,8 +70,7 @@ __global__ __launch_bounds__(256) void fin_boot_resample_kernel(const ull* h, co
             const uint32_t k = lane + 64u * m;
             if (k < here) sum += fin_boot_block_sum(hj, i0 + k, n, b, seed);
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d);
+        sum = fin_wave_sum(sum);
         wave_tot += sum;
         if (lane == 0u) {
             if (n <= FIN_BOOT_SLAB) counts[j] = (ull)sum;

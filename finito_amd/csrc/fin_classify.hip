@@ -7,16 +7,14 @@
 // among the other labels, n_labelled = the sum of c}, or {FIN_NO_LABEL, 0, 0, 0} when nothing was counted.  All four are the same when the slot order is
 // reversed, so a record found on the reverse strand (meta bit 8) needs no special case.
 //
-// What is read (as fin_rsm_kernel).  Where the step left records, a lane per read:
-//   kind 1 -- the 32-byte record and one label: the record lies in ONE unitig, the class is {labels[u], n, 0, n} with n = the sum of the stretches of
-//             sgm_rec_walk.  The read's pairs are never touched -- in text mode 2 they do not exist.
+// What is read (the frame is fin_wave.h's).  Where the step left records, a lane per read:
+//   kind 1 -- the record and one label: the record lies in ONE unitig, the class is {labels[u], n, 0, n} with n = the sum of the stretches of sgm_rec_walk.
 //   kind 2 -- the empty class.
-//   kind 0 -- the wave scans the read's pairs through out_offs, a row of 64 slots at a time, the next row's load issued ahead.  Every found lane gathers its
-//             unitig's label (u repeats along a segment: mostly one cache line); a loop over the row's DISTINCT labels (readlane of the first lane left, a
-//             ballot of the lanes that hold the same label, a popcount) turns the row into (label, count) items, typically one or two.  The items go into a
+//   kind 0 -- the wave scans the read's pairs, a row of 64 slots at a time, the next row loaded ahead.  Every found lane gathers its
+//             unitig's label (u repeats along a segment: mostly one cache line); a loop over the row's DISTINCT labels (readlane of the first lane left, a ballot of the lanes with it, a popcount)
+//             turns the row into (label, count) items, typically one or two.  The items go into a
 //             table the wave keeps in its registers, entry i in lane i: a ballot finds the entry of a label, else lane n_ent takes the item.  At the read's end
 //             two wave reductions give the class: the maximum of (count << 32) | ~label, then the largest count among the other entries.
-// Where the step left no records (frec null) every read is scanned as a kind-0 read.
 //
 // More than 64 distinct labels in one read: the read is scanned again, in label-ordered passes, and stays exact.  A pass admits the labels in [floor, ceil):
 // floor is where the pass before stopped (0 at first), ceil starts unbounded.  When the table is full and a new label arrives, the larger of it and the table's
@@ -31,29 +29,13 @@
 // distinct slot per wave (the same distinct-value loop): ten labels and millions of reads would otherwise queue on ten addresses.
 #include "fin_device.h"
 #include "fin_kernels.h"
-#include "fin_rec_walk.h"
+#include "fin_wave.h"
 
 #define FIN_CLS_BLK 256u        // reads per block: a lane per read
 #define FIN_CLS_NONE 0xFFFFFFFFu   // FIN_NO_LABEL
 
 namespace {
 typedef unsigned long long ull;
-
-__device__ __forceinline__ uint32_t cls_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-__device__ __forceinline__ uint64_t cls_bcast64(uint64_t v, int src) { return ((uint64_t)cls_bcast((uint32_t)(v >> 32), src) << 32) | cls_bcast((uint32_t)v, src); }
-__device__ __forceinline__ uint32_t cls_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
-__device__ __forceinline__ ull cls_wave_max64(ull v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const ull o = ((ull)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 // slots [lo, hi) of the pair array are one read's: its class {label, n_best, n_second, n_labelled}, the whole wave, a row of 64 slots at a time.
 // Wave-converged; every lane returns the same value.  A unitig number at or above n_unitigs (the absent slot's 0xFFFFFFFF is one) has no label
@@ -66,21 +48,15 @@ __device__ __forceinline__ uint4 cls_scan(const int2* pairs, uint64_t lo, uint64
         uint32_t ceil = FIN_CLS_NONE;
         uint32_t n_ent = 0;                 // the table: entry i < n_ent in lane i
         uint32_t t_lab = FIN_CLS_NONE, t_cnt = 0;
-        int2 pn = make_int2(-1, -1);        // the row to come, loaded a row ahead
-        if (lo + lane < hi) pn = pairs[lo + lane];
-        for (uint64_t base = lo; base < hi; base += 64u) {
-            const uint64_t j = base + lane;
-            const int2 p = pn;              // (-1,-1) in a lane beyond the read's end
-            pn = make_int2(-1, -1);
-            if (j + 64u < hi) pn = pairs[j + 64u];
-            const uint32_t u = (uint32_t)p.x;
+        fin_each_pair_row(pairs, lo, hi, [&](uint64_t, uint64_t, int2 p) {
+            const uint32_t u = (uint32_t)p.x;   // ((-1,-1) in a lane beyond the read's end)
             uint32_t L = FIN_CLS_NONE;
             if (u < n_unitigs) L = labels[u];
             if (floor == 0u) n_labelled += (uint32_t)__popcll(__ballot(L != FIN_CLS_NONE));   // (the first pass sees every slot)
             ull rem = __ballot(L >= floor && L < ceil);
-            while (rem) {                   // the row's distinct admitted labels, one item each
+            while (rem) {                   // the row's distinct admitted labels, one item each (its own text, not fin_each_distinct: profiles/r28/wave_frame.md)
                 const int src = __ffsll((long long)rem) - 1;
-                const uint32_t Lc = cls_bcast(L, src);
+                const uint32_t Lc = fin_bcast(L, src);
                 const ull m = __ballot(L == Lc);
                 const uint32_t c = (uint32_t)__popcll(m);
                 rem &= ~m;
@@ -91,18 +67,18 @@ __device__ __forceinline__ uint4 cls_scan(const int2* pairs, uint64_t lo, uint64
                     if (lane == n_ent) { t_lab = Lc; t_cnt = c; }
                     n_ent++;
                 } else {                    // full: the larger of Lc and the table's largest label waits for a later pass
-                    const uint32_t M = (uint32_t)__builtin_amdgcn_readfirstlane((int)cls_wave_max(t_lab));   // (every lane holds it: kept wave-uniform for ceil)
+                    const uint32_t M = (uint32_t)__builtin_amdgcn_readfirstlane((int)fin_wave_max(t_lab));   // (every lane holds it: kept wave-uniform for ceil)
                     if (Lc < M) {
                         if (t_lab == M) { t_lab = Lc; t_cnt = c; }
                         ceil = M;
                     } else ceil = Lc;
                 }
             }
-        }
+        });
         // fold the table into the running class: its best entry, the largest count among its others, and the loser of the two bests
         const bool live = lane < n_ent;
-        const ull k1 = cls_wave_max64(live ? ((ull)t_cnt << 32) | (uint32_t)~t_lab : 0ull);
-        const uint32_t s1 = cls_wave_max(live && t_lab != (uint32_t)~(uint32_t)k1 ? t_cnt : 0u);
+        const ull k1 = fin_wave_max64(live ? ((ull)t_cnt << 32) | (uint32_t)~t_lab : 0ull);
+        const uint32_t s1 = fin_wave_max(live && t_lab != (uint32_t)~(uint32_t)k1 ? t_cnt : 0u);
         const ull loser = k1 > best ? best : k1;
         if (k1 > best) best = k1;
         n_second = max(n_second, max(s1, (uint32_t)(loser >> 32)));
@@ -118,33 +94,18 @@ __device__ __forceinline__ uint4 cls_scan(const int2* pairs, uint64_t lo, uint64
 __global__ __launch_bounds__(256) void fin_cls_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
                                                       const uint32_t* labels, uint32_t n_unitigs, uint4* cls) {
     const uint32_t r = blockIdx.x * FIN_CLS_BLK + threadIdx.x, lane = threadIdx.x & 63u;
-    uint32_t kind = 2u;
-    uint64_t p_lo = 0, p_hi = 0;
-    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
-    if (r < n_reads) {
-        kind = 0u;
-        if (frec) {
-            a = ((const uint4*)(frec + r))[0];   // u, off0, meta, nk
-            kind = a.z >> 16;
-            if (kind == 1u) b = ((const uint4*)(frec + r))[1];
-        }
-        if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
-    }
+    const FinReadItem it = fin_read_item<true>(frec, out_offs, r, n_reads);
     uint4 mine = make_uint4(FIN_CLS_NONE, 0u, 0u, 0u);
-    if (kind == 1u && a.w != 0u) {
+    if (it.kind == 1u && it.a.w != 0u) {
         uint32_t L = FIN_CLS_NONE, n = 0;
-        if (a.x < n_unitigs) L = labels[a.x];
-        (void)sgm_rec_walk(a, b, k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
+        if (it.a.x < n_unitigs) L = labels[it.a.x];
+        (void)sgm_rec_walk(it.a, it.b, k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
         if (L != FIN_CLS_NONE && n != 0u) mine = make_uint4(L, n, 0u, n);
     }
-    // ---- the searched reads' pairs: the wave takes its lanes' reads one after the other ----
-    ull todo = __ballot(kind == 0u && p_hi > p_lo);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
-        const uint4 s = cls_scan(pairs, cls_bcast64(p_lo, src), cls_bcast64(p_hi, src), labels, n_unitigs);
+    fin_each_searched_read(it, [&](int src, uint64_t lo, uint64_t hi) {
+        const uint4 s = cls_scan(pairs, lo, hi, labels, n_unitigs);
         if ((int)lane == src) mine = s;
-    }
+    });
     if (r < n_reads) cls[r] = mine;
 }
 
@@ -153,21 +114,16 @@ __global__ __launch_bounds__(256) void fin_cls_tally_kernel(const uint4* cls, co
                                                             uint32_t min_permille, uint32_t min_margin, ull* reads) {
     const uint32_t r = blockIdx.x * FIN_CLS_BLK + threadIdx.x, lane = threadIdx.x & 63u;
     const bool active = r < n_reads;
-    uint32_t slot = n_labels;
+    uint32_t slot = 0xFFFFFFFFu;            // a lane beyond n_reads: no slot of the tally (n_labels is at most 2^31)
     if (active) {
         const uint4 c = cls[r];
         const uint64_t nb = c.y, nk = out_offs[r + 1] - out_offs[r];
         const bool ok = nb >= (uint64_t)max(min_found, 1u) && 1000ull * nb >= (uint64_t)min_permille * nk && nb >= (uint64_t)c.z + (uint64_t)min_margin;
-        if (ok && c.x < n_labels) slot = c.x;
+        slot = ok && c.x < n_labels ? c.x : n_labels;
     }
-    ull rem = __ballot(active);
-    while (rem) {
-        const int src = __ffsll((long long)rem) - 1;
-        const uint32_t S = cls_bcast(slot, src);
-        const ull m = __ballot(active && slot == S);
-        rem &= ~m;
+    fin_each_distinct(slot, active, [&](int src, uint32_t S, ull m) {
         if ((int)lane == src) atomicAdd(reads + S, (ull)__popcll(m));
-    }
+    });
 }
 
 extern "C" int fin_launch_classify(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const uint32_t* labels,

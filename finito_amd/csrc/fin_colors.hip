@@ -5,13 +5,10 @@
 // The matrix: uint64 bits[n_unitigs][W], W = ceil(n_colors / 64) <= 64; colour c of unitig u is bit c & 63 of bits[u * W + (c >> 6)]; bits at or above n_colors
 // are 0.  Behind the matrix lies one flag word (bit 0: a step whose overflow list overran was offered to fin_batch_add_colors -- nothing of it is set).
 //
-// fin_col_add_kernel: every unitig in which the run found at least one k-mer gets bit `color`.  A lane per read:
-//   kind 1 -- the record lies in one unitig; if sgm_rec_walk gives a found slot, one plain load of the word and, if the bit is clear, one 64-bit atomic OR.  The
-//             read's pairs are never touched -- in text mode 2 they do not exist.
-//   kind 2 -- nothing.
-//   kind 0 -- (and every read where the step left no records) the wave scans the read's pairs through out_offs, a row of 64 slots at a time, the next row loaded
-//             ahead; a loop over the row's DISTINCT unitigs (readlane of the first lane left, a ballot of the lanes with the same unitig); that first lane does
-//             the load-then-OR.
+// fin_col_add_kernel: every unitig in which the run found at least one k-mer gets bit `color`.  A lane per read (the frame is fin_wave.h's):
+//   kind 1 -- the record lies in one unitig; if sgm_rec_walk gives a found slot, one plain load of the word and, if the bit is clear, one 64-bit atomic OR.
+//   kind 0 -- the wave scans the read's pairs, a row of 64 slots at a time, the next row loaded ahead; a loop over the row's DISTINCT unitigs
+//             (fin_each_distinct); the first lane of each does the load-then-OR.
 // Between two resets bits are only ever set: whatever the plain load returns is a subset of the truth, a stale view costs a redundant OR, never a lost one.  OR is
 // idempotent: adding a run twice changes nothing.  A unitig number at or above n_unitigs (the absent slot's 0xFFFFFFFF is one) is skipped.
 //
@@ -21,7 +18,8 @@
 //   kind 1 -- n found slots in unitig u: every cnt is n, so the row is bits[u] itself (n > 0), head {n, row non-empty ? n : 0, popcount, 0}.  The copies are
 //             wave-cooperative: a ballot of the lanes whose row is a copy (or zero: kind 2, reads without pairs), then for each the wave moves the row, lane i
 //             word i -- coalesced loads and stores.  W = 1: a lane moves its own read's word, which is coalesced as it is.
-//   kind 0 -- the wave scans the read's pairs once, by rows, with the distinct-unitig loop, and keeps a table (unitig, count) in its registers, entry i in lane i.
+//   kind 0 -- the wave scans the read's pairs once, by rows, with the distinct-unitig loop, and keeps a table (unitig, count) in its registers, entry i in lane i
+//             (FinUnitigTable).
 //             At the read's end n_coloured = the counts of the entries with a non-empty row; then for each word w lane e gathers bits[u_e * W + w], a wave-uniform
 //             loop over the entries broadcasts entry e's word and count, lane b adds the count if bit b is set: lane b holds cnt[64 w + b], and the output word is
 //             ONE BALLOT of the threshold test, stored by one lane.
@@ -32,20 +30,12 @@
 // absent.
 #include "fin_device.h"
 #include "fin_kernels.h"
-#include "fin_rec_walk.h"
+#include "fin_wave.h"
 
 #define FIN_COL_BLK 256u   // reads per block: a lane per read
 
 namespace {
 typedef unsigned long long ull;
-
-__device__ __forceinline__ uint32_t col_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-__device__ __forceinline__ uint64_t col_bcast64(uint64_t v, int src) { return ((uint64_t)col_bcast((uint32_t)(v >> 32), src) << 32) | col_bcast((uint32_t)v, src); }
-__device__ __forceinline__ uint32_t col_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
 
 // bits[w] |= m: one plain load, the atomic only where the bit is clear.  The caller has checked that w is a word of the matrix
 __device__ __forceinline__ void col_or(ull* bits, uint64_t w, ull m) {
@@ -56,109 +46,33 @@ __device__ __forceinline__ void col_or(ull* bits, uint64_t w, ull m) {
 // slots [lo, hi) of the pair array are one read's: bit `color` for every distinct unitig.  Wave-converged
 __device__ __forceinline__ void col_add_scan(const int2* pairs, uint64_t lo, uint64_t hi, ull* bits, uint32_t W, uint32_t n_unitigs, uint32_t color) {
     const uint32_t lane = threadIdx.x & 63u;
-    int2 pn = make_int2(-1, -1);            // the row to come, loaded a row ahead
-    if (lo + lane < hi) pn = pairs[lo + lane];
-    for (uint64_t base = lo; base < hi; base += 64u) {
-        const uint64_t j = base + lane;
-        const int2 p = pn;                  // (-1,-1) in a lane beyond the read's end
-        pn = make_int2(-1, -1);
-        if (j + 64u < hi) pn = pairs[j + 64u];
+    fin_each_pair_row(pairs, lo, hi, [&](uint64_t, uint64_t, int2 p) {
         const uint32_t u = (uint32_t)p.x;
-        ull rem = __ballot(u < n_unitigs);
-        while (rem) {
-            const int src = __ffsll((long long)rem) - 1;
-            const uint32_t uc = col_bcast(u, src);
-            rem &= ~__ballot(u == uc);
+        fin_each_distinct(u, u < n_unitigs, [&](int src, uint32_t uc, ull) {
             if ((int)lane == src) col_or(bits, (uint64_t)uc * W + (color >> 6), 1ull << (color & 63u));
-        }
-    }
+        });
+    });
 }
 
 // slots [lo, hi) are one read's: its row into out[0 .. W), its head {n_found, n_coloured, popcount of the row} returned in every lane.  Wave-converged
 __device__ __forceinline__ uint4 col_pseudo_scan(const int2* pairs, uint64_t lo, uint64_t hi, const ull* bits, uint32_t W, uint32_t n_unitigs, uint32_t permille,
                                                  ull* out) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t n_found = 0, n_ent = 0;        // the table: entry i < n_ent in lane i
-    uint32_t t_u = 0, t_cnt = 0;
-    bool over = false;                      // more than 64 distinct unitigs: the table is dropped
-    {
-        int2 pn = make_int2(-1, -1);
-        if (lo + lane < hi) pn = pairs[lo + lane];
-        for (uint64_t base = lo; base < hi; base += 64u) {
-            const uint64_t j = base + lane;
-            const int2 p = pn;
-            pn = make_int2(-1, -1);
-            if (j + 64u < hi) pn = pairs[j + 64u];
-            const uint32_t u = (uint32_t)p.x;
-            ull rem = __ballot(u < n_unitigs);
-            n_found += (uint32_t)__popcll(rem);
-            while (rem && !over) {          // the row's distinct unitigs, one item each
-                const int src = __ffsll((long long)rem) - 1;
-                const uint32_t uc = col_bcast(u, src);
-                const ull m = __ballot(u == uc);
-                rem &= ~m;
-                const bool mine = lane < n_ent && t_u == uc;
-                if (__ballot(mine)) { if (mine) t_cnt += (uint32_t)__popcll(m); }
-                else if (n_ent < 64u) {
-                    if (lane == n_ent) { t_u = uc; t_cnt = (uint32_t)__popcll(m); }
-                    n_ent++;
-                } else over = true;
-            }
-        }
-    }
+    uint32_t n_found = 0;
+    FinUnitigTable tab;
+    fin_each_pair_row(pairs, lo, hi, [&](uint64_t, uint64_t, int2 p) {
+        const uint32_t u = (uint32_t)p.x;
+        n_found += (uint32_t)__popcll(__ballot(u < n_unitigs));
+        fin_each_distinct(u, u < n_unitigs, [&](int, uint32_t uc, ull m) { (void)tab.add(uc, (uint32_t)__popcll(m)); });
+    });
     uint32_t n_colored = 0, pc = 0;
-    if (!over) {
-        const bool live = lane < n_ent;
-        const ull* row = bits + (uint64_t)t_u * W;   // (t_u = 0 in a lane without an entry: never read)
-        bool ne = false;
-        for (uint32_t w = 0; w < W; w++) if (live && row[w] != 0ull) ne = true;
-        n_colored = col_wave_sum(live && ne ? t_cnt : 0u);
+    if (!tab.over) {
+        n_colored = fin_wave_sum(tab.colored(bits, W) ? tab.t_cnt : 0u);
         const uint64_t need = (uint64_t)permille * n_colored;
-        for (uint32_t w = 0; w < W; w++) {
-            const ull word = live ? row[w] : 0ull;
-            uint32_t cnt = 0;
-            for (uint32_t e = 0; e < n_ent; e++) {   // wave-uniform
-                const ull we = col_bcast64(word, (int)e);
-                const uint32_t ce = col_bcast(t_cnt, (int)e);
-                if ((we >> lane) & 1ull) cnt += ce;
-            }
-            const ull o = __ballot(cnt >= 1u && 1000ull * cnt >= need);
-            if (lane == 0u) out[w] = o;
-            pc += (uint32_t)__popcll(o);
-        }
+        for (uint32_t w = 0; w < W; w++) pc += fin_row_word(tab.word_counts(bits, W, w), need, true, out, w);
     } else {
-        // n_coloured: a lane per slot looks at its unitig's row
-        for (uint64_t base = lo; base < hi; base += 64u) {
-            const uint64_t j = base + lane;
-            uint32_t u = 0xFFFFFFFFu;
-            if (j < hi) u = (uint32_t)pairs[j].x;
-            bool ne = false;
-            if (u < n_unitigs) for (uint32_t w = 0; w < W; w++) if (bits[(uint64_t)u * W + w] != 0ull) ne = true;
-            n_colored += (uint32_t)__popcll(__ballot(ne));
-        }
+        n_colored = fin_rescan_colored(pairs, lo, hi, bits, W, n_unitigs);
         const uint64_t need = (uint64_t)permille * n_colored;
-        for (uint32_t w = 0; w < W; w++) {
-            uint32_t cnt = 0;
-            for (uint64_t base = lo; base < hi; base += 64u) {
-                const uint64_t j = base + lane;
-                uint32_t u = 0xFFFFFFFFu;
-                if (j < hi) u = (uint32_t)pairs[j].x;
-                ull word = 0ull;
-                if (u < n_unitigs) word = bits[(uint64_t)u * W + w];
-                ull rem = __ballot(u < n_unitigs);
-                while (rem) {
-                    const int src = __ffsll((long long)rem) - 1;
-                    const uint32_t uc = col_bcast(u, src);
-                    const ull m = __ballot(u == uc);
-                    rem &= ~m;
-                    const ull we = col_bcast64(word, src);
-                    if ((we >> lane) & 1ull) cnt += (uint32_t)__popcll(m);
-                }
-            }
-            const ull o = __ballot(cnt >= 1u && 1000ull * cnt >= need);
-            if (lane == 0u) out[w] = o;
-            pc += (uint32_t)__popcll(o);
-        }
+        for (uint32_t w = 0; w < W; w++) pc += fin_row_word(fin_rescan_word(pairs, lo, hi, bits, W, n_unitigs, w), need, true, out, w);
     }
     return make_uint4(n_found, n_colored, pc, 0u);
 }
@@ -169,30 +83,13 @@ __device__ __forceinline__ uint4 col_pseudo_scan(const int2* pairs, uint64_t lo,
 __global__ __launch_bounds__(256) void fin_col_add_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k, ull* bits,
                                                           uint32_t W, uint32_t n_unitigs, uint32_t color, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap) {
     if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
-    const uint32_t r = blockIdx.x * FIN_COL_BLK + threadIdx.x;
-    uint32_t kind = 2u;
-    uint64_t p_lo = 0, p_hi = 0;
-    if (r < n_reads) {
-        kind = 0u;
-        if (frec) {
-            const uint4 a = ((const uint4*)(frec + r))[0];   // u, off0, meta, nk
-            kind = a.z >> 16;
-            if (kind == 1u && a.w != 0u && a.x < n_unitigs) {
-                const uint4 b = ((const uint4*)(frec + r))[1];
-                uint32_t n = 0;
-                (void)sgm_rec_walk(a, b, k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
-                if (n != 0u) col_or(bits, (uint64_t)a.x * W + (color >> 6), 1ull << (color & 63u));
-            }
-        }
-        if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
+    const FinReadItem it = fin_read_item<false>(frec, out_offs, blockIdx.x * FIN_COL_BLK + threadIdx.x, n_reads);
+    if (it.kind == 1u && it.a.w != 0u && it.a.x < n_unitigs) {
+        uint32_t n = 0;
+        (void)sgm_rec_walk(it.a, it.load_b(), k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
+        if (n != 0u) col_or(bits, (uint64_t)it.a.x * W + (color >> 6), 1ull << (color & 63u));
     }
-    // ---- the searched reads' pairs: the wave takes its lanes' reads one after the other ----
-    ull todo = __ballot(kind == 0u && p_hi > p_lo);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
-        col_add_scan(pairs, col_bcast64(p_lo, src), col_bcast64(p_hi, src), bits, W, n_unitigs, color);
-    }
+    fin_each_searched_read(it, [&](int, uint64_t lo, uint64_t hi) { col_add_scan(pairs, lo, hi, bits, W, n_unitigs, color); });
 }
 
 // rows[r][0 .. W) = read r's colour row, heads[r] = {n_found, n_coloured, popcount, 0}.  frec null: the step left no records, every read is scanned.
@@ -200,23 +97,13 @@ __global__ __launch_bounds__(256) void fin_col_pseudo_kernel(const FinFastRec* f
                                                              const ull* bits, uint32_t W, uint32_t n_unitigs, uint32_t permille, ull* rows, uint4* heads) {
     const uint32_t r = blockIdx.x * FIN_COL_BLK + threadIdx.x, lane = threadIdx.x & 63u;
     const uint32_t r0 = r - lane;           // the wave's first read
-    uint32_t kind = 2u;
-    uint64_t p_lo = 0, p_hi = 0;
+    const FinReadItem it = fin_read_item<false>(frec, out_offs, r, n_reads);
     uint32_t u = 0, n = 0;                  // a kind-1 read's unitig and found slots
-    if (r < n_reads) {
-        kind = 0u;
-        if (frec) {
-            const uint4 a = ((const uint4*)(frec + r))[0];   // u, off0, meta, nk
-            kind = a.z >> 16;
-            if (kind == 1u && a.w != 0u && a.x < n_unitigs) {
-                const uint4 b = ((const uint4*)(frec + r))[1];
-                (void)sgm_rec_walk(a, b, k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
-                u = a.x;
-            }
-        }
-        if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
+    if (it.kind == 1u && it.a.w != 0u && it.a.x < n_unitigs) {
+        (void)sgm_rec_walk(it.a, it.load_b(), k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
+        u = it.a.x;
     }
-    const bool scanned = kind == 0u && p_hi > p_lo;
+    const bool scanned = it.scanned();
     uint4 mine = make_uint4(0u, 0u, 0u, 0u);
     // ---- the rows that are a copy of one unitig's row, or zero ----
     if (W == 1u) {
@@ -226,28 +113,21 @@ __global__ __launch_bounds__(256) void fin_col_pseudo_kernel(const FinFastRec* f
             mine = make_uint4(n, word ? n : 0u, (uint32_t)__popcll(word), 0u);
         }
     } else {
-        ull copy = __ballot(r < n_reads && !scanned);
-        while (copy) {
-            const int src = __ffsll((long long)copy) - 1;
-            copy &= copy - 1ull;
-            const uint32_t us = col_bcast(u, src), ns = col_bcast(n, src);
+        fin_each_lane(r < n_reads && !scanned, [&](int src) {
+            const uint32_t us = fin_bcast(u, src), ns = fin_bcast(n, src);
             ull word = 0ull;
             if (lane < W) {
                 if (ns != 0u) word = bits[(uint64_t)us * W + lane];
                 rows[(uint64_t)(r0 + (uint32_t)src) * W + lane] = word;
             }
-            const uint32_t pc = col_wave_sum((uint32_t)__popcll(word));
+            const uint32_t pc = fin_wave_sum((uint32_t)__popcll(word));
             if ((int)lane == src) mine = make_uint4(n, pc ? n : 0u, pc, 0u);
-        }
+        });
     }
-    // ---- the searched reads' pairs: the wave takes its lanes' reads one after the other ----
-    ull todo = __ballot(scanned);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
-        const uint4 s = col_pseudo_scan(pairs, col_bcast64(p_lo, src), col_bcast64(p_hi, src), bits, W, n_unitigs, permille, rows + (uint64_t)(r0 + (uint32_t)src) * W);
+    fin_each_searched_read(it, [&](int src, uint64_t lo, uint64_t hi) {
+        const uint4 s = col_pseudo_scan(pairs, lo, hi, bits, W, n_unitigs, permille, rows + (uint64_t)(r0 + (uint32_t)src) * W);
         if ((int)lane == src) mine = s;
-    }
+    });
     if (r < n_reads) heads[r] = mine;
 }
 

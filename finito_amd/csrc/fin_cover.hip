@@ -4,18 +4,16 @@
 //
 // Position g is bit g & 63 of uint64 word g >> 6; the bitmap has (total_len + 63) / 64 words -- the geometry of safe[].  start(u) = ends_p[u].
 //
-// What is read.  Where the step left records (kernel 4, merged strands, fast path on, text mode 1 or 2), a lane per read:
-//   kind 1 -- the 32-byte record alone.  Slot sl of strand A is (u, off0 + sl) unless a disagreeing position lies in [sl, sl + k - 1]: the found strand slots are
-//             [0, nk) minus at most eight gap intervals, the gaps of fin_rec_walk.h (clamping to [0, nk - 1], a gap never starts below the end
-//             of its predecessor).  Strand-slot order ascends in `off` whichever strand A is, so the strand bit does not matter.  The lane walks the words that
-//             [g0, g0 + nk) touches and makes ONE mask per word -- the range's bits minus the gaps' -- and one OR: two or three for a 150-base read.
-//   kind 2 -- nothing.
-//   kind 0 -- the wave scans the read's pairs through out_offs, a row of 64 slots at a time.  Neighbouring lanes are compared: a lane is a run head unless its
+// What is read (the frame is fin_wave.h's).  Where the step left records, a lane per read:
+//   kind 1 -- slot sl of strand A is (u, off0 + sl) unless a gap of fin_rec_walk.h covers it.  Strand-slot order ascends in `off` whichever strand A is, so the
+//             strand bit does not matter.  The lane walks the words that [g0, g0 + nk) touches and makes ONE mask per word -- the range's bits minus the gaps' --
+//             and one OR: two or three for a 150-base read.
+//   kind 0 -- the wave scans the read's pairs, a row of 64 slots at a time.  Neighbouring lanes are compared: a lane is a run head unless its
 //             (u, off) continues the lane before it by one step in the run's direction.  Offsets ASCEND by one per slot for a read found on its forward strand
 //             and DESCEND by one for a read found on its reverse strand (output slot i is strand slot nk - 1 - i): both merge.  A ballot gives each head its
 //             run's length; only the head looks up start(u), and it issues one OR per (run, word) -- a run of at most 64 slots touches at most two words.
 //             Absent slots set nothing.
-// Where the step left no records (forward-only search, kernels 0 / 2 / 3, fast path off, k > 63, text mode 0) the flat pair array is scanned the same way.
+// Where the step left no records the flat pair array is scanned the same way.
 //
 // ORs are 64-bit __hip_atomic_fetch_or, relaxed, agent scope, result unused.  OR is idempotent and commutative: the bitmap is exact whatever order the lanes
 // arrive in, and the same run added twice changes nothing.
@@ -38,7 +36,7 @@
 // Out of scope: partitioned indexes, fin_search_batch_multi, ORing across ranks (the caller ORs the downloaded bitmaps), per-position depth, the C++ mirror.
 #include "fin_device.h"
 #include "fin_kernels.h"
-#include "fin_rec_walk.h"
+#include "fin_wave.h"
 
 #define FIN_COVER_FLAT 4096u   // slots a wave scans in the flat form
 
@@ -99,11 +97,12 @@ __device__ __forceinline__ void cover_scan(const int2* pairs, uint64_t lo, uint6
 }
 }  // namespace
 
-// A step that left records: a lane per read.  kind 1 -- the record's found ranges, a mask per word; kind 2 -- nothing; kind 0 -- the wave scans the read's pairs
+// A step that left records: a lane per read.  kind 1 -- the record's found ranges, a mask per word; kind 0 -- the wave scans the read's pairs
 __global__ __launch_bounds__(256) void fin_cover_rec_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
                                                             const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len, ull* bits, uint32_t* flags,
                                                             const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t probe) {
     if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
+    // the opening in this kernel's own text, not fin_read_item: a searched read's slot range is loaded BEHIND the record walk (profiles/r28/wave_frame.md, section 3)
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     uint32_t kind = 2u;
     uint64_t p_lo = 0, p_hi = 0;
@@ -126,13 +125,9 @@ __global__ __launch_bounds__(256) void fin_cover_rec_kernel(const FinFastRec* fr
             }
         } else if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
     }
-    // ---- the searched reads' pairs ----
-    ull todo = __ballot(kind == 0u && p_hi > p_lo);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
+    fin_each_lane(kind == 0u && p_hi > p_lo, [&](int src) {
         cover_scan(pairs, fin_bcast64(p_lo, src), fin_bcast64(p_hi, src), ends_p, n_unitigs, total_len, bits, flags, probe != 0u);
-    }
+    });
 }
 
 // A step that left no records: every slot of the pair array, FIN_COVER_FLAT consecutive slots per wave (runs then reach across reads, which a bitmap does not mind)
@@ -165,9 +160,7 @@ __global__ __launch_bounds__(256) void fin_cover_count_kernel(const ull* bits, u
     // one unitig for the whole wave: one add
     const uint32_t u0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)u);
     if (__ballot(act && !(inside && u == u0)) == 0ull) {
-        uint32_t c = (uint32_t)__popcll(x);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
+        const uint32_t c = fin_wave_sum((uint32_t)__popcll(x));
         if ((threadIdx.x & 63u) == 0u && c) (void)__hip_atomic_fetch_add(covered + u0, (ull)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }

@@ -8,12 +8,10 @@
 // (fin_depth_download).  The -1 lands inside the same unitig: its last k - 1 positions begin no k-mer; entry total_len is there for a place in the last of them
 // that only a hand-made pair can name.  Arithmetic is modulo 2^32: exact while every position's true depth is below 2^32.
 //
-// What is read.  Where the step left records (kernel 4, merged strands, fast path on, text mode 1 or 2), a lane per read:
-//   kind 1 -- the 32-byte record and ends_p[u] alone: the found strand slots are [0, nk) minus at most eight gaps: the found stretches of fin_rec_walk.h
-//             (clamping to [0, nk - 1], a gap never starts below the end of its predecessor).  Strand-slot
-//             order ascends in `off` whichever strand A is.  Two adds per stretch; in text mode 2 the read's pairs do not exist and are never touched.
-//   kind 2 -- nothing.
-//   kind 0 -- the wave scans the read's pairs through out_offs, a row of 64 slots at a time.  fin_cover's run rule (greedy, not the segment rule: depth does not
+// What is read (the frame is fin_wave.h's).  Where the step left records, a lane per read:
+//   kind 1 -- the record and ends_p[u] alone: the found stretches of fin_rec_walk.h.  Strand-slot order ascends in `off` whichever strand A is.  Two adds per
+//             stretch.
+//   kind 0 -- the wave scans the read's pairs, a row of 64 slots at a time.  fin_cover's run rule (greedy, not the segment rule: depth does not
 //             care where a run is cut): a lane is a run head unless its (u, off) continues the lane before it by one step in the run's direction, ascending or
 //             descending.  A ballot gives each head its run's length and the head issues the two adds.  A repeated identical pair is two runs and both count.  A
 //             run that continues into the next row is cut at the boundary.
@@ -29,13 +27,13 @@
 // list overran was offered -- nothing of it is added).  The add kernels read the step's overflow counter themselves: no host synchronisation.
 //
 // The download path: the prefix sum over a CHUNK of the difference array into a staging buffer of depths, in three passes -- tile sums, one block scanning the
-// tile sums behind the carry of the chunks before (fin_rec_scan_kernel's pattern), apply -- and a statistics kernel over the staged depths.  No block waits for
+// tile sums behind the carry of the chunks before (fin_blk_scan_kernel's pattern), apply -- and a statistics kernel over the staged depths.  No block waits for
 // another.  The difference array is only read: the accumulator stays additive across downloads.  Element indices are uint64.
 //
 // Out of scope: partitioned indexes, fin_search_batch_multi, sums across ranks (the caller adds the downloaded arrays), the C++ mirror, medians, saturation.
 #include "fin_device.h"
 #include "fin_kernels.h"
-#include "fin_rec_walk.h"
+#include "fin_wave.h"
 
 #define FIN_DEPTH_FLAT 4096u   // slots a wave scans in the flat form
 #define FIN_DEPTH_STAT_P 8u    // positions a lane of the statistics kernel takes
@@ -102,55 +100,31 @@ __device__ __forceinline__ void depth_tile_load(const uint32_t* x, uint64_t base
         v[j] = (j < per && i < tile && base + i < n) ? x[base + i] : 0u;
     }
 }
-// sum of v over the block's 256 threads' predecessors (exclusive), and -- in *total, if not null -- over all of them
-__device__ __forceinline__ uint32_t depth_block_exclusive(uint32_t mine, uint32_t* lds, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)inc, d); if ((int)lane >= d) inc += y; }
-    if (lane == 63u) lds[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; w++) before += lds[w];
-    if (total) *total = lds[0] + lds[1] + lds[2] + lds[3];
-    return before + inc - mine;
-}
 }  // namespace
 
-// A step that left records: a lane per read.  kind 1 -- the record's found stretches, two adds each; kind 2 -- nothing; kind 0 -- the wave scans the read's pairs
+// A step that left records: a lane per read.  kind 1 -- the record's found stretches, two adds each; kind 0 -- the wave scans the read's pairs
 __global__ __launch_bounds__(256) void fin_depth_rec_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
                                                             const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len, int32_t* diff, uint32_t* flags,
                                                             const uint32_t* ovf_count, uint32_t ovf_cap) {
     if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    uint32_t kind = 2u;
-    uint64_t p_lo = 0, p_hi = 0;
-    if (r < n_reads) {
-        const uint4 a = ((const uint4*)(frec + r))[0];   // u, off0, meta, nk
-        kind = a.z >> 16;
-        if (kind == 1u && a.w != 0u) {
-            if (a.x >= n_unitigs) depth_flag(flags, 2u);
-            else {
-                const uint4 b = ((const uint4*)(frec + r))[1];
-                const uint32_t nk = a.w;
-                const uint64_t g0 = (uint64_t)ends_p[a.x] + a.y;
-                uint32_t lim = nk;   // strand slots [0, lim) name places of the text
-                if (g0 + nk > total_len) { depth_flag(flags, 2u); lim = g0 < total_len ? (uint32_t)(total_len - g0) : 0u; }   // (the slots beyond it count as absent)
-                // the found stretches (fin_rec_walk.h), each cut off at `lim`
-                (void)sgm_rec_walk(a, b, k, [&](uint32_t, uint32_t from, uint32_t to) {
-                    if (to > lim) to = lim;
-                    if (from < to) depth_range(diff, g0 + from, g0 + to);
-                });
-            }
-        } else if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
+    const FinReadItem it = fin_read_item<false>(frec, out_offs, blockIdx.x * 256u + threadIdx.x, n_reads);
+    if (it.kind == 1u && it.a.w != 0u) {
+        const uint4 a = it.a;
+        if (a.x >= n_unitigs) depth_flag(flags, 2u);
+        else {
+            const uint4 b = it.load_b();
+            const uint32_t nk = a.w;
+            const uint64_t g0 = (uint64_t)ends_p[a.x] + a.y;
+            uint32_t lim = nk;   // strand slots [0, lim) name places of the text
+            if (g0 + nk > total_len) { depth_flag(flags, 2u); lim = g0 < total_len ? (uint32_t)(total_len - g0) : 0u; }   // (the slots beyond it count as absent)
+            // the found stretches (fin_rec_walk.h), each cut off at `lim`
+            (void)sgm_rec_walk(a, b, k, [&](uint32_t, uint32_t from, uint32_t to) {
+                if (to > lim) to = lim;
+                if (from < to) depth_range(diff, g0 + from, g0 + to);
+            });
+        }
     }
-    // ---- the searched reads' pairs ----
-    ull todo = __ballot(kind == 0u && p_hi > p_lo);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
-        depth_scan(pairs, fin_bcast64(p_lo, src), fin_bcast64(p_hi, src), ends_p, n_unitigs, total_len, diff, flags);
-    }
+    fin_each_searched_read(it, [&](int, uint64_t lo, uint64_t hi) { depth_scan(pairs, lo, hi, ends_p, n_unitigs, total_len, diff, flags); });
 }
 
 // A step that left no records: every slot of the pair array, FIN_DEPTH_FLAT consecutive slots per wave (runs then reach across reads, which depth does not mind)
@@ -174,7 +148,7 @@ __global__ __launch_bounds__(256) void fin_depth_tile_sum_kernel(const uint32_t*
 #pragma unroll
     for (uint32_t j = 0; j < 16u; j++) s += v[j];
     uint32_t total = 0;
-    (void)depth_block_exclusive(s, lds, &total);
+    (void)fin_block_exclusive4(s, lds, &total);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 // 2. one block: tile_sum[b] becomes what lies in front of tile b -- *carry (the chunks before this one) plus the tiles before it; *carry takes this chunk's sum in
@@ -205,7 +179,7 @@ __global__ __launch_bounds__(256) void fin_depth_apply_kernel(const uint32_t* x,
     uint32_t s = 0;
 #pragma unroll
     for (uint32_t j = 0; j < 16u; j++) { s += v[j]; v[j] = s; }   // inclusive inside the thread
-    const uint32_t before = tile_sum[blockIdx.x] + depth_block_exclusive(s, lds, nullptr);
+    const uint32_t before = tile_sum[blockIdx.x] + fin_block_exclusive4(s, lds, nullptr);
     if (tile == 4096u && base + 4096u <= n) {
         uint4* q = (uint4*)(depth + base + (uint64_t)threadIdx.x * 16u);
 #pragma unroll

@@ -30,10 +30,11 @@
 // W = 1: a lane per row.  W > 1: the wave takes its 64 rows one after the other, lane i holding word i -- fin_col_pseudo_kernel's row copy: coalesced loads, a
 // commutative mix per (word, index), an xor reduction over the wave, one ballot for "empty".
 //
-// The download compacts on the device: fin_ec_occ_kernel counts the occupied slots per block of 256, fin_launch_blk_scan (fin_segments.hip) makes the blocks'
+// The download compacts on the device: fin_ec_occ_kernel counts the occupied slots per block of 256, fin_launch_blk_scan (fin_records.hip) makes the blocks'
 // offsets and the total, fin_ec_gather_kernel writes the dense {row, reads} list.
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_wave.h"
 #include "fin_rowhash.h"   // ec_mix, ec_word_hash, ec_wave_xor: the row hash, shared with fin_bootstrap.hip
 
 #define FIN_EC_BLK 256u
@@ -43,8 +44,6 @@
 namespace {
 typedef unsigned long long ull;
 
-__device__ __forceinline__ uint32_t ec_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-__device__ __forceinline__ uint64_t ec_bcast64(uint64_t v, int src) { return ((uint64_t)ec_bcast((uint32_t)(v >> 32), src) << 32) | ec_bcast((uint32_t)v, src); }
 __device__ __forceinline__ uint64_t ec_tag(uint64_t h, uint32_t tag_bits) {
     const uint64_t t = h & ((1ull << tag_bits) - 1ull);   // tag_bits is 1 .. 63
     return t ? t : 1ull;
@@ -82,7 +81,7 @@ __device__ __forceinline__ void ec_count(uint32_t r, uint32_t s, bool eq, ull* c
         ull rem = m_eq;
         while (rem) {                        // the wave's distinct slots, one atomic each
             const int src = __ffsll((long long)rem) - 1;
-            const uint32_t sc = ec_bcast(s, src);
+            const uint32_t sc = fin_bcast(s, src);
             const ull m = __ballot(has && eq && s == sc);
             rem &= ~m;
             if ((int)lane == src) (void)atomicAdd(counts + sc, (ull)__popcll(m));
@@ -91,7 +90,7 @@ __device__ __forceinline__ void ec_count(uint32_t r, uint32_t s, bool eq, ull* c
     if (m_ne) {                              // two distinct rows under one tag: the serial pass settles them
         ull base = 0;
         if (lane == 0u) base = atomicAdd(ctr + 5, (ull)__popcll(m_ne));
-        base = ec_bcast64(base, 0);
+        base = fin_bcast64(base, 0);
         const ull at = base + (ull)__popcll(m_ne & ((1ull << lane) - 1ull));
         if (has && !eq && at < n_rows) coll[at] = r;   // (the list starts every add empty: at < n_rows always)
     }
@@ -131,8 +130,8 @@ __global__ __launch_bounds__(256) void fin_ec_claim_kernel(const ull* rows, uint
                 const uint64_t tag = ec_tag(ec_wave_xor(lane < W ? ec_word_hash(word, lane) : 0ull), tag_bits);
                 bool won = false;
                 if (lane == 0u) res = ec_probe(tags, lg, tag, &won);
-                res = ec_bcast(res, 0);
-                if (ec_bcast((uint32_t)won, 0)) {
+                res = fin_bcast(res, 0);
+                if (fin_bcast((uint32_t)won, 0)) {
                     if (lane < W) tab_rows[(uint64_t)res * W + lane] = word;
                     if (lane == 0u) ec_new_class(ctr, max_classes);
                 }
@@ -158,7 +157,7 @@ __global__ __launch_bounds__(256) void fin_ec_count_kernel(const ull* rows, uint
         ull a = 0ull, b = 0ull;             // the pair to come, loaded a row ahead
         if (todo) {
             const int src = __ffsll((long long)todo) - 1;
-            const uint32_t ss = ec_bcast(s, src);
+            const uint32_t ss = fin_bcast(s, src);
             if (lane < W) { a = rows[(uint64_t)(r0 + (uint32_t)src) * W + lane]; b = tab_rows[(uint64_t)ss * W + lane]; }
         }
         while (todo) {
@@ -168,7 +167,7 @@ __global__ __launch_bounds__(256) void fin_ec_count_kernel(const ull* rows, uint
             a = b = 0ull;
             if (todo) {
                 const int nx = __ffsll((long long)todo) - 1;
-                const uint32_t ss = ec_bcast(s, nx);
+                const uint32_t ss = fin_bcast(s, nx);
                 if (lane < W) { a = rows[(uint64_t)(r0 + (uint32_t)nx) * W + lane]; b = tab_rows[(uint64_t)ss * W + lane]; }
             }
             const bool same = __ballot(x != y) == 0ull;
@@ -190,7 +189,7 @@ __global__ __launch_bounds__(64) void fin_ec_serial_kernel(const ull* rows, uint
     for (uint64_t j = 0; j < n; j++) {
         const uint32_t r = coll[j], cand = slot_of[r];
         const ull word = lane < W ? rows[(uint64_t)r * W + lane] : 0ull;
-        const ull tag = ec_bcast64(lane == (cand & 63u) ? tags[cand] : 0ull, (int)(cand & 63u));   // the candidate's tag is the row's
+        const ull tag = fin_bcast64(lane == (cand & 63u) ? tags[cand] : 0ull, (int)(cand & 63u));   // the candidate's tag is the row's
         uint32_t s = (cand + 1u) & mask;
         bool done = false;
         for (uint64_t probed = 0; probed < slots && !done;) {
@@ -202,7 +201,7 @@ __global__ __launch_bounds__(64) void fin_ec_serial_kernel(const ull* rows, uint
                 const int q = __ffsll((long long)cm) - 1;
                 cm &= cm - 1ull;
                 const uint32_t sq = b + (uint32_t)q;
-                if (ec_bcast64(t, q) == 0ull) {      // an empty slot ends the chain: the row is new
+                if (fin_bcast64(t, q) == 0ull) {      // an empty slot ends the chain: the row is new
                     if ((int)lane == q) { tags[sq] = tag; counts[sq] = 1ull; }
                     if (lane < W) tab_rows[(uint64_t)sq * W + lane] = word;
                     n_new++; n_done++; done = true;

@@ -19,18 +19,13 @@
 // Nothing here writes anything but counts[] and the accumulator's flag word; the records and the pairs are read only.
 #include "fin_device.h"
 #include "fin_kernels.h"
-#include "fin_rec_walk.h"
+#include "fin_wave.h"
 
 #define FIN_HITS_FLAT 4096u   // slots a wave scans in the flat form (64 rows: the held-back run pays off)
 
 namespace {
 typedef unsigned long long ull;
 
-__device__ __forceinline__ uint32_t hits_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
 __device__ __forceinline__ void hits_add(ull* counts, uint32_t n_unitigs, uint32_t* flags, uint32_t u, ull n) {
     if (n == 0ull) return;
     if (u < n_unitigs) (void)__hip_atomic_fetch_add(counts + u, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -62,7 +57,7 @@ __device__ __forceinline__ void hits_scan(const int2* pairs, uint64_t lo, uint64
         const ull F = __ballot(head && u != 0xFFFFFFFFu);
         if (F == 0ull) continue;
         const uint32_t last = 63u - (uint32_t)__clzll((long long)F);
-        const uint32_t ul = (uint32_t)__builtin_amdgcn_readlane((int)u, (int)last);
+        const uint32_t ul = fin_bcast(u, (int)last);
         const uint32_t s = (uint32_t)__popcll(__ballot(act && u == ul));
         if (head && u != ul && u != 0xFFFFFFFFu) hits_add(counts, n_unitigs, flags, u, n);
         if (c.n && c.u != ul) { if (lane == 0u) hits_add(counts, n_unitigs, flags, c.u, c.n); c.n = 0ull; }
@@ -75,44 +70,34 @@ __device__ __forceinline__ void hits_flush(ull* counts, uint32_t n_unitigs, uint
 }
 }  // namespace
 
-// A step that left records: a lane per read.  kind 1 -- the record's number, summed over the wave's lanes with the same unitig; kind 2 -- nothing;
+// A step that left records: a lane per read (fin_wave.h).  kind 1 -- the record's number, summed over the wave's lanes with the same unitig;
 // kind 0 -- the wave scans the read's pairs, read by read
 __global__ __launch_bounds__(256) void fin_hits_rec_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
                                                            ull* counts, uint32_t n_unitigs, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, uint32_t combine) {
     if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    uint32_t u = 0, cnt = 0, kind = 2u;
-    uint64_t p_lo = 0, p_hi = 0;
-    if (r < n_reads) {
-        const uint4 a = ((const uint4*)(frec + r))[0];   // u, off0, meta, nk
-        kind = a.z >> 16;
-        if (kind == 1u) {
-            const uint4 b = ((const uint4*)(frec + r))[1];
-            uint32_t gaps = 0;
-            fin_rec_gaps(a.w, a.z & 0xFFu, b.x, b.y, b.z, b.w, k, [&](uint32_t lo, uint32_t hi_excl) { gaps += hi_excl - lo; });
-            u = a.x; cnt = a.w - gaps;
-        } else if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
+    const FinReadItem it = fin_read_item<false>(frec, out_offs, blockIdx.x * 256u + threadIdx.x, n_reads);
+    uint32_t u = 0, cnt = 0;
+    if (it.kind == 1u) {
+        const uint4 a = it.a, b = it.load_b();
+        uint32_t gaps = 0;
+        fin_rec_gaps(a.w, a.z & 0xFFu, b.x, b.y, b.z, b.w, k, [&](uint32_t lo, uint32_t hi_excl) { gaps += hi_excl - lo; });
+        u = a.x; cnt = a.w - gaps;
     }
     // ---- the records' numbers ----
-    ull open = __ballot(kind == 1u && cnt != 0u);
+    ull open = __ballot(it.kind == 1u && cnt != 0u);
     for (uint32_t round = 0; round < combine && open; round++) {
         const int lead = __ffsll((long long)open) - 1;
-        const uint32_t lu = (uint32_t)__builtin_amdgcn_readlane((int)u, lead);
+        const uint32_t lu = fin_bcast(u, lead);
         const bool mine = ((open >> lane) & 1ull) && u == lu;
-        const uint32_t s = hits_wave_sum(mine ? cnt : 0u);   // (a record's nk is below 2^16: positions are 16 bits)
+        const uint32_t s = fin_wave_sum(mine ? cnt : 0u);   // (a record's nk is below 2^16: positions are 16 bits)
         if ((int)lane == lead) hits_add(counts, n_unitigs, flags, lu, (ull)s);
         open &= ~__ballot(mine);
     }
     if ((open >> lane) & 1ull) hits_add(counts, n_unitigs, flags, u, (ull)cnt);
     // ---- the searched reads' pairs ----
-    ull todo = __ballot(kind == 0u && p_hi > p_lo);
     HitsCarry c = {0xFFFFFFFFu, 0ull};
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
-        hits_scan(pairs, fin_bcast64(p_lo, src), fin_bcast64(p_hi, src), counts, n_unitigs, flags, combine != 0u, c);
-    }
+    fin_each_searched_read(it, [&](int, uint64_t lo, uint64_t hi) { hits_scan(pairs, lo, hi, counts, n_unitigs, flags, combine != 0u, c); });
     hits_flush(counts, n_unitigs, flags, c);
 }
 

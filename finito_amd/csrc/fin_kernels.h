@@ -151,7 +151,7 @@ int fin_launch_sgm_count(const void* frec, const uint64_t* out_offs, const void*
                          uint64_t* blk_off, uint64_t* total, hipStream_t stream);
 int fin_launch_sgm_write(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const uint32_t* cnt,
                          const uint64_t* blk_off, uint64_t* seg_offs, void* segs, hipStream_t stream);
-// the one-block exclusive prefix of n_blk > 0 per-block counts and their total, both uint64 (fin_segments.hip's scan by itself)
+// the one-block exclusive prefix of n_blk > 0 per-block counts and their total, both uint64 (fin_blk_scan_kernel, fin_records.hip: every dense output made from per-block counts shares it)
 int fin_launch_blk_scan(const uint32_t* blk_sum, uint32_t n_blk, uint64_t* blk_off, uint64_t* total, hipStream_t stream);
 // fin_readsum.hip: a finished step's results as one summary {n_found, n_segments, longest, span} of 16 bytes per read (sum[n_reads]).  frec / out_offs / pairs
 // as fin_launch_hits_add.  The screen made from the summaries: fin_launch_screen_bits writes bits[(n_reads + 63) / 64] (uint64, bit r & 63 of word r >> 6: read r

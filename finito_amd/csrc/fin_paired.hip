@@ -14,7 +14,7 @@
 //             out[w] = (wa & wb & M(pab)) | (wa & ~wb & M(pa)) | (wb & ~wa & M(pb)).  ua == ub is no special case.  W > 1: wave-cooperative, a ballot of the lanes on
 //             this path, for each the wave loads both rows, lane i word i; one ballot each of wa != 0 and wb != 0 are the non-empty flags; lane i stores word i; a
 //             wave sum is the popcount.  W = 1: a lane does its own fragment, coalesced as it is.
-//   a mate scanned -- the wave takes such fragments one after the other with fin_colors.hip's register table (entry i in lane i), SEEDED with (u, n) of a kind-1
+//   a mate scanned -- the wave takes such fragments one after the other with fin_colors.hip's register table (FinUnitigTable, entry i in lane i), SEEDED with (u, n) of a kind-1
 //             partner, every entry with a second count: the slots that came from the first mate.  Either or both ranges are scanned through out_offs; the output
 //             word is one ballot of the threshold test; n_coloured_first is a wave sum.
 //   more than 64 distinct unitigs in the FRAGMENT -- the table is dropped, the fragment is rescanned: n_coloured from a lane per slot over both ranges plus the
@@ -22,38 +22,22 @@
 // No LDS, no atomics, no global scratch; every output word has one writer.  A slot whose unitig number is at or above n_unitigs counts as absent.
 #include "fin_device.h"
 #include "fin_kernels.h"
-#include "fin_rec_walk.h"
+#include "fin_wave.h"
 
 #define FIN_PAIR_BLK 256u   // fragments per block: a lane per fragment
 
 namespace {
 typedef unsigned long long ull;
 
-__device__ __forceinline__ uint32_t pr_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-__device__ __forceinline__ uint64_t pr_bcast64(uint64_t v, int src) { return ((uint64_t)pr_bcast((uint32_t)(v >> 32), src) << 32) | pr_bcast((uint32_t)v, src); }
-__device__ __forceinline__ uint32_t pr_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
-
 // read r as a mate: n found slots in unitig u (a kind-1 record), or the pair range [lo, hi) to scan (hi > lo), or nothing (n = 0, hi = lo = 0)
-__device__ __forceinline__ void pr_mate(const FinFastRec* frec, const uint64_t* out_offs, uint32_t r, uint32_t k, uint32_t n_unitigs, uint32_t& u, uint32_t& n,
-                                        uint64_t& lo, uint64_t& hi) {
-    uint32_t kind = 0u;
-    if (frec) {
-        const uint4 a = ((const uint4*)(frec + r))[0];   // u, off0, meta, nk
-        kind = a.z >> 16;
-        if (kind == 1u && a.w != 0u && a.x < n_unitigs) {
-            const uint4 b = ((const uint4*)(frec + r))[1];
-            (void)sgm_rec_walk(a, b, k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
-            u = a.x;
-        }
+__device__ __forceinline__ void pr_mate(const FinFastRec* frec, const uint64_t* out_offs, uint32_t r, uint32_t n_reads, uint32_t k, uint32_t n_unitigs, uint32_t& u,
+                                        uint32_t& n, uint64_t& lo, uint64_t& hi) {
+    const FinReadItem it = fin_read_item<false>(frec, out_offs, r, n_reads);
+    if (it.kind == 1u && it.a.w != 0u && it.a.x < n_unitigs) {
+        (void)sgm_rec_walk(it.a, it.load_b(), k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
+        u = it.a.x;
     }
-    if (kind == 0u) {
-        const uint64_t l = out_offs[r], h = out_offs[r + 1];
-        if (h > l) { lo = l; hi = h; }
-    }
+    if (it.scanned()) { lo = it.p_lo; hi = it.p_hi; }
 }
 
 // the closed form of two mates that lie in one unitig each: word w of the fragment's row from word w of the two rows (0 where the mate has no coloured slot)
@@ -64,71 +48,17 @@ __device__ __forceinline__ ull pr_closed(ull wa, ull wb, uint32_t ca, uint32_t c
     return (wa & wb & (pab ? ~0ull : 0ull)) | (wa & ~wb & (pa ? ~0ull : 0ull)) | (wb & ~wa & (pb ? ~0ull : 0ull));
 }
 
-// slots [lo, hi) of one mate into the wave's table (entry i < n_ent in lane i): t_cnt, and t_first if the mate is the first.  Wave-converged
-__device__ __forceinline__ void pr_table_scan(const int2* pairs, uint64_t lo, uint64_t hi, uint32_t n_unitigs, bool first, uint32_t& n_found, uint32_t& n_ent,
-                                              uint32_t& t_u, uint32_t& t_cnt, uint32_t& t_first, bool& over) {
-    const uint32_t lane = threadIdx.x & 63u;
-    int2 pn = make_int2(-1, -1);            // the row to come, loaded a row ahead
-    if (lo + lane < hi) pn = pairs[lo + lane];
-    for (uint64_t base = lo; base < hi; base += 64u) {
-        const uint64_t j = base + lane;
-        const int2 p = pn;                  // (-1,-1) in a lane beyond the mate's end
-        pn = make_int2(-1, -1);
-        if (j + 64u < hi) pn = pairs[j + 64u];
+// slots [lo, hi) of one mate into the wave's table: its counts, and t_first -- the slots that came from the first mate -- beside them.  Wave-converged
+__device__ __forceinline__ void pr_table_scan(const int2* pairs, uint64_t lo, uint64_t hi, uint32_t n_unitigs, bool first, uint32_t& n_found, FinUnitigTable& tab,
+                                              uint32_t& t_first) {
+    fin_each_pair_row(pairs, lo, hi, [&](uint64_t, uint64_t, int2 p) {
         const uint32_t u = (uint32_t)p.x;
-        ull rem = __ballot(u < n_unitigs);
-        n_found += (uint32_t)__popcll(rem);
-        while (rem && !over) {              // the row's distinct unitigs, one item each
-            const int src = __ffsll((long long)rem) - 1;
-            const uint32_t uc = pr_bcast(u, src);
-            const ull m = __ballot(u == uc);
-            rem &= ~m;
+        n_found += (uint32_t)__popcll(__ballot(u < n_unitigs));
+        fin_each_distinct(u, u < n_unitigs, [&](int, uint32_t uc, ull m) {
             const uint32_t c = (uint32_t)__popcll(m);
-            const bool mine = lane < n_ent && t_u == uc;
-            if (__ballot(mine)) { if (mine) { t_cnt += c; if (first) t_first += c; } }
-            else if (n_ent < 64u) {
-                if (lane == n_ent) { t_u = uc; t_cnt = c; t_first = first ? c : 0u; }
-                n_ent++;
-            } else over = true;
-        }
-    }
-}
-
-// the rescans of a fragment whose table overflowed.  n_coloured of slots [lo, hi): a lane per slot looks at its unitig's row
-__device__ __forceinline__ uint32_t pr_rescan_colored(const int2* pairs, uint64_t lo, uint64_t hi, const ull* bits, uint32_t W, uint32_t n_unitigs) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t nc = 0;
-    for (uint64_t base = lo; base < hi; base += 64u) {
-        const uint64_t j = base + lane;
-        uint32_t u = 0xFFFFFFFFu;
-        if (j < hi) u = (uint32_t)pairs[j].x;
-        bool ne = false;
-        if (u < n_unitigs) for (uint32_t w = 0; w < W; w++) if (bits[(uint64_t)u * W + w] != 0ull) ne = true;
-        nc += (uint32_t)__popcll(__ballot(ne));
-    }
-    return nc;
-}
-// what slots [lo, hi) add to cnt[64 w + lane]: for each distinct unitig of a row its word w is broadcast, the lanes whose bit is set add the ballot's popcount
-__device__ __forceinline__ uint32_t pr_rescan_word(const int2* pairs, uint64_t lo, uint64_t hi, const ull* bits, uint32_t W, uint32_t n_unitigs, uint32_t w) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t cnt = 0;
-    for (uint64_t base = lo; base < hi; base += 64u) {
-        const uint64_t j = base + lane;
-        uint32_t u = 0xFFFFFFFFu;
-        if (j < hi) u = (uint32_t)pairs[j].x;
-        ull word = 0ull;
-        if (u < n_unitigs) word = bits[(uint64_t)u * W + w];
-        ull rem = __ballot(u < n_unitigs);
-        while (rem) {
-            const int src = __ffsll((long long)rem) - 1;
-            const uint32_t uc = pr_bcast(u, src);
-            const ull m = __ballot(u == uc);
-            rem &= ~m;
-            const ull we = pr_bcast64(word, src);
-            if ((we >> lane) & 1ull) cnt += (uint32_t)__popcll(m);
-        }
-    }
-    return cnt;
+            if (tab.add(uc, c) && first) t_first += c;   // (t_first is 0 in a lane without an entry)
+        });
+    });
 }
 
 // one fragment with a scanned mate: slots [alo, ahi) are the first mate's, [blo, bhi) the second's (either may be empty), the seed sn found slots in unitig su
@@ -136,51 +66,31 @@ __device__ __forceinline__ uint32_t pr_rescan_word(const int2* pairs, uint64_t l
 __device__ __forceinline__ uint4 pr_scan(const int2* pairs, uint64_t alo, uint64_t ahi, uint64_t blo, uint64_t bhi, uint32_t su, uint32_t sn, bool sfirst, const ull* bits,
                                          uint32_t W, uint32_t n_unitigs, uint32_t permille, uint32_t mode, ull* out) {
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t n_found = sn, n_ent = 0;       // the table: entry i < n_ent in lane i
-    uint32_t t_u = 0, t_cnt = 0, t_first = 0;
-    bool over = false;                      // more than 64 distinct unitigs: the table is dropped
-    if (sn != 0u) {
-        if (lane == 0u) { t_u = su; t_cnt = sn; t_first = sfirst ? sn : 0u; }
-        n_ent = 1u;
-    }
-    pr_table_scan(pairs, alo, ahi, n_unitigs, true, n_found, n_ent, t_u, t_cnt, t_first, over);
-    pr_table_scan(pairs, blo, bhi, n_unitigs, false, n_found, n_ent, t_u, t_cnt, t_first, over);
+    uint32_t n_found = sn, t_first = 0;
+    FinUnitigTable tab;
+    if (sn != 0u && tab.add(su, sn) && sfirst) t_first = sn;   // the seed is entry 0
+    pr_table_scan(pairs, alo, ahi, n_unitigs, true, n_found, tab, t_first);
+    pr_table_scan(pairs, blo, bhi, n_unitigs, false, n_found, tab, t_first);
     uint32_t n_colored = 0, n_first = 0, pc = 0;
-    if (!over) {
-        const bool live = lane < n_ent;
-        const ull* row = bits + (uint64_t)t_u * W;   // (t_u = 0 in a lane without an entry: never read)
-        bool ne = false;
-        for (uint32_t w = 0; w < W; w++) if (live && row[w] != 0ull) ne = true;
-        n_colored = pr_wave_sum(live && ne ? t_cnt : 0u);
-        n_first = pr_wave_sum(live && ne ? t_first : 0u);
+    if (!tab.over) {
+        const bool ne = tab.colored(bits, W);
+        n_colored = fin_wave_sum(ne ? tab.t_cnt : 0u);
+        n_first = fin_wave_sum(ne ? t_first : 0u);
         const bool keep = mode == 0u || (n_first != 0u && n_colored != n_first);
         const uint64_t need = (uint64_t)permille * n_colored;
-        for (uint32_t w = 0; w < W; w++) {
-            const ull word = live ? row[w] : 0ull;
-            uint32_t cnt = 0;
-            for (uint32_t e = 0; e < n_ent; e++) {   // wave-uniform
-                const ull we = pr_bcast64(word, (int)e);
-                const uint32_t ce = pr_bcast(t_cnt, (int)e);
-                if ((we >> lane) & 1ull) cnt += ce;
-            }
-            const ull o = keep ? __ballot(cnt >= 1u && 1000ull * cnt >= need) : 0ull;
-            if (lane == 0u) out[w] = o;
-            pc += (uint32_t)__popcll(o);
-        }
+        for (uint32_t w = 0; w < W; w++) pc += fin_row_word(tab.word_counts(bits, W, w), need, keep, out, w);
     } else {
         bool sne = false;                   // the seed's row: lane i looks at word i
         if (sn != 0u) sne = __ballot(lane < W && bits[(uint64_t)su * W + (lane < W ? lane : 0u)] != 0ull) != 0ull;
         const uint32_t sc = sne ? sn : 0u;
-        n_first = pr_rescan_colored(pairs, alo, ahi, bits, W, n_unitigs) + (sfirst ? sc : 0u);
-        n_colored = n_first + pr_rescan_colored(pairs, blo, bhi, bits, W, n_unitigs) + (sfirst ? 0u : sc);
+        n_first = fin_rescan_colored(pairs, alo, ahi, bits, W, n_unitigs) + (sfirst ? sc : 0u);
+        n_colored = n_first + fin_rescan_colored(pairs, blo, bhi, bits, W, n_unitigs) + (sfirst ? 0u : sc);
         const bool keep = mode == 0u || (n_first != 0u && n_colored != n_first);
         const uint64_t need = (uint64_t)permille * n_colored;
         for (uint32_t w = 0; w < W; w++) {
-            uint32_t cnt = pr_rescan_word(pairs, alo, ahi, bits, W, n_unitigs, w) + pr_rescan_word(pairs, blo, bhi, bits, W, n_unitigs, w);
+            uint32_t cnt = fin_rescan_word(pairs, alo, ahi, bits, W, n_unitigs, w) + fin_rescan_word(pairs, blo, bhi, bits, W, n_unitigs, w);
             if (sn != 0u && ((bits[(uint64_t)su * W + w] >> lane) & 1ull)) cnt += sn;
-            const ull o = keep ? __ballot(cnt >= 1u && 1000ull * cnt >= need) : 0ull;
-            if (lane == 0u) out[w] = o;
-            pc += (uint32_t)__popcll(o);
+            pc += fin_row_word(cnt, need, keep, out, w);
         }
     }
     return make_uint4(n_found, n_colored, pc, n_first);
@@ -196,8 +106,8 @@ __global__ __launch_bounds__(256) void fin_pair_pseudo_kernel(const FinFastRec* 
     uint32_t ua = 0, na = 0, ub = 0, nb = 0;   // a kind-1 mate's unitig and found slots
     uint64_t alo = 0, ahi = 0, blo = 0, bhi = 0;
     if (f < n_frags) {
-        pr_mate(frec, out_offs, 2u * f, k, n_unitigs, ua, na, alo, ahi);
-        pr_mate(frec, out_offs, 2u * f + 1u, k, n_unitigs, ub, nb, blo, bhi);
+        pr_mate(frec, out_offs, 2u * f, 2u * n_frags, k, n_unitigs, ua, na, alo, ahi);
+        pr_mate(frec, out_offs, 2u * f + 1u, 2u * n_frags, k, n_unitigs, ub, nb, blo, bhi);
     }
     const bool scanned = ahi > alo || bhi > blo;
     uint4 mine = make_uint4(0u, 0u, 0u, 0u);
@@ -211,11 +121,8 @@ __global__ __launch_bounds__(256) void fin_pair_pseudo_kernel(const FinFastRec* 
             mine = make_uint4(na + nb, ca + cb, (uint32_t)__popcll(o), ca);
         }
     } else {
-        ull todo = __ballot(f < n_frags && !scanned);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1ull;
-            const uint32_t uas = pr_bcast(ua, src), nas = pr_bcast(na, src), ubs = pr_bcast(ub, src), nbs = pr_bcast(nb, src);
+        fin_each_lane(f < n_frags && !scanned, [&](int src) {
+            const uint32_t uas = fin_bcast(ua, src), nas = fin_bcast(na, src), ubs = fin_bcast(ub, src), nbs = fin_bcast(nb, src);
             ull wa = 0ull, wb = 0ull;
             if (lane < W) {
                 if (nas != 0u) wa = bits[(uint64_t)uas * W + lane];
@@ -224,21 +131,18 @@ __global__ __launch_bounds__(256) void fin_pair_pseudo_kernel(const FinFastRec* 
             const uint32_t ca = __ballot(wa != 0ull) ? nas : 0u, cb = __ballot(wb != 0ull) ? nbs : 0u;
             const ull o = pr_closed(wa, wb, ca, cb, permille, mode);
             if (lane < W) rows[(uint64_t)(f0 + (uint32_t)src) * W + lane] = o;
-            const uint32_t pc = pr_wave_sum((uint32_t)__popcll(o));
+            const uint32_t pc = fin_wave_sum((uint32_t)__popcll(o));
             if ((int)lane == src) mine = make_uint4(nas + nbs, ca + cb, pc, ca);
-        }
+        });
     }
     // ---- a mate scanned: the wave takes its lanes' fragments one after the other ----
-    ull todo = __ballot(scanned);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
-        const uint32_t nas = pr_bcast(na, src), nbs = pr_bcast(nb, src);   // (a scanned mate's n is 0: at most one of them is a seed)
-        const uint32_t su = nas != 0u ? pr_bcast(ua, src) : pr_bcast(ub, src);
-        const uint4 s = pr_scan(pairs, pr_bcast64(alo, src), pr_bcast64(ahi, src), pr_bcast64(blo, src), pr_bcast64(bhi, src), su, nas + nbs, nas != 0u, bits, W,
+    fin_each_lane(scanned, [&](int src) {
+        const uint32_t nas = fin_bcast(na, src), nbs = fin_bcast(nb, src);   // (a scanned mate's n is 0: at most one of them is a seed)
+        const uint32_t su = nas != 0u ? fin_bcast(ua, src) : fin_bcast(ub, src);
+        const uint4 s = pr_scan(pairs, fin_bcast64(alo, src), fin_bcast64(ahi, src), fin_bcast64(blo, src), fin_bcast64(bhi, src), su, nas + nbs, nas != 0u, bits, W,
                                 n_unitigs, permille, mode, rows + (uint64_t)(f0 + (uint32_t)src) * W);
         if ((int)lane == src) mine = s;
-    }
+    });
     if (f < n_frags) heads[f] = mine;
 }
 

@@ -5,58 +5,41 @@
 // under the rule of fin_segments.hip (link(i) and link(i - 1) decide a head), the longest segment, and last found slot - first found slot + 1.  All four are the
 // same when the slot order is reversed, so a record found on the reverse strand (meta bit 8) needs no special case.
 //
-// What is read (as fin_sgm_kernel<false>).  Where the step left records, a lane per read:
-//   kind 1 -- the 32-byte record alone, through sgm_rec_walk: n_found = the sum of the stretches, n_segments = how many, longest = the longest,
-//             span = the last stretch's end - the first one's start.  The read's pairs are never touched -- in text mode 2 they do not exist.
+// What is read (the frame is fin_wave.h's).  Where the step left records, a lane per read:
+//   kind 1 -- through sgm_rec_walk: n_found = the sum of the stretches, n_segments = how many, longest = the longest, span = the last stretch's end - the first
+//             one's start.
 //   kind 2 -- all zero.
-//   kind 0 -- the wave scans the read's pairs through out_offs, a row of 64 slots at a time, the next row's load issued ahead.  Links and heads as in sgm_scan;
-//             found slots and heads are counted from ballots.  Carried across rows, in wave-uniform registers: the last slot of the row before and its link
-//             (the two-slot history of the head rule), the length so far of the segment still open at the row's end (so `longest` is right for a segment
-//             that crosses any number of rows), the first and the last found slot.
-// Where the step left no records (frec null) every read is scanned as a kind-0 read.
+//   kind 0 -- the wave scans the read's pairs, a row of 64 slots at a time, the next row loaded ahead.  Links and heads by fin_seg_head; found slots and heads are
+//             counted from ballots.  Carried across rows, in wave-uniform registers: the two-slot history of the head rule, the length so far of the segment
+//             still open at the row's end (so `longest` is right for a segment that crosses any number of rows), the first and the last found slot.
 // A lane writes its read's summary as one 16-byte store; nothing else is written, and there are no atomics: every output word has one writer.
 //
 // The screen: read r passes when (n_found >= min_found && 1000 * n_found >= min_permille * nk) != invert, in 64-bit arithmetic, nk from out_offs.  bits: a
 // wave's ballot is one uint64 word of the bitmap, stored by lane 0.  ids: the passing read numbers, dense and ascending, by the three steps of fin_sgm_*: (1)
-// fin_scr_bits_kernel also counts per block of 256 reads, (2) the one-block uint64 scan (fin_launch_blk_scan, fin_segments.hip), (3) fin_scr_ids_kernel
+// fin_scr_bits_kernel also counts per block of 256 reads, (2) the one-block uint64 scan (fin_launch_blk_scan, fin_records.hip), (3) fin_scr_ids_kernel
 // places a read at its block's offset + the passing reads before it in the block, taken from the bitmap's words.
 #include "fin_device.h"
 #include "fin_kernels.h"
-#include "fin_rec_walk.h"
+#include "fin_wave.h"
 
 #define FIN_RSM_BLK 256u   // reads per block: a lane per read
 
 namespace {
 typedef unsigned long long ull;
 
-__device__ __forceinline__ uint32_t rsm_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-__device__ __forceinline__ uint64_t rsm_bcast64(uint64_t v, int src) { return ((uint64_t)rsm_bcast((uint32_t)(v >> 32), src) << 32) | rsm_bcast((uint32_t)v, src); }
-
 // slots [lo, hi) of the pair array are one read's: its summary {n_found, n_segments, longest, span}, the whole wave, a row of 64 slots at a time.
 // Wave-converged; every lane returns the same value.
 __device__ __forceinline__ uint4 rsm_scan(const int2* pairs, uint64_t lo, uint64_t hi) {
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t pu = 0xFFFFFFFFu, poff = 0u;   // the last slot of the row before (0xFFFFFFFF: absent, or there is none)
-    int plink = 0;                          // and its link
+    FinSegCarry carry;
     uint32_t n_found = 0, n_seg = 0, longest = 0;
     uint32_t open_len = 0;                  // a segment reached the end of the row before: its slots so far (0: none did)
     uint32_t first = 0xFFFFFFFFu, last = 0; // the first and the last found slot so far
-    int2 pn = make_int2(-1, -1);            // the row to come, loaded a row ahead
-    if (lo + lane < hi) pn = pairs[lo + lane];
-    for (uint64_t base = lo; base < hi; base += 64u) {
-        const uint64_t j = base + lane;
-        const int2 p = pn;                  // (-1,-1) in a lane beyond the read's end
-        pn = make_int2(-1, -1);
-        if (j + 64u < hi) pn = pairs[j + 64u];
+    fin_each_pair_row(pairs, lo, hi, [&](uint64_t base, uint64_t, int2 p) {
         const uint32_t u = (uint32_t)p.x, off = (uint32_t)p.y;
         const bool found = u != 0xFFFFFFFFu;
-        uint32_t up = (uint32_t)__shfl_up((int)u, 1), offp = (uint32_t)__shfl_up((int)off, 1);
-        if (lane == 0u) { up = pu; offp = poff; }
-        int link = 0;
-        if (found && u == up) link = off == offp + 1u ? 1 : off + 1u == offp ? -1 : 0;   // (u == up and found: the slot before is found too)
-        int linkp = __shfl_up(link, 1);
-        if (lane == 0u) linkp = plink;
-        const bool head = found && (link == 0 || (linkp != 0 && linkp != link));
+        int link;
+        const bool head = fin_seg_head(u, off, found, carry, link);
         const ull F = __ballot(found), H = __ballot(head);
         const ull B = H | ~F;               // where a segment ends: the next head, the next absent slot (a lane beyond the read's end is one)
         n_found += (uint32_t)__popcll(F);
@@ -74,16 +57,13 @@ __device__ __forceinline__ uint4 rsm_scan(const int2* pairs, uint64_t lo, uint64
         if (H) {                            // the segments that begin in this row (a head closes whatever came in: open_len is 0 here)
             const ull above = lane == 63u ? 0ull : (B >> (lane + 1u)) << (lane + 1u);
             const uint32_t end = above ? (uint32_t)__ffsll((long long)above) - 1u : 64u;
-            uint32_t m = head && end < 64u ? end - lane : 0u;   // closed inside the row; the one that reaches the row's end (the last head's, if any) stays open
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d));
-            longest = max(longest, m);
+            // closed inside the row; the one that reaches the row's end (the last head's, if any) stays open
+            longest = max(longest, fin_wave_max(head && end < 64u ? end - lane : 0u));
             const uint32_t hl = 63u - (uint32_t)__clzll((long long)H);
             if ((hl == 63u ? 0ull : B >> (hl + 1u)) == 0ull) open_len = 64u - hl;
         }
-        pu = rsm_bcast(u, 63); poff = rsm_bcast(off, 63);
-        plink = __builtin_amdgcn_readlane(link, 63);
-    }
+        fin_seg_next_row(carry, u, off, link);
+    });
     longest = max(longest, open_len);       // (the read ended on a row's last slot)
     return make_uint4(n_found, n_seg, longest, n_found ? last - first + 1u : 0u);
 }
@@ -92,36 +72,21 @@ __device__ __forceinline__ uint4 rsm_scan(const int2* pairs, uint64_t lo, uint64
 // sum[r] = read r's summary.  frec null: the step left no records, every read is scanned.
 __global__ __launch_bounds__(256) void fin_rsm_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k, uint4* sum) {
     const uint32_t r = blockIdx.x * FIN_RSM_BLK + threadIdx.x, lane = threadIdx.x & 63u;
-    uint32_t kind = 2u;
-    uint64_t p_lo = 0, p_hi = 0;
-    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
-    if (r < n_reads) {
-        kind = 0u;
-        if (frec) {
-            a = ((const uint4*)(frec + r))[0];   // u, off0, meta, nk
-            kind = a.z >> 16;
-            if (kind == 1u) b = ((const uint4*)(frec + r))[1];
-        }
-        if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
-    }
+    const FinReadItem it = fin_read_item<true>(frec, out_offs, r, n_reads);
     uint4 mine = make_uint4(0u, 0u, 0u, 0u);
-    if (kind == 1u && a.w != 0u) {
+    if (it.kind == 1u && it.a.w != 0u) {
         uint32_t n_found = 0, longest = 0, first = 0, last = 0;
-        const uint32_t n = sgm_rec_walk(a, b, k, [&](uint32_t s, uint32_t from, uint32_t to) {
+        const uint32_t n = sgm_rec_walk(it.a, it.b, k, [&](uint32_t s, uint32_t from, uint32_t to) {
             n_found += to - from; longest = max(longest, to - from);
             if (s == 0u) first = from;
             last = to;
         });
         mine = make_uint4(n_found, n, longest, last - first);   // (no stretch: first = last = 0)
     }
-    // ---- the searched reads' pairs: the wave takes its lanes' reads one after the other ----
-    ull todo = __ballot(kind == 0u && p_hi > p_lo);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
-        const uint4 s = rsm_scan(pairs, rsm_bcast64(p_lo, src), rsm_bcast64(p_hi, src));
+    fin_each_searched_read(it, [&](int src, uint64_t lo, uint64_t hi) {
+        const uint4 s = rsm_scan(pairs, lo, hi);
         if ((int)lane == src) mine = s;
-    }
+    });
     if (r < n_reads) sum[r] = mine;
 }
 

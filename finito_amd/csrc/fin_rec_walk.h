@@ -1,7 +1,8 @@
 // fin_rec_walk.h -- THE statement of the record gap rule, for the device and the host alike: what a fast-path record (FinFastRec, fin_read_record) means is
 // worked out here and nowhere else.  Every consumer of records takes the gaps (fin_rec_gaps) or their complement, the found stretches (fin_rec_stretches):
 // fin_hits.hip, fin_cover.hip, fin_depth.hip, fin_segments.hip, fin_readsum.hip, fin_classify.hip, fin_colors.hip, fin_paired.hip and the host twins of
-// fin_records_host.cpp.  Under hipcc the header also holds the two small things every device consumer of a step's records does around the walk.
+// fin_records_host.cpp.  What a device consumer does AROUND the walk -- which reads have a record, the wave's turn through the searched ones, a read's rows --
+// is fin_wave.h's.
 #pragma once
 #include <stdint.h>
 
@@ -59,9 +60,5 @@ __device__ __forceinline__ bool fin_step_withheld(const uint32_t* ovf_count, uin
     if (!ovf_count || *ovf_count <= ovf_cap) return false;
     if (blockIdx.x == 0 && threadIdx.x == 0) (void)__hip_atomic_fetch_or(flags, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return true;
-}
-// lane src's 64-bit value, for the whole wave (the "searched reads' pairs" loops hand one lane's slot range to the wave's scan)
-__device__ __forceinline__ uint64_t fin_bcast64(uint64_t v, int src) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
 }
 #endif

@@ -7,20 +7,9 @@
 // and their records are stamped {0, 0, 0, nk, 0, 0}: records + stream are the batch's whole result (fin_expand_records, fin_capi.cpp, makes the pairs).
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_wave.h"
 
 #define FIN_REC_BLK 1024u   // reads per block
-
-namespace {
-__device__ __forceinline__ uint32_t rec_block_sum(uint32_t v, uint32_t* lds) {   // sum over the block's 256 threads, in every thread
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t t = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return t;
-}
-}  // namespace
 
 // 1. per block of FIN_REC_BLK reads: pairs of the reads whose record is zero (meta >> 16 == 0: the pipeline searched them)
 __global__ __launch_bounds__(256) void fin_rec_count_kernel(const FinFastRec* frec, const uint64_t* out_offs, uint32_t n_reads, uint32_t* blk_sum) {
@@ -31,11 +20,13 @@ __global__ __launch_bounds__(256) void fin_rec_count_kernel(const FinFastRec* fr
         const uint32_t r = r0 + i;
         if (r < n_reads && (frec[r].meta >> 16) == 0u) s += (uint32_t)(out_offs[r + 1] - out_offs[r]);
     }
-    s = rec_block_sum(s, lds);
+    s = fin_block_sum4(s, lds);
     if (threadIdx.x == 0) blk_sum[blockIdx.x] = s;
 }
-// 2. exclusive prefix of the block sums (one block; n_blk <= 2^16 for a batch of 2^26 reads) and the stream's length
-__global__ __launch_bounds__(1024) void fin_rec_scan_kernel(const uint32_t* blk_sum, uint32_t n_blk, uint64_t* blk_off, uint64_t* total) {
+// 2. exclusive prefix of the block sums (one block; n_blk <= 2^16 for a batch of 2^26 reads) and their total -- here the stream's length --, both uint64: a
+// batch's k-mers may number more than 2^32.  THE one-block scan of every dense output made from per-block counts: segments, the screen's ids, the equivalence
+// classes' download and the bootstrap's slabs go through fin_launch_blk_scan as well
+__global__ __launch_bounds__(1024) void fin_blk_scan_kernel(const uint32_t* blk_sum, uint32_t n_blk, uint64_t* blk_off, uint64_t* total) {
     __shared__ uint64_t lds[1024];
     const uint32_t per = (n_blk + 1023u) / 1024u, b0 = threadIdx.x * per;
     uint64_t s = 0;
@@ -54,7 +45,7 @@ __global__ __launch_bounds__(1024) void fin_rec_scan_kernel(const uint32_t* blk_
 }
 // 3. per block: where each of its unfinished reads' pairs go in the stream; their records stamped with nk; their pairs copied, a wave per read
 __global__ __launch_bounds__(256) void fin_rec_compact_kernel(FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, const uint64_t* blk_off, int2* stream) {
-    __shared__ uint32_t lds[4], lds_w[4];
+    __shared__ uint32_t lds_w[4];
     __shared__ uint32_t dst[FIN_REC_BLK];   // offset of read i's pairs inside the block's stretch of the stream; 0xFFFFFFFF: a finished read
     const uint32_t r0 = blockIdx.x * FIN_REC_BLK, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     // a thread's four consecutive reads, then the exclusive prefix over the block's threads
@@ -65,14 +56,7 @@ __global__ __launch_bounds__(256) void fin_rec_compact_kernel(FinFastRec* frec, 
         nk[j] = 0xFFFFFFFFu;
         if (r < n_reads && (frec[r].meta >> 16) == 0u) { nk[j] = (uint32_t)(out_offs[r + 1] - out_offs[r]); mine += nk[j]; }
     }
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)inc, d); if ((int)lane >= d) inc += y; }
-    if (lane == 63u) lds_w[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; w++) before += lds_w[w];
-    uint32_t at = before + inc - mine;
+    uint32_t at = fin_block_exclusive4(mine, lds_w, nullptr);
 #pragma unroll
     for (uint32_t j = 0; j < 4u; j++) {
         const uint32_t i = threadIdx.x * 4u + j;
@@ -80,7 +64,6 @@ __global__ __launch_bounds__(256) void fin_rec_compact_kernel(FinFastRec* frec, 
         if (nk[j] != 0xFFFFFFFFu) { frec[r0 + i].nk = nk[j]; at += nk[j]; }
     }
     __syncthreads();
-    (void)lds;
     int2* const out = stream + blk_off[blockIdx.x];
     for (uint32_t i = wave; i < FIN_REC_BLK; i += 4u) {
         const uint32_t d = dst[i];
@@ -91,14 +74,18 @@ __global__ __launch_bounds__(256) void fin_rec_compact_kernel(FinFastRec* frec, 
     }
 }
 
+// the scan by itself.  n_blk > 0
+extern "C" int fin_launch_blk_scan(const uint32_t* blk_sum, uint32_t n_blk, uint64_t* blk_off, uint64_t* total, hipStream_t stream) {
+    hipLaunchKernelGGL(fin_blk_scan_kernel, dim3(1), dim3(1024), 0, stream, blk_sum, n_blk, blk_off, total);
+    return (int)hipGetLastError();
+}
 extern "C" uint32_t fin_rec_blocks(uint32_t n_reads) { return (n_reads + FIN_REC_BLK - 1u) / FIN_REC_BLK; }
 // blk_sum: fin_rec_blocks() u32; blk_off: as many u64; total: one u64 (the stream's pairs).  Launches kernels 1 and 2.
 extern "C" int fin_launch_rec_count(const void* frec, const uint64_t* out_offs, uint32_t n_reads, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total, hipStream_t stream) {
     const uint32_t nb = fin_rec_blocks(n_reads);
     if (nb == 0) return (int)hipMemsetAsync(total, 0, 8, stream);
     hipLaunchKernelGGL(fin_rec_count_kernel, dim3(nb), dim3(256), 0, stream, (const FinFastRec*)frec, out_offs, n_reads, blk_sum);
-    hipLaunchKernelGGL(fin_rec_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)blk_sum, nb, blk_off, total);
-    return (int)hipGetLastError();
+    return fin_launch_blk_scan(blk_sum, nb, blk_off, total, stream);
 }
 extern "C" int fin_launch_rec_compact(void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, const uint64_t* blk_off, void* stream_out, hipStream_t stream) {
     const uint32_t nb = fin_rec_blocks(n_reads);

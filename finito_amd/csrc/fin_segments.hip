@@ -8,24 +8,20 @@
 // a single slot).  Offsets 5,6,5,6,5 in one unitig give [5,6] [5] [6] [5].  This is NOT fin_cover_rec_kernel's run rule (that one merges greedily, a bitmap
 // does not care where a run is cut).
 //
-// What is read.  Where the step left records (kernel 4, merged strands, fast path on, text mode 1 or 2), a lane per read:
-//   kind 1 -- the 32-byte record alone: the found strand slots are [0, nk) minus at most eight gaps, worked out exactly as fin_expand_records does (clamping to
-//             [0, nk - 1], a gap never starts below the end of its predecessor): at most nine stretches, each one segment.  A read found on its reverse strand
-//             (meta bit 8) has output slot i = strand slot nk - 1 - i: its stretches come out in reverse order, `off` at the stretch's highest offset, len < 0.
-//             The read's pairs are never touched -- in text mode 2 they do not exist.
-//   kind 2 -- nothing.
-//   kind 0 -- the wave scans the read's pairs through out_offs, a row of 64 slots at a time (the next row's load is issued before this row is worked on): links from neighbour compares, heads from the rule, a ballot.  The
-//             two-slot history (the last slot of the row before, and its link) is carried across rows in wave-uniform registers.  A head lane writes its
-//             segment; a segment still open at a row's end gets its u, off and slot from its head lane and its length from the row that closes it, so every
-//             byte is written once.
-// Where the step left no records (forward-only search, kernels 0 / 2 / 3, fast path off, k > 63, text mode 0) every read is scanned as a kind-0 read.
+// What is read (the frame is fin_wave.h's).  Where the step left records, a lane per read:
+//   kind 1 -- at most nine found stretches (sgm_rec_walk), each one segment.  A read found on its reverse strand (meta bit 8) has output slot i = strand slot
+//             nk - 1 - i: its stretches come out in reverse order, `off` at the stretch's highest offset, len < 0.
+//   kind 0 -- the wave scans the read's pairs, a row of 64 slots at a time, the next row loaded ahead: links from neighbour compares, heads from the rule
+//             (fin_seg_head), a ballot.  The two-slot history (the last slot of the row before, and its link) is carried across rows in wave-uniform registers.
+//             A head lane writes its segment; a segment still open at a row's end gets its u, off and slot from its head lane and its length from the row that
+//             closes it, so every byte is written once.
 //
-// Three steps, because the output is dense: (1) fin_sgm_kernel<false> counts per read (cnt[r]) and per block of 256 reads; (2) fin_sgm_scan_kernel, one block,
-// makes the blocks' exclusive prefix and the total in uint64; (3) fin_sgm_kernel<true> scans its block's counts, writes seg_offs and the segments.  The kind-0
+// Three steps, because the output is dense: (1) fin_sgm_kernel<false> counts per read (cnt[r]) and per block of 256 reads; (2) the one-block scan
+// (fin_launch_blk_scan, fin_records.hip) makes the blocks' exclusive prefix and the total in uint64; (3) fin_sgm_kernel<true> scans its block's counts, writes seg_offs and the segments.  The kind-0
 // pairs are read twice.  Records, pairs and text are read only; plain vector stores only.
 #include "fin_device.h"
 #include "fin_kernels.h"
-#include "fin_rec_walk.h"
+#include "fin_wave.h"
 
 #define FIN_SGM_BLK 256u   // reads per block: a lane per read
 
@@ -37,29 +33,17 @@ typedef unsigned long long ull;
 template <bool WRITE>
 __device__ __forceinline__ uint32_t sgm_scan(const int2* pairs, uint64_t lo, uint64_t hi, uint4* out) {
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t pu = 0xFFFFFFFFu, poff = 0u;   // the last slot of the row before (0xFFFFFFFF: absent, or there is none)
-    int plink = 0;                          // and its link
+    FinSegCarry carry;
     uint32_t cnt = 0;
     bool open = false;                      // a segment reached the end of the row before: its ordinal, its slots so far, its direction (0: not known yet)
     uint32_t open_idx = 0, open_len = 0;
     int open_dir = 0;
-    int2 pn = make_int2(-1, -1);            // the row to come, loaded a row ahead: two loads in flight, the compares of one row hide the other's latency
-    if (lo + lane < hi) pn = pairs[lo + lane];
-    for (uint64_t base = lo; base < hi; base += 64u) {
-        const uint64_t j = base + lane;
+    fin_each_pair_row(pairs, lo, hi, [&](uint64_t base, uint64_t j, int2 p) {
         const bool last_row = base + 64u >= hi;
-        const int2 p = pn;                  // (-1,-1) in a lane beyond the read's end
-        pn = make_int2(-1, -1);
-        if (j + 64u < hi) pn = pairs[j + 64u];
         const uint32_t u = (uint32_t)p.x, off = (uint32_t)p.y;
         const bool found = u != 0xFFFFFFFFu;   // (an inactive lane holds (-1,-1))
-        uint32_t up = (uint32_t)__shfl_up((int)u, 1), offp = (uint32_t)__shfl_up((int)off, 1);
-        if (lane == 0u) { up = pu; offp = poff; }
-        int link = 0;
-        if (found && u == up) link = off == offp + 1u ? 1 : off + 1u == offp ? -1 : 0;   // (u == up and found: the slot before is found too)
-        int linkp = __shfl_up(link, 1);
-        if (lane == 0u) linkp = plink;
-        const bool head = found && (link == 0 || (linkp != 0 && linkp != link));
+        int link;
+        const bool head = fin_seg_head(u, off, found, carry, link);
         const ull H = __ballot(head);
         if (WRITE) {
             const ull B = __ballot(head || !found);   // where a segment ends: the next head, the next absent slot, the read's end
@@ -93,9 +77,8 @@ __device__ __forceinline__ uint32_t sgm_scan(const int2* pairs, uint64_t lo, uin
             }
         }
         cnt += (uint32_t)__popcll(H);
-        pu = (uint32_t)__builtin_amdgcn_readlane((int)u, 63); poff = (uint32_t)__builtin_amdgcn_readlane((int)off, 63);
-        plink = __builtin_amdgcn_readlane(link, 63);
-    }
+        fin_seg_next_row(carry, u, off, link);
+    });
     return cnt;
 }
 }  // namespace
@@ -107,35 +90,18 @@ template <bool WRITE>
 __global__ __launch_bounds__(256) void fin_sgm_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k, uint32_t* cnt,
                                                       uint32_t* blk_sum, const uint64_t* blk_off, uint64_t* seg_offs, uint4* segs) {
     __shared__ uint32_t lds_w[4];
-    const uint32_t r = blockIdx.x * FIN_SGM_BLK + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t kind = 2u;
-    uint64_t p_lo = 0, p_hi = 0;
-    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
-    if (r < n_reads) {
-        kind = 0u;
-        if (frec) {
-            a = ((const uint4*)(frec + r))[0];   // u, off0, meta, nk
-            kind = a.z >> 16;
-            if (kind == 1u) b = ((const uint4*)(frec + r))[1];
-        }
-        if (kind == 0u) { p_lo = out_offs[r]; p_hi = out_offs[r + 1]; }
-    }
+    const uint32_t r = blockIdx.x * FIN_SGM_BLK + threadIdx.x;
+    const FinReadItem it = fin_read_item<true>(frec, out_offs, r, n_reads);
     uint32_t mine = 0;
     uint64_t at = 0;   // WRITE: where this read's segments begin
     if (WRITE) {
         if (r < n_reads) mine = cnt[r];
-        uint32_t inc = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)inc, d); if ((int)lane >= d) inc += y; }
-        if (lane == 63u) lds_w[wave] = inc;
-        __syncthreads();
-        uint32_t before = 0;
-        for (uint32_t w = 0; w < wave; w++) before += lds_w[w];
-        at = blk_off[blockIdx.x] + before + inc - mine;
+        at = blk_off[blockIdx.x] + fin_block_exclusive4(mine, lds_w, nullptr);
         if (r < n_reads) seg_offs[r] = at;
         if (r == n_reads - 1u) seg_offs[n_reads] = at + mine;
     }
-    if (kind == 1u && a.w != 0u) {
+    if (it.kind == 1u && it.a.w != 0u) {
+        const uint4 a = it.a, b = it.b;
         if (WRITE) {
             const bool rev = (a.z >> 8) & 1u;
             uint4* const out = segs + at;
@@ -146,49 +112,17 @@ __global__ __launch_bounds__(256) void fin_sgm_kernel(const FinFastRec* frec, co
             });
         } else mine = sgm_rec_walk(a, b, k, [](uint32_t, uint32_t, uint32_t) {});
     }
-    // ---- the searched reads' pairs: the wave takes its lanes' reads one after the other ----
-    ull todo = __ballot(kind == 0u && p_hi > p_lo);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1ull;
-        const uint32_t c = sgm_scan<WRITE>(pairs, fin_bcast64(p_lo, src), fin_bcast64(p_hi, src), segs + fin_bcast64(at, src));
-        if (!WRITE && (int)lane == src) mine = c;
-    }
+    fin_each_searched_read(it, [&](int src, uint64_t lo, uint64_t hi) {
+        const uint32_t c = sgm_scan<WRITE>(pairs, lo, hi, segs + fin_bcast64(at, src));
+        if (!WRITE && (int)(threadIdx.x & 63u) == src) mine = c;
+    });
     if (!WRITE) {
         if (r < n_reads) cnt[r] = mine;
-        uint32_t s = mine;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += (uint32_t)__shfl_xor((int)s, d);
-        if (lane == 0u) lds_w[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) blk_sum[blockIdx.x] = lds_w[0] + lds_w[1] + lds_w[2] + lds_w[3];
+        const uint32_t s = fin_block_sum4(mine, lds_w);
+        if (threadIdx.x == 0) blk_sum[blockIdx.x] = s;
     }
 }
 
-// exclusive prefix of the block sums (one block: fin_rec_scan_kernel's pattern) and the total, both uint64 -- a batch's k-mers may number more than 2^32
-__global__ __launch_bounds__(1024) void fin_sgm_scan_kernel(const uint32_t* blk_sum, uint32_t n_blk, uint64_t* blk_off, uint64_t* total) {
-    __shared__ uint64_t lds[1024];
-    const uint32_t per = (n_blk + 1023u) / 1024u, b0 = threadIdx.x * per;
-    uint64_t s = 0;
-    for (uint32_t i = 0; i < per; i++) if (b0 + i < n_blk) s += blk_sum[b0 + i];
-    lds[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const uint64_t y = threadIdx.x >= d ? lds[threadIdx.x - d] : 0ull;
-        __syncthreads();
-        lds[threadIdx.x] += y;
-        __syncthreads();
-    }
-    uint64_t at = lds[threadIdx.x] - s;
-    for (uint32_t i = 0; i < per; i++) if (b0 + i < n_blk) { blk_off[b0 + i] = at; at += blk_sum[b0 + i]; }
-    if (threadIdx.x == 1023u) *total = lds[1023];
-}
-
-// the scan by itself, for the other dense outputs made from per-block counts (fin_readsum.hip: the screen's ids).  n_blk > 0
-extern "C" int fin_launch_blk_scan(const uint32_t* blk_sum, uint32_t n_blk, uint64_t* blk_off, uint64_t* total, hipStream_t stream) {
-    hipLaunchKernelGGL(fin_sgm_scan_kernel, dim3(1), dim3(1024), 0, stream, blk_sum, n_blk, blk_off, total);
-    return (int)hipGetLastError();
-}
 extern "C" uint32_t fin_sgm_blocks(uint32_t n_reads) { return (n_reads + FIN_SGM_BLK - 1u) / FIN_SGM_BLK; }
 // cnt: n_reads u32; blk_sum: fin_sgm_blocks() u32; blk_off: as many u64; total: one u64 (the batch's segments).  The counting pass and the scan.  n_reads > 0
 extern "C" int fin_launch_sgm_count(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, uint32_t* cnt, uint32_t* blk_sum,
@@ -197,8 +131,7 @@ extern "C" int fin_launch_sgm_count(const void* frec, const uint64_t* out_offs, 
     if (nb == 0) return (int)hipMemsetAsync(total, 0, 8, stream);
     hipLaunchKernelGGL(fin_sgm_kernel<false>, dim3(nb), dim3(256), 0, stream, (const FinFastRec*)frec, out_offs, (const int2*)pairs, n_reads, k, cnt, blk_sum,
                        (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint4*)nullptr);
-    hipLaunchKernelGGL(fin_sgm_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)blk_sum, nb, blk_off, total);
-    return (int)hipGetLastError();
+    return fin_launch_blk_scan(blk_sum, nb, blk_off, total, stream);
 }
 // seg_offs: n_reads + 1 u64; segs: room for *total segments of 16 bytes
 extern "C" int fin_launch_sgm_write(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const uint32_t* cnt,
