@@ -356,8 +356,7 @@ class Batch:
         self.n_reads = len(offsets) - 1
         h = C.c_void_p()
         err = C.create_string_buffer(512)
-        _check(self.L.fin_batch_create(index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                       self.n_reads, C.byref(h), err, 512), err)
+        _check(self.L.fin_batch_create(index.h, *_reads_args((bases, offsets)), C.byref(h), err, 512), err)
         self.h = h
         self._keep = None   # the reads live in HBM now
 
@@ -365,8 +364,7 @@ class Batch:
         """Replace the reads of this batch, keeping its device buffers (fin_batch_reload)."""
         bases, offsets = flatten(reads)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_batch_reload(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                       len(offsets) - 1, err, 512), err)
+        _check(self.L.fin_batch_reload(self.h, *_reads_args((bases, offsets)), err, 512), err)
         self.n_reads = len(offsets) - 1
 
     @property
@@ -601,39 +599,75 @@ class Batch:
             pass
 
 
-class Hits:
+def _reads_args(reads):
+    """(bases pointer, offsets pointer, n_reads): a read set as the C ABI takes it, `reads` as flatten takes them; the pointers keep their arrays alive"""
+    bases, offsets = flatten(reads)
+    return bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1
+
+
+def _acc_add(acc, fn, batch, stream, *args):
+    """the plumbing of every accumulator's add: the batch's most recent run into `acc` by the C function `fn`, on a HIP stream"""
+    err = C.create_string_buffer(512)
+    _check(getattr(acc.L, fn)(batch.h, acc.h, *args, C.c_void_p(stream or 0), err, 512), err)
+    return acc
+
+
+def _acc_add_reads(acc, fn, reads, strands, *args):
+    """... and of every add_reads: a read set from host buffers through the pipeline of acc.index, into `acc` (anything with index, h and L: the C side checks
+    that they belong together)"""
+    err = C.create_string_buffer(512)
+    _check(getattr(acc.L, fn)(acc.index.h, *_reads_args(reads), int(strands), acc.h, *args, err, 512), err)
+    return acc
+
+
+class _Accumulator:
+    """what the device accumulators share: the handle's life and reset.  A subclass names its C functions; self.index is the index it lives beside"""
+    _FREE = _RESET = None
+
+    def _create(self, fn, *args):
+        self.L = lib()
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        _check(getattr(self.L, fn)(*args, C.byref(h), err, 512), err)
+        self.h = h
+
+    def reset(self, stream=None):
+        """zero what was accumulated (a labelling itself stays), on a HIP stream, behind the adds issued so far"""
+        rc = getattr(self.L, self._RESET)(self.h, C.c_void_p(stream or 0))
+        if rc != 0:
+            raise FinitoError(rc, self._RESET)
+        return self
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.L, self._FREE)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Hits(_Accumulator):
     """uint64 found-k-mer counts per unitig, resident in HBM beside one replica of the index (fin_hits_* of the C ABI): the profile of
     everything that was added, however many reads that was.  Unitig numbers are the index's own, the numbers the pairs carry."""
+    _FREE, _RESET = "fin_hits_free", "fin_hits_reset"
 
     def __init__(self, index, device=0):
         self.index = index
-        self.L = lib()
         self.n_unitigs = index.n_unitigs
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_hits_create(index.h, int(device), C.byref(h), err, 512), err)
-        self.h = h
+        self._create("fin_hits_create", index.h, int(device))
 
     def add(self, batch, stream=None):
         """counts += the hits of the batch's most recent run, on a HIP stream, behind that run; no sync (fin_batch_add_hits).  Adding the
         same run twice counts it twice."""
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_batch_add_hits(batch.h, self.h, C.c_void_p(stream or 0), err, 512), err)
-        return self
+        return _acc_add(self, "fin_batch_add_hits", batch, stream)
 
     def add_reads(self, reads, strands=FIN_MERGED):
         """search a read set from host buffers, sub-batches pipelined as in search_reads, and add its hits; nothing comes back (fin_search_batch_add_hits)"""
-        bases, offsets = flatten(reads)
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_add_hits(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
-                                                int(strands), self.h, err, 512), err)
-        return self
-
-    def reset(self, stream=None):
-        rc = self.L.fin_hits_reset(self.h, C.c_void_p(stream or 0))
-        if rc != 0:
-            raise FinitoError(rc, "fin_hits_reset")
-        return self
+        return _acc_add_reads(self, "fin_search_batch_add_hits", reads, strands)
 
     def download(self):
         """(uint64 counts[n_unitigs], their sum = the k-mers found); waits for the adds (fin_hits_download)"""
@@ -646,17 +680,6 @@ class Hits:
     def device_ptr(self):
         return int(self.L.fin_hits_device_counts(self.h) or 0)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fin_hits_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _class_thresholds(what, min_found, min_permille, min_margin):
     if not all(0 <= int(v) <= 0xFFFFFFFF for v in (min_found, min_permille, min_margin)):
@@ -664,13 +687,13 @@ def _class_thresholds(what, min_found, min_permille, min_margin):
     return int(min_found), int(min_permille), int(min_margin)
 
 
-class Labels:
+class Labels(_Accumulator):
     """a labelling of the index's unitigs (uint32 per unitig: a label below n_labels, or FIN_NO_LABEL) resident in HBM beside one replica, with the tally of the
     reads assigned to each label (fin_labels_* of the C ABI).  Unitig numbers are the index's own (FinimizerIndex.unitig_numbers maps an input order to them)."""
+    _FREE, _RESET = "fin_labels_free", "fin_labels_reset"
 
     def __init__(self, index, unitig_labels, n_labels=None, device=0):
         self.index = index
-        self.L = lib()
         lab = np.asarray(unitig_labels)
         if lab.ndim != 1 or len(lab) != index.n_unitigs:
             raise FinitoError(FIN_EINVAL, "labels: one label per unitig of the index (%d), got %s" % (index.n_unitigs, lab.shape))
@@ -683,34 +706,18 @@ class Labels:
         if not 0 <= int(n_labels) <= 0xFFFFFFFF:
             raise FinitoError(FIN_EINVAL, "labels: n_labels is 1 .. 2^31")
         self.n_labels = int(n_labels)
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_labels_create(index.h, int(device), lab.ctypes.data_as(C.c_void_p), self.n_labels, C.byref(h), err, 512), err)
-        self.h = h
+        self._create("fin_labels_create", index.h, int(device), lab.ctypes.data_as(C.c_void_p), self.n_labels)
 
     def add(self, batch, min_found=1, min_permille=0, min_margin=0, stream=None):
         """tally += the reads of the batch's most recent run: a read goes to its class's label when n_best >= max(min_found, 1), 1000 * n_best >= min_permille * nk
         and n_best >= n_second + min_margin, else to `unassigned`; on a HIP stream, behind that run, no sync (fin_batch_add_classes).  Adding twice counts twice."""
         t = _class_thresholds("Labels.add", min_found, min_permille, min_margin)
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_batch_add_classes(batch.h, self.h, t[0], t[1], t[2], C.c_void_p(stream or 0), err, 512), err)
-        return self
+        return _acc_add(self, "fin_batch_add_classes", batch, stream, *t)
 
     def add_reads(self, reads, min_found=1, min_permille=0, min_margin=0, strands=FIN_MERGED):
         """search a read set from host buffers, sub-batches pipelined as in search_reads, and tally its reads; nothing comes back (fin_search_batch_add_classes)"""
         t = _class_thresholds("Labels.add_reads", min_found, min_permille, min_margin)
-        bases, offsets = flatten(reads)
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_add_classes(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
-                                                   int(strands), self.h, t[0], t[1], t[2], err, 512), err)
-        return self
-
-    def reset(self, stream=None):
-        """zero the tally; the labelling stays"""
-        rc = self.L.fin_labels_reset(self.h, C.c_void_p(stream or 0))
-        if rc != 0:
-            raise FinitoError(rc, "fin_labels_reset")
-        return self
+        return _acc_add_reads(self, "fin_search_batch_add_classes", reads, strands, *t)
 
     def download(self):
         """(uint64 reads[n_labels + 1] -- the reads assigned to each label, then the unassigned ones --, their sum = the reads added); waits for the adds
@@ -725,17 +732,6 @@ class Labels:
         """(labels uint32[n_unitigs], reads uint64[n_labels + 1]) device pointers"""
         return int(self.L.fin_labels_device_labels(self.h) or 0), int(self.L.fin_labels_device_reads(self.h) or 0)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fin_labels_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _permille(what, permille):
     if not 0 <= int(permille) <= 0xFFFFFFFF:
@@ -743,23 +739,20 @@ def _permille(what, permille):
     return int(permille)
 
 
-class Colors:
+class Colors(_Accumulator):
     """the colour set of every unitig of the index -- which of n_colors references it occurs in -- as a bit matrix uint64[n_unitigs, W], W = ceil(n_colors / 64),
     resident in HBM beside one replica (fin_colors_* of the C ABI): colour c of unitig u is bit c & 63 of bits[u, c >> 6].  1 <= n_colors <= 4096.  Unitig numbers
     are the index's own."""
+    _FREE, _RESET = "fin_colors_free", "fin_colors_reset"
 
     def __init__(self, index, n_colors, device=0):
         self.index = index
-        self.L = lib()
         self.n_unitigs = index.n_unitigs
         if not 0 <= int(n_colors) <= 0xFFFFFFFF:
             raise FinitoError(FIN_ELIMIT, "colors: n_colors is 1 .. 4096")
         self.n_colors = int(n_colors)
         self.words = (self.n_colors + 63) // 64
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_colors_create(index.h, int(device), self.n_colors, C.byref(h), err, 512), err)
-        self.h = h
+        self._create("fin_colors_create", index.h, int(device), self.n_colors)
 
     def upload(self, bits):
         """replace the matrix: uint64[n_unitigs, W]; a set bit at or above n_colors is refused (fin_colors_upload)"""
@@ -774,30 +767,18 @@ class Colors:
     def add(self, batch, color, stream=None):
         """every unitig in which the batch's most recent run found a k-mer gets `color`, on a HIP stream, behind that run; no sync (fin_batch_add_colors).
         Adding twice changes nothing."""
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_batch_add_colors(batch.h, self.h, self._color(color), C.c_void_p(stream or 0), err, 512), err)
-        return self
+        return _acc_add(self, "fin_batch_add_colors", batch, stream, self._color(color))
 
     def add_reads(self, reads, color, strands=FIN_MERGED):
         """search a sequence set (a reference genome's) from host buffers, sub-batches pipelined as in search_reads, and give `color` to every unitig it is
         found in; nothing comes back (fin_search_batch_add_colors)"""
-        bases, offsets = flatten(reads)
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_add_colors(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
-                                                  int(strands), self.h, self._color(color), err, 512), err)
-        return self
+        bases_offsets = flatten(reads)
+        return _acc_add_reads(self, "fin_search_batch_add_colors", bases_offsets, strands, self._color(color))
 
     def _color(self, color):
         if not 0 <= int(color) < self.n_colors:
             raise FinitoError(FIN_EINVAL, "colors: colour %r is not in 0 .. %d" % (color, self.n_colors - 1))
         return int(color)
-
-    def reset(self, stream=None):
-        """zero the matrix"""
-        rc = self.L.fin_colors_reset(self.h, C.c_void_p(stream or 0))
-        if rc != 0:
-            raise FinitoError(rc, "fin_colors_reset")
-        return self
 
     def download(self):
         """(uint64 bits[n_unitigs, W], the number of set bits); waits for the adds (fin_colors_download)"""
@@ -814,51 +795,32 @@ class Colors:
         """an accumulator of equivalence classes beside this matrix (EqClasses)"""
         return EqClasses(self, max_classes)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fin_colors_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class EqClasses:
+class EqClasses(_Accumulator):
     """the equivalence classes of pseudoaligned reads -- the distinct colour rows the added runs produced and how many reads have each --, accumulated in HBM
     beside a colour matrix (fin_eqclasses_* of the C ABI).  An all-zero row is an unaligned read and belongs to no class.  At most max_classes (1 .. 2^26)
     distinct rows; free it before the colours."""
+    _FREE, _RESET = "fin_eqclasses_free", "fin_eqclasses_reset"
 
     def __init__(self, colors, max_classes=1 << 20):
         self.colors = colors
         self.index = colors.index
-        self.L = lib()
         self.n_colors = colors.n_colors
         self.words = colors.words
         if not 0 <= int(max_classes) <= 0xFFFFFFFFFFFFFFFF:
             raise FinitoError(FIN_ELIMIT, "eqclasses: max_classes is 1 .. 2^26")
         self.max_classes = int(max_classes)
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_eqclasses_create(colors.h, self.max_classes, C.byref(h), err, 512), err)
-        self.h = h
+        self._create("fin_eqclasses_create", colors.h, self.max_classes)
 
     def add(self, batch, permille=1000, stream=None):
         """the batch's most recent run, pseudoaligned against the colours at `permille` and added, on a HIP stream; no sync (fin_batch_add_eqclasses).  Adding
         twice counts twice."""
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_batch_add_eqclasses(batch.h, self.h, _permille("EqClasses.add", permille), C.c_void_p(stream or 0), err, 512), err)
-        return self
+        return _acc_add(self, "fin_batch_add_eqclasses", batch, stream, _permille("EqClasses.add", permille))
 
     def add_pairs(self, batch, permille=1000, both=False, stream=None):
         """the batch's most recent run as interleaved mates: one row per FRAGMENT, made by Batch.pseudoalign_pairs' kernel and added, on a HIP stream; no sync
         (fin_batch_add_eqclasses_paired).  A fragment is one "read" of its class"""
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_batch_add_eqclasses_paired(batch.h, self.h, _permille("EqClasses.add_pairs", permille), FIN_PAIR_BOTH if both else FIN_PAIR_ANY,
-                                                     C.c_void_p(stream or 0), err, 512), err)
-        return self
+        return _acc_add(self, "fin_batch_add_eqclasses_paired", batch, stream, _permille("EqClasses.add_pairs", permille), FIN_PAIR_BOTH if both else FIN_PAIR_ANY)
 
     def add_rows(self, ptr, n_rows, stream=None):
         """rows any producer left in HBM: a device pointer to uint64[n_rows, W], valid until the add has finished (fin_eqclasses_add_rows)"""
@@ -871,27 +833,14 @@ class EqClasses:
     def add_reads(self, reads, permille=1000, strands=FIN_MERGED):
         """search a read set from host buffers, sub-batches pipelined as in search_reads, and add every read's row; nothing comes back
         (fin_search_batch_add_eqclasses)"""
-        bases, offsets = flatten(reads)
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_add_eqclasses(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
-                                                     int(strands), self.h, _permille("EqClasses.add_reads", permille), err, 512), err)
-        return self
+        bases_offsets = flatten(reads)
+        return _acc_add_reads(self, "fin_search_batch_add_eqclasses", bases_offsets, strands, _permille("EqClasses.add_reads", permille))
 
     def add_read_pairs(self, reads, permille=1000, both=False, strands=FIN_MERGED):
         """add_reads for interleaved mates: every fragment's row is added; no sub-batch splits a pair (fin_search_batch_add_eqclasses_paired)"""
-        bases, offsets = flatten(reads)
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_add_eqclasses_paired(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                            len(offsets) - 1, int(strands), self.h, _permille("EqClasses.add_read_pairs", permille),
-                                                            FIN_PAIR_BOTH if both else FIN_PAIR_ANY, err, 512), err)
-        return self
-
-    def reset(self, stream=None):
-        """empty the accumulator and clear its flags"""
-        rc = self.L.fin_eqclasses_reset(self.h, C.c_void_p(stream or 0))
-        if rc != 0:
-            raise FinitoError(rc, "fin_eqclasses_reset")
-        return self
+        bases_offsets = flatten(reads)
+        return _acc_add_reads(self, "fin_search_batch_add_eqclasses_paired", bases_offsets, strands, _permille("EqClasses.add_read_pairs", permille),
+                              FIN_PAIR_BOTH if both else FIN_PAIR_ANY)
 
     def download(self):
         """(rows uint64[n, W], reads uint64[n], n_unaligned) in canonical order -- np.unique(rows, axis=0)'s; waits for the adds (fin_eqclasses_download)"""
@@ -951,17 +900,6 @@ class EqClasses:
         err = C.create_string_buffer(512)
         _check(self.L.fin_eqclasses_stats(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), err, 512), err)
         return [int(v) for v in out]
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fin_eqclasses_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Abundance:
@@ -1055,40 +993,25 @@ def _abundance_trace(what, trace, max_iters):
     return trace
 
 
-class Cover:
+class Cover(_Accumulator):
     """one bit per base of the concatenated unitig text, resident in HBM beside one replica of the index (fin_cover_* of the C ABI): bit start(u) + off is set
     iff a found pair (u, off) was added -- which k-mers of each unitig were seen, where Hits says how often the unitig was hit."""
+    _FREE, _RESET = "fin_cover_free", "fin_cover_reset"
 
     def __init__(self, index, device=0):
         self.index = index
-        self.L = lib()
         self.n_unitigs = index.n_unitigs
         self.n_words = (index.total_len + 63) // 64
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_cover_create(index.h, int(device), C.byref(h), err, 512), err)
-        self.h = h
+        self._create("fin_cover_create", index.h, int(device))
 
     def add(self, batch, stream=None):
         """bits |= the found places of the batch's most recent run, on a HIP stream, behind that run; no sync (fin_batch_add_cover).  Adding the same run
         twice changes nothing."""
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_batch_add_cover(batch.h, self.h, C.c_void_p(stream or 0), err, 512), err)
-        return self
+        return _acc_add(self, "fin_batch_add_cover", batch, stream)
 
     def add_reads(self, reads, strands=FIN_MERGED):
         """search a read set from host buffers, sub-batches pipelined as in search_reads, and set its places; nothing comes back (fin_search_batch_add_cover)"""
-        bases, offsets = flatten(reads)
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_add_cover(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
-                                                 int(strands), self.h, err, 512), err)
-        return self
-
-    def reset(self, stream=None):
-        rc = self.L.fin_cover_reset(self.h, C.c_void_p(stream or 0))
-        if rc != 0:
-            raise FinitoError(rc, "fin_cover_reset")
-        return self
+        return _acc_add_reads(self, "fin_search_batch_add_cover", reads, strands)
 
     def download(self):
         """(uint64 bits[(total_len + 63) // 64], uint64 covered[n_unitigs], their sum = the distinct k-mers found); waits for the adds (fin_cover_download)"""
@@ -1102,52 +1025,26 @@ class Cover:
     def device_ptr(self):
         return int(self.L.fin_cover_device_bits(self.h) or 0)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fin_cover_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Depth:
+class Depth(_Accumulator):
     """how many times each position of the concatenated unitig text was found, resident in HBM beside one replica of the index as a difference array
     (fin_depth_* of the C ABI): between Hits (the depth summed over a unitig) and Cover (where it is above zero)."""
+    _FREE, _RESET = "fin_depth_free", "fin_depth_reset"
 
     def __init__(self, index, device=0):
         self.index = index
-        self.L = lib()
         self.n_unitigs = index.n_unitigs
         self.total_len = index.total_len
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_depth_create(index.h, int(device), C.byref(h), err, 512), err)
-        self.h = h
+        self._create("fin_depth_create", index.h, int(device))
 
     def add(self, batch, stream=None):
         """depth += the found places of the batch's most recent run, on a HIP stream, behind that run; no sync (fin_batch_add_depth).  Adding the same run
         twice counts it twice."""
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_batch_add_depth(batch.h, self.h, C.c_void_p(stream or 0), err, 512), err)
-        return self
+        return _acc_add(self, "fin_batch_add_depth", batch, stream)
 
     def add_reads(self, reads, strands=FIN_MERGED):
         """search a read set from host buffers, sub-batches pipelined as in search_reads, and add its places; nothing comes back (fin_search_batch_add_depth)"""
-        bases, offsets = flatten(reads)
-        err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_add_depth(self.index.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
-                                                 int(strands), self.h, err, 512), err)
-        return self
-
-    def reset(self, stream=None):
-        rc = self.L.fin_depth_reset(self.h, C.c_void_p(stream or 0))
-        if rc != 0:
-            raise FinitoError(rc, "fin_depth_reset")
-        return self
+        return _acc_add_reads(self, "fin_search_batch_add_depth", reads, strands)
 
     def download(self, min_depth=1, want_positions=True):
         """(uint32 depth[total_len] -- None without want_positions --, DEPTH_STAT_DTYPE stats[n_unitigs] with n_at_least counted against min_depth, the sum over
@@ -1163,17 +1060,6 @@ class Depth:
     def device_ptr(self):
         return int(self.L.fin_depth_device_diff(self.h) or 0)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fin_depth_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class FinimizerIndex:
     """Mirror of the reference class (FinimizerIndex.hh:26-259) backed by the HIP path."""
@@ -1187,11 +1073,9 @@ class FinimizerIndex:
     def build(cls, unitigs, k, n_threads=0):
         """FinimizerIndexBuilder (FinimizerIndex.hh:262-395) + `sbwt build` + LCS, in one call."""
         L = lib()
-        bases, offsets = flatten(unitigs)
         h = C.c_void_p()
         err = C.create_string_buffer(512)
-        _check(L.fin_index_build(bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                 len(offsets) - 1, int(k), int(n_threads) if n_threads > 0 else host_threads(), C.byref(h), err, 512), err)
+        _check(L.fin_index_build(*_reads_args(unitigs), int(k), int(n_threads) if n_threads > 0 else host_threads(), C.byref(h), err, 512), err)
         return cls(h)
 
     @classmethod
@@ -1199,12 +1083,11 @@ class FinimizerIndex:
         """the same index built on a HIP device (fin_index_build_device; every k <= 255): bit-identical to build()'s.  The stages' device
         times in milliseconds are left in .build_phase_ms"""
         L = lib()
-        bases, offsets = flatten(unitigs)
         h = C.c_void_p()
         err = C.create_string_buffer(512)
         ph = (C.c_double * 8)()
         L.fin_index_build_device.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
-        _check(L.fin_index_build_device(bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1, int(k), int(device),
+        _check(L.fin_index_build_device(*_reads_args(unitigs), int(k), int(device),
                                         C.byref(h), ph, err, 512), err)
         x = cls(h)
         x.build_phase_ms = dict(zip(("upload_kmers", "sort_unique", "dummies", "sbwt", "unitigs", "finimizers", "dictionaries", "copy_back"), (float(v) for v in ph)))
@@ -1252,11 +1135,9 @@ class FinimizerIndex:
 
     def finimizer_stats(self, seqs, kind="shortest", t=1):
         """build-fmin --type shortest / verify (build_fmin.hh:95-214): (distinct finimizers, sum of frequencies, sum of lengths)."""
-        bases, offsets = flatten(seqs)
         n, sf, sl = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_index_finimizer_stats(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                len(offsets) - 1, 1 if kind == "shortest" else 2, int(t), C.byref(n), C.byref(sf), C.byref(sl), err, 512), err)
+        _check(self.L.fin_index_finimizer_stats(self.h, *_reads_args(seqs), 1 if kind == "shortest" else 2, int(t), C.byref(n), C.byref(sf), C.byref(sl), err, 512), err)
         return int(n.value), int(sf.value), int(sl.value)
 
     def prefix_table_depth(self, device=0):
@@ -1432,8 +1313,7 @@ class FinimizerIndex:
         assert out.dtype == np.int32 and out.flags["C_CONTIGUOUS"] and out.shape[0] >= max(nk, 1)
         npos = C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                       len(lens), int(strands), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(npos), err, 512), err)
+        _check(self.L.fin_search_batch(self.h, *_reads_args((bases, offsets)), int(strands), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(npos), err, 512), err)
         return out[:nk], int(npos.value)
 
     def search_reads_records(self, reads):
@@ -1447,7 +1327,7 @@ class FinimizerIndex:
         got = C.c_uint64(0)
         err = C.create_string_buffer(512)
         self.L.fin_search_batch_records.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
-        _check(self.L.fin_search_batch_records(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+        _check(self.L.fin_search_batch_records(self.h, *_reads_args((bases, offsets)),
                                                recs.ctypes.data_as(C.c_void_p), stream.ctypes.data_as(C.c_void_p), nk, C.byref(got), err, 512), err)
         return recs, stream[: int(got.value)]
 
@@ -1461,7 +1341,7 @@ class FinimizerIndex:
         segs = np.zeros(max(nk, 1), dtype=SEGMENT_DTYPE)
         got, npos = C.c_uint64(0), C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_segments(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands),
+        _check(self.L.fin_search_batch_segments(self.h, *_reads_args((bases, offsets)), int(strands),
                                                 seg_offs.ctypes.data_as(C.POINTER(C.c_uint64)), segs.ctypes.data_as(C.c_void_p), nk, C.byref(got), C.byref(npos), err, 512), err)
         return seg_offs, segs[: int(got.value)].copy(), int(npos.value)
 
@@ -1472,7 +1352,7 @@ class FinimizerIndex:
         out = np.zeros(max(n, 1), dtype=READ_SUMMARY_DTYPE)
         npos = C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_read_summaries(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands),
+        _check(self.L.fin_search_batch_read_summaries(self.h, *_reads_args((bases, offsets)), int(strands),
                                                       out.ctypes.data_as(C.c_void_p), C.byref(npos), err, 512), err)
         return out[:n], int(npos.value)
 
@@ -1486,7 +1366,7 @@ class FinimizerIndex:
         bits = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
         n_pass = C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_screen(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands),
+        _check(self.L.fin_search_batch_screen(self.h, *_reads_args((bases, offsets)), int(strands),
                                               int(min_found), int(min_permille), 1 if invert else 0, bits.ctypes.data_as(C.POINTER(C.c_uint64)),
                                               C.byref(n_pass), err, 512), err)
         out = np.unpackbits(bits.view(np.uint8), bitorder="little")[:n].astype(bool)
@@ -1504,7 +1384,7 @@ class FinimizerIndex:
         n = len(offsets) - 1
         out = np.zeros(max(n, 1), dtype=READ_CLASS_DTYPE)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_classify(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands), labels.h,
+        _check(self.L.fin_search_batch_classify(self.h, *_reads_args((bases, offsets)), int(strands), labels.h,
                                                 out.ctypes.data_as(C.c_void_p), None, err, 512), err)
         return out[:n]
 
@@ -1522,7 +1402,7 @@ class FinimizerIndex:
         heads = np.zeros(max(n, 1), dtype=READ_PSEUDO_DTYPE)
         npos = C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_pseudoalign(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands), colors.h,
+        _check(self.L.fin_search_batch_pseudoalign(self.h, *_reads_args((bases, offsets)), int(strands), colors.h,
                                                    _permille("pseudoalign_reads", permille), rows.ctypes.data_as(C.POINTER(C.c_uint64)) if want_rows else None,
                                                    heads.ctypes.data_as(C.c_void_p), C.byref(npos), err, 512), err)
         return (rows[:n] if want_rows else None), heads[:n], int(npos.value)
@@ -1537,7 +1417,7 @@ class FinimizerIndex:
         heads = np.zeros(max(nf, 1), dtype=PAIR_PSEUDO_DTYPE)
         npos = C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_pseudoalign_paired(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(strands),
+        _check(self.L.fin_search_batch_pseudoalign_paired(self.h, *_reads_args((bases, offsets)), int(strands),
                                                           colors.h, _permille("pseudoalign_pairs", permille), FIN_PAIR_BOTH if both else FIN_PAIR_ANY,
                                                           rows.ctypes.data_as(C.POINTER(C.c_uint64)) if want_rows else None, heads.ctypes.data_as(C.c_void_p),
                                                           C.byref(npos), err, 512), err)
@@ -1550,7 +1430,7 @@ class FinimizerIndex:
         n = len(offsets) - 1
         out = np.zeros(max(n, 1), dtype=np.uint32)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_index_unitig_numbers(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+        _check(self.L.fin_index_unitig_numbers(self.h, *_reads_args((bases, offsets)),
                                                out.ctypes.data_as(C.c_void_p), err, 512), err)
         return out[:n]
 
@@ -1561,11 +1441,10 @@ class FinimizerIndex:
     def unitig_counts(self, reads, strands=FIN_MERGED):
         """the profile of a read set over host buffers (fin_search_batch_unitig_counts): (uint64 counts[n_unitigs], total_positive) -- how many of the
         reads' k-mers were found in each unitig; only the counts come back from the device"""
-        bases, offsets = flatten(reads)
         out = np.zeros(max(self.n_unitigs, 1), dtype=np.uint64)
         npos = C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_unitig_counts(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+        _check(self.L.fin_search_batch_unitig_counts(self.h, *_reads_args(reads),
                                                      int(strands), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(npos), err, 512), err)
         return out[: self.n_unitigs], int(npos.value)
 
@@ -1576,11 +1455,10 @@ class FinimizerIndex:
     def unitig_coverage(self, reads, strands=FIN_MERGED):
         """the breadth of a read set over host buffers (fin_search_batch_unitig_coverage): (uint64 covered[n_unitigs], total_positive) -- how many DISTINCT
         k-mers of each unitig were found, and the k-mers found as search_reads reports them; only the covered numbers come back from the device"""
-        bases, offsets = flatten(reads)
         out = np.zeros(max(self.n_unitigs, 1), dtype=np.uint64)
         npos = C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_unitig_coverage(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+        _check(self.L.fin_search_batch_unitig_coverage(self.h, *_reads_args(reads),
                                                        int(strands), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(npos), err, 512), err)
         return out[: self.n_unitigs], int(npos.value)
 
@@ -1591,23 +1469,20 @@ class FinimizerIndex:
     def unitig_depth(self, reads, strands=FIN_MERGED, min_depth=1):
         """the depth of a read set over host buffers, per unitig (fin_search_batch_unitig_depth): (DEPTH_STAT_DTYPE stats[n_unitigs], total_positive) -- each
         unitig's summed and greatest depth and how many of its positions were found at least min_depth times; only the statistics come back from the device"""
-        bases, offsets = flatten(reads)
         out = np.zeros(max(self.n_unitigs, 1), dtype=DEPTH_STAT_DTYPE)
         npos = C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_search_batch_unitig_depth(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+        _check(self.L.fin_search_batch_unitig_depth(self.h, *_reads_args(reads),
                                                     int(strands), int(min_depth), out.ctypes.data_as(C.c_void_p), C.byref(npos), err, 512), err)
         return out[: self.n_unitigs], int(npos.value)
 
     def search_reads_text(self, reads, strands=FIN_MERGED):
         """run_fmin_queries_streaming with its printed text as the result (fin_search_batch_text): (bytes, total_positive)"""
-        bases, offsets = flatten(reads)
         t = self.L.fin_text_create()
         try:
             npos = C.c_uint64(0)
             err = C.create_string_buffer(512)
-            _check(self.L.fin_search_batch_text(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                len(offsets) - 1, int(strands), t, C.byref(npos), err, 512), err)
+            _check(self.L.fin_search_batch_text(self.h, *_reads_args(reads), int(strands), t, C.byref(npos), err, 512), err)
             n = int(self.L.fin_text_size(t))
             return C.string_at(self.L.fin_text_data(t), n) if n else b"", int(npos.value)
         finally:
@@ -1622,8 +1497,7 @@ class FinimizerIndex:
         npos = C.c_uint64(0)
         err = C.create_string_buffer(512)
         devs = (C.c_int * len(devices))(*devices)
-        _check(self.L.fin_search_batch_multi(self.h, devs, len(devices), bases.ctypes.data_as(C.c_char_p),
-                                             offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(lens), int(strands),
+        _check(self.L.fin_search_batch_multi(self.h, devs, len(devices), *_reads_args((bases, offsets)), int(strands),
                                              out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(npos), err, 512), err)
         return out[:nk], int(npos.value)
 
@@ -1659,9 +1533,8 @@ class PartitionedBatch:
 
     def __init__(self, pindex, reads):
         self.L = lib(); self.h = C.c_void_p(); self.pindex = pindex
-        bases, offsets = flatten(reads)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_pbatch_create(pindex.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+        _check(self.L.fin_pbatch_create(pindex.h, *_reads_args(reads),
                                         C.byref(self.h), err, 512), err)
         self.n_kmers = int(self.L.fin_pbatch_n_kmers(self.h))
 
@@ -1725,8 +1598,7 @@ class PartitionedIndex:
         if _load_prefix is not None:
             _check(L.fin_pindex_load(str(_load_prefix).encode(), int(device), C.byref(self.h), err, 1024), err)
             return
-        bases, offsets = flatten(unitigs)
-        _check(L.fin_pindex_build_device(bases.ctypes.data_as(cp), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1, int(k), int(device),
+        _check(L.fin_pindex_build_device(*_reads_args(unitigs), int(k), int(device),
                                          int(max_part_bases), 1 if verify else 0, C.byref(self.h), err, 1024), err)
 
     @classmethod
@@ -1782,7 +1654,7 @@ class PartitionedIndex:
         out = np.empty((max(nk, 1), 2), dtype=np.int32)
         npos = C.c_uint64(0)
         err = C.create_string_buffer(512)
-        _check(self.L.fin_pindex_search_batch(self.h, bases.ctypes.data_as(C.c_char_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(offsets) - 1,
+        _check(self.L.fin_pindex_search_batch(self.h, *_reads_args((bases, offsets)),
                                               out.ctypes.data_as(C.c_void_p), C.byref(npos), err, 512), err)
         return out[:nk], int(npos.value)
 

@@ -1433,16 +1433,12 @@ int fin_batch_download_screen(fin_batch* b, uint32_t* ids_out, uint64_t* bits_ou
 
 // ---- the profile over the unitig set (fin_hits.hip) ---------------------------------------------------------------------------------
 // what the download of a device accumulator (fin_hits, fin_cover, fin_depth) waits for: an event per stream that work on the accumulator was put on
+extern "C++" {   // (templates among them)
 struct AccPending {
     std::mutex mu; std::vector<std::pair<hipStream_t, hipEvent_t>> pending;
     int mark(hipStream_t st, char* err, size_t errlen) {
         std::lock_guard<std::mutex> g(mu);
-        for (auto& p : pending) if (p.first == st) { HIPCHK(hipEventRecord(p.second, st)); return FIN_OK; }
-        hipEvent_t ev = nullptr;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        pending.push_back({st, ev});
-        HIPCHK(hipEventRecord(ev, st));
-        return FIN_OK;
+        return mark_locked(st, err, errlen);
     }
     int wait(char* err, size_t errlen) {
         std::lock_guard<std::mutex> g(mu);
@@ -1452,28 +1448,22 @@ struct AccPending {
     // `st` waits for everything marked so far (a reader of the accumulator on another stream than its adds)
     int order(hipStream_t st, char* err, size_t errlen) {
         std::lock_guard<std::mutex> g(mu);
-        for (auto& p : pending) if (p.first != st) HIPCHK(hipStreamWaitEvent(st, p.second, 0));
-        return FIN_OK;
+        return order_locked(st, err, errlen);
     }
     // a reset does not commute with the adds: it runs behind everything issued so far on other streams, and every later add on another stream runs behind it
     // (the reset's own event -- a stream's mark is recorded again by its next add --, which behind_reset makes an add's stream wait for).  One lock is held from
-    // the waits over `zero` (the memset, on `st`) to the two records, so an add from another host thread falls before the reset or behind it, never in between.
-    // Adds among themselves stay unordered: they are atomic and commute
+    // the waits over the zeroing (a memset of `bytes` at `p`, on `st`) to the two records, so an add from another host thread falls before the reset or behind it,
+    // never in between.  Adds among themselves stay unordered: they are atomic and commute
     hipStream_t reset_st = nullptr; hipEvent_t reset_ev = nullptr;
-    int reset(hipStream_t st, const std::function<hipError_t()>& zero) {
+    int reset(hipStream_t st, void* p, size_t bytes) {
         char* err = nullptr; const size_t errlen = 0;
         std::lock_guard<std::mutex> g(mu);
-        for (auto& p : pending) if (p.first != st) HIPCHK(hipStreamWaitEvent(st, p.second, 0));
-        if (zero() != hipSuccess) return FIN_ENODEV;
+        if (const int orc = order_locked(st, err, errlen)) return orc;
+        if (hipMemsetAsync(p, 0, bytes, st) != hipSuccess) return FIN_ENODEV;
         if (!reset_ev) HIPCHK(hipEventCreateWithFlags(&reset_ev, hipEventDisableTiming));
         HIPCHK(hipEventRecord(reset_ev, st));
         reset_st = st;
-        for (auto& p : pending) if (p.first == st) { HIPCHK(hipEventRecord(p.second, st)); return FIN_OK; }
-        hipEvent_t ev = nullptr;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        pending.push_back({st, ev});
-        HIPCHK(hipEventRecord(ev, st));
-        return FIN_OK;
+        return mark_locked(st, err, errlen);
     }
     int behind_reset(hipStream_t st, char* err, size_t errlen) {
         std::lock_guard<std::mutex> g(mu);
@@ -1485,8 +1475,95 @@ struct AccPending {
         pending.clear();
         if (reset_ev) { (void)hipEventSynchronize(reset_ev); (void)hipEventDestroy(reset_ev); reset_ev = nullptr; }
     }
+private:   // (with `mu` held)
+    int mark_locked(hipStream_t st, char* err, size_t errlen) {
+        for (auto& p : pending) if (p.first == st) { HIPCHK(hipEventRecord(p.second, st)); return FIN_OK; }
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        pending.push_back({st, ev});
+        HIPCHK(hipEventRecord(ev, st));
+        return FIN_OK;
+    }
+    int order_locked(hipStream_t st, char* err, size_t errlen) {
+        for (auto& p : pending) if (p.first != st) HIPCHK(hipStreamWaitEvent(st, p.second, 0));
+        return FIN_OK;
+    }
 };
-// behind the batch's most recent run, whichever stream it was launched on: what fin_batch_add_hits, fin_batch_add_cover and fin_batch_add_depth check and order alike
+// what the six device accumulators are alike in (they are opaque in finito_amd.h): the index and device they live beside, and what their readers wait for
+struct fin_acc {
+    const fin_index* idx = nullptr;
+    int device = -1;
+    AccPending pend;
+};
+// ---- the accumulators' frame: each step of create / free / reset / download / add that they share, stated once --------------------------------------------
+// create, behind the caller's own argument checks: the replica the accumulator goes beside (`rep`, may be null, learns it), the device made current
+static int acc_create_open(const fin_index* idx, int device, const fin_index::Replica** rep, char* err, size_t errlen) {
+    const fin_index::Replica* r = idx->replica_on(device);
+    if (!r) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
+    HIPCHK(hipSetDevice(device));
+    if (rep) *rep = r;
+    return FIN_OK;
+}
+template <class A> static A* acc_new(const fin_index* idx, int device, char* err, size_t errlen) {
+    A* a = new (std::nothrow) A();
+    if (!a) { set_err(err, errlen, "out of memory"); return nullptr; }
+    a->idx = idx; a->device = device;
+    return a;
+}
+// the accumulator's buffer of `bytes`, its first `zero_bytes` zeroed.  The two unwinds: a failed allocation deletes the bare struct, a failed memset goes through
+// the accumulator's own free (`no_room` is the whole message of the first)
+template <class A> static int acc_alloc_zero(A* a, void** p, size_t bytes, size_t zero_bytes, const char* no_room, void (*free_a)(A*), char* err, size_t errlen) {
+    if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); delete a; set_err(err, errlen, no_room); return FIN_ENOMEM; }
+    if (hipMemset(*p, 0, zero_bytes) != hipSuccess) { free_a(a); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    return FIN_OK;
+}
+// free: false for null; else the device is current and nothing is pending any more -- the caller frees its buffers and deletes
+static bool acc_free_open(fin_acc* a) {
+    if (!a) return false;
+    if (a->device >= 0) (void)hipSetDevice(a->device);
+    a->pend.drop();
+    return true;
+}
+static int acc_reset(fin_acc* a, void* hip_stream, void* p, size_t bytes) {
+    if (!a) return FIN_EINVAL;
+    if (hipSetDevice(a->device) != hipSuccess) return FIN_ENODEV;
+    return a->pend.reset((hipStream_t)hip_stream, p, bytes);
+}
+// download: the device current, the adds waited for, and the flag word at `d_flags` (null: the accumulator has none) read -- flag 1 answers FIN_ELIMIT with
+// `flag1`, flag 2 FIN_EINVAL with `flag2` (null: no such flag)
+static int acc_download_open(fin_acc* a, const uint32_t* d_flags, const char* flag1, const char* flag2, char* err, size_t errlen) {
+    HIPCHK(hipSetDevice(a->device));
+    if (const int wrc = a->pend.wait(err, errlen)) return wrc;
+    if (!d_flags) return FIN_OK;
+    uint32_t flags = 0;
+    HIPCHK(hipMemcpy(&flags, d_flags, 4, hipMemcpyDeviceToHost));
+    if (flags & 1u) { set_err(err, errlen, flag1); return FIN_ELIMIT; }
+    if (flag2 && (flags & 2u)) { set_err(err, errlen, flag2); return FIN_EINVAL; }
+    return FIN_OK;
+}
+// where a download's numbers go when the caller wants only their sum: `dst`, or a temporary of n entries
+template <class T> static T* dst_or_tmp(T* dst, std::vector<T>& tmp, size_t n) {
+    if (!dst) { tmp.resize(n); dst = tmp.data(); }
+    return dst;
+}
+template <class T, class F> static uint64_t sum_of(const T* v, size_t n, F what) {
+    uint64_t t = 0;
+    for (size_t q = 0; q < n; q++) t += (uint64_t)what(v[q]);
+    return t;
+}
+// `st` waits for what was put on `src` so far (rows or classes made on the run's stream, behind the run, and added on another)
+static int stream_behind(hipStream_t st, hipStream_t src, char* err, size_t errlen) {
+    if (st == src) return FIN_OK;
+    hipEvent_t ev = nullptr;
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, src);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+    (void)hipEventDestroy(ev);   // (released once it has completed)
+    HIPCHK(e);
+    return FIN_OK;
+}
+// behind the batch's most recent run, whichever stream it was launched on: what every fin_batch_add_* checks and orders alike
 static int acc_behind_run(fin_batch* b, const fin_index* acc_idx, int acc_device, hipStream_t st, char* err, size_t errlen) {
     if (!b->ran) { set_err(err, errlen, "this batch has not run: there are no hits to add (fin_batch_run first)"); return FIN_EINVAL; }
     if (b->idx != acc_idx || b->device != acc_device) { set_err(err, errlen, "batch and accumulator belong to different indexes or devices"); return FIN_EINVAL; }
@@ -1498,21 +1575,41 @@ static int acc_behind_run(fin_batch* b, const fin_index* acc_idx, int acc_device
     }
     return FIN_OK;
 }
+// the frame of an add: behind the run and behind the accumulator's last reset; then the caller launches on `st`, and acc_add_close turns the launch's result
+// into the message `what` + the error's name, or marks `st` for the downloads
+static int acc_add_open(fin_batch* b, fin_acc* a, hipStream_t st, char* err, size_t errlen) {
+    if (const int brc = acc_behind_run(b, a->idx, a->device, st, err, errlen)) return brc;
+    return a->pend.behind_reset(st, err, errlen);
+}
+static int acc_add_close(fin_acc* a, hipStream_t st, int launch_rc, const char* what, char* err, size_t errlen) {
+    if (launch_rc != 0) { set_err(err, errlen, std::string(what) + hipGetErrorString((hipError_t)launch_rc)); return FIN_ENODEV; }
+    return a->pend.mark(st, err, errlen);
+}
+// the argument tests that several entry points make, each with its message
+static const char* const BAD_PERMILLE = "permille is a share in thousandths: 0 .. 1000";
+static const char* const BAD_MIN_PERMILLE = "min_permille is a share in thousandths: 0 .. 1000";
+static int check_permille(uint32_t permille, const char* bad, char* err, size_t errlen) {
+    if (permille > 1000u) { set_err(err, errlen, bad); return FIN_EINVAL; }
+    return FIN_OK;
+}
+static int check_pair_mode(uint32_t mode, char* err, size_t errlen) {
+    if (mode != FIN_PAIR_ANY && mode != FIN_PAIR_BOTH) { set_err(err, errlen, "mode is FIN_PAIR_ANY (0) or FIN_PAIR_BOTH (1)"); return FIN_EINVAL; }
+    return FIN_OK;
+}
+static int check_even(uint64_t n_reads, char* err, size_t errlen) {
+    if (n_reads & 1u) { set_err(err, errlen, "paired pseudoalignment wants interleaved mates: " + std::to_string(n_reads) + " reads are an odd number"); return FIN_EINVAL; }
+    return FIN_OK;
+}
+}  // extern "C++"
 
-struct fin_hits {
-    const fin_index* idx = nullptr;
-    int device = -1;
+struct fin_hits : fin_acc {
     uint64_t n_unitigs = 0;
     void* d_counts = nullptr;   // uint64[n_unitigs], then the flag word (fin_launch_hits_add)
-    AccPending pend;
 };
 static uint32_t* hits_flags(const fin_hits* h) { return (uint32_t*)((uint64_t*)h->d_counts + h->n_unitigs); }
-static int hits_mark(fin_hits* h, hipStream_t st, char* err, size_t errlen) { return h->pend.mark(st, err, errlen); }
 
 void fin_hits_free(fin_hits* h) {
-    if (!h) return;
-    if (h->device >= 0) (void)hipSetDevice(h->device);
-    h->pend.drop();
+    if (!acc_free_open(h)) return;
     (void)hipFree(h->d_counts);
     delete h;
 }
@@ -1520,23 +1617,17 @@ void fin_hits_free(fin_hits* h) {
 int fin_hits_create(const fin_index* idx, int device, fin_hits** out, char* err, size_t errlen) {
     if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     *out = nullptr;
-    if (!idx->replica_on(device)) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
-    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
-    HIPCHK(hipSetDevice(device));
-    fin_hits* h = new (std::nothrow) fin_hits();
-    if (!h) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
-    h->idx = idx; h->device = device; h->n_unitigs = idx->n_unitigs;
-    if (hipMalloc(&h->d_counts, h->n_unitigs * 8 + 8) != hipSuccess) { (void)hipGetLastError(); delete h; set_err(err, errlen, "out of device memory (unitig counts)"); return FIN_ENOMEM; }
-    if (hipMemset(h->d_counts, 0, h->n_unitigs * 8 + 8) != hipSuccess) { fin_hits_free(h); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    if (const int orc = acc_create_open(idx, device, nullptr, err, errlen)) return orc;
+    fin_hits* h = acc_new<fin_hits>(idx, device, err, errlen);
+    if (!h) return FIN_ENOMEM;
+    h->n_unitigs = idx->n_unitigs;
+    if (const int arc = acc_alloc_zero(h, &h->d_counts, h->n_unitigs * 8 + 8, h->n_unitigs * 8 + 8, "out of device memory (unitig counts)", fin_hits_free, err, errlen)) return arc;
     *out = h;
     return FIN_OK;
 }
 
 int fin_hits_reset(fin_hits* h, void* hip_stream) {
-    if (!h) return FIN_EINVAL;
-    if (hipSetDevice(h->device) != hipSuccess) return FIN_ENODEV;
-    hipStream_t st = (hipStream_t)hip_stream;
-    return h->pend.reset(st, [&] { return hipMemsetAsync(h->d_counts, 0, h->n_unitigs * 8 + 8, st); });
+    return acc_reset(h, hip_stream, h ? h->d_counts : nullptr, h ? h->n_unitigs * 8 + 8 : 0);
 }
 
 void* fin_hits_device_counts(const fin_hits* h) { return h ? h->d_counts : nullptr; }
@@ -1544,47 +1635,35 @@ void* fin_hits_device_counts(const fin_hits* h) { return h ? h->d_counts : nullp
 int fin_batch_add_hits(fin_batch* b, fin_hits* h, void* hip_stream, char* err, size_t errlen) {
     if (!b || !h) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     hipStream_t st = (hipStream_t)hip_stream;
-    if (const int brc = acc_behind_run(b, h->idx, h->device, st, err, errlen)) return brc;
-    if (const int orc = h->pend.behind_reset(st, err, errlen)) return orc;
+    if (const int orc = acc_add_open(b, h, st, err, errlen)) return orc;
     const int rc = fin_launch_hits_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, h->d_counts,
                                        (uint32_t)h->n_unitigs, hits_flags(h), b->d_ovf_count, b->last_ovf_cap, (uint32_t)optv(b->idx, O_hits_combine), st);
-    if (rc != 0) { set_err(err, errlen, std::string("hits kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
-    return hits_mark(h, st, err, errlen);
+    return acc_add_close(h, st, rc, "hits kernel: ", err, errlen);
 }
 
 int fin_hits_download(fin_hits* h, uint64_t* counts_out, uint64_t* total, char* err, size_t errlen) {
     if (!h || (h->n_unitigs && !counts_out && !total)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    HIPCHK(hipSetDevice(h->device));
-    if (const int wrc = h->pend.wait(err, errlen)) return wrc;
-    uint32_t flags = 0;
-    HIPCHK(hipMemcpy(&flags, hits_flags(h), 4, hipMemcpyDeviceToHost));
-    if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)"); return FIN_ELIMIT; }
-    if (flags & 2u) { set_err(err, errlen, "a pair with a unitig number outside the index was met (not counted)"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(h, hits_flags(h), "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)",
+                                          "a pair with a unitig number outside the index was met (not counted)", err, errlen)) return orc;
     std::vector<uint64_t> tmp;
-    uint64_t* dst = counts_out;
-    if (!dst) { tmp.resize((size_t)h->n_unitigs); dst = tmp.data(); }
+    uint64_t* const dst = dst_or_tmp(counts_out, tmp, (size_t)h->n_unitigs);
     if (h->n_unitigs) HIPCHK(hipMemcpy(dst, h->d_counts, h->n_unitigs * 8, hipMemcpyDeviceToHost));
-    if (total) { uint64_t t = 0; for (uint64_t u = 0; u < h->n_unitigs; u++) t += dst[u]; *total = t; }
+    if (total) *total = sum_of(dst, (size_t)h->n_unitigs, [](uint64_t v) { return v; });
     return FIN_OK;
 }
 
 // ---- read classification by unitig labels (fin_classify.hip) ---------------------------------------------------------------------------
 static_assert(sizeof(fin_read_class) == 16, "a read class is 16 bytes");
-struct fin_labels {
-    const fin_index* idx = nullptr;
-    int device = -1;
+struct fin_labels : fin_acc {
     uint64_t n_unitigs = 0; uint32_t n_labels = 0;
     uint64_t serial = 0;        // which labelling a batch's classes were made for (an address can come back after a free)
     void* d_labels = nullptr;   // uint32[n_unitigs]
     void* d_reads = nullptr;    // the tally: uint64[n_labels + 1]
-    AccPending pend;
 };
 static std::atomic<uint64_t> g_labels_serial{0};
 
 void fin_labels_free(fin_labels* l) {
-    if (!l) return;
-    if (l->device >= 0) (void)hipSetDevice(l->device);
-    l->pend.drop();
+    if (!acc_free_open(l)) return;
     (void)hipFree(l->d_labels); (void)hipFree(l->d_reads);
     delete l;
 }
@@ -1598,12 +1677,10 @@ int fin_labels_create(const fin_index* idx, int device, const uint32_t* unitig_l
             set_err(err, errlen, "unitig " + std::to_string(u) + " has label " + std::to_string(unitig_labels[u]) + ": neither below n_labels = " + std::to_string(n_labels) + " nor FIN_NO_LABEL");
             return FIN_EINVAL;
         }
-    if (!idx->replica_on(device)) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
-    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
-    HIPCHK(hipSetDevice(device));
-    fin_labels* l = new (std::nothrow) fin_labels();
-    if (!l) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
-    l->idx = idx; l->device = device; l->n_unitigs = idx->n_unitigs; l->n_labels = n_labels; l->serial = ++g_labels_serial;
+    if (const int orc = acc_create_open(idx, device, nullptr, err, errlen)) return orc;
+    fin_labels* l = acc_new<fin_labels>(idx, device, err, errlen);
+    if (!l) return FIN_ENOMEM;
+    l->n_unitigs = idx->n_unitigs; l->n_labels = n_labels; l->serial = ++g_labels_serial;
     const size_t tally = ((size_t)n_labels + 1) * 8;
     if (hipMalloc(&l->d_labels, (size_t)l->n_unitigs * 4 + 16) != hipSuccess || hipMalloc(&l->d_reads, tally) != hipSuccess) {
         (void)hipGetLastError(); fin_labels_free(l); set_err(err, errlen, "out of device memory (unitig labels and tally)"); return FIN_ENOMEM;
@@ -1616,10 +1693,7 @@ int fin_labels_create(const fin_index* idx, int device, const uint32_t* unitig_l
 }
 
 int fin_labels_reset(fin_labels* l, void* hip_stream) {
-    if (!l) return FIN_EINVAL;
-    if (hipSetDevice(l->device) != hipSuccess) return FIN_ENODEV;
-    hipStream_t st = (hipStream_t)hip_stream;
-    return l->pend.reset(st, [&] { return hipMemsetAsync(l->d_reads, 0, ((size_t)l->n_labels + 1) * 8, st); });
+    return acc_reset(l, hip_stream, l ? l->d_reads : nullptr, l ? ((size_t)l->n_labels + 1) * 8 : 0);
 }
 
 void* fin_labels_device_labels(const fin_labels* l) { return l ? l->d_labels : nullptr; }
@@ -1627,14 +1701,13 @@ void* fin_labels_device_reads(const fin_labels* l) { return l ? l->d_reads : nul
 
 int fin_labels_download(fin_labels* l, uint64_t* reads_out, uint64_t* total, char* err, size_t errlen) {
     if (!l) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    HIPCHK(hipSetDevice(l->device));
-    if (const int wrc = l->pend.wait(err, errlen)) return wrc;
+    if (const int orc = acc_download_open(l, nullptr, nullptr, nullptr, err, errlen)) return orc;   // (a tally has no flags)
+    if (!reads_out && !total) return FIN_OK;
     const size_t n = (size_t)l->n_labels + 1;
     std::vector<uint64_t> tmp;
-    uint64_t* dst = reads_out;
-    if (!dst) { if (!total) return FIN_OK; tmp.resize(n); dst = tmp.data(); }
+    uint64_t* const dst = dst_or_tmp(reads_out, tmp, n);
     HIPCHK(hipMemcpy(dst, l->d_reads, n * 8, hipMemcpyDeviceToHost));
-    if (total) { uint64_t t = 0; for (size_t q = 0; q < n; q++) t += dst[q]; *total = t; }
+    if (total) *total = sum_of(dst, n, [](uint64_t v) { return v; });
     return FIN_OK;
 }
 
@@ -1670,41 +1743,27 @@ int fin_batch_download_read_classes(fin_batch* b, fin_read_class* out, char* err
 
 int fin_batch_add_classes(fin_batch* b, fin_labels* l, uint32_t min_found, uint32_t min_permille, uint32_t min_margin, void* hip_stream, char* err, size_t errlen) {
     if (!b || !l) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    if (min_permille > 1000u) { set_err(err, errlen, "min_permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (const int crc = check_permille(min_permille, BAD_MIN_PERMILLE, err, errlen)) return crc;
     if (!b->cls_ready || b->cls_labels != l->serial) if (const int rc = fin_batch_classify(b, l, err, errlen)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    if (const int brc = acc_behind_run(b, l->idx, l->device, st, err, errlen)) return brc;
-    if (const int orc = l->pend.behind_reset(st, err, errlen)) return orc;
-    if (st != b->last_stream) {   // the classes were made on the run's stream, behind the run: the add waits for them too
-        hipEvent_t ev = nullptr;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ev, b->last_stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
-        (void)hipEventDestroy(ev);   // (released once it has completed)
-        HIPCHK(e);
-    }
+    if (const int orc = acc_add_open(b, l, st, err, errlen)) return orc;
+    if (const int src = stream_behind(st, b->last_stream, err, errlen)) return src;   // the classes were made on the run's stream, behind the run: the add waits for them too
     const int rc = fin_launch_class_tally(b->d_cls, (const uint64_t*)b->d_out_offs, (uint32_t)b->n_reads, l->n_labels, min_found, min_permille, min_margin,
                                           (uint64_t*)l->d_reads, st);
-    if (rc != 0) { set_err(err, errlen, std::string("class tally kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
-    return l->pend.mark(st, err, errlen);
+    return acc_add_close(l, st, rc, "class tally kernel: ", err, errlen);
 }
 
 // ---- colour sets per unitig and read pseudoalignment (fin_colors.hip) -------------------------------------------------------------------
 static_assert(sizeof(fin_read_pseudo) == 16, "a pseudoalignment head is 16 bytes");
-struct fin_colors {
-    const fin_index* idx = nullptr;
-    int device = -1;
+struct fin_colors : fin_acc {
     uint64_t n_unitigs = 0; uint32_t n_colors = 0, words = 0;
     void* d_bits = nullptr;     // uint64[n_unitigs * words], then the flag word (fin_launch_colors_add)
-    AccPending pend;
 };
 static size_t colors_bytes(const fin_colors* c) { return (size_t)c->n_unitigs * c->words * 8; }
 static uint32_t* colors_flags(const fin_colors* c) { return (uint32_t*)((char*)c->d_bits + colors_bytes(c)); }
 
 void fin_colors_free(fin_colors* c) {
-    if (!c) return;
-    if (c->device >= 0) (void)hipSetDevice(c->device);
-    c->pend.drop();
+    if (!acc_free_open(c)) return;
     (void)hipFree(c->d_bits);
     delete c;
 }
@@ -1713,14 +1772,11 @@ int fin_colors_create(const fin_index* idx, int device, uint32_t n_colors, fin_c
     if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     *out = nullptr;
     if (n_colors == 0 || n_colors > FIN_MAX_COLORS) { set_err(err, errlen, "n_colors is 1 .. " + std::to_string(FIN_MAX_COLORS)); return FIN_ELIMIT; }
-    if (!idx->replica_on(device)) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
-    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
-    HIPCHK(hipSetDevice(device));
-    fin_colors* c = new (std::nothrow) fin_colors();
-    if (!c) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
-    c->idx = idx; c->device = device; c->n_unitigs = idx->n_unitigs; c->n_colors = n_colors; c->words = (n_colors + 63u) / 64u;
-    if (hipMalloc(&c->d_bits, colors_bytes(c) + 8) != hipSuccess) { (void)hipGetLastError(); delete c; set_err(err, errlen, "out of device memory (colour matrix)"); return FIN_ENOMEM; }
-    if (hipMemset(c->d_bits, 0, colors_bytes(c) + 8) != hipSuccess) { fin_colors_free(c); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    if (const int orc = acc_create_open(idx, device, nullptr, err, errlen)) return orc;
+    fin_colors* c = acc_new<fin_colors>(idx, device, err, errlen);
+    if (!c) return FIN_ENOMEM;
+    c->n_unitigs = idx->n_unitigs; c->n_colors = n_colors; c->words = (n_colors + 63u) / 64u;
+    if (const int arc = acc_alloc_zero(c, &c->d_bits, colors_bytes(c) + 8, colors_bytes(c) + 8, "out of device memory (colour matrix)", fin_colors_free, err, errlen)) return arc;
     *out = c;
     return FIN_OK;
 }
@@ -1737,10 +1793,7 @@ int fin_colors_upload(fin_colors* c, const uint64_t* bits, char* err, size_t err
 }
 
 int fin_colors_reset(fin_colors* c, void* hip_stream) {
-    if (!c) return FIN_EINVAL;
-    if (hipSetDevice(c->device) != hipSuccess) return FIN_ENODEV;
-    hipStream_t st = (hipStream_t)hip_stream;
-    return c->pend.reset(st, [&] { return hipMemsetAsync(c->d_bits, 0, colors_bytes(c) + 8, st); });
+    return acc_reset(c, hip_stream, c ? c->d_bits : nullptr, c ? colors_bytes(c) + 8 : 0);
 }
 
 void* fin_colors_device_bits(const fin_colors* c) { return c ? c->d_bits : nullptr; }
@@ -1749,17 +1802,14 @@ uint32_t fin_colors_words(const fin_colors* c) { return c ? c->words : 0; }
 
 int fin_colors_download(fin_colors* c, uint64_t* bits_out, uint64_t* n_set, char* err, size_t errlen) {
     if (!c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    HIPCHK(hipSetDevice(c->device));
-    if (const int wrc = c->pend.wait(err, errlen)) return wrc;
-    uint32_t flags = 0;
-    HIPCHK(hipMemcpy(&flags, colors_flags(c), 4, hipMemcpyDeviceToHost));
-    if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: it has no results, nothing of it was coloured (reset the colours)"); return FIN_ELIMIT; }
+    if (const int orc = acc_download_open(c, colors_flags(c), "a step whose overflow list overran was added: it has no results, nothing of it was coloured (reset the colours)",
+                                          nullptr, err, errlen)) return orc;
+    if (!bits_out && !n_set) return FIN_OK;
     const size_t n = (size_t)c->n_unitigs * c->words;
     std::vector<uint64_t> tmp;
-    uint64_t* dst = bits_out;
-    if (!dst) { if (!n_set) return FIN_OK; tmp.resize(n); dst = tmp.data(); }
+    uint64_t* const dst = dst_or_tmp(bits_out, tmp, n);
     if (n) HIPCHK(hipMemcpy(dst, c->d_bits, n * 8, hipMemcpyDeviceToHost));
-    if (n_set) { uint64_t t = 0; for (size_t q = 0; q < n; q++) t += (uint64_t)__builtin_popcountll(dst[q]); *n_set = t; }
+    if (n_set) *n_set = sum_of(dst, n, [](uint64_t w) { return __builtin_popcountll(w); });
     return FIN_OK;
 }
 
@@ -1767,19 +1817,16 @@ int fin_batch_add_colors(fin_batch* b, fin_colors* c, uint32_t color, void* hip_
     if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     if (color >= c->n_colors) { set_err(err, errlen, "colour " + std::to_string(color) + " is not below n_colors = " + std::to_string(c->n_colors)); return FIN_EINVAL; }
     hipStream_t st = (hipStream_t)hip_stream;
-    if (const int brc = acc_behind_run(b, c->idx, c->device, st, err, errlen)) return brc;
-    if (const int orc = c->pend.behind_reset(st, err, errlen)) return orc;
-    if (b->n_kmers != 0) {   // (no read has a k-mer: the step searched nothing)
-        const int rc = fin_launch_colors_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->dev.k, c->d_bits, c->words,
-                                             (uint32_t)c->n_unitigs, color, colors_flags(c), b->d_ovf_count, b->last_ovf_cap, st);
-        if (rc != 0) { set_err(err, errlen, std::string("colour kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
-    }
-    return c->pend.mark(st, err, errlen);
+    if (const int orc = acc_add_open(b, c, st, err, errlen)) return orc;
+    // (no read has a k-mer: the step searched nothing)
+    const int rc = b->n_kmers == 0 ? 0 : fin_launch_colors_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->dev.k, c->d_bits,
+                                                               c->words, (uint32_t)c->n_unitigs, color, colors_flags(c), b->d_ovf_count, b->last_ovf_cap, st);
+    return acc_add_close(c, st, rc, "colour kernel: ", err, errlen);
 }
 
 int fin_batch_pseudoalign(fin_batch* b, const fin_colors* c, uint32_t permille, char* err, size_t errlen) {
     if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    if (const int crc = check_permille(permille, BAD_PERMILLE, err, errlen)) return crc;
     if (!b->ran) { set_err(err, errlen, "this batch has not run: there is nothing to pseudoalign (fin_batch_run first)"); return FIN_EINVAL; }
     if (b->idx != c->idx || b->device != c->device) { set_err(err, errlen, "batch and colours belong to different indexes or devices"); return FIN_EINVAL; }
     HIPCHK(hipSetDevice(b->device));
@@ -1817,11 +1864,11 @@ int fin_batch_download_pseudo(fin_batch* b, uint64_t* rows_out, fin_read_pseudo*
 static_assert(sizeof(fin_pair_pseudo) == 16, "a fragment's pseudoalignment head is 16 bytes");
 int fin_batch_pseudoalign_paired(fin_batch* b, const fin_colors* c, uint32_t permille, uint32_t mode, char* err, size_t errlen) {
     if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
-    if (mode != FIN_PAIR_ANY && mode != FIN_PAIR_BOTH) { set_err(err, errlen, "mode is FIN_PAIR_ANY (0) or FIN_PAIR_BOTH (1)"); return FIN_EINVAL; }
+    if (const int crc = check_permille(permille, BAD_PERMILLE, err, errlen)) return crc;
+    if (const int crc = check_pair_mode(mode, err, errlen)) return crc;
     if (!b->ran) { set_err(err, errlen, "this batch has not run: there is nothing to pseudoalign (fin_batch_run first)"); return FIN_EINVAL; }
     if (b->idx != c->idx || b->device != c->device) { set_err(err, errlen, "batch and colours belong to different indexes or devices"); return FIN_EINVAL; }
-    if (b->n_reads & 1u) { set_err(err, errlen, "paired pseudoalignment wants interleaved mates: " + std::to_string(b->n_reads) + " reads are an odd number"); return FIN_EINVAL; }
+    if (const int crc = check_even(b->n_reads, err, errlen)) return crc;
     HIPCHK(hipSetDevice(b->device));
     hipStream_t st = b->last_stream;
     b->pair_ready = false;
@@ -1854,10 +1901,8 @@ int fin_batch_download_pair_pseudo(fin_batch* b, uint64_t* rows_out, fin_pair_ps
 }
 
 // ---- equivalence classes of pseudoaligned reads (fin_eqclasses.hip) ---------------------------------------------------------------------
-struct fin_eqclasses {
+struct fin_eqclasses : fin_acc {
     const fin_colors* colors = nullptr;
-    const fin_index* idx = nullptr;
-    int device = -1;
     uint32_t n_colors = 0, words = 0, lg = 0;
     uint64_t max_classes = 0, slots = 0;
     void* d_tab = nullptr;      // ctr uint64[8] | tags uint64[slots] | counts uint64[slots] | rows uint64[slots * words]
@@ -1865,7 +1910,6 @@ struct fin_eqclasses {
     size_t cap_rows = 0;
     uint32_t tag_bits = 0;      // option "ec_tag_bits" as the first add since the creation or the last reset read it (0: none yet)
     std::mutex mu;              // an add (order, three launches, mark) and a reset are one step each: calls from several host threads take effect in issue order
-    AccPending pend;
 };
 static uint64_t* ec_ctr(const fin_eqclasses* e) { return (uint64_t*)e->d_tab; }
 static uint64_t* ec_tags(const fin_eqclasses* e) { return (uint64_t*)e->d_tab + 8; }
@@ -1874,9 +1918,7 @@ static uint64_t* ec_rows(const fin_eqclasses* e) { return ec_counts(e) + e->slot
 static size_t ec_zero_bytes(const fin_eqclasses* e) { return (size_t)(8 + 2 * e->slots) * 8; }   // (a slot's row is written when the slot is claimed)
 
 void fin_eqclasses_free(fin_eqclasses* e) {
-    if (!e) return;
-    if (e->device >= 0) (void)hipSetDevice(e->device);
-    e->pend.drop();
+    if (!acc_free_open(e)) return;
     (void)hipFree(e->d_tab); (void)hipFree(e->d_scratch);
     delete e;
 }
@@ -1885,16 +1927,15 @@ int fin_eqclasses_create(const fin_colors* c, uint64_t max_classes, fin_eqclasse
     if (!c || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     *out = nullptr;
     if (max_classes == 0 || max_classes > (1ull << 26)) { set_err(err, errlen, "max_classes is 1 .. 2^26"); return FIN_ELIMIT; }
-    HIPCHK(hipSetDevice(c->device));
-    fin_eqclasses* e = new (std::nothrow) fin_eqclasses();
-    if (!e) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
-    e->colors = c; e->idx = c->idx; e->device = c->device; e->n_colors = c->n_colors; e->words = c->words; e->max_classes = max_classes;
+    HIPCHK(hipSetDevice(c->device));   // (not acc_create_open: it goes beside a colour matrix, which has passed those checks)
+    fin_eqclasses* e = acc_new<fin_eqclasses>(c->idx, c->device, err, errlen);
+    if (!e) return FIN_ENOMEM;
+    e->colors = c; e->n_colors = c->n_colors; e->words = c->words; e->max_classes = max_classes;
     e->lg = 1;
     while ((1ull << e->lg) < 2 * max_classes) e->lg++;
     e->slots = 1ull << e->lg;
     const size_t bytes = ec_zero_bytes(e) + (size_t)e->slots * e->words * 8;
-    if (hipMalloc(&e->d_tab, bytes) != hipSuccess) { (void)hipGetLastError(); delete e; set_err(err, errlen, "out of device memory (table of equivalence classes)"); return FIN_ENOMEM; }
-    if (hipMemset(e->d_tab, 0, ec_zero_bytes(e)) != hipSuccess) { fin_eqclasses_free(e); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    if (const int arc = acc_alloc_zero(e, &e->d_tab, bytes, ec_zero_bytes(e), "out of device memory (table of equivalence classes)", fin_eqclasses_free, err, errlen)) return arc;
     *out = e;
     return FIN_OK;
 }
@@ -1902,10 +1943,9 @@ int fin_eqclasses_create(const fin_colors* c, uint64_t max_classes, fin_eqclasse
 int fin_eqclasses_reset(fin_eqclasses* e, void* hip_stream) {
     if (!e) return FIN_EINVAL;
     if (hipSetDevice(e->device) != hipSuccess) return FIN_ENODEV;
-    hipStream_t st = (hipStream_t)hip_stream;
     std::lock_guard<std::mutex> g(e->mu);
     e->tag_bits = 0;
-    return e->pend.reset(st, [&] { return hipMemsetAsync(e->d_tab, 0, ec_zero_bytes(e), st); });
+    return acc_reset(e, hip_stream, e->d_tab, ec_zero_bytes(e));
 }
 
 // the add proper, on `st`: behind every add and reset issued so far, whichever streams they were given
@@ -1940,14 +1980,7 @@ int fin_batch_add_eqclasses(fin_batch* b, fin_eqclasses* e, uint32_t permille, v
     // always: the batch does not remember which matrix and threshold its rows belong to, and the matrix may have changed
     if (const int rc = fin_batch_pseudoalign(b, e->colors, permille, err, errlen)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    if (st != b->last_stream) {   // the rows were made on the run's stream, behind the run: the add waits for them
-        hipEvent_t ev = nullptr;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t rc = hipEventRecord(ev, b->last_stream);
-        if (rc == hipSuccess) rc = hipStreamWaitEvent(st, ev, 0);
-        (void)hipEventDestroy(ev);   // (released once it has completed)
-        HIPCHK(rc);
-    }
+    if (const int src = stream_behind(st, b->last_stream, err, errlen)) return src;   // the rows were made on the run's stream, behind the run: the add waits for them
     return ec_add_rows(e, b->d_psa_rows, b->n_reads, st, err, errlen);
 }
 
@@ -1956,14 +1989,7 @@ int fin_batch_add_eqclasses_paired(fin_batch* b, fin_eqclasses* e, uint32_t perm
     // always, as fin_batch_add_eqclasses does: the batch does not remember which matrix, threshold and mode its rows belong to
     if (const int rc = fin_batch_pseudoalign_paired(b, e->colors, permille, mode, err, errlen)) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
-    if (st != b->last_stream) {   // the rows were made on the run's stream, behind the run: the add waits for them
-        hipEvent_t ev = nullptr;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t rc = hipEventRecord(ev, b->last_stream);
-        if (rc == hipSuccess) rc = hipStreamWaitEvent(st, ev, 0);
-        (void)hipEventDestroy(ev);   // (released once it has completed)
-        HIPCHK(rc);
-    }
+    if (const int src = stream_behind(st, b->last_stream, err, errlen)) return src;   // the rows were made on the run's stream, behind the run: the add waits for them
     return ec_add_rows(e, b->d_pair_rows, b->n_reads / 2, st, err, errlen);   // a fragment is one row
 }
 
@@ -2406,22 +2432,17 @@ int fin_classes_bootstrap(const uint64_t* class_rows, const uint64_t* class_read
 }
 
 // ---- breadth of coverage over the unitig text (fin_cover.hip) -------------------------------------------------------------------------
-struct fin_cover {
-    const fin_index* idx = nullptr;
-    int device = -1;
+struct fin_cover : fin_acc {
     uint64_t n_unitigs = 0, total_len = 0, n_words = 0;
     const uint32_t* d_ends = nullptr;   // the replica's ends_p
     void* d_bits = nullptr;             // uint64[n_words], then the flag word (fin_launch_cover_add)
     void* d_covered = nullptr;          // uint64[n_unitigs]: fin_cover_download's popcounts
     std::mutex count_mu;                // one download at a time counts into d_covered
-    AccPending pend;
 };
 static uint32_t* cover_flags(const fin_cover* c) { return (uint32_t*)((uint64_t*)c->d_bits + c->n_words); }
 
 void fin_cover_free(fin_cover* c) {
-    if (!c) return;
-    if (c->device >= 0) (void)hipSetDevice(c->device);
-    c->pend.drop();
+    if (!acc_free_open(c)) return;
     (void)hipFree(c->d_bits); (void)hipFree(c->d_covered);
     delete c;
 }
@@ -2429,25 +2450,19 @@ void fin_cover_free(fin_cover* c) {
 int fin_cover_create(const fin_index* idx, int device, fin_cover** out, char* err, size_t errlen) {
     if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     *out = nullptr;
-    const fin_index::Replica* rep = idx->replica_on(device);
-    if (!rep) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
-    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
-    HIPCHK(hipSetDevice(device));
-    fin_cover* c = new (std::nothrow) fin_cover();
-    if (!c) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
-    c->idx = idx; c->device = device; c->n_unitigs = idx->n_unitigs; c->total_len = idx->total_len; c->n_words = (idx->total_len + 63) / 64; c->d_ends = rep->dev.ends;
-    if (hipMalloc(&c->d_bits, c->n_words * 8 + 8) != hipSuccess) { (void)hipGetLastError(); delete c; set_err(err, errlen, "out of device memory (coverage bitmap)"); return FIN_ENOMEM; }
-    if (hipMemset(c->d_bits, 0, c->n_words * 8 + 8) != hipSuccess) { fin_cover_free(c); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    const fin_index::Replica* rep = nullptr;
+    if (const int orc = acc_create_open(idx, device, &rep, err, errlen)) return orc;
+    fin_cover* c = acc_new<fin_cover>(idx, device, err, errlen);
+    if (!c) return FIN_ENOMEM;
+    c->n_unitigs = idx->n_unitigs; c->total_len = idx->total_len; c->n_words = (idx->total_len + 63) / 64; c->d_ends = rep->dev.ends;
+    if (const int arc = acc_alloc_zero(c, &c->d_bits, c->n_words * 8 + 8, c->n_words * 8 + 8, "out of device memory (coverage bitmap)", fin_cover_free, err, errlen)) return arc;
     if (c->n_unitigs && hipMalloc(&c->d_covered, c->n_unitigs * 8) != hipSuccess) { (void)hipGetLastError(); c->d_covered = nullptr; fin_cover_free(c); set_err(err, errlen, "out of device memory (covered counts)"); return FIN_ENOMEM; }
     *out = c;
     return FIN_OK;
 }
 
 int fin_cover_reset(fin_cover* c, void* hip_stream) {
-    if (!c) return FIN_EINVAL;
-    if (hipSetDevice(c->device) != hipSuccess) return FIN_ENODEV;
-    hipStream_t st = (hipStream_t)hip_stream;
-    return c->pend.reset(st, [&] { return hipMemsetAsync(c->d_bits, 0, c->n_words * 8 + 8, st); });
+    return acc_reset(c, hip_stream, c ? c->d_bits : nullptr, c ? c->n_words * 8 + 8 : 0);
 }
 
 void* fin_cover_device_bits(const fin_cover* c) { return c ? c->d_bits : nullptr; }
@@ -2455,43 +2470,34 @@ void* fin_cover_device_bits(const fin_cover* c) { return c ? c->d_bits : nullptr
 int fin_batch_add_cover(fin_batch* b, fin_cover* c, void* hip_stream, char* err, size_t errlen) {
     if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     hipStream_t st = (hipStream_t)hip_stream;
-    if (const int brc = acc_behind_run(b, c->idx, c->device, st, err, errlen)) return brc;
-    if (const int orc = c->pend.behind_reset(st, err, errlen)) return orc;
+    if (const int orc = acc_add_open(b, c, st, err, errlen)) return orc;
     const int rc = fin_launch_cover_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, c->d_ends,
                                         (uint32_t)c->n_unitigs, c->total_len, c->d_bits, cover_flags(c), b->d_ovf_count, b->last_ovf_cap,
                                         (uint32_t)optv(b->idx, O_cover_probe), st);
-    if (rc != 0) { set_err(err, errlen, std::string("cover kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
-    return c->pend.mark(st, err, errlen);
+    return acc_add_close(c, st, rc, "cover kernel: ", err, errlen);
 }
 
 int fin_cover_download(fin_cover* c, uint64_t* bits_out, uint64_t* covered_out, uint64_t* total_covered, char* err, size_t errlen) {
     if (!c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    HIPCHK(hipSetDevice(c->device));
-    if (const int wrc = c->pend.wait(err, errlen)) return wrc;
-    uint32_t flags = 0;
-    HIPCHK(hipMemcpy(&flags, cover_flags(c), 4, hipMemcpyDeviceToHost));
-    if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: it has no results, nothing of it was set (reset the accumulator)"); return FIN_ELIMIT; }
-    if (flags & 2u) { set_err(err, errlen, "a pair with a unitig number or a position outside the index was met (not set)"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(c, cover_flags(c), "a step whose overflow list overran was added: it has no results, nothing of it was set (reset the accumulator)",
+                                          "a pair with a unitig number or a position outside the index was met (not set)", err, errlen)) return orc;
     if (bits_out && c->n_words) HIPCHK(hipMemcpy(bits_out, c->d_bits, c->n_words * 8, hipMemcpyDeviceToHost));
     if (covered_out || total_covered) {
         std::vector<uint64_t> tmp;
-        uint64_t* dst = covered_out;
-        if (!dst) { tmp.resize((size_t)c->n_unitigs); dst = tmp.data(); }
+        uint64_t* const dst = dst_or_tmp(covered_out, tmp, (size_t)c->n_unitigs);
         if (c->n_unitigs) {
             std::lock_guard<std::mutex> g(c->count_mu);
             const int rc = fin_launch_cover_count(c->d_bits, c->d_ends, (uint32_t)c->n_unitigs, c->total_len, c->d_covered, nullptr);
             if (rc != 0) { set_err(err, errlen, std::string("cover count kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
             HIPCHK(hipMemcpy(dst, c->d_covered, c->n_unitigs * 8, hipMemcpyDeviceToHost));   // (the null stream: behind the kernel)
         }
-        if (total_covered) { uint64_t t = 0; for (uint64_t u = 0; u < c->n_unitigs; u++) t += dst[u]; *total_covered = t; }
+        if (total_covered) *total_covered = sum_of(dst, (size_t)c->n_unitigs, [](uint64_t v) { return v; });
     }
     return FIN_OK;
 }
 
 // ---- per-position depth over the unitig text (fin_depth.hip) ---------------------------------------------------------------------------
-struct fin_depth {
-    const fin_index* idx = nullptr;
-    int device = -1;
+struct fin_depth : fin_acc {
     uint64_t n_unitigs = 0, total_len = 0;
     const uint32_t* d_ends = nullptr;   // the replica's ends_p
     void* d_diff = nullptr;             // int32[total_len + 1], the difference array, then the flag word (fin_launch_depth_add)
@@ -2501,16 +2507,13 @@ struct fin_depth {
     void* d_stats = nullptr;            // fin_depth_stat[n_unitigs]
     uint64_t stage_len = 0;
     std::mutex scan_mu;                 // one download at a time scans through the staging buffer
-    AccPending pend;
 };
 static_assert(sizeof(fin_depth_stat) == 16 && sizeof(FinDepthStat) == 16, "fin_depth_stat is 16 bytes on both sides");
 static uint32_t* depth_flags(const fin_depth* d) { return (uint32_t*)((int32_t*)d->d_diff + d->total_len + 1); }
 static size_t depth_bytes(const fin_depth* d) { return (size_t)(d->total_len + 2) * 4; }
 
 void fin_depth_free(fin_depth* d) {
-    if (!d) return;
-    if (d->device >= 0) (void)hipSetDevice(d->device);
-    d->pend.drop();
+    if (!acc_free_open(d)) return;
     (void)hipFree(d->d_diff); (void)hipFree(d->d_stage); (void)hipFree(d->d_tile); (void)hipFree(d->d_stats);
     delete d;
 }
@@ -2518,24 +2521,18 @@ void fin_depth_free(fin_depth* d) {
 int fin_depth_create(const fin_index* idx, int device, fin_depth** out, char* err, size_t errlen) {
     if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     *out = nullptr;
-    const fin_index::Replica* rep = idx->replica_on(device);
-    if (!rep) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
-    if (idx->n_unitigs >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 unitigs"); return FIN_ELIMIT; }
-    HIPCHK(hipSetDevice(device));
-    fin_depth* d = new (std::nothrow) fin_depth();
-    if (!d) { set_err(err, errlen, "out of memory"); return FIN_ENOMEM; }
-    d->idx = idx; d->device = device; d->n_unitigs = idx->n_unitigs; d->total_len = idx->total_len; d->d_ends = rep->dev.ends;
-    if (hipMalloc(&d->d_diff, depth_bytes(d)) != hipSuccess) { (void)hipGetLastError(); delete d; set_err(err, errlen, "out of device memory (depth difference array)"); return FIN_ENOMEM; }
-    if (hipMemset(d->d_diff, 0, depth_bytes(d)) != hipSuccess) { fin_depth_free(d); set_err(err, errlen, "hipMemset failed"); return FIN_ENODEV; }
+    const fin_index::Replica* rep = nullptr;
+    if (const int orc = acc_create_open(idx, device, &rep, err, errlen)) return orc;
+    fin_depth* d = acc_new<fin_depth>(idx, device, err, errlen);
+    if (!d) return FIN_ENOMEM;
+    d->n_unitigs = idx->n_unitigs; d->total_len = idx->total_len; d->d_ends = rep->dev.ends;
+    if (const int arc = acc_alloc_zero(d, &d->d_diff, depth_bytes(d), depth_bytes(d), "out of device memory (depth difference array)", fin_depth_free, err, errlen)) return arc;
     *out = d;
     return FIN_OK;
 }
 
 int fin_depth_reset(fin_depth* d, void* hip_stream) {
-    if (!d) return FIN_EINVAL;
-    if (hipSetDevice(d->device) != hipSuccess) return FIN_ENODEV;
-    hipStream_t st = (hipStream_t)hip_stream;
-    return d->pend.reset(st, [&] { return hipMemsetAsync(d->d_diff, 0, depth_bytes(d), st); });
+    return acc_reset(d, hip_stream, d ? d->d_diff : nullptr, d ? depth_bytes(d) : 0);
 }
 
 void* fin_depth_device_diff(const fin_depth* d) { return d ? d->d_diff : nullptr; }
@@ -2543,22 +2540,16 @@ void* fin_depth_device_diff(const fin_depth* d) { return d ? d->d_diff : nullptr
 int fin_batch_add_depth(fin_batch* b, fin_depth* d, void* hip_stream, char* err, size_t errlen) {
     if (!b || !d) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     hipStream_t st = (hipStream_t)hip_stream;
-    if (const int brc = acc_behind_run(b, d->idx, d->device, st, err, errlen)) return brc;
-    if (const int orc = d->pend.behind_reset(st, err, errlen)) return orc;
+    if (const int orc = acc_add_open(b, d, st, err, errlen)) return orc;
     const int rc = fin_launch_depth_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, b->n_kmers, b->dev.k, d->d_ends,
                                         (uint32_t)d->n_unitigs, d->total_len, d->d_diff, depth_flags(d), b->d_ovf_count, b->last_ovf_cap, st);
-    if (rc != 0) { set_err(err, errlen, std::string("depth kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
-    return d->pend.mark(st, err, errlen);
+    return acc_add_close(d, st, rc, "depth kernel: ", err, errlen);
 }
 
 int fin_depth_download(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, fin_depth_stat* stats_out, uint64_t* total, char* err, size_t errlen) {
     if (!d) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    HIPCHK(hipSetDevice(d->device));
-    if (const int wrc = d->pend.wait(err, errlen)) return wrc;
-    uint32_t flags = 0;
-    HIPCHK(hipMemcpy(&flags, depth_flags(d), 4, hipMemcpyDeviceToHost));
-    if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)"); return FIN_ELIMIT; }
-    if (flags & 2u) { set_err(err, errlen, "a pair with a unitig number or a position outside the index was met (not counted)"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(d, depth_flags(d), "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)",
+                                          "a pair with a unitig number or a position outside the index was met (not counted)", err, errlen)) return orc;
     if (total) *total = 0;
     const bool want_stats = stats_out || total;
     if (!depth_out && !want_stats) return FIN_OK;
@@ -2586,10 +2577,9 @@ int fin_depth_download(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, fi
     }
     if (want_stats) {
         std::vector<fin_depth_stat> tmp;
-        fin_depth_stat* dst = stats_out;
-        if (!dst) { tmp.resize((size_t)d->n_unitigs); dst = tmp.data(); }
+        fin_depth_stat* const dst = dst_or_tmp(stats_out, tmp, (size_t)d->n_unitigs);
         HIPCHK(hipMemcpy(dst, d->d_stats, (size_t)d->n_unitigs * sizeof(fin_depth_stat), hipMemcpyDeviceToHost));
-        if (total) { uint64_t t = 0; for (uint64_t u = 0; u < d->n_unitigs; u++) t += dst[u].sum; *total = t; }
+        if (total) *total = sum_of(dst, (size_t)d->n_unitigs, [](const fin_depth_stat& s) { return s.sum; });
     }
     return FIN_OK;
 }
@@ -2676,45 +2666,24 @@ int64_t fin_batch_overflow_reads(fin_batch* b) {
 // while one sub-batch is being searched, the previous one's pairs travel back over PCIe and the next one's reads travel in
 // (H2D + kernel + D2H double-buffered).  With page-locked caller buffers (fin_host_alloc) the copies are DMA at
 // link speed; pageable buffers work too, staged by the runtime.
-// text mode of the pipeline below: every sub-batch's text lands behind its predecessors' in one caller buffer
-struct TextSink {
-    // (records instead of text when `recs` is set: fin_search_batch_records -- `len` then counts a sub-batch's stream pairs)
-    fin_read_record* recs = nullptr; int32_t* rpairs = nullptr; uint64_t rcap = 0; uint64_t read0 = 0;
-    char* buf = nullptr; uint64_t cap = 0;
-    fin_hits* hits = nullptr;   // the profile instead of text (fin_search_batch_unitig_counts): every sub-batch is added on the device, nothing comes back
-    fin_cover* cover = nullptr; // the coverage bitmap (fin_search_batch_add_cover); with `hits` too, both adds go behind the same run
-    fin_depth* depth = nullptr; // the per-position depth (fin_search_batch_add_depth), likewise
-    // (segments when `seg_offs` is set: fin_search_batch_segments -- `len` then counts a sub-batch's segments, seg_offs is rebased to the whole read set)
-    uint64_t* seg_offs = nullptr; fin_segment* segs = nullptr; uint64_t seg_cap = 0; std::atomic<bool> seg_over{false};
-    // (summaries when `rsum` is set: fin_search_batch_read_summaries -- a sub-batch's land at its reads' numbers; a screen when `screen` is set:
-    //  fin_search_batch_screen -- a sub-batch's bitmap is shifted into scr_bits (may be null) at its first read's bit, under `mu`)
-    fin_read_summary* rsum = nullptr;
-    bool screen = false; uint32_t scr_min_found = 0, scr_min_permille = 0; int scr_invert = 0; uint64_t* scr_bits = nullptr; std::atomic<uint64_t> scr_pass{0};
-    // (classes when `cls` is set: fin_search_batch_classify -- a sub-batch's land at its reads' numbers; with `tally` every sub-batch is added to the
-    //  labelling's tally on the device instead and nothing comes back: fin_search_batch_add_classes)
-    const fin_labels* labels = nullptr; fin_read_class* cls = nullptr; fin_labels* tally = nullptr; uint32_t cls_min_found = 0, cls_min_permille = 0, cls_min_margin = 0;
-    // (colouring when `paint` is set: fin_search_batch_add_colors -- every sub-batch's unitigs get `paint_color` on the device, nothing comes back;
-    //  pseudoalignment when `psa` is set: fin_search_batch_pseudoalign -- a sub-batch's rows (may be null) and heads land at its reads' numbers)
-    fin_colors* paint = nullptr; uint32_t paint_color = 0;
-    const fin_colors* psa = nullptr; uint32_t psa_permille = 0; uint64_t* psa_rows = nullptr; fin_read_pseudo* psa_heads = nullptr;
-    // (equivalence classes when `eqc` is set: fin_search_batch_add_eqclasses -- every sub-batch is pseudoaligned and added on the device, nothing comes back)
-    fin_eqclasses* eqc = nullptr; uint32_t eqc_permille = 0;
-    // (fragments when `group` is 2: fin_search_batch_pseudoalign_paired / _add_eqclasses_paired -- the reads are interleaved mates, a sub-batch ends only after an
-    //  even number of reads counted from the range's first, psa_pheads takes the fragments' heads and rows and heads land at the fragments' numbers)
-    uint64_t group = 1; uint32_t pair_mode = 0; fin_pair_pseudo* psa_pheads = nullptr;
-    std::vector<uint64_t> len; std::vector<char> known;
-    std::mutex mu; std::condition_variable cv;
-    uint64_t total = 0;
+// What an entry point does with one searched sub-batch is its PRODUCT: `take` runs on the worker's thread behind fin_batch_run (text mode 2: the pairs are not the
+// product) with the batch, the sub-batch's place in the caller's read set and `pos`, to which it adds what the entry point reports as found; a code other than
+// FIN_OK and a message in `e` end the search.  Products whose sub-batches land one behind the other in a caller buffer (text, records, segments) name their
+// Landing: the pipeline sizes it and gives it up when a worker fails.  Without a product the pairs themselves come back (fin_search_batch, _multi)
+struct SubBatch { size_t i; uint64_t lo, hi, pair_off; };   // reads [lo, hi) of the caller's set; pair_off: the k-mers of the range's reads before lo
+struct Product {
+    uint64_t group = 1;   // reads that a sub-batch boundary never separates (2: interleaved mates)
+    Landing* landing = nullptr;
+    std::function<int(fin_batch*, const SubBatch&, uint64_t& pos, char* e, size_t elen)> take;
 };
 
 static int search_range_on(const fin_index* idx, int device, const char* bases, const uint64_t* offsets, uint64_t lo, uint64_t hi,
-                           int strands, int32_t* pairs_out, uint64_t* n_positive, char* err, size_t errlen, TextSink* ts = nullptr) {
+                           int strands, int32_t* pairs_out, uint64_t* n_positive, char* err, size_t errlen, const Product* product = nullptr) {
     // A device batch addresses k-mers and bases with 32 bits (also bounds the HBM one sub-batch takes)
     const uint64_t MAX_BASES = 1ull << 31, MAX_READS = 1ull << 26;
     const uint64_t MAX_KMERS = std::min<uint64_t>((uint64_t)optv(idx, O_max_batch_kmers), (uint64_t)optv(idx, O_pipeline_kmers));
-    const uint64_t k = idx->k, group = ts ? ts->group : 1;
-    struct Sub { uint64_t lo, hi, pair_off; };
-    std::vector<Sub> subs;
+    const uint64_t k = idx->k, group = product ? product->group : 1;
+    std::vector<SubBatch> subs;
     {
         uint64_t pair_off = 0;
         do {
@@ -2729,11 +2698,12 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
                 if (h2 > lo && (nb + glen > MAX_BASES || nk + gkk > MAX_KMERS || g2 - lo > MAX_READS)) break;
                 nb += glen; nk += gkk; h2 = g2;
             }
-            subs.push_back(Sub{lo, h2, pair_off});
+            subs.push_back(SubBatch{subs.size(), lo, h2, pair_off});
             pair_off += nk; lo = h2;
         } while (lo < hi);
     }
-    if (ts) { ts->len.assign(subs.size(), 0); ts->known.assign(subs.size(), 0); }
+    Landing* const landing = product ? product->landing : nullptr;
+    if (landing) landing->reset(subs.size());
     const uint64_t hi_bases = offsets[subs.back().hi] - offsets[subs.front().lo];
     const int n_workers = (int)std::min<size_t>(subs.size(), (size_t)optv(idx, O_pipeline_depth));
     std::atomic<size_t> next{0};
@@ -2749,7 +2719,7 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
         for (;;) {
             const size_t i = next.fetch_add(1);
             if (i >= subs.size() || first_rc.load() != FIN_OK) break;
-            const Sub& s = subs[i];
+            const SubBatch& s = subs[i];
             int rc = FIN_OK;
             const char* first = bases ? bases + offsets[s.lo] : nullptr;
             const size_t nb = (size_t)(offsets[s.hi] - offsets[s.lo]);
@@ -2772,141 +2742,10 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
                 }
                 if (rc == FIN_OK) rc = batch_load(b, first, offsets + s.lo, s.hi - s.lo, e, sizeof e);
             }
-            if (rc == FIN_OK) { b->text_mode = ts ? 2 : 0; rc = fin_batch_run(b, strands, (void*)b->own_stream, e, sizeof e); }   // (text sink: the text is the only product)
+            if (rc == FIN_OK) { b->text_mode = product ? 2 : 0; rc = fin_batch_run(b, strands, (void*)b->own_stream, e, sizeof e); }   // (a product: the pairs are not kept for the host)
             uint64_t pos = 0;
-            if (rc == FIN_OK && ts && (ts->hits || ts->cover || ts->depth)) {
-                // (behind the run on the batch's own stream: the next batch_load on that stream finds the add done; fin_hits_download waits for the last ones)
-                if (ts->hits) rc = fin_batch_add_hits(b, ts->hits, (void*)b->own_stream, e, sizeof e);
-                if (rc == FIN_OK && ts->cover) rc = fin_batch_add_cover(b, ts->cover, (void*)b->own_stream, e, sizeof e);
-                if (rc == FIN_OK && ts->depth) rc = fin_batch_add_depth(b, ts->depth, (void*)b->own_stream, e, sizeof e);
-            } else
-            if (rc == FIN_OK && ts && ts->seg_offs) {
-                // segments: made behind the run on the device; the sub-batch's land behind those of all earlier sub-batches, its seg_offs at its reads' numbers
-                uint64_t L = 0;
-                rc = fin_batch_segments(b, &L, e, sizeof e);
-                {
-                    std::lock_guard<std::mutex> g(ts->mu);
-                    ts->len[i] = rc == FIN_OK ? L : 0; ts->known[i] = 1;
-                }
-                ts->cv.notify_all();
-                if (rc == FIN_OK) {
-                    uint64_t at = 0;
-                    {
-                        std::unique_lock<std::mutex> g(ts->mu);
-                        ts->cv.wait(g, [&] { for (size_t j = 0; j < i; j++) if (!ts->known[j]) return false; return true; });
-                        for (size_t j = 0; j < i; j++) at += ts->len[j];
-                    }
-                    if (at + L > ts->seg_cap) ts->seg_over.store(true);   // (nothing more is copied; the sub-batches go on being counted, so the caller learns how many there are)
-                    else if (!ts->seg_over.load()) {
-                        std::vector<uint64_t> so((size_t)(s.hi - s.lo) + 1);
-                        rc = fin_batch_download_segments(b, so.data(), ts->segs ? ts->segs + at : nullptr, e, sizeof e);
-                        if (rc == FIN_OK) {
-                            uint64_t* const dst = ts->seg_offs + (s.lo - ts->read0);   // (entry 0 is the sub-batch before's last, or the caller's)
-                            for (size_t r = 1; r < so.size(); r++) dst[r] = so[r] + at;
-                            for (uint64_t q = 0; q < L; q++) { const int32_t n = ts->segs[at + q].len; pos += (uint64_t)(n < 0 ? -(int64_t)n : (int64_t)n); }
-                        }
-                    }
-                }
-            } else
-            if (rc == FIN_OK && ts && ts->rsum) {
-                rc = fin_batch_read_summaries(b, e, sizeof e);
-                fin_read_summary* const dst = ts->rsum + (s.lo - ts->read0);
-                if (rc == FIN_OK) rc = fin_batch_download_read_summaries(b, dst, e, sizeof e);
-                if (rc == FIN_OK) for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_found;
-            } else
-            if (rc == FIN_OK && ts && ts->paint) {
-                rc = fin_batch_add_colors(b, ts->paint, ts->paint_color, (void*)b->own_stream, e, sizeof e);
-            } else
-            if (rc == FIN_OK && ts && ts->psa && ts->group == 2) {
-                rc = fin_batch_pseudoalign_paired(b, ts->psa, ts->psa_permille, ts->pair_mode, e, sizeof e);
-                const uint64_t at = (s.lo - ts->read0) / 2;   // (every sub-batch begins at an even read)
-                fin_pair_pseudo* const dst = ts->psa_pheads + at;
-                if (rc == FIN_OK) rc = fin_batch_download_pair_pseudo(b, ts->psa_rows ? ts->psa_rows + at * fin_colors_words(ts->psa) : nullptr, dst, e, sizeof e);
-                if (rc == FIN_OK) for (uint64_t f = 0; f < (s.hi - s.lo) / 2; f++) pos += dst[f].n_colored;
-            } else
-            if (rc == FIN_OK && ts && ts->eqc && ts->group == 2) {
-                rc = fin_batch_add_eqclasses_paired(b, ts->eqc, ts->eqc_permille, ts->pair_mode, (void*)b->own_stream, e, sizeof e);
-            } else
-            if (rc == FIN_OK && ts && ts->psa) {
-                rc = fin_batch_pseudoalign(b, ts->psa, ts->psa_permille, e, sizeof e);
-                const uint64_t at = s.lo - ts->read0;
-                fin_read_pseudo* const dst = ts->psa_heads + at;
-                if (rc == FIN_OK) rc = fin_batch_download_pseudo(b, ts->psa_rows ? ts->psa_rows + at * fin_colors_words(ts->psa) : nullptr, dst, e, sizeof e);
-                if (rc == FIN_OK) for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_colored;
-            } else
-            if (rc == FIN_OK && ts && ts->eqc) {
-                rc = fin_batch_add_eqclasses(b, ts->eqc, ts->eqc_permille, (void*)b->own_stream, e, sizeof e);
-            } else
-            if (rc == FIN_OK && ts && ts->tally) {
-                rc = fin_batch_add_classes(b, ts->tally, ts->cls_min_found, ts->cls_min_permille, ts->cls_min_margin, (void*)b->own_stream, e, sizeof e);
-            } else
-            if (rc == FIN_OK && ts && ts->cls) {
-                rc = fin_batch_classify(b, ts->labels, e, sizeof e);
-                fin_read_class* const dst = ts->cls + (s.lo - ts->read0);
-                if (rc == FIN_OK) rc = fin_batch_download_read_classes(b, dst, e, sizeof e);
-                if (rc == FIN_OK) for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_labelled;
-            } else
-            if (rc == FIN_OK && ts && ts->screen) {
-                uint64_t np = 0;
-                rc = fin_batch_screen(b, ts->scr_min_found, ts->scr_min_permille, ts->scr_invert, &np, e, sizeof e);
-                if (rc == FIN_OK) ts->scr_pass += np;
-                if (rc == FIN_OK && ts->scr_bits) {
-                    // the sub-batch's bitmap begins at bit 0; in the whole read set's it begins at its first read's bit, which need not start a word
-                    const uint64_t n = s.hi - s.lo, at = s.lo - ts->read0;
-                    std::vector<uint64_t> w((size_t)((n + 63) / 64) + 1, 0);
-                    rc = fin_batch_download_screen(b, nullptr, w.data(), e, sizeof e);
-                    if (rc == FIN_OK) {
-                        const uint32_t sh = (uint32_t)(at & 63);
-                        std::lock_guard<std::mutex> g(ts->mu);   // (neighbouring sub-batches share a word)
-                        for (size_t q = 0; q + 1 < w.size(); q++) {
-                            if (!w[q]) continue;
-                            ts->scr_bits[(at >> 6) + q] |= w[q] << sh;
-                            if (sh && (w[q] >> (64u - sh))) ts->scr_bits[(at >> 6) + q + 1] |= w[q] >> (64u - sh);   // (a set bit is a read below s.hi: the word exists)
-                        }
-                    }
-                }
-            } else
-            if (rc == FIN_OK && ts && ts->recs) {
-                // records: the sub-batch's stream of pairs lands behind the streams of all earlier sub-batches, its records at its reads' numbers
-                uint64_t L = 0;
-                rc = fin_batch_records(b, &L, e, sizeof e);
-                {
-                    std::lock_guard<std::mutex> g(ts->mu);
-                    ts->len[i] = rc == FIN_OK ? L : 0; ts->known[i] = 1;
-                }
-                ts->cv.notify_all();
-                if (rc == FIN_OK) {
-                    uint64_t at = 0;
-                    {
-                        std::unique_lock<std::mutex> g(ts->mu);
-                        ts->cv.wait(g, [&] { for (size_t j = 0; j < i; j++) if (!ts->known[j]) return false; return true; });
-                        for (size_t j = 0; j < i; j++) at += ts->len[j];
-                    }
-                    if (at + L > ts->rcap) { rc = FIN_ELIMIT; snprintf(e, sizeof e, "pair stream buffer too small"); }
-                    else rc = fin_batch_download_records(b, ts->recs + (s.lo - ts->read0), ts->rpairs ? ts->rpairs + 2 * at : nullptr, e, sizeof e);
-                }
-            } else
-            if (rc == FIN_OK && ts) {
-                // the text is made on the device; its place in the caller's buffer is behind the text of all earlier sub-batches
-                uint64_t L = 0;
-                rc = fin_batch_format_text(b, &L, e, sizeof e);
-                {
-                    std::lock_guard<std::mutex> g(ts->mu);
-                    ts->len[i] = rc == FIN_OK ? L : 0; ts->known[i] = 1;
-                }
-                ts->cv.notify_all();
-                if (rc == FIN_OK) {
-                    uint64_t at = 0;
-                    {
-                        std::unique_lock<std::mutex> g(ts->mu);
-                        ts->cv.wait(g, [&] { for (size_t j = 0; j < i; j++) if (!ts->known[j]) return false; return true; });
-                        for (size_t j = 0; j < i; j++) at += ts->len[j];
-                    }
-                    if (at + L > ts->cap) { rc = FIN_ELIMIT; snprintf(e, sizeof e, "text buffer too small"); }
-                    else rc = fin_batch_download_text(b, ts->buf + at, e, sizeof e);
-                    if (rc == FIN_OK && n_positive) rc = fin_batch_download(b, nullptr, &pos, e, sizeof e);
-                }
-            } else
+            if (rc == FIN_OK && product) rc = product->take(b, s, pos, e, sizeof e);
+            else
             if (rc == FIN_OK) {
                 int32_t* dst = pairs_out ? pairs_out + 2 * s.pair_off : nullptr;
                 const size_t ob = (size_t)b->n_kmers * 8;
@@ -2922,10 +2761,7 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
             if (rc != FIN_OK) {
                 int expect = FIN_OK;
                 if (first_rc.compare_exchange_strong(expect, rc)) { std::lock_guard<std::mutex> g(err_mu); set_err(err, errlen, e); }
-                if (ts) {   // nobody may wait for the sub-batches this worker will not do
-                    { std::lock_guard<std::mutex> g(ts->mu); for (size_t j = 0; j < subs.size(); j++) ts->known[j] = 1; }
-                    ts->cv.notify_all();
-                }
+                if (landing) landing->give_up();   // nobody may wait for the sub-batches this worker will not do
                 break;
             }
             pos_total += pos;
@@ -2945,9 +2781,31 @@ static int search_range_on(const fin_index* idx, int device, const char* bases, 
     }
     if (first_rc.load() != FIN_OK) return first_rc.load();
     if (n_positive) *n_positive = pos_total.load();
-    if (ts) { ts->total = 0; for (uint64_t l : ts->len) ts->total += l; }
     return FIN_OK;
 }
+
+// the opening that the fin_search_batch_* entry points share, behind their argument test: where the search runs.  With `beside` (a labelling, a colour matrix, an
+// accumulator) that is its device, and it must belong to the index -- else `other_index` is the message; without, the index's first replica, and there must be one
+static int search_home(const fin_index* idx, const fin_acc* beside, const char* other_index, int* device, char* err, size_t errlen) {
+    if (beside) {
+        if (beside->idx != idx) { set_err(err, errlen, other_index); return FIN_EINVAL; }
+        *device = beside->device;
+        return FIN_OK;
+    }
+    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    *device = idx->replicas[0].device;
+    return FIN_OK;
+}
+// ... and with the argument test of all but the three oldest: `rest_ok` is what the entry point asks of its own pointers (`beside` not null among it)
+static int search_open(const fin_index* idx, const uint64_t* offsets, int strands, bool rest_ok, const fin_acc* beside, const char* other_index, int* device, char* err,
+                       size_t errlen) {
+    if (!idx || !offsets || !rest_ok || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
+    return search_home(idx, beside, other_index, device, err, errlen);
+}
+static const char* const OTHER_LABELS = "the labelling belongs to another index";
+static const char* const OTHER_COLORS = "the colours belong to another index";
+static const char* const OTHER_EQCLASSES = "the equivalence classes belong to another index";
+static const char* const OTHER_ACC = "the accumulator belongs to another index";
 
 // ---- the streaming loop with the reference's text as its result (search_fmin.hh:43-72 including :62-65) ----
 struct fin_text { void* p = nullptr; size_t cap = 0; uint64_t size = 0; };
@@ -2965,10 +2823,19 @@ int fin_text_reserve(fin_text* t, uint64_t bytes) {   // page-lock room ahead of
 const char* fin_text_data(const fin_text* t) { return t ? (const char*)t->p : nullptr; }
 uint64_t fin_text_size(const fin_text* t) { return t ? t->size : 0; }
 
+// the whole read set through the pipeline with a product, on `device`
+static int search_product(const fin_index* idx, int device, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const Product& p,
+                          uint64_t* n_positive, char* err, size_t errlen) {
+    return search_range_on(idx, device, bases, offsets, 0, n_reads, strands, nullptr, n_positive, err, errlen, &p);
+}
+// (an add goes behind the run on the batch's own stream: the next batch_load on that stream finds it done; the accumulator's download waits for the last ones)
+static void* own(const fin_batch* b) { return (void*)b->own_stream; }
+
 int fin_search_batch_text(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_text* out,
                           uint64_t* n_positive, char* err, size_t errlen) {
     if (!idx || !offsets || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    int device = -1;
+    if (const int orc = search_home(idx, nullptr, nullptr, &device, err, errlen)) return orc;
     if (n_positive) *n_positive = 0;
     out->size = 0;
     if (n_reads == 0) return FIN_OK;
@@ -2991,154 +2858,239 @@ int fin_search_batch_text(const fin_index* idx, const char* bases, const uint64_
         if (hipHostMalloc(&out->p, need + need / 16, hipHostMallocDefault) != hipSuccess) { set_err(err, errlen, "page-locked text buffer: out of memory"); return FIN_ENOMEM; }
         out->cap = need + need / 16;
     }
-    TextSink ts; ts.buf = (char*)out->p; ts.cap = out->cap;
-    const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, strands, nullptr, n_positive, err, errlen, &ts);
-    if (rc == FIN_OK) out->size = ts.total;
+    // the text is made on the device; its place in the caller's buffer is behind the text of all earlier sub-batches
+    Landing land;
+    Product p; p.landing = &land;
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t& pos, char* e, size_t elen) -> int {
+        uint64_t L = 0;
+        if (const int rc = fin_batch_format_text(b, &L, e, elen)) return rc;
+        const uint64_t at = land.place(s.i, L);
+        if (at + L > out->cap) { snprintf(e, elen, "text buffer too small"); return FIN_ELIMIT; }
+        if (const int rc = fin_batch_download_text(b, (char*)out->p + at, e, elen)) return rc;
+        return n_positive ? fin_batch_download(b, nullptr, &pos, e, elen) : FIN_OK;
+    };
+    const int rc = search_product(idx, device, bases, offsets, n_reads, strands, p, n_positive, err, errlen);
+    if (rc == FIN_OK) out->size = land.total();
     return rc;
 }
 
 int fin_search_batch_records(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, fin_read_record* recs_out,
                              int32_t* stream_pairs_out, uint64_t stream_cap_pairs, uint64_t* n_stream_pairs, char* err, size_t errlen) {
     if (!idx || !offsets || (n_reads && !recs_out)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    int device = -1;
+    if (const int orc = search_home(idx, nullptr, nullptr, &device, err, errlen)) return orc;
     if (n_stream_pairs) *n_stream_pairs = 0;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.recs = recs_out; ts.rpairs = stream_pairs_out; ts.rcap = stream_pairs_out ? stream_cap_pairs : 0; ts.read0 = 0;
-    const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, FIN_MERGED, nullptr, nullptr, err, errlen, &ts);
-    if (rc == FIN_OK && n_stream_pairs) *n_stream_pairs = ts.total;
+    // the sub-batch's stream of pairs lands behind the streams of all earlier sub-batches, its records at its reads' numbers
+    const uint64_t cap = stream_pairs_out ? stream_cap_pairs : 0;
+    Landing land;
+    Product p; p.landing = &land;
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t&, char* e, size_t elen) -> int {
+        uint64_t L = 0;
+        if (const int rc = fin_batch_records(b, &L, e, elen)) return rc;
+        const uint64_t at = land.place(s.i, L);
+        if (at + L > cap) { snprintf(e, elen, "pair stream buffer too small"); return FIN_ELIMIT; }
+        return fin_batch_download_records(b, recs_out + s.lo, stream_pairs_out ? stream_pairs_out + 2 * at : nullptr, e, elen);
+    };
+    const int rc = search_product(idx, device, bases, offsets, n_reads, FIN_MERGED, p, nullptr, err, errlen);
+    if (rc == FIN_OK && n_stream_pairs) *n_stream_pairs = land.total();
     return rc;
 }
 
 int fin_search_batch_segments(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint64_t* seg_offs_out,
                               fin_segment* segs_out, uint64_t seg_cap, uint64_t* n_segments, uint64_t* n_positive, char* err, size_t errlen) {
-    if (!idx || !offsets || !seg_offs_out || (seg_cap && !segs_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, seg_offs_out && (!seg_cap || segs_out), nullptr, nullptr, &device, err, errlen)) return orc;
     if (n_segments) *n_segments = 0;
     if (n_positive) *n_positive = 0;
     seg_offs_out[0] = 0;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.seg_offs = seg_offs_out; ts.segs = segs_out; ts.seg_cap = segs_out ? seg_cap : 0; ts.read0 = 0;
+    // made behind the run on the device; the sub-batch's segments land behind those of all earlier sub-batches, its seg_offs at its reads' numbers, rebased to the
+    // whole read set.  Once they no longer fit nothing more is copied; the sub-batches go on being counted, so the caller learns how many there are
+    const uint64_t cap = segs_out ? seg_cap : 0;
+    std::atomic<bool> over{false};
+    Landing land;
+    Product p; p.landing = &land;
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t& pos, char* e, size_t elen) -> int {
+        uint64_t L = 0;
+        if (const int rc = fin_batch_segments(b, &L, e, elen)) return rc;
+        const uint64_t at = land.place(s.i, L);
+        if (at + L > cap) { over.store(true); return FIN_OK; }
+        if (over.load()) return FIN_OK;
+        std::vector<uint64_t> so((size_t)(s.hi - s.lo) + 1);
+        if (const int rc = fin_batch_download_segments(b, so.data(), segs_out ? segs_out + at : nullptr, e, elen)) return rc;
+        uint64_t* const dst = seg_offs_out + s.lo;   // (entry 0 is the sub-batch before's last, or the caller's)
+        for (size_t r = 1; r < so.size(); r++) dst[r] = so[r] + at;
+        for (uint64_t q = 0; q < L; q++) { const int32_t n = segs_out[at + q].len; pos += (uint64_t)(n < 0 ? -(int64_t)n : (int64_t)n); }
+        return FIN_OK;
+    };
     uint64_t pos = 0;
-    const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
-    if (rc == FIN_OK && n_segments) *n_segments = ts.total;
-    if (rc == FIN_OK && ts.seg_over.load()) {
-        set_err(err, errlen, "segment buffer too small: room for " + std::to_string(ts.seg_cap) + " segments, " + std::to_string(ts.total) + " needed");
+    const int rc = search_product(idx, device, bases, offsets, n_reads, strands, p, &pos, err, errlen);
+    if (rc != FIN_OK) return rc;
+    const uint64_t total = land.total();
+    if (n_segments) *n_segments = total;
+    if (over.load()) {
+        set_err(err, errlen, "segment buffer too small: room for " + std::to_string(cap) + " segments, " + std::to_string(total) + " needed");
         return FIN_ELIMIT;
     }
-    if (rc == FIN_OK && n_positive) *n_positive = pos;
-    return rc;
+    if (n_positive) *n_positive = pos;
+    return FIN_OK;
 }
 
 int fin_search_batch_read_summaries(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_read_summary* out,
                                     uint64_t* n_positive, char* err, size_t errlen) {
-    if (!idx || !offsets || (n_reads && !out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, !n_reads || out, nullptr, nullptr, &device, err, errlen)) return orc;
     if (n_positive) *n_positive = 0;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.rsum = out; ts.read0 = 0;
-    uint64_t pos = 0;
-    const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
-    if (rc == FIN_OK && n_positive) *n_positive = pos;
-    return rc;
+    Product p;   // a sub-batch's summaries land at its reads' numbers
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t& pos, char* e, size_t elen) -> int {
+        if (const int rc = fin_batch_read_summaries(b, e, elen)) return rc;
+        fin_read_summary* const dst = out + s.lo;
+        if (const int rc = fin_batch_download_read_summaries(b, dst, e, elen)) return rc;
+        for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_found;
+        return FIN_OK;
+    };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, n_positive, err, errlen);
 }
 
 int fin_search_batch_screen(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint32_t min_found, uint32_t min_permille,
                             int invert, uint64_t* bits_out, uint64_t* n_pass, char* err, size_t errlen) {
+    // (not search_open: this entry point tests its threshold before the index's residence, and coinciding faults keep reporting the same one)
     if (!idx || !offsets || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (min_permille > 1000u) { set_err(err, errlen, "min_permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
-    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    if (const int crc = check_permille(min_permille, BAD_MIN_PERMILLE, err, errlen)) return crc;
+    int device = -1;
+    if (const int orc = search_home(idx, nullptr, nullptr, &device, err, errlen)) return orc;
     if (n_pass) *n_pass = 0;
     if (n_reads == 0) return FIN_OK;
     if (bits_out) for (uint64_t w = 0; w < (n_reads + 63) / 64; w++) bits_out[w] = 0;
-    TextSink ts; ts.screen = true; ts.scr_min_found = min_found; ts.scr_min_permille = min_permille; ts.scr_invert = invert; ts.scr_bits = bits_out; ts.read0 = 0;
-    const int rc = search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
-    if (rc == FIN_OK && n_pass) *n_pass = ts.scr_pass.load();
+    std::atomic<uint64_t> pass{0};
+    std::mutex bits_mu;   // (neighbouring sub-batches share a word)
+    Product p;
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t&, char* e, size_t elen) -> int {
+        uint64_t np = 0;
+        if (const int rc = fin_batch_screen(b, min_found, min_permille, invert, &np, e, elen)) return rc;
+        pass += np;
+        if (!bits_out) return FIN_OK;
+        // the sub-batch's bitmap begins at bit 0; in the whole read set's it begins at its first read's bit, which need not start a word
+        const uint64_t n = s.hi - s.lo, at = s.lo;
+        std::vector<uint64_t> w((size_t)((n + 63) / 64) + 1, 0);
+        if (const int rc = fin_batch_download_screen(b, nullptr, w.data(), e, elen)) return rc;
+        const uint32_t sh = (uint32_t)(at & 63);
+        std::lock_guard<std::mutex> g(bits_mu);
+        for (size_t q = 0; q + 1 < w.size(); q++) {
+            if (!w[q]) continue;
+            bits_out[(at >> 6) + q] |= w[q] << sh;
+            if (sh && (w[q] >> (64u - sh))) bits_out[(at >> 6) + q + 1] |= w[q] >> (64u - sh);   // (a set bit is a read below s.hi: the word exists)
+        }
+        return FIN_OK;
+    };
+    const int rc = search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
+    if (rc == FIN_OK && n_pass) *n_pass = pass.load();
     return rc;
 }
 
 int fin_search_batch_classify(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_labels* l,
                               fin_read_class* out, uint64_t* n_positive, char* err, size_t errlen) {
-    if (!idx || !offsets || !l || (n_reads && !out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (l->idx != idx) { set_err(err, errlen, "the labelling belongs to another index"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, l && (!n_reads || out), l, OTHER_LABELS, &device, err, errlen)) return orc;
     if (n_positive) *n_positive = 0;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.labels = l; ts.cls = out; ts.read0 = 0;
-    uint64_t pos = 0;
-    const int rc = search_range_on(idx, l->device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
-    if (rc == FIN_OK && n_positive) *n_positive = pos;
-    return rc;
+    Product p;   // a sub-batch's classes land at its reads' numbers
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t& pos, char* e, size_t elen) -> int {
+        if (const int rc = fin_batch_classify(b, l, e, elen)) return rc;
+        fin_read_class* const dst = out + s.lo;
+        if (const int rc = fin_batch_download_read_classes(b, dst, e, elen)) return rc;
+        for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_labelled;
+        return FIN_OK;
+    };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, n_positive, err, errlen);
 }
 
 int fin_search_batch_add_colors(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_colors* c, uint32_t color, char* err,
                                 size_t errlen) {
-    if (!idx || !offsets || !c || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (c->idx != idx) { set_err(err, errlen, "the colours belong to another index"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, c, c, OTHER_COLORS, &device, err, errlen)) return orc;
     if (color >= c->n_colors) { set_err(err, errlen, "colour " + std::to_string(color) + " is not below n_colors = " + std::to_string(c->n_colors)); return FIN_EINVAL; }
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.paint = c; ts.paint_color = color;
-    return search_range_on(idx, c->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+    Product p;   // every sub-batch's unitigs get the colour on the device, nothing comes back
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_colors(b, c, color, own(b), e, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 
 int fin_search_batch_pseudoalign(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_colors* c, uint32_t permille,
                                  uint64_t* rows_out, fin_read_pseudo* heads_out, uint64_t* n_positive, char* err, size_t errlen) {
-    if (!idx || !offsets || !c || (n_reads && !heads_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (c->idx != idx) { set_err(err, errlen, "the colours belong to another index"); return FIN_EINVAL; }
-    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, c && (!n_reads || heads_out), c, OTHER_COLORS, &device, err, errlen)) return orc;
+    if (const int crc = check_permille(permille, BAD_PERMILLE, err, errlen)) return crc;
     if (n_positive) *n_positive = 0;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.psa = c; ts.psa_permille = permille; ts.psa_rows = rows_out; ts.psa_heads = heads_out; ts.read0 = 0;
-    uint64_t pos = 0;
-    const int rc = search_range_on(idx, c->device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
-    if (rc == FIN_OK && n_positive) *n_positive = pos;
-    return rc;
+    Product p;   // a sub-batch's rows (may be null) and heads land at its reads' numbers
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t& pos, char* e, size_t elen) -> int {
+        if (const int rc = fin_batch_pseudoalign(b, c, permille, e, elen)) return rc;
+        fin_read_pseudo* const dst = heads_out + s.lo;
+        if (const int rc = fin_batch_download_pseudo(b, rows_out ? rows_out + s.lo * c->words : nullptr, dst, e, elen)) return rc;
+        for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_colored;
+        return FIN_OK;
+    };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, n_positive, err, errlen);
 }
 
 int fin_search_batch_pseudoalign_paired(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_colors* c,
                                         uint32_t permille, uint32_t mode, uint64_t* rows_out, fin_pair_pseudo* heads_out, uint64_t* n_positive, char* err, size_t errlen) {
-    if (!idx || !offsets || !c || (n_reads >= 2 && !heads_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (c->idx != idx) { set_err(err, errlen, "the colours belong to another index"); return FIN_EINVAL; }
-    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
-    if (mode != FIN_PAIR_ANY && mode != FIN_PAIR_BOTH) { set_err(err, errlen, "mode is FIN_PAIR_ANY (0) or FIN_PAIR_BOTH (1)"); return FIN_EINVAL; }
-    if (n_reads & 1u) { set_err(err, errlen, "paired pseudoalignment wants interleaved mates: " + std::to_string(n_reads) + " reads are an odd number"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, c && (n_reads < 2 || heads_out), c, OTHER_COLORS, &device, err, errlen)) return orc;
+    if (const int crc = check_permille(permille, BAD_PERMILLE, err, errlen)) return crc;
+    if (const int crc = check_pair_mode(mode, err, errlen)) return crc;
+    if (const int crc = check_even(n_reads, err, errlen)) return crc;
     if (n_positive) *n_positive = 0;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.psa = c; ts.psa_permille = permille; ts.psa_rows = rows_out; ts.psa_pheads = heads_out; ts.read0 = 0; ts.group = 2; ts.pair_mode = mode;
-    uint64_t pos = 0;
-    const int rc = search_range_on(idx, c->device, bases, offsets, 0, n_reads, strands, nullptr, &pos, err, errlen, &ts);
-    if (rc == FIN_OK && n_positive) *n_positive = pos;
-    return rc;
+    // the reads are interleaved mates: a sub-batch ends only after an even number of reads, and the fragments' rows and heads land at the fragments' numbers
+    Product p; p.group = 2;
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t& pos, char* e, size_t elen) -> int {
+        if (const int rc = fin_batch_pseudoalign_paired(b, c, permille, mode, e, elen)) return rc;
+        const uint64_t at = s.lo / 2;   // (every sub-batch begins at an even read)
+        fin_pair_pseudo* const dst = heads_out + at;
+        if (const int rc = fin_batch_download_pair_pseudo(b, rows_out ? rows_out + at * c->words : nullptr, dst, e, elen)) return rc;
+        for (uint64_t f = 0; f < (s.hi - s.lo) / 2; f++) pos += dst[f].n_colored;
+        return FIN_OK;
+    };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, n_positive, err, errlen);
 }
 
 int fin_search_batch_add_classes(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_labels* l, uint32_t min_found,
                                  uint32_t min_permille, uint32_t min_margin, char* err, size_t errlen) {
-    if (!idx || !offsets || !l || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (l->idx != idx) { set_err(err, errlen, "the labelling belongs to another index"); return FIN_EINVAL; }
-    if (min_permille > 1000u) { set_err(err, errlen, "min_permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, l, l, OTHER_LABELS, &device, err, errlen)) return orc;
+    if (const int crc = check_permille(min_permille, BAD_MIN_PERMILLE, err, errlen)) return crc;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.tally = l; ts.cls_min_found = min_found; ts.cls_min_permille = min_permille; ts.cls_min_margin = min_margin;
-    return search_range_on(idx, l->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+    Product p;   // every sub-batch is added to the labelling's tally on the device, nothing comes back
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_classes(b, l, min_found, min_permille, min_margin, own(b), e, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 
 int fin_search_batch_add_eqclasses(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_eqclasses* e, uint32_t permille,
                                    char* err, size_t errlen) {
-    if (!idx || !offsets || !e || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (e->idx != idx) { set_err(err, errlen, "the equivalence classes belong to another index"); return FIN_EINVAL; }
-    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, e, e, OTHER_EQCLASSES, &device, err, errlen)) return orc;
+    if (const int crc = check_permille(permille, BAD_PERMILLE, err, errlen)) return crc;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.eqc = e; ts.eqc_permille = permille;
-    return search_range_on(idx, e->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+    Product p;   // every sub-batch is pseudoaligned and added on the device, nothing comes back
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* em, size_t elen) -> int { return fin_batch_add_eqclasses(b, e, permille, own(b), em, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 
 int fin_search_batch_add_eqclasses_paired(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_eqclasses* e,
                                           uint32_t permille, uint32_t mode, char* err, size_t errlen) {
-    if (!idx || !offsets || !e || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (e->idx != idx) { set_err(err, errlen, "the equivalence classes belong to another index"); return FIN_EINVAL; }
-    if (permille > 1000u) { set_err(err, errlen, "permille is a share in thousandths: 0 .. 1000"); return FIN_EINVAL; }
-    if (mode != FIN_PAIR_ANY && mode != FIN_PAIR_BOTH) { set_err(err, errlen, "mode is FIN_PAIR_ANY (0) or FIN_PAIR_BOTH (1)"); return FIN_EINVAL; }
-    if (n_reads & 1u) { set_err(err, errlen, "paired pseudoalignment wants interleaved mates: " + std::to_string(n_reads) + " reads are an odd number"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, e, e, OTHER_EQCLASSES, &device, err, errlen)) return orc;
+    if (const int crc = check_permille(permille, BAD_PERMILLE, err, errlen)) return crc;
+    if (const int crc = check_pair_mode(mode, err, errlen)) return crc;
+    if (const int crc = check_even(n_reads, err, errlen)) return crc;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.eqc = e; ts.eqc_permille = permille; ts.group = 2; ts.pair_mode = mode;
-    return search_range_on(idx, e->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+    Product p; p.group = 2;   // (interleaved mates: no sub-batch splits a pair)
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* em, size_t elen) -> int { return fin_batch_add_eqclasses_paired(b, e, permille, mode, own(b), em, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 
 // the index's numbers of the caller's unitigs: each one's first k-mer, searched forward, must come back as (u, 0)
@@ -3169,20 +3121,21 @@ int fin_index_unitig_numbers(const fin_index* idx, const char* bases, const uint
 }
 
 int fin_search_batch_add_hits(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_hits* h, char* err, size_t errlen) {
-    if (!idx || !offsets || !h || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (h->idx != idx) { set_err(err, errlen, "the accumulator belongs to another index"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, h, h, OTHER_ACC, &device, err, errlen)) return orc;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.hits = h;
-    return search_range_on(idx, h->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+    Product p;   // every sub-batch is added on the device, nothing comes back
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_hits(b, h, own(b), e, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 
 int fin_search_batch_unitig_counts(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint64_t* counts_out,
                                    uint64_t* n_positive, char* err, size_t errlen) {
-    if (!idx || !offsets || (idx->n_unitigs && !counts_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, !(idx && idx->n_unitigs && !counts_out), nullptr, nullptr, &device, err, errlen)) return orc;
     if (n_positive) *n_positive = 0;
     fin_hits* h = nullptr;
-    int rc = fin_hits_create(idx, idx->replicas[0].device, &h, err, errlen);
+    int rc = fin_hits_create(idx, device, &h, err, errlen);
     if (rc != FIN_OK) return rc;
     rc = fin_search_batch_add_hits(idx, bases, offsets, n_reads, strands, h, err, errlen);
     if (rc == FIN_OK) rc = fin_hits_download(h, counts_out, n_positive, err, errlen);
@@ -3191,26 +3144,30 @@ int fin_search_batch_unitig_counts(const fin_index* idx, const char* bases, cons
 }
 
 int fin_search_batch_add_cover(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_cover* c, char* err, size_t errlen) {
-    if (!idx || !offsets || !c || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (c->idx != idx) { set_err(err, errlen, "the accumulator belongs to another index"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, c, c, OTHER_ACC, &device, err, errlen)) return orc;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.cover = c;
-    return search_range_on(idx, c->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+    Product p;
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_cover(b, c, own(b), e, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 
 int fin_search_batch_unitig_coverage(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint64_t* covered_out,
                                      uint64_t* n_positive, char* err, size_t errlen) {
-    if (!idx || !offsets || (idx->n_unitigs && !covered_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, !(idx && idx->n_unitigs && !covered_out), nullptr, nullptr, &device, err, errlen)) return orc;
     if (n_positive) *n_positive = 0;
-    const int device = idx->replicas[0].device;
     fin_cover* c = nullptr;
     fin_hits* h = nullptr;   // the found k-mers are a sum of depths, which the bitmap does not hold: asked for, they come from a profile added behind the same runs
     int rc = fin_cover_create(idx, device, &c, err, errlen);
     if (rc == FIN_OK && n_positive) rc = fin_hits_create(idx, device, &h, err, errlen);
     if (rc == FIN_OK && n_reads) {
-        TextSink ts; ts.cover = c; ts.hits = h;
-        rc = search_range_on(idx, device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+        Product p;   // both adds go behind the same run
+        p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int {
+            if (h) if (const int hrc = fin_batch_add_hits(b, h, own(b), e, elen)) return hrc;
+            return fin_batch_add_cover(b, c, own(b), e, elen);
+        };
+        rc = search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
     }
     if (rc == FIN_OK) rc = fin_cover_download(c, nullptr, covered_out, nullptr, err, errlen);
     if (rc == FIN_OK && h) rc = fin_hits_download(h, nullptr, n_positive, err, errlen);
@@ -3219,20 +3176,21 @@ int fin_search_batch_unitig_coverage(const fin_index* idx, const char* bases, co
 }
 
 int fin_search_batch_add_depth(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_depth* d, char* err, size_t errlen) {
-    if (!idx || !offsets || !d || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (d->idx != idx) { set_err(err, errlen, "the accumulator belongs to another index"); return FIN_EINVAL; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, d, d, OTHER_ACC, &device, err, errlen)) return orc;
     if (n_reads == 0) return FIN_OK;
-    TextSink ts; ts.depth = d;
-    return search_range_on(idx, d->device, bases, offsets, 0, n_reads, strands, nullptr, nullptr, err, errlen, &ts);
+    Product p;
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_depth(b, d, own(b), e, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 
 int fin_search_batch_unitig_depth(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, uint32_t min_depth,
                                   fin_depth_stat* stats_out, uint64_t* n_positive, char* err, size_t errlen) {
-    if (!idx || !offsets || (idx->n_unitigs && !stats_out) || (strands != FIN_FWD && strands != FIN_MERGED)) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
-    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, !(idx && idx->n_unitigs && !stats_out), nullptr, nullptr, &device, err, errlen)) return orc;
     if (n_positive) *n_positive = 0;
     fin_depth* d = nullptr;
-    int rc = fin_depth_create(idx, idx->replicas[0].device, &d, err, errlen);
+    int rc = fin_depth_create(idx, device, &d, err, errlen);
     if (rc != FIN_OK) return rc;
     rc = fin_search_batch_add_depth(idx, bases, offsets, n_reads, strands, d, err, errlen);
     if (rc == FIN_OK) rc = fin_depth_download(d, min_depth, nullptr, stats_out, n_positive, err, errlen);   // (the found k-mers are the sum of the depths)
@@ -3243,9 +3201,10 @@ int fin_search_batch_unitig_depth(const fin_index* idx, const char* bases, const
 int fin_search_batch(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands,
                      int32_t* pairs_out, uint64_t* n_positive, char* err, size_t errlen) {
     if (!idx || !offsets) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    if (idx->replicas.empty()) { set_err(err, errlen, "index is not resident on a device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    int device = -1;
+    if (const int orc = search_home(idx, nullptr, nullptr, &device, err, errlen)) return orc;
     if (n_positive) *n_positive = 0;
-    return search_range_on(idx, idx->replicas[0].device, bases, offsets, 0, n_reads, strands, pairs_out, n_positive, err, errlen);
+    return search_range_on(idx, device, bases, offsets, 0, n_reads, strands, pairs_out, n_positive, err, errlen);
 }
 
 int fin_search_batch_multi(fin_index* idx, const int* devices, int n_devices, const char* bases, const uint64_t* offsets,

@@ -3,8 +3,8 @@ begins, or a grid-stride loop makes its second trip.  Every other test stays bel
 32-bit carry would shift offsets only for batches of the size real users run.
 
 | kernel                                                        | first level ends at     | reached here by                                                        |
-| fin_rec_scan_kernel (fin_records.hip), 1024 reads a block     | 1 048 576 reads         | N = 1 050 923 reads: 1027 blocks, per = 2, thread 513 has one block    |
-| fin_sgm_scan_kernel (fin_segments.hip; the screen's ids too)  | 262 144 reads           | the same N: 4106 blocks, per = 5, thread 821 has one; 300 000 real reads |
+| fin_blk_scan_kernel (fin_records.hip) over records' blocks    | 1 048 576 reads         | N = 1 050 923 reads: 1027 blocks, per = 2, thread 513 has one block    |
+| fin_blk_scan_kernel over segments' blocks (screen's ids too)  | 262 144 reads           | the same N: 4106 blocks, per = 5, thread 821 has one; 300 000 real reads |
 | fin_text_scan1/2 over segments (text from records)            | 1 048 576 reads         | the same N: 257 chunks, per = 2 in scan2, n_found over 257 chunks      |
 | fin_text_scan1/2 over pair blocks (text from pairs)           | 4 194 304 pairs         | the same N in text mode 0: more than 4097 blocks, chunk_base[1] != 0   |
 | fin_depth_tile_scan_kernel (fin_depth.hip), tile 4096         | 4 194 304 positions     | a 4.5 Mbp index: more than 1024 tiles, per = 2                         |
@@ -428,7 +428,7 @@ def dev():
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", [1, 2])
 def test_records_and_stream_past_one_block_a_thread(mode, dev):
-    """fin_rec_scan_kernel with per = 2: the records byte for byte with nk stamped, the stream = the searched reads' pairs in read order"""
+    """fin_blk_scan_kernel over the records' blocks with per = 2: the records byte for byte with nk stamped, the stream = the searched reads' pairs in read order"""
     c, b = case(), dev.injected(mode)
     got_recs, got_stream = b.records()
     assert len(got_stream) == len(c.stream), "text mode %d: a stream of %d pairs, expected %d" % (mode, len(got_stream), len(c.stream))
@@ -440,7 +440,7 @@ def test_records_and_stream_past_one_block_a_thread(mode, dev):
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", [1, 2, 0])
 def test_segments_past_one_block_a_thread(mode, dev):
-    """fin_sgm_scan_kernel with per = 5 and a partial last thread; mode 0: every read scanned from hand-made pairs"""
+    """fin_blk_scan_kernel over the segments' blocks with per = 5 and a partial last thread; mode 0: every read scanned from hand-made pairs"""
     b = dev.injected(mode)
     (want_offs, want_segs) = want("segments")
     got_offs, got_segs = b.segments()
@@ -517,7 +517,7 @@ def genome_reads(rng, g, n, k):
 
 @pytest.mark.gpu
 def test_one_real_run_past_the_segment_threshold(dev):
-    """300 000 genome reads in text mode 2 -- 1172 blocks of 256 reads, per = 2 in fin_sgm_scan_kernel -- against the oracle: records + stream by brute_expand's
+    """300 000 genome reads in text mode 2 -- 1172 blocks of 256 reads, per = 2 in fin_blk_scan_kernel -- against the oracle: records + stream by brute_expand's
     rule, the segments, a screen, the text, and the classes and their tally through Labels.add_reads"""
     c = case()
     n = 300_000
