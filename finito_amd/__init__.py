@@ -190,6 +190,18 @@ def lib():
         L.fin_search_batch_add_depth.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
         L.fin_search_batch_unitig_depth.argtypes = [vp, cp, u64p, u64, C.c_int, C.c_uint32, vp, u64p, cp, C.c_size_t]
         L.fin_records_depth.argtypes = [vp, u64, vp, u64, C.c_int, i64p, u64, vp, C.c_int]
+        L.fin_pileup_create.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_pileup_reset.argtypes = [vp, vp]
+        L.fin_batch_add_pileup.argtypes = [vp, vp, vp, cp, C.c_size_t]
+        L.fin_pileup_device_alt.restype = vp
+        L.fin_pileup_device_alt.argtypes = [vp]
+        L.fin_pileup_device_cover_diff.restype = vp
+        L.fin_pileup_device_cover_diff.argtypes = [vp]
+        L.fin_pileup_download.argtypes = [vp, vp, vp, u64p, cp, C.c_size_t]
+        L.fin_pileup_call.argtypes = [vp, C.c_uint32, C.c_uint32, vp, u64, u64p, cp, C.c_size_t]
+        L.fin_pileup_free.argtypes = [vp]
+        L.fin_search_batch_add_pileup.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
+        L.fin_records_pileup.argtypes = [vp, u64, vp, u64, C.c_int, cp, u64p, i64p, u64, vp, C.c_uint32, vp, vp, u64p, C.c_int]
         L.fin_batch_segments.argtypes = [vp, u64p, cp, C.c_size_t]
         L.fin_batch_device_segments.argtypes = [vp]
         L.fin_batch_device_segments.restype = vp
@@ -1061,6 +1073,61 @@ class Depth(_Accumulator):
         return int(self.L.fin_depth_device_diff(self.h) or 0)
 
 
+class Pileup(_Accumulator):
+    """which base was seen at each position of the concatenated unitig text, resident in HBM beside one replica of the index (fin_pileup_* of the C ABI;
+    DESIGN.md 4.19): cover[g] = the placed reads that span g, alt[g][b] = how many of them show base b where the text has another.  A read counts when its found
+    k-mers lie on one diagonal of one unitig, the whole read lies inside that unitig and it has at most max_mismatch mismatches."""
+    _FREE, _RESET = "fin_pileup_free", "fin_pileup_reset"
+
+    def __init__(self, index, device=0, max_mismatch=8):
+        self.index = index
+        self.n_unitigs = index.n_unitigs
+        self.total_len = index.total_len
+        self.max_mismatch = int(max_mismatch)
+        if not 0 <= self.max_mismatch <= 255:
+            raise FinitoError(FIN_EINVAL, "Pileup: max_mismatch is 0 .. 255")
+        self._create("fin_pileup_create", index.h, int(device), self.max_mismatch)
+
+    def add(self, batch, stream=None):
+        """pileup += the reads of the batch's most recent run, on a HIP stream, behind that run; no sync (fin_batch_add_pileup).  Adding the same run twice
+        counts it twice."""
+        return _acc_add(self, "fin_batch_add_pileup", batch, stream)
+
+    def add_reads(self, reads, strands=FIN_MERGED):
+        """search a read set from host buffers, sub-batches pipelined as in search_reads, and add its reads; nothing comes back (fin_search_batch_add_pileup)"""
+        return _acc_add_reads(self, "fin_search_batch_add_pileup", reads, strands)
+
+    def download(self):
+        """(uint32 cover[total_len], uint32 alt[total_len, 4], uint64 counters[4] = reads kept, not straight, off their unitig, with too many mismatches); waits
+        for the adds, runs cover's prefix sum on the device and leaves the accumulator as it is (fin_pileup_download)"""
+        cover = np.zeros(max(self.total_len, 1), dtype=np.uint32)
+        alt = np.zeros((max(self.total_len, 1), 4), dtype=np.uint32)
+        counters = np.zeros(4, dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_pileup_download(self.h, cover.ctypes.data_as(C.c_void_p), alt.ctypes.data_as(C.c_void_p), counters.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          err, 512), err)
+        return cover[: self.total_len], alt[: self.total_len], counters
+
+    def call(self, min_alt=2, min_permille=200, cap=None):
+        """the candidate positions as a VARIANT_DTYPE array, ascending: those whose greatest alt count m has m >= max(min_alt, 1) and
+        1000 m >= min_permille * cover (fin_pileup_call).  cap: room for so many -- FinitoError FIN_ELIMIT beyond; None: as many as there are"""
+        err = C.create_string_buffer(512)
+        n = C.c_uint64(0)
+        room = 1024 if cap is None else int(cap)
+        while True:
+            out = np.zeros(max(room, 1), dtype=VARIANT_DTYPE)
+            rc = self.L.fin_pileup_call(self.h, int(min_alt), int(min_permille), out.ctypes.data_as(C.c_void_p), room, C.byref(n), err, 512)
+            if rc == FIN_ELIMIT and cap is None and int(n.value) > room:
+                room = int(n.value)
+                continue
+            _check(rc, err)
+            return out[: int(n.value)]
+
+    def device_ptrs(self):
+        """(alt uint32[total_len][4], cover's difference array int32[total_len + 1]) in HBM"""
+        return int(self.L.fin_pileup_device_alt(self.h) or 0), int(self.L.fin_pileup_device_cover_diff(self.h) or 0)
+
+
 class FinimizerIndex:
     """Mirror of the reference class (FinimizerIndex.hh:26-259) backed by the HIP path."""
 
@@ -1466,6 +1533,10 @@ class FinimizerIndex:
         """a zeroed per-position depth accumulator beside the replica on `device` (Depth)"""
         return Depth(self, device)
 
+    def pileup(self, max_mismatch=8, device=0):
+        """a zeroed base pileup beside the replica on `device` (Pileup)"""
+        return Pileup(self, device, max_mismatch)
+
     def unitig_depth(self, reads, strands=FIN_MERGED, min_depth=1):
         """the depth of a read set over host buffers, per unitig (fin_search_batch_unitig_depth): (DEPTH_STAT_DTYPE stats[n_unitigs], total_positive) -- each
         unitig's summed and greatest depth and how many of its positions were found at least min_depth times; only the statistics come back from the device"""
@@ -1526,6 +1597,7 @@ PAIR_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), 
 FIN_PAIR_ANY, FIN_PAIR_BOTH = 0, 1
 FIN_MAX_COLORS = 4096
 DEPTH_STAT_DTYPE = np.dtype([("sum", np.uint64), ("max", np.uint32), ("n_at_least", np.uint32)])            # fin_depth_stat
+VARIANT_DTYPE = np.dtype([("u", np.uint32), ("off", np.uint32), ("cover", np.uint32), ("ref", np.uint32), ("alt", np.uint32, (4,))])   # fin_variant
 
 
 class PartitionedBatch:
@@ -1722,6 +1794,27 @@ def records_depth(recs, stream, k, ends, n_threads=0):
     if rc != 0:
         raise FinitoError(rc, "fin_records_depth: a unitig number outside the index, a k-mer that does not lie inside its unitig, or records and stream do not belong together")
     return out[:total_len]
+
+
+def records_pileup(recs, stream, k, reads, ends, concat, max_mismatch=8, n_threads=0):
+    """fin_records_pileup (host): (cover uint32[ends[-1]], alt uint32[ends[-1], 4], counters uint64[4]) from records + stream and the reads themselves (as
+    flatten takes them), every placed read compared with the text whole; `ends` as export(X_ENDS), `concat` as export(X_CONCAT)"""
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE); stream = np.ascontiguousarray(stream, dtype=np.int32)
+    ends = np.ascontiguousarray(ends, dtype=np.int64); concat = np.ascontiguousarray(concat, dtype=np.uint8)
+    total_len = int(ends[-1]) if len(ends) else 0
+    bases, offsets, n_reads = _reads_args(reads)
+    if n_reads != len(recs) or len(concat) < total_len:
+        raise FinitoError(FIN_EINVAL, "records_pileup: %d reads for %d records, or a text shorter than the unitigs' ends" % (n_reads, len(recs)))
+    cover = np.zeros(max(total_len, 1), dtype=np.uint32)
+    alt = np.zeros((max(total_len, 1), 4), dtype=np.uint32)
+    counters = np.zeros(4, dtype=np.uint64)
+    rc = lib().fin_records_pileup(recs.ctypes.data_as(C.c_void_p), len(recs), stream.ctypes.data_as(C.c_void_p), len(stream.reshape(-1, 2)), int(k), bases, offsets,
+                                  ends.ctypes.data_as(C.POINTER(C.c_int64)), len(ends), concat.ctypes.data_as(C.c_void_p), int(max_mismatch),
+                                  cover.ctypes.data_as(C.c_void_p), alt.ctypes.data_as(C.c_void_p), counters.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_pileup: a unitig number outside the index, a k-mer that does not lie inside its unitig, records and stream or reads that do "
+                              "not belong together, or max_mismatch above 255")
+    return cover[:total_len], alt[:total_len], counters
 
 
 def expand_segments(seg_offs, segs, nk_per_read, n_threads=0):

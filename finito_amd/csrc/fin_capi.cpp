@@ -1432,7 +1432,7 @@ int fin_batch_download_screen(fin_batch* b, uint32_t* ids_out, uint64_t* bits_ou
 }
 
 // ---- the profile over the unitig set (fin_hits.hip) ---------------------------------------------------------------------------------
-// what the download of a device accumulator (fin_hits, fin_cover, fin_depth) waits for: an event per stream that work on the accumulator was put on
+// what the download of a device accumulator (fin_hits, fin_cover, fin_depth, fin_pileup) waits for: an event per stream that work on the accumulator was put on
 extern "C++" {   // (templates among them)
 struct AccPending {
     std::mutex mu; std::vector<std::pair<hipStream_t, hipEvent_t>> pending;
@@ -1489,7 +1489,7 @@ private:   // (with `mu` held)
         return FIN_OK;
     }
 };
-// what the six device accumulators are alike in (they are opaque in finito_amd.h): the index and device they live beside, and what their readers wait for
+// what the seven device accumulators are alike in (they are opaque in finito_amd.h): the index and device they live beside, and what their readers wait for
 struct fin_acc {
     const fin_index* idx = nullptr;
     int device = -1;
@@ -2584,6 +2584,147 @@ int fin_depth_download(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, fi
     return FIN_OK;
 }
 
+// ---- base pileup over the unitig text (fin_pileup.hip) -----------------------------------------------------------------------------------
+struct fin_pileup : fin_acc {
+    uint64_t n_unitigs = 0, total_len = 0;
+    uint32_t max_mismatch = 0;
+    const uint32_t* d_ends = nullptr;     // the replica's ends_p
+    const uint32_t* d_concat = nullptr;   // ... and its 2-bit text
+    // one allocation, zeroed by one memset: uint32 alt[total_len][4], the four counters (u64), the flag word in a 16-byte line of its own, int32 cov_diff[total_len + 1]
+    void* d_buf = nullptr;
+    // fin_pileup_download's and fin_pileup_call's: made by the first of them, kept
+    uint32_t* d_stage = nullptr;          // uint32[stage_len]: one chunk's cover
+    uint32_t* d_tile = nullptr;           // uint32[fin_depth_max_chunk_tiles()]: the chunk's tile sums, then the carry word
+    uint32_t* d_blk_sum = nullptr;        // the call's per-block counts of a chunk, fin_pileup_call_blocks(call chunk) of them
+    uint64_t* d_blk_off = nullptr;        // ... their offsets, then the chunk's total
+    void* d_ent = nullptr;                // fin_variant[call chunk]: a chunk's entries
+    uint64_t stage_len = 0;
+    std::mutex scan_mu;                   // one download or call at a time scans through the staging buffers
+};
+static_assert(sizeof(fin_variant) == 32, "fin_variant is two 16-byte stores of the call's writing pass");
+static const uint32_t PILEUP_CALL_CHUNK_TILES = 256;   // a call's chunk: at most 256 tiles of 4096 positions -- 32 MB of entries if every position were a candidate
+static uint64_t* pileup_counters(const fin_pileup* p) { return (uint64_t*)((uint8_t*)p->d_buf + p->total_len * 16); }
+static uint32_t* pileup_flags(const fin_pileup* p) { return (uint32_t*)((uint8_t*)p->d_buf + p->total_len * 16 + 32); }
+static int32_t* pileup_diff(const fin_pileup* p) { return (int32_t*)((uint8_t*)p->d_buf + p->total_len * 16 + 48); }
+static size_t pileup_bytes(const fin_pileup* p) { return (size_t)p->total_len * 16 + 48 + (size_t)(p->total_len + 1) * 4; }
+static const char* const PILEUP_WITHHELD = "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)";
+static const char* const PILEUP_OUTSIDE = "a slot or a record outside the index was met (not counted)";
+
+void fin_pileup_free(fin_pileup* p) {
+    if (!acc_free_open(p)) return;
+    (void)hipFree(p->d_buf); (void)hipFree(p->d_stage); (void)hipFree(p->d_tile); (void)hipFree(p->d_blk_sum); (void)hipFree(p->d_blk_off); (void)hipFree(p->d_ent);
+    delete p;
+}
+
+int fin_pileup_create(const fin_index* idx, int device, uint32_t max_mismatch, fin_pileup** out, char* err, size_t errlen) {
+    if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (max_mismatch > 255u) { set_err(err, errlen, "max_mismatch is 0 .. 255"); return FIN_EINVAL; }
+    const fin_index::Replica* rep = nullptr;
+    if (const int orc = acc_create_open(idx, device, &rep, err, errlen)) return orc;
+    fin_pileup* p = acc_new<fin_pileup>(idx, device, err, errlen);
+    if (!p) return FIN_ENOMEM;
+    p->n_unitigs = idx->n_unitigs; p->total_len = idx->total_len; p->max_mismatch = max_mismatch; p->d_ends = rep->dev.ends; p->d_concat = rep->dev.concat;
+    if (const int arc = acc_alloc_zero(p, &p->d_buf, pileup_bytes(p), pileup_bytes(p), "out of device memory (pileup: 20 bytes per indexed base)", fin_pileup_free, err, errlen)) return arc;
+    *out = p;
+    return FIN_OK;
+}
+
+int fin_pileup_reset(fin_pileup* p, void* hip_stream) {
+    return acc_reset(p, hip_stream, p ? p->d_buf : nullptr, p ? pileup_bytes(p) : 0);
+}
+
+void* fin_pileup_device_alt(const fin_pileup* p) { return p ? p->d_buf : nullptr; }
+void* fin_pileup_device_cover_diff(const fin_pileup* p) { return p ? (void*)pileup_diff(p) : nullptr; }
+
+int fin_batch_add_pileup(fin_batch* b, fin_pileup* p, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !p) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (const int orc = acc_add_open(b, p, st, err, errlen)) return orc;
+    const int rc = p->n_unitigs == 0 || p->total_len == 0 ? 0 :
+        fin_launch_pileup_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, b->d_bases, (const uint64_t*)b->d_offs, (uint32_t)b->n_reads,
+                              b->dev.k, p->d_ends, p->d_concat, (uint32_t)p->n_unitigs, p->total_len, p->max_mismatch, p->d_buf, pileup_diff(p), pileup_counters(p),
+                              pileup_flags(p), b->d_ovf_count, b->last_ovf_cap, st);
+    return acc_add_close(p, st, rc, "pileup kernel: ", err, errlen);
+}
+
+// the staging buffers of the download and the call (with scan_mu held); the tile and the chunk's tiles as fin_depth_download takes them from "debug_depth_tile"
+static int pileup_stage(fin_pileup* p, bool for_call, uint32_t* tile, uint32_t* chunk_tiles, char* err, size_t errlen) {
+    const uint32_t dbg = (uint32_t)optv(p->idx, O_debug_depth_tile);
+    *tile = dbg ? dbg : fin_depth_max_tile(); *chunk_tiles = dbg ? 64u : fin_depth_max_chunk_tiles();
+    if (for_call) *chunk_tiles = std::min(*chunk_tiles, PILEUP_CALL_CHUNK_TILES);
+    auto room = [&](void** q, size_t bytes, const char* what) {
+        if (*q || hipMalloc(q, bytes) == hipSuccess) return FIN_OK;
+        (void)hipGetLastError(); *q = nullptr; set_err(err, errlen, what); return FIN_ENOMEM;
+    };
+    if (!p->d_stage) p->stage_len = std::min<uint64_t>((uint64_t)fin_depth_max_tile() * fin_depth_max_chunk_tiles(), p->total_len);
+    if (const int rc = room((void**)&p->d_stage, (size_t)p->stage_len * 4, "out of device memory (pileup staging buffer)")) return rc;
+    if (const int rc = room((void**)&p->d_tile, ((size_t)fin_depth_max_chunk_tiles() + 1) * 4, "out of device memory (pileup tile sums)")) return rc;
+    if (!for_call) return FIN_OK;
+    const uint64_t call_chunk = std::min<uint64_t>((uint64_t)fin_depth_max_tile() * PILEUP_CALL_CHUNK_TILES, p->total_len);
+    const size_t nb = fin_pileup_call_blocks(call_chunk);
+    if (const int rc = room((void**)&p->d_blk_sum, nb * 4, "out of device memory (pileup call)")) return rc;
+    if (const int rc = room((void**)&p->d_blk_off, (nb + 1) * 8, "out of device memory (pileup call)")) return rc;
+    return room(&p->d_ent, (size_t)call_chunk * sizeof(fin_variant), "out of device memory (pileup call entries)");
+}
+
+int fin_pileup_download(fin_pileup* p, uint32_t* cover_out, uint32_t* alt_out, uint64_t counters_out[4], char* err, size_t errlen) {
+    if (!p) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(p, pileup_flags(p), PILEUP_WITHHELD, PILEUP_OUTSIDE, err, errlen)) return orc;
+    if (counters_out) HIPCHK(hipMemcpy(counters_out, pileup_counters(p), 32, hipMemcpyDeviceToHost));
+    if (p->total_len == 0 || p->n_unitigs == 0) return FIN_OK;
+    if (alt_out) HIPCHK(hipMemcpy(alt_out, p->d_buf, (size_t)p->total_len * 16, hipMemcpyDeviceToHost));
+    if (!cover_out) return FIN_OK;
+    std::lock_guard<std::mutex> g(p->scan_mu);
+    uint32_t tile = 0, chunk_tiles = 0;
+    if (const int src = pileup_stage(p, false, &tile, &chunk_tiles, err, errlen)) return src;
+    const uint64_t chunk = (uint64_t)tile * chunk_tiles;
+    uint32_t* const d_carry = p->d_tile + fin_depth_max_chunk_tiles();
+    HIPCHK(hipMemsetAsync(d_carry, 0, 4, nullptr));
+    for (uint64_t base = 0; base < p->total_len; base += chunk) {
+        const uint64_t n = std::min<uint64_t>(chunk, p->total_len - base);
+        const int rc = fin_launch_depth_scan_chunk(pileup_diff(p) + base, n, tile, p->d_tile, d_carry, p->d_stage, nullptr);
+        if (rc != 0) { set_err(err, errlen, std::string("pileup scan kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+        HIPCHK(hipMemcpy(cover_out + base, p->d_stage, (size_t)n * 4, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels, and done before the next chunk is staged)
+    }
+    return FIN_OK;
+}
+
+int fin_pileup_call(fin_pileup* p, uint32_t min_alt, uint32_t min_permille, fin_variant* out, uint64_t cap, uint64_t* n_out, char* err, size_t errlen) {
+    if (!p || !n_out || (cap && !out)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *n_out = 0;
+    if (const int prc = check_permille(min_permille, BAD_MIN_PERMILLE, err, errlen)) return prc;
+    if (const int orc = acc_download_open(p, pileup_flags(p), PILEUP_WITHHELD, PILEUP_OUTSIDE, err, errlen)) return orc;
+    if (p->total_len == 0 || p->n_unitigs == 0) return FIN_OK;
+    std::lock_guard<std::mutex> g(p->scan_mu);
+    uint32_t tile = 0, chunk_tiles = 0;
+    if (const int src = pileup_stage(p, true, &tile, &chunk_tiles, err, errlen)) return src;
+    const uint64_t chunk = (uint64_t)tile * chunk_tiles;
+    uint32_t* const d_carry = p->d_tile + fin_depth_max_chunk_tiles();
+    uint64_t* const d_total = p->d_blk_off + fin_pileup_call_blocks(std::min<uint64_t>((uint64_t)fin_depth_max_tile() * PILEUP_CALL_CHUNK_TILES, p->total_len));
+    HIPCHK(hipMemsetAsync(d_carry, 0, 4, nullptr));
+    uint64_t total = 0;
+    // every chunk is counted, so that the count is the true one also when the entries do not fit; they are written only while they do
+    for (uint64_t base = 0; base < p->total_len; base += chunk) {
+        const uint64_t n = std::min<uint64_t>(chunk, p->total_len - base);
+        const uint32_t* const alt = (const uint32_t*)p->d_buf + base * 4;
+        int rc = fin_launch_depth_scan_chunk(pileup_diff(p) + base, n, tile, p->d_tile, d_carry, p->d_stage, nullptr);
+        if (rc == 0) rc = fin_launch_pileup_call_count(p->d_stage, alt, n, min_alt, min_permille, p->d_blk_sum, p->d_blk_off, d_total, nullptr);
+        if (rc != 0) { set_err(err, errlen, std::string("pileup call kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+        uint64_t c = 0;
+        HIPCHK(hipMemcpy(&c, d_total, 8, hipMemcpyDeviceToHost));
+        if (c && total + c <= cap) {
+            rc = fin_launch_pileup_call_write(p->d_stage, alt, base, n, min_alt, min_permille, p->d_ends, p->d_concat, (uint32_t)p->n_unitigs, p->d_blk_off, p->d_ent, nullptr);
+            if (rc != 0) { set_err(err, errlen, std::string("pileup call kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+            HIPCHK(hipMemcpy(out + total, p->d_ent, (size_t)c * sizeof(fin_variant), hipMemcpyDeviceToHost));
+        }
+        total += c;
+    }
+    *n_out = total;
+    if (total > cap) { set_err(err, errlen, std::to_string(total) + " candidates, room for " + std::to_string(cap)); return FIN_ELIMIT; }
+    return FIN_OK;
+}
+
 int fin_batch_step_time(const fin_batch* b, uint64_t skip_first, double ms_parts[5], uint64_t* n_runs) {
     if (!b) return FIN_EINVAL;
     double t[5] = {0, 0, 0, 0, 0}; uint64_t n = 0;
@@ -3196,6 +3337,15 @@ int fin_search_batch_unitig_depth(const fin_index* idx, const char* bases, const
     if (rc == FIN_OK) rc = fin_depth_download(d, min_depth, nullptr, stats_out, n_positive, err, errlen);   // (the found k-mers are the sum of the depths)
     fin_depth_free(d);
     return rc;
+}
+
+int fin_search_batch_add_pileup(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_pileup* pl, char* err, size_t errlen) {
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, pl, pl, OTHER_ACC, &device, err, errlen)) return orc;
+    if (n_reads == 0) return FIN_OK;
+    Product p;
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_pileup(b, pl, own(b), e, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 
 int fin_search_batch(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands,

@@ -143,6 +143,21 @@ int fin_launch_depth_scan_chunk(const void* diff, uint64_t n, uint32_t tile, uin
 // stats[u] += {sum, max, positions with depth >= min_depth} (FinDepthStat, zeroed by the caller) over depth[0 .. n), the depths of text positions g_base ..
 int fin_launch_depth_stats(const uint32_t* depth, uint64_t g_base, uint64_t n, const uint32_t* ends_p, uint32_t n_unitigs, uint32_t min_depth, void* stats,
                            hipStream_t stream);
+// fin_pileup.hip: the base pileup of a finished step -- alt uint32[total_len][4], diff int32[total_len + 1] (cover's difference array), counters
+// 4 x u64 {kept, not straight, off the unitig, too many mismatches}, flags one u32 (bit 0: the step's overflow list overran -- nothing added; bit 1: a slot or record
+// outside the index).  frec / out_offs / pairs / ovf_count / ovf_cap as fin_launch_hits_add; bases / offs: the batch's ASCII reads and their n_reads + 1 offsets;
+// concat: the replica's 2-bit text
+int fin_launch_pileup_add(const void* frec, const uint64_t* out_offs, const void* pairs, const uint8_t* bases, const uint64_t* offs, uint32_t n_reads, uint32_t k,
+                          const uint32_t* ends_p, const uint32_t* concat, uint32_t n_unitigs, uint64_t total_len, uint32_t max_mismatch, void* alt, void* diff,
+                          void* counters, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap, hipStream_t stream);
+// the call over one staged chunk -- cover[0 .. n) and alt[0 .. n) are text positions g_base .. g_base + n: fin_launch_pileup_call_count leaves blk_sum (u32) and
+// blk_off (u64), fin_pileup_call_blocks(n) entries each, and *total = the chunk's candidates; fin_launch_pileup_call_write, once out has room for them: the
+// entries {u, off, cover, ref, alt[4]} of 32 bytes, ascending
+uint32_t fin_pileup_call_blocks(uint64_t n);
+int fin_launch_pileup_call_count(const uint32_t* cover, const void* alt, uint64_t n, uint32_t min_alt, uint32_t min_permille, uint32_t* blk_sum, uint64_t* blk_off,
+                                 uint64_t* total, hipStream_t stream);
+int fin_launch_pileup_call_write(const uint32_t* cover, const void* alt, uint64_t g_base, uint64_t n, uint32_t min_alt, uint32_t min_permille, const uint32_t* ends_p,
+                                 const uint32_t* concat, uint32_t n_unitigs, const uint64_t* blk_off, void* out, hipStream_t stream);
 // fin_segments.hip: a finished step's results as segments {u, off, slot, len} of 16 bytes, dense and in read order, delimited per read by seg_offs[n_reads + 1].
 // frec / out_offs / pairs as fin_launch_hits_add.  fin_launch_sgm_count: cnt[n_reads] u32, blk_sum[fin_sgm_blocks()] u32, blk_off as many u64, *total the
 // batch's segments; fin_launch_sgm_write, once segs has room for them: seg_offs and the segments

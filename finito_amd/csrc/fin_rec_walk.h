@@ -1,6 +1,6 @@
 // fin_rec_walk.h -- THE statement of the record gap rule, for the device and the host alike: what a fast-path record (FinFastRec, fin_read_record) means is
 // worked out here and nowhere else.  Every consumer of records takes the gaps (fin_rec_gaps) or their complement, the found stretches (fin_rec_stretches):
-// fin_hits.hip, fin_cover.hip, fin_depth.hip, fin_segments.hip, fin_readsum.hip, fin_classify.hip, fin_colors.hip, fin_paired.hip and the host twins of
+// fin_hits.hip, fin_cover.hip, fin_depth.hip, fin_pileup.hip, fin_segments.hip, fin_readsum.hip, fin_classify.hip, fin_colors.hip, fin_paired.hip and the host twins of
 // fin_records_host.cpp.  What a device consumer does AROUND the walk -- which reads have a record, the wave's turn through the searched ones, a read's rows --
 // is fin_wave.h's.
 #pragma once

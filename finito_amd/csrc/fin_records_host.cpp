@@ -532,4 +532,87 @@ int fin_records_depth(const fin_read_record* recs, uint64_t n_reads, const int32
     return ok ? FIN_OK : FIN_EINVAL;
 }
 
+// the pileup of fin_pileup.hip from records + stream and the reads: the definition of include/finito_amd.h read off a read's pairs, whichever kind its record
+// is -- a kind-1 record's are made as fin_expand_records makes them -- and every placed read compared with the text whole.  A chunk of reads per thread; with more
+// than one thread the positions are added atomically
+int fin_records_pileup(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const char* bases,
+                       const uint64_t* offsets, const int64_t* unitig_ends, uint64_t n_unitigs, const uint8_t* concat, uint32_t max_mismatch, uint32_t* cover_out,
+                       uint32_t* alt_out, uint64_t counters_out[4], int n_threads) {
+    if ((n_reads && (!recs || !offsets)) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !unitig_ends) || max_mismatch > 255u) return FIN_EINVAL;
+    int64_t prev = 0;
+    for (uint64_t u = 0; u < n_unitigs; u++) { if (unitig_ends[u] < prev) return FIN_EINVAL; prev = unitig_ends[u]; }
+    const uint64_t total_len = (uint64_t)prev;
+    if (total_len && !concat) return FIN_EINVAL;
+    if (n_reads && offsets[n_reads] > offsets[0] && !bases) return FIN_EINVAL;
+    if (cover_out) for (uint64_t g = 0; g < total_len; g++) cover_out[g] = 0;
+    if (alt_out) for (uint64_t g = 0; g < 4 * total_len; g++) alt_out[g] = 0;
+    if (counters_out) for (int c = 0; c < 4; c++) counters_out[c] = 0;
+    Chunks C(n_reads, n_threads);
+    if (C.stream(recs, n_stream_pairs)) return FIN_EINVAL;
+    const int T = C.T;
+    auto code = [](char ch) -> uint32_t { const char x = (char)(ch & 0xDF); return x == 'A' ? 0u : x == 'C' ? 1u : x == 'G' ? 2u : x == 'T' ? 3u : 4u; };
+    auto add32 = [&](uint32_t* p) { if (T == 1) (*p)++; else __atomic_fetch_add(p, 1u, __ATOMIC_RELAXED); };
+    std::vector<uint64_t> cnt((size_t)C.T * 4, 0);
+    const bool ok = C.run([&](int t) {
+        uint64_t sp = C.str0[(size_t)t];
+        uint64_t* const my = cnt.data() + (size_t)t * 4;
+        std::vector<int32_t> own;   // a kind-1 or kind-2 read's pairs
+        for (uint64_t r = C.lo(t); r < C.hi(t); r++) {
+            const fin_read_record& R = recs[r];
+            const uint32_t nk = R.nk, kind = R.meta >> 16;
+            const uint64_t L = offsets[r + 1] - offsets[r];
+            if (offsets[r + 1] < offsets[r] || (nk ? L != (uint64_t)nk + (uint64_t)k - 1 : L >= (uint64_t)k) || kind > 2u) return false;
+            const int32_t* p = nullptr;
+            if (kind == 0u) { p = stream_pairs + 2 * sp; sp += nk; }
+            else {
+                own.assign((size_t)nk * 2, -1);
+                if (kind == 1u) {
+                    const bool rev = (R.meta >> 8) & 1u;
+                    (void)rec_stretches(R, k, [&](uint32_t, uint32_t from, uint32_t to) {
+                        for (uint32_t sl = from; sl < to; sl++) { const uint32_t i = rev ? nk - 1u - sl : sl; own[2 * (size_t)i] = (int32_t)R.u; own[2 * (size_t)i + 1] = (int32_t)(R.off0 + sl); }
+                    });
+                }
+                p = own.data();
+            }
+            // 1. straight
+            uint64_t n_found = 0; int64_t u0 = -1, dF = 0, dR = 0; bool okF = true, okR = true;
+            for (uint32_t i = 0; i < nk; i++) {
+                const int64_t u = p[2 * (size_t)i], off = p[2 * (size_t)i + 1];
+                if (u < 0 || off < 0) { if (u != -1) return false; continue; }
+                if ((uint64_t)u >= n_unitigs) return false;
+                const uint64_t start = u ? (uint64_t)unitig_ends[u - 1] : 0, end = (uint64_t)unitig_ends[u];
+                if (start + (uint64_t)off + (uint64_t)k > end) return false;
+                if (n_found == 0) { u0 = u; dF = off - (int64_t)i; dR = off + (int64_t)i; }
+                n_found++;
+                if (u != u0 || off - (int64_t)i != dF) okF = false;
+                if (u != u0 || off + (int64_t)i != dR) okR = false;
+            }
+            if (n_found < 2 || okF == okR) { my[FIN_PILEUP_NOT_STRAIGHT]++; continue; }
+            // 2. placed: strand A at [s0, s0 + L) of u0
+            const bool rev = okR;
+            const int64_t s0 = rev ? dR - (int64_t)nk + 1 : dF;
+            const uint64_t start = u0 ? (uint64_t)unitig_ends[u0 - 1] : 0, end = (uint64_t)unitig_ends[u0];
+            if (s0 < 0 || start + (uint64_t)s0 + L > end) { my[FIN_PILEUP_OFF_UNITIG]++; continue; }
+            // 3. mismatches: strand position s is read[s] forward, the complement of read[L - 1 - s] reverse
+            const uint64_t g0 = start + (uint64_t)s0;
+            const char* const rd = bases + offsets[r];
+            auto observed = [&](uint64_t s) -> uint32_t { const uint32_t c = code(rd[rev ? L - 1 - s : s]); return rev && c < 4u ? 3u - c : c; };
+            uint64_t n_mm = 0;
+            for (uint64_t s = 0; s < L; s++) { const uint32_t o = observed(s); if (o < 4u && o != concat[g0 + s]) n_mm++; }
+            if (n_mm > max_mismatch) { my[FIN_PILEUP_TOO_MANY]++; continue; }
+            // 4. what a kept read adds
+            for (uint64_t s = 0; s < L; s++) {
+                if (cover_out) add32(cover_out + g0 + s);
+                const uint32_t o = observed(s);
+                if (alt_out && o < 4u && o != concat[g0 + s]) add32(alt_out + 4 * (g0 + s) + o);
+            }
+            my[FIN_PILEUP_KEPT]++;
+        }
+        return true;
+    });
+    if (!ok) return FIN_EINVAL;
+    if (counters_out) for (int t = 0; t < C.T; t++) for (int c = 0; c < 4; c++) counters_out[c] += cnt[(size_t)t * 4 + (size_t)c];
+    return FIN_OK;
+}
+
 }  // extern "C"

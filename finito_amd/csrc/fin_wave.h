@@ -7,7 +7,7 @@
 //   kind 0 -- the pipeline searched the read: its pairs are slots [out_offs[r], out_offs[r + 1]) of the pair array.  The wave takes its lanes' searched reads one
 //             after the other and scans each a row of 64 slots at a time.
 // Where the step left no records (frec null: forward-only search, kernels 0 / 2 / 3, fast path off, k > 63, text mode 0) every read is a kind-0 read.
-// fin_hits.hip, fin_cover.hip, fin_depth.hip, fin_segments.hip, fin_readsum.hip, fin_classify.hip, fin_colors.hip and fin_paired.hip say only what is their own.
+// fin_hits.hip, fin_cover.hip, fin_depth.hip, fin_pileup.hip, fin_segments.hip, fin_readsum.hip, fin_classify.hip, fin_colors.hip and fin_paired.hip say only what is their own.
 //
 // Everything here is wave-converged unless it says "a lane": callers hand in lambdas that capture by reference; they inline, and what they capture stays in registers
 // as long as nothing is indexed by a run-time count.

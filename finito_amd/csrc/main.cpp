@@ -459,6 +459,14 @@ static const char* SEARCH_HELP =
     "                        were found at least T times (--min-depth). Kept on the first GPU, 4 bytes per base of the unitig text, from one more\n"
     "                        search of every chunk; goes with -o, --unitig-counts, --unitig-coverage and --segments. Not for a partitioned index.\n"
     "      --min-depth T     the T of --unitig-depth (default: 1); only with --unitig-depth\n"
+    "      --pileup FILE     also write the run's base pileup over the unitig text: a line unitig<TAB>offset<TAB>ref<TAB>cover<TAB>A<TAB>C<TAB>G<TAB>T\n"
+    "                        for every position a placed read spans (cover > 0) -- how many reads span it and how many show each base other\n"
+    "                        than the text's -- and a last line #reads<TAB>kept<TAB>not_straight<TAB>off_unitig<TAB>too_many. A read is placed when\n"
+    "                        its found k-mers lie on one diagonal of one unitig and the whole read lies inside it. Kept on the first GPU, 20 bytes\n"
+    "                        per base of the unitig text, from one more pass over each chunk. Not for a partitioned index.\n"
+    "      --variants FILE   the same columns for the candidate positions only, called on the GPU: the greatest alt count is at least\n"
+    "                        --min-alt N (default: 2) and at least --min-alt-permille P thousandths of the cover (default: 200)\n"
+    "      --pileup-max-mismatch M  reads with more than M mismatches are left out of the pileup (0 .. 255, default: 8)\n"
     "      --segments FILE   also write every read's path through the unitig set: one line `read<TAB>slot<TAB>length<TAB>unitig<TAB>offset<TAB>+|-` per\n"
     "                        segment -- `length` consecutive k-mers of read `read` (0-based ordinal in the query file, counted through a list of\n"
     "                        query files), from its k-mer number `slot` on, found in `unitig` at `offset`, `offset + 1`, ... (+) or `offset`,\n"
@@ -710,6 +718,12 @@ static fin_depth* g_depth = nullptr;
 static void add_depth_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
     char err[512] = {0};
     if (fin_search_batch_add_depth(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_depth, err, sizeof err) != FIN_OK) throw runtime_error(err);
+}
+// --pileup FILE / --variants FILE: the same for the base pileup (fin_search_batch_add_pileup)
+static fin_pileup* g_pileup = nullptr;
+static void add_pileup_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
+    char err[512] = {0};
+    if (fin_search_batch_add_pileup(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_pileup, err, sizeof err) != FIN_OK) throw runtime_error(err);
 }
 // --segments FILE: every chunk's segments are made on the first device (fin_search_batch_segments) and written as lines, by the search stage, in chunk order
 static FILE* g_seg_file = nullptr;
@@ -1019,6 +1033,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_depth) add_depth_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_pileup) add_pileup_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_seg_file) c->positive = segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                         if (g_rs_file) c->positive = read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
@@ -1041,6 +1056,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);   // (a second pass over the chunk on the device: the text is what bounds this loop)
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_depth) add_depth_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_pileup) add_pileup_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_seg_file) (void)segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                         if (g_rs_file) (void)read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
@@ -1162,12 +1178,12 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance"))
-        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance"))
+        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
     g_paired = o.has("paired") && o.get("paired") != "0" && o.get("paired") != "false";
@@ -1241,6 +1257,18 @@ static int search_fmin(int argc, char** argv) {
         if (v.empty() || used != v.size() || v[0] == '-' || t > 0xFFFFFFFFull) throw runtime_error("--min-depth wants a number from 0 to 4294967295");
         min_depth = (uint32_t)t;
     }
+    const bool want_pileup = o.has("pileup") || o.has("variants");
+    if ((o.has("pileup-max-mismatch") || o.has("min-alt") || o.has("min-alt-permille")) && !want_pileup)
+        throw runtime_error("--pileup-max-mismatch, --min-alt and --min-alt-permille are only legal together with --pileup or --variants");
+    auto pileup_number = [&](const char* name, unsigned long long dflt, unsigned long long top) -> uint32_t {
+        if (!o.has(name)) return (uint32_t)dflt;
+        const string v = o.get(name);
+        size_t used = 0; unsigned long long t = 0;
+        try { t = stoull(v, &used); } catch (...) { used = 0; }
+        if (v.empty() || used != v.size() || v[0] == '-' || t > top) throw runtime_error(string("--") + name + " wants a number from 0 to " + to_string(top));
+        return (uint32_t)t;
+    };
+    const uint32_t pileup_max_mm = pileup_number("pileup-max-mismatch", 8, 255), min_alt = pileup_number("min-alt", 2, 0xFFFFFFFFull), min_alt_permille = pileup_number("min-alt-permille", 200, 1000);
     if (g_no_text && g_strand_counts) throw runtime_error("--no-text 1 and --strand-counts 1 do not go together");
     if (!o.has("query-file")) throw runtime_error("Option 'query-file' has no value");
     if (!o.has("index-file")) throw runtime_error("Option 'index-file' has no value");
@@ -1265,6 +1293,9 @@ static int search_fmin(int argc, char** argv) {
     if (!cover_file.empty()) check_writable(cover_file);
     const string depth_file = o.get("unitig-depth", "");
     if (!depth_file.empty()) check_writable(depth_file);
+    const string pileup_file = o.get("pileup", ""), variants_file = o.get("variants", "");
+    if (!pileup_file.empty()) check_writable(pileup_file);
+    if (!variants_file.empty()) check_writable(variants_file);
     const string seg_file = o.get("segments", "");
     if (!seg_file.empty()) check_writable(seg_file);
     const string rs_file = o.get("read-summary", "");
@@ -1331,6 +1362,7 @@ static int search_fmin(int argc, char** argv) {
     if (!counts_file.empty() && index.partitioned()) throw runtime_error("--unitig-counts is not available with a partitioned index");
     if (!cover_file.empty() && index.partitioned()) throw runtime_error("--unitig-coverage is not available with a partitioned index");
     if (!depth_file.empty() && index.partitioned()) throw runtime_error("--unitig-depth is not available with a partitioned index");
+    if (want_pileup && index.partitioned()) throw runtime_error("--pileup and --variants are not available with a partitioned index");
     if (!seg_file.empty() && index.partitioned()) throw runtime_error("--segments is not available with a partitioned index");
     if (!rs_file.empty() && index.partitioned()) throw runtime_error("--read-summary is not available with a partitioned index");
     if (!scr_file.empty() && index.partitioned()) throw runtime_error("--screen is not available with a partitioned index");
@@ -1352,6 +1384,11 @@ static int search_fmin(int argc, char** argv) {
     if (!depth_file.empty()) {
         char err[512] = {0};
         if (fin_depth_create(index.handle(), first_dev, &g_depth, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    }
+    struct PileupOwner { ~PileupOwner() { fin_pileup_free(g_pileup); g_pileup = nullptr; } } pileup_owner;
+    if (want_pileup) {
+        char err[512] = {0};
+        if (fin_pileup_create(index.handle(), first_dev, pileup_max_mm, &g_pileup, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     struct SegOwner { ~SegOwner() { if (g_seg_file) fclose(g_seg_file); g_seg_file = nullptr; } } seg_owner;
     if (!seg_file.empty()) {
@@ -1582,6 +1619,57 @@ static int search_fmin(int argc, char** argv) {
         ofstream cf(depth_file, ios::binary | ios::trunc);
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + depth_file);
+    }
+    if (g_pileup) {   // the pileup, after the last chunk: the covered positions, and the candidates called on the device
+        char err[512] = {0};
+        const size_t nu = (size_t)index.number_of_unitigs();
+        uint64_t counters[4] = {0, 0, 0, 0};
+        auto line = [](string& t, uint64_t u, uint64_t off, uint32_t ref, uint32_t cover, const uint32_t* alt) {
+            t += to_string(u); t += '\t'; t += to_string(off); t += '\t'; t += "ACGT"[ref & 3u]; t += '\t'; t += to_string(cover);
+            for (int b = 0; b < 4; b++) { t += '\t'; t += to_string(alt[b]); }
+            t += '\n';
+        };
+        auto last_line = [&](string& t) {
+            t += "#reads";
+            for (int c = 0; c < 4; c++) { t += '\t'; t += to_string(counters[c]); }
+            t += '\n';
+        };
+        auto write_file = [](const string& name, const string& t) {
+            ofstream cf(name, ios::binary | ios::trunc);
+            cf.write(t.data(), (streamsize)t.size());
+            if (!cf) throw runtime_error("Error writing to file: " + name);
+        };
+        if (!pileup_file.empty()) {
+            const size_t total = (size_t)fin_index_total_len(index.handle());
+            vector<uint32_t> cover(total + 1), alt(4 * total + 4);
+            vector<uint8_t> concat(total + 1);
+            vector<int64_t> ends(nu + 1);
+            if (fin_pileup_download(g_pileup, cover.data(), alt.data(), counters, err, sizeof err) != FIN_OK) throw runtime_error(err);
+            if (fin_index_export(index.handle(), FIN_X_ENDS, ends.data(), nu * sizeof(int64_t), err, sizeof err) != FIN_OK) throw runtime_error(err);
+            if (fin_index_export(index.handle(), FIN_X_CONCAT, concat.data(), total, err, sizeof err) != FIN_OK) throw runtime_error(err);
+            string text;
+            for (size_t u = 0; u < nu; u++) {
+                const size_t start = u ? (size_t)ends[u - 1] : 0;
+                for (size_t g = start; g < (size_t)ends[u]; g++) if (cover[g]) line(text, u, g - start, concat[g], cover[g], &alt[4 * g]);
+            }
+            last_line(text);
+            write_file(pileup_file, text);
+        }
+        if (!variants_file.empty()) {
+            if (fin_pileup_download(g_pileup, nullptr, nullptr, counters, err, sizeof err) != FIN_OK) throw runtime_error(err);
+            vector<fin_variant> v(1024);
+            uint64_t n = 0;
+            for (;;) {   // a call that does not fit says how many there are
+                const int rc = fin_pileup_call(g_pileup, min_alt, min_alt_permille, v.data(), v.size(), &n, err, sizeof err);
+                if (rc == FIN_OK) break;
+                if (rc != FIN_ELIMIT || n <= v.size()) throw runtime_error(err);
+                v.resize((size_t)n);
+            }
+            string text;
+            for (uint64_t q = 0; q < n; q++) line(text, v[q].u, v[q].off, v[q].ref, v[q].cover, v[q].alt);
+            last_line(text);
+            write_file(variants_file, text);
+        }
     }
     if (g_hits && !counts_file.empty()) {   // the profile, after the last chunk: one line per unitig of the index
         char err[512] = {0};

@@ -588,6 +588,72 @@ int fin_records_depth(const fin_read_record* recs, uint64_t n_reads, const int32
                       uint64_t n_unitigs, uint32_t* depth_out, int n_threads);
 void fin_depth_free(fin_depth* d);
 
+/* ---- PILEUP of a run over the unitig text: which base was seen at each position, and where the sample differs ----
+ * fin_hits, fin_cover and fin_depth say where a read's k-mers lie; the pileup says what the read says there.  Stated on the pairs fin_search_batch delivers, for a
+ * read of L bases with nk = L - k + 1 >= 1 slots (u_i, off_i):
+ *  1. STRAIGHT: at least two found slots, all in one unitig u, and either off_i - i is one constant dF over them (forward) or off_i + i is one constant dR
+ *     (reverse).  One found slot does not tell the strand; a mosaic, an indel (two diagonals) and a repeated identical pair are not straight.
+ *  2. PLACED: forward, read base j lies at offset dF + j of u and is observed as read[j]; reverse, at dR + k - 1 - j and is observed as the complement of read[j].
+ *     Only if all L positions lie inside u: a straight read that hangs over an end of its unitig is not placed.  (A kind-1 record: strand A at [off0, off0 + L),
+ *     meta bit 8 the direction, dR = off0 + nk - 1.)
+ *  3. MISMATCH: a position whose observed base is A, C, G or T (either case) and differs from the text's.  Any other letter is no observation and no mismatch.  A
+ *     placed read with more than max_mismatch mismatches is dropped whole.
+ *  4. A kept read adds 1 to cover[g] at each of its L positions g = start(u) + offset (those under a non-ACGT letter too) and 1 to alt[g][b] at each mismatch, b the
+ *     observed base's code (A, C, G, T = 0 .. 3) in the text's orientation.  alt[g][text[g]] stays 0; the reference base was seen cover - sum(alt) - (non-ACGT
+ *     letters there) times.
+ *  5. Four counters, summed over the adds: reads kept; not straight (reads shorter than k among them); straight but not inside their unitig; dropped for too many
+ *     mismatches.  They sum to the reads offered.
+ * Arithmetic is uint32, modulo 2^32; adding the same run twice doubles it.  On a set that is not disjoint the same rule is applied to the place the reference
+ * reports: the numbers are exact, but a read may then be compared with a place that does not spell it (as fin_depth and fin_cover count a k-mer in the copy that
+ * is the reference's choice).
+ * The accumulator lies in HBM beside one replica, 20 bytes per indexed base: uint32 alt[total_len][4] and cover as an int32 difference array of total_len + 1
+ * entries (fin_depth's form: two atomic adds per kept read).  fin_batch_add_pileup launches one kernel behind the batch's most recent run (fin_pileup.hip): a read
+ * the fast path finished is taken from its 32-byte record and one ASCII base per disagreeing position; a read the pipeline searched is checked for straightness
+ * from its pairs and compared with the 2-bit text, 64 bases a row.  fin_pileup_call leaves only the candidate positions to cross PCIe.
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi and the distributed driver, the C++ mirror (FinimizerIndex.hh), indels, base
+ * qualities, saturation, reads that bridge unitigs. */
+typedef struct fin_pileup fin_pileup;
+/* a called position: unitig and offset, its cover, the text's base code and the four alt counts (alt[ref] == 0) */
+typedef struct fin_variant { uint32_t u, off, cover, ref; uint32_t alt[4]; } fin_variant;   /* 32 bytes */
+/* the counters' order in counters_out[4] */
+#define FIN_PILEUP_KEPT 0
+#define FIN_PILEUP_NOT_STRAIGHT 1
+#define FIN_PILEUP_OFF_UNITIG 2
+#define FIN_PILEUP_TOO_MANY 3
+/* a zeroed accumulator for `idx` on `device`, max_mismatch in 0 .. 255 (FIN_EINVAL beyond).  FIN_ENODEV: the index has no replica there; FIN_ENOMEM: 20 bytes
+ * per indexed base do not fit */
+int fin_pileup_create(const fin_index* idx, int device, uint32_t max_mismatch, fin_pileup** out, char* err, size_t errlen);
+/* zeroes the accumulator and its counters, on the given stream; does not wait; ordered against the adds as fin_hits_reset is */
+int fin_pileup_reset(fin_pileup* p, void* hip_stream);
+/* pileup += the reads of the batch's most recent run: one launch on the given stream, ordered behind that run; does not wait.  fin_batch_add_depth's ordering and
+ * refusal rules: FIN_EINVAL when the batch has not run or batch and accumulator belong to different indexes or devices; records, pairs, bases and text are read
+ * only (the batch must not be reloaded on another stream before the add has finished); a run whose overflow list overran adds nothing and fin_pileup_download /
+ * fin_pileup_call report FIN_ELIMIT until the reset.  A slot or a record outside the index adds nothing and they report FIN_EINVAL "outside the index" until the
+ * reset. */
+int fin_batch_add_pileup(fin_batch* b, fin_pileup* p, void* hip_stream, char* err, size_t errlen);
+/* uint32[fin_index_total_len][4] and int32[fin_index_total_len + 1] in HBM (valid once the adds on their streams have finished): cover[g] = diff[0] + ... + diff[g] */
+void* fin_pileup_device_alt(const fin_pileup* p);
+void* fin_pileup_device_cover_diff(const fin_pileup* p);
+/* waits for every add and reset issued so far.  cover_out[fin_index_total_len] (the prefix sum, made on the device a chunk at a time),
+ * alt_out[4 * fin_index_total_len] (copied as it lies), counters_out[4]; each may be NULL.  The accumulator is not changed. */
+int fin_pileup_download(fin_pileup* p, uint32_t* cover_out, uint32_t* alt_out, uint64_t counters_out[4], char* err, size_t errlen);
+/* the candidates, made on the device: position g is one when m = max_b alt[g][b] has m >= max(min_alt, 1) and 1000 m >= min_permille cover[g] (min_permille in
+ * 0 .. 1000).  out[cap] receives them ascending in g, *n how many there are.  FIN_ELIMIT: more than cap -- *n is still the true count, out's content is not
+ * defined.  Waits as fin_pileup_download does and leaves the accumulator unchanged. */
+int fin_pileup_call(fin_pileup* p, uint32_t min_alt, uint32_t min_permille, fin_variant* out, uint64_t cap, uint64_t* n, char* err, size_t errlen);
+/* fin_search_batch_add_depth's loop with the pileup as its product: host buffers in, sub-batches pipelined, each run in text mode 2 where the fast path is on and
+ * added on the device behind its run, nothing downloaded */
+int fin_search_batch_add_pileup(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_pileup* p, char* err, size_t errlen);
+/* host, no device: the definition above from records + stream and the reads themselves -- bases / offsets[n_reads + 1] as fin_search_batch takes them,
+ * unitig_ends[n_unitigs] as FIN_X_ENDS, concat as FIN_X_CONCAT (a 0 .. 3 code per base).  Every placed read is compared with the text whole, whichever kind its
+ * record is: this is the CPU statement of the definition, not of the kernel's shortcut.  cover_out[total_len], alt_out[4 * total_len] and counters_out[4] are
+ * overwritten; each may be NULL.  n_threads <= 0: all cores.  FIN_EINVAL: what fin_records_depth refuses (a unitig number >= n_unitigs, a k-mer that does not lie
+ * inside its unitig, a stream that is not this record set's), a read whose length is not nk + k - 1, or max_mismatch > 255 */
+int fin_records_pileup(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const char* bases,
+                       const uint64_t* offsets, const int64_t* unitig_ends, uint64_t n_unitigs, const uint8_t* concat, uint32_t max_mismatch, uint32_t* cover_out,
+                       uint32_t* alt_out, uint64_t counters_out[4], int n_threads);
+void fin_pileup_free(fin_pileup* p);
+
 /* ---- results as SEGMENTS: a read's path through the unitig set, made on the device for every read ----
  * Records (above) are compact only for the reads the fast path finished; a read the pipeline searched -- an indel, a mosaic over several unitigs, more than eight
  * substitutions, any read at k > 63 or in a forward-only search -- still comes back as 8 bytes per k-mer, although it is almost always two to five straight
