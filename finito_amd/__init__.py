@@ -280,6 +280,10 @@ def lib():
         L.fin_eqclasses_free.argtypes = [vp]
         L.fin_eqclasses_free.restype = None
         L.fin_eqclasses_add_rows.argtypes = [vp, vp, u64, vp, cp, C.c_size_t]
+        L.fin_eqclasses_add_classes.argtypes = [vp, vp, vp, u64, u64, vp, cp, C.c_size_t]
+        L.fin_eqclasses_add_classes_host.argtypes = [vp, u64p, u64p, u64, u64, cp, C.c_size_t]
+        L.fin_eqclasses_merge.argtypes = [vp, vp, vp, cp, C.c_size_t]
+        L.fin_classes_merge.argtypes = [u64p, u64p, u64, u64p, u64p, u64, u32, u64p, u64p, u64, u64p]
         L.fin_batch_add_eqclasses.argtypes = [vp, vp, u32, vp, cp, C.c_size_t]
         L.fin_search_batch_add_eqclasses.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, cp, C.c_size_t]
         L.fin_eqclasses_download.argtypes = [vp, u64p, u64p, u64, u64p, u64p, cp, C.c_size_t]
@@ -840,6 +844,36 @@ class EqClasses(_Accumulator):
             raise FinitoError(FIN_EINVAL, "EqClasses.add_rows: n_rows is an unsigned 64-bit number")
         err = C.create_string_buffer(512)
         _check(self.L.fin_eqclasses_add_rows(self.h, C.c_void_p(int(ptr) or 0), int(n_rows), C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add_classes(self, class_rows, class_reads, n_unaligned=0):
+        """classes {row, reads} from host arrays -- a download, another rank's classes --, added as if row r had been added class_reads[r] times, and n_unaligned
+        empty rows besides; exact, in integers.  A row with a bit at or above n_colors is refused before anything is added; returns when the add has run
+        (fin_eqclasses_add_classes_host)"""
+        a, r = _classes("EqClasses.add_classes", class_rows, class_reads, self.n_colors)
+        un = _u64("EqClasses.add_classes", "n_unaligned", n_unaligned)
+        u64p = C.POINTER(C.c_uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_eqclasses_add_classes_host(self.h, a.ctypes.data_as(u64p), r.ctypes.data_as(u64p), len(a), un, err, 512), err)
+        return self
+
+    def add_classes_device(self, rows_ptr, reads_ptr, n_classes, n_unaligned=0, stream=None):
+        """the same from device pointers: uint64[n_classes, W] and uint64[n_classes] in HBM, valid until the add has finished; on a HIP stream, no sync
+        (fin_eqclasses_add_classes)"""
+        n = _u64("EqClasses.add_classes_device", "n_classes", n_classes)
+        un = _u64("EqClasses.add_classes_device", "n_unaligned", n_unaligned)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_eqclasses_add_classes(self.h, C.c_void_p(int(rows_ptr) or 0), C.c_void_p(int(reads_ptr) or 0), n, un, C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def merge(self, other, stream=None):
+        """this accumulator gains what `other` holds (its classes and its unaligned count), on the device; `other` is left as it was found.  Waits for `other`'s
+        adds, not for its own; `other` must be another accumulator on the same device with the same n_colors, and not flagged (fin_eqclasses_merge).
+        Accumulators on different devices: add_classes(*other.download())"""
+        if not isinstance(other, EqClasses) or not getattr(other, "h", None):
+            raise FinitoError(FIN_EINVAL, "EqClasses.merge: another EqClasses")
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_eqclasses_merge(self.h, other.h, C.c_void_p(stream or 0), err, 512), err)
         return self
 
     def add_reads(self, reads, permille=1000, strands=FIN_MERGED):
@@ -1930,6 +1964,31 @@ def rows_eqclasses(rows, n_colors):
     if rc != 0:
         raise FinitoError(rc, "fin_rows_eqclasses: n_colors outside 1 .. 4096, or a row with a bit at or above n_colors")
     return out[: int(n.value)], reads[: int(n.value)], int(un.value)
+
+
+def _u64(what, name, v):
+    if not 0 <= int(v) <= 0xFFFFFFFFFFFFFFFF:
+        raise FinitoError(FIN_EINVAL, "%s: %s is an unsigned 64-bit number" % (what, name))
+    return int(v)
+
+
+def classes_merge(rows_a, reads_a, rows_b, reads_b, n_colors):
+    """host: (class rows uint64[n, W], reads uint64[n]) of the union of two class lists, in canonical order (fin_classes_merge) -- the CPU statement of
+    EqClasses.merge and add_classes.  Either list may be unsorted and hold duplicate rows; classes of 0 reads and all-zero rows are dropped"""
+    if not 1 <= int(n_colors) <= 4096:
+        raise FinitoError(FIN_ELIMIT, "classes_merge: n_colors is 1 .. 4096")
+    a, ra = _classes("classes_merge", rows_a, reads_a, n_colors)
+    b, rb = _classes("classes_merge", rows_b, reads_b, n_colors)
+    u64p = C.POINTER(C.c_uint64)
+    cap = max(len(a) + len(b), 1)
+    out = np.zeros((cap, a.shape[1]), dtype=np.uint64)
+    reads = np.zeros(cap, dtype=np.uint64)
+    n = C.c_uint64(0)
+    rc = lib().fin_classes_merge(a.ctypes.data_as(u64p), ra.ctypes.data_as(u64p), len(a), b.ctypes.data_as(u64p), rb.ctypes.data_as(u64p), len(b), int(n_colors),
+                                 out.ctypes.data_as(u64p), reads.ctypes.data_as(u64p), cap, C.byref(n))
+    if rc != 0:
+        raise FinitoError(rc, "fin_classes_merge: n_colors outside 1 .. 4096, or a class with a bit at or above n_colors")
+    return out[: int(n.value)], reads[: int(n.value)]
 
 
 def classes_abundance(class_rows, class_reads, n_colors, lengths=None, max_iters=1000, tol=1e-6, trace=False, n_threads=0):

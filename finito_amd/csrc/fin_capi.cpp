@@ -1900,6 +1900,12 @@ int fin_batch_download_pair_pseudo(fin_batch* b, uint64_t* rows_out, fin_pair_ps
     return FIN_OK;
 }
 
+// every device buffer of an estimate (or of a host add's upload), freed on every way out
+struct AbBufs {
+    std::vector<void*> p;
+    ~AbBufs() { for (void* q : p) (void)hipFree(q); }
+    void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return q; }
+};
 // ---- equivalence classes of pseudoaligned reads (fin_eqclasses.hip) ---------------------------------------------------------------------
 struct fin_eqclasses : fin_acc {
     const fin_colors* colors = nullptr;
@@ -1908,6 +1914,8 @@ struct fin_eqclasses : fin_acc {
     void* d_tab = nullptr;      // ctr uint64[8] | tags uint64[slots] | counts uint64[slots] | rows uint64[slots * words]
     void* d_scratch = nullptr;  // slot_of uint32[cap_rows] | coll uint32[cap_rows]: kept and only grown
     size_t cap_rows = 0;
+    void* d_merge = nullptr;    // fin_eqclasses_merge's scratch, this accumulator being the destination: blk_off | blk_sum | the source's dense rows | reads.  Kept and only grown
+    size_t cap_merge = 0;       // (bytes)
     uint32_t tag_bits = 0;      // option "ec_tag_bits" as the first add since the creation or the last reset read it (0: none yet)
     std::mutex mu;              // an add (order, three launches, mark) and a reset are one step each: calls from several host threads take effect in issue order
 };
@@ -1917,9 +1925,16 @@ static uint64_t* ec_counts(const fin_eqclasses* e) { return ec_tags(e) + e->slot
 static uint64_t* ec_rows(const fin_eqclasses* e) { return ec_counts(e) + e->slots; }
 static size_t ec_zero_bytes(const fin_eqclasses* e) { return (size_t)(8 + 2 * e->slots) * 8; }   // (a slot's row is written when the slot is claimed)
 
+// what a flagged accumulator answers its readers until the reset
+static int ec_flagged(const fin_eqclasses* e, const uint64_t* ctr, char* err, size_t errlen) {
+    if (ctr[4] & 1u) { set_err(err, errlen, "a row with a bit at or above n_colors was added (not counted; reset the accumulator)"); return FIN_EINVAL; }
+    if ((ctr[4] & 2u) || ctr[2] > e->max_classes) { set_err(err, errlen, "more than max_classes distinct rows (max_classes = " + std::to_string(e->max_classes) + "; reset the accumulator)"); return FIN_ELIMIT; }
+    return FIN_OK;
+}
+
 void fin_eqclasses_free(fin_eqclasses* e) {
     if (!acc_free_open(e)) return;
-    (void)hipFree(e->d_tab); (void)hipFree(e->d_scratch);
+    (void)hipFree(e->d_tab); (void)hipFree(e->d_scratch); (void)hipFree(e->d_merge);
     delete e;
 }
 
@@ -1948,10 +1963,9 @@ int fin_eqclasses_reset(fin_eqclasses* e, void* hip_stream) {
     return acc_reset(e, hip_stream, e->d_tab, ec_zero_bytes(e));
 }
 
-// the add proper, on `st`: behind every add and reset issued so far, whichever streams they were given
-static int ec_add_rows(fin_eqclasses* e, const void* d_rows, uint64_t n_rows, hipStream_t st, char* err, size_t errlen) {
-    if (n_rows >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 rows in one add"); return FIN_ELIMIT; }
-    std::lock_guard<std::mutex> g(e->mu);
+// the add proper, on `st`: behind every add and reset issued so far, whichever streams they were given.  With the accumulator's lock held.  d_weights null: every
+// row counts once (fin_launch_ec_add); else row r counts d_weights[r] times and n_unaligned all-zero rows are counted besides (fin_launch_ec_add_classes)
+static int ec_add_locked(fin_eqclasses* e, const void* d_rows, const void* d_weights, uint64_t n_rows, uint64_t n_unaligned, hipStream_t st, char* err, size_t errlen) {
     if (n_rows > e->cap_rows) {   // (the adds under way use the old scratch)
         if (const int wrc = e->pend.wait(err, errlen)) return wrc;
         (void)hipFree(e->d_scratch); e->d_scratch = nullptr; e->cap_rows = 0;
@@ -1961,18 +1975,101 @@ static int ec_add_rows(fin_eqclasses* e, const void* d_rows, uint64_t n_rows, hi
     }
     if (e->tag_bits == 0) e->tag_bits = (uint32_t)optv(e->idx, O_ec_tag_bits);
     if (const int orc = e->pend.order(st, err, errlen)) return orc;
-    if (n_rows) {
-        const int rc = fin_launch_ec_add(d_rows, (uint32_t)n_rows, e->words, e->n_colors, ec_tags(e), ec_counts(e), ec_rows(e), e->lg, e->max_classes, e->tag_bits,
-                                         (uint32_t)optv(e->idx, O_ec_combine), ec_ctr(e), (uint32_t*)e->d_scratch, (uint32_t*)e->d_scratch + e->cap_rows, st);
-        if (rc != 0) { set_err(err, errlen, std::string("equivalence class kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
-    }
+    int rc = 0;
+    if (d_weights || n_unaligned)
+        rc = fin_launch_ec_add_classes(d_rows, d_weights, (uint32_t)n_rows, n_unaligned, e->words, e->n_colors, ec_tags(e), ec_counts(e), ec_rows(e), e->lg, e->max_classes,
+                                       e->tag_bits, ec_ctr(e), (uint32_t*)e->d_scratch, (uint32_t*)e->d_scratch + e->cap_rows, st);
+    else if (n_rows)
+        rc = fin_launch_ec_add(d_rows, (uint32_t)n_rows, e->words, e->n_colors, ec_tags(e), ec_counts(e), ec_rows(e), e->lg, e->max_classes, e->tag_bits,
+                               (uint32_t)optv(e->idx, O_ec_combine), ec_ctr(e), (uint32_t*)e->d_scratch, (uint32_t*)e->d_scratch + e->cap_rows, st);
+    if (rc != 0) { set_err(err, errlen, std::string("equivalence class kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
     return e->pend.mark(st, err, errlen);
+}
+static int ec_add_rows(fin_eqclasses* e, const void* d_rows, uint64_t n_rows, hipStream_t st, char* err, size_t errlen, const void* d_weights = nullptr,
+                       uint64_t n_unaligned = 0) {
+    if (n_rows >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 rows in one add"); return FIN_ELIMIT; }
+    std::lock_guard<std::mutex> g(e->mu);
+    return ec_add_locked(e, d_rows, d_weights, n_rows, n_unaligned, st, err, errlen);
 }
 
 int fin_eqclasses_add_rows(fin_eqclasses* e, const void* d_rows, uint64_t n_rows, void* hip_stream, char* err, size_t errlen) {
     if (!e || (n_rows && !d_rows)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     HIPCHK(hipSetDevice(e->device));
     return ec_add_rows(e, d_rows, n_rows, (hipStream_t)hip_stream, err, errlen);
+}
+
+int fin_eqclasses_add_classes(fin_eqclasses* e, const void* d_rows, const void* d_reads, uint64_t n_classes, uint64_t n_unaligned, void* hip_stream, char* err,
+                              size_t errlen) {
+    if (!e || (n_classes && (!d_rows || !d_reads))) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    return ec_add_rows(e, d_rows, n_classes, (hipStream_t)hip_stream, err, errlen, n_classes ? d_reads : nullptr, n_unaligned);
+}
+
+// the first row of n with a bit at or above n_colors; n: none
+static uint64_t ec_first_stray(const uint64_t* rows, uint64_t n, uint32_t n_colors, uint32_t W) {
+    const uint64_t stray = (n_colors & 63u) ? ~0ull << (n_colors & 63u) : 0ull;
+    for (uint64_t r = 0; r < n; r++) if (rows[r * W + (W - 1)] & stray) return r;
+    return n;
+}
+
+int fin_eqclasses_add_classes_host(fin_eqclasses* e, const uint64_t* rows, const uint64_t* reads, uint64_t n_classes, uint64_t n_unaligned, char* err, size_t errlen) {
+    if (!e || (n_classes && (!rows || !reads))) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (n_classes >= 0x80000000ull) { set_err(err, errlen, "more than 2^31-1 classes in one add"); return FIN_ELIMIT; }
+    const uint64_t bad = ec_first_stray(rows, n_classes, e->n_colors, e->words);
+    if (bad != n_classes) { set_err(err, errlen, "class " + std::to_string(bad) + " has a bit at or above n_colors = " + std::to_string(e->n_colors) + " set (nothing was added)"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(e->device));
+    AbBufs bufs;   // (freed on every way out)
+    uint64_t* d = nullptr;
+    if (n_classes) {
+        const size_t n = (size_t)n_classes, W = e->words;
+        d = (uint64_t*)bufs.get(n * (W + 1) * 8);
+        if (!d) { set_err(err, errlen, "out of device memory (classes to add)"); return FIN_ENOMEM; }
+        HIPCHK(hipMemcpy(d, rows, n * W * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d + n * W, reads, n * 8, hipMemcpyHostToDevice));
+    }
+    if (const int rc = ec_add_rows(e, d, n_classes, nullptr, err, errlen, d ? d + (size_t)n_classes * e->words : nullptr, n_unaligned)) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));   // the device copy is freed behind the add; the caller's arrays were free since the copies
+    return FIN_OK;
+}
+
+int fin_eqclasses_merge(fin_eqclasses* dst, fin_eqclasses* src, void* hip_stream, char* err, size_t errlen) {
+    if (!dst || !src) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (dst == src) { set_err(err, errlen, "an accumulator cannot be merged into itself"); return FIN_EINVAL; }
+    if (dst->device != src->device) { set_err(err, errlen, "the accumulators are on different devices (fin_eqclasses_download and fin_eqclasses_add_classes_host carry classes between devices)"); return FIN_EINVAL; }
+    if (dst->n_colors != src->n_colors) { set_err(err, errlen, "the accumulators have different n_colors (" + std::to_string(dst->n_colors) + " and " + std::to_string(src->n_colors) + ")"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(dst->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // both locks, in a fixed order: two merges in opposite directions from two host threads do not wait for each other
+    fin_eqclasses* const first = std::less<fin_eqclasses*>()(dst, src) ? dst : src;
+    fin_eqclasses* const second = first == dst ? src : dst;
+    std::lock_guard<std::mutex> g1(first->mu);
+    std::lock_guard<std::mutex> g2(second->mu);
+    if (const int wrc = src->pend.wait(err, errlen)) return wrc;
+    uint64_t ctr[8];
+    HIPCHK(hipMemcpy(ctr, ec_ctr(src), sizeof ctr, hipMemcpyDeviceToHost));
+    if (const int frc = ec_flagged(src, ctr, err, errlen)) return frc;
+    // the source's occupied slots are its classes, ctr[2]: a slot's tag is written exactly where the class counter is bumped (claim pass, serial pass) and both
+    // are zeroed together.  So the dense list's length is known without a look at the scan's total, and nothing here waits for the destination
+    const uint64_t n = ctr[2];
+    const uint32_t W = src->words, nb = fin_ec_blocks((uint32_t)src->slots);
+    const size_t off_bytes = (size_t)nb * 8 + 8, sum_bytes = ((size_t)nb * 4 + 7) & ~(size_t)7, want = off_bytes + sum_bytes + (size_t)n * (W + 1) * 8;
+    if (n && want > dst->cap_merge) {   // (an earlier merge's add may still read the old list)
+        if (const int wrc = dst->pend.wait(err, errlen)) return wrc;
+        (void)hipFree(dst->d_merge); dst->d_merge = nullptr; dst->cap_merge = 0;
+        if (hipMalloc(&dst->d_merge, want + want / 8) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (the dense class list of a merge)"); return FIN_ENOMEM; }
+        dst->cap_merge = want + want / 8;
+    }
+    uint64_t* d_rows = nullptr;
+    if (n) {
+        uint64_t* const d_off = (uint64_t*)dst->d_merge; uint64_t* const d_total = d_off + nb; uint32_t* const d_sum = (uint32_t*)((char*)dst->d_merge + off_bytes);
+        d_rows = (uint64_t*)((char*)dst->d_merge + off_bytes + sum_bytes);
+        if (const int orc = dst->pend.order(st, err, errlen)) return orc;   // the scratch is free once the destination's earlier adds have run
+        int rc = fin_launch_ec_occupied(ec_tags(src), (uint32_t)src->slots, d_sum, d_off, d_total, st);
+        if (rc == 0) rc = fin_launch_ec_gather(ec_tags(src), ec_counts(src), ec_rows(src), (uint32_t)src->slots, W, d_off, d_rows, d_rows + (size_t)n * W, st);
+        if (rc != 0) { set_err(err, errlen, std::string("compaction of the equivalence classes: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+        if (const int mrc = src->pend.mark(st, err, errlen)) return mrc;   // a later add or reset of the source runs behind the gather
+    }
+    return ec_add_locked(dst, d_rows, n ? d_rows + (size_t)n * W : nullptr, n, ctr[1], st, err, errlen);
 }
 
 int fin_batch_add_eqclasses(fin_batch* b, fin_eqclasses* e, uint32_t permille, void* hip_stream, char* err, size_t errlen) {
@@ -2007,13 +2104,6 @@ static void ec_canonical(const uint64_t* rows, uint64_t n, uint32_t W, std::vect
     perm.resize((size_t)n);
     for (uint64_t i = 0; i < n; i++) perm[(size_t)i] = i;
     std::sort(perm.begin(), perm.end(), [&](uint64_t a, uint64_t b) { return std::lexicographical_compare(rows + a * W, rows + a * W + W, rows + b * W, rows + b * W + W); });
-}
-
-// what a flagged accumulator answers its readers until the reset
-static int ec_flagged(const fin_eqclasses* e, const uint64_t* ctr, char* err, size_t errlen) {
-    if (ctr[4] & 1u) { set_err(err, errlen, "a row with a bit at or above n_colors was added (not counted; reset the accumulator)"); return FIN_EINVAL; }
-    if ((ctr[4] & 2u) || ctr[2] > e->max_classes) { set_err(err, errlen, "more than max_classes distinct rows (max_classes = " + std::to_string(e->max_classes) + "; reset the accumulator)"); return FIN_ELIMIT; }
-    return FIN_OK;
 }
 
 int fin_eqclasses_download(fin_eqclasses* e, uint64_t* rows_out, uint64_t* reads_out, uint64_t cap, uint64_t* n_classes, uint64_t* n_unaligned, char* err, size_t errlen) {
@@ -2086,6 +2176,39 @@ int fin_rows_eqclasses(const uint64_t* rows, uint64_t n_rows, uint32_t n_colors,
     return n > cap ? FIN_ELIMIT : FIN_OK;
 }
 
+// host twin of the weighted add and of fin_eqclasses_merge: the classes of the union of two class lists -- both lists' non-empty rows with reads > 0 sorted, the
+// reads of runs of equal rows summed
+int fin_classes_merge(const uint64_t* rows_a, const uint64_t* reads_a, uint64_t n_a, const uint64_t* rows_b, const uint64_t* reads_b, uint64_t n_b, uint32_t n_colors,
+                      uint64_t* rows_out, uint64_t* reads_out, uint64_t cap, uint64_t* n_classes) {
+    if (n_colors == 0 || n_colors > FIN_MAX_COLORS) return FIN_ELIMIT;
+    if ((n_a && (!rows_a || !reads_a)) || (n_b && (!rows_b || !reads_b)) || !n_classes || (cap && (!rows_out || !reads_out))) return FIN_EINVAL;
+    const uint32_t W = (n_colors + 63u) / 64u;
+    if (ec_first_stray(rows_a, n_a, n_colors, W) != n_a || ec_first_stray(rows_b, n_b, n_colors, W) != n_b) return FIN_EINVAL;
+    std::vector<std::pair<const uint64_t*, uint64_t>> live;   // {row, reads}
+    const auto take = [&](const uint64_t* rows, const uint64_t* reads, uint64_t n) {
+        for (uint64_t r = 0; r < n; r++) {
+            const uint64_t* row = rows + r * W;
+            bool ne = false;
+            for (uint32_t w = 0; w < W; w++) if (row[w]) ne = true;
+            if (ne && reads[r]) live.push_back({row, reads[r]});
+        }
+    };
+    take(rows_a, reads_a, n_a); take(rows_b, reads_b, n_b);
+    std::sort(live.begin(), live.end(), [&](const std::pair<const uint64_t*, uint64_t>& a, const std::pair<const uint64_t*, uint64_t>& b) {
+        return std::lexicographical_compare(a.first, a.first + W, b.first, b.first + W);
+    });
+    uint64_t n = 0;
+    for (size_t i = 0; i < live.size();) {
+        size_t j = i;
+        uint64_t sum = 0;
+        while (j < live.size() && !memcmp(live[i].first, live[j].first, (size_t)W * 8)) sum += live[j++].second;
+        if (n < cap) { memcpy(rows_out + n * W, live[i].first, (size_t)W * 8); reads_out[n] = sum; }
+        n++; i = j;
+    }
+    *n_classes = n;
+    return n > cap ? FIN_ELIMIT : FIN_OK;
+}
+
 // host: reads_with[c] = the reads of the classes that contain colour c; reads_only[c] = the reads of the class {c}
 int fin_eqclasses_color_tally(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, uint64_t* reads_with, uint64_t* reads_only) {
     if (n_colors == 0 || n_colors > FIN_MAX_COLORS) return FIN_ELIMIT;
@@ -2122,12 +2245,6 @@ static void ab_empty(uint32_t n_colors, double* alpha_out, fin_abundance_info* i
     if (info) { *info = fin_abundance_info(); info->n_unaligned = n_unaligned; info->converged = 1; }
 }
 
-// every device buffer of an estimate, freed on every way out
-struct AbBufs {
-    std::vector<void*> p;
-    ~AbBufs() { for (void* q : p) (void)hipFree(q); }
-    void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return q; }
-};
 // the dense class list of an accumulator and the buffers of the estimates over it: what fin_eqclasses_abundance and fin_eqclasses_bootstrap prepare alike
 struct AbPrep {
     AbBufs bufs;

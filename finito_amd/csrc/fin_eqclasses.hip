@@ -30,6 +30,16 @@
 // W = 1: a lane per row.  W > 1: the wave takes its 64 rows one after the other, lane i holding word i -- fin_col_pseudo_kernel's row copy: coalesced loads, a
 // commutative mix per (word, index), an xor reduction over the wave, one ballot for "empty".
 //
+// THE WEIGHTED ADD (fin_launch_ec_add_classes): a list of {row, weight} pairs -- another accumulator's dense list -- is added as if row r had been
+// added weights[r] times, and n_unaligned all-zero rows besides.  The same three passes, instantiated with WT = true (fin_ec_claimw_kernel, fin_ec_countw_kernel,
+// fin_ec_serialw_kernel); the WT = false instantiations are the kernels above, unchanged:
+//   1  a row of weight 0 becomes EC_DROP before anything looks at it: no class, no flag.
+//   2  counts[s] += w, ONE 64-BIT ATOMIC PER ROW: a merged list is a compacted table, its rows are distinct, so combining a wave's adds over equal slots would
+//      find nothing to combine (duplicate rows are legal and sum, one atomic each).  ctr[0] and ctr[1] get the wave's total weight -- fin_wave_sum64, a weight
+//      may exceed 2^32 -- in one add per wave.
+//   3  counts[sq] = w on a claim, += w on a match; n_done is the sum of the settled weights, ctr[3] still counts list entries.  The scalar n_unaligned is added
+//      here, by lane 0 before the loop bound is looked at: an add of no rows is this launch alone.
+//
 // The download compacts on the device: fin_ec_occ_kernel counts the occupied slots per block of 256, fin_launch_blk_scan (fin_records.hip) makes the blocks'
 // offsets and the total, fin_ec_gather_kernel writes the dense {row, reads} list.
 #include "fin_device.h"
@@ -95,16 +105,38 @@ __device__ __forceinline__ void ec_count(uint32_t r, uint32_t s, bool eq, ull* c
         if (has && !eq && at < n_rows) coll[at] = r;   // (the list starts every add empty: at < n_rows always)
     }
 }
+// pass 2's tail with weights: counts[s] += w where the slot's row is the lane's own, one atomic per row (the list's rows are distinct: nothing to combine); the
+// wave's total weight goes to ctr[0] and ctr[1] in one add each.  w is 0 in a lane without a row and in a dropped one
+__device__ __forceinline__ void ec_count_w(uint32_t r, uint32_t s, bool eq, ull w, ull* counts, ull* ctr, uint32_t* coll, uint32_t n_rows) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool has = s < EC_DROP;
+    const ull m_ne = __ballot(has && !eq);
+    const ull n_un = fin_wave_sum64(s == EC_UNAL ? w : 0ull), n_add = n_un + fin_wave_sum64(has && eq ? w : 0ull);
+    if (lane == 0u) {
+        if (n_add) (void)atomicAdd(ctr + 0, n_add);
+        if (n_un) (void)atomicAdd(ctr + 1, n_un);
+    }
+    if (has && eq) (void)atomicAdd(counts + s, w);
+    if (m_ne) {                              // two distinct rows under one tag: the serial pass settles them
+        ull base = 0;
+        if (lane == 0u) base = atomicAdd(ctr + 5, (ull)__popcll(m_ne));
+        base = fin_bcast64(base, 0);
+        const ull at = base + (ull)__popcll(m_ne & ((1ull << lane) - 1ull));
+        if (has && !eq && at < n_rows) coll[at] = r;   // (the list starts every add empty: at < n_rows always)
+    }
+}
 }  // namespace
 
-// pass 1.  rows: uint64[n_rows * W]; stray: the bits of word W - 1 that no colour has (0: none)
-__global__ __launch_bounds__(256) void fin_ec_claim_kernel(const ull* rows, uint32_t n_rows, uint32_t W, ull stray, ull* tags, ull* tab_rows, uint32_t lg,
-                                                           uint64_t max_classes, uint32_t tag_bits, ull* ctr, uint32_t* slot_of) {
+// pass 1.  rows: uint64[n_rows * W]; stray: the bits of word W - 1 that no colour has (0: none).  WT: weights[n_rows], a row of weight 0 is dropped unseen
+template <bool WT>
+__device__ __forceinline__ void ec_claim(const ull* rows, const ull* weights, uint32_t n_rows, uint32_t W, ull stray, ull* tags, ull* tab_rows, uint32_t lg,
+                                         uint64_t max_classes, uint32_t tag_bits, ull* ctr, uint32_t* slot_of) {
     const uint32_t r = blockIdx.x * FIN_EC_BLK + threadIdx.x, lane = threadIdx.x & 63u;
     const uint32_t r0 = r - lane;           // the wave's first row
     uint32_t mine = EC_DROP;
+    const bool idle = WT && r < n_rows && weights[r] == 0ull;   // (WT false: a constant)
     if (W == 1u) {
-        if (r < n_rows) {
+        if (r < n_rows && !idle) {
             const ull word = rows[r];
             if (word == 0ull) mine = EC_UNAL;
             else if (word & stray) (void)atomicOr(ctr + 4, 1ull);
@@ -117,6 +149,7 @@ __global__ __launch_bounds__(256) void fin_ec_claim_kernel(const ull* rows, uint
         }
     } else {
         const uint32_t n_here = r0 < n_rows ? min(64u, n_rows - r0) : 0u;   // wave-uniform
+        const ull m_idle = WT ? __ballot(idle) : 0ull;
         ull next = 0ull;                    // the row to come, loaded a row ahead
         if (n_here != 0u && lane < W) next = rows[(uint64_t)r0 * W + lane];
         for (uint32_t i = 0; i < n_here; i++) {
@@ -124,7 +157,8 @@ __global__ __launch_bounds__(256) void fin_ec_claim_kernel(const ull* rows, uint
             next = 0ull;
             if (i + 1u < n_here && lane < W) next = rows[(uint64_t)(r0 + i + 1u) * W + lane];
             uint32_t res = EC_DROP;
-            if (__ballot(word != 0ull) == 0ull) res = EC_UNAL;
+            if (WT && ((m_idle >> i) & 1ull)) {}
+            else if (__ballot(word != 0ull) == 0ull) res = EC_UNAL;
             else if (__ballot(lane == W - 1u && (word & stray) != 0ull)) { if (lane == 0u) (void)atomicOr(ctr + 4, 1ull); }
             else {
                 const uint64_t tag = ec_tag(ec_wave_xor(lane < W ? ec_word_hash(word, lane) : 0ull), tag_bits);
@@ -142,13 +176,18 @@ __global__ __launch_bounds__(256) void fin_ec_claim_kernel(const ull* rows, uint
     }
     if (r < n_rows) slot_of[r] = mine;
 }
+__global__ __launch_bounds__(256) void fin_ec_claim_kernel(const ull* rows, uint32_t n_rows, uint32_t W, ull stray, ull* tags, ull* tab_rows, uint32_t lg,
+                                                           uint64_t max_classes, uint32_t tag_bits, ull* ctr, uint32_t* slot_of) {
+    ec_claim<false>(rows, nullptr, n_rows, W, stray, tags, tab_rows, lg, max_classes, tag_bits, ctr, slot_of);
+}
+__global__ __launch_bounds__(256) void fin_ec_claimw_kernel(const ull* rows, const ull* weights, uint32_t n_rows, uint32_t W, ull stray, ull* tags, ull* tab_rows,
+                                                            uint32_t lg, uint64_t max_classes, uint32_t tag_bits, ull* ctr, uint32_t* slot_of) {
+    ec_claim<true>(rows, weights, n_rows, W, stray, tags, tab_rows, lg, max_classes, tag_bits, ctr, slot_of);
+}
 
-// pass 2
-__global__ __launch_bounds__(256) void fin_ec_count_kernel(const ull* rows, uint32_t n_rows, uint32_t W, const ull* tab_rows, ull* counts, ull* ctr,
-                                                           const uint32_t* slot_of, uint32_t* coll, uint32_t combine) {
-    const uint32_t r = blockIdx.x * FIN_EC_BLK + threadIdx.x, lane = threadIdx.x & 63u;
-    const uint32_t r0 = r - lane;
-    const uint32_t s = r < n_rows ? slot_of[r] : EC_DROP;
+// pass 2: is the row of the lane's slot s (or EC_UNAL / EC_DROP: no) its own row r?  Wave-converged
+__device__ __forceinline__ bool ec_same(const ull* rows, uint32_t r, uint32_t s, uint32_t W, const ull* tab_rows) {
+    const uint32_t lane = threadIdx.x & 63u, r0 = r - lane;
     bool eq = false;
     if (W == 1u) {
         if (s < EC_DROP) eq = rows[r] == tab_rows[s];
@@ -174,13 +213,29 @@ __global__ __launch_bounds__(256) void fin_ec_count_kernel(const ull* rows, uint
             if ((int)lane == src) eq = same;
         }
     }
-    ec_count(r, s, eq, counts, ctr, coll, n_rows, combine);
+    return eq;
+}
+__global__ __launch_bounds__(256) void fin_ec_count_kernel(const ull* rows, uint32_t n_rows, uint32_t W, const ull* tab_rows, ull* counts, ull* ctr,
+                                                           const uint32_t* slot_of, uint32_t* coll, uint32_t combine) {
+    const uint32_t r = blockIdx.x * FIN_EC_BLK + threadIdx.x;
+    const uint32_t s = r < n_rows ? slot_of[r] : EC_DROP;
+    ec_count(r, s, ec_same(rows, r, s, W, tab_rows), counts, ctr, coll, n_rows, combine);
+}
+__global__ __launch_bounds__(256) void fin_ec_countw_kernel(const ull* rows, const ull* weights, uint32_t n_rows, uint32_t W, const ull* tab_rows, ull* counts, ull* ctr,
+                                                            const uint32_t* slot_of, uint32_t* coll) {
+    const uint32_t r = blockIdx.x * FIN_EC_BLK + threadIdx.x;
+    const uint32_t s = r < n_rows ? slot_of[r] : EC_DROP;
+    const ull w = s != EC_DROP ? weights[r] : 0ull;   // (s is EC_DROP in a lane beyond n_rows)
+    ec_count_w(r, s, ec_same(rows, r, s, W, tab_rows), w, counts, ctr, coll, n_rows);
 }
 
-// pass 3: one wave.  Lane s & 63 owns tags[s] and counts[s], lane i word i of every row, lane 0 the counters
-__global__ __launch_bounds__(64) void fin_ec_serial_kernel(const ull* rows, uint32_t n_rows, uint32_t W, ull* tags, ull* counts, ull* tab_rows, uint32_t lg, uint64_t max_classes,
-                                                           ull* ctr, const uint32_t* slot_of, const uint32_t* coll) {
+// pass 3: one wave.  Lane s & 63 owns tags[s] and counts[s], lane i word i of every row, lane 0 the counters.  WT: a listed row settles with its weight, and
+// n_unaligned all-zero rows are counted besides
+template <bool WT>
+__device__ __forceinline__ void ec_serial(const ull* rows, const ull* weights, uint32_t n_rows, ull n_unaligned, uint32_t W, ull* tags, ull* counts, ull* tab_rows, uint32_t lg,
+                                          uint64_t max_classes, ull* ctr, const uint32_t* slot_of, const uint32_t* coll) {
     const uint32_t lane = threadIdx.x;
+    if (WT && lane == 0u && n_unaligned) { ctr[0] += n_unaligned; ctr[1] += n_unaligned; }   // (lane 0 owns the counters; its later ctr[0] += is behind this in program order)
     const uint64_t n = min((uint64_t)ctr[5], (uint64_t)n_rows);
     if (n == 0ull) return;
     const uint32_t slots = 1u << lg, mask = slots - 1u, width = min(64u, slots);
@@ -189,6 +244,7 @@ __global__ __launch_bounds__(64) void fin_ec_serial_kernel(const ull* rows, uint
     for (uint64_t j = 0; j < n; j++) {
         const uint32_t r = coll[j], cand = slot_of[r];
         const ull word = lane < W ? rows[(uint64_t)r * W + lane] : 0ull;
+        const ull w = WT ? weights[r] : 1ull;
         const ull tag = fin_bcast64(lane == (cand & 63u) ? tags[cand] : 0ull, (int)(cand & 63u));   // the candidate's tag is the row's
         uint32_t s = (cand + 1u) & mask;
         bool done = false;
@@ -202,12 +258,12 @@ __global__ __launch_bounds__(64) void fin_ec_serial_kernel(const ull* rows, uint
                 cm &= cm - 1ull;
                 const uint32_t sq = b + (uint32_t)q;
                 if (fin_bcast64(t, q) == 0ull) {      // an empty slot ends the chain: the row is new
-                    if ((int)lane == q) { tags[sq] = tag; counts[sq] = 1ull; }
+                    if ((int)lane == q) { tags[sq] = tag; counts[sq] = w; }
                     if (lane < W) tab_rows[(uint64_t)sq * W + lane] = word;
-                    n_new++; n_done++; done = true;
+                    n_new++; n_done += w; done = true;
                 } else if (__ballot(lane < W && tab_rows[(uint64_t)sq * W + lane] != word) == 0ull) {
-                    if ((int)lane == q) counts[sq] += 1ull;
-                    n_done++; done = true;
+                    if ((int)lane == q) counts[sq] += w;
+                    n_done += w; done = true;
                 }
             }
             probed += (uint64_t)(b + width - s);
@@ -221,6 +277,14 @@ __global__ __launch_bounds__(64) void fin_ec_serial_kernel(const ull* rows, uint
         if (full || classes > max_classes) ctr[4] |= 2ull;
         ctr[5] = 0ull;
     }
+}
+__global__ __launch_bounds__(64) void fin_ec_serial_kernel(const ull* rows, uint32_t n_rows, uint32_t W, ull* tags, ull* counts, ull* tab_rows, uint32_t lg, uint64_t max_classes,
+                                                           ull* ctr, const uint32_t* slot_of, const uint32_t* coll) {
+    ec_serial<false>(rows, nullptr, n_rows, 0ull, W, tags, counts, tab_rows, lg, max_classes, ctr, slot_of, coll);
+}
+__global__ __launch_bounds__(64) void fin_ec_serialw_kernel(const ull* rows, const ull* weights, uint32_t n_rows, ull n_unaligned, uint32_t W, ull* tags, ull* counts,
+                                                            ull* tab_rows, uint32_t lg, uint64_t max_classes, ull* ctr, const uint32_t* slot_of, const uint32_t* coll) {
+    ec_serial<true>(rows, weights, n_rows, n_unaligned, W, tags, counts, tab_rows, lg, max_classes, ctr, slot_of, coll);
 }
 
 // blk_sum[block] = the occupied slots among the block's 256
@@ -263,6 +327,25 @@ extern "C" int fin_launch_ec_add(const void* rows, uint32_t n_rows, uint32_t W, 
                        (const uint32_t*)slot_of, coll, combine);
     hipLaunchKernelGGL(fin_ec_serial_kernel, dim3(1), dim3(64), 0, stream, (const ull*)rows, n_rows, W, (ull*)tags, (ull*)counts, (ull*)tab_rows, lg, max_classes, (ull*)ctr,
                        (const uint32_t*)slot_of, (const uint32_t*)coll);
+    return (int)hipGetLastError();
+}
+// the weighted add: row r counts weights[r] times (uint64[n_rows], 0: the row is skipped), and n_unaligned all-zero rows besides.  The same table arguments and
+// scratch; the count pass has no combine.  Three launches; the serial pass alone where there are no rows
+extern "C" int fin_launch_ec_add_classes(const void* rows, const void* weights, uint32_t n_rows, uint64_t n_unaligned, uint32_t W, uint32_t n_colors, void* tags, void* counts,
+                                         void* tab_rows, uint32_t lg, uint64_t max_classes, uint32_t tag_bits, void* ctr, uint32_t* slot_of, uint32_t* coll,
+                                         hipStream_t stream) {
+    const uint32_t nb = (n_rows + FIN_EC_BLK - 1u) / FIN_EC_BLK;
+    if (nb == 0 && n_unaligned == 0) return 0;
+    if (W == 0 || W > 64u || lg == 0 || lg > 27u || tag_bits == 0 || tag_bits > 63u) return (int)hipErrorInvalidValue;
+    const ull stray = (n_colors & 63u) ? ~0ull << (n_colors & 63u) : 0ull;
+    if (nb != 0) {
+        hipLaunchKernelGGL(fin_ec_claimw_kernel, dim3(nb), dim3(256), 0, stream, (const ull*)rows, (const ull*)weights, n_rows, W, stray, (ull*)tags, (ull*)tab_rows, lg,
+                           max_classes, tag_bits, (ull*)ctr, slot_of);
+        hipLaunchKernelGGL(fin_ec_countw_kernel, dim3(nb), dim3(256), 0, stream, (const ull*)rows, (const ull*)weights, n_rows, W, (const ull*)tab_rows, (ull*)counts,
+                           (ull*)ctr, (const uint32_t*)slot_of, coll);
+    }
+    hipLaunchKernelGGL(fin_ec_serialw_kernel, dim3(1), dim3(64), 0, stream, (const ull*)rows, (const ull*)weights, n_rows, (ull)n_unaligned, W, (ull*)tags, (ull*)counts,
+                       (ull*)tab_rows, lg, max_classes, (ull*)ctr, (const uint32_t*)slot_of, (const uint32_t*)coll);
     return (int)hipGetLastError();
 }
 extern "C" uint32_t fin_ec_blocks(uint32_t slots) { return (slots + FIN_EC_BLK - 1u) / FIN_EC_BLK; }

@@ -201,6 +201,9 @@ int fin_launch_pseudoalign_paired(const void* frec, const uint64_t* out_offs, co
 // "ec_combine".  fin_launch_ec_occupied + fin_launch_ec_gather: the occupied slots as a dense {row, reads} list in slot order
 int fin_launch_ec_add(const void* rows, uint32_t n_rows, uint32_t W, uint32_t n_colors, void* tags, void* counts, void* tab_rows, uint32_t lg, uint64_t max_classes,
                       uint32_t tag_bits, uint32_t combine, void* ctr, uint32_t* slot_of, uint32_t* coll, hipStream_t stream);
+// the weighted add: row r counts weights[r] times (uint64[n_rows]; 0: skipped, no class), n_unaligned all-zero rows besides; no combine
+int fin_launch_ec_add_classes(const void* rows, const void* weights, uint32_t n_rows, uint64_t n_unaligned, uint32_t W, uint32_t n_colors, void* tags, void* counts,
+                              void* tab_rows, uint32_t lg, uint64_t max_classes, uint32_t tag_bits, void* ctr, uint32_t* slot_of, uint32_t* coll, hipStream_t stream);
 uint32_t fin_ec_blocks(uint32_t slots);
 int fin_launch_ec_occupied(const void* tags, uint32_t slots, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total, hipStream_t stream);
 int fin_launch_ec_gather(const void* tags, const void* counts, const void* tab_rows, uint32_t slots, uint32_t W, const uint64_t* blk_off, void* out_rows,

@@ -25,6 +25,11 @@ __device__ __forceinline__ uint32_t fin_wave_sum(uint32_t v) {
     for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
     return v;
 }
+__device__ __forceinline__ uint64_t fin_wave_sum64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, d);
+    return v;
+}
 __device__ __forceinline__ uint32_t fin_wave_max(uint32_t v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));

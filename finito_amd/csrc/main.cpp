@@ -516,6 +516,13 @@ static const char* SEARCH_HELP =
     "      --color-report FILE  from the same classes: `colour<TAB>reads<TAB>reads_only` for every colour -- the reads whose set contains the colour and\n"
     "                        the reads whose set is that colour alone --, then `unaligned<TAB>N`, the reads without a colour\n"
     "      --eq-max-classes N  room for N distinct colour sets, 1 to 67108864 (default: 1048576); more is an error\n"
+    "      --eqclasses-in LIST  a file with one path per line, each a classes file as --eqclasses writes it (optionally ended by `unaligned<TAB>N`), made\n"
+    "                        under the same --color-refs: their classes are added on the GPU before the first chunk, exactly and in integers, so\n"
+    "                        --eqclasses, --color-report and --abundance (with --ab-bootstraps) cover the earlier runs and this one. A colour at or above\n"
+    "                        the number of references, a malformed line or a wrong n_colours is an error that names file and line. Only legal together\n"
+    "                        with --eqclasses, --color-report or --abundance\n"
+    "      --eqclasses-unaligned 1  end the file of --eqclasses with the line `unaligned<TAB>N`, the reads without a colour, so that --eqclasses-in carries\n"
+    "                        them into a later run (default: no such line). Only legal together with --eqclasses\n"
     "      --abundance FILE  from the same classes, on the GPU: expected reads per reference by EM (each class's reads split over its colours in\n"
     "                        proportion to the current estimate, repeated). `colour<TAB>reads<TAB>share` per colour -- reads = the expected reads, share =\n"
     "                        reads / length over its sum, both as %.10g --, then `unaligned<TAB>N`, `iterations<TAB>T<TAB>converged` (or `max_iters`) and\n"
@@ -942,6 +949,72 @@ static void color_by_search(const FinimizerIndex& index, const string& fasta, ui
 // --eqclasses FILE / --color-report FILE: one accumulator of equivalence classes for the whole run; every chunk's reads are pseudoaligned and added on the
 // first device (fin_search_batch_add_eqclasses), nothing per read comes back; both files are written after the last chunk
 static fin_eqclasses* g_eqc = nullptr;
+// --eqclasses-in: one classes file, as --eqclasses writes it -- `reads<TAB>n_colours<TAB>c1,c2,...` per class, then at most one line `unaligned<TAB>N` --, parsed
+// before the index is loaded (every error names the file and the line) and added to the accumulator once it exists (fin_eqclasses_add_classes_host)
+static bool parse_u64(const string& t, uint64_t& out) {
+    if (t.empty() || t.size() > 20) return false;
+    out = 0;
+    for (char ch : t) {
+        if (ch < '0' || ch > '9') return false;
+        const uint64_t d = (uint64_t)(ch - '0');
+        if (out > (UINT64_MAX - d) / 10) return false;
+        out = out * 10 + d;
+    }
+    return true;
+}
+struct EqClassesFile { string path; vector<uint64_t> rows, reads; uint64_t unaligned = 0; };
+static EqClassesFile eqclasses_parse_file(const string& path, uint32_t n_colors) {
+    ifstream in(path);
+    if (!in.good()) throw runtime_error("--eqclasses-in: error opening file " + path);
+    EqClassesFile out;
+    out.path = path;
+    vector<uint64_t>& rows = out.rows; vector<uint64_t>& reads = out.reads;
+    uint64_t& unaligned = out.unaligned;
+    const uint32_t W = (n_colors + 63u) / 64u;
+    uint64_t line_no = 0;
+    bool closed = false;   // the unaligned line was met: nothing may follow
+    string line;
+    const auto bad = [&](const string& what) { return runtime_error("--eqclasses-in: " + path + " line " + to_string(line_no) + ": " + what); };
+    while (getline(in, line)) {
+        line_no++;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        if (closed) throw bad("a line behind the `unaligned` line");
+        const size_t t1 = line.find('\t');
+        if (t1 == string::npos) throw bad("malformed line, `reads<TAB>n_colours<TAB>c1,c2,...` or `unaligned<TAB>N` wanted");
+        if (line.compare(0, t1, "unaligned") == 0) {
+            if (!parse_u64(line.substr(t1 + 1), unaligned)) throw bad("malformed line, `unaligned<TAB>N` wanted");
+            closed = true;
+            continue;
+        }
+        const size_t t2 = line.find('\t', t1 + 1);
+        uint64_t n_reads = 0, n_listed = 0;
+        if (t2 == string::npos || !parse_u64(line.substr(0, t1), n_reads) || !parse_u64(line.substr(t1 + 1, t2 - t1 - 1), n_listed) || t2 + 1 == line.size())
+            throw bad("malformed line, `reads<TAB>n_colours<TAB>c1,c2,...` wanted");
+        const size_t at = rows.size();
+        rows.resize(at + W, 0);
+        uint64_t n_set = 0;
+        for (size_t p = t2 + 1; p <= line.size();) {
+            size_t q = line.find(',', p);
+            if (q == string::npos) q = line.size();
+            uint64_t c = 0;
+            if (!parse_u64(line.substr(p, q - p), c)) throw bad("malformed line, a colour list `c1,c2,...` wanted");
+            if (c >= n_colors) throw bad("colour " + to_string(c) + " is not below the " + to_string(n_colors) + " references of --color-refs");
+            if (rows[at + (size_t)(c >> 6)] >> (c & 63) & 1) throw bad("malformed line, colour " + to_string(c) + " is listed twice");
+            rows[at + (size_t)(c >> 6)] |= 1ull << (c & 63);
+            n_set++;
+            p = q + 1;
+        }
+        if (n_set != n_listed) throw bad("n_colours is " + to_string(n_listed) + ", the list has " + to_string(n_set) + " colours");
+        reads.push_back(n_reads);
+    }
+    return out;
+}
+static void eqclasses_add_file(const EqClassesFile& f) {
+    char err[512] = {0};
+    if (fin_eqclasses_add_classes_host(g_eqc, f.rows.data(), f.reads.data(), f.reads.size(), f.unaligned, err, sizeof err) != FIN_OK)
+        throw runtime_error("--eqclasses-in: " + f.path + ": " + err);
+}
 static void eqclasses_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
     char err[512] = {0};
     if (g_paired) {
@@ -1178,7 +1251,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
@@ -1195,6 +1268,8 @@ static int search_fmin(int argc, char** argv) {
     if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
     if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
     if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses, --color-report or --abundance");
+    if (o.has("eqclasses-in") && !eq_asked) throw runtime_error("--eqclasses-in is only legal together with --eqclasses, --color-report or --abundance");
+    if (o.has("eqclasses-unaligned") && !o.has("eqclasses")) throw runtime_error("--eqclasses-unaligned is only legal together with --eqclasses");
     if (o.has("ab-seed") && !o.has("ab-bootstraps")) throw runtime_error("--ab-seed is only legal together with --ab-bootstraps");
     for (const char* name : {"ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps"})
         if (o.has(name) && !o.has("abundance")) throw runtime_error(string("--") + name + " is only legal together with --abundance");
@@ -1246,6 +1321,13 @@ static int search_fmin(int argc, char** argv) {
         color_refs = readlines(o.get("color-refs"));
         if (color_refs.empty()) throw runtime_error("--color-refs: " + o.get("color-refs") + " is empty, it names no reference");
         if (color_refs.size() > FIN_MAX_COLORS) throw runtime_error("--color-refs: " + o.get("color-refs") + " names " + to_string(color_refs.size()) + " references, at most " + to_string(FIN_MAX_COLORS) + " colours are supported");
+    }
+    const bool eqc_unaligned = o.has("eqclasses-unaligned") && o.get("eqclasses-unaligned") != "0" && o.get("eqclasses-unaligned") != "false";
+    vector<EqClassesFile> eqc_in;
+    if (o.has("eqclasses-in")) {
+        const vector<string> paths = readlines(o.get("eqclasses-in"));
+        if (paths.empty()) throw runtime_error("--eqclasses-in: " + o.get("eqclasses-in") + " is empty, it names no classes file");
+        for (auto& f : paths) eqc_in.push_back(eqclasses_parse_file(f, (uint32_t)color_refs.size()));
     }
     g_scr_invert = o.has("screen-invert") && o.get("screen-invert") != "0" && o.get("screen-invert") != "false" ? 1 : 0;
     if (o.has("min-depth") && !o.has("unitig-depth")) throw runtime_error("--min-depth is only legal together with --unitig-depth");
@@ -1445,6 +1527,7 @@ static int search_fmin(int argc, char** argv) {
             g_psa_read0 = 0;
         }
         if ((!eqc_file.empty() || !crep_file.empty() || !ab_file.empty()) && fin_eqclasses_create(g_colors, eq_max_classes, &g_eqc, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        if (g_eqc) for (auto& f : eqc_in) eqclasses_add_file(f);   // the earlier runs' classes, before the first chunk
     }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
@@ -1557,6 +1640,7 @@ static int search_fmin(int argc, char** argv) {
                 append_colors(text, rows.data() + (size_t)i * W, W);
                 text += '\n';
             }
+            if (eqc_unaligned) { text += "unaligned\t"; text += to_string(un); text += '\n'; }
             ofstream cf(eqc_file, ios::binary | ios::trunc);
             cf.write(text.data(), (streamsize)text.size());
             if (!cf) throw runtime_error("Error writing to file: " + eqc_file);

@@ -61,3 +61,32 @@ def pair_offsets(offsets, k):
     out = np.zeros(len(nk) + 1, dtype=np.int64)
     np.cumsum(nk, out=out[1:])
     return out
+
+
+def replicate_colors(colors, index, n_colors, rank, dist, src=0):
+    """Every rank gets rank `src`'s colour matrix: its Colors.download() bits are broadcast (the index is replicated, so unitig numbers agree), and every other
+    rank uploads them into a Colors of its own beside its replica.  `colors` is rank src's matrix (ignored elsewhere); returns this rank's Colors."""
+    box = [colors.download()[0] if rank == src else None]
+    dist.broadcast_object_list(box, src=src)
+    if rank == src:
+        return colors
+    return index.colors(n_colors, box[0])
+
+
+def gather_other_classes(rows, reads, n_unaligned, rank, dist):
+    """The gather of allreduce_eqclasses, callable without an accumulator: every rank contributes its class list and unaligned count (all_gather_object: gloo and
+    RCCL alike); returns the other ranks' [(rows, reads, n_unaligned)], in rank order."""
+    world = dist.get_world_size()
+    gathered = [None] * world
+    dist.all_gather_object(gathered, (np.ascontiguousarray(rows, dtype=np.uint64), np.ascontiguousarray(reads, dtype=np.uint64), int(n_unaligned)))
+    return [gathered[r] for r in range(world) if r != rank]
+
+
+def allreduce_eqclasses(eq, dist):
+    """Every rank's EqClasses gains every other rank's classes: afterwards each holds the whole sample's classes in HBM, and eq.abundance() / eq.bootstrap() give
+    every rank the estimate of the same sufficient statistic.  Exact, in integers (EqClasses.add_classes).  This ADDS to `eq`: calling it twice counts the other
+    ranks twice.  Returns eq."""
+    rows, reads, un = eq.download()
+    for o_rows, o_reads, o_un in gather_other_classes(rows, reads, un, dist.get_rank(), dist):
+        eq.add_classes(o_rows, o_reads, o_un)
+    return eq

@@ -883,8 +883,10 @@ int fin_records_pseudoalign(const fin_read_record* recs, uint64_t n_reads, const
  * row is compared in the next).  So where the others say "adds on different streams stay unordered", here every add runs behind every add and reset of this
  * accumulator issued so far, on whichever stream; order, launches and mark are one step under the accumulator's lock, so adds from several host threads take
  * effect in issue order.  Resets are ordered as fin_hits_reset is.
- * Out of scope: partitioned indexes, fin_search_batch_multi / dist.py, the C++ mirror (a caller with several GPUs keeps an
- * accumulator per replica and merges the downloads with fin_rows_eqclasses' arithmetic), a growing table, more than 4096 colours. */
+ * SEVERAL ACCUMULATORS: the classes are the sufficient statistic, and accumulators over disjoint read sets merge exactly, in integers, into the
+ * accumulator of the union -- fin_eqclasses_merge on one device, fin_eqclasses_download + fin_eqclasses_add_classes_host between devices, ranks or runs
+ * (finito_amd/dist.py: allreduce_eqclasses); fin_classes_merge is the host statement.
+ * Out of scope: partitioned indexes, fin_search_batch_multi, the C++ mirror, a growing table, more than 4096 colours. */
 typedef struct fin_eqclasses fin_eqclasses;
 /* an empty accumulator beside the colours.  FIN_ELIMIT: max_classes is not 1 .. 2^26.  Free it before the colours. */
 int fin_eqclasses_create(const fin_colors* c, uint64_t max_classes, fin_eqclasses** out, char* err, size_t errlen);
@@ -892,6 +894,27 @@ int fin_eqclasses_reset(fin_eqclasses* e, void* hip_stream);   /* empties it and
 void fin_eqclasses_free(fin_eqclasses* e);
 /* rows any producer left in HBM: uint64[n_rows * W] on the accumulator's device, valid until the add has finished; on hip_stream, no sync.  n_rows < 2^31 */
 int fin_eqclasses_add_rows(fin_eqclasses* e, const void* d_rows, uint64_t n_rows, void* hip_stream, char* err, size_t errlen);
+/* THE WEIGHTED ADD: a class list {row, reads} any producer left in HBM -- d_rows uint64[n_classes * W], d_reads uint64[n_classes], on the accumulator's device,
+ * valid until the add has finished; on hip_stream, no sync; n_classes < 2^31.  Exact and in integers: as if row r had been added d_reads[r] times by
+ * fin_eqclasses_add_rows, and n_unaligned all-zero rows besides.  An all-zero row counts its reads as unaligned; a row of 0 reads adds nothing and makes no
+ * class; duplicate rows are legal and sum; a stray bit and a full table flag the accumulator as they do for fin_eqclasses_add_rows.  Ordered behind every add and
+ * reset issued so far, as every add is. */
+int fin_eqclasses_add_classes(fin_eqclasses* e, const void* d_rows, const void* d_reads, uint64_t n_classes, uint64_t n_unaligned, void* hip_stream, char* err,
+                              size_t errlen);
+/* the same from host arrays (a download, another rank's classes, a file): FIN_EINVAL, before anything is added, if any row has a bit at or above n_colors.
+ * Uploads, adds on the null stream and returns when the add has run: the arrays may be reused at once. */
+int fin_eqclasses_add_classes_host(fin_eqclasses* e, const uint64_t* rows, const uint64_t* reads, uint64_t n_classes, uint64_t n_unaligned, char* err, size_t errlen);
+/* dst gains what src holds -- its classes with their reads, and its unaligned count --; src is left as it was found.  A WAITING call for src: under both
+ * accumulators' locks (taken in address order) it waits for src's adds and resets and reads its flags; a flagged src is refused with the download's codes
+ * (FIN_EINVAL: a stray bit, FIN_ELIMIT: more than max_classes) and dst is untouched.  Then, on hip_stream and without a further wait: src's table is compacted on
+ * the device (the download's count, scan and gather; neither the table nor the dense list crosses PCIe) and the list is added to dst by the weighted add, behind
+ * every add and reset of dst issued so far.  LIFETIME: the dense list is scratch that DST OWNS and only grows (n_classes * (8 W + 8) bytes beside dst's table); a
+ * later merge into dst reuses it behind this one's add, so the call does not wait for its own add.  src may be added to, reset or freed at once: each of these runs behind, or
+ * waits for, the gather.
+ * FIN_EINVAL: a null argument, dst == src, different devices, different n_colors.  Two fin_colors objects with equal n_colors on one device are legal: the rows
+ * mean what the caller's colour numbering means.  Accumulators on DIFFERENT DEVICES go through fin_eqclasses_download and fin_eqclasses_add_classes_host (a peer
+ * copy is not built). */
+int fin_eqclasses_merge(fin_eqclasses* dst, fin_eqclasses* src, void* hip_stream, char* err, size_t errlen);
 /* the batch's most recent run, pseudoaligned against the accumulator's colours at `permille`, then added.  fin_batch_pseudoalign is ALWAYS called first (the
  * batch does not remember which matrix and threshold its rows belong to): its FIN_EINVAL / FIN_ELIMIT are this call's -- the batch has not run, another index or
  * device, permille > 1000, a run whose overflow list overran (nothing of it is added) --, it may wait for the run's overflow verdict, and afterwards the batch's
@@ -912,6 +935,12 @@ int fin_eqclasses_stats(fin_eqclasses* e, uint64_t out[4], char* err, size_t err
  * too small (*n_classes still set) */
 int fin_rows_eqclasses(const uint64_t* rows, uint64_t n_rows, uint32_t n_colors, uint64_t* rows_out, uint64_t* reads_out, uint64_t cap, uint64_t* n_classes,
                        uint64_t* n_unaligned);
+/* host, no device: the twin of the weighted add and of fin_eqclasses_merge -- the classes of the union of two class lists, in canonical order, into
+ * rows_out[cap * W] and reads_out[cap].  Either list may be unsorted and may hold duplicate rows (their reads sum); classes of 0 reads are dropped, and so are
+ * all-zero rows (they are no class: the caller adds the unaligned counts itself).  Error codes as fin_rows_eqclasses: FIN_EINVAL: a bit at or above n_colors;
+ * FIN_ELIMIT: n_colors is 0 or above FIN_MAX_COLORS, or cap is too small (*n_classes still set) */
+int fin_classes_merge(const uint64_t* rows_a, const uint64_t* reads_a, uint64_t n_a, const uint64_t* rows_b, const uint64_t* reads_b, uint64_t n_b, uint32_t n_colors,
+                      uint64_t* rows_out, uint64_t* reads_out, uint64_t cap, uint64_t* n_classes);
 /* host: the per-colour tally of n_classes classes: reads_with[n_colors], reads_only[n_colors] */
 int fin_eqclasses_color_tally(const uint64_t* class_rows, const uint64_t* class_reads, uint64_t n_classes, uint32_t n_colors, uint64_t* reads_with, uint64_t* reads_only);
 
