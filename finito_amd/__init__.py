@@ -298,6 +298,25 @@ def lib():
         L.fin_eqclasses_bootstrap.argtypes = [vp, f64p, u32, C.c_double, u32, u64, f64p, C.POINTER(AbundanceInfo), f64p, u64p, u32p, u8p, cp, C.c_size_t]
         L.fin_classes_resample.argtypes = [u64p, u64p, u64, u32, u64, u32, u64p, C.c_int]
         L.fin_classes_bootstrap.argtypes = [u64p, u64p, u64, u32, f64p, u32, C.c_double, u32, u64, f64p, C.POINTER(AbundanceInfo), f64p, u64p, u32p, u8p, C.c_int]
+        L.fin_assign_create.argtypes = [vp, f64p, f64p, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_assign_reset.argtypes = [vp, vp]
+        L.fin_assign_free.argtypes = [vp]
+        L.fin_assign_free.restype = None
+        L.fin_assign_set.argtypes = [vp, f64p, f64p, vp, cp, C.c_size_t]
+        L.fin_assign_rows.argtypes = [vp, vp, u64, vp, vp, vp, cp, C.c_size_t]
+        L.fin_assign_download.argtypes = [vp, u64p, u64p, u64p, cp, C.c_size_t]
+        L.fin_batch_assign.argtypes = [vp, vp, u32, u32, vp, cp, C.c_size_t]
+        L.fin_batch_device_assign_rows.restype = vp
+        L.fin_batch_device_assign_rows.argtypes = [vp]
+        L.fin_batch_device_assign_heads.restype = vp
+        L.fin_batch_device_assign_heads.argtypes = [vp]
+        L.fin_batch_download_assign.argtypes = [vp, u64p, vp, cp, C.c_size_t]
+        L.fin_batch_assign_bin.argtypes = [vp, u32, u64p, cp, C.c_size_t]
+        L.fin_batch_device_bin_ids.restype = vp
+        L.fin_batch_device_bin_ids.argtypes = [vp]
+        L.fin_batch_download_bin.argtypes = [vp, u32p, cp, C.c_size_t]
+        L.fin_search_batch_assign.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, u64p, vp, cp, C.c_size_t]
+        L.fin_rows_assign.argtypes = [u64p, u64, u32, f64p, f64p, u64p, vp, u64p, u64p, u64p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -556,6 +575,38 @@ class Batch:
         """(rows, heads) device pointers of the fragments' rows, 0 before pseudoalign_pairs()"""
         return int(self.L.fin_batch_device_pair_rows(self.h) or 0), int(self.L.fin_batch_device_pair_heads(self.h) or 0)
 
+    def assign(self, assigner, permille=1000, pairs=False, both=False, stream=None):
+        """the most recent run's reads (pairs: its fragments) assigned to references under an Assign's weights and thresholds, made and counted on the device
+        (fin_batch_assign + fin_batch_download_assign): (assigned rows uint64[F, W], heads READ_ASSIGN_DTYPE[F]).  Pseudoaligns first, at `permille`; the
+        pseudo rows survive"""
+        assigner.add(self, permille, pairs, both, stream)
+        n = self.n_reads // 2 if pairs else self.n_reads
+        rows = np.zeros((max(n, 1), assigner.words), dtype=np.uint64)
+        heads = np.zeros(max(n, 1), dtype=READ_ASSIGN_DTYPE)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_download_assign(self.h, rows.ctypes.data_as(C.POINTER(C.c_uint64)), heads.ctypes.data_as(C.c_void_p), err, 512), err)
+        return rows[:n], heads[:n]
+
+    def assign_bin(self, colour):
+        """the ascending numbers (uint32) of the reads or fragments of the last assign() that have `colour` assigned, compacted on the device
+        (fin_batch_assign_bin + fin_batch_download_bin); device_bin_ptr() is the list in HBM"""
+        if not 0 <= int(colour) <= 0xFFFFFFFF:
+            raise FinitoError(FIN_EINVAL, "Batch.assign_bin: colour is an unsigned 32-bit number")
+        n = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_assign_bin(self.h, int(colour), C.byref(n), err, 512), err)
+        ids = np.zeros(max(int(n.value), 1), dtype=np.uint32)
+        _check(self.L.fin_batch_download_bin(self.h, ids.ctypes.data_as(C.POINTER(C.c_uint32)), err, 512), err)
+        return ids[: int(n.value)]
+
+    def device_assign_ptrs(self):
+        """(assigned rows, heads) device pointers, 0 before assign()"""
+        return int(self.L.fin_batch_device_assign_rows(self.h) or 0), int(self.L.fin_batch_device_assign_heads(self.h) or 0)
+
+    def device_bin_ptr(self):
+        """the bin's ids in HBM, 0 before assign_bin()"""
+        return int(self.L.fin_batch_device_bin_ids(self.h) or 0)
+
     def pipeline_counts(self, n=64):
         """kernel 4's queue counters of the last run (fin_batch_pipeline_counts)"""
         out = (C.c_uint32 * n)()
@@ -811,6 +862,11 @@ class Colors(_Accumulator):
         """an accumulator of equivalence classes beside this matrix (EqClasses)"""
         return EqClasses(self, max_classes)
 
+    def assigner(self, weights, thresholds=0.5):
+        """an accumulator that assigns reads to references beside this matrix (Assign): weights one per colour, usually Abundance.weights(); thresholds one per
+        colour or a scalar for all -- thresholds=ab.theta is the mGEMS rule"""
+        return Assign(self, weights, thresholds)
+
 
 class EqClasses(_Accumulator):
     """the equivalence classes of pseudoaligned reads -- the distinct colour rows the added runs produced and how many reads have each --, accumulated in HBM
@@ -948,6 +1004,93 @@ class EqClasses(_Accumulator):
         return [int(v) for v in out]
 
 
+def _assign_args(what, n_colors, weights, thresholds):
+    """the checks of fin_assign_create, fin_assign_set and fin_rows_assign, made here so that the message can say what was wrong; a scalar threshold is broadcast"""
+    nc = int(n_colors)
+    if not 1 <= nc <= 4096:
+        raise FinitoError(FIN_ELIMIT, "%s: n_colors is 1 .. 4096" % what)
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if len(w) != nc:
+        raise FinitoError(FIN_EINVAL, "%s: %d weights for %d colours" % (what, len(w), nc))
+    t = np.asarray(thresholds, dtype=np.float64)
+    t = np.full(nc, float(t), dtype=np.float64) if t.ndim == 0 else np.ascontiguousarray(t).reshape(-1)
+    if len(t) != nc:
+        raise FinitoError(FIN_EINVAL, "%s: %d thresholds for %d colours" % (what, len(t), nc))
+    bad = np.nonzero(~(np.isfinite(w) & (w >= 0)))[0]
+    if len(bad):
+        raise FinitoError(FIN_EINVAL, "%s: the weight of colour %d is not a finite number >= 0" % (what, int(bad[0])))
+    bad = np.nonzero(~((t >= 0) & (t <= 1)))[0]
+    if len(bad):
+        raise FinitoError(FIN_EINVAL, "%s: the threshold of colour %d is not a number in 0 .. 1" % (what, int(bad[0])))
+    return w, t
+
+
+def _assign_unit(pairs, both):
+    return (2 if both else 1) if pairs else 0
+
+
+class Assign(_Accumulator):
+    """reads assigned to references from per-colour weights, on the device beside a colour matrix (fin_assign_* of the C ABI): colour c of a row
+    is assigned iff x[c] > 0, d > 0 and x[c] >= thr[c] * d, d being the sum of the row's weights in the EM's order.  Accumulates assigned[c], sole[c] and the
+    counters {rows, unaligned, unassigned, multi}; free it before the colours."""
+    _FREE, _RESET = "fin_assign_free", "fin_assign_reset"
+
+    def __init__(self, colors, weights, thresholds=0.5):
+        self.colors = colors
+        self.index = colors.index
+        self.n_colors = colors.n_colors
+        self.words = colors.words
+        w, t = _assign_args("Assign", self.n_colors, weights, thresholds)
+        f64p = C.POINTER(C.c_double)
+        self._create("fin_assign_create", colors.h, w.ctypes.data_as(f64p), t.ctypes.data_as(f64p))
+
+    def set(self, weights, thresholds=0.5, stream=None):
+        """new weights and thresholds, behind the adds issued so far; the counts stay (fin_assign_set)"""
+        w, t = _assign_args("Assign.set", self.n_colors, weights, thresholds)
+        f64p = C.POINTER(C.c_double)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_assign_set(self.h, w.ctypes.data_as(f64p), t.ctypes.data_as(f64p), C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add(self, batch, permille=1000, pairs=False, both=False, stream=None):
+        """the batch's most recent run, pseudoaligned at `permille` per read (pairs: per fragment; both: FIN_PAIR_BOTH), assigned and counted on a HIP stream;
+        no sync (fin_batch_assign).  Batch.assign() also brings the rows and heads back"""
+        return _acc_add(self, "fin_batch_assign", batch, stream, _permille("Assign.add", permille), _assign_unit(pairs, both))
+
+    def add_rows(self, ptr, n_rows, out_rows_ptr=0, heads_ptr=0, stream=None):
+        """rows any producer left in HBM: a device pointer to uint64[n_rows, W]; the assigned rows and READ_ASSIGN_DTYPE heads go to the device pointers given
+        (0: not wanted).  All valid until the add has finished; no sync (fin_assign_rows)"""
+        if not 0 <= int(n_rows) <= 0xFFFFFFFFFFFFFFFF:
+            raise FinitoError(FIN_EINVAL, "Assign.add_rows: n_rows is an unsigned 64-bit number")
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_assign_rows(self.h, C.c_void_p(int(ptr) or 0), int(n_rows), C.c_void_p(int(out_rows_ptr) or 0), C.c_void_p(int(heads_ptr) or 0),
+                                      C.c_void_p(stream or 0), err, 512), err)
+        return self
+
+    def add_reads(self, reads, permille=1000, pairs=False, both=False, strands=FIN_MERGED, want_rows=True):
+        """(assigned rows uint64[F, W] or None, heads READ_ASSIGN_DTYPE[F]): a read set from host buffers, sub-batches pipelined and cut between pairs only,
+        pseudoaligned, assigned and counted (fin_search_batch_assign)"""
+        bases, offsets = flatten(reads)
+        n = len(offsets) - 1
+        nf = n // 2 if pairs else n
+        rows = np.zeros((max(nf, 1), self.words), dtype=np.uint64) if want_rows else None
+        heads = np.zeros(max(nf, 1), dtype=READ_ASSIGN_DTYPE)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_assign(self.index.h, *_reads_args((bases, offsets)), int(strands), self.h, _permille("Assign.add_reads", permille),
+                                              _assign_unit(pairs, both), rows.ctypes.data_as(C.POINTER(C.c_uint64)) if want_rows else None,
+                                              heads.ctypes.data_as(C.c_void_p), err, 512), err)
+        return (rows[:nf] if want_rows else None), heads[:nf]
+
+    def download(self):
+        """(assigned uint64[n_colors], sole uint64[n_colors], counters uint64[4] = rows, unaligned, unassigned, multi); waits for the adds (fin_assign_download)"""
+        u64p = C.POINTER(C.c_uint64)
+        assigned, sole = np.zeros(self.n_colors, dtype=np.uint64), np.zeros(self.n_colors, dtype=np.uint64)
+        counters = np.zeros(4, dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_assign_download(self.h, assigned.ctypes.data_as(u64p), sole.ctypes.data_as(u64p), counters.ctypes.data_as(u64p), err, 512), err)
+        return assigned, sole, counters
+
+
 class Abundance:
     """the result of an abundance estimate: alpha = expected reads per colour, theta = alpha / N, rho = (alpha / len) / sum(alpha / len) -- the
     share of the sample's copies; iters, converged, loglik (of the last iteration), max_change (max |delta alpha| / max(alpha, 1) of the last iteration),
@@ -962,6 +1105,11 @@ class Abundance:
         per_len = alpha / lengths if lengths is not None else alpha
         self.rho = per_len / per_len.sum() if per_len.sum() > 0 else np.zeros_like(alpha)
         self.trace = trace[: self.iters] if trace is not None else None
+        self.lengths = lengths
+
+    def weights(self):
+        """alpha / lengths: the per-colour weights of Colors.assigner"""
+        return self.alpha / self.lengths if self.lengths is not None else self.alpha.copy()
 
 
 class Bootstrap:
@@ -1630,6 +1778,8 @@ READ_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), 
 PAIR_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), ("n_colors", np.uint32), ("n_colored_first", np.uint32)])   # fin_pair_pseudo
 FIN_PAIR_ANY, FIN_PAIR_BOTH = 0, 1
 FIN_MAX_COLORS = 4096
+READ_ASSIGN_DTYPE = np.dtype([("n_assigned", np.uint32), ("best", np.uint32)])   # fin_read_assign
+FIN_NO_COLOR = 0xFFFFFFFF
 DEPTH_STAT_DTYPE = np.dtype([("sum", np.uint64), ("max", np.uint32), ("n_at_least", np.uint32)])            # fin_depth_stat
 VARIANT_DTYPE = np.dtype([("u", np.uint32), ("off", np.uint32), ("cover", np.uint32), ("ref", np.uint32), ("alt", np.uint32, (4,))])   # fin_variant
 
@@ -1964,6 +2114,25 @@ def rows_eqclasses(rows, n_colors):
     if rc != 0:
         raise FinitoError(rc, "fin_rows_eqclasses: n_colors outside 1 .. 4096, or a row with a bit at or above n_colors")
     return out[: int(n.value)], reads[: int(n.value)], int(un.value)
+
+
+def rows_assign(rows, n_colors, weights, thresholds=0.5, n_threads=0):
+    """host: (assigned rows uint64[n, W], heads READ_ASSIGN_DTYPE[n], assigned uint64[n_colors], sole uint64[n_colors], counters uint64[4]) of rows
+    uint64[n, W] under weights and thresholds (fin_rows_assign) -- the CPU statement of Assign, in its order; the result does not depend on n_threads"""
+    w, t = _assign_args("rows_assign", n_colors, weights, thresholds)
+    nc = int(n_colors)
+    W = (nc + 63) // 64
+    a = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, W)
+    n = len(a)
+    out = np.zeros((max(n, 1), W), dtype=np.uint64)
+    heads = np.zeros(max(n, 1), dtype=READ_ASSIGN_DTYPE)
+    assigned, sole, counters = np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    u64p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+    rc = lib().fin_rows_assign(a.ctypes.data_as(u64p), n, nc, w.ctypes.data_as(f64p), t.ctypes.data_as(f64p), out.ctypes.data_as(u64p), heads.ctypes.data_as(C.c_void_p),
+                               assigned.ctypes.data_as(u64p), sole.ctypes.data_as(u64p), counters.ctypes.data_as(u64p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_rows_assign: a row with a bit at or above n_colors")
+    return out[:n], heads[:n], assigned, sole, counters
 
 
 def _u64(what, name, v):

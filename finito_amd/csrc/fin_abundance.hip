@@ -25,23 +25,13 @@
 #include "fin_device.h"
 #include "fin_kernels.h"
 #include "fin_wave.h"
+#include "fin_absum.h"
 
 #define FIN_AB_BLK 256u
 #define FIN_AB_RED_WAVES 16u
 
 namespace {
 typedef unsigned long long ull;
-
-// the sum over lanes 0 .. width - 1 (a power of two <= 64), the same in each of them: the order is the butterfly's, whatever the values
-__device__ __forceinline__ double ab_butterfly(double v, uint32_t width) {
-    for (uint32_t d = width >> 1; d >= 1u; d >>= 1) v += __shfl_xor(v, (int)d);
-    return v;
-}
-__device__ __forceinline__ double ab_bits_sum(ull word, const double* x64) {   // x over the word's set bits, ascending
-    double s = 0.0;
-    for (; word; word &= word - 1ull) s += x64[__ffsll((long long)word) - 1];
-    return s;
-}
 }  // namespace
 
 // rowsT[w][j] = rows[j][w]: a tile of 64 classes through LDS, both sides coalesced

@@ -96,7 +96,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -134,6 +134,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"ec_tag_bits", 63, 1, 63},                    // fin_eqclasses: bits of a row's tag in the table (fin_eqclasses.hip); tests narrow it so that distinct rows share tags and go through the serial pass.  Read by the first add after the accumulator's creation or reset and kept until the next reset: a table's tags are made one way
     {"ec_combine", 1, 0, 1},                       // fin_eqclasses' count pass: 1 = a wave's adds combined over its distinct slots, one atomic each; 0 = one atomic per row (tools/ab_eqclasses.py measures both)
     {"ab_chunk", 0, 0, 1ll << 26},                 // fin_eqclasses_abundance's column pass: classes per chunk, rounded up to a multiple of 64 (fin_abundance.hip); 0 = auto: 256, more once that would make over 1024 chunks (which also bounds what a value can ask for).  The order of the column sums is a function of it, so two estimates compare bit for bit only under one value; tests set 64 so that small cases cross chunk seams
+    {"assign_rpb", 0, 0, 1ll << 26},               // fin_assign_rows: rows per block of fin_assign_rows_kernel (fin_assign.hip); 0 = auto: 1024, more once that would make over 2048 blocks; never so few that there would be over 2^20 blocks.  The results do not depend on it; tests set 64 so that small cases cross block seams
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -729,6 +730,12 @@ struct fin_batch {
     void* d_psa_rows = nullptr; size_t cap_psa_rows = 0; void* d_psa_heads = nullptr; size_t cap_psa_heads = 0; bool psa_ready = false; uint32_t psa_words = 0;
     // per-fragment colour rows and heads (fin_batch_pseudoalign_paired): buffers of their own, kept and only grown; forgotten whenever the per-read rows are
     void* d_pair_rows = nullptr; size_t cap_pair_rows = 0; void* d_pair_heads = nullptr; size_t cap_pair_heads = 0; bool pair_ready = false; uint32_t pair_words = 0;
+    // the assigned rows and heads of fin_batch_assign (per read or per fragment: asg_n of them) and the bin of fin_batch_assign_bin made from them: buffers of their
+    // own, kept and only grown; asg_stream = the stream the assignment was put on, which its readers follow
+    void* d_asg_rows = nullptr; size_t cap_asg_rows = 0; void* d_asg_heads = nullptr; size_t cap_asg_heads = 0; bool asg_ready = false; uint32_t asg_words = 0, asg_colors = 0;
+    uint64_t asg_n = 0; hipStream_t asg_stream = nullptr;
+    void* d_bin_bits = nullptr; void* d_bin_ids = nullptr; void* d_bin_bsum = nullptr; void* d_bin_boff = nullptr;
+    size_t cap_bin_bits = 0, cap_bin_ids = 0, cap_bin_bsum = 0, cap_bin_boff = 0; uint64_t n_bin = 0; bool bin_ready = false;
     uint64_t text_bytes = 0;
     // kernel 4: the queue counters of the most recent finished run, copied to page-locked memory behind every run: the next run launches only
     // as many stream / walk rounds as that one needed, plus one (fin_launch_search_v4's `rounds`)
@@ -765,6 +772,7 @@ void fin_batch_free(fin_batch* b) {
     (void)hipFree(b->d_cstream); (void)hipFree(b->d_frec); (void)hipFree(b->d_seg); (void)hipFree(b->d_text); (void)hipFree(b->d_last_bits); (void)hipFree(b->d_blk_sum); (void)hipFree(b->d_blk_off); (void)hipFree(b->d_total);
     (void)hipFree(b->d_sgm_cnt); (void)hipFree(b->d_sgm_bsum); (void)hipFree(b->d_sgm_boff); (void)hipFree(b->d_sgm_offs); (void)hipFree(b->d_sgm);
     (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls); (void)hipFree(b->d_psa_rows); (void)hipFree(b->d_psa_heads); (void)hipFree(b->d_pair_rows); (void)hipFree(b->d_pair_heads);
+    (void)hipFree(b->d_asg_rows); (void)hipFree(b->d_asg_heads); (void)hipFree(b->d_bin_bits); (void)hipFree(b->d_bin_ids); (void)hipFree(b->d_bin_bsum); (void)hipFree(b->d_bin_boff);
     (void)hipFree(b->d_ovf_list); (void)hipFree(b->d_ovf_count); (void)hipFree(b->d_ovf_scratch); (void)hipFree(b->d_count);
     for (auto& r : b->runs) for (auto& e : r.e) (void)hipEventDestroy(e);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -888,7 +896,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     //  decoding, inside its timed region, search_fmin.hh:46-71 -- is the first kernel of every step, see fin_batch_run)
     b->n_chunks = n_chunks; b->max_read_len = max_len;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "upload");
-    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false;
+    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
     b->rounds_hint = 0; b->ctr_pending = false;   // (new reads: nothing is known about the rounds they need)
     b->text_reads_state = 0;
     return FIN_OK;
@@ -932,7 +940,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     b->dev.budget_mult = (uint32_t)optv(b->idx, O_epoch_budget_mult); b->dev.budget_add = (uint32_t)optv(b->idx, O_epoch_budget_add);
     b->dev.ovf_cap = (uint32_t)std::min<uint64_t>(b->cap_ovf_list / 4, 0xFFFFFFFFull);
     if (const int64_t forced = optv(b->idx, O_debug_ovf_cap)) b->dev.ovf_cap = (uint32_t)std::min<int64_t>(forced, (int64_t)b->dev.ovf_cap);   // (tests: a tiny list)
-    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false;
+    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
     b->dev.pp_seg = (uint32_t)optv(b->idx, O_debug_pp_seg);
     b->dev.pp_max_len = (uint32_t)std::min<uint64_t>(b->max_read_len, 0xFFFFFFFFull);
     b->dev.pp_park = (uint32_t)optv(b->idx, O_pp_park);
@@ -1068,7 +1076,7 @@ int fin_batch_set_pairs(fin_batch* b, const int32_t* pairs, char* err, size_t er
     HIPCHK(hipSetDevice(b->device));
     if (b->last_stream) HIPCHK(hipStreamSynchronize(b->last_stream));
     HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
-    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false;   // (the records of the last run say nothing about these pairs)
+    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;   // (the records of the last run say nothing about these pairs)
     return FIN_OK;
 }
 
@@ -1109,7 +1117,7 @@ int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32
     if (b->n_reads) HIPCHK(hipMemcpy(b->d_frec, recs, (size_t)b->n_reads * sizeof(FinFastRec), hipMemcpyHostToDevice));
     if (pairs && b->n_kmers) HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
     // last_frec / last_text_only stay as the run left them (a text-only batch still refuses its pairs); whatever was made from the old records goes
-    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false;
+    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
     b->rec_ready = false; b->rec_passthrough = false; b->rec_stream_pairs = 0;
     return FIN_OK;
 }
@@ -2224,6 +2232,178 @@ int fin_eqclasses_color_tally(const uint64_t* class_rows, const uint64_t* class_
             for (uint64_t m = row[w]; m; m &= m - 1) { last = 64u * w + (uint32_t)__builtin_ctzll(m); reads_with[last] += class_reads[i]; pc++; }
         if (pc == 1u) reads_only[last] += class_reads[i];
     }
+    return FIN_OK;
+}
+
+// ---- reads assigned to references from per-colour weights (fin_assign.hip) ------------------------------------------------
+static_assert(sizeof(fin_read_assign) == 8, "an assignment head is 8 bytes");
+struct fin_assign : fin_acc {
+    const fin_colors* colors = nullptr;
+    uint32_t n_colors = 0, words = 0;
+    void* d_cnt = nullptr;      // assigned uint64[n_colors] | sole uint64[n_colors] | counters uint64[4]: what a reset zeroes
+    void* d_w = nullptr;        // x double[64 words] | thr double[64 words], 0 behind n_colors
+    std::mutex mu;              // a set and an add are one step each
+};
+static size_t asg_cnt_bytes(const fin_assign* a) { return ((size_t)2 * a->n_colors + 4) * 8; }
+static uint64_t* asg_assigned(const fin_assign* a) { return (uint64_t*)a->d_cnt; }
+static uint64_t* asg_sole(const fin_assign* a) { return (uint64_t*)a->d_cnt + a->n_colors; }
+static uint64_t* asg_counters(const fin_assign* a) { return (uint64_t*)a->d_cnt + 2 * (size_t)a->n_colors; }
+static double* asg_x(const fin_assign* a) { return (double*)a->d_w; }
+static double* asg_thr(const fin_assign* a) { return (double*)a->d_w + 64u * (size_t)a->words; }
+
+static int asg_check(uint32_t n_colors, const double* weights, const double* thresholds, char* err, size_t errlen) {
+    int what = 0;
+    const uint32_t bad = fin_assign_first_bad(weights, thresholds, n_colors, &what);
+    if (bad == n_colors) return FIN_OK;
+    set_err(err, errlen, what == 0 ? "the weight of colour " + std::to_string(bad) + " is not a finite number >= 0"
+                                   : "the threshold of colour " + std::to_string(bad) + " is not a number in 0 .. 1");
+    return FIN_EINVAL;
+}
+// the new weights and thresholds, on `st` behind every add issued so far; returns when they are in place, so every later add finds them
+static int asg_upload(fin_assign* a, const double* weights, const double* thresholds, hipStream_t st, char* err, size_t errlen) {
+    const size_t pad = 64u * (size_t)a->words;
+    std::vector<double> h(2 * pad, 0.0);
+    for (uint32_t c = 0; c < a->n_colors; c++) { h[c] = weights[c]; h[pad + c] = thresholds[c]; }
+    if (const int orc = a->pend.order(st, err, errlen)) return orc;
+    HIPCHK(hipMemcpyAsync(a->d_w, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
+void fin_assign_free(fin_assign* a) {
+    if (!acc_free_open(a)) return;
+    (void)hipFree(a->d_cnt); (void)hipFree(a->d_w);
+    delete a;
+}
+
+int fin_assign_create(const fin_colors* c, const double* weights, const double* thresholds, fin_assign** out, char* err, size_t errlen) {
+    if (!c || !weights || !thresholds || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (const int crc = asg_check(c->n_colors, weights, thresholds, err, errlen)) return crc;
+    HIPCHK(hipSetDevice(c->device));   // (not acc_create_open: it goes beside a colour matrix, which has passed those checks)
+    fin_assign* a = acc_new<fin_assign>(c->idx, c->device, err, errlen);
+    if (!a) return FIN_ENOMEM;
+    a->colors = c; a->n_colors = c->n_colors; a->words = c->words;
+    if (const int arc = acc_alloc_zero(a, &a->d_cnt, asg_cnt_bytes(a), asg_cnt_bytes(a), "out of device memory (assignment counts)", fin_assign_free, err, errlen)) return arc;
+    if (hipMalloc(&a->d_w, (size_t)a->words * 1024u) != hipSuccess) { (void)hipGetLastError(); fin_assign_free(a); set_err(err, errlen, "out of device memory (assignment weights)"); return FIN_ENOMEM; }
+    if (const int urc = asg_upload(a, weights, thresholds, nullptr, err, errlen)) { fin_assign_free(a); return urc; }
+    *out = a;
+    return FIN_OK;
+}
+
+int fin_assign_reset(fin_assign* a, void* hip_stream) {
+    return acc_reset(a, hip_stream, a ? a->d_cnt : nullptr, a ? asg_cnt_bytes(a) : 0);
+}
+
+int fin_assign_set(fin_assign* a, const double* weights, const double* thresholds, void* hip_stream, char* err, size_t errlen) {
+    if (!a || !weights || !thresholds) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int crc = asg_check(a->n_colors, weights, thresholds, err, errlen)) return crc;
+    HIPCHK(hipSetDevice(a->device));
+    std::lock_guard<std::mutex> g(a->mu);
+    return asg_upload(a, weights, thresholds, (hipStream_t)hip_stream, err, errlen);
+}
+
+// the add proper, on `st`: behind the accumulator's last reset (a set has finished when it returns)
+static int asg_add_rows(fin_assign* a, const void* d_rows, uint64_t n_rows, void* d_out_rows, void* d_heads, hipStream_t st, char* err, size_t errlen) {
+    if (n_rows > 0xFFFFFFFFull) { set_err(err, errlen, "more than 2^32-1 rows in one add"); return FIN_ELIMIT; }
+    std::lock_guard<std::mutex> g(a->mu);
+    if (const int brc = a->pend.behind_reset(st, err, errlen)) return brc;
+    const int rc = fin_launch_assign_rows(d_rows, n_rows, a->words, a->n_colors, (uint32_t)optv(a->idx, O_assign_rpb), asg_x(a), asg_thr(a), d_out_rows, d_heads,
+                                          asg_assigned(a), asg_sole(a), asg_counters(a), st);
+    return acc_add_close(a, st, rc, "assignment kernel: ", err, errlen);
+}
+
+int fin_assign_rows(fin_assign* a, const void* rows_dev, uint64_t n_rows, void* out_rows_dev, void* heads_dev, void* hip_stream, char* err, size_t errlen) {
+    if (!a || (n_rows && !rows_dev)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(a->device));
+    return asg_add_rows(a, rows_dev, n_rows, out_rows_dev, heads_dev, (hipStream_t)hip_stream, err, errlen);
+}
+
+int fin_assign_download(fin_assign* a, uint64_t* assigned, uint64_t* sole, uint64_t counters[4], char* err, size_t errlen) {
+    if (!a) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(a, nullptr, nullptr, nullptr, err, errlen)) return orc;   // (the counts have no flags)
+    if (assigned) HIPCHK(hipMemcpy(assigned, asg_assigned(a), (size_t)a->n_colors * 8, hipMemcpyDeviceToHost));
+    if (sole) HIPCHK(hipMemcpy(sole, asg_sole(a), (size_t)a->n_colors * 8, hipMemcpyDeviceToHost));
+    if (counters) HIPCHK(hipMemcpy(counters, asg_counters(a), 32, hipMemcpyDeviceToHost));
+    return FIN_OK;
+}
+
+static int check_assign_unit(uint32_t unit, char* err, size_t errlen) {
+    if (unit > 2u) { set_err(err, errlen, "unit is 0 (reads), 1 (pairs, FIN_PAIR_ANY) or 2 (pairs, FIN_PAIR_BOTH)"); return FIN_EINVAL; }
+    return FIN_OK;
+}
+
+int fin_batch_assign(fin_batch* b, fin_assign* a, uint32_t permille, uint32_t unit, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !a) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int crc = check_assign_unit(unit, err, errlen)) return crc;
+    // always, as fin_batch_add_eqclasses does: the batch does not remember which matrix, threshold and mode its rows belong to
+    if (const int rc = unit == 0u ? fin_batch_pseudoalign(b, a->colors, permille, err, errlen)
+                                  : fin_batch_pseudoalign_paired(b, a->colors, permille, unit == 1u ? FIN_PAIR_ANY : FIN_PAIR_BOTH, err, errlen)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    b->asg_ready = false; b->bin_ready = false;
+    const uint64_t n = unit == 0u ? b->n_reads : b->n_reads / 2;
+    const void* const d_rows = unit == 0u ? b->d_psa_rows : b->d_pair_rows;
+    // (an earlier assignment's readers ran on its stream: a buffer that grows is freed behind them)
+    if (batch_grow(b, &b->d_asg_rows, b->cap_asg_rows, (size_t)n * a->words * 8 + 16, b->asg_stream) || batch_grow(b, &b->d_asg_heads, b->cap_asg_heads, (size_t)n * 8 + 16, b->asg_stream)) {
+        set_err(err, errlen, "out of device memory (assigned rows)"); return FIN_ENOMEM;
+    }
+    if (const int src = stream_behind(st, b->last_stream, err, errlen)) return src;   // the rows were made on the run's stream, behind the run: the add waits for them
+    if (b->asg_stream != st) if (const int src = stream_behind(st, b->asg_stream, err, errlen)) return src;   // ... and the buffers' earlier readers come first
+    if (const int rc = asg_add_rows(a, d_rows, n, b->d_asg_rows, b->d_asg_heads, st, err, errlen)) return rc;
+    b->asg_ready = true; b->asg_words = a->words; b->asg_colors = a->n_colors; b->asg_n = n; b->asg_stream = st;
+    return FIN_OK;
+}
+
+void* fin_batch_device_assign_rows(const fin_batch* b) { return b && b->asg_ready ? b->d_asg_rows : nullptr; }
+void* fin_batch_device_assign_heads(const fin_batch* b) { return b && b->asg_ready ? b->d_asg_heads : nullptr; }
+
+int fin_batch_download_assign(fin_batch* b, uint64_t* rows_out, fin_read_assign* heads_out, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->asg_ready) { set_err(err, errlen, "fin_batch_assign first"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->asg_stream;
+    if (b->asg_n && rows_out) HIPCHK(hipMemcpyAsync(rows_out, b->d_asg_rows, (size_t)b->asg_n * b->asg_words * 8, hipMemcpyDeviceToHost, st));
+    if (b->asg_n && heads_out) HIPCHK(hipMemcpyAsync(heads_out, b->d_asg_heads, (size_t)b->asg_n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
+int fin_batch_assign_bin(fin_batch* b, uint32_t colour, uint64_t* n_ids, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null batch"); return FIN_EINVAL; }
+    if (!b->asg_ready) { set_err(err, errlen, "fin_batch_assign first"); return FIN_EINVAL; }
+    if (colour >= b->asg_colors) { set_err(err, errlen, "colour " + std::to_string(colour) + " is not below n_colors = " + std::to_string(b->asg_colors)); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->asg_stream;
+    b->bin_ready = false;
+    const uint32_t n = (uint32_t)b->asg_n, nb = fin_rsm_blocks(n);
+    if (batch_grow(b, &b->d_bin_bits, b->cap_bin_bits, (size_t)((n + 63u) / 64u) * 8 + 8, st) || batch_grow(b, &b->d_bin_bsum, b->cap_bin_bsum, (size_t)nb * 4 + 4, st) ||
+        batch_grow(b, &b->d_bin_boff, b->cap_bin_boff, (size_t)nb * 8 + 8, st)) {
+        set_err(err, errlen, "out of device memory (bin tables)"); return FIN_ENOMEM;
+    }
+    uint64_t* const d_total = (uint64_t*)b->d_bin_boff + nb;   // (behind the block offsets)
+    int rc = fin_launch_assign_column(b->d_asg_rows, n, b->asg_words, colour, (uint64_t*)b->d_bin_bits, (uint32_t*)b->d_bin_bsum, (uint64_t*)b->d_bin_boff, d_total, st);
+    if (rc != 0) { set_err(err, errlen, std::string("bin kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (total > n) { set_err(err, errlen, "bin kernels: more rows in the bin than rows"); return FIN_ENODEV; }
+    if (batch_grow(b, &b->d_bin_ids, b->cap_bin_ids, (size_t)total * 4 + 16, st)) { set_err(err, errlen, "out of device memory (bin ids)"); return FIN_ENOMEM; }
+    rc = fin_launch_screen_ids((const uint64_t*)b->d_bin_bits, (const uint64_t*)b->d_bin_boff, n, (uint32_t*)b->d_bin_ids, st);
+    if (rc != 0) { set_err(err, errlen, std::string("bin kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    b->n_bin = total; b->bin_ready = true;
+    if (n_ids) *n_ids = total;
+    return FIN_OK;
+}
+
+void* fin_batch_device_bin_ids(const fin_batch* b) { return b && b->bin_ready ? b->d_bin_ids : nullptr; }
+
+int fin_batch_download_bin(fin_batch* b, uint32_t* ids_out, char* err, size_t errlen) {
+    if (!b || (b->bin_ready && b->n_bin && !ids_out)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->bin_ready) { set_err(err, errlen, "fin_batch_assign_bin first"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->asg_stream;
+    if (b->n_bin) HIPCHK(hipMemcpyAsync(ids_out, b->d_bin_ids, (size_t)b->n_bin * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return FIN_OK;
 }
 
@@ -3348,6 +3528,24 @@ int fin_search_batch_add_eqclasses_paired(const fin_index* idx, const char* base
     if (n_reads == 0) return FIN_OK;
     Product p; p.group = 2;   // (interleaved mates: no sub-batch splits a pair)
     p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* em, size_t elen) -> int { return fin_batch_add_eqclasses_paired(b, e, permille, mode, own(b), em, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
+}
+
+int fin_search_batch_assign(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_assign* a, uint32_t permille,
+                            uint32_t unit, uint64_t* rows_out, fin_read_assign* heads_out, char* err, size_t errlen) {
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, a && (n_reads < (unit ? 2u : 1u) || heads_out), a, OTHER_ACC, &device, err, errlen)) return orc;
+    if (const int crc = check_permille(permille, BAD_PERMILLE, err, errlen)) return crc;
+    if (const int crc = check_assign_unit(unit, err, errlen)) return crc;
+    if (unit) if (const int crc = check_even(n_reads, err, errlen)) return crc;
+    if (n_reads == 0) return FIN_OK;
+    // every sub-batch is pseudoaligned, assigned and counted on the device; its assigned rows (may be null) and heads land at its reads' or fragments' numbers
+    Product p; p.group = unit ? 2 : 1;   // (interleaved mates: no sub-batch splits a pair, every sub-batch begins at an even read)
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t&, char* e, size_t elen) -> int {
+        if (const int rc = fin_batch_assign(b, a, permille, unit, own(b), e, elen)) return rc;
+        const uint64_t at = unit ? s.lo / 2 : s.lo;
+        return fin_batch_download_assign(b, rows_out ? rows_out + at * a->words : nullptr, heads_out + at, e, elen);
+    };
     return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 

@@ -227,6 +227,17 @@ int fin_launch_ab_rowhash(const void* rows, uint64_t C, uint32_t W, void* h, hip
 int fin_launch_ab_slabs(const void* reads, uint64_t C, uint32_t* slabs, uint64_t* prefix, uint64_t* total, hipStream_t stream);
 int fin_launch_ab_resample(const void* h, const void* reads, const uint64_t* prefix, uint64_t C, uint64_t S, uint64_t seed, uint32_t b, void* counts, void* n_b,
                            hipStream_t stream);
+// fin_assign.hip -- rows assigned to colours from per-colour weights: rows uint64[n_rows * W] in HBM; x, thr: 64 W doubles each (0 behind n_colors);
+// out_rows uint64[n_rows * W] and heads {n_assigned, best} of 8 bytes per row (either may be null); assigned, sole: uint64[n_colors]; counters: 4 uint64 {rows,
+// unaligned, unassigned, multi} -- all three added to with integer atomics.  assign_rpb: option "assign_rpb"; fin_assign_rpb: the rows a block then takes.
+// fin_launch_assign_column: bit `color` of every assigned row as the bitmap, block sums, block offsets and total that fin_launch_screen_ids takes
+uint32_t fin_assign_rpb(uint64_t n_rows, uint32_t assign_rpb);
+// (fin_assign_host.cpp, no device) the first colour whose weight is negative, NaN or infinite (*what = 0) or whose threshold is outside [0, 1] or NaN (*what = 1); n_colors: none
+uint32_t fin_assign_first_bad(const double* weights, const double* thresholds, uint32_t n_colors, int* what);
+int fin_launch_assign_rows(const void* rows, uint64_t n_rows, uint32_t W, uint32_t n_colors, uint32_t assign_rpb, const double* x, const double* thr, void* out_rows,
+                           void* heads, uint64_t* assigned, uint64_t* sole, uint64_t* counters, hipStream_t stream);
+int fin_launch_assign_column(const void* arows, uint32_t n_rows, uint32_t W, uint32_t color, uint64_t* bits, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total,
+                             hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

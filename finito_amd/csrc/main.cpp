@@ -536,6 +536,16 @@ static const char* SEARCH_HELP =
     "                        `<TAB>boot_mean<TAB>boot_sd` -- mean and standard deviation (B - 1 in the divisor; 0 for B = 1) of the replicates' reads, as %.10g --,\n"
     "                        and a line `bootstraps<TAB>B<TAB>seed<TAB>S` follows the `loglik` line\n"
     "      --ab-seed S       the seed of --ab-bootstraps, an unsigned 64-bit number (default: 0)\n"
+    "      --assign-weights FILE  assign every read (with --paired 1: every fragment) to references, on the GPU, from per-reference weights: FILE is what\n"
+    "                        --abundance wrote in an earlier run over the same --color-refs, its `reads` column divided by the lengths of --ab-lengths where\n"
+    "                        given (lines `unaligned`, `iterations`, `loglik`, `bootstraps` and bootstrap columns are ignored). Colour c of a read's colour set\n"
+    "                        at --pseudo-permille is assigned iff weight[c] > 0 and weight[c] >= threshold[c] * (the sum of the set's weights).\n"
+    "                        Wants --color-refs and --assign and / or --assign-report; goes with --no-text 1, --pseudoalign, --eqclasses and --abundance.\n"
+    "      --assign-threshold X  X: one number from 0 to 1 for every colour (default: 0.5); `abundance`: the `share` column of the weights file\n"
+    "      --assign FILE     one line per read or fragment, in input order: `read<TAB>best<TAB>c1,c2,...` -- best = the colour of its set with the largest\n"
+    "                        weight, then the assigned colours; `-` where there is none\n"
+    "      --assign-report FILE  `colour<TAB>assigned<TAB>sole` per colour (reads the colour is assigned to; reads assigned to it alone), then\n"
+    "                        `unaligned<TAB>N`, `unassigned<TAB>N` (a colour set, none assigned) and `multi<TAB>N` (two or more assigned)\n"
     "      --paired arg      1: the query file holds INTERLEAVED mates, records 2f and 2f + 1 are fragment f (needs --color-refs). Chunks are cut after an\n"
     "                        even number of records; a file with an odd number of records is an error. --pseudoalign then writes one line per fragment,\n"
     "                        `fragment<TAB>k-mers<TAB>found<TAB>coloured<TAB>coloured_first<TAB>c1,c2,...` -- the k-mers of both mates together, coloured_first = the\n"
@@ -1023,6 +1033,63 @@ static void eqclasses_chunk(const FinimizerIndex& index, const char* bases, cons
     }
     if (fin_search_batch_add_eqclasses(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_eqc, g_psa_permille, err, sizeof err) != FIN_OK) throw runtime_error(err);
 }
+// --assign-weights FILE: one assignment accumulator for the whole run; every chunk's reads (or fragments) are pseudoaligned, assigned and counted on the first
+// device (fin_search_batch_assign); --assign's lines are written by the search stage in chunk order, --assign-report after the last chunk
+static fin_assign* g_asg = nullptr;
+static FILE* g_asg_file = nullptr;
+static uint64_t g_asg_read0 = 0;
+static vector<uint64_t> g_asg_rows; static vector<fin_read_assign> g_asg_heads; static string g_asg_text;
+static void assign_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
+    char err[512] = {0};
+    const uint32_t W = fin_colors_words(g_colors), unit = g_paired ? (g_pair_mode == FIN_PAIR_BOTH ? 2u : 1u) : 0u;
+    const uint64_t n = g_paired ? n_reads / 2 : n_reads;   // (the parser cuts chunks after an even number of records)
+    if (g_asg_file) g_asg_rows.resize((size_t)n * W + 1);
+    g_asg_heads.resize(n + 1);
+    if (fin_search_batch_assign(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_asg, g_psa_permille, unit, g_asg_file ? g_asg_rows.data() : nullptr, g_asg_heads.data(),
+                                err, sizeof err) != FIN_OK)
+        throw runtime_error(err);
+    if (!g_asg_file) return;
+    string& t = g_asg_text;
+    t.clear();
+    for (uint64_t r = 0; r < n; r++) {
+        t += to_string(g_asg_read0 + r); t += '\t';
+        if (g_asg_heads[r].best == FIN_NO_COLOR) t += '-'; else t += to_string(g_asg_heads[r].best);
+        t += '\t';
+        append_colors(t, g_asg_rows.data() + (size_t)r * W, W);
+        t += '\n';
+    }
+    if (!t.empty() && fwrite(t.data(), 1, t.size(), g_asg_file) != t.size()) throw runtime_error("Error writing the assignment file");
+    g_asg_read0 += n;
+}
+// the `reads` and `share` columns of a file --abundance wrote: a line per colour, `colour<TAB>reads<TAB>share[<TAB>...]`, colours ascending from 0
+static void assign_parse_weights(const string& path, size_t n_refs, vector<double>& reads, vector<double>& share) {
+    ifstream in(path);
+    if (!in.good()) throw runtime_error("--assign-weights: error opening file " + path);
+    string line;
+    size_t line_no = 0;
+    while (getline(in, line)) {
+        line_no++;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const string head = line.substr(0, line.find('\t'));
+        if (head == "unaligned" || head == "iterations" || head == "loglik" || head == "bootstraps") continue;
+        const auto bad = [&](const string& what) { return runtime_error("--assign-weights: " + path + " line " + to_string(line_no) + ": " + what); };
+        vector<string> f;
+        for (size_t at = 0;;) { const size_t e = line.find('\t', at); f.push_back(line.substr(at, e == string::npos ? e : e - at)); if (e == string::npos) break; at = e + 1; }
+        if (f.size() < 3) throw bad("wants `colour<TAB>reads<TAB>share`");
+        if (f[0] != to_string(reads.size())) throw bad("colour " + to_string(reads.size()) + " expected, got `" + f[0] + "`");
+        double v[2];
+        for (int q = 0; q < 2; q++) {
+            size_t used = 0;
+            try { v[q] = stod(f[1 + q], &used); } catch (...) { used = 0; }
+            if (f[1 + q].empty() || used != f[1 + q].size() || !(v[q] >= 0.0) || !std::isfinite(v[q])) throw bad(string(q ? "share" : "reads") + " is not a finite number >= 0");
+        }
+        if (v[1] > 1.0) throw bad("share is above 1");
+        reads.push_back(v[0]); share.push_back(v[1]);
+    }
+    if (reads.size() != n_refs)
+        throw runtime_error("--assign-weights: " + path + " has " + to_string(reads.size()) + " colours, --color-refs names " + to_string(n_refs) + " references");
+}
 static bool g_no_text = false;
 static uint64_t g_hits_total = 0;   // the accumulator's sum after the previous query file
 
@@ -1113,6 +1180,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_eqc) eqclasses_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_asg) assign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                     }
                     else {
                         // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
@@ -1136,6 +1204,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_eqc) eqclasses_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_asg) assign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                     }
                     if (g_strand_counts) {
                         c->positive_fwd = index.count_found_one_strand(c->bases.get(0), c->offsets.data(), n_reads);
@@ -1251,11 +1320,11 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance"))
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights"))
         throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
@@ -1265,14 +1334,19 @@ static int search_fmin(int argc, char** argv) {
     if (pair_both && !g_paired) throw runtime_error("--pair-both 1 is only legal together with --paired 1");
     g_pair_mode = pair_both ? FIN_PAIR_BOTH : FIN_PAIR_ANY;
     const bool eq_asked = o.has("eqclasses") || o.has("color-report") || o.has("abundance");
-    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
-    if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
+    const bool asg_asked = o.has("assign-weights");
+    if (asg_asked && !o.has("color-refs")) throw runtime_error("--assign-weights wants colours: --color-refs LIST");
+    if (asg_asked && !o.has("assign") && !o.has("assign-report")) throw runtime_error("--assign-weights wants a result: --assign FILE and / or --assign-report FILE");
+    for (const char* name : {"assign", "assign-report", "assign-threshold"})
+        if (o.has(name) && !asg_asked) throw runtime_error(string("--") + name + " is only legal together with --assign-weights");
+    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
+    if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked && !asg_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
     if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses, --color-report or --abundance");
     if (o.has("eqclasses-in") && !eq_asked) throw runtime_error("--eqclasses-in is only legal together with --eqclasses, --color-report or --abundance");
     if (o.has("eqclasses-unaligned") && !o.has("eqclasses")) throw runtime_error("--eqclasses-unaligned is only legal together with --eqclasses");
     if (o.has("ab-seed") && !o.has("ab-bootstraps")) throw runtime_error("--ab-seed is only legal together with --ab-bootstraps");
     for (const char* name : {"ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps"})
-        if (o.has(name) && !o.has("abundance")) throw runtime_error(string("--") + name + " is only legal together with --abundance");
+        if (o.has(name) && !o.has("abundance") && !(asg_asked && !strcmp(name, "ab-lengths"))) throw runtime_error(string("--") + name + " is only legal together with --abundance");
     if ((o.has("classify") || o.has("label-report")) && !(o.has("label-unitigs") && o.has("labels"))) throw runtime_error("--classify and --label-report want a labelling: --label-unitigs FASTA --labels FILE");
     if ((o.has("label-unitigs") || o.has("labels")) && !o.has("classify") && !o.has("label-report")) throw runtime_error("--label-unitigs and --labels are only legal together with --classify or --label-report");
     for (const char* name : {"class-min-found", "class-min-permille", "class-min-margin"})
@@ -1401,6 +1475,24 @@ static int search_fmin(int argc, char** argv) {
             if (!positive_number(v, false, ab_lengths[c])) throw runtime_error("--ab-lengths: line " + to_string(c + 1) + " (colour " + to_string(c) + ") is not a finite positive number");
         }
     }
+    // --assign-weights: the weights and thresholds, read before the index is loaded; a wrong colour count is an error before any search
+    const string asg_file = o.get("assign", ""), asg_report = o.get("assign-report", "");
+    vector<double> asg_w, asg_thr;
+    if (asg_asked) {
+        vector<double> share;
+        assign_parse_weights(o.get("assign-weights"), color_refs.size(), asg_w, share);
+        if (!ab_lengths.empty()) for (size_t c = 0; c < asg_w.size(); c++) asg_w[c] = asg_w[c] / ab_lengths[c];
+        const string tv = o.get("assign-threshold", "0.5");
+        if (tv == "abundance") asg_thr = share;
+        else {
+            double t = 0.0; size_t used = 0;
+            try { t = stod(tv, &used); } catch (...) { used = 0; }
+            if (tv.empty() || used != tv.size() || !(t >= 0.0 && t <= 1.0)) throw runtime_error("--assign-threshold wants a number from 0 to 1, or `abundance`");
+            asg_thr.assign(asg_w.size(), t);
+        }
+        if (!asg_file.empty()) check_writable(asg_file);
+        if (!asg_report.empty()) check_writable(asg_report);
+    }
     if (!ab_file.empty()) check_writable(ab_file);
     if (!eqc_file.empty()) check_writable(eqc_file);
     if (!crep_file.empty()) check_writable(crep_file);
@@ -1502,7 +1594,7 @@ static int search_fmin(int argc, char** argv) {
             if (!g_cls_file) throw runtime_error("Error writing to file: " + cls_file);
         }
     }
-    struct ColorOwner { ~ColorOwner() { if (g_psa_file) fclose(g_psa_file); g_psa_file = nullptr; fin_eqclasses_free(g_eqc); g_eqc = nullptr; fin_colors_free(g_colors); g_colors = nullptr; } } color_owner;
+    struct ColorOwner { ~ColorOwner() { if (g_psa_file) fclose(g_psa_file); g_psa_file = nullptr; if (g_asg_file) fclose(g_asg_file); g_asg_file = nullptr; fin_assign_free(g_asg); g_asg = nullptr; fin_eqclasses_free(g_eqc); g_eqc = nullptr; fin_colors_free(g_colors); g_colors = nullptr; } } color_owner;
     if (!color_refs.empty()) {
         for (auto& f : color_refs) check_readable(f);
         char err[512] = {0};
@@ -1528,6 +1620,14 @@ static int search_fmin(int argc, char** argv) {
         }
         if ((!eqc_file.empty() || !crep_file.empty() || !ab_file.empty()) && fin_eqclasses_create(g_colors, eq_max_classes, &g_eqc, err, sizeof err) != FIN_OK) throw runtime_error(err);
         if (g_eqc) for (auto& f : eqc_in) eqclasses_add_file(f);   // the earlier runs' classes, before the first chunk
+        if (asg_asked) {
+            if (fin_assign_create(g_colors, asg_w.data(), asg_thr.data(), &g_asg, err, sizeof err) != FIN_OK) throw runtime_error(string("--assign-weights: ") + err);
+            if (!asg_file.empty()) {
+                g_asg_file = fopen(asg_file.c_str(), "wb");
+                if (!g_asg_file) throw runtime_error("Error writing to file: " + asg_file);
+                g_asg_read0 = 0;
+            }
+        }
     }
     if (getenv("FINITO_TIMING"))
         cerr << "[timing] startup seconds: until load " << (t_l0 - micros_start) * 1e-6 << "  index load " << (t_l1 - t_l0) * 1e-6 << "  upload + tables (first HIP call) "
@@ -1574,6 +1674,24 @@ static int search_fmin(int argc, char** argv) {
         const bool bad = fflush(g_psa_file) != 0 || ferror(g_psa_file);
         fclose(g_psa_file); g_psa_file = nullptr;
         if (bad) throw runtime_error("Error writing to file: " + psa_file);
+    }
+    if (g_asg_file) {
+        const bool bad = fflush(g_asg_file) != 0 || ferror(g_asg_file);
+        fclose(g_asg_file); g_asg_file = nullptr;
+        if (bad) throw runtime_error("Error writing to file: " + asg_file);
+    }
+    if (g_asg && !asg_report.empty()) {   // the counts of the run's assignment, kept on the device until now
+        char err[512] = {0};
+        const uint32_t nc = fin_colors_n_colors(g_colors);
+        vector<uint64_t> assigned(nc), sole(nc);
+        uint64_t counters[4] = {0, 0, 0, 0};
+        if (fin_assign_download(g_asg, assigned.data(), sole.data(), counters, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        string text;
+        for (uint32_t c = 0; c < nc; c++) { text += to_string(c); text += '\t'; text += to_string(assigned[c]); text += '\t'; text += to_string(sole[c]); text += '\n'; }
+        text += "unaligned\t" + to_string(counters[1]) + "\nunassigned\t" + to_string(counters[2]) + "\nmulti\t" + to_string(counters[3]) + "\n";
+        ofstream cf(asg_report, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + asg_report);
     }
     if (g_eqc && !ab_file.empty()) {   // the abundances, estimated on the device from the run's classes: the rows stay there
         char err[512] = {0};

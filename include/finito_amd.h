@@ -1059,6 +1059,58 @@ int fin_classes_bootstrap(const uint64_t* class_rows, const uint64_t* class_read
                           double tol, uint32_t n_boot, uint64_t seed, double* alpha_out, fin_abundance_info* info, double* boot_alpha_out, uint64_t* boot_reads_out,
                           uint32_t* boot_iters_out, uint8_t* boot_converged_out, int n_threads);
 
+/* ---- READS ASSIGNED TO REFERENCES from the abundances, on the device ----
+ * The way back from alpha to the reads: which colours of an ambiguous row {A, B} the read belongs to, now that A is known to be forty times as abundant as B
+ * (mGEMS behind Themisto and mSWEEP; kallisto's posterior turned into a read bin).  The rows stay in HBM.
+ *   INPUTS      rows R_r, r < n, uint64[n][W], W = ceil(n_colors / 64); weights x[c], one per colour, finite doubles >= 0 -- usually alpha[c] / len[c]; thresholds
+ *               thr[c], one per colour, finite doubles in [0, 1].
+ *   ARITHMETIC  IEEE double in a fixed order.  s_w = the sum of x[c] over the set bits of word w in ascending bit order, starting from 0.0; s_w = 0.0 for
+ *               W <= w < wp2, the power of two at or above W.  d folds the vector s in halves until one value is left: v = v[:h] + v[h:], h = len(v) / 2.  This
+ *               is the d_j of the EM's first pass (fin_abundance.hip), bit for bit: a posterior x[c] / d taken here is the one the EM used.
+ *   ASSIGNED    colour c is assigned to row r iff bit c is set in R_r, x[c] > 0, d > 0 and x[c] >= thr[c] * d: one multiply and one compare, no division and
+ *               nothing that can contract into a fused multiply-add.
+ *   BEST        the colour of the row with the largest x[c], the smaller colour on a tie; FIN_NO_COLOR unless d > 0.
+ *   PER ROW     the assigned row A_r, a subset of R_r, uint64[W]; the head fin_read_assign {n_assigned, best}.
+ *   PER ACCUMULATOR, exact integers that depend on no order: assigned[c] = the rows with c in A_r; sole[c] = the rows whose A_r is {c}; counters {rows,
+ *               unaligned (all-zero R_r), unassigned (non-empty R_r, empty A_r), multi (n_assigned >= 2)}.
+ *   IDENTITIES  rows = unaligned + unassigned + #(n_assigned >= 1); the sum of assigned[c] = the sum of n_assigned; with every thr = 0 and every x > 0, A_r = R_r.
+ * FIN_EINVAL for a weight that is negative, NaN or infinite and for a threshold outside [0, 1] or NaN; the message names the colour.  Bits at or above n_colors:
+ * the device masks them, the host twin refuses them with FIN_EINVAL as its siblings do.
+ * The accumulator lives beside a colour matrix (free it before the colours).  fin_assign_set replaces weights and thresholds on hip_stream, ordered behind the
+ * adds issued so far, and every later add is ordered behind it; fin_assign_reset zeroes the counts and leaves the weights.  fin_assign_rows takes any rows in
+ * HBM (n_rows < 2^32; 0 is legal), writes out_rows_dev uint64[n_rows * W] and heads_dev fin_read_assign[n_rows] where they are not NULL, and does not sync.
+ * fin_assign_download waits for the adds; each of its three outputs may be NULL. */
+#define FIN_NO_COLOR 0xFFFFFFFFu
+typedef struct fin_read_assign { uint32_t n_assigned, best; } fin_read_assign;   /* 8 bytes */
+typedef struct fin_assign fin_assign;
+int fin_assign_create(const fin_colors* c, const double* weights, const double* thresholds, fin_assign** out, char* err, size_t errlen);
+int fin_assign_reset(fin_assign* a, void* hip_stream);
+void fin_assign_free(fin_assign* a);
+int fin_assign_set(fin_assign* a, const double* weights, const double* thresholds, void* hip_stream, char* err, size_t errlen);
+int fin_assign_rows(fin_assign* a, const void* rows_dev, uint64_t n_rows, void* out_rows_dev /* may be NULL */, void* heads_dev /* may be NULL */, void* hip_stream,
+                    char* err, size_t errlen);
+int fin_assign_download(fin_assign* a, uint64_t* assigned /* n_colors */, uint64_t* sole /* n_colors */, uint64_t counters[4], char* err, size_t errlen);
+/* the batch's most recent run: pseudoaligned at `permille` -- always, as fin_batch_add_eqclasses does, with that call's errors --, per read (unit 0) or per
+ * fragment (unit 1: FIN_PAIR_ANY, unit 2: FIN_PAIR_BOTH; an odd n_reads is then FIN_EINVAL), and the rows assigned and counted on hip_stream (it waits for the
+ * rows through an event when that is not the run's stream).  The assigned rows and heads go into buffers of the batch's own, kept and only grown; the pseudo
+ * rows survive.  F below = the reads (unit 0) or the fragments of that call */
+int fin_batch_assign(fin_batch* b, fin_assign* a, uint32_t permille, uint32_t unit, void* hip_stream, char* err, size_t errlen);
+void* fin_batch_device_assign_rows(const fin_batch* b);    /* uint64[F * W] in HBM; NULL before fin_batch_assign */
+void* fin_batch_device_assign_heads(const fin_batch* b);   /* fin_read_assign[F] in HBM; NULL before fin_batch_assign */
+int fin_batch_download_assign(fin_batch* b, uint64_t* rows_out, fin_read_assign* heads_out, char* err, size_t errlen);   /* either pointer may be NULL; waits */
+/* the BIN of a colour: the ascending numbers (uint32) of the reads or fragments of the last fin_batch_assign that have `colour` assigned, in HBM -- one ballot per
+ * word of a bitmap, then the screen's compaction.  colour >= n_colors is FIN_EINVAL.  Waits for the count */
+int fin_batch_assign_bin(fin_batch* b, uint32_t colour, uint64_t* n_ids, char* err, size_t errlen);
+void* fin_batch_device_bin_ids(const fin_batch* b);        /* uint32[n_ids] in HBM; NULL before fin_batch_assign_bin */
+int fin_batch_download_bin(fin_batch* b, uint32_t* ids_out, char* err, size_t errlen);
+/* a read set from host buffers through the pipeline: every sub-batch is pseudoaligned, assigned and counted on the device; the assigned rows (rows_out may be
+ * NULL) and heads land at the reads' or fragments' numbers.  No sub-batch cuts a pair */
+int fin_search_batch_assign(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_assign* a, uint32_t permille,
+                            uint32_t unit, uint64_t* rows_out, fin_read_assign* heads_out, char* err, size_t errlen);
+/* host twin, no device: the definition in the stated order over rows in host memory; the result does not depend on n_threads.  Every output may be NULL */
+int fin_rows_assign(const uint64_t* rows, uint64_t n_rows, uint32_t n_colors, const double* weights, const double* thresholds, uint64_t* out_rows,
+                    fin_read_assign* heads, uint64_t* assigned, uint64_t* sole, uint64_t counters[4], int n_threads);
+
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
  * k-mer is in no unitig), 1 a verified claim, 2 an unverified one (| 8: the exact side table has the k-mer, g is its answer), | 4 the text at [g-k+1, g] spells
