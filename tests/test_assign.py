@@ -1,13 +1,15 @@
 """Reads assigned to references on the device (include/finito_amd.h: fin_assign_rows, fin_batch_assign, fin_batch_assign_bin, fin_search_batch_assign; DESIGN.md
 4.21) against the host twin fin_rows_assign and the numpy model of tests/test_assign_host.py.  All expectations are exact: rows, heads, assigned, sole and
-counters are compared byte for byte.  Option "assign_rpb" is 64 in the row cases, so several blocks flush into the same colours and the last block is partial."""
+counters are compared byte for byte.  Option "assign_rpb" is 64 in the row cases, so several blocks flush into the same colours and the last block is partial.
+The bins (fin_assign_column_kernel) are held to np.flatnonzero over the unpacked column of the rows Batch.assign returns: at 130 colours (W = 3) for colours in
+every word and at bit 63, at 1 .. 1000 reads, and once past 262 144 reads, where the scan of the blocks' counts leaves its first level."""
 import numpy as np
 import pytest
 import torch
 
 import finito_amd as fa
 from tests.test_assign_host import (N_COLORS, assert_identities, assert_same, dyadic_weights, model, random_rows, random_weights, unpack_bool)
-from tests.test_colors_host import words_of
+from tests.test_colors_host import pack_members, words_of
 from tests.test_eqclasses import on_device, small   # noqa: F401 (the fixture: the suite's small index)
 from tests.test_streams import Delay
 from tests.util import cut_unitigs, random_genome, sample_reads
@@ -257,3 +259,73 @@ def test_add_reads_in_sub_batches(three):
         asg.add_reads(reads[:11], pairs=True)
     assert e.value.code == fa.FIN_EINVAL and "odd" in str(e.value)
     asg.close()
+
+
+# ---- bins of a colour in every word, bit 63, partial waves and blocks, more than 1024 blocks of 256 rows ----------------------------------------------------
+BIN_COLORS = (0, 63, 64, 127, 128, 129)   # the first and last bit of words 0 and 1, the first bit of word 2 and the top colour
+NOBODY = 77                               # a colour no unitig has: an empty bin
+
+
+@pytest.fixture(scope="module")
+def coloured(small):
+    """the small index with 130 colours drawn at random over its unitigs -- words 0, 1 and 2 all populated, the colours of BIN_COLORS on many unitigs, NOBODY on
+    none --, an assigner that keeps every colour of a row (all weights 1, thresholds 0), and the index's text to cut reads from"""
+    p, _, _ = small
+    rng = np.random.default_rng(3950)
+    n_colors = 130
+    member = rng.random((p.n_unitigs, n_colors)) < 0.03
+    member[np.arange(p.n_unitigs), np.array(BIN_COLORS)[rng.integers(0, len(BIN_COLORS), p.n_unitigs)]] |= rng.random(p.n_unitigs) < 0.7
+    member[:, NOBODY] = False
+    bits = pack_members(member)
+    assert bits.shape[1] == 3 and bits.any(axis=0).all() and all(member[:, c].sum() >= 10 for c in BIN_COLORS) and not member.any(axis=1).all()
+    col = p.colors(n_colors, bits)
+    asg = col.assigner(np.ones(n_colors), 0.0)
+    text = np.frombuffer(b"ACGT", dtype=np.uint8)[p.export(fa.X_CONCAT)]
+    yield p, col, asg, text, p.export(fa.X_ENDS).astype(np.int64), n_colors
+    asg.close(); col.close()
+
+
+def cut_reads(rng, text, ends, k, n):
+    """n reads of k bases, each cut from inside one unitig (nk = 1), as (bases, offsets)"""
+    starts = np.concatenate([[0], ends[:-1]])
+    u = rng.integers(0, len(ends), n)
+    a = starts[u] + (rng.random(n) * (ends[u] - starts[u] - k + 1)).astype(np.int64)
+    bases = np.ascontiguousarray(text[a[:, None] + np.arange(k)[None, :]]).reshape(-1)
+    return bases, (np.arange(n + 1, dtype=np.uint64) * np.uint64(k))
+
+
+def check_bins(b, asg, n_colors, colours, what):
+    """Batch.assign_bin against the rows Batch.assign returns: np.flatnonzero over the unpacked column; returns the rows"""
+    rows, _ = b.assign(asg.reset())
+    M = unpack_bool(rows, n_colors)
+    for c in colours:
+        ids = b.assign_bin(c)
+        want = np.flatnonzero(M[:, c])
+        assert ids.dtype == np.uint32 and np.array_equal(ids, want), "%s: bin of colour %d: %d ids, %d rows have the colour" % (what, c, len(ids), len(want))
+    return rows, M
+
+
+@pytest.mark.parametrize("n_reads", [1, 63, 64, 65, 255, 256, 257, 1000])
+def test_bins_of_colours_in_every_word(coloured, n_reads):
+    """fin_assign_column_kernel at W = 3: the word of the colour (c >> 6), bit 63 of a word, a last wave and a last block that are partial"""
+    p, col, asg, text, ends, n_colors = coloured
+    rng = np.random.default_rng(3960 + n_reads)
+    b = p.batch(cut_reads(rng, text, ends, p.k, n_reads)); b.run(fa.FIN_MERGED)
+    rows, M = check_bins(b, asg, n_colors, BIN_COLORS + (NOBODY,), "%d reads" % n_reads)
+    assert rows.shape == (n_reads, 3) and len(b.assign_bin(NOBODY)) == 0
+    if n_reads == 1000:
+        assert all(M[:, c].sum() >= 20 for c in BIN_COLORS) and rows.any(axis=0).all() and not M.any(axis=1).all()
+        assert M[-1].any() or M[-2].any() or M[-3].any()   # the partial block's rows are not all empty
+    b.close()
+
+
+def test_bins_past_one_block_a_scan_thread(coloured):
+    """more than 262 144 reads, that is more than 1024 blocks of 256 rows: a thread of fin_blk_scan_kernel carries two blocks, and the last block is partial"""
+    p, col, asg, text, ends, n_colors = coloured
+    n_reads = 262_144 + 256 + 57
+    b = p.batch(cut_reads(np.random.default_rng(3970), text, ends, p.k, n_reads)); b.run(fa.FIN_MERGED)
+    rows, M = check_bins(b, asg, n_colors, (0, 128), "%d reads" % n_reads)
+    for c in (0, 128):   # rows on both sides of the first level's end and in the last, partial block
+        have = np.flatnonzero(M[:, c])
+        assert (have < 262_144).sum() > 1000 and (have >= 262_144).any() and (have >= 262_144 + 256).any()
+    b.close()

@@ -9,6 +9,9 @@ The reference is always tests/test_records.py::brute_expand -- the record's mean
 searched reads; each consumer's expectation is plain numpy over those pairs (np.bincount, np.unique, the segment definition of tests/test_segments_host.py,
 oracle.oracle.format_pairs).  Nothing is expected from fin_expand_records, fin_records_* or a device output, and every comparison is exact equality.
 
+The base pileup (fin_pileup_add_kernel's kind-1 branch) is a consumer of the same records, but it trusts them where its definition reads the text: it needs reads
+spelled to agree with their records and faces these cases, through `inject`, in tests/test_pileup_records.py.
+
 Out of reach from here: the pre-pass's own pair writer for a finished read (fin_prepass.hip; its branch for more than four positions).  It is the producer, not a
 consumer: hand-made records do not pass through it, and it cannot run while FIN_FAST_MAXE is 4."""
 import numpy as np

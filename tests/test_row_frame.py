@@ -3,7 +3,8 @@
 A consumer of a step's results is a lane per read: the read's kind decides what the lane loads (kind 1: the record alone; kind 2: nothing; kind 0, and every read
 where the step left no records: the pair range from out_offs), then the wave takes its lanes' searched reads one after the other and scans each a row of 64 slots
 at a time, most of them with the next row loaded a row ahead.  Hits, cover, depth, segments, read summaries and the screen, classes and the tally, colouring,
-pseudoalignment, its paired form and the record gather all repeat that frame; this file pins it where it can go wrong, at the smallest shapes:
+pseudoalignment, its paired form, the record gather and the base pileup all repeat that frame; this file pins it where it can go wrong, at the smallest shapes
+(the pileup reads the reads themselves, so it takes this case with spelled reads, and ten searched reads more, in tests/test_pileup_records.py):
 
   - 200 reads: three full waves and one of eight lanes (lanes at and beyond n_reads, a block's last wave);
   - nk cycling through 1, 63, 64, 65, 127, 128, 129, 193: less than a row, exactly one, a second row of one slot, a last row that is empty, full, or one slot;
