@@ -317,6 +317,8 @@ def lib():
         L.fin_batch_download_bin.argtypes = [vp, u32p, cp, C.c_size_t]
         L.fin_search_batch_assign.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, u64p, vp, cp, C.c_size_t]
         L.fin_rows_assign.argtypes = [u64p, u64, u32, f64p, f64p, u64p, vp, u64p, u64p, u64p, C.c_int]
+        L.fin_colors_coverage.argtypes = [vp, vp, vp, u32, vp, vp, cp, C.c_size_t]
+        L.fin_unitig_color_coverage.argtypes = [u64p, u64, u32, u64p, u64p, vp, vp, vp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -819,7 +821,8 @@ class Colors(_Accumulator):
             raise FinitoError(FIN_ELIMIT, "colors: n_colors is 1 .. 4096")
         self.n_colors = int(n_colors)
         self.words = (self.n_colors + 63) // 64
-        self._create("fin_colors_create", index.h, int(device), self.n_colors)
+        self.device = int(device)
+        self._create("fin_colors_create", index.h, self.device, self.n_colors)
 
     def upload(self, bits):
         """replace the matrix: uint64[n_unitigs, W]; a set bit at or above n_colors is refused (fin_colors_upload)"""
@@ -866,6 +869,18 @@ class Colors(_Accumulator):
         """an accumulator that assigns reads to references beside this matrix (Assign): weights one per colour, usually Abundance.weights(); thresholds one per
         colour or a scalar for all -- thresholds=ab.theta is the mGEMS rule"""
         return Assign(self, weights, thresholds)
+
+    def coverage(self, cover=None, depth=None, min_depth=1):
+        """the per-unitig coverage numbers projected through this matrix, on the device (fin_colors_coverage): a ColorCoverage.  cover: a Cover,
+        depth: a Depth of the same index and device, either may be None (its sums are 0; both None: kmers / kmers_only alone, the references' sizes in the graph);
+        n_at_least of the depth is counted against min_depth.  Waits for the adds to all three; changes none of them"""
+        if not 0 <= int(min_depth) <= 0xFFFFFFFF:
+            raise FinitoError(FIN_EINVAL, "Colors.coverage: min_depth is an unsigned 32-bit number")
+        out = np.zeros(self.n_colors + 1, dtype=COLOR_COVERAGE_DTYPE)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_coverage(self.h, cover.h if cover is not None else None, depth.h if depth is not None else None, int(min_depth),
+                                          out.ctypes.data_as(C.c_void_p), out[self.n_colors:].ctypes.data_as(C.c_void_p), err, 512), err)
+        return ColorCoverage(out[: self.n_colors], out[self.n_colors])
 
 
 class EqClasses(_Accumulator):
@@ -1002,6 +1017,41 @@ class EqClasses(_Accumulator):
         err = C.create_string_buffer(512)
         _check(self.L.fin_eqclasses_stats(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), err, 512), err)
         return [int(v) for v in out]
+
+
+class ColorCoverage:
+    """breadth and depth of coverage per reference (Colors.coverage, unitig_color_coverage): the eight uint64[n_colors] arrays kmers, kmers_only, covered,
+    covered_only, depth_sum, depth_sum_only, solid, solid_only -- the unitigs' k-mers, distinct found k-mers, summed depth and positions at or above min_depth,
+    summed over the unitigs that carry colour c and (_only) over those that carry c alone -- and `uncolored`, a dict of the four sums over the unitigs without a
+    colour.  table: the COLOR_COVERAGE_DTYPE array they are views of.  The ratios are derived here, in float64; the library stays in integers"""
+    FIELDS = ("kmers", "kmers_only", "covered", "covered_only", "depth_sum", "depth_sum_only", "solid", "solid_only")
+
+    def __init__(self, table, uncolored):
+        self.table = table
+        for f in self.FIELDS:
+            setattr(self, f, table[f])
+        self.uncolored = {f: int(uncolored[f]) for f in ("kmers", "covered", "depth_sum", "solid")}
+
+    @staticmethod
+    def _ratio(num, den):
+        out = np.full(len(num), np.nan)
+        np.divide(num.astype(np.float64), den.astype(np.float64), out=out, where=den != 0)
+        return out
+
+    @property
+    def breadth(self):
+        """covered / kmers: the share of the reference's k-mers that were found; nan for a reference without k-mers in the graph"""
+        return self._ratio(self.covered, self.kmers)
+
+    @property
+    def breadth_only(self):
+        """covered_only / kmers_only: the same over the k-mers of unitigs that carry this colour alone; nan where there are none"""
+        return self._ratio(self.covered_only, self.kmers_only)
+
+    @property
+    def mean_depth(self):
+        """depth_sum / covered: the mean depth of the found k-mers; nan where none was found"""
+        return self._ratio(self.depth_sum, self.covered)
 
 
 def _assign_args(what, n_colors, weights, thresholds):
@@ -1715,6 +1765,18 @@ class FinimizerIndex:
         """a zeroed per-position depth accumulator beside the replica on `device` (Depth)"""
         return Depth(self, device)
 
+    def color_coverage(self, reads, colors, min_depth=1, strands=FIN_MERGED):
+        """breadth and depth of a read set per reference of `colors` (a Colors of this index): a fresh Cover and Depth beside the colours, the reads searched
+        into each, then Colors.coverage -- a ColorCoverage"""
+        cov, dep = Cover(self, colors.device), Depth(self, colors.device)
+        try:
+            reads = flatten(reads)
+            cov.add_reads(reads, strands)
+            dep.add_reads(reads, strands)
+            return colors.coverage(cov, dep, min_depth)
+        finally:
+            cov.close(); dep.close()
+
     def pileup(self, max_mismatch=8, device=0):
         """a zeroed base pileup beside the replica on `device` (Pileup)"""
         return Pileup(self, device, max_mismatch)
@@ -1781,6 +1843,7 @@ FIN_MAX_COLORS = 4096
 READ_ASSIGN_DTYPE = np.dtype([("n_assigned", np.uint32), ("best", np.uint32)])   # fin_read_assign
 FIN_NO_COLOR = 0xFFFFFFFF
 DEPTH_STAT_DTYPE = np.dtype([("sum", np.uint64), ("max", np.uint32), ("n_at_least", np.uint32)])            # fin_depth_stat
+COLOR_COVERAGE_DTYPE = np.dtype([(f, np.uint64) for f in ColorCoverage.FIELDS])   # fin_color_coverage
 VARIANT_DTYPE = np.dtype([("u", np.uint32), ("off", np.uint32), ("cover", np.uint32), ("ref", np.uint32), ("alt", np.uint32, (4,))])   # fin_variant
 
 
@@ -2133,6 +2196,36 @@ def rows_assign(rows, n_colors, weights, thresholds=0.5, n_threads=0):
     if rc != 0:
         raise FinitoError(rc, "fin_rows_assign: a row with a bit at or above n_colors")
     return out[:n], heads[:n], assigned, sole, counters
+
+
+def unitig_color_coverage(bits, n_colors, nk, covered=None, stats=None, n_threads=0):
+    """host: the ColorCoverage of a colour matrix uint64[n_unitigs, W] over per-unitig numbers -- nk uint64[n_unitigs], covered uint64[n_unitigs] or None,
+    stats DEPTH_STAT_DTYPE[n_unitigs] or None (fin_unitig_color_coverage) -- the CPU statement of Colors.coverage; the result does not depend on n_threads"""
+    nc = int(n_colors)
+    if not 1 <= nc <= FIN_MAX_COLORS:
+        raise FinitoError(FIN_ELIMIT, "unitig_color_coverage: n_colors is 1 .. 4096")
+    W = (nc + 63) // 64
+    a = np.ascontiguousarray(bits, dtype=np.uint64).reshape(-1, W)
+    n = len(a)
+    u64p = C.POINTER(C.c_uint64)
+
+    def per_unitig(what, v, dtype):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, dtype=dtype)
+        if v.shape != (n,):
+            raise FinitoError(FIN_EINVAL, "unitig_color_coverage: %s has shape %s, the matrix has %d unitigs" % (what, v.shape, n))
+        return v
+    nk_, cov_, st_ = per_unitig("nk", nk, np.uint64), per_unitig("covered", covered, np.uint64), per_unitig("stats", stats, DEPTH_STAT_DTYPE)
+    if nk_ is None:
+        raise FinitoError(FIN_EINVAL, "unitig_color_coverage: nk is needed")
+    out = np.zeros(nc + 1, dtype=COLOR_COVERAGE_DTYPE)
+    rc = lib().fin_unitig_color_coverage(a.ctypes.data_as(u64p), n, nc, nk_.ctypes.data_as(u64p), cov_.ctypes.data_as(u64p) if cov_ is not None else None,
+                                         st_.ctypes.data_as(C.c_void_p) if st_ is not None else None, out.ctypes.data_as(C.c_void_p),
+                                         out[nc:].ctypes.data_as(C.c_void_p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_unitig_color_coverage: a row with a bit at or above n_colors")
+    return ColorCoverage(out[:nc], out[nc])
 
 
 def _u64(what, name, v):

@@ -96,7 +96,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_colcov_chunk, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -135,6 +135,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"ec_combine", 1, 0, 1},                       // fin_eqclasses' count pass: 1 = a wave's adds combined over its distinct slots, one atomic each; 0 = one atomic per row (tools/ab_eqclasses.py measures both)
     {"ab_chunk", 0, 0, 1ll << 26},                 // fin_eqclasses_abundance's column pass: classes per chunk, rounded up to a multiple of 64 (fin_abundance.hip); 0 = auto: 256, more once that would make over 1024 chunks (which also bounds what a value can ask for).  The order of the column sums is a function of it, so two estimates compare bit for bit only under one value; tests set 64 so that small cases cross chunk seams
     {"assign_rpb", 0, 0, 1ll << 26},               // fin_assign_rows: rows per block of fin_assign_rows_kernel (fin_assign.hip); 0 = auto: 1024, more once that would make over 2048 blocks; never so few that there would be over 2^20 blocks.  The results do not depend on it; tests set 64 so that small cases cross block seams
+    {"colcov_chunk", 0, 0, 1ll << 26},             // fin_colors_coverage: unitigs per chunk of fin_colcov_column_kernel (fin_colcov.hip), rounded up to a multiple of 64; 0 = auto: 1024, more once that would make over 8192 waves; never so few that there would be over 2^20 chunks.  The results do not depend on it; tests set 64 so that small cases cross chunk seams
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -1766,13 +1767,16 @@ static_assert(sizeof(fin_read_pseudo) == 16, "a pseudoalignment head is 16 bytes
 struct fin_colors : fin_acc {
     uint64_t n_unitigs = 0; uint32_t n_colors = 0, words = 0;
     void* d_bits = nullptr;     // uint64[n_unitigs * words], then the flag word (fin_launch_colors_add)
+    // fin_colors_coverage's: made by the first call, kept
+    void* d_ccv = nullptr;      // uint64[(n_colors + 1) * 8]: the table and the uncoloured entry; then the class byte of every unitig
+    std::mutex ccv_mu;          // one projection at a time goes through d_ccv
 };
 static size_t colors_bytes(const fin_colors* c) { return (size_t)c->n_unitigs * c->words * 8; }
 static uint32_t* colors_flags(const fin_colors* c) { return (uint32_t*)((char*)c->d_bits + colors_bytes(c)); }
 
 void fin_colors_free(fin_colors* c) {
     if (!acc_free_open(c)) return;
-    (void)hipFree(c->d_bits);
+    (void)hipFree(c->d_bits); (void)hipFree(c->d_ccv);
     delete c;
 }
 
@@ -2774,6 +2778,13 @@ int fin_batch_add_cover(fin_batch* b, fin_cover* c, void* hip_stream, char* err,
     return acc_add_close(c, st, rc, "cover kernel: ", err, errlen);
 }
 
+// covered[] of the bitmap as it stands, into c->d_covered on the null stream (with count_mu held; n_unitigs > 0): fin_cover_download's and fin_colors_coverage's
+static int cover_count(fin_cover* c, char* err, size_t errlen) {
+    const int rc = fin_launch_cover_count(c->d_bits, c->d_ends, (uint32_t)c->n_unitigs, c->total_len, c->d_covered, nullptr);
+    if (rc != 0) { set_err(err, errlen, std::string("cover count kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    return FIN_OK;
+}
+
 int fin_cover_download(fin_cover* c, uint64_t* bits_out, uint64_t* covered_out, uint64_t* total_covered, char* err, size_t errlen) {
     if (!c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     if (const int orc = acc_download_open(c, cover_flags(c), "a step whose overflow list overran was added: it has no results, nothing of it was set (reset the accumulator)",
@@ -2784,8 +2795,7 @@ int fin_cover_download(fin_cover* c, uint64_t* bits_out, uint64_t* covered_out, 
         uint64_t* const dst = dst_or_tmp(covered_out, tmp, (size_t)c->n_unitigs);
         if (c->n_unitigs) {
             std::lock_guard<std::mutex> g(c->count_mu);
-            const int rc = fin_launch_cover_count(c->d_bits, c->d_ends, (uint32_t)c->n_unitigs, c->total_len, c->d_covered, nullptr);
-            if (rc != 0) { set_err(err, errlen, std::string("cover count kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+            if (const int rc = cover_count(c, err, errlen)) return rc;
             HIPCHK(hipMemcpy(dst, c->d_covered, c->n_unitigs * 8, hipMemcpyDeviceToHost));   // (the null stream: behind the kernel)
         }
         if (total_covered) *total_covered = sum_of(dst, (size_t)c->n_unitigs, [](uint64_t v) { return v; });
@@ -2843,19 +2853,14 @@ int fin_batch_add_depth(fin_batch* b, fin_depth* d, void* hip_stream, char* err,
     return acc_add_close(d, st, rc, "depth kernel: ", err, errlen);
 }
 
-int fin_depth_download(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, fin_depth_stat* stats_out, uint64_t* total, char* err, size_t errlen) {
-    if (!d) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
-    if (const int orc = acc_download_open(d, depth_flags(d), "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)",
-                                          "a pair with a unitig number or a position outside the index was met (not counted)", err, errlen)) return orc;
-    if (total) *total = 0;
-    const bool want_stats = stats_out || total;
-    if (!depth_out && !want_stats) return FIN_OK;
-    if (d->total_len == 0 || d->n_unitigs == 0) return FIN_OK;
+// the prefix sum of the difference array as it stands, a chunk at a time through the staging buffer on the null stream (with scan_mu held; total_len and
+// n_unitigs > 0): every chunk's depths to depth_out (may be null), the per-unitig statistics under min_depth into d->d_stats (want_stats).  fin_depth_download's
+// and fin_colors_coverage's
+static int depth_scan(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, bool want_stats, char* err, size_t errlen) {
     // the prefix sum, a chunk of the difference array at a time through one staging buffer: no second array of total_len entries on the device
     const uint32_t dbg = (uint32_t)optv(d->idx, O_debug_depth_tile);
     const uint32_t tile = dbg ? dbg : fin_depth_max_tile(), chunk_tiles = dbg ? 64u : fin_depth_max_chunk_tiles();
     const uint64_t chunk = (uint64_t)tile * chunk_tiles;
-    std::lock_guard<std::mutex> g(d->scan_mu);
     if (!d->d_stage) {
         d->stage_len = std::min<uint64_t>((uint64_t)fin_depth_max_tile() * fin_depth_max_chunk_tiles(), d->total_len);
         if (hipMalloc((void**)&d->d_stage, (size_t)d->stage_len * 4) != hipSuccess) { (void)hipGetLastError(); d->d_stage = nullptr; set_err(err, errlen, "out of device memory (depth staging buffer)"); return FIN_ENOMEM; }
@@ -2872,12 +2877,64 @@ int fin_depth_download(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, fi
         if (rc != 0) { set_err(err, errlen, std::string("depth scan kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
         if (depth_out) HIPCHK(hipMemcpy(depth_out + base, d->d_stage, (size_t)n * 4, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels, and done before the next chunk is staged)
     }
+    return FIN_OK;
+}
+
+int fin_depth_download(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, fin_depth_stat* stats_out, uint64_t* total, char* err, size_t errlen) {
+    if (!d) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(d, depth_flags(d), "a step whose overflow list overran was added: it has no results, nothing of it was counted (reset the accumulator)",
+                                          "a pair with a unitig number or a position outside the index was met (not counted)", err, errlen)) return orc;
+    if (total) *total = 0;
+    const bool want_stats = stats_out || total;
+    if (!depth_out && !want_stats) return FIN_OK;
+    if (d->total_len == 0 || d->n_unitigs == 0) return FIN_OK;
+    std::lock_guard<std::mutex> g(d->scan_mu);
+    if (const int rc = depth_scan(d, min_depth, depth_out, want_stats, err, errlen)) return rc;
     if (want_stats) {
         std::vector<fin_depth_stat> tmp;
         fin_depth_stat* const dst = dst_or_tmp(stats_out, tmp, (size_t)d->n_unitigs);
         HIPCHK(hipMemcpy(dst, d->d_stats, (size_t)d->n_unitigs * sizeof(fin_depth_stat), hipMemcpyDeviceToHost));
         if (total) *total = sum_of(dst, (size_t)d->n_unitigs, [](const fin_depth_stat& s) { return s.sum; });
     }
+    return FIN_OK;
+}
+
+// ---- breadth and depth of coverage per reference (fin_colcov.hip) -------------------------------------------------------------------------
+static_assert(sizeof(fin_color_coverage) == 64, "fin_color_coverage is eight uint64");
+int fin_colors_coverage(fin_colors* c, fin_cover* cov, fin_depth* dep, uint32_t min_depth, fin_color_coverage* out, fin_color_coverage* uncolored, char* err, size_t errlen) {
+    if (!c || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (cov && (cov->idx != c->idx || cov->device != c->device)) { set_err(err, errlen, "colours and coverage bitmap belong to different indexes or devices"); return FIN_EINVAL; }
+    if (dep && (dep->idx != c->idx || dep->device != c->device)) { set_err(err, errlen, "colours and depth accumulator belong to different indexes or devices"); return FIN_EINVAL; }
+    // the three waits, with the downloads' own codes and messages for a withheld step or a pair outside the index (nothing else happens in these calls)
+    if (const int rc = fin_colors_download(c, nullptr, nullptr, err, errlen)) return rc;
+    if (cov) if (const int rc = fin_cover_download(cov, nullptr, nullptr, nullptr, err, errlen)) return rc;
+    if (dep) if (const int rc = fin_depth_download(dep, min_depth, nullptr, nullptr, nullptr, err, errlen)) return rc;
+    const fin_index::Replica* rep = c->idx->replica_on(c->device);
+    if (!rep) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    const size_t table = ((size_t)c->n_colors + 1) * 64;
+    std::lock_guard<std::mutex> g(c->ccv_mu);
+    if (!c->d_ccv && hipMalloc(&c->d_ccv, table + (size_t)c->n_unitigs + 8) != hipSuccess) { (void)hipGetLastError(); c->d_ccv = nullptr; set_err(err, errlen, "out of device memory (colour coverage table)"); return FIN_ENOMEM; }
+    // covered[] and the statistics stay on the device; everything below is on the null stream, and the two locks keep a download from counting or scanning in between
+    std::unique_lock<std::mutex> gc, gd;
+    const bool with_cov = cov && c->n_unitigs, with_dep = dep && dep->total_len && c->n_unitigs;
+    if (with_cov) {
+        gc = std::unique_lock<std::mutex>(cov->count_mu);
+        if (const int rc = cover_count(cov, err, errlen)) return rc;
+    }
+    if (with_dep) {
+        gd = std::unique_lock<std::mutex>(dep->scan_mu);
+        if (const int rc = depth_scan(dep, min_depth, nullptr, true, err, errlen)) return rc;
+    }
+    uint64_t* const d_out = (uint64_t*)c->d_ccv;
+    uint64_t* const d_none = d_out + (size_t)c->n_colors * 8;
+    const int rc = fin_launch_color_coverage(c->d_bits, (uint32_t)c->n_unitigs, c->words, c->n_colors, rep->dev.ends, c->idx->total_len, rep->dev.k,
+                                             with_cov ? cov->d_covered : nullptr, with_dep ? dep->d_stats : nullptr, d_none + 8, (uint32_t)optv(c->idx, O_colcov_chunk), 0u,
+                                             d_out, d_none, nullptr);
+    if (rc != 0) { set_err(err, errlen, std::string("colour coverage kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    std::vector<fin_color_coverage> host((size_t)c->n_colors + 1);
+    HIPCHK(hipMemcpy(host.data(), d_out, table, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels)
+    memcpy(out, host.data(), (size_t)c->n_colors * 64);
+    if (uncolored) *uncolored = host[c->n_colors];
     return FIN_OK;
 }
 

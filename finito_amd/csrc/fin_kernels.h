@@ -238,6 +238,15 @@ int fin_launch_assign_rows(const void* rows, uint64_t n_rows, uint32_t W, uint32
                            void* heads, uint64_t* assigned, uint64_t* sole, uint64_t* counters, hipStream_t stream);
 int fin_launch_assign_column(const void* arows, uint32_t n_rows, uint32_t W, uint32_t color, uint64_t* bits, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total,
                              hipStream_t stream);
+// fin_colcov.hip -- the per-unitig coverage numbers projected through the colour matrix: bits uint64[n_unitigs * W]; ends_p, total_len and k give
+// nk(u); covered uint64[n_unitigs] and stats FinDepthStat[n_unitigs] (either may be null: zeros); cls: n_unitigs bytes the launcher fills (0 empty row, 1 one
+// colour, 2 more).  out uint64[n_colors][8] {kmers, kmers_only, covered, covered_only, depth_sum, depth_sum_only, solid, solid_only} and none uint64[8] (the
+// unitigs without a colour; its _only places stay 0), both zeroed on `stream` by the launcher.  colcov_chunk: option "colcov_chunk"; fin_colcov_chunk: the
+// unitigs a wave then takes.  loads: 0 coalesced slices broadcast through the wave (the library's), 1 wave-uniform loads (kept for tools/ab_colcov.py)
+uint32_t fin_colcov_chunk(uint64_t n_unitigs, uint32_t W, uint32_t colcov_chunk);
+int fin_launch_color_coverage(const void* bits, uint32_t n_unitigs, uint32_t W, uint32_t n_colors, const uint32_t* ends_p, uint64_t total_len, uint32_t k,
+                              const void* covered, const void* stats, void* cls, uint32_t colcov_chunk, uint32_t loads, uint64_t* out, uint64_t* none,
+                              hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -458,7 +458,7 @@ static const char* SEARCH_HELP =
     "                        unitig's count of --unitig-counts, max = the most often any one of its k-mers was found, solid = how many of its k-mers\n"
     "                        were found at least T times (--min-depth). Kept on the first GPU, 4 bytes per base of the unitig text, from one more\n"
     "                        search of every chunk; goes with -o, --unitig-counts, --unitig-coverage and --segments. Not for a partitioned index.\n"
-    "      --min-depth T     the T of --unitig-depth (default: 1); only with --unitig-depth\n"
+    "      --min-depth T     the T of --unitig-depth and --color-coverage (default: 1); only with one of them\n"
     "      --pileup FILE     also write the run's base pileup over the unitig text: a line unitig<TAB>offset<TAB>ref<TAB>cover<TAB>A<TAB>C<TAB>G<TAB>T\n"
     "                        for every position a placed read spans (cover > 0) -- how many reads span it and how many show each base other\n"
     "                        than the text's -- and a last line #reads<TAB>kept<TAB>not_straight<TAB>off_unitig<TAB>too_many. A read is placed when\n"
@@ -504,6 +504,14 @@ static const char* SEARCH_HELP =
     "                        its k-mers is found gets colour c. Sequences longer than 4096 k-mers are cut into windows that overlap by k - 1 bases, so\n"
     "                        that no k-mer is lost. Needed by --colors-out and --pseudoalign. Not for a partitioned index.\n"
     "      --colors-out FILE  write `unitig<TAB>c1,c2,...` per unitig of the index, in the index's unitig numbers, `-` for a unitig without a colour\n"
+    "      --color-coverage FILE  also write the run's breadth and depth per reference of --color-refs: one line\n"
+    "                        `colour<TAB>kmers<TAB>covered<TAB>kmers_only<TAB>covered_only<TAB>depth_sum<TAB>depth_sum_only<TAB>solid<TAB>solid_only` per colour --\n"
+    "                        the k-mers of the unitigs that carry the colour, how many of them were found, their summed depth and how many were found at\n"
+    "                        least T times (--min-depth), and the same over the unitigs that carry this colour alone --, then a line\n"
+    "                        `uncoloured<TAB>kmers<TAB>covered<TAB>depth_sum<TAB>solid` over the unitigs without a colour. Projected on the first GPU after the\n"
+    "                        last chunk from a coverage bitmap and a depth kept there (those of --unitig-coverage / --unitig-depth when they are asked for\n"
+    "                        too), at their cost: one more search of every chunk each. Coverage counts k-mers, so with --paired 1 mates need no pairing.\n"
+    "                        Wants --color-refs; goes with --no-text 1, --abundance, --eqclasses, --assign-weights and --paired 1. Not for a partitioned index.\n"
     "      --pseudoalign FILE  also write one line per read, in input order: `read<TAB>k-mers<TAB>found<TAB>coloured<TAB>c1,c2,...` -- `read` and k-mers as\n"
     "                        in --read-summary, found = the k-mers found, coloured = those of them in a unitig with a colour, then the colours that at\n"
     "                        least P thousandths of the coloured k-mers have (`-` for none). Made on the first GPU from one more search of every chunk;\n"
@@ -1320,14 +1328,15 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights"))
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage"))
         throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
+    if (o.has("color-coverage") && !o.has("color-refs")) throw runtime_error("--color-coverage wants colours: --color-refs LIST");
     g_paired = o.has("paired") && o.get("paired") != "0" && o.get("paired") != "false";
     const bool pair_both = o.has("pair-both") && o.get("pair-both") != "0" && o.get("pair-both") != "false";
     if (g_paired && !o.has("color-refs")) throw runtime_error("--paired 1 wants colours: --color-refs LIST (fragments are what --pseudoalign, --eqclasses, --color-report and --abundance then take)");
@@ -1339,7 +1348,7 @@ static int search_fmin(int argc, char** argv) {
     if (asg_asked && !o.has("assign") && !o.has("assign-report")) throw runtime_error("--assign-weights wants a result: --assign FILE and / or --assign-report FILE");
     for (const char* name : {"assign", "assign-report", "assign-threshold"})
         if (o.has(name) && !asg_asked) throw runtime_error(string("--") + name + " is only legal together with --assign-weights");
-    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
+    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked && !o.has("color-coverage")) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
     if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked && !asg_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
     if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses, --color-report or --abundance");
     if (o.has("eqclasses-in") && !eq_asked) throw runtime_error("--eqclasses-in is only legal together with --eqclasses, --color-report or --abundance");
@@ -1404,7 +1413,7 @@ static int search_fmin(int argc, char** argv) {
         for (auto& f : paths) eqc_in.push_back(eqclasses_parse_file(f, (uint32_t)color_refs.size()));
     }
     g_scr_invert = o.has("screen-invert") && o.get("screen-invert") != "0" && o.get("screen-invert") != "false" ? 1 : 0;
-    if (o.has("min-depth") && !o.has("unitig-depth")) throw runtime_error("--min-depth is only legal together with --unitig-depth");
+    if (o.has("min-depth") && !o.has("unitig-depth") && !o.has("color-coverage")) throw runtime_error("--min-depth is only legal together with --unitig-depth");
     uint32_t min_depth = 1;
     if (o.has("min-depth")) {
         const string v = o.get("min-depth");
@@ -1449,6 +1458,8 @@ static int search_fmin(int argc, char** argv) {
     if (!cover_file.empty()) check_writable(cover_file);
     const string depth_file = o.get("unitig-depth", "");
     if (!depth_file.empty()) check_writable(depth_file);
+    const string colcov_file = o.get("color-coverage", "");
+    if (!colcov_file.empty()) check_writable(colcov_file);
     const string pileup_file = o.get("pileup", ""), variants_file = o.get("variants", "");
     if (!pileup_file.empty()) check_writable(pileup_file);
     if (!variants_file.empty()) check_writable(variants_file);
@@ -1542,6 +1553,7 @@ static int search_fmin(int argc, char** argv) {
     if (!scr_file.empty() && index.partitioned()) throw runtime_error("--screen is not available with a partitioned index");
     if (!cls_file.empty() && index.partitioned()) throw runtime_error("--classify is not available with a partitioned index");
     if (!report_file.empty() && index.partitioned()) throw runtime_error("--label-report is not available with a partitioned index");
+    if (!colcov_file.empty() && index.partitioned()) throw runtime_error("--color-coverage is not available with a partitioned index");
     if (!color_refs.empty() && index.partitioned()) throw runtime_error("--color-refs is not available with a partitioned index");
     index.to_device();
     struct HitsOwner { ~HitsOwner() { fin_hits_free(g_hits); g_hits = nullptr; } } hits_owner;
@@ -1550,12 +1562,12 @@ static int search_fmin(int argc, char** argv) {
         if (fin_hits_create(index.handle(), first_dev, &g_hits, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     struct CoverOwner { ~CoverOwner() { fin_cover_free(g_cover); g_cover = nullptr; } } cover_owner;
-    if (!cover_file.empty()) {
+    if (!cover_file.empty() || !colcov_file.empty()) {   // (--color-coverage shares the bitmap and the depth of --unitig-coverage / --unitig-depth)
         char err[512] = {0};
         if (fin_cover_create(index.handle(), first_dev, &g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     struct DepthOwner { ~DepthOwner() { fin_depth_free(g_depth); g_depth = nullptr; } } depth_owner;
-    if (!depth_file.empty()) {
+    if (!depth_file.empty() || !colcov_file.empty()) {
         char err[512] = {0};
         if (fin_depth_create(index.handle(), first_dev, &g_depth, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
@@ -1785,7 +1797,7 @@ static int search_fmin(int argc, char** argv) {
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + report_file);
     }
-    if (g_cover) {   // the coverage, after the last chunk: one line per unitig of the index
+    if (!cover_file.empty()) {   // the coverage, after the last chunk: one line per unitig of the index
         char err[512] = {0};
         const size_t nu = (size_t)index.number_of_unitigs();
         vector<uint64_t> covered(nu + 1);
@@ -1803,7 +1815,7 @@ static int search_fmin(int argc, char** argv) {
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + cover_file);
     }
-    if (g_depth) {   // the depth, after the last chunk: the prefix sum and the statistics on the device, one line per unitig of the index
+    if (!depth_file.empty()) {   // the depth, after the last chunk: the prefix sum and the statistics on the device, one line per unitig of the index
         char err[512] = {0};
         const size_t nu = (size_t)index.number_of_unitigs();
         vector<fin_depth_stat> stats(nu + 1);
@@ -1821,6 +1833,25 @@ static int search_fmin(int argc, char** argv) {
         ofstream cf(depth_file, ios::binary | ios::trunc);
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + depth_file);
+    }
+    if (!colcov_file.empty()) {   // breadth and depth per reference, after the last chunk: projected on the device, one line per colour
+        char err[512] = {0};
+        const size_t nc = color_refs.size();
+        vector<fin_color_coverage> cc(nc + 1);
+        if (fin_colors_coverage(g_colors, g_cover, g_depth, min_depth, cc.data(), &cc[nc], err, sizeof err) != FIN_OK) throw runtime_error(err);
+        string text;
+        for (size_t c = 0; c < nc; c++) {
+            const fin_color_coverage& e = cc[c];
+            text += to_string(c);
+            for (uint64_t v : {e.kmers, e.covered, e.kmers_only, e.covered_only, e.depth_sum, e.depth_sum_only, e.solid, e.solid_only}) { text += '\t'; text += to_string(v); }
+            text += '\n';
+        }
+        text += "uncoloured";
+        for (uint64_t v : {cc[nc].kmers, cc[nc].covered, cc[nc].depth_sum, cc[nc].solid}) { text += '\t'; text += to_string(v); }
+        text += '\n';
+        ofstream cf(colcov_file, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + colcov_file);
     }
     if (g_pileup) {   // the pileup, after the last chunk: the covered positions, and the candidates called on the device
         char err[512] = {0};

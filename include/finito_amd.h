@@ -1111,6 +1111,36 @@ int fin_search_batch_assign(const fin_index* idx, const char* bases, const uint6
 int fin_rows_assign(const uint64_t* rows, uint64_t n_rows, uint32_t n_colors, const double* weights, const double* thresholds, uint64_t* out_rows,
                     fin_read_assign* heads, uint64_t* assigned, uint64_t* sole, uint64_t counters[4], int n_threads);
 
+/* ---- BREADTH AND DEPTH OF COVERAGE PER REFERENCE, projected on the device ----
+ * Where the colour line and the coverage line meet: how much of each reference the sample covered, and how deep -- an abundance of 40 000 reads means something
+ * else when 97 % of a reference's k-mers were seen than when 3 % were.  Everything in existing quantities, exact 64-bit integers.  For unitig u of the index:
+ *   nk(u) = len(u) - k + 1, its k-mers; R(u) its row of the colour matrix; cov(u) = covered[u] of fin_cover_download (0 without a bitmap);
+ *   {sum(u), n_at_least(u)} = fin_depth_download's fin_depth_stat under min_depth (0 without a depth accumulator).
+ * For every colour c < n_colors, over the unitigs whose row has bit c:      ... and over those whose row is {c} alone:
+ *   kmers[c]     = the sum of nk(u)                                         kmers_only[c]
+ *   covered[c]   = the sum of cov(u)                                        covered_only[c]
+ *   depth_sum[c] = the sum of sum(u)                                        depth_sum_only[c]
+ *   solid[c]     = the sum of n_at_least(u)                                 solid_only[c]
+ * `uncolored` holds the same four sums over the unitigs whose row is empty -- what the run found that belongs to no reference; its _only fields are 0.
+ *   IDENTITIES  covered[c] <= kmers[c].  With min_depth = 1 and bitmap and depth filled by the same runs, solid[c] == covered[c].  The sum of kmers_only[c] over
+ *               c + uncolored.kmers + the sum of nk(u) over the rows of two or more colours = the sum of nk(u) over all unitigs.
+ *   MEANING     On a compacted graph coloured by search (fin_batch_add_colors) every k-mer of a unitig shares its colour set: kmers[c] is exactly the distinct
+ *               k-mers of reference c.  On any other colouring it is "k-mers of unitigs that carry c".  On an index whose unitigs are not disjoint, bitmap and
+ *               depth hold what fin_cover / fin_depth hold there: the place the search reports for a k-mer.
+ * A waiting call, like the downloads: it waits for every add and reset issued so far to each accumulator given, makes covered[] and the depth statistics on the
+ * device as the two downloads do, runs the projection and copies 64 (n_colors + 1) bytes back.  None of the three accumulators is changed.  cov and dep may both
+ * be NULL: kmers / kmers_only alone are the references' sizes in the graph.  FIN_EINVAL for a NULL c or out and for an accumulator of another index or device
+ * (the message says which); the codes and messages of fin_colors_download, fin_cover_download and fin_depth_download for a withheld step or a pair outside the
+ * index are passed on, and then nothing is written to out. */
+typedef struct fin_color_coverage { uint64_t kmers, kmers_only, covered, covered_only, depth_sum, depth_sum_only, solid, solid_only; } fin_color_coverage;   /* 64 bytes */
+int fin_colors_coverage(fin_colors* c, fin_cover* cov /* may be NULL */, fin_depth* dep /* may be NULL */, uint32_t min_depth,
+                        fin_color_coverage* out /* [n_colors] */, fin_color_coverage* uncolored /* may be NULL */, char* err, size_t errlen);
+/* host twin, no device: bits uint64[n_unitigs][W], nk uint64[n_unitigs]; covered (uint64[n_unitigs]) and stats may be NULL (zeros).  Threads take ranges of
+ * unitigs and their tables are added at the end: the result does not depend on n_threads.  FIN_EINVAL for a bit at or above n_colors, FIN_ELIMIT for n_colors
+ * outside 1 .. 4096.  uncolored may be NULL */
+int fin_unitig_color_coverage(const uint64_t* bits, uint64_t n_unitigs, uint32_t n_colors, const uint64_t* nk, const uint64_t* covered /* may be NULL */,
+                              const fin_depth_stat* stats /* may be NULL */, fin_color_coverage* out, fin_color_coverage* uncolored, int n_threads);
+
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
  * k-mer is in no unitig), 1 a verified claim, 2 an unverified one (| 8: the exact side table has the k-mer, g is its answer), | 4 the text at [g-k+1, g] spells
