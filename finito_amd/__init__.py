@@ -1848,10 +1848,12 @@ VARIANT_DTYPE = np.dtype([("u", np.uint32), ("off", np.uint32), ("cover", np.uin
 
 
 class PartitionedBatch:
-    """A read set resident on the device of a PartitionedIndex (fin_pbatch_*): run() = every part's step and its merge."""
+    """A read set resident on the device of a PartitionedIndex (fin_pbatch_*): run() = every part's step and its merge.  The batch holds its own
+    reference on the C side's set (include/finito_amd.h: the free-order contract), not on the Python object: it stays usable after the index is
+    closed or collected, until it is closed itself."""
 
     def __init__(self, pindex, reads):
-        self.L = lib(); self.h = C.c_void_p(); self.pindex = pindex
+        self.L = lib(); self.h = C.c_void_p()
         err = C.create_string_buffer(512)
         _check(self.L.fin_pbatch_create(pindex.h, *_reads_args(reads),
                                         C.byref(self.h), err, 512), err)
@@ -1890,7 +1892,7 @@ class PartitionedIndex:
     for the input the reference requires, a disjoint spectrum-preserving string set (README.md:79-80), which verify=True checks on the device."""
 
     def __init__(self, unitigs, k, device=0, max_part_bases=0, verify=True, _load_prefix=None):
-        self.L = L = lib(); self.h = C.c_void_p()
+        self.L = L = lib(); self._h = C.c_void_p()
         vp, cp = C.c_void_p, C.c_char_p
         L.fin_pindex_save.argtypes = [vp, cp, cp, C.c_size_t]
         L.fin_pindex_load.argtypes = [cp, C.c_int, C.POINTER(vp), cp, C.c_size_t]
@@ -1915,10 +1917,10 @@ class PartitionedIndex:
         err = C.create_string_buffer(1024)
         self.device = int(device)
         if _load_prefix is not None:
-            _check(L.fin_pindex_load(str(_load_prefix).encode(), int(device), C.byref(self.h), err, 1024), err)
+            _check(L.fin_pindex_load(str(_load_prefix).encode(), int(device), C.byref(self._h), err, 1024), err)
             return
         _check(L.fin_pindex_build_device(*_reads_args(unitigs), int(k), int(device),
-                                         int(max_part_bases), 1 if verify else 0, C.byref(self.h), err, 1024), err)
+                                         int(max_part_bases), 1 if verify else 0, C.byref(self._h), err, 1024), err)
 
     @classmethod
     def load(cls, index_prefix, device=0):
@@ -1980,9 +1982,17 @@ class PartitionedIndex:
     def batch(self, reads):
         return PartitionedBatch(self, reads)
 
+    @property
+    def h(self):
+        """the fin_pindex handle; a closed index has none, and whatever asks for it is refused here, before the C side sees a null or a dangling pointer"""
+        if not self._h:
+            raise FinitoError(FIN_EINVAL, "the PartitionedIndex is closed")
+        return self._h
+
     def close(self):
-        if self.h:
-            self.L.fin_pindex_free(self.h); self.h = C.c_void_p()
+        """fin_pindex_free: the owner's reference.  Batches made by batch() hold their own and stay usable until they are closed themselves"""
+        if self._h:
+            self.L.fin_pindex_free(self._h); self._h = C.c_void_p()
 
     def __del__(self):
         try:

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -17,6 +18,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/finito_amd.h"
@@ -202,15 +204,66 @@ int fin_index_build_device(const char* unitig_bases, const uint64_t* unitig_offs
     return FIN_OK;
 }
 
-int fin_index_save(const fin_index* idx, const char* prefix, char* err, size_t errlen) {
-    if (!idx || !prefix) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+static bool file_exists(const std::string& p) { FILE* f = fopen(p.c_str(), "rb"); if (f) fclose(f); return f != nullptr; }
+
+// <prefix>.finparts, the manifest of a partitioned index (fin_pindex_save writes it, below): what it says, for the loader and for whoever saves over it
+struct PartsManifest {
+    int k = 0;
+    unsigned long long n_unitigs = 0; long long shared_kmers = -1;
+    std::vector<uint64_t> first_unitig;   // per part
+    std::vector<size_t> n_part_unitigs;   // per part
+    size_t parts() const { return n_part_unitigs.size(); }
+};
+// -1: no such file; 0: a file that is not a manifest; 1: read
+static int read_parts_manifest(const std::string& pre, PartsManifest& m) {
+    FILE* f = fopen((pre + ".finparts").c_str(), "r");
+    if (!f) return -1;
+    int ver = 0; size_t P = 0;
+    bool ok = fscanf(f, "finito-parts %d k %d parts %zu unitigs %llu shared_kmers %lld", &ver, &m.k, &P, &m.n_unitigs, &m.shared_kmers) == 5 && ver == 1 && P >= 1 && P < 65536;
+    m.first_unitig.assign(ok ? P : 0, 0); m.n_part_unitigs.assign(ok ? P : 0, 0);
+    for (size_t p = 0; ok && p < P; p++) {
+        size_t pi = 0; unsigned long long fu = 0;
+        ok = fscanf(f, " part %zu first_unitig %llu unitigs %zu", &pi, &fu, &m.n_part_unitigs[p]) == 3 && pi == p;
+        m.first_unitig[p] = fu;
+    }
+    fclose(f);
+    if (!ok) { m.first_unitig.clear(); m.n_part_unitigs.clear(); }
+    return ok ? 1 : 0;
+}
+// a file that is not there is removed already; one that is there and stays is an error
+static int remove_file(const std::string& path, char* err, size_t errlen) {
+    if (std::remove(path.c_str()) == 0 || errno == ENOENT) return FIN_OK;
+    set_err(err, errlen, "cannot remove " + path + ": " + strerror(errno));
+    return FIN_EIO;
+}
+// part i's container and table of set-wide unitig numbers, for i in [from, to)
+static int remove_part_files(const std::string& pre, size_t from, size_t to, char* err, size_t errlen) {
+    for (size_t i = from; i < to; i++)
+        for (const char* ext : {".finamd", ".gid"})
+            if (const int rc = remove_file(pre + ".p" + std::to_string(i) + ext, err, errlen)) return rc;
+    return FIN_OK;
+}
+
+static int index_save_container(const fin_index* idx, const char* prefix, char* err, size_t errlen) {
     std::string msg;
     int rc = fin_save_index(*idx, prefix, msg);
     if (rc) set_err(err, errlen, msg);
     return rc;
 }
 
-static bool file_exists(const std::string& p) { FILE* f = fopen(p.c_str(), "rb"); if (f) fclose(f); return f != nullptr; }
+// Saving under a prefix REPLACES what was there: loaders take the partitioned index whenever <prefix>.finparts exists (FinimizerIndex::load, search-fmin), so a
+// manifest an earlier fin_pindex_save left under this prefix would answer for the index written here.  It goes first (from then on the prefix is this index),
+// then the part files it names, if it can be read.
+int fin_index_save(const fin_index* idx, const char* prefix, char* err, size_t errlen) {
+    if (!idx || !prefix) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int rc = index_save_container(idx, prefix, err, errlen)) return rc;
+    const std::string pre(prefix);
+    PartsManifest old;
+    const int had = read_parts_manifest(pre, old);
+    if (had < 0) return FIN_OK;
+    if (const int rc = remove_file(pre + ".finparts", err, errlen)) return rc;
+    return remove_part_files(pre, 0, old.parts(), err, errlen);
+}
 
 int fin_index_load(const char* prefix, fin_index** out, char* err, size_t errlen) {
     if (!prefix || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
@@ -3840,16 +3893,27 @@ struct fin_pindex {
     double verify_s = 0.0;
     // fin_pindex_search_batch keeps its device batches from call to call (a caller that streams chunks of reads through it allocates once)
     mutable std::mutex mu; mutable struct fin_pbatch* cached = nullptr;
+    // Lifetime: the owner holds one reference and every fin_pbatch one (its parts' batches live on the set's fin_index handles and its merge reads d_gid), so
+    // fin_pindex_free and fin_pbatch_free may come in either order; whoever drops the last reference destroys the set.
+    mutable std::atomic<int> refs{1};
 };
 void fin_pbatch_free(fin_pbatch* sb);
 
-void fin_pindex_free(fin_pindex* s) {
-    if (!s) return;
+static void pindex_release(const fin_pindex* cs) {
+    if (!cs || cs->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
+    fin_pindex* s = const_cast<fin_pindex*>(cs);
     if (s->device >= 0) (void)hipSetDevice(s->device);
-    fin_pbatch_free(s->cached);
     for (uint32_t* g : s->d_gid) (void)hipFree(g);
     for (fin_index* p : s->parts) fin_index_free(p);
     delete s;
+}
+// the owner's reference.  The cached batch of fin_pindex_search_batch is the owner's too: it goes here (with its reference), or it would keep the set alive
+void fin_pindex_free(fin_pindex* s) {
+    if (!s) return;
+    fin_pbatch* c = nullptr;
+    { std::lock_guard<std::mutex> g(s->mu); c = s->cached; s->cached = nullptr; }
+    fin_pbatch_free(c);
+    pindex_release(s);
 }
 uint32_t fin_pindex_parts(const fin_pindex* s) { return s ? (uint32_t)s->parts.size() : 0u; }
 const fin_index* fin_pindex_part(const fin_pindex* s, uint32_t p) { return (s && p < s->parts.size()) ? s->parts[p] : nullptr; }
@@ -3898,9 +3962,11 @@ static int pindex_upload(fin_pindex* s, char* err, size_t errlen) {
 int fin_pindex_save(const fin_pindex* s, const char* prefix, char* err, size_t errlen) {
     if (!s || !prefix) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     const std::string pre(prefix);
+    PartsManifest old;   // (read before it is overwritten: the part files it names beyond this set's are removed below)
+    (void)read_parts_manifest(pre, old);
     for (size_t p = 0; p < s->parts.size(); p++) {
         const std::string pp = pre + ".p" + std::to_string(p);
-        const int rc = fin_index_save(s->parts[p], pp.c_str(), err, errlen);
+        const int rc = index_save_container(s->parts[p], pp.c_str(), err, errlen);
         if (rc != FIN_OK) return rc;
         FILE* f = fopen((pp + ".gid").c_str(), "wb");
         if (!f || fwrite(s->gid[p].data(), sizeof(uint32_t), s->gid[p].size(), f) != s->gid[p].size() || fclose(f) != 0) { set_err(err, errlen, "cannot write " + pp + ".gid"); if (f) fclose(f); return FIN_EIO; }
@@ -3910,28 +3976,25 @@ int fin_pindex_save(const fin_pindex* s, const char* prefix, char* err, size_t e
     fprintf(f, "finito-parts 1\nk %d\nparts %zu\nunitigs %llu\nshared_kmers %lld\n", s->k, s->parts.size(), (unsigned long long)s->n_unitigs, (long long)s->shared_kmers);
     for (size_t p = 0; p < s->parts.size(); p++) fprintf(f, "part %zu first_unitig %llu unitigs %zu\n", p, (unsigned long long)s->first_unitig[p], s->gid[p].size());
     if (fclose(f) != 0) { set_err(err, errlen, "cannot write " + pre + ".finparts"); return FIN_EIO; }
-    return FIN_OK;
+    // what was under this prefix before is replaced: the higher-numbered parts of a larger set (no manifest names them any more), a one-index container
+    if (const int rc = remove_part_files(pre, s->parts.size(), old.parts(), err, errlen)) return rc;
+    return remove_file(pre + ".finamd", err, errlen);
 }
 int fin_pindex_exists(const char* prefix) { return prefix && file_exists(std::string(prefix) + ".finparts") ? 1 : 0; }
 int fin_pindex_load(const char* prefix, int device, fin_pindex** out, char* err, size_t errlen) {
     if (!prefix || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     const std::string pre(prefix);
-    FILE* f = fopen((pre + ".finparts").c_str(), "r");
-    if (!f) { set_err(err, errlen, "cannot open " + pre + ".finparts"); return FIN_EIO; }
+    PartsManifest m;
+    const int have = read_parts_manifest(pre, m);
+    if (have < 0) { set_err(err, errlen, "cannot open " + pre + ".finparts"); return FIN_EIO; }
+    if (have == 0) { set_err(err, errlen, pre + ".finparts is not a partitioned index's manifest"); return FIN_EIO; }
     std::unique_ptr<fin_pindex, void (*)(fin_pindex*)> s(new fin_pindex, fin_pindex_free);
-    s->device = device;
-    int ver = 0; size_t P = 0; unsigned long long nu = 0; long long shared = -1;
-    bool ok = fscanf(f, "finito-parts %d k %d parts %zu unitigs %llu shared_kmers %lld", &ver, &s->k, &P, &nu, &shared) == 5 && ver == 1 && P >= 1 && P < 65536;
-    std::vector<size_t> cnt(ok ? P : 0);
-    s->first_unitig.assign(ok ? P + 1 : 1, 0);
-    for (size_t p = 0; ok && p < P; p++) {
-        size_t pi = 0; unsigned long long fu = 0;
-        ok = fscanf(f, " part %zu first_unitig %llu unitigs %zu", &pi, &fu, &cnt[p]) == 3 && pi == p;
-        s->first_unitig[p] = fu;
-    }
-    fclose(f);
-    if (!ok) { set_err(err, errlen, pre + ".finparts is not a partitioned index's manifest"); return FIN_EIO; }
-    s->n_unitigs = nu; s->shared_kmers = shared; s->first_unitig[P] = nu;
+    s->device = device; s->k = m.k;
+    const size_t P = m.parts();
+    const unsigned long long nu = m.n_unitigs;
+    const std::vector<size_t>& cnt = m.n_part_unitigs;
+    s->first_unitig = m.first_unitig; s->first_unitig.push_back(nu);
+    s->n_unitigs = nu; s->shared_kmers = m.shared_kmers;
     uint64_t seen = 0;
     for (size_t p = 0; p < P; p++) {
         const std::string pp = pre + ".p" + std::to_string(p);
@@ -3955,6 +4018,33 @@ int fin_pindex_load(const char* prefix, int device, fin_pindex** out, char* err,
     return FIN_OK;
 }
 
+// Where to cut the input unitigs [u0, u1), which together hold a k-mer twice (same strand: what fin_index_is_disjoint counts), so that the front piece does not:
+// *cut = the first unitig that holds a k-mer of a unitig before it.  Host, plain strings: this runs for the rare part of an unchecked set that needs it.
+static int pindex_split_point(const char* B, const uint64_t* O, uint64_t u0, uint64_t u1, int k, uint64_t* cut, char* err, size_t errlen) {
+    if (O[u1] - O[u0] > (1ull << 26)) {
+        set_err(err, errlen, "index set: a part of more than 2^26 bases holds a k-mer twice; it is not split here -- pass a smaller max_part_bases, or a disjoint set");
+        return FIN_ELIMIT;
+    }
+    std::unordered_map<std::string, uint64_t> owner;   // k-mer -> the first unitig that holds it
+    for (uint64_t u = u0; u < u1; u++) {
+        const uint64_t len = O[u + 1] - O[u];
+        for (uint64_t i = 0; i + (uint64_t)k <= len; i++) {
+            std::string m(B + O[u] + i, (size_t)k);
+            for (char& c : m) c &= (char)0xDF;
+            const auto ins = owner.emplace(std::move(m), u);
+            if (ins.second) continue;
+            if (ins.first->second == u) {
+                set_err(err, errlen, "index set: input unitig " + std::to_string(u) + " holds a k-mer twice by itself: no part can hold it and answer for what it reports");
+                return FIN_EINVAL;
+            }
+            *cut = u;
+            return FIN_OK;
+        }
+    }
+    set_err(err, errlen, "index set: a part holds a k-mer twice, but no unitig of it repeats a k-mer of another (bases other than ACGT?): it cannot be split");
+    return FIN_EINVAL;
+}
+
 int fin_pindex_build_device(const char* unitig_bases, const uint64_t* unitig_offsets, uint64_t n_unitigs, int k, int device, uint64_t max_part_bases,
                                int verify, fin_pindex** out, char* err, size_t errlen) {
     if (!unitig_bases || !unitig_offsets || !out || n_unitigs == 0 || k < 2 || k > 255) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
@@ -3976,14 +4066,25 @@ int fin_pindex_build_device(const char* unitig_bases, const uint64_t* unitig_off
         }
         s->first_unitig.push_back(n_unitigs);
     }
-    const size_t P = s->first_unitig.size() - 1;
-    for (size_t p = 0; p < P; p++) {
+    for (size_t p = 0; p + 1 < s->first_unitig.size();) {
         const uint64_t u0 = s->first_unitig[p], nu = s->first_unitig[p + 1] - u0;
         fin_index* x = nullptr;
         const int rc = fin_index_build_device(unitig_bases, unitig_offsets + u0, nu, k, device, &x, nullptr, err, errlen);
         if (rc != FIN_OK) return rc;
+        // An UNCHECKED set must still be made of parts that are disjoint by themselves: an index that holds a k-mer twice answers as the reference does over
+        // duplicated unitigs -- its walk can follow the wrong copy's text and name places that do not spell the k-mer (common.hh:61-67) --, and then nothing could
+        // be said about what the set returns.  Such a part is cut in front of the first unitig that repeats a k-mer of the unitigs before it, and built again.
+        if (!verify && !fin_index_is_disjoint(x)) {
+            fin_index_free(x);
+            uint64_t cut = 0;
+            if (const int src = pindex_split_point(unitig_bases, unitig_offsets, u0, u0 + nu, k, &cut, err, errlen)) return src;
+            s->first_unitig.insert(s->first_unitig.begin() + (ptrdiff_t)p + 1, cut);
+            continue;   // ([u0, cut) holds no k-mer twice; [cut, ...) is looked at in its turn)
+        }
         s->parts.push_back(x);
+        p++;
     }
+    const size_t P = s->first_unitig.size() - 1;
     // the set's unitig numbers: permute_unitigs over ALL unitigs -- colex order of the first k-mers (the last base is the most significant), ties by input order
     {
         std::vector<uint32_t> order(n_unitigs);
@@ -4045,23 +4146,26 @@ int fin_pindex_build_device(const char* unitig_bases, const uint64_t* unitig_off
 }
 
 struct fin_pbatch {
-    const fin_pindex* set = nullptr;
+    const fin_pindex* set = nullptr;   // a reference (fin_pindex::refs): the set outlives the batch, whichever is freed first
     std::vector<fin_batch*> b;
     struct Ev { hipEvent_t e0, e1; };
+    static constexpr size_t MAX_RUNS = 1024;   // the timing window: the event pairs of the most recent runs
     std::vector<Ev> runs;
+    uint64_t runs_dropped = 0;         // runs whose events left the window: runs[i] is run number runs_dropped + i since creation
     hipStream_t last_stream = nullptr; bool ran = false;
 };
 void fin_pbatch_free(fin_pbatch* sb) {
     if (!sb) return;
     if (sb->set && sb->set->device >= 0) (void)hipSetDevice(sb->set->device);
     for (auto& r : sb->runs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-    for (fin_batch* x : sb->b) fin_batch_free(x);
+    for (fin_batch* x : sb->b) fin_batch_free(x);   // (before the set's reference goes: they live on its parts)
+    pindex_release(sb->set);
     delete sb;
 }
 int fin_pbatch_create(const fin_pindex* s, const char* bases, const uint64_t* offsets, uint64_t n_reads, fin_pbatch** out, char* err, size_t errlen) {
     if (!s || !out || !offsets) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     std::unique_ptr<fin_pbatch, void (*)(fin_pbatch*)> sb(new fin_pbatch, fin_pbatch_free);
-    sb->set = s;
+    sb->set = s; s->refs.fetch_add(1, std::memory_order_relaxed);
     for (fin_index* p : s->parts) {
         fin_batch* x = nullptr;
         const int rc = fin_batch_create_on(p, s->device, bases, offsets, n_reads, &x, err, errlen);
@@ -4084,7 +4188,10 @@ int fin_pbatch_run(fin_pbatch* sb, void* hip_stream, char* err, size_t errlen) {
     if (!sb || sb->b.empty()) { set_err(err, errlen, "bad argument"); return FIN_EINVAL; }
     HIPCHK(hipSetDevice(sb->set->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (sb->runs.size() >= 1024) { (void)hipEventDestroy(sb->runs.front().e0); (void)hipEventDestroy(sb->runs.front().e1); sb->runs.erase(sb->runs.begin()); }
+    if (sb->runs.size() >= fin_pbatch::MAX_RUNS) {
+        (void)hipEventDestroy(sb->runs.front().e0); (void)hipEventDestroy(sb->runs.front().e1);
+        sb->runs.erase(sb->runs.begin()); sb->runs_dropped++;
+    }
     fin_pbatch::Ev ev;
     HIPCHK(hipEventCreate(&ev.e0)); HIPCHK(hipEventCreate(&ev.e1));
     sb->runs.push_back(ev);
@@ -4118,11 +4225,13 @@ int fin_pbatch_download(fin_pbatch* sb, int32_t* pairs_out, uint64_t* n_positive
     if (n_positive) *n_positive = c;
     return FIN_OK;
 }
-// device time of a set step (HIP events on the launch stream), averaged over the runs behind the first skip_first
+// device time of a set step (HIP events on the launch stream), averaged over the runs behind the first skip_first SINCE CREATION that are still in the
+// window (the skipped runs the window has dropped already count as skipped)
 int fin_pbatch_step_time(const fin_pbatch* sb, uint64_t skip_first, double* ms_avg, uint64_t* n_runs) {
     if (!sb || !ms_avg) return FIN_EINVAL;
     double t = 0; uint64_t n = 0;
-    for (size_t i = (size_t)skip_first; i < sb->runs.size(); i++) {
+    const uint64_t from = skip_first > sb->runs_dropped ? skip_first - sb->runs_dropped : 0;
+    for (size_t i = (size_t)std::min<uint64_t>(from, sb->runs.size()); i < sb->runs.size(); i++) {
         float ms = 0;
         if (hipEventSynchronize(sb->runs[i].e1) != hipSuccess || hipEventElapsedTime(&ms, sb->runs[i].e0, sb->runs[i].e1) != hipSuccess) { (void)hipGetLastError(); continue; }
         t += ms; n++;

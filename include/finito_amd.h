@@ -151,7 +151,8 @@ int fin_index_build(const char* unitig_bases, const uint64_t* unitig_offsets, ui
 int fin_index_build_device(const char* unitig_bases, const uint64_t* unitig_offsets, uint64_t n_unitigs, int k, int device,
                            fin_index** out, double* phase_ms, char* err, size_t errlen);
 
-/* FinimizerIndex::serialize(prefix) (FinimizerIndex.hh:187-207): writes <prefix>.finamd (one container file). */
+/* FinimizerIndex::serialize(prefix) (FinimizerIndex.hh:187-207): writes <prefix>.finamd (one container file), and removes the partitioned index an earlier
+ * fin_pindex_save left under the same prefix (its manifest and the part files it names; see there): the prefix then holds this index alone. */
 int fin_index_save(const fin_index* idx, const char* prefix, char* err, size_t errlen);
 /* FinimizerIndex::load(prefix) (FinimizerIndex.hh:209-241): <prefix>.finamd if it exists, else the reference's own seven files
  * <prefix>.{O,FBV,packed_unitigs,unitig_endpoints,Ustart,LCS}.sdsl + <prefix>.sbwt (an index built by the reference's tools). */
@@ -382,14 +383,30 @@ int fin_batch_debug_ingest(const fin_batch* b, uint32_t* fused, void* chunks, ui
  * provided the input is what the reference requires (README.md:79-80), a disjoint spectrum-preserving string set: no k-mer, nor its reverse complement,
  * a second time anywhere.  verify != 0 checks exactly that on the device (no part holds a k-mer twice; every part's unitigs searched in the parts behind
  * it) and refuses a set that fails with FIN_EINVAL: which occurrence of a shared k-mer the reference reports depends on the WHOLE index.  A step costs the
- * parts' steps plus a merge pass each.  At most 2^31-1 unitigs. */
+ * parts' steps plus a merge pass each.  At most 2^31-1 unitigs.
+ * An UNCHECKED set (verify == 0; fin_pindex_shared_kmers is -1) over an input that is not disjoint is the caller's risk in this sense only: every pair
+ * (u, off) it reports is a true occurrence -- with U the input unitig whose set-wide number is u (the rank of its first k-mer among ALL input unitigs in
+ * colex order, ties by input order), U[off, off + k) is the read's k-mer or its reverse complement -- and a slot is (-1,-1) iff neither occurs anywhere in
+ * the set; WHICH occurrence of a k-mer that has several is reported is unspecified (the last part that finds it writes the slot) and need not be the one
+ * index's.  This rests on every PART being disjoint by itself: one index that holds a k-mer twice answers as the reference does over duplicated unitigs
+ * and can name places that do not spell the k-mer (its walk follows the wrong copy's text, common.hh:61-67).  So an unchecked build cuts a part that holds
+ * a k-mer twice (same strand: what fin_index_is_disjoint counts) in front of the first unitig that repeats a k-mer of the part's unitigs before it, and
+ * looks at the rest in its turn: such a set has more parts than max_part_bases alone gives.  The cut is found on the host; it is refused for a part of
+ * more than 2^26 bases (FIN_ELIMIT), and an input unitig that holds a k-mer twice by itself is refused (FIN_EINVAL), unchecked or not.
+ * Lifetime: fin_pindex_free and fin_pbatch_free may be called in either order, and a batch stays fully usable (reload, run, download, step_time) until it is
+ * freed itself: the set is reference-counted -- the owner holds one reference, every fin_pbatch one -- and is destroyed with the last of them.  After
+ * fin_pindex_free the caller's fin_pindex pointer is gone (no further fin_pindex_* call, no new batch), whatever batches are still alive. */
 typedef struct fin_pindex fin_pindex;
 typedef struct fin_pbatch fin_pbatch;
 int fin_pindex_build_device(const char* unitig_bases, const uint64_t* unitig_offsets, uint64_t n_unitigs, int k, int device, uint64_t max_part_bases,
                                int verify, fin_pindex** out, char* err, size_t errlen);
 void fin_pindex_free(fin_pindex* s);
 /* persistence: <prefix>.finparts (a text manifest), <prefix>.p<i>.finamd (every part's container, as fin_index_save) and <prefix>.p<i>.gid (its table of
- * set-wide unitig numbers).  fin_pindex_load uploads every part's replica to `device`; fin_pindex_exists: 1 iff <prefix>.finparts is there */
+ * set-wide unitig numbers).  fin_pindex_load uploads every part's replica to `device`; fin_pindex_exists: 1 iff <prefix>.finparts is there.
+ * Saving under a prefix REPLACES whatever kind of index was there (loaders take the partitioned index whenever the manifest exists): a successful
+ * fin_index_save removes <prefix>.finparts and, if it can be read as a manifest, the .p<i>.finamd and .p<i>.gid files it names; a successful fin_pindex_save
+ * of P parts removes the part files i >= P that the manifest it overwrites named, and <prefix>.finamd.  A file that is there and cannot be removed: FIN_EIO,
+ * the file named in the message (what was saved stays). */
 int fin_pindex_save(const fin_pindex* s, const char* prefix, char* err, size_t errlen);
 int fin_pindex_load(const char* prefix, int device, fin_pindex** out, char* err, size_t errlen);
 int fin_pindex_exists(const char* prefix);
@@ -417,6 +434,9 @@ int fin_pbatch_run(fin_pbatch* b, void* hip_stream, char* err, size_t errlen);
 uint64_t fin_pbatch_n_kmers(const fin_pbatch* b);
 void* fin_pbatch_device_pairs(const fin_pbatch* b);
 int fin_pbatch_download(fin_pbatch* b, int32_t* pairs_out, uint64_t* n_positive, char* err, size_t errlen);
+/* device time of a step (HIP events on the launch stream), averaged.  The batch keeps the events of its most recent 1024 runs (the window); skip_first
+ * counts runs SINCE CREATION, so the average is over the runs numbered skip_first and up that are still in the window, and *n_runs is how many that were
+ * (0, with *ms_avg = 0.0, when there are none) */
 int fin_pbatch_step_time(const fin_pbatch* b, uint64_t skip_first, double* ms_avg, uint64_t* n_runs);
 void fin_pbatch_free(fin_pbatch* b);
 

@@ -111,3 +111,46 @@ def test_partitioned_index_entry_points_refuse_bad_input_without_a_device(tmp_pa
     assert not h.value
     assert L.fin_pindex_parts(None) == 0 and L.fin_pindex_n_nodes(None) == -1
     L.fin_pindex_free(None)
+
+
+_MANIFEST = "finito-parts 1\nk 31\nparts 2\nunitigs 10\nshared_kmers 0\npart 0 first_unitig 0 unitigs 5\npart 1 first_unitig 5 unitigs 5\n"
+
+
+def test_saving_one_index_removes_the_partitioned_index_under_its_prefix(tmp_path):
+    """Saving under a prefix replaces whatever kind of index was there (include/finito_amd.h): loaders take the partitioned index whenever <prefix>.finparts
+    exists, so a manifest that an earlier fin_pindex_save left behind would answer for the index saved here.  A successful fin_index_save removes it and the part
+    files it names -- those and no others; a manifest that cannot be read is removed alone; what cannot be removed is FIN_EIO with the file named."""
+    unitigs = ["ACGGTACCAGTTTGA", "GGATTCAGGCAATCC", "TTGACCGTAAGCAT"]
+    idx = fa.FinimizerIndex.build(unitigs, 7)
+    names = lambda: sorted(os.listdir(tmp_path))
+    # a well-formed manifest of two parts, their files, and bystanders no manifest names
+    (tmp_path / "px.finparts").write_text(_MANIFEST)
+    for f in ("px.p0.finamd", "px.p0.gid", "px.p1.finamd", "px.p1.gid", "px.p2.finamd", "px.p2.gid", "pxx.p0.gid", "other.finparts"):
+        (tmp_path / f).write_bytes(b"dummy")
+    assert fa.PartitionedIndex.exists(str(tmp_path / "px"))
+    idx.serialize(str(tmp_path / "px"))
+    assert not fa.PartitionedIndex.exists(str(tmp_path / "px"))
+    assert names() == ["other.finparts", "px.finamd", "px.p2.finamd", "px.p2.gid", "pxx.p0.gid"]
+    q = fa.FinimizerIndex().load(str(tmp_path / "px"))
+    assert q.n_kmers == idx.n_kmers == len({u[i:i + 7] for u in unitigs for i in range(len(u) - 6)}) and q.k == idx.k == 7 and q.n_unitigs == 3
+    q.close()
+    # an unparsable manifest: removed too, and nothing else is touched
+    (tmp_path / "bad.finparts").write_text("not a manifest\n")
+    for f in ("bad.p0.finamd", "bad.p0.gid"):
+        (tmp_path / f).write_bytes(b"dummy")
+    before = names()
+    idx.serialize(str(tmp_path / "bad"))
+    assert not fa.PartitionedIndex.exists(str(tmp_path / "bad"))
+    assert names() == sorted(set(before) - {"bad.finparts"} | {"bad.finamd"})
+    # a prefix without a manifest: the container and nothing else
+    before = names()
+    idx.serialize(str(tmp_path / "plain"))
+    assert names() == sorted(before + ["plain.finamd"])
+    # a manifest that cannot be removed (a directory that is not empty): FIN_EIO, the file named; what was saved stays
+    (tmp_path / "dir.finparts").mkdir()
+    (tmp_path / "dir.finparts" / "inside").write_text("")
+    with pytest.raises(fa.FinitoError) as e:
+        idx.serialize(str(tmp_path / "dir"))
+    assert e.value.code == fa.FIN_EIO and "dir.finparts" in str(e.value)
+    assert os.path.exists(tmp_path / "dir.finamd") and os.path.exists(tmp_path / "dir.finparts" / "inside")
+    idx.close()
