@@ -319,6 +319,8 @@ def lib():
         L.fin_rows_assign.argtypes = [u64p, u64, u32, f64p, f64p, u64p, vp, u64p, u64p, u64p, C.c_int]
         L.fin_colors_coverage.argtypes = [vp, vp, vp, u32, vp, vp, cp, C.c_size_t]
         L.fin_unitig_color_coverage.argtypes = [u64p, u64, u32, u64p, u64p, vp, vp, vp, C.c_int]
+        L.fin_colors_shared.argtypes = [vp, vp, vp, vp, cp, C.c_size_t]
+        L.fin_unitig_color_shared.argtypes = [u64p, u64, u32, u64p, u64p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -882,6 +884,23 @@ class Colors(_Accumulator):
                                           out.ctypes.data_as(C.c_void_p), out[self.n_colors:].ctypes.data_as(C.c_void_p), err, 512), err)
         return ColorCoverage(out[: self.n_colors], out[self.n_colors])
 
+    def shared(self, cover=None, weights=None):
+        """the k-mers every pair of references shares: this matrix times itself under a weight per unitig, on the device (fin_colors_shared) -- a
+        ColorShared.  Neither given: the unitigs' k-mers, the references' overlap in the graph; cover: a Cover of the same index and device, the k-mers that bitmap
+        found; weights: uint64[n_unitigs] of the caller's (sums are mod 2^64).  Not both.  Waits for the adds to the matrix and the bitmap; changes neither"""
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.uint64)
+            if w.shape != (self.n_unitigs,):
+                raise FinitoError(FIN_EINVAL, "Colors.shared: weights has shape %s, the index has %d unitigs" % (w.shape, self.n_unitigs))
+            if self.n_unitigs == 0:
+                w = np.zeros(1, dtype=np.uint64)
+        out = np.zeros((self.n_colors, self.n_colors), dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_shared(self.h, cover.h if cover is not None else None, w.ctypes.data_as(C.c_void_p) if w is not None else None,
+                                        out.ctypes.data_as(C.c_void_p), err, 512), err)
+        return ColorShared(out)
+
 
 class EqClasses(_Accumulator):
     """the equivalence classes of pseudoaligned reads -- the distinct colour rows the added runs produced and how many reads have each --, accumulated in HBM
@@ -988,7 +1007,8 @@ class EqClasses(_Accumulator):
     def abundance(self, lengths=None, max_iters=1000, tol=1e-6, trace=False):
         """expected reads per colour by EM over the classes, on the device: an Abundance; waits for the adds and leaves the accumulator as it found it
         (fin_eqclasses_abundance).  lengths: one finite positive number per colour (None: all 1); trace: keep the log-likelihood of every iteration -- an
-        array given here is written in place, entries behind `iters` left alone"""
+        array given here is written in place, entries behind `iters` left alone.  References with the same column of the colour matrix
+        (Colors.shared().identical_groups()) are not identifiable: the EM splits their reads by its starting point, only the group's sum means something"""
         lens, mi, tol = _abundance_args("EqClasses.abundance", self.n_colors, lengths, max_iters, tol)
         alpha = np.zeros(self.n_colors, dtype=np.float64)
         tr = _abundance_trace("EqClasses.abundance", trace, mi)
@@ -1052,6 +1072,52 @@ class ColorCoverage:
     def mean_depth(self):
         """depth_sum / covered: the mean depth of the found k-mers; nan where none was found"""
         return self._ratio(self.depth_sum, self.covered)
+
+
+class ColorShared:
+    """what every pair of references shares (Colors.shared, unitig_color_shared): table uint64[n_colors, n_colors], table[i, j] = the sum of the unitigs' weights
+    over the unitigs that carry colour i and colour j -- symmetric; sizes is its diagonal.  With the default weights on a graph coloured by search, table[i, j] is
+    the number of distinct k-mers references i and j have in common.  The ratios are derived here, in float64; the groups and pairs from the integers, exactly"""
+
+    def __init__(self, table):
+        self.table = table
+        self.sizes = np.ascontiguousarray(np.diagonal(table))
+
+    @property
+    def jaccard(self):
+        """s_ij / (s_ii + s_jj - s_ij), float64[n_colors, n_colors]; nan where both references are empty"""
+        s, d = self.table.astype(np.float64), self.sizes.astype(np.float64)
+        den = d[:, None] + d[None, :] - s
+        out = np.full(s.shape, np.nan)
+        np.divide(s, den, out=out, where=den != 0)
+        return out
+
+    @property
+    def containment(self):
+        """[i, j] = s_ij / s_ii, the share of reference i that reference j has, float64[n_colors, n_colors]; row i is nan for an empty reference i"""
+        s, d = self.table.astype(np.float64), self.sizes.astype(np.float64)
+        out = np.full(s.shape, np.nan)
+        np.divide(s, d[:, None], out=out, where=(d != 0)[:, None])
+        return out
+
+    def identical_groups(self):
+        """the lists of two or more colours with s_ij == s_ii == s_jj > 0 -- the same column of the matrix, as far as the weights can see: no estimate downstream
+        can tell their members apart --, each ascending, each group once, by its first member"""
+        d, groups, seen = self.sizes, [], np.zeros(len(self.sizes), dtype=bool)
+        for i in range(len(d)):
+            if seen[i] or d[i] == 0:
+                continue
+            members = np.nonzero((self.table[i] == d[i]) & (d == d[i]))[0]
+            seen[members] = True
+            if len(members) >= 2:
+                groups.append([int(c) for c in members])
+        return groups
+
+    def contained(self):
+        """the pairs (i, j), i != j, with s_ij == s_ii > 0 and s_jj > s_ii: reference i lies in reference j and j has more; ascending"""
+        d = self.sizes
+        i, j = np.nonzero((self.table == d[:, None]) & (d[:, None] > 0) & (d[None, :] > d[:, None]))
+        return [(int(a), int(b)) for a, b in zip(i, j)]
 
 
 def _assign_args(what, n_colors, weights, thresholds):
@@ -2236,6 +2302,28 @@ def unitig_color_coverage(bits, n_colors, nk, covered=None, stats=None, n_thread
     if rc != 0:
         raise FinitoError(rc, "fin_unitig_color_coverage: a row with a bit at or above n_colors")
     return ColorCoverage(out[:nc], out[nc])
+
+
+def unitig_color_shared(bits, n_colors, v, n_threads=0):
+    """host: the ColorShared of a colour matrix uint64[n_unitigs, W] under the weights v uint64[n_unitigs] (fin_unitig_color_shared) -- the CPU statement of
+    Colors.shared; sums are mod 2^64 and the result does not depend on n_threads"""
+    nc = int(n_colors)
+    if not 1 <= nc <= FIN_MAX_COLORS:
+        raise FinitoError(FIN_ELIMIT, "unitig_color_shared: n_colors is 1 .. 4096")
+    W = (nc + 63) // 64
+    a = np.ascontiguousarray(bits, dtype=np.uint64).reshape(-1, W)
+    n = len(a)
+    if v is None:
+        raise FinitoError(FIN_EINVAL, "unitig_color_shared: v is needed")
+    v_ = np.ascontiguousarray(v, dtype=np.uint64)
+    if v_.shape != (n,):
+        raise FinitoError(FIN_EINVAL, "unitig_color_shared: v has shape %s, the matrix has %d unitigs" % (v_.shape, n))
+    out = np.zeros((nc, nc), dtype=np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    rc = lib().fin_unitig_color_shared(a.ctypes.data_as(u64p), n, nc, v_.ctypes.data_as(u64p), out.ctypes.data_as(u64p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_unitig_color_shared: a row with a bit at or above n_colors")
+    return ColorShared(out)
 
 
 def _u64(what, name, v):

@@ -98,7 +98,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_colcov_chunk, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_colcov_chunk, O_colsim_chunk, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -138,6 +138,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"ab_chunk", 0, 0, 1ll << 26},                 // fin_eqclasses_abundance's column pass: classes per chunk, rounded up to a multiple of 64 (fin_abundance.hip); 0 = auto: 256, more once that would make over 1024 chunks (which also bounds what a value can ask for).  The order of the column sums is a function of it, so two estimates compare bit for bit only under one value; tests set 64 so that small cases cross chunk seams
     {"assign_rpb", 0, 0, 1ll << 26},               // fin_assign_rows: rows per block of fin_assign_rows_kernel (fin_assign.hip); 0 = auto: 1024, more once that would make over 2048 blocks; never so few that there would be over 2^20 blocks.  The results do not depend on it; tests set 64 so that small cases cross block seams
     {"colcov_chunk", 0, 0, 1ll << 26},             // fin_colors_coverage: unitigs per chunk of fin_colcov_column_kernel (fin_colcov.hip), rounded up to a multiple of 64; 0 = auto: 1024, more once that would make over 8192 waves; never so few that there would be over 2^20 chunks.  The results do not depend on it; tests set 64 so that small cases cross chunk seams
+    {"colsim_chunk", 0, 0, 1ll << 26},             // fin_colors_shared: unitigs per chunk of fin_colsim_tile_kernel (fin_colsim.hip), rounded up to a multiple of 64; 0 = auto: 4096, more once that would make over 16384 waves; never so few that tiles x chunks would pass 2^30 blocks.  The results do not depend on it; tests set 64 so that small cases cross chunk seams
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -2988,6 +2989,38 @@ int fin_colors_coverage(fin_colors* c, fin_cover* cov, fin_depth* dep, uint32_t 
     HIPCHK(hipMemcpy(host.data(), d_out, table, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels)
     memcpy(out, host.data(), (size_t)c->n_colors * 64);
     if (uncolored) *uncolored = host[c->n_colors];
+    return FIN_OK;
+}
+
+// ---- shared k-mers between references (fin_colsim.hip) ---------------------------------------------------------------------------------------
+int fin_colors_shared(fin_colors* c, fin_cover* cov, const uint64_t* weights, uint64_t* out, char* err, size_t errlen) {
+    if (!c || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (cov && weights) { set_err(err, errlen, "a coverage bitmap and weights were both given: one weight per unitig and call"); return FIN_EINVAL; }
+    if (cov && (cov->idx != c->idx || cov->device != c->device)) { set_err(err, errlen, "colours and coverage bitmap belong to different indexes or devices"); return FIN_EINVAL; }
+    // the two waits, with the downloads' own codes and messages for a withheld step (nothing else happens in these calls)
+    if (const int rc = fin_colors_download(c, nullptr, nullptr, err, errlen)) return rc;
+    if (cov) if (const int rc = fin_cover_download(cov, nullptr, nullptr, nullptr, err, errlen)) return rc;
+    const fin_index::Replica* rep = c->idx->replica_on(c->device);
+    if (!rep) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    // the call's own buffers, freed on every way out: no result of an earlier call is there to be read
+    struct Buf { void* p = nullptr; ~Buf() { (void)hipFree(p); } } d_out, d_w;
+    const size_t table = (size_t)c->n_colors * c->n_colors * 8;
+    if (hipMalloc(&d_out.p, table) != hipSuccess) { (void)hipGetLastError(); d_out.p = nullptr; set_err(err, errlen, "out of device memory (shared k-mer table)"); return FIN_ENOMEM; }
+    const bool with_w = weights && c->n_unitigs, with_cov = cov && c->n_unitigs;
+    if (with_w) {
+        if (hipMalloc(&d_w.p, (size_t)c->n_unitigs * 8) != hipSuccess) { (void)hipGetLastError(); d_w.p = nullptr; set_err(err, errlen, "out of device memory (unitig weights)"); return FIN_ENOMEM; }
+        HIPCHK(hipMemcpy(d_w.p, weights, (size_t)c->n_unitigs * 8, hipMemcpyHostToDevice));
+    }
+    // covered[] stays on the device; everything below is on the null stream, and the lock keeps a download from counting in between
+    std::unique_lock<std::mutex> gc;
+    if (with_cov) {
+        gc = std::unique_lock<std::mutex>(cov->count_mu);
+        if (const int rc = cover_count(cov, err, errlen)) return rc;
+    }
+    const int rc = fin_launch_color_shared(c->d_bits, (uint32_t)c->n_unitigs, c->words, c->n_colors, rep->dev.ends, c->idx->total_len, rep->dev.k,
+                                           with_cov ? cov->d_covered : d_w.p, (uint32_t)optv(c->idx, O_colsim_chunk), (uint64_t*)d_out.p, nullptr);
+    if (rc != 0) { set_err(err, errlen, std::string("shared k-mer kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    HIPCHK(hipMemcpy(out, d_out.p, table, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels)
     return FIN_OK;
 }
 

@@ -23,6 +23,7 @@
 
 #include "fin_device.h"
 #include "fin_kernels.h"
+#include "fin_nk.h"
 #include "fin_wave.h"
 
 #define FIN_CCV_BLK 256u
@@ -32,11 +33,6 @@ typedef unsigned long long ull;
 
 __device__ __forceinline__ void ccv_add(ull* p, ull v) {
     if (v) (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// nk(u): ends_p[u + 1] is the exclusive end of unitig u; the last unitig ends at total_len
-__device__ __forceinline__ uint32_t ccv_nk(const uint32_t* ends_p, uint32_t u, uint32_t n_unitigs, uint64_t total_len, uint32_t k) {
-    const uint64_t s = ends_p[u], e = u + 1u < n_unitigs ? (uint64_t)ends_p[u + 1u] : total_len;
-    return e >= s + k ? (uint32_t)(e - s - k + 1u) : 0u;
 }
 }  // namespace
 
@@ -57,7 +53,7 @@ __global__ __launch_bounds__(256) void fin_colcov_class_kernel(const ull* bits, 
     if (__ballot(empty) == 0ull) return;   // wave-uniform
     ull v0 = 0, v1 = 0, v2 = 0, v3 = 0;
     if (empty) {
-        v0 = ccv_nk(ends_p, u, n_unitigs, total_len, k);
+        v0 = fin_unitig_nk(ends_p, u, n_unitigs, total_len, k);
         if (covered) v1 = covered[u];
         if (stats) { v2 = stats[u].sum; v3 = stats[u].n_at_least; }
     }
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(256) void fin_colcov_column_kernel(const ull* bits,
             ull cv = 0, sum = 0;
             if (word != 0ull) {
                 c = cls[u];
-                nk = ccv_nk(ends_p, u, n_unitigs, total_len, k);
+                nk = fin_unitig_nk(ends_p, u, n_unitigs, total_len, k);
                 if (covered) cv = covered[u];
                 if (stats) { sum = stats[u].sum; sol = stats[u].n_at_least; }
             }
@@ -107,7 +103,7 @@ __global__ __launch_bounds__(256) void fin_colcov_column_kernel(const ull* bits,
             const ull wd = bits[(uint64_t)u * W + w];
             if (wd == 0ull) continue;
             const bool only = cls[u] == 1u;
-            const ull b_nk = ccv_nk(ends_p, u, n_unitigs, total_len, k), b_cv = covered ? covered[u] : 0ull, b_sum = stats ? stats[u].sum : 0ull,
+            const ull b_nk = fin_unitig_nk(ends_p, u, n_unitigs, total_len, k), b_cv = covered ? covered[u] : 0ull, b_sum = stats ? stats[u].sum : 0ull,
                       b_sol = stats ? stats[u].n_at_least : 0u;
             if ((wd >> lane) & 1ull) {
                 a_k += b_nk; a_c += b_cv; a_s += b_sum; a_n += b_sol;

@@ -247,6 +247,12 @@ uint32_t fin_colcov_chunk(uint64_t n_unitigs, uint32_t W, uint32_t colcov_chunk)
 int fin_launch_color_coverage(const void* bits, uint32_t n_unitigs, uint32_t W, uint32_t n_colors, const uint32_t* ends_p, uint64_t total_len, uint32_t k,
                               const void* covered, const void* stats, void* cls, uint32_t colcov_chunk, uint32_t loads, uint64_t* out, uint64_t* none,
                               hipStream_t stream);
+// fin_colsim.hip -- the colour matrix times itself under a weight per unitig: out uint64[n_colors][n_colors], out[i][j] = the sum of v(u) over the
+// unitigs whose row has bits i and j, mod 2^64, the full symmetric matrix, zeroed on `stream` by the launcher.  vals uint64[n_unitigs], or null: nk(u) from
+// ends_p, total_len and k.  colsim_chunk: option "colsim_chunk"; fin_colsim_chunk: the unitigs a wave then takes
+uint32_t fin_colsim_chunk(uint64_t n_unitigs, uint32_t W, uint32_t colsim_chunk);
+int fin_launch_color_shared(const void* bits, uint32_t n_unitigs, uint32_t W, uint32_t n_colors, const uint32_t* ends_p, uint64_t total_len, uint32_t k,
+                            const void* vals, uint32_t colsim_chunk, uint64_t* out, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -512,6 +512,14 @@ static const char* SEARCH_HELP =
     "                        last chunk from a coverage bitmap and a depth kept there (those of --unitig-coverage / --unitig-depth when they are asked for\n"
     "                        too), at their cost: one more search of every chunk each. Coverage counts k-mers, so with --paired 1 mates need no pairing.\n"
     "                        Wants --color-refs; goes with --no-text 1, --abundance, --eqclasses, --assign-weights and --paired 1. Not for a partitioned index.\n"
+    "      --color-similarity FILE  also write what the references of --color-refs share, integers only: one line\n"
+    "                        `colour_a<TAB>colour_b<TAB>size_a<TAB>size_b<TAB>shared` per pair a < b with shared > 0, ascending -- the k-mers of the unitigs that\n"
+    "                        carry a, that carry b, and that carry both --, then one line `identical<TAB>c1,c2,...` per group of references with the same\n"
+    "                        column of the colour matrix (no estimate can tell its members apart). The colour matrix times itself on the first GPU, right\n"
+    "                        after the colouring. Wants --color-refs; goes with everything --color-coverage goes with.\n"
+    "      --color-similarity-covered FILE2  the same over the k-mers the run found: sizes and shared count found k-mers only. Made after the last chunk\n"
+    "                        from a coverage bitmap kept on the first GPU (that of --unitig-coverage / --color-coverage when they are asked for too), at its\n"
+    "                        cost: one more search of every chunk. Wants --color-similarity.\n"
     "      --pseudoalign FILE  also write one line per read, in input order: `read<TAB>k-mers<TAB>found<TAB>coloured<TAB>c1,c2,...` -- `read` and k-mers as\n"
     "                        in --read-summary, found = the k-mers found, coloured = those of them in a unitig with a colour, then the colours that at\n"
     "                        least P thousandths of the coloured k-mers have (`-` for none). Made on the first GPU from one more search of every chunk;\n"
@@ -1326,17 +1334,48 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
     return number_of_queries;
 }
 
+// --color-similarity / --color-similarity-covered: the colour matrix times itself on the first GPU (fin_colors_shared), over the unitigs' k-mers (cov null) or the
+// found k-mers of a bitmap -- `a<TAB>b<TAB>size_a<TAB>size_b<TAB>shared` per pair a < b that shares anything, then `identical<TAB>c1,c2,...` per group of equal columns
+static void write_color_similarity(const string& path, fin_cover* cov, size_t nc) {
+    char err[512] = {0};
+    vector<uint64_t> s(nc * nc + 1);
+    if (fin_colors_shared(g_colors, cov, nullptr, s.data(), err, sizeof err) != FIN_OK) throw runtime_error(err);
+    string text;
+    for (size_t a = 0; a < nc; a++)
+        for (size_t b = a + 1; b < nc; b++) {
+            if (s[a * nc + b] == 0) continue;
+            text += to_string(a); text += '\t'; text += to_string(b);
+            for (uint64_t v : {s[a * nc + a], s[b * nc + b], s[a * nc + b]}) { text += '\t'; text += to_string(v); }
+            text += '\n';
+        }
+    vector<char> seen(nc, 0);
+    for (size_t a = 0; a < nc; a++) {
+        const uint64_t d = s[a * nc + a];
+        if (seen[a] || d == 0) continue;
+        string line = "identical\t" + to_string(a);
+        size_t members = 1;
+        for (size_t b = a + 1; b < nc; b++)
+            if (s[a * nc + b] == d && s[b * nc + b] == d) { seen[b] = 1; members++; line += ','; line += to_string(b); }
+        if (members >= 2) { text += line; text += '\n'; }
+    }
+    ofstream cf(path, ios::binary | ios::trunc);
+    cf.write(text.data(), (streamsize)text.size());
+    if (!cf) throw runtime_error("Error writing to file: " + path);
+}
+
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "color-similarity", "color-similarity-covered", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage"))
+    if (o.has("color-similarity-covered") && !o.has("color-similarity")) throw runtime_error("--color-similarity-covered is only legal together with --color-similarity");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity"))
         throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
     if (o.has("color-coverage") && !o.has("color-refs")) throw runtime_error("--color-coverage wants colours: --color-refs LIST");
+    if ((o.has("color-similarity") || o.has("color-similarity-covered")) && !o.has("color-refs")) throw runtime_error("--color-similarity and --color-similarity-covered want colours: --color-refs LIST");
     g_paired = o.has("paired") && o.get("paired") != "0" && o.get("paired") != "false";
     const bool pair_both = o.has("pair-both") && o.get("pair-both") != "0" && o.get("pair-both") != "false";
     if (g_paired && !o.has("color-refs")) throw runtime_error("--paired 1 wants colours: --color-refs LIST (fragments are what --pseudoalign, --eqclasses, --color-report and --abundance then take)");
@@ -1348,7 +1387,7 @@ static int search_fmin(int argc, char** argv) {
     if (asg_asked && !o.has("assign") && !o.has("assign-report")) throw runtime_error("--assign-weights wants a result: --assign FILE and / or --assign-report FILE");
     for (const char* name : {"assign", "assign-report", "assign-threshold"})
         if (o.has(name) && !asg_asked) throw runtime_error(string("--") + name + " is only legal together with --assign-weights");
-    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked && !o.has("color-coverage")) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
+    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked && !o.has("color-coverage") && !o.has("color-similarity")) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
     if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked && !asg_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
     if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses, --color-report or --abundance");
     if (o.has("eqclasses-in") && !eq_asked) throw runtime_error("--eqclasses-in is only legal together with --eqclasses, --color-report or --abundance");
@@ -1460,6 +1499,9 @@ static int search_fmin(int argc, char** argv) {
     if (!depth_file.empty()) check_writable(depth_file);
     const string colcov_file = o.get("color-coverage", "");
     if (!colcov_file.empty()) check_writable(colcov_file);
+    const string colsim_file = o.get("color-similarity", ""), colsim_cov_file = o.get("color-similarity-covered", "");
+    if (!colsim_file.empty()) check_writable(colsim_file);
+    if (!colsim_cov_file.empty()) check_writable(colsim_cov_file);
     const string pileup_file = o.get("pileup", ""), variants_file = o.get("variants", "");
     if (!pileup_file.empty()) check_writable(pileup_file);
     if (!variants_file.empty()) check_writable(variants_file);
@@ -1562,7 +1604,7 @@ static int search_fmin(int argc, char** argv) {
         if (fin_hits_create(index.handle(), first_dev, &g_hits, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     struct CoverOwner { ~CoverOwner() { fin_cover_free(g_cover); g_cover = nullptr; } } cover_owner;
-    if (!cover_file.empty() || !colcov_file.empty()) {   // (--color-coverage shares the bitmap and the depth of --unitig-coverage / --unitig-depth)
+    if (!cover_file.empty() || !colcov_file.empty() || !colsim_cov_file.empty()) {   // (--color-coverage and --color-similarity-covered share the bitmap and the depth of --unitig-coverage / --unitig-depth)
         char err[512] = {0};
         if (fin_cover_create(index.handle(), first_dev, &g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
@@ -1625,6 +1667,7 @@ static int search_fmin(int argc, char** argv) {
             cf.write(text.data(), (streamsize)text.size());
             if (!cf) throw runtime_error("Error writing to file: " + colors_file);
         }
+        if (!colsim_file.empty()) write_color_similarity(colsim_file, nullptr, color_refs.size());   // (what the references share in the graph, before any read)
         if (!psa_file.empty()) {
             g_psa_file = fopen(psa_file.c_str(), "wb");
             if (!g_psa_file) throw runtime_error("Error writing to file: " + psa_file);
@@ -1853,6 +1896,7 @@ static int search_fmin(int argc, char** argv) {
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + colcov_file);
     }
+    if (!colsim_cov_file.empty()) write_color_similarity(colsim_cov_file, g_cover, color_refs.size());   // ... and in what the run found, after the last chunk
     if (g_pileup) {   // the pileup, after the last chunk: the covered positions, and the candidates called on the device
         char err[512] = {0};
         const size_t nu = (size_t)index.number_of_unitigs();

@@ -1161,6 +1161,28 @@ int fin_colors_coverage(fin_colors* c, fin_cover* cov /* may be NULL */, fin_dep
 int fin_unitig_color_coverage(const uint64_t* bits, uint64_t n_unitigs, uint32_t n_colors, const uint64_t* nk, const uint64_t* covered /* may be NULL */,
                               const fin_depth_stat* stats /* may be NULL */, fin_color_coverage* out, fin_color_coverage* uncolored, int n_threads);
 
+/* ---- SHARED K-MERS BETWEEN REFERENCES: the colour matrix times itself, on the device ----
+ * How the references relate to each other: two references with the same column of the colour matrix cannot be told apart by anything downstream, one contained
+ * in another has no k-mer of its own.  For a weight v(u) per unitig, exact 64-bit integers:
+ *   shared[i][j] = the sum of v(u) over the unitigs u whose row R(u) holds colour i and colour j,   0 <= i, j < n_colors
+ * returned as the full symmetric uint64[n_colors][n_colors], row stride n_colors; the diagonal shared[i][i] is the sum of v(u) over the unitigs that carry i.
+ * Exactly one v per call:
+ *   cov NULL, weights NULL   v(u) = nk(u) = len(u) - k + 1: the diagonal is fin_colors_coverage's kmers[], and on a graph coloured by search shared[i][j] is the
+ *                            number of distinct k-mers references i and j have in common
+ *   cov given                v(u) = covered[u] of that bitmap, made on the device as fin_cover_download makes it: the diagonal is fin_colors_coverage's covered[],
+ *                            shared[i][j] the k-mers the sample found that i and j share
+ *   weights given            v(u) = weights[u], a host uint64[n_unitigs] uploaded for the call (unitig counts, depth sums, 1 for "shared unitigs")
+ * SUMS ARE MOD 2^64.  With nk or covered they cannot overflow (the text has fewer than 2^32 bases); with weights of the caller's they can, silently.
+ * A waiting call, like fin_colors_coverage: it waits for every add and reset issued so far to c and to cov, changes neither, and copies 8 n_colors^2 bytes back.
+ * FIN_EINVAL for a NULL c or out, for cov and weights both given, and for a cov of another index or device; the codes and messages of fin_colors_download and
+ * fin_cover_download for a withheld step are passed on; FIN_ENOMEM when HBM lacks the 8 n_colors^2 bytes of the result (128 MB at 4096 colours) or the 8 bytes
+ * per unitig of the weights.  On every error nothing is written to out. */
+int fin_colors_shared(fin_colors* c, fin_cover* cov /* may be NULL */, const uint64_t* weights /* host, may be NULL */, uint64_t* out /* [n_colors * n_colors] */,
+                      char* err, size_t errlen);
+/* host twin, no device: bits uint64[n_unitigs][W], v uint64[n_unitigs]; out as above, sums mod 2^64.  Threads take ranges of unitigs and their tables are added
+ * at the end: the result does not depend on n_threads.  FIN_EINVAL for a bit at or above n_colors, FIN_ELIMIT for n_colors outside 1 .. 4096 */
+int fin_unitig_color_shared(const uint64_t* bits, uint64_t n_unitigs, uint32_t n_colors, const uint64_t* v, uint64_t* out, int n_threads);
+
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
  * k-mer is in no unitig), 1 a verified claim, 2 an unverified one (| 8: the exact side table has the k-mer, g is its answer), | 4 the text at [g-k+1, g] spells
