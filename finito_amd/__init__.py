@@ -243,6 +243,25 @@ def lib():
         L.fin_search_batch_add_classes.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, u32, cp, C.c_size_t]
         L.fin_records_read_classes.argtypes = [vp, u64, vp, u64, C.c_int, vp, u64, vp, C.c_int]
         L.fin_index_unitig_numbers.argtypes = [vp, cp, u64p, u64, vp, cp, C.c_size_t]
+        L.fin_taxonomy_create.argtypes = [vp, C.c_int, vp, u64, vp, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_taxonomy_create_from_colors.argtypes = [vp, vp, u64, vp, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_taxonomy_device_labels.argtypes = [vp]
+        L.fin_taxonomy_device_labels.restype = vp
+        L.fin_taxonomy_download_labels.argtypes = [vp, vp, cp, C.c_size_t]
+        L.fin_taxonomy_reset.argtypes = [vp, vp]
+        L.fin_taxonomy_download.argtypes = [vp, u64p, u64p, u64p, cp, C.c_size_t]
+        L.fin_taxonomy_free.argtypes = [vp]
+        L.fin_taxonomy_free.restype = None
+        L.fin_batch_taxa.argtypes = [vp, vp, u32, u32, cp, C.c_size_t]
+        L.fin_batch_device_read_taxa.argtypes = [vp]
+        L.fin_batch_device_read_taxa.restype = vp
+        L.fin_batch_download_read_taxa.argtypes = [vp, vp, cp, C.c_size_t]
+        L.fin_batch_add_taxa.argtypes = [vp, vp, u32, u32, vp, cp, C.c_size_t]
+        L.fin_search_batch_taxa.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, vp, u64p, cp, C.c_size_t]
+        L.fin_search_batch_add_taxa.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, cp, C.c_size_t]
+        L.fin_unitig_lca_labels.argtypes = [u64p, u64, u32, vp, u64, vp, vp, C.c_int]
+        L.fin_records_read_taxa.argtypes = [vp, u64, vp, u64, C.c_int, vp, u64, vp, u64, u32, u32, vp, C.c_int]
+        L.fin_taxa_clade_reads.argtypes = [u64p, vp, u64, u64p]
         L.fin_colors_create.argtypes = [vp, C.c_int, u32, C.POINTER(vp), cp, C.c_size_t]
         L.fin_colors_upload.argtypes = [vp, u64p, cp, C.c_size_t]
         L.fin_colors_reset.argtypes = [vp, vp]
@@ -543,6 +562,21 @@ class Batch:
         _check(self.L.fin_batch_download_read_classes(self.h, out.ctypes.data_as(C.c_void_p), err, 512), err)
         return out[: self.n_reads]
 
+    def taxa(self, tax, min_found=1, confidence=0):
+        """the most recent run's results as one taxon per read under a Taxonomy, by Kraken's root-to-leaf rule, made on the device (fin_batch_taxa +
+        fin_batch_download_read_taxa): READ_TAXON_DTYPE[n_reads] -- taxon (FIN_NO_LABEL: unclassified), score, clade, n_labelled.  confidence is in thousandths
+        of the read's k-mers, 0 .. 1000"""
+        t = _taxa_thresholds("Batch.taxa", min_found, confidence)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_batch_taxa(self.h, tax.h, *t, err, 512), err)
+        out = np.zeros(max(self.n_reads, 1), dtype=READ_TAXON_DTYPE)
+        _check(self.L.fin_batch_download_read_taxa(self.h, out.ctypes.data_as(C.c_void_p), err, 512), err)
+        return out[: self.n_reads]
+
+    def device_read_taxa_ptr(self):
+        """the read taxa's device pointer, 0 before taxa() / Taxonomy.add()"""
+        return int(self.L.fin_batch_device_read_taxa(self.h) or 0)
+
     def device_read_classes_ptr(self):
         """the classes' device pointer, 0 before classify() / Labels.add()"""
         return int(self.L.fin_batch_device_read_classes(self.h) or 0)
@@ -804,6 +838,96 @@ class Labels(_Accumulator):
         return int(self.L.fin_labels_device_labels(self.h) or 0), int(self.L.fin_labels_device_reads(self.h) or 0)
 
 
+def _taxa_thresholds(what, min_found, confidence):
+    if not all(0 <= int(v) <= 0xFFFFFFFF for v in (min_found, confidence)):
+        raise FinitoError(FIN_EINVAL, what + ": min_found and confidence are unsigned 32-bit numbers")
+    return int(min_found), int(confidence)
+
+
+def _taxa_parent(what, parent):
+    p = np.asarray(parent)
+    if p.ndim != 1 or len(p) == 0 or p.dtype.kind not in "iu" or int(p.min()) < 0 or int(p.max()) > 0xFFFFFFFF:
+        raise FinitoError(FIN_EINVAL, what + ": parent is one unsigned 32-bit number per taxon, taxon 0 the root")
+    return np.ascontiguousarray(p, dtype=np.uint32)
+
+
+class Taxonomy(_Accumulator):
+    """a tree over taxa (parent[n_taxa] in topological numbering: parent[0] == 0, parent[t] < t; taxonomy_order makes it from arbitrary ids) with a taxon per
+    unitig of the index, resident in HBM beside one replica, and the tally of the reads called at each taxon (fin_taxonomy_* of the C ABI).
+    Made by FinimizerIndex.taxonomy from labels of the caller's, or by Colors.taxonomy from the colour matrix: a unitig's taxon is the LCA of its colours' taxa."""
+    _FREE, _RESET = "fin_taxonomy_free", "fin_taxonomy_reset"
+
+    def __init__(self, index, parent, unitig_labels=None, device=0, colors=None, color_taxon=None):
+        self.index = index
+        self.parent = _taxa_parent("taxonomy", parent)
+        self.n_taxa = len(self.parent)
+        self.color_taxon = None
+        if colors is not None:
+            ct = np.asarray(color_taxon)
+            if ct.shape != (colors.n_colors,) or ct.dtype.kind not in "iu" or (len(ct) and (int(ct.min()) < 0 or int(ct.max()) > 0xFFFFFFFF)):
+                raise FinitoError(FIN_EINVAL, "taxonomy: one taxon per colour (%d), got %s" % (colors.n_colors, ct.shape))
+            ct = np.ascontiguousarray(ct, dtype=np.uint32)
+            self.device = colors.device
+            self._create("fin_taxonomy_create_from_colors", colors.h, self.parent.ctypes.data_as(C.c_void_p), self.n_taxa, ct.ctypes.data_as(C.c_void_p))
+            self.color_taxon = ct   # (accepted: each is below n_taxa)
+            return
+        lab = np.asarray(unitig_labels)
+        if lab.ndim != 1 or len(lab) != index.n_unitigs:
+            raise FinitoError(FIN_EINVAL, "taxonomy: one label per unitig of the index (%d), got %s" % (index.n_unitigs, lab.shape))
+        if len(lab) and (lab.dtype.kind not in "iu" or int(lab.min()) < 0 or int(lab.max()) > FIN_NO_LABEL):
+            raise FinitoError(FIN_EINVAL, "taxonomy: labels are unsigned 32-bit numbers, FIN_NO_LABEL for none")
+        lab = np.ascontiguousarray(lab, dtype=np.uint32)
+        self.device = int(device)
+        self._create("fin_taxonomy_create", index.h, self.device, self.parent.ctypes.data_as(C.c_void_p), self.n_taxa, lab.ctypes.data_as(C.c_void_p))
+
+    def labels(self):
+        """uint32 label[n_unitigs]: every unitig's taxon, FIN_NO_LABEL for none (fin_taxonomy_download_labels)"""
+        out = np.zeros(max(self.index.n_unitigs, 1), dtype=np.uint32)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_taxonomy_download_labels(self.h, out.ctypes.data_as(C.c_void_p), err, 512), err)
+        return out[: self.index.n_unitigs]
+
+    def as_labels(self):
+        """the same labelling as a Labels with n_labels = n_taxa: the majority vote (Batch.classify) runs on it as it is.  A copy through the host: the labels
+        are downloaded and uploaded again into the new Labels (4 bytes per unitig each way, once)"""
+        return Labels(self.index, self.labels(), self.n_taxa, self.device)
+
+    def add(self, batch, min_found=1, confidence=0, stream=None):
+        """tally += the reads of the batch's most recent run, each at the taxon Batch.taxa gives it under these thresholds, unclassified ones apart; on a HIP
+        stream, behind that run (fin_batch_add_taxa).  Adding twice counts twice."""
+        return _acc_add(self, "fin_batch_add_taxa", batch, stream, *_taxa_thresholds("Taxonomy.add", min_found, confidence))
+
+    def add_reads(self, reads, min_found=1, confidence=0, strands=FIN_MERGED):
+        """search a read set from host buffers, sub-batches pipelined as in search_reads, and tally its reads; nothing comes back (fin_search_batch_add_taxa)"""
+        return _acc_add_reads(self, "fin_search_batch_add_taxa", reads, strands, *_taxa_thresholds("Taxonomy.add_reads", min_found, confidence))
+
+    def download(self):
+        """(direct uint64[n_taxa] -- the reads called at each taxon --, clade uint64[n_taxa] -- the reads called at or below it, rolled up on the device --,
+        unclassified); clade[0] + unclassified = the reads added.  Waits for the adds (fin_taxonomy_download)"""
+        direct = np.zeros(self.n_taxa + 1, dtype=np.uint64)
+        clade = np.zeros(self.n_taxa, dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_taxonomy_download(self.h, direct.ctypes.data_as(C.POINTER(C.c_uint64)), clade.ctypes.data_as(C.POINTER(C.c_uint64)), None, err, 512), err)
+        return direct[: self.n_taxa], clade, int(direct[self.n_taxa])
+
+    def rollup(self, values_per_colour):
+        """host only, float64: out[t] = the sum of values_per_colour[c] over the colours c whose taxon is t or below it -- Abundance.alpha summed into clades.
+        A fixed order: the colours ascending into their taxa, then the taxa descending into their parents.  For a taxonomy made from colours"""
+        v = np.asarray(values_per_colour, dtype=np.float64)
+        ct = self.color_taxon
+        if ct is None or v.shape != ct.shape:
+            raise FinitoError(FIN_EINVAL, "Taxonomy.rollup: one value per colour of the colour matrix this taxonomy was made from")
+        out = np.zeros(self.n_taxa, dtype=np.float64)
+        for c in range(len(v)):
+            out[int(ct[c])] += v[c]
+        for t in range(self.n_taxa - 1, 0, -1):
+            out[int(self.parent[t])] += out[t]
+        return out
+
+    def device_labels_ptr(self):
+        return int(self.L.fin_taxonomy_device_labels(self.h) or 0)
+
+
 def _permille(what, permille):
     if not 0 <= int(permille) <= 0xFFFFFFFF:
         raise FinitoError(FIN_EINVAL, what + ": permille is an unsigned 32-bit number")
@@ -866,6 +990,11 @@ class Colors(_Accumulator):
     def eqclasses(self, max_classes=1 << 20):
         """an accumulator of equivalence classes beside this matrix (EqClasses)"""
         return EqClasses(self, max_classes)
+
+    def taxonomy(self, parent, color_taxon):
+        """a Taxonomy beside this matrix whose unitig labels are the LCA of their colours' taxa, made on the device (fin_taxonomy_create_from_colors): parent in
+        topological numbering, color_taxon one taxon per colour.  Waits for the adds to the matrix; later adds do not change the labels"""
+        return Taxonomy(self.index, parent, colors=self, color_taxon=color_taxon)
 
     def assigner(self, weights, thresholds=0.5):
         """an accumulator that assigns reads to references beside this matrix (Assign): weights one per colour, usually Abundance.weights(); thresholds one per
@@ -1753,6 +1882,20 @@ class FinimizerIndex:
                                                 out.ctypes.data_as(C.c_void_p), None, err, 512), err)
         return out[:n]
 
+    def taxonomy(self, parent, unitig_labels, device=0):
+        """a Taxonomy of this index beside the replica on `device` from a labelling the caller brings: a taxon (or FIN_NO_LABEL) per unitig"""
+        return Taxonomy(self, parent, unitig_labels, device)
+
+    def taxa_reads(self, reads, tax, min_found=1, confidence=0, strands=FIN_MERGED):
+        """fin_search_batch_taxa: READ_TAXON_DTYPE[n_reads] from host buffers -- 16 bytes per read come back, nothing per k-mer"""
+        t = _taxa_thresholds("taxa_reads", min_found, confidence)
+        bases, offsets = flatten(reads)
+        n = len(offsets) - 1
+        out = np.zeros(max(n, 1), dtype=READ_TAXON_DTYPE)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_taxa(self.h, *_reads_args((bases, offsets)), int(strands), tax.h, *t, out.ctypes.data_as(C.c_void_p), None, err, 512), err)
+        return out[:n]
+
     def colors(self, n_colors, bits=None, device=0):
         """a colour matrix of this index on `device` (Colors), zeroed or holding `bits`"""
         c = Colors(self, n_colors, device)
@@ -1902,6 +2045,7 @@ SEGMENT_DTYPE = np.dtype([("u", np.int32), ("off", np.int32), ("slot", np.uint32
 READ_SUMMARY_DTYPE = np.dtype([("n_found", np.uint32), ("n_segments", np.uint32), ("longest", np.uint32), ("span", np.uint32)])   # fin_read_summary
 READ_CLASS_DTYPE = np.dtype([("label", np.uint32), ("n_best", np.uint32), ("n_second", np.uint32), ("n_labelled", np.uint32)])   # fin_read_class
 FIN_NO_LABEL = 0xFFFFFFFF
+READ_TAXON_DTYPE = np.dtype([("taxon", np.uint32), ("score", np.uint32), ("clade", np.uint32), ("n_labelled", np.uint32)])   # fin_read_taxon
 READ_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), ("n_colors", np.uint32), ("reserved", np.uint32)])   # fin_read_pseudo
 PAIR_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), ("n_colors", np.uint32), ("n_colored_first", np.uint32)])   # fin_pair_pseudo
 FIN_PAIR_ANY, FIN_PAIR_BOTH = 0, 1
@@ -2194,6 +2338,96 @@ def records_read_classes(recs, stream, k, unitig_labels, n_threads=0):
         raise FinitoError(rc, "fin_records_read_classes: a unitig number outside the labelling, records and stream that do not belong together, or a pair that is "
                               "neither found nor (-1,-1)")
     return out[: len(recs)]
+
+
+def unitig_lca_labels(bits, n_colors, parent, color_taxon, n_threads=0):
+    """fin_unitig_lca_labels (host): uint32 label[n_unitigs] from the colour matrix bits[n_unitigs, W] -- the LCA of the taxa of each row's colours, FIN_NO_LABEL
+    for an empty row -- the CPU statement of Colors.taxonomy"""
+    W = (int(n_colors) + 63) // 64 if 0 < int(n_colors) <= FIN_MAX_COLORS else 1
+    b = np.ascontiguousarray(bits, dtype=np.uint64).reshape(-1, W)
+    p = _taxa_parent("unitig_lca_labels", parent)
+    ct = np.ascontiguousarray(color_taxon, dtype=np.uint32)
+    if len(ct) != int(n_colors):
+        raise FinitoError(FIN_EINVAL, "unitig_lca_labels: one taxon per colour")
+    out = np.zeros(max(len(b), 1), dtype=np.uint32)
+    rc = lib().fin_unitig_lca_labels(b.ctypes.data_as(C.POINTER(C.c_uint64)), len(b), int(n_colors), p.ctypes.data_as(C.c_void_p), len(p),
+                                     ct.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_unitig_lca_labels: a parent that breaks the topological numbering, a colour's taxon outside the tree, a bit at or above "
+                              "n_colors, or n_colors outside 1 .. 4096")
+    return out[: len(b)]
+
+
+def records_read_taxa(recs, stream, k, unitig_labels, parent, min_found=1, confidence=0, n_threads=0):
+    """fin_records_read_taxa (host): READ_TAXON_DTYPE[n_reads] from records + stream under unitig_labels and the tree `parent`, written from the definitions -- the
+    CPU statement of Batch.taxa"""
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE); stream = np.ascontiguousarray(stream, dtype=np.int32)
+    lab = np.ascontiguousarray(unitig_labels, dtype=np.uint32)
+    p = _taxa_parent("records_read_taxa", parent)
+    t = _taxa_thresholds("records_read_taxa", min_found, confidence)
+    out = np.zeros(max(len(recs), 1), dtype=READ_TAXON_DTYPE)
+    rc = lib().fin_records_read_taxa(recs.ctypes.data_as(C.c_void_p), len(recs), stream.ctypes.data_as(C.c_void_p), len(stream.reshape(-1, 2)), int(k),
+                                     lab.ctypes.data_as(C.c_void_p), len(lab), p.ctypes.data_as(C.c_void_p), len(p), *t, out.ctypes.data_as(C.c_void_p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_read_taxa: a bad taxonomy, label or confidence, a unitig number outside the labelling, records and stream that do not "
+                              "belong together, or a pair that is neither found nor (-1,-1)")
+    return out[: len(recs)]
+
+
+def taxa_clade_reads(direct, parent):
+    """fin_taxa_clade_reads (host): uint64 clade[n_taxa] -- direct[t] summed over every taxon's subtree -- the CPU statement of Taxonomy.download's roll-up"""
+    p = _taxa_parent("taxa_clade_reads", parent)
+    d = np.ascontiguousarray(direct, dtype=np.uint64)
+    if len(d) < len(p):
+        raise FinitoError(FIN_EINVAL, "taxa_clade_reads: one count per taxon")
+    out = np.zeros(len(p), dtype=np.uint64)
+    rc = lib().fin_taxa_clade_reads(d.ctypes.data_as(C.POINTER(C.c_uint64)), p.ctypes.data_as(C.c_void_p), len(p), out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc != 0:
+        raise FinitoError(rc, "fin_taxa_clade_reads: a parent that breaks the topological numbering")
+    return out
+
+
+def taxonomy_order(ids, parent_ids):
+    """arbitrary integer taxon ids (NCBI nodes.dmp's first two columns, say) into the topological numbering a Taxonomy takes: (order, parent) with order[i] = the
+    new number of ids[i] and parent uint32[n] in the new numbers -- the root is 0 and its own parent, every other parent is below its child.  The root is the one
+    node that is its own parent.  Children are numbered breadth-first, siblings in input order.  ValueError for a repeated id, an unknown parent, no root or more
+    than one, and a cycle (nodes the root does not reach)"""
+    ids = [int(x) for x in ids]
+    pids = [int(x) for x in parent_ids]
+    if len(ids) != len(pids) or not ids:
+        raise ValueError("taxonomy_order: one parent id per id, at least one")
+    at = {}
+    for i, x in enumerate(ids):
+        if x in at:
+            raise ValueError("taxonomy_order: id %d is given twice (entries %d and %d)" % (x, at[x], i))
+        at[x] = i
+    kids = [[] for _ in ids]
+    roots = []
+    for i, (x, p) in enumerate(zip(ids, pids)):
+        if p == x:
+            roots.append(i)
+        elif p not in at:
+            raise ValueError("taxonomy_order: entry %d: id %d has the unknown parent %d" % (i, x, p))
+        else:
+            kids[at[p]].append(i)
+    if len(roots) != 1:
+        raise ValueError("taxonomy_order: %s" % ("no root (a node that is its own parent)" if not roots else
+                                                 "more than one root: ids %d and %d are their own parents" % (ids[roots[0]], ids[roots[1]])))
+    order = np.full(len(ids), -1, dtype=np.int64)
+    parent = np.zeros(len(ids), dtype=np.uint32)
+    queue = [roots[0]]
+    order[roots[0]] = 0
+    n = 1
+    for i in queue:   # (grows while it is walked)
+        for c in kids[i]:
+            order[c] = n
+            parent[n] = order[i]
+            n += 1
+            queue.append(c)
+    if n != len(ids):
+        bad = int(np.flatnonzero(order < 0)[0])
+        raise ValueError("taxonomy_order: a cycle: id %d (entry %d) never reaches the root" % (ids[bad], bad))
+    return order, parent
 
 
 def records_pseudoalign(recs, stream, k, bits, n_colors, permille=1000, n_threads=0):

@@ -26,6 +26,7 @@
 #include "fin_bootrng.h"
 #include "fin_host.h"
 #include "fin_kernels.h"
+#include "fin_taxa.h"
 
 static void set_err(char* err, size_t errlen, const std::string& msg) {
     if (err && errlen) { snprintf(err, errlen, "%s", msg.c_str()); }
@@ -781,6 +782,8 @@ struct fin_batch {
     size_t cap_rsum = 0, cap_scr_bits = 0, cap_scr_ids = 0, cap_scr_bsum = 0, cap_scr_boff = 0; uint64_t n_pass = 0; bool rsum_ready = false, scr_ready = false;
     // per-read classes under a labelling (fin_batch_classify): kept and only grown; cls_labels = the serial number of the labelling they were made for
     void* d_cls = nullptr; size_t cap_cls = 0; bool cls_ready = false; uint64_t cls_labels = 0;
+    // per-read taxa under a taxonomy (fin_batch_taxa): kept and only grown; made for the taxonomy with serial tax_serial under these two thresholds
+    void* d_tax = nullptr; size_t cap_tax = 0; bool tax_ready = false; uint64_t tax_serial = 0; uint32_t tax_min_found = 0, tax_conf = 0;
     // per-read colour rows and heads under a colour matrix (fin_batch_pseudoalign): kept and only grown; psa_words = the matrix's words per row
     void* d_psa_rows = nullptr; size_t cap_psa_rows = 0; void* d_psa_heads = nullptr; size_t cap_psa_heads = 0; bool psa_ready = false; uint32_t psa_words = 0;
     // per-fragment colour rows and heads (fin_batch_pseudoalign_paired): buffers of their own, kept and only grown; forgotten whenever the per-read rows are
@@ -826,7 +829,7 @@ void fin_batch_free(fin_batch* b) {
     if (b->ev_ctr) (void)hipEventDestroy(b->ev_ctr);
     (void)hipFree(b->d_cstream); (void)hipFree(b->d_frec); (void)hipFree(b->d_seg); (void)hipFree(b->d_text); (void)hipFree(b->d_last_bits); (void)hipFree(b->d_blk_sum); (void)hipFree(b->d_blk_off); (void)hipFree(b->d_total);
     (void)hipFree(b->d_sgm_cnt); (void)hipFree(b->d_sgm_bsum); (void)hipFree(b->d_sgm_boff); (void)hipFree(b->d_sgm_offs); (void)hipFree(b->d_sgm);
-    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls); (void)hipFree(b->d_psa_rows); (void)hipFree(b->d_psa_heads); (void)hipFree(b->d_pair_rows); (void)hipFree(b->d_pair_heads);
+    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls); (void)hipFree(b->d_tax); (void)hipFree(b->d_psa_rows); (void)hipFree(b->d_psa_heads); (void)hipFree(b->d_pair_rows); (void)hipFree(b->d_pair_heads);
     (void)hipFree(b->d_asg_rows); (void)hipFree(b->d_asg_heads); (void)hipFree(b->d_bin_bits); (void)hipFree(b->d_bin_ids); (void)hipFree(b->d_bin_bsum); (void)hipFree(b->d_bin_boff);
     (void)hipFree(b->d_ovf_list); (void)hipFree(b->d_ovf_count); (void)hipFree(b->d_ovf_scratch); (void)hipFree(b->d_count);
     for (auto& r : b->runs) for (auto& e : r.e) (void)hipEventDestroy(e);
@@ -951,7 +954,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     //  decoding, inside its timed region, search_fmin.hh:46-71 -- is the first kernel of every step, see fin_batch_run)
     b->n_chunks = n_chunks; b->max_read_len = max_len;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "upload");
-    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
+    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
     b->rounds_hint = 0; b->ctr_pending = false;   // (new reads: nothing is known about the rounds they need)
     b->text_reads_state = 0;
     return FIN_OK;
@@ -995,7 +998,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     b->dev.budget_mult = (uint32_t)optv(b->idx, O_epoch_budget_mult); b->dev.budget_add = (uint32_t)optv(b->idx, O_epoch_budget_add);
     b->dev.ovf_cap = (uint32_t)std::min<uint64_t>(b->cap_ovf_list / 4, 0xFFFFFFFFull);
     if (const int64_t forced = optv(b->idx, O_debug_ovf_cap)) b->dev.ovf_cap = (uint32_t)std::min<int64_t>(forced, (int64_t)b->dev.ovf_cap);   // (tests: a tiny list)
-    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
+    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
     b->dev.pp_seg = (uint32_t)optv(b->idx, O_debug_pp_seg);
     b->dev.pp_max_len = (uint32_t)std::min<uint64_t>(b->max_read_len, 0xFFFFFFFFull);
     b->dev.pp_park = (uint32_t)optv(b->idx, O_pp_park);
@@ -1131,7 +1134,7 @@ int fin_batch_set_pairs(fin_batch* b, const int32_t* pairs, char* err, size_t er
     HIPCHK(hipSetDevice(b->device));
     if (b->last_stream) HIPCHK(hipStreamSynchronize(b->last_stream));
     HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
-    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;   // (the records of the last run say nothing about these pairs)
+    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;   // (the records of the last run say nothing about these pairs)
     return FIN_OK;
 }
 
@@ -1172,7 +1175,7 @@ int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32
     if (b->n_reads) HIPCHK(hipMemcpy(b->d_frec, recs, (size_t)b->n_reads * sizeof(FinFastRec), hipMemcpyHostToDevice));
     if (pairs && b->n_kmers) HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
     // last_frec / last_text_only stay as the run left them (a text-only batch still refuses its pairs); whatever was made from the old records goes
-    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
+    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
     b->rec_ready = false; b->rec_passthrough = false; b->rec_stream_pairs = 0;
     return FIN_OK;
 }
@@ -1924,6 +1927,180 @@ int fin_batch_download_pseudo(fin_batch* b, uint64_t* rows_out, fin_read_pseudo*
     if (b->n_reads && heads_out) HIPCHK(hipMemcpyAsync(heads_out, b->d_psa_heads, (size_t)b->n_reads * 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return FIN_OK;
+}
+
+// ---- taxonomic classification: LCA labels, Kraken's rule, tally and clade counts (fin_taxa.hip) -------------------------------------------------
+struct fin_taxonomy : fin_acc {
+    uint64_t n_unitigs = 0; uint32_t n_taxa = 0;
+    uint64_t serial = 0;        // which taxonomy a batch's read taxa were made for
+    void* d_parent = nullptr;   // uint32[n_taxa]
+    void* d_labels = nullptr;   // uint32[n_unitigs]
+    void* d_direct = nullptr;   // the tally: uint64[n_taxa + 1]
+    void* d_clade = nullptr;    // uint64[n_taxa], made by every download that asks for it
+    std::mutex clade_mu;        // one roll-up at a time goes through d_clade
+};
+static std::atomic<uint64_t> g_taxonomy_serial{0};
+
+void fin_taxonomy_free(fin_taxonomy* t) {
+    if (!acc_free_open(t)) return;
+    (void)hipFree(t->d_parent); (void)hipFree(t->d_labels); (void)hipFree(t->d_direct); (void)hipFree(t->d_clade);
+    delete t;
+}
+
+// the tests of the tree both creates make first, before anything is held against n_taxa
+static int taxonomy_check(const uint32_t* parent, uint64_t n_taxa, char* err, size_t errlen) {
+    if (n_taxa == 0 || n_taxa > 0x80000000ull) { set_err(err, errlen, "n_taxa is 1 .. 2^31"); return FIN_EINVAL; }
+    const uint64_t bad = fin_taxa_first_bad_parent(parent, n_taxa);
+    if (bad != n_taxa) {
+        set_err(err, errlen, "taxon " + std::to_string(bad) + " has parent " + std::to_string(parent[bad]) +
+                                 (bad == 0 ? ": taxon 0 is the root and its own parent" : ": a parent's number is below its child's (topological numbering)"));
+        return FIN_EINVAL;
+    }
+    return FIN_OK;
+}
+// the buffers the two creates share, behind taxonomy_check: the tree on the device, the tally zeroed, room for the labels.  The caller fills d_labels
+static int taxonomy_new(const fin_index* idx, int device, const uint32_t* parent, uint64_t n_taxa, fin_taxonomy** out, char* err, size_t errlen) {
+    if (const int orc = acc_create_open(idx, device, nullptr, err, errlen)) return orc;
+    fin_taxonomy* t = acc_new<fin_taxonomy>(idx, device, err, errlen);
+    if (!t) return FIN_ENOMEM;
+    t->n_unitigs = idx->n_unitigs; t->n_taxa = (uint32_t)n_taxa; t->serial = ++g_taxonomy_serial;
+    const size_t tally = ((size_t)n_taxa + 1) * 8;
+    if (hipMalloc(&t->d_parent, (size_t)n_taxa * 4) != hipSuccess || hipMalloc(&t->d_labels, (size_t)t->n_unitigs * 4 + 16) != hipSuccess ||
+        hipMalloc(&t->d_direct, tally) != hipSuccess || hipMalloc(&t->d_clade, (size_t)n_taxa * 8) != hipSuccess) {
+        (void)hipGetLastError(); fin_taxonomy_free(t); set_err(err, errlen, "out of device memory (taxonomy, unitig labels and tally)"); return FIN_ENOMEM;
+    }
+    if (hipMemcpy(t->d_parent, parent, (size_t)n_taxa * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemset(t->d_direct, 0, tally) != hipSuccess) {
+        fin_taxonomy_free(t); set_err(err, errlen, "copying the taxonomy failed"); return FIN_ENODEV;
+    }
+    *out = t;
+    return FIN_OK;
+}
+
+int fin_taxonomy_create(const fin_index* idx, int device, const uint32_t* parent, uint64_t n_taxa, const uint32_t* unitig_labels, fin_taxonomy** out, char* err,
+                        size_t errlen) {
+    if (!idx || !out || !parent || (idx->n_unitigs && !unitig_labels)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (const int trc = taxonomy_check(parent, n_taxa, err, errlen)) return trc;
+    for (uint64_t u = 0; u < idx->n_unitigs; u++)
+        if (unitig_labels[u] != FIN_NO_LABEL && (uint64_t)unitig_labels[u] >= n_taxa) {
+            set_err(err, errlen, "unitig " + std::to_string(u) + " has label " + std::to_string(unitig_labels[u]) + ": neither below n_taxa = " + std::to_string(n_taxa) + " nor FIN_NO_LABEL");
+            return FIN_EINVAL;
+        }
+    fin_taxonomy* t = nullptr;
+    if (const int rc = taxonomy_new(idx, device, parent, n_taxa, &t, err, errlen)) return rc;
+    if (t->n_unitigs && hipMemcpy(t->d_labels, unitig_labels, (size_t)t->n_unitigs * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        fin_taxonomy_free(t); set_err(err, errlen, "copying the labels failed"); return FIN_ENODEV;
+    }
+    *out = t;
+    return FIN_OK;
+}
+
+int fin_taxonomy_create_from_colors(fin_colors* c, const uint32_t* parent, uint64_t n_taxa, const uint32_t* color_taxon, fin_taxonomy** out, char* err, size_t errlen) {
+    if (!c || !out || !parent || !color_taxon) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (const int trc = taxonomy_check(parent, n_taxa, err, errlen)) return trc;
+    for (uint32_t q = 0; q < c->n_colors; q++)
+        if ((uint64_t)color_taxon[q] >= n_taxa) {
+            set_err(err, errlen, "colour " + std::to_string(q) + " has taxon " + std::to_string(color_taxon[q]) + ": not below n_taxa = " + std::to_string(n_taxa));
+            return FIN_EINVAL;
+        }
+    fin_taxonomy* t = nullptr;
+    if (const int rc = taxonomy_new(c->idx, c->device, parent, n_taxa, &t, err, errlen)) return rc;
+    // the adds to the matrix, on whichever streams, have finished; a withheld step among them is the colours' own refusal
+    if (const int orc = acc_download_open(c, colors_flags(c), "a step whose overflow list overran was added: it has no results, nothing of it was coloured (reset the colours)",
+                                          nullptr, err, errlen)) { fin_taxonomy_free(t); return orc; }
+    void* d_ct = nullptr;
+    int rc = FIN_OK;
+    if (hipMalloc(&d_ct, (size_t)c->n_colors * 4) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (colour taxa)"); rc = FIN_ENOMEM; }
+    else if (hipMemcpy(d_ct, color_taxon, (size_t)c->n_colors * 4, hipMemcpyHostToDevice) != hipSuccess) { set_err(err, errlen, "copying the colour taxa failed"); rc = FIN_ENODEV; }
+    else {
+        const int lrc = fin_launch_taxa_labels((const uint64_t*)c->d_bits, c->words, (uint32_t)c->n_unitigs, (const uint32_t*)d_ct, (const uint32_t*)t->d_parent,
+                                               (uint32_t*)t->d_labels, nullptr);
+        const hipError_t e = lrc != 0 ? (hipError_t)lrc : hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) { set_err(err, errlen, std::string("unitig LCA kernel: ") + hipGetErrorString(e)); rc = FIN_ENODEV; }
+    }
+    (void)hipFree(d_ct);
+    if (rc != FIN_OK) { fin_taxonomy_free(t); return rc; }
+    *out = t;
+    return FIN_OK;
+}
+
+int fin_taxonomy_reset(fin_taxonomy* t, void* hip_stream) {
+    return acc_reset(t, hip_stream, t ? t->d_direct : nullptr, t ? ((size_t)t->n_taxa + 1) * 8 : 0);
+}
+
+void* fin_taxonomy_device_labels(const fin_taxonomy* t) { return t ? t->d_labels : nullptr; }
+
+int fin_taxonomy_download_labels(const fin_taxonomy* t, uint32_t* labels_out, char* err, size_t errlen) {
+    if (!t || (t->n_unitigs && !labels_out)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(t->device));
+    if (t->n_unitigs) HIPCHK(hipMemcpy(labels_out, t->d_labels, (size_t)t->n_unitigs * 4, hipMemcpyDeviceToHost));
+    return FIN_OK;
+}
+
+int fin_taxonomy_download(fin_taxonomy* t, uint64_t* direct_out, uint64_t* clade_out, uint64_t* total, char* err, size_t errlen) {
+    if (!t) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(t, nullptr, nullptr, nullptr, err, errlen)) return orc;   // (a tally has no flags)
+    const size_t n = (size_t)t->n_taxa + 1;
+    if (direct_out || total) {
+        std::vector<uint64_t> tmp;
+        uint64_t* const dst = dst_or_tmp(direct_out, tmp, n);
+        HIPCHK(hipMemcpy(dst, t->d_direct, n * 8, hipMemcpyDeviceToHost));
+        if (total) *total = sum_of(dst, n, [](uint64_t v) { return v; });
+    }
+    if (clade_out) {   // the adds have finished: the roll-up runs on the null stream, into the second buffer
+        std::lock_guard<std::mutex> g(t->clade_mu);
+        HIPCHK(hipMemsetAsync(t->d_clade, 0, (size_t)t->n_taxa * 8, nullptr));
+        const int rc = fin_launch_taxa_clades((const uint64_t*)t->d_direct, (const uint32_t*)t->d_parent, t->n_taxa, (uint64_t*)t->d_clade, nullptr);
+        if (rc != 0) { set_err(err, errlen, std::string("clade kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+        HIPCHK(hipMemcpy(clade_out, t->d_clade, (size_t)t->n_taxa * 8, hipMemcpyDeviceToHost));
+    }
+    return FIN_OK;
+}
+
+static const char* const BAD_CONFIDENCE = "confidence_permille is a share in thousandths: 0 .. 1000";
+
+int fin_batch_taxa(fin_batch* b, const fin_taxonomy* t, uint32_t min_found, uint32_t confidence_permille, char* err, size_t errlen) {
+    if (!b || !t) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int crc = check_permille(confidence_permille, BAD_CONFIDENCE, err, errlen)) return crc;
+    if (!b->ran) { set_err(err, errlen, "this batch has not run: there is nothing to classify (fin_batch_run first)"); return FIN_EINVAL; }
+    if (b->idx != t->idx || b->device != t->device) { set_err(err, errlen, "batch and taxonomy belong to different indexes or devices"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    b->tax_ready = false;
+    // (no read has a k-mer: the step searched nothing, there is no overflow list to look at -- every read is unclassified)
+    if (b->n_kmers != 0) if (const int orc = batch_overrun_check(b, st, err, errlen)) return orc;   // a run without results: nothing is written
+    const uint32_t nr = (uint32_t)b->n_reads;
+    if (batch_grow(b, &b->d_tax, b->cap_tax, (size_t)nr * 16 + 16, st)) { set_err(err, errlen, "out of device memory (read taxa)"); return FIN_ENOMEM; }
+    const int rc = fin_launch_taxa_reads(b->n_kmers != 0 && b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, nr, b->dev.k,
+                                         (const uint32_t*)t->d_labels, (uint32_t)t->n_unitigs, (const uint32_t*)t->d_parent, min_found, confidence_permille, b->d_tax, st);
+    if (rc != 0) { set_err(err, errlen, std::string("read taxa kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    b->tax_ready = true; b->tax_serial = t->serial; b->tax_min_found = min_found; b->tax_conf = confidence_permille;
+    return FIN_OK;
+}
+
+void* fin_batch_device_read_taxa(const fin_batch* b) { return b && b->tax_ready ? b->d_tax : nullptr; }
+
+int fin_batch_download_read_taxa(fin_batch* b, fin_read_taxon* out, char* err, size_t errlen) {
+    if (!b || (b->n_reads && !out)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->tax_ready) { set_err(err, errlen, "fin_batch_taxa first"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    if (b->n_reads) HIPCHK(hipMemcpyAsync(out, b->d_tax, (size_t)b->n_reads * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
+int fin_batch_add_taxa(fin_batch* b, fin_taxonomy* t, uint32_t min_found, uint32_t confidence_permille, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !t) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int crc = check_permille(confidence_permille, BAD_CONFIDENCE, err, errlen)) return crc;
+    if (!b->tax_ready || b->tax_serial != t->serial || b->tax_min_found != min_found || b->tax_conf != confidence_permille)
+        if (const int rc = fin_batch_taxa(b, t, min_found, confidence_permille, err, errlen)) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (const int orc = acc_add_open(b, t, st, err, errlen)) return orc;
+    if (const int src = stream_behind(st, b->last_stream, err, errlen)) return src;   // the read taxa were made on the run's stream, behind the run: the add waits for them too
+    const int rc = fin_launch_taxa_tally(b->d_tax, (uint32_t)b->n_reads, t->n_taxa, (uint64_t*)t->d_direct, st);
+    return acc_add_close(t, st, rc, "taxon tally kernel: ", err, errlen);
 }
 
 // ---- paired-end pseudoalignment: one colour row per fragment (fin_paired.hip) -------------------------------------------------------------
@@ -3647,6 +3824,36 @@ int fin_search_batch_add_classes(const fin_index* idx, const char* bases, const 
     if (n_reads == 0) return FIN_OK;
     Product p;   // every sub-batch is added to the labelling's tally on the device, nothing comes back
     p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_classes(b, l, min_found, min_permille, min_margin, own(b), e, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
+}
+
+static const char* const OTHER_TAXONOMY = "the taxonomy belongs to another index";
+int fin_search_batch_taxa(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_taxonomy* t, uint32_t min_found,
+                          uint32_t confidence_permille, fin_read_taxon* out, uint64_t* n_positive, char* err, size_t errlen) {
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, t && (!n_reads || out), t, OTHER_TAXONOMY, &device, err, errlen)) return orc;
+    if (const int crc = check_permille(confidence_permille, BAD_CONFIDENCE, err, errlen)) return crc;
+    if (n_positive) *n_positive = 0;
+    if (n_reads == 0) return FIN_OK;
+    Product p;   // a sub-batch's read taxa land at its reads' numbers
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t& pos, char* e, size_t elen) -> int {
+        if (const int rc = fin_batch_taxa(b, t, min_found, confidence_permille, e, elen)) return rc;
+        fin_read_taxon* const dst = out + s.lo;
+        if (const int rc = fin_batch_download_read_taxa(b, dst, e, elen)) return rc;
+        for (uint64_t r = 0; r < s.hi - s.lo; r++) pos += dst[r].n_labelled;
+        return FIN_OK;
+    };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, n_positive, err, errlen);
+}
+
+int fin_search_batch_add_taxa(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_taxonomy* t, uint32_t min_found,
+                              uint32_t confidence_permille, char* err, size_t errlen) {
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, t, t, OTHER_TAXONOMY, &device, err, errlen)) return orc;
+    if (const int crc = check_permille(confidence_permille, BAD_CONFIDENCE, err, errlen)) return crc;
+    if (n_reads == 0) return FIN_OK;
+    Product p;   // every sub-batch is added to the taxonomy's tally on the device, nothing comes back
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_taxa(b, t, min_found, confidence_permille, own(b), e, elen); };
     return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 

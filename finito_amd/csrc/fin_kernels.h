@@ -184,6 +184,15 @@ int fin_launch_classify(const void* frec, const uint64_t* out_offs, const void* 
                         void* cls, hipStream_t stream);
 int fin_launch_class_tally(const void* cls, const uint64_t* out_offs, uint32_t n_reads, uint32_t n_labels, uint32_t min_found, uint32_t min_permille,
                            uint32_t min_margin, uint64_t* reads, hipStream_t stream);
+// fin_taxa.hip -- taxonomic classification over parent[n_taxa] in topological numbering (fin_taxa.h).
+// fin_launch_taxa_labels: label[u] = the LCA of the taxa of unitig u's colours (uint32[n_unitigs]; color_taxon on the device);
+// fin_launch_taxa_reads: fin_read_taxon[n_reads], 16 bytes each, by Kraken's rule with the thresholds applied (frec null: every read's pairs are scanned);
+// fin_launch_taxa_tally: direct[taxon] += 1 / direct[n_taxa] += 1 per read (uint64[n_taxa + 1]); fin_launch_taxa_clades: clade[n_taxa], zeroed by the caller, += direct over the subtrees
+int fin_launch_taxa_labels(const uint64_t* bits, uint32_t W, uint32_t n_unitigs, const uint32_t* color_taxon, const uint32_t* parent, uint32_t* label, hipStream_t stream);
+int fin_launch_taxa_reads(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const uint32_t* labels, uint32_t n_unitigs,
+                          const uint32_t* parent, uint32_t min_found, uint32_t conf, void* out, hipStream_t stream);
+int fin_launch_taxa_tally(const void* rt, uint32_t n_reads, uint32_t n_taxa, uint64_t* direct, hipStream_t stream);
+int fin_launch_taxa_clades(const uint64_t* direct, const uint32_t* parent, uint32_t n_taxa, uint64_t* clade, hipStream_t stream);
 // fin_colors.hip -- colour sets per unitig: bits uint64[n_unitigs * W], then one flag word (bit 0: a step whose overflow list overran was offered).
 // fin_launch_colors_add: bit `color` for every unitig in which the step found a k-mer (frec null: every read's pairs are scanned).
 // fin_launch_pseudoalign: rows uint64[n_reads * W] and heads {n_found, n_coloured, popcount, 0} per read under the threshold permille

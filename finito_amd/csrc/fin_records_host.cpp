@@ -15,6 +15,7 @@
 #include "fin_format.h"
 #include "fin_host.h"
 #include "fin_rec_walk.h"
+#include "fin_taxa.h"
 
 static_assert(sizeof(fin_read_record) == sizeof(FinFastRec) && offsetof(fin_read_record, nk) == 12 && offsetof(FinFastRec, nk) == 12 &&
               offsetof(fin_read_record, Es) == 16 && offsetof(FinFastRec, Es) == 16 && offsetof(fin_read_record, Es2) == 24 && offsetof(FinFastRec, Es2) == 24,
@@ -373,6 +374,34 @@ int fin_records_read_classes(const fin_read_record* recs, uint64_t n_reads, cons
                 i = j;
             }
             out[r] = K;
+        }
+        return good;
+    });
+    return ok ? FIN_OK : FIN_EINVAL;
+}
+
+// the read taxa of fin_taxa.hip from records + stream, over the same segments: a segment of |len| slots in unitig u is |len| votes for labels[u]; the rule
+// itself is fin_taxa_call's (fin_taxa_host.cpp)
+int fin_records_read_taxa(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint32_t* unitig_labels,
+                          uint64_t n_unitigs, const uint32_t* parent, uint64_t n_taxa, uint32_t min_found, uint32_t confidence_permille, fin_read_taxon* out,
+                          int n_threads) {
+    if ((n_reads && (!recs || !out)) || k < 1 || (n_stream_pairs && !stream_pairs) || (n_unitigs && !unitig_labels) || !parent) return FIN_EINVAL;
+    if (n_taxa == 0 || n_taxa > 0x80000000ull || confidence_permille > 1000u || fin_taxa_first_bad_parent(parent, n_taxa) != n_taxa) return FIN_EINVAL;
+    for (uint64_t u = 0; u < n_unitigs; u++) if (unitig_labels[u] != FIN_NO_LABEL && (uint64_t)unitig_labels[u] >= n_taxa) return FIN_EINVAL;
+    Chunks C(n_reads, n_threads);
+    if (C.stream(recs, n_stream_pairs)) return FIN_EINVAL;
+    const bool ok = C.run([&](int t) {
+        uint64_t sp = C.str0[(size_t)t];
+        bool good = true;
+        std::vector<std::pair<uint32_t, uint32_t>> votes;   // (taxon, slots) per segment
+        for (uint64_t r = C.lo(t); r < C.hi(t) && good; r++) {
+            votes.clear();
+            good = read_segments(recs[r], stream_pairs, sp, k, [&](int32_t u, int32_t, uint32_t, int32_t len) {
+                if ((uint64_t)(uint32_t)u >= n_unitigs) { good = false; return; }
+                const uint32_t L = unitig_labels[(uint32_t)u];
+                if (L != FIN_NO_LABEL) votes.push_back({L, (uint32_t)(len < 0 ? -(int64_t)len : (int64_t)len)});
+            }) && good;
+            out[r] = fin_taxa_call(votes, parent, recs[r].nk, min_found, confidence_permille);
         }
         return good;
     });

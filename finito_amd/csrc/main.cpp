@@ -36,6 +36,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "FinimizerIndex.hh"
@@ -525,6 +526,16 @@ static const char* SEARCH_HELP =
     "                        least P thousandths of the coloured k-mers have (`-` for none). Made on the first GPU from one more search of every chunk;\n"
     "                        goes with everything --read-summary goes with. Not for a partitioned index.\n"
     "      --pseudo-permille P  the P of --pseudoalign, --eqclasses and --color-report, 0 to 1000 (default: 1000, the intersection; 0 is the union)\n"
+    "      --taxonomy FILE   a tree over taxa: one line `id<TAB>parent_id` per taxon, any integer ids (NCBI's, say), the root its own parent. A cycle, an\n"
+    "                        unknown parent, a second root and a repeated id are errors that name the line. Wants --color-taxa and --taxa or --taxon-report.\n"
+    "      --color-taxa FILE  one taxon id per line, the taxon of the reference on the same line of --color-refs (empty lines do not count). A unitig's taxon is\n"
+    "                        the lowest common ancestor of its references' taxa, made on the GPU after the colouring.\n"
+    "      --taxa FILE       also write one line per read, in input order: `read<TAB>k-mers<TAB>taxon<TAB>score<TAB>clade<TAB>labelled` -- the deepest taxon\n"
+    "                        the read's k-mers support (Kraken's root-to-leaf rule; `-`: unclassified), the best root-to-leaf score, the k-mers at or below\n"
+    "                        the taxon and the k-mers that have a taxon at all. Made on the GPU; goes with -o and the other per-run outputs, and with --no-text 1.\n"
+    "      --taxon-report FILE  also write `taxon<TAB>clade_reads<TAB>direct_reads` for every taxon with a read at or below it, then `unclassified<TAB>N`.\n"
+    "      --taxa-confidence P  a call moves up the tree until its clade holds P thousandths of the read's k-mers, 0 to 1000 (default: 0)\n"
+    "      --taxa-min-found N   ... and at least N k-mers (default: 1). Not for a partitioned index, not with --paired 1.\n"
     "      --eqclasses FILE  the equivalence classes of the reads under the colours of --color-refs: one line `reads<TAB>n_colours<TAB>c1,c2,...` per\n"
     "                        distinct non-empty colour set a read has at the P of --pseudo-permille, reads = how many reads have it, in ascending order\n"
     "                        of the sets as bit rows. Accumulated on the first GPU from one more search of every chunk, nothing per read comes back;\n"
@@ -853,6 +864,104 @@ static void classify_chunk(const FinimizerIndex& index, const char* bases, const
                                                      err, sizeof err) != FIN_OK)
         throw runtime_error(err);
     g_cls_read0 += n_reads;
+}
+// --taxa FILE: every chunk's reads are called by Kraken's rule under the taxonomy of --taxonomy / --color-taxa on the first device (fin_search_batch_taxa) and
+// written as lines, taxa in the caller's ids.  --taxon-report FILE: every chunk's reads are tallied on the device (fin_search_batch_add_taxa)
+static fin_taxonomy* g_tax = nullptr;
+static FILE* g_tax_file = nullptr;
+static bool g_tax_report = false;
+static uint64_t g_tax_read0 = 0;
+static uint32_t g_tax_min_found = 1, g_tax_confidence = 0;
+static vector<int64_t> g_tax_ids;   // the caller's id of every taxon, by its number
+static vector<fin_read_taxon> g_tax_reads; static string g_tax_text;
+static void taxa_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads, const uint64_t* pair_off) {
+    char err[512] = {0};
+    if (g_tax_file) {
+        g_tax_reads.resize(n_reads + 1);
+        if (fin_search_batch_taxa(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_tax, g_tax_min_found, g_tax_confidence, g_tax_reads.data(), nullptr, err, sizeof err) != FIN_OK)
+            throw runtime_error(err);
+        string& t = g_tax_text;
+        t.clear();
+        for (uint64_t r = 0; r < n_reads; r++) {
+            const fin_read_taxon& S = g_tax_reads[r];
+            t += to_string(g_tax_read0 + r); t += '\t'; t += to_string(pair_off[r + 1] - pair_off[r]); t += '\t';
+            if (S.taxon == FIN_NO_LABEL) t += '-'; else t += to_string(g_tax_ids[S.taxon]);
+            t += '\t'; t += to_string(S.score); t += '\t'; t += to_string(S.clade); t += '\t'; t += to_string(S.n_labelled); t += '\n';
+        }
+        if (!t.empty() && fwrite(t.data(), 1, t.size(), g_tax_file) != t.size()) throw runtime_error("Error writing the taxa file");
+    }
+    if (g_tax_report && fin_search_batch_add_taxa(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_tax, g_tax_min_found, g_tax_confidence, err, sizeof err) != FIN_OK)
+        throw runtime_error(err);
+    g_tax_read0 += n_reads;
+}
+// one integer of a taxonomy file's line; false for anything else
+static bool taxon_id(const string& v, int64_t& out) {
+    size_t used = 0;
+    try { out = stoll(v, &used); } catch (...) { return false; }
+    return !v.empty() && used == v.size();
+}
+// --taxonomy FILE: `id<TAB>parent_id` per line, any integer ids, the root its own parent; empty lines are skipped (and still count as lines).  ids[t] = the id of
+// taxon t in the topological numbering the library takes (the root 0, then breadth-first, siblings in file order), parent[t] in those numbers.  Every refusal
+// names the line
+static void taxonomy_parse_file(const string& path, vector<int64_t>& ids, vector<uint32_t>& parent, unordered_map<int64_t, uint32_t>& number) {
+    ifstream in(path);
+    if (!in) throw runtime_error("--taxonomy: cannot read " + path);
+    auto bad = [&](size_t line, const string& what) { return runtime_error("--taxonomy: " + path + " line " + to_string(line) + ": " + what); };
+    vector<int64_t> id, pid; vector<size_t> line_of;
+    unordered_map<int64_t, size_t> at;
+    string line;
+    for (size_t n = 1; getline(in, line); n++) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const size_t tab = line.find('\t');
+        int64_t a = 0, b = 0;
+        if (tab == string::npos || !taxon_id(line.substr(0, tab), a) || !taxon_id(line.substr(tab + 1), b)) throw bad(n, "wants `id<TAB>parent_id`, two integers");
+        if (at.count(a)) throw bad(n, "taxon " + to_string(a) + " was given on line " + to_string(line_of[at[a]]) + " already");
+        at[a] = id.size(); id.push_back(a); pid.push_back(b); line_of.push_back(n);
+    }
+    if (id.empty()) throw runtime_error("--taxonomy: " + path + " is empty, it names no taxon");
+    if (id.size() > 0x80000000ull) throw runtime_error("--taxonomy: " + path + " names more than 2^31 taxa");
+    vector<vector<uint32_t>> kids(id.size());
+    size_t root = id.size();
+    for (size_t i = 0; i < id.size(); i++) {
+        if (pid[i] == id[i]) {
+            if (root != id.size()) throw bad(line_of[i], "a second root: taxon " + to_string(id[i]) + " is its own parent, as taxon " + to_string(id[root]) + " of line " + to_string(line_of[root]) + " is");
+            root = i;
+        } else {
+            auto it = at.find(pid[i]);
+            if (it == at.end()) throw bad(line_of[i], "taxon " + to_string(id[i]) + " has the unknown parent " + to_string(pid[i]));
+            kids[it->second].push_back((uint32_t)i);
+        }
+    }
+    if (root == id.size()) throw bad(line_of[0], "no root: no taxon is its own parent (every taxon lies on a cycle or below one)");
+    vector<uint32_t> order{(uint32_t)root}, num(id.size(), 0xFFFFFFFFu);
+    num[root] = 0;
+    parent.assign(1, 0u);
+    for (size_t q = 0; q < order.size(); q++)
+        for (uint32_t c : kids[order[q]]) { num[c] = (uint32_t)order.size(); order.push_back(c); parent.push_back(num[order[q]]); }
+    for (size_t i = 0; i < id.size(); i++)
+        if (num[i] == 0xFFFFFFFFu) throw bad(line_of[i], "a cycle: taxon " + to_string(id[i]) + " never reaches the root");
+    ids.clear(); number.clear();
+    for (uint32_t i : order) { number[id[i]] = (uint32_t)ids.size(); ids.push_back(id[i]); }
+}
+// --color-taxa FILE: one taxon id per reference of --color-refs, in its order; empty lines are skipped and do not count, as in that list
+static vector<uint32_t> color_taxa_parse_file(const string& path, const unordered_map<int64_t, uint32_t>& number, size_t n_refs) {
+    ifstream in(path);
+    if (!in) throw runtime_error("--color-taxa: cannot read " + path);
+    vector<uint32_t> out;
+    string line;
+    for (size_t n = 1; getline(in, line); n++) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        int64_t a = 0;
+        if (!taxon_id(line, a)) throw runtime_error("--color-taxa: " + path + " line " + to_string(n) + ": wants one taxon id, an integer");
+        auto it = number.find(a);
+        if (it == number.end()) throw runtime_error("--color-taxa: " + path + " line " + to_string(n) + ": taxon " + to_string(a) + " is not in the file of --taxonomy");
+        if (out.size() == n_refs) throw runtime_error("--color-taxa: " + path + " line " + to_string(n) + ": a taxon more than the " + to_string(n_refs) + " references --color-refs names");
+        out.push_back(it->second);
+    }
+    if (out.size() != n_refs) throw runtime_error("--color-taxa: " + path + " has " + to_string(out.size()) + " taxa, --color-refs names " + to_string(n_refs) + " references");
+    return out;
 }
 // the labelling of --label-unitigs FASTA --labels FILE, in the index's unitig numbers (fin_index_unitig_numbers); *n_labels = the largest label + 1
 static vector<uint32_t> load_labelling(const FinimizerIndex& index, const string& fasta, const string& file, uint32_t* n_labels) {
@@ -1194,6 +1303,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_rs_file) c->positive = read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
+                        if (g_tax) taxa_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_eqc) eqclasses_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_asg) assign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
@@ -1218,6 +1328,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_rs_file) (void)read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_scr_file) screen_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_labels) classify_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
+                        if (g_tax) taxa_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_eqc) eqclasses_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_asg) assign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
@@ -1365,12 +1476,12 @@ static void write_color_similarity(const string& path, fin_cover* cov, size_t nc
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "color-similarity", "color-similarity-covered", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "color-similarity", "color-similarity-covered", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
     if (o.has("color-similarity-covered") && !o.has("color-similarity")) throw runtime_error("--color-similarity-covered is only legal together with --color-similarity");
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity"))
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity") && !o.has("taxa") && !o.has("taxon-report"))
         throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
@@ -1383,11 +1494,16 @@ static int search_fmin(int argc, char** argv) {
     g_pair_mode = pair_both ? FIN_PAIR_BOTH : FIN_PAIR_ANY;
     const bool eq_asked = o.has("eqclasses") || o.has("color-report") || o.has("abundance");
     const bool asg_asked = o.has("assign-weights");
+    const bool tax_asked = o.has("taxa") || o.has("taxon-report");
+    if (tax_asked && !(o.has("taxonomy") && o.has("color-taxa") && o.has("color-refs"))) throw runtime_error("--taxa and --taxon-report want a taxonomy over colours: --color-refs LIST --taxonomy FILE --color-taxa FILE");
+    for (const char* name : {"taxonomy", "color-taxa", "taxa-confidence", "taxa-min-found"})
+        if (o.has(name) && !tax_asked) throw runtime_error(string("--") + name + " is only legal together with --taxa or --taxon-report");
+    if (tax_asked && g_paired) throw runtime_error("--taxa and --taxon-report call reads, not fragments: not together with --paired 1");
     if (asg_asked && !o.has("color-refs")) throw runtime_error("--assign-weights wants colours: --color-refs LIST");
     if (asg_asked && !o.has("assign") && !o.has("assign-report")) throw runtime_error("--assign-weights wants a result: --assign FILE and / or --assign-report FILE");
     for (const char* name : {"assign", "assign-report", "assign-threshold"})
         if (o.has(name) && !asg_asked) throw runtime_error(string("--") + name + " is only legal together with --assign-weights");
-    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked && !o.has("color-coverage") && !o.has("color-similarity")) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
+    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked && !o.has("color-coverage") && !o.has("color-similarity") && !tax_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
     if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked && !asg_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
     if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses, --color-report or --abundance");
     if (o.has("eqclasses-in") && !eq_asked) throw runtime_error("--eqclasses-in is only legal together with --eqclasses, --color-report or --abundance");
@@ -1415,6 +1531,8 @@ static int search_fmin(int argc, char** argv) {
     g_cls_min_permille = u32_option("class-min-permille", 0, 1000);
     g_cls_min_margin = u32_option("class-min-margin", 0, 0xFFFFFFFFull);
     g_psa_permille = u32_option("pseudo-permille", 1000, 1000);
+    g_tax_confidence = u32_option("taxa-confidence", 0, 1000);
+    g_tax_min_found = u32_option("taxa-min-found", 1, 0xFFFFFFFFull);
     const uint32_t eq_max_classes = u32_option("eq-max-classes", 1u << 20, 1u << 26);
     if (eq_max_classes == 0) throw runtime_error("--eq-max-classes wants a number from 1 to " + to_string(1u << 26));
     const uint32_t ab_max_iters = u32_option("ab-max-iters", 1000, 100000);
@@ -1444,6 +1562,15 @@ static int search_fmin(int argc, char** argv) {
         if (color_refs.empty()) throw runtime_error("--color-refs: " + o.get("color-refs") + " is empty, it names no reference");
         if (color_refs.size() > FIN_MAX_COLORS) throw runtime_error("--color-refs: " + o.get("color-refs") + " names " + to_string(color_refs.size()) + " references, at most " + to_string(FIN_MAX_COLORS) + " colours are supported");
     }
+    vector<uint32_t> tax_parent, tax_color_taxon;
+    if (tax_asked) {
+        unordered_map<int64_t, uint32_t> number;
+        taxonomy_parse_file(o.get("taxonomy"), g_tax_ids, tax_parent, number);
+        tax_color_taxon = color_taxa_parse_file(o.get("color-taxa"), number, color_refs.size());
+    }
+    const string taxa_file = o.get("taxa", ""), taxrep_file = o.get("taxon-report", "");
+    if (!taxa_file.empty()) check_writable(taxa_file);
+    if (!taxrep_file.empty()) check_writable(taxrep_file);
     const bool eqc_unaligned = o.has("eqclasses-unaligned") && o.get("eqclasses-unaligned") != "0" && o.get("eqclasses-unaligned") != "false";
     vector<EqClassesFile> eqc_in;
     if (o.has("eqclasses-in")) {
@@ -1648,6 +1775,7 @@ static int search_fmin(int argc, char** argv) {
             if (!g_cls_file) throw runtime_error("Error writing to file: " + cls_file);
         }
     }
+    struct TaxOwner { ~TaxOwner() { if (g_tax_file) fclose(g_tax_file); g_tax_file = nullptr; fin_taxonomy_free(g_tax); g_tax = nullptr; } } tax_owner;   // (it reads the colours at its creation only: the order of the two frees does not matter)
     struct ColorOwner { ~ColorOwner() { if (g_psa_file) fclose(g_psa_file); g_psa_file = nullptr; if (g_asg_file) fclose(g_asg_file); g_asg_file = nullptr; fin_assign_free(g_asg); g_asg = nullptr; fin_eqclasses_free(g_eqc); g_eqc = nullptr; fin_colors_free(g_colors); g_colors = nullptr; } } color_owner;
     if (!color_refs.empty()) {
         for (auto& f : color_refs) check_readable(f);
@@ -1668,6 +1796,15 @@ static int search_fmin(int argc, char** argv) {
             if (!cf) throw runtime_error("Error writing to file: " + colors_file);
         }
         if (!colsim_file.empty()) write_color_similarity(colsim_file, nullptr, color_refs.size());   // (what the references share in the graph, before any read)
+        if (tax_asked) {   // every unitig's taxon: the LCA of its colours' taxa, made on the device from the matrix as it stands now
+            if (fin_taxonomy_create_from_colors(g_colors, tax_parent.data(), tax_parent.size(), tax_color_taxon.data(), &g_tax, err, sizeof err) != FIN_OK) throw runtime_error(err);
+            g_tax_report = !taxrep_file.empty();
+            g_tax_read0 = 0;
+            if (!taxa_file.empty()) {
+                g_tax_file = fopen(taxa_file.c_str(), "wb");
+                if (!g_tax_file) throw runtime_error("Error writing to file: " + taxa_file);
+            }
+        }
         if (!psa_file.empty()) {
             g_psa_file = fopen(psa_file.c_str(), "wb");
             if (!g_psa_file) throw runtime_error("Error writing to file: " + psa_file);
@@ -1724,6 +1861,11 @@ static int search_fmin(int argc, char** argv) {
         const bool bad = fflush(g_cls_file) != 0 || ferror(g_cls_file);
         fclose(g_cls_file); g_cls_file = nullptr;
         if (bad) throw runtime_error("Error writing to file: " + cls_file);
+    }
+    if (g_tax_file) {
+        const bool bad = fflush(g_tax_file) != 0 || ferror(g_tax_file);
+        fclose(g_tax_file); g_tax_file = nullptr;
+        if (bad) throw runtime_error("Error writing to file: " + taxa_file);
     }
     if (g_psa_file) {
         const bool bad = fflush(g_psa_file) != 0 || ferror(g_psa_file);
@@ -1828,6 +1970,19 @@ static int search_fmin(int argc, char** argv) {
             cf.write(text.data(), (streamsize)text.size());
             if (!cf) throw runtime_error("Error writing to file: " + crep_file);
         }
+    }
+    if (g_tax && g_tax_report) {   // the tally and the clade counts, after the last chunk: one line per taxon with a read at or below it, in the caller's ids
+        char err[512] = {0};
+        const size_t n = g_tax_ids.size();
+        vector<uint64_t> direct(n + 1), clade(n);
+        if (fin_taxonomy_download(g_tax, direct.data(), clade.data(), nullptr, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        string text;
+        for (size_t t = 0; t < n; t++)
+            if (clade[t]) { text += to_string(g_tax_ids[t]); text += '\t'; text += to_string(clade[t]); text += '\t'; text += to_string(direct[t]); text += '\n'; }
+        text += "unclassified\t"; text += to_string(direct[n]); text += '\n';
+        ofstream cf(taxrep_file, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + taxrep_file);
     }
     if (g_labels && g_cls_report) {   // the tally, after the last chunk: one line per label, then the unassigned reads
         char err[512] = {0};

@@ -1183,6 +1183,80 @@ int fin_colors_shared(fin_colors* c, fin_cover* cov /* may be NULL */, const uin
  * at the end: the result does not depend on n_threads.  FIN_EINVAL for a bit at or above n_colors, FIN_ELIMIT for n_colors outside 1 .. 4096 */
 int fin_unitig_color_shared(const uint64_t* bits, uint64_t n_unitigs, uint32_t n_colors, const uint64_t* v, uint64_t* out, int n_threads);
 
+/* ---- TAXONOMIC CLASSIFICATION: LCA labels and Kraken's rule, on the device ----
+ * Reference collections are trees -- strains, species, genera --, and the flat outputs above cannot say "this read is from that species, I cannot tell which
+ * strain".  A TAXONOMY is a tree over n_taxa taxa, 1 <= n_taxa <= 2^31, given as uint32 parent[n_taxa] in TOPOLOGICAL NUMBERING: taxon 0 is the root and
+ * parent[0] == 0; parent[t] < t for every t >= 1.  Anything else is FIN_EINVAL, and the message names the taxon.  (The Python helper taxonomy_order and the CLI
+ * renumber arbitrary ids.)  With this numbering
+ *   lca(a, b):  while (a != b) { if (a > b) a = parent[a]; else b = parent[b]; }      a is an ancestor-or-self of b  iff  lca(a, b) == a.
+ * UNITIG LABELS FROM COLOURS.  With color_taxon[n_colors], each entry < n_taxa: label[u] = the lca of color_taxon[c] over the set bits c of unitig u's colour row,
+ * FIN_NO_LABEL for an empty row.  It is an ordinary labelling with n_labels = n_taxa: fin_labels_create takes it, the majority vote runs on it as it is.
+ * THE CALL OF A READ (Kraken's root-to-leaf rule), integers only.  Over the read's output slots 0 .. nk - 1, c[t] = the number of found slots whose unitig's label
+ * is t (a unitig number >= the index's unitigs has no label); H = { t : c[t] > 0 }; n_labelled = the sum of c;
+ *   score(t) = the sum of c[a] over the a in H that are ancestor-or-self of t;    S = the maximum of score over H;
+ *   call     = the lca of all t in H with score(t) == S;
+ *   clade(t) = the sum of c[x] over the x in H of which t is ancestor-or-self -- clade(0) == n_labelled.
+ * LIFTING: while 1000 * clade(call) < confidence_permille * nk or clade(call) < max(min_found, 1), in 64-bit arithmetic: if call == 0 the read is unclassified,
+ * otherwise call = parent[call].  The result is
+ *   classified              {call, S, clade(call), n_labelled}
+ *   unclassified with hits  {FIN_NO_LABEL, S, n_labelled, n_labelled}
+ *   nothing labelled        {FIN_NO_LABEL, 0, 0, 0}
+ * Every field is invariant under reversing the slot order.  Exact for every read, however many distinct taxa it touches.  16 bytes per read come back, or 16 bytes
+ * per taxon for a whole run (direct and clade counts); nothing per k-mer crosses PCIe.
+ * THE TALLY: direct[taxon] += 1 per classified read, direct[n_taxa] += 1 per unclassified read; clade_reads[t] = the sum of direct[x] over t's subtree, so
+ * clade_reads[0] + direct[n_taxa] == the reads added.  Adding twice counts twice.
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, fragments (paired mates pooled into one call), Kraken 2's
+ * minimizer hit groups. */
+typedef struct fin_read_taxon { uint32_t taxon, score, clade, n_labelled; } fin_read_taxon;   /* 16 bytes */
+typedef struct fin_taxonomy fin_taxonomy;
+/* a taxonomy beside the replica on `device`, with a labelling the caller brings and its zeroed tally: parent[n_taxa] and unitig_labels[fin_index_n_unitigs]
+ * (each < n_taxa or FIN_NO_LABEL), both copied.  It is an accumulator like fin_labels: adds and resets are ordered by the same rules.  FIN_EINVAL: n_taxa outside
+ * 1 .. 2^31, a parent that breaks the numbering (the message names the taxon), a label that is neither (the message names the unitig).  FIN_ENODEV: no replica
+ * on that device. */
+int fin_taxonomy_create(const fin_index* idx, int device, const uint32_t* parent, uint64_t n_taxa, const uint32_t* unitig_labels, fin_taxonomy** out, char* err,
+                        size_t errlen);
+/* ... beside a colour matrix, on its index and device, the labels made from its rows on the device (fin_taxa.hip): color_taxon[n_colors], each < n_taxa (else
+ * FIN_EINVAL; the message names the colour).  A waiting call: it waits for every add and reset issued so far to the colours, whichever streams they were given,
+ * and passes on fin_colors_download's code and message for a withheld step.  The colours are read once; later adds to them do not change the labels. */
+int fin_taxonomy_create_from_colors(fin_colors* colors, const uint32_t* parent, uint64_t n_taxa, const uint32_t* color_taxon, fin_taxonomy** out, char* err,
+                                    size_t errlen);
+void* fin_taxonomy_device_labels(const fin_taxonomy* t);   /* uint32[fin_index_n_unitigs] in HBM */
+int fin_taxonomy_download_labels(const fin_taxonomy* t, uint32_t* labels_out, char* err, size_t errlen);   /* labels_out[fin_index_n_unitigs] */
+int fin_taxonomy_reset(fin_taxonomy* t, void* hip_stream);   /* zeroes the tally only (asynchronous on hip_stream; ordered against the adds as fin_hits_reset is) */
+/* waits for every add and reset issued so far; direct_out[n_taxa + 1] (may be NULL): the reads called at each taxon, then the unclassified ones; clade_out[n_taxa]
+ * (may be NULL): the reads called at or below each taxon, rolled up on the device into a second buffer -- the direct counts stay as they are; *total (may be
+ * NULL) = the reads added = clade_out[0] + direct_out[n_taxa] */
+int fin_taxonomy_download(fin_taxonomy* t, uint64_t* direct_out, uint64_t* clade_out, uint64_t* total, char* err, size_t errlen);
+void fin_taxonomy_free(fin_taxonomy* t);
+/* Behind the batch's most recent run, on that run's stream and ordered behind the run, as fin_batch_classify: one kernel, a lane per read; a read the fast path
+ * finished lies in one unitig and is called from its record and one label, every other read's pairs are scanned in place, a second and third time only when it
+ * touches more than 64 distinct taxa.  The read taxa stay in HBM in a buffer the batch keeps and only grows; a call with other thresholds or another taxonomy
+ * replaces them.  fin_batch_run, fin_batch_reload, fin_batch_set_records and fin_batch_set_pairs forget them.
+ * FIN_EINVAL: the batch has not run, the taxonomy belongs to another index or device, confidence_permille above 1000.  FIN_ELIMIT: the run's overflow list
+ * overran -- it has no results. */
+int fin_batch_taxa(fin_batch* b, const fin_taxonomy* t, uint32_t min_found, uint32_t confidence_permille, char* err, size_t errlen);
+void* fin_batch_device_read_taxa(const fin_batch* b);   /* fin_read_taxon[n_reads] in HBM; NULL before fin_batch_taxa */
+int fin_batch_download_read_taxa(fin_batch* b, fin_read_taxon* out, char* err, size_t errlen);   /* out[n_reads] */
+/* the tally += the batch's reads, on hip_stream behind the run.  Makes the read taxa if they are not there for this taxonomy and these thresholds, and then waits
+ * as fin_batch_add_classes does. */
+int fin_batch_add_taxa(fin_batch* b, fin_taxonomy* t, uint32_t min_found, uint32_t confidence_permille, void* hip_stream, char* err, size_t errlen);
+/* host buffers in: the pipeline of fin_search_batch_classify, on the taxonomy's device.  out[n_reads]; *n_positive (may be NULL) = the sum of n_labelled */
+int fin_search_batch_taxa(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, const fin_taxonomy* t, uint32_t min_found,
+                          uint32_t confidence_permille, fin_read_taxon* out, uint64_t* n_positive, char* err, size_t errlen);
+int fin_search_batch_add_taxa(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_taxonomy* t, uint32_t min_found,
+                              uint32_t confidence_permille, char* err, size_t errlen);
+/* host twins, no device.  The labels: bits uint64[n_unitigs][W]; out[n_unitigs].  FIN_EINVAL for a bad taxonomy, a color_taxon >= n_taxa or a bit at or above
+ * n_colors; FIN_ELIMIT for n_colors outside 1 .. 4096 */
+int fin_unitig_lca_labels(const uint64_t* bits, uint64_t n_unitigs, uint32_t n_colors, const uint32_t* parent, uint64_t n_taxa, const uint32_t* color_taxon,
+                          uint32_t* out, int n_threads);
+/* ... the read taxa from records + stream (the sibling of fin_records_read_classes, with its refusals; a label >= n_taxa that is not FIN_NO_LABEL and a
+ * confidence_permille above 1000 are FIN_EINVAL too).  Written from the definitions above, level by level. */
+int fin_records_read_taxa(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint32_t* unitig_labels,
+                          uint64_t n_unitigs, const uint32_t* parent, uint64_t n_taxa, uint32_t min_found, uint32_t confidence_permille, fin_read_taxon* out,
+                          int n_threads);
+/* ... the roll-up: direct[n_taxa] (an entry n_taxa is not read), clade_out[n_taxa] */
+int fin_taxa_clade_reads(const uint64_t* direct, const uint32_t* parent, uint64_t n_taxa, uint64_t* clade_out);
+
 /* diagnostic (tests): the compact k-mer table of the replica on `device` asked about n k-mers, each given as its two key words (2-bit codes A=0 C=1 G=2 T=3, first
  * base in the low bits; k0 = bases 0..31, k1 = bases 32..k-1, 0 for k <= 32): out[2 i] = the answer g the table claims, out[2 i + 1] = flags -- 0 no claim (the
  * k-mer is in no unitig), 1 a verified claim, 2 an unverified one (| 8: the exact side table has the k-mer, g is its answer), | 4 the text at [g-k+1, g] spells
