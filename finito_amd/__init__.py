@@ -274,6 +274,21 @@ def lib():
         L.fin_colors_download.argtypes = [vp, u64p, u64p, cp, C.c_size_t]
         L.fin_colors_free.argtypes = [vp]
         L.fin_colors_free.restype = None
+        u32p = C.POINTER(C.c_uint32)
+        L.fin_colors_compact.argtypes = [vp, u64, vp, cp, C.c_size_t]
+        L.fin_colors_expand.argtypes = [vp, vp, cp, C.c_size_t]
+        L.fin_colors_is_compact.argtypes = [vp]
+        L.fin_colors_n_sets.argtypes = [vp]
+        L.fin_colors_n_sets.restype = u64
+        L.fin_colors_device_set_of.argtypes = [vp]
+        L.fin_colors_device_set_of.restype = vp
+        L.fin_colors_device_sets.argtypes = [vp]
+        L.fin_colors_device_sets.restype = vp
+        L.fin_colors_download_sets.argtypes = [vp, u32p, u64p, u64, u64p, cp, C.c_size_t]
+        L.fin_colors_upload_sets.argtypes = [vp, u32p, u64p, u64, cp, C.c_size_t]
+        L.fin_colors_compact_stats.argtypes = [vp, u64p]
+        L.fin_unitig_color_sets.argtypes = [u64p, u64, u32, u32p, u64p, u64, u64p, C.c_int]
+        L.fin_color_sets_expand.argtypes = [u32p, u64p, u64, u64, u32, u64p, C.c_int]
         L.fin_batch_add_colors.argtypes = [vp, vp, u32, vp, cp, C.c_size_t]
         L.fin_search_batch_add_colors.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, cp, C.c_size_t]
         L.fin_batch_pseudoalign.argtypes = [vp, vp, u32, cp, C.c_size_t]
@@ -985,7 +1000,73 @@ class Colors(_Accumulator):
         return out[: self.n_unitigs], int(n.value)
 
     def device_ptr(self):
+        """the dense matrix in HBM; 0 while compact"""
         return int(self.L.fin_colors_device_bits(self.h) or 0)
+
+    # ---- the compact state: every distinct row once (fin_colors_compact; DESIGN.md 4.25) ----
+    def compact(self, max_sets=0, stream=None):
+        """deduplicate the rows on the device, behind every add so far, and free the dense matrix: set_of[n_unitigs] and sets[n_sets + 1, W] take its place.
+        max_sets 0: min(n_unitigs, 2^26).  FIN_ELIMIT -- the object unchanged and still dense -- for more distinct non-empty rows than max_sets or a flagged
+        matrix.  pseudoalign and all behind it work unchanged; add / add_reads / coverage / shared / taxonomy want expand() first.  A no-op when compact"""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_compact(self.h, _u64("Colors.compact", "max_sets", max_sets), C.c_void_p(int(stream or 0)), err, 512), err)
+        return self
+
+    def expand(self, stream=None):
+        """back to the dense matrix, gathered on the device (fin_colors_expand); a no-op when dense"""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_expand(self.h, C.c_void_p(int(stream or 0)), err, 512), err)
+        return self
+
+    @property
+    def is_compact(self):
+        return bool(self.L.fin_colors_is_compact(self.h))
+
+    @property
+    def n_sets(self):
+        """the number of sets beside the empty one; 0 while dense"""
+        return int(self.L.fin_colors_n_sets(self.h))
+
+    def device_set_of_ptr(self):
+        return int(self.L.fin_colors_device_set_of(self.h) or 0)
+
+    def device_sets_ptr(self):
+        return int(self.L.fin_colors_device_sets(self.h) or 0)
+
+    def download_sets(self):
+        """(set_of uint32[n_unitigs], sets uint64[n_sets + 1, W]) of a compact object: sets[0] is empty, sets[set_of[u]] is unitig u's row; the order of the ids
+        the device made is unspecified (fin_colors_download_sets)"""
+        n = self.n_sets
+        set_of = np.zeros(max(self.n_unitigs, 1), dtype=np.uint32)
+        sets = np.zeros((n + 1, self.words), dtype=np.uint64)
+        got = C.c_uint64(0)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_download_sets(self.h, set_of.ctypes.data_as(C.POINTER(C.c_uint32)), sets.ctypes.data_as(C.POINTER(C.c_uint64)), n + 1, C.byref(got),
+                                               err, 512), err)
+        return set_of[: self.n_unitigs], sets
+
+    def upload_sets(self, set_of, sets):
+        """make the object compact from host arrays (fin_colors_upload_sets): set_of[n_unitigs], sets[n_sets + 1, W] with sets[0] empty.  Duplicate rows and
+        unused sets are legal"""
+        so = np.asarray(set_of)
+        a = np.asarray(sets)
+        if so.shape != (self.n_unitigs,) or so.dtype.kind not in "iu" or (so.size and (int(so.min()) < 0 or int(so.max()) > 0xFFFFFFFF)):
+            raise FinitoError(FIN_EINVAL, "colors: set_of is %d unsigned 32-bit set ids, got shape %s" % (self.n_unitigs, so.shape))
+        if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != self.words or a.dtype.kind not in "iu":
+            raise FinitoError(FIN_EINVAL, "colors: sets has shape (n_sets + 1, %d), got %s" % (self.words, a.shape))
+        so = np.ascontiguousarray(so, dtype=np.uint32)
+        if self.n_unitigs == 0:
+            so = np.zeros(1, dtype=np.uint32)
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_upload_sets(self.h, so.ctypes.data_as(C.POINTER(C.c_uint32)), a.ctypes.data_as(C.POINTER(C.c_uint64)), a.shape[0] - 1, err, 512), err)
+        return self
+
+    def compact_stats(self):
+        """what the most recent compact() met: (n_sets, rows that met a foreign row under their tag, the longest probe, slots) -- fin_colors_compact_stats"""
+        out = np.zeros(4, dtype=np.uint64)
+        self.L.fin_colors_compact_stats(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return tuple(int(v) for v in out)
 
     def eqclasses(self, max_classes=1 << 20):
         """an accumulator of equivalence classes beside this matrix (EqClasses)"""
@@ -1896,9 +1977,14 @@ class FinimizerIndex:
         _check(self.L.fin_search_batch_taxa(self.h, *_reads_args((bases, offsets)), int(strands), tax.h, *t, out.ctypes.data_as(C.c_void_p), None, err, 512), err)
         return out[:n]
 
-    def colors(self, n_colors, bits=None, device=0):
-        """a colour matrix of this index on `device` (Colors), zeroed or holding `bits`"""
+    def colors(self, n_colors, bits=None, device=0, set_of=None, sets=None):
+        """a colour matrix of this index on `device` (Colors), zeroed or holding `bits`; or compact from the start, from set_of and sets (both or neither;
+        Colors.upload_sets)"""
+        if (set_of is None) != (sets is None) or (bits is not None and sets is not None):
+            raise FinitoError(FIN_EINVAL, "colors: set_of and sets go together, and not beside bits")
         c = Colors(self, n_colors, device)
+        if sets is not None:
+            return c.upload_sets(set_of, sets)
         return c if bits is None else c.upload(bits)
 
     def pseudoalign_reads(self, reads, colors, permille=1000, strands=FIN_MERGED, want_rows=True):
@@ -2558,6 +2644,48 @@ def unitig_color_shared(bits, n_colors, v, n_threads=0):
     if rc != 0:
         raise FinitoError(rc, "fin_unitig_color_shared: a row with a bit at or above n_colors")
     return ColorShared(out)
+
+
+def unitig_color_sets(bits, n_colors, n_threads=0):
+    """host: (set_of uint32[n_unitigs], sets uint64[n_sets + 1, W]) of a colour matrix uint64[n_unitigs, W] in CANONICAL form (fin_unitig_color_sets) -- the CPU
+    statement of Colors.compact: sets[0] empty, sets[1:] = np.unique(axis=0) of the non-empty rows, sets[set_of] == bits"""
+    nc = int(n_colors)
+    if not 1 <= nc <= FIN_MAX_COLORS:
+        raise FinitoError(FIN_ELIMIT, "unitig_color_sets: n_colors is 1 .. 4096")
+    W = (nc + 63) // 64
+    a = np.ascontiguousarray(bits, dtype=np.uint64).reshape(-1, W)
+    n = len(a)
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    if n >= 1 << 31:
+        raise FinitoError(FIN_ELIMIT, "unitig_color_sets: more than 2^31-1 unitigs")
+    got = C.c_uint64(0)
+    src = a if n else np.zeros((1, W), dtype=np.uint64)
+    set_of = np.zeros(max(n, 1), dtype=np.uint32)
+    sets = np.zeros((n + 1, W), dtype=np.uint64)     # room for every row being a set of its own: one call
+    rc = lib().fin_unitig_color_sets(src.ctypes.data_as(u64p), n, nc, set_of.ctypes.data_as(u32p), sets.ctypes.data_as(u64p), n + 1, C.byref(got), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_unitig_color_sets: a row with a bit at or above n_colors")
+    return set_of[:n], sets[: int(got.value) + 1].copy()
+
+
+def color_sets_expand(set_of, sets, n_colors=None, n_threads=0):
+    """host: the dense matrix uint64[n_unitigs, W] back from (set_of, sets) (fin_color_sets_expand).  n_colors None: all 64 W bits of a row may be used"""
+    a = np.ascontiguousarray(sets, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[0] < 1 or not 1 <= a.shape[1] <= 64:
+        raise FinitoError(FIN_EINVAL, "color_sets_expand: sets has shape (n_sets + 1, W), W in 1 .. 64")
+    W = a.shape[1]
+    nc = 64 * W if n_colors is None else int(n_colors)
+    if not 1 <= nc <= FIN_MAX_COLORS or (nc + 63) // 64 != W:
+        raise FinitoError(FIN_ELIMIT, "color_sets_expand: n_colors does not go with W = %d" % W)
+    so = np.ascontiguousarray(set_of, dtype=np.uint32).reshape(-1)
+    n = len(so)
+    out = np.zeros((max(n, 1), W), dtype=np.uint64)
+    src = so if n else np.zeros(1, dtype=np.uint32)
+    rc = lib().fin_color_sets_expand(src.ctypes.data_as(C.POINTER(C.c_uint32)), a.ctypes.data_as(C.POINTER(C.c_uint64)), n, a.shape[0] - 1, nc,
+                                     out.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_color_sets_expand: a set id above n_sets, a non-empty set 0 or a bit at or above n_colors")
+    return out[:n]
 
 
 def _u64(what, name, v):

@@ -99,7 +99,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_colcov_chunk, O_colsim_chunk, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_colcov_chunk, O_colsim_chunk, O_colorsets_tag_bits, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -140,6 +140,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"assign_rpb", 0, 0, 1ll << 26},               // fin_assign_rows: rows per block of fin_assign_rows_kernel (fin_assign.hip); 0 = auto: 1024, more once that would make over 2048 blocks; never so few that there would be over 2^20 blocks.  The results do not depend on it; tests set 64 so that small cases cross block seams
     {"colcov_chunk", 0, 0, 1ll << 26},             // fin_colors_coverage: unitigs per chunk of fin_colcov_column_kernel (fin_colcov.hip), rounded up to a multiple of 64; 0 = auto: 1024, more once that would make over 8192 waves; never so few that there would be over 2^20 chunks.  The results do not depend on it; tests set 64 so that small cases cross chunk seams
     {"colsim_chunk", 0, 0, 1ll << 26},             // fin_colors_shared: unitigs per chunk of fin_colsim_tile_kernel (fin_colsim.hip), rounded up to a multiple of 64; 0 = auto: 4096, more once that would make over 16384 waves; never so few that tiles x chunks would pass 2^30 blocks.  The results do not depend on it; tests set 64 so that small cases cross chunk seams
+    {"colorsets_tag_bits", 31, 1, 31},             // fin_colors_compact: bits of a row's tag in the dedup table (fin_colorsets.hip); the home slot is a function of the tag, so tests narrow it to force distinct rows under one tag and long probe chains.  The results do not depend on it
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -1531,6 +1532,17 @@ struct AccPending {
         reset_st = st;
         return mark_locked(st, err, errlen);
     }
+    // a change of the accumulator's FORM (fin_colors_compact, fin_colors_expand) is ordered as a reset is: f() puts its work on `st` behind everything issued so
+    // far, with the one lock held from the waits to the two records; every later add on another stream runs behind it.  f() failed: nothing is recorded
+    template <class F> int reform(hipStream_t st, F&& f, char* err, size_t errlen) {
+        std::lock_guard<std::mutex> g(mu);
+        if (const int orc = order_locked(st, err, errlen)) return orc;
+        if (const int frc = f()) return frc;
+        if (!reset_ev) HIPCHK(hipEventCreateWithFlags(&reset_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(reset_ev, st));
+        reset_st = st;
+        return mark_locked(st, err, errlen);
+    }
     int behind_reset(hipStream_t st, char* err, size_t errlen) {
         std::lock_guard<std::mutex> g(mu);
         if (reset_ev && reset_st != st) HIPCHK(hipStreamWaitEvent(st, reset_ev, 0));
@@ -1823,7 +1835,12 @@ int fin_batch_add_classes(fin_batch* b, fin_labels* l, uint32_t min_found, uint3
 static_assert(sizeof(fin_read_pseudo) == 16, "a pseudoalignment head is 16 bytes");
 struct fin_colors : fin_acc {
     uint64_t n_unitigs = 0; uint32_t n_colors = 0, words = 0;
-    void* d_bits = nullptr;     // uint64[n_unitigs * words], then the flag word (fin_launch_colors_add)
+    void* d_bits = nullptr;     // DENSE: uint64[n_unitigs * words], then the flag word (fin_launch_colors_add); null while compact
+    // COMPACT (fin_colorsets.hip; fin_colors_compact, fin_colors_upload_sets): these two in place of d_bits.  A compact object has no flags: a flagged matrix is not compacted
+    bool compact = false; uint64_t n_sets = 0;
+    void* d_set_of = nullptr;   // uint32[n_unitigs]
+    void* d_sets = nullptr;     // uint64[(n_sets + 1) * words], row 0 zero
+    uint64_t cs_stats[4] = {0, 0, 0, 0};   // fin_colors_compact_stats
     // fin_colors_coverage's: made by the first call, kept
     void* d_ccv = nullptr;      // uint64[(n_colors + 1) * 8]: the table and the uncoloured entry; then the class byte of every unitig
     std::mutex ccv_mu;          // one projection at a time goes through d_ccv
@@ -1833,7 +1850,7 @@ static uint32_t* colors_flags(const fin_colors* c) { return (uint32_t*)((char*)c
 
 void fin_colors_free(fin_colors* c) {
     if (!acc_free_open(c)) return;
-    (void)hipFree(c->d_bits); (void)hipFree(c->d_ccv);
+    (void)hipFree(c->d_bits); (void)hipFree(c->d_ccv); (void)hipFree(c->d_set_of); (void)hipFree(c->d_sets);
     delete c;
 }
 
@@ -1850,27 +1867,76 @@ int fin_colors_create(const fin_index* idx, int device, uint32_t n_colors, fin_c
     return FIN_OK;
 }
 
+// the two forms of a fin_colors (finito_amd.h, "DEDUPLICATED COLOUR SETS").  What reads bits[u * W + w] directly refuses a compact object with this message
+static const char* const COLORS_COMPACT = "the colours are compact (deduplicated sets): fin_colors_expand first";
+static int colors_want_dense(const fin_colors* c, char* err, size_t errlen) {
+    if (!c->compact) return FIN_OK;
+    set_err(err, errlen, COLORS_COMPACT);
+    return FIN_EINVAL;
+}
+// a compact object gets an (unwritten) dense matrix in place of its sets: what fin_colors_upload and fin_colors_reset then fill.  The device is current; the sets
+// are freed once the device has finished whatever still reads them
+static int colors_make_dense(fin_colors* c, char* err, size_t errlen) {
+    if (!c->compact) return FIN_OK;
+    void* bits = nullptr;
+    if (hipMalloc(&bits, colors_bytes(c) + 8) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (colour matrix)"); return FIN_ENOMEM; }
+    (void)hipDeviceSynchronize();
+    (void)hipFree(c->d_set_of); (void)hipFree(c->d_sets);
+    c->d_set_of = c->d_sets = nullptr; c->d_bits = bits; c->compact = false; c->n_sets = 0;
+    for (uint64_t& v : c->cs_stats) v = 0;  // (they describe the compact form that goes)
+    return FIN_OK;
+}
+
 int fin_colors_upload(fin_colors* c, const uint64_t* bits, char* err, size_t errlen) {
     if (!c || (c->n_unitigs && !bits)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     const uint64_t bad = colors_first_stray(bits, c->n_unitigs, c->n_colors, c->words);
     if (bad != c->n_unitigs) { set_err(err, errlen, "unitig " + std::to_string(bad) + " has a bit at or above n_colors = " + std::to_string(c->n_colors) + " set"); return FIN_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
     if (const int wrc = c->pend.wait(err, errlen)) return wrc;
+    if (const int drc = colors_make_dense(c, err, errlen)) return drc;
     if (c->n_unitigs) HIPCHK(hipMemcpy(c->d_bits, bits, colors_bytes(c), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(colors_flags(c), 0, 8));
     return FIN_OK;
 }
 
 int fin_colors_reset(fin_colors* c, void* hip_stream) {
+    if (c && c->compact) {
+        if (hipSetDevice(c->device) != hipSuccess) return FIN_ENODEV;
+        if (const int drc = colors_make_dense(c, nullptr, 0)) return drc;
+    }
     return acc_reset(c, hip_stream, c ? c->d_bits : nullptr, c ? colors_bytes(c) + 8 : 0);
 }
 
-void* fin_colors_device_bits(const fin_colors* c) { return c ? c->d_bits : nullptr; }
+void* fin_colors_device_bits(const fin_colors* c) { return c && !c->compact ? c->d_bits : nullptr; }
 uint32_t fin_colors_n_colors(const fin_colors* c) { return c ? c->n_colors : 0; }
 uint32_t fin_colors_words(const fin_colors* c) { return c ? c->words : 0; }
 
+// the sets of a compact object on the host (the device current, the object's work waited for)
+static int colors_sets_to_host(fin_colors* c, std::vector<uint32_t>& set_of, std::vector<uint64_t>& sets, char* err, size_t errlen) {
+    set_of.resize((size_t)c->n_unitigs); sets.resize((size_t)(c->n_sets + 1) * c->words);
+    if (c->n_unitigs) HIPCHK(hipMemcpy(set_of.data(), c->d_set_of, (size_t)c->n_unitigs * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sets.data(), c->d_sets, sets.size() * 8, hipMemcpyDeviceToHost));
+    return FIN_OK;
+}
+// fin_colors_download of a compact object: the dense matrix expanded on the host, the set bits counted per set; the object stays compact
+static int colors_download_compact(fin_colors* c, uint64_t* bits_out, uint64_t* n_set, char* err, size_t errlen) {
+    if (const int orc = acc_download_open(c, nullptr, nullptr, nullptr, err, errlen)) return orc;   // (a compact object has no flags)
+    if (!bits_out && !n_set) return FIN_OK;
+    std::vector<uint32_t> set_of; std::vector<uint64_t> sets;
+    if (const int rc = colors_sets_to_host(c, set_of, sets, err, errlen)) return rc;
+    const uint32_t W = c->words;
+    if (bits_out) for (size_t u = 0; u < set_of.size(); u++) memcpy(bits_out + u * W, sets.data() + (size_t)set_of[u] * W, (size_t)W * 8);
+    if (n_set) {
+        std::vector<uint32_t> pc((size_t)c->n_sets + 1, 0);
+        for (size_t q = 0; q < pc.size(); q++) pc[q] = (uint32_t)sum_of(sets.data() + q * W, W, [](uint64_t w) { return __builtin_popcountll(w); });
+        *n_set = sum_of(set_of.data(), set_of.size(), [&](uint32_t q) { return pc[q]; });
+    }
+    return FIN_OK;
+}
+
 int fin_colors_download(fin_colors* c, uint64_t* bits_out, uint64_t* n_set, char* err, size_t errlen) {
     if (!c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (c->compact) return colors_download_compact(c, bits_out, n_set, err, errlen);
     if (const int orc = acc_download_open(c, colors_flags(c), "a step whose overflow list overran was added: it has no results, nothing of it was coloured (reset the colours)",
                                           nullptr, err, errlen)) return orc;
     if (!bits_out && !n_set) return FIN_OK;
@@ -1882,9 +1948,124 @@ int fin_colors_download(fin_colors* c, uint64_t* bits_out, uint64_t* n_set, char
     return FIN_OK;
 }
 
+// ---- the compact state: deduplicated colour sets (fin_colorsets.hip) ----
+int fin_colors_is_compact(const fin_colors* c) { return c && c->compact ? 1 : 0; }
+uint64_t fin_colors_n_sets(const fin_colors* c) { return c && c->compact ? c->n_sets : 0; }
+void* fin_colors_device_set_of(const fin_colors* c) { return c && c->compact ? c->d_set_of : nullptr; }
+void* fin_colors_device_sets(const fin_colors* c) { return c && c->compact ? c->d_sets : nullptr; }
+int fin_colors_compact_stats(const fin_colors* c, uint64_t out[4]) {
+    if (!c || !out) return FIN_EINVAL;
+    for (int q = 0; q < 4; q++) out[q] = c->cs_stats[q];
+    return FIN_OK;
+}
+
+int fin_colors_compact(fin_colors* c, uint64_t max_sets, void* hip_stream, char* err, size_t errlen) {
+    if (!c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (max_sets > (1ull << 26)) { set_err(err, errlen, "max_sets is at most 2^26 (0: the number of unitigs, at most 2^26)"); return FIN_ELIMIT; }
+    if (max_sets == 0) max_sets = std::min<uint64_t>(c->n_unitigs, 1ull << 26);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    uint32_t lg = 1;
+    while ((1ull << lg) < 2 * max_sets) lg++;
+    // (n_unitigs, words and the index are fixed at creation: what is computed here does not depend on the object's form)
+    const uint32_t n = (uint32_t)c->n_unitigs, W = c->words, tag_bits = (uint32_t)optv(c->idx, O_colorsets_tag_bits);
+    const size_t n_slots = (size_t)1 << lg, nsb = fin_cs_blocks((uint32_t)n_slots);
+    // the scratch, sized from n_unitigs and max_sets alone: slots u64 | ctr 4 u64, total | blk_off u64 | slot_of u32 (padded) | slot_id u32 | blk_sum u32
+    const size_t o_ctr = n_slots * 8, o_off = o_ctr + 5 * 8, o_slot_of = o_off + nsb * 8, o_slot_id = o_slot_of + (((size_t)n + 1) & ~(size_t)1) * 4, o_sum = o_slot_id + n_slots * 4,
+                 tmp_bytes = o_sum + nsb * 4 + 16;
+    return c->pend.reform(st, [&]() -> int {
+        if (c->compact) return FIN_OK;      // the form is looked at with the object's lock held
+        uint32_t flags = 0;
+        HIPCHK(hipMemcpyAsync(&flags, colors_flags(c), 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (flags & 1u) { set_err(err, errlen, "a step whose overflow list overran was added: the matrix is not compacted (reset the colours)"); return FIN_ELIMIT; }
+        char* tmp = nullptr;
+        if (hipMalloc((void**)&tmp, tmp_bytes) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (colour set table)"); return FIN_ENOMEM; }
+        void* d_sets = nullptr; void* d_set_of = nullptr;
+        uint64_t ctr[5] = {0, 0, 0, 0, 0};
+        auto fail = [&](int code, const std::string& msg) { (void)hipStreamSynchronize(st); (void)hipFree(tmp); (void)hipFree(d_sets); (void)hipFree(d_set_of); set_err(err, errlen, msg); return code; };
+        if (hipMemsetAsync(tmp, 0, o_off, st) != hipSuccess) return fail(FIN_ENODEV, "hipMemsetAsync failed");
+        int rc = fin_launch_cs_claim(c->d_bits, n, W, tmp, lg, tag_bits, max_sets, (uint32_t*)(tmp + o_slot_of), tmp + o_ctr, (uint32_t*)(tmp + o_sum), (uint64_t*)(tmp + o_off),
+                                     (uint64_t*)(tmp + o_ctr) + 4, st);
+        if (rc != 0) return fail(FIN_ENODEV, std::string("colour set kernels: ") + hipGetErrorString((hipError_t)rc));
+        if (hipMemcpyAsync(ctr, tmp + o_ctr, sizeof ctr, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(FIN_ENODEV, "reading the colour set counters failed");
+        if ((ctr[3] & 1u) || ctr[4] > max_sets)
+            return fail(FIN_ELIMIT, "more than max_sets = " + std::to_string(max_sets) + " distinct non-empty colour rows: the matrix stays dense");
+        const uint64_t n_sets = ctr[4];
+        if (hipMalloc(&d_sets, (size_t)(n_sets + 1) * W * 8) != hipSuccess || hipMalloc(&d_set_of, (size_t)n * 4 + 16) != hipSuccess) {
+            (void)hipGetLastError(); return fail(FIN_ENOMEM, "out of device memory (colour sets)");
+        }
+        rc = fin_launch_cs_gather(c->d_bits, n, W, tmp, lg, (const uint32_t*)(tmp + o_slot_of), (const uint64_t*)(tmp + o_off), (uint32_t*)(tmp + o_slot_id), d_sets,
+                                  (uint32_t*)d_set_of, st);
+        if (rc != 0) return fail(FIN_ENODEV, std::string("colour set kernels: ") + hipGetErrorString((hipError_t)rc));
+        if (hipDeviceSynchronize() != hipSuccess) return fail(FIN_ENODEV, "the colour set kernels failed");   // (and nothing reads the dense matrix any more)
+        (void)hipFree(tmp); (void)hipFree(c->d_bits);
+        c->d_bits = nullptr; c->d_sets = d_sets; c->d_set_of = d_set_of; c->n_sets = n_sets; c->compact = true;
+        c->cs_stats[0] = n_sets; c->cs_stats[1] = ctr[1]; c->cs_stats[2] = ctr[2]; c->cs_stats[3] = n_slots;
+        return FIN_OK;
+    }, err, errlen);
+}
+
+int fin_colors_expand(fin_colors* c, void* hip_stream, char* err, size_t errlen) {
+    if (!c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    return c->pend.reform(st, [&]() -> int {
+        if (!c->compact) return FIN_OK;     // the form is looked at with the object's lock held
+        void* bits = nullptr;
+        if (hipMalloc(&bits, colors_bytes(c) + 8) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (colour matrix)"); return FIN_ENOMEM; }
+        const int rc = fin_launch_cs_expand((const uint32_t*)c->d_set_of, c->d_sets, (uint32_t)c->n_unitigs, c->words, bits, st);
+        if (rc != 0 || hipMemsetAsync((char*)bits + colors_bytes(c), 0, 8, st) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            (void)hipFree(bits); set_err(err, errlen, "colour set expand kernel failed"); return FIN_ENODEV;
+        }
+        (void)hipFree(c->d_set_of); (void)hipFree(c->d_sets);
+        c->d_set_of = c->d_sets = nullptr; c->d_bits = bits; c->compact = false; c->n_sets = 0;
+        for (uint64_t& v : c->cs_stats) v = 0;
+        return FIN_OK;
+    }, err, errlen);
+}
+
+int fin_colors_download_sets(fin_colors* c, uint32_t* set_of_out, uint64_t* sets_out, uint64_t cap_sets, uint64_t* n_sets, char* err, size_t errlen) {
+    if (n_sets) *n_sets = c && c->compact ? c->n_sets : 0;
+    if (!c || !n_sets) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!c->compact) { set_err(err, errlen, "the colours are dense: fin_colors_compact or fin_colors_upload_sets first"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(c, nullptr, nullptr, nullptr, err, errlen)) return orc;
+    if (cap_sets < c->n_sets + 1) { set_err(err, errlen, "room for " + std::to_string(cap_sets) + " rows, the sets are " + std::to_string(c->n_sets) + " + the empty one"); return FIN_ELIMIT; }
+    if (set_of_out && c->n_unitigs) HIPCHK(hipMemcpy(set_of_out, c->d_set_of, (size_t)c->n_unitigs * 4, hipMemcpyDeviceToHost));
+    if (sets_out) HIPCHK(hipMemcpy(sets_out, c->d_sets, (size_t)(c->n_sets + 1) * c->words * 8, hipMemcpyDeviceToHost));
+    return FIN_OK;
+}
+
+int fin_colors_upload_sets(fin_colors* c, const uint32_t* set_of, const uint64_t* sets, uint64_t n_sets, char* err, size_t errlen) {
+    if (!c || !sets || (c->n_unitigs && !set_of)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (n_sets > 0xFFFFFFFEull) { set_err(err, errlen, "at most 2^32 - 2 sets"); return FIN_ELIMIT; }
+    const uint32_t W = c->words;
+    for (uint32_t w = 0; w < W; w++) if (sets[w]) { set_err(err, errlen, "set 0 is the empty set: its row has a bit set"); return FIN_EINVAL; }
+    const uint64_t bad = colors_first_stray(sets, n_sets + 1, c->n_colors, W);
+    if (bad != n_sets + 1) { set_err(err, errlen, "set " + std::to_string(bad) + " has a bit at or above n_colors = " + std::to_string(c->n_colors) + " set"); return FIN_EINVAL; }
+    for (uint64_t u = 0; u < c->n_unitigs; u++)
+        if (set_of[u] > n_sets) { set_err(err, errlen, "unitig " + std::to_string(u) + " has set " + std::to_string(set_of[u]) + ": not in 0 .. n_sets = " + std::to_string(n_sets)); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int wrc = c->pend.wait(err, errlen)) return wrc;
+    void* d_sets = nullptr; void* d_set_of = nullptr;
+    if (hipMalloc(&d_sets, (size_t)(n_sets + 1) * W * 8) != hipSuccess || hipMalloc(&d_set_of, (size_t)c->n_unitigs * 4 + 16) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(d_sets); set_err(err, errlen, "out of device memory (colour sets)"); return FIN_ENOMEM;
+    }
+    if (hipMemcpy(d_sets, sets, (size_t)(n_sets + 1) * W * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        (c->n_unitigs && hipMemcpy(d_set_of, set_of, (size_t)c->n_unitigs * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipFree(d_sets); (void)hipFree(d_set_of); set_err(err, errlen, "copying the colour sets failed"); return FIN_ENODEV;
+    }
+    (void)hipDeviceSynchronize();           // nothing reads the form that goes any more
+    (void)hipFree(c->d_bits); (void)hipFree(c->d_set_of); (void)hipFree(c->d_sets);
+    c->d_bits = nullptr; c->d_sets = d_sets; c->d_set_of = d_set_of; c->n_sets = n_sets; c->compact = true;
+    for (uint64_t& v : c->cs_stats) v = 0;  // (no table made these sets)
+    return FIN_OK;
+}
+
 int fin_batch_add_colors(fin_batch* b, fin_colors* c, uint32_t color, void* hip_stream, char* err, size_t errlen) {
     if (!b || !c) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     if (color >= c->n_colors) { set_err(err, errlen, "colour " + std::to_string(color) + " is not below n_colors = " + std::to_string(c->n_colors)); return FIN_EINVAL; }
+    if (const int drc = colors_want_dense(c, err, errlen)) return drc;
     hipStream_t st = (hipStream_t)hip_stream;
     if (const int orc = acc_add_open(b, c, st, err, errlen)) return orc;
     // (no read has a k-mer: the step searched nothing)
@@ -1908,8 +2089,11 @@ int fin_batch_pseudoalign(fin_batch* b, const fin_colors* c, uint32_t permille, 
         set_err(err, errlen, "out of device memory (colour rows of the reads)"); return FIN_ENOMEM;
     }
     if (const int orc = const_cast<fin_colors*>(c)->pend.order(st, err, errlen)) return orc;   // the adds to the matrix, on whichever streams, come first
-    const int rc = fin_launch_pseudoalign(b->n_kmers != 0 && b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, nr, b->dev.k, c->d_bits, c->words,
-                                          (uint32_t)c->n_unitigs, permille, b->d_psa_rows, b->d_psa_heads, st);
+    const void* const frec = b->n_kmers != 0 && b->last_frec ? b->d_frec : nullptr;
+    const int rc = c->compact ? fin_launch_pseudoalign_sets(frec, (const uint64_t*)b->d_out_offs, b->d_out, nr, b->dev.k, c->d_sets, c->words, (uint32_t)c->n_sets,
+                                                            (const uint32_t*)c->d_set_of, (uint32_t)c->n_unitigs, permille, b->d_psa_rows, b->d_psa_heads, st)
+                              : fin_launch_pseudoalign(frec, (const uint64_t*)b->d_out_offs, b->d_out, nr, b->dev.k, c->d_bits, c->words, (uint32_t)c->n_unitigs, permille,
+                                                       b->d_psa_rows, b->d_psa_heads, st);
     if (rc != 0) { set_err(err, errlen, std::string("pseudoalignment kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
     b->psa_ready = true; b->psa_words = c->words;
     return FIN_OK;
@@ -1998,6 +2182,7 @@ int fin_taxonomy_create(const fin_index* idx, int device, const uint32_t* parent
 int fin_taxonomy_create_from_colors(fin_colors* c, const uint32_t* parent, uint64_t n_taxa, const uint32_t* color_taxon, fin_taxonomy** out, char* err, size_t errlen) {
     if (!c || !out || !parent || !color_taxon) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     *out = nullptr;
+    if (const int drc = colors_want_dense(c, err, errlen)) return drc;   // (the labels are made from bits[u * W + w])
     if (const int trc = taxonomy_check(parent, n_taxa, err, errlen)) return trc;
     for (uint32_t q = 0; q < c->n_colors; q++)
         if ((uint64_t)color_taxon[q] >= n_taxa) {
@@ -2121,8 +2306,11 @@ int fin_batch_pseudoalign_paired(fin_batch* b, const fin_colors* c, uint32_t per
         set_err(err, errlen, "out of device memory (colour rows of the fragments)"); return FIN_ENOMEM;
     }
     if (const int orc = const_cast<fin_colors*>(c)->pend.order(st, err, errlen)) return orc;   // the adds to the matrix, on whichever streams, come first
-    const int rc = fin_launch_pseudoalign_paired(b->n_kmers != 0 && b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, nf, b->dev.k, c->d_bits,
-                                                 c->words, (uint32_t)c->n_unitigs, permille, mode, b->d_pair_rows, b->d_pair_heads, st);
+    const void* const frec = b->n_kmers != 0 && b->last_frec ? b->d_frec : nullptr;
+    const int rc = c->compact ? fin_launch_pseudoalign_paired_sets(frec, (const uint64_t*)b->d_out_offs, b->d_out, nf, b->dev.k, c->d_sets, c->words, (uint32_t)c->n_sets,
+                                                                   (const uint32_t*)c->d_set_of, (uint32_t)c->n_unitigs, permille, mode, b->d_pair_rows, b->d_pair_heads, st)
+                              : fin_launch_pseudoalign_paired(frec, (const uint64_t*)b->d_out_offs, b->d_out, nf, b->dev.k, c->d_bits, c->words, (uint32_t)c->n_unitigs,
+                                                              permille, mode, b->d_pair_rows, b->d_pair_heads, st);
     if (rc != 0) { set_err(err, errlen, std::string("paired pseudoalignment kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
     b->pair_ready = true; b->pair_words = c->words;
     return FIN_OK;
@@ -3136,6 +3324,7 @@ int fin_colors_coverage(fin_colors* c, fin_cover* cov, fin_depth* dep, uint32_t 
     if (!c || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     if (cov && (cov->idx != c->idx || cov->device != c->device)) { set_err(err, errlen, "colours and coverage bitmap belong to different indexes or devices"); return FIN_EINVAL; }
     if (dep && (dep->idx != c->idx || dep->device != c->device)) { set_err(err, errlen, "colours and depth accumulator belong to different indexes or devices"); return FIN_EINVAL; }
+    if (const int drc = colors_want_dense(c, err, errlen)) return drc;   // (the projection reads bits[u * W + w])
     // the three waits, with the downloads' own codes and messages for a withheld step or a pair outside the index (nothing else happens in these calls)
     if (const int rc = fin_colors_download(c, nullptr, nullptr, err, errlen)) return rc;
     if (cov) if (const int rc = fin_cover_download(cov, nullptr, nullptr, nullptr, err, errlen)) return rc;
@@ -3174,6 +3363,7 @@ int fin_colors_shared(fin_colors* c, fin_cover* cov, const uint64_t* weights, ui
     if (!c || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
     if (cov && weights) { set_err(err, errlen, "a coverage bitmap and weights were both given: one weight per unitig and call"); return FIN_EINVAL; }
     if (cov && (cov->idx != c->idx || cov->device != c->device)) { set_err(err, errlen, "colours and coverage bitmap belong to different indexes or devices"); return FIN_EINVAL; }
+    if (const int drc = colors_want_dense(c, err, errlen)) return drc;   // (the product reads bits[u * W + w])
     // the two waits, with the downloads' own codes and messages for a withheld step (nothing else happens in these calls)
     if (const int rc = fin_colors_download(c, nullptr, nullptr, err, errlen)) return rc;
     if (cov) if (const int rc = fin_cover_download(cov, nullptr, nullptr, nullptr, err, errlen)) return rc;
@@ -3770,6 +3960,7 @@ int fin_search_batch_add_colors(const fin_index* idx, const char* bases, const u
     int device = -1;
     if (const int orc = search_open(idx, offsets, strands, c, c, OTHER_COLORS, &device, err, errlen)) return orc;
     if (color >= c->n_colors) { set_err(err, errlen, "colour " + std::to_string(color) + " is not below n_colors = " + std::to_string(c->n_colors)); return FIN_EINVAL; }
+    if (const int drc = colors_want_dense(c, err, errlen)) return drc;
     if (n_reads == 0) return FIN_OK;
     Product p;   // every sub-batch's unitigs get the colour on the device, nothing comes back
     p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_colors(b, c, color, own(b), e, elen); };

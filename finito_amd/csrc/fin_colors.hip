@@ -28,6 +28,10 @@
 //             popcount.  Counts are additive over rows: exact, at W + 1 rescans for a read that rare.
 // No LDS, no atomics, no global scratch on the per-read result; every output word has one writer.  A slot whose unitig number is at or above n_unitigs counts as
 // absent.
+//
+// fin_col_pseudo_sets_kernel: the same body over a COMPACT matrix (fin_colorsets.hip) -- every unitig number becomes set_of[u] as it is loaded
+// (fin_wave.h: fin_row_key), bits = sets, n_unitigs = n_sets + 1, and the table is keyed by set id: counts are additive over the unitigs of one set, so only a
+// read with more than 64 distinct SETS is rescanned.  Set 0 is the empty row: "coloured" needs no special case.
 #include "fin_device.h"
 #include "fin_kernels.h"
 #include "fin_wave.h"
@@ -54,13 +58,15 @@ __device__ __forceinline__ void col_add_scan(const int2* pairs, uint64_t lo, uin
     });
 }
 
-// slots [lo, hi) are one read's: its row into out[0 .. W), its head {n_found, n_coloured, popcount of the row} returned in every lane.  Wave-converged
+// slots [lo, hi) are one read's: its row into out[0 .. W), its head {n_found, n_coloured, popcount of the row} returned in every lane.  Wave-converged.
+// SETS: the rows are keyed by set id (fin_row_key): bits = sets, n_unitigs = n_sets + 1, set_of and n_u the map and the index's unitigs
+template <bool SETS>
 __device__ __forceinline__ uint4 col_pseudo_scan(const int2* pairs, uint64_t lo, uint64_t hi, const ull* bits, uint32_t W, uint32_t n_unitigs, uint32_t permille,
-                                                 ull* out) {
+                                                 ull* out, const uint32_t* set_of, uint32_t n_u) {
     uint32_t n_found = 0;
     FinUnitigTable tab;
     fin_each_pair_row(pairs, lo, hi, [&](uint64_t, uint64_t, int2 p) {
-        const uint32_t u = (uint32_t)p.x;
+        const uint32_t u = fin_row_key<SETS>((uint32_t)p.x, set_of, n_u);
         n_found += (uint32_t)__popcll(__ballot(u < n_unitigs));
         fin_each_distinct(u, u < n_unitigs, [&](int, uint32_t uc, ull m) { (void)tab.add(uc, (uint32_t)__popcll(m)); });
     });
@@ -70,38 +76,24 @@ __device__ __forceinline__ uint4 col_pseudo_scan(const int2* pairs, uint64_t lo,
         const uint64_t need = (uint64_t)permille * n_colored;
         for (uint32_t w = 0; w < W; w++) pc += fin_row_word(tab.word_counts(bits, W, w), need, true, out, w);
     } else {
-        n_colored = fin_rescan_colored(pairs, lo, hi, bits, W, n_unitigs);
+        n_colored = fin_rescan_colored<SETS>(pairs, lo, hi, bits, W, n_unitigs, set_of, n_u);
         const uint64_t need = (uint64_t)permille * n_colored;
-        for (uint32_t w = 0; w < W; w++) pc += fin_row_word(fin_rescan_word(pairs, lo, hi, bits, W, n_unitigs, w), need, true, out, w);
+        for (uint32_t w = 0; w < W; w++) pc += fin_row_word(fin_rescan_word<SETS>(pairs, lo, hi, bits, W, n_unitigs, w, set_of, n_u), need, true, out, w);
     }
     return make_uint4(n_found, n_colored, pc, 0u);
 }
 
-}  // namespace
-
-// bits[u][color] = 1 for every unitig u in which the run found a k-mer.  frec null: the step left no records, every read is scanned.
-__global__ __launch_bounds__(256) void fin_col_add_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k, ull* bits,
-                                                          uint32_t W, uint32_t n_unitigs, uint32_t color, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap) {
-    if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
-    const FinReadItem it = fin_read_item<false>(frec, out_offs, blockIdx.x * FIN_COL_BLK + threadIdx.x, n_reads);
-    if (it.kind == 1u && it.a.w != 0u && it.a.x < n_unitigs) {
-        uint32_t n = 0;
-        (void)sgm_rec_walk(it.a, it.load_b(), k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
-        if (n != 0u) col_or(bits, (uint64_t)it.a.x * W + (color >> 6), 1ull << (color & 63u));
-    }
-    fin_each_searched_read(it, [&](int, uint64_t lo, uint64_t hi) { col_add_scan(pairs, lo, hi, bits, W, n_unitigs, color); });
-}
-
-// rows[r][0 .. W) = read r's colour row, heads[r] = {n_found, n_coloured, popcount, 0}.  frec null: the step left no records, every read is scanned.
-__global__ __launch_bounds__(256) void fin_col_pseudo_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
-                                                             const ull* bits, uint32_t W, uint32_t n_unitigs, uint32_t permille, ull* rows, uint4* heads) {
+// the body of fin_col_pseudo_kernel and, with SETS, of fin_col_pseudo_sets_kernel: there a kind-1 record's unitig becomes its set id as well
+template <bool SETS>
+__device__ __forceinline__ void col_pseudo_body(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k, const ull* bits,
+                                                uint32_t W, uint32_t n_unitigs, uint32_t permille, ull* rows, uint4* heads, const uint32_t* set_of, uint32_t n_u) {
     const uint32_t r = blockIdx.x * FIN_COL_BLK + threadIdx.x, lane = threadIdx.x & 63u;
     const uint32_t r0 = r - lane;           // the wave's first read
     const FinReadItem it = fin_read_item<false>(frec, out_offs, r, n_reads);
     uint32_t u = 0, n = 0;                  // a kind-1 read's unitig and found slots
-    if (it.kind == 1u && it.a.w != 0u && it.a.x < n_unitigs) {
+    if (it.kind == 1u && it.a.w != 0u && it.a.x < (SETS ? n_u : n_unitigs)) {
         (void)sgm_rec_walk(it.a, it.load_b(), k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
-        u = it.a.x;
+        u = fin_row_key<SETS>(it.a.x, set_of, n_u);
     }
     const bool scanned = it.scanned();
     uint4 mine = make_uint4(0u, 0u, 0u, 0u);
@@ -125,10 +117,37 @@ __global__ __launch_bounds__(256) void fin_col_pseudo_kernel(const FinFastRec* f
         });
     }
     fin_each_searched_read(it, [&](int src, uint64_t lo, uint64_t hi) {
-        const uint4 s = col_pseudo_scan(pairs, lo, hi, bits, W, n_unitigs, permille, rows + (uint64_t)(r0 + (uint32_t)src) * W);
+        const uint4 s = col_pseudo_scan<SETS>(pairs, lo, hi, bits, W, n_unitigs, permille, rows + (uint64_t)(r0 + (uint32_t)src) * W, set_of, n_u);
         if ((int)lane == src) mine = s;
     });
     if (r < n_reads) heads[r] = mine;
+}
+
+}  // namespace
+
+// bits[u][color] = 1 for every unitig u in which the run found a k-mer.  frec null: the step left no records, every read is scanned.
+__global__ __launch_bounds__(256) void fin_col_add_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k, ull* bits,
+                                                          uint32_t W, uint32_t n_unitigs, uint32_t color, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap) {
+    if (fin_step_withheld(ovf_count, ovf_cap, flags)) return;
+    const FinReadItem it = fin_read_item<false>(frec, out_offs, blockIdx.x * FIN_COL_BLK + threadIdx.x, n_reads);
+    if (it.kind == 1u && it.a.w != 0u && it.a.x < n_unitigs) {
+        uint32_t n = 0;
+        (void)sgm_rec_walk(it.a, it.load_b(), k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
+        if (n != 0u) col_or(bits, (uint64_t)it.a.x * W + (color >> 6), 1ull << (color & 63u));
+    }
+    fin_each_searched_read(it, [&](int, uint64_t lo, uint64_t hi) { col_add_scan(pairs, lo, hi, bits, W, n_unitigs, color); });
+}
+
+// rows[r][0 .. W) = read r's colour row, heads[r] = {n_found, n_coloured, popcount, 0}.  frec null: the step left no records, every read is scanned.
+__global__ __launch_bounds__(256) void fin_col_pseudo_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
+                                                             const ull* bits, uint32_t W, uint32_t n_unitigs, uint32_t permille, ull* rows, uint4* heads) {
+    col_pseudo_body<false>(frec, out_offs, pairs, n_reads, k, bits, W, n_unitigs, permille, rows, heads, nullptr, 0u);
+}
+// the same over a compact matrix: sets uint64[(n_sets + 1) * W] and set_of[n_unitigs]; every unitig number becomes its set id as it is loaded
+__global__ __launch_bounds__(256) void fin_col_pseudo_sets_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_reads, uint32_t k,
+                                                                  const ull* sets, uint32_t W, uint32_t n_sets1, const uint32_t* set_of, uint32_t n_unitigs,
+                                                                  uint32_t permille, ull* rows, uint4* heads) {
+    col_pseudo_body<true>(frec, out_offs, pairs, n_reads, k, sets, W, n_sets1, permille, rows, heads, set_of, n_unitigs);
 }
 
 // bits: uint64[n_unitigs * W]; flags: one u32 (bit 0: a step without results was offered).  frec null: every read is scanned.  ovf_count (may be null) / ovf_cap:
@@ -148,5 +167,14 @@ extern "C" int fin_launch_pseudoalign(const void* frec, const uint64_t* out_offs
     if (nb == 0) return 0;
     hipLaunchKernelGGL(fin_col_pseudo_kernel, dim3(nb), dim3(256), 0, stream, (const FinFastRec*)frec, out_offs, (const int2*)pairs, n_reads, k, (const ull*)bits, W,
                        n_unitigs, permille, (ull*)rows, (uint4*)heads);
+    return (int)hipGetLastError();
+}
+// the same over a compact matrix: sets uint64[(n_sets + 1) * W], row 0 empty; set_of: uint32[n_unitigs], each <= n_sets
+extern "C" int fin_launch_pseudoalign_sets(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const void* sets, uint32_t W,
+                                           uint32_t n_sets, const uint32_t* set_of, uint32_t n_unitigs, uint32_t permille, void* rows, void* heads, hipStream_t stream) {
+    const uint32_t nb = (n_reads + FIN_COL_BLK - 1u) / FIN_COL_BLK;
+    if (nb == 0) return 0;
+    hipLaunchKernelGGL(fin_col_pseudo_sets_kernel, dim3(nb), dim3(256), 0, stream, (const FinFastRec*)frec, out_offs, (const int2*)pairs, n_reads, k, (const ull*)sets, W,
+                       n_sets + 1u, set_of, n_unitigs, permille, (ull*)rows, (uint4*)heads);
     return (int)hipGetLastError();
 }

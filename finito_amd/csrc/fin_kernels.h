@@ -204,6 +204,24 @@ int fin_launch_pseudoalign(const void* frec, const uint64_t* out_offs, const voi
 // n_coloured of the first mate} under the threshold permille; mode 0: any mate, 1: the row is zero unless both mates have a coloured slot
 int fin_launch_pseudoalign_paired(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_frags, uint32_t k, const void* bits, uint32_t W,
                                   uint32_t n_unitigs, uint32_t permille, uint32_t mode, void* rows, void* heads, hipStream_t stream);
+// ... over a COMPACT matrix (fin_colorsets.hip's state): sets uint64[(n_sets + 1) * W] with row 0 empty, set_of uint32[n_unitigs], each <= n_sets.  A unitig number
+// becomes its set id as it is loaded, the register table is keyed by set id; the results are those of the dense launch over the expanded matrix, bit for bit
+int fin_launch_pseudoalign_sets(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const void* sets, uint32_t W, uint32_t n_sets,
+                                const uint32_t* set_of, uint32_t n_unitigs, uint32_t permille, void* rows, void* heads, hipStream_t stream);
+int fin_launch_pseudoalign_paired_sets(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_frags, uint32_t k, const void* sets, uint32_t W,
+                                       uint32_t n_sets, const uint32_t* set_of, uint32_t n_unitigs, uint32_t permille, uint32_t mode, void* rows, void* heads,
+                                       hipStream_t stream);
+// fin_colorsets.hip -- the distinct rows of a colour matrix, each once.  fin_launch_cs_claim: slots (2^lg u64, lg 1 .. 27) and ctr (4 u64: slots claimed, rows that
+// met a foreign row under their tag, the longest probe, flags -- bit 0: the table or max_sets overran) zeroed by the caller; slot_of n_unitigs u32; blk_sum
+// fin_cs_blocks(2^lg) u32, blk_off as many u64, *total = n_sets.  tag_bits: option "colorsets_tag_bits".  Once the host has read ctr and *total:
+// fin_launch_cs_gather writes sets ((n_sets + 1) rows of W words, row 0 zero) and set_of (n_unitigs u32); slot_id: 2^lg u32 of scratch.
+// fin_launch_cs_expand: bits[u] = sets[set_of[u]]
+uint32_t fin_cs_blocks(uint32_t slots);
+int fin_launch_cs_claim(const void* bits, uint32_t n_unitigs, uint32_t W, void* slots, uint32_t lg, uint32_t tag_bits, uint64_t max_sets, uint32_t* slot_of, void* ctr,
+                        uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total, hipStream_t stream);
+int fin_launch_cs_gather(const void* bits, uint32_t n_unitigs, uint32_t W, const void* slots, uint32_t lg, const uint32_t* slot_of, const uint64_t* blk_off,
+                         uint32_t* slot_id, void* sets, uint32_t* set_of, hipStream_t stream);
+int fin_launch_cs_expand(const uint32_t* set_of, const void* sets, uint32_t n_unitigs, uint32_t W, void* bits, hipStream_t stream);
 // fin_eqclasses.hip -- equivalence classes of colour rows: an open-addressing table of 2^lg slots (tags, counts: a u64 per slot; tab_rows: W u64 per slot; ctr:
 // 8 u64 -- rows added, unaligned, classes, rows through the serial pass, flags, the collision list's length).  fin_launch_ec_add: rows uint64[n_rows * W] are added
 // in three launches (claim, verify and count, collisions serially); slot_of and coll: n_rows u32 of scratch each.  tag_bits / combine: options "ec_tag_bits" and

@@ -29,13 +29,15 @@
 namespace {
 typedef unsigned long long ull;
 
-// read r as a mate: n found slots in unitig u (a kind-1 record), or the pair range [lo, hi) to scan (hi > lo), or nothing (n = 0, hi = lo = 0)
+// read r as a mate: n found slots in unitig u (a kind-1 record), or the pair range [lo, hi) to scan (hi > lo), or nothing (n = 0, hi = lo = 0).
+// SETS (here and below): the rows are keyed by set id (fin_wave.h: fin_row_key) -- bits = sets, n_unitigs = n_sets + 1, set_of and n_u the map and the index's unitigs
+template <bool SETS>
 __device__ __forceinline__ void pr_mate(const FinFastRec* frec, const uint64_t* out_offs, uint32_t r, uint32_t n_reads, uint32_t k, uint32_t n_unitigs, uint32_t& u,
-                                        uint32_t& n, uint64_t& lo, uint64_t& hi) {
+                                        uint32_t& n, uint64_t& lo, uint64_t& hi, const uint32_t* set_of, uint32_t n_u) {
     const FinReadItem it = fin_read_item<false>(frec, out_offs, r, n_reads);
-    if (it.kind == 1u && it.a.w != 0u && it.a.x < n_unitigs) {
+    if (it.kind == 1u && it.a.w != 0u && it.a.x < (SETS ? n_u : n_unitigs)) {
         (void)sgm_rec_walk(it.a, it.load_b(), k, [&](uint32_t, uint32_t from, uint32_t to) { n += to - from; });
-        u = it.a.x;
+        u = fin_row_key<SETS>(it.a.x, set_of, n_u);
     }
     if (it.scanned()) { lo = it.p_lo; hi = it.p_hi; }
 }
@@ -49,10 +51,11 @@ __device__ __forceinline__ ull pr_closed(ull wa, ull wb, uint32_t ca, uint32_t c
 }
 
 // slots [lo, hi) of one mate into the wave's table: its counts, and t_first -- the slots that came from the first mate -- beside them.  Wave-converged
+template <bool SETS>
 __device__ __forceinline__ void pr_table_scan(const int2* pairs, uint64_t lo, uint64_t hi, uint32_t n_unitigs, bool first, uint32_t& n_found, FinUnitigTable& tab,
-                                              uint32_t& t_first) {
+                                              uint32_t& t_first, const uint32_t* set_of, uint32_t n_u) {
     fin_each_pair_row(pairs, lo, hi, [&](uint64_t, uint64_t, int2 p) {
-        const uint32_t u = (uint32_t)p.x;
+        const uint32_t u = fin_row_key<SETS>((uint32_t)p.x, set_of, n_u);
         n_found += (uint32_t)__popcll(__ballot(u < n_unitigs));
         fin_each_distinct(u, u < n_unitigs, [&](int, uint32_t uc, ull m) {
             const uint32_t c = (uint32_t)__popcll(m);
@@ -63,14 +66,15 @@ __device__ __forceinline__ void pr_table_scan(const int2* pairs, uint64_t lo, ui
 
 // one fragment with a scanned mate: slots [alo, ahi) are the first mate's, [blo, bhi) the second's (either may be empty), the seed sn found slots in unitig su
 // (sn = 0: none; sfirst: they are the first mate's).  Its row into out[0 .. W), its head returned in every lane.  Wave-converged
+template <bool SETS>
 __device__ __forceinline__ uint4 pr_scan(const int2* pairs, uint64_t alo, uint64_t ahi, uint64_t blo, uint64_t bhi, uint32_t su, uint32_t sn, bool sfirst, const ull* bits,
-                                         uint32_t W, uint32_t n_unitigs, uint32_t permille, uint32_t mode, ull* out) {
+                                         uint32_t W, uint32_t n_unitigs, uint32_t permille, uint32_t mode, ull* out, const uint32_t* set_of, uint32_t n_u) {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t n_found = sn, t_first = 0;
     FinUnitigTable tab;
     if (sn != 0u && tab.add(su, sn) && sfirst) t_first = sn;   // the seed is entry 0
-    pr_table_scan(pairs, alo, ahi, n_unitigs, true, n_found, tab, t_first);
-    pr_table_scan(pairs, blo, bhi, n_unitigs, false, n_found, tab, t_first);
+    pr_table_scan<SETS>(pairs, alo, ahi, n_unitigs, true, n_found, tab, t_first, set_of, n_u);
+    pr_table_scan<SETS>(pairs, blo, bhi, n_unitigs, false, n_found, tab, t_first, set_of, n_u);
     uint32_t n_colored = 0, n_first = 0, pc = 0;
     if (!tab.over) {
         const bool ne = tab.colored(bits, W);
@@ -83,31 +87,30 @@ __device__ __forceinline__ uint4 pr_scan(const int2* pairs, uint64_t alo, uint64
         bool sne = false;                   // the seed's row: lane i looks at word i
         if (sn != 0u) sne = __ballot(lane < W && bits[(uint64_t)su * W + (lane < W ? lane : 0u)] != 0ull) != 0ull;
         const uint32_t sc = sne ? sn : 0u;
-        n_first = fin_rescan_colored(pairs, alo, ahi, bits, W, n_unitigs) + (sfirst ? sc : 0u);
-        n_colored = n_first + fin_rescan_colored(pairs, blo, bhi, bits, W, n_unitigs) + (sfirst ? 0u : sc);
+        n_first = fin_rescan_colored<SETS>(pairs, alo, ahi, bits, W, n_unitigs, set_of, n_u) + (sfirst ? sc : 0u);
+        n_colored = n_first + fin_rescan_colored<SETS>(pairs, blo, bhi, bits, W, n_unitigs, set_of, n_u) + (sfirst ? 0u : sc);
         const bool keep = mode == 0u || (n_first != 0u && n_colored != n_first);
         const uint64_t need = (uint64_t)permille * n_colored;
         for (uint32_t w = 0; w < W; w++) {
-            uint32_t cnt = fin_rescan_word(pairs, alo, ahi, bits, W, n_unitigs, w) + fin_rescan_word(pairs, blo, bhi, bits, W, n_unitigs, w);
+            uint32_t cnt = fin_rescan_word<SETS>(pairs, alo, ahi, bits, W, n_unitigs, w, set_of, n_u) + fin_rescan_word<SETS>(pairs, blo, bhi, bits, W, n_unitigs, w, set_of, n_u);
             if (sn != 0u && ((bits[(uint64_t)su * W + w] >> lane) & 1ull)) cnt += sn;
             pc += fin_row_word(cnt, need, keep, out, w);
         }
     }
     return make_uint4(n_found, n_colored, pc, n_first);
 }
-}  // namespace
 
-// rows[f][0 .. W) = fragment f's colour row, heads[f] = {n_found, n_coloured, popcount, n_coloured_first}; fragment f = reads 2f and 2f + 1.  frec null: the step
-// left no records, every mate is scanned.
-__global__ __launch_bounds__(256) void fin_pair_pseudo_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_frags, uint32_t k,
-                                                              const ull* bits, uint32_t W, uint32_t n_unitigs, uint32_t permille, uint32_t mode, ull* rows, uint4* heads) {
+// the body of fin_pair_pseudo_kernel and, with SETS, of fin_pair_pseudo_sets_kernel
+template <bool SETS>
+__device__ __forceinline__ void pr_body(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_frags, uint32_t k, const ull* bits, uint32_t W,
+                                        uint32_t n_unitigs, uint32_t permille, uint32_t mode, ull* rows, uint4* heads, const uint32_t* set_of, uint32_t n_u) {
     const uint32_t f = blockIdx.x * FIN_PAIR_BLK + threadIdx.x, lane = threadIdx.x & 63u;
     const uint32_t f0 = f - lane;           // the wave's first fragment
     uint32_t ua = 0, na = 0, ub = 0, nb = 0;   // a kind-1 mate's unitig and found slots
     uint64_t alo = 0, ahi = 0, blo = 0, bhi = 0;
     if (f < n_frags) {
-        pr_mate(frec, out_offs, 2u * f, 2u * n_frags, k, n_unitigs, ua, na, alo, ahi);
-        pr_mate(frec, out_offs, 2u * f + 1u, 2u * n_frags, k, n_unitigs, ub, nb, blo, bhi);
+        pr_mate<SETS>(frec, out_offs, 2u * f, 2u * n_frags, k, n_unitigs, ua, na, alo, ahi, set_of, n_u);
+        pr_mate<SETS>(frec, out_offs, 2u * f + 1u, 2u * n_frags, k, n_unitigs, ub, nb, blo, bhi, set_of, n_u);
     }
     const bool scanned = ahi > alo || bhi > blo;
     uint4 mine = make_uint4(0u, 0u, 0u, 0u);
@@ -139,11 +142,25 @@ __global__ __launch_bounds__(256) void fin_pair_pseudo_kernel(const FinFastRec* 
     fin_each_lane(scanned, [&](int src) {
         const uint32_t nas = fin_bcast(na, src), nbs = fin_bcast(nb, src);   // (a scanned mate's n is 0: at most one of them is a seed)
         const uint32_t su = nas != 0u ? fin_bcast(ua, src) : fin_bcast(ub, src);
-        const uint4 s = pr_scan(pairs, fin_bcast64(alo, src), fin_bcast64(ahi, src), fin_bcast64(blo, src), fin_bcast64(bhi, src), su, nas + nbs, nas != 0u, bits, W,
-                                n_unitigs, permille, mode, rows + (uint64_t)(f0 + (uint32_t)src) * W);
+        const uint4 s = pr_scan<SETS>(pairs, fin_bcast64(alo, src), fin_bcast64(ahi, src), fin_bcast64(blo, src), fin_bcast64(bhi, src), su, nas + nbs, nas != 0u, bits, W,
+                                      n_unitigs, permille, mode, rows + (uint64_t)(f0 + (uint32_t)src) * W, set_of, n_u);
         if ((int)lane == src) mine = s;
     });
     if (f < n_frags) heads[f] = mine;
+}
+}  // namespace
+
+// rows[f][0 .. W) = fragment f's colour row, heads[f] = {n_found, n_coloured, popcount, n_coloured_first}; fragment f = reads 2f and 2f + 1.  frec null: the step
+// left no records, every mate is scanned.
+__global__ __launch_bounds__(256) void fin_pair_pseudo_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_frags, uint32_t k,
+                                                              const ull* bits, uint32_t W, uint32_t n_unitigs, uint32_t permille, uint32_t mode, ull* rows, uint4* heads) {
+    pr_body<false>(frec, out_offs, pairs, n_frags, k, bits, W, n_unitigs, permille, mode, rows, heads, nullptr, 0u);
+}
+// the same over a compact matrix: sets uint64[(n_sets + 1) * W] and set_of[n_unitigs]; every unitig number becomes its set id as it is loaded
+__global__ __launch_bounds__(256) void fin_pair_pseudo_sets_kernel(const FinFastRec* frec, const uint64_t* out_offs, const int2* pairs, uint32_t n_frags, uint32_t k,
+                                                                   const ull* sets, uint32_t W, uint32_t n_sets1, const uint32_t* set_of, uint32_t n_unitigs,
+                                                                   uint32_t permille, uint32_t mode, ull* rows, uint4* heads) {
+    pr_body<true>(frec, out_offs, pairs, n_frags, k, sets, W, n_sets1, permille, mode, rows, heads, set_of, n_unitigs);
 }
 
 // rows: uint64[n_frags * W]; heads: 16 bytes per fragment; out_offs and frec are the step's, over 2 n_frags reads.  mode: 0 any, 1 both
@@ -153,5 +170,15 @@ extern "C" int fin_launch_pseudoalign_paired(const void* frec, const uint64_t* o
     if (nb == 0) return 0;
     hipLaunchKernelGGL(fin_pair_pseudo_kernel, dim3(nb), dim3(256), 0, stream, (const FinFastRec*)frec, out_offs, (const int2*)pairs, n_frags, k, (const ull*)bits, W,
                        n_unitigs, permille, mode, (ull*)rows, (uint4*)heads);
+    return (int)hipGetLastError();
+}
+// the same over a compact matrix: sets uint64[(n_sets + 1) * W], row 0 empty; set_of: uint32[n_unitigs], each <= n_sets
+extern "C" int fin_launch_pseudoalign_paired_sets(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_frags, uint32_t k, const void* sets, uint32_t W,
+                                                  uint32_t n_sets, const uint32_t* set_of, uint32_t n_unitigs, uint32_t permille, uint32_t mode, void* rows, void* heads,
+                                                  hipStream_t stream) {
+    const uint32_t nb = (n_frags + FIN_PAIR_BLK - 1u) / FIN_PAIR_BLK;
+    if (nb == 0) return 0;
+    hipLaunchKernelGGL(fin_pair_pseudo_sets_kernel, dim3(nb), dim3(256), 0, stream, (const FinFastRec*)frec, out_offs, (const int2*)pairs, n_frags, k, (const ull*)sets, W,
+                       n_sets + 1u, set_of, n_unitigs, permille, mode, (ull*)rows, (uint4*)heads);
     return (int)hipGetLastError();
 }

@@ -161,7 +161,8 @@ __device__ __forceinline__ void fin_seg_next_row(FinSegCarry& c, uint32_t u, uin
     c.plink = __builtin_amdgcn_readlane(link, 63);
 }
 
-// ---- the wave's table of a read's distinct unitigs, for the colour rows (fin_colors.hip, fin_paired.hip): entry i < n_ent in lane i ----
+// ---- the wave's table of a read's distinct unitigs -- over a compact matrix, of its distinct SET IDS: counts are additive over the unitigs of one set --, for the
+// colour rows (fin_colors.hip, fin_paired.hip): entry i < n_ent in lane i ----
 struct FinUnitigTable {
     uint32_t n_ent = 0, t_u = 0, t_cnt = 0;
     bool over = false;                      // more than 64 distinct unitigs: the table is dropped, the caller rescans
@@ -200,14 +201,23 @@ struct FinUnitigTable {
         return cnt;
     }
 };
+// what keys the rows (fin_colors.hip, fin_paired.hip).  Over the dense matrix a unitig number is its own key.  Over a compact one (SETS; fin_colorsets.hip) it
+// becomes its set id as it is loaded: bits = sets, n_unitigs = n_sets + 1, and a number at or above the index's n_u stays absent.  Set 0 is the empty row
+template <bool SETS>
+__device__ __forceinline__ uint32_t fin_row_key(uint32_t u, const uint32_t* set_of, uint32_t n_u) {
+    if (SETS) return u < n_u ? set_of[u] : 0xFFFFFFFFu;
+    return u;
+}
 // the rescans of a read whose table overflowed, a row at a time without looking ahead.  n_coloured of slots [lo, hi): a lane per slot looks at its unitig's row
-__device__ __forceinline__ uint32_t fin_rescan_colored(const int2* pairs, uint64_t lo, uint64_t hi, const unsigned long long* bits, uint32_t W, uint32_t n_unitigs) {
+template <bool SETS = false>
+__device__ __forceinline__ uint32_t fin_rescan_colored(const int2* pairs, uint64_t lo, uint64_t hi, const unsigned long long* bits, uint32_t W, uint32_t n_unitigs,
+                                                       const uint32_t* set_of = nullptr, uint32_t n_u = 0u) {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t nc = 0;
     for (uint64_t base = lo; base < hi; base += 64u) {
         const uint64_t j = base + lane;
         uint32_t u = 0xFFFFFFFFu;
-        if (j < hi) u = (uint32_t)pairs[j].x;
+        if (j < hi) u = fin_row_key<SETS>((uint32_t)pairs[j].x, set_of, n_u);
         bool ne = false;
         if (u < n_unitigs) for (uint32_t w = 0; w < W; w++) if (bits[(uint64_t)u * W + w] != 0ull) ne = true;
         nc += (uint32_t)__popcll(__ballot(ne));
@@ -215,13 +225,15 @@ __device__ __forceinline__ uint32_t fin_rescan_colored(const int2* pairs, uint64
     return nc;
 }
 // what slots [lo, hi) add to cnt[64 w + lane]: for each distinct unitig of a row its word w is broadcast, the lanes whose bit is set add the ballot's popcount
-__device__ __forceinline__ uint32_t fin_rescan_word(const int2* pairs, uint64_t lo, uint64_t hi, const unsigned long long* bits, uint32_t W, uint32_t n_unitigs, uint32_t w) {
+template <bool SETS = false>
+__device__ __forceinline__ uint32_t fin_rescan_word(const int2* pairs, uint64_t lo, uint64_t hi, const unsigned long long* bits, uint32_t W, uint32_t n_unitigs, uint32_t w,
+                                                    const uint32_t* set_of = nullptr, uint32_t n_u = 0u) {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t cnt = 0;
     for (uint64_t base = lo; base < hi; base += 64u) {
         const uint64_t j = base + lane;
         uint32_t u = 0xFFFFFFFFu;
-        if (j < hi) u = (uint32_t)pairs[j].x;
+        if (j < hi) u = fin_row_key<SETS>((uint32_t)pairs[j].x, set_of, n_u);
         unsigned long long word = 0ull;
         if (u < n_unitigs) word = bits[(uint64_t)u * W + w];
         fin_each_distinct(u, u < n_unitigs, [&](int src, uint32_t, unsigned long long m) {

@@ -513,6 +513,11 @@ static const char* SEARCH_HELP =
     "                        last chunk from a coverage bitmap and a depth kept there (those of --unitig-coverage / --unitig-depth when they are asked for\n"
     "                        too), at their cost: one more search of every chunk each. Coverage counts k-mers, so with --paired 1 mates need no pairing.\n"
     "                        Wants --color-refs; goes with --no-text 1, --abundance, --eqclasses, --assign-weights and --paired 1. Not for a partitioned index.\n"
+    "      --compact-colors 1  with --color-refs: after the colouring and before the first chunk of reads, deduplicate the colour rows on the GPU\n"
+    "                        (every distinct colour set once and a set id per unitig instead of the dense matrix). Prints\n"
+    "                        'colour sets<TAB>n_sets<TAB>bytes dense<TAB>bytes compact' to stderr; every per-read and per-run colour output is byte-identical.\n"
+    "                        Not with --color-coverage, --color-similarity or --taxonomy (they read the dense matrix).\n"
+    "      --color-sets-out PREFIX  with --compact-colors 1: PREFIX.set_of.u32 (uint32 per unitig) and PREFIX.sets.u64 (W uint64 per set, set 0 empty), raw little-endian.\n"
     "      --color-similarity FILE  also write what the references of --color-refs share, integers only: one line\n"
     "                        `colour_a<TAB>colour_b<TAB>size_a<TAB>size_b<TAB>shared` per pair a < b with shared > 0, ascending -- the k-mers of the unitigs that\n"
     "                        carry a, that carry b, and that carry both --, then one line `identical<TAB>c1,c2,...` per group of references with the same\n"
@@ -1476,7 +1481,7 @@ static void write_color_similarity(const string& path, fin_cover* cov, size_t nc
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "color-similarity", "color-similarity-covered", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "color-similarity", "color-similarity-covered", "compact-colors", "color-sets-out", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
@@ -1487,6 +1492,12 @@ static int search_fmin(int argc, char** argv) {
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
     if (o.has("color-coverage") && !o.has("color-refs")) throw runtime_error("--color-coverage wants colours: --color-refs LIST");
     if ((o.has("color-similarity") || o.has("color-similarity-covered")) && !o.has("color-refs")) throw runtime_error("--color-similarity and --color-similarity-covered want colours: --color-refs LIST");
+    const bool compact_colors = o.has("compact-colors") && o.get("compact-colors") != "0" && o.get("compact-colors") != "false";
+    if (compact_colors && !o.has("color-refs")) throw runtime_error("--compact-colors 1 wants colours: --color-refs LIST");
+    if (o.has("color-sets-out") && !compact_colors) throw runtime_error("--color-sets-out is only legal together with --compact-colors 1");
+    for (const char* name : {"color-coverage", "color-similarity", "taxonomy"})
+        if (compact_colors && o.has(name))
+            throw runtime_error(string("--compact-colors 1 is not available with --") + name + ": coverage, shared k-mers and taxonomy read the dense colour matrix (fin_colors_expand), over sets they are not built");
     g_paired = o.has("paired") && o.get("paired") != "0" && o.get("paired") != "false";
     const bool pair_both = o.has("pair-both") && o.get("pair-both") != "0" && o.get("pair-both") != "false";
     if (g_paired && !o.has("color-refs")) throw runtime_error("--paired 1 wants colours: --color-refs LIST (fragments are what --pseudoalign, --eqclasses, --color-report and --abundance then take)");
@@ -1796,6 +1807,23 @@ static int search_fmin(int argc, char** argv) {
             if (!cf) throw runtime_error("Error writing to file: " + colors_file);
         }
         if (!colsim_file.empty()) write_color_similarity(colsim_file, nullptr, color_refs.size());   // (what the references share in the graph, before any read)
+        if (compact_colors) {   // every distinct row once, before the first chunk of reads: what follows reads the sets
+            if (fin_colors_compact(g_colors, 0, nullptr, err, sizeof err) != FIN_OK) throw runtime_error(string("--compact-colors: ") + err);
+            const uint64_t n_sets = fin_colors_n_sets(g_colors);
+            cerr << "colour sets\t" << n_sets << "\t" << (uint64_t)nu * W * 8 << "\t" << (uint64_t)nu * 4 + (n_sets + 1) * W * 8 << endl;
+            if (o.has("color-sets-out")) {   // PREFIX.set_of.u32: uint32[n_unitigs]; PREFIX.sets.u64: uint64[(n_sets + 1) * W], little-endian, what fin_colors_upload_sets takes
+                vector<uint32_t> set_of(nu + 1);
+                vector<uint64_t> sets((size_t)(n_sets + 1) * W);
+                uint64_t got = 0;
+                if (fin_colors_download_sets(g_colors, set_of.data(), sets.data(), n_sets + 1, &got, err, sizeof err) != FIN_OK) throw runtime_error(err);
+                const string f1 = o.get("color-sets-out") + ".set_of.u32", f2 = o.get("color-sets-out") + ".sets.u64";
+                ofstream a(f1, ios::binary | ios::trunc), b(f2, ios::binary | ios::trunc);
+                a.write((const char*)set_of.data(), (streamsize)(nu * 4));
+                b.write((const char*)sets.data(), (streamsize)(sets.size() * 8));
+                if (!a) throw runtime_error("Error writing to file: " + f1);
+                if (!b) throw runtime_error("Error writing to file: " + f2);
+            }
+        }
         if (tax_asked) {   // every unitig's taxon: the LCA of its colours' taxa, made on the device from the matrix as it stands now
             if (fin_taxonomy_create_from_colors(g_colors, tax_parent.data(), tax_parent.size(), tax_color_taxon.data(), &g_tax, err, sizeof err) != FIN_OK) throw runtime_error(err);
             g_tax_report = !taxrep_file.empty();

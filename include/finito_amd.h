@@ -838,7 +838,8 @@ int fin_index_unitig_numbers(const fin_index* idx, const char* bases, const uint
  * 0 .. 1000 colour c is in the read's row iff cnt[c] >= 1 and 1000 * cnt[c] >= permille * n_colored (64-bit arithmetic).  permille = 1000 is the intersection over
  * the coloured k-mers -- found k-mers in uncoloured unitigs and absent k-mers are ignored --, permille = 0 the union.  All of it is invariant under reversing the
  * slot order.  A pair whose unitig number is at or above the index's number of unitigs counts as absent on the device and is FIN_EINVAL on the host.
- * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, more than 4096 colours, compressed or deduplicated colour sets.  (A per-colour
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, more than 4096 colours, compressed colour sets, coverage / shared / taxonomy over a
+ * compact matrix (fin_colors_coverage, fin_colors_shared, fin_taxonomy_create_from_colors read bits[u * W + w]: fin_colors_expand first).  (A per-colour
  * tally of reads: the EQUIVALENCE CLASSES below.  Paired-end data: one row per FRAGMENT, the same definition over both mates' slots, DESIGN.md 4.17 below.) */
 #define FIN_MAX_COLORS 4096u
 typedef struct fin_read_pseudo { uint32_t n_found, n_colored, n_colors, reserved /* 0 */; } fin_read_pseudo;   /* 16 bytes; n_colors = the popcount of the read's row */
@@ -856,6 +857,51 @@ uint32_t fin_colors_words(const fin_colors* c);          /* W */
  * overflow list overran was added (nothing of it was coloured) */
 int fin_colors_download(fin_colors* c, uint64_t* bits_out, uint64_t* n_set, char* err, size_t errlen);
 void fin_colors_free(fin_colors* c);
+/* ---- DEDUPLICATED COLOUR SETS: the COMPACT state of a fin_colors (fin_colorsets.hip) ----
+ * The unitigs of a graph over many references carry few distinct rows.  A compact fin_colors holds, in HBM and IN PLACE of the dense matrix,
+ *   uint32 set_of[n_unitigs]   and   uint64 sets[n_sets + 1][W]:
+ * sets[0] is the empty set, all zero, always there; set_of[u] == 0 iff unitig u's row is empty; sets[set_of[u]] is unitig u's row bit for bit.  Rows 1 .. n_sets
+ * are non-empty and pairwise distinct when the device made them; their ORDER IS UNSPECIFIED (the canonical order is fin_unitig_color_sets's, on the host).
+ * On a compact object:
+ *   fin_batch_pseudoalign[_paired] and all that is made from their rows (equivalence classes, abundances, bootstrap, merge, assign, the fin_search_batch_*
+ *     pipelines over them) work unchanged with bit-identical results: a unitig number becomes its set id as it is loaded, and the per-read register table is keyed by
+ *     set id -- a read crossing 200 unitigs of 3 sets stays on the table path;
+ *   fin_colors_download returns the dense matrix and n_set as before (expanded on the host; the object stays compact);
+ *   fin_colors_upload and fin_colors_reset leave the object DENSE, as they always do;
+ *   fin_colors_device_bits returns NULL;
+ *   fin_batch_add_colors, fin_search_batch_add_colors, fin_colors_coverage, fin_colors_shared and fin_taxonomy_create_from_colors return FIN_EINVAL with a message
+ *     that names fin_colors_expand.
+ * LIMITS: at most 2^26 sets from fin_colors_compact (its table has 2^lg >= 2 max_sets slots of 8 bytes, beside 4 bytes per unitig and per slot of scratch while it
+ * runs, and dense and compact form are both in HBM until it ends); at most 2^32 - 2 sets from fin_colors_upload_sets; rows are stored whole (no compression).
+ *
+ * fin_colors_compact: behind every add, upload and reset issued so far, under the object's lock (no add falls in between), on hip_stream; deduplicates the rows on
+ * the device and frees the dense matrix; waits for its own work.  max_sets: 0 = min(n_unitigs, 2^26); above 2^26 FIN_ELIMIT.  FIN_ELIMIT also if there are more
+ * than max_sets distinct non-empty rows, or if the matrix is flagged (a step whose overflow list overran was offered): the object is then UNCHANGED and still dense.
+ * On a compact object a no-op that succeeds.  fin_colors_expand: back to the dense matrix, gathered on the device; a no-op on a dense object. */
+int fin_colors_compact(fin_colors* c, uint64_t max_sets, void* hip_stream, char* err, size_t errlen);
+int fin_colors_expand(fin_colors* c, void* hip_stream, char* err, size_t errlen);
+int fin_colors_is_compact(const fin_colors* c);
+uint64_t fin_colors_n_sets(const fin_colors* c);            /* 0 while dense */
+void* fin_colors_device_set_of(const fin_colors* c);        /* uint32[n_unitigs] in HBM; NULL while dense */
+void* fin_colors_device_sets(const fin_colors* c);          /* uint64[(n_sets + 1) * W] in HBM; NULL while dense */
+/* waits; set_of_out[n_unitigs] and sets_out[(n_sets + 1) * W] (either may be NULL); *n_sets is always set.  FIN_ELIMIT: cap_sets < n_sets + 1 (cap_sets counts
+ * rows of sets_out, row 0 among them).  FIN_EINVAL on a dense object. */
+int fin_colors_download_sets(fin_colors* c, uint32_t* set_of_out, uint64_t* sets_out, uint64_t cap_sets, uint64_t* n_sets, char* err, size_t errlen);
+/* makes the object compact directly from host arrays (waits for every add issued so far): the persisted form, and the way in for a colouring whose dense matrix
+ * would not fit.  set_of[n_unitigs], sets[(n_sets + 1) * W].  FIN_EINVAL, naming the unitig or the set, for a set_of[u] > n_sets, a non-zero sets[0] or a bit at
+ * or above n_colors; FIN_ELIMIT for n_sets above 2^32 - 2.  Duplicate rows and unused sets are legal: no result depends on them.  On failure nothing changes. */
+int fin_colors_upload_sets(fin_colors* c, const uint32_t* set_of, const uint64_t* sets, uint64_t n_sets, char* err, size_t errlen);
+/* what the fin_colors_compact that made the object's present compact form met (all 0 while dense, and after fin_colors_upload_sets): out[0] n_sets, [1] rows that met a foreign row under their tag (option "colorsets_tag_bits", 1 .. 31,
+ * default 31, narrows the tag and the home slot with it so that tests force this), [2] the longest probe (slots looked at behind a home slot), [3] slots.  The home slot of tag t is ~(ec_mix(t) >> 7) & (slots - 1), fin_rowhash.h: tag 0 starts
+ * at the last slot, so under narrow tags its chain wraps */
+int fin_colors_compact_stats(const fin_colors* c, uint64_t out[4]);
+/* host, no device: the same sets in CANONICAL form -- sets_out[1 ..] ascending by word 0, then word 1 and so on (np.unique(axis=0) of the non-empty rows),
+ * set_of_out accordingly (either may be NULL).  *n_sets is always set.  FIN_ELIMIT: n_colors is 0 or above FIN_MAX_COLORS, or cap_sets < n_sets + 1; FIN_EINVAL: a
+ * bit at or above n_colors.  n_threads <= 0: all cores; the result does not depend on it. */
+int fin_unitig_color_sets(const uint64_t* bits, uint64_t n_unitigs, uint32_t n_colors, uint32_t* set_of_out, uint64_t* sets_out, uint64_t cap_sets, uint64_t* n_sets,
+                          int n_threads);
+/* host: bits_out[n_unitigs * W] = sets[set_of[u]].  FIN_EINVAL: a set_of[u] > n_sets, a non-zero sets[0], a bit at or above n_colors */
+int fin_color_sets_expand(const uint32_t* set_of, const uint64_t* sets, uint64_t n_unitigs, uint64_t n_sets, uint32_t n_colors, uint64_t* bits_out, int n_threads);
 /* COLOURING BY SEARCH: behind the batch's most recent run, on hip_stream, ordered as fin_batch_add_hits is: every unitig in which that run found at least one
  * k-mer gets bit `color` set (fin_colors.hip: one plain load per unitig met, an atomic OR only where the bit is clear).  Adding twice changes nothing.  Search
  * reference genome i through the index and add with color = i: that is the colouring.  Works in every text mode, FIN_MERGED and FIN_FWD, every k.
