@@ -355,6 +355,10 @@ def lib():
         L.fin_unitig_color_coverage.argtypes = [u64p, u64, u32, u64p, u64p, vp, vp, vp, C.c_int]
         L.fin_colors_shared.argtypes = [vp, vp, vp, vp, cp, C.c_size_t]
         L.fin_unitig_color_shared.argtypes = [u64p, u64, u32, u64p, u64p, C.c_int]
+        L.fin_depth_histogram.argtypes = [vp, u32, u32, vp, cp, C.c_size_t]
+        L.fin_colors_depth_histogram.argtypes = [vp, vp, u32, u32, vp, vp, cp, C.c_size_t]
+        L.fin_depth_positions_histogram.argtypes = [vp, vp, u64, C.c_int, u32, u32, vp, C.c_int]
+        L.fin_unitig_color_depth_histogram.argtypes = [vp, vp, u64, C.c_int, vp, u32, u32, u32, vp, vp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -1111,6 +1115,18 @@ class Colors(_Accumulator):
                                         out.ctypes.data_as(C.c_void_p), err, 512), err)
         return ColorShared(out)
 
+    def depth_histogram(self, depth, n_bins=256, bin_width=1):
+        """the histogram of every reference's k-mer depths, on the device (fin_colors_depth_histogram): a ColorDepthHistogram -- what medians and
+        quartiles are read from.  depth: a Depth of the same index and device; bin(d) = min(d // bin_width, n_bins - 1), n_bins 1 .. 1024.  Waits for the adds to
+        both; changes neither"""
+        nb, bw = _hist_args("Colors.depth_histogram", n_bins, bin_width)
+        if depth is None:
+            raise FinitoError(FIN_EINVAL, "Colors.depth_histogram: a Depth is needed")
+        out = np.zeros((self.n_colors * 2 + 1, nb), dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_colors_depth_histogram(self.h, depth.h, nb, bw, out.ctypes.data_as(C.c_void_p), out[self.n_colors * 2:].ctypes.data_as(C.c_void_p), err, 512), err)
+        return ColorDepthHistogram(out[: self.n_colors * 2].reshape(self.n_colors, 2, nb), out[self.n_colors * 2], bw)
+
 
 class EqClasses(_Accumulator):
     """the equivalence classes of pseudoaligned reads -- the distinct colour rows the added runs produced and how many reads have each --, accumulated in HBM
@@ -1282,6 +1298,79 @@ class ColorCoverage:
     def mean_depth(self):
         """depth_sum / covered: the mean depth of the found k-mers; nan where none was found"""
         return self._ratio(self.depth_sum, self.covered)
+
+
+FIN_DEPTH_HIST_MAX_BINS = 1024
+
+
+def _hist_args(what, n_bins, bin_width):
+    nb, bw = int(n_bins), int(bin_width)
+    if not 1 <= nb <= FIN_DEPTH_HIST_MAX_BINS:
+        raise FinitoError(FIN_EINVAL, "%s: n_bins is 1 .. %d" % (what, FIN_DEPTH_HIST_MAX_BINS))
+    if not 1 <= bw <= 0xFFFFFFFF:
+        raise FinitoError(FIN_EINVAL, "%s: bin_width is 1 .. 2^32 - 1" % what)
+    return nb, bw
+
+
+def histogram_quantile(hist, permille, bin_width=1):
+    """the quantile rule of include/finito_amd.h (DEPTH HISTOGRAMS AND QUANTILES) for one histogram, in Python integers: with N = sum(hist) and
+    t = max(1, ceil(permille * N / 1000)), the smallest bin b whose cumulative count reaches t -- (b * bin_width, saturated), saturated when b is the last of
+    more than one bin ("this much or more"); None when the histogram is empty"""
+    p, bw = int(permille), int(bin_width)
+    if not 0 <= p <= 1000:
+        raise FinitoError(FIN_EINVAL, "histogram_quantile: permille is 0 .. 1000")
+    if bw < 1:
+        raise FinitoError(FIN_EINVAL, "histogram_quantile: bin_width is at least 1")
+    h = [int(x) for x in hist]
+    n = sum(h)
+    if n == 0:
+        return None
+    t = max(1, (p * n + 999) // 1000)
+    acc = 0
+    for b, x in enumerate(h):
+        acc += x
+        if acc >= t:
+            return b * bw, (b == len(h) - 1 and len(h) > 1)
+    raise AssertionError("unreachable: t <= N")
+
+
+class ColorDepthHistogram:
+    """the histogram of every reference's k-mer depths (Colors.depth_histogram, unitig_color_depth_histogram): table uint64[n_colors, 2, n_bins] -- [c, 0] over the
+    unitigs that carry colour c, [c, 1] over those that carry c alone --, uncolored uint64[n_bins] over the unitigs without a colour, n_bins, bin_width; kmers and
+    kmers_only are the row sums.  Bin b holds the k-mer positions whose depth d has min(d // bin_width, n_bins - 1) == b.  Quantiles follow histogram_quantile"""
+
+    def __init__(self, table, uncolored, bin_width):
+        self.table, self.uncolored = table, uncolored
+        self.n_colors, _, self.n_bins = table.shape
+        self.bin_width = int(bin_width)
+        self.kmers = table[:, 0, :].sum(axis=1, dtype=np.uint64)
+        self.kmers_only = table[:, 1, :].sum(axis=1, dtype=np.uint64)
+
+    def quantile(self, permille, only=False):
+        """(values int64[n_colors], saturated bool[n_colors]): every colour's quantile in thousandths as a depth (the bin's lower edge); -1 where the colour has
+        no k-mers"""
+        values, sat = np.full(self.n_colors, -1, dtype=np.int64), np.zeros(self.n_colors, dtype=bool)
+        for c in range(self.n_colors):
+            q = histogram_quantile(self.table[c, 1 if only else 0], permille, self.bin_width)
+            if q is not None:
+                values[c], sat[c] = q
+        return values, sat
+
+    def median(self, only=False):
+        return self.quantile(500, only)
+
+    def iqr(self, only=False):
+        """(q750 - q250 int64[n_colors], saturated where either quartile is): -1 where the colour has no k-mers"""
+        (lo, s_lo), (hi, s_hi) = self.quantile(250, only), self.quantile(750, only)
+        return np.where(lo < 0, -1, hi - lo), s_lo | s_hi
+
+    def breadth(self, only=False):
+        """1 - table[:, ., 0] / kmers: the share of the k-mers found at least bin_width times; nan for a colour without k-mers"""
+        j = 1 if only else 0
+        den = self.kmers_only if only else self.kmers
+        out = np.full(self.n_colors, np.nan)
+        np.divide(self.table[:, j, 0].astype(np.float64), den.astype(np.float64), out=out, where=den != 0)
+        return np.where(den != 0, 1.0 - out, np.nan)
 
 
 class ColorShared:
@@ -1576,6 +1665,15 @@ class Depth(_Accumulator):
         _check(self.L.fin_depth_download(self.h, int(min_depth), depth.ctypes.data_as(C.c_void_p) if want_positions else None, stats.ctypes.data_as(C.c_void_p),
                                          C.byref(tot), err, 512), err)
         return (depth[: self.total_len] if want_positions else None), stats[: self.n_unitigs], int(tot.value)
+
+    def histogram(self, n_bins=256, bin_width=1):
+        """the k-mer spectrum of the run, made on the device (fin_depth_histogram): uint64[n_bins], entry b the k-mer positions of the text whose
+        depth d has min(d // bin_width, n_bins - 1) == b.  Waits for the adds; leaves the accumulator as it is"""
+        nb, bw = _hist_args("Depth.histogram", n_bins, bin_width)
+        out = np.zeros(nb, dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_depth_histogram(self.h, nb, bw, out.ctypes.data_as(C.c_void_p), err, 512), err)
+        return out
 
     def device_ptr(self):
         return int(self.L.fin_depth_device_diff(self.h) or 0)
@@ -2071,6 +2169,16 @@ class FinimizerIndex:
             return colors.coverage(cov, dep, min_depth)
         finally:
             cov.close(); dep.close()
+
+    def color_depth_histogram(self, reads, colors, n_bins=256, bin_width=1, strands=FIN_MERGED):
+        """the depth histogram of a read set per reference of `colors` (a Colors of this index): a fresh Depth beside the colours, the reads searched into it,
+        then Colors.depth_histogram -- a ColorDepthHistogram"""
+        dep = Depth(self, colors.device)
+        try:
+            dep.add_reads(flatten(reads), strands)
+            return colors.depth_histogram(dep, n_bins, bin_width)
+        finally:
+            dep.close()
 
     def pileup(self, max_mismatch=8, device=0):
         """a zeroed base pileup beside the replica on `device` (Pileup)"""
@@ -2644,6 +2752,55 @@ def unitig_color_shared(bits, n_colors, v, n_threads=0):
     if rc != 0:
         raise FinitoError(rc, "fin_unitig_color_shared: a row with a bit at or above n_colors")
     return ColorShared(out)
+
+
+def _hist_inputs(what, depth, ends, k):
+    e = np.ascontiguousarray(ends, dtype=np.int64).reshape(-1)
+    d = np.ascontiguousarray(depth, dtype=np.uint32).reshape(-1)
+    total = int(e[-1]) if len(e) else 0
+    if len(d) < total:
+        raise FinitoError(FIN_EINVAL, "%s: depth has %d entries, the unitigs end at %d" % (what, len(d), total))
+    if len(d) == 0:
+        d = np.zeros(1, dtype=np.uint32)
+    if int(k) < 1:
+        raise FinitoError(FIN_EINVAL, "%s: k is at least 1" % what)
+    if len(e) and (e[0] < 0 or (np.diff(e) < 0).any()):
+        raise FinitoError(FIN_EINVAL, "%s: the unitig ends decrease" % what)
+    return d, e
+
+
+def depth_positions_histogram(depth, ends, k, n_bins=256, bin_width=1, n_threads=0):
+    """host: the k-mer spectrum uint64[n_bins] of per-position depths uint32[total_len] over unitigs ending at ends (X_ENDS) -- the CPU statement of
+    Depth.histogram (fin_depth_positions_histogram); the result does not depend on n_threads"""
+    nb, bw = _hist_args("depth_positions_histogram", n_bins, bin_width)
+    d, e = _hist_inputs("depth_positions_histogram", depth, ends, k)
+    out = np.zeros(nb, dtype=np.uint64)
+    vp = C.c_void_p
+    rc = lib().fin_depth_positions_histogram(d.ctypes.data_as(vp), e.ctypes.data_as(vp) if len(e) else None, len(e), int(k), nb, bw, out.ctypes.data_as(vp), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_depth_positions_histogram: refused with code %d" % rc)   # (every refusal it has is caught above)
+    return out
+
+
+def unitig_color_depth_histogram(depth, ends, k, bits, n_colors, n_bins=256, bin_width=1, n_threads=0):
+    """host: the ColorDepthHistogram of per-position depths under a colour matrix uint64[n_unitigs, W] -- the CPU statement of Colors.depth_histogram
+    (fin_unitig_color_depth_histogram); the result does not depend on n_threads"""
+    nc = int(n_colors)
+    if not 1 <= nc <= FIN_MAX_COLORS:
+        raise FinitoError(FIN_ELIMIT, "unitig_color_depth_histogram: n_colors is 1 .. 4096")
+    nb, bw = _hist_args("unitig_color_depth_histogram", n_bins, bin_width)
+    d, e = _hist_inputs("unitig_color_depth_histogram", depth, ends, k)
+    W = (nc + 63) // 64
+    a = np.ascontiguousarray(bits, dtype=np.uint64).reshape(-1, W)
+    if len(a) != len(e):
+        raise FinitoError(FIN_EINVAL, "unitig_color_depth_histogram: the matrix has %d rows, there are %d unitigs" % (len(a), len(e)))
+    out = np.zeros((nc * 2 + 1, nb), dtype=np.uint64)
+    vp = C.c_void_p
+    rc = lib().fin_unitig_color_depth_histogram(d.ctypes.data_as(vp), e.ctypes.data_as(vp) if len(e) else None, len(e), int(k), a.ctypes.data_as(vp) if len(e) else None,
+                                                nc, nb, bw, out.ctypes.data_as(vp), out[nc * 2:].ctypes.data_as(vp), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_unitig_color_depth_histogram: a row with a bit at or above n_colors")   # (the other refusals are caught above)
+    return ColorDepthHistogram(out[: nc * 2].reshape(nc, 2, nb), out[nc * 2], bw)
 
 
 def unitig_color_sets(bits, n_colors, n_threads=0):

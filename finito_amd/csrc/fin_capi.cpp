@@ -1,7 +1,6 @@
 // fin_capi.cpp -- implementation of the C ABI declared in include/finito_amd.h.
 // Host orchestration only: index lifetime, HBM replica, batches, launches.  No CPU search path exists here:
 // without a HIP device every search entry point fails with FIN_ENODEV.
-#include <functional>
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -13,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -99,7 +99,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_colcov_chunk, O_colsim_chunk, O_colorsets_tag_bits, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_colcov_chunk, O_colsim_chunk, O_colorsets_tag_bits, O_depthhist_unitigs, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -141,6 +141,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"colcov_chunk", 0, 0, 1ll << 26},             // fin_colors_coverage: unitigs per chunk of fin_colcov_column_kernel (fin_colcov.hip), rounded up to a multiple of 64; 0 = auto: 1024, more once that would make over 8192 waves; never so few that there would be over 2^20 chunks.  The results do not depend on it; tests set 64 so that small cases cross chunk seams
     {"colsim_chunk", 0, 0, 1ll << 26},             // fin_colors_shared: unitigs per chunk of fin_colsim_tile_kernel (fin_colsim.hip), rounded up to a multiple of 64; 0 = auto: 4096, more once that would make over 16384 waves; never so few that tiles x chunks would pass 2^30 blocks.  The results do not depend on it; tests set 64 so that small cases cross chunk seams
     {"colorsets_tag_bits", 31, 1, 31},             // fin_colors_compact: bits of a row's tag in the dedup table (fin_colorsets.hip); the home slot is a function of the tag, so tests narrow it to force distinct rows under one tag and long probe chains.  The results do not depend on it
+    {"depthhist_unitigs", 0, 0, 1ll << 26},        // fin_colors_depth_histogram: unitigs per sub-range of a staged chunk, each binned into a table uint32[unitigs][n_bins] and projected (fin_depthhist.hip); 0 = auto: what a table of 64 MB holds, at least 64.  A value is cut to that budget too.  The results do not depend on it; tests set 16 so that small cases cross sub-range seams
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -1844,13 +1845,17 @@ struct fin_colors : fin_acc {
     // fin_colors_coverage's: made by the first call, kept
     void* d_ccv = nullptr;      // uint64[(n_colors + 1) * 8]: the table and the uncoloured entry; then the class byte of every unitig
     std::mutex ccv_mu;          // one projection at a time goes through d_ccv
+    // fin_colors_depth_histogram's: made by the first call, grown when a later one asks for more, kept (as d_ccv is: hipFree would synchronise the device in every call)
+    void* d_dh = nullptr;       // the table uint64[n_colors][2][n_bins] and the uncoloured histogram behind it; 64 bytes of the class kernel's scratch; the class bytes; the sub-range's uint32[unitigs][n_bins]
+    size_t dh_bytes = 0;
+    std::mutex dh_mu;           // one call at a time goes through d_dh
 };
 static size_t colors_bytes(const fin_colors* c) { return (size_t)c->n_unitigs * c->words * 8; }
 static uint32_t* colors_flags(const fin_colors* c) { return (uint32_t*)((char*)c->d_bits + colors_bytes(c)); }
 
 void fin_colors_free(fin_colors* c) {
     if (!acc_free_open(c)) return;
-    (void)hipFree(c->d_bits); (void)hipFree(c->d_ccv); (void)hipFree(c->d_set_of); (void)hipFree(c->d_sets);
+    (void)hipFree(c->d_bits); (void)hipFree(c->d_ccv); (void)hipFree(c->d_dh); (void)hipFree(c->d_set_of); (void)hipFree(c->d_sets);
     delete c;
 }
 
@@ -3231,6 +3236,7 @@ struct fin_depth : fin_acc {
     uint32_t* d_stage = nullptr;        // uint32[stage_len]: one chunk's depths
     uint32_t* d_tile = nullptr;         // uint32[fin_depth_max_chunk_tiles()]: the chunk's tile sums, then the carry word
     void* d_stats = nullptr;            // fin_depth_stat[n_unitigs]
+    void* d_hist = nullptr;             // fin_depth_histogram's uint64[FIN_DEPTH_HIST_MAX_BINS]: made by the first call, kept
     uint64_t stage_len = 0;
     std::mutex scan_mu;                 // one download at a time scans through the staging buffer
 };
@@ -3240,7 +3246,7 @@ static size_t depth_bytes(const fin_depth* d) { return (size_t)(d->total_len + 2
 
 void fin_depth_free(fin_depth* d) {
     if (!acc_free_open(d)) return;
-    (void)hipFree(d->d_diff); (void)hipFree(d->d_stage); (void)hipFree(d->d_tile); (void)hipFree(d->d_stats);
+    (void)hipFree(d->d_diff); (void)hipFree(d->d_stage); (void)hipFree(d->d_tile); (void)hipFree(d->d_stats); (void)hipFree(d->d_hist);
     delete d;
 }
 
@@ -3273,9 +3279,10 @@ int fin_batch_add_depth(fin_batch* b, fin_depth* d, void* hip_stream, char* err,
 }
 
 // the prefix sum of the difference array as it stands, a chunk at a time through the staging buffer on the null stream (with scan_mu held; total_len and
-// n_unitigs > 0): every chunk's depths to depth_out (may be null), the per-unitig statistics under min_depth into d->d_stats (want_stats).  fin_depth_download's
-// and fin_colors_coverage's
-static int depth_scan(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, bool want_stats, char* err, size_t errlen) {
+// n_unitigs > 0): every chunk's depths to depth_out (may be null), the per-unitig statistics under min_depth into d->d_stats (want_stats), and each_chunk (may be
+// empty) called on every chunk once it is staged.  fin_depth_download's, fin_colors_coverage's and the depth histograms'
+typedef std::function<int(uint64_t base, uint64_t n)> depth_chunk_fn;   // what else is made of a staged chunk: launches on the null stream, a hipError_t as int
+static int depth_scan(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, bool want_stats, char* err, size_t errlen, const depth_chunk_fn& each_chunk = nullptr) {
     // the prefix sum, a chunk of the difference array at a time through one staging buffer: no second array of total_len entries on the device
     const uint32_t dbg = (uint32_t)optv(d->idx, O_debug_depth_tile);
     const uint32_t tile = dbg ? dbg : fin_depth_max_tile(), chunk_tiles = dbg ? 64u : fin_depth_max_chunk_tiles();
@@ -3293,6 +3300,7 @@ static int depth_scan(fin_depth* d, uint32_t min_depth, uint32_t* depth_out, boo
         const uint64_t n = std::min<uint64_t>(chunk, d->total_len - base);
         int rc = fin_launch_depth_scan_chunk((const int32_t*)d->d_diff + base, n, tile, d->d_tile, d_carry, d->d_stage, nullptr);
         if (rc == 0 && want_stats) rc = fin_launch_depth_stats(d->d_stage, base, n, d->d_ends, (uint32_t)d->n_unitigs, min_depth, d->d_stats, nullptr);
+        if (rc == 0 && each_chunk) rc = each_chunk(base, n);
         if (rc != 0) { set_err(err, errlen, std::string("depth scan kernels: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
         if (depth_out) HIPCHK(hipMemcpy(depth_out + base, d->d_stage, (size_t)n * 4, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels, and done before the next chunk is staged)
     }
@@ -3355,6 +3363,91 @@ int fin_colors_coverage(fin_colors* c, fin_cover* cov, fin_depth* dep, uint32_t 
     HIPCHK(hipMemcpy(host.data(), d_out, table, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels)
     memcpy(out, host.data(), (size_t)c->n_colors * 64);
     if (uncolored) *uncolored = host[c->n_colors];
+    return FIN_OK;
+}
+
+// ---- depth histograms, per index and per reference (fin_depthhist.hip) ---------------------------------------------------------------------
+static int depthhist_args(uint32_t n_bins, uint32_t bin_width, char* err, size_t errlen) {
+    if (n_bins == 0 || n_bins > FIN_DEPTH_HIST_MAX_BINS) { set_err(err, errlen, "n_bins is 1 .. " + std::to_string(FIN_DEPTH_HIST_MAX_BINS)); return FIN_EINVAL; }
+    if (bin_width == 0) { set_err(err, errlen, "bin_width is at least 1"); return FIN_EINVAL; }
+    return FIN_OK;
+}
+int fin_depth_histogram(fin_depth* d, uint32_t n_bins, uint32_t bin_width, uint64_t* hist_out, char* err, size_t errlen) {
+    if (!d || !hist_out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int arc = depthhist_args(n_bins, bin_width, err, errlen)) return arc;
+    // the wait, with the download's own codes and messages for a withheld step or a pair outside the index (nothing else happens in this call)
+    if (const int rc = fin_depth_download(d, 0, nullptr, nullptr, nullptr, err, errlen)) return rc;
+    if (d->total_len == 0 || d->n_unitigs == 0) { memset(hist_out, 0, (size_t)n_bins * 8); return FIN_OK; }
+    const uint32_t k = d->idx->k;
+    std::lock_guard<std::mutex> g(d->scan_mu);   // (d_hist is the scan's, like the staging buffer)
+    if (!d->d_hist && hipMalloc(&d->d_hist, (size_t)FIN_DEPTH_HIST_MAX_BINS * 8) != hipSuccess) { (void)hipGetLastError(); d->d_hist = nullptr; set_err(err, errlen, "out of device memory (depth histogram)"); return FIN_ENOMEM; }
+    HIPCHK(hipMemsetAsync(d->d_hist, 0, (size_t)n_bins * 8, nullptr));
+    const int rc = depth_scan(d, 0, nullptr, false, err, errlen, [&](uint64_t base, uint64_t n) {
+        return fin_launch_depth_spectrum(d->d_stage, base, n, d->d_ends, (uint32_t)d->n_unitigs, d->total_len, k, n_bins, bin_width, (uint64_t*)d->d_hist, nullptr);
+    });
+    if (rc) return rc;
+    std::vector<uint64_t> host(n_bins);
+    HIPCHK(hipMemcpy(host.data(), d->d_hist, (size_t)n_bins * 8, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels)
+    memcpy(hist_out, host.data(), (size_t)n_bins * 8);
+    return FIN_OK;
+}
+
+int fin_colors_depth_histogram(fin_colors* c, fin_depth* dep, uint32_t n_bins, uint32_t bin_width, uint64_t* out, uint64_t* uncolored, char* err, size_t errlen) {
+    if (!c || !dep || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int arc = depthhist_args(n_bins, bin_width, err, errlen)) return arc;
+    if (dep->idx != c->idx || dep->device != c->device) { set_err(err, errlen, "colours and depth accumulator belong to different indexes or devices"); return FIN_EINVAL; }
+    if (const int drc = colors_want_dense(c, err, errlen)) return drc;   // (the projection reads bits[u * W + w])
+    if (const int rc = fin_colors_download(c, nullptr, nullptr, err, errlen)) return rc;
+    if (const int rc = fin_depth_download(dep, 0, nullptr, nullptr, nullptr, err, errlen)) return rc;
+    const size_t cells = (size_t)c->n_colors * 2 * n_bins;
+    if (dep->total_len == 0 || c->n_unitigs == 0) {
+        memset(out, 0, cells * 8);
+        if (uncolored) memset(uncolored, 0, (size_t)n_bins * 8);
+        return FIN_OK;
+    }
+    const fin_index::Replica* rep = c->idx->replica_on(c->device);
+    if (!rep) { set_err(err, errlen, "index is not resident on that device: call fin_index_to_device first (no CPU fallback)"); return FIN_ENODEV; }
+    // unitigs per sub-range: what the table's budget holds, the option below it
+    const uint64_t budget = (64ull << 20) / ((uint64_t)n_bins * 4);   // >= 16384
+    const uint64_t opt = (uint64_t)optv(c->idx, O_depthhist_unitigs);
+    const uint32_t per = (uint32_t)std::min<uint64_t>(opt ? std::min(opt, budget) : budget, c->n_unitigs);
+    // one buffer kept on the colours: the table and the uncoloured histogram behind it, the class kernel's scratch, the class bytes, the sub-range's table
+    const size_t out_bytes = (cells + n_bins) * 8, cls_bytes = ((size_t)c->n_unitigs + 15) / 16 * 16, need = out_bytes + 64 + cls_bytes + (size_t)per * n_bins * 4;
+    std::lock_guard<std::mutex> gh(c->dh_mu);
+    if (c->dh_bytes < need) {
+        (void)hipFree(c->d_dh); c->d_dh = nullptr; c->dh_bytes = 0;
+        if (hipMalloc(&c->d_dh, need) != hipSuccess) { (void)hipGetLastError(); c->d_dh = nullptr; set_err(err, errlen, "out of device memory (colour depth histograms)"); return FIN_ENOMEM; }
+        c->dh_bytes = need;
+    }
+    uint64_t* const o = (uint64_t*)c->d_dh;
+    uint64_t* const none8 = (uint64_t*)((char*)c->d_dh + out_bytes);
+    uint8_t* const cls = (uint8_t*)c->d_dh + out_bytes + 64;
+    uint32_t* const d_V = (uint32_t*)((char*)c->d_dh + out_bytes + 64 + cls_bytes);
+    const uint32_t nu = (uint32_t)c->n_unitigs, k = rep->dev.k;
+    const uint32_t* const ends = c->idx->ends.data();   // ends_p on the host: ends[u] is the start of unitig u, ends[nu] == total_len
+    std::lock_guard<std::mutex> g(dep->scan_mu);
+    HIPCHK(hipMemsetAsync(o, 0, out_bytes, nullptr));
+    if (const int krc = fin_launch_color_classes(c->d_bits, nu, c->words, rep->dev.ends, c->idx->total_len, k, cls, none8, nullptr)) {
+        set_err(err, errlen, std::string("colour class kernel: ") + hipGetErrorString((hipError_t)krc)); return FIN_ENODEV;
+    }
+    uint32_t u_at = 0;   // the unitig that holds the chunk's first position: chunks ascend, so does this
+    const int rc = depth_scan(dep, 0, nullptr, false, err, errlen, [&](uint64_t base, uint64_t n) {
+        while (u_at + 1u < nu && ends[u_at + 1u] <= base) u_at++;
+        // a unitig that straddles a chunk or a sub-range seam is binned twice with partial counts, which the sums do not notice
+        for (uint64_t u_lo = u_at; u_lo < nu && ends[u_lo] < base + n; u_lo += per) {
+            const uint32_t u_hi = (uint32_t)std::min<uint64_t>(nu, u_lo + per);
+            const uint64_t lo = std::max<uint64_t>(ends[u_lo], base) - base, hi = std::min<uint64_t>(ends[u_hi], base + n) - base;
+            const int krc = fin_launch_color_depth_hist(dep->d_stage, base, n, lo, hi, rep->dev.ends, nu, c->idx->total_len, k, n_bins, bin_width, (uint32_t)u_lo, u_hi,
+                                                        d_V, c->d_bits, c->words, c->n_colors, cls, 0u, o, o + cells, nullptr);
+            if (krc) return krc;
+        }
+        return 0;
+    });
+    if (rc) return rc;
+    std::vector<uint64_t> host(cells + n_bins);
+    HIPCHK(hipMemcpy(host.data(), o, out_bytes, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels)
+    memcpy(out, host.data(), cells * 8);
+    if (uncolored) memcpy(uncolored, host.data() + cells, (size_t)n_bins * 8);
     return FIN_OK;
 }
 

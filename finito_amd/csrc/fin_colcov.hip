@@ -130,6 +130,22 @@ extern "C" uint32_t fin_colcov_chunk(uint64_t n_unitigs, uint32_t W, uint32_t co
     return (uint32_t)((c + 63u) / 64u * 64u);
 }
 
+// the class byte alone, for a caller that projects something else through the matrix (fin_depthhist.hip): cls[u] = 0, 1 or 2 as above, by fin_colcov_class_kernel
+// as it stands.  none8: eight uint64 of device scratch the kernel adds the empty rows' k-mers to (zeroed here; not a result)
+extern "C" int fin_launch_color_classes(const void* bits, uint32_t n_unitigs, uint32_t W, const uint32_t* ends_p, uint64_t total_len, uint32_t k, void* cls, uint64_t* none8,
+                                        hipStream_t stream) {
+    if (W == 0 || W > 64u || n_unitigs >= 0x80000000u) return (int)hipErrorInvalidValue;
+    if (n_unitigs == 0) return 0;
+    const hipError_t e = hipMemsetAsync(none8, 0, 64u, stream);
+    if (e != hipSuccess) return (int)e;
+    uint32_t S = 1;
+    while (S < W) S <<= 1;
+    const uint32_t per_block = FIN_CCV_BLK / S;
+    hipLaunchKernelGGL(fin_colcov_class_kernel, dim3((n_unitigs + per_block - 1u) / per_block), dim3(FIN_CCV_BLK), 0, stream, (const ull*)bits, n_unitigs, W, S, ends_p,
+                       total_len, k, (const ull*)nullptr, (const FinDepthStat*)nullptr, (uint8_t*)cls, (ull*)none8);
+    return (int)hipGetLastError();
+}
+
 // out: uint64[n_colors][8], none: uint64[8], both zeroed here on `stream`; cls: n_unitigs bytes, written here.  covered (uint64[n_unitigs]) and stats
 // (FinDepthStat[n_unitigs]) may be null.  loads: 0, the coalesced slices (what the library uses), or 1, wave-uniform loads (tools/ab_colcov.py compares them)
 extern "C" int fin_launch_color_coverage(const void* bits, uint32_t n_unitigs, uint32_t W, uint32_t n_colors, const uint32_t* ends_p, uint64_t total_len, uint32_t k,

@@ -30,7 +30,8 @@
 // tile sums behind the carry of the chunks before (fin_blk_scan_kernel's pattern), apply -- and a statistics kernel over the staged depths.  No block waits for
 // another.  The difference array is only read: the accumulator stays additive across downloads.  Element indices are uint64.
 //
-// Out of scope: partitioned indexes, fin_search_batch_multi, sums across ranks (the caller adds the downloaded arrays), the C++ mirror, medians, saturation.
+// Out of scope: partitioned indexes, fin_search_batch_multi, sums across ranks (the caller adds the downloaded arrays), the C++ mirror, saturation.  (Histograms, medians
+// and other quantiles of the staged depths: fin_depthhist.hip.)
 #include "fin_device.h"
 #include "fin_kernels.h"
 #include "fin_wave.h"

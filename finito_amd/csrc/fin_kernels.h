@@ -280,6 +280,21 @@ int fin_launch_color_coverage(const void* bits, uint32_t n_unitigs, uint32_t W, 
 uint32_t fin_colsim_chunk(uint64_t n_unitigs, uint32_t W, uint32_t colsim_chunk);
 int fin_launch_color_shared(const void* bits, uint32_t n_unitigs, uint32_t W, uint32_t n_colors, const uint32_t* ends_p, uint64_t total_len, uint32_t k,
                             const void* vals, uint32_t colsim_chunk, uint64_t* out, hipStream_t stream);
+// ... the class byte alone (fin_colcov_class_kernel unchanged): cls n_unitigs bytes; none8: eight uint64 of device scratch, zeroed and written here, not a result
+int fin_launch_color_classes(const void* bits, uint32_t n_unitigs, uint32_t W, const uint32_t* ends_p, uint64_t total_len, uint32_t k, void* cls, uint64_t* none8,
+                             hipStream_t stream);
+// fin_depthhist.hip -- depth histograms over the staged depths of fin_launch_depth_scan_chunk: bin(d) = min(d / bin_width, n_bins - 1), 1 <= n_bins <=
+// fin_depthhist_max_bins() = 1024, bin_width >= 1; a position counts iff a k-mer begins there (g + k <= the end of its unitig).  depth[0 .. n) are the depths of text
+// positions g_base .. g_base + n, 16-byte aligned.  fin_launch_depth_spectrum: hist uint64[n_bins], zeroed by the caller, += the chunk's spectrum.
+// fin_launch_color_depth_hist: one sub-range of unitigs [u_lo, u_hi) of the chunk, whose positions are the window [lo, hi) of the stage (fewer than 2^32): V
+// uint32[(u_hi - u_lo) * n_bins] is zeroed and binned, then projected through bits uint64[n_unitigs * W] under the class bytes cls: out uint64[n_colors][2][n_bins]
+// {all, only} and none uint64[n_bins] are added to (the caller zeroes them before the first sub-range).  variant: 0 = lane per colour, the only projection built
+uint32_t fin_depthhist_max_bins(void);
+int fin_launch_depth_spectrum(const uint32_t* depth, uint64_t g_base, uint64_t n, const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len, uint32_t k,
+                              uint32_t n_bins, uint32_t bin_width, uint64_t* hist, hipStream_t stream);
+int fin_launch_color_depth_hist(const uint32_t* depth, uint64_t g_base, uint64_t n, uint64_t lo, uint64_t hi, const uint32_t* ends_p, uint32_t n_unitigs,
+                                uint64_t total_len, uint32_t k, uint32_t n_bins, uint32_t bin_width, uint32_t u_lo, uint32_t u_hi, uint32_t* V, const void* bits,
+                                uint32_t W, uint32_t n_colors, const void* cls, uint32_t variant, uint64_t* out, uint64_t* none, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -513,6 +513,14 @@ static const char* SEARCH_HELP =
     "                        last chunk from a coverage bitmap and a depth kept there (those of --unitig-coverage / --unitig-depth when they are asked for\n"
     "                        too), at their cost: one more search of every chunk each. Coverage counts k-mers, so with --paired 1 mates need no pairing.\n"
     "                        Wants --color-refs; goes with --no-text 1, --abundance, --eqclasses, --assign-weights and --paired 1. Not for a partitioned index.\n"
+    "      --depth-histogram FILE  also write the run's k-mer spectrum, binned on the GPU after the last chunk: one line depth<TAB>k-mers per bin -- how many\n"
+    "                        k-mer positions of the unitig text were found that many times; the last bin's depth is written >=X. Bins: --depth-bins B (1 .. 1024,\n"
+    "                        default 256) of --depth-bin-width D depths each (default 1), bin(d) = min(d / D, B - 1). Goes with -o and every per-unitig output.\n"
+    "      --color-depth-histogram FILE  with --color-refs: the same per reference. Lines colour<TAB>all|only<TAB>depth<TAB>k-mers for the non-zero entries (all: over\n"
+    "                        the unitigs that carry the colour, only: over those that carry it alone), then uncoloured<TAB>-<TAB>depth<TAB>k-mers.\n"
+    "      --color-depth-quantiles FILE  with --color-refs: the quartiles of every reference's k-mer depth, read from those histograms. Lines\n"
+    "                        colour<TAB>kmers<TAB>q250<TAB>q500<TAB>q750<TAB>kmers_only<TAB>q250_only<TAB>q500_only<TAB>q750_only; - where there are no\n"
+    "                        k-mers, >=X where the quantile lies in the last bin. Neither colour file goes with --compact-colors 1.\n"
     "      --compact-colors 1  with --color-refs: after the colouring and before the first chunk of reads, deduplicate the colour rows on the GPU\n"
     "                        (every distinct colour set once and a set id per unitig instead of the dense matrix). Prints\n"
     "                        'colour sets<TAB>n_sets<TAB>bytes dense<TAB>bytes compact' to stderr; every per-read and per-run colour output is byte-identical.\n"
@@ -1481,16 +1489,17 @@ static void write_color_similarity(const string& path, fin_cover* cov, size_t nc
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "color-similarity", "color-similarity-covered", "compact-colors", "color-sets-out", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "depth-histogram", "depth-bins", "depth-bin-width", "color-depth-histogram", "color-depth-quantiles", "color-similarity", "color-similarity-covered", "compact-colors", "color-sets-out", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
     if (o.has("color-similarity-covered") && !o.has("color-similarity")) throw runtime_error("--color-similarity-covered is only legal together with --color-similarity");
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity") && !o.has("taxa") && !o.has("taxon-report"))
-        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity") && !o.has("taxa") && !o.has("taxon-report") && !o.has("depth-histogram") && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles"))
+        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report, --abundance, --depth-histogram, --color-depth-histogram or --color-depth-quantiles (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
     if (o.has("color-coverage") && !o.has("color-refs")) throw runtime_error("--color-coverage wants colours: --color-refs LIST");
+    if ((o.has("color-depth-histogram") || o.has("color-depth-quantiles")) && !o.has("color-refs")) throw runtime_error("--color-depth-histogram and --color-depth-quantiles want colours: --color-refs LIST");
     if ((o.has("color-similarity") || o.has("color-similarity-covered")) && !o.has("color-refs")) throw runtime_error("--color-similarity and --color-similarity-covered want colours: --color-refs LIST");
     const bool compact_colors = o.has("compact-colors") && o.get("compact-colors") != "0" && o.get("compact-colors") != "false";
     if (compact_colors && !o.has("color-refs")) throw runtime_error("--compact-colors 1 wants colours: --color-refs LIST");
@@ -1498,6 +1507,21 @@ static int search_fmin(int argc, char** argv) {
     for (const char* name : {"color-coverage", "color-similarity", "taxonomy"})
         if (compact_colors && o.has(name))
             throw runtime_error(string("--compact-colors 1 is not available with --") + name + ": coverage, shared k-mers and taxonomy read the dense colour matrix (fin_colors_expand), over sets they are not built");
+    for (const char* name : {"color-depth-histogram", "color-depth-quantiles"})
+        if (compact_colors && o.has(name))
+            throw runtime_error(string("--compact-colors 1 is not available with --") + name + ": the depth histograms read the dense colour matrix (fin_colors_expand), over sets they are not built");
+    // the bins of --depth-histogram, --color-depth-histogram and --color-depth-quantiles: bin(d) = min(d / D, B - 1)
+    const bool dh_asked = o.has("depth-histogram") || o.has("color-depth-histogram") || o.has("color-depth-quantiles");
+    if ((o.has("depth-bins") || o.has("depth-bin-width")) && !dh_asked) throw runtime_error("--depth-bins and --depth-bin-width are only legal together with --depth-histogram, --color-depth-histogram or --color-depth-quantiles");
+    auto dh_number = [&](const char* name, unsigned long long dflt, unsigned long long top) -> uint32_t {
+        if (!o.has(name)) return (uint32_t)dflt;
+        const string v = o.get(name);
+        size_t used = 0; unsigned long long t = 0;
+        try { t = stoull(v, &used); } catch (...) { used = 0; }
+        if (v.empty() || used != v.size() || v[0] == '-' || t < 1 || t > top) throw runtime_error(string("--") + name + " wants a number from 1 to " + to_string(top));
+        return (uint32_t)t;
+    };
+    const uint32_t dh_bins = dh_number("depth-bins", 256, FIN_DEPTH_HIST_MAX_BINS), dh_width = dh_number("depth-bin-width", 1, 0xFFFFFFFFull);
     g_paired = o.has("paired") && o.get("paired") != "0" && o.get("paired") != "false";
     const bool pair_both = o.has("pair-both") && o.get("pair-both") != "0" && o.get("pair-both") != "false";
     if (g_paired && !o.has("color-refs")) throw runtime_error("--paired 1 wants colours: --color-refs LIST (fragments are what --pseudoalign, --eqclasses, --color-report and --abundance then take)");
@@ -1514,7 +1538,7 @@ static int search_fmin(int argc, char** argv) {
     if (asg_asked && !o.has("assign") && !o.has("assign-report")) throw runtime_error("--assign-weights wants a result: --assign FILE and / or --assign-report FILE");
     for (const char* name : {"assign", "assign-report", "assign-threshold"})
         if (o.has(name) && !asg_asked) throw runtime_error(string("--") + name + " is only legal together with --assign-weights");
-    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked && !o.has("color-coverage") && !o.has("color-similarity") && !tax_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report or --abundance");
+    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked && !o.has("color-coverage") && !o.has("color-similarity") && !tax_asked && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles")) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report, --abundance, --color-depth-histogram or --color-depth-quantiles");
     if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked && !asg_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
     if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses, --color-report or --abundance");
     if (o.has("eqclasses-in") && !eq_asked) throw runtime_error("--eqclasses-in is only legal together with --eqclasses, --color-report or --abundance");
@@ -1637,6 +1661,8 @@ static int search_fmin(int argc, char** argv) {
     if (!depth_file.empty()) check_writable(depth_file);
     const string colcov_file = o.get("color-coverage", "");
     if (!colcov_file.empty()) check_writable(colcov_file);
+    const string dh_file = o.get("depth-histogram", ""), cdh_file = o.get("color-depth-histogram", ""), cdq_file = o.get("color-depth-quantiles", "");
+    for (const string* f : {&dh_file, &cdh_file, &cdq_file}) if (!f->empty()) check_writable(*f);
     const string colsim_file = o.get("color-similarity", ""), colsim_cov_file = o.get("color-similarity-covered", "");
     if (!colsim_file.empty()) check_writable(colsim_file);
     if (!colsim_cov_file.empty()) check_writable(colsim_cov_file);
@@ -1733,6 +1759,7 @@ static int search_fmin(int argc, char** argv) {
     if (!scr_file.empty() && index.partitioned()) throw runtime_error("--screen is not available with a partitioned index");
     if (!cls_file.empty() && index.partitioned()) throw runtime_error("--classify is not available with a partitioned index");
     if (!report_file.empty() && index.partitioned()) throw runtime_error("--label-report is not available with a partitioned index");
+    if (dh_asked && index.partitioned()) throw runtime_error("--depth-histogram, --color-depth-histogram and --color-depth-quantiles are not available with a partitioned index");
     if (!colcov_file.empty() && index.partitioned()) throw runtime_error("--color-coverage is not available with a partitioned index");
     if (!color_refs.empty() && index.partitioned()) throw runtime_error("--color-refs is not available with a partitioned index");
     index.to_device();
@@ -1747,7 +1774,7 @@ static int search_fmin(int argc, char** argv) {
         if (fin_cover_create(index.handle(), first_dev, &g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     struct DepthOwner { ~DepthOwner() { fin_depth_free(g_depth); g_depth = nullptr; } } depth_owner;
-    if (!depth_file.empty() || !colcov_file.empty()) {
+    if (!depth_file.empty() || !colcov_file.empty() || dh_asked) {   // (the depth histograms share the depth of --unitig-depth / --color-coverage)
         char err[512] = {0};
         if (fin_depth_create(index.handle(), first_dev, &g_depth, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
@@ -2078,6 +2105,62 @@ static int search_fmin(int argc, char** argv) {
         ofstream cf(colcov_file, ios::binary | ios::trunc);
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + colcov_file);
+    }
+    if (dh_asked) {   // the depth histograms, after the last chunk: binned on the device from the staged prefix sum
+        char err[512] = {0};
+        auto write_file = [](const string& name, const string& t) {
+            ofstream cf(name, ios::binary | ios::trunc);
+            cf.write(t.data(), (streamsize)t.size());
+            if (!cf) throw runtime_error("Error writing to file: " + name);
+        };
+        // a bin's depth: its lower edge, the last of several bins as ">=X"
+        auto bin_name = [&](uint32_t b) { return string(b == dh_bins - 1u && dh_bins > 1u ? ">=" : "") + to_string((uint64_t)b * dh_width); };
+        if (!dh_file.empty()) {
+            vector<uint64_t> hist(dh_bins);
+            if (fin_depth_histogram(g_depth, dh_bins, dh_width, hist.data(), err, sizeof err) != FIN_OK) throw runtime_error(err);
+            string text;
+            for (uint32_t b = 0; b < dh_bins; b++) { text += bin_name(b); text += '\t'; text += to_string(hist[b]); text += '\n'; }
+            write_file(dh_file, text);
+        }
+        if (!cdh_file.empty() || !cdq_file.empty()) {
+            const size_t nc = color_refs.size();
+            vector<uint64_t> tab(nc * 2 * dh_bins), unc(dh_bins);
+            if (fin_colors_depth_histogram(g_colors, g_depth, dh_bins, dh_width, tab.data(), unc.data(), err, sizeof err) != FIN_OK) throw runtime_error(err);
+            if (!cdh_file.empty()) {   // the non-zero entries
+                string text;
+                for (size_t c = 0; c < nc; c++)
+                    for (int j = 0; j < 2; j++)
+                        for (uint32_t b = 0; b < dh_bins; b++)
+                            if (const uint64_t v = tab[(c * 2 + j) * dh_bins + b]) { text += to_string(c); text += j ? "\tonly\t" : "\tall\t"; text += bin_name(b); text += '\t'; text += to_string(v); text += '\n'; }
+                for (uint32_t b = 0; b < dh_bins; b++)
+                    if (unc[b]) { text += "uncoloured\t-\t"; text += bin_name(b); text += '\t'; text += to_string(unc[b]); text += '\n'; }
+                write_file(cdh_file, text);
+            }
+            if (!cdq_file.empty()) {
+                // the quantile rule of finito_amd.h: t = max(1, ceil(p N / 1000)), the smallest bin whose cumulative count reaches t; "-" without k-mers.  (N is
+                // below 2^32, the text's length: p N fits 64 bits)
+                auto quantile = [&](const uint64_t* h, uint64_t N, uint32_t p) -> string {
+                    if (N == 0) return "-";
+                    const uint64_t t = max<uint64_t>(1, ((uint64_t)p * N + 999u) / 1000u);
+                    uint64_t acc = 0;
+                    for (uint32_t b = 0; b < dh_bins; b++) { acc += h[b]; if (acc >= t) return bin_name(b); }
+                    return "-";   // (not reached: t <= N)
+                };
+                string text;
+                for (size_t c = 0; c < nc; c++) {
+                    text += to_string(c);
+                    for (int j = 0; j < 2; j++) {
+                        const uint64_t* h = tab.data() + (c * 2 + j) * dh_bins;
+                        uint64_t N = 0;
+                        for (uint32_t b = 0; b < dh_bins; b++) N += h[b];
+                        text += '\t'; text += to_string(N);
+                        for (uint32_t p : {250u, 500u, 750u}) { text += '\t'; text += quantile(h, N, p); }
+                    }
+                    text += '\n';
+                }
+                write_file(cdq_file, text);
+            }
+        }
     }
     if (!colsim_cov_file.empty()) write_color_similarity(colsim_cov_file, g_cover, color_refs.size());   // ... and in what the run found, after the last chunk
     if (g_pileup) {   // the pileup, after the last chunk: the covered positions, and the candidates called on the device

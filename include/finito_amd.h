@@ -575,7 +575,8 @@ int fin_records_cover(const fin_read_record* recs, uint64_t n_reads, const int32
  * stretch, not one per k-mer (fin_depth.hip).  fin_depth_download makes the depths with a prefix sum on the device, a chunk at a time through a fixed staging
  * buffer, and leaves the difference array as it is: add, download, add, download gives the sum.
  * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi, sums across the ranks of a job (a caller with several GPUs keeps an accumulator per
- * replica and adds the downloaded arrays), the C++ mirror (FinimizerIndex.hh), medians on the device, saturation. */
+ * replica and adds the downloaded arrays), the C++ mirror (FinimizerIndex.hh), saturation.  Medians and other quantiles of the depth: fin_depth_histogram and
+ * fin_colors_depth_histogram below (DEPTH HISTOGRAMS AND QUANTILES). */
 typedef struct fin_depth fin_depth;
 /* a unitig's statistics: the sum of its positions' depths (= fin_hits' count), the greatest, and how many positions have depth >= min_depth */
 typedef struct fin_depth_stat { uint64_t sum; uint32_t max; uint32_t n_at_least; } fin_depth_stat;   /* 16 bytes */
@@ -1206,6 +1207,45 @@ int fin_colors_coverage(fin_colors* c, fin_cover* cov /* may be NULL */, fin_dep
  * outside 1 .. 4096.  uncolored may be NULL */
 int fin_unitig_color_coverage(const uint64_t* bits, uint64_t n_unitigs, uint32_t n_colors, const uint64_t* nk, const uint64_t* covered /* may be NULL */,
                               const fin_depth_stat* stats /* may be NULL */, fin_color_coverage* out, fin_color_coverage* uncolored, int n_threads);
+
+/* ---- DEPTH HISTOGRAMS AND QUANTILES, per index and per reference, on the device ----
+ * The mean depth of fin_colors_coverage is the number a repeat, a plasmid or a conserved region dominates; what tells whether a reference is present is the
+ * MEDIAN k-mer depth and its inter-quartile range, and what tells where error k-mers end is the k-mer SPECTRUM of the run.  Integers throughout.
+ *   BINS      n_bins in 1 .. FIN_DEPTH_HIST_MAX_BINS, bin_width >= 1; bin(d) = min(d / bin_width, n_bins - 1) with integer division: the last bin is "this much
+ *             or more".
+ *   COUNTED   a position g of the unitig text counts iff a k-mer begins there: with u the unitig that holds g, g - start(u) < nk(u) = len(u) - k + 1 (0 for a
+ *             unitig shorter than k).  The last k - 1 positions of every unitig never count, whatever the difference array holds there.
+ *   SPECTRUM  hist[b] = the number of counted positions g with bin(depth[g]) == b; depth is fin_depth_download's, uint32, modulo 2^32.  The sum over b of
+ *             hist[b] is the sum over u of nk(u).
+ *   PER REFERENCE, for every colour c < n_colors: out[c][0][b] is the same count over the unitigs whose row has bit c, out[c][1][b] over those whose row is {c}
+ *             alone; uncolored[b] over the unitigs with an empty row.
+ *   IDENTITIES (bin_width 1, n_bins above the greatest depth, against fin_colors_coverage of the same objects): the sum over b of out[c][0][b] is kmers[c], of
+ *             b * out[c][0][b] depth_sum[c], over b >= T solid[c] under min_depth = T; the same for [1] and the _only fields and for uncolored; hist ==
+ *             uncolored + the sum over c of out[c][1] + the histogram over the unitigs of two or more colours.
+ *   QUANTILE, in thousandths like every other threshold here.  For a histogram h with N = the sum of h > 0 and p in 0 .. 1000:
+ *               t = max(1, ceil(p * N / 1000));  the quantile is the smallest b with h[0] + ... + h[b] >= t, reported as the bin's lower edge b * bin_width;
+ *               it is SATURATED ("this much or more") when b == n_bins - 1 and n_bins > 1.  With N == 0 there is no quantile.
+ *             The median is p = 500, the quartiles 250 and 750.  The library returns histograms; the rule is applied by the callers (the Python module's
+ *             histogram_quantile and the command's --color-depth-quantiles), which must agree with this statement.
+ * Both calls are waiting calls with fin_depth_download's and fin_colors_coverage's contract: they wait for every add and reset issued so far to each accumulator,
+ * change none, and run inside the chunk loop of the download's prefix sum -- a chunk is scanned into the staging buffer and binned from there, no second array of
+ * total_len entries exists.  The per-reference call walks a staged chunk in sub-ranges of unitigs (option "depthhist_unitigs") whose table uint32[unitigs][n_bins]
+ * fits a fixed budget; the results do not depend on it.  FIN_EINVAL for a NULL argument (uncolored may be NULL), n_bins outside 1 .. 1024, bin_width == 0 and a
+ * depth accumulator of another index or device (the message says which), and for a compact matrix ("fin_colors_expand first"); the downloads' codes and messages
+ * for a withheld step or a pair outside the index are passed on.  On every error nothing is written.  An empty index gives zeros.
+ * Out of scope: partitioned indexes, fin_search_batch_multi, the C++ mirror, compact colour sets, more than 1024 bins, logarithmic bins. */
+#define FIN_DEPTH_HIST_MAX_BINS 1024u
+int fin_depth_histogram(fin_depth* d, uint32_t n_bins, uint32_t bin_width, uint64_t* hist_out /* [n_bins] */, char* err, size_t errlen);
+int fin_colors_depth_histogram(fin_colors* c, fin_depth* dep, uint32_t n_bins, uint32_t bin_width, uint64_t* out /* [n_colors][2][n_bins] */,
+                               uint64_t* uncolored /* [n_bins], may be NULL */, char* err, size_t errlen);
+/* host twins, no device: depth uint32[total_len] (fin_depth_download's), unitig_ends[n_unitigs] as FIN_X_ENDS, bits uint64[n_unitigs][W].  Threads take ranges of
+ * unitigs and their tables are added at the end: the result does not depend on n_threads (<= 0: all cores).  FIN_EINVAL for a NULL argument (uncolored may be
+ * NULL), k < 1, n_bins outside 1 .. 1024, bin_width == 0, ends that decrease and a bit at or above n_colors; FIN_ELIMIT for n_colors outside 1 .. 4096 */
+int fin_depth_positions_histogram(const uint32_t* depth, const int64_t* unitig_ends, uint64_t n_unitigs, int k, uint32_t n_bins, uint32_t bin_width,
+                                  uint64_t* hist_out /* [n_bins] */, int n_threads);
+int fin_unitig_color_depth_histogram(const uint32_t* depth, const int64_t* unitig_ends, uint64_t n_unitigs, int k, const uint64_t* bits, uint32_t n_colors,
+                                     uint32_t n_bins, uint32_t bin_width, uint64_t* out /* [n_colors][2][n_bins] */, uint64_t* uncolored /* [n_bins], may be NULL */,
+                                     int n_threads);
 
 /* ---- SHARED K-MERS BETWEEN REFERENCES: the colour matrix times itself, on the device ----
  * How the references relate to each other: two references with the same column of the colour matrix cannot be told apart by anything downstream, one contained
