@@ -309,6 +309,22 @@ def lib():
         L.fin_search_batch_pseudoalign_paired.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, u64p, vp, u64p, cp, C.c_size_t]
         L.fin_search_batch_add_eqclasses_paired.argtypes = [vp, cp, u64p, u64, C.c_int, vp, u32, u32, cp, C.c_size_t]
         L.fin_records_pseudoalign_paired.argtypes = [vp, u64, vp, u64, C.c_int, u64p, u64, u32, u32, u32, u64p, vp, C.c_int]
+        L.fin_fragments_create.argtypes = [vp, C.c_int, u32, u32, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_fragments_reset.argtypes = [vp, vp]
+        L.fin_fragments_free.argtypes = [vp]
+        L.fin_fragments_free.restype = None
+        L.fin_batch_add_fragments.argtypes = [vp, vp, vp, cp, C.c_size_t]
+        L.fin_fragments_download.argtypes = [vp, vp, vp, cp, C.c_size_t]
+        L.fin_fragments_device_hist.argtypes = [vp]
+        L.fin_fragments_device_hist.restype = vp
+        L.fin_batch_fragments.argtypes = [vp, u64p, cp, C.c_size_t]
+        L.fin_batch_download_fragments.argtypes = [vp, vp, cp, C.c_size_t]
+        L.fin_batch_device_fragments.argtypes = [vp]
+        L.fin_batch_device_fragments.restype = vp
+        L.fin_search_batch_add_fragments.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
+        L.fin_search_batch_fragments.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
+        L.fin_records_fragments.argtypes = [vp, u64, vp, u64, C.c_int, i64p, u64, u32, u32, vp, vp, vp, C.c_int]
+        L.fin_effective_lengths.argtypes = [vp, u32, u32, vp, u64, vp]
         L.fin_eqclasses_create.argtypes = [vp, u64, C.POINTER(vp), cp, C.c_size_t]
         L.fin_eqclasses_reset.argtypes = [vp, vp]
         L.fin_eqclasses_free.argtypes = [vp]
@@ -631,6 +647,20 @@ class Batch:
     def device_pair_ptrs(self):
         """(rows, heads) device pointers of the fragments' rows, 0 before pseudoalign_pairs()"""
         return int(self.L.fin_batch_device_pair_rows(self.h) or 0), int(self.L.fin_batch_device_pair_heads(self.h) or 0)
+
+    def fragments(self):
+        """the most recent run's reads as interleaved mates, one FRAGMENT_DTYPE entry per fragment, made on the device (fin_batch_fragments +
+        fin_batch_download_fragments; include/finito_amd.h: FRAGMENT GEOMETRY): where the mates lie, which way they face, the class and the length"""
+        err = C.create_string_buffer(512)
+        nf = C.c_uint64(0)
+        _check(self.L.fin_batch_fragments(self.h, C.byref(nf), err, 512), err)
+        out = np.zeros(max(int(nf.value), 1), dtype=FRAGMENT_DTYPE)
+        _check(self.L.fin_batch_download_fragments(self.h, out.ctypes.data_as(C.c_void_p), err, 512), err)
+        return out[: int(nf.value)]
+
+    def device_fragments_ptr(self):
+        """the fragments' device pointer, 0 before fragments()"""
+        return int(self.L.fin_batch_device_fragments(self.h) or 0)
 
     def assign(self, assigner, permille=1000, pairs=False, both=False, stream=None):
         """the most recent run's reads (pairs: its fragments) assigned to references under an Assign's weights and thresholds, made and counted on the device
@@ -1734,6 +1764,96 @@ class Pileup(_Accumulator):
         return int(self.L.fin_pileup_device_alt(self.h) or 0), int(self.L.fin_pileup_device_cover_diff(self.h) or 0)
 
 
+FIN_FRAG_NONE, FIN_FRAG_ONE, FIN_FRAG_SPLIT, FIN_FRAG_TANDEM, FIN_FRAG_OUTWARD, FIN_FRAG_INWARD = range(6)
+FIN_FRAG_MAX_BINS = 4096
+FRAGMENT_CLASS_NAMES = ("none", "one", "split", "tandem", "outward", "inward")
+
+
+def _frag_hist_args(what, n_bins, bin_width):
+    nb, bw = int(n_bins), int(bin_width)
+    if not 1 <= nb <= FIN_FRAG_MAX_BINS:
+        raise FinitoError(FIN_EINVAL, "%s: n_bins is 1 .. %d" % (what, FIN_FRAG_MAX_BINS))
+    if not 1 <= bw <= 0xFFFFFFFF:
+        raise FinitoError(FIN_EINVAL, "%s: bin_width is 1 .. 2^32 - 1" % what)
+    return nb, bw
+
+
+def effective_lengths(hist, ref_lengths, bin_width=1):
+    """host: float64[n], the effective length of references of ref_lengths[n] bases under the fragment-length histogram `hist` (fin_effective_lengths;
+    include/finito_amd.h): the length minus the mean of the fragment lengths that fit, plus one; the last bin, "this much or more", is left out.  bin_width must
+    be 1"""
+    h = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    rl = np.ascontiguousarray(ref_lengths, dtype=np.uint64).reshape(-1)
+    if int(bin_width) != 1:
+        raise FinitoError(FIN_EINVAL, "effective_lengths: bin_width must be 1 (it is %d): effective lengths are read from a histogram of single lengths" % int(bin_width))
+    if not 1 <= len(h) <= FIN_FRAG_MAX_BINS:
+        raise FinitoError(FIN_EINVAL, "effective_lengths: the histogram must have 1 .. %d bins (it has %d)" % (FIN_FRAG_MAX_BINS, len(h)))
+    out = np.zeros(max(len(rl), 1), dtype=np.float64)
+    rc = lib().fin_effective_lengths(h.ctypes.data_as(C.c_void_p), len(h), int(bin_width), rl.ctypes.data_as(C.c_void_p), len(rl), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise FinitoError(rc, "fin_effective_lengths refused its arguments")
+    return out[: len(rl)]
+
+
+class FragmentStats:
+    """what Fragments.download() returns: hist uint64[n_bins] of the inward fragments' lengths (bin b: min(length // bin_width, n_bins - 1) == b), counters
+    uint64[7] = the six classes and len_sum; the classes by name (none, one, split, tandem, outward, inward), n_fragments their sum"""
+
+    def __init__(self, hist, counters, bin_width):
+        self.hist, self.counters, self.bin_width = hist, counters, int(bin_width)
+        self.n_bins = len(hist)
+        for i, name in enumerate(FRAGMENT_CLASS_NAMES):
+            setattr(self, name, int(counters[i]))
+        self.len_sum = int(counters[6])
+        self.n_fragments = sum(int(c) for c in counters[:6])
+
+    @property
+    def mean(self):
+        """the mean length of the inward fragments, None without one"""
+        return self.len_sum / self.inward if self.inward else None
+
+    def quantile(self, permille):
+        """(length, saturated) of the inward fragments under histogram_quantile's rule, None without one"""
+        return histogram_quantile(self.hist, permille, self.bin_width)
+
+    def effective_lengths(self, ref_lengths):
+        """float64[n]: effective_lengths() under this histogram (bin_width must be 1)"""
+        return effective_lengths(self.hist, ref_lengths, self.bin_width)
+
+
+class Fragments(_Accumulator):
+    """the insert-size histogram and the class counters of a run's fragments -- interleaved mates, fragment f = reads 2f and 2f + 1 --, resident in HBM beside one
+    replica of the index (fin_fragments_* of the C ABI; include/finito_amd.h: FRAGMENT GEOMETRY)"""
+    _FREE, _RESET = "fin_fragments_free", "fin_fragments_reset"
+
+    def __init__(self, index, device=0, n_bins=1024, bin_width=1):
+        self.index = index
+        self.n_bins, self.bin_width = _frag_hist_args("Fragments", n_bins, bin_width)
+        self._create("fin_fragments_create", index.h, int(device), self.n_bins, self.bin_width)
+
+    def add(self, batch, stream=None):
+        """accumulator += the fragments of the batch's most recent run, on a HIP stream, behind that run; no sync (fin_batch_add_fragments).  Adding the same run
+        twice counts it twice."""
+        return _acc_add(self, "fin_batch_add_fragments", batch, stream)
+
+    def add_reads(self, reads, strands=FIN_MERGED):
+        """search interleaved mates from host buffers, sub-batches pipelined and cut between pairs only, and add their fragments; nothing comes back
+        (fin_search_batch_add_fragments)"""
+        return _acc_add_reads(self, "fin_search_batch_add_fragments", reads, strands)
+
+    def download(self):
+        """FragmentStats; waits for the adds and leaves the accumulator as it is (fin_fragments_download)"""
+        hist = np.zeros(self.n_bins, dtype=np.uint64)
+        counters = np.zeros(7, dtype=np.uint64)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_fragments_download(self.h, hist.ctypes.data_as(C.c_void_p), counters.ctypes.data_as(C.c_void_p), err, 512), err)
+        return FragmentStats(hist, counters, self.bin_width)
+
+    def device_ptr(self):
+        """uint64 hist[n_bins], then the seven counters, in HBM"""
+        return int(self.L.fin_fragments_device_hist(self.h) or 0)
+
+
 class FinimizerIndex:
     """Mirror of the reference class (FinimizerIndex.hh:26-259) backed by the HIP path."""
 
@@ -2115,6 +2235,19 @@ class FinimizerIndex:
                                                           C.byref(npos), err, 512), err)
         return (rows[:nf] if want_rows else None), heads[:nf], int(npos.value)
 
+    def fragments(self, n_bins=1024, bin_width=1, device=0):
+        """a zeroed fragment-length histogram with its class counters beside the replica on `device` (Fragments)"""
+        return Fragments(self, device, n_bins, bin_width)
+
+    def fragments_reads(self, reads, strands=FIN_MERGED):
+        """FRAGMENT_DTYPE[F]: interleaved mates from host buffers as fragments, sub-batches pipelined and cut between pairs only (fin_search_batch_fragments)"""
+        bases, offsets = flatten(reads)
+        nf = (len(offsets) - 1) // 2
+        out = np.zeros(max(nf, 1), dtype=FRAGMENT_DTYPE)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_fragments(self.h, *_reads_args((bases, offsets)), int(strands), out.ctypes.data_as(C.c_void_p), err, 512), err)
+        return out[:nf]
+
     def unitig_numbers(self, unitigs):
         """fin_index_unitig_numbers: uint32[len(unitigs)] -- the index's number of each given unitig sequence (the index renumbers its input); raises for a
         sequence that is not a unitig of this index"""
@@ -2243,6 +2376,7 @@ READ_TAXON_DTYPE = np.dtype([("taxon", np.uint32), ("score", np.uint32), ("clade
 READ_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), ("n_colors", np.uint32), ("reserved", np.uint32)])   # fin_read_pseudo
 PAIR_PSEUDO_DTYPE = np.dtype([("n_found", np.uint32), ("n_colored", np.uint32), ("n_colors", np.uint32), ("n_colored_first", np.uint32)])   # fin_pair_pseudo
 FIN_PAIR_ANY, FIN_PAIR_BOTH = 0, 1
+FRAGMENT_DTYPE = np.dtype([("u", np.uint32), ("start", np.uint32), ("length", np.uint32), ("cls", np.uint32)])   # fin_fragment
 FIN_MAX_COLORS = 4096
 READ_ASSIGN_DTYPE = np.dtype([("n_assigned", np.uint32), ("best", np.uint32)])   # fin_read_assign
 FIN_NO_COLOR = 0xFFFFFFFF
@@ -2663,6 +2797,27 @@ def records_pseudoalign_pairs(recs, stream, k, bits, n_colors, permille=1000, bo
         raise FinitoError(rc, "fin_records_pseudoalign_paired: an odd number of reads, a mode that is neither FIN_PAIR_ANY nor FIN_PAIR_BOTH, n_colors outside 1 .. 4096, "
                               "permille above 1000, a bit at or above n_colors, a unitig number outside the matrix, or records and stream that do not belong together")
     return rows[:nf], heads[:nf]
+
+
+def records_fragments(recs, stream, k, ends, n_bins=1024, bin_width=1, n_threads=0):
+    """host: (frags FRAGMENT_DTYPE[F], hist uint64[n_bins], counters uint64[7]) from the records + stream of interleaved mates (fin_records_fragments) -- the CPU
+    statement of Batch.fragments and Fragments, read off every read's expanded slots"""
+    r = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+    st = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1, 2)
+    e = np.ascontiguousarray(ends, dtype=np.int64)
+    if not (0 <= int(n_bins) <= 0xFFFFFFFF and 0 <= int(bin_width) <= 0xFFFFFFFF):
+        raise FinitoError(FIN_EINVAL, "records_fragments: n_bins and bin_width are unsigned 32-bit numbers")
+    nf = len(r) // 2
+    frags = np.zeros(max(nf, 1), dtype=FRAGMENT_DTYPE)
+    hist = np.zeros(max(min(int(n_bins), FIN_FRAG_MAX_BINS), 1), dtype=np.uint64)
+    counters = np.zeros(7, dtype=np.uint64)
+    rc = lib().fin_records_fragments(r.ctypes.data_as(C.c_void_p), len(r), st.ctypes.data_as(C.c_void_p), len(st), int(k), e.ctypes.data_as(C.POINTER(C.c_int64)), len(e),
+                                     int(n_bins), int(bin_width), frags.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(C.c_void_p), counters.ctypes.data_as(C.c_void_p),
+                                     int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_fragments: an odd number of reads, n_bins outside 1 .. %d, bin_width 0, a unitig number outside the index, a k-mer that does "
+                              "not lie inside its unitig, or records and stream that do not belong together" % FIN_FRAG_MAX_BINS)
+    return frags[:nf], hist, counters
 
 
 def rows_eqclasses(rows, n_colors):

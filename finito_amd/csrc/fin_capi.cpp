@@ -790,6 +790,9 @@ struct fin_batch {
     void* d_psa_rows = nullptr; size_t cap_psa_rows = 0; void* d_psa_heads = nullptr; size_t cap_psa_heads = 0; bool psa_ready = false; uint32_t psa_words = 0;
     // per-fragment colour rows and heads (fin_batch_pseudoalign_paired): buffers of their own, kept and only grown; forgotten whenever the per-read rows are
     void* d_pair_rows = nullptr; size_t cap_pair_rows = 0; void* d_pair_heads = nullptr; size_t cap_pair_heads = 0; bool pair_ready = false; uint32_t pair_words = 0;
+    // per-fragment geometry (fin_batch_fragments): fin_fragment[n_reads / 2], then a flag word in a 16-byte line of its own; a buffer of its own, kept and only
+    // grown; forgotten wherever the read summaries are
+    void* d_frag = nullptr; size_t cap_frag = 0; bool frag_ready = false;
     // the assigned rows and heads of fin_batch_assign (per read or per fragment: asg_n of them) and the bin of fin_batch_assign_bin made from them: buffers of their
     // own, kept and only grown; asg_stream = the stream the assignment was put on, which its readers follow
     void* d_asg_rows = nullptr; size_t cap_asg_rows = 0; void* d_asg_heads = nullptr; size_t cap_asg_heads = 0; bool asg_ready = false; uint32_t asg_words = 0, asg_colors = 0;
@@ -831,7 +834,7 @@ void fin_batch_free(fin_batch* b) {
     if (b->ev_ctr) (void)hipEventDestroy(b->ev_ctr);
     (void)hipFree(b->d_cstream); (void)hipFree(b->d_frec); (void)hipFree(b->d_seg); (void)hipFree(b->d_text); (void)hipFree(b->d_last_bits); (void)hipFree(b->d_blk_sum); (void)hipFree(b->d_blk_off); (void)hipFree(b->d_total);
     (void)hipFree(b->d_sgm_cnt); (void)hipFree(b->d_sgm_bsum); (void)hipFree(b->d_sgm_boff); (void)hipFree(b->d_sgm_offs); (void)hipFree(b->d_sgm);
-    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls); (void)hipFree(b->d_tax); (void)hipFree(b->d_psa_rows); (void)hipFree(b->d_psa_heads); (void)hipFree(b->d_pair_rows); (void)hipFree(b->d_pair_heads);
+    (void)hipFree(b->d_rsum); (void)hipFree(b->d_scr_bits); (void)hipFree(b->d_scr_ids); (void)hipFree(b->d_scr_bsum); (void)hipFree(b->d_scr_boff); (void)hipFree(b->d_cls); (void)hipFree(b->d_tax); (void)hipFree(b->d_psa_rows); (void)hipFree(b->d_psa_heads); (void)hipFree(b->d_pair_rows); (void)hipFree(b->d_pair_heads); (void)hipFree(b->d_frag);
     (void)hipFree(b->d_asg_rows); (void)hipFree(b->d_asg_heads); (void)hipFree(b->d_bin_bits); (void)hipFree(b->d_bin_ids); (void)hipFree(b->d_bin_bsum); (void)hipFree(b->d_bin_boff);
     (void)hipFree(b->d_ovf_list); (void)hipFree(b->d_ovf_count); (void)hipFree(b->d_ovf_scratch); (void)hipFree(b->d_count);
     for (auto& r : b->runs) for (auto& e : r.e) (void)hipEventDestroy(e);
@@ -956,7 +959,7 @@ static int batch_load(fin_batch* b, const char* first_base, const uint64_t* offs
     //  decoding, inside its timed region, search_fmin.hh:46-71 -- is the first kernel of every step, see fin_batch_run)
     b->n_chunks = n_chunks; b->max_read_len = max_len;
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "upload");
-    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
+    b->ran = false; b->last_stream = nullptr; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->frag_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
     b->rounds_hint = 0; b->ctr_pending = false;   // (new reads: nothing is known about the rounds they need)
     b->text_reads_state = 0;
     return FIN_OK;
@@ -1000,7 +1003,7 @@ int fin_batch_run(fin_batch* b, int strands, void* hip_stream, char* err, size_t
     b->dev.budget_mult = (uint32_t)optv(b->idx, O_epoch_budget_mult); b->dev.budget_add = (uint32_t)optv(b->idx, O_epoch_budget_add);
     b->dev.ovf_cap = (uint32_t)std::min<uint64_t>(b->cap_ovf_list / 4, 0xFFFFFFFFull);
     if (const int64_t forced = optv(b->idx, O_debug_ovf_cap)) b->dev.ovf_cap = (uint32_t)std::min<int64_t>(forced, (int64_t)b->dev.ovf_cap);   // (tests: a tiny list)
-    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
+    b->last_ovf_cap = b->dev.ovf_cap; b->ovf_state = 0; b->rec_ready = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->frag_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
     b->dev.pp_seg = (uint32_t)optv(b->idx, O_debug_pp_seg);
     b->dev.pp_max_len = (uint32_t)std::min<uint64_t>(b->max_read_len, 0xFFFFFFFFull);
     b->dev.pp_park = (uint32_t)optv(b->idx, O_pp_park);
@@ -1136,7 +1139,7 @@ int fin_batch_set_pairs(fin_batch* b, const int32_t* pairs, char* err, size_t er
     HIPCHK(hipSetDevice(b->device));
     if (b->last_stream) HIPCHK(hipStreamSynchronize(b->last_stream));
     HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
-    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;   // (the records of the last run say nothing about these pairs)
+    b->last_frec = false; b->last_text_only = false; b->count_from_text = false; b->sgm_ready = false; b->rsum_ready = false; b->scr_ready = false; b->frag_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;   // (the records of the last run say nothing about these pairs)
     return FIN_OK;
 }
 
@@ -1177,7 +1180,7 @@ int fin_batch_set_records(fin_batch* b, const fin_read_record* recs, const int32
     if (b->n_reads) HIPCHK(hipMemcpy(b->d_frec, recs, (size_t)b->n_reads * sizeof(FinFastRec), hipMemcpyHostToDevice));
     if (pairs && b->n_kmers) HIPCHK(hipMemcpy(b->d_out, pairs, (size_t)b->n_kmers * 8, hipMemcpyHostToDevice));
     // last_frec / last_text_only stay as the run left them (a text-only batch still refuses its pairs); whatever was made from the old records goes
-    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
+    b->count_from_text = false; b->text_bytes = 0; b->sgm_ready = false; b->n_segments = 0; b->rsum_ready = false; b->scr_ready = false; b->frag_ready = false; b->cls_ready = false; b->tax_ready = false; b->psa_ready = false; b->pair_ready = false; b->asg_ready = false; b->bin_ready = false;
     b->rec_ready = false; b->rec_passthrough = false; b->rec_stream_pairs = 0;
     return FIN_OK;
 }
@@ -3625,6 +3628,103 @@ int fin_pileup_call(fin_pileup* p, uint32_t min_alt, uint32_t min_permille, fin_
     return FIN_OK;
 }
 
+// ---- fragment geometry of paired reads (fin_fragments.hip) -------------------------------------------------------------------------------
+struct fin_fragments : fin_acc {
+    uint64_t n_unitigs = 0;
+    uint32_t n_bins = 0, bin_width = 0;
+    const uint32_t* d_ends = nullptr;     // the replica's ends_p
+    void* d_buf = nullptr;                // one allocation, zeroed by one memset: uint64 hist[n_bins], the seven counters (u64), the flag word
+};
+static_assert(sizeof(fin_fragment) == 16, "fin_fragment is one 16-byte store of the kernel");
+static uint64_t* fragments_counters(const fin_fragments* f) { return (uint64_t*)f->d_buf + f->n_bins; }
+static uint32_t* fragments_flags(const fin_fragments* f) { return (uint32_t*)((uint64_t*)f->d_buf + f->n_bins + 7); }
+static size_t fragments_bytes(const fin_fragments* f) { return ((size_t)f->n_bins + 8) * 8; }
+static int check_even_fragments(uint64_t n_reads, char* err, size_t errlen) {
+    if (n_reads & 1u) { set_err(err, errlen, "fragments want interleaved mates: " + std::to_string(n_reads) + " reads are an odd number"); return FIN_EINVAL; }
+    return FIN_OK;
+}
+
+void fin_fragments_free(fin_fragments* f) {
+    if (!acc_free_open(f)) return;
+    (void)hipFree(f->d_buf);
+    delete f;
+}
+
+int fin_fragments_create(const fin_index* idx, int device, uint32_t n_bins, uint32_t bin_width, fin_fragments** out, char* err, size_t errlen) {
+    if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (n_bins == 0 || n_bins > FIN_FRAG_MAX_BINS) { set_err(err, errlen, "n_bins is 1 .. " + std::to_string(FIN_FRAG_MAX_BINS)); return FIN_EINVAL; }
+    if (bin_width == 0) { set_err(err, errlen, "bin_width is at least 1"); return FIN_EINVAL; }
+    const fin_index::Replica* rep = nullptr;
+    if (const int orc = acc_create_open(idx, device, &rep, err, errlen)) return orc;
+    fin_fragments* f = acc_new<fin_fragments>(idx, device, err, errlen);
+    if (!f) return FIN_ENOMEM;
+    f->n_unitigs = idx->n_unitigs; f->n_bins = n_bins; f->bin_width = bin_width; f->d_ends = rep->dev.ends;
+    if (const int arc = acc_alloc_zero(f, &f->d_buf, fragments_bytes(f), fragments_bytes(f), "out of device memory (fragment histogram)", fin_fragments_free, err, errlen)) return arc;
+    *out = f;
+    return FIN_OK;
+}
+
+int fin_fragments_reset(fin_fragments* f, void* hip_stream) {
+    return acc_reset(f, hip_stream, f ? f->d_buf : nullptr, f ? fragments_bytes(f) : 0);
+}
+
+void* fin_fragments_device_hist(const fin_fragments* f) { return f ? f->d_buf : nullptr; }
+
+int fin_batch_add_fragments(fin_batch* b, fin_fragments* f, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !f) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int crc = check_even_fragments(b->n_reads, err, errlen)) return crc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (const int orc = acc_add_open(b, f, st, err, errlen)) return orc;
+    const int rc = fin_launch_fragments(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)(b->n_reads / 2), b->dev.k, f->d_ends,
+                                        (uint32_t)f->n_unitigs, f->n_bins, f->bin_width, nullptr, f->d_buf, fragments_counters(f), fragments_flags(f), b->d_ovf_count,
+                                        b->last_ovf_cap, st);
+    return acc_add_close(f, st, rc, "fragments kernel: ", err, errlen);
+}
+
+int fin_fragments_download(fin_fragments* f, uint64_t* hist_out, uint64_t counters_out[7], char* err, size_t errlen) {
+    if (!f) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(f, fragments_flags(f), PILEUP_WITHHELD, PILEUP_OUTSIDE, err, errlen)) return orc;
+    if (hist_out) HIPCHK(hipMemcpy(hist_out, f->d_buf, (size_t)f->n_bins * 8, hipMemcpyDeviceToHost));
+    if (counters_out) HIPCHK(hipMemcpy(counters_out, fragments_counters(f), 56, hipMemcpyDeviceToHost));
+    return FIN_OK;
+}
+
+// the batch's own fragments: fin_fragment[n_reads / 2] and, behind them, the flag word the kernel wants (nobody reads it: an outside mate is not placed)
+int fin_batch_fragments(fin_batch* b, uint64_t* n_frags, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (n_frags) *n_frags = 0;
+    if (!b->ran) { set_err(err, errlen, "this batch has not run: there are no fragments to make (fin_batch_run first)"); return FIN_EINVAL; }
+    if (const int crc = check_even_fragments(b->n_reads, err, errlen)) return crc;
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    b->frag_ready = false;
+    if (b->n_kmers != 0) if (const int orc = batch_overrun_check(b, st, err, errlen)) return orc;   // a run without results: nothing is written
+    const uint32_t nf = (uint32_t)(b->n_reads / 2);
+    if (batch_grow(b, &b->d_frag, b->cap_frag, (size_t)nf * 16 + 16, st)) { set_err(err, errlen, "out of device memory (fragments)"); return FIN_ENOMEM; }
+    uint32_t* const d_flags = (uint32_t*)((uint8_t*)b->d_frag + (size_t)nf * 16);
+    HIPCHK(hipMemsetAsync(d_flags, 0, 16, st));
+    const int rc = fin_launch_fragments(b->n_kmers != 0 && b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, nf, b->dev.k, b->dev.ends,
+                                        (uint32_t)b->idx->n_unitigs, 0, 0, b->d_frag, nullptr, nullptr, d_flags, nullptr, 0, st);
+    if (rc != 0) { set_err(err, errlen, std::string("fragments kernel: ") + hipGetErrorString((hipError_t)rc)); return FIN_ENODEV; }
+    b->frag_ready = true;
+    if (n_frags) *n_frags = nf;
+    return FIN_OK;
+}
+
+void* fin_batch_device_fragments(const fin_batch* b) { return b && b->frag_ready ? b->d_frag : nullptr; }
+
+int fin_batch_download_fragments(fin_batch* b, fin_fragment* out, char* err, size_t errlen) {
+    if (!b) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (!b->frag_ready) { set_err(err, errlen, "fin_batch_fragments first"); return FIN_EINVAL; }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = b->last_stream;
+    const size_t nf = (size_t)(b->n_reads / 2);
+    if (nf && out) HIPCHK(hipMemcpyAsync(out, b->d_frag, nf * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FIN_OK;
+}
+
 int fin_batch_step_time(const fin_batch* b, uint64_t skip_first, double ms_parts[5], uint64_t* n_runs) {
     if (!b) return FIN_EINVAL;
     double t[5] = {0, 0, 0, 0, 0}; uint64_t n = 0;
@@ -4294,6 +4394,31 @@ int fin_search_batch_add_pileup(const fin_index* idx, const char* bases, const u
     if (n_reads == 0) return FIN_OK;
     Product p;
     p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_pileup(b, pl, own(b), e, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
+}
+
+int fin_search_batch_add_fragments(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_fragments* f, char* err,
+                                   size_t errlen) {
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, f, f, OTHER_ACC, &device, err, errlen)) return orc;
+    if (const int crc = check_even_fragments(n_reads, err, errlen)) return crc;
+    if (n_reads == 0) return FIN_OK;
+    Product p; p.group = 2;   // (interleaved mates: no sub-batch splits a pair)
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_fragments(b, f, own(b), e, elen); };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
+}
+
+int fin_search_batch_fragments(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_fragment* frags_out, char* err,
+                               size_t errlen) {
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, n_reads < 2 || frags_out, nullptr, nullptr, &device, err, errlen)) return orc;
+    if (const int crc = check_even_fragments(n_reads, err, errlen)) return crc;
+    if (n_reads == 0) return FIN_OK;
+    Product p; p.group = 2;   // a sub-batch's fragments land at the fragments' numbers (every sub-batch begins at an even read)
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t&, char* e, size_t elen) -> int {
+        if (const int rc = fin_batch_fragments(b, nullptr, e, elen)) return rc;
+        return fin_batch_download_fragments(b, frags_out + s.lo / 2, e, elen);
+    };
     return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 

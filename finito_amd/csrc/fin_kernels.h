@@ -204,6 +204,12 @@ int fin_launch_pseudoalign(const void* frec, const uint64_t* out_offs, const voi
 // n_coloured of the first mate} under the threshold permille; mode 0: any mate, 1: the row is zero unless both mates have a coloured slot
 int fin_launch_pseudoalign_paired(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_frags, uint32_t k, const void* bits, uint32_t W,
                                   uint32_t n_unitigs, uint32_t permille, uint32_t mode, void* rows, void* heads, hipStream_t stream);
+// fin_fragments.hip -- the geometry of every FRAGMENT (reads 2f and 2f + 1 of the step): frags {u, start, length, cls} of 16 bytes each (may be
+// null), and hist uint64[n_bins] += the inward fragments by min(length / bin_width, n_bins - 1), counters 7 x u64 += {the six classes, the inward lengths' sum}
+// (both null: nothing is accumulated; n_bins <= 4096).  flags one u32, never null (bits as fin_launch_pileup_add); ends_p: the replica's unitig bounds
+int fin_launch_fragments(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_frags, uint32_t k, const uint32_t* ends_p, uint32_t n_unitigs,
+                         uint32_t n_bins, uint32_t bin_width, void* frags, void* hist, void* counters, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap,
+                         hipStream_t stream);
 // ... over a COMPACT matrix (fin_colorsets.hip's state): sets uint64[(n_sets + 1) * W] with row 0 empty, set_of uint32[n_unitigs], each <= n_sets.  A unitig number
 // becomes its set id as it is loaded, the register table is keyed by set id; the results are those of the dense launch over the expanded matrix, bit for bit
 int fin_launch_pseudoalign_sets(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const void* sets, uint32_t W, uint32_t n_sets,

@@ -593,6 +593,14 @@ static const char* SEARCH_HELP =
     "                        --pseudoalign over both mates' k-mers together (at P = 1000 the intersection of the mates' sets where both have coloured\n"
     "                        k-mers). Everything else is per read as before\n"
     "      --pair-both arg   1 (only with --paired 1): a fragment has colours only if BOTH mates have a coloured k-mer\n"
+    "      --fragments FILE  with --paired 1: the geometry of every fragment, made on the GPU. Lines fragment<TAB>class<TAB>unitig<TAB>start<TAB>length<TAB>dir1<TAB>dir2;\n"
+    "                        class 0 none, 1 one, 2 split, 3 tandem, 4 outward, 5 inward; dir F or R per placed mate; `-` where there is nothing to report\n"
+    "      --fragment-lengths FILE  with --paired 1: the insert-size histogram of the inward fragments, written after the last chunk: length<TAB>fragments per\n"
+    "                        non-zero bin (the last bin as >=X), the six class lines and mean<TAB>M. --fragment-bins B (1 .. 4096, default 1024) and\n"
+    "                        --fragment-bin-width D (default 1): bin(len) = min(len / D, B - 1)\n"
+    "      --ab-fragment-lengths arg  1 (with --paired 1, --abundance and --ab-lengths): the numbers of --ab-lengths are the references' lengths in bases; they\n"
+    "                        become effective lengths under the run's own fragment-length histogram (bin width 1) after the last chunk, before the EM, and are\n"
+    "                        written as a further column of the abundance file\n"
     "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify,\n"
     "                        --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance): do not make or write the pair\n"
     "                        text, the other results asked for are the only ones\n"
@@ -1158,6 +1166,33 @@ static EqClassesFile eqclasses_parse_file(const string& path, uint32_t n_colors)
     }
     return out;
 }
+// --fragments / --fragment-lengths / --ab-fragment-lengths (with --paired 1): the geometry of every fragment, made on the first device; --fragments' lines are written
+// by the search stage in chunk order, the histogram and the effective lengths after the last chunk (include/finito_amd.h: FRAGMENT GEOMETRY)
+static fin_fragments* g_frag = nullptr;
+static FILE* g_frag_file = nullptr;
+static uint64_t g_frag0 = 0;
+static vector<fin_fragment> g_frag_buf; static string g_frag_text;
+static void fragments_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
+    char err[512] = {0};
+    if (g_frag && fin_search_batch_add_fragments(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_frag, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    if (!g_frag_file) return;
+    const uint64_t nf = n_reads / 2;   // (the parser cuts chunks after an even number of records)
+    g_frag_buf.resize(nf + 1);
+    if (fin_search_batch_fragments(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_frag_buf.data(), err, sizeof err) != FIN_OK) throw runtime_error(err);
+    string& t = g_frag_text;
+    t.clear();
+    for (uint64_t f = 0; f < nf; f++) {
+        const fin_fragment& S = g_frag_buf[f];
+        t += to_string(g_frag0 + f); t += '\t'; t += to_string(S.cls & 0xFFu); t += '\t';
+        if (S.u == 0xFFFFFFFFu) t += "-\t-\t-";
+        else { t += to_string(S.u); t += '\t'; t += to_string(S.start); t += '\t'; t += to_string(S.length); }
+        t += '\t'; t += (S.cls >> 10) & 1u ? ((S.cls >> 8) & 1u ? 'R' : 'F') : '-';
+        t += '\t'; t += (S.cls >> 11) & 1u ? ((S.cls >> 9) & 1u ? 'R' : 'F') : '-';
+        t += '\n';
+    }
+    if (!t.empty() && fwrite(t.data(), 1, t.size(), g_frag_file) != t.size()) throw runtime_error("Error writing the fragments file");
+    g_frag0 += nf;
+}
 static void eqclasses_add_file(const EqClassesFile& f) {
     char err[512] = {0};
     if (fin_eqclasses_add_classes_host(g_eqc, f.rows.data(), f.reads.data(), f.reads.size(), f.unaligned, err, sizeof err) != FIN_OK)
@@ -1320,6 +1355,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_eqc) eqclasses_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_asg) assign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_frag || g_frag_file) fragments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                     }
                     else {
                         // the text comes from the GPU when it can (one device, every read has a k-mer), else the pairs do
@@ -1345,6 +1381,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_psa_file) pseudoalign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
                         if (g_eqc) eqclasses_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_asg) assign_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_frag || g_frag_file) fragments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                     }
                     if (g_strand_counts) {
                         c->positive_fwd = index.count_found_one_strand(c->bases.get(0), c->offsets.data(), n_reads);
@@ -1489,13 +1526,13 @@ static void write_color_similarity(const string& path, fin_cover* cov, size_t nc
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "depth-histogram", "depth-bins", "depth-bin-width", "color-depth-histogram", "color-depth-quantiles", "color-similarity", "color-similarity-covered", "compact-colors", "color-sets-out", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "depth-histogram", "depth-bins", "depth-bin-width", "color-depth-histogram", "color-depth-quantiles", "color-similarity", "color-similarity-covered", "compact-colors", "color-sets-out", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "fragments", "fragment-lengths", "fragment-bins", "fragment-bin-width", "ab-fragment-lengths", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
     if (o.has("color-similarity-covered") && !o.has("color-similarity")) throw runtime_error("--color-similarity-covered is only legal together with --color-similarity");
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity") && !o.has("taxa") && !o.has("taxon-report") && !o.has("depth-histogram") && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles"))
-        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report, --abundance, --depth-histogram, --color-depth-histogram or --color-depth-quantiles (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity") && !o.has("taxa") && !o.has("taxon-report") && !o.has("depth-histogram") && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles") && !o.has("fragments") && !o.has("fragment-lengths"))
+        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report, --abundance, --depth-histogram, --color-depth-histogram, --color-depth-quantiles, --fragments or --fragment-lengths (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
     if (o.has("color-coverage") && !o.has("color-refs")) throw runtime_error("--color-coverage wants colours: --color-refs LIST");
@@ -1527,6 +1564,18 @@ static int search_fmin(int argc, char** argv) {
     if (g_paired && !o.has("color-refs")) throw runtime_error("--paired 1 wants colours: --color-refs LIST (fragments are what --pseudoalign, --eqclasses, --color-report and --abundance then take)");
     if (pair_both && !g_paired) throw runtime_error("--pair-both 1 is only legal together with --paired 1");
     g_pair_mode = pair_both ? FIN_PAIR_BOTH : FIN_PAIR_ANY;
+    // --fragments, --fragment-lengths, --ab-fragment-lengths: all three want --paired 1; the bins as --depth-bins; everything is refused before the index is loaded
+    const bool ab_frag = o.has("ab-fragment-lengths") && o.get("ab-fragment-lengths") != "0" && o.get("ab-fragment-lengths") != "false";
+    const bool frag_asked = o.has("fragments") || o.has("fragment-lengths") || ab_frag;
+    for (const char* name : {"fragments", "fragment-lengths"})
+        if (o.has(name) && !g_paired) throw runtime_error(string("--") + name + " wants interleaved mates: --paired 1");
+    if (ab_frag && !g_paired) throw runtime_error("--ab-fragment-lengths 1 wants interleaved mates: --paired 1");
+    if (ab_frag && !(o.has("abundance") && o.has("ab-lengths"))) throw runtime_error("--ab-fragment-lengths 1 wants --abundance FILE and --ab-lengths FILE (the references' lengths in bases)");
+    if (ab_frag && o.has("ab-bootstraps")) throw runtime_error("--ab-fragment-lengths 1 is not available with --ab-bootstraps");
+    for (const char* name : {"fragment-bins", "fragment-bin-width"})
+        if (o.has(name) && !o.has("fragment-lengths") && !ab_frag) throw runtime_error(string("--") + name + " is only legal together with --fragment-lengths or --ab-fragment-lengths 1");
+    const uint32_t frag_bins = dh_number("fragment-bins", 1024, FIN_FRAG_MAX_BINS), frag_width = dh_number("fragment-bin-width", 1, 0xFFFFFFFFull);
+    if (ab_frag && frag_width != 1) throw runtime_error("--ab-fragment-lengths 1 wants --fragment-bin-width 1: effective lengths are read from a histogram of single lengths");
     const bool eq_asked = o.has("eqclasses") || o.has("color-report") || o.has("abundance");
     const bool asg_asked = o.has("assign-weights");
     const bool tax_asked = o.has("taxa") || o.has("taxon-report");
@@ -1538,7 +1587,7 @@ static int search_fmin(int argc, char** argv) {
     if (asg_asked && !o.has("assign") && !o.has("assign-report")) throw runtime_error("--assign-weights wants a result: --assign FILE and / or --assign-report FILE");
     for (const char* name : {"assign", "assign-report", "assign-threshold"})
         if (o.has(name) && !asg_asked) throw runtime_error(string("--") + name + " is only legal together with --assign-weights");
-    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked && !o.has("color-coverage") && !o.has("color-similarity") && !tax_asked && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles")) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report, --abundance, --color-depth-histogram or --color-depth-quantiles");
+    if (o.has("color-refs") && !o.has("pseudoalign") && !o.has("colors-out") && !eq_asked && !asg_asked && !o.has("color-coverage") && !o.has("color-similarity") && !tax_asked && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles") && !frag_asked) throw runtime_error("--color-refs is only legal together with --pseudoalign, --colors-out, --eqclasses, --color-report, --abundance, --color-depth-histogram or --color-depth-quantiles");
     if (o.has("pseudo-permille") && !o.has("pseudoalign") && !eq_asked && !asg_asked) throw runtime_error("--pseudo-permille is only legal together with --pseudoalign, --eqclasses, --color-report or --abundance");
     if (o.has("eq-max-classes") && !eq_asked) throw runtime_error("--eq-max-classes is only legal together with --eqclasses, --color-report or --abundance");
     if (o.has("eqclasses-in") && !eq_asked) throw runtime_error("--eqclasses-in is only legal together with --eqclasses, --color-report or --abundance");
@@ -1690,6 +1739,8 @@ static int search_fmin(int argc, char** argv) {
             string v = lines[c];
             if (!v.empty() && v.back() == '\r') v.pop_back();
             if (!positive_number(v, false, ab_lengths[c])) throw runtime_error("--ab-lengths: line " + to_string(c + 1) + " (colour " + to_string(c) + ") is not a finite positive number");
+            if (ab_frag && !(ab_lengths[c] >= 1.0 && ab_lengths[c] <= 9007199254740992.0 && ab_lengths[c] == std::floor(ab_lengths[c])))
+                throw runtime_error("--ab-fragment-lengths 1: --ab-lengths line " + to_string(c + 1) + " (colour " + to_string(c) + ") is not a length in bases, a whole number from 1");
         }
     }
     // --assign-weights: the weights and thresholds, read before the index is loaded; a wrong colour count is an error before any search
@@ -1711,6 +1762,9 @@ static int search_fmin(int argc, char** argv) {
         if (!asg_report.empty()) check_writable(asg_report);
     }
     if (!ab_file.empty()) check_writable(ab_file);
+    const string frag_file = o.get("fragments", ""), fraglen_file = o.get("fragment-lengths", "");
+    if (!frag_file.empty()) check_writable(frag_file);
+    if (!fraglen_file.empty()) check_writable(fraglen_file);
     if (!eqc_file.empty()) check_writable(eqc_file);
     if (!crep_file.empty()) check_writable(crep_file);
     if (!colors_file.empty()) check_writable(colors_file);
@@ -1762,7 +1816,17 @@ static int search_fmin(int argc, char** argv) {
     if (dh_asked && index.partitioned()) throw runtime_error("--depth-histogram, --color-depth-histogram and --color-depth-quantiles are not available with a partitioned index");
     if (!colcov_file.empty() && index.partitioned()) throw runtime_error("--color-coverage is not available with a partitioned index");
     if (!color_refs.empty() && index.partitioned()) throw runtime_error("--color-refs is not available with a partitioned index");
+    if (frag_asked && index.partitioned()) throw runtime_error("--fragments, --fragment-lengths and --ab-fragment-lengths are not available with a partitioned index");
     index.to_device();
+    struct FragOwner { ~FragOwner() { if (g_frag_file) fclose(g_frag_file); g_frag_file = nullptr; fin_fragments_free(g_frag); g_frag = nullptr; } } frag_owner;
+    if (!fraglen_file.empty() || ab_frag) {
+        char err[512] = {0};
+        if (fin_fragments_create(index.handle(), first_dev, frag_bins, frag_width, &g_frag, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    }
+    if (!frag_file.empty()) {
+        g_frag_file = fopen(frag_file.c_str(), "wb");
+        if (!g_frag_file) throw runtime_error("Error writing to file: " + frag_file);
+    }
     struct HitsOwner { ~HitsOwner() { fin_hits_free(g_hits); g_hits = nullptr; } } hits_owner;
     if (!counts_file.empty() || (g_no_text && seg_file.empty() && rs_file.empty())) {   // (with --segments the found k-mers are the sum of the segments' lengths, with --read-summary the sum of `found`)
         char err[512] = {0};
@@ -1945,6 +2009,39 @@ static int search_fmin(int argc, char** argv) {
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + asg_report);
     }
+    if (g_frag_file) {
+        const bool bad = fflush(g_frag_file) != 0 || ferror(g_frag_file);
+        fclose(g_frag_file); g_frag_file = nullptr;
+        if (bad) throw runtime_error("Error writing to file: " + frag_file);
+    }
+    if (g_frag) {   // the run's fragment-length histogram: --fragment-lengths' file, and --ab-lengths' lengths in bases made effective lengths before the EM
+        char err[512] = {0};
+        vector<uint64_t> hist(frag_bins);
+        uint64_t cnt[7] = {0, 0, 0, 0, 0, 0, 0};
+        if (fin_fragments_download(g_frag, hist.data(), cnt, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        if (!fraglen_file.empty()) {
+            string text;
+            for (uint32_t b = 0; b < frag_bins; b++) {
+                if (!hist[b]) continue;
+                if (b == frag_bins - 1) text += ">=";
+                text += to_string((uint64_t)b * frag_width); text += '\t'; text += to_string(hist[b]); text += '\n';
+            }
+            static const char* const names[6] = {"none", "one", "split", "tandem", "outward", "inward"};
+            for (int c = 0; c < 6; c++) { text += names[c]; text += '\t'; text += to_string(cnt[c]); text += '\n'; }
+            char num[64];
+            if (cnt[FIN_FRAG_INWARD]) snprintf(num, sizeof num, "mean\t%.10g\n", (double)cnt[FIN_FRAG_LEN_SUM] / (double)cnt[FIN_FRAG_INWARD]);
+            else snprintf(num, sizeof num, "mean\t-\n");
+            text += num;
+            ofstream cf(fraglen_file, ios::binary | ios::trunc);
+            cf.write(text.data(), (streamsize)text.size());
+            if (!cf) throw runtime_error("Error writing to file: " + fraglen_file);
+        }
+        if (ab_frag) {
+            vector<uint64_t> ref(ab_lengths.size());
+            for (size_t c = 0; c < ref.size(); c++) ref[c] = (uint64_t)ab_lengths[c];
+            if (fin_effective_lengths(hist.data(), frag_bins, frag_width, ref.data(), ref.size(), ab_lengths.data()) != FIN_OK) throw runtime_error("--ab-fragment-lengths 1: fin_effective_lengths refused the histogram");
+        }
+    }
     if (g_eqc && !ab_file.empty()) {   // the abundances, estimated on the device from the run's classes: the rows stay there
         char err[512] = {0};
         const uint32_t nc = fin_colors_n_colors(g_colors);
@@ -1978,6 +2075,7 @@ static int search_fmin(int argc, char** argv) {
         for (uint32_t c = 0; c < nc; c++) {
             const double share = per_len_sum > 0.0 ? alpha[c] / (ab_lengths.empty() ? 1.0 : ab_lengths[c]) / per_len_sum : 0.0;
             if (ab_bootstraps) snprintf(num, sizeof num, "%u\t%.10g\t%.10g\t%.10g\t%.10g\n", c, alpha[c], share, boot_mean[c], boot_sd[c]);
+            else if (ab_frag) snprintf(num, sizeof num, "%u\t%.10g\t%.10g\t%.10g\n", c, alpha[c], share, ab_lengths[c]);   // (the effective lengths used)
             else snprintf(num, sizeof num, "%u\t%.10g\t%.10g\n", c, alpha[c], share);
             text += num;
         }

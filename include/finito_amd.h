@@ -1022,7 +1022,8 @@ int fin_eqclasses_color_tally(const uint64_t* class_rows, const uint64_t* class_
  * mode FIN_PAIR_ANY: as above.  FIN_PAIR_BOTH: the row is all zero and n_colors = 0 unless BOTH mates have at least one coloured slot; the three counts are reported
  * either way.  Any other mode is FIN_EINVAL.
  * A fragment's row is a row like any other: fin_eqclasses_add_rows, the classes and fin_eqclasses_abundance take it as it stands, a fragment counting as one "read".
- * Out of scope: a second query file read in lockstep, orientation or insert-size filters, partitioned indexes, fin_search_batch_multi / dist.py, the C++ mirror. */
+ * Out of scope: a second query file read in lockstep, an orientation or insert-size FILTER on the rows (FRAGMENT GEOMETRY, below, gives every fragment's class and
+ * length: the filter is a host-side mask), partitioned indexes, fin_search_batch_multi / dist.py, the C++ mirror. */
 #define FIN_PAIR_ANY 0u
 #define FIN_PAIR_BOTH 1u
 typedef struct fin_pair_pseudo { uint32_t n_found, n_colored, n_colors, n_colored_first; } fin_pair_pseudo;   /* 16 bytes; n_colored_first = the first mate's share of n_colored */
@@ -1049,6 +1050,89 @@ int fin_search_batch_add_eqclasses_paired(const fin_index* idx, const char* base
  * heads_out[F], F = n_reads / 2.  fin_records_pseudoalign's error codes, and FIN_EINVAL for an odd n_reads or a mode that is neither */
 int fin_records_pseudoalign_paired(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const uint64_t* bits,
                                    uint64_t n_unitigs, uint32_t n_colors, uint32_t permille, uint32_t mode, uint64_t* rows_out, fin_pair_pseudo* heads_out, int n_threads);
+
+/* ---- FRAGMENT GEOMETRY of paired reads: insert sizes and classes, made on the device ----
+ * The pooled rows above forget where a fragment's mates lie.  This section says it: per fragment, which way the mates face and how long the fragment is; over a run,
+ * the insert-size histogram, the share of proper pairs and -- from the histogram -- the effective length of each reference.  THE definition, stated here once;
+ * fin_fragments.hip, fin_fragments_host.cpp, the Python layer, the CLI and DESIGN.md point here.  All arithmetic is in integers and exact.
+ *  A MATE IS PLACED iff it meets the pileup's rules 1 and 2 (PILEUP, above) word for word; no mismatch rule takes part and no bases are read:
+ *   - it is STRAIGHT: at least two found slots, all in one unitig u, on one diagonal;
+ *   - strand A lies at offsets [s0, s0 + L) of u, all inside u, L = nk + k - 1; forward: s0 = dF; reverse: s0 = dR - nk + 1; a kind-1 record: s0 = off0 and meta
+ *     bit 8 gives the direction.
+ *   A kind-2 read, a read shorter than k, nk = 1, a mosaic, an indel and a read that hangs over an end of its unitig are not placed.
+ *  CLASSES.  Fragment f is reads 2f (first mate) and 2f + 1 (second mate); the class numbers are the counters' order:
+ *   0 FIN_FRAG_NONE     neither mate is placed
+ *   1 FIN_FRAG_ONE      exactly one mate is placed
+ *   2 FIN_FRAG_SPLIT    both are placed, in different unitigs
+ *   3 FIN_FRAG_TANDEM   same unitig, same direction
+ *   4 FIN_FRAG_OUTWARD  same unitig, opposite directions, not inward
+ *   5 FIN_FRAG_INWARD   same unitig, and the forward mate F and the reverse mate R satisfy s0(F) <= s0(R) and s0(F) + L(F) <= s0(R) + L(R)
+ *   The inward rule is invariant under swapping the mates (it names them by direction, not by number) and under storing the unitig the other way round (then F and R
+ *   change roles and every offset x becomes len(u) - x: the two conditions change places).  An inward fragment's LENGTH is s0(R) + L(R) - s0(F).  Only inward
+ *   fragments enter the histogram and len_sum.
+ *  PER FRAGMENT, fin_fragment {u, start, length, cls}, 16 bytes: cls & 0xFF is the class; bit 8 / bit 9: the first / second mate is placed and reverse; bit 10 / bit
+ *   11: the first / second mate is placed.  Classes 3 to 5: u, start = the smaller s0, length = the larger end minus start.  Class 1: the placed mate's u, s0, L.
+ *   Classes 0 and 2: u = 0xFFFFFFFF, start = length = 0.
+ *  THE ACCUMULATOR, fin_fragments, lives in HBM beside one replica: uint64 hist[n_bins] with bin(len) = min(len / bin_width, n_bins - 1), 1 <= n_bins <=
+ *   FIN_FRAG_MAX_BINS and bin_width >= 1, both fixed at creation; uint64 counters[7]: the six classes and len_sum; and the flag word of the siblings -- bit 0: a
+ *   withheld step was offered, and nothing of it is added; bit 1: a slot or record outside the index, that mate counts as not placed.  Adding the same run twice
+ *   doubles everything.
+ *  EFFECTIVE LENGTHS, fin_effective_lengths, a host function: see there.
+ * Out of scope: a proper-pair FILTER inside the pseudoalignment kernel (the per-fragment classes make it a host-side mask over the fragments' rows), fragments that
+ * bridge unitigs, strand-specific library types, partitioned indexes, fin_search_batch_multi / dist.py (add the downloaded histograms), the C++ mirror, a second
+ * query file read in lockstep. */
+#define FIN_FRAG_NONE 0u
+#define FIN_FRAG_ONE 1u
+#define FIN_FRAG_SPLIT 2u
+#define FIN_FRAG_TANDEM 3u
+#define FIN_FRAG_OUTWARD 4u
+#define FIN_FRAG_INWARD 5u
+#define FIN_FRAG_LEN_SUM 6      /* counters[6] */
+#define FIN_FRAG_MAX_BINS 4096u
+typedef struct fin_fragment { uint32_t u, start, length, cls; } fin_fragment;   /* 16 bytes */
+typedef struct fin_fragments fin_fragments;
+/* a zeroed accumulator for `idx` on `device`.  FIN_EINVAL: n_bins outside 1 .. FIN_FRAG_MAX_BINS or bin_width 0; FIN_ENODEV: the index has no replica there */
+int fin_fragments_create(const fin_index* idx, int device, uint32_t n_bins, uint32_t bin_width, fin_fragments** out, char* err, size_t errlen);
+/* zeroes histogram, counters and flags, on the given stream; does not wait; ordered against the adds as fin_hits_reset is */
+int fin_fragments_reset(fin_fragments* f, void* hip_stream);
+/* accumulator += the fragments of the batch's most recent run: one launch on the given stream (fin_fragments.hip), ordered behind that run; does not wait.
+ * fin_batch_add_pileup's ordering and refusal rules: FIN_EINVAL when the batch has not run or batch and accumulator belong to different indexes or devices, and for an
+ * odd n_reads; records and pairs are read only; a run whose overflow list overran adds nothing and fin_fragments_download reports FIN_ELIMIT until the reset; a slot
+ * or a record outside the index makes its mate not placed and the download reports FIN_EINVAL "outside the index" until the reset. */
+int fin_batch_add_fragments(fin_batch* b, fin_fragments* f, void* hip_stream, char* err, size_t errlen);
+/* waits for every add and reset issued so far.  hist_out[n_bins] and counters_out[7]; each may be NULL.  The accumulator is not changed. */
+int fin_fragments_download(fin_fragments* f, uint64_t* hist_out, uint64_t counters_out[7], char* err, size_t errlen);
+/* uint64[n_bins], then the seven counters, in HBM (valid once the adds on their streams have finished) */
+void* fin_fragments_device_hist(const fin_fragments* f);
+void fin_fragments_free(fin_fragments* f);
+/* the most recent run's fragments, one fin_fragment each, made on the device: fin_batch_pseudoalign_paired's ordering -- behind the run, on the run's stream, the
+ * overrun check first (FIN_ELIMIT: no result) -- into a buffer OF ITS OWN, which the batch keeps and only grows and forgets wherever it forgets its read summaries
+ * (a new run, a reload, fin_batch_set_pairs, fin_batch_set_records).  *n_frags (may be NULL) = n_reads / 2; 0 is legal.  FIN_EINVAL: an odd n_reads or the batch
+ * has not run.  A mate with a slot or a record outside the index is not placed, which bits 10 and 11 of its fragment say; nothing else reports it here. */
+int fin_batch_fragments(fin_batch* b, uint64_t* n_frags, char* err, size_t errlen);
+int fin_batch_download_fragments(fin_batch* b, fin_fragment* out, char* err, size_t errlen);
+void* fin_batch_device_fragments(const fin_batch* b);   /* fin_fragment[n_reads / 2] in HBM; NULL before fin_batch_fragments */
+/* host buffers in, interleaved mates: fin_search_batch_add_eqclasses_paired's loop -- sub-batches end only after an even number of reads, so no pair is split, each
+ * run in text mode 2 where the fast path is on -- with the accumulator as its product, nothing downloaded.  An odd n_reads is FIN_EINVAL before anything runs. */
+int fin_search_batch_add_fragments(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_fragments* f, char* err,
+                                   size_t errlen);
+/* ... with the fragments themselves as its product: frags_out[n_reads / 2], landing at the fragments' numbers */
+int fin_search_batch_fragments(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_fragment* frags_out, char* err,
+                               size_t errlen);
+/* host, no device: the definition above from records + stream of interleaved mates, read off every read's expanded slots whichever kind its record is -- the CPU
+ * statement of the definition, not of the kernel's shortcut.  unitig_ends[n_unitigs] as FIN_X_ENDS.  frags_out[n_reads / 2], hist_out[n_bins] and counters_out[7]
+ * are overwritten; each may be NULL (n_bins and bin_width are looked at only with hist_out).  n_threads <= 0: all cores.  FIN_EINVAL: what fin_records_pileup refuses
+ * (a unitig number >= n_unitigs, a k-mer that does not lie inside its unitig, a stream that is not this record set's, a kind above 2), an odd n_reads, n_bins
+ * outside 1 .. FIN_FRAG_MAX_BINS or bin_width 0 */
+int fin_records_fragments(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
+                          uint64_t n_unitigs, uint32_t n_bins, uint32_t bin_width, fin_fragment* frags_out, uint64_t* hist_out, uint64_t counters_out[7],
+                          int n_threads);
+/* host, no device part: out[i] = the effective length of a reference of ref_len[i] bases under the fragment-length histogram hist[n_bins] (bin_width must be 1:
+ * FIN_EINVAL otherwise, as for n_bins outside 1 .. FIN_FRAG_MAX_BINS).  The last bin means "this much or more" and is excluded.  With S0(l) and S1(l) the prefix sums
+ * of hist[j] and j * hist[j] over j <= l in uint64, and m = min(ref_len, n_bins - 2):
+ *   out = (double)ref_len + 1.0 - (double)S1(m) / (double)S0(m)      -- kallisto's length minus the truncated mean plus one;
+ * if S0(m) == 0 (n_bins == 1 among it) or that value is below 1, out = (double)ref_len.  One division per reference: reproducible bit for bit. */
+int fin_effective_lengths(const uint64_t* hist, uint32_t n_bins, uint32_t bin_width, const uint64_t* ref_len, uint64_t n, double* out);
 
 /* ---- ABUNDANCES from the equivalence classes: EM on the device ----
  * The step every consumer of such classes runs next (kallisto's EM, mSWEEP's behind Themisto): split each class's reads over its colours in proportion to the
