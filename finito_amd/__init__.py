@@ -324,6 +324,26 @@ def lib():
         L.fin_search_batch_add_fragments.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
         L.fin_search_batch_fragments.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
         L.fin_records_fragments.argtypes = [vp, u64, vp, u64, C.c_int, i64p, u64, u32, u32, vp, vp, vp, C.c_int]
+        L.fin_refpaths_create.argtypes = [vp, C.c_int, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_refpaths_reset.argtypes = [vp, vp]
+        L.fin_refpaths_free.argtypes = [vp]
+        L.fin_refpaths_free.restype = None
+        for f in ("n_seqs", "n_segments", "n_slots"):
+            getattr(L, "fin_refpaths_" + f).argtypes = [vp]
+            getattr(L, "fin_refpaths_" + f).restype = u64
+        L.fin_refpaths_download.argtypes = [vp, vp, vp, vp, cp, C.c_size_t]
+        L.fin_refpaths_upload.argtypes = [vp, vp, vp, vp, u64, cp, C.c_size_t]
+        L.fin_refpaths_device_segments.argtypes = [vp]
+        L.fin_refpaths_device_segments.restype = vp
+        L.fin_refpaths_device_segment_offsets.argtypes = [vp]
+        L.fin_refpaths_device_segment_offsets.restype = vp
+        L.fin_batch_add_refpaths.argtypes = [vp, vp, vp, cp, C.c_size_t]
+        L.fin_search_batch_add_refpaths.argtypes = [vp, cp, u64p, u64, vp, cp, C.c_size_t]
+        L.fin_refpaths_depth.argtypes = [vp, vp, u32, u32, vp, vp, u64, u64p, cp, C.c_size_t]
+        L.fin_refpaths_lift_variants.argtypes = [vp, vp, u64, vp, u64, u64p, cp, C.c_size_t]
+        L.fin_segments_check.argtypes = [vp, vp, vp, u64, C.c_int, i64p, u64, cp, C.c_size_t]
+        L.fin_segments_window_depth.argtypes = [vp, vp, vp, u64, C.c_int, i64p, u64, vp, u32, u32, vp, vp, u64, u64p, C.c_int, cp, C.c_size_t]
+        L.fin_segments_lift_variants.argtypes = [vp, vp, vp, u64, C.c_int, i64p, u64, vp, u64, vp, u64, u64p, C.c_int, cp, C.c_size_t]
         L.fin_effective_lengths.argtypes = [vp, u32, u32, vp, u64, vp]
         L.fin_eqclasses_create.argtypes = [vp, u64, C.POINTER(vp), cp, C.c_size_t]
         L.fin_eqclasses_reset.argtypes = [vp, vp]
@@ -1854,6 +1874,138 @@ class Fragments(_Accumulator):
         return int(self.L.fin_fragments_device_hist(self.h) or 0)
 
 
+def _window_args(what, window, min_depth):
+    w, md = int(window), int(min_depth)
+    if not 1 <= w <= 0xFFFFFFFF:
+        raise FinitoError(FIN_EINVAL, "%s: window is 1 .. 2^32 - 1" % what)
+    if not 0 <= md <= 0xFFFFFFFF:
+        raise FinitoError(FIN_EINVAL, "%s: min_depth is an unsigned 32-bit number" % what)
+    return w, md
+
+
+def _path_set(what, seq_nk, seg_offs, segs):
+    nk = np.ascontiguousarray(seq_nk, dtype=np.uint32).reshape(-1)
+    so = np.ascontiguousarray(seg_offs, dtype=np.uint64).reshape(-1)
+    sg = np.ascontiguousarray(segs, dtype=SEGMENT_DTYPE).reshape(-1)
+    if len(so) != len(nk) + 1 or int(so[-1]) > len(sg):
+        raise FinitoError(FIN_EINVAL, "%s: seg_offs has one entry more than seq_nk and its last entry is the number of segments" % what)
+    return nk, so, sg
+
+
+class RefDepth:
+    """what depth_windows returns: win_offs uint64[n_seqs + 1] and windows REF_WINDOW_DTYPE[n_windows] -- sequence s owns windows win_offs[s] .. win_offs[s + 1] - 1,
+    window w of it the slots [w * window, (w + 1) * window); mean_depth = depth_sum / in_graph and breadth = covered / in_graph per window, float64, nan where
+    no slot of the window lies in the graph"""
+
+    def __init__(self, win_offs, windows, window, min_depth):
+        self.win_offs, self.windows, self.window, self.min_depth = win_offs, windows, int(window), int(min_depth)
+
+    def of(self, seq):
+        """the windows of sequence `seq`"""
+        return self.windows[int(self.win_offs[seq]):int(self.win_offs[seq + 1])]
+
+    @staticmethod
+    def _ratio(num, den):
+        out = np.full(len(den), np.nan, dtype=np.float64)
+        np.divide(num.astype(np.float64), den.astype(np.float64), out=out, where=den != 0)
+        return out
+
+    @property
+    def mean_depth(self):
+        return self._ratio(self.windows["depth_sum"], self.windows["in_graph"])
+
+    @property
+    def breadth(self):
+        return self._ratio(self.windows["covered"], self.windows["in_graph"])
+
+
+class RefPaths(_Accumulator):
+    """the paths of sequences -- reference records searched as reads -- through the unitig set, as segments in HBM beside one replica of the index (fin_refpaths_* of
+    the C ABI; include/finito_amd.h: REFERENCE COORDINATES): what lifts depth and variant candidates from unitig coordinates onto the sequences"""
+    _FREE, _RESET = "fin_refpaths_free", "fin_refpaths_reset"
+
+    def __init__(self, index, device=0):
+        self.index = index
+        self._create("fin_refpaths_create", index.h, int(device))
+
+    def add(self, batch, stream=None):
+        """append the reads of the batch's most recent run as sequences, device to device on a HIP stream behind that run (fin_batch_add_refpaths)"""
+        return _acc_add(self, "fin_batch_add_refpaths", batch, stream)
+
+    def add_reads(self, seqs):
+        """search sequences from host buffers, sub-batches pipelined and cut between sequences only, and append their paths (fin_search_batch_add_refpaths)"""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_search_batch_add_refpaths(self.index.h, *_reads_args(seqs), self.h, err, 512), err)
+        return self
+
+    @property
+    def n_seqs(self): return int(self.L.fin_refpaths_n_seqs(self.h))
+    @property
+    def n_segments(self): return int(self.L.fin_refpaths_n_segments(self.h))
+    @property
+    def n_slots(self): return int(self.L.fin_refpaths_n_slots(self.h))
+
+    def upload(self, seq_nk, seg_offs, segs):
+        """replace the path set by host arrays; FinitoError FIN_EINVAL names the first segment that is not valid against the index (fin_refpaths_upload)"""
+        nk, so, sg = _path_set("RefPaths.upload", seq_nk, seg_offs, segs)
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_refpaths_upload(self.h, nk.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), sg.ctypes.data_as(C.c_void_p), len(nk), err, 512), err)
+        return self
+
+    def download(self):
+        """(seq_nk uint32[n_seqs], seg_offs uint64[n_seqs + 1], segs SEGMENT_DTYPE[n_segments]); waits for the appends (fin_refpaths_download)"""
+        err = C.create_string_buffer(512)
+        _check(self.L.fin_refpaths_download(self.h, None, None, None, err, 512), err)
+        ns, ng = self.n_seqs, self.n_segments
+        nk = np.zeros(max(ns, 1), dtype=np.uint32); so = np.zeros(ns + 1, dtype=np.uint64); sg = np.zeros(max(ng, 1), dtype=SEGMENT_DTYPE)
+        _check(self.L.fin_refpaths_download(self.h, nk.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), sg.ctypes.data_as(C.c_void_p), err, 512), err)
+        return nk[:ns], so, sg[:ng]
+
+    def depth_windows(self, depth, window=1000, min_depth=1):
+        """RefDepth: a Depth accumulator lifted onto the sequences in windows of `window` slots, on the device; only the windows come back (fin_refpaths_depth)"""
+        w, md = _window_args("RefPaths.depth_windows", window, min_depth)
+        err = C.create_string_buffer(512)
+        n = C.c_uint64(0)
+        rc = self.L.fin_refpaths_depth(self.h, depth.h, w, md, None, None, 0, C.byref(n), err, 512)
+        if rc != FIN_ELIMIT:
+            _check(rc, err)
+        wo = np.zeros(self.n_seqs + 1, dtype=np.uint64)
+        out = np.zeros(max(int(n.value), 1), dtype=REF_WINDOW_DTYPE)
+        _check(self.L.fin_refpaths_depth(self.h, depth.h, w, md, wo.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), int(n.value), C.byref(n), err, 512), err)
+        return RefDepth(wo, out[: int(n.value)], w, md)
+
+    def lift_variants(self, variants):
+        """REF_VARIANT_DTYPE[n]: Pileup.call's candidates under every sequence that crosses them -- seq, pos (the sequence base, 0-based), var (the index into
+        `variants`), flags (bit 0: the sequence runs against the text there, bases are to be complemented); by segment, then by pos (fin_refpaths_lift_variants)"""
+        v = np.ascontiguousarray(variants, dtype=VARIANT_DTYPE).reshape(-1)
+        err = C.create_string_buffer(512)
+        n = C.c_uint64(0)
+        room = max(1024, 4 * len(v))   # (a candidate usually lies under a few sequences: one call; beyond that the refusal says how many there are)
+        while True:
+            out = np.zeros(room, dtype=REF_VARIANT_DTYPE)
+            rc = self.L.fin_refpaths_lift_variants(self.h, v.ctypes.data_as(C.c_void_p), len(v), out.ctypes.data_as(C.c_void_p), room, C.byref(n), err, 512)
+            if rc == FIN_ELIMIT and int(n.value) > room:
+                room = int(n.value)
+                continue
+            _check(rc, err)
+            return out[: int(n.value)]
+
+    def device_ptrs(self):
+        """(segments, seg_offs) in HBM"""
+        return int(self.L.fin_refpaths_device_segments(self.h) or 0), int(self.L.fin_refpaths_device_segment_offsets(self.h) or 0)
+
+
+def ref_variant_bases(lifted, variants):
+    """(ref uint32[n], alt uint32[n, 4]) of lifted records in the SEQUENCE's orientation: the text's base code and the four alt counts (A, C, G, T) of
+    variants[lifted["var"]], complemented -- code b becomes 3 - b -- where bit 0 of flags is set"""
+    v = np.ascontiguousarray(variants, dtype=VARIANT_DTYPE).reshape(-1)
+    l = np.ascontiguousarray(lifted, dtype=REF_VARIANT_DTYPE).reshape(-1)
+    rev = (l["flags"] & 1) != 0
+    ref = v["ref"][l["var"]].astype(np.uint32)
+    alt = v["alt"][l["var"]].reshape(-1, 4).astype(np.uint32)
+    return np.where(rev, 3 - ref, ref).astype(np.uint32), np.where(rev[:, None], alt[:, ::-1], alt)
+
+
 class FinimizerIndex:
     """Mirror of the reference class (FinimizerIndex.hh:26-259) backed by the HIP path."""
 
@@ -2239,6 +2391,10 @@ class FinimizerIndex:
         """a zeroed fragment-length histogram with its class counters beside the replica on `device` (Fragments)"""
         return Fragments(self, device, n_bins, bin_width)
 
+    def ref_paths(self, device=0):
+        """an empty path set beside the replica on `device` (RefPaths)"""
+        return RefPaths(self, device)
+
     def fragments_reads(self, reads, strands=FIN_MERGED):
         """FRAGMENT_DTYPE[F]: interleaved mates from host buffers as fragments, sub-batches pipelined and cut between pairs only (fin_search_batch_fragments)"""
         bases, offsets = flatten(reads)
@@ -2383,6 +2539,8 @@ FIN_NO_COLOR = 0xFFFFFFFF
 DEPTH_STAT_DTYPE = np.dtype([("sum", np.uint64), ("max", np.uint32), ("n_at_least", np.uint32)])            # fin_depth_stat
 COLOR_COVERAGE_DTYPE = np.dtype([(f, np.uint64) for f in ColorCoverage.FIELDS])   # fin_color_coverage
 VARIANT_DTYPE = np.dtype([("u", np.uint32), ("off", np.uint32), ("cover", np.uint32), ("ref", np.uint32), ("alt", np.uint32, (4,))])   # fin_variant
+REF_WINDOW_DTYPE = np.dtype([("depth_sum", np.uint64), ("in_graph", np.uint32), ("covered", np.uint32)])   # fin_ref_window
+REF_VARIANT_DTYPE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("var", np.uint32), ("flags", np.uint32)])   # fin_ref_variant
 
 
 class PartitionedBatch:
@@ -2818,6 +2976,64 @@ def records_fragments(recs, stream, k, ends, n_bins=1024, bin_width=1, n_threads
         raise FinitoError(rc, "fin_records_fragments: an odd number of reads, n_bins outside 1 .. %d, bin_width 0, a unitig number outside the index, a k-mer that does "
                               "not lie inside its unitig, or records and stream that do not belong together" % FIN_FRAG_MAX_BINS)
     return frags[:nf], hist, counters
+
+
+def _twin_ends(ends):
+    e = np.ascontiguousarray(ends, dtype=np.int64).reshape(-1)
+    return e, e.ctypes.data_as(C.POINTER(C.c_int64)), len(e)
+
+
+def segments_check(seq_nk, seg_offs, segs, k, ends):
+    """host: FinitoError FIN_EINVAL naming the first segment of a path set that is not valid, and the clause (fin_segments_check)"""
+    nk, so, sg = _path_set("segments_check", seq_nk, seg_offs, segs)
+    e, ep, ne = _twin_ends(ends)
+    err = C.create_string_buffer(512)
+    _check(lib().fin_segments_check(nk.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), sg.ctypes.data_as(C.c_void_p), len(nk), int(k), ep, ne, err, 512), err)
+
+
+def segments_window_depth(seq_nk, seg_offs, segs, k, ends, depth, window=1000, min_depth=1, n_threads=0, cap=None):
+    """host: RefDepth of a path set over depth uint32[total_len] (fin_segments_window_depth) -- the CPU statement of RefPaths.depth_windows.  cap: room for so many
+    windows, FinitoError FIN_ELIMIT beyond (its n_windows attribute the true count); None: as many as there are"""
+    nk, so, sg = _path_set("segments_window_depth", seq_nk, seg_offs, segs)
+    e, ep, ne = _twin_ends(ends)
+    d = np.ascontiguousarray(depth, dtype=np.uint32).reshape(-1)
+    w, md = _window_args("segments_window_depth", window, min_depth)
+    room = int(sum(-(-int(x) // w) for x in nk)) if cap is None else int(cap)
+    wo = np.zeros(len(nk) + 1, dtype=np.uint64)
+    out = np.zeros(max(room, 1), dtype=REF_WINDOW_DTYPE)
+    n = C.c_uint64(0)
+    err = C.create_string_buffer(512)
+    rc = lib().fin_segments_window_depth(nk.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), sg.ctypes.data_as(C.c_void_p), len(nk), int(k), ep, ne,
+                                         d.ctypes.data_as(C.c_void_p), w, md, wo.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), room, C.byref(n),
+                                         int(n_threads), err, 512)
+    if rc != 0:
+        ex = FinitoError(rc, "fin_segments_window_depth: " + err.value.decode())
+        ex.n_windows = int(n.value)
+        raise ex
+    return RefDepth(wo, out[: int(n.value)], w, md)
+
+
+def segments_lift_variants(seq_nk, seg_offs, segs, k, ends, variants, n_threads=0, cap=None):
+    """host: REF_VARIANT_DTYPE[n] of a path set and Pileup.call's candidates (fin_segments_lift_variants) -- the CPU statement of RefPaths.lift_variants.  cap: room
+    for so many records, FinitoError FIN_ELIMIT beyond (its n_out attribute the true count); None: as many as there are"""
+    nk, so, sg = _path_set("segments_lift_variants", seq_nk, seg_offs, segs)
+    e, ep, ne = _twin_ends(ends)
+    v = np.ascontiguousarray(variants, dtype=VARIANT_DTYPE).reshape(-1)
+    n = C.c_uint64(0)
+    err = C.create_string_buffer(512)
+    room = 1024 if cap is None else int(cap)
+    while True:
+        out = np.zeros(max(room, 1), dtype=REF_VARIANT_DTYPE)
+        rc = lib().fin_segments_lift_variants(nk.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), sg.ctypes.data_as(C.c_void_p), len(nk), int(k), ep, ne,
+                                              v.ctypes.data_as(C.c_void_p), len(v), out.ctypes.data_as(C.c_void_p), room, C.byref(n), int(n_threads), err, 512)
+        if rc == FIN_ELIMIT and cap is None and int(n.value) > room:
+            room = int(n.value)
+            continue
+        if rc != 0:
+            ex = FinitoError(rc, "fin_segments_lift_variants: " + err.value.decode())
+            ex.n_out = int(n.value)
+            raise ex
+        return out[: int(n.value)]
 
 
 def rows_eqclasses(rows, n_colors):

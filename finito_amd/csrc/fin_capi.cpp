@@ -99,7 +99,7 @@ const char* fin_version(void) { return "finito-amd 0.1 (gfx950)"; }
 // A handle that has its own value of an option uses it, every other handle follows the process-wide value.  The per-handle form is the
 // one to use when handles are shared between threads: it touches nothing but its index.
 enum : int { O_lds_deque_limit, O_kernel, O_probe_prepass, O_ptab_t, O_jtab_t, O_write_gaps, O_overlap_prefill, O_filt_f, O_seed_anchors, O_kmer_table,
-              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_colcov_chunk, O_colsim_chunk, O_colorsets_tag_bits, O_depthhist_unitigs, O_COUNT };
+              O_defer_strand, O_fast_path, O_cbf_m, O_lean_tables, O_text_anchors, O_epoch_budget_mult, O_epoch_budget_add, O_max_batch_kmers, O_pipeline_kmers, O_pipeline_depth, O_stage_pageable, O_debug_ovf_cap, O_debug_pp_seg, O_lean_walk, O_fused_ingest, O_pp_park, O_debug_pp_park_cap, O_pp_wide_out, O_hits_combine, O_cover_probe, O_debug_depth_tile, O_ec_tag_bits, O_ec_combine, O_ab_chunk, O_assign_rpb, O_colcov_chunk, O_colsim_chunk, O_colorsets_tag_bits, O_depthhist_unitigs, O_refpaths_tile, O_COUNT };
 static_assert(O_COUNT <= FIN_N_OPTIONS, "fin_index::opt_val has room for every option");
 struct OptDef { const char* name; int64_t def, lo, hi; };
 static const OptDef OPTS[O_COUNT] = {
@@ -142,6 +142,7 @@ static const OptDef OPTS[O_COUNT] = {
     {"colsim_chunk", 0, 0, 1ll << 26},             // fin_colors_shared: unitigs per chunk of fin_colsim_tile_kernel (fin_colsim.hip), rounded up to a multiple of 64; 0 = auto: 4096, more once that would make over 16384 waves; never so few that tiles x chunks would pass 2^30 blocks.  The results do not depend on it; tests set 64 so that small cases cross chunk seams
     {"colorsets_tag_bits", 31, 1, 31},             // fin_colors_compact: bits of a row's tag in the dedup table (fin_colorsets.hip); the home slot is a function of the tag, so tests narrow it to force distinct rows under one tag and long probe chains.  The results do not depend on it
     {"depthhist_unitigs", 0, 0, 1ll << 26},        // fin_colors_depth_histogram: unitigs per sub-range of a staged chunk, each binned into a table uint32[unitigs][n_bins] and projected (fin_depthhist.hip); 0 = auto: what a table of 64 MB holds, at least 64.  A value is cut to that budget too.  The results do not depend on it; tests set 16 so that small cases cross sub-range seams
+    {"refpaths_tile", 0, 0, 1ll << 26},            // fin_refpaths_depth: slots of a segment per tile, a wave's work in fin_rp_depth_kernel (fin_refpaths.hip), rounded up to a multiple of 64; 0 = auto: 4096.  The results do not depend on it; tests set 64 so that small segments cross tile seams
 };
 static std::atomic<int64_t> g_opt[O_COUNT];
 static const bool g_opt_init = [] { for (int i = 0; i < O_COUNT; i++) g_opt[i].store(OPTS[i].def); return true; }();
@@ -4420,6 +4421,320 @@ int fin_search_batch_fragments(const fin_index* idx, const char* bases, const ui
         return fin_batch_download_fragments(b, frags_out + s.lo / 2, e, elen);
     };
     return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
+}
+
+// ---- reference coordinates: depth and variant candidates lifted onto sequences (fin_refpaths.hip) ---------------------------------------------
+// The sequences' tables are small and live on the host (seq_nk, seg_offs); the segments lie in HBM alone.  seg_offs goes to the device when a kernel or a caller
+// wants it.  `mu` guards everything but `pend`
+struct fin_refpaths : fin_acc {
+    uint64_t n_unitigs = 0, total_len = 0;
+    const uint32_t* d_ends = nullptr;     // the replica's ends_p
+    std::mutex mu;
+    std::vector<uint32_t> seq_nk;         // [n_seqs]
+    std::vector<uint64_t> seg_offs{0};    // [n_seqs + 1]
+    uint64_t n_slots = 0;
+    void* d_segs = nullptr; size_t cap_segs = 0;         // fin_segment[n_segments], room for cap_segs of them
+    void* d_seg_offs = nullptr; size_t cap_offs = 0;     // uint64[n_seqs + 1] where offs_fresh
+    bool offs_fresh = false;
+    uint32_t* d_ctl = nullptr;            // 16 bytes: what a reset zeroes (the appends are ordered against it), word 0 the flag word of a call, words 2 and 3 a call's uint64 total
+};
+static_assert(sizeof(fin_ref_window) == 16 && sizeof(fin_ref_variant) == 16 && sizeof(fin_variant) == 32, "the kernels' 16- and 32-byte entries");
+static const char* const REFPATHS_OUTSIDE = "a segment outside the index was met: nothing was written (reset the path set)";
+namespace {
+struct DevMem {   // a call's own allocation, freed on every way out
+    void* p = nullptr;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    bool get(size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; } return true; }
+};
+}  // namespace
+static uint64_t refpaths_n_segs(const fin_refpaths* rp) { return rp->seg_offs.back(); }
+// room for n segments, what is there kept (with mu held)
+static int refpaths_room(fin_refpaths* rp, uint64_t n, char* err, size_t errlen) {
+    if (n <= rp->cap_segs) return FIN_OK;
+    if (const int wrc = rp->pend.wait(err, errlen)) return wrc;
+    const size_t want = (size_t)(n + n / 4 + 1024);
+    void* p = nullptr;
+    if (hipMalloc(&p, want * 16) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (reference paths)"); return FIN_ENOMEM; }
+    const uint64_t have = refpaths_n_segs(rp);
+    if (have && hipMemcpy(p, rp->d_segs, (size_t)have * 16, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(p); set_err(err, errlen, "hipMemcpy failed"); return FIN_ENODEV; }
+    (void)hipFree(rp->d_segs);
+    rp->d_segs = p; rp->cap_segs = want;
+    return FIN_OK;
+}
+// seg_offs on the device, on the null stream (with mu held)
+static int refpaths_offs(fin_refpaths* rp, char* err, size_t errlen) {
+    if (rp->offs_fresh) return FIN_OK;
+    const size_t n = rp->seg_offs.size();
+    if (n > rp->cap_offs) {
+        (void)hipFree(rp->d_seg_offs); rp->d_seg_offs = nullptr; rp->cap_offs = 0;
+        if (hipMalloc(&rp->d_seg_offs, (n + n / 4 + 64) * 8) != hipSuccess) { (void)hipGetLastError(); rp->d_seg_offs = nullptr; set_err(err, errlen, "out of device memory (reference paths)"); return FIN_ENOMEM; }
+        rp->cap_offs = n + n / 4 + 64;
+    }
+    HIPCHK(hipMemcpy(rp->d_seg_offs, rp->seg_offs.data(), n * 8, hipMemcpyHostToDevice));
+    rp->offs_fresh = true;
+    return FIN_OK;
+}
+
+void fin_refpaths_free(fin_refpaths* rp) {
+    if (!acc_free_open(rp)) return;
+    (void)hipFree(rp->d_segs); (void)hipFree(rp->d_seg_offs); (void)hipFree(rp->d_ctl);
+    delete rp;
+}
+
+int fin_refpaths_create(const fin_index* idx, int device, fin_refpaths** out, char* err, size_t errlen) {
+    if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    const fin_index::Replica* rep = nullptr;
+    if (const int orc = acc_create_open(idx, device, &rep, err, errlen)) return orc;
+    fin_refpaths* rp = acc_new<fin_refpaths>(idx, device, err, errlen);
+    if (!rp) return FIN_ENOMEM;
+    rp->n_unitigs = idx->n_unitigs; rp->total_len = idx->total_len; rp->d_ends = rep->dev.ends;
+    if (const int arc = acc_alloc_zero(rp, (void**)&rp->d_ctl, 16, 16, "out of device memory (reference paths)", fin_refpaths_free, err, errlen)) return arc;
+    *out = rp;
+    return FIN_OK;
+}
+
+int fin_refpaths_reset(fin_refpaths* rp, void* hip_stream) {
+    if (!rp) return FIN_EINVAL;
+    std::lock_guard<std::mutex> g(rp->mu);
+    rp->seq_nk.clear(); rp->seg_offs.assign(1, 0); rp->n_slots = 0; rp->offs_fresh = false;
+    return acc_reset(rp, hip_stream, rp->d_ctl, 16);
+}
+
+uint64_t fin_refpaths_n_seqs(const fin_refpaths* rp) { if (!rp) return 0; std::lock_guard<std::mutex> g(const_cast<fin_refpaths*>(rp)->mu); return rp->seq_nk.size(); }
+uint64_t fin_refpaths_n_segments(const fin_refpaths* rp) { if (!rp) return 0; std::lock_guard<std::mutex> g(const_cast<fin_refpaths*>(rp)->mu); return refpaths_n_segs(rp); }
+uint64_t fin_refpaths_n_slots(const fin_refpaths* rp) { if (!rp) return 0; std::lock_guard<std::mutex> g(const_cast<fin_refpaths*>(rp)->mu); return rp->n_slots; }
+void* fin_refpaths_device_segments(const fin_refpaths* rp) { return rp ? rp->d_segs : nullptr; }
+void* fin_refpaths_device_segment_offsets(fin_refpaths* rp) {
+    if (!rp || hipSetDevice(rp->device) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> g(rp->mu);
+    return refpaths_offs(rp, nullptr, 0) == FIN_OK ? rp->d_seg_offs : nullptr;
+}
+
+int fin_refpaths_download(fin_refpaths* rp, uint32_t* seq_nk_out, uint64_t* seg_offs_out, fin_segment* segs_out, char* err, size_t errlen) {
+    if (!rp) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (const int orc = acc_download_open(rp, nullptr, nullptr, nullptr, err, errlen)) return orc;
+    std::lock_guard<std::mutex> g(rp->mu);
+    if (seq_nk_out && !rp->seq_nk.empty()) memcpy(seq_nk_out, rp->seq_nk.data(), rp->seq_nk.size() * 4);
+    if (seg_offs_out) memcpy(seg_offs_out, rp->seg_offs.data(), rp->seg_offs.size() * 8);
+    if (segs_out && refpaths_n_segs(rp)) HIPCHK(hipMemcpy(segs_out, rp->d_segs, (size_t)refpaths_n_segs(rp) * 16, hipMemcpyDeviceToHost));
+    return FIN_OK;
+}
+
+// unitigs.ends as FIN_X_ENDS has them, from the index's starts
+static std::vector<int64_t> refpaths_host_ends(const fin_index* idx) {
+    std::vector<int64_t> e((size_t)idx->n_unitigs);
+    for (uint64_t u = 0; u < idx->n_unitigs; u++) e[(size_t)u] = (int64_t)idx->ends[u + 1];
+    return e;
+}
+
+int fin_refpaths_upload(fin_refpaths* rp, const uint32_t* seq_nk, const uint64_t* seg_offs, const fin_segment* segs, uint64_t n_seqs, char* err, size_t errlen) {
+    if (!rp || (n_seqs && (!seq_nk || !seg_offs))) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    const std::vector<int64_t> ends = refpaths_host_ends(rp->idx);
+    if (const int crc = fin_segments_check(seq_nk, seg_offs, segs, n_seqs, (int)rp->idx->k, ends.data(), rp->n_unitigs, err, errlen)) return crc;
+    HIPCHK(hipSetDevice(rp->device));
+    if (const int wrc = rp->pend.wait(err, errlen)) return wrc;
+    std::lock_guard<std::mutex> g(rp->mu);
+    const uint64_t n = n_seqs ? seg_offs[n_seqs] : 0;
+    if (n > rp->cap_segs) {   // (nothing is kept: the contents are replaced)
+        void* p = nullptr;
+        if (hipMalloc(&p, (size_t)n * 16) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (reference paths)"); return FIN_ENOMEM; }
+        (void)hipFree(rp->d_segs);
+        rp->d_segs = p; rp->cap_segs = (size_t)n;
+    }
+    if (n) HIPCHK(hipMemcpy(rp->d_segs, segs, (size_t)n * 16, hipMemcpyHostToDevice));
+    rp->seq_nk.assign(seq_nk, seq_nk + n_seqs);
+    if (n_seqs) rp->seg_offs.assign(seg_offs, seg_offs + n_seqs + 1); else rp->seg_offs.assign(1, 0);
+    rp->n_slots = sum_of(seq_nk, (size_t)n_seqs, [](uint32_t v) { return v; });
+    rp->offs_fresh = false;
+    return FIN_OK;
+}
+
+// the batch's segments as they lie in HBM, made if there are none, and its seg_offs on the host: everything the segment kernels were given has finished
+static int refpaths_batch_segments(fin_batch* b, std::vector<uint64_t>& so, char* err, size_t errlen) {
+    if (!b->sgm_ready) if (const int rc = fin_batch_segments(b, nullptr, err, errlen)) return rc;
+    so.resize((size_t)b->n_reads + 1);
+    HIPCHK(hipMemcpyAsync(so.data(), b->d_sgm_offs, so.size() * 8, hipMemcpyDeviceToHost, b->last_stream));
+    HIPCHK(hipStreamSynchronize(b->last_stream));
+    if (so[0] != 0 || so.back() != b->n_segments) { set_err(err, errlen, "segment kernels: offsets and count disagree"); return FIN_ENODEV; }
+    return FIN_OK;
+}
+// the sequences of one batch behind those that are there (with mu held): the tables on the host, the segments from `src` device to device on `st`
+static int refpaths_append(fin_refpaths* rp, const fin_batch* b, const std::vector<uint64_t>& so, const void* src, hipStream_t st, char* err, size_t errlen) {
+    const uint64_t have = refpaths_n_segs(rp), L = so.back();
+    if (const int rrc = refpaths_room(rp, have + L, err, errlen)) return rrc;
+    if (L) HIPCHK(hipMemcpyAsync((char*)rp->d_segs + (size_t)have * 16, src, (size_t)L * 16, hipMemcpyDeviceToDevice, st));
+    for (uint64_t r = 0; r < b->n_reads; r++) {
+        const uint32_t nk = (uint32_t)(b->h_out_offs[r + 1] - b->h_out_offs[r]);
+        rp->seq_nk.push_back(nk); rp->n_slots += nk;
+        rp->seg_offs.push_back(have + so[(size_t)r + 1]);
+    }
+    rp->offs_fresh = false;
+    return FIN_OK;
+}
+
+int fin_batch_add_refpaths(fin_batch* b, fin_refpaths* rp, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !rp) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (const int orc = acc_add_open(b, rp, st, err, errlen)) return orc;
+    std::vector<uint64_t> so;
+    if (const int src = refpaths_batch_segments(b, so, err, errlen)) return src;
+    std::lock_guard<std::mutex> g(rp->mu);
+    if (const int arc = refpaths_append(rp, b, so, b->d_sgm, st, err, errlen)) return arc;
+    return acc_add_close(rp, st, 0, "", err, errlen);
+}
+
+int fin_search_batch_add_refpaths(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, fin_refpaths* rp, char* err, size_t errlen) {
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, FIN_MERGED, rp, rp, OTHER_ACC, &device, err, errlen)) return orc;
+    if (n_reads == 0) return FIN_OK;
+    // Sub-batches finish in any order and the sequences are appended in the reads': each worker copies its segments device to device into a buffer of its own,
+    // and they are put behind one another once all are there.  Nobody waits for anybody, so a worker that fails strands no other
+    struct Part { size_t i; std::vector<uint32_t> nk; std::vector<uint64_t> so; void* d = nullptr; };
+    std::mutex pmu;
+    std::vector<Part> parts;
+    Product p;
+    p.take = [&](fin_batch* b, const SubBatch& s, uint64_t&, char* e, size_t elen) -> int {
+        Part q; q.i = s.i;
+        if (const int rc = refpaths_batch_segments(b, q.so, e, elen)) return rc;
+        const uint64_t L = q.so.back();
+        if (L) {
+            if (hipMalloc(&q.d, (size_t)L * 16) != hipSuccess) { (void)hipGetLastError(); snprintf(e, elen, "out of device memory (reference paths)"); return FIN_ENOMEM; }
+            if (hipMemcpy(q.d, b->d_sgm, (size_t)L * 16, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(q.d); snprintf(e, elen, "hipMemcpy failed"); return FIN_ENODEV; }
+        }
+        q.nk.resize((size_t)b->n_reads);
+        for (uint64_t r = 0; r < b->n_reads; r++) q.nk[(size_t)r] = (uint32_t)(b->h_out_offs[r + 1] - b->h_out_offs[r]);
+        std::lock_guard<std::mutex> g(pmu);
+        parts.push_back(std::move(q));
+        return FIN_OK;
+    };
+    int rc = search_product(idx, device, bases, offsets, n_reads, FIN_MERGED, p, nullptr, err, errlen);
+    if (rc == FIN_OK && hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); rc = FIN_ENODEV; }
+    if (rc == FIN_OK) {
+        std::sort(parts.begin(), parts.end(), [](const Part& a, const Part& b) { return a.i < b.i; });
+        uint64_t more = 0;
+        for (const Part& q : parts) more += q.so.back();
+        std::lock_guard<std::mutex> g(rp->mu);
+        rc = refpaths_room(rp, refpaths_n_segs(rp) + more, err, errlen);
+        for (size_t j = 0; rc == FIN_OK && j < parts.size(); j++) {
+            const Part& q = parts[j];
+            const uint64_t have = refpaths_n_segs(rp), L = q.so.back();
+            if (L && hipMemcpy((char*)rp->d_segs + (size_t)have * 16, q.d, (size_t)L * 16, hipMemcpyDeviceToDevice) != hipSuccess) { set_err(err, errlen, "hipMemcpy failed"); rc = FIN_ENODEV; break; }
+            for (size_t r = 0; r < q.nk.size(); r++) { rp->seq_nk.push_back(q.nk[r]); rp->n_slots += q.nk[r]; rp->seg_offs.push_back(have + q.so[r + 1]); }
+            rp->offs_fresh = false;
+        }
+    }
+    for (Part& q : parts) (void)hipFree(q.d);
+    return rc;
+}
+
+int fin_refpaths_depth(fin_refpaths* rp, fin_depth* dep, uint32_t window, uint32_t min_depth, uint64_t* win_offs_out, fin_ref_window* out, uint64_t cap,
+                       uint64_t* n_windows, char* err, size_t errlen) {
+    if (n_windows) *n_windows = 0;
+    if (!rp || !dep) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    if (window == 0) { set_err(err, errlen, "window is at least 1"); return FIN_EINVAL; }
+    if (dep->idx != rp->idx || dep->device != rp->device) { set_err(err, errlen, "paths and depth accumulator belong to different indexes or devices"); return FIN_EINVAL; }
+    // the two waits, with the downloads' own codes and messages for a withheld step or a pair outside the index (nothing else happens in these calls)
+    if (const int rc = fin_refpaths_download(rp, nullptr, nullptr, nullptr, err, errlen)) return rc;
+    if (const int rc = fin_depth_download(dep, min_depth, nullptr, nullptr, nullptr, err, errlen)) return rc;
+    std::lock_guard<std::mutex> g(rp->mu);
+    const uint64_t n_seqs = rp->seq_nk.size(), n_segs = refpaths_n_segs(rp);
+    std::vector<uint64_t> wo((size_t)n_seqs + 1, 0);
+    for (uint64_t s = 0; s < n_seqs; s++) wo[(size_t)s + 1] = wo[(size_t)s] + ((uint64_t)rp->seq_nk[(size_t)s] + window - 1) / window;
+    const uint64_t W = wo[(size_t)n_seqs];
+    if (n_windows) *n_windows = W;
+    if (W > cap || (W && !out)) { set_err(err, errlen, "window buffer too small: room for " + std::to_string(cap) + " windows, " + std::to_string(W) + " needed"); return FIN_ELIMIT; }
+    if (W == 0 || n_segs == 0 || rp->total_len == 0) {   // nothing lies in the graph
+        if (win_offs_out) memcpy(win_offs_out, wo.data(), wo.size() * 8);
+        if (W) memset(out, 0, (size_t)W * sizeof(fin_ref_window));
+        return FIN_OK;
+    }
+    if (const int orc = refpaths_offs(rp, err, errlen)) return orc;
+    // the call's own memory: the depths of the whole text; then the windows, their offsets, and the tiles' tables
+    const uint32_t tile = fin_rp_tile((uint32_t)optv(rp->idx, O_refpaths_tile)), nb = fin_rp_blocks(n_segs);
+    DevMem full, aux;
+    const size_t b_win = (size_t)W * 16, b_wo = wo.size() * 8, b_toffs = ((size_t)n_segs + 1) * 8, b_boff = ((size_t)nb + 1) * 8, b_cnt = ((size_t)n_segs + 4) / 4 * 16,
+                 b_bsum = ((size_t)nb + 4) / 4 * 16;
+    if (!full.get((size_t)rp->total_len * 4) || !aux.get(b_win + b_wo + b_toffs + b_boff + b_cnt + b_bsum)) { set_err(err, errlen, "out of device memory (reference depth)"); return FIN_ENOMEM; }
+    char* const a = (char*)aux.p;
+    void* const d_win = a;
+    uint64_t* const d_wo = (uint64_t*)(a + b_win);
+    uint64_t* const d_toffs = (uint64_t*)(a + b_win + b_wo);
+    uint64_t* const d_boff = (uint64_t*)(a + b_win + b_wo + b_toffs);
+    uint32_t* const d_cnt = (uint32_t*)(a + b_win + b_wo + b_toffs + b_boff);
+    uint32_t* const d_bsum = (uint32_t*)(a + b_win + b_wo + b_toffs + b_boff + b_cnt);
+    uint64_t* const d_total = (uint64_t*)(rp->d_ctl + 2);
+    {   // everything below is on the null stream; the lock keeps a download from scanning in between
+        std::lock_guard<std::mutex> gd(dep->scan_mu);
+        const int rc = depth_scan(dep, min_depth, nullptr, false, err, errlen, [&](uint64_t base, uint64_t n) {
+            return (int)hipMemcpyAsync((uint32_t*)full.p + base, dep->d_stage, (size_t)n * 4, hipMemcpyDeviceToDevice, nullptr);
+        });
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemsetAsync(d_win, 0, b_win, nullptr));
+    HIPCHK(hipMemsetAsync(rp->d_ctl, 0, 16, nullptr));
+    HIPCHK(hipMemcpyAsync(d_wo, wo.data(), b_wo, hipMemcpyHostToDevice, nullptr));
+    int krc = fin_launch_rp_tiles(rp->d_segs, n_segs, tile, d_cnt, d_bsum, d_boff, d_toffs, d_total, nullptr);
+    uint64_t n_tiles = 0;
+    if (krc == 0) {
+        HIPCHK(hipMemcpy(&n_tiles, d_total, 8, hipMemcpyDeviceToHost));
+        krc = fin_launch_rp_depth(rp->d_segs, n_segs, (const uint64_t*)rp->d_seg_offs, n_seqs, d_toffs, n_tiles, tile, d_wo, window, min_depth, (const uint32_t*)full.p,
+                                  rp->d_ends, (uint32_t)rp->n_unitigs, rp->total_len, rp->idx->k, d_win, rp->d_ctl, nullptr);
+    }
+    if (krc != 0) { set_err(err, errlen, std::string("reference depth kernels: ") + hipGetErrorString((hipError_t)krc)); return FIN_ENODEV; }
+    uint32_t flags = 0;
+    HIPCHK(hipMemcpy(&flags, rp->d_ctl, 4, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels)
+    if (flags) { set_err(err, errlen, REFPATHS_OUTSIDE); return FIN_EINVAL; }
+    HIPCHK(hipMemcpy(out, d_win, b_win, hipMemcpyDeviceToHost));
+    if (win_offs_out) memcpy(win_offs_out, wo.data(), wo.size() * 8);
+    return FIN_OK;
+}
+
+int fin_refpaths_lift_variants(fin_refpaths* rp, const fin_variant* vars, uint64_t n, fin_ref_variant* out, uint64_t cap, uint64_t* n_out, char* err, size_t errlen) {
+    if (n_out) *n_out = 0;
+    if (!rp || (n && !vars)) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    // the variants, on the host: inside the index, strictly ascending
+    const fin_index* idx = rp->idx;
+    uint64_t prev = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (vars[i].u >= idx->n_unitigs || (uint64_t)idx->ends[vars[i].u] + vars[i].off >= idx->ends[vars[i].u + 1]) { set_err(err, errlen, "variant " + std::to_string(i) + " lies outside the index"); return FIN_EINVAL; }
+        const uint64_t g = (uint64_t)idx->ends[vars[i].u] + vars[i].off;
+        if (i && g <= prev) { set_err(err, errlen, "variant " + std::to_string(i) + " does not ascend: the variants are strictly ascending in start(u) + off"); return FIN_EINVAL; }
+        prev = g;
+    }
+    if (const int rc = fin_refpaths_download(rp, nullptr, nullptr, nullptr, err, errlen)) return rc;
+    std::lock_guard<std::mutex> g(rp->mu);
+    const uint64_t n_seqs = rp->seq_nk.size(), n_segs = refpaths_n_segs(rp);
+    if (n_segs == 0) return FIN_OK;   // (with no variant the segments are still looked at: the guard)
+    if (const int orc = refpaths_offs(rp, err, errlen)) return orc;
+    const uint32_t nb = fin_rp_blocks(n_segs);
+    DevMem aux, rec;
+    const size_t b_vars = (size_t)n * 32, b_g = (size_t)n * 8 + 8, b_boff = ((size_t)nb + 1) * 8, b_cnt = ((size_t)n_segs + 4) / 4 * 16, b_bsum = ((size_t)nb + 4) / 4 * 16;
+    if (!aux.get(b_vars + b_g + b_boff + b_cnt + b_bsum)) { set_err(err, errlen, "out of device memory (lifted variants)"); return FIN_ENOMEM; }
+    char* const a = (char*)aux.p;
+    uint64_t* const d_g = (uint64_t*)(a + b_vars);
+    uint64_t* const d_boff = (uint64_t*)(a + b_vars + b_g);
+    uint32_t* const d_cnt = (uint32_t*)(a + b_vars + b_g + b_boff);
+    uint32_t* const d_bsum = (uint32_t*)(a + b_vars + b_g + b_boff + b_cnt);
+    uint64_t* const d_total = (uint64_t*)(rp->d_ctl + 2);
+    const uint32_t nu = (uint32_t)rp->n_unitigs, k = idx->k;
+    if (n) HIPCHK(hipMemcpyAsync(a, vars, b_vars, hipMemcpyHostToDevice, nullptr));
+    HIPCHK(hipMemsetAsync(rp->d_ctl, 0, 16, nullptr));
+    int krc = fin_launch_rp_var_g(a, n, rp->d_ends, d_g, nullptr);
+    if (krc == 0) krc = fin_launch_rp_var_count(rp->d_segs, n_segs, d_g, n, rp->d_ends, nu, rp->total_len, k, d_cnt, d_bsum, d_boff, d_total, rp->d_ctl, nullptr);
+    if (krc != 0) { set_err(err, errlen, std::string("variant lift kernels: ") + hipGetErrorString((hipError_t)krc)); return FIN_ENODEV; }
+    uint32_t ctl[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(ctl, rp->d_ctl, 16, hipMemcpyDeviceToHost));   // (the null stream: behind the kernels)
+    if (ctl[0]) { set_err(err, errlen, REFPATHS_OUTSIDE); return FIN_EINVAL; }
+    const uint64_t total = ((uint64_t)ctl[3] << 32) | ctl[2];
+    if (n_out) *n_out = total;
+    if (total > cap || (total && !out)) { set_err(err, errlen, "record buffer too small: room for " + std::to_string(cap) + " records, " + std::to_string(total) + " needed"); return FIN_ELIMIT; }
+    if (total == 0) return FIN_OK;
+    if (!rec.get((size_t)total * 16)) { set_err(err, errlen, "out of device memory (lifted variants)"); return FIN_ENOMEM; }
+    krc = fin_launch_rp_var_write(rp->d_segs, n_segs, (const uint64_t*)rp->d_seg_offs, n_seqs, d_g, n, rp->d_ends, nu, rp->total_len, k, d_boff, rec.p, rp->d_ctl, nullptr);
+    if (krc != 0) { set_err(err, errlen, std::string("variant lift kernels: ") + hipGetErrorString((hipError_t)krc)); return FIN_ENODEV; }
+    HIPCHK(hipMemcpy(out, rec.p, (size_t)total * 16, hipMemcpyDeviceToHost));
+    return FIN_OK;
 }
 
 int fin_search_batch(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands,

@@ -301,6 +301,25 @@ int fin_launch_depth_spectrum(const uint32_t* depth, uint64_t g_base, uint64_t n
 int fin_launch_color_depth_hist(const uint32_t* depth, uint64_t g_base, uint64_t n, uint64_t lo, uint64_t hi, const uint32_t* ends_p, uint32_t n_unitigs,
                                 uint64_t total_len, uint32_t k, uint32_t n_bins, uint32_t bin_width, uint32_t u_lo, uint32_t u_hi, uint32_t* V, const void* bits,
                                 uint32_t W, uint32_t n_colors, const void* cls, uint32_t variant, uint64_t* out, uint64_t* none, hipStream_t stream);
+// fin_refpaths.hip -- reference coordinates: segs fin_segment[n_segs] of n_seqs sequences delimited by seg_offs[n_seqs + 1], both in HBM.
+// fin_rp_tile: the slots a wave's tile holds under option "refpaths_tile" (0: auto).  fin_launch_rp_tiles: cnt n_segs u32, blk_sum fin_rp_blocks() u32, blk_off as
+// many u64, tile_offs[n_segs + 1] u64 and *total = the tiles.  fin_launch_rp_depth, once the host has read *total: win {u64 depth_sum, u32 in_graph, u32 covered} per
+// window, zeroed by the caller, win_offs[n_seqs + 1] the sequences' first windows, depth uint32[total_len]; flags one u32 (bit 1: a segment outside the index or
+// outside its sequence's windows -- it added nothing).  fin_launch_rp_var_g: g[n] = the text positions of fin_variant vars[n].  fin_launch_rp_var_count /
+// fin_launch_rp_var_write: the variants inside every segment's base interval as records {seq, pos, var, flags} of 16 bytes, by segment, then by pos; out has room for
+// *total of them
+uint32_t fin_rp_tile(uint32_t refpaths_tile);
+uint32_t fin_rp_blocks(uint64_t n_segs);
+int fin_launch_rp_tiles(const void* segs, uint64_t n_segs, uint32_t tile, uint32_t* cnt, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* tile_offs, uint64_t* total,
+                        hipStream_t stream);
+int fin_launch_rp_depth(const void* segs, uint64_t n_segs, const uint64_t* seg_offs, uint64_t n_seqs, const uint64_t* tile_offs, uint64_t n_tiles, uint32_t tile,
+                        const uint64_t* win_offs, uint32_t window, uint32_t min_depth, const uint32_t* depth, const uint32_t* ends_p, uint32_t n_unitigs,
+                        uint64_t total_len, uint32_t k, void* win, uint32_t* flags, hipStream_t stream);
+int fin_launch_rp_var_g(const void* vars, uint64_t n, const uint32_t* ends_p, uint64_t* g, hipStream_t stream);
+int fin_launch_rp_var_count(const void* segs, uint64_t n_segs, const uint64_t* g, uint64_t n_vars, const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len,
+                            uint32_t k, uint32_t* cnt, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total, uint32_t* flags, hipStream_t stream);
+int fin_launch_rp_var_write(const void* segs, uint64_t n_segs, const uint64_t* seg_offs, uint64_t n_seqs, const uint64_t* g, uint64_t n_vars, const uint32_t* ends_p,
+                            uint32_t n_unitigs, uint64_t total_len, uint32_t k, const uint64_t* blk_off, void* out, uint32_t* flags, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

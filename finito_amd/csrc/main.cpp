@@ -601,6 +601,15 @@ static const char* SEARCH_HELP =
     "      --ab-fragment-lengths arg  1 (with --paired 1, --abundance and --ab-lengths): the numbers of --ab-lengths are the references' lengths in bases; they\n"
     "                        become effective lengths under the run's own fragment-length histogram (bin width 1) after the last chunk, before the EM, and are\n"
     "                        written as a further column of the abundance file\n"
+    "      --ref-paths LIST  reference coordinates: LIST names one FASTA/FASTQ file per line; every record is searched before the first chunk of reads and its\n"
+    "                        path through the unitig set stays on the first GPU. Wants --ref-depth or --ref-variants; independent of --color-refs. Not for a\n"
+    "                        partitioned index.\n"
+    "      --ref-depth FILE  with --ref-paths: the depth of the run along every record, in windows of --ref-window W slots (1 .. 2147483648, default 1000),\n"
+    "                        lifted on the GPU after the last chunk: ref<TAB>record<TAB>start<TAB>end<TAB>in_graph<TAB>covered<TAB>depth_sum, ref the line of LIST from 0,\n"
+    "                        record the record's number in its file, [start, end) 0-based k-mer slots; covered counts against --min-depth\n"
+    "      --ref-variants FILE  with --ref-paths: the pileup's candidates (--min-alt, --min-alt-permille, --pileup-max-mismatch) under every record that\n"
+    "                        crosses them: ref<TAB>record<TAB>pos<TAB>+|-<TAB>ref_base<TAB>cover<TAB>A<TAB>C<TAB>G<TAB>T<TAB>unitig<TAB>offset, pos 1-based, bases and counts\n"
+    "                        in the record's orientation\n"
     "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify,\n"
     "                        --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance): do not make or write the pair\n"
     "                        text, the other results asked for are the only ones\n"
@@ -786,6 +795,7 @@ static void add_depth_chunk(const FinimizerIndex& index, const char* bases, cons
 }
 // --pileup FILE / --variants FILE: the same for the base pileup (fin_search_batch_add_pileup)
 static fin_pileup* g_pileup = nullptr;
+static fin_refpaths* g_refpaths = nullptr;   // --ref-paths: the references' paths through the unitig set, made before the first chunk
 static void add_pileup_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
     char err[512] = {0};
     if (fin_search_batch_add_pileup(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_pileup, err, sizeof err) != FIN_OK) throw runtime_error(err);
@@ -1526,12 +1536,12 @@ static void write_color_similarity(const string& path, fin_cover* cov, size_t nc
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "depth-histogram", "depth-bins", "depth-bin-width", "color-depth-histogram", "color-depth-quantiles", "color-similarity", "color-similarity-covered", "compact-colors", "color-sets-out", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "fragments", "fragment-lengths", "fragment-bins", "fragment-bin-width", "ab-fragment-lengths", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "depth-histogram", "depth-bins", "depth-bin-width", "color-depth-histogram", "color-depth-quantiles", "color-similarity", "color-similarity-covered", "compact-colors", "color-sets-out", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "fragments", "fragment-lengths", "fragment-bins", "fragment-bin-width", "ab-fragment-lengths", "ref-paths", "ref-depth", "ref-window", "ref-variants", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
     if (o.has("color-similarity-covered") && !o.has("color-similarity")) throw runtime_error("--color-similarity-covered is only legal together with --color-similarity");
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity") && !o.has("taxa") && !o.has("taxon-report") && !o.has("depth-histogram") && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles") && !o.has("fragments") && !o.has("fragment-lengths"))
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity") && !o.has("taxa") && !o.has("taxon-report") && !o.has("depth-histogram") && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles") && !o.has("fragments") && !o.has("fragment-lengths") && !o.has("ref-depth") && !o.has("ref-variants"))
         throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report, --abundance, --depth-histogram, --color-depth-histogram, --color-depth-quantiles, --fragments or --fragment-lengths (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
@@ -1663,7 +1673,7 @@ static int search_fmin(int argc, char** argv) {
         for (auto& f : paths) eqc_in.push_back(eqclasses_parse_file(f, (uint32_t)color_refs.size()));
     }
     g_scr_invert = o.has("screen-invert") && o.get("screen-invert") != "0" && o.get("screen-invert") != "false" ? 1 : 0;
-    if (o.has("min-depth") && !o.has("unitig-depth") && !o.has("color-coverage")) throw runtime_error("--min-depth is only legal together with --unitig-depth");
+    if (o.has("min-depth") && !o.has("unitig-depth") && !o.has("color-coverage") && !o.has("ref-depth")) throw runtime_error("--min-depth is only legal together with --unitig-depth");
     uint32_t min_depth = 1;
     if (o.has("min-depth")) {
         const string v = o.get("min-depth");
@@ -1672,9 +1682,28 @@ static int search_fmin(int argc, char** argv) {
         if (v.empty() || used != v.size() || v[0] == '-' || t > 0xFFFFFFFFull) throw runtime_error("--min-depth wants a number from 0 to 4294967295");
         min_depth = (uint32_t)t;
     }
-    const bool want_pileup = o.has("pileup") || o.has("variants");
+    // --ref-paths LIST --ref-depth FILE [--ref-window W] --ref-variants FILE: every refusal before the index is loaded, naming its flag
+    for (const char* name : {"ref-depth", "ref-variants"})
+        if (o.has(name) && !o.has("ref-paths")) throw runtime_error(string("--") + name + " wants --ref-paths LIST: the references whose coordinates it writes");
+    if (o.has("ref-paths") && !o.has("ref-depth") && !o.has("ref-variants")) throw runtime_error("--ref-paths is only legal together with --ref-depth or --ref-variants");
+    if (o.has("ref-window") && !o.has("ref-depth")) throw runtime_error("--ref-window is only legal together with --ref-depth");
+    uint32_t ref_window = 1000;
+    if (o.has("ref-window")) {
+        const string v = o.get("ref-window");
+        size_t used = 0; unsigned long long t = 0;
+        try { t = stoull(v, &used); } catch (...) { used = 0; }
+        if (v.empty() || used != v.size() || v[0] == '-' || t < 1 || t > 2147483648ull) throw runtime_error("--ref-window wants a number from 1 to 2147483648");
+        ref_window = (uint32_t)t;
+    }
+    vector<string> ref_paths;
+    if (o.has("ref-paths")) {
+        ref_paths = readlines(o.get("ref-paths"));
+        if (ref_paths.empty()) throw runtime_error("--ref-paths: " + o.get("ref-paths") + " is empty, it names no reference");
+        if (o.has("index-file") && ifstream(o.get("index-file") + ".finparts").good()) throw runtime_error("--ref-paths is not available with a partitioned index");
+    }
+    const bool want_pileup = o.has("pileup") || o.has("variants") || o.has("ref-variants");
     if ((o.has("pileup-max-mismatch") || o.has("min-alt") || o.has("min-alt-permille")) && !want_pileup)
-        throw runtime_error("--pileup-max-mismatch, --min-alt and --min-alt-permille are only legal together with --pileup or --variants");
+        throw runtime_error("--pileup-max-mismatch, --min-alt and --min-alt-permille are only legal together with --pileup or --variants (or --ref-variants)");
     auto pileup_number = [&](const char* name, unsigned long long dflt, unsigned long long top) -> uint32_t {
         if (!o.has(name)) return (uint32_t)dflt;
         const string v = o.get(name);
@@ -1718,6 +1747,10 @@ static int search_fmin(int argc, char** argv) {
     const string pileup_file = o.get("pileup", ""), variants_file = o.get("variants", "");
     if (!pileup_file.empty()) check_writable(pileup_file);
     if (!variants_file.empty()) check_writable(variants_file);
+    const string refdepth_file = o.get("ref-depth", ""), refvar_file = o.get("ref-variants", "");
+    if (!refdepth_file.empty()) check_writable(refdepth_file);
+    if (!refvar_file.empty()) check_writable(refvar_file);
+    for (auto& f : ref_paths) check_readable(f);
     const string seg_file = o.get("segments", "");
     if (!seg_file.empty()) check_writable(seg_file);
     const string rs_file = o.get("read-summary", "");
@@ -1816,6 +1849,7 @@ static int search_fmin(int argc, char** argv) {
     if (dh_asked && index.partitioned()) throw runtime_error("--depth-histogram, --color-depth-histogram and --color-depth-quantiles are not available with a partitioned index");
     if (!colcov_file.empty() && index.partitioned()) throw runtime_error("--color-coverage is not available with a partitioned index");
     if (!color_refs.empty() && index.partitioned()) throw runtime_error("--color-refs is not available with a partitioned index");
+    if (!ref_paths.empty() && index.partitioned()) throw runtime_error("--ref-paths is not available with a partitioned index");
     if (frag_asked && index.partitioned()) throw runtime_error("--fragments, --fragment-lengths and --ab-fragment-lengths are not available with a partitioned index");
     index.to_device();
     struct FragOwner { ~FragOwner() { if (g_frag_file) fclose(g_frag_file); g_frag_file = nullptr; fin_fragments_free(g_frag); g_frag = nullptr; } } frag_owner;
@@ -1838,7 +1872,7 @@ static int search_fmin(int argc, char** argv) {
         if (fin_cover_create(index.handle(), first_dev, &g_cover, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
     struct DepthOwner { ~DepthOwner() { fin_depth_free(g_depth); g_depth = nullptr; } } depth_owner;
-    if (!depth_file.empty() || !colcov_file.empty() || dh_asked) {   // (the depth histograms share the depth of --unitig-depth / --color-coverage)
+    if (!depth_file.empty() || !colcov_file.empty() || dh_asked || !refdepth_file.empty()) {   // (--ref-depth and the depth histograms share the depth of --unitig-depth / --color-coverage)
         char err[512] = {0};
         if (fin_depth_create(index.handle(), first_dev, &g_depth, err, sizeof err) != FIN_OK) throw runtime_error(err);
     }
@@ -1846,6 +1880,34 @@ static int search_fmin(int argc, char** argv) {
     if (want_pileup) {
         char err[512] = {0};
         if (fin_pileup_create(index.handle(), first_dev, pileup_max_mm, &g_pileup, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    }
+    // the references' paths, before the first chunk of reads, one reference file after another: every record whole, as one sequence (ref, record)
+    struct RefPathsOwner { ~RefPathsOwner() { fin_refpaths_free(g_refpaths); g_refpaths = nullptr; } } refpaths_owner;
+    vector<pair<uint32_t, uint32_t>> ref_ids;
+    if (!ref_paths.empty()) {
+        char err[512] = {0};
+        if (fin_refpaths_create(index.handle(), first_dev, &g_refpaths, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        const uint64_t FLUSH_BASES = 64u << 20;
+        for (size_t r = 0; r < ref_paths.size(); r++) {
+            string bases; vector<uint64_t> offsets{0};
+            auto flush = [&]() {
+                if (offsets.size() > 1 && fin_search_batch_add_refpaths(index.handle(), bases.data(), offsets.data(), offsets.size() - 1, g_refpaths, err, sizeof err) != FIN_OK)
+                    throw runtime_error(ref_paths[r] + ": " + err);
+                bases.clear(); offsets.assign(1, 0);
+            };
+            SeqReader reader(ref_paths[r]);
+            int64_t len;
+            uint32_t record = 0;
+            while ((len = reader.get_next_read_to_buffer()) > 0) {
+                bases.append(reader.read_buf.data(), (size_t)len); offsets.push_back(bases.size());
+                ref_ids.push_back({(uint32_t)r, record++});
+                if (bases.size() >= FLUSH_BASES) flush();
+            }
+            flush();
+        }
+        if (fin_refpaths_n_seqs(g_refpaths) != ref_ids.size()) throw runtime_error("--ref-paths: the paths and the records read do not agree");
+        write_log("Reference paths: " + to_string(ref_ids.size()) + " records of " + to_string(ref_paths.size()) + " files, " + to_string(fin_refpaths_n_segments(g_refpaths)) +
+                  " segments over " + to_string(fin_refpaths_n_slots(g_refpaths)) + " k-mers");
     }
     struct SegOwner { ~SegOwner() { if (g_seg_file) fclose(g_seg_file); g_seg_file = nullptr; } } seg_owner;
     if (!seg_file.empty()) {
@@ -2311,6 +2373,66 @@ static int search_fmin(int argc, char** argv) {
             last_line(text);
             write_file(variants_file, text);
         }
+    }
+    if (!refdepth_file.empty()) {   // the depth along every reference record, lifted on the device after the last chunk
+        char err[512] = {0};
+        const size_t ns = ref_ids.size();
+        vector<uint32_t> nk(ns + 1);
+        vector<uint64_t> wo(ns + 1, 0);
+        if (fin_refpaths_download(g_refpaths, nk.data(), nullptr, nullptr, err, sizeof err) != FIN_OK) throw runtime_error(err);
+        vector<fin_ref_window> win(1);
+        uint64_t n = 0;
+        for (;;) {   // a call that does not fit says how many there are
+            const int rc = fin_refpaths_depth(g_refpaths, g_depth, ref_window, min_depth, wo.data(), win.data(), win.size(), &n, err, sizeof err);
+            if (rc == FIN_OK) break;
+            if (rc != FIN_ELIMIT || n <= win.size()) throw runtime_error(err);
+            win.resize((size_t)n);
+        }
+        ofstream cf(refdepth_file, ios::binary | ios::trunc);
+        string text;
+        for (size_t s = 0; s < ns; s++) {
+            for (uint64_t w = wo[s]; w < wo[s + 1]; w++) {
+                const uint64_t start = (w - wo[s]) * ref_window, end = min<uint64_t>(nk[s], start + ref_window);
+                text += to_string(ref_ids[s].first); text += '\t'; text += to_string(ref_ids[s].second); text += '\t'; text += to_string(start); text += '\t';
+                text += to_string(end); text += '\t'; text += to_string(win[w].in_graph); text += '\t'; text += to_string(win[w].covered); text += '\t';
+                text += to_string(win[w].depth_sum); text += '\n';
+            }
+            if (text.size() >= (8u << 20)) { cf.write(text.data(), (streamsize)text.size()); text.clear(); }
+        }
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + refdepth_file);
+    }
+    if (!refvar_file.empty()) {   // the pileup's candidates under every reference record that crosses them
+        char err[512] = {0};
+        vector<fin_variant> v(1024);
+        uint64_t n = 0;
+        for (;;) {
+            const int rc = fin_pileup_call(g_pileup, min_alt, min_alt_permille, v.data(), v.size(), &n, err, sizeof err);
+            if (rc == FIN_OK) break;
+            if (rc != FIN_ELIMIT || n <= v.size()) throw runtime_error(err);
+            v.resize((size_t)n);
+        }
+        vector<fin_ref_variant> lifted((size_t)(4 * n + 1024));
+        uint64_t m = 0;
+        for (;;) {
+            const int rc = fin_refpaths_lift_variants(g_refpaths, v.data(), n, lifted.data(), lifted.size(), &m, err, sizeof err);
+            if (rc == FIN_OK) break;
+            if (rc != FIN_ELIMIT || m <= lifted.size()) throw runtime_error(err);
+            lifted.resize((size_t)m);
+        }
+        string text;
+        for (uint64_t q = 0; q < m; q++) {
+            const fin_ref_variant& l = lifted[q];
+            const fin_variant& x = v[l.var];
+            const bool rev = l.flags & 1u;
+            text += to_string(ref_ids[l.seq].first); text += '\t'; text += to_string(ref_ids[l.seq].second); text += '\t'; text += to_string((uint64_t)l.pos + 1); text += '\t';
+            text += rev ? '-' : '+'; text += '\t'; text += "ACGT"[(rev ? 3u - x.ref : x.ref) & 3u]; text += '\t'; text += to_string(x.cover);
+            for (int b = 0; b < 4; b++) { text += '\t'; text += to_string(x.alt[rev ? 3 - b : b]); }
+            text += '\t'; text += to_string(x.u); text += '\t'; text += to_string(x.off); text += '\n';
+        }
+        ofstream cf(refvar_file, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + refvar_file);
     }
     if (g_hits && !counts_file.empty()) {   // the profile, after the last chunk: one line per unitig of the index
         char err[512] = {0};

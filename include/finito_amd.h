@@ -576,7 +576,8 @@ int fin_records_cover(const fin_read_record* recs, uint64_t n_reads, const int32
  * buffer, and leaves the difference array as it is: add, download, add, download gives the sum.
  * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi, sums across the ranks of a job (a caller with several GPUs keeps an accumulator per
  * replica and adds the downloaded arrays), the C++ mirror (FinimizerIndex.hh), saturation.  Medians and other quantiles of the depth: fin_depth_histogram and
- * fin_colors_depth_histogram below (DEPTH HISTOGRAMS AND QUANTILES). */
+ * fin_colors_depth_histogram below (DEPTH HISTOGRAMS AND QUANTILES).  The depth along a reference sequence, in windows of its own positions: fin_refpaths_depth
+ * below (REFERENCE COORDINATES). */
 typedef struct fin_depth fin_depth;
 /* a unitig's statistics: the sum of its positions' depths (= fin_hits' count), the greatest, and how many positions have depth >= min_depth */
 typedef struct fin_depth_stat { uint64_t sum; uint32_t max; uint32_t n_at_least; } fin_depth_stat;   /* 16 bytes */
@@ -632,7 +633,8 @@ void fin_depth_free(fin_depth* d);
  * the fast path finished is taken from its 32-byte record and one ASCII base per disagreeing position; a read the pipeline searched is checked for straightness
  * from its pairs and compared with the 2-bit text, 64 bases a row.  fin_pileup_call leaves only the candidate positions to cross PCIe.
  * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi and the distributed driver, the C++ mirror (FinimizerIndex.hh), indels, base
- * qualities, saturation, reads that bridge unitigs. */
+ * qualities, saturation, reads that bridge unitigs.  The candidates in the coordinates of a reference sequence: fin_refpaths_lift_variants below (REFERENCE
+ * COORDINATES). */
 typedef struct fin_pileup fin_pileup;
 /* a called position: unitig and offset, its cover, the text's base code and the four alt counts (alt[ref] == 0) */
 typedef struct fin_variant { uint32_t u, off, cover, ref; uint32_t alt[4]; } fin_variant;   /* 32 bytes */
@@ -1133,6 +1135,81 @@ int fin_records_fragments(const fin_read_record* recs, uint64_t n_reads, const i
  *   out = (double)ref_len + 1.0 - (double)S1(m) / (double)S0(m)      -- kallisto's length minus the truncated mean plus one;
  * if S0(m) == 0 (n_bins == 1 among it) or that value is below 1, out = (double)ref_len.  One division per reference: reproducible bit for bit. */
 int fin_effective_lengths(const uint64_t* hist, uint32_t n_bins, uint32_t bin_width, const uint64_t* ref_len, uint64_t n, double* out);
+
+/* ---- REFERENCE COORDINATES: depth and variant candidates lifted onto the sequences whose paths are known ----
+ * Depth (fin_depth), its histograms and the pileup's candidates (fin_pileup_call) speak in unitig coordinates, an artefact of how the graph was compacted.  A user
+ * works with a place in a reference: record 3 of genome 17, position 1 234 567.  A reference record searched as a read gives its walk through the unitig set as
+ * segments (fin_batch_segments); what follows is the join of such walks with the per-position products, on the device.  Everything is in integers.
+ *  start(u), len(u) and nk(u) = len(u) - k + 1 are FIN_X_ENDS' (start(u) = ends[u - 1], 0 for u = 0).
+ *  A PATH SET holds n_seqs sequences: seq_nk[s], the sequence's number of k-mer slots; seg_offs[n_seqs + 1], CSR offsets; segs[], the canonical segments above with
+ *   `slot` in the sequence's own slots, ordered by sequence, then by slot.  Write n = |len|.  A segment is VALID iff 0 <= u < n_unitigs and n >= 1;
+ *   slot + n <= seq_nk[s]; a sequence's segments ascend and do not overlap; for len > 0: off >= 0 and off + n - 1 < nk(u); for len < 0: off - (n - 1) >= 0 and
+ *   off < nk(u).
+ *  K-MER STARTS.  Slot slot + j, 0 <= j < n, is the k-mer that begins at text position g = start(u) + off + j (len > 0) or g = start(u) + off - j (len < 0).  A slot
+ *   in no segment has no place.  The map is one to one per slot.
+ *  BASES.  For 0 <= i < n + k - 1: sequence base slot + i of a forward segment is text offset off + i of u; of a reverse segment it is text offset off + k - 1 - i,
+ *   read as its complement (the pileup's rule 2).  Consecutive segments of one sequence share up to k - 1 sequence bases; those lie in two places of the text,
+ *   because unitigs overlap, and both places count.
+ *  WINDOW DEPTH takes window >= 1 and min_depth.  Sequence s has ceil(seq_nk[s] / window) windows over its slots, win_offs[n_seqs + 1] delimits them; per window a
+ *   fin_ref_window: in_graph = the window's slots that lie in a segment, depth_sum = the sum of depth[g] over those slots, covered = those with
+ *   depth[g] >= max(min_depth, 1).  window = 1 is the per-position track.
+ *  LIFTED VARIANTS.  Input: fin_variant v[n] as fin_pileup_call writes them -- strictly ascending in g = start(v.u) + v.off, inside the index (v.u < n_unitigs,
+ *   v.off < len(v.u)); anything else is FIN_EINVAL before anything is written.  For a variant at text offset x of unitig u and every segment in u whose BASE interval
+ *   holds x -- forward [off, off + n + k - 2], reverse [off - n + 1, off + k - 1] -- one fin_ref_variant {seq, pos, var, flags}: pos the sequence base, 0-based;
+ *   var the index into v; flags bit 0: the segment is reverse, the bases are to be complemented.  Ordered by segment, then by pos ascending.  The same variant may
+ *   appear under many sequences, unitigs being shared, and twice in one sequence.  FIN_ELIMIT when the records do not fit; *n_out is still the true count.
+ * THE OBJECT, fin_refpaths, lies in HBM beside one replica: the segments, 16 bytes each, and the sequences' offsets.  The kernels (fin_refpaths.hip) do not trust
+ * the segments, which hand-made pairs (fin_batch_set_pairs, fin_batch_set_records) can reach: a segment that is not valid against the index adds nothing, and the
+ * call reports FIN_EINVAL "outside the index" and writes nothing, until fin_refpaths_reset.
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi / dist.py, the C++ mirror, sequence names, indels, chaining segments across a
+ * substitution, lifting the coverage bitmap, a sorted inverse index over the text. */
+typedef struct fin_refpaths fin_refpaths;
+typedef struct fin_ref_window { uint64_t depth_sum; uint32_t in_graph; uint32_t covered; } fin_ref_window;   /* 16 bytes */
+typedef struct fin_ref_variant { uint32_t seq, pos, var, flags; } fin_ref_variant;                          /* 16 bytes */
+/* an empty path set for `idx` on `device` (FIN_ENODEV: the index has no replica there) */
+int fin_refpaths_create(const fin_index* idx, int device, fin_refpaths** out, char* err, size_t errlen);
+/* empties the path set, ordered on the given stream against the appends as fin_hits_reset is against the adds; does not wait */
+int fin_refpaths_reset(fin_refpaths* rp, void* hip_stream);
+void fin_refpaths_free(fin_refpaths* rp);
+uint64_t fin_refpaths_n_seqs(const fin_refpaths* rp);
+uint64_t fin_refpaths_n_segments(const fin_refpaths* rp);
+uint64_t fin_refpaths_n_slots(const fin_refpaths* rp);   /* the sum of seq_nk */
+/* waits for every append and reset issued so far.  seq_nk_out[n_seqs], seg_offs_out[n_seqs + 1], segs_out[n_segments]; each may be NULL */
+int fin_refpaths_download(fin_refpaths* rp, uint32_t* seq_nk_out, uint64_t* seg_offs_out, fin_segment* segs_out, char* err, size_t errlen);
+/* replaces the path set by host arrays, validated on the host against the index's ends first (fin_segments_check): FIN_EINVAL names the first bad segment and
+ * leaves the object as it was */
+int fin_refpaths_upload(fin_refpaths* rp, const uint32_t* seq_nk, const uint64_t* seg_offs, const fin_segment* segs, uint64_t n_seqs, char* err, size_t errlen);
+void* fin_refpaths_device_segments(const fin_refpaths* rp);        /* fin_segment[n_segments] in HBM (valid once the appends on their streams have finished); may be NULL when there are none */
+void* fin_refpaths_device_segment_offsets(fin_refpaths* rp);       /* uint64[n_seqs + 1] in HBM, brought up to date by this call; NULL on failure */
+/* appends the reads of the batch's most recent run as sequences, in read order: makes the segments if the batch has none (fin_batch_segments), copies them device
+ * to device on the given stream behind that run, `slot` values staying the read's own.  UNLIKE fin_batch_add_depth THIS CALL WAITS on the host for the run and
+ * the segment kernels: the batch's seg_offs (8 (n_reads + 1) bytes) are read back, because the sequences' tables live on the host; only the copy of the segments is
+ * left running on the given stream.  Otherwise fin_batch_add_depth's ordering and refusal rules: FIN_EINVAL when the batch
+ * has not run or belongs to another index or device; FIN_ELIMIT for a run whose overflow list overran -- nothing is appended. */
+int fin_batch_add_refpaths(fin_batch* b, fin_refpaths* rp, void* hip_stream, char* err, size_t errlen);
+/* host buffers in through the sub-batch pipeline (merged strands), cut between reads only; the sequences are appended in the order of the reads */
+int fin_search_batch_add_refpaths(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, fin_refpaths* rp, char* err, size_t errlen);
+/* WINDOW DEPTH on the device.  Waits for the adds of both objects through their downloads called with no outputs, so a withheld step or a pair outside the index in
+ * the depth answers with fin_depth_download's code and message.  The scanned depth is materialised in HBM for the call (4 bytes per indexed base, the call's own
+ * allocation, freed on every way out; FIN_ENOMEM otherwise), fin_rp_depth_kernel lifts it, and only the windows come back: win_offs_out[n_seqs + 1] (may be NULL),
+ * out[cap]; *n_windows = how many there are, also when FIN_ELIMIT says they do not fit.  FIN_EINVAL: window 0, objects of different indexes or devices, a segment
+ * "outside the index" (nothing is written).  Neither object is changed. */
+int fin_refpaths_depth(fin_refpaths* rp, fin_depth* depth, uint32_t window, uint32_t min_depth, uint64_t* win_offs_out, fin_ref_window* out, uint64_t cap,
+                       uint64_t* n_windows, char* err, size_t errlen);
+/* LIFTED VARIANTS on the device: vars[n] are checked on the host, uploaded, their places made on the device and looked up by every segment (fin_rp_var_*_kernel).
+ * out[cap], *n_out as above */
+int fin_refpaths_lift_variants(fin_refpaths* rp, const fin_variant* vars, uint64_t n, fin_ref_variant* out, uint64_t cap, uint64_t* n_out, char* err, size_t errlen);
+/* host twins, no device: the definitions above over host arrays, threads over sequences (n_threads <= 0: all cores).  unitig_ends[n_unitigs] as FIN_X_ENDS, depth
+ * uint32[total_len] as fin_depth_download leaves it.  fin_segments_check: FIN_EINVAL and the first bad segment and its clause in err.  The other two check first and
+ * write nothing on a refusal */
+int fin_segments_check(const uint32_t* seq_nk, const uint64_t* seg_offs, const fin_segment* segs, uint64_t n_seqs, int k, const int64_t* unitig_ends,
+                       uint64_t n_unitigs, char* err, size_t errlen);
+int fin_segments_window_depth(const uint32_t* seq_nk, const uint64_t* seg_offs, const fin_segment* segs, uint64_t n_seqs, int k, const int64_t* unitig_ends,
+                              uint64_t n_unitigs, const uint32_t* depth, uint32_t window, uint32_t min_depth, uint64_t* win_offs_out, fin_ref_window* out, uint64_t cap,
+                              uint64_t* n_windows, int n_threads, char* err, size_t errlen);
+int fin_segments_lift_variants(const uint32_t* seq_nk, const uint64_t* seg_offs, const fin_segment* segs, uint64_t n_seqs, int k, const int64_t* unitig_ends,
+                               uint64_t n_unitigs, const fin_variant* vars, uint64_t n, fin_ref_variant* out, uint64_t cap, uint64_t* n_out, int n_threads, char* err,
+                               size_t errlen);
 
 /* ---- ABUNDANCES from the equivalence classes: EM on the device ----
  * The step every consumer of such classes runs next (kallisto's EM, mSWEEP's behind Themisto): split each class's reads over its colours in proportion to the
