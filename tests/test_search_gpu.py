@@ -1302,7 +1302,8 @@ def test_compact_kmer_table_k_mer_by_k_mer(kernel):
     proven by the text.  Asked directly (fin_index_debug_kmer_table), k-mer by k-mer: EVERY k-mer of the unitig text is claimed, with the answer the faithful
     oracle computes for that k-mer searched alone (FinimizerIndex::search on the k-mer: no walk reaches it), and the text at the answer spells it -- or, on a set
     with duplicated stretches, the claim is flagged unverified, the text there spells another k-mer, and the exact side table holds the k-mer with the same answer;
-    k-mers that are in no unitig are not claimed (a claim by a shared tag would fail its proof: the text check)."""
+    k-mers that are in no unitig are not claimed (a claim by a shared tag would fail its proof: the text check -- tests/test_kmer_table_collisions.py constructs such
+    k-mers and feeds them to the search)."""
     if kernel != 4:
         pytest.skip("one pass is enough")
     rng = np.random.default_rng(63)

@@ -799,3 +799,333 @@ def digit_case():
         a.setflags(write=False)
     _DIGIT_CASE = SimpleNamespace(k=k, unitigs=unitigs, ends=ends, reads=reads, nks=nks, recs=recs, stream=stream, pairs=pairs, boundary=boundary)
     return _DIGIT_CASE
+
+
+# ---- constructed colliders of the compact k-mer table (finito_amd/csrc/fin_format.h: FinDevIndex::kt3, fin_kt3_hash) --------------------------------------------
+# The table holds no k-mer: a slot is {answer g, 30-bit tag}, the bucket comes from the hash's high word, and a tag match is a claim that only the text at g proves.
+# fin_mix64 is a bijection and fin_kt3_hash(k0, k1 ...) = fin_mix64(k0 ^ fold(k1 ...)): for a k-mer y, h' = h(y) ^ (d << 30), d = 1, 2, 3, keeps the high word (the
+# bucket, for ANY number of buckets) and the low 30 bits (the tag), and k0' = mix64^-1(h') ^ fold(k1 ...) is the first key word of a k-mer x != y with that hash.
+# Any 64-bit k0' is a k-mer's first word for k >= 32; for k = 31 it must lie below 2^62.  (No control over how far x lies from y: a collider a base or two from
+# its victim -- a sibling -- cannot be made this way.)  tests/test_kmer_table_collisions_host.py holds these restatements against the header itself.
+KT3_FOLD = 0x9E3779B97F4A7C15
+KT3_TAG_BITS = 30
+_MIX_A, _MIX_B = 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+_MIX_A_INV, _MIX_B_INV = pow(_MIX_A, -1, 1 << 64), pow(_MIX_B, -1, 1 << 64)
+
+
+def mix64(x):
+    """fin_mix64 on a Python integer"""
+    x ^= x >> 29; x = (x * _MIX_A) & _M64; x ^= x >> 32; x = (x * _MIX_B) & _M64; x ^= x >> 29
+    return x
+
+
+def unmix64(h):
+    """the inverse of fin_mix64: every step undone in reverse order (x ^= x >> 29 is undone by x ^= x >> 29 ^ x >> 58, x ^= x >> 32 by itself)"""
+    h ^= (h >> 29) ^ (h >> 58); h = (h * _MIX_B_INV) & _M64; h ^= h >> 32; h = (h * _MIX_A_INV) & _M64; h ^= (h >> 29) ^ (h >> 58)
+    return h
+
+
+def kmer_words(s):
+    """the key words of a k-mer: word j = bases 32 j .. 32 j + 31, the first base in the low bits (2-bit codes A0 C1 G2 T3)"""
+    return [string_key(s[a:a + 32]) for a in range(0, len(s), 32)]
+
+
+def words_kmer(words, k):
+    return "".join("ACGT"[(words[j >> 5] >> (2 * (j & 31))) & 3] for j in range(k))
+
+
+def kt3_fold(key, word, j):
+    """fin_kt3_fold: word j >= 1 enters the key as a finaliser of itself plus j times the constant; a word of zeros adds nothing"""
+    return key ^ mix64((word + KT3_FOLD * j) & _M64) if word else key
+
+
+def kt3_key(words):
+    key = words[0]
+    for j in range(1, len(words)):
+        key = kt3_fold(key, words[j], j)
+    return key
+
+
+def kt3_hash(words):
+    """fin_kt3_hash of a k-mer given as its key words (any number of them; one or two: the two-word form of the header)"""
+    return mix64(kt3_key(words))
+
+
+def kt3_bucket(h, n_buckets):
+    """fin_kt3_bucket"""
+    return ((h >> 32) * n_buckets) >> 32
+
+
+def _with_hash(kmer, h):
+    """the k-mer that keeps every key word of `kmer` but the first and hashes to h; None: that first word is no k-mer's (k < 32)"""
+    words = kmer_words(kmer)
+    w0 = unmix64(h) ^ kt3_key(words) ^ words[0]
+    if len(kmer) < 32 and w0 >> (2 * len(kmer)):
+        return None
+    return words_kmer([w0] + words[1:], len(kmer))
+
+
+def colliders_of(kmer):
+    """the valid k-mers (up to three) whose hash differs from this k-mer's in bits 30 and 31 only: the same bucket in a table of any size, the same tag"""
+    h = kt3_hash(kmer_words(kmer))
+    return [x for x in (_with_hash(kmer, h ^ (d << KT3_TAG_BITS)) for d in (1, 2, 3)) if x is not None]
+
+
+def control_of(kmer):
+    """a valid k-mer with this k-mer's high hash word -- its bucket -- and ANOTHER tag: the lowest tag bit flipped; k = 31, where three first words in four are no
+    k-mer's (not below 2^62): the first of the masks 1, 2, 3 ... over the low tag bits that gives one"""
+    h = kt3_hash(kmer_words(kmer))
+    for mask in range(1, 1 << 12):
+        x = _with_hash(kmer, h ^ mask)
+        if x is not None:
+            return x
+    raise AssertionError("no control for %s" % kmer)
+
+
+# The cases of tests/test_kmer_table_collisions.py (device) and tests/test_kmer_table_collisions_host.py (what each presupposes, asserted on the CPU).  A read is
+# a list of parts -- strings, and ("K", k-mer) for a member of a tag group --, reverse-complemented or not: the CONTROL batch is the same reads with every such
+# member replaced by control_of (same bucket, another tag).  A look-up of the walk kernel comes behind probes that passed: a k-mer none of whose strings is in a unitig
+# is settled by the string filters and never reaches the table (measured with bare colliders: kernel 3's list stayed empty in scenario 1 at k = 31, 32 and 100 and
+# in scenario 2 at k = 31, 32, 64 and 100).  So every absent collider AND every control k-mer has all its strings of k - 1 bases in the index (_support; scenario 4:
+# the whole run, with the collider and with its control): both get past the probes to the same bucket, and what the two batches send to kernel 3 differs by the
+# tag alone.  collision_case_problems asserts on the CPU that these strings are in the filters and that the k-mers are absent.
+COLLISION_KS = (31, 32, 63, 64, 100, 127, 200)
+COLLISION_SCENARIOS = {1: "absent collider, verified victim", 2: "where the claimed place lies", 3: "present collider", 4: "runs of absent k-mers whose strings all occur",
+                       5: "unverified victim"}
+_COLLISION_CASES = {}
+
+
+def collision_scenarios(k):
+    return (1, 2, 3) if k == 200 else (1, 2, 3, 4, 5) if k == 31 else (1, 2, 3, 5)
+
+
+def prepass_middle_start(read_len, k):
+    """where the k-mer starts that the fast pre-pass looks at third (fin_prepass.hip, middle_look: the k-mer that ENDS at t = (r_len + k) / 2 - 1)"""
+    return (read_len + k) // 2 - k
+
+
+def render_read(spec, sub=None):
+    parts, rev = spec
+    s = "".join(p if isinstance(p, str) else (sub or {}).get(p[1], p[1]) for p in parts)
+    return rc(s) if rev else s
+
+
+def _placements(rng, g, k, x):
+    """the reads that carry the k-mer x where a look or a look-up meets it: as the first, the last and the pre-pass's middle k-mer (junk around it: that look is made
+    only when the first and the last k-mer of both strands are in no unitig), spliced between two stretches of the genome, alone, and twice; each on both strands.
+    [(kind, spec)]"""
+    def S():
+        n = k + int(rng.integers(3, 40 if k < 40 else 25)); a = int(rng.integers(0, len(g) - n + 1))   # (k <= 64: no read beyond the fast path's 256 bases)
+        return g[a:a + n]
+    m = int(rng.integers(6, 30)); odd = int(rng.integers(0, 2))
+    mid = [random_genome(rng, m), ("K", x), random_genome(rng, m + odd)]
+    assert prepass_middle_start(2 * m + odd + k, k) == m
+    out = [("first", [("K", x), S()]), ("last", [S(), ("K", x)]), ("middle", mid), ("spliced", [S(), ("K", x), S()]), ("whole", [("K", x)]), ("twice", [("K", x), S(), ("K", x)])]
+    return [(kind, (parts, rev)) for kind, parts in out for rev in (False, True)]
+
+
+def _along(rng, k, m, left, right):
+    """reads along the text around a k-mer m that IS in the index (left / right: the bases on its sides there): the whole stretch, from m on, up to m, m alone"""
+    out = [("along", [left, ("K", m), right]), ("first", [("K", m), right]), ("last", [left, ("K", m)]), ("whole", [("K", m)])]
+    return [(kind, (parts, rev)) for kind, parts in out for rev in (False, True)]
+
+
+def _support(rng, k, s):
+    """unitigs of k bases that hold every string of k - 1 bases of s and none of its k-mers: each string goes on with another base than s does -- with C or G, so that
+    in the index's order (by first k-mer, from its last base) none of them becomes the first or the last unitig of the text (scenario 2 needs those for its victims)"""
+    out = []
+    for i in range(len(s) - k + 2):
+        nxt = s[i + k - 1] if i + k - 1 < len(s) else ""
+        ok = [b for b in "CG" if b != nxt]
+        out.append(s[i:i + k - 1] + ok[int(rng.integers(0, len(ok)))])
+    return out
+
+
+def _answers(o, text, ends, k, kmers):
+    """per k-mer: (the text position g the oracle's search of the k-mer alone answers, or -1; does the text spell the k-mer there, inside one unitig)"""
+    starts = np.concatenate([[0], ends[:-1]])
+    out = {}
+    for q in kmers:
+        (u, off), = o.search(q)[0]
+        g = int(starts[u]) + off + k - 1 if u >= 0 else -1
+        out[q] = (g, u >= 0 and off + k <= int(ends[u] - starts[u]) and text[g - k + 1:g + 1] == q)
+    return out
+
+
+def _collision_try(k, scenario, seed):
+    from types import SimpleNamespace
+    from oracle.oracle import OracleIndex
+    rng = np.random.default_rng(seed)
+    g = random_genome(rng, int(rng.integers(3000, 6001)))
+    if scenario == 5:   # duplicated stretches: answers that do not spell their k-mer (tests/test_search_gpu.py::test_compact_kmer_table_k_mer_by_k_mer, cases 2-4)
+        for _ in range(6):
+            a = int(rng.integers(0, len(g) - 300 - k)); n = int(rng.integers(k + 3, k + 300)); at = int(rng.integers(0, len(g)))
+            g = g[:at] + g[a:a + n] + g[at:]
+    base = cut_unitigs(rng, g, k, max_len=max(200, 2 * k + 100))
+    o = OracleIndex.build(base, k)
+    ends = np.asarray(o.ends(), dtype=np.int64); starts = np.concatenate([[0], ends[:-1]]); text = text_of(o.concat())
+    at = kmer_ends(ends, k)
+    n_col = 3 if k >= 32 else 1
+    has = lambda q: len(colliders_of(q)) >= 1
+    where = {}
+    # ---- the victims (k-mers of the text), by scenario
+    if scenario == 2:
+        u = next((u for u in range(1, len(ends) - 1) if has(text[starts[u]:starts[u] + k]) and has(text[ends[u] - k:ends[u]]) and ends[u] - starts[u] > k), None)
+        if u is None:
+            return None
+        where = {"text_first": k - 1, "text_last": len(text) - 1, "unitig_first": int(starts[u]) + k - 1, "unitig_last": int(ends[u]) - 1}
+        if k == 31:   # the claimed place inside one 64-base text window (the walk kernel compares in W_RES4), and across two (W_KFV)
+            one = [int(e) for e in at if ((e - k + 1) & 63) + k <= 64 and has(text[e - k + 1:e + 1]) and e not in where.values()]
+            two = [int(e) for e in at if ((e - k + 1) & 63) + k > 64 and has(text[e - k + 1:e + 1]) and e not in where.values()]
+            if not one or not two:
+                return None
+            where["one_window"] = one[int(rng.integers(0, len(one)))]; where["two_windows"] = two[int(rng.integers(0, len(two)))]
+        victims = [text[e - k + 1:e + 1] for e in where.values()]
+    else:
+        pool = [text[e - k + 1:e + 1] for e in at[rng.permutation(len(at))]]
+        if scenario == 5:
+            ans = _answers(o, text, ends, k, pool)
+            pool = [q for q in pool if not ans[q][1]]
+        pool = [q for q in dict.fromkeys(pool) if has(q)]
+        want = {1: 8 if k >= 32 else 20, 3: 3, 4: 8, 5: 6}[scenario]
+        victims = pool[:want]
+        if len(victims) < want:
+            return None
+    if not all(has(v) for v in victims) or len(set(victims)) < len(victims):
+        return None
+    groups = [(v, colliders_of(v)[:n_col]) for v in victims]
+    # ---- which colliders go into the index, the unitigs that carry them, and the reads
+    extra, present, flanks, runs, reads = [], set(), {}, [], []
+    add = lambda what, specs: reads.extend((what, kind, spec) for kind, spec in specs)
+    if scenario in (1, 2):
+        for v, cs in groups:
+            for x in cs:
+                add("absent", _placements(rng, g, k, x))
+    elif scenario == 3:   # one collider present; (k >= 32) all three present: four entries of one tag in one chain
+        for i, (v, cs) in enumerate(groups):
+            groups[i] = (v, cs if i == 1 else cs[:1])
+            present.update(groups[i][1])
+    elif scenario == 5:   # half the victims meet an absent collider (a miss in the exact side table), half a present one
+        for i, (v, cs) in enumerate(groups):
+            groups[i] = (v, cs[:1])
+            if i % 2:
+                present.add(cs[0])
+            else:
+                add("absent", _placements(rng, g, k, cs[0]))
+    if scenario == 4:   # R = J1 + x + J2: no k-mer of R is in the index, and every string of k - 1 bases of R is (_support, below)
+        for v, cs in groups:
+            x = cs[0]
+            R = random_genome(rng, 3) + x + random_genome(rng, 12)   # (one run per collider; the reads enter it 0 .. 3 bases in front of x)
+            runs.append(R)
+            for n1 in range(4):
+                parts = [R[3 - n1:3], ("K", x), R[3 + k:]]
+                n = k + int(rng.integers(3, 40)); a = int(rng.integers(0, len(g) - n + 1)); b = int(rng.integers(0, len(g) - n + 1))
+                # the run first in the read (x is the epoch's first look-up at n1 = 0, a later one behind n1 absent k-mers), and behind a stretch of the genome
+                add("run", [("run_first", (parts + [g[a:a + n]], rev)) for rev in (False, True)] + [("run_inside", ([g[b:b + n]] + parts + [g[a:a + n]], rev)) for rev in (False, True)])
+    for x in sorted(present):
+        n = int(rng.integers(30, 80)) if k < 100 else int(rng.integers(10, 40))
+        flanks[x] = (random_genome(rng, n), random_genome(rng, n))
+        extra.append(flanks[x][0] + x + flanks[x][1])
+    if present:
+        for v, cs in groups:
+            if any(x in present for x in cs):
+                n = 40 if k < 100 else 25
+                a = g.find(v)
+                if a >= 0:
+                    left, right = g[max(0, a - n):a], g[a + k:a + k + n]
+                else:   # (the victim's unitig went into the set reverse-complemented)
+                    a = g.find(rc(v))
+                    left, right = rc(g[a + k:a + k + n]), rc(g[max(0, a - n):a])
+                add("member", _along(rng, k, v, left, right))
+                for x in cs:
+                    if x in present:
+                        add("member", _along(rng, k, x, *flanks[x]))
+    members = list(dict.fromkeys(p[1] for _, _, spec in reads for p in spec[0] if not isinstance(p, str)))
+    control = {m: control_of(m) for m in members}
+    # what must get past the probes without being in the index: the absent colliders and the control k-mers (scenario 4: the runs, with either)
+    victims_set = {v for v, _ in groups}
+    supported = [m for m in members if m not in present and m not in victims_set] + list(control.values())
+    if scenario == 4:
+        supported = runs + [R.replace(cs[0], control[cs[0]]) for R, (v, cs) in zip(runs, groups)]
+    for s_ in supported:
+        extra += _support(rng, k, s_)
+    unitigs = base + extra
+    if extra:
+        order = rng.permutation(len(unitigs)); unitigs = [unitigs[i] for i in order]
+        o = OracleIndex.build(unitigs, k)
+        ends = np.asarray(o.ends(), dtype=np.int64); text = text_of(o.concat())
+        where = {name: text.find(v) + k - 1 for name, (v, _) in zip(where, groups)}   # (the new unitigs have their places in the index's order: the victims have moved)
+    c = SimpleNamespace(k=k, scenario=scenario, seed=seed, genome=g, unitigs=tuple(unitigs), oracle=o, text=text, ends=ends, groups=groups, present=present, where=where,
+                        flanks=flanks, runs=runs, supported=supported, control=control, kinds=[(what, kind, spec[1]) for what, kind, spec in reads], reads=[render_read(spec) for _, _, spec in reads],
+                        control_reads=[render_read(spec, control) for _, _, spec in reads])
+    c.answers = _answers(o, text, ends, k, [v for v, _ in groups] + [x for _, cs in groups for x in cs] + list(control.values()))
+    if collision_case_problems(c):
+        return None
+    c.first_reads = [i for i, (what, kind, rev) in enumerate(c.kinds) if what == "absent" and kind == "first" and not rev]
+    c.expected = {}
+    for name, rd in (("reads", c.reads), ("control", c.control_reads)):
+        merged = o.search_batch(rd)[0]
+        fwd = np.array([x for r in rd for x in o.search(r)[0]], dtype=np.int64).reshape(-1, 2)
+        merged.setflags(write=False); fwd.setflags(write=False)
+        c.expected[name] = (merged, fwd)
+    return c
+
+
+def collision_case_problems(c):
+    """what a case presupposes, on the CPU: every victim is in the text and answered as its scenario says (verified at its own place; scenario 5: at a place that does
+    not spell it), a present collider is found at its own place, an absent collider and every control k-mer is found on neither strand; and of
+    everything that must get past the probes -- absent colliders, control k-mers, scenario 4's runs with either -- no k-mer is in the index and every string of the
+    filters' length is in a unitig.  Returns the list of what does not hold"""
+    k, bad = c.k, []
+    for v, cs in c.groups:
+        g, spelled = c.answers[v]
+        if g < 0 or spelled != (c.scenario != 5):
+            bad.append(("victim", v, g, spelled))
+        for x in cs:
+            h, hv = kt3_hash(kmer_words(x)), kt3_hash(kmer_words(v))
+            if x == v or (h ^ hv) & ~(3 << KT3_TAG_BITS):
+                bad.append(("not a collider", v, x))
+            gx, sx = c.answers[x]
+            if x in c.present and not (gx >= 0 and sx):
+                bad.append(("present collider", x, gx, sx))
+            if x not in c.present and (gx >= 0 or c.oracle.search(rc(x))[0][0][0] >= 0):
+                bad.append(("absent collider", x, gx))
+    for m, q in c.control.items():
+        hm, hq = kt3_hash(kmer_words(m)), kt3_hash(kmer_words(q))
+        if hm >> 32 != hq >> 32 or not (hm ^ hq) & ((1 << KT3_TAG_BITS) - 1) or c.answers[q][0] >= 0 or c.oracle.search(rc(q))[0][0][0] >= 0:
+            bad.append(("control", m, q))
+    for name, e in c.where.items():
+        v = c.groups[list(c.where).index(name)][0]
+        if c.answers[v][0] != e or c.text[e - k + 1:e + 1] != v:
+            bad.append(("place", name, e))
+    if c.scenario == 2:
+        w, starts = c.where, [0] + [int(e) for e in c.ends[:-1]]
+        if w["text_first"] != k - 1 or w["text_last"] != len(c.text) - 1 or w["unitig_first"] - k + 1 not in starts[1:] or w["unitig_last"] + 1 not in [int(e) for e in c.ends[:-1]]:
+            bad.append(("scenario 2's places", dict(w)))
+        if k == 31 and not ((w["one_window"] - k + 1) & 63) + k <= 64 < ((w["two_windows"] - k + 1) & 63) + k:
+            bad.append(("scenario 2's windows", dict(w)))
+    m = default_cbf_m(k)
+    strings = {c.text[e - m + 1:e + 1] for e in string_keys(c.oracle.concat(), c.ends, m)[2]}
+    absent = [x for _, cs in c.groups for x in cs if x not in c.present] + list(c.control.values())
+    if not set(absent) <= {R[i:i + k] for R in c.supported for i in range(len(R) - k + 1)}:
+        bad.append(("an absent collider or a control k-mer without its strings in the index",))
+    for R in c.supported:
+        if any(R[i:i + m] not in strings for i in range(len(R) - m + 1)):
+            bad.append(("a string is in no unitig", R))
+        if any(u >= 0 for u, _ in c.oracle.search_merged(R)):
+            bad.append(("a k-mer is in the index", R))
+    return bad
+
+
+def collision_case(k, scenario):
+    """the one case of (k, scenario), made once and shared; nobody changes it.  Deterministic: the first seed of a fixed sequence whose draw has what the scenario
+    presupposes (at k = 31 only some 55 % of the k-mers have a collider at all; a collider's unitig may disturb a neighbour's answer)"""
+    if (k, scenario) not in _COLLISION_CASES:
+        assert scenario in collision_scenarios(k)
+        for t in range(60):
+            c = _collision_try(k, scenario, 31000 + 1000 * scenario + 10 * k + 100000 * t)
+            if c is not None:
+                break
+        assert c is not None, "no seed gives the case k=%d scenario %d" % (k, scenario)
+        _COLLISION_CASES[(k, scenario)] = c
+    return _COLLISION_CASES[(k, scenario)]
