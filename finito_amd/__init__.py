@@ -324,6 +324,20 @@ def lib():
         L.fin_search_batch_add_fragments.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
         L.fin_search_batch_fragments.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
         L.fin_records_fragments.argtypes = [vp, u64, vp, u64, C.c_int, i64p, u64, u32, u32, vp, vp, vp, C.c_int]
+        L.fin_link_hash.argtypes = [u64]
+        L.fin_link_hash.restype = u64
+        L.fin_links_create.argtypes = [vp, C.c_int, u64, C.POINTER(vp), cp, C.c_size_t]
+        L.fin_links_reset.argtypes = [vp, vp]
+        L.fin_links_free.argtypes = [vp]
+        L.fin_links_free.restype = None
+        L.fin_batch_add_links.argtypes = [vp, vp, vp, cp, C.c_size_t]
+        L.fin_links_download.argtypes = [vp, u64, vp, u64, u64p, vp, cp, C.c_size_t]
+        L.fin_links_device_table.argtypes = [vp]
+        L.fin_links_device_table.restype = vp
+        L.fin_links_capacity.argtypes = [vp]
+        L.fin_links_capacity.restype = u64
+        L.fin_search_batch_add_links.argtypes = [vp, cp, u64p, u64, C.c_int, vp, cp, C.c_size_t]
+        L.fin_records_links.argtypes = [vp, u64, vp, u64, C.c_int, i64p, u64, u64, vp, u64, u64p, vp, C.c_int]
         L.fin_refpaths_create.argtypes = [vp, C.c_int, C.POINTER(vp), cp, C.c_size_t]
         L.fin_refpaths_reset.argtypes = [vp, vp]
         L.fin_refpaths_free.argtypes = [vp]
@@ -1874,6 +1888,123 @@ class Fragments(_Accumulator):
         return int(self.L.fin_fragments_device_hist(self.h) or 0)
 
 
+FIN_LINKS_MAX = 1 << 28
+LINK_DTYPE = np.dtype([("u_a", np.uint32), ("off_a", np.uint32), ("u_b", np.uint32), ("off_b", np.uint32), ("count", np.uint64)])   # fin_link
+LINK_EDGE_DTYPE = np.dtype([("u_a", np.uint32), ("end_a", "S1"), ("u_b", np.uint32), ("end_b", "S1"), ("count", np.uint64)])
+_M64 = (1 << 64) - 1
+
+
+def link_hash(key):
+    """the link table's hash (fin_link_hash of the C ABI, restated here): a key's home slot is link_hash(key) & (cap - 1)"""
+    x = int(key) & _M64
+    x ^= x >> 30; x = (x * 0xBF58476D1CE4E5B9) & _M64
+    x ^= x >> 27; x = (x * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def _links_canonical(links):
+    """LINK_DTYPE in the canonical order: ascending by (g_a, g_b), which is ascending by (u_a, off_a, u_b, off_b)"""
+    links = np.ascontiguousarray(links, dtype=LINK_DTYPE).reshape(-1)
+    return links[np.lexsort((links["off_b"], links["u_b"], links["off_a"], links["u_a"]))]
+
+
+class UnitigEdges:
+    """LinkTable.unitig_edges' result: `edges`, LINK_EDGE_DTYPE ascending by (u_a, end_a, u_b, end_b) with the counts summed; n_edge, the transitions along edges
+    of the graph (both ends S, E or B); n_jump, those with an interior end"""
+    def __init__(self, edges, n_edge, n_jump):
+        self.edges, self.n_edge, self.n_jump = edges, int(n_edge), int(n_jump)
+
+
+class LinkTable:
+    """a downloaded link table (include/finito_amd.h: LINKS): `links`, LINK_DTYPE in the canonical order -- the a end is the lower place --; `transitions`, how many
+    were counted; `n_distinct`, the distinct links of the whole table; `n_self`, those of them whose two places are equal"""
+    def __init__(self, links, transitions, n_distinct, n_self):
+        self.links, self.transitions, self.n_distinct, self.n_self = links, int(transitions), int(n_distinct), int(n_self)
+
+    def unitig_edges(self, ends, k):
+        """host: every end of every link classed by where it lies in its unitig -- S: offset 0, E: the last k-mer, B: both (a unitig of one k-mer), I: the
+        interior -- and the counts summed per (u_a, end_a, u_b, end_b).  A link between S / E / B ends walks an edge of the graph; one with an I end is a jump
+        that the indexed sequences do not make there.  UnitigEdges"""
+        e = np.ascontiguousarray(ends, dtype=np.int64).reshape(-1)
+        last = np.diff(np.concatenate([[0], e])) - int(k)   # the offset of a unitig's last k-mer
+        lk = self.links
+
+        def cls(u, off):
+            o, l = off.astype(np.int64), last[u]
+            c = np.full(len(u), b"I", dtype="S1")
+            c[o == 0] = b"S"
+            c[o == l] = b"E"
+            c[(o == 0) & (l == 0)] = b"B"
+            return c
+        if len(lk) and int(max(lk["u_a"].max(), lk["u_b"].max())) >= len(e):
+            raise FinitoError(FIN_EINVAL, "unitig_edges: a link names a unitig beyond `ends`")
+        ca, cb = cls(lk["u_a"], lk["off_a"]), cls(lk["u_b"], lk["off_b"])
+        sums = {}
+        for ua, a, ub, b, c in zip(lk["u_a"].tolist(), ca.tolist(), lk["u_b"].tolist(), cb.tolist(), lk["count"].tolist()):
+            sums[(ua, a, ub, b)] = sums.get((ua, a, ub, b), 0) + c
+        edges = np.zeros(len(sums), dtype=LINK_EDGE_DTYPE)
+        for i, key in enumerate(sorted(sums)):
+            edges[i] = key + (sums[key],)
+        jump = (edges["end_a"] == b"I") | (edges["end_b"] == b"I")
+        return UnitigEdges(edges, edges["count"][~jump].sum(), edges["count"][jump].sum())
+
+
+def links_merge(a, b):
+    """host: two downloaded LinkTables added -- same keys, counts summed, canonical order.  How the tables of several ranks or runs combine.  n_distinct and n_self
+    are those of the merged rows: exact when both tables were downloaded with min_count 1"""
+    la, lb = _links_canonical(a.links), _links_canonical(b.links)
+    both = np.concatenate([la, lb])
+    keys = np.stack([both["u_a"], both["off_a"], both["u_b"], both["off_b"]], axis=1).astype(np.uint32)
+    uniq, inv = np.unique(keys, axis=0, return_inverse=True) if len(keys) else (keys, np.zeros(0, dtype=np.int64))
+    out = np.zeros(len(uniq), dtype=LINK_DTYPE)
+    if len(uniq):
+        out["u_a"], out["off_a"], out["u_b"], out["off_b"] = uniq[:, 0], uniq[:, 1], uniq[:, 2], uniq[:, 3]
+        np.add.at(out["count"], np.asarray(inv).reshape(-1), both["count"])
+    out = _links_canonical(out)
+    n_self = int(((out["u_a"] == out["u_b"]) & (out["off_a"] == out["off_b"])).sum())
+    return LinkTable(out, a.transitions + b.transitions, len(out), n_self)
+
+
+class Links(_Accumulator):
+    """the junctions reads cross, counted in a hash table resident in HBM beside one replica of the index: which edges of the unitig graph a sample walked, and
+    how often (fin_links_* of the C ABI; include/finito_amd.h: LINKS).  The table holds up to max_links distinct links and does not grow"""
+    _FREE, _RESET = "fin_links_free", "fin_links_reset"
+
+    def __init__(self, index, device=0, max_links=1 << 20):
+        self.index = index
+        self.max_links = int(max_links)
+        if not 0 <= self.max_links < (1 << 64):
+            raise FinitoError(FIN_ELIMIT, "Links: max_links is 1 .. 2^28")
+        self._create("fin_links_create", index.h, int(device), self.max_links)
+        self.capacity = int(self.L.fin_links_capacity(self.h))
+
+    def add(self, batch, stream=None):
+        """table += the transitions of the batch's most recent run, on a HIP stream, behind that run; no sync (fin_batch_add_links).  Adding the same run twice
+        counts it twice."""
+        return _acc_add(self, "fin_batch_add_links", batch, stream)
+
+    def add_reads(self, reads, strands=FIN_MERGED):
+        """search a read set from host buffers, sub-batches pipelined as in search_reads, and add its transitions; nothing comes back (fin_search_batch_add_links)"""
+        return _acc_add_reads(self, "fin_search_batch_add_links", reads, strands)
+
+    def download(self, min_count=1):
+        """LinkTable of the links with count >= max(min_count, 1), filtered, compacted and decoded on the device; waits for the adds and leaves the accumulator as
+        it is (fin_links_download)"""
+        mc = int(min_count)
+        if not 0 <= mc < (1 << 64):
+            raise FinitoError(FIN_EINVAL, "Links.download: min_count is an unsigned 64-bit number")
+        n, err = C.c_uint64(0), C.create_string_buffer(512)
+        _check(self.L.fin_links_download(self.h, mc, None, 0, C.byref(n), None, err, 512), err)
+        links = np.zeros(max(int(n.value), 1), dtype=LINK_DTYPE)
+        counters = np.zeros(4, dtype=np.uint64)
+        _check(self.L.fin_links_download(self.h, mc, links.ctypes.data_as(C.c_void_p), len(links), C.byref(n), counters.ctypes.data_as(C.c_void_p), err, 512), err)
+        return LinkTable(links[: int(n.value)], counters[0], counters[1], counters[3])
+
+    def device_ptr(self):
+        """`capacity` slots of {uint64 key, uint64 count}, then uint64 n_distinct, in HBM"""
+        return int(self.L.fin_links_device_table(self.h) or 0)
+
+
 def _window_args(what, window, min_depth):
     w, md = int(window), int(min_depth)
     if not 1 <= w <= 0xFFFFFFFF:
@@ -2390,6 +2521,10 @@ class FinimizerIndex:
     def fragments(self, n_bins=1024, bin_width=1, device=0):
         """a zeroed fragment-length histogram with its class counters beside the replica on `device` (Fragments)"""
         return Fragments(self, device, n_bins, bin_width)
+
+    def links(self, max_links=1 << 20, device=0):
+        """an empty link table for up to max_links distinct links beside the replica on `device` (Links)"""
+        return Links(self, device, max_links)
 
     def ref_paths(self, device=0):
         """an empty path set beside the replica on `device` (RefPaths)"""
@@ -2976,6 +3111,27 @@ def records_fragments(recs, stream, k, ends, n_bins=1024, bin_width=1, n_threads
         raise FinitoError(rc, "fin_records_fragments: an odd number of reads, n_bins outside 1 .. %d, bin_width 0, a unitig number outside the index, a k-mer that does "
                               "not lie inside its unitig, or records and stream that do not belong together" % FIN_FRAG_MAX_BINS)
     return frags[:nf], hist, counters
+
+
+def records_links(recs, stream, k, ends, min_count=1, n_threads=0):
+    """host: the LinkTable of records + stream (fin_records_links) -- the CPU statement of Links, read off every read's expanded slots"""
+    r = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+    st = np.ascontiguousarray(stream, dtype=np.int32).reshape(-1, 2)
+    e = np.ascontiguousarray(ends, dtype=np.int64).reshape(-1)
+    mc = int(min_count)
+    if not 0 <= mc < (1 << 64):
+        raise FinitoError(FIN_EINVAL, "records_links: min_count is an unsigned 64-bit number")
+    n = C.c_uint64(0)
+    counters = np.zeros(4, dtype=np.uint64)
+    args = (r.ctypes.data_as(C.c_void_p), len(r), st.ctypes.data_as(C.c_void_p), len(st), int(k), e.ctypes.data_as(C.POINTER(C.c_int64)), len(e), mc)
+    rc = lib().fin_records_links(*args, None, 0, C.byref(n), None, int(n_threads))
+    links = np.zeros(max(int(n.value), 1), dtype=LINK_DTYPE)
+    if rc == 0:
+        rc = lib().fin_records_links(*args, links.ctypes.data_as(C.c_void_p), len(links), C.byref(n), counters.ctypes.data_as(C.c_void_p), int(n_threads))
+    if rc != 0:
+        raise FinitoError(rc, "fin_records_links: a transition with an end outside the index, a record kind above 2, unitig ends that descend or reach 2^32, or "
+                              "records and stream that do not belong together")
+    return LinkTable(links[: int(n.value)], counters[0], counters[1], counters[3])
 
 
 def _twin_ends(ends):

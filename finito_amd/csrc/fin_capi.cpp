@@ -18,6 +18,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -3726,6 +3727,106 @@ int fin_batch_download_fragments(fin_batch* b, fin_fragment* out, char* err, siz
     return FIN_OK;
 }
 
+// ---- links: the junctions reads cross (fin_links.hip) --------------------------------------------------------------------------------------
+struct fin_links : fin_acc {
+    uint64_t n_unitigs = 0, total_len = 0, max_links = 0;
+    uint32_t cap = 0;                     // slots: a power of two, 4 .. 2^29
+    const uint32_t* d_ends = nullptr;     // the replica's ends_p
+    void* d_tab = nullptr;                // cap slots of {u64 key, u64 count}, then the trailer: u64 n_distinct, the flag word (fin_launch_links_add)
+};
+static_assert(sizeof(fin_link) == 24, "fin_link is 24 bytes on both sides");
+static uint64_t* links_ctr(const fin_links* l) { return (uint64_t*)l->d_tab + 2 * (size_t)l->cap; }
+static size_t links_bytes(const fin_links* l) { return (size_t)l->cap * 16 + FIN_LINKS_TRAILER; }
+
+void fin_links_free(fin_links* l) {
+    if (!acc_free_open(l)) return;
+    (void)hipFree(l->d_tab);
+    delete l;
+}
+
+int fin_links_create(const fin_index* idx, int device, uint64_t max_links, fin_links** out, char* err, size_t errlen) {
+    if (!idx || !out) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *out = nullptr;
+    if (max_links == 0 || max_links > FIN_LINKS_MAX) { set_err(err, errlen, "max_links is 1 .. 2^28"); return FIN_ELIMIT; }
+    const fin_index::Replica* rep = nullptr;
+    if (const int orc = acc_create_open(idx, device, &rep, err, errlen)) return orc;
+    fin_links* l = acc_new<fin_links>(idx, device, err, errlen);
+    if (!l) return FIN_ENOMEM;
+    l->n_unitigs = idx->n_unitigs; l->total_len = idx->total_len; l->max_links = max_links; l->d_ends = rep->dev.ends;
+    l->cap = 4;
+    while ((uint64_t)l->cap < 2 * max_links) l->cap <<= 1;
+    if (hipMalloc(&l->d_tab, links_bytes(l)) != hipSuccess) { (void)hipGetLastError(); delete l; set_err(err, errlen, "out of device memory (table of links)"); return FIN_ENOMEM; }
+    const int rc = fin_launch_links_clear(l->d_tab, l->cap, nullptr);
+    if (rc != 0 || hipStreamSynchronize(nullptr) != hipSuccess) { (void)hipGetLastError(); fin_links_free(l); set_err(err, errlen, "links clear kernel failed"); return FIN_ENODEV; }
+    *out = l;
+    return FIN_OK;
+}
+
+// the empty key is all ones, so the reset is a small kernel, not a memset: ordered as a reset is (AccPending::reform)
+int fin_links_reset(fin_links* l, void* hip_stream) {
+    if (!l) return FIN_EINVAL;
+    if (hipSetDevice(l->device) != hipSuccess) return FIN_ENODEV;
+    hipStream_t st = (hipStream_t)hip_stream;
+    return l->pend.reform(st, [&]() -> int { return fin_launch_links_clear(l->d_tab, l->cap, st) == 0 ? FIN_OK : FIN_ENODEV; }, nullptr, 0);
+}
+
+void* fin_links_device_table(const fin_links* l) { return l ? l->d_tab : nullptr; }
+uint64_t fin_links_capacity(const fin_links* l) { return l ? l->cap : 0; }
+
+int fin_batch_add_links(fin_batch* b, fin_links* l, void* hip_stream, char* err, size_t errlen) {
+    if (!b || !l) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (const int orc = acc_add_open(b, l, st, err, errlen)) return orc;
+    int rc = 0;
+    if (l->n_unitigs != 0 && l->total_len != 0 && b->n_kmers != 0)
+        rc = fin_launch_links_add(b->last_frec ? b->d_frec : nullptr, (const uint64_t*)b->d_out_offs, b->d_out, (uint32_t)b->n_reads, l->d_ends, (uint32_t)l->n_unitigs,
+                                  l->total_len, l->d_tab, l->cap, l->max_links, b->d_ovf_count, b->last_ovf_cap, st);
+    return acc_add_close(l, st, rc, "links kernel: ", err, errlen);
+}
+
+int fin_links_download(fin_links* l, uint64_t min_count, fin_link* links_out, uint64_t cap_out, uint64_t* n_links, uint64_t counters_out[4], char* err, size_t errlen) {
+    if (!l || !n_links) { set_err(err, errlen, "null argument"); return FIN_EINVAL; }
+    *n_links = 0;
+    if (const int orc = acc_download_open(l, nullptr, nullptr, nullptr, err, errlen)) return orc;
+    uint64_t trailer[2] = {0, 0};   // n_distinct, the flag word
+    HIPCHK(hipMemcpy(trailer, links_ctr(l), sizeof trailer, hipMemcpyDeviceToHost));
+    const uint32_t flags = (uint32_t)trailer[1];
+    if (flags & 1u) { set_err(err, errlen, PILEUP_WITHHELD); return FIN_ELIMIT; }
+    if (flags & 2u) { set_err(err, errlen, "a transition with a unitig number or a place outside the index was met (not counted; reset the accumulator)"); return FIN_EINVAL; }
+    if ((flags & 4u) || trailer[0] > l->max_links) { set_err(err, errlen, "more than max_links distinct links (max_links = " + std::to_string(l->max_links) + "; reset the accumulator)"); return FIN_ELIMIT; }
+    if (min_count == 0) min_count = 1;
+    // compaction on the device: the slots to keep counted per block, scanned, written as fin_link into a dense list -- the table itself never crosses PCIe
+    const uint32_t nb = fin_links_blocks(l->cap);
+    void* d_tmp = nullptr; void* d_dense = nullptr;
+    const size_t off_bytes = (size_t)nb * 8 + 24, sum_bytes = (size_t)nb * 4;   // blk_off | total | stats[2] | blk_sum
+    if (hipMalloc(&d_tmp, off_bytes + sum_bytes) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "out of device memory (compaction of the links)"); return FIN_ENOMEM; }
+    uint64_t* const d_off = (uint64_t*)d_tmp; uint64_t* const d_total = d_off + nb; uint32_t* const d_sum = (uint32_t*)((char*)d_tmp + off_bytes);
+    hipError_t he = hipMemsetAsync(d_total, 0, 24, nullptr);
+    if (he == hipSuccess) he = (hipError_t)fin_launch_links_count(l->d_tab, l->cap, min_count, d_sum, d_off, d_total, d_total + 1, nullptr);
+    uint64_t res[3] = {0, 0, 0};   // kept, the sum of the counts, self links
+    if (he == hipSuccess) he = hipMemcpy(res, d_total, sizeof res, hipMemcpyDeviceToHost);
+    const uint64_t total = res[0];
+    std::vector<fin_link> links;
+    if (he == hipSuccess && links_out && total && total <= cap_out && l->n_unitigs) {
+        links.resize((size_t)total);
+        he = hipMalloc(&d_dense, (size_t)total * sizeof(fin_link));
+        if (he == hipSuccess) he = (hipError_t)fin_launch_links_write(l->d_tab, l->cap, min_count, d_off, l->d_ends, (uint32_t)l->n_unitigs, d_dense, nullptr);
+        if (he == hipSuccess) he = hipMemcpy(links.data(), d_dense, (size_t)total * sizeof(fin_link), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_tmp); (void)hipFree(d_dense);
+    if (he != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, std::string("compaction of the links: ") + hipGetErrorString(he)); return FIN_ENODEV; }
+    *n_links = total;
+    if (counters_out) { counters_out[0] = res[1]; counters_out[1] = trailer[0]; counters_out[2] = total; counters_out[3] = res[2]; }
+    if (!links_out) return FIN_OK;
+    if (total > cap_out) { set_err(err, errlen, "room for " + std::to_string(cap_out) + " links, " + std::to_string(total) + " needed"); return FIN_ELIMIT; }
+    // the canonical order, ascending by (g_a, g_b): places ascend with (u, off)
+    std::sort(links.begin(), links.end(), [](const fin_link& x, const fin_link& y) {
+        return std::make_tuple(x.u_a, x.off_a, x.u_b, x.off_b) < std::make_tuple(y.u_a, y.off_a, y.u_b, y.off_b);
+    });
+    if (total) memcpy(links_out, links.data(), (size_t)total * sizeof(fin_link));
+    return FIN_OK;
+}
+
 int fin_batch_step_time(const fin_batch* b, uint64_t skip_first, double ms_parts[5], uint64_t* n_runs) {
     if (!b) return FIN_EINVAL;
     double t[5] = {0, 0, 0, 0, 0}; uint64_t n = 0;
@@ -4420,6 +4521,15 @@ int fin_search_batch_fragments(const fin_index* idx, const char* bases, const ui
         if (const int rc = fin_batch_fragments(b, nullptr, e, elen)) return rc;
         return fin_batch_download_fragments(b, frags_out + s.lo / 2, e, elen);
     };
+    return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
+}
+
+int fin_search_batch_add_links(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_links* l, char* err, size_t errlen) {
+    int device = -1;
+    if (const int orc = search_open(idx, offsets, strands, l, l, OTHER_ACC, &device, err, errlen)) return orc;
+    if (n_reads == 0) return FIN_OK;
+    Product p;   // (no sub-batch cuts a read: nothing is lost between them)
+    p.take = [&](fin_batch* b, const SubBatch&, uint64_t&, char* e, size_t elen) -> int { return fin_batch_add_links(b, l, own(b), e, elen); };
     return search_product(idx, device, bases, offsets, n_reads, strands, p, nullptr, err, errlen);
 }
 

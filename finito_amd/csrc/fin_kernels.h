@@ -210,6 +210,20 @@ int fin_launch_pseudoalign_paired(const void* frec, const uint64_t* out_offs, co
 int fin_launch_fragments(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_frags, uint32_t k, const uint32_t* ends_p, uint32_t n_unitigs,
                          uint32_t n_bins, uint32_t bin_width, void* frags, void* hist, void* counters, uint32_t* flags, const uint32_t* ovf_count, uint32_t ovf_cap,
                          hipStream_t stream);
+// fin_links.hip -- the LINKS of a step (include/finito_amd.h: LINKS).  tab: cap slots of {u64 key, u64 count}, cap a power of two >= 4, then the
+// trailer u64 n_distinct | u32 flags | u32 0 (FIN_LINKS_TRAILER bytes).  fin_launch_links_clear empties all of it; fin_launch_links_add inserts the step's
+// transitions (a lane per read; only kind-0 reads are scanned); ends_p: the replica's unitig bounds
+#define FIN_LINKS_TRAILER 16u
+int fin_launch_links_clear(void* tab, uint32_t cap, hipStream_t stream);
+int fin_launch_links_add(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, const uint32_t* ends_p, uint32_t n_unitigs, uint64_t total_len,
+                         void* tab, uint32_t cap, uint64_t max_links, const uint32_t* ovf_count, uint32_t ovf_cap, hipStream_t stream);
+// the download's passes on the table as it stands.  Count: blk_sum[fin_links_blocks(cap)] = the slots per block of 256 with count >= min_count (>= 1), blk_off and
+// *total their exclusive prefix and sum (fin_launch_blk_scan), stats u64[2] += {the sum of all counts, the occupied slots whose two places are equal} (zeroed
+// by the caller).  Write: out[d] = the d-th such slot as fin_link, in slot order, its ends found by binary search in ends_p
+uint32_t fin_links_blocks(uint32_t cap);
+int fin_launch_links_count(const void* tab, uint32_t cap, uint64_t min_count, uint32_t* blk_sum, uint64_t* blk_off, uint64_t* total, uint64_t* stats, hipStream_t stream);
+int fin_launch_links_write(const void* tab, uint32_t cap, uint64_t min_count, const uint64_t* blk_off, const uint32_t* ends_p, uint32_t n_unitigs, void* out,
+                           hipStream_t stream);
 // ... over a COMPACT matrix (fin_colorsets.hip's state): sets uint64[(n_sets + 1) * W] with row 0 empty, set_of uint32[n_unitigs], each <= n_sets.  A unitig number
 // becomes its set id as it is loaded, the register table is keyed by set id; the results are those of the dense launch over the expanded matrix, bit for bit
 int fin_launch_pseudoalign_sets(const void* frec, const uint64_t* out_offs, const void* pairs, uint32_t n_reads, uint32_t k, const void* sets, uint32_t W, uint32_t n_sets,

@@ -610,6 +610,12 @@ static const char* SEARCH_HELP =
     "      --ref-variants FILE  with --ref-paths: the pileup's candidates (--min-alt, --min-alt-permille, --pileup-max-mismatch) under every record that\n"
     "                        crosses them: ref<TAB>record<TAB>pos<TAB>+|-<TAB>ref_base<TAB>cover<TAB>A<TAB>C<TAB>G<TAB>T<TAB>unitig<TAB>offset, pos 1-based, bases and counts\n"
     "                        in the record's orientation\n"
+    "      --links FILE      also write the junctions the reads crossed, counted on the GPU (include/finito_amd.h: LINKS): after the last chunk one line\n"
+    "                        unitig_a<TAB>offset_a<TAB>unitig_b<TAB>offset_b<TAB>count per link, ascending by place, the a end the lower place; then\n"
+    "                        #transitions<TAB>T, #links<TAB>D (distinct links), #self<TAB>S. Goes with -o, --no-text 1 and the per-unitig outputs.\n"
+    "                        Not for a partitioned index.\n"
+    "      --max-links N     the most distinct links the table of --links holds (default: 1048576; 1 to 268435456); the run fails beyond it\n"
+    "      --links-min-count C  write only the links crossed at least C times (default: 1)\n"
     "      --no-text arg     1 (only with --unitig-counts, --unitig-coverage, --unitig-depth, --segments, --read-summary, --screen, --classify,\n"
     "                        --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report or --abundance): do not make or write the pair\n"
     "                        text, the other results asked for are the only ones\n"
@@ -792,6 +798,12 @@ static fin_depth* g_depth = nullptr;
 static void add_depth_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
     char err[512] = {0};
     if (fin_search_batch_add_depth(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_depth, err, sizeof err) != FIN_OK) throw runtime_error(err);
+}
+// --links FILE: the same for the junctions the reads cross (fin_search_batch_add_links)
+static fin_links* g_links = nullptr;
+static void add_links_chunk(const FinimizerIndex& index, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
+    char err[512] = {0};
+    if (fin_search_batch_add_links(index.handle(), bases, offsets, n_reads, FIN_MERGED, g_links, err, sizeof err) != FIN_OK) throw runtime_error(err);
 }
 // --pileup FILE / --variants FILE: the same for the base pileup (fin_search_batch_add_pileup)
 static fin_pileup* g_pileup = nullptr;
@@ -1356,6 +1368,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_depth) add_depth_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_links) add_links_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_pileup) add_pileup_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_seg_file) c->positive = segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                         if (g_rs_file) c->positive = read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
@@ -1382,6 +1395,7 @@ static int64_t run_fmin_queries_streaming(SeqReader* reader, BlockReader* breade
                         if (g_hits) index.add_unitig_hits(c->bases.get(0), c->offsets.data(), n_reads, g_hits);   // (a second pass over the chunk on the device: the text is what bounds this loop)
                         if (g_cover) add_cover_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_depth) add_depth_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
+                        if (g_links) add_links_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_pileup) add_pileup_chunk(index, c->bases.get(0), c->offsets.data(), n_reads);
                         if (g_seg_file) (void)segments_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off[n_reads]);
                         if (g_rs_file) (void)read_summary_chunk(index, c->bases.get(0), c->offsets.data(), n_reads, c->pair_off.data());
@@ -1536,13 +1550,13 @@ static void write_color_similarity(const string& path, fin_cover* cov, size_t nc
 
 static int search_fmin(int argc, char** argv) {
     int64_t micros_start = cur_time_micros();
-    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "depth-histogram", "depth-bins", "depth-bin-width", "color-depth-histogram", "color-depth-quantiles", "color-similarity", "color-similarity-covered", "compact-colors", "color-sets-out", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "fragments", "fragment-lengths", "fragment-bins", "fragment-bin-width", "ab-fragment-lengths", "ref-paths", "ref-depth", "ref-window", "ref-variants", "no-text"});
+    Opts o = parse(argc, argv, {{"o", "out-file"}, {"i", "index-file"}, {"q", "query-file"}}, {"out-file", "index-file", "query-file", "device", "gpus", "strand-counts", "unitig-counts", "unitig-coverage", "unitig-depth", "min-depth", "pileup", "variants", "pileup-max-mismatch", "min-alt", "min-alt-permille", "segments", "read-summary", "screen", "min-found", "min-permille", "screen-invert", "label-unitigs", "labels", "classify", "label-report", "class-min-found", "class-min-permille", "class-min-margin", "color-refs", "colors-out", "color-coverage", "depth-histogram", "depth-bins", "depth-bin-width", "color-depth-histogram", "color-depth-quantiles", "color-similarity", "color-similarity-covered", "compact-colors", "color-sets-out", "taxonomy", "color-taxa", "taxa", "taxon-report", "taxa-confidence", "taxa-min-found", "pseudoalign", "pseudo-permille", "eqclasses", "color-report", "eq-max-classes", "eqclasses-in", "eqclasses-unaligned", "abundance", "ab-lengths", "ab-max-iters", "ab-tol", "ab-bootstraps", "ab-seed", "assign-weights", "assign-threshold", "assign", "assign-report", "paired", "pair-both", "fragments", "fragment-lengths", "fragment-bins", "fragment-bin-width", "ab-fragment-lengths", "ref-paths", "ref-depth", "ref-window", "ref-variants", "links", "max-links", "links-min-count", "no-text"});
     if (argc == 1 || o.help) { cerr << SEARCH_HELP << endl; exit(1); }
     g_strand_counts = o.has("strand-counts") && o.get("strand-counts") != "0" && o.get("strand-counts") != "false";
     g_no_text = o.has("no-text") && o.get("no-text") != "0" && o.get("no-text") != "false";
     if (o.has("color-similarity-covered") && !o.has("color-similarity")) throw runtime_error("--color-similarity-covered is only legal together with --color-similarity");
-    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity") && !o.has("taxa") && !o.has("taxon-report") && !o.has("depth-histogram") && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles") && !o.has("fragments") && !o.has("fragment-lengths") && !o.has("ref-depth") && !o.has("ref-variants"))
-        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report, --abundance, --depth-histogram, --color-depth-histogram, --color-depth-quantiles, --fragments or --fragment-lengths (the run would have no result)");
+    if (g_no_text && !o.has("unitig-counts") && !o.has("unitig-coverage") && !o.has("unitig-depth") && !o.has("pileup") && !o.has("variants") && !o.has("segments") && !o.has("read-summary") && !o.has("screen") && !o.has("classify") && !o.has("label-report") && !o.has("colors-out") && !o.has("pseudoalign") && !o.has("eqclasses") && !o.has("color-report") && !o.has("abundance") && !o.has("assign-weights") && !o.has("color-coverage") && !o.has("color-similarity") && !o.has("taxa") && !o.has("taxon-report") && !o.has("depth-histogram") && !o.has("color-depth-histogram") && !o.has("color-depth-quantiles") && !o.has("fragments") && !o.has("fragment-lengths") && !o.has("ref-depth") && !o.has("ref-variants") && !o.has("links"))
+        throw runtime_error("--no-text 1 is only legal together with --unitig-counts, --unitig-coverage, --unitig-depth, --pileup, --variants, --segments, --read-summary, --screen, --classify, --label-report, --colors-out, --pseudoalign, --eqclasses, --color-report, --abundance, --depth-histogram, --color-depth-histogram, --color-depth-quantiles, --fragments, --fragment-lengths or --links (the run would have no result)");
     if ((o.has("pseudoalign") || o.has("colors-out")) && !o.has("color-refs")) throw runtime_error("--pseudoalign and --colors-out want colours: --color-refs LIST");
     if ((o.has("eqclasses") || o.has("color-report") || o.has("abundance")) && !o.has("color-refs")) throw runtime_error("--eqclasses, --color-report and --abundance want colours: --color-refs LIST");
     if (o.has("color-coverage") && !o.has("color-refs")) throw runtime_error("--color-coverage wants colours: --color-refs LIST");
@@ -1569,6 +1583,18 @@ static int search_fmin(int argc, char** argv) {
         return (uint32_t)t;
     };
     const uint32_t dh_bins = dh_number("depth-bins", 256, FIN_DEPTH_HIST_MAX_BINS), dh_width = dh_number("depth-bin-width", 1, 0xFFFFFFFFull);
+    // --links FILE [--max-links N] [--links-min-count C]: the numbers are refused before the index is loaded
+    for (const char* name : {"max-links", "links-min-count"})
+        if (o.has(name) && !o.has("links")) throw runtime_error(string("--") + name + " is only legal together with --links");
+    auto links_number = [&](const char* name, unsigned long long dflt, unsigned long long top) -> uint64_t {
+        if (!o.has(name)) return dflt;
+        const string v = o.get(name);
+        size_t used = 0; unsigned long long t = 0;
+        try { t = stoull(v, &used); } catch (...) { used = 0; }
+        if (v.empty() || used != v.size() || v[0] == '-' || t < 1 || t > top) throw runtime_error(string("--") + name + " wants a number from 1 to " + to_string(top));
+        return t;
+    };
+    const uint64_t max_links = links_number("max-links", 1ull << 20, FIN_LINKS_MAX), links_min_count = links_number("links-min-count", 1, ~0ull);
     g_paired = o.has("paired") && o.get("paired") != "0" && o.get("paired") != "false";
     const bool pair_both = o.has("pair-both") && o.get("pair-both") != "0" && o.get("pair-both") != "false";
     if (g_paired && !o.has("color-refs")) throw runtime_error("--paired 1 wants colours: --color-refs LIST (fragments are what --pseudoalign, --eqclasses, --color-report and --abundance then take)");
@@ -1736,6 +1762,8 @@ static int search_fmin(int argc, char** argv) {
     const string cover_file = o.get("unitig-coverage", "");
     if (!cover_file.empty()) check_writable(cover_file);
     const string depth_file = o.get("unitig-depth", "");
+    const string links_file = o.get("links", "");
+    if (o.has("links")) check_writable(links_file);
     if (!depth_file.empty()) check_writable(depth_file);
     const string colcov_file = o.get("color-coverage", "");
     if (!colcov_file.empty()) check_writable(colcov_file);
@@ -1802,6 +1830,7 @@ static int search_fmin(int argc, char** argv) {
     if (!crep_file.empty()) check_writable(crep_file);
     if (!colors_file.empty()) check_writable(colors_file);
     if (!psa_file.empty()) check_writable(psa_file);
+    if (!links_file.empty() && fin_pindex_exists(index_prefix.c_str())) throw runtime_error("--links is not available with a partitioned index");
     cerr << "Loading index..." << endl;
     const int first_dev = stoi(o.get("device", "0"));
     // beside the index load: page-lock the pipeline's buffers (four chunks of 48 MB of bases and of up to 16 bytes of text per k-mer)
@@ -1875,6 +1904,12 @@ static int search_fmin(int argc, char** argv) {
     if (!depth_file.empty() || !colcov_file.empty() || dh_asked || !refdepth_file.empty()) {   // (--ref-depth and the depth histograms share the depth of --unitig-depth / --color-coverage)
         char err[512] = {0};
         if (fin_depth_create(index.handle(), first_dev, &g_depth, err, sizeof err) != FIN_OK) throw runtime_error(err);
+    }
+    struct LinksOwner { ~LinksOwner() { fin_links_free(g_links); g_links = nullptr; } } links_owner;
+    if (!links_file.empty()) {
+        char err[512] = {0};
+        if (index.partitioned()) throw runtime_error("--links is not available with a partitioned index");
+        if (fin_links_create(index.handle(), first_dev, max_links, &g_links, err, sizeof err) != FIN_OK) throw runtime_error(string("--links: ") + err);
     }
     struct PileupOwner { ~PileupOwner() { fin_pileup_free(g_pileup); g_pileup = nullptr; } } pileup_owner;
     if (want_pileup) {
@@ -2246,6 +2281,24 @@ static int search_fmin(int argc, char** argv) {
         ofstream cf(depth_file, ios::binary | ios::trunc);
         cf.write(text.data(), (streamsize)text.size());
         if (!cf) throw runtime_error("Error writing to file: " + depth_file);
+    }
+    if (!links_file.empty()) {   // the links, after the last chunk: filtered, compacted and decoded on the device, in the canonical order
+        char err[512] = {0};
+        uint64_t n = 0, cnt[4] = {0, 0, 0, 0};
+        if (fin_links_download(g_links, links_min_count, nullptr, 0, &n, cnt, err, sizeof err) != FIN_OK) throw runtime_error(string("--links (--max-links ") + to_string(max_links) + "): " + err);
+        vector<fin_link> links((size_t)n + 1);
+        if (fin_links_download(g_links, links_min_count, links.data(), n, &n, cnt, err, sizeof err) != FIN_OK) throw runtime_error(string("--links: ") + err);
+        string text;
+        text.reserve((size_t)n * 40 + 64);
+        for (uint64_t i = 0; i < n; i++) {
+            const fin_link& l = links[(size_t)i];
+            text += to_string(l.u_a); text += '\t'; text += to_string(l.off_a); text += '\t'; text += to_string(l.u_b); text += '\t'; text += to_string(l.off_b); text += '\t';
+            text += to_string(l.count); text += '\n';
+        }
+        text += "#transitions\t" + to_string(cnt[0]) + "\n#links\t" + to_string(cnt[1]) + "\n#self\t" + to_string(cnt[3]) + "\n";
+        ofstream cf(links_file, ios::binary | ios::trunc);
+        cf.write(text.data(), (streamsize)text.size());
+        if (!cf) throw runtime_error("Error writing to file: " + links_file);
     }
     if (!colcov_file.empty()) {   // breadth and depth per reference, after the last chunk: projected on the device, one line per colour
         char err[512] = {0};

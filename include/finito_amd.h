@@ -1136,6 +1136,66 @@ int fin_records_fragments(const fin_read_record* recs, uint64_t n_reads, const i
  * if S0(m) == 0 (n_bins == 1 among it) or that value is below 1, out = (double)ref_len.  One division per reference: reproducible bit for bit. */
 int fin_effective_lengths(const uint64_t* hist, uint32_t n_bins, uint32_t bin_width, const uint64_t* ref_len, uint64_t n, double* out);
 
+/* ---- LINKS: the junctions reads cross, counted on the device ----
+ * Everything above looks inside one unitig at a time.  The index is a de Bruijn graph; this section says which of its edges a sample walked and how often, and
+ * where reads jump in ways the indexed sequences never do: which branch of a bubble the reads take, which unitig follows which, breakpoints and mis-joins.  THE
+ * definition, stated here once; fin_links.hip, fin_links_host.cpp, the Python layer, the CLI and DESIGN.md point here.  Everything is in integers and exact.
+ *  A TRANSITION.  For a read with output slots 0 .. nk-1 (the pairs fin_search_batch delivers for it, whichever kind its record is), slot i >= 1 makes a
+ *   transition when slots i-1 and i are both found (unitig number != -1) and link(i) == 0 by the segment rule (SEGMENTS, above): they are not
+ *   in the same unitig with offsets that differ by exactly +1 or -1.  A step of -1 inside a unitig is straight and no transition; a repeated identical pair
+ *   is one (a self link).  Slot 0 never makes one: the last slot of read r and the first slot of read r + 1 never meet, however they lie in the pair array.  An
+ *   absent slot between two found ones makes none (no gapped links).
+ *  THE PLACE of a found slot (u, off) is g = start(u) + off, the geometry of fin_cover and fin_depth (start(u) = unitigs.ends[u - 1] of FIN_X_ENDS, 0 for u = 0).
+ *   A slot with u >= n_unitigs or g >= fin_index_total_len is OUTSIDE THE INDEX; a transition with such an end is not counted and sets flag bit 1.  Slots that
+ *   make no transition are not looked at.
+ *  THE KEY of a transition with places gA and gB is the UNORDERED pair, key = (uint64)min(gA, gB) << 32 | max(gA, gB).  Merged pairs name a k-mer's place
+ *   whichever strand found it, so a read and its reverse complement give the same keys.
+ *  A LINK is a key with its count: the number of transitions with that key over all reads added.  uint64, exact, independent of the order of reads and adds; adding
+ *   the same run twice doubles every count.  A link is reported as fin_link {u_a, off_a, u_b, off_b, count}: the `a` end is the lower place, and an end is named by
+ *   the unitig whose text holds its place, u = the last unitig with start(u) <= g and off = g - start(u) (for every place a search produces that is the slot's own
+ *   (u, off)).  The canonical order of links is ascending by (g_a, g_b).
+ *  THE ACCUMULATOR, fin_links, is a hash table in HBM beside one replica: cap = max(4, the smallest power of two >= 2 * max_links) slots of 16 bytes {key, count},
+ *   fixed at creation -- it does not grow.  The empty key is all ones (no place is 0xFFFFFFFF: total_len < 2^32).  A key's home slot is fin_link_hash(key) & (cap - 1)
+ *   and a taken slot sends it on to the next one, wrapping (linear probing).  The flag word: bit 0 -- a withheld step was offered, nothing of it is added; bit 1 -- a
+ *   transition with an end outside the index, not counted; bit 2 -- more than max_links distinct links, or no free slot within cap probes (that transition is not
+ *   counted).  fin_links_download refuses while a flag is set, until fin_links_reset.
+ * Out of scope: partitioned indexes (fin_pindex_*), fin_search_batch_multi and sums across the ranks of a job (download per replica and merge the tables: same
+ * keys, counts added), the C++ mirror (FinimizerIndex.hh), transitions across absent slots (gapped links), a direction per link, a table that grows, a sort on
+ * the device. */
+typedef struct fin_link { uint32_t u_a, off_a, u_b, off_b; uint64_t count; } fin_link;   /* 24 bytes */
+typedef struct fin_links fin_links;
+#define FIN_LINKS_MAX (1ull << 28)   /* the largest max_links */
+/* the table's hash, host: x = key; x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31 (in uint64) */
+uint64_t fin_link_hash(uint64_t key);
+/* an empty table for `idx` on `device`.  FIN_ELIMIT: max_links outside 1 .. FIN_LINKS_MAX; FIN_ENODEV: the index has no replica there */
+int fin_links_create(const fin_index* idx, int device, uint64_t max_links, fin_links** out, char* err, size_t errlen);
+/* empties table, counters and flags, on the given stream (one small kernel); does not wait; ordered against the adds as fin_hits_reset is */
+int fin_links_reset(fin_links* l, void* hip_stream);
+/* table += the transitions of the batch's most recent run: one launch on the given stream (fin_links.hip), ordered behind that run; does not wait.
+ * fin_batch_add_depth's ordering and refusal rules: FIN_EINVAL when the batch has not run or batch and accumulator belong to different indexes or devices; FIN_ELIMIT
+ * for a step known to have overrun; records and pairs are read only; a run whose overflow list overran adds nothing and the download reports FIN_ELIMIT until the
+ * reset.  Only the reads the pipeline searched (kind 0) can hold a transition: a kind-1 record is one diagonal of one unitig and a kind-2 read has no found slot. */
+int fin_batch_add_links(fin_batch* b, fin_links* l, void* hip_stream, char* err, size_t errlen);
+/* waits for every add and reset issued so far; then the links with count >= max(min_count, 1) are counted, compacted and turned into fin_link on the device, and
+ * only those 24 bytes each cross to the host, where they are put into the canonical order.  *n_links = how many there are; counters_out[4] = {transitions counted,
+ * distinct links, links kept (= *n_links), self links (distinct links with g_a == g_b)}, the first, second and fourth over the whole table whatever min_count is.
+ * links_out NULL: only the numbers.  Otherwise links_out[cap_out]; FIN_ELIMIT when cap_out < *n_links (which is still true).  FIN_ELIMIT after flag bit 0 or 2,
+ * FIN_EINVAL "outside the index" after bit 1, each until the reset.  n_links must not be NULL; counters_out may be.  The accumulator is not changed. */
+int fin_links_download(fin_links* l, uint64_t min_count, fin_link* links_out, uint64_t cap_out, uint64_t* n_links, uint64_t counters_out[4], char* err, size_t errlen);
+/* the table in HBM (valid once the adds on their streams have finished): fin_links_capacity slots of {uint64 key, uint64 count}, then uint64 n_distinct */
+void* fin_links_device_table(const fin_links* l);
+uint64_t fin_links_capacity(const fin_links* l);   /* cap; 0 for NULL */
+void fin_links_free(fin_links* l);
+/* fin_search_batch_add_depth's loop with the links as its only product: host buffers in, sub-batches pipelined, each run in text mode 2 where the fast path is on
+ * and added on the device behind its run, nothing downloaded.  No sub-batch cuts a read, so nothing is lost between them. */
+int fin_search_batch_add_links(const fin_index* idx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int strands, fin_links* l, char* err, size_t errlen);
+/* host, no device: the definition above from records + stream, read off every read's expanded slots whichever kind its record is; the same output in the same
+ * order, with fin_links_download's conventions for min_count, links_out, cap_out, n_links and counters_out.  unitig_ends[n_unitigs] as FIN_X_ENDS.  n_threads <= 0:
+ * all cores; the result does not depend on it.  FIN_EINVAL: a transition with an end outside the index, a kind above 2, a stream that is not this record set's,
+ * unitig_ends that descend or end at or above 2^32; FIN_ELIMIT: cap_out < *n_links */
+int fin_records_links(const fin_read_record* recs, uint64_t n_reads, const int32_t* stream_pairs, uint64_t n_stream_pairs, int k, const int64_t* unitig_ends,
+                      uint64_t n_unitigs, uint64_t min_count, fin_link* links_out, uint64_t cap_out, uint64_t* n_links, uint64_t counters_out[4], int n_threads);
+
 /* ---- REFERENCE COORDINATES: depth and variant candidates lifted onto the sequences whose paths are known ----
  * Depth (fin_depth), its histograms and the pileup's candidates (fin_pileup_call) speak in unitig coordinates, an artefact of how the graph was compacted.  A user
  * works with a place in a reference: record 3 of genome 17, position 1 234 567.  A reference record searched as a read gives its walk through the unitig set as
